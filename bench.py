@@ -6,20 +6,28 @@ A "step" is one complete render of the workload: cornellbox.bin, 1024 x 1024, 25
 with the fused HIP path, rank 0 gathers the stripes (RCCL over xGMI) and assembles the image.
 The image is fixed as N grows: "scaling": "strong".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started WITHOUT a torch.distributed launcher (no RANK in the environment) and with --gpus N > 1,
 this process starts the N ranks itself -- N fresh interpreters, created before torch or the HIP
 runtime is loaded here -- relays rank 0's JSON line and exits with the worst rank's code.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (pt_trace_kernel, timed with
-HIP events on its own stream inside the timed region); `cpu_baseline` times the CPU oracle
-("port": this repo's restatement of the reference kernel -- the reference has no CPU executor)
-on a bounded sample of the same workload on rank 0's host cores, at N=1 only.  `extra.configs`
-(N=1 only) carries the other single-GPU BASELINE configurations, timed in the same process
-after the headline region: configs[1] (512^2 x 64 spp, depth 2) and configs[4]'s scene
-(10^6-triangle soup, 1024^2 x 256 spp, through the LBVH).
+Rank 0 prints ONE JSON line.  A plain run does only what the headline figure needs: set-up, W
+warm-up steps, K timed steps, the outputs (--dump-outputs) and the line.  --full adds the rest:
+`kernels` and `roofline` are for the dominant kernel (pt_trace_kernel, timed with HIP events on
+its own stream inside the timed region); `cpu_baseline` times the CPU oracle ("port": this
+repo's restatement of the reference kernel -- the reference has no CPU executor) on a bounded
+sample of the same workload on rank 0's host cores, at N=1 only.  `extra.configs` (N=1 only)
+carries the other single-GPU BASELINE configurations, timed in the same process after the
+headline region: configs[1] (512^2 x 64 spp, depth 2) and configs[4]'s scene (10^6-triangle
+soup, 1024^2 x 256 spp, through the LBVH).
+
+--dump-outputs DIR writes, on rank 0, the image the last timed step assembled: DIR/image.npy,
+float32 [height, width, 4].  An image larger than DUMP_LIMIT_BYTES is written as a fixed, seeded
+sample of its pixels instead (image_sample.npy [n, 4] and their flat pixel indices,
+image_sample_pixels.npy, float64).  The workload's inputs are fixed by the arguments: two runs
+with the same arguments render the same image.
 """
 from __future__ import annotations
 
@@ -145,8 +153,13 @@ def parse_args(argv=None):
     ap.add_argument("--depth", type=int, default=None)
     ap.add_argument("--stripe-rows", type=int, default=4,
                     help="rows per image stripe of the N-rank split (4: the ranks' shares of configs[2] are equal to 1 %%; 16: 2 %%)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the configs[1] / configs[3] / configs[4] legs of extra.configs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel times and rooflines (HIP events in the timed region; "
+                         "the soup's tallied render), the CPU baseline and the other BASELINE configurations (extra.configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the image of the last one (rank 0) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline")
+    ap.add_argument("--no-extra-configs", action="store_true", help="(--full) skip the configs[1] / configs[3] / configs[4] legs of extra.configs")
     ap.add_argument("--quad-filter", type=int, default=0, help="PT_OPT_QUAD_FILTER (A/B timing): 0 strongest, 1 none, 4 packed")
     ap.add_argument("--accel", type=int, default=0, help="PT_OPT_ACCEL: 0 auto (LBVH from 512 triangles), 1 brute force, 2 LBVH")
     ap.add_argument("--soup", type=int, default=None, help="render the synthetic N-triangle soup of BASELINE configs[4] (Cornell box + "
@@ -175,6 +188,8 @@ def parse_args(argv=None):
     args.soup = soup if args.soup is None else args.soup
     args.steps = steps if args.steps is None else args.steps
     args.warmup = warm if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return args
 
 
@@ -254,6 +269,25 @@ def time_render(img, fence, steps, warmup, spp, depth):
         img.gather()
     fence()
     return time.perf_counter() - t0
+
+
+DUMP_LIMIT_BYTES = 48 << 20      # --dump-outputs: an image up to this size is written whole (configs[2]: 16 MiB)
+DUMP_SAMPLE_PIXELS = 1 << 20     # ... a larger one as this many pixels drawn with a fixed seed (16 MiB + 8 MiB of indices)
+
+
+def dump_outputs(out_dir, image):
+    """Write the last timed step's image (host float32 [H, W, 4]) under out_dir; see the module docstring."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    if image.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), image)
+        return
+    flat = image.reshape(-1, 4)
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), flat[idx])
+    np.save(os.path.join(out_dir, "image_sample_pixels.npy"), idx.astype(np.float64))
 
 
 def bvh_tallies(dev, lib, shim, tris, mats, W, H, depth):
@@ -427,8 +461,9 @@ def main():
     run_steps(args.warmup)
     fence()
     img.reset_stats()
-    shim.check(lib.pt_profile_enable(dev._h, 1))
-    shim.check(lib.pt_profile_reset(dev._h))
+    if args.full:
+        shim.check(lib.pt_profile_enable(dev._h, 1))
+        shim.check(lib.pt_profile_reset(dev._h))
     fence()
     t0 = time.perf_counter()
     run_steps(args.steps)
@@ -450,14 +485,18 @@ def main():
         if not rehearsal:
             assert len(set(devices_seen)) == world, "ranks share a device: %r" % (devices_seen,)
 
-    # per-launch duration of the dominant kernel on this rank, and its work counters
+    # per-launch duration of the dominant kernel on this rank (--full), and its work counters
     tot_ms, launches = ctypes.c_double(), ctypes.c_uint64()
-    shim.check(lib.pt_profile_query(dev._h, shim.PT_PROF_TRACE, ctypes.byref(tot_ms), ctypes.byref(launches)))
     fold_ms, fold_n = ctypes.c_double(), ctypes.c_uint64()
-    shim.check(lib.pt_profile_query(dev._h, shim.PT_PROF_FOLD, ctypes.byref(fold_ms), ctypes.byref(fold_n)))
     union_ms = ctypes.c_double()
-    shim.check(lib.pt_profile_query_union(dev._h, shim.PT_PROF_TRACE, ctypes.byref(union_ms)))
-    shim.check(lib.pt_profile_enable(dev._h, 0))
+    if args.full:
+        shim.check(lib.pt_profile_query(dev._h, shim.PT_PROF_TRACE, ctypes.byref(tot_ms), ctypes.byref(launches)))
+        shim.check(lib.pt_profile_query(dev._h, shim.PT_PROF_FOLD, ctypes.byref(fold_ms), ctypes.byref(fold_n)))
+        shim.check(lib.pt_profile_query_union(dev._h, shim.PT_PROF_TRACE, ctypes.byref(union_ms)))
+        shim.check(lib.pt_profile_enable(dev._h, 0))
+    if args.dump_outputs and rank == 0:
+        # the image the last timed step assembled (fence() above has waited for it)
+        dump_outputs(args.dump_outputs, img.image.cpu().numpy())
     st = img.read_stats()
     counters = torch.tensor([st["samples"], st["rays"]], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
     if world > 1:
@@ -488,79 +527,81 @@ def main():
         out["config"]["workspace_bytes"] = int(dev.getWorkspaceMemory())
         if rehearsal:
             out["rehearsal"] = "%d ranks share %d device(s), gloo gather through the host: code-path check, NOT a scaling measurement" % (world, ndev)
-        n_launch = max(int(launches.value), 1)
-        avg_ms = tot_ms.value / n_launch
-        rank_samples = st["samples"] / n_launch
-        rank_rays = st["rays"] / n_launch
-        out["kernels"] = {"pt_trace_kernel_ms_total": tot_ms.value, "pt_trace_kernel_launches": n_launch,
-                          "pt_trace_kernel_ms_union": union_ms.value,
-                          "pt_fold_kernel_ms_total": fold_ms.value, "pt_fold_kernel_launches": int(fold_n.value),
-                          "note": "total = sum of the launches' [start, stop] durations (what rocprofv3 --stats averages); union = time during which at "
-                                  "least one trace launch was executing: with two render lanes launch c+1 starts while launch c drains, so the sum "
-                                  "counts that overlap twice"}
-        cpu = None
         if args.soup:
             out["metric"] = "Msamples/sec (pixels x spp / s), %d-triangle soup %dx%d" % (len(tris), W, H)
             out["config"]["workload"] = ("BASELINE configs[4]: " if args.named and args.config == 4 else "") + \
                 "soup of %d triangles (BASELINE configs[4] generator) %dx%d, %d spp, depth %d, accel %d" % (len(tris), W, H, spp, depth, args.accel)
-            if args.accel != 1 and world == 1:
-                tally = bvh_tallies(dev, lib, shim, tris, mats, W, H, depth)
-                out["roofline"], out["roofline_valu"] = soup_roofline(tally, rank_rays, rank_samples, avg_ms)
+        cpu = None
+        if args.full:
+            n_launch = max(int(launches.value), 1)
+            avg_ms = tot_ms.value / n_launch
+            rank_samples = st["samples"] / n_launch
+            rank_rays = st["rays"] / n_launch
+            out["kernels"] = {"pt_trace_kernel_ms_total": tot_ms.value, "pt_trace_kernel_launches": n_launch,
+                              "pt_trace_kernel_ms_union": union_ms.value,
+                              "pt_fold_kernel_ms_total": fold_ms.value, "pt_fold_kernel_launches": int(fold_n.value),
+                              "note": "total = sum of the launches' [start, stop] durations (what rocprofv3 --stats averages); union = time during which at "
+                                      "least one trace launch was executing: with two render lanes launch c+1 starts while launch c drains, so the sum "
+                                      "counts that overlap twice"}
+            if args.soup:
+                if args.accel != 1 and world == 1:
+                    tally = bvh_tallies(dev, lib, shim, tris, mats, W, H, depth)
+                    out["roofline"], out["roofline_valu"] = soup_roofline(tally, rank_rays, rank_samples, avg_ms)
+                else:
+                    out["roofline"] = None
             else:
-                out["roofline"] = None
-        else:
-            tallies = None
-            if world == 1 and not args.no_cpu_baseline:
-                try:
-                    cpu, tallies = cpu_baseline(tris, mats, depth)
-                except Exception as e:  # noqa: BLE001 -- the GPU measurement stands; the line says what happened to the CPU leg
-                    cpu, tallies = {"error": "%s: %s" % (type(e).__name__, e)}, None
-            # roofline of pt_trace_kernel on rank 0: algorithmic work of ONE launch / its mean duration
-            if tallies is not None:
-                fpr = flops_per_ray_from_tallies(tallies)
-                basis = "outcome-weighted (SURVEY S8d) from the cpu_baseline sample's tallies"
-            else:
-                # no CPU leg in this run (N > 1 or --no-cpu-baseline): outcome mix of the committed golden
-                # tallies (tests/golden/work_counters.json, oracle, same scene and depth cap 16)
-                try:
-                    with open(os.path.join(ROOT, "tests", "golden", "work_counters.json")) as f:
-                        fpr = flops_per_ray_from_tallies(json.load(f)["cornell_64x64_f8_d16"])
-                    basis = "outcome-weighted (SURVEY S8d) from tests/golden/work_counters.json (cornell_64x64_f8_d16)"
-                except (OSError, KeyError, ValueError):
-                    fpr = 36 * 52.0 + 130.0
-                    basis = "fallback tri_tests x 52 + 130 shading"
-            flops = rank_samples * (F_GEN + F_ACC) + rank_rays * fpr
-            tfl = flops / (avg_ms * 1e-3) / 1e12
-            pmc = pmc_traffic()
-            tr_traffic = fo_traffic = None
-            if pmc is not None:
-                tr_traffic = pmc["pt_trace_kernel"]["hbm_bytes_per_sample"] * rank_samples
-                fo_traffic = pmc["pt_fold_kernel"]["hbm_bytes_per_sample"] * rank_samples
-            out["roofline"] = {
-                "bound": "valu", "achieved": tfl, "peak": PEAK_FP32_VALU_TFLOPS, "unit": "TFLOP/s", "frac": tfl / PEAK_FP32_VALU_TFLOPS,
-                "traffic": tr_traffic, "kernel": "pt_trace_kernel", "avg_launch_ms": avg_ms, "launches": n_launch,
-                "algorithmic_flops_per_launch": flops, "flops_per_ray": fpr, "flops_basis": basis,
-                "traffic_basis": (pmc["file"] + ": measured HBM bytes/sample x samples of this launch") if pmc else None,
-                "from_committed_profile": bool(pmc), "profile_head": (pmc or {}).get("head"),
-                # with two render lanes consecutive launches overlap (launch c+1 becomes resident while launch c drains): `achieved` and
-                # `frac` divide by the launches' own [start, stop] durations -- what rocprofv3 --stats averages -- which count the
-                # overlap twice; the *_exclusive pair divides by the time during which at least one launch was executing
-                "avg_launch_ms_exclusive": union_ms.value / n_launch,
-                "achieved_exclusive": flops / (union_ms.value / n_launch * 1e-3) / 1e12 if union_ms.value > 0 else None,
-                "frac_exclusive": flops / (union_ms.value / n_launch * 1e-3) / 1e12 / PEAK_FP32_VALU_TFLOPS if union_ms.value > 0 else None,
-                "note": "FP32 vector-ALU bound, no MFMA (no dense contraction); the f32 MFMA peak equals the VALU peak on gfx950",
-            }
-            # the 32 B/sample of the reference are moved by trace + fold + framebuffer together: over the step
-            gbs = (W * H * spp) * BYTES_PER_SAMPLE / (step_ms * 1e-3) / 1e9
-            out["roofline_hbm"] = {"bound": "hbm", "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS,
-                                   "traffic": (tr_traffic + fo_traffic) if pmc else None,
-                                   "algorithmic_bytes_per_sample": BYTES_PER_SAMPLE,
-                                   "note": "reference semantics: 16 B read + 16 B write of the pixel per sample, over the whole "
-                                           "step (all ranks); scene is 3.4 KB; traffic = trace (radiance stores) + fold "
-                                           "(radiance reads) kernels of rank 0"}
-        if world == 1 and not args.soup and not args.no_extra_configs:
-            # (the extra legs never cost the headline line: a failure in one of them is recorded in its place)
-            out["extra"] = {"configs": extra_configs(dev, lib, shim, scene, adl, fence, args)}
+                tallies = None
+                if world == 1 and not args.no_cpu_baseline:
+                    try:
+                        cpu, tallies = cpu_baseline(tris, mats, depth)
+                    except Exception as e:  # noqa: BLE001 -- the GPU measurement stands; the line says what happened to the CPU leg
+                        cpu, tallies = {"error": "%s: %s" % (type(e).__name__, e)}, None
+                # roofline of pt_trace_kernel on rank 0: algorithmic work of ONE launch / its mean duration
+                if tallies is not None:
+                    fpr = flops_per_ray_from_tallies(tallies)
+                    basis = "outcome-weighted (SURVEY S8d) from the cpu_baseline sample's tallies"
+                else:
+                    # no CPU leg in this run (N > 1 or --no-cpu-baseline): outcome mix of the committed golden
+                    # tallies (tests/golden/work_counters.json, oracle, same scene and depth cap 16)
+                    try:
+                        with open(os.path.join(ROOT, "tests", "golden", "work_counters.json")) as f:
+                            fpr = flops_per_ray_from_tallies(json.load(f)["cornell_64x64_f8_d16"])
+                        basis = "outcome-weighted (SURVEY S8d) from tests/golden/work_counters.json (cornell_64x64_f8_d16)"
+                    except (OSError, KeyError, ValueError):
+                        fpr = 36 * 52.0 + 130.0
+                        basis = "fallback tri_tests x 52 + 130 shading"
+                flops = rank_samples * (F_GEN + F_ACC) + rank_rays * fpr
+                tfl = flops / (avg_ms * 1e-3) / 1e12
+                pmc = pmc_traffic()
+                tr_traffic = fo_traffic = None
+                if pmc is not None:
+                    tr_traffic = pmc["pt_trace_kernel"]["hbm_bytes_per_sample"] * rank_samples
+                    fo_traffic = pmc["pt_fold_kernel"]["hbm_bytes_per_sample"] * rank_samples
+                out["roofline"] = {
+                    "bound": "valu", "achieved": tfl, "peak": PEAK_FP32_VALU_TFLOPS, "unit": "TFLOP/s", "frac": tfl / PEAK_FP32_VALU_TFLOPS,
+                    "traffic": tr_traffic, "kernel": "pt_trace_kernel", "avg_launch_ms": avg_ms, "launches": n_launch,
+                    "algorithmic_flops_per_launch": flops, "flops_per_ray": fpr, "flops_basis": basis,
+                    "traffic_basis": (pmc["file"] + ": measured HBM bytes/sample x samples of this launch") if pmc else None,
+                    "from_committed_profile": bool(pmc), "profile_head": (pmc or {}).get("head"),
+                    # with two render lanes consecutive launches overlap (launch c+1 becomes resident while launch c drains): `achieved` and
+                    # `frac` divide by the launches' own [start, stop] durations -- what rocprofv3 --stats averages -- which count the
+                    # overlap twice; the *_exclusive pair divides by the time during which at least one launch was executing
+                    "avg_launch_ms_exclusive": union_ms.value / n_launch,
+                    "achieved_exclusive": flops / (union_ms.value / n_launch * 1e-3) / 1e12 if union_ms.value > 0 else None,
+                    "frac_exclusive": flops / (union_ms.value / n_launch * 1e-3) / 1e12 / PEAK_FP32_VALU_TFLOPS if union_ms.value > 0 else None,
+                    "note": "FP32 vector-ALU bound, no MFMA (no dense contraction); the f32 MFMA peak equals the VALU peak on gfx950",
+                }
+                # the 32 B/sample of the reference are moved by trace + fold + framebuffer together: over the step
+                gbs = (W * H * spp) * BYTES_PER_SAMPLE / (step_ms * 1e-3) / 1e9
+                out["roofline_hbm"] = {"bound": "hbm", "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS,
+                                       "traffic": (tr_traffic + fo_traffic) if pmc else None,
+                                       "algorithmic_bytes_per_sample": BYTES_PER_SAMPLE,
+                                       "note": "reference semantics: 16 B read + 16 B write of the pixel per sample, over the whole "
+                                               "step (all ranks); scene is 3.4 KB; traffic = trace (radiance stores) + fold "
+                                               "(radiance reads) kernels of rank 0"}
+            if world == 1 and not args.soup and not args.no_extra_configs:
+                # (the extra legs never cost the headline line: a failure in one of them is recorded in its place)
+                out["extra"] = {"configs": extra_configs(dev, lib, shim, scene, adl, fence, args)}
         if cpu is not None:
             out["cpu_baseline"] = cpu
             if "value" in cpu:

@@ -139,6 +139,38 @@ def test_bench_names_the_baseline_workloads():
     assert a.soup == 5000 and not a.named
 
 
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """A plain bench.py run measures the headline only (--full adds the rest); --steps is the number of timed steps; --dump-outputs
+    writes the last step's image whole, or a fixed seeded sample of its pixels when it is larger than the limit."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+    img = np.random.default_rng(1).random((24, 40, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), img)
+    got = np.load(tmp_path / "whole" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+
+    bench.DUMP_LIMIT_BYTES, bench.DUMP_SAMPLE_PIXELS = 1024, 50
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), img)
+    s = np.load(tmp_path / "s1" / "image_sample.npy")
+    idx = np.load(tmp_path / "s1" / "image_sample_pixels.npy")
+    assert s.dtype == np.float32 and s.shape == (50, 4) and idx.dtype == np.float64
+    assert np.array_equal(s, img.reshape(-1, 4)[idx.astype(np.int64)]) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "image_sample_pixels.npy"))   # the same pixels every run
+    assert not (tmp_path / "s1" / "image.npy").exists()
+
+
 def test_bench_stops_all_ranks_when_one_fails():
     """spawn_ranks used to wait for rank 0 alone.  Without a GPU every rank exits at once with an error; the parent
     must come back with a non-zero code in seconds, not sit in a rendezvous."""

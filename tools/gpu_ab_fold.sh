@@ -3,7 +3,7 @@
 # lane's trace launch reads long), trace / fold totals per step from the bench's HIP events
 set -o pipefail
 for lib in libptshim_old.so libptshim.so libptshim_old.so libptshim.so; do
-  PT_SHIM_LIB=$(pwd)/oclpathtracer_amd/$lib timeout -k 10 200 python bench.py --steps 10 --warmup 3 --lanes 1 --no-cpu-baseline --no-extra-configs > /tmp/ab_fold.json || exit 1
+  PT_SHIM_LIB=$(pwd)/oclpathtracer_amd/$lib timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --lanes 1 --no-cpu-baseline --no-extra-configs > /tmp/ab_fold.json || exit 1
   python3 - "$lib" <<'PY'
 import json, sys
 for l in open("/tmp/ab_fold.json"):
