@@ -319,6 +319,35 @@ int pt_render_frames(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materia
                      pt_buffer_t stats /* may be NULL; PT_STAT_WORDS uint64, accumulated */,
                      pt_event_t ev);
 
+/* ---- the camera --------------------------------------------------------------------------
+ * The reference keeps its camera in the kernel source: GenerateColors.cl:263-269 declares fov, eye, center and up as
+ * literals inside generateRay, and a user moves the camera by editing those lines (Adl compiles the .cl at run time).  The
+ * kernels here are compiled ahead of time, so the same four values are passed instead; no Adl entry point has a counterpart.
+ * The derived values -- viewDir, holDir, upDir (:270-272) and angle = tan(fov / 2) (:268) -- are computed once per render
+ * on the host, in binary32 with the reference's normalize / cross, in its order; the per-ray expression
+ * (:278-287) is the reference's, unchanged. */
+typedef struct pt_camera {
+    float eye[3];        /* GenerateColors.cl:265 (0, 2.75, 4) */
+    float center[3];     /* :266, the point looked at (eye + (0, 0, -1)) */
+    float up[3];         /* :267 (0, 1, 0) */
+    float fov_y_deg;     /* vertical field of view in degrees, (0, 180) (:263: 60) */
+    int32_t reserved[6]; /* must be 0 */
+} pt_camera;             /* 64 bytes */
+
+/* the reference's camera (:263-267) */
+void pt_camera_reference(pt_camera* out);
+/* Host only, no device: validate cam and return its derived values {eye xyz, viewDir xyz, holDir xyz, upDir xyz, angle, 0, 0, 0}.
+ * PT_ERR_INVALID when an input is not finite, fov_y_deg is outside (0, 180), a reserved field is not 0, or a derived value is
+ * not finite (center == eye, up parallel to the view direction) -- cases in which the reference makes NaN rays. */
+int pt_camera_derive(const pt_camera* cam, float out[16]);
+/* pt_render_frames seen from cam (validated as pt_camera_derive does; an invalid camera renders nothing and returns
+ * PT_ERR_INVALID).  cam == NULL is exactly pt_render_frames.  Rendering with another camera than the previous call rewrites
+ * the pass-1 filter's tables on the device, behind the renders in flight; it neither waits for the device nor allocates.
+ * (The Adl-shaped GenerateColors launches -- pt_launch_2d -- keep the reference's camera: its kernel signature has none.) */
+int pt_render_frames_camera(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t framebuffer,
+                            const pt_render_params* params, const pt_camera* cam,
+                            pt_buffer_t stats /* may be NULL */, pt_event_t ev);
+
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.
  * pt_profile_query synchronises the stream and returns the summed duration and launch count

@@ -85,6 +85,14 @@ static_assert(sizeof(PtLeafTri) == 64, "leaf record layout");
 #define PT_LDS_TRI_STRIDE 12    // dwords per triangle record in the LDS copy (p1, e1, e2, 3 pad)
 #define PT_LDS_TRI_MAX 256      // scenes up to this many triangles keep the copy (12 KiB per workgroup)
 
+// the render's camera, derived on the host once per render (pt_camera_derive, include/pt_shim.h; GenerateColors.cl:263-276):
+// eye, the orthonormal-to-rounding basis {viewDir, holDir, upDir} and angle = tan(fov / 2).  The eye is also the ANCHOR of the
+// pass-1 filters (pt_quad3_pass1: K = cross(e2, a - eye), the tame check |o - eye|_inf <= ray_radius)
+struct PtCamera {
+    float eye[3], view[3], hol[3], up[3];
+    float angle;
+};
+
 struct PtTraceParams {
     const PtPrepTriangle* tris;
     const PtRawMaterial* mats;
@@ -131,6 +139,7 @@ struct PtTraceParams {
     uint32_t* carry;              // PT_CARRY_STRIDE_DW dwords per wave of the grid
     uint32_t carry_in_waves;
     uint32_t carry_out;
+    PtCamera cam;                 // read from the kernarg segment where rays are generated and where pass 1 checks a ray (every kernel)
 };
 // a work queue: PT_QUEUE_SHARDS counters and, behind them, the stop word of checkpointed launches (one bit per shard found empty), each on
 // a line of its own, PT_QUEUE_SHARD_WORDS apart (4 KiB + 128 B: whatever the address-to-channel map is, neighbours differ in both fields)
@@ -152,19 +161,37 @@ struct PtFoldParams {
 
 // det_bound_bits: FOUR device words: [0] bit pattern of max_i (|e1|_1 * |e2|_1), [1] number of odd
 // triangles whose e2 is not the exact negation of their predecessor's (0 = the scene is all quads),
-// [2] bit pattern of max |vertex - eye|_inf, [3] number of odd triangles whose p1 is not their
+// [2] non-zero when some vertex coordinate is not finite, [3] number of odd triangles whose p1 is not their
 // predecessor's p3 (0 = every pair is (a,b,c),(c,d,a))
 // [4], [5] (one 64-bit word): checksum of the raw records
-#define PT_PREP_WORDS 6
+// [6..8] per axis the COMPLEMENT of the order key (ptk_order_key) of the smallest vertex coordinate, [9..11] the order key of
+// the largest (both reduced with atomicMax over zeroed words), once per scene upload: the host derives
+// the scene's radius about ANY eye from them without another device read (fl(v - e) is monotone in v)
+#define PT_PREP_WORDS 12
+__host__ __device__ static inline unsigned ptk_order_key(float f)   // finite floats -> unsigned integers in the same order (-0 and +0 apart, harmlessly)
+{
+    unsigned u;
+    __builtin_memcpy(&u, &f, sizeof u);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__host__ __device__ static inline float ptk_order_float(unsigned k)
+{
+    const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float f;
+    __builtin_memcpy(&f, &u, sizeof f);
+    return f;
+}
 hipError_t ptk_prep_triangles(const PtRawTriangle* raw, PtPrepTriangle* out, int ntri, unsigned int* det_bound_bits,
                               hipStream_t s);
 // quad mode 2: writes every odd record's pad0[0] = slack of its shared-u bound (needs the scene
 // diameter bound D from word [2] of the first pass, hence a second tiny launch)
 // p1tab (may be null): quad mode 3's table, PT_P1_STRIDE floats per pair of quads (pt_quad3_pass1)
-hipError_t ptk_prep_quad_margins(PtPrepTriangle* out, int ntri, float diameter, float delta1, float* p1tab, hipStream_t s);
+// anchor: the render's eye (PtCamera), the point K = cross(e2, a - anchor) of the packed table is taken about.  Camera
+// changes rerun this (pt_shim.hip: ensure_anchor); the pairing checks of the first pass are not redone
+hipError_t ptk_prep_quad_margins(PtPrepTriangle* out, int ntri, float diameter, float delta1, float* p1tab, const float anchor[3], hipStream_t s);
 #define PT_P1_STRIDE 24  // floats per quad pair: nx ny nz e2x e2y e2z Kx Ky Kz dhi, each {quad 2p, quad 2p+1}, 4 pad
 static inline size_t ptk_p1tab_floats(int ntri) { return (size_t)((ntri / 2 + 1) / 2) * PT_P1_STRIDE; }
-// fills p.pmask (when not null) for the image geometry of p; needs p.p1tab (quad mode 3)
+// fills p.pmask (when not null) for the image geometry and the camera of p; needs p.p1tab (quad mode 3) made about p.cam.eye
 hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s);
 // det_bounded: every triangle satisfies |e1|_1*|e2|_1 <= PT_DET_BOUND_MAX (short exact reciprocal valid)
 // quads: 0 = independent triangles (pt_tri_pass1); 3 = ntri is even, every pair (2k, 2k+1) is a quad

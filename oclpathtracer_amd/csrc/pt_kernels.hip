@@ -48,14 +48,16 @@ PTK_DEV pt_kargs_p pt_kargs()
     asm volatile("" : "+s"(k));
     return k;
 }
+// the anchor of the pass-1 filters (the render's eye, PtTraceParams::cam), read where a ray is checked -- in EVERY trace kernel,
+// like the camera where rays are made (PT_CAM_K(K->cam)): the LBVH kernel's SGPRs are spent already
+PTK_DEV f3 pt_anchor()
+{
+    const pt_kargs_p K = pt_kargs();
+    return mk3(K->cam.eye[0], K->cam.eye[1], K->cam.eye[2]);
+}
 // LATE (template parameter of the functions below): read the argument where it is used (the table trace kernels), or take
 // it from the by-value copy (the LBVH kernel, which has SGPRs to spare and measured 13 % slower with late reads)
 #define PT_ARG(field) (LATE ? K->field : P.field)
-
-// camera position, GenerateColors.cl:265
-#define PT_EYE_X 0.0f
-#define PT_EYE_Y 2.75f
-#define PT_EYE_Z 4.0f
 
 // ------------------------------------------------------------------------------------------
 // scene preparation
@@ -94,16 +96,27 @@ __global__ void pt_prep_kernel(const PtRawTriangle* __restrict__ raw, PtPrepTria
         // (a,b,c),(c,d,a): this triangle starts at its predecessor's third vertex (pt_quad2_pass1)
         if (!(p1.x == q3.x && p1.y == q3.y && p1.z == q3.z)) atomicAdd(&det_bound_bits[3], 1u);
     }
-    // scene radius about the camera position (GenerateColors.cl:265), for pt_quad2_pass1's error bound
-    float r = 0.0f;
-    const f3 vs[3] = { p1, p2, p3 };
-    for (int k = 0; k < 3; ++k) {
-        float ax = __builtin_fabsf(vs[k].x - PT_EYE_X), ay = __builtin_fabsf(vs[k].y - PT_EYE_Y), az = __builtin_fabsf(vs[k].z - PT_EYE_Z);
-        r = !(ax <= r) ? ax : r;  // a NaN replaces r and then sticks (every later "<=" is false too)
-        r = !(ay <= r) ? ay : r;
-        r = !(az <= r) ? az : r;
+    // the scene's bounding box, per axis, for the radius about the render's eye (pt_quad2_pass1's error bound; the host
+    // derives it per camera: pt_shim.hip, anchor_radius) and a flag for coordinates that are not finite
+    {
+        const f3 vs[3] = { p1, p2, p3 };
+        bool fin = true;
+        float lo[3], hi[3];
+        for (int a = 0; a < 3; ++a) { lo[a] = hi[a] = a == 0 ? p1.x : a == 1 ? p1.y : p1.z; }
+        for (int k = 0; k < 3; ++k) {
+            const float c[3] = { vs[k].x, vs[k].y, vs[k].z };
+            for (int a = 0; a < 3; ++a) {
+                fin = fin && __builtin_isfinite(c[a]);
+                lo[a] = c[a] < lo[a] ? c[a] : lo[a];
+                hi[a] = c[a] > hi[a] ? c[a] : hi[a];
+            }
+        }
+        if (!fin) atomicOr(&det_bound_bits[2], 1u);
+        for (int a = 0; a < 3; ++a) {
+            atomicMax(&det_bound_bits[6 + a], ~ptk_order_key(lo[a]));
+            atomicMax(&det_bound_bits[9 + a], ptk_order_key(hi[a]));
+        }
     }
-    atomicMax(&det_bound_bits[2], __float_as_uint(r) & 0x7fffffffu);
     // words 4, 5: a 64-bit checksum of the raw records (position-dependent mix per record, summed: order of arrival does not matter).
     // A buffer the caller can write behind the ABI is prepared again for every render (pt_shim.hip); the checksum tells whether that
     // changed anything, i.e. whether the LBVH and the primary-ray masks made from the previous contents still stand.
@@ -141,9 +154,10 @@ __global__ void pt_prep_quad_margins_kernel(PtPrepTriangle* __restrict__ out, in
 // the operands of the packed pass-1 filter, interleaved {quad 2p, quad 2p+1} so that every one is
 // an SGPR pair of a v_pk_fma_f32:
 //   n' = cross(e2, e1) * 1.000002f   (det * c = dir . n')
-//   e2, K = cross(e2, a - eye)       (un = e2 . ((o - eye) x dir) - dir . K)
+//   e2, K = cross(e2, a - anchor)    (un = e2 . ((o - anchor) x dir) - dir . K; anchor = the render's eye)
 //   dhi = delta3 + deltaD * c + deltaP (slack of the outer bound; -1 for the padding quad)
-__global__ void pt_prep_p1tab_kernel(const PtPrepTriangle* __restrict__ tris, int ntri, float diameter, float* __restrict__ tab)
+__global__ void pt_prep_p1tab_kernel(const PtPrepTriangle* __restrict__ tris, int ntri, float diameter, float* __restrict__ tab,
+                                     float ax, float ay, float az)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     const int nquads = ntri / 2;
@@ -157,7 +171,7 @@ __global__ void pt_prep_p1tab_kernel(const PtPrepTriangle* __restrict__ tris, in
         if (q < nquads) {
             const PtPrepTriangle a = tris[2 * q], b = tris[2 * q + 1];
             const f3 e2 = mk3(a.e2[0], a.e2[1], a.e2[2]);
-            const f3 ac = mk3(a.p1[0] - PT_EYE_X, a.p1[1] - PT_EYE_Y, a.p1[2] - PT_EYE_Z);
+            const f3 ac = mk3(a.p1[0] - ax, a.p1[1] - ay, a.p1[2] - az);
             const f3 K = cross3(e2, ac);
             v[0] = a.n[0] * 1.000002f; v[1] = a.n[1] * 1.000002f; v[2] = a.n[2] * 1.000002f;
             v[3] = e2.x; v[4] = e2.y; v[5] = e2.z;
@@ -175,18 +189,24 @@ __global__ void pt_prep_p1tab_kernel(const PtPrepTriangle* __restrict__ tris, in
 // the camera ray through image-plane position (x, y), in pixels (GenerateColors.cl:265-287 after the jitter).
 // inv_w = 1.0f / (float)W, inv_h = 1.0f / (float)H, aspect = (float)W / (float)H are IEEE quotients of image constants:
 // computed once on the host (PtTraceParams), the same bits as :266-267 evaluated per work-item.
-// The camera basis of :270-276 is a constant of the reference (eye, center = eye + (0,0,-1), up = (0,1,0)); evaluated
-// with PTSPEC's normalize / cross it is exactly
-//     viewDir = (+0, +0, -1)     holDir = normalize(cross(viewDir, up)) = (1, -0, +0)     upDir = normalize(cross(holDir, viewDir)) = (+0, 1, +0)
-// (every length is exactly 1; the signed zeros are those of the fma forms).  Using the constants keeps nine values out of
-// registers for the kernel's lifetime; the expression below is unchanged, so the results are too.
-PTK_DEV void pt_camera_ray(float x, float y, float inv_w, float inv_h, float aspect, f3& org, f3& dir_out)
+// The camera (eye, and the basis of :270-276 with angle = tan(fov / 2) of :268) is the render's, derived ONCE per render on
+// the host with PTSPEC's normalize / cross (pt_camera_derive, pt_shim.hip): the same bits as :270-276 evaluated per
+// work-item.  For the reference's camera (eye (0, 2.75, 4), center = eye + (0,0,-1), up = (0,1,0), 60 degrees) it is exactly
+//     viewDir = (+0, +0, -1)     holDir = (1, -0, +0)     upDir = (+0, 1, +0)     angle = 0x1.279a74p-1f
+// (every length is exactly 1; the signed zeros are those of the fma forms).  The per-ray expression below is the reference's,
+// unchanged.  Callers read the camera from the kernarg segment where rays are made (PT_CAM_K), so that its thirteen values
+// occupy no registers for the kernel's lifetime.
+struct PtCam { f3 eye, view, hol, up; float angle; };
+#define PT_CAM_K(c) PtCam{ mk3((c).eye[0], (c).eye[1], (c).eye[2]), mk3((c).view[0], (c).view[1], (c).view[2]), \
+                           mk3((c).hol[0], (c).hol[1], (c).hol[2]), mk3((c).up[0], (c).up[1], (c).up[2]), (c).angle }
+
+PTK_DEV void pt_camera_ray(float x, float y, float inv_w, float inv_h, float aspect, const PtCam& c, f3& org, f3& dir_out)
 {
-    const float angle = PTK_TAN_HALF_FOV;
-    const f3 eye = mk3(PT_EYE_X, PT_EYE_Y, PT_EYE_Z);
-    const f3 viewDir = mk3(0.0f, 0.0f, -1.0f);
-    const f3 holDir = mk3(1.0f, -0.0f, 0.0f);
-    const f3 upDir = mk3(0.0f, 1.0f, 0.0f);
+    const float angle = c.angle;
+    const f3 eye = c.eye;
+    const f3 viewDir = c.view;
+    const f3 holDir = c.hol;
+    const f3 upDir = c.up;
 
     x = (2.0f * ((x + 0.5f) * inv_w) - 1.0f) * angle * aspect;
     y = -(1.0f - 2.0f * ((y + 0.5f) * inv_h)) * angle;
@@ -199,24 +219,30 @@ PTK_DEV void pt_camera_ray(float x, float y, float inv_w, float inv_h, float asp
     dir_out = normalize3(normalize3(sub3(pointAimed, eye)));  // :287 then getRay's own normalize (:75)
 }
 
-PTK_DEV void pt_generate_ray(int xc, int yc, float inv_w, float inv_h, float aspect, uint32_t& seed, f3& org, f3& dir_out)
+PTK_DEV void pt_generate_ray(int xc, int yc, float inv_w, float inv_h, float aspect, const PtCam& c, uint32_t& seed, f3& org, f3& dir_out)
 {
     float x = (float)xc + pt_random_float(seed) - 0.5f;  // :278-279: two draws, x first
     float y = (float)yc + pt_random_float(seed) - 0.5f;
-    pt_camera_ray(x, y, inv_w, inv_h, aspect, org, dir_out);
+    pt_camera_ray(x, y, inv_w, inv_h, aspect, c, org, dir_out);
 }
 
 // ------------------------------------------------------------------------------------------
 // primary-ray candidate masks (quad scenes of up to 64 triangles)
 // ------------------------------------------------------------------------------------------
-// The camera is fixed (eye, view direction: GenerateColors.cl:265-272), so what a pixel's primary rays can hit
-// is a property of the pixel: every frame's ray goes through the pixel's footprint, jittered by less than half
-// a pixel (:278-281).  For a primary ray M = (o - eye) x dir = 0 and pass 1's two forms (pt_quad3_pass1) are
-// LINEAR in the direction: un(d) = -K . d, T(d) = n' . d + dhi.  Over the footprint the direction stays within
-// eps of the centre ray's d_c in every component:
-//     the unnormalised direction moves by at most h = |(angle aspect / W, angle / H)|_2 (hol, up orthonormal),
-//     its length is >= 1, and radial projection onto the unit sphere from outside is 1-Lipschitz;
-//     eps = 1.01 h + 4e-6 also covers the rounding of the reference's own ray set-up (three normalisations).
+// The camera is fixed for a render (eye, basis: PtCamera), so what a pixel's primary rays can hit is a property of the
+// pixel: every frame's ray goes through the pixel's footprint, jittered by less than half a pixel (:278-281).  The packed
+// table is made about the render's eye (K = cross(e2, a - eye)) and a primary ray starts exactly AT the eye (org = eye,
+// bit for bit), so M = (o - eye) x dir = 0 and pass 1's two forms (pt_quad3_pass1) are LINEAR in the direction:
+// un(d) = -K . d, T(d) = n' . d + dhi.  Over the footprint the direction stays within eps of the centre ray's d_c in every
+// component:
+//     the unnormalised direction x hol + my up + view moves by at most |dx hol + dmy up|_2 <= (|dx|^2 + |dmy|^2)^(1/2) (1 + 2e-6)
+//     for dx <= angle aspect / W, dmy <= angle / H: hol and up come out of three float normalisations, so each has unit
+//     length within a few ulp (< 1e-6 relative) and hol . up is a rounding residue of the same size, |cos| < 1e-6 -- the
+//     Gram factor (1 + |cos|)^(1/2) (1 + 1e-6) stays below 1 + 2e-6.  Its length is >= |view| (1 - 1e-6) (view is
+//     orthogonal to hol, up up to the same residues, and |view| = 1 within an ulp), and radial projection onto the unit
+//     sphere from outside the ball of radius 1 - 1e-6 is (1 + 1e-6)-Lipschitz: together a factor below 1 + 4e-6;
+//     eps = 1.01 h + 4e-6 covers it with room to spare (the 1.01 alone is 2 500 times the 4e-6 needed), and its additive
+//     4e-6 covers the rounding of the reference's own ray set-up (three normalisations of a unit-length vector).
 // Hence |un(d) - un(d_c)| <= eps |K|_1 =: rho_u and |T(d) - T(d_c)| <= eps |n'|_1 =: rho_T for every ray of the
 // pixel, and a (ray, quad) pair pass 1 would keep -- |un| <= T, un >= lo (first triangle), un <= hi (second),
 // each evaluated in binary32 within deltaP of the real value -- has |un(d_c)| <= T(d_c) + rho_u + rho_T + 4 deltaP
@@ -231,6 +257,7 @@ struct PtMaskParams {
     int32_t stripe_rows, n_ranks, rank;
     uint32_t npix_local;
     float p1_lo, p1_hi;
+    PtCamera cam;   // the render's (and the anchor of p1tab)
 };
 
 __global__ void pt_primary_mask_kernel(const PtMaskParams P)
@@ -245,9 +272,10 @@ __global__ void pt_primary_mask_kernel(const PtMaskParams P)
         grow = (sl * (unsigned)P.n_ranks + (unsigned)P.rank) * (unsigned)P.stripe_rows + within;
     }
     f3 o, dc;
-    pt_camera_ray((float)x, (float)grow, 1.0f / (float)P.width, 1.0f / (float)P.height, (float)P.width / (float)P.height, o, dc);  // the jitter's midpoint: xi = 0.5
-    const float hx = PTK_TAN_HALF_FOV * ((float)P.width / (float)P.height) / (float)P.width;
-    const float hy = PTK_TAN_HALF_FOV / (float)P.height;
+    const PtCam cam = PT_CAM_K(P.cam);
+    pt_camera_ray((float)x, (float)grow, 1.0f / (float)P.width, 1.0f / (float)P.height, (float)P.width / (float)P.height, cam, o, dc);  // the jitter's midpoint: xi = 0.5
+    const float hx = cam.angle * ((float)P.width / (float)P.height) / (float)P.width;
+    const float hy = cam.angle / (float)P.height;
     const float eps = __builtin_sqrtf(hx * hx + hy * hy) * 1.01f + 4e-6f;
     const float E = -4.0f * P.p1_lo;  // 4 deltaP
     const int nquads = P.ntri / 2;
@@ -646,7 +674,10 @@ PTK_DEV void pt_pass2_finish(const PtPrepTriangle* tris, const f3& o, const f3& 
 // spends 16 single-rate instructions per quad on SGPR operands; here
 //     un  = tvec . (dir x e2) = e2 . ((o - eye) x dir) - dir . K,     K  = e2 x (a - eye)
 //     T   = det * c + dhi     = dir . n' + dhi,                       n' = (e2 x e1) * c
-// with M = (o - eye) x dir computed once per ray: 9 v_pk_fma_f32 give un and T of TWO quads, whose
+// where "eye" is the ANCHOR, any fixed point: the identity holds for every one.  It is the render's eye (PtCamera), so a
+// primary ray (o = eye bit for bit) has M = 0 exactly (pt_primary_mask_kernel), and the radius the bounds below are sized by
+// is the scene's about it (pt_shim.hip: anchor_radius; a camera change rewrites the table and the margins, ensure_anchor).
+// With M = (o - eye) x dir computed once per ray: 9 v_pk_fma_f32 give un and T of TWO quads, whose
 // per-quad constants come interleaved from the table pt_prep_p1tab_kernel wrote.
 // These are other roundings of the same real numbers than the reference's, so BOTH triangles now
 // need slack (same assumptions as mode 2: D bounds every coordinate difference, |dir|^2 <= 1.001,
@@ -706,7 +737,7 @@ PTK_DEV void pt_quad3_pass1(pt_const_f32p t, const PtRay3& r, pt_f2& un, pt_f2& 
 template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
 PTK_DEV unsigned pt_intersect_two_pass(pt_const_f32p T, const PtPrepTriangle* tris, int ntri, const f3& o, const f3& d,
                                        bool alive, float& tmax, float& hu, float& hv, int& hidx,
-                                       float delta1, float ray_radius, pt_const_f32p p1tab, float p1_lo, float p1_hi,
+                                       float delta1, float ray_radius, pt_const_f32p p1tab, float p1_lo, float p1_hi, const f3& anchor,
                                        PtTail tl, unsigned lane,
                                        unsigned long long* vstat = nullptr, unsigned long long* p1_ticks = nullptr)
 {
@@ -715,20 +746,21 @@ PTK_DEV unsigned pt_intersect_two_pass(pt_const_f32p T, const PtPrepTriangle* tr
 #if PT_STAMPS
     unsigned long long ta = 0, tb = 0;
 #endif
-    (void)vstat; (void)p1_ticks; (void)ray_radius; (void)p1tab; (void)p1_lo; (void)p1_hi;
+    (void)vstat; (void)p1_ticks; (void)ray_radius; (void)p1tab; (void)p1_lo; (void)p1_hi; (void)anchor;
     unsigned steps = 0;  // pass-2 iterations of this wave (diagnostics only)
-    // the assumptions of the shared-u error bound (derivation above pt_quad3_pass1), checked for THIS ray
+    // the assumptions of the shared-u error bound (derivation above pt_quad3_pass1), checked for THIS ray; the anchor is the
+    // render's eye, the point the packed table's K was taken about (a primary ray starts exactly there: M = 0)
     bool tame = true;
     PtRay3 r3v;
     if (QUADS == 3 && DET_BOUNDED) {
-        const f3 oc = mk3(o.x - PT_EYE_X, o.y - PT_EYE_Y, o.z - PT_EYE_Z);
+        const f3 oc = mk3(o.x - anchor.x, o.y - anchor.y, o.z - anchor.z);
         const f3 M = cross3(oc, d);
         r3v.dxy = pt_f2{ d.x, d.y }; r3v.dzMx = pt_f2{ d.z, M.x }; r3v.Myz = pt_f2{ M.y, M.z };
     }
     if (QUADS == 3 && DET_BOUNDED) {
         float dd = pt_fma(d.z, d.z, pt_fma(d.y, d.y, d.x * d.x));
-        tame = (dd <= 1.001f) & (__builtin_fabsf(o.x - PT_EYE_X) <= ray_radius) &
-               (__builtin_fabsf(o.y - PT_EYE_Y) <= ray_radius) & (__builtin_fabsf(o.z - PT_EYE_Z) <= ray_radius);
+        tame = (dd <= 1.001f) & (__builtin_fabsf(o.x - anchor.x) <= ray_radius) &
+               (__builtin_fabsf(o.y - anchor.y) <= ray_radius) & (__builtin_fabsf(o.z - anchor.z) <= ray_radius);
     }
     for (int base = 0; base < ntri; base += 32) {
         const int n = ntri - base < 32 ? ntri - base : 32;
@@ -1308,7 +1340,7 @@ PTK_DEV bool pt_start_fresh(const PtTraceParams& P, unsigned lane, PtWaveQueue& 
         const unsigned gid = grow * W + x;
         const int frame = PT_ARG(frame_begin) - (int)PT_ARG(chunk_f0) + (int)q.frame;   // (the render's first frame + q.frame)
         s.seed = gid + pt_hash_u32((uint32_t)frame);                                 // :308
-        pt_generate_ray((int)x, (int)grow, PT_ARG(inv_width), PT_ARG(inv_height), PT_ARG(aspect), s.seed, s.o, s.d);      // :310
+        pt_generate_ray((int)x, (int)grow, PT_ARG(inv_width), PT_ARG(inv_height), PT_ARG(aspect), PT_CAM_K(K->cam), s.seed, s.o, s.d);      // :310
         s.mask = mk3(1.0f, 1.0f, 1.0f);
         s.L = mk3(0.0f, 0.0f, 0.0f);
         s.bounce = 0;
@@ -1424,7 +1456,7 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         else
             p2steps = pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>(T, P.tris, ntri, s.o, s.d, alive, tmax, hu, hv, hidx,
                                                                                           P.quad_delta1, P.ray_radius,
-                                                                                          (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, tl, lane,
+                                                                                          (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, pt_anchor(), tl, lane,
                                                                                           PT_VALIDATE_FILTER && P.stats ? P.stats + 2 : nullptr,
 #if PT_STAMPS
                                                                                           &c_p1
@@ -1586,7 +1618,7 @@ PTK_DEV void pt_regenerate_lanes(const PtTraceParams& P, unsigned lane, PtWaveQu
             const unsigned gid = grow * (unsigned)PT_ARG(width) + x;
             const int frame = PT_ARG(frame_begin) - (int)PT_ARG(chunk_f0) + (int)q.frame;
             s.seed = gid + pt_hash_u32((uint32_t)frame);                                 // :308
-            pt_generate_ray((int)x, (int)grow, PT_ARG(inv_width), PT_ARG(inv_height), PT_ARG(aspect), s.seed, s.o, s.d);      // :310
+            pt_generate_ray((int)x, (int)grow, PT_ARG(inv_width), PT_ARG(inv_height), PT_ARG(aspect), PT_CAM_K(K->cam), s.seed, s.o, s.d);      // :310
             s.mask = mk3(1.0f, 1.0f, 1.0f);
             s.L = mk3(0.0f, 0.0f, 0.0f);
             s.bounce = 0;
@@ -1979,7 +2011,7 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
                     int hp = -1;
                     tl.keys[lane] = ~0ull;
                     pt_intersect_two_pass<DET_BOUNDED, 1, (DET_BOUNDED ? BIGQ : 0)>(bigT, P.bigtab, P.nbig, s.o, s.d, start, L.tmax, L.hu, L.hv, hp,
-                                                                                      P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, tl, lane,
+                                                                                      P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, pt_anchor(), tl, lane,
                                                                                       PT_VALIDATE_FILTER && !TALLY && P.stats ? P.stats + 2 : nullptr);  // (diagnostic build: tools/validate_filter.py)
                     if (start && hp >= 0) L.hidx = P.bigidx[hp];
                 }
@@ -2385,14 +2417,14 @@ hipError_t ptk_prep_triangles(const PtRawTriangle* raw, PtPrepTriangle* out, int
     return hipGetLastError();
 }
 
-hipError_t ptk_prep_quad_margins(PtPrepTriangle* out, int ntri, float diameter, float delta1, float* p1tab, hipStream_t s)
+hipError_t ptk_prep_quad_margins(PtPrepTriangle* out, int ntri, float diameter, float delta1, float* p1tab, const float anchor[3], hipStream_t s)
 {
     if (ntri < 2) return hipSuccess;
     const int pairs = ntri / 2;
     hipLaunchKernelGGL(pt_prep_quad_margins_kernel, dim3((pairs + 255) / 256), dim3(256), 0, s, out, ntri, diameter, delta1);
     if (p1tab) {
         const int qpairs = (pairs + 1) / 2;
-        hipLaunchKernelGGL(pt_prep_p1tab_kernel, dim3((qpairs + 255) / 256), dim3(256), 0, s, out, ntri, diameter, p1tab);
+        hipLaunchKernelGGL(pt_prep_p1tab_kernel, dim3((qpairs + 255) / 256), dim3(256), 0, s, out, ntri, diameter, p1tab, anchor[0], anchor[1], anchor[2]);
     }
     return hipGetLastError();
 }
@@ -2407,6 +2439,7 @@ hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s)
     m.stripe_rows = p.stripe_rows; m.n_ranks = p.n_ranks; m.rank = p.rank;
     m.npix_local = p.npix_local;
     m.p1_lo = p.p1_lo; m.p1_hi = p.p1_hi;
+    m.cam = p.cam;
     hipLaunchKernelGGL(pt_primary_mask_kernel, dim3((p.npix_local + 255u) / 256u), dim3(256), 0, s, m);
     return hipGetLastError();
 }

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -104,8 +105,15 @@ struct pt_device_s {
     int prep_quads;             // 0: independent triangles; 3: every pair (2k, 2k+1) is a quad (a,b,c),(c,d,a),
                                 // finite radius, margins and the packed table prepared
     float prep_delta1, prep_ray_radius;  // quad modes 2, 3 (pt_quad2_pass1)
-    float prep_radius;                   // max |vertex - eye|_inf of the prepared scene (NaN when not finite)
+    bool prep_finite;                    // every vertex coordinate of the prepared scene is finite ...
+    float prep_lo[3], prep_hi[3];        // ... and these are their per-axis extremes: the radius about any eye (anchor_radius)
+    bool prep_pairs;                     // the scene is made of quads (a,b,c),(c,d,a) and det-bounded: mode 3 if the radius allows
+    float prep_anchor[3];                // the eye the margins and the packed table were made about (ensure_anchor) ...
+    bool prep_anchor_valid;              // ... since the scene was last prepared
     int big_quads;                       // the LBVH's table of big triangles: 3 = made of quads, its filter table (big_p1tab) and bounds prepared
+    bool big_pairs;                      // ... made of quads: mode 3 if the radius allows
+    float big_anchor[3];                 // as prep_anchor, for the table of big triangles
+    bool big_anchor_valid;
     float* big_p1tab;
     float big_delta1, big_ray_radius, big_p1_lo, big_p1_hi;
     PtBvh8Node* bvh;             // LBVH of the prepared scene (built on demand: ensure_bvh): its 64-byte records, sized with prep
@@ -149,7 +157,7 @@ struct pt_device_s {
     size_t carry_waves;      // waves each of them holds
     uint2* pmask;            // primary-ray candidate masks of the local pixels (pt_primary_mask_kernel)
     size_t pmask_pixels;
-    struct { uint64_t scene_gen; int32_t g[7]; bool valid; } pmask_key;  // what the masks in hand were made for
+    struct { uint64_t scene_gen; int32_t g[7]; PtCamera cam; bool valid; } pmask_key;  // what the masks in hand were made for
     unsigned int* counters;  // PT_QUEUE_COUNTERS work-queue counters, PT_QUEUE_STRIDE words apart: zero between launches
     bool counters_dirty;     // a failed call may have left one non-zero
     unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
@@ -917,6 +925,88 @@ extern "C" int pt_local_rows(int height, int stripe_rows, int n_ranks, int rank)
     return (int)rows;
 }
 
+// ---- the camera (GenerateColors.cl:263-276) -------------------------------------------------------------------------
+// Derived once per render, here on the host, in binary32 with PTSPEC's cross / normalize (explicit fmaf, no contraction: this
+// translation unit is compiled with -ffp-contract=off) in the reference's order -- the same bits as the reference evaluates
+// per work-item.  The angle is the host libm's double tan of the float half-angle, rounded once to float (for 60 degrees:
+// 0x1.279a74p-1f, the reference's constant); tests/camera_oracle.c uses the same expression and the same libm.
+struct HostV3 { float x, y, z; };
+static HostV3 hv_sub(HostV3 a, HostV3 b) { return { a.x - b.x, a.y - b.y, a.z - b.z }; }
+static HostV3 hv_cross(HostV3 a, HostV3 b)
+{
+    return { fmaf(a.y, b.z, -(a.z * b.y)), fmaf(a.z, b.x, -(a.x * b.z)), fmaf(a.x, b.y, -(a.y * b.x)) };
+}
+static HostV3 hv_normalize(HostV3 a)
+{
+    const float inv = 1.0f / sqrtf(fmaf(a.z, a.z, fmaf(a.y, a.y, a.x * a.x)));
+    return { a.x * inv, a.y * inv, a.z * inv };
+}
+
+static void camera_reference(pt_camera* c)
+{
+    memset(c, 0, sizeof *c);
+    c->eye[0] = 0.0f; c->eye[1] = 2.75f; c->eye[2] = 4.0f;              // :265
+    c->center[0] = 0.0f; c->center[1] = 2.75f; c->center[2] = 3.0f;     // :266 eye + (0, 0, -1)
+    c->up[0] = 0.0f; c->up[1] = 1.0f; c->up[2] = 0.0f;                  // :267
+    c->fov_y_deg = 60.0f;                                               // :263
+}
+
+static int camera_derive(const pt_camera* c, PtCamera* out)
+{
+    for (int i = 0; i < 6; ++i)
+        if (c->reserved[i] != 0) return fail(PT_ERR_INVALID, "camera: reserved fields must be zero");
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(c->eye[i]) || !std::isfinite(c->center[i]) || !std::isfinite(c->up[i]))
+            return fail(PT_ERR_INVALID, "camera: eye, center and up must be finite");
+    if (!(c->fov_y_deg > 0.0f && c->fov_y_deg < 180.0f)) return fail(PT_ERR_INVALID, "camera: fov_y_deg must lie in (0, 180)");
+    const HostV3 eye = { c->eye[0], c->eye[1], c->eye[2] };
+    const HostV3 center = { c->center[0], c->center[1], c->center[2] };
+    const HostV3 up = { c->up[0], c->up[1], c->up[2] };
+    const HostV3 view = hv_normalize(hv_sub(center, eye));   // :270
+    const HostV3 hol = hv_normalize(hv_cross(view, up));     // :271
+    const HostV3 upd = hv_normalize(hv_cross(hol, view));    // :272
+    const float fov = (float)(((double)c->fov_y_deg * M_PI) / 180.0);
+    const float angle = (float)tan((double)(0.5f * fov));
+    const float v[13] = { eye.x, eye.y, eye.z, view.x, view.y, view.z, hol.x, hol.y, hol.z, upd.x, upd.y, upd.z, angle };
+    for (float x : v)
+        if (!std::isfinite(x)) return fail(PT_ERR_INVALID, "camera: degenerate (center == eye, or up parallel to the view direction)");
+    memcpy(out->eye, v, sizeof out->eye);
+    memcpy(out->view, v + 3, sizeof out->view);
+    memcpy(out->hol, v + 6, sizeof out->hol);
+    memcpy(out->up, v + 9, sizeof out->up);
+    out->angle = angle;
+    return PT_OK;
+}
+
+static PtCamera reference_camera()
+{
+    static const PtCamera c = [] {
+        pt_camera rc;
+        camera_reference(&rc);
+        PtCamera r;
+        camera_derive(&rc, &r);
+        return r;
+    }();
+    return c;
+}
+
+extern "C" void pt_camera_reference(pt_camera* out)
+{
+    if (out) camera_reference(out);
+}
+
+extern "C" int pt_camera_derive(const pt_camera* cam, float out[16])
+{
+    if (!cam || !out) return fail(PT_ERR_INVALID, "null argument");
+    PtCamera c;
+    int rc = camera_derive(cam, &c);
+    if (rc) return rc;
+    const float v[16] = { c.eye[0], c.eye[1], c.eye[2], c.view[0], c.view[1], c.view[2], c.hol[0], c.hol[1], c.hol[2],
+                          c.up[0], c.up[1], c.up[2], c.angle, 0.0f, 0.0f, 0.0f };
+    memcpy(out, v, sizeof v);
+    return PT_OK;
+}
+
 static int ensure_prep(pt_device_s* d, const pt_buffer_s* tris, int ntri)
 {
     // wrapped (caller-owned) memory can change behind our back, and so can a buffer whose device pointer has been handed
@@ -953,31 +1043,21 @@ static int ensure_prep(pt_device_s* d, const pt_buffer_s* tris, int ntri)
     unsigned int words[PT_PREP_WORDS] = { 0u, 1u, 0x7fc00000u, 1u };
     HIP_TRY(hipMemcpyAsync(words, d->det_bound_dev, sizeof words, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));  // once per scene upload
-    float bound, radius;
+    float bound;
     memcpy(&bound, &words[0], sizeof bound);
-    memcpy(&radius, &words[2], sizeof radius);
     d->prep_det_bounded = bound <= PT_DET_BOUND_MAX;  // false for NaN / Inf too
-    d->prep_radius = radius;
-    const bool pairs = words[1] == 0u && ntri > 0 && (ntri & 1) == 0;  // every (2k, 2k+1) has e2' == -e2
+    d->prep_finite = words[2] == 0u && ntri > 0;
+    for (int a = 0; a < 3; ++a) {
+        d->prep_lo[a] = ptk_order_float(~words[6 + a]);
+        d->prep_hi[a] = ptk_order_float(words[9 + a]);
+    }
+    // every (2k, 2k+1) has e2' == -e2 and is (a,b,c),(c,d,a): quad mode 3 for every camera about which the scene's radius is
+    // finite and moderate (ensure_anchor: the margins and the packed table are made per anchor, on the device, no host wait)
+    d->prep_pairs = words[1] == 0u && words[3] == 0u && ntri > 0 && (ntri & 1) == 0 && d->prep_det_bounded && d->prep_finite;
     d->prep_quads = 0;
     d->prep_delta1 = 0.0f;
     d->prep_ray_radius = 0.0f;
-    if (pairs && d->prep_det_bounded && words[3] == 0u && radius <= 1.0e15f) {
-        // quad mode 2: secondary rays start 0.01 off a surface (GenerateColors.cl:253), so their
-        // origins stay within ray_radius of the eye; D bounds every coordinate difference between
-        // two points of that box; delta1 = 128 u D^2 (derivation: pt_quad2_pass1)
-        const float ray_radius = radius * 1.001f + 0.05f;
-        const float diameter = 2.0f * ray_radius * 1.001f;
-        const float delta1 = 128.0f * 5.9604645e-8f * diameter * diameter * 1.001f;
-        HIP_TRY(ptk_prep_quad_margins(d->prep, ntri, diameter, delta1, d->p1tab, d->stream));
-        d->prep_quads = 3;
-        d->prep_delta1 = delta1;
-        d->prep_ray_radius = ray_radius;
-        // mode 3 (pt_quad3_pass1): deltaP = 192 u D^2; first triangle un >= -deltaP, second un <= delta1 + deltaP
-        const float deltaP = 192.0f * 5.9604645e-8f * diameter * diameter * 1.001f;
-        d->prep_p1_lo = -deltaP;
-        d->prep_p1_hi = (delta1 + deltaP) * 1.001f;
-    }
+    d->prep_anchor_valid = false;   // the prep kernel has just zeroed the margins
     d->blocks_per_cu = ptk_trace_blocks_per_cu(ntri);  // the LDS footprint follows the scene
     // Memory the caller can write behind the ABI is prepared again for every render; the checksum of the raw records says whether
     // that changed anything -- if not, the LBVH (a radix sort, a build, host waits) and the primary-ray masks still stand
@@ -1033,26 +1113,17 @@ static int ensure_bvh(pt_device_s* d, const pt_buffer_s* tris, int ntri)
     // filter (pt_quad3_pass1) like a quad scene on the brute-force path: same preparation (ensure_prep), on the table.  The
     // filter's error bound is about where RAYS start: anywhere on the scene, so the radius is the whole scene's.
     d->big_quads = 0;
+    d->big_pairs = false;
+    d->big_anchor_valid = false;
 #ifndef PT_EXP_NO_BIGQ  // (A/B builds: the big triangles' search with the plain filter)
-    if (d->nbig >= 2 && (d->nbig & 1) == 0 && d->prep_det_bounded && d->prep_radius <= 1.0e15f) {
+    if (d->nbig >= 2 && (d->nbig & 1) == 0 && d->prep_det_bounded && d->prep_finite) {
         PtRawTriangle* rawbig = reinterpret_cast<PtRawTriangle*>(d->big_p1tab + ptk_p1tab_floats(PT_BVH_BIG_MAX));
         HIP_TRY(ptk_bvh_big_raw((const PtRawTriangle*)tris->dptr, d->bigidx, d->nbig, rawbig, d->stream));
         HIP_TRY(ptk_prep_triangles(rawbig, d->bigtab, d->nbig, d->det_bound_dev, d->stream));  // (rewrites the same records)
         unsigned int words[PT_PREP_WORDS] = { 0u, 1u, 0x7fc00000u, 1u };
         HIP_TRY(hipMemcpyAsync(words, d->det_bound_dev, sizeof words, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(hipStreamSynchronize(d->stream));
-        if (words[1] == 0u && words[3] == 0u) {
-            const float ray_radius = d->prep_radius * 1.001f + 0.05f;
-            const float diameter = 2.0f * ray_radius * 1.001f;
-            const float delta1 = 128.0f * 5.9604645e-8f * diameter * diameter * 1.001f;
-            HIP_TRY(ptk_prep_quad_margins(d->bigtab, d->nbig, diameter, delta1, d->big_p1tab, d->stream));
-            const float deltaP = 192.0f * 5.9604645e-8f * diameter * diameter * 1.001f;
-            d->big_quads = 3;
-            d->big_delta1 = delta1;
-            d->big_ray_radius = ray_radius;
-            d->big_p1_lo = -deltaP;
-            d->big_p1_hi = (delta1 + deltaP) * 1.001f;
-        }
+        d->big_pairs = words[1] == 0u && words[3] == 0u;   // margins and packed table: ensure_anchor, per camera
     }
 #endif
     d->bvh_valid = true;
@@ -1060,10 +1131,73 @@ static int ensure_bvh(pt_device_s* d, const pt_buffer_s* tris, int ntri)
     return PT_OK;
 }
 
+// max |v - eye|_inf over the prepared scene's vertices, from its per-axis extremes: fl(v - e) is monotone in v, so the largest
+// |fl(v - e)| of an axis is reached at its smallest or its largest coordinate -- the same float as a reduction over every
+// vertex.  NaN when a coordinate is not finite.
+static float anchor_radius(const pt_device_s* d, const float eye[3])
+{
+    if (!d->prep_finite) return NAN;
+    float r = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        const float lo = fabsf(d->prep_lo[a] - eye[a]), hi = fabsf(d->prep_hi[a] - eye[a]);
+        r = !(lo <= r) ? lo : r;
+        r = !(hi <= r) ? hi : r;
+    }
+    return r;
+}
+
+// The pass-1 filter of a quad scene (pt_quad3_pass1) is made about an ANCHOR, the render's eye: its error bounds are sized by
+// the scene's radius about it, its packed table holds K = cross(e2, a - eye).  When the eye moves, the margins (pad0 of the
+// prepared records) and the packed table are rewritten by kernels enqueued on the handle's stream, behind the renders in
+// flight (lanes_join: a device-side wait), for the brute-force scene (big = false) or the LBVH's table of big triangles.  The
+// pairing checks of the scene preparation do not depend on the camera and stand; the LBVH is not touched.  The same eye as
+// the table's does nothing at all.
+static int ensure_anchor(pt_device_s* d, const float eye[3], bool big)
+{
+    float* key = big ? d->big_anchor : d->prep_anchor;
+    bool& valid = big ? d->big_anchor_valid : d->prep_anchor_valid;
+    if (valid && memcmp(key, eye, 3 * sizeof(float)) == 0) return PT_OK;
+    const bool pairs = big ? d->big_pairs : d->prep_pairs;
+    const float radius = anchor_radius(d, eye);
+    int& quads = big ? d->big_quads : d->prep_quads;
+    quads = 0;
+    if (pairs && radius <= 1.0e15f) {
+        // quad mode 2: secondary rays start 0.01 off a surface (GenerateColors.cl:253), so their origins stay within ray_radius
+        // of the eye -- checked per ray, a ray outside keeps every triangle; the big triangles' filter is about where RAYS
+        // start: anywhere on the scene, so its radius is the whole scene's too.  D bounds every coordinate difference between
+        // two points of that box; delta1 = 128 u D^2 (derivation: pt_quad2_pass1)
+        const float ray_radius = radius * 1.001f + 0.05f;
+        const float diameter = 2.0f * ray_radius * 1.001f;
+        const float delta1 = 128.0f * 5.9604645e-8f * diameter * diameter * 1.001f;
+        // mode 3 (pt_quad3_pass1): deltaP = 192 u D^2; first triangle un >= -deltaP, second un <= delta1 + deltaP
+        const float deltaP = 192.0f * 5.9604645e-8f * diameter * diameter * 1.001f;
+        int rc = lanes_join(d);   // (a render through the old table may still be running)
+        if (rc) return rc;
+        d->main_dirty = true;
+        if (big) {
+            HIP_TRY(ptk_prep_quad_margins(d->bigtab, d->nbig, diameter, delta1, d->big_p1tab, eye, d->stream));
+            d->big_delta1 = delta1;
+            d->big_ray_radius = ray_radius;
+            d->big_p1_lo = -deltaP;
+            d->big_p1_hi = (delta1 + deltaP) * 1.001f;
+        } else {
+            HIP_TRY(ptk_prep_quad_margins(d->prep, d->prep_ntri, diameter, delta1, d->p1tab, eye, d->stream));
+            d->prep_delta1 = delta1;
+            d->prep_ray_radius = ray_radius;
+            d->prep_p1_lo = -deltaP;
+            d->prep_p1_hi = (delta1 + deltaP) * 1.001f;
+        }
+        quads = 3;
+    }
+    memcpy(key, eye, 3 * sizeof(float));
+    valid = true;
+    return PT_OK;
+}
+
 // one render of at most 32 768 frames: its launches on one lane (pt_device_s).  ev_start / ev_stop: the caller's event, when
 // this part begins / ends the call
-static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_buffer_s* fb, const pt_render_params& rp, uint32_t npix,
-                       pt_buffer_s* stats, pt_event_s* ev_start, pt_event_s* ev_stop)
+static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_buffer_s* fb, const pt_render_params& rp, const PtCamera& cam,
+                       uint32_t npix, pt_buffer_s* stats, pt_event_s* ev_start, pt_event_s* ev_stop)
 {
     int rc;
     // PT_OPT_ACCEL: 0 = BVH for scenes of PT_BVH_AUTO_MIN triangles or more, 1 = brute force, 2 = BVH (needs >= 2 triangles)
@@ -1075,6 +1209,7 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
         return fail(PT_ERR_INVALID, "the LBVH search packs a record index (2 x triangles) in 26 bits: %d triangles are too many", rp.num_triangles);
     if ((rc = ensure_prep(d, tris, rp.num_triangles))) return rc;
     if (use_bvh && (rc = ensure_bvh(d, tris, rp.num_triangles))) return rc;
+    if ((rc = ensure_anchor(d, cam.eye, use_bvh))) return rc;
 
     // ---- the staging ring: whole frames per chunk, as many as a slot holds -------------------------------------------------
     // Steady state allocates nothing: the ring exists from the first render on (pt_device_reserve_staging) and is replaced
@@ -1090,13 +1225,14 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
     const int chunk = (rp.frame_count + nchunks - 1) / nchunks;      // S: equal chunks -- 40 frames through a 16-frame slot go 14, 14, 12
 
     // primary-ray candidate masks: quad scenes of up to 64 triangles on the brute-force path (PT_OPT_PRIMARY_MASKS).  They are a
-    // function of the image geometry and the prepared scene: made when either changes, on the handle's stream, behind the lanes
+    // function of the image geometry, the camera and the prepared scene: made when any changes, on the handle's stream, behind the lanes
     const int quads_sel = (d->opt_quads == 0 || d->opt_quads == 4) ? d->prep_quads : 0;
     const bool use_pmask = d->opt_pmask && quads_sel == 3 && !use_bvh && rp.num_triangles <= 64 && d->prep_det_bounded;
     bool make_pmask = false;
     if (use_pmask) {
         const int32_t g[7] = { rp.width, rp.height, rp.stripe_rows, rp.n_ranks, rp.rank, (int32_t)npix, rp.num_triangles };
-        make_pmask = !d->pmask_key.valid || d->pmask_key.scene_gen != d->scene_gen || memcmp(d->pmask_key.g, g, sizeof g) != 0;
+        make_pmask = !d->pmask_key.valid || d->pmask_key.scene_gen != d->scene_gen || memcmp(d->pmask_key.g, g, sizeof g) != 0 ||
+                     memcmp(&d->pmask_key.cam, &cam, sizeof cam) != 0;
         if (make_pmask) {
             if ((rc = lanes_join(d))) return rc;   // (a render with the old masks may still be running)
             d->main_dirty = true;
@@ -1112,6 +1248,7 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
             }
             d->pmask_key.scene_gen = d->scene_gen;
             memcpy(d->pmask_key.g, g, sizeof g);
+            d->pmask_key.cam = cam;
         }
     }
     if (d->counters_dirty) {   // an earlier call failed between a trace launch and the fold that resets its counter
@@ -1171,6 +1308,7 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
     tp.ring_magic = (uint32_t)(0x100000000ull / (2u * (uint32_t)chunk)) + 1u;
     tp.rad = d->ring;
     tp.rad1 = reinterpret_cast<float*>(reinterpret_cast<char*>(d->ring) + d->ring_slot_bytes);
+    tp.cam = cam;
     if (make_pmask) {
         HIP_TRY(ptk_primary_masks(tp, d->stream));  // (cheap: one thread per pixel)
         d->pmask_key.valid = true;
@@ -1305,7 +1443,7 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
 
 // pixel_count: 0 = all local pixels; otherwise the first pixel_count local pixels (n_ranks must be 1)
 static int render_internal(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_buffer_s* fb,
-                           const pt_render_params& rp, uint32_t pixel_count, pt_buffer_s* stats, pt_event_s* ev)
+                           const pt_render_params& rp, const PtCamera& cam, uint32_t pixel_count, pt_buffer_s* stats, pt_event_s* ev)
 {
     if (!tris || !mats || !fb) return fail(PT_ERR_INVALID, "null buffer handle");
     if (tris->dev != d || mats->dev != d || fb->dev != d || (stats && stats->dev != d))
@@ -1351,7 +1489,7 @@ static int render_internal(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats,
     for (int done = 0; done < rp.frame_count; done += PART) {
         part.frame_begin = rp.frame_begin + done;
         part.frame_count = std::min(PART, rp.frame_count - done);
-        if ((rc = render_part(d, tris, mats, fb, part, npix, stats, done == 0 ? ev : nullptr, done + PART >= rp.frame_count ? ev : nullptr))) return rc;
+        if ((rc = render_part(d, tris, mats, fb, part, cam, npix, stats, done == 0 ? ev : nullptr, done + PART >= rp.frame_count ? ev : nullptr))) return rc;
     }
     fb->version++;
     if (stats) stats->version++;
@@ -1375,17 +1513,25 @@ static int flush_pending(pt_device_s* d)
     rp.stripe_rows = 1;
     rp.n_ranks = 1;
     rp.rank = 0;
-    return render_internal(d, p.tris, p.mats, p.fb, rp, p.pixel_count, nullptr, nullptr);
+    return render_internal(d, p.tris, p.mats, p.fb, rp, reference_camera(), p.pixel_count, nullptr, nullptr);
+}
+
+extern "C" int pt_render_frames_camera(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t framebuffer,
+                                       const pt_render_params* params, const pt_camera* cam, pt_buffer_t stats, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
+    PtCamera c = reference_camera();
+    if (cam && (rc = camera_derive(cam, &c))) return rc;   // (nothing enqueued, nothing submitted)
+    if ((rc = flush_pending(d))) return rc;
+    return render_internal(d, triangles, materials, framebuffer, *params, c, 0, stats, ev);
 }
 
 extern "C" int pt_render_frames(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t framebuffer,
                                 const pt_render_params* params, pt_buffer_t stats, pt_event_t ev)
 {
-    int rc = use_device(d);
-    if (rc) return rc;
-    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
-    if ((rc = flush_pending(d))) return rc;
-    return render_internal(d, triangles, materials, framebuffer, *params, 0, stats, ev);
+    return pt_render_frames_camera(d, triangles, materials, framebuffer, params, nullptr, stats, ev);
 }
 
 static int assemble_check(pt_device_s* d, pt_buffer_s* gathered, pt_buffer_s* image, int width, int height, int stripe_rows, int n_ranks, int slab_rows);
@@ -1593,7 +1739,7 @@ static int launch_generate_colors(pt_device_s* d, const pt_launch_arg* a, int na
         HIP_TRY(hipEventCreate(&e1));
         HIP_TRY(hipEventRecord(e0, d->stream));
     }
-    int rc = render_internal(d, t, m, fb, rp, (uint32_t)npix, nullptr, ev);
+    int rc = render_internal(d, t, m, fb, rp, reference_camera(), (uint32_t)npix, nullptr, ev);   // (the reference's kernel takes no camera)
     if (d->opt_profile) {
         float ms = 0.f;
         if (!rc) rc = lanes_join(d);   // PROFILE_RETURN_TIME: the launch's duration as the handle's stream sees it

@@ -82,11 +82,13 @@ class StripeImage:
     tensor (so the collective moves it with no staging copy) wrapped by the shim."""
 
     def __init__(self, dev: adl.Device, triangles, materials, width: int, height: int, *, world: int = 1, rank: int = 0,
-                 stripe_rows: int = 16, want_stats: bool = False, pipelined: bool = False):
+                 stripe_rows: int = 16, want_stats: bool = False, pipelined: bool = False, camera=None):
         """``pipelined``: two local framebuffers (and, for N > 1, two gather buffers), so that the collective of one render can run
         while the next render is already on the GPU -- and consecutive renders overlap: the next image's first trace launch fills
         the machine while this image's last one runs its paths out (``render`` returns the slot it rendered into, ``gather(slot)``
-        takes it; see ``bench.py``).  Every render must then start at frame 0 or continue its own slot's frames."""
+        takes it; see ``bench.py``).  Every render must then start at frame 0 or continue its own slot's frames.
+        ``camera``: the viewpoint (a :class:`~oclpathtracer_amd.camera.Camera`, None = the reference's); seeds and camera rays use
+        global pixel ids, so the assembled image equals the one-device image for any camera."""
         self.dev, self.world, self.rank = dev, int(world), int(rank)
         self.width, self.height = int(width), int(height)
         self.plan = StripePlan(height, stripe_rows, world)
@@ -101,7 +103,7 @@ class StripeImage:
         self.local = self._locals[0]
         dev.waitStream(torch.cuda.current_stream(self.cuda).cuda_stream)  # the zero fill precedes the first render
         self.renderer = Renderer(dev, triangles, materials, width, height, n_ranks=world, rank=rank,
-                                 stripe_rows=stripe_rows, fb_device_ptr=self.local.data_ptr(), want_stats=want_stats)
+                                 stripe_rows=stripe_rows, fb_device_ptr=self.local.data_ptr(), want_stats=want_stats, camera=camera)
         assert self.renderer.local_rows == self.plan.local_rows(rank)
         self._fbs = [self.renderer.fb]
         for t in self._locals[1:]:
@@ -153,6 +155,10 @@ class StripeImage:
         if self.pipelined:
             self._slot ^= 1
         return slot
+
+    def set_camera(self, camera) -> None:
+        """Move the camera (None: the reference's): accumulation restarts, the next render is frame 0."""
+        self.renderer.set_camera(camera)
 
     def ready(self) -> torch.Tensor:
         """Order torch's current stream after the last render and return the local framebuffer tensor

@@ -16,14 +16,15 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import adl, shim
+from .camera import Camera
 from .render import BOUNCES, Renderer
 
 
 class ProgressiveRenderer:
     def __init__(self, dev: adl.Device, triangles: np.ndarray, materials: np.ndarray, width: int, height: int, *,
-                 frames_per_step: int = 16, max_bounces: int = BOUNCES):
+                 frames_per_step: int = 16, max_bounces: int = BOUNCES, camera: Optional[Camera] = None):
         self.dev = dev
-        self.renderer = Renderer(dev, triangles, materials, width, height)
+        self.renderer = Renderer(dev, triangles, materials, width, height, camera=camera)
         self.width, self.height = int(width), int(height)
         self.frames_per_step, self.max_bounces = int(frames_per_step), int(max_bounces)
         self._lib = shim.load()
@@ -54,6 +55,11 @@ class ProgressiveRenderer:
         shim.check(self._lib.pt_buffer_read(self.renderer.fb._h, self._host[slot], self._bytes, 0, self._events[slot]._h))
         self._frames[slot] = self.renderer.frames_done
         self._steps += 1
+
+    def set_camera(self, camera: Optional[Camera]) -> None:
+        """Move the camera (None: the reference's): accumulation restarts, the next step renders frame 0.  Snapshots
+        already enqueued keep the frames of the old camera."""
+        self.renderer.set_camera(camera)
 
     def latest(self, block: bool = False) -> Optional[Tuple[int, np.ndarray]]:
         """``(frames, image)`` of the newest completed snapshot, ``image`` a (W*H, 4) float32 view of

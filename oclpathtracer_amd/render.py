@@ -15,6 +15,7 @@ from typing import Optional
 import numpy as np
 
 from . import adl, scene, shim
+from .camera import Camera
 
 BOUNCES = 16        # GenerateColors.cl:5
 NUM_TRIANGLES = 36  # GenerateColors.cl:6
@@ -69,13 +70,16 @@ class Renderer:
     ``n_ranks``/``rank``/``stripe_rows`` select the rows this device owns (rows are
     dealt in stripes, round-robin); the local framebuffer holds exactly those rows.  With the
     defaults it is the whole image.  ``fb_device_ptr`` lets the framebuffer live in caller-owned
-    device memory (a torch tensor) so a collective can move it without a copy.
+    device memory (a torch tensor) so a collective can move it without a copy.  ``camera`` (a :class:`Camera`; None =
+    the reference's camera, through ``pt_render_frames`` exactly as before) is the viewpoint (``set_camera``).
     """
 
     def __init__(self, dev: adl.Device, triangles: np.ndarray, materials: np.ndarray, width: int, height: int, *,
                  n_ranks: int = 1, rank: int = 0, stripe_rows: int = 16, fb_device_ptr: Optional[int] = None,
-                 want_stats: bool = False):
+                 want_stats: bool = False, camera: Optional[Camera] = None):
         self.dev = dev
+        self.camera, self._cam = None, None
+        self._set_camera(camera)
         self.width, self.height = int(width), int(height)
         self.n_ranks, self.rank, self.stripe_rows = int(n_ranks), int(rank), int(stripe_rows)
         self.num_triangles, self.num_materials = len(triangles), len(materials)
@@ -108,10 +112,28 @@ class Renderer:
         p.max_bounces = int(max_bounces)
         p.num_triangles, p.num_materials = self.num_triangles, self.num_materials
         p.stripe_rows, p.n_ranks, p.rank = self.stripe_rows, self.n_ranks, self.rank
-        shim.check(shim.load().pt_render_frames(self.dev._h, self.tbuf._h, self.mbuf._h, (fb or self.fb)._h, ctypes.byref(p),
-                                                self.stats._h if self.stats else None,
-                                                sync._h if sync is not None else None))
+        if self._cam is None:
+            shim.check(shim.load().pt_render_frames(self.dev._h, self.tbuf._h, self.mbuf._h, (fb or self.fb)._h, ctypes.byref(p),
+                                                    self.stats._h if self.stats else None,
+                                                    sync._h if sync is not None else None))
+        else:
+            shim.check(shim.load().pt_render_frames_camera(self.dev._h, self.tbuf._h, self.mbuf._h, (fb or self.fb)._h, ctypes.byref(p),
+                                                           ctypes.byref(self._cam), self.stats._h if self.stats else None,
+                                                           sync._h if sync is not None else None))
         self.frames_done = frame_begin + frames
+
+    def _set_camera(self, camera: Optional[Camera]) -> None:
+        if camera is not None and not isinstance(camera, Camera):
+            raise TypeError("camera must be an oclpathtracer_amd.camera.Camera or None")
+        self.camera = camera
+        self._cam = camera.to_struct() if camera is not None else None
+
+    def set_camera(self, camera: Optional[Camera]) -> None:
+        """Render from ``camera`` from now on (None: the reference's).  A moved camera invalidates the running mean
+        (GenerateColors.cl:314-321): accumulation restarts, the next render is frame 0.  Renders already enqueued keep the
+        camera they were enqueued with."""
+        self._set_camera(camera)
+        self.frames_done = 0
 
     def read(self) -> np.ndarray:
         """Local framebuffer as (local_rows*W, 4) float32 (synchronises)."""

@@ -54,6 +54,16 @@ class RenderParams(_c.Structure):
     ]
 
 
+class Camera(_c.Structure):
+    """pt_camera (64 bytes): eye, center, up, vertical field of view in degrees; reserved must be 0."""
+
+    _fields_ = [
+        ("eye", _c.c_float * 3), ("center", _c.c_float * 3), ("up", _c.c_float * 3),
+        ("fov_y_deg", _c.c_float),
+        ("reserved", _c.c_int32 * 6),
+    ]
+
+
 # every symbol include/pt_shim.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "pt_last_error": (_c.c_char_p, []),
@@ -103,6 +113,9 @@ SIGNATURES = {
                                 _c.POINTER(_c.c_float)]),
     "pt_local_rows": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "pt_render_frames": (_c.c_int, [_H, _H, _H, _H, _c.POINTER(RenderParams), _H, _H]),
+    "pt_camera_reference": (None, [_c.POINTER(Camera)]),
+    "pt_camera_derive": (_c.c_int, [_c.POINTER(Camera), _c.POINTER(_c.c_float)]),
+    "pt_render_frames_camera": (_c.c_int, [_H, _H, _H, _H, _c.POINTER(RenderParams), _c.POINTER(Camera), _H, _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_profile_query_union": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double)]),

@@ -3,8 +3,9 @@
 build).  For every (ray, triangle) pair actually traced, the reference's predicate of
 GenerateColors.cl:100,109 (literal form, IEEE division) is evaluated beside the filter; a pair the
 reference keeps but the filter dropped is a VIOLATION and must never occur.
-usage: PT_SHIM_LIB=.../libptshim_validate.so python tools/validate_filter.py [scene] [W H spp] [quad_filter]
-(make -C oclpathtracer_amd/csrc ../libptshim_validate.so; quad_filter = PT_OPT_QUAD_FILTER, 0 = auto)"""
+usage: PT_SHIM_LIB=.../libptshim_validate.so python tools/validate_filter.py [scene] [W H spp] [quad_filter] [camera]
+(make -C oclpathtracer_amd/csrc ../libptshim_validate.so; quad_filter = PT_OPT_QUAD_FILTER, 0 = auto;
+camera = "ex,ey,ez,cx,cy,cz[,fov[,ux,uy,uz]]": eye, center, field of view, up -- the filters' anchor moves with the eye)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -14,6 +15,12 @@ from oclpathtracer_amd.render import Renderer
 kind = sys.argv[1] if len(sys.argv) > 1 else "cornell"
 W, H, spp = (int(x) for x in (sys.argv[2:5] + ["512", "512", "64"][len(sys.argv[2:5]):]))
 quad_filter = int(sys.argv[5]) if len(sys.argv) > 5 else 0
+camera = None
+if len(sys.argv) > 6:
+    from oclpathtracer_amd.camera import Camera
+    v = [float(x) for x in sys.argv[6].split(",")]
+    camera = Camera(tuple(v[0:3]), tuple(v[3:6]), up=tuple(v[7:10]) if len(v) >= 10 else (0.0, 1.0, 0.0),
+                    fov_y_deg=v[6] if len(v) > 6 else 60.0)
 t, m = scene.load_model()
 if kind == "rolled":          # pairs broken: per-triangle filter
     t = np.roll(t, 1)
@@ -45,13 +52,14 @@ elif kind.startswith("random:"):  # the fuzz scenes of tests/test_gpu_parity.py:
 assert adl.init()
 dev = adl.DeviceUtils.allocate()
 dev.setOption(shim.PT_OPT_QUAD_FILTER, quad_filter)
-r = Renderer(dev, t, m, W, H, want_stats=True)
+r = Renderer(dev, t, m, W, H, want_stats=True, camera=camera)
 r.render(spp)
 out = np.zeros(shim.PT_STAT_WORDS, np.uint64)
 r.stats.read(out, shim.PT_STAT_WORDS); dev.waitForCompletion()
 samples, rays, pairs, ref_keep, flt_keep, viol = (int(x) for x in out[:6])
-print("%-8s qf=%d %dx%d x %d: %d rays, %.4g pairs examined; reference keeps %.3f%%, filter keeps %.3f%%; VIOLATIONS: %d"
-      % (kind, quad_filter, W, H, spp, rays, pairs, 100.0 * ref_keep / max(pairs, 1), 100.0 * flt_keep / max(pairs, 1), viol))
+print("%-8s qf=%d %dx%d x %d%s: %d rays, %.4g pairs examined; reference keeps %.3f%%, filter keeps %.3f%%; VIOLATIONS: %d"
+      % (kind, quad_filter, W, H, spp, " camera=%s" % sys.argv[6] if camera else "", rays, pairs, 100.0 * ref_keep / max(pairs, 1),
+         100.0 * flt_keep / max(pairs, 1), viol))
 r.release(); adl.DeviceUtils.deallocate(dev)
 if out[6] or out[7]:  # shared-u filter active: headroom of its error bounds (must be <= 1)
     r1, r3 = (float(np.array([x], np.uint64).astype(np.uint32).view(np.float32)[0]) for x in out[6:8])
