@@ -724,9 +724,6 @@ PTK_DEV void pt_quad3_pass1(pt_const_f32p t, const PtRay3& r, pt_f2& un, pt_f2& 
 #ifndef PT_STAMPS
 #define PT_STAMPS 0
 #endif
-#ifndef PT_LAUNCH_STAMPS
-#define PT_LAUNCH_STAMPS 0   // DIAGNOSTIC build (tools/launch_stamps.py): start / first stop / last exit of one checkpointed launch
-#endif
 #if PT_STAMPS
 #define PT_STAMP(var) do { __builtin_amdgcn_sched_barrier(0); var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
@@ -913,18 +910,9 @@ struct PtPath {
 
 // ---- shade one bounce of a live path (:229-258); on path end store its radiance --------------------
 template <bool DET_BOUNDED, bool LATE>
-PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax, float hu, float hv, int hidx,
-                      unsigned long long* sub = nullptr)
+PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax, float hu, float hv, int hidx)
 {
     const pt_kargs_p K = pt_kargs();  // tris, mats, nmat, max_bounces, rad, npix_local: read here, not kept in SGPRs
-#if PT_STAMPS == 2
-    unsigned long long q0 = 0, q1 = 0, q2 = 0, q3 = 0, q4 = 0, q5 = 0, q6 = 0;
-#define PT_SUB(var) PT_STAMP(var)
-#else
-#define PT_SUB(var) do { } while (0)
-#endif
-    (void)sub;
-    PT_SUB(q0);
     bool finished = false;
     if (hidx < 0) {
         const float bg = pt_max(0.45f, 0.0f);
@@ -940,7 +928,6 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
         __builtin_amdgcn_sched_barrier(0);
         pt_sincos(phi, sp, cp);
         __builtin_amdgcn_sched_barrier(0);
-        PT_SUB(q1);
 
         // deferred HitRecord of the closest hit (:127-130): same values as writing it at every
         // acceptance, only the last one is read.
@@ -964,14 +951,12 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
 
         n = dot3(n, s.d) < 0.0f ? n : scale3(n, -1.0f);  // :243
         f3 wo = neg3(s.d);
-        PT_SUB(q2);
 
         // sampleHemisphereCosine (:161-172) and sampleGGX (:180-192) share everything
         // except (sinTheta, cosTheta)
         f3 axis = __builtin_fabsf(n.x) > 0.001f ? mk3(0.0f, 1.0f, 0.0f) : mk3(1.0f, 0.0f, 0.0f);
         f3 tv = normalize3(cross3(axis, n));
         f3 sv = cross3(n, tv);
-        PT_SUB(q3);
         // one sqrt pair for both BRDFs (a wave usually holds both material types): only the
         // radicands differ -- diffuse: sqrt(xi), sqrt(1-xi); GGX: sqrt((1-xi)/(xi(r^2-1)+1)), then
         // sqrt(max(0, 1-cos^2))
@@ -984,7 +969,6 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
         f3 b = scale3(scale3(tv, sp), sinTheta);
         f3 c = scale3(n, cosTheta);
         f3 sdir = normalize3(add3(add3(a, b), c));
-        PT_SUB(q4);
 
         f3 wi = sdir;
         f3 color = mk3(0.0f, 0.0f, 0.0f);
@@ -1008,7 +992,6 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
                 color = mk3(alb.x * g * 2.0f, alb.y * g * 2.0f, alb.z * g * 2.0f);
             }
         }
-        PT_SUB(q5);
         if (pdf <= 0.0f) {  // :251
             finished = true;
         } else {
@@ -1047,11 +1030,6 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
         *reinterpret_cast<pt_f3v*>(out) = v;  // one 12-byte store (global_store_dwordx3)
         alive = false;
     }
-#if PT_STAMPS == 2
-    PT_SUB(q6);
-    if (sub && q1) { sub[0] += q1 - q0; sub[1] += q2 - q1; sub[2] += q3 - q2; sub[3] += q4 - q3; sub[4] += q5 - q4; sub[5] += q6 - q5; }
-#endif
-#undef PT_SUB
 }
 
 // (n_rays, n_samples: wave-uniform tallies kept in SGPRs -- popcounts of the lanes that shaded / finished; as per-lane counters they
@@ -1120,11 +1098,6 @@ PTK_DEV bool pt_queue_refill(const PtTraceParams& P, unsigned lane, PtWaveQueue&
         unsigned seen = 0u;
         if (lane == 0u) seen = atomicOr(PT_ARG(batch_counter) + PT_QUEUE_STOP_WORD, 1u << sh);
         empty_mask |= (1u << sh) | (unsigned)__builtin_amdgcn_readfirstlane(seen);
-#if PT_LAUNCH_STAMPS
-        if (lane == 0u && PT_ARG(stats) != nullptr && (((unsigned)__builtin_amdgcn_readfirstlane(seen) | (1u << sh)) == (1u << PT_QUEUE_SHARDS) - 1u) &&
-            (unsigned)__builtin_amdgcn_readfirstlane(seen) != (1u << PT_QUEUE_SHARDS) - 1u && PT_ARG(stats)[13] * PT_ARG(slot_frames) == PT_ARG(chunk_f0))
-            atomicMin(&PT_ARG(stats)[14], (unsigned long long)__builtin_amdgcn_s_memrealtime());   // the moment the stop word became complete
-#endif
     }
     if (!got) { q.g = PT_Q_EMPTY; return false; }
     q.g = sh;
@@ -1399,24 +1372,11 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
     unsigned n_rays = 0, n_samples = 0, n_carried = 0;   // (n_carried: samples this wave's checkpoints have handed on, PT_STAT_CARRIED)
     // checkpointed launches: resume what the previous launch of the render left in this wave's region
     // (the wave's number through readfirstlane: to the compiler threadIdx.x >> 6 differs between lanes, and so would everything below)
-    // checkpointed launches: resume what the previous launch of the render left in this wave's region
-    // (the wave's number through readfirstlane: to the compiler threadIdx.x >> 6 differs between lanes, and so would everything below)
     if (blockIdx.x * (PT_TRACE_THREADS / 64) + wave_in_wg < P.carry_in_waves)
         pt_carry_load<true>(P, P.carry + (size_t)(blockIdx.x * (PT_TRACE_THREADS / 64) + wave_in_wg) * PT_CARRY_STRIDE_DW, lane, s, alive, q, n_rays, n_samples, n_carried);
     q.g = (blockIdx.x * (PT_TRACE_THREADS / 64) + wave_in_wg) & (PT_QUEUE_SHARDS - 1u);   // the wave's first shard of this launch's queue
-#if PT_LAUNCH_STAMPS   // DIAGNOSTIC build (tools/launch_stamps.py): where a checkpointed launch's time goes -- s_memrealtime (100 MHz) of the
-    // first wave's start, the moment the stop word is complete, the last wave's exit; stats[9..12]
-    const unsigned long long ls_start = __builtin_amdgcn_s_memrealtime();
-    bool ls_saw_stop = false;
-    unsigned ls_boundaries = 0u, ls_iters = 0u, ls_iters_at_boundary = 0u;
-    unsigned long long ls_t_boundary = ls_start;
-#endif
 #if PT_STAMPS
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, c_regen = 0, c_loop = 0, c_shade = 0, c_iters = 0, c_steps = 0, c_p1 = 0;
-#endif
-#if PT_STAMPS == 2
-    unsigned long long c_sub[6] = { 0, 0, 0, 0, 0, 0 };
-    (void)c_regen; (void)c_loop; (void)c_shade; (void)c_iters; (void)c_steps;  // this build reports the sub-phases instead
 #endif
 
     for (;;) {
@@ -1425,15 +1385,8 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         if (__ballot(!alive) != 0ull) {
             if (pool_n == 0u) {
                 const int next = pt_queue_next<true>(P, lane, q, s, alive);
-#if PT_LAUNCH_STAMPS
-                ++ls_boundaries;
-                if (next != 2) { ls_t_boundary = __builtin_amdgcn_s_memrealtime(); ls_iters_at_boundary = ls_iters; }
-#endif
                 if (next != 0) {
                     pt_pool_push(pool, pool_n, s, alive);                // park every live path ...
-#if PT_LAUNCH_STAMPS
-                    if (next == 2) ls_saw_stop = true;
-#endif
                     if (next == 2) break;                                // ... for the next launch (a checkpoint) ...
                     primary = pt_start_fresh<true>(P, lane, q, s, alive);      // ... or start 64 coherent primary rays
                 }
@@ -1441,9 +1394,6 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
             pt_pool_pop(pool, pool_n, s, alive);           // dead lanes resume parked paths
         }
         if (__ballot(alive) == 0ull) break;
-#if PT_LAUNCH_STAMPS
-        ++ls_iters;
-#endif
         PT_STAMP(t1);
 
         // ---- intersectWorld (:137-154) ------------------------------------------------------
@@ -1473,11 +1423,7 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         PT_STAMP(t2);
         const unsigned long long shaded = __ballot(alive);
         n_rays += (unsigned)__popcll(shaded);
-#if PT_STAMPS == 2
-        if (alive) pt_shade<DET_BOUNDED, true>(P, s, alive, tmax, hu, hv, hidx, c_sub);
-#else
         if (alive) pt_shade<DET_BOUNDED, true>(P, s, alive, tmax, hu, hv, hidx);
-#endif
         n_samples += (unsigned)__popcll(shaded & ~__ballot(alive));   // (a path leaves pt_shade dead only when it has finished)
 #if PT_STAMPS
         PT_STAMP(t3);
@@ -1487,37 +1433,18 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
 
 #if PT_STAMPS
     if (P.stats && lane == 0) {
-#if PT_STAMPS != 2
         atomicAdd(&P.stats[2], c_regen);
         atomicAdd(&P.stats[3], c_loop);
         atomicAdd(&P.stats[4], c_shade);
         atomicAdd(&P.stats[5], c_iters);
-#endif
-#if PT_STAMPS == 2
-        for (int k = 0; k < 6; ++k) atomicAdd(&P.stats[2 + k], c_sub[k]);  // shade sub-phases instead
-#else
         atomicAdd(&P.stats[7], c_steps);
         atomicAdd(&P.stats[6], c_p1);
-#endif
     }
 #endif
     {
         // (a wave that left the loop because nothing was alive holds nothing: no parked path, no rest of a batch -- an empty checkpoint)
         const pt_kargs_p K = pt_kargs();
         if (K->carry_out != 0u) {
-#if PT_LAUNCH_STAMPS
-            // per wave, plain stores into the CALLER'S oversized stats buffer (16 + 4 * waves words): no atomics on a shared line -- those,
-            // 8 192 waves leaving together, backed the L2 channel up and slowed the waves still running five-fold (the first version
-            // of this diagnostic measured its own congestion)
-            if (K->stats != nullptr && lane == 0u && K->stats[13] * K->slot_frames == K->chunk_f0) {   // (stats[13]: which chunk's launch to stamp)
-                const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-                unsigned long long* mine = K->stats + 16 + 4u * (size_t)(blockIdx.x * (PT_TRACE_THREADS / 64) + wave_in_wg);
-                mine[0] = ls_start;
-                mine[1] = ls_t_boundary;
-                mine[2] = now;
-                mine[3] = ((unsigned long long)ls_boundaries << 40) | ((unsigned long long)(ls_iters - ls_iters_at_boundary) << 20) | ls_iters | (ls_saw_stop ? 1ull << 63 : 0ull);
-            }
-#endif
             pt_carry_store(K->carry + (size_t)(blockIdx.x * (PT_TRACE_THREADS / 64) + wave_in_wg) * PT_CARRY_STRIDE_DW, lane, pool, pool_n, q, n_rays, n_samples, n_carried);
             return;   // (the tallies went with it)
         }

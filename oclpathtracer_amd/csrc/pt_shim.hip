@@ -82,6 +82,15 @@ struct PendingFrames {  // deferred GenerateColors launches (PT_OPT_BATCH_FRAMES
     uint32_t pixel_count;
 };
 
+// the pass-1 filter of one triangle table (pt_quad3_pass1): the brute-force scene's or the LBVH's table of big triangles
+struct PtFilterTable {
+    bool pairs;                 // every (2k, 2k+1) is a quad (a,b,c),(c,d,a), det-bounded: mode 3 if the radius allows
+    int quads;                  // 0: independent triangles; 3: pairs, finite radius, margins and the packed table prepared
+    float anchor[3]; bool anchor_valid;   // the eye the margins and the packed table were made about (ensure_anchor), since the table was last prepared
+    float* p1tab;               // the packed table
+    float delta1, ray_radius, p1_lo, p1_hi;   // the filter's bounds: quad modes 2, 3 (pt_quad2_pass1, pt_quad3_pass1)
+};
+
 struct pt_device_s {
     int idx;
     hipDeviceProp_t prop;
@@ -102,20 +111,10 @@ struct pt_device_s {
     uint64_t scene_gen;         // bumped whenever the prepared scene's CONTENTS changed
     uint64_t bvh_builds;        // LBVH builds so far (PT_OPT_BVH_BUILD_COUNT)
     bool prep_det_bounded;      // scene extent allows the short exact reciprocal
-    int prep_quads;             // 0: independent triangles; 3: every pair (2k, 2k+1) is a quad (a,b,c),(c,d,a),
-                                // finite radius, margins and the packed table prepared
-    float prep_delta1, prep_ray_radius;  // quad modes 2, 3 (pt_quad2_pass1)
-    bool prep_finite;                    // every vertex coordinate of the prepared scene is finite ...
-    float prep_lo[3], prep_hi[3];        // ... and these are their per-axis extremes: the radius about any eye (anchor_radius)
-    bool prep_pairs;                     // the scene is made of quads (a,b,c),(c,d,a) and det-bounded: mode 3 if the radius allows
-    float prep_anchor[3];                // the eye the margins and the packed table were made about (ensure_anchor) ...
-    bool prep_anchor_valid;              // ... since the scene was last prepared
-    int big_quads;                       // the LBVH's table of big triangles: 3 = made of quads, its filter table (big_p1tab) and bounds prepared
-    bool big_pairs;                      // ... made of quads: mode 3 if the radius allows
-    float big_anchor[3];                 // as prep_anchor, for the table of big triangles
-    bool big_anchor_valid;
-    float* big_p1tab;
-    float big_delta1, big_ray_radius, big_p1_lo, big_p1_hi;
+    bool prep_finite;           // every vertex coordinate of the prepared scene is finite ...
+    float prep_lo[3], prep_hi[3];  // ... and these are their per-axis extremes: the radius about any eye (anchor_radius)
+    PtFilterTable scene_filter;    // the prepared scene's (p1tab sized with prep)
+    PtFilterTable big_filter;      // the LBVH's table of big triangles (p1tab: ws_big_p1tab, the big triangles' raw records behind it)
     PtBvh8Node* bvh;             // LBVH of the prepared scene (built on demand: ensure_bvh): its 64-byte records, sized with prep
     PtBvhGrid bvh_grid;         // the grid of its nodes' origins
     size_t bvh_records;         // records in use (nodes + leaves)
@@ -124,8 +123,6 @@ struct pt_device_s {
     int nbig;
     int bvh_blocks_per_cu;
     bool bvh_valid;
-    float* p1tab;               // quad mode 3: packed pass-1 table (pt_quad3_pass1), sized with prep
-    float prep_p1_lo, prep_p1_hi;
     unsigned int* det_bound_dev;  // PT_PREP_WORDS device words written by the prep kernel
     // fused-render workspace: the STREAMING renderer.  A render walks its frames in chunks of S frames (as many as a ring slot
     // holds) through a ring of two radiance slots; chunk number seq (a running number over all renders of the handle) uses slot
@@ -215,10 +212,11 @@ static hipError_t ws_malloc(pt_device_s* d, void** p, size_t bytes)
 }
 template <class T> static hipError_t ws_malloc(pt_device_s* d, T** p, size_t bytes) { return ws_malloc(d, reinterpret_cast<void**>(p), bytes); }
 
-static void ws_free(pt_device_s* d, void* p, size_t bytes)
+template <class T> static void ws_free(pt_device_s* d, T*& p, size_t bytes)
 {
     if (!p) return;
     hipFree(p);
+    p = nullptr;
     d->workspace -= bytes;
 }
 
@@ -264,14 +262,14 @@ extern "C" int pt_device_count(void)
 static void destroy_device_objects(pt_device_s* d)
 {
     ws_free(d, d->prep, d->prep_capacity * sizeof(PtPrepTriangle));
-    ws_free(d, d->p1tab, ptk_p1tab_floats((int)d->prep_capacity) * sizeof(float));
+    ws_free(d, d->scene_filter.p1tab, ptk_p1tab_floats((int)d->prep_capacity) * sizeof(float));
     ws_free(d, d->bvh, ptk_bvh_record_count((int)d->prep_capacity) * sizeof(PtBvh8Node));
     ws_free(d, d->ring, PT_RING_SLOTS * d->ring_slot_bytes);
     ws_free(d, d->pmask, d->pmask_pixels * sizeof(uint2));
     ws_free(d, d->counters, WS_COUNTERS);
     ws_free(d, d->bigtab, WS_BIGTAB);
     ws_free(d, d->bigidx, WS_BIGIDX);
-    ws_free(d, d->big_p1tab, ws_big_p1tab());
+    ws_free(d, d->big_filter.p1tab, ws_big_p1tab());
     ws_free(d, d->det_bound_dev, WS_DETBOUND);
     if (d->trav_host) hipHostFree(d->trav_host);
     if (d->prof_pairs) {
@@ -336,7 +334,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->kernels[KERNEL_FOLD_CHECK] = { KERNEL_FOLD_CHECK, "PtShimTest", "FoldCheckKernel" };
     d->prof_pairs = new std::vector<std::pair<hipEvent_t, hipEvent_t>>[PT_PROF_KINDS];
     bool ok = ws_malloc(d, &d->bigtab, WS_BIGTAB) == hipSuccess && ws_malloc(d, &d->bigidx, WS_BIGIDX) == hipSuccess &&
-              ws_malloc(d, &d->counters, WS_COUNTERS) == hipSuccess && ws_malloc(d, &d->big_p1tab, ws_big_p1tab()) == hipSuccess &&
+              ws_malloc(d, &d->counters, WS_COUNTERS) == hipSuccess && ws_malloc(d, &d->big_filter.p1tab, ws_big_p1tab()) == hipSuccess &&
               ws_malloc(d, &d->det_bound_dev, WS_DETBOUND) == hipSuccess;
     // the render lanes and their events (no timing: they only order streams)
     for (int k = 0; ok && k < 2; ++k)
@@ -517,7 +515,6 @@ static int free_ring(pt_device_s* d)
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));   // nothing in flight may still write it
     ws_free(d, d->ring, PT_RING_SLOTS * d->ring_slot_bytes);
-    d->ring = nullptr;
     d->ring_slot_bytes = 0;
     return PT_OK;
 }
@@ -1007,6 +1004,15 @@ extern "C" int pt_camera_derive(const pt_camera* cam, float out[16])
     return PT_OK;
 }
 
+// the prep kernel over n raw records, then the PT_PREP_WORDS it wrote, read back: a host wait (once per scene upload)
+static int prep_triangles(pt_device_s* d, const PtRawTriangle* raw, PtPrepTriangle* out, int n, unsigned int (&words)[PT_PREP_WORDS])
+{
+    HIP_TRY(ptk_prep_triangles(raw, out, n, d->det_bound_dev, d->stream));
+    HIP_TRY(hipMemcpyAsync(words, d->det_bound_dev, sizeof words, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    return PT_OK;
+}
+
 static int ensure_prep(pt_device_s* d, const pt_buffer_s* tris, int ntri)
 {
     // wrapped (caller-owned) memory can change behind our back, and so can a buffer whose device pointer has been handed
@@ -1020,29 +1026,23 @@ static int ensure_prep(pt_device_s* d, const pt_buffer_s* tris, int ntri)
     if (d->prep_capacity < (size_t)ntri) {
         HIP_TRY(hipStreamSynchronize(d->stream));
         ws_free(d, d->prep, d->prep_capacity * sizeof(PtPrepTriangle));
-        ws_free(d, d->p1tab, ptk_p1tab_floats((int)d->prep_capacity) * sizeof(float));
+        ws_free(d, d->scene_filter.p1tab, ptk_p1tab_floats((int)d->prep_capacity) * sizeof(float));
         ws_free(d, d->bvh, ptk_bvh_record_count((int)d->prep_capacity) * sizeof(PtBvh8Node));
-        d->prep = nullptr;
-        d->p1tab = nullptr;
-        d->bvh = nullptr;
         d->bvh_valid = false;
         d->prep_capacity = 0;
         d->prep_src = nullptr;
         d->prep_hash_valid = false;
         size_t cap = std::max<size_t>((size_t)ntri, 64);
         hipError_t e = ws_malloc(d, &d->prep, cap * sizeof(PtPrepTriangle));
-        if (e == hipSuccess) e = ws_malloc(d, &d->p1tab, ptk_p1tab_floats((int)cap) * sizeof(float));
+        if (e == hipSuccess) e = ws_malloc(d, &d->scene_filter.p1tab, ptk_p1tab_floats((int)cap) * sizeof(float));
         if (e != hipSuccess) {
             ws_free(d, d->prep, cap * sizeof(PtPrepTriangle));
-            d->prep = nullptr;
             return fail(PT_ERR_OOM, "scene workspace allocation failed: %s", hipGetErrorString(e));
         }
         d->prep_capacity = cap;
     }
-    HIP_TRY(ptk_prep_triangles((const PtRawTriangle*)tris->dptr, d->prep, ntri, d->det_bound_dev, d->stream));
-    unsigned int words[PT_PREP_WORDS] = { 0u, 1u, 0x7fc00000u, 1u };
-    HIP_TRY(hipMemcpyAsync(words, d->det_bound_dev, sizeof words, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));  // once per scene upload
+    unsigned int words[PT_PREP_WORDS];
+    if ((rc = prep_triangles(d, (const PtRawTriangle*)tris->dptr, d->prep, ntri, words))) return rc;
     float bound;
     memcpy(&bound, &words[0], sizeof bound);
     d->prep_det_bounded = bound <= PT_DET_BOUND_MAX;  // false for NaN / Inf too
@@ -1053,11 +1053,11 @@ static int ensure_prep(pt_device_s* d, const pt_buffer_s* tris, int ntri)
     }
     // every (2k, 2k+1) has e2' == -e2 and is (a,b,c),(c,d,a): quad mode 3 for every camera about which the scene's radius is
     // finite and moderate (ensure_anchor: the margins and the packed table are made per anchor, on the device, no host wait)
-    d->prep_pairs = words[1] == 0u && words[3] == 0u && ntri > 0 && (ntri & 1) == 0 && d->prep_det_bounded && d->prep_finite;
-    d->prep_quads = 0;
-    d->prep_delta1 = 0.0f;
-    d->prep_ray_radius = 0.0f;
-    d->prep_anchor_valid = false;   // the prep kernel has just zeroed the margins
+    PtFilterTable& ft = d->scene_filter;
+    ft.pairs = words[1] == 0u && words[3] == 0u && ntri > 0 && (ntri & 1) == 0 && d->prep_det_bounded && d->prep_finite;
+    ft.quads = 0;
+    ft.delta1 = 0.0f; ft.ray_radius = 0.0f;
+    ft.anchor_valid = false;   // the prep kernel has just zeroed the margins
     d->blocks_per_cu = ptk_trace_blocks_per_cu(ntri);  // the LDS footprint follows the scene
     // Memory the caller can write behind the ABI is prepared again for every render; the checksum of the raw records says whether
     // that changed anything -- if not, the LBVH (a radix sort, a build, host waits) and the primary-ray masks still stand
@@ -1112,20 +1112,15 @@ static int ensure_bvh(pt_device_s* d, const pt_buffer_s* tris, int ntri)
     // of quads (a,b,c),(c,d,a) -- the Cornell box's walls among a soup of small triangles -- it gets the packed shared-u
     // filter (pt_quad3_pass1) like a quad scene on the brute-force path: same preparation (ensure_prep), on the table.  The
     // filter's error bound is about where RAYS start: anywhere on the scene, so the radius is the whole scene's.
-    d->big_quads = 0;
-    d->big_pairs = false;
-    d->big_anchor_valid = false;
-#ifndef PT_EXP_NO_BIGQ  // (A/B builds: the big triangles' search with the plain filter)
+    PtFilterTable& ft = d->big_filter;
+    ft.quads = 0; ft.pairs = false; ft.anchor_valid = false;
     if (d->nbig >= 2 && (d->nbig & 1) == 0 && d->prep_det_bounded && d->prep_finite) {
-        PtRawTriangle* rawbig = reinterpret_cast<PtRawTriangle*>(d->big_p1tab + ptk_p1tab_floats(PT_BVH_BIG_MAX));
+        PtRawTriangle* rawbig = reinterpret_cast<PtRawTriangle*>(ft.p1tab + ptk_p1tab_floats(PT_BVH_BIG_MAX));
         HIP_TRY(ptk_bvh_big_raw((const PtRawTriangle*)tris->dptr, d->bigidx, d->nbig, rawbig, d->stream));
-        HIP_TRY(ptk_prep_triangles(rawbig, d->bigtab, d->nbig, d->det_bound_dev, d->stream));  // (rewrites the same records)
-        unsigned int words[PT_PREP_WORDS] = { 0u, 1u, 0x7fc00000u, 1u };
-        HIP_TRY(hipMemcpyAsync(words, d->det_bound_dev, sizeof words, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(hipStreamSynchronize(d->stream));
-        d->big_pairs = words[1] == 0u && words[3] == 0u;   // margins and packed table: ensure_anchor, per camera
+        unsigned int words[PT_PREP_WORDS];
+        if ((rc = prep_triangles(d, rawbig, d->bigtab, d->nbig, words))) return rc;  // (rewrites the same records)
+        ft.pairs = words[1] == 0u && words[3] == 0u;   // margins and packed table: ensure_anchor, per camera
     }
-#endif
     d->bvh_valid = true;
     d->bvh_builds++;
     return PT_OK;
@@ -1149,19 +1144,15 @@ static float anchor_radius(const pt_device_s* d, const float eye[3])
 // The pass-1 filter of a quad scene (pt_quad3_pass1) is made about an ANCHOR, the render's eye: its error bounds are sized by
 // the scene's radius about it, its packed table holds K = cross(e2, a - eye).  When the eye moves, the margins (pad0 of the
 // prepared records) and the packed table are rewritten by kernels enqueued on the handle's stream, behind the renders in
-// flight (lanes_join: a device-side wait), for the brute-force scene (big = false) or the LBVH's table of big triangles.  The
-// pairing checks of the scene preparation do not depend on the camera and stand; the LBVH is not touched.  The same eye as
-// the table's does nothing at all.
-static int ensure_anchor(pt_device_s* d, const float eye[3], bool big)
+// flight (lanes_join: a device-side wait), for table ft -- the brute-force scene's or the LBVH's table of big triangles -- whose
+// ntri prepared records are tris.  The pairing checks of the scene preparation do not depend on the camera and stand; the LBVH
+// is not touched.  The same eye as the table's does nothing at all.
+static int ensure_anchor(pt_device_s* d, PtFilterTable& ft, PtPrepTriangle* tris, int ntri, const float eye[3])
 {
-    float* key = big ? d->big_anchor : d->prep_anchor;
-    bool& valid = big ? d->big_anchor_valid : d->prep_anchor_valid;
-    if (valid && memcmp(key, eye, 3 * sizeof(float)) == 0) return PT_OK;
-    const bool pairs = big ? d->big_pairs : d->prep_pairs;
+    if (ft.anchor_valid && memcmp(ft.anchor, eye, 3 * sizeof(float)) == 0) return PT_OK;
     const float radius = anchor_radius(d, eye);
-    int& quads = big ? d->big_quads : d->prep_quads;
-    quads = 0;
-    if (pairs && radius <= 1.0e15f) {
+    ft.quads = 0;
+    if (ft.pairs && radius <= 1.0e15f) {
         // quad mode 2: secondary rays start 0.01 off a surface (GenerateColors.cl:253), so their origins stay within ray_radius
         // of the eye -- checked per ray, a ray outside keeps every triangle; the big triangles' filter is about where RAYS
         // start: anywhere on the scene, so its radius is the whole scene's too.  D bounds every coordinate difference between
@@ -1174,23 +1165,142 @@ static int ensure_anchor(pt_device_s* d, const float eye[3], bool big)
         int rc = lanes_join(d);   // (a render through the old table may still be running)
         if (rc) return rc;
         d->main_dirty = true;
-        if (big) {
-            HIP_TRY(ptk_prep_quad_margins(d->bigtab, d->nbig, diameter, delta1, d->big_p1tab, eye, d->stream));
-            d->big_delta1 = delta1;
-            d->big_ray_radius = ray_radius;
-            d->big_p1_lo = -deltaP;
-            d->big_p1_hi = (delta1 + deltaP) * 1.001f;
-        } else {
-            HIP_TRY(ptk_prep_quad_margins(d->prep, d->prep_ntri, diameter, delta1, d->p1tab, eye, d->stream));
-            d->prep_delta1 = delta1;
-            d->prep_ray_radius = ray_radius;
-            d->prep_p1_lo = -deltaP;
-            d->prep_p1_hi = (delta1 + deltaP) * 1.001f;
-        }
-        quads = 3;
+        HIP_TRY(ptk_prep_quad_margins(tris, ntri, diameter, delta1, ft.p1tab, eye, d->stream));
+        ft.delta1 = delta1; ft.ray_radius = ray_radius;
+        ft.p1_lo = -deltaP; ft.p1_hi = (delta1 + deltaP) * 1.001f;
+        ft.quads = 3;
     }
-    memcpy(key, eye, 3 * sizeof(float));
-    valid = true;
+    memcpy(ft.anchor, eye, 3 * sizeof(float));
+    ft.anchor_valid = true;
+    return PT_OK;
+}
+
+// the search and what it reads: the prepared scene, its LBVH, the filter of the table the two-pass search runs over.
+// PT_OPT_ACCEL: 0 = BVH for scenes of PT_BVH_AUTO_MIN triangles or more, 1 = brute force, 2 = BVH (needs >= 2 triangles)
+static int prepare_search(pt_device_s* d, const pt_buffer_s* tris, int ntri, const float eye[3], bool& use_bvh)
+{
+    use_bvh = ntri >= 2 && (d->opt_accel == 2 || (d->opt_accel == 0 && ntri >= PT_BVH_AUTO_MIN));
+    if (!use_bvh && ntri >= (1 << 26))
+        return fail(PT_ERR_INVALID, "the brute-force search packs a triangle index in 26 bits: use PT_OPT_ACCEL 0 or 2 for %d triangles", ntri);
+    if (use_bvh && ntri >= (1 << 25))
+        return fail(PT_ERR_INVALID, "the LBVH search packs a record index (2 x triangles) in 26 bits: %d triangles are too many", ntri);
+    int rc;
+    if ((rc = ensure_prep(d, tris, ntri))) return rc;
+    if (use_bvh && (rc = ensure_bvh(d, tris, ntri))) return rc;
+    return use_bvh ? ensure_anchor(d, d->big_filter, d->bigtab, d->nbig, eye) : ensure_anchor(d, d->scene_filter, d->prep, d->prep_ntri, eye);
+}
+
+// ---- the staging ring: whole frames per chunk, as many as a slot holds -------------------------------------------------
+// Steady state allocates nothing: the ring exists from the first render on (pt_device_reserve_staging) and is replaced
+// only when ONE frame of this image does not fit a slot.  A render of frame_count frames goes in nchunks chunks of `chunk` frames.
+static int plan_chunks(pt_device_s* d, int frame_count, uint32_t npix, int& nchunks, int& chunk)
+{
+    int rc;
+    const uint64_t frame_bytes = (uint64_t)npix * 12;
+    if (!d->ring || d->ring_slot_bytes < frame_bytes) {
+        if (d->ring && (rc = free_ring(d))) return rc;
+        if ((rc = alloc_ring(d, (size_t)std::max<uint64_t>(frame_bytes, PT_DEFAULT_SLOT_BYTES)))) return rc;
+    }
+    uint64_t slot_frames = std::min<uint64_t>(d->ring_slot_bytes / frame_bytes, 16383);   // (fl + ring_phase stays below 65 536: pt_kernels.h, ring_magic)
+    if (d->opt_chunk > 0) slot_frames = std::min<uint64_t>(slot_frames, (uint64_t)d->opt_chunk);
+    nchunks = (int)(((uint64_t)frame_count + slot_frames - 1) / slot_frames);
+    chunk = (frame_count + nchunks - 1) / nchunks;      // S: equal chunks -- 40 frames through a 16-frame slot go 14, 14, 12
+    return PT_OK;
+}
+
+// primary-ray candidate masks: quad scenes of up to 64 triangles on the brute-force path (PT_OPT_PRIMARY_MASKS).  They are a
+// function of the image geometry, the camera and the prepared scene: made when any changes, on the handle's stream, behind the
+// lanes.  make: the masks in hand are stale -- room for new ones is made here and their key updated; render_part launches them
+static int refresh_pmask(pt_device_s* d, const pt_render_params& rp, const PtCamera& cam, uint32_t npix, bool& make)
+{
+    int rc;
+    const int32_t g[7] = { rp.width, rp.height, rp.stripe_rows, rp.n_ranks, rp.rank, (int32_t)npix, rp.num_triangles };
+    make = !d->pmask_key.valid || d->pmask_key.scene_gen != d->scene_gen || memcmp(d->pmask_key.g, g, sizeof g) != 0 ||
+           memcmp(&d->pmask_key.cam, &cam, sizeof cam) != 0;
+    if (!make) return PT_OK;
+    if ((rc = lanes_join(d))) return rc;   // (a render with the old masks may still be running)
+    d->main_dirty = true;
+    d->pmask_key.valid = false;
+    if (d->pmask_pixels < npix) {
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        ws_free(d, d->pmask, d->pmask_pixels * sizeof(uint2));
+        d->pmask_pixels = 0;
+        hipError_t e = ws_malloc(d, &d->pmask, (size_t)npix * sizeof(uint2));
+        if (e != hipSuccess) return fail(PT_ERR_OOM, "primary-mask allocation (%zu bytes) failed: %s", (size_t)npix * sizeof(uint2), hipGetErrorString(e));
+        d->pmask_pixels = npix;
+    }
+    d->pmask_key.scene_gen = d->scene_gen;
+    memcpy(d->pmask_key.g, g, sizeof g);
+    d->pmask_key.cam = cam;
+    return PT_OK;
+}
+
+// Samples per work-queue grab.  A wave that finds the queue empty idles until the last wave is
+// done, on average for half a batch: large batches (fewer atomics) when every wave gets many of
+// them, smaller ones when the launch is short (a rank's share of a multi-GPU render, small images).
+// bpf: batches per frame.  blocks: the persistent grid -- it fills the chip, but never with more waves than a chunk has
+// batches; ONE grid for all launches of the render (a checkpoint is resumed by the wave of the same number)
+static int choose_batch(const pt_device_s* d, bool use_bvh, uint32_t npix, int chunk, uint32_t& batch, uint32_t& bpf, int& blocks)
+{
+    const int wg_waves = PT_TRACE_THREADS / 64;
+    blocks = d->prop.multiProcessorCount * (use_bvh ? d->bvh_blocks_per_cu : d->blocks_per_cu);   // all the chip holds
+    const uint64_t resident_waves = (uint64_t)blocks * wg_waves;
+    const uint64_t chunk_samples = (uint64_t)npix * (uint64_t)chunk;
+    // (not below 128: at 64 the ONE queue counter takes 4 M atomics per launch of configs[2] and the
+    // L2 atomic unit saturates -- measured +30 % launch time)
+    batch = PT_TRACE_BATCH;
+    while (batch > 128u && chunk_samples / batch < 64u * resident_waves) batch >>= 1;
+    bpf = (npix + batch - 1) / batch;
+    if ((uint64_t)bpf * (uint64_t)chunk + PT_QUEUE_SHARDS > 0xffffffffull) return fail(PT_ERR_INVALID, "chunk too large");
+    const uint64_t blocks_needed = ((uint64_t)bpf * (uint64_t)chunk + wg_waves - 1) / wg_waves;
+    if ((uint64_t)blocks > blocks_needed) blocks = (int)blocks_needed;
+    return PT_OK;
+}
+
+// what every trace launch of the render is given; render_part's trace() sets the per-launch rest (queue, frames, checkpoints)
+static PtTraceParams trace_params(const pt_device_s* d, const pt_buffer_s* mats, const pt_buffer_s* stats, const pt_render_params& rp,
+                                  const PtCamera& cam, uint32_t npix, const PtFilterTable& ft, bool use_bvh, bool use_pmask, int chunk,
+                                  uint32_t batch, uint32_t bpf)
+{
+    PtTraceParams tp;
+    memset(&tp, 0, sizeof tp);
+    tp.tris = d->prep;
+    tp.mats = (const PtRawMaterial*)mats->dptr;
+    tp.stats = stats ? (unsigned long long*)stats->dptr : nullptr;
+    tp.width = rp.width; tp.height = rp.height;
+    tp.inv_width = 1.0f / (float)rp.width;     // IEEE quotients: the translation unit is compiled without fast-math
+    tp.inv_height = 1.0f / (float)rp.height;
+    tp.aspect = (float)rp.width / (float)rp.height;
+    tp.max_bounces = rp.max_bounces; tp.ntri = rp.num_triangles; tp.nmat = rp.num_materials;
+    tp.stripe_rows = rp.stripe_rows; tp.n_ranks = rp.n_ranks; tp.rank = rp.rank;
+    tp.npix_local = npix;
+    tp.batches_per_frame = bpf; tp.batch = batch;
+    tp.quad_delta1 = ft.delta1; tp.ray_radius = ft.ray_radius;
+    tp.p1tab = ft.p1tab; tp.p1_lo = ft.p1_lo; tp.p1_hi = ft.p1_hi;
+    tp.bvh = d->bvh; tp.bvh_records = (int32_t)d->bvh_records; tp.grid = d->bvh_grid;
+    tp.bigtab = d->bigtab; tp.bigidx = d->bigidx; tp.nbig = use_bvh ? d->nbig : 0;
+    tp.pmask = use_pmask ? d->pmask : nullptr;
+    tp.bvh_flags = d->trav_dev; tp.bvh_stack_limit = (int32_t)d->opt_bvh_stack;
+    tp.slot_frames = (uint32_t)chunk;
+    tp.ring_magic = (uint32_t)(0x100000000ull / (2u * (uint32_t)chunk)) + 1u;
+    tp.rad = d->ring;
+    tp.rad1 = reinterpret_cast<float*>(reinterpret_cast<char*>(d->ring) + d->ring_slot_bytes);
+    tp.cam = cam;
+    return tp;
+}
+
+// the checkpoint regions of both lanes, for as many waves as any kernel's grid can have
+static int ensure_carry(pt_device_s* d, int blocks)
+{
+    const int wg_waves = PT_TRACE_THREADS / 64;
+    const size_t waves = (size_t)d->prop.multiProcessorCount * 8 * wg_waves;   // (no kernel has more than 8 workgroups per CU resident)
+    if ((size_t)blocks * wg_waves > waves) return fail(PT_ERR_INVALID, "grid larger than the checkpoint regions");
+    for (int k = 0; k < 2; ++k)
+        if (!d->carry[k]) {   // once per device handle, at its first such render
+            hipError_t e = ws_malloc(d, &d->carry[k], waves * PT_CARRY_STRIDE_DW * sizeof(uint32_t));
+            if (e != hipSuccess) return fail(PT_ERR_OOM, "checkpoint buffer allocation failed: %s", hipGetErrorString(e));
+            d->carry_waves = waves;
+        }
     return PT_OK;
 }
 
@@ -1200,129 +1310,29 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
                        uint32_t npix, pt_buffer_s* stats, pt_event_s* ev_start, pt_event_s* ev_stop)
 {
     int rc;
-    // PT_OPT_ACCEL: 0 = BVH for scenes of PT_BVH_AUTO_MIN triangles or more, 1 = brute force, 2 = BVH (needs >= 2 triangles)
-    const bool use_bvh = rp.num_triangles >= 2 &&
-                         (d->opt_accel == 2 || (d->opt_accel == 0 && rp.num_triangles >= PT_BVH_AUTO_MIN));
-    if (!use_bvh && rp.num_triangles >= (1 << 26))
-        return fail(PT_ERR_INVALID, "the brute-force search packs a triangle index in 26 bits: use PT_OPT_ACCEL 0 or 2 for %d triangles", rp.num_triangles);
-    if (use_bvh && rp.num_triangles >= (1 << 25))
-        return fail(PT_ERR_INVALID, "the LBVH search packs a record index (2 x triangles) in 26 bits: %d triangles are too many", rp.num_triangles);
-    if ((rc = ensure_prep(d, tris, rp.num_triangles))) return rc;
-    if (use_bvh && (rc = ensure_bvh(d, tris, rp.num_triangles))) return rc;
-    if ((rc = ensure_anchor(d, cam.eye, use_bvh))) return rc;
-
-    // ---- the staging ring: whole frames per chunk, as many as a slot holds -------------------------------------------------
-    // Steady state allocates nothing: the ring exists from the first render on (pt_device_reserve_staging) and is replaced
-    // only when ONE frame of this image does not fit a slot.
-    const uint64_t frame_bytes = (uint64_t)npix * 12;
-    if (!d->ring || d->ring_slot_bytes < frame_bytes) {
-        if (d->ring && (rc = free_ring(d))) return rc;
-        if ((rc = alloc_ring(d, (size_t)std::max<uint64_t>(frame_bytes, PT_DEFAULT_SLOT_BYTES)))) return rc;
-    }
-    uint64_t slot_frames = std::min<uint64_t>(d->ring_slot_bytes / frame_bytes, 16383);   // (fl + ring_phase stays below 65 536: pt_kernels.h, ring_magic)
-    if (d->opt_chunk > 0) slot_frames = std::min<uint64_t>(slot_frames, (uint64_t)d->opt_chunk);
-    const int nchunks = (int)(((uint64_t)rp.frame_count + slot_frames - 1) / slot_frames);
-    const int chunk = (rp.frame_count + nchunks - 1) / nchunks;      // S: equal chunks -- 40 frames through a 16-frame slot go 14, 14, 12
-
-    // primary-ray candidate masks: quad scenes of up to 64 triangles on the brute-force path (PT_OPT_PRIMARY_MASKS).  They are a
-    // function of the image geometry, the camera and the prepared scene: made when any changes, on the handle's stream, behind the lanes
-    const int quads_sel = (d->opt_quads == 0 || d->opt_quads == 4) ? d->prep_quads : 0;
-    const bool use_pmask = d->opt_pmask && quads_sel == 3 && !use_bvh && rp.num_triangles <= 64 && d->prep_det_bounded;
+    bool use_bvh;
+    if ((rc = prepare_search(d, tris, rp.num_triangles, cam.eye, use_bvh))) return rc;
+    const PtFilterTable& ft = use_bvh ? d->big_filter : d->scene_filter;
+    int nchunks, chunk;
+    if ((rc = plan_chunks(d, rp.frame_count, npix, nchunks, chunk))) return rc;
+    // PT_OPT_QUAD_FILTER: 0 / 4 = the packed shared-u filter when the table allows it, 1..3 = independent triangles
+    const int quads = (d->opt_quads == 0 || d->opt_quads == 4) ? ft.quads : 0;
+    const bool use_pmask = d->opt_pmask && quads == 3 && !use_bvh && rp.num_triangles <= 64 && d->prep_det_bounded;
     bool make_pmask = false;
-    if (use_pmask) {
-        const int32_t g[7] = { rp.width, rp.height, rp.stripe_rows, rp.n_ranks, rp.rank, (int32_t)npix, rp.num_triangles };
-        make_pmask = !d->pmask_key.valid || d->pmask_key.scene_gen != d->scene_gen || memcmp(d->pmask_key.g, g, sizeof g) != 0 ||
-                     memcmp(&d->pmask_key.cam, &cam, sizeof cam) != 0;
-        if (make_pmask) {
-            if ((rc = lanes_join(d))) return rc;   // (a render with the old masks may still be running)
-            d->main_dirty = true;
-            d->pmask_key.valid = false;
-            if (d->pmask_pixels < npix) {
-                HIP_TRY(hipStreamSynchronize(d->stream));
-                ws_free(d, d->pmask, d->pmask_pixels * sizeof(uint2));
-                d->pmask = nullptr;
-                d->pmask_pixels = 0;
-                hipError_t e = ws_malloc(d, &d->pmask, (size_t)npix * sizeof(uint2));
-                if (e != hipSuccess) return fail(PT_ERR_OOM, "primary-mask allocation (%zu bytes) failed: %s", (size_t)npix * sizeof(uint2), hipGetErrorString(e));
-                d->pmask_pixels = npix;
-            }
-            d->pmask_key.scene_gen = d->scene_gen;
-            memcpy(d->pmask_key.g, g, sizeof g);
-            d->pmask_key.cam = cam;
-        }
-    }
+    if (use_pmask && (rc = refresh_pmask(d, rp, cam, npix, make_pmask))) return rc;
     if (d->counters_dirty) {   // an earlier call failed between a trace launch and the fold that resets its counter
         if ((rc = lanes_join(d))) return rc;
         HIP_TRY(hipMemsetAsync(d->counters, 0, WS_COUNTERS, d->stream));
         d->main_dirty = true;
         d->counters_dirty = false;
     }
-
-    // Samples per work-queue grab.  A wave that finds the queue empty idles until the last wave is
-    // done, on average for half a batch: large batches (fewer atomics) when every wave gets many of
-    // them, smaller ones when the launch is short (a rank's share of a multi-GPU render, small images).
-    const uint64_t resident_waves = (uint64_t)d->prop.multiProcessorCount * (uint64_t)(use_bvh ? d->bvh_blocks_per_cu : d->blocks_per_cu) * (PT_TRACE_THREADS / 64);
-    const uint64_t chunk_samples = (uint64_t)npix * (uint64_t)chunk;
-    // (not below 128: at 64 the ONE queue counter takes 4 M atomics per launch of configs[2] and the
-    // L2 atomic unit saturates -- measured +30 % launch time)
-    uint32_t batch = PT_TRACE_BATCH;
-    while (batch > 128u && chunk_samples / batch < 64u * resident_waves) batch >>= 1;
-    if (getenv("PT_SHIM_BATCH")) batch = (uint32_t)std::max(64, atoi(getenv("PT_SHIM_BATCH")));   // (experiments)
-    const uint32_t bpf = (npix + batch - 1) / batch;
-    if ((uint64_t)bpf * (uint64_t)chunk + PT_QUEUE_SHARDS > 0xffffffffull) return fail(PT_ERR_INVALID, "chunk too large");
-
-    PtTraceParams tp;
-    memset(&tp, 0, sizeof tp);
-    tp.tris = d->prep;
-    tp.mats = (const PtRawMaterial*)mats->dptr;
-    tp.stats = stats ? (unsigned long long*)stats->dptr : nullptr;
-    tp.width = rp.width;
-    tp.height = rp.height;
-    tp.inv_width = 1.0f / (float)rp.width;     // IEEE quotients: the translation unit is compiled without fast-math
-    tp.inv_height = 1.0f / (float)rp.height;
-    tp.aspect = (float)rp.width / (float)rp.height;
-    tp.max_bounces = rp.max_bounces;
-    tp.ntri = rp.num_triangles;
-    tp.nmat = rp.num_materials;
-    tp.stripe_rows = rp.stripe_rows;
-    tp.n_ranks = rp.n_ranks;
-    tp.rank = rp.rank;
-    tp.npix_local = npix;
-    tp.batches_per_frame = bpf;
-    tp.batch = batch;
-    tp.quad_delta1 = use_bvh ? d->big_delta1 : d->prep_delta1;
-    tp.ray_radius = use_bvh ? d->big_ray_radius : d->prep_ray_radius;
-    tp.p1tab = use_bvh ? d->big_p1tab : d->p1tab;
-    tp.p1_lo = use_bvh ? d->big_p1_lo : d->prep_p1_lo;
-    tp.p1_hi = use_bvh ? d->big_p1_hi : d->prep_p1_hi;
-    tp.bvh = d->bvh;
-    tp.bvh_records = (int32_t)d->bvh_records;
-    tp.grid = d->bvh_grid;
-    tp.bigtab = d->bigtab;
-    tp.bigidx = d->bigidx;
-    tp.nbig = use_bvh ? d->nbig : 0;
-    tp.pmask = use_pmask ? d->pmask : nullptr;
-    tp.bvh_flags = d->trav_dev;
-    tp.bvh_stack_limit = (int32_t)d->opt_bvh_stack;
-    tp.slot_frames = (uint32_t)chunk;
-    tp.ring_magic = (uint32_t)(0x100000000ull / (2u * (uint32_t)chunk)) + 1u;
-    tp.rad = d->ring;
-    tp.rad1 = reinterpret_cast<float*>(reinterpret_cast<char*>(d->ring) + d->ring_slot_bytes);
-    tp.cam = cam;
+    uint32_t batch, bpf;
+    int blocks;
+    if ((rc = choose_batch(d, use_bvh, npix, chunk, batch, bpf, blocks))) return rc;
+    PtTraceParams tp = trace_params(d, mats, stats, rp, cam, npix, ft, use_bvh, use_pmask, chunk, batch, bpf);
     if (make_pmask) {
         HIP_TRY(ptk_primary_masks(tp, d->stream));  // (cheap: one thread per pixel)
         d->pmask_key.valid = true;
-    }
-    // PT_OPT_QUAD_FILTER: 0 / 4 = the packed shared-u filter when the scene allows it, 1..3 = independent triangles
-    const int quads = (d->opt_quads == 0 || d->opt_quads == 4) ? (use_bvh ? d->big_quads : d->prep_quads) : 0;
-
-    // persistent grid: fill the chip, but never more waves than a chunk has batches; ONE grid for all launches of the render (a
-    // checkpoint is resumed by the wave of the same number)
-    const int wg_waves = PT_TRACE_THREADS / 64;
-    int blocks = d->prop.multiProcessorCount * (use_bvh ? d->bvh_blocks_per_cu : d->blocks_per_cu);
-    {
-        const uint64_t blocks_needed = ((uint64_t)bpf * (uint64_t)chunk + wg_waves - 1) / wg_waves;
-        if ((uint64_t)blocks > blocks_needed) blocks = (int)blocks_needed;
     }
     // checkpointed launches (PtTraceParams::carry): the table kernels stop at a fresh-phase boundary, the LBVH kernel between two searches
     // (a render of ONE chunk has nothing to hand on: its only launch runs its paths out, beside the next render's first launch on the other lane --
@@ -1332,16 +1342,8 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
     // chunk c+1's launch becomes resident while chunk c's runs its paths out (an LBVH launch's tail is milliseconds of falling lane use)
     int ln = d->opt_lanes == 2 ? (int)(d->render_seq++ & 1u) : 0;
     hipStream_t st = d->lane[ln];
-    if (carry) {
-        const size_t waves = (size_t)d->prop.multiProcessorCount * 8 * wg_waves;   // (no kernel has more than 8 workgroups per CU resident)
-        if ((size_t)blocks * wg_waves > waves) return fail(PT_ERR_INVALID, "grid larger than the checkpoint regions");
-        for (int k = 0; k < 2; ++k)
-            if (!d->carry[k]) {   // once per device handle, at its first such render
-                hipError_t e = ws_malloc(d, &d->carry[k], waves * PT_CARRY_STRIDE_DW * sizeof(uint32_t));
-                if (e != hipSuccess) return fail(PT_ERR_OOM, "checkpoint buffer allocation failed: %s", hipGetErrorString(e));
-                d->carry_waves = waves;
-            }
-    }
+    if (carry && (rc = ensure_carry(d, blocks))) return rc;
+    const int wg_waves = PT_TRACE_THREADS / 64;
 
     // ---- fork: the lanes go behind the handle's stream (what uploaded the scene, cleared the framebuffer, made the masks ...)
     if (d->main_dirty || d->external) {
@@ -1496,24 +1498,27 @@ static int render_internal(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats,
     return PT_OK;
 }
 
+// what GenerateColors launches render: the reference's constants, one rank
+static pt_render_params reference_params(int width, int height, int frame_begin, int frame_count, const pt_buffer_s* mats)
+{
+    pt_render_params rp;
+    memset(&rp, 0, sizeof rp);
+    rp.width = width; rp.height = height;
+    rp.frame_begin = frame_begin; rp.frame_count = frame_count;
+    rp.max_bounces = 16;    // BOUNCES       GenerateColors.cl:5
+    rp.num_triangles = 36;  // NUM_TRIANGLES GenerateColors.cl:6
+    rp.num_materials = (int)std::min<size_t>(mats->bytes / sizeof(PtRawMaterial), 0x7fffffff);
+    rp.stripe_rows = 1; rp.n_ranks = 1; rp.rank = 0;
+    return rp;
+}
+
 static int flush_pending(pt_device_s* d)
 {
     if (!d->pending.active) return PT_OK;
     PendingFrames p = d->pending;
     d->pending.active = false;
-    pt_render_params rp;
-    memset(&rp, 0, sizeof rp);
-    rp.width = p.width;
-    rp.height = p.height;
-    rp.frame_begin = p.z_begin;
-    rp.frame_count = p.z_count;
-    rp.max_bounces = 16;    // BOUNCES       GenerateColors.cl:5
-    rp.num_triangles = 36;  // NUM_TRIANGLES GenerateColors.cl:6
-    rp.num_materials = (int)std::min<size_t>(p.mats->bytes / sizeof(PtRawMaterial), 0x7fffffff);
-    rp.stripe_rows = 1;
-    rp.n_ranks = 1;
-    rp.rank = 0;
-    return render_internal(d, p.tris, p.mats, p.fb, rp, reference_camera(), p.pixel_count, nullptr, nullptr);
+    return render_internal(d, p.tris, p.mats, p.fb, reference_params(p.width, p.height, p.z_begin, p.z_count, p.mats), reference_camera(),
+                           p.pixel_count, nullptr, nullptr);
 }
 
 extern "C" int pt_render_frames_camera(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t framebuffer,
@@ -1723,13 +1728,7 @@ static int launch_generate_colors(pt_device_s* d, const pt_launch_arg* a, int na
         if (ms_out) *ms_out = 0.f;
         return PT_OK;
     }
-    pt_render_params rp;
-    memset(&rp, 0, sizeof rp);
-    rp.width = c[0]; rp.height = c[1];
-    rp.frame_begin = c[2]; rp.frame_count = 1;
-    rp.max_bounces = 16; rp.num_triangles = 36;
-    rp.num_materials = (int)std::min<size_t>(m->bytes / sizeof(PtRawMaterial), 0x7fffffff);
-    rp.stripe_rows = 1; rp.n_ranks = 1; rp.rank = 0;
+    const pt_render_params rp = reference_params(c[0], c[1], c[2], 1, m);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (d->opt_profile) {
         int jrc = lanes_join(d);   // earlier renders are not part of this launch's time
