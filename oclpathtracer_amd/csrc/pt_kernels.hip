@@ -1069,6 +1069,16 @@ struct PtWaveQueue {  // wave-uniform (SGPRs): the wave's current range [pix, en
 
 #define PT_Q_EMPTY 0xffffffffu   // PtWaveQueue::g once the wave has found every shard of the queue empty
 
+// q.row / col / sl / within of q.pix: wave-uniform divisions, once per batch
+template <bool LATE>
+PTK_DEV void pt_queue_locate(const PtTraceParams& P, pt_kargs_p K, PtWaveQueue& q)
+{
+    q.row = q.pix / (unsigned)PT_ARG(width);
+    q.col = q.pix - q.row * (unsigned)PT_ARG(width);
+    q.sl = q.row / (unsigned)PT_ARG(stripe_rows);
+    q.within = q.row - q.sl * (unsigned)PT_ARG(stripe_rows);
+}
+
 // Makes [q.pix, q.end) non-empty when the current batch is used up; false when there is nothing (more) to start in this launch.
 // The batches of a launch's chunk (128 or 256 consecutive pixels of one frame, numbered frame-major) come off a SHARDED queue:
 // PT_QUEUE_SHARDS counters, each on a cache line of its own; shard s deals the batches s, s + NS, s + 2 NS, ...  One counter for
@@ -1107,30 +1117,58 @@ PTK_DEV bool pt_queue_refill(const PtTraceParams& P, unsigned lane, PtWaveQueue&
     q.pix = bi * PT_ARG(batch);
     const unsigned e = q.pix + PT_ARG(batch);
     q.end = e < PT_ARG(npix_local) ? e : PT_ARG(npix_local);
-    q.row = q.pix / (unsigned)PT_ARG(width);  // wave-uniform divisions, once per batch
-    q.col = q.pix - q.row * (unsigned)PT_ARG(width);
-    q.sl = q.row / (unsigned)PT_ARG(stripe_rows);
-    q.within = q.row - q.sl * (unsigned)PT_ARG(stripe_rows);
+    pt_queue_locate<LATE>(P, K, q);
     return true;
 }
 
-// pool slot k of a wave: 60 bytes = three float4 arrays of PT_POOL entries (conflict-free b128 accesses) + one array of
-// three dwords.  (64-byte slots would put the workgroup over 160 KB / 8: the LDS is what decides whether 8 workgroups
-// -- 8 waves per SIMD -- fit a CU.)
+// The parked-path record: 60 bytes, three float4 and three dwords, wherever a path waits --
 //   [0] o.xyz d.x   [1] d.yz mask.xy   [2] mask.z L.xyz   [3] seed, lp, fl | bounce << 16
+// PtPathSlots says where: float4 word j of record k at A[j fs + k], dword j at W[j ws + k wk].  The pool of a wave (LDS) keeps three
+// float4 arrays of PT_POOL entries (conflict-free b128 accesses) and one array of dword triples.  (64-byte slots would put the
+// workgroup over 160 KB / 8: the LDS is what decides whether 8 workgroups -- 8 waves per SIMD -- fit a CU.)  A carry region keeps
+// three float4 arrays and three dword arrays of PT_CARRY_RECORDS entries (lane k moves entry k, coalesced).
+struct PtPathSlots {
+    float4* A;
+    unsigned* W;
+    unsigned fs, ws, wk;
+    PTK_DEV float4& vec(unsigned j, unsigned k) const { return A[j * fs + k]; }
+    PTK_DEV unsigned& word(unsigned j, unsigned k) const { return W[j * ws + wk * k]; }
+};
+
 #define PT_POOL_DWORDS (PT_POOL * 15)
+PTK_DEV PtPathSlots pt_pool_slots(float4* pool) { return { pool, reinterpret_cast<unsigned*>(pool + 3 * PT_POOL), PT_POOL, 1u, 3u }; }
+PTK_DEV PtPathSlots pt_carry_slots(uint32_t* region) { return { (float4*)(region + 16), region + 16 + PT_CARRY_RECORDS * 12, PT_CARRY_RECORDS, PT_CARRY_RECORDS, 1u }; }
+
+PTK_DEV void pt_path_store(const PtPathSlots& S, unsigned k, const PtPath& s)
+{
+    S.vec(0, k) = make_float4(s.o.x, s.o.y, s.o.z, s.d.x);
+    S.vec(1, k) = make_float4(s.d.y, s.d.z, s.mask.x, s.mask.y);
+    S.vec(2, k) = make_float4(s.mask.z, s.L.x, s.L.y, s.L.z);
+    S.word(0, k) = s.seed;
+    S.word(1, k) = s.lp;
+    S.word(2, k) = s.fl | ((unsigned)s.bounce << 16);  // both below 65 536 (pt_render_frames checks: the ring has fewer frames)
+}
+
+PTK_DEV void pt_path_load(const PtPathSlots& S, unsigned k, PtPath& s)
+{
+    const float4 a0 = S.vec(0, k), a1 = S.vec(1, k), a2 = S.vec(2, k);
+    const unsigned w2 = S.word(2, k);
+    s.o = mk3(a0.x, a0.y, a0.z);
+    s.d = mk3(a0.w, a1.x, a1.y);
+    s.mask = mk3(a1.z, a1.w, a2.x);
+    s.L = mk3(a2.y, a2.z, a2.w);
+    s.seed = S.word(0, k);
+    s.lp = S.word(1, k);
+    s.fl = w2 & 0xffffu;
+    s.bounce = (int)(w2 >> 16);
+}
+
 PTK_DEV void pt_pool_push(float4* pool, unsigned& pool_n, const PtPath& s, bool& alive)
 {
     const unsigned long long live = __ballot(alive);
     if (alive) {
         const unsigned k = pool_n + pt_mbcnt(live);
-        pool[k] = make_float4(s.o.x, s.o.y, s.o.z, s.d.x);
-        pool[PT_POOL + k] = make_float4(s.d.y, s.d.z, s.mask.x, s.mask.y);
-        pool[2 * PT_POOL + k] = make_float4(s.mask.z, s.L.x, s.L.y, s.L.z);
-        unsigned* w = reinterpret_cast<unsigned*>(pool + 3 * PT_POOL) + 3u * k;
-        w[0] = s.seed;
-        w[1] = s.lp;
-        w[2] = s.fl | ((unsigned)s.bounce << 16);  // both below 65 536 (pt_render_frames checks: the ring has fewer frames)
+        pt_path_store(pt_pool_slots(pool), k, s);
     }
     pool_n += (unsigned)__popcll(live);
     alive = false;
@@ -1150,17 +1188,7 @@ PTK_DEV void pt_pool_pop(float4* pool, unsigned& pool_n, PtPath& s, bool& alive)
     const unsigned rank = pt_mbcnt(need);
     if (!alive && rank < take) {
         const unsigned k = pool_n - 1u - rank;
-        const float4 a0 = pool[k], a1 = pool[PT_POOL + k], a2 = pool[2 * PT_POOL + k];
-        const unsigned* w = reinterpret_cast<const unsigned*>(pool + 3 * PT_POOL) + 3u * k;
-        const unsigned w0 = w[0], w1 = w[1], w2 = w[2];
-        s.o = mk3(a0.x, a0.y, a0.z);
-        s.d = mk3(a0.w, a1.x, a1.y);
-        s.mask = mk3(a1.z, a1.w, a2.x);
-        s.L = mk3(a2.y, a2.z, a2.w);
-        s.seed = w0;
-        s.lp = w1;
-        s.fl = w2 & 0xffffu;
-        s.bounce = (int)(w2 >> 16);
+        pt_path_load(pt_pool_slots(pool), k, s);
         alive = true;
     }
     pool_n -= take;
@@ -1173,70 +1201,53 @@ PTK_DEV void pt_pool_pop(float4* pool, unsigned& pool_n, PtPath& s, bool& alive)
 // ---- checkpointed launches (PtTraceParams::carry) ---------------------------------------------------------------------
 // A wave stops only where its pool is empty and a fresh phase would begin: it parks its live paths exactly as a fresh phase does
 // (the bounce loop's own pt_pool_push site -- a second copy of that code after the loop cost fourteen spilled registers INSIDE
-// the loop) and leaves; the pool then goes to the wave's region: 16 header dwords and the parked-path record as arrays of
-// PT_CARRY_RECORDS entries (three float4 arrays, three dword arrays: lane k moves entry k, coalesced).
-PTK_DEV void pt_carry_store(uint32_t* region, unsigned lane, const float4* pool, unsigned pool_n, const PtWaveQueue& q, unsigned n_rays, unsigned n_samples,
+// the loop) and leaves; the pool then goes to the wave's region: 16 header dwords and n parked-path records (pt_path_store).
+
+// the header: n paths, the rest of the batch, the wave's tallies.  The tallies travel with the checkpoint and reach the stats buffer
+// at the end of the render's last launch, where the waves leave one by one: 8 192 waves leaving TOGETHER, two or three atomics each
+// on the same line, measured 0.25 ms per launch
+PTK_DEV void pt_carry_header(uint32_t* region, unsigned n, const PtWaveQueue& q, unsigned n_rays, unsigned n_samples, unsigned n_carried)
+{
+    region[0] = n;
+    region[1] = q.pix;
+    region[2] = q.end;
+    region[3] = q.frame;
+    region[4] = n_rays;
+    region[5] = n_samples;
+    region[6] = n_carried + n + (q.end - q.pix);
+}
+
+PTK_DEV void pt_carry_store(uint32_t* region, unsigned lane, float4* pool, unsigned pool_n, const PtWaveQueue& q, unsigned n_rays, unsigned n_samples,
                             unsigned n_carried)
 {
-    float4* A = reinterpret_cast<float4*>(region + 16);
-    unsigned* W = region + 16 + PT_CARRY_RECORDS * 12;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the wave's own pool writes, read by other lanes: as in pt_pool_pop
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (lane < pool_n) {
-        A[lane] = pool[lane];
-        A[PT_CARRY_RECORDS + lane] = pool[PT_POOL + lane];
-        A[2 * PT_CARRY_RECORDS + lane] = pool[2 * PT_POOL + lane];
-        const unsigned* w = reinterpret_cast<const unsigned*>(pool + 3 * PT_POOL) + 3u * lane;
-        W[lane] = w[0];
-        W[PT_CARRY_RECORDS + lane] = w[1];
-        W[2 * PT_CARRY_RECORDS + lane] = w[2];
+        const PtPathSlots from = pt_pool_slots(pool), to = pt_carry_slots(region);
+        for (unsigned j = 0; j < 3u; ++j) to.vec(j, lane) = from.vec(j, lane);
+        for (unsigned j = 0; j < 3u; ++j) to.word(j, lane) = from.word(j, lane);
     }
-    if (lane == 0u) {
-        region[0] = pool_n;
-        region[1] = q.pix;
-        region[2] = q.end;
-        region[3] = q.frame;
-        // the wave's tallies travel with the checkpoint and reach the stats buffer at the end of the render's last launch, where the
-        // waves leave one by one: 8 192 waves leaving TOGETHER, two or three atomics each on the same line, measured 0.25 ms per launch
-        region[4] = n_rays;
-        region[5] = n_samples;
-        region[6] = n_carried + pool_n + (q.end - q.pix);
-    }
+    if (lane == 0u) pt_carry_header(region, pool_n, q, n_rays, n_samples, n_carried);
 }
 
 // the LBVH kernel's checkpoint: no pool -- the live lanes go to the region directly, compacted (its registers have room for it)
 PTK_DEV void pt_carry_store_lanes(uint32_t* region, unsigned lane, const PtPath& s, bool alive, const PtWaveQueue& q, unsigned n_rays, unsigned n_samples,
                                   unsigned n_carried)
 {
-    float4* A = reinterpret_cast<float4*>(region + 16);
-    unsigned* W = region + 16 + PT_CARRY_RECORDS * 12;
     const unsigned long long live = __ballot(alive);
     const unsigned n_live = (unsigned)__popcll(live);
     if (alive) {
         const unsigned k = pt_mbcnt(live);
-        A[k] = make_float4(s.o.x, s.o.y, s.o.z, s.d.x);
-        A[PT_CARRY_RECORDS + k] = make_float4(s.d.y, s.d.z, s.mask.x, s.mask.y);
-        A[2 * PT_CARRY_RECORDS + k] = make_float4(s.mask.z, s.L.x, s.L.y, s.L.z);
-        W[k] = s.seed;
-        W[PT_CARRY_RECORDS + k] = s.lp;
-        W[2 * PT_CARRY_RECORDS + k] = s.fl | ((unsigned)s.bounce << 16);
+        pt_path_store(pt_carry_slots(region), k, s);
     }
-    if (lane == 0u) {
-        region[0] = n_live;
-        region[1] = q.pix;
-        region[2] = q.end;
-        region[3] = q.frame;
-        region[4] = n_rays;
-        region[5] = n_samples;
-        region[6] = n_carried + n_live + (q.end - q.pix);
-    }
+    if (lane == 0u) pt_carry_header(region, n_live, q, n_rays, n_samples, n_carried);
 }
 
 // resumes a checkpoint: the parked paths go straight into lanes (at most 64: the pool was empty when they were parked), the rest
 // of the batch becomes the wave's current range
 template <bool LATE>
-PTK_DEV void pt_carry_load(const PtTraceParams& P, const uint32_t* region, unsigned lane, PtPath& s, bool& alive, PtWaveQueue& q, unsigned& n_rays,
+PTK_DEV void pt_carry_load(const PtTraceParams& P, uint32_t* region, unsigned lane, PtPath& s, bool& alive, PtWaveQueue& q, unsigned& n_rays,
                            unsigned& n_samples, unsigned& n_carried)
 {
     const pt_kargs_p K = pt_kargs();
@@ -1247,23 +1258,9 @@ PTK_DEV void pt_carry_load(const PtTraceParams& P, const uint32_t* region, unsig
     q.pix = __builtin_amdgcn_readfirstlane(region[1]);
     q.end = __builtin_amdgcn_readfirstlane(region[2]);
     q.frame = __builtin_amdgcn_readfirstlane(region[3]);
-    q.row = q.pix / (unsigned)PT_ARG(width);
-    q.col = q.pix - q.row * (unsigned)PT_ARG(width);
-    q.sl = q.row / (unsigned)PT_ARG(stripe_rows);
-    q.within = q.row - q.sl * (unsigned)PT_ARG(stripe_rows);
-    const float4* A = reinterpret_cast<const float4*>(region + 16);
-    const unsigned* W = region + 16 + PT_CARRY_RECORDS * 12;
+    pt_queue_locate<LATE>(P, K, q);
     if (lane < n) {
-        const float4 a0 = A[lane], a1 = A[PT_CARRY_RECORDS + lane], a2 = A[2 * PT_CARRY_RECORDS + lane];
-        const unsigned w2 = W[2 * PT_CARRY_RECORDS + lane];
-        s.o = mk3(a0.x, a0.y, a0.z);
-        s.d = mk3(a0.w, a1.x, a1.y);
-        s.mask = mk3(a1.z, a1.w, a2.x);
-        s.L = mk3(a2.y, a2.z, a2.w);
-        s.seed = W[lane];
-        s.lp = W[PT_CARRY_RECORDS + lane];
-        s.fl = w2 & 0xffffu;
-        s.bounce = (int)(w2 >> 16);
+        pt_path_load(pt_carry_slots(region), lane, s);
         alive = true;
     }
 }
@@ -1288,6 +1285,28 @@ PTK_DEV int pt_queue_next(const PtTraceParams& P, unsigned lane, PtWaveQueue& q,
     return pt_queue_refill<LATE>(P, lane, q, empty_mask) ? 1 : 0;
 }
 
+// local row sl * stripe_rows + within -> global row: the image's rows are dealt to the ranks in stripes
+template <bool LATE>
+PTK_DEV unsigned pt_stripe_row(const PtTraceParams& P, pt_kargs_p K, unsigned sl, unsigned within)
+{
+    return (sl * (unsigned)PT_ARG(n_ranks) + (unsigned)PT_ARG(rank)) * (unsigned)PT_ARG(stripe_rows) + within;
+}
+
+// a new sample of (column x, global row grow) -- local pixel lp, frame `frame` of the render -- at bounce 0: seed :308, camera ray :310
+template <bool LATE>
+PTK_DEV void pt_sample_begin(const PtTraceParams& P, pt_kargs_p K, unsigned x, unsigned grow, unsigned lp, unsigned frame, PtPath& s)
+{
+    const unsigned gid = grow * (unsigned)PT_ARG(width) + x;
+    const int f = PT_ARG(frame_begin) - (int)PT_ARG(chunk_f0) + (int)frame;   // (the render's first frame + frame)
+    s.seed = gid + pt_hash_u32((uint32_t)f);
+    pt_generate_ray((int)x, (int)grow, PT_ARG(inv_width), PT_ARG(inv_height), PT_ARG(aspect), PT_CAM_K(K->cam), s.seed, s.o, s.d);
+    s.mask = mk3(1.0f, 1.0f, 1.0f);
+    s.L = mk3(0.0f, 0.0f, 0.0f);
+    s.bounce = 0;
+    s.lp = lp;
+    s.fl = frame;
+}
+
 // FRESH phase: every lane is dead (its path parked); the next (up to) 64 samples of the wave's range start
 // in lanes 0.. at bounce 0 -- seed :308, camera ray :310
 // returns true when all 64 lanes started a primary ray
@@ -1299,26 +1318,17 @@ PTK_DEV bool pt_start_fresh(const PtTraceParams& P, unsigned lane, PtWaveQueue& 
     const unsigned count = avail < 64u ? avail : 64u;
     const unsigned W = (unsigned)PT_ARG(width), SR = (unsigned)PT_ARG(stripe_rows);
     if (lane < count) {
-        const unsigned lp = q.pix + lane;
         // local pixel -> (local row, column): walk from the range's own (row, col); 64 pixels span one or two rows
         // unless the image is narrower than a wave
         unsigned x = q.col + lane, up = 0u;
         while (x >= W) { x -= W; ++up; }
-        unsigned grow = q.row + up;  // local row -> global row (image rows dealt to ranks in stripes)
+        unsigned grow = q.row + up;
         if (PT_ARG(n_ranks) > 1) {
             unsigned sl = q.sl, within = q.within + up;
             while (within >= SR) { within -= SR; ++sl; }
-            grow = (sl * (unsigned)PT_ARG(n_ranks) + (unsigned)PT_ARG(rank)) * SR + within;
+            grow = pt_stripe_row<LATE>(P, K, sl, within);
         }
-        const unsigned gid = grow * W + x;
-        const int frame = PT_ARG(frame_begin) - (int)PT_ARG(chunk_f0) + (int)q.frame;   // (the render's first frame + q.frame)
-        s.seed = gid + pt_hash_u32((uint32_t)frame);                                 // :308
-        pt_generate_ray((int)x, (int)grow, PT_ARG(inv_width), PT_ARG(inv_height), PT_ARG(aspect), PT_CAM_K(K->cam), s.seed, s.o, s.d);      // :310
-        s.mask = mk3(1.0f, 1.0f, 1.0f);
-        s.L = mk3(0.0f, 0.0f, 0.0f);
-        s.bounce = 0;
-        s.lp = lp;
-        s.fl = q.frame;
+        pt_sample_begin<LATE>(P, K, x, grow, q.pix + lane, q.frame, s);
         alive = true;
     }
     q.pix += count;
@@ -1330,6 +1340,45 @@ PTK_DEV bool pt_start_fresh(const PtTraceParams& P, unsigned lane, PtWaveQueue& 
     }
     return count == 64u;
 }
+
+// ---- what both kinds of trace kernel do around their loops ----------------------------------------------------------
+PTK_DEV PtPath pt_path_idle()  // what a lane without a path holds
+{
+    PtPath s;
+    s.o = mk3(0.0f, 0.0f, 0.0f); s.d = mk3(0.0f, 0.0f, 1.0f);
+    s.mask = mk3(1.0f, 1.0f, 1.0f); s.L = mk3(0.0f, 0.0f, 0.0f);
+    s.seed = 0; s.bounce = 0; s.lp = 0; s.fl = 0;
+    return s;
+}
+
+// the wave's number in its workgroup and in the grid, through readfirstlane: to the compiler threadIdx.x >> 6 differs between lanes,
+// and so would everything computed from it (the addresses that use it live in SGPRs)
+PTK_DEV unsigned pt_wave_in_wg() { return (unsigned)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+PTK_DEV unsigned pt_wave() { return blockIdx.x * (PT_TRACE_THREADS / 64) + pt_wave_in_wg(); }
+PTK_DEV uint32_t* pt_carry_region(uint32_t* carry, unsigned wave) { return carry + (size_t)wave * PT_CARRY_STRIDE_DW; }
+
+// this wave's pass-2 tail: 64 key slots at w, then the pending-pair ring; tile: its record tile (TILED mode only)
+PTK_DEV PtTail pt_tail_init(pt_lds_u32* w, unsigned tile, unsigned lane)
+{
+    PtTail tl;
+    tl.keys = (pt_lds_u64*)w;
+    tl.list = w + 128;
+    tl.wr = tl.rd = 0u;
+    tl.kbest = ~0ull; tl.ku = tl.kv = 0.0f;
+    tl.tile = tile;
+    tl.keys[lane] = ~0ull;
+    return tl;
+}
+
+// ---- the LDS of a table-kernel workgroup, in dwords (the bodies, ptk_trace_lds_bytes): the triangle table (LDS_TABLE 1,
+// ntri <= PT_LDS_TRI_MAX), then the waves' pools of parked paths (PT_POOL_DWORDS each), then their pass-2 tails (64 x 8 B keys + PT_TAIL_LIST
+// pairs of 2 B beside the table, of 4 B without), then their record tiles of the current 32-triangle chunk (LDS_TABLE 2: TILED)
+#define PT_LDS_TILE_DW (32u * PT_LDS_TRI_STRIDE)
+template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_tail_dw() { return 128u + (LDS_TABLE == 1 ? PT_TAIL_LIST / 2u : PT_TAIL_LIST); }
+template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_pools(int ntri) { return LDS_TABLE == 1 ? ntri * PT_LDS_TRI_STRIDE : 0; }
+template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_tails(int ntri) { return pt_lds_pools<LDS_TABLE>(ntri) + (PT_TRACE_THREADS / 64) * PT_POOL_DWORDS; }
+template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_tiles(int ntri) { return pt_lds_tails<LDS_TABLE>(ntri) + (PT_TRACE_THREADS / 64) * pt_lds_tail_dw<LDS_TABLE>(); }
+template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_total(int ntri) { return pt_lds_tiles<LDS_TABLE>(ntri) + (LDS_TABLE == 2 ? (PT_TRACE_THREADS / 64) * PT_LDS_TILE_DW : 0u); }
 
 template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
 PTK_DEV void pt_trace_body(const PtTraceParams& P)
@@ -1345,36 +1394,21 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         }
         __syncthreads();
     }
-    // this wave's pool of parked paths, behind the triangle table (ptk_trace_lds_bytes)
-    const unsigned wave_in_wg = (unsigned)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (uniform to the compiler too: the addresses below live in SGPRs)
-    float4* pool = reinterpret_cast<float4*>(pt_lds_tab + (LDS_TABLE == 1 ? ntri * PT_LDS_TRI_STRIDE : 0) + wave_in_wg * PT_POOL_DWORDS);
+    // this wave's pool of parked paths, pass-2 tail and record tile
+    const unsigned wave_in_wg = pt_wave_in_wg();
+    float4* pool = reinterpret_cast<float4*>(pt_lds_tab + pt_lds_pools<LDS_TABLE>(ntri) + wave_in_wg * PT_POOL_DWORDS);
     unsigned pool_n = 0u;                    // parked paths (wave-uniform)
-    // this wave's pass-2 tail: 64 key slots + the pending-pair ring, behind the four pools
-    PtTail tl;
-    {
-        const unsigned tail_dw = 128u + (LDS_TABLE == 1 ? PT_TAIL_LIST / 2u : PT_TAIL_LIST);  // keys + pair ring (2-byte pairs beside the table)
-        const unsigned tails = (LDS_TABLE == 1 ? ntri * PT_LDS_TRI_STRIDE : 0) + (PT_TRACE_THREADS / 64) * PT_POOL_DWORDS;
-        pt_lds_u32* w = (pt_lds_u32*)pt_lds_tab + tails + (threadIdx.x >> 6) * tail_dw;
-        tl.keys = (pt_lds_u64*)w;
-        tl.list = w + 128;
-        tl.wr = tl.rd = 0u;
-        tl.kbest = ~0ull; tl.ku = tl.kv = 0.0f;
-        tl.tile = tails + (PT_TRACE_THREADS / 64) * tail_dw + (threadIdx.x >> 6) * (32u * PT_LDS_TRI_STRIDE);  // (TILED mode only)
-        tl.keys[lane] = ~0ull;
-    }
+    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_lds_tails<LDS_TABLE>(ntri) + (threadIdx.x >> 6) * pt_lds_tail_dw<LDS_TABLE>(),
+                             pt_lds_tiles<LDS_TABLE>(ntri) + (threadIdx.x >> 6) * PT_LDS_TILE_DW, lane);
 
     PtWaveQueue q = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };   // wave-uniform (SGPRs)
     bool alive = false;
-    PtPath s;
-    s.o = mk3(0.0f, 0.0f, 0.0f); s.d = mk3(0.0f, 0.0f, 1.0f);
-    s.mask = mk3(1.0f, 1.0f, 1.0f); s.L = mk3(0.0f, 0.0f, 0.0f);
-    s.seed = 0; s.bounce = 0; s.lp = 0; s.fl = 0;
+    PtPath s = pt_path_idle();
     unsigned n_rays = 0, n_samples = 0, n_carried = 0;   // (n_carried: samples this wave's checkpoints have handed on, PT_STAT_CARRIED)
     // checkpointed launches: resume what the previous launch of the render left in this wave's region
-    // (the wave's number through readfirstlane: to the compiler threadIdx.x >> 6 differs between lanes, and so would everything below)
-    if (blockIdx.x * (PT_TRACE_THREADS / 64) + wave_in_wg < P.carry_in_waves)
-        pt_carry_load<true>(P, P.carry + (size_t)(blockIdx.x * (PT_TRACE_THREADS / 64) + wave_in_wg) * PT_CARRY_STRIDE_DW, lane, s, alive, q, n_rays, n_samples, n_carried);
-    q.g = (blockIdx.x * (PT_TRACE_THREADS / 64) + wave_in_wg) & (PT_QUEUE_SHARDS - 1u);   // the wave's first shard of this launch's queue
+    const unsigned wave = pt_wave();
+    if (wave < P.carry_in_waves) pt_carry_load<true>(P, pt_carry_region(P.carry, wave), lane, s, alive, q, n_rays, n_samples, n_carried);
+    q.g = wave & (PT_QUEUE_SHARDS - 1u);   // the wave's first shard of this launch's queue
 #if PT_STAMPS
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, c_regen = 0, c_loop = 0, c_shade = 0, c_iters = 0, c_steps = 0, c_p1 = 0;
 #endif
@@ -1445,7 +1479,7 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         // (a wave that left the loop because nothing was alive holds nothing: no parked path, no rest of a batch -- an empty checkpoint)
         const pt_kargs_p K = pt_kargs();
         if (K->carry_out != 0u) {
-            pt_carry_store(K->carry + (size_t)(blockIdx.x * (PT_TRACE_THREADS / 64) + wave_in_wg) * PT_CARRY_STRIDE_DW, lane, pool, pool_n, q, n_rays, n_samples, n_carried);
+            pt_carry_store(pt_carry_region(K->carry, wave), lane, pool, pool_n, q, n_rays, n_samples, n_carried);
             return;   // (the tallies went with it)
         }
     }
@@ -1521,6 +1555,14 @@ void pt_trace_tiled_kernel(const PtTraceParams P)
 #define PT_BVH_REFILL 40
 #endif
 
+// ---- the LDS of an LBVH workgroup, in dwords (pt_trace_bvh_body, ptk_trace_bvh_lds_bytes): the table of the triangles outside the
+// hierarchy, the stacks of the workgroup's lanes (PT_BVH_LDS_STACK two-dword entries each), the waves' pass-2 tails (64 x 8 B keys +
+// PT_TAIL_LIST x 4 B pairs each), the 2 KB child-order table nxt
+#define PT_BVH_TAIL_DW (128u + PT_TAIL_LIST)
+__host__ __device__ __forceinline__ unsigned pt_bvh_lds_stacks() { return PT_BVH_BIG_MAX * PT_LDS_TRI_STRIDE; }
+__host__ __device__ __forceinline__ unsigned pt_bvh_lds_tails() { return pt_bvh_lds_stacks() + 2 * PT_BVH_LDS_STACK * PT_TRACE_THREADS; }
+__host__ __device__ __forceinline__ unsigned pt_bvh_lds_nxt() { return pt_bvh_lds_tails() + (PT_TRACE_THREADS / 64) * PT_BVH_TAIL_DW; }
+__host__ __device__ __forceinline__ unsigned pt_bvh_lds_total() { return pt_bvh_lds_nxt() + 2048u / 4u; }
 
 // dead lanes take the next samples of the wave's range, one by one (no coherence to keep here: the search dominates)
 template <bool LATE>
@@ -1536,21 +1578,12 @@ PTK_DEV void pt_regenerate_lanes(const PtTraceParams& P, unsigned lane, PtWaveQu
         if (!alive && rank < take) {
             const unsigned lp = q.pix + rank;
             const unsigned lr = lp / (unsigned)PT_ARG(width), x = lp - lr * (unsigned)PT_ARG(width);
-            unsigned grow = lr;  // local row -> global row (image rows dealt to ranks in stripes)
+            unsigned grow = lr;
             if (PT_ARG(n_ranks) > 1) {
                 const unsigned sl = lr / (unsigned)PT_ARG(stripe_rows);
-                const unsigned within = lr - sl * (unsigned)PT_ARG(stripe_rows);
-                grow = (sl * (unsigned)PT_ARG(n_ranks) + (unsigned)PT_ARG(rank)) * (unsigned)PT_ARG(stripe_rows) + within;
+                grow = pt_stripe_row<LATE>(P, K, sl, lr - sl * (unsigned)PT_ARG(stripe_rows));
             }
-            const unsigned gid = grow * (unsigned)PT_ARG(width) + x;
-            const int frame = PT_ARG(frame_begin) - (int)PT_ARG(chunk_f0) + (int)q.frame;
-            s.seed = gid + pt_hash_u32((uint32_t)frame);                                 // :308
-            pt_generate_ray((int)x, (int)grow, PT_ARG(inv_width), PT_ARG(inv_height), PT_ARG(aspect), PT_CAM_K(K->cam), s.seed, s.o, s.d);      // :310
-            s.mask = mk3(1.0f, 1.0f, 1.0f);
-            s.L = mk3(0.0f, 0.0f, 0.0f);
-            s.bounce = 0;
-            s.lp = lp;
-            s.fl = q.frame;
+            pt_sample_begin<LATE>(P, K, x, grow, lp, q.frame, s);
             alive = true;
         }
         q.pix += take;
@@ -1813,8 +1846,7 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
     const unsigned lane = pt_lane_id();
     const int ntri = P.ntri;
     const unsigned n_recs = (unsigned)P.bvh_records;
-    // LDS: the table of the triangles outside the hierarchy (pass 2 fetches its records per lane: pt_fetch_rec), the
-    // stacks of the workgroup's 256 lanes, then every wave's pass-2 tail (ptk_trace_bvh_lds_bytes)
+    // LDS (pt_bvh_lds_*): the table of the triangles outside the hierarchy (pass 2 fetches its records per lane: pt_fetch_rec)
     {
         const float* g = reinterpret_cast<const float*>(P.bigtab);
         for (int k = (int)threadIdx.x; k < P.nbig * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
@@ -1823,9 +1855,8 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
         }
     }
     // which child of a group comes next: nxt[oct << 8 | hits] = the slot s among the hits (by slot) with the largest
-    // s ^ oct -- the octant nearest to where the ray comes from (2 KB, after the tails)
-    pt_lds_u8* nxt = (pt_lds_u8*)((pt_lds_u32*)pt_lds_tab + PT_BVH_BIG_MAX * PT_LDS_TRI_STRIDE + 2 * PT_BVH_LDS_STACK * PT_TRACE_THREADS +
-                                  (PT_TRACE_THREADS / 64) * (128u + PT_TAIL_LIST));
+    // s ^ oct -- the octant nearest to where the ray comes from
+    pt_lds_u8* nxt = (pt_lds_u8*)((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_nxt());
     for (unsigned k = threadIdx.x; k < 2048u; k += PT_TRACE_THREADS) {
         const unsigned o = k >> 8, h = k & 255u;
         unsigned best = 0u, bp = 0u;
@@ -1835,28 +1866,15 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
     }
     __syncthreads();
     // stack entry e of this lane: stk[2 e * PT_TRACE_THREADS] = base, stk[(2 e + 1) * PT_TRACE_THREADS] = masks
-    pt_lds_u32* stk = (pt_lds_u32*)pt_lds_tab + PT_BVH_BIG_MAX * PT_LDS_TRI_STRIDE + threadIdx.x;
+    pt_lds_u32* stk = (pt_lds_u32*)pt_lds_tab + pt_bvh_lds_stacks() + threadIdx.x;
     unsigned ovf[2 * (PT_BVH_STACK - PT_BVH_LDS_STACK)];
-    PtTail tl;
-    {
-        pt_lds_u32* w = (pt_lds_u32*)pt_lds_tab + PT_BVH_BIG_MAX * PT_LDS_TRI_STRIDE + 2 * PT_BVH_LDS_STACK * PT_TRACE_THREADS +
-                        (threadIdx.x >> 6) * (128u + PT_TAIL_LIST);
-        tl.keys = (pt_lds_u64*)w;
-        tl.list = w + 128;
-        tl.wr = tl.rd = 0u;
-        tl.kbest = ~0ull; tl.ku = tl.kv = 0.0f;
-        tl.tile = 0u;
-        tl.keys[lane] = ~0ull;
-    }
+    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_tails() + (threadIdx.x >> 6) * PT_BVH_TAIL_DW, 0u, lane);
     pt_const_f32p bigT = (pt_const_f32p)(const float*)P.bigtab;
 
-    PtWaveQueue q = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, (blockIdx.x * (PT_TRACE_THREADS / 64) + (unsigned)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) & (PT_QUEUE_SHARDS - 1u) };
+    PtWaveQueue q = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, pt_wave() & (PT_QUEUE_SHARDS - 1u) };
     bool alive = false;  // the lane holds a path
     bool trav = false;   // ... whose closest-hit search is in progress
-    PtPath s;
-    s.o = mk3(0.0f, 0.0f, 0.0f); s.d = mk3(0.0f, 0.0f, 1.0f);
-    s.mask = mk3(1.0f, 1.0f, 1.0f); s.L = mk3(0.0f, 0.0f, 0.0f);
-    s.seed = 0; s.bounce = 0; s.lp = 0; s.fl = 0;
+    PtPath s = pt_path_idle();
     unsigned n_rays = 0, n_samples = 0, n_carried = 0;
     // checkpointed launches (PtTraceParams::carry), as in the table kernels: a launch whose queue has handed out its last batch stops
     // starting searches -- the lanes still searching finish THAT search (a hundred node steps, not the up to sixteen bounces a path has
@@ -1867,10 +1885,10 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
     bool parked = false;    // the lane's path is between two searches (shaded; its next search not begun): what a checkpoint holds
     {
         const pt_kargs_p K = pt_kargs();
-        const unsigned wave = blockIdx.x * (PT_TRACE_THREADS / 64) + (unsigned)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const unsigned wave = pt_wave();
         if (wave < K->carry_in_waves) {
             const unsigned shard = q.g;
-            pt_carry_load<true>(P, K->carry + (size_t)wave * PT_CARRY_STRIDE_DW, lane, s, alive, q, n_rays, n_samples, n_carried);
+            pt_carry_load<true>(P, pt_carry_region(K->carry, wave), lane, s, alive, q, n_rays, n_samples, n_carried);
             q.g = shard;
             parked = alive;
         }
@@ -1973,8 +1991,7 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
         // travel with it either way)
         const pt_kargs_p K = pt_kargs();
         if (K->carry_out != 0u) {
-            const unsigned wave = blockIdx.x * (PT_TRACE_THREADS / 64) + (unsigned)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-            pt_carry_store_lanes(K->carry + (size_t)wave * PT_CARRY_STRIDE_DW, lane, s, alive, q, n_rays, n_samples, n_carried);
+            pt_carry_store_lanes(pt_carry_region(K->carry, pt_wave()), lane, s, alive, q, n_rays, n_samples, n_carried);
             return;
         }
     }
@@ -2373,33 +2390,18 @@ hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s)
 
 hipError_t ptk_trace(const PtTraceParams& p, int num_blocks, bool det_bounded, int quads, bool bvh, bool tally, hipStream_t s)
 {
-    if (bvh) {
-        const size_t lds = ptk_trace_bvh_lds_bytes();
-        const bool bq = det_bounded && quads == 3;
-        if (tally) {
-            if (bq) hipLaunchKernelGGL((pt_trace_bvh_kernel<true, true, 3>), dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-            else if (det_bounded) hipLaunchKernelGGL((pt_trace_bvh_kernel<true, true, 0>), dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-            else hipLaunchKernelGGL((pt_trace_bvh_kernel<false, true, 0>), dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-        } else {
-            if (bq) hipLaunchKernelGGL((pt_trace_bvh_kernel<true, false, 3>), dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-            else if (det_bounded) hipLaunchKernelGGL((pt_trace_bvh_kernel<true, false, 0>), dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-            else hipLaunchKernelGGL((pt_trace_bvh_kernel<false, false, 0>), dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-        }
-        return hipGetLastError();
-    }
-    if (p.ntri <= PT_LDS_TRI_MAX) {
-        const size_t lds = ptk_trace_lds_bytes(p.ntri);
-        if (det_bounded && quads == 3)
-            hipLaunchKernelGGL((pt_trace_kernel<true, 1, 3>), dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-        else if (det_bounded)
-            hipLaunchKernelGGL((pt_trace_kernel<true, 1, 0>), dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-        else
-            hipLaunchKernelGGL((pt_trace_kernel<false, 1, 0>), dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-    } else {
-        const size_t lds = ptk_trace_lds_bytes(p.ntri);
-        if (det_bounded) hipLaunchKernelGGL(pt_trace_tiled_kernel<true>, dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-        else hipLaunchKernelGGL(pt_trace_tiled_kernel<false>, dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
-    }
+    // (the order the instantiations appear in is the order of the kernels in the code object)
+    const bool q3 = quads == 3;
+    void (*kernel)(const PtTraceParams);
+    if (bvh)
+        kernel = tally ? (det_bounded ? (q3 ? pt_trace_bvh_kernel<true, true, 3> : pt_trace_bvh_kernel<true, true, 0>) : pt_trace_bvh_kernel<false, true, 0>)
+                       : (det_bounded ? (q3 ? pt_trace_bvh_kernel<true, false, 3> : pt_trace_bvh_kernel<true, false, 0>) : pt_trace_bvh_kernel<false, false, 0>);
+    else if (p.ntri <= PT_LDS_TRI_MAX)
+        kernel = det_bounded ? (q3 ? pt_trace_kernel<true, 1, 3> : pt_trace_kernel<true, 1, 0>) : pt_trace_kernel<false, 1, 0>;
+    else
+        kernel = det_bounded ? pt_trace_tiled_kernel<true> : pt_trace_tiled_kernel<false>;
+    const size_t lds = bvh ? ptk_trace_bvh_lds_bytes() : ptk_trace_lds_bytes(p.ntri);
+    hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
     return hipGetLastError();
 }
 
@@ -2451,18 +2453,12 @@ hipError_t ptk_fill_i32(int32_t* dst, int32_t value, int n, hipStream_t s)
 
 size_t ptk_trace_lds_bytes(int ntri)
 {
-    const size_t table = ntri <= PT_LDS_TRI_MAX ? (size_t)ntri * PT_LDS_TRI_STRIDE * sizeof(float) : 0;
-    // per wave: the pool of parked paths (PT_POOL x 60 B) + the pass-2 tail (64 x 8 B keys, PT_TAIL_LIST x 2 or 4 B pairs)
-    // + for scenes too large for the table, the record tile of the current chunk (32 x 48 B)
-    const size_t tile = ntri <= PT_LDS_TRI_MAX ? 0 : (size_t)32 * PT_LDS_TRI_STRIDE * sizeof(float);
-    const size_t ring = ntri <= PT_LDS_TRI_MAX ? PT_TAIL_LIST * 2 : PT_TAIL_LIST * 4;
-    return table + (size_t)(PT_TRACE_THREADS / 64) * (PT_POOL_DWORDS * 4 + 64 * 8 + ring + tile);
+    return (size_t)(ntri <= PT_LDS_TRI_MAX ? pt_lds_total<1>(ntri) : pt_lds_total<2>(ntri)) * sizeof(float);
 }
 
 size_t ptk_trace_bvh_lds_bytes(void)
 {
-    // the big-triangle table + the 256 lanes' stacks + per wave the pass-2 tail (64 x 8 B keys, PT_TAIL_LIST x 4 B pairs)
-    return (size_t)PT_BVH_BIG_MAX * PT_LDS_TRI_STRIDE * 4 + (size_t)2 * PT_BVH_LDS_STACK * PT_TRACE_THREADS * 4 + (size_t)(PT_TRACE_THREADS / 64) * (64 * 8 + PT_TAIL_LIST * 4) + 2048;
+    return (size_t)pt_bvh_lds_total() * sizeof(float);
 }
 
 int ptk_trace_bvh_blocks_per_cu(void)
