@@ -348,6 +348,39 @@ int pt_render_frames_camera(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t 
                             const pt_render_params* params, const pt_camera* cam,
                             pt_buffer_t stats /* may be NULL */, pt_event_t ev);
 
+/* ---- batched ray queries -----------------------------------------------------------------------------------------
+ * The renderer's closest-hit search -- intersectWorld (GenerateColors.cl:137-154) over the reference's exact triangle test
+ * (:96-125), ties to the lower index -- for rays of the caller's.  No Adl entry point has a counterpart: the reference reaches
+ * the search only from inside its kernel.  The search is chosen exactly as for renders (PT_OPT_ACCEL, PT_OPT_QUAD_FILTER, the
+ * scene's determinant bound) and uses the handle's prepared scene: querying the triangle buffer a render uses neither prepares
+ * it again nor rebuilds its LBVH (PT_OPT_BVH_BUILD_COUNT), and a query never moves the pass-1 filter's anchor (the eye of the
+ * last render).  Work goes to the handle's stream in call order, behind the renders in flight, and is asynchronous: `ev` (may
+ * be NULL) completes with it.  Once the scene is prepared, a query neither allocates nor waits for the device.  An LBVH
+ * search cut short raises the word behind PT_ERR_TRAVERSAL, reported as for renders.  Argument errors (PT_ERR_INVALID,
+ * PT_ERR_RANGE) are returned before anything is enqueued; buffers are 16-byte aligned, rays and results do not overlap. */
+typedef struct pt_ray {      /* 32 bytes: the arguments of getRay (GenerateColors.cl:73-77) */
+    float origin[3];
+    float tmax;              /* a hit counts at 0 < t < min(tmax, 1e20); tmax NaN or <= 0: the ray misses */
+    float dir[3];            /* any length: normalised on the device exactly as getRay does; t is a distance */
+    int32_t reserved;
+} pt_ray;
+typedef struct pt_hit {      /* 48 bytes */
+    float t; int32_t tri; float u, v;   /* miss: t = +inf, tri = -1, u = v = 0 (and p = n = 0, material = -1) */
+    float p[3]; int32_t material;       /* p = origin + normalize(dir) * t (:127); material = the triangle's id field */
+    float n[3]; int32_t reserved;       /* the HitRecord's normal, normalize(N u + N v + N w), N = cross(e2, e1) (:123, :128-130) */
+} pt_hit;
+enum { PT_QUERY_CLOSEST = 0 /* one pt_hit per ray */, PT_QUERY_OCCLUDED = 1 /* one int32 per ray: 1 if the closest query hits, else 0 */ };
+/* num_rays rays of `rays` (pt_ray) -> `out`, for the first num_triangles records of `triangles` (0: every ray misses) */
+int pt_intersect_rays(pt_device_t dev, pt_buffer_t triangles, int num_triangles, pt_buffer_t rays,
+                      pt_buffer_t out, size_t num_rays, int mode, pt_event_t ev);
+/* width x height rays into `rays`: ray gid = y * width + x is the primary ray the renderer traces for pixel gid in frame
+ * `frame` (seed gid + hash(frame), :305-308; the camera's jitter and expression, :278-287) seen from cam (NULL = the
+ * reference's; validated as by pt_render_frames_camera).  origin = the eye, tmax = 1e20, dir = the vector the reference passes
+ * to getRay at :287, normalised once: pt_intersect_rays normalises it again as getRay does, so a query of these rays traces the
+ * renderer's primary rays bit for bit. */
+int pt_camera_rays(pt_device_t dev, const pt_camera* cam /* NULL = reference */, int width, int height,
+                   int frame, pt_buffer_t rays, pt_event_t ev);
+
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.
  * pt_profile_query synchronises the stream and returns the summed duration and launch count

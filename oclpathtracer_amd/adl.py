@@ -72,9 +72,10 @@ class Device:
     PROFILE_NON = 0
     PROFILE_RETURN_TIME = 1 << 1
 
-    def __init__(self, handle):
+    def __init__(self, handle, device_idx: int = 0):
         self._h = handle
         self.m_type = TYPE_HIP
+        self.m_deviceIdx = int(device_idx)   # the HIP ordinal (Config::m_deviceIdx): torch's cuda:<m_deviceIdx>
         self._lib = shim.load()
 
     # -- validity / info (Adl/Adl.h:153-177)
@@ -174,7 +175,7 @@ class DeviceUtils:
         cfg = cfg or Config()
         out = ctypes.c_void_p()
         shim.check(shim.load().pt_device_create(cfg.m_deviceIdx, ctypes.byref(out)))
-        return Device(out.value)
+        return Device(out.value, cfg.m_deviceIdx)
 
     @staticmethod
     def deallocate(device: Device) -> None:

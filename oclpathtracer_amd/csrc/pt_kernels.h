@@ -222,6 +222,21 @@ hipError_t ptk_fill_i32(int32_t* dst, int32_t value, int n, hipStream_t s);
 hipError_t ptk_math(const float* in, float* out, int n, hipStream_t s);
 // the fold kernel's short forms against the literal operations (pt_fold_check_kernel); out: 6 counters
 hipError_t ptk_fold_check(unsigned long long* out, int mode, unsigned first, unsigned long long count, hipStream_t s);
+// batched ray queries (pt_intersect_rays): t carries the search -- the prepared scene (tris, ntri), the filter of the table the
+// two-pass search runs over (quad_delta1 .. p1_hi, its anchor in cam.eye), the LBVH (bvh .. nbig, bvh_flags, bvh_stack_limit);
+// the other fields of t are not read
+struct PtQueryParams {
+    PtTraceParams t;
+    const float4* rays;   // [nrays] pt_ray: origin xyz tmax | dir xyz reserved (two float4)
+    void* out;            // [nrays] pt_hit (three float4), or int32 when occluded
+    uint32_t nrays;
+    int32_t occluded;
+};
+// bvh_blocks: the persistent grid of the LBVH kernel (CUs x ptk_query_bvh_blocks_per_cu)
+hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s);
+int ptk_query_bvh_blocks_per_cu(void);
+// rays[2 gid], rays[2 gid + 1] = the pt_ray of pixel gid, frame `frame` (the renderer's sample start) for the camera cam
+hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s);
 // dynamic LDS of a trace workgroup (pt_kernels.hip: pt_lds_total, pt_bvh_lds_total)
 size_t ptk_trace_lds_bytes(int ntri);
 int ptk_trace_blocks_per_cu(int ntri);

@@ -200,7 +200,8 @@ struct PtCam { f3 eye, view, hol, up; float angle; };
 #define PT_CAM_K(c) PtCam{ mk3((c).eye[0], (c).eye[1], (c).eye[2]), mk3((c).view[0], (c).view[1], (c).view[2]), \
                            mk3((c).hol[0], (c).hol[1], (c).hol[2]), mk3((c).up[0], (c).up[1], (c).up[2]), (c).angle }
 
-PTK_DEV void pt_camera_ray(float x, float y, float inv_w, float inv_h, float aspect, const PtCam& c, f3& org, f3& dir_out)
+// the ray of image point (x, y) as the reference hands it to getRay at :287: `aim` is normalised ONCE (getRay normalises it again)
+PTK_DEV void pt_camera_aim(float x, float y, float inv_w, float inv_h, float aspect, const PtCam& c, f3& org, f3& aim)
 {
     const float angle = c.angle;
     const f3 eye = c.eye;
@@ -216,13 +217,27 @@ PTK_DEV void pt_camera_ray(float x, float y, float inv_w, float inv_h, float asp
     f3 dir = normalize3(d);
     f3 pointAimed = add3(eye, scale3(dir, 4.0f));
     org = eye;
-    dir_out = normalize3(normalize3(sub3(pointAimed, eye)));  // :287 then getRay's own normalize (:75)
+    aim = normalize3(sub3(pointAimed, eye));  // :287
+}
+
+PTK_DEV void pt_camera_ray(float x, float y, float inv_w, float inv_h, float aspect, const PtCam& c, f3& org, f3& dir_out)
+{
+    f3 aim;
+    pt_camera_aim(x, y, inv_w, inv_h, aspect, c, org, aim);
+    dir_out = normalize3(aim);  // getRay's own normalize (:75)
+}
+
+// the jittered image point of pixel (xc, yc): :278-279, two draws, x first
+PTK_DEV void pt_pixel_jitter(int xc, int yc, uint32_t& seed, float& x, float& y)
+{
+    x = (float)xc + pt_random_float(seed) - 0.5f;
+    y = (float)yc + pt_random_float(seed) - 0.5f;
 }
 
 PTK_DEV void pt_generate_ray(int xc, int yc, float inv_w, float inv_h, float aspect, const PtCam& c, uint32_t& seed, f3& org, f3& dir_out)
 {
-    float x = (float)xc + pt_random_float(seed) - 0.5f;  // :278-279: two draws, x first
-    float y = (float)yc + pt_random_float(seed) - 0.5f;
+    float x, y;
+    pt_pixel_jitter(xc, yc, seed, x, y);
     pt_camera_ray(x, y, inv_w, inv_h, aspect, c, org, dir_out);
 }
 
@@ -2350,6 +2365,222 @@ __global__ void pt_fill_i32_kernel(int32_t* dst, int32_t value, int n)
 }
 
 // ------------------------------------------------------------------------------------------
+// batched ray queries (pt_intersect_rays, pt_camera_rays)
+// ------------------------------------------------------------------------------------------
+// A query ray is the pair of arguments of getRay (GenerateColors.cl:73-77): the direction is normalised here as getRay does it,
+// the search is the renderer's own (pt_intersect_two_pass over the prepared scene, or the big-triangle table and then the LBVH:
+// pt_bvh_step / pt_bvh_round), and the HitRecord (:126-130) is pt_shade's deferred one.  Nothing here is new arithmetic.
+// The caller's tmax (pt_ray::tmax) starts the search in place of the reference's 1e20 (:141): a hit counts at
+// 0 < t < min(tmax, 1e20); a tmax that is NaN or <= 0 searches nothing and misses.  Strictness: pass 2 and the tail merge of the
+// two-pass search compare t < tmax as the reference does, but the LBVH's ring keeps a 64-bit (t, index) minimum whose incumbent is
+// (tmax, no triangle) -- a candidate AT tmax beats that key.  The renderer never meets it (its tmax is 1e20, which the exact
+// test already excludes); a query does, so the result is taken as a hit only when t < tmax as well (pt_query_store).  The
+// minimum over {t <= tmax} is below tmax exactly when the reference's strict winner exists, and then it is that winner.
+struct PtQueryRay {
+    f3 o, d;      // origin, normalize(dir) (:75)
+    float tlim;   // min(tmax, 1e20); 0 when the ray is not live, so that no t counts
+    bool live;    // tmax > 0 (false for NaN): the search runs
+};
+
+PTK_DEV PtQueryRay pt_query_load(const float4* rays, unsigned i)
+{
+    const float4 a = rays[2 * (size_t)i], b = rays[2 * (size_t)i + 1];   // origin xyz tmax | dir xyz reserved
+    PtQueryRay r;
+    r.o = mk3(a.x, a.y, a.z);
+    r.d = normalize3(mk3(b.x, b.y, b.z));
+    r.live = a.w > 0.0f;
+    r.tlim = !r.live ? 0.0f : (a.w < 1e20f ? a.w : 1e20f);
+    return r;
+}
+
+PTK_DEV PtQueryRay pt_query_idle()   // what a lane without a ray holds
+{
+    PtQueryRay r;
+    r.o = mk3(0.0f, 0.0f, 0.0f); r.d = mk3(0.0f, 0.0f, 1.0f);
+    r.tlim = 0.0f; r.live = false;
+    return r;
+}
+
+// result i: a pt_hit (three 16-byte stores) or, for occlusion queries, 1 / 0
+PTK_DEV void pt_query_store(const PtQueryParams& Q, unsigned i, const PtQueryRay& r, float t, float u, float v, int hidx)
+{
+    const bool hit = (hidx >= 0) & (t < r.tlim);
+    if (Q.occluded) {
+        reinterpret_cast<int32_t*>(Q.out)[i] = hit ? 1 : 0;
+        return;
+    }
+    float4* o = reinterpret_cast<float4*>(Q.out) + 3 * (size_t)i;
+    if (!hit) {
+        o[0] = make_float4(__builtin_inff(), __int_as_float(-1), 0.0f, 0.0f);
+        o[1] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+        o[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    // pt_shade's deferred HitRecord (:127-130)
+    const float4 nid = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(Q.t.tris + hidx) + 12);
+    const f3 N = mk3(nid.x, nid.y, nid.z);
+    const f3 p = add3(r.o, scale3(r.d, t));
+    const float w = 1.0f - u - v;
+    const f3 n = normalize3(add3(add3(scale3(N, u), scale3(N, v)), scale3(N, w)));
+    o[0] = make_float4(t, __int_as_float(hidx), u, v);
+    o[1] = make_float4(p.x, p.y, p.z, nid.w);   // material: the triangle's id field, as stored
+    o[2] = make_float4(n.x, n.y, n.z, 0.0f);
+}
+
+// LDS of a brute-force query workgroup, in dwords: the table (LDS_TABLE 1), the waves' pass-2 tails, their record tiles (LDS_TABLE 2)
+// -- the trace kernel's layout without the pools of parked paths
+template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_query_lds_tails(int ntri) { return pt_lds_pools<LDS_TABLE>(ntri); }
+template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_query_lds_tiles(int ntri) { return pt_query_lds_tails<LDS_TABLE>(ntri) + (PT_TRACE_THREADS / 64) * pt_lds_tail_dw<LDS_TABLE>(); }
+template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_query_lds_total(int ntri) { return pt_query_lds_tiles<LDS_TABLE>(ntri) + (LDS_TABLE == 2 ? (PT_TRACE_THREADS / 64) * PT_LDS_TILE_DW : 0u); }
+
+// brute force: one wave = 64 consecutive rays, one search (the search is wave-uniform over the triangles: every lane finishes
+// together, so there is nothing to refill)
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_query_kernel(const PtQueryParams Q)
+{
+    const PtTraceParams& P = Q.t;
+    const unsigned lane = pt_lane_id();
+    const int ntri = P.ntri;
+    if (LDS_TABLE == 1) {
+        const float* g = reinterpret_cast<const float*>(P.tris);
+        for (int k = (int)threadIdx.x; k < ntri * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
+            const int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
+            pt_lds_tab[k] = g[tri * 16 + w];
+        }
+        __syncthreads();
+    }
+    const unsigned wave_in_wg = pt_wave_in_wg();
+    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_query_lds_tails<LDS_TABLE>(ntri) + wave_in_wg * pt_lds_tail_dw<LDS_TABLE>(),
+                             pt_query_lds_tiles<LDS_TABLE>(ntri) + wave_in_wg * PT_LDS_TILE_DW, lane);
+    const unsigned i = pt_wave() * 64u + lane;
+    const bool act = i < Q.nrays;
+    const PtQueryRay r = act ? pt_query_load(Q.rays, i) : pt_query_idle();
+    float tmax = r.tlim, hu = 0.0f, hv = 0.0f;
+    int hidx = -1;
+    // (the filter's anchor is the table's, P.cam.eye: a ray far from it fails the tame check and keeps every triangle)
+    pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, r.o, r.d, r.live, tmax, hu, hv, hidx,
+                                                         P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi,
+                                                         mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]), tl, lane);
+    if (act) pt_query_store(Q, i, r, tmax, hu, hv, hidx);
+}
+
+// LBVH: a persistent grid; wave w takes the groups of 64 consecutive rays w, w + W, w + 2W ... (W = the grid's waves) and, like the
+// LBVH trace kernel, refills its finished lanes with the next rays as soon as no more than PT_BVH_REFILL lanes still traverse
+// (pt_regenerate_lanes), so that a wave does not wait for its slowest ray.  Its LDS is the trace kernel's (pt_bvh_lds_*).
+template <bool DET_BOUNDED, int BIGQ>
+__global__ __launch_bounds__(PT_TRACE_THREADS) PT_BVH_WAVES_ATTR
+void pt_query_bvh_kernel(const PtQueryParams Q)
+{
+    const PtTraceParams& P = Q.t;
+    const unsigned lane = pt_lane_id();
+    const int ntri = P.ntri;
+    const unsigned n_recs = (unsigned)P.bvh_records;
+    {
+        const float* g = reinterpret_cast<const float*>(P.bigtab);
+        for (int k = (int)threadIdx.x; k < P.nbig * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
+            const int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
+            pt_lds_tab[k] = g[tri * 16 + w];
+        }
+    }
+    pt_lds_u8* nxt = (pt_lds_u8*)((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_nxt());
+    for (unsigned k = threadIdx.x; k < 2048u; k += PT_TRACE_THREADS) {
+        const unsigned o = k >> 8, h = k & 255u;
+        unsigned best = 0u, bp = 0u;
+        for (unsigned sl = 0; sl < 8u; ++sl)
+            if (((h >> sl) & 1u) && ((sl ^ o) >= bp)) { bp = sl ^ o; best = sl; }
+        nxt[k] = (unsigned char)best;
+    }
+    __syncthreads();
+    pt_lds_u32* stk = (pt_lds_u32*)pt_lds_tab + pt_bvh_lds_stacks() + threadIdx.x;
+    unsigned ovf[2 * (PT_BVH_STACK - PT_BVH_LDS_STACK)];
+    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_tails() + (threadIdx.x >> 6) * PT_BVH_TAIL_DW, 0u, lane);
+    pt_const_f32p bigT = (pt_const_f32p)(const float*)P.bigtab;
+    const f3 anchor = mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]);
+
+    // the wave's rays (wave-uniform): [next, gend) of its current group; groups start at multiples of 64
+    const unsigned stride = gridDim.x * (PT_TRACE_THREADS / 64) * 64u;
+    const unsigned nrays = Q.nrays;
+    unsigned next = pt_wave() * 64u;
+    unsigned gend = next + 64u < nrays ? next + 64u : nrays;
+    bool alive = false;   // the lane holds a ray whose result is not stored yet
+    bool trav = false;    // ... and its search is in progress
+    unsigned ray = 0u;
+    PtQueryRay r = pt_query_idle();
+    PtBvhLane L;
+    L.tmax = 1e20f; L.hu = 0.0f; L.hv = 0.0f; L.hidx = -1;
+    L.gbase = L.gm = L.oct = 0u; L.sp = 0; L.ix = L.iy = L.iz = 0.0f; L.budget = 0u;
+    unsigned c_nodes = 0, c_leaves = 0, c_maxsp = 0;   // (pt_bvh_step's tallies: not kept)
+    unsigned long long c_steps = 0, c_tsteps = 0;
+
+    for (;;) {
+        if ((unsigned)__popcll(__ballot(trav)) <= (unsigned)PT_BVH_REFILL) {
+            // the pending pairs first: a lane with no nodes left has its closest hit only once its leaves are tested
+            if (tl.wr != tl.rd) pt_bvh_round<DET_BOUNDED>(P, L, tl, tl.wr - tl.rd, lane, r.o, r.d, n_recs);
+            if (alive && !trav) {
+                pt_query_store(Q, ray, r, L.tmax, L.hu, L.hv, L.hidx);
+                alive = false;
+            }
+            bool fresh = false;
+            for (unsigned long long need = __ballot(!alive); need != 0ull && next < nrays; need = __ballot(!alive)) {
+                const unsigned n_need = (unsigned)__popcll(need), avail = gend - next;
+                const unsigned take = n_need < avail ? n_need : avail;
+                const unsigned rank = pt_mbcnt(need);
+                if (!alive && rank < take) {
+                    ray = next + rank;
+                    r = pt_query_load(Q.rays, ray);
+                    alive = true;
+                    fresh = true;
+                }
+                next += take;
+                if (next == gend) {   // the wave's next group
+                    next = ((gend - 1u) & ~63u) + stride;
+                    next = next < nrays ? next : nrays;
+                    gend = next + 64u < nrays ? next + 64u : nrays;
+                }
+            }
+            // every fresh lane drops the previous ray's result (a fresh ray that searches nothing is stored as a miss at the next refill)
+            if (fresh) { L.tmax = r.tlim; L.hu = 0.0f; L.hv = 0.0f; L.hidx = -1; }
+            const bool start = fresh && r.live;
+            if (__ballot(start) != 0ull) {
+                if (P.nbig > 0) {
+                    // the triangles outside the hierarchy, by the two-pass search (its tail shares the key slots with pt_bvh_round and
+                    // expects them empty: the ring has just been flushed)
+                    int hp = -1;
+                    tl.keys[lane] = ~0ull;
+                    pt_intersect_two_pass<DET_BOUNDED, 1, (DET_BOUNDED ? BIGQ : 0)>(bigT, P.bigtab, P.nbig, r.o, r.d, start, L.tmax, L.hu, L.hv, hp,
+                                                                                      P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi,
+                                                                                      anchor, tl, lane);
+                    if (start && hp >= 0) L.hidx = P.bigidx[hp];
+                }
+                if (start) {
+                    pt_bvh_lane_start(L, r.d, ntri);
+                    trav = true;
+                }
+            }
+            if (__ballot(alive) == 0ull) break;
+        }
+        pt_bvh_step<DET_BOUNDED, false>(P, L, trav, r.o, r.d, stk, ovf, nxt, tl, lane, n_recs, c_nodes, c_leaves, c_steps, c_tsteps, c_maxsp);
+    }
+}
+
+// ray gid of frame `frame` as the renderer traces it (seed :305-308, pixel jitter, the camera's expression), with the direction
+// getRay receives at :287 -- a query normalises it once more, as getRay does, and traces the renderer's primary ray bit for bit
+__global__ __launch_bounds__(256) void pt_camera_rays_kernel(const PtCamera cam, int width, unsigned npix, float inv_w, float inv_h, float aspect,
+                                                             int frame, float4* __restrict__ rays)
+{
+    const unsigned gid = blockIdx.x * 256u + threadIdx.x;
+    if (gid >= npix) return;
+    uint32_t seed = gid + pt_hash_u32((uint32_t)frame);
+    const unsigned y = gid / (unsigned)width, x = gid - y * (unsigned)width;
+    float fx, fy;
+    pt_pixel_jitter((int)x, (int)y, seed, fx, fy);
+    f3 org, aim;
+    pt_camera_aim(fx, fy, inv_w, inv_h, aspect, PT_CAM_K(cam), org, aim);
+    rays[2 * (size_t)gid] = make_float4(org.x, org.y, org.z, 1e20f);
+    rays[2 * (size_t)gid + 1] = make_float4(aim.x, aim.y, aim.z, 0.0f);
+}
+
+// ------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------
 hipError_t ptk_prep_triangles(const PtRawTriangle* raw, PtPrepTriangle* out, int ntri, unsigned int* det_bound_bits,
@@ -2477,4 +2708,48 @@ int ptk_trace_blocks_per_cu(int ntri)
                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pt_trace_tiled_kernel<true>, PT_TRACE_THREADS, ptk_trace_lds_bytes(ntri));
     if (e != hipSuccess || nb < 1) nb = 2;
     return nb;
+}
+
+// ---- batched ray queries --------------------------------------------------------------------------------------------------
+// (instantiated here, after every trace kernel: the existing kernels keep their place in the code object)
+hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s)
+{
+    if (q.nrays == 0) return hipSuccess;
+    const bool q3 = quads == 3;
+    const unsigned groups = (q.nrays + 63u) / 64u;   // 64 rays per wave
+    const unsigned wg_waves = PT_TRACE_THREADS / 64;
+    void (*kernel)(const PtQueryParams);
+    unsigned blocks = (groups + wg_waves - 1u) / wg_waves;
+    size_t lds;
+    if (bvh) {
+        kernel = det_bounded ? (q3 ? pt_query_bvh_kernel<true, 3> : pt_query_bvh_kernel<true, 0>) : pt_query_bvh_kernel<false, 0>;
+        if (bvh_blocks > 0 && blocks > (unsigned)bvh_blocks) blocks = (unsigned)bvh_blocks;   // persistent: what the chip holds
+        lds = ptk_trace_bvh_lds_bytes();
+    } else if (q.t.ntri <= PT_LDS_TRI_MAX) {
+        kernel = det_bounded ? (q3 ? pt_query_kernel<true, 1, 3> : pt_query_kernel<true, 1, 0>) : pt_query_kernel<false, 1, 0>;
+        lds = (size_t)pt_query_lds_total<1>(q.t.ntri) * sizeof(float);
+    } else {
+        kernel = det_bounded ? pt_query_kernel<true, 2, 0> : pt_query_kernel<false, 2, 0>;
+        lds = (size_t)pt_query_lds_total<2>(q.t.ntri) * sizeof(float);
+    }
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(PT_TRACE_THREADS), lds, s, q);
+    return hipGetLastError();
+}
+
+int ptk_query_bvh_blocks_per_cu(void)
+{
+    int nb = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pt_query_bvh_kernel<true, 3>, PT_TRACE_THREADS, ptk_trace_bvh_lds_bytes());
+    if (e != hipSuccess || nb < 1) nb = 2;
+    return nb;
+}
+
+hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s)
+{
+    const unsigned npix = (unsigned)width * (unsigned)height;
+    if (npix == 0) return hipSuccess;
+    // the renderer's per-image constants (pt_shim.hip: trace_params)
+    const float inv_w = 1.0f / (float)width, inv_h = 1.0f / (float)height, aspect = (float)width / (float)height;
+    hipLaunchKernelGGL(pt_camera_rays_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, s, cam, width, npix, inv_w, inv_h, aspect, frame, rays);
+    return hipGetLastError();
 }

@@ -122,6 +122,7 @@ struct pt_device_s {
     int* bigidx;
     int nbig;
     int bvh_blocks_per_cu;
+    int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query kernel (pt_intersect_rays)
     bool bvh_valid;
     unsigned int* det_bound_dev;  // PT_PREP_WORDS device words written by the prep kernel
     // fused-render workspace: the STREAMING renderer.  A render walks its frames in chunks of S frames (as many as a ring slot
@@ -357,6 +358,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     }
     d->blocks_per_cu = ptk_trace_blocks_per_cu(36);
     d->bvh_blocks_per_cu = ptk_trace_bvh_blocks_per_cu();
+    d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
     *out = d;
     return PT_OK;
 }
@@ -1177,7 +1179,9 @@ static int ensure_anchor(pt_device_s* d, PtFilterTable& ft, PtPrepTriangle* tris
 
 // the search and what it reads: the prepared scene, its LBVH, the filter of the table the two-pass search runs over.
 // PT_OPT_ACCEL: 0 = BVH for scenes of PT_BVH_AUTO_MIN triangles or more, 1 = brute force, 2 = BVH (needs >= 2 triangles)
-static int prepare_search(pt_device_s* d, const pt_buffer_s* tris, int ntri, const float eye[3], bool& use_bvh)
+// eye: the filter's anchor, the render's eye.  NULL (a ray query, whose origins are anywhere) keeps the anchor the table has, so
+// that a query never rewrites the table under the renders of a moved camera, and makes the reference eye's when it has none
+static int prepare_search(pt_device_s* d, const pt_buffer_s* tris, int ntri, const float* eye, bool& use_bvh)
 {
     use_bvh = ntri >= 2 && (d->opt_accel == 2 || (d->opt_accel == 0 && ntri >= PT_BVH_AUTO_MIN));
     if (!use_bvh && ntri >= (1 << 26))
@@ -1187,6 +1191,11 @@ static int prepare_search(pt_device_s* d, const pt_buffer_s* tris, int ntri, con
     int rc;
     if ((rc = ensure_prep(d, tris, ntri))) return rc;
     if (use_bvh && (rc = ensure_bvh(d, tris, ntri))) return rc;
+    const PtCamera ref = reference_camera();
+    if (!eye) {
+        const PtFilterTable& ft = use_bvh ? d->big_filter : d->scene_filter;
+        eye = ft.anchor_valid ? ft.anchor : ref.eye;
+    }
     return use_bvh ? ensure_anchor(d, d->big_filter, d->bigtab, d->nbig, eye) : ensure_anchor(d, d->scene_filter, d->prep, d->prep_ntri, eye);
 }
 
@@ -1537,6 +1546,87 @@ extern "C" int pt_render_frames(pt_device_t d, pt_buffer_t triangles, pt_buffer_
                                 const pt_render_params* params, pt_buffer_t stats, pt_event_t ev)
 {
     return pt_render_frames_camera(d, triangles, materials, framebuffer, params, nullptr, stats, ev);
+}
+
+// ---- batched ray queries (include/pt_shim.h) ------------------------------------------------------------------------------
+// On the handle's stream, behind the renders in flight (enter_stream: a device-side wait), through the renders' prepared scene,
+// LBVH and filter tables (prepare_search): a triangle buffer the renders use is neither prepared again nor rebuilt.
+static_assert(sizeof(pt_ray) == 32 && sizeof(pt_hit) == 48, "query record layout");
+
+static bool ranges_overlap(const pt_buffer_s* a, size_t abytes, const pt_buffer_s* b, size_t bbytes)
+{
+    const uintptr_t a0 = (uintptr_t)a->dptr, b0 = (uintptr_t)b->dptr;
+    return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+extern "C" int pt_intersect_rays(pt_device_t d, pt_buffer_t triangles, int num_triangles, pt_buffer_t rays, pt_buffer_t out,
+                                 size_t num_rays, int mode, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!triangles || !rays || !out) return fail(PT_ERR_INVALID, "null buffer handle");
+    if (triangles->dev != d || rays->dev != d || out->dev != d) return fail(PT_ERR_INVALID, "buffer belongs to another device");
+    if (ev && ev->dev != d) return fail(PT_ERR_INVALID, "event belongs to another device");
+    if (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_OCCLUDED) return fail(PT_ERR_INVALID, "mode %d is neither PT_QUERY_CLOSEST nor PT_QUERY_OCCLUDED", mode);
+    if (num_triangles < 0) return fail(PT_ERR_INVALID, "num_triangles < 0");
+    if ((size_t)num_triangles * sizeof(PtRawTriangle) > triangles->bytes)
+        return fail(PT_ERR_RANGE, "triangle buffer holds %zu bytes, %d triangles need %zu", triangles->bytes, num_triangles,
+                    (size_t)num_triangles * sizeof(PtRawTriangle));
+    if (num_rays > 0x7fffffffu) return fail(PT_ERR_RANGE, "%zu rays: at most 2^31 - 1 per call", num_rays);
+    const size_t ray_bytes = num_rays * sizeof(pt_ray), out_bytes = num_rays * (mode == PT_QUERY_CLOSEST ? sizeof(pt_hit) : sizeof(int32_t));
+    if (ray_bytes > rays->bytes) return fail(PT_ERR_RANGE, "ray buffer holds %zu bytes, %zu rays need %zu", rays->bytes, num_rays, ray_bytes);
+    if (out_bytes > out->bytes) return fail(PT_ERR_RANGE, "result buffer holds %zu bytes, %zu results need %zu", out->bytes, num_rays, out_bytes);
+    if (num_rays && (((uintptr_t)rays->dptr | (uintptr_t)out->dptr) & 15u)) return fail(PT_ERR_INVALID, "ray and result buffers must be 16-byte aligned");
+    if (ranges_overlap(rays, ray_bytes, out, out_bytes)) return fail(PT_ERR_INVALID, "the rays and the results overlap");
+    // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
+    if ((rc = check_traversal(d))) return rc;
+    if ((rc = enter_stream(d))) return rc;
+    bool use_bvh = false;
+    if (num_rays && num_triangles > 0 && (rc = prepare_search(d, triangles, num_triangles, nullptr, use_bvh))) return rc;
+    if ((rc = event_begin(d, ev))) return rc;
+    if (num_rays) {
+        const PtFilterTable& ft = use_bvh ? d->big_filter : d->scene_filter;
+        // PT_OPT_QUAD_FILTER as for renders (render_part); an empty scene has no table
+        const int quads = num_triangles > 0 && (d->opt_quads == 0 || d->opt_quads == 4) ? ft.quads : 0;
+        PtQueryParams q;
+        memset(&q, 0, sizeof q);
+        q.t.tris = d->prep;
+        q.t.ntri = num_triangles;
+        q.t.quad_delta1 = ft.delta1; q.t.ray_radius = ft.ray_radius;
+        q.t.p1tab = ft.p1tab; q.t.p1_lo = ft.p1_lo; q.t.p1_hi = ft.p1_hi;
+        memcpy(q.t.cam.eye, ft.anchor, sizeof q.t.cam.eye);   // the anchor the table was made about
+        q.t.bvh = d->bvh; q.t.bvh_records = (int32_t)d->bvh_records; q.t.grid = d->bvh_grid;
+        q.t.bigtab = d->bigtab; q.t.bigidx = d->bigidx; q.t.nbig = use_bvh ? d->nbig : 0;
+        q.t.bvh_flags = d->trav_dev; q.t.bvh_stack_limit = (int32_t)d->opt_bvh_stack;
+        q.rays = (const float4*)rays->dptr;
+        q.out = out->dptr;
+        q.nrays = (uint32_t)num_rays;
+        q.occluded = mode == PT_QUERY_OCCLUDED;
+        HIP_TRY(ptk_query(q, d->prop.multiProcessorCount * d->query_bvh_blocks_per_cu, num_triangles > 0 && d->prep_det_bounded, quads, use_bvh,
+                          d->stream));
+    }
+    out->version++;
+    return event_end(d, ev);
+}
+
+extern "C" int pt_camera_rays(pt_device_t d, const pt_camera* cam, int width, int height, int frame, pt_buffer_t rays, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    PtCamera c = reference_camera();
+    if (cam && (rc = camera_derive(cam, &c))) return rc;
+    if (!rays) return fail(PT_ERR_INVALID, "null buffer handle");
+    if (rays->dev != d) return fail(PT_ERR_INVALID, "buffer belongs to another device");
+    if (ev && ev->dev != d) return fail(PT_ERR_INVALID, "event belongs to another device");
+    if (width < 1 || height < 1 || frame < 0) return fail(PT_ERR_INVALID, "invalid image geometry or frame");
+    if ((long long)width * height > 0x7fffffffLL) return fail(PT_ERR_INVALID, "image too large");
+    const size_t bytes = (size_t)width * (size_t)height * sizeof(pt_ray);
+    if (bytes > rays->bytes) return fail(PT_ERR_RANGE, "ray buffer holds %zu bytes, %d x %d rays need %zu", rays->bytes, width, height, bytes);
+    if ((uintptr_t)rays->dptr & 15u) return fail(PT_ERR_INVALID, "the ray buffer must be 16-byte aligned");
+    if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
+    HIP_TRY(ptk_camera_rays(c, width, height, frame, (float4*)rays->dptr, d->stream));
+    rays->version++;
+    return event_end(d, ev);
 }
 
 static int assemble_check(pt_device_s* d, pt_buffer_s* gathered, pt_buffer_s* image, int width, int height, int stripe_rows, int n_ranks, int slab_rows);

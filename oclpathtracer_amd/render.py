@@ -156,6 +156,13 @@ class Renderer:
         out = self.read_stats_raw()
         return {"samples": int(out[shim.PT_STAT_SAMPLES]), "rays": int(out[shim.PT_STAT_RAYS])}
 
+    def ray_caster(self):
+        """A :class:`query.RayCaster` over this renderer's triangle buffer: queries and renders share the device's prepared scene
+        and LBVH, so interleaving them prepares and builds nothing again.  Release it before the renderer."""
+        from .query import RayCaster
+
+        return RayCaster(self.dev, self.tbuf, num_triangles=self.num_triangles)
+
     def global_rows(self) -> np.ndarray:
         """Global row index of every local row (ascending)."""
         rows = np.arange(self.height)

@@ -25,6 +25,7 @@ PT_STAT_SAMPLES, PT_STAT_RAYS, PT_STAT_WORDS = 0, 1, 16
 PT_STAT_BVH_NODES, PT_STAT_BVH_TRIS, PT_STAT_BVH_STEPS, PT_STAT_BVH_TRI_STEPS, PT_STAT_BVH_MAX_STACK, PT_STAT_CARRIED, PT_STAT_BVH_GRAZING = 2, 3, 4, 5, 6, 7, 8
 PT_PROF_TRACE, PT_PROF_FOLD = 0, 1
 PT_STREAM_LEGACY = 1  # hipStreamLegacy: how a caller names the legacy default stream to pt_device_set_stream
+PT_QUERY_CLOSEST, PT_QUERY_OCCLUDED = 0, 1  # pt_intersect_rays modes
 
 _c = ctypes
 _H = _c.c_void_p  # opaque handles
@@ -61,6 +62,23 @@ class Camera(_c.Structure):
         ("eye", _c.c_float * 3), ("center", _c.c_float * 3), ("up", _c.c_float * 3),
         ("fov_y_deg", _c.c_float),
         ("reserved", _c.c_int32 * 6),
+    ]
+
+
+class Ray(_c.Structure):
+    """pt_ray (32 bytes): the arguments of getRay -- origin, tmax (a hit counts at 0 < t < min(tmax, 1e20)), direction (any
+    length; normalised on the device as getRay does), reserved."""
+
+    _fields_ = [("origin", _c.c_float * 3), ("tmax", _c.c_float), ("dir", _c.c_float * 3), ("reserved", _c.c_int32)]
+
+
+class Hit(_c.Structure):
+    """pt_hit (48 bytes): t, triangle, u, v | hit point, material | normal, reserved.  A miss: t = +inf, tri = -1."""
+
+    _fields_ = [
+        ("t", _c.c_float), ("tri", _c.c_int32), ("u", _c.c_float), ("v", _c.c_float),
+        ("p", _c.c_float * 3), ("material", _c.c_int32),
+        ("n", _c.c_float * 3), ("reserved", _c.c_int32),
     ]
 
 
@@ -116,6 +134,8 @@ SIGNATURES = {
     "pt_camera_reference": (None, [_c.POINTER(Camera)]),
     "pt_camera_derive": (_c.c_int, [_c.POINTER(Camera), _c.POINTER(_c.c_float)]),
     "pt_render_frames_camera": (_c.c_int, [_H, _H, _H, _H, _c.POINTER(RenderParams), _c.POINTER(Camera), _H, _H]),
+    "pt_intersect_rays": (_c.c_int, [_H, _H, _c.c_int, _H, _H, _c.c_size_t, _c.c_int, _H]),
+    "pt_camera_rays": (_c.c_int, [_H, _c.POINTER(Camera), _c.c_int, _c.c_int, _c.c_int, _H, _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_profile_query_union": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double)]),

@@ -1,0 +1,94 @@
+/*
+ * query_oracle.c -- the CPU oracle's closest hit and camera rays in the layouts of pt_intersect_rays / pt_camera_rays.
+ * TEST INFRASTRUCTURE.
+ *
+ * Includes tests/camera_oracle.c (and through it oracle/pt_oracle.c) whole; the operations are the oracle's own:
+ *   - oq_closest: ptor_get_ray, then ptor_intersect_triangle over the triangles in ascending order (the loop of
+ *     ptor_intersect_world, GenerateColors.cl:137-154) with hitDistance starting at min(tmax, 1e20) instead of 1e20 -- a ray
+ *     whose tmax is NaN or <= 0 tests nothing -- plus the winner's (u, v) and material, which ptor_hit does not keep: u and v
+ *     restate :96-117 with the oracle's v3 functions;
+ *   - oq_camera_rays: ocam_generate_ray's expression up to the argument the reference passes to getRay at :287 (normalised once).
+ * Compiled with oracle/Makefile's flags (tests/query_oracle.py).
+ */
+#include "camera_oracle.c"
+
+/* n rays of 8 floats (origin xyz, tmax, dir xyz, reserved) -> n records of 12 words in pt_hit's layout:
+ * t, tri, u, v, p xyz, material, n xyz, 0; a miss is t = +inf, tri = -1, material = -1, everything else 0 */
+PTOR_CLONES
+void oq_closest(const void* tris_, int ntri, const float* rays, int64_t n, float* out)
+{
+    const ptor_triangle* tris = (const ptor_triangle*)tris_;
+    ptor_stats st;
+    memset(&st, 0, sizeof st);
+    for (int64_t k = 0; k < n; ++k) {
+        const float* r8 = rays + 8 * k;
+        float* o = out + 12 * k;
+        int32_t* oi = (int32_t*)o;
+        const ptor_ray r = ptor_get_ray(v3_make(r8[0], r8[1], r8[2]), v3_make(r8[4], r8[5], r8[6]));
+        ptor_hit rec;
+        memset(&rec, 0, sizeof rec);
+        rec.tri = -1;
+        int hit = 0;
+        if (r8[3] > 0.0f) {
+            float hitDistance = r8[3] < 1e20f ? r8[3] : 1e20f;
+            for (int i = 0; i < ntri; i++)
+                if (ptor_intersect_triangle(&r, &tris[i], i, &rec, hitDistance, &st)) {
+                    hitDistance = rec.t;
+                    hit = 1;
+                }
+        }
+        memset(o, 0, 12 * sizeof(float));
+        if (!hit) {
+            o[0] = INFINITY;
+            oi[1] = -1;
+            oi[7] = -1;
+            continue;
+        }
+        const ptor_triangle* t = &tris[rec.tri];
+        const v3 p1 = v3_make(t->p1[0], t->p1[1], t->p1[2]);
+        const v3 e1 = v3_sub(v3_make(t->p2[0], t->p2[1], t->p2[2]), p1);
+        const v3 e2 = v3_sub(v3_make(t->p3[0], t->p3[1], t->p3[2]), p1);
+        const v3 pvec = v3_cross(r.dir, e2);
+        const float inv_det = 1.0f / v3_dot(e1, pvec);
+        const v3 tvec = v3_sub(r.origin, p1);
+        const float u = v3_dot(tvec, pvec) * inv_det;
+        const v3 qvec = v3_cross(tvec, e1);
+        const float v = v3_dot(r.dir, qvec) * inv_det;
+        o[0] = rec.t;
+        oi[1] = rec.tri;
+        o[2] = u;
+        o[3] = v;
+        o[4] = rec.p.x; o[5] = rec.p.y; o[6] = rec.p.z;
+        oi[7] = t->id;
+        o[8] = rec.n.x; o[9] = rec.n.y; o[10] = rec.n.z;
+    }
+}
+
+/* width x height rays of 8 floats: eye, 1e20, the direction getRay receives at :287, 0; seed gid + hash(frame) (:305-308).
+ * cam10: eye xyz, center xyz, up xyz, fov_y_deg (NULL = the reference's).  Returns -1 for a camera ocam_derive rejects. */
+PTOR_CLONES
+int oq_camera_rays(const float* cam10, int W, int H, int frame, float* out)
+{
+    static const float ref10[10] = { 0.0f, 2.75f, 4.0f, 0.0f, 2.75f, 3.0f, 0.0f, 1.0f, 0.0f, 60.0f };
+    float d16[16];
+    if (ocam_derive(cam10 ? cam10 : ref10, d16) != 0) return -1;
+    const ocam c = ocam_from(d16);
+    const float invWidth = 1.0f / (float)W, invHeight = 1.0f / (float)H;
+    const float aspectratio = (float)W / (float)H;
+    for (int64_t gid = 0; gid < (int64_t)W * H; ++gid) {
+        uint32_t seed = (uint32_t)gid + ptor_hash_u32((uint32_t)frame);
+        float x = (float)(gid % W) + ptor_random_float(&seed) - 0.5f;
+        float y = (float)(gid / W) + ptor_random_float(&seed) - 0.5f;
+        x = (2.0f * ((x + 0.5f) * invWidth) - 1.0f) * c.angle * aspectratio;
+        y = -(1.0f - 2.0f * ((y + 0.5f) * invHeight)) * c.angle;
+        float my = -1.0f * y;
+        v3 d = v3_add(v3_add(v3_scale(c.hol, x), v3_scale(c.up, my)), c.view);
+        v3 dir = v3_normalize(d);
+        v3 pointAimed = v3_add(c.eye, v3_scale(dir, 4.0f));
+        const v3 aim = v3_normalize(v3_sub(pointAimed, c.eye));
+        float* o = out + 8 * gid;
+        o[0] = c.eye.x; o[1] = c.eye.y; o[2] = c.eye.z; o[3] = 1e20f;
+        o[4] = aim.x; o[5] = aim.y; o[6] = aim.z; o[7] = 0.0f;
+    }
+    return 0;
+}
