@@ -380,6 +380,43 @@ int pt_intersect_rays(pt_device_t dev, pt_buffer_t triangles, int num_triangles,
  * renderer's primary rays bit for bit. */
 int pt_camera_rays(pt_device_t dev, const pt_camera* cam /* NULL = reference */, int width, int height,
                    int frame, pt_buffer_t rays, pt_event_t ev);
+/* One int32 per ray, the same value pt_intersect_rays(..., PT_QUERY_OCCLUDED) writes, found by a search that stops at the
+ * first triangle the exact test accepts at 0 < t < min(tmax, 1e20) (through the LBVH; brute force runs the closest search).
+ * Arguments, stream, scene preparation and the deferred PT_ERR_TRAVERSAL are pt_intersect_rays's. */
+int pt_occluded_rays(pt_device_t dev, pt_buffer_t triangles, int num_triangles, pt_buffer_t rays, pt_buffer_t out,
+                     size_t num_rays, pt_event_t ev);
+
+/* ---- ambient occlusion ---------------------------------------------------------------------------------------------
+ * The AmbientOcclusion case the reference's harness declares (test/RaytraceTest.cpp:293-295) with an empty body, composed of
+ * the reference's own steps.  A sample of pixel gid = y * width + x in frame z: seed = gid + hash(z) (GenerateColors.cl:308), the
+ * renderer's primary ray (:263-288) and its closest hit from tmax 1e20 (:141).  A miss adds nothing.  A hit adds 1 to `hits`; with
+ * p = o + d t (:127) and n the HitRecord normal (:128-130) turned to face the ray (:243), K times in order: wi =
+ * sampleHemisphereCosine(n, &seed) (:161-172, the same seed), and the ray getRay(p + wi 0.01, wi) (:257) adds 1 to `open` when no
+ * triangle passes the exact test (:96-125) at 0 < t < min(radius, 1e20).  Every triangle occludes; materials play no part.
+ * counts: pt_local_rows(...) x width records {uint32 open, uint32 hits} in the renderer's stripe layout (pt_render_params),
+ * overwritten when frame_begin = 0 (the :314-321 rule), otherwise added to.  image (may be NULL): float4 (a, a, a, 1) per local
+ * pixel from everything the counts hold after this call, a = hits > 0 ? (float)open / (float)(K hits) : miss_value (K hits in
+ * uint32; one IEEE division) -- the renderer's framebuffer layout, for pt_assemble_stripes and pt_tonemap_ppm.
+ * AO renders behave like queries: the handle's stream, behind renders in flight, asynchronous (ev); the scene, LBVH and filter
+ * tables as a query uses them (no anchor move, no rebuild); once the scene is prepared no allocation and no wait; PT_OPT_ACCEL
+ * and PT_OPT_QUAD_FILTER choose the search, PT_OPT_PRIMARY_MASKS is not used; a cut-short LBVH search raises PT_ERR_TRAVERSAL.
+ * Errors come before anything is enqueued and leave the counts untouched: PT_ERR_INVALID for a field out of range, a reserved
+ * field not 0, a camera pt_camera_derive rejects, counts not 8-byte or image not 16-byte aligned, counts and image overlapping,
+ * a buffer of another device, frame_begin + frame_count or width x height above 2^31 - 1; PT_ERR_RANGE for a buffer too small
+ * or (frame_begin + frame_count) x K above 2^32 - 1 (so that neither open nor K hits can wrap). */
+typedef struct pt_ao_params {
+    int32_t width, height;       /* the image */
+    int32_t frame_begin;         /* first frame; 0 = the counts are overwritten, otherwise added to */
+    int32_t frame_count;         /* >= 0; 0 enqueues nothing */
+    int32_t num_triangles;       /* >= 0; 0 = every primary ray misses */
+    int32_t rays_per_sample;     /* K, 1..256 */
+    float radius;                /* finite, > 0: an occlusion ray counts hits at 0 < t < min(radius, 1e20) */
+    float miss_value;            /* finite: the image value of a pixel none of whose samples hit the scene */
+    int32_t stripe_rows, n_ranks, rank;   /* image sharding exactly as pt_render_params */
+    int32_t reserved[5];         /* must be 0 */
+} pt_ao_params;                  /* 64 bytes */
+int pt_render_ao(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t counts, pt_buffer_t image /* may be NULL */,
+                 const pt_ao_params* params, const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
 
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.

@@ -235,6 +235,24 @@ struct PtQueryParams {
 // bvh_blocks: the persistent grid of the LBVH kernel (CUs x ptk_query_bvh_blocks_per_cu)
 hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s);
 int ptk_query_bvh_blocks_per_cu(void);
+// pt_occluded_rays through the LBVH: the any-hit search on the query kernel's persistent grid (brute force: ptk_query, occluded)
+hipError_t ptk_occluded_bvh(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, hipStream_t s);
+// ambient occlusion (pt_render_ao): t carries the search as PtQueryParams::t does (the filter's anchor in t.cam.eye) and the image
+// geometry (width, inv_width, inv_height, aspect, stripe_rows, n_ranks, rank); cam is the camera
+struct PtAoParams {
+    PtTraceParams t;
+    PtCamera cam;
+    unsigned long long* counts;   // [npix] open | hits << 32 (the {open, hits} uint32 pair), added to
+    uint32_t npix;                // local pixels
+    uint32_t nitems;              // samples of this launch, frame-major: item = f * npix + local pixel (< 2^31)
+    int32_t frame0;               // the frame of item 0
+    int32_t K;                    // occlusion rays per hit
+    float tlim;                   // min(radius, 1e20)
+};
+hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s);
+int ptk_ao_bvh_blocks_per_cu(void);
+// image[i] = float4(a, a, a, 1) of counts[i] = {open, hits}: a = open / (K hits), miss_value when hits = 0
+hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s);
 // rays[2 gid], rays[2 gid + 1] = the pt_ray of pixel gid, frame `frame` (the renderer's sample start) for the camera cam
 hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s);
 // dynamic LDS of a trace workgroup (pt_kernels.hip: pt_lds_total, pt_bvh_lds_total)

@@ -1690,9 +1690,13 @@ PTK_DEV void pt_raise_flag(unsigned int* flags, unsigned bit)
 #ifndef PT_BVH_RING_MIN
 #define PT_BVH_RING_MIN 32u
 #endif
-template <bool DET_BOUNDED>
+// ANY: some lanes run an ANY-HIT search (any, per lane: pt_occluded_rays, the occlusion rays of pt_render_ao).  Such a ray's limit
+// L.tmax never shrinks, a pair counts only at t < that limit (the closest search's key minimum lets a candidate AT tmax beat the
+// incumbent (tmax, no triangle): pt_query_store filters it, an any-hit search must not take it), and the owner keeps the first
+// winner's index in L.hidx -- pt_bvh_step then ends its search.  ANY = false is the closest search alone, as before.
+template <bool DET_BOUNDED, bool ANY = false>
 PTK_DEV void pt_bvh_round(const PtTraceParams& P, PtBvhLane& L, PtTail& tl, unsigned cnt, unsigned lane, const f3& o, const f3& d,
-                          unsigned n_recs)
+                          unsigned n_recs, bool any = false)
 {
     // every lane, as the owner of a ray, publishes its incumbent; a slot nobody improves reads back unchanged
     const unsigned long long k0 = ((unsigned long long)__float_as_uint(L.tmax) << 32) |
@@ -1734,6 +1738,10 @@ PTK_DEV void pt_bvh_round(const PtTraceParams& P, PtBvhLane& L, PtTail& tl, unsi
         t = pt_fma(r.e2z, qvz, pt_fma(r.e2y, qvy, r.e2x * qvx)) * inv_det;
         ok &= (t > 0.0f) & (t < 1e20f);  // :125 against the initial tmax (:141)
     }
+    if (ANY) {   // the owner's search kind and limit travel with its ray
+        const bool pany = __builtin_amdgcn_ds_bpermute((int)a, any ? 1 : 0) != 0;
+        ok &= !pany | (t < pt_from_lane(a, L.tmax));
+    }
     if (ok & valid) {
         const unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | (unsigned long long)((tri << 6) | lane);
         __hip_atomic_fetch_min(tl.keys + ray, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -1745,11 +1753,15 @@ PTK_DEV void pt_bvh_round(const PtTraceParams& P, PtBvhLane& L, PtTail& tl, unsi
     const unsigned from = ((unsigned)slot & 63u) << 2;
     const float pu = pt_from_lane(from, u), pv = pt_from_lane(from, v);
     if (slot != k0) {  // (t, index) < the incumbent's: the new closest hit
-        L.tmax = __uint_as_float((unsigned)(slot >> 32));
-        L.hidx = (int)(((unsigned)slot >> 6) & 0x3ffffffu);
-        L.hu = pu;
-        L.hv = pv;
-        pt_bvh_scale(L, d);
+        if (ANY && any) {
+            L.hidx = (int)(((unsigned)slot >> 6) & 0x3ffffffu);   // an any-hit search: some triangle is hit below the limit
+        } else {
+            L.tmax = __uint_as_float((unsigned)(slot >> 32));
+            L.hidx = (int)(((unsigned)slot >> 6) & 0x3ffffffu);
+            L.hu = pu;
+            L.hv = pv;
+            pt_bvh_scale(L, d);
+        }
     }
     tl.rd += cnt;
 }
@@ -1757,10 +1769,12 @@ PTK_DEV void pt_bvh_round(const PtTraceParams& P, PtBvhLane& L, PtTail& tl, unsi
 // one step of the wave: a node phase for every traversing lane (trav: the lane still has nodes to enter), its leaf hits to the
 // ring, a round when enough pairs are pending.  stk: this lane's stack in LDS, ovf: its overflow in scratch, nxt: the 2 KB
 // child-order table
-template <bool DET_BOUNDED, bool TALLY>
+// (ANY, any: pt_bvh_round -- an any-hit lane leaves its traversal at the first accepted pair; its pairs still in the ring are
+// tested for it alone and change nothing)
+template <bool DET_BOUNDED, bool TALLY, bool ANY = false>
 PTK_DEV void pt_bvh_step(const PtTraceParams& P, PtBvhLane& L, bool& trav, const f3& o, const f3& d, pt_lds_u32* stk, unsigned* ovf,
                          const pt_lds_u8* nxt, PtTail& tl, unsigned lane, unsigned n_recs, unsigned& c_nodes, unsigned& c_leaves,
-                         unsigned long long& c_steps, unsigned long long& c_tsteps, unsigned& c_maxsp)
+                         unsigned long long& c_steps, unsigned long long& c_tsteps, unsigned& c_maxsp, bool any = false)
 {
     unsigned ht = 0u, cmask = 0u, cbase = 0u;
     if (TALLY) ++c_steps;
@@ -1844,13 +1858,14 @@ PTK_DEV void pt_bvh_step(const PtTraceParams& P, PtBvhLane& L, bool& trav, const
         tl.wr += (unsigned)__popcll(has);
         if (tl.wr - tl.rd >= 64u) {  // (room for the next 64)
             if (TALLY) ++c_tsteps;
-            pt_bvh_round<DET_BOUNDED>(P, L, tl, 64u, lane, o, d, n_recs);
+            pt_bvh_round<DET_BOUNDED, ANY>(P, L, tl, 64u, lane, o, d, n_recs, any);
         }
     }
     if (tl.wr - tl.rd >= (unsigned)PT_BVH_RING_MIN) {
         if (TALLY) ++c_tsteps;
-        pt_bvh_round<DET_BOUNDED>(P, L, tl, tl.wr - tl.rd, lane, o, d, n_recs);
+        pt_bvh_round<DET_BOUNDED, ANY>(P, L, tl, tl.wr - tl.rd, lane, o, d, n_recs, any);
     }
+    if (ANY && any && L.hidx >= 0) trav = false;
 }
 
 // BIGQ: the filter of the brute-force search over the big triangles: 0 = independent triangles, 3 = the packed shared-u filter
@@ -2581,6 +2596,316 @@ __global__ __launch_bounds__(256) void pt_camera_rays_kernel(const PtCamera cam,
 }
 
 // ------------------------------------------------------------------------------------------
+// early-exit occlusion search (pt_occluded_rays) and ambient occlusion (pt_render_ao)
+// ------------------------------------------------------------------------------------------
+// What an LBVH workgroup of the persistent query kernels holds in LDS before its loop: the table of the triangles outside the
+// hierarchy and the 2 KB child-order table (pt_query_bvh_kernel's preamble).  Returns the child-order table.
+PTK_DEV pt_lds_u8* pt_bvh_wg_setup(const PtTraceParams& P)
+{
+    const float* g = reinterpret_cast<const float*>(P.bigtab);
+    for (int k = (int)threadIdx.x; k < P.nbig * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
+        const int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
+        pt_lds_tab[k] = g[tri * 16 + w];
+    }
+    pt_lds_u8* nxt = (pt_lds_u8*)((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_nxt());
+    for (unsigned k = threadIdx.x; k < 2048u; k += PT_TRACE_THREADS) {
+        const unsigned o = k >> 8, h = k & 255u;
+        unsigned best = 0u, bp = 0u;
+        for (unsigned sl = 0; sl < 8u; ++sl)
+            if (((h >> sl) & 1u) && ((sl ^ o) >= bp)) { bp = sl ^ o; best = sl; }
+        nxt[k] = (unsigned char)best;
+    }
+    __syncthreads();
+    return nxt;
+}
+
+// a lane's search state at the start of a new ray: the limit, no hit
+PTK_DEV void pt_bvh_lane_clear(PtBvhLane& L, float tlim)
+{
+    L.tmax = tlim; L.hu = 0.0f; L.hv = 0.0f; L.hidx = -1;
+}
+
+// The start of a ray's LBVH search for the lanes in `start`: the triangles outside the hierarchy by the two-pass search (its
+// tail shares the key slots with pt_bvh_round and expects them empty: the ring has just been flushed), then the root.  An
+// any-hit ray (any) that hits one of them is done: it does not traverse.
+template <bool DET_BOUNDED, int BIGQ>
+PTK_DEV void pt_bvh_search_start(const PtTraceParams& P, PtBvhLane& L, bool& trav, bool start, bool any, const f3& o, const f3& d,
+                                 PtTail& tl, unsigned lane)
+{
+    if (__ballot(start) == 0ull) return;
+    if (P.nbig > 0) {
+        int hp = -1;
+        tl.keys[lane] = ~0ull;
+        pt_intersect_two_pass<DET_BOUNDED, 1, (DET_BOUNDED ? BIGQ : 0)>((pt_const_f32p)(const float*)P.bigtab, P.bigtab, P.nbig, o, d, start,
+                                                                          L.tmax, L.hu, L.hv, hp, P.quad_delta1, P.ray_radius,
+                                                                          (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi,
+                                                                          mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]), tl, lane);
+        if (start && hp >= 0) L.hidx = P.bigidx[hp];
+    }
+    if (start && !(any && L.hidx >= 0)) {
+        pt_bvh_lane_start(L, d, P.ntri);
+        trav = true;
+    }
+}
+
+// pt_occluded_rays through the LBVH: pt_query_bvh_kernel's persistent grid and lane refill, with every search an any-hit one.
+// The result is PT_QUERY_OCCLUDED's: some triangle passes the exact test at 0 < t < min(tmax, 1e20) (the two-pass search of the
+// big triangles and pt_bvh_round both compare strictly).
+template <bool DET_BOUNDED, int BIGQ>
+__global__ __launch_bounds__(PT_TRACE_THREADS) PT_BVH_WAVES_ATTR
+void pt_occluded_bvh_kernel(const PtQueryParams Q)
+{
+    const PtTraceParams& P = Q.t;
+    const unsigned lane = pt_lane_id();
+    const unsigned n_recs = (unsigned)P.bvh_records;
+    const pt_lds_u8* nxt = pt_bvh_wg_setup(P);
+    pt_lds_u32* stk = (pt_lds_u32*)pt_lds_tab + pt_bvh_lds_stacks() + threadIdx.x;
+    unsigned ovf[2 * (PT_BVH_STACK - PT_BVH_LDS_STACK)];
+    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_tails() + (threadIdx.x >> 6) * PT_BVH_TAIL_DW, 0u, lane);
+
+    const unsigned stride = gridDim.x * (PT_TRACE_THREADS / 64) * 64u;
+    const unsigned nrays = Q.nrays;
+    unsigned next = pt_wave() * 64u;
+    unsigned gend = next + 64u < nrays ? next + 64u : nrays;
+    bool alive = false, trav = false;
+    unsigned ray = 0u;
+    PtQueryRay r = pt_query_idle();
+    PtBvhLane L;
+    pt_bvh_lane_clear(L, 0.0f);
+    L.gbase = L.gm = L.oct = 0u; L.sp = 0; L.ix = L.iy = L.iz = 0.0f; L.budget = 0u;
+    unsigned c_nodes = 0, c_leaves = 0, c_maxsp = 0;
+    unsigned long long c_steps = 0, c_tsteps = 0;
+
+    for (;;) {
+        if ((unsigned)__popcll(__ballot(trav)) <= (unsigned)PT_BVH_REFILL) {
+            if (tl.wr != tl.rd) pt_bvh_round<DET_BOUNDED, true>(P, L, tl, tl.wr - tl.rd, lane, r.o, r.d, n_recs, true);
+            if (alive && !trav) {
+                reinterpret_cast<int32_t*>(Q.out)[ray] = L.hidx >= 0 ? 1 : 0;
+                alive = false;
+            }
+            bool fresh = false;
+            for (unsigned long long need = __ballot(!alive); need != 0ull && next < nrays; need = __ballot(!alive)) {
+                const unsigned n_need = (unsigned)__popcll(need), avail = gend - next;
+                const unsigned take = n_need < avail ? n_need : avail;
+                const unsigned rank = pt_mbcnt(need);
+                if (!alive && rank < take) {
+                    ray = next + rank;
+                    r = pt_query_load(Q.rays, ray);
+                    alive = true;
+                    fresh = true;
+                }
+                next += take;
+                if (next == gend) {
+                    next = ((gend - 1u) & ~63u) + stride;
+                    next = next < nrays ? next : nrays;
+                    gend = next + 64u < nrays ? next + 64u : nrays;
+                }
+            }
+            if (fresh) pt_bvh_lane_clear(L, r.tlim);   // (a ray that searches nothing is stored as a miss at the next refill)
+            pt_bvh_search_start<DET_BOUNDED, BIGQ>(P, L, trav, fresh && r.live, true, r.o, r.d, tl, lane);
+            if (__ballot(alive) == 0ull) break;
+        }
+        pt_bvh_step<DET_BOUNDED, false, true>(P, L, trav, r.o, r.d, stk, ovf, nxt, tl, lane, n_recs, c_nodes, c_leaves, c_steps, c_tsteps, c_maxsp, true);
+    }
+}
+
+// ---- ambient occlusion ---------------------------------------------------------------------------------------------------
+// One work item is one sample (local pixel lp, frame f0 + j / npix): the renderer's primary ray (seed :308, pt_generate_ray), its
+// closest hit from tmax 1e20 (:141); on a hit, K occlusion rays getRay(p + wi 0.01, wi) (:257) with wi = sampleHemisphereCosine
+// (n, &seed) (:161-172) about the HitRecord normal turned to face the ray (:243), each an any-hit search at 0 < t < min(radius, 1e20).
+// counts[lp] += open | hits << 32: hits = 1 for a primary hit, open = the occlusion rays that hit nothing.
+
+// the sample's start: its local pixel and its primary ray (pt_sample_begin's seed and camera ray, for the AO parameters)
+PTK_DEV void pt_ao_begin(const PtAoParams& A, unsigned item, unsigned& lp, uint32_t& seed, f3& o, f3& d)
+{
+    const PtTraceParams& P = A.t;
+    const unsigned f = item / A.npix;
+    lp = item - f * A.npix;
+    const unsigned W = (unsigned)P.width;
+    const unsigned lr = lp / W, x = lp - lr * W;
+    unsigned grow = lr;
+    if (P.n_ranks > 1) {
+        const unsigned sl = lr / (unsigned)P.stripe_rows;
+        grow = (sl * (unsigned)P.n_ranks + (unsigned)P.rank) * (unsigned)P.stripe_rows + (lr - sl * (unsigned)P.stripe_rows);   // pt_stripe_row
+    }
+    const unsigned gid = grow * W + x;
+    seed = gid + pt_hash_u32((uint32_t)(A.frame0 + (int)f));
+    pt_generate_ray((int)x, (int)grow, P.inv_width, P.inv_height, P.aspect, PT_CAM_K(A.cam), seed, o, d);
+}
+
+// the primary hit's point and normal (pt_shade: the deferred HitRecord of :127-130, turned to face the ray as at :243)
+PTK_DEV void pt_ao_surface(const PtTraceParams& P, const f3& o, const f3& d, float t, float hu, float hv, int hidx, f3& p, f3& n)
+{
+    const float4 nid = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(P.tris + hidx) + 12);
+    const f3 N = mk3(nid.x, nid.y, nid.z);
+    p = add3(o, scale3(d, t));
+    const float w = 1.0f - hu - hv;
+    n = normalize3(add3(add3(scale3(N, hu), scale3(N, hv)), scale3(N, w)));
+    n = dot3(n, d) < 0.0f ? n : scale3(n, -1.0f);
+}
+
+// occlusion ray k of the sample: wi = sampleHemisphereCosine(n, &seed) (:161-172: phi, then sinThetaSqr -- pt_shade's diffuse
+// branch), the ray getRay(p + wi 0.01, wi) (:257)
+PTK_DEV void pt_ao_ray(const f3& p, const f3& n, uint32_t& seed, f3& o, f3& d)
+{
+    const float phi = PTK_TWO_PI * pt_random_float(seed);
+    const float xi = pt_random_float(seed);
+    float sp, cp;
+    pt_sincos(phi, sp, cp);
+    const f3 axis = __builtin_fabsf(n.x) > 0.001f ? mk3(0.0f, 1.0f, 0.0f) : mk3(1.0f, 0.0f, 0.0f);
+    const f3 tv = normalize3(cross3(axis, n));
+    const f3 sv = cross3(n, tv);
+    const float cosTheta = pt_sqrt(1.0f - xi);
+    const float sinTheta = pt_sqrt(xi);
+    const f3 a = scale3(scale3(sv, cp), sinTheta);
+    const f3 b = scale3(scale3(tv, sp), sinTheta);
+    const f3 c = scale3(n, cosTheta);
+    const f3 wi = normalize3(add3(add3(a, b), c));
+    o = add3(p, scale3(wi, 0.01f));
+    d = normalize3(wi);
+}
+
+PTK_DEV void pt_ao_count(const PtAoParams& A, unsigned lp, unsigned hits, unsigned open)
+{
+    if (hits | open)
+        __hip_atomic_fetch_add(A.counts + lp, (unsigned long long)open | ((unsigned long long)hits << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// brute force: one wave = 64 consecutive samples; the primary search, then the K occlusion rays of the lanes that hit, all in step
+// (the search is wave-uniform over the triangles: pt_query_kernel)
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_ao_kernel(const PtAoParams A)
+{
+    const PtTraceParams& P = A.t;
+    const unsigned lane = pt_lane_id();
+    const int ntri = P.ntri;
+    if (LDS_TABLE == 1) {
+        const float* g = reinterpret_cast<const float*>(P.tris);
+        for (int k = (int)threadIdx.x; k < ntri * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
+            const int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
+            pt_lds_tab[k] = g[tri * 16 + w];
+        }
+        __syncthreads();
+    }
+    const unsigned wave_in_wg = pt_wave_in_wg();
+    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_query_lds_tails<LDS_TABLE>(ntri) + wave_in_wg * pt_lds_tail_dw<LDS_TABLE>(),
+                             pt_query_lds_tiles<LDS_TABLE>(ntri) + wave_in_wg * PT_LDS_TILE_DW, lane);
+    const f3 anchor = mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]);
+    const unsigned item = pt_wave() * 64u + lane;
+    const bool act = item < A.nitems;
+    unsigned lp = 0u;
+    uint32_t seed = 0u;
+    f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f);
+    if (act) pt_ao_begin(A, item, lp, seed, o, d);
+    float tmax = 1e20f, hu = 0.0f, hv = 0.0f;
+    int hidx = -1;
+    pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, act, tmax, hu, hv, hidx,
+                                                         P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+    const bool hit = act & (hidx >= 0);
+    if (__ballot(hit) == 0ull) return;
+    f3 p = o, n = d;
+    if (hit) pt_ao_surface(P, o, d, tmax, hu, hv, hidx, p, n);
+    unsigned open = 0u;
+    for (int k = 0; k < A.K; ++k) {
+        if (hit) pt_ao_ray(p, n, seed, o, d);
+        float t = A.tlim, su = 0.0f, sv = 0.0f;
+        int sidx = -1;
+        pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, hit, t, su, sv, sidx,
+                                                             P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+        open += (hit & !((sidx >= 0) & (t < A.tlim))) ? 1u : 0u;   // pt_query_store's occlusion test
+    }
+    if (hit) pt_ao_count(A, lp, 1u, open);
+}
+
+// LBVH: pt_query_bvh_kernel's persistent grid.  A lane holds one sample and runs its searches one after the other -- the primary
+// ray's closest search, then its occlusion rays' any-hit searches; at every refill the lanes whose search has ended go on to
+// their sample's next ray, and the lanes whose sample is done take the wave's next samples.
+template <bool DET_BOUNDED, int BIGQ>
+__global__ __launch_bounds__(PT_TRACE_THREADS) PT_BVH_WAVES_ATTR
+void pt_ao_bvh_kernel(const PtAoParams A)
+{
+    const PtTraceParams& P = A.t;
+    const unsigned lane = pt_lane_id();
+    const unsigned n_recs = (unsigned)P.bvh_records;
+    const pt_lds_u8* nxt = pt_bvh_wg_setup(P);
+    pt_lds_u32* stk = (pt_lds_u32*)pt_lds_tab + pt_bvh_lds_stacks() + threadIdx.x;
+    unsigned ovf[2 * (PT_BVH_STACK - PT_BVH_LDS_STACK)];
+    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_tails() + (threadIdx.x >> 6) * PT_BVH_TAIL_DW, 0u, lane);
+
+    const unsigned stride = gridDim.x * (PT_TRACE_THREADS / 64) * 64u;
+    const unsigned nitems = A.nitems;
+    unsigned next = pt_wave() * 64u;
+    unsigned gend = next + 64u < nitems ? next + 64u : nitems;
+    bool alive = false;   // the lane holds a sample that is not counted yet
+    bool trav = false;    // ... and the search of its current ray is in progress
+    int k = -1;           // the current ray: -1 = the primary, 0 .. K-1 = occlusion ray k
+    unsigned lp = 0u, open = 0u;
+    uint32_t seed = 0u;
+    f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f), p = o, n = d;
+    PtBvhLane L;
+    pt_bvh_lane_clear(L, 0.0f);
+    L.gbase = L.gm = L.oct = 0u; L.sp = 0; L.ix = L.iy = L.iz = 0.0f; L.budget = 0u;
+    unsigned c_nodes = 0, c_leaves = 0, c_maxsp = 0;
+    unsigned long long c_steps = 0, c_tsteps = 0;
+
+    for (;;) {
+        if ((unsigned)__popcll(__ballot(trav)) <= (unsigned)PT_BVH_REFILL) {
+            if (tl.wr != tl.rd) pt_bvh_round<DET_BOUNDED, true>(P, L, tl, tl.wr - tl.rd, lane, o, d, n_recs, k >= 0);
+            bool fresh = false;
+            if (alive && !trav) {   // the search of the current ray has ended
+                bool done = false;
+                if (k < 0) {
+                    done = L.hidx < 0;   // a primary miss adds nothing
+                    if (!done) pt_ao_surface(P, o, d, L.tmax, L.hu, L.hv, L.hidx, p, n);
+                } else {
+                    open += L.hidx < 0 ? 1u : 0u;
+                }
+                if (!done && ++k < A.K) {
+                    pt_ao_ray(p, n, seed, o, d);
+                    fresh = true;
+                } else {
+                    if (!done) pt_ao_count(A, lp, 1u, open);
+                    alive = false;
+                }
+            }
+            for (unsigned long long need = __ballot(!alive); need != 0ull && next < nitems; need = __ballot(!alive)) {
+                const unsigned n_need = (unsigned)__popcll(need), avail = gend - next;
+                const unsigned take = n_need < avail ? n_need : avail;
+                const unsigned rank = pt_mbcnt(need);
+                if (!alive && rank < take) {
+                    pt_ao_begin(A, next + rank, lp, seed, o, d);
+                    k = -1;
+                    open = 0u;
+                    alive = true;
+                    fresh = true;
+                }
+                next += take;
+                if (next == gend) {
+                    next = ((gend - 1u) & ~63u) + stride;
+                    next = next < nitems ? next : nitems;
+                    gend = next + 64u < nitems ? next + 64u : nitems;
+                }
+            }
+            if (fresh) pt_bvh_lane_clear(L, k < 0 ? 1e20f : A.tlim);
+            pt_bvh_search_start<DET_BOUNDED, BIGQ>(P, L, trav, fresh, k >= 0, o, d, tl, lane);
+            if (__ballot(alive) == 0ull) break;
+        }
+        pt_bvh_step<DET_BOUNDED, false, true>(P, L, trav, o, d, stk, ovf, nxt, tl, lane, n_recs, c_nodes, c_leaves, c_steps, c_tsteps, c_maxsp, k >= 0);
+    }
+}
+
+// image[i] = (a, a, a, 1), a = open / (K hits) (each converted to float, then one IEEE division), miss_value for a pixel never hit
+__global__ __launch_bounds__(256) void pt_ao_resolve_kernel(const uint2* __restrict__ counts, float4* __restrict__ image, unsigned npix,
+                                                            unsigned K, float miss_value)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npix) return;
+    const uint2 c = counts[i];
+    const float a = c.y > 0u ? (float)c.x / (float)(K * c.y) : miss_value;
+    image[i] = make_float4(a, a, a, 1.0f);
+}
+
+// ------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------
 hipError_t ptk_prep_triangles(const PtRawTriangle* raw, PtPrepTriangle* out, int ntri, unsigned int* det_bound_bits,
@@ -2752,4 +3077,55 @@ hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame
     const float inv_w = 1.0f / (float)width, inv_h = 1.0f / (float)height, aspect = (float)width / (float)height;
     hipLaunchKernelGGL(pt_camera_rays_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, s, cam, width, npix, inv_w, inv_h, aspect, frame, rays);
     return hipGetLastError();
+}
+
+// ---- early-exit occlusion and ambient occlusion ---------------------------------------------------------------------------
+hipError_t ptk_occluded_bvh(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, hipStream_t s)
+{
+    if (q.nrays == 0) return hipSuccess;
+    const unsigned wg_waves = PT_TRACE_THREADS / 64;
+    unsigned blocks = ((q.nrays + 63u) / 64u + wg_waves - 1u) / wg_waves;
+    if (bvh_blocks > 0 && blocks > (unsigned)bvh_blocks) blocks = (unsigned)bvh_blocks;
+    void (*kernel)(const PtQueryParams) =
+        det_bounded ? (quads == 3 ? pt_occluded_bvh_kernel<true, 3> : pt_occluded_bvh_kernel<true, 0>) : pt_occluded_bvh_kernel<false, 0>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(PT_TRACE_THREADS), ptk_trace_bvh_lds_bytes(), s, q);
+    return hipGetLastError();
+}
+
+hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s)
+{
+    if (a.nitems == 0) return hipSuccess;
+    const bool q3 = quads == 3;
+    const unsigned wg_waves = PT_TRACE_THREADS / 64;
+    unsigned blocks = ((a.nitems + 63u) / 64u + wg_waves - 1u) / wg_waves;   // 64 samples per wave
+    void (*kernel)(const PtAoParams);
+    size_t lds;
+    if (bvh) {
+        kernel = det_bounded ? (q3 ? pt_ao_bvh_kernel<true, 3> : pt_ao_bvh_kernel<true, 0>) : pt_ao_bvh_kernel<false, 0>;
+        if (bvh_blocks > 0 && blocks > (unsigned)bvh_blocks) blocks = (unsigned)bvh_blocks;
+        lds = ptk_trace_bvh_lds_bytes();
+    } else if (a.t.ntri <= PT_LDS_TRI_MAX) {
+        kernel = det_bounded ? (q3 ? pt_ao_kernel<true, 1, 3> : pt_ao_kernel<true, 1, 0>) : pt_ao_kernel<false, 1, 0>;
+        lds = (size_t)pt_query_lds_total<1>(a.t.ntri) * sizeof(float);
+    } else {
+        kernel = det_bounded ? pt_ao_kernel<true, 2, 0> : pt_ao_kernel<false, 2, 0>;
+        lds = (size_t)pt_query_lds_total<2>(a.t.ntri) * sizeof(float);
+    }
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(PT_TRACE_THREADS), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s)
+{
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(pt_ao_resolve_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, s, counts, image, npix, K, miss_value);
+    return hipGetLastError();
+}
+
+int ptk_ao_bvh_blocks_per_cu(void)
+{
+    int nb = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pt_ao_bvh_kernel<true, 3>, PT_TRACE_THREADS, ptk_trace_bvh_lds_bytes());
+    if (e != hipSuccess || nb < 1) nb = 2;
+    return nb;
 }

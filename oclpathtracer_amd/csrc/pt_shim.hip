@@ -123,6 +123,7 @@ struct pt_device_s {
     int nbig;
     int bvh_blocks_per_cu;
     int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query kernel (pt_intersect_rays)
+    int ao_bvh_blocks_per_cu;      // ... and of the LBVH ambient-occlusion kernel (pt_render_ao)
     bool bvh_valid;
     unsigned int* det_bound_dev;  // PT_PREP_WORDS device words written by the prep kernel
     // fused-render workspace: the STREAMING renderer.  A render walks its frames in chunks of S frames (as many as a ring slot
@@ -359,6 +360,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->blocks_per_cu = ptk_trace_blocks_per_cu(36);
     d->bvh_blocks_per_cu = ptk_trace_bvh_blocks_per_cu();
     d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
+    d->ao_bvh_blocks_per_cu = ptk_ao_bvh_blocks_per_cu();
     *out = d;
     return PT_OK;
 }
@@ -1559,21 +1561,41 @@ static bool ranges_overlap(const pt_buffer_s* a, size_t abytes, const pt_buffer_
     return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
 }
 
-extern "C" int pt_intersect_rays(pt_device_t d, pt_buffer_t triangles, int num_triangles, pt_buffer_t rays, pt_buffer_t out,
-                                 size_t num_rays, int mode, pt_event_t ev)
+// the search of a query, AO render or occlusion search over the prepared scene: its fields of PtTraceParams (PtQueryParams::t) --
+// the scene, the filter of the table the two-pass search runs over with its anchor in cam.eye, the LBVH -- and the filter mode,
+// PT_OPT_QUAD_FILTER as for renders (render_part; an empty scene has no table)
+static PtTraceParams search_params(const pt_device_s* d, int num_triangles, bool use_bvh, int& quads)
 {
-    int rc = use_device(d);
-    if (rc) return rc;
+    const PtFilterTable& ft = use_bvh ? d->big_filter : d->scene_filter;
+    quads = num_triangles > 0 && (d->opt_quads == 0 || d->opt_quads == 4) ? ft.quads : 0;
+    PtTraceParams t;
+    memset(&t, 0, sizeof t);
+    t.tris = d->prep;
+    t.ntri = num_triangles;
+    t.quad_delta1 = ft.delta1; t.ray_radius = ft.ray_radius;
+    t.p1tab = ft.p1tab; t.p1_lo = ft.p1_lo; t.p1_hi = ft.p1_hi;
+    memcpy(t.cam.eye, ft.anchor, sizeof t.cam.eye);   // the anchor the table was made about
+    t.bvh = d->bvh; t.bvh_records = (int32_t)d->bvh_records; t.grid = d->bvh_grid;
+    t.bigtab = d->bigtab; t.bigidx = d->bigidx; t.nbig = use_bvh ? d->nbig : 0;
+    t.bvh_flags = d->trav_dev; t.bvh_stack_limit = (int32_t)d->opt_bvh_stack;
+    return t;
+}
+
+// pt_intersect_rays / pt_occluded_rays up to the launch: the argument checks, the deferred error, the stream, the scene and the
+// kernel parameters (out_record: bytes per result)
+static int query_begin(pt_device_s* d, pt_buffer_s* triangles, int num_triangles, pt_buffer_s* rays, pt_buffer_s* out, size_t num_rays,
+                       size_t out_record, bool occluded, pt_event_s* ev, PtQueryParams& q, bool& use_bvh, int& quads)
+{
+    int rc;
     if (!triangles || !rays || !out) return fail(PT_ERR_INVALID, "null buffer handle");
     if (triangles->dev != d || rays->dev != d || out->dev != d) return fail(PT_ERR_INVALID, "buffer belongs to another device");
     if (ev && ev->dev != d) return fail(PT_ERR_INVALID, "event belongs to another device");
-    if (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_OCCLUDED) return fail(PT_ERR_INVALID, "mode %d is neither PT_QUERY_CLOSEST nor PT_QUERY_OCCLUDED", mode);
     if (num_triangles < 0) return fail(PT_ERR_INVALID, "num_triangles < 0");
     if ((size_t)num_triangles * sizeof(PtRawTriangle) > triangles->bytes)
         return fail(PT_ERR_RANGE, "triangle buffer holds %zu bytes, %d triangles need %zu", triangles->bytes, num_triangles,
                     (size_t)num_triangles * sizeof(PtRawTriangle));
     if (num_rays > 0x7fffffffu) return fail(PT_ERR_RANGE, "%zu rays: at most 2^31 - 1 per call", num_rays);
-    const size_t ray_bytes = num_rays * sizeof(pt_ray), out_bytes = num_rays * (mode == PT_QUERY_CLOSEST ? sizeof(pt_hit) : sizeof(int32_t));
+    const size_t ray_bytes = num_rays * sizeof(pt_ray), out_bytes = num_rays * out_record;
     if (ray_bytes > rays->bytes) return fail(PT_ERR_RANGE, "ray buffer holds %zu bytes, %zu rays need %zu", rays->bytes, num_rays, ray_bytes);
     if (out_bytes > out->bytes) return fail(PT_ERR_RANGE, "result buffer holds %zu bytes, %zu results need %zu", out->bytes, num_rays, out_bytes);
     if (num_rays && (((uintptr_t)rays->dptr | (uintptr_t)out->dptr) & 15u)) return fail(PT_ERR_INVALID, "ray and result buffers must be 16-byte aligned");
@@ -1581,31 +1603,134 @@ extern "C" int pt_intersect_rays(pt_device_t d, pt_buffer_t triangles, int num_t
     // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
     if ((rc = check_traversal(d))) return rc;
     if ((rc = enter_stream(d))) return rc;
-    bool use_bvh = false;
+    use_bvh = false;
     if (num_rays && num_triangles > 0 && (rc = prepare_search(d, triangles, num_triangles, nullptr, use_bvh))) return rc;
+    memset(&q, 0, sizeof q);
+    q.t = search_params(d, num_triangles, use_bvh, quads);
+    q.rays = (const float4*)rays->dptr;
+    q.out = out->dptr;
+    q.nrays = (uint32_t)num_rays;
+    q.occluded = occluded;
+    return PT_OK;
+}
+
+extern "C" int pt_intersect_rays(pt_device_t d, pt_buffer_t triangles, int num_triangles, pt_buffer_t rays, pt_buffer_t out,
+                                 size_t num_rays, int mode, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_OCCLUDED) return fail(PT_ERR_INVALID, "mode %d is neither PT_QUERY_CLOSEST nor PT_QUERY_OCCLUDED", mode);
+    PtQueryParams q;
+    bool use_bvh;
+    int quads;
+    if ((rc = query_begin(d, triangles, num_triangles, rays, out, num_rays, mode == PT_QUERY_CLOSEST ? sizeof(pt_hit) : sizeof(int32_t),
+                          mode == PT_QUERY_OCCLUDED, ev, q, use_bvh, quads)))
+        return rc;
     if ((rc = event_begin(d, ev))) return rc;
-    if (num_rays) {
-        const PtFilterTable& ft = use_bvh ? d->big_filter : d->scene_filter;
-        // PT_OPT_QUAD_FILTER as for renders (render_part); an empty scene has no table
-        const int quads = num_triangles > 0 && (d->opt_quads == 0 || d->opt_quads == 4) ? ft.quads : 0;
-        PtQueryParams q;
-        memset(&q, 0, sizeof q);
-        q.t.tris = d->prep;
-        q.t.ntri = num_triangles;
-        q.t.quad_delta1 = ft.delta1; q.t.ray_radius = ft.ray_radius;
-        q.t.p1tab = ft.p1tab; q.t.p1_lo = ft.p1_lo; q.t.p1_hi = ft.p1_hi;
-        memcpy(q.t.cam.eye, ft.anchor, sizeof q.t.cam.eye);   // the anchor the table was made about
-        q.t.bvh = d->bvh; q.t.bvh_records = (int32_t)d->bvh_records; q.t.grid = d->bvh_grid;
-        q.t.bigtab = d->bigtab; q.t.bigidx = d->bigidx; q.t.nbig = use_bvh ? d->nbig : 0;
-        q.t.bvh_flags = d->trav_dev; q.t.bvh_stack_limit = (int32_t)d->opt_bvh_stack;
-        q.rays = (const float4*)rays->dptr;
-        q.out = out->dptr;
-        q.nrays = (uint32_t)num_rays;
-        q.occluded = mode == PT_QUERY_OCCLUDED;
+    if (num_rays)
         HIP_TRY(ptk_query(q, d->prop.multiProcessorCount * d->query_bvh_blocks_per_cu, num_triangles > 0 && d->prep_det_bounded, quads, use_bvh,
                           d->stream));
+    out->version++;
+    return event_end(d, ev);
+}
+
+// PT_QUERY_OCCLUDED by a search that stops at the first accepted triangle: the any-hit LBVH kernel; brute force keeps the two-pass
+// closest search (a few dozen triangles leave little to stop early from)
+extern "C" int pt_occluded_rays(pt_device_t d, pt_buffer_t triangles, int num_triangles, pt_buffer_t rays, pt_buffer_t out,
+                                size_t num_rays, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    PtQueryParams q;
+    bool use_bvh;
+    int quads;
+    if ((rc = query_begin(d, triangles, num_triangles, rays, out, num_rays, sizeof(int32_t), true, ev, q, use_bvh, quads))) return rc;
+    if ((rc = event_begin(d, ev))) return rc;
+    if (num_rays) {
+        const bool det_bounded = num_triangles > 0 && d->prep_det_bounded;
+        if (use_bvh) HIP_TRY(ptk_occluded_bvh(q, d->prop.multiProcessorCount * d->query_bvh_blocks_per_cu, det_bounded, quads, d->stream));
+        else HIP_TRY(ptk_query(q, 0, det_bounded, quads, false, d->stream));
     }
     out->version++;
+    return event_end(d, ev);
+}
+
+// ---- ambient occlusion (include/pt_shim.h) -----------------------------------------------------------------------------------
+static_assert(sizeof(pt_ao_params) == 64, "pt_ao_params layout");
+
+extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t counts, pt_buffer_t image, const pt_ao_params* params,
+                            const pt_camera* cam, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
+    const pt_ao_params a = *params;
+    PtCamera c = reference_camera();
+    if (cam && (rc = camera_derive(cam, &c))) return rc;
+    if (!triangles || !counts) return fail(PT_ERR_INVALID, "null buffer handle");
+    if (triangles->dev != d || counts->dev != d || (image && image->dev != d)) return fail(PT_ERR_INVALID, "buffer belongs to another device");
+    if (ev && ev->dev != d) return fail(PT_ERR_INVALID, "event belongs to another device");
+    if (a.width < 1 || a.height < 1 || a.frame_begin < 0 || a.frame_count < 0 || a.num_triangles < 0 || a.rays_per_sample < 1 ||
+        a.rays_per_sample > 256 || !(std::isfinite(a.radius) && a.radius > 0.0f) || !std::isfinite(a.miss_value) || a.stripe_rows < 1 ||
+        a.n_ranks < 1 || a.rank < 0 || a.rank >= a.n_ranks)
+        return fail(PT_ERR_INVALID, "invalid AO parameters");
+    for (int i = 0; i < 5; ++i)
+        if (a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    if ((long long)a.width * a.height > 0x7fffffffLL) return fail(PT_ERR_INVALID, "image too large");
+    if ((long long)a.frame_begin + a.frame_count > 0x7fffffffLL) return fail(PT_ERR_INVALID, "frame index overflow");
+    // open <= frames K and K hits <= frames K: neither uint32 count can wrap
+    if (((long long)a.frame_begin + a.frame_count) * a.rays_per_sample > 0xffffffffLL)
+        return fail(PT_ERR_RANGE, "(frame_begin + frame_count) x rays_per_sample exceeds 2^32 - 1: the counts could wrap");
+    const uint32_t npix = (uint32_t)((uint64_t)pt_local_rows(a.height, a.stripe_rows, a.n_ranks, a.rank) * (uint64_t)a.width);
+    const size_t count_bytes = (size_t)npix * 8, image_bytes = (size_t)npix * sizeof(float4);
+    if ((size_t)a.num_triangles * sizeof(PtRawTriangle) > triangles->bytes)
+        return fail(PT_ERR_RANGE, "triangle buffer holds %zu bytes, %d triangles need %zu", triangles->bytes, a.num_triangles,
+                    (size_t)a.num_triangles * sizeof(PtRawTriangle));
+    if (count_bytes > counts->bytes) return fail(PT_ERR_RANGE, "count buffer holds %zu bytes, %u pixels need %zu", counts->bytes, npix, count_bytes);
+    if (image && image_bytes > image->bytes) return fail(PT_ERR_RANGE, "image buffer holds %zu bytes, %u pixels need %zu", image->bytes, npix, image_bytes);
+    if ((uintptr_t)counts->dptr & 7u) return fail(PT_ERR_INVALID, "the count buffer must be 8-byte aligned");
+    if (image && ((uintptr_t)image->dptr & 15u)) return fail(PT_ERR_INVALID, "the image buffer must be 16-byte aligned");
+    if (image && ranges_overlap(counts, count_bytes, image, image_bytes)) return fail(PT_ERR_INVALID, "the counts and the image overlap");
+    // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
+    if ((rc = check_traversal(d))) return rc;
+    if ((rc = enter_stream(d))) return rc;
+    if (a.frame_count == 0 || npix == 0) {
+        if ((rc = event_begin(d, ev))) return rc;
+        return event_end(d, ev);
+    }
+    bool use_bvh = false;
+    if (a.num_triangles > 0 && (rc = prepare_search(d, triangles, a.num_triangles, nullptr, use_bvh))) return rc;
+    if ((rc = event_begin(d, ev))) return rc;
+    if (a.frame_begin == 0) HIP_TRY(hipMemsetAsync(counts->dptr, 0, count_bytes, d->stream));   // the :314-321 rule: frame 0 starts afresh
+    if (a.num_triangles > 0) {
+        int quads;
+        PtAoParams p;
+        memset(&p, 0, sizeof p);
+        p.t = search_params(d, a.num_triangles, use_bvh, quads);
+        p.t.width = a.width; p.t.height = a.height;
+        p.t.inv_width = 1.0f / (float)a.width;     // the renderer's per-image constants (trace_params)
+        p.t.inv_height = 1.0f / (float)a.height;
+        p.t.aspect = (float)a.width / (float)a.height;
+        p.t.stripe_rows = a.stripe_rows; p.t.n_ranks = a.n_ranks; p.t.rank = a.rank;
+        p.t.npix_local = npix;
+        p.cam = c;
+        p.counts = (unsigned long long*)counts->dptr;
+        p.npix = npix;
+        p.K = a.rays_per_sample;
+        p.tlim = a.radius < 1e20f ? a.radius : 1e20f;
+        // frame-major samples, fewer than 2^31 per launch
+        const int per_launch = (int)std::max<uint32_t>(1u, 0x7fffffffu / npix);
+        const int blocks = d->prop.multiProcessorCount * (use_bvh ? d->ao_bvh_blocks_per_cu : 0);
+        for (int64_t done = 0; done < a.frame_count; done += per_launch) {   // (64-bit: done + per_launch may pass 2^31 - 1)
+            const int nf = (int)std::min<int64_t>(per_launch, a.frame_count - done);
+            p.frame0 = a.frame_begin + (int)done;
+            p.nitems = (uint32_t)nf * npix;
+            HIP_TRY(ptk_ao(p, blocks, d->prep_det_bounded, quads, use_bvh, d->stream));
+        }
+    }
+    if (image) HIP_TRY(ptk_ao_resolve((const uint2*)counts->dptr, (float4*)image->dptr, npix, (uint32_t)a.rays_per_sample, a.miss_value, d->stream));
+    counts->version++;
+    if (image) image->version++;
     return event_end(d, ev);
 }
 

@@ -32,6 +32,7 @@ RAY_WORDS, HIT_WORDS = 8, 12   # float32 words per record: the torch layouts [N,
 # frees one: torch's caching allocator hands the same blocks back, and a wrap is reused for whatever tensor occupies its range.
 # Wraps beyond this many are freed only where the caster waits for the device anyway (the numpy path) and at release().
 _WRAP_KEEP = 64
+_EARLY_EXIT = -1   # RayCaster._query: occlusion by pt_occluded_rays (not a pt_intersect_rays mode)
 
 
 def make_rays(origins, dirs, tmax=1e20) -> np.ndarray:
@@ -141,9 +142,19 @@ class RayCaster:
         rays; view it as int32 for tri and material)."""
         return self._query(rays, shim.PT_QUERY_CLOSEST)
 
-    def occluded(self, rays):
-        """1 where the ray hits some triangle at 0 < t < min(tmax, 1e20), else 0: int32 [N], numpy or a device tensor."""
-        return self._query(rays, shim.PT_QUERY_OCCLUDED)
+    def occluded(self, rays, early_exit: bool = False):
+        """1 where the ray hits some triangle at 0 < t < min(tmax, 1e20), else 0: int32 [N], numpy or a device tensor.
+        ``early_exit``: the search stops at the first triangle accepted below the limit (``pt_occluded_rays``); the result is the
+        same array."""
+        if not isinstance(early_exit, bool):
+            raise TypeError("early_exit must be a bool")
+        return self._query(rays, _EARLY_EXIT if early_exit else shim.PT_QUERY_OCCLUDED)
+
+    def _launch(self, rb, ob, n: int, mode: int, ev) -> None:
+        if mode == _EARLY_EXIT:
+            shim.check(self._lib.pt_occluded_rays(self.dev._h, self.tbuf._h, self.num_triangles, rb._h, ob._h, n, ev))
+        else:
+            shim.check(self._lib.pt_intersect_rays(self.dev._h, self.tbuf._h, self.num_triangles, rb._h, ob._h, n, mode, ev))
 
     def _query(self, rays, mode: int):
         if _is_tensor(rays):
@@ -155,7 +166,7 @@ class RayCaster:
         ob = self._staging("out", out.nbytes)
         if n:
             rb.write(r.view(np.uint8), r.nbytes)
-        shim.check(self._lib.pt_intersect_rays(self.dev._h, self.tbuf._h, self.num_triangles, rb._h, ob._h, n, mode, None))
+        self._launch(rb, ob, n, mode, None)
         if n:
             ob.read(out.view(np.uint8), out.nbytes)
         self.dev.waitForCompletion()
@@ -176,7 +187,7 @@ class RayCaster:
         rb, ob = self._wrap(rays), self._wrap(out)
         ev = self._event()
         self.dev.waitStream(stream.cuda_stream)   # the rays are written and the results' memory is free on torch's stream
-        shim.check(self._lib.pt_intersect_rays(self.dev._h, self.tbuf._h, self.num_triangles, rb._h, ob._h, n, mode, ev._h))
+        self._launch(rb, ob, n, mode, ev._h)
         ev.waitOnStream(stream.cuda_stream)       # torch's later work sees the results
         return out
 

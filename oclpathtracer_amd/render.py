@@ -163,6 +163,19 @@ class Renderer:
 
         return RayCaster(self.dev, self.tbuf, num_triangles=self.num_triangles)
 
+    def ao_renderer(self, **kw):
+        """An :class:`ao.AORenderer` of this renderer's image over its triangle buffer (keyword arguments: AORenderer's; the
+        image size, camera and sharding default to this renderer's): AO renders and renders share the device's prepared scene and
+        LBVH.  Release it before the renderer."""
+        from .ao import AORenderer
+
+        kw.setdefault("camera", self.camera)
+        kw.setdefault("stripe_rows", self.stripe_rows)
+        kw.setdefault("n_ranks", self.n_ranks)
+        kw.setdefault("rank", self.rank)
+        return AORenderer(self.dev, self.tbuf, kw.pop("width", self.width), kw.pop("height", self.height),
+                          num_triangles=kw.pop("num_triangles", self.num_triangles), **kw)
+
     def global_rows(self) -> np.ndarray:
         """Global row index of every local row (ascending)."""
         rows = np.arange(self.height)

@@ -82,6 +82,20 @@ class Hit(_c.Structure):
     ]
 
 
+class AoParams(_c.Structure):
+    """pt_ao_params (64 bytes): image, frames, triangles, K occlusion rays per hit, their radius, the value of a pixel never hit,
+    image sharding as RenderParams; reserved must be 0."""
+
+    _fields_ = [
+        ("width", _c.c_int32), ("height", _c.c_int32),
+        ("frame_begin", _c.c_int32), ("frame_count", _c.c_int32),
+        ("num_triangles", _c.c_int32), ("rays_per_sample", _c.c_int32),
+        ("radius", _c.c_float), ("miss_value", _c.c_float),
+        ("stripe_rows", _c.c_int32), ("n_ranks", _c.c_int32), ("rank", _c.c_int32),
+        ("reserved", _c.c_int32 * 5),
+    ]
+
+
 # every symbol include/pt_shim.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "pt_last_error": (_c.c_char_p, []),
@@ -136,6 +150,8 @@ SIGNATURES = {
     "pt_render_frames_camera": (_c.c_int, [_H, _H, _H, _H, _c.POINTER(RenderParams), _c.POINTER(Camera), _H, _H]),
     "pt_intersect_rays": (_c.c_int, [_H, _H, _c.c_int, _H, _H, _c.c_size_t, _c.c_int, _H]),
     "pt_camera_rays": (_c.c_int, [_H, _c.POINTER(Camera), _c.c_int, _c.c_int, _c.c_int, _H, _H]),
+    "pt_occluded_rays": (_c.c_int, [_H, _H, _c.c_int, _H, _H, _c.c_size_t, _H]),
+    "pt_render_ao": (_c.c_int, [_H, _H, _H, _H, _c.POINTER(AoParams), _c.POINTER(Camera), _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_profile_query_union": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double)]),
