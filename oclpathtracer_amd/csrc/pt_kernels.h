@@ -232,11 +232,11 @@ struct PtQueryParams {
     uint32_t nrays;
     int32_t occluded;
 };
-// bvh_blocks: the persistent grid of the LBVH kernel (CUs x ptk_query_bvh_blocks_per_cu)
-hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s);
+// bvh_blocks: the persistent grid of the LBVH kernel (CUs x ptk_query_bvh_blocks_per_cu: the driver's kernels -- closest, any-hit, AO -- are all
+// pinned to five waves per SIMD and use the trace kernel's LDS, so one figure, the closest kernel's, sizes every such grid)
+// any: (bvh and q.occluded only) pt_occluded_rays: an any-hit search, which stops at the first accepted triangle
+hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, bool bvh, bool any, hipStream_t s);
 int ptk_query_bvh_blocks_per_cu(void);
-// pt_occluded_rays through the LBVH: the any-hit search on the query kernel's persistent grid (brute force: ptk_query, occluded)
-hipError_t ptk_occluded_bvh(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, hipStream_t s);
 // ambient occlusion (pt_render_ao): t carries the search as PtQueryParams::t does (the filter's anchor in t.cam.eye) and the image
 // geometry (width, inv_width, inv_height, aspect, stripe_rows, n_ranks, rank); cam is the camera
 struct PtAoParams {
@@ -250,7 +250,6 @@ struct PtAoParams {
     float tlim;                   // min(radius, 1e20)
 };
 hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s);
-int ptk_ao_bvh_blocks_per_cu(void);
 // image[i] = float4(a, a, a, 1) of counts[i] = {open, hits}: a = open / (K hits), miss_value when hits = 0
 hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s);
 // rays[2 gid], rays[2 gid + 1] = the pt_ray of pixel gid, frame `frame` (the renderer's sample start) for the camera cam

@@ -1307,6 +1307,19 @@ PTK_DEV unsigned pt_stripe_row(const PtTraceParams& P, pt_kargs_p K, unsigned sl
     return (sl * (unsigned)PT_ARG(n_ranks) + (unsigned)PT_ARG(rank)) * (unsigned)PT_ARG(stripe_rows) + within;
 }
 
+// local pixel lp of a rank's stripes -> its column and its row in the whole image
+template <bool LATE>
+PTK_DEV void pt_pixel_xy(const PtTraceParams& P, pt_kargs_p K, unsigned lp, unsigned& x, unsigned& grow)
+{
+    const unsigned lr = lp / (unsigned)PT_ARG(width);
+    x = lp - lr * (unsigned)PT_ARG(width);
+    grow = lr;
+    if (PT_ARG(n_ranks) > 1) {
+        const unsigned sl = lr / (unsigned)PT_ARG(stripe_rows);
+        grow = pt_stripe_row<LATE>(P, K, sl, lr - sl * (unsigned)PT_ARG(stripe_rows));
+    }
+}
+
 // a new sample of (column x, global row grow) -- local pixel lp, frame `frame` of the render -- at bounce 0: seed :308, camera ray :310
 template <bool LATE>
 PTK_DEV void pt_sample_begin(const PtTraceParams& P, pt_kargs_p K, unsigned x, unsigned grow, unsigned lp, unsigned frame, PtPath& s)
@@ -1385,15 +1398,26 @@ PTK_DEV PtTail pt_tail_init(pt_lds_u32* w, unsigned tile, unsigned lane)
     return tl;
 }
 
+// the first n prepared records (12 of their 16 dwords each) into the front of the workgroup's LDS; the caller's barrier follows
+PTK_DEV void pt_lds_table_load(const PtPrepTriangle* tris, int n)
+{
+    const float* g = reinterpret_cast<const float*>(tris);
+    for (int k = (int)threadIdx.x; k < n * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
+        const int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
+        pt_lds_tab[k] = g[tri * 16 + w];
+    }
+}
+
 // ---- the LDS of a table-kernel workgroup, in dwords (the bodies, ptk_trace_lds_bytes): the triangle table (LDS_TABLE 1,
 // ntri <= PT_LDS_TRI_MAX), then the waves' pools of parked paths (PT_POOL_DWORDS each), then their pass-2 tails (64 x 8 B keys + PT_TAIL_LIST
 // pairs of 2 B beside the table, of 4 B without), then their record tiles of the current 32-triangle chunk (LDS_TABLE 2: TILED)
 #define PT_LDS_TILE_DW (32u * PT_LDS_TRI_STRIDE)
 template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_tail_dw() { return 128u + (LDS_TABLE == 1 ? PT_TAIL_LIST / 2u : PT_TAIL_LIST); }
 template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_pools(int ntri) { return LDS_TABLE == 1 ? ntri * PT_LDS_TRI_STRIDE : 0; }
-template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_tails(int ntri) { return pt_lds_pools<LDS_TABLE>(ntri) + (PT_TRACE_THREADS / 64) * PT_POOL_DWORDS; }
-template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_tiles(int ntri) { return pt_lds_tails<LDS_TABLE>(ntri) + (PT_TRACE_THREADS / 64) * pt_lds_tail_dw<LDS_TABLE>(); }
-template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_total(int ntri) { return pt_lds_tiles<LDS_TABLE>(ntri) + (LDS_TABLE == 2 ? (PT_TRACE_THREADS / 64) * PT_LDS_TILE_DW : 0u); }
+// (POOLS = false: the brute-force query and AO kernels, which park nothing)
+template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ unsigned pt_lds_tails(int ntri) { return pt_lds_pools<LDS_TABLE>(ntri) + (POOLS ? (PT_TRACE_THREADS / 64) * PT_POOL_DWORDS : 0u); }
+template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ unsigned pt_lds_tiles(int ntri) { return pt_lds_tails<LDS_TABLE, POOLS>(ntri) + (PT_TRACE_THREADS / 64) * pt_lds_tail_dw<LDS_TABLE>(); }
+template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ unsigned pt_lds_total(int ntri) { return pt_lds_tiles<LDS_TABLE, POOLS>(ntri) + (LDS_TABLE == 2 ? (PT_TRACE_THREADS / 64) * PT_LDS_TILE_DW : 0u); }
 
 template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
 PTK_DEV void pt_trace_body(const PtTraceParams& P)
@@ -1402,11 +1426,7 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
     pt_const_f32p T = (pt_const_f32p)(const float*)P.tris;
     const int ntri = P.ntri;
     if (LDS_TABLE == 1) {
-        const float* g = reinterpret_cast<const float*>(P.tris);
-        for (int k = (int)threadIdx.x; k < ntri * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
-            int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
-            pt_lds_tab[k] = g[tri * 16 + w];
-        }
+        pt_lds_table_load(P.tris, ntri);
         __syncthreads();
     }
     // this wave's pool of parked paths, pass-2 tail and record tile
@@ -1592,12 +1612,8 @@ PTK_DEV void pt_regenerate_lanes(const PtTraceParams& P, unsigned lane, PtWaveQu
         const unsigned rank = pt_mbcnt(need);
         if (!alive && rank < take) {
             const unsigned lp = q.pix + rank;
-            const unsigned lr = lp / (unsigned)PT_ARG(width), x = lp - lr * (unsigned)PT_ARG(width);
-            unsigned grow = lr;
-            if (PT_ARG(n_ranks) > 1) {
-                const unsigned sl = lr / (unsigned)PT_ARG(stripe_rows);
-                grow = pt_stripe_row<LATE>(P, K, sl, lr - sl * (unsigned)PT_ARG(stripe_rows));
-            }
+            unsigned x, grow;
+            pt_pixel_xy<LATE>(P, K, lp, x, grow);
             pt_sample_begin<LATE>(P, K, x, grow, lp, q.frame, s);
             alive = true;
         }
@@ -1771,6 +1787,8 @@ PTK_DEV void pt_bvh_round(const PtTraceParams& P, PtBvhLane& L, PtTail& tl, unsi
 // child-order table
 // (ANY, any: pt_bvh_round -- an any-hit lane leaves its traversal at the first accepted pair; its pairs still in the ring are
 // tested for it alone and change nothing)
+// c_*: the search's work counters, touched by the TALLY instantiations alone.  (Five scalars on purpose: bundled into a struct they move
+// the compiled code of the timed trace kernels, profiles/driver/disasm_comparison.txt.)  A caller that keeps none uses the form below.
 template <bool DET_BOUNDED, bool TALLY, bool ANY = false>
 PTK_DEV void pt_bvh_step(const PtTraceParams& P, PtBvhLane& L, bool& trav, const f3& o, const f3& d, pt_lds_u32* stk, unsigned* ovf,
                          const pt_lds_u8* nxt, PtTail& tl, unsigned lane, unsigned n_recs, unsigned& c_nodes, unsigned& c_leaves,
@@ -1867,25 +1885,22 @@ PTK_DEV void pt_bvh_step(const PtTraceParams& P, PtBvhLane& L, bool& trav, const
     }
     if (ANY && any && L.hidx >= 0) trav = false;
 }
-
-// BIGQ: the filter of the brute-force search over the big triangles: 0 = independent triangles, 3 = the packed shared-u filter
-// (their table is made of quads -- the Cornell box's walls among a soup -- and the host prepared its pass-1 table)
-template <bool DET_BOUNDED, bool TALLY, int BIGQ>
-PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
+// ... for the callers that keep no counters (pt_bvh_drive)
+template <bool DET_BOUNDED, bool ANY>
+PTK_DEV void pt_bvh_step(const PtTraceParams& P, PtBvhLane& L, bool& trav, const f3& o, const f3& d, pt_lds_u32* stk, unsigned* ovf,
+                         const pt_lds_u8* nxt, PtTail& tl, unsigned lane, unsigned n_recs, bool any)
 {
-    const unsigned lane = pt_lane_id();
-    const int ntri = P.ntri;
-    const unsigned n_recs = (unsigned)P.bvh_records;
-    // LDS (pt_bvh_lds_*): the table of the triangles outside the hierarchy (pass 2 fetches its records per lane: pt_fetch_rec)
-    {
-        const float* g = reinterpret_cast<const float*>(P.bigtab);
-        for (int k = (int)threadIdx.x; k < P.nbig * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
-            const int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
-            pt_lds_tab[k] = g[tri * 16 + w];
-        }
-    }
-    // which child of a group comes next: nxt[oct << 8 | hits] = the slot s among the hits (by slot) with the largest
-    // s ^ oct -- the octant nearest to where the ray comes from
+    unsigned c32 = 0u;
+    unsigned long long c64 = 0ull;
+    pt_bvh_step<DET_BOUNDED, false, ANY>(P, L, trav, o, d, stk, ovf, nxt, tl, lane, n_recs, c32, c32, c64, c64, c32, any);
+}
+
+// What an LBVH workgroup holds in LDS before its loop (pt_bvh_lds_*): the table of the triangles outside the hierarchy (pass 2
+// fetches its records per lane: pt_fetch_rec) and the 2 KB child-order table, which it returns: nxt[oct << 8 | hits] = the slot s
+// among the hits (by slot) with the largest s ^ oct -- the octant nearest to where the ray comes from
+PTK_DEV pt_lds_u8* pt_bvh_wg_setup(const PtTraceParams& P)
+{
+    pt_lds_table_load(P.bigtab, P.nbig);
     pt_lds_u8* nxt = (pt_lds_u8*)((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_nxt());
     for (unsigned k = threadIdx.x; k < 2048u; k += PT_TRACE_THREADS) {
         const unsigned o = k >> 8, h = k & 255u;
@@ -1895,6 +1910,55 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
         nxt[k] = (unsigned char)best;
     }
     __syncthreads();
+    return nxt;
+}
+
+// a lane's search state at the start of a new ray: the limit, no hit
+PTK_DEV void pt_bvh_lane_clear(PtBvhLane& L, float tlim)
+{
+    L.tmax = tlim; L.hu = 0.0f; L.hv = 0.0f; L.hidx = -1;
+}
+
+PTK_DEV PtBvhLane pt_bvh_lane_idle(float tlim)   // what a lane that searches nothing holds
+{
+    PtBvhLane L;
+    pt_bvh_lane_clear(L, tlim);
+    L.gbase = L.gm = L.oct = 0u; L.sp = 0; L.ix = L.iy = L.iz = 0.0f; L.budget = 0u;
+    return L;
+}
+
+// The start of a ray's LBVH search for the lanes in `start`: the triangles outside the hierarchy by the two-pass search (its
+// tail shares the key slots with pt_bvh_round and expects them empty: the ring has just been flushed), then the root.  An
+// any-hit ray (any) that hits one of them is done: it does not traverse.
+template <bool DET_BOUNDED, int BIGQ>
+PTK_DEV void pt_bvh_search_start(const PtTraceParams& P, PtBvhLane& L, bool& trav, bool start, bool any, const f3& o, const f3& d,
+                                 PtTail& tl, unsigned lane)
+{
+    if (__ballot(start) == 0ull) return;
+    if (P.nbig > 0) {
+        int hp = -1;
+        tl.keys[lane] = ~0ull;
+        pt_intersect_two_pass<DET_BOUNDED, 1, (DET_BOUNDED ? BIGQ : 0)>((pt_const_f32p)(const float*)P.bigtab, P.bigtab, P.nbig, o, d, start,
+                                                                          L.tmax, L.hu, L.hv, hp, P.quad_delta1, P.ray_radius,
+                                                                          (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi,
+                                                                          mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]), tl, lane);
+        if (start && hp >= 0) L.hidx = P.bigidx[hp];
+    }
+    if (start && !(any && L.hidx >= 0)) {
+        pt_bvh_lane_start(L, d, P.ntri);
+        trav = true;
+    }
+}
+
+// BIGQ: the filter of the brute-force search over the big triangles: 0 = independent triangles, 3 = the packed shared-u filter
+// (their table is made of quads -- the Cornell box's walls among a soup -- and the host prepared its pass-1 table)
+template <bool DET_BOUNDED, bool TALLY, int BIGQ>
+PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
+{
+    const unsigned lane = pt_lane_id();
+    const int ntri = P.ntri;
+    const unsigned n_recs = (unsigned)P.bvh_records;
+    const pt_lds_u8* nxt = pt_bvh_wg_setup(P);
     // stack entry e of this lane: stk[2 e * PT_TRACE_THREADS] = base, stk[(2 e + 1) * PT_TRACE_THREADS] = masks
     pt_lds_u32* stk = (pt_lds_u32*)pt_lds_tab + pt_bvh_lds_stacks() + threadIdx.x;
     unsigned ovf[2 * (PT_BVH_STACK - PT_BVH_LDS_STACK)];
@@ -1923,9 +1987,7 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
             parked = alive;
         }
     }
-    PtBvhLane L;  // the search's state
-    L.tmax = 1e20f; L.hu = 0.0f; L.hv = 0.0f; L.hidx = -1;
-    L.gbase = L.gm = L.oct = 0u; L.sp = 0; L.ix = L.iy = L.iz = 0.0f; L.budget = 0u;
+    PtBvhLane L = pt_bvh_lane_idle(1e20f);  // the search's state
     unsigned c_nodes = 0, c_leaves = 0, c_maxsp = 0, c_graze = 0;
     unsigned long long c_steps = 0, c_tsteps = 0;
 
@@ -1979,7 +2041,8 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
             const bool start = alive && !trav;
             parked = false;
             if (__ballot(start) != 0ull) {
-                if (start) { L.tmax = 1e20f; L.hu = 0.0f; L.hv = 0.0f; L.hidx = -1; }
+                if (start) pt_bvh_lane_clear(L, 1e20f);
+                // (pt_bvh_search_start's steps, kept in place here: routed through it, this kernel's compiled code moves)
                 if (P.nbig > 0) {
                     // the triangles outside the hierarchy, in ascending index order; hp = position in their table.  (Its tail
                     // shares the key slots with pt_bvh_round and expects them empty: the ring has just been flushed.)
@@ -2416,6 +2479,18 @@ PTK_DEV PtQueryRay pt_query_idle()   // what a lane without a ray holds
     return r;
 }
 
+// pt_shade's deferred HitRecord (:127-130) of the hit (t, u, v) of the ray (o, d) on triangle hidx: the point and the normal;
+// returns the triangle's id field, as stored
+PTK_DEV float pt_hit_record(const PtPrepTriangle* tris, int hidx, const f3& o, const f3& d, float t, float u, float v, f3& p, f3& n)
+{
+    const float4 nid = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(tris + hidx) + 12);
+    const f3 N = mk3(nid.x, nid.y, nid.z);
+    p = add3(o, scale3(d, t));
+    const float w = 1.0f - u - v;
+    n = normalize3(add3(add3(scale3(N, u), scale3(N, v)), scale3(N, w)));
+    return nid.w;
+}
+
 // result i: a pt_hit (three 16-byte stores) or, for occlusion queries, 1 / 0
 PTK_DEV void pt_query_store(const PtQueryParams& Q, unsigned i, const PtQueryRay& r, float t, float u, float v, int hidx)
 {
@@ -2431,22 +2506,26 @@ PTK_DEV void pt_query_store(const PtQueryParams& Q, unsigned i, const PtQueryRay
         o[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
-    // pt_shade's deferred HitRecord (:127-130)
-    const float4 nid = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(Q.t.tris + hidx) + 12);
-    const f3 N = mk3(nid.x, nid.y, nid.z);
-    const f3 p = add3(r.o, scale3(r.d, t));
-    const float w = 1.0f - u - v;
-    const f3 n = normalize3(add3(add3(scale3(N, u), scale3(N, v)), scale3(N, w)));
+    f3 p, n;
+    const float id = pt_hit_record(Q.t.tris, hidx, r.o, r.d, t, u, v, p, n);
     o[0] = make_float4(t, __int_as_float(hidx), u, v);
-    o[1] = make_float4(p.x, p.y, p.z, nid.w);   // material: the triangle's id field, as stored
+    o[1] = make_float4(p.x, p.y, p.z, id);   // material
     o[2] = make_float4(n.x, n.y, n.z, 0.0f);
 }
 
-// LDS of a brute-force query workgroup, in dwords: the table (LDS_TABLE 1), the waves' pass-2 tails, their record tiles (LDS_TABLE 2)
-// -- the trace kernel's layout without the pools of parked paths
-template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_query_lds_tails(int ntri) { return pt_lds_pools<LDS_TABLE>(ntri); }
-template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_query_lds_tiles(int ntri) { return pt_query_lds_tails<LDS_TABLE>(ntri) + (PT_TRACE_THREADS / 64) * pt_lds_tail_dw<LDS_TABLE>(); }
-template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_query_lds_total(int ntri) { return pt_query_lds_tiles<LDS_TABLE>(ntri) + (LDS_TABLE == 2 ? (PT_TRACE_THREADS / 64) * PT_LDS_TILE_DW : 0u); }
+// What a brute-force query / AO workgroup holds in LDS before its search: the table (LDS_TABLE 1), the waves' pass-2 tails, their record
+// tiles (LDS_TABLE 2) -- the trace kernel's layout without the pools of parked paths (pt_lds_*, POOLS = false).  Returns this wave's tail.
+template <int LDS_TABLE>
+PTK_DEV PtTail pt_table_wg_setup(const PtTraceParams& P, unsigned lane)
+{
+    if (LDS_TABLE == 1) {
+        pt_lds_table_load(P.tris, P.ntri);
+        __syncthreads();
+    }
+    const unsigned wave_in_wg = pt_wave_in_wg();
+    return pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_lds_tails<LDS_TABLE, false>(P.ntri) + wave_in_wg * pt_lds_tail_dw<LDS_TABLE>(),
+                        pt_lds_tiles<LDS_TABLE, false>(P.ntri) + wave_in_wg * PT_LDS_TILE_DW, lane);
+}
 
 // brute force: one wave = 64 consecutive rays, one search (the search is wave-uniform over the triangles: every lane finishes
 // together, so there is nothing to refill)
@@ -2456,17 +2535,7 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_query_kernel(const PtQuer
     const PtTraceParams& P = Q.t;
     const unsigned lane = pt_lane_id();
     const int ntri = P.ntri;
-    if (LDS_TABLE == 1) {
-        const float* g = reinterpret_cast<const float*>(P.tris);
-        for (int k = (int)threadIdx.x; k < ntri * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
-            const int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
-            pt_lds_tab[k] = g[tri * 16 + w];
-        }
-        __syncthreads();
-    }
-    const unsigned wave_in_wg = pt_wave_in_wg();
-    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_query_lds_tails<LDS_TABLE>(ntri) + wave_in_wg * pt_lds_tail_dw<LDS_TABLE>(),
-                             pt_query_lds_tiles<LDS_TABLE>(ntri) + wave_in_wg * PT_LDS_TILE_DW, lane);
+    PtTail tl = pt_table_wg_setup<LDS_TABLE>(P, lane);
     const unsigned i = pt_wave() * 64u + lane;
     const bool act = i < Q.nrays;
     const PtQueryRay r = act ? pt_query_load(Q.rays, i) : pt_query_idle();
@@ -2479,103 +2548,119 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_query_kernel(const PtQuer
     if (act) pt_query_store(Q, i, r, tmax, hu, hv, hidx);
 }
 
-// LBVH: a persistent grid; wave w takes the groups of 64 consecutive rays w, w + W, w + 2W ... (W = the grid's waves) and, like the
-// LBVH trace kernel, refills its finished lanes with the next rays as soon as no more than PT_BVH_REFILL lanes still traverse
-// (pt_regenerate_lanes), so that a wave does not wait for its slowest ray.  Its LDS is the trace kernel's (pt_bvh_lds_*).
-template <bool DET_BOUNDED, int BIGQ>
-__global__ __launch_bounds__(PT_TRACE_THREADS) PT_BVH_WAVES_ATTR
-void pt_query_bvh_kernel(const PtQueryParams Q)
+// ---- the persistent LBVH search driver (pt_query_bvh_kernel, pt_ao_bvh_kernel) -----------------------------------------------
+// A persistent grid over n work items: wave w takes the groups of 64 consecutive items w, w + W, w + 2W ... (W = the grid's
+// waves).  Its cursor is wave-uniform: [next, gend) is what is left of the wave's current group; groups start at multiples of 64.
+struct PtWorkCursor { unsigned next, gend, stride, n; };
+
+PTK_DEV PtWorkCursor pt_cursor_init(unsigned n)
 {
-    const PtTraceParams& P = Q.t;
-    const unsigned lane = pt_lane_id();
-    const int ntri = P.ntri;
-    const unsigned n_recs = (unsigned)P.bvh_records;
-    {
-        const float* g = reinterpret_cast<const float*>(P.bigtab);
-        for (int k = (int)threadIdx.x; k < P.nbig * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
-            const int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
-            pt_lds_tab[k] = g[tri * 16 + w];
+    PtWorkCursor c;
+    c.n = n;
+    c.stride = gridDim.x * (PT_TRACE_THREADS / 64) * 64u;
+    c.next = pt_wave() * 64u;
+    c.gend = c.next + 64u < n ? c.next + 64u : n;
+    return c;
+}
+
+// the lanes without an item take the wave's next ones, in order (the lane of rank r among them: item next + r -- neighbours get
+// neighbouring rays); true for a lane that got one, which is alive from then on
+PTK_DEV bool pt_cursor_take(PtWorkCursor& c, bool& alive, unsigned& item)
+{
+    bool got = false;
+    for (unsigned long long need = __ballot(!alive); need != 0ull && c.next < c.n; need = __ballot(!alive)) {
+        const unsigned n_need = (unsigned)__popcll(need), avail = c.gend - c.next;
+        const unsigned take = n_need < avail ? n_need : avail;
+        const unsigned rank = pt_mbcnt(need);
+        if (!alive && rank < take) {
+            item = c.next + rank;
+            alive = got = true;
+        }
+        c.next += take;
+        if (c.next == c.gend) {   // the wave's next group
+            c.next = ((c.gend - 1u) & ~63u) + c.stride;
+            c.next = c.next < c.n ? c.next : c.n;
+            c.gend = c.next + 64u < c.n ? c.next + 64u : c.n;
         }
     }
-    pt_lds_u8* nxt = (pt_lds_u8*)((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_nxt());
-    for (unsigned k = threadIdx.x; k < 2048u; k += PT_TRACE_THREADS) {
-        const unsigned o = k >> 8, h = k & 255u;
-        unsigned best = 0u, bp = 0u;
-        for (unsigned sl = 0; sl < 8u; ++sl)
-            if (((h >> sl) & 1u) && ((sl ^ o) >= bp)) { bp = sl ^ o; best = sl; }
-        nxt[k] = (unsigned char)best;
-    }
-    __syncthreads();
+    return got;
+}
+
+// The loop of a persistent LBVH kernel.  Like the LBVH trace kernel it steps all traversing lanes together and, as soon as no more
+// than PT_BVH_REFILL of them still traverse, refills: the lanes whose search has ended hand it to their work (next_ray), which may
+// go on with another ray of the same item; the free ones take the wave's next items (begin); all of them start their searches
+// while the stragglers keep theirs, so that a wave does not wait for its slowest ray.  Its LDS is the trace kernel's (pt_bvh_lds_*).
+// Work, per lane:  n            the launch's items (uniform)
+//                  begin(item)  the lane takes an item: its first ray
+//                  next_ray(L)  the search of the current ray has ended with L: keep the result; true = the item has another ray
+//                  org(), dir(), limit(), live()   the current ray, its tmax, whether it searches anything at all
+//                  ANY, any()   some searches are any-hit ones (pt_bvh_round) / the current one is
+template <bool DET_BOUNDED, int BIGQ, class Work>
+PTK_DEV void pt_bvh_drive(const PtTraceParams& P, Work& W)
+{
+    const unsigned lane = pt_lane_id();
+    const unsigned n_recs = (unsigned)P.bvh_records;
+    const pt_lds_u8* nxt = pt_bvh_wg_setup(P);
     pt_lds_u32* stk = (pt_lds_u32*)pt_lds_tab + pt_bvh_lds_stacks() + threadIdx.x;
     unsigned ovf[2 * (PT_BVH_STACK - PT_BVH_LDS_STACK)];
     PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_tails() + (threadIdx.x >> 6) * PT_BVH_TAIL_DW, 0u, lane);
-    pt_const_f32p bigT = (pt_const_f32p)(const float*)P.bigtab;
-    const f3 anchor = mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]);
-
-    // the wave's rays (wave-uniform): [next, gend) of its current group; groups start at multiples of 64
-    const unsigned stride = gridDim.x * (PT_TRACE_THREADS / 64) * 64u;
-    const unsigned nrays = Q.nrays;
-    unsigned next = pt_wave() * 64u;
-    unsigned gend = next + 64u < nrays ? next + 64u : nrays;
-    bool alive = false;   // the lane holds a ray whose result is not stored yet
-    bool trav = false;    // ... and its search is in progress
-    unsigned ray = 0u;
-    PtQueryRay r = pt_query_idle();
-    PtBvhLane L;
-    L.tmax = 1e20f; L.hu = 0.0f; L.hv = 0.0f; L.hidx = -1;
-    L.gbase = L.gm = L.oct = 0u; L.sp = 0; L.ix = L.iy = L.iz = 0.0f; L.budget = 0u;
-    unsigned c_nodes = 0, c_leaves = 0, c_maxsp = 0;   // (pt_bvh_step's tallies: not kept)
-    unsigned long long c_steps = 0, c_tsteps = 0;
+    PtWorkCursor c = pt_cursor_init(W.n);
+    bool alive = false;   // the lane holds an item that is not finished
+    bool trav = false;    // ... and the search of its current ray is in progress
+    PtBvhLane L = pt_bvh_lane_idle(0.0f);
 
     for (;;) {
         if ((unsigned)__popcll(__ballot(trav)) <= (unsigned)PT_BVH_REFILL) {
-            // the pending pairs first: a lane with no nodes left has its closest hit only once its leaves are tested
-            if (tl.wr != tl.rd) pt_bvh_round<DET_BOUNDED>(P, L, tl, tl.wr - tl.rd, lane, r.o, r.d, n_recs);
-            if (alive && !trav) {
-                pt_query_store(Q, ray, r, L.tmax, L.hu, L.hv, L.hidx);
-                alive = false;
+            // the pending pairs first: a lane with no nodes left has its result only once its leaves are tested
+            if (tl.wr != tl.rd) pt_bvh_round<DET_BOUNDED, Work::ANY>(P, L, tl, tl.wr - tl.rd, lane, W.org(), W.dir(), n_recs, W.any());
+            bool fresh = false;   // the lane has a new ray
+            if (alive && !trav) alive = fresh = W.next_ray(L);
+            unsigned item = 0u;
+            if (pt_cursor_take(c, alive, item)) {
+                W.begin(item);
+                fresh = true;
             }
-            bool fresh = false;
-            for (unsigned long long need = __ballot(!alive); need != 0ull && next < nrays; need = __ballot(!alive)) {
-                const unsigned n_need = (unsigned)__popcll(need), avail = gend - next;
-                const unsigned take = n_need < avail ? n_need : avail;
-                const unsigned rank = pt_mbcnt(need);
-                if (!alive && rank < take) {
-                    ray = next + rank;
-                    r = pt_query_load(Q.rays, ray);
-                    alive = true;
-                    fresh = true;
-                }
-                next += take;
-                if (next == gend) {   // the wave's next group
-                    next = ((gend - 1u) & ~63u) + stride;
-                    next = next < nrays ? next : nrays;
-                    gend = next + 64u < nrays ? next + 64u : nrays;
-                }
-            }
-            // every fresh lane drops the previous ray's result (a fresh ray that searches nothing is stored as a miss at the next refill)
-            if (fresh) { L.tmax = r.tlim; L.hu = 0.0f; L.hv = 0.0f; L.hidx = -1; }
-            const bool start = fresh && r.live;
-            if (__ballot(start) != 0ull) {
-                if (P.nbig > 0) {
-                    // the triangles outside the hierarchy, by the two-pass search (its tail shares the key slots with pt_bvh_round and
-                    // expects them empty: the ring has just been flushed)
-                    int hp = -1;
-                    tl.keys[lane] = ~0ull;
-                    pt_intersect_two_pass<DET_BOUNDED, 1, (DET_BOUNDED ? BIGQ : 0)>(bigT, P.bigtab, P.nbig, r.o, r.d, start, L.tmax, L.hu, L.hv, hp,
-                                                                                      P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi,
-                                                                                      anchor, tl, lane);
-                    if (start && hp >= 0) L.hidx = P.bigidx[hp];
-                }
-                if (start) {
-                    pt_bvh_lane_start(L, r.d, ntri);
-                    trav = true;
-                }
-            }
+            // every fresh lane drops the previous ray's result (a fresh ray that searches nothing ends as a miss at the next refill)
+            if (fresh) pt_bvh_lane_clear(L, W.limit());
+            pt_bvh_search_start<DET_BOUNDED, BIGQ>(P, L, trav, fresh && W.live(), W.any(), W.org(), W.dir(), tl, lane);
             if (__ballot(alive) == 0ull) break;
         }
-        pt_bvh_step<DET_BOUNDED, false>(P, L, trav, r.o, r.d, stk, ovf, nxt, tl, lane, n_recs, c_nodes, c_leaves, c_steps, c_tsteps, c_maxsp);
+        pt_bvh_step<DET_BOUNDED, Work::ANY>(P, L, trav, W.org(), W.dir(), stk, ovf, nxt, tl, lane, n_recs, W.any());
     }
+}
+
+// pt_intersect_rays / pt_occluded_rays through the LBVH: one item = one ray.  ANYHIT: every search is an any-hit one
+// (pt_occluded_rays: the search stops at the first accepted triangle) and the result is PT_QUERY_OCCLUDED's 1 / 0.
+template <bool ANYHIT>
+struct PtQueryWork {
+    static constexpr bool ANY = ANYHIT;
+    const PtQueryParams& Q;
+    unsigned n, ray;
+    PtQueryRay r;
+    PTK_DEV void begin(unsigned item) { ray = item; r = pt_query_load(Q.rays, item); }
+    PTK_DEV bool next_ray(const PtBvhLane& L)
+    {
+        // Two rules, each where it belongs.  A closest search's ring lets a candidate exactly AT tmax beat the incumbent (tmax, no
+        // triangle), so its hit counts only at t < tlim as well: pt_query_store.  An any-hit lane's L.tmax never shrinks -- it
+        // stays at the ray's limit, where that comparison would turn every hit into a miss -- and pt_bvh_round has compared
+        // strictly already: its result is L.hidx >= 0 alone.
+        if (ANYHIT) reinterpret_cast<int32_t*>(Q.out)[ray] = L.hidx >= 0 ? 1 : 0;
+        else pt_query_store(Q, ray, r, L.tmax, L.hu, L.hv, L.hidx);
+        return false;
+    }
+    PTK_DEV const f3& org() const { return r.o; }
+    PTK_DEV const f3& dir() const { return r.d; }
+    PTK_DEV float limit() const { return r.tlim; }
+    PTK_DEV bool live() const { return r.live; }
+    PTK_DEV bool any() const { return ANYHIT; }
+};
+
+template <bool DET_BOUNDED, int BIGQ, bool ANYHIT>
+__global__ __launch_bounds__(PT_TRACE_THREADS) PT_BVH_WAVES_ATTR
+void pt_query_bvh_kernel(const PtQueryParams Q)
+{
+    PtQueryWork<ANYHIT> W = { Q, Q.nrays, 0u, pt_query_idle() };
+    pt_bvh_drive<DET_BOUNDED, BIGQ>(Q.t, W);
 }
 
 // ray gid of frame `frame` as the renderer traces it (seed :305-308, pixel jitter, the camera's expression), with the direction
@@ -2596,120 +2681,8 @@ __global__ __launch_bounds__(256) void pt_camera_rays_kernel(const PtCamera cam,
 }
 
 // ------------------------------------------------------------------------------------------
-// early-exit occlusion search (pt_occluded_rays) and ambient occlusion (pt_render_ao)
+// ambient occlusion (pt_render_ao)
 // ------------------------------------------------------------------------------------------
-// What an LBVH workgroup of the persistent query kernels holds in LDS before its loop: the table of the triangles outside the
-// hierarchy and the 2 KB child-order table (pt_query_bvh_kernel's preamble).  Returns the child-order table.
-PTK_DEV pt_lds_u8* pt_bvh_wg_setup(const PtTraceParams& P)
-{
-    const float* g = reinterpret_cast<const float*>(P.bigtab);
-    for (int k = (int)threadIdx.x; k < P.nbig * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
-        const int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
-        pt_lds_tab[k] = g[tri * 16 + w];
-    }
-    pt_lds_u8* nxt = (pt_lds_u8*)((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_nxt());
-    for (unsigned k = threadIdx.x; k < 2048u; k += PT_TRACE_THREADS) {
-        const unsigned o = k >> 8, h = k & 255u;
-        unsigned best = 0u, bp = 0u;
-        for (unsigned sl = 0; sl < 8u; ++sl)
-            if (((h >> sl) & 1u) && ((sl ^ o) >= bp)) { bp = sl ^ o; best = sl; }
-        nxt[k] = (unsigned char)best;
-    }
-    __syncthreads();
-    return nxt;
-}
-
-// a lane's search state at the start of a new ray: the limit, no hit
-PTK_DEV void pt_bvh_lane_clear(PtBvhLane& L, float tlim)
-{
-    L.tmax = tlim; L.hu = 0.0f; L.hv = 0.0f; L.hidx = -1;
-}
-
-// The start of a ray's LBVH search for the lanes in `start`: the triangles outside the hierarchy by the two-pass search (its
-// tail shares the key slots with pt_bvh_round and expects them empty: the ring has just been flushed), then the root.  An
-// any-hit ray (any) that hits one of them is done: it does not traverse.
-template <bool DET_BOUNDED, int BIGQ>
-PTK_DEV void pt_bvh_search_start(const PtTraceParams& P, PtBvhLane& L, bool& trav, bool start, bool any, const f3& o, const f3& d,
-                                 PtTail& tl, unsigned lane)
-{
-    if (__ballot(start) == 0ull) return;
-    if (P.nbig > 0) {
-        int hp = -1;
-        tl.keys[lane] = ~0ull;
-        pt_intersect_two_pass<DET_BOUNDED, 1, (DET_BOUNDED ? BIGQ : 0)>((pt_const_f32p)(const float*)P.bigtab, P.bigtab, P.nbig, o, d, start,
-                                                                          L.tmax, L.hu, L.hv, hp, P.quad_delta1, P.ray_radius,
-                                                                          (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi,
-                                                                          mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]), tl, lane);
-        if (start && hp >= 0) L.hidx = P.bigidx[hp];
-    }
-    if (start && !(any && L.hidx >= 0)) {
-        pt_bvh_lane_start(L, d, P.ntri);
-        trav = true;
-    }
-}
-
-// pt_occluded_rays through the LBVH: pt_query_bvh_kernel's persistent grid and lane refill, with every search an any-hit one.
-// The result is PT_QUERY_OCCLUDED's: some triangle passes the exact test at 0 < t < min(tmax, 1e20) (the two-pass search of the
-// big triangles and pt_bvh_round both compare strictly).
-template <bool DET_BOUNDED, int BIGQ>
-__global__ __launch_bounds__(PT_TRACE_THREADS) PT_BVH_WAVES_ATTR
-void pt_occluded_bvh_kernel(const PtQueryParams Q)
-{
-    const PtTraceParams& P = Q.t;
-    const unsigned lane = pt_lane_id();
-    const unsigned n_recs = (unsigned)P.bvh_records;
-    const pt_lds_u8* nxt = pt_bvh_wg_setup(P);
-    pt_lds_u32* stk = (pt_lds_u32*)pt_lds_tab + pt_bvh_lds_stacks() + threadIdx.x;
-    unsigned ovf[2 * (PT_BVH_STACK - PT_BVH_LDS_STACK)];
-    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_tails() + (threadIdx.x >> 6) * PT_BVH_TAIL_DW, 0u, lane);
-
-    const unsigned stride = gridDim.x * (PT_TRACE_THREADS / 64) * 64u;
-    const unsigned nrays = Q.nrays;
-    unsigned next = pt_wave() * 64u;
-    unsigned gend = next + 64u < nrays ? next + 64u : nrays;
-    bool alive = false, trav = false;
-    unsigned ray = 0u;
-    PtQueryRay r = pt_query_idle();
-    PtBvhLane L;
-    pt_bvh_lane_clear(L, 0.0f);
-    L.gbase = L.gm = L.oct = 0u; L.sp = 0; L.ix = L.iy = L.iz = 0.0f; L.budget = 0u;
-    unsigned c_nodes = 0, c_leaves = 0, c_maxsp = 0;
-    unsigned long long c_steps = 0, c_tsteps = 0;
-
-    for (;;) {
-        if ((unsigned)__popcll(__ballot(trav)) <= (unsigned)PT_BVH_REFILL) {
-            if (tl.wr != tl.rd) pt_bvh_round<DET_BOUNDED, true>(P, L, tl, tl.wr - tl.rd, lane, r.o, r.d, n_recs, true);
-            if (alive && !trav) {
-                reinterpret_cast<int32_t*>(Q.out)[ray] = L.hidx >= 0 ? 1 : 0;
-                alive = false;
-            }
-            bool fresh = false;
-            for (unsigned long long need = __ballot(!alive); need != 0ull && next < nrays; need = __ballot(!alive)) {
-                const unsigned n_need = (unsigned)__popcll(need), avail = gend - next;
-                const unsigned take = n_need < avail ? n_need : avail;
-                const unsigned rank = pt_mbcnt(need);
-                if (!alive && rank < take) {
-                    ray = next + rank;
-                    r = pt_query_load(Q.rays, ray);
-                    alive = true;
-                    fresh = true;
-                }
-                next += take;
-                if (next == gend) {
-                    next = ((gend - 1u) & ~63u) + stride;
-                    next = next < nrays ? next : nrays;
-                    gend = next + 64u < nrays ? next + 64u : nrays;
-                }
-            }
-            if (fresh) pt_bvh_lane_clear(L, r.tlim);   // (a ray that searches nothing is stored as a miss at the next refill)
-            pt_bvh_search_start<DET_BOUNDED, BIGQ>(P, L, trav, fresh && r.live, true, r.o, r.d, tl, lane);
-            if (__ballot(alive) == 0ull) break;
-        }
-        pt_bvh_step<DET_BOUNDED, false, true>(P, L, trav, r.o, r.d, stk, ovf, nxt, tl, lane, n_recs, c_nodes, c_leaves, c_steps, c_tsteps, c_maxsp, true);
-    }
-}
-
-// ---- ambient occlusion ---------------------------------------------------------------------------------------------------
 // One work item is one sample (local pixel lp, frame f0 + j / npix): the renderer's primary ray (seed :308, pt_generate_ray), its
 // closest hit from tmax 1e20 (:141); on a hit, K occlusion rays getRay(p + wi 0.01, wi) (:257) with wi = sampleHemisphereCosine
 // (n, &seed) (:161-172) about the HitRecord normal turned to face the ray (:243), each an any-hit search at 0 < t < min(radius, 1e20).
@@ -2721,26 +2694,17 @@ PTK_DEV void pt_ao_begin(const PtAoParams& A, unsigned item, unsigned& lp, uint3
     const PtTraceParams& P = A.t;
     const unsigned f = item / A.npix;
     lp = item - f * A.npix;
-    const unsigned W = (unsigned)P.width;
-    const unsigned lr = lp / W, x = lp - lr * W;
-    unsigned grow = lr;
-    if (P.n_ranks > 1) {
-        const unsigned sl = lr / (unsigned)P.stripe_rows;
-        grow = (sl * (unsigned)P.n_ranks + (unsigned)P.rank) * (unsigned)P.stripe_rows + (lr - sl * (unsigned)P.stripe_rows);   // pt_stripe_row
-    }
-    const unsigned gid = grow * W + x;
+    unsigned x, grow;
+    pt_pixel_xy<false>(P, nullptr, lp, x, grow);
+    const unsigned gid = grow * (unsigned)P.width + x;
     seed = gid + pt_hash_u32((uint32_t)(A.frame0 + (int)f));
     pt_generate_ray((int)x, (int)grow, P.inv_width, P.inv_height, P.aspect, PT_CAM_K(A.cam), seed, o, d);
 }
 
-// the primary hit's point and normal (pt_shade: the deferred HitRecord of :127-130, turned to face the ray as at :243)
+// the primary hit's point and normal: the HitRecord's, turned to face the ray as at :243
 PTK_DEV void pt_ao_surface(const PtTraceParams& P, const f3& o, const f3& d, float t, float hu, float hv, int hidx, f3& p, f3& n)
 {
-    const float4 nid = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(P.tris + hidx) + 12);
-    const f3 N = mk3(nid.x, nid.y, nid.z);
-    p = add3(o, scale3(d, t));
-    const float w = 1.0f - hu - hv;
-    n = normalize3(add3(add3(scale3(N, hu), scale3(N, hv)), scale3(N, w)));
+    pt_hit_record(P.tris, hidx, o, d, t, hu, hv, p, n);
     n = dot3(n, d) < 0.0f ? n : scale3(n, -1.0f);
 }
 
@@ -2779,17 +2743,7 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_ao_kernel(const PtAoParam
     const PtTraceParams& P = A.t;
     const unsigned lane = pt_lane_id();
     const int ntri = P.ntri;
-    if (LDS_TABLE == 1) {
-        const float* g = reinterpret_cast<const float*>(P.tris);
-        for (int k = (int)threadIdx.x; k < ntri * PT_LDS_TRI_STRIDE; k += PT_TRACE_THREADS) {
-            const int tri = k / PT_LDS_TRI_STRIDE, w = k - tri * PT_LDS_TRI_STRIDE;
-            pt_lds_tab[k] = g[tri * 16 + w];
-        }
-        __syncthreads();
-    }
-    const unsigned wave_in_wg = pt_wave_in_wg();
-    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_query_lds_tails<LDS_TABLE>(ntri) + wave_in_wg * pt_lds_tail_dw<LDS_TABLE>(),
-                             pt_query_lds_tiles<LDS_TABLE>(ntri) + wave_in_wg * PT_LDS_TILE_DW, lane);
+    PtTail tl = pt_table_wg_setup<LDS_TABLE>(P, lane);
     const f3 anchor = mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]);
     const unsigned item = pt_wave() * 64u + lane;
     const bool act = item < A.nitems;
@@ -2817,81 +2771,51 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_ao_kernel(const PtAoParam
     if (hit) pt_ao_count(A, lp, 1u, open);
 }
 
-// LBVH: pt_query_bvh_kernel's persistent grid.  A lane holds one sample and runs its searches one after the other -- the primary
-// ray's closest search, then its occlusion rays' any-hit searches; at every refill the lanes whose search has ended go on to
-// their sample's next ray, and the lanes whose sample is done take the wave's next samples.
+// LBVH (pt_bvh_drive): one item = one sample; the lane runs its searches one after the other -- the primary ray's closest search,
+// then its occlusion rays' any-hit searches -- and is free when the sample is counted
+struct PtAoWork {
+    static constexpr bool ANY = true;
+    const PtAoParams& A;
+    unsigned n;
+    int k;           // the current ray: -1 = the primary, 0 .. K-1 = occlusion ray k
+    unsigned lp, open;
+    uint32_t seed;
+    f3 o, d, p, nrm;
+    PTK_DEV void begin(unsigned item)
+    {
+        pt_ao_begin(A, item, lp, seed, o, d);
+        k = -1;
+        open = 0u;
+    }
+    PTK_DEV bool next_ray(const PtBvhLane& L)
+    {
+        if (k < 0) {
+            if (L.hidx < 0) return false;   // a primary miss adds nothing
+            pt_ao_surface(A.t, o, d, L.tmax, L.hu, L.hv, L.hidx, p, nrm);
+        } else {
+            open += L.hidx < 0 ? 1u : 0u;   // (an any-hit search: L.hidx >= 0 alone says occluded, PtQueryWork::next_ray)
+        }
+        if (++k < A.K) {
+            pt_ao_ray(p, nrm, seed, o, d);
+            return true;
+        }
+        pt_ao_count(A, lp, 1u, open);
+        return false;
+    }
+    PTK_DEV const f3& org() const { return o; }
+    PTK_DEV const f3& dir() const { return d; }
+    PTK_DEV float limit() const { return k < 0 ? 1e20f : A.tlim; }
+    PTK_DEV bool live() const { return true; }
+    PTK_DEV bool any() const { return k >= 0; }
+};
+
 template <bool DET_BOUNDED, int BIGQ>
 __global__ __launch_bounds__(PT_TRACE_THREADS) PT_BVH_WAVES_ATTR
 void pt_ao_bvh_kernel(const PtAoParams A)
 {
-    const PtTraceParams& P = A.t;
-    const unsigned lane = pt_lane_id();
-    const unsigned n_recs = (unsigned)P.bvh_records;
-    const pt_lds_u8* nxt = pt_bvh_wg_setup(P);
-    pt_lds_u32* stk = (pt_lds_u32*)pt_lds_tab + pt_bvh_lds_stacks() + threadIdx.x;
-    unsigned ovf[2 * (PT_BVH_STACK - PT_BVH_LDS_STACK)];
-    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_bvh_lds_tails() + (threadIdx.x >> 6) * PT_BVH_TAIL_DW, 0u, lane);
-
-    const unsigned stride = gridDim.x * (PT_TRACE_THREADS / 64) * 64u;
-    const unsigned nitems = A.nitems;
-    unsigned next = pt_wave() * 64u;
-    unsigned gend = next + 64u < nitems ? next + 64u : nitems;
-    bool alive = false;   // the lane holds a sample that is not counted yet
-    bool trav = false;    // ... and the search of its current ray is in progress
-    int k = -1;           // the current ray: -1 = the primary, 0 .. K-1 = occlusion ray k
-    unsigned lp = 0u, open = 0u;
-    uint32_t seed = 0u;
-    f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f), p = o, n = d;
-    PtBvhLane L;
-    pt_bvh_lane_clear(L, 0.0f);
-    L.gbase = L.gm = L.oct = 0u; L.sp = 0; L.ix = L.iy = L.iz = 0.0f; L.budget = 0u;
-    unsigned c_nodes = 0, c_leaves = 0, c_maxsp = 0;
-    unsigned long long c_steps = 0, c_tsteps = 0;
-
-    for (;;) {
-        if ((unsigned)__popcll(__ballot(trav)) <= (unsigned)PT_BVH_REFILL) {
-            if (tl.wr != tl.rd) pt_bvh_round<DET_BOUNDED, true>(P, L, tl, tl.wr - tl.rd, lane, o, d, n_recs, k >= 0);
-            bool fresh = false;
-            if (alive && !trav) {   // the search of the current ray has ended
-                bool done = false;
-                if (k < 0) {
-                    done = L.hidx < 0;   // a primary miss adds nothing
-                    if (!done) pt_ao_surface(P, o, d, L.tmax, L.hu, L.hv, L.hidx, p, n);
-                } else {
-                    open += L.hidx < 0 ? 1u : 0u;
-                }
-                if (!done && ++k < A.K) {
-                    pt_ao_ray(p, n, seed, o, d);
-                    fresh = true;
-                } else {
-                    if (!done) pt_ao_count(A, lp, 1u, open);
-                    alive = false;
-                }
-            }
-            for (unsigned long long need = __ballot(!alive); need != 0ull && next < nitems; need = __ballot(!alive)) {
-                const unsigned n_need = (unsigned)__popcll(need), avail = gend - next;
-                const unsigned take = n_need < avail ? n_need : avail;
-                const unsigned rank = pt_mbcnt(need);
-                if (!alive && rank < take) {
-                    pt_ao_begin(A, next + rank, lp, seed, o, d);
-                    k = -1;
-                    open = 0u;
-                    alive = true;
-                    fresh = true;
-                }
-                next += take;
-                if (next == gend) {
-                    next = ((gend - 1u) & ~63u) + stride;
-                    next = next < nitems ? next : nitems;
-                    gend = next + 64u < nitems ? next + 64u : nitems;
-                }
-            }
-            if (fresh) pt_bvh_lane_clear(L, k < 0 ? 1e20f : A.tlim);
-            pt_bvh_search_start<DET_BOUNDED, BIGQ>(P, L, trav, fresh, k >= 0, o, d, tl, lane);
-            if (__ballot(alive) == 0ull) break;
-        }
-        pt_bvh_step<DET_BOUNDED, false, true>(P, L, trav, o, d, stk, ovf, nxt, tl, lane, n_recs, c_nodes, c_leaves, c_steps, c_tsteps, c_maxsp, k >= 0);
-    }
+    const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
+    PtAoWork W = { A, A.nitems, -1, 0u, 0u, 0u, o0, d0, o0, d0 };
+    pt_bvh_drive<DET_BOUNDED, BIGQ>(A.t, W);
 }
 
 // image[i] = (a, a, a, 1), a = open / (K hits) (each converted to float, then one IEEE division), miss_value for a pixel never hit
@@ -3017,102 +2941,67 @@ size_t ptk_trace_bvh_lds_bytes(void)
     return (size_t)pt_bvh_lds_total() * sizeof(float);
 }
 
-int ptk_trace_bvh_blocks_per_cu(void)
+// resident workgroups per CU of a kernel of PT_TRACE_THREADS threads with `lds` bytes of dynamic LDS
+template <class Kernel> static int pt_blocks_per_cu(Kernel kernel, size_t lds)
 {
     int nb = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pt_trace_bvh_kernel<true, false, 3>, PT_TRACE_THREADS, ptk_trace_bvh_lds_bytes());
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, PT_TRACE_THREADS, lds);
     if (e != hipSuccess || nb < 1) nb = 2;
     return nb;
 }
 
+int ptk_trace_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_trace_bvh_kernel<true, false, 3>, ptk_trace_bvh_lds_bytes()); }
+int ptk_query_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_query_bvh_kernel<true, 3, false>, ptk_trace_bvh_lds_bytes()); }
 int ptk_trace_blocks_per_cu(int ntri)
 {
-    int nb = 0;
-    hipError_t e = ntri <= PT_LDS_TRI_MAX
-                       ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pt_trace_kernel<true, 1, 3>, PT_TRACE_THREADS, ptk_trace_lds_bytes(ntri))
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pt_trace_tiled_kernel<true>, PT_TRACE_THREADS, ptk_trace_lds_bytes(ntri));
-    if (e != hipSuccess || nb < 1) nb = 2;
-    return nb;
+    return ntri <= PT_LDS_TRI_MAX ? pt_blocks_per_cu(pt_trace_kernel<true, 1, 3>, ptk_trace_lds_bytes(ntri))
+                                  : pt_blocks_per_cu(pt_trace_tiled_kernel<true>, ptk_trace_lds_bytes(ntri));
 }
 
-// ---- batched ray queries --------------------------------------------------------------------------------------------------
-// (instantiated here, after every trace kernel: the existing kernels keep their place in the code object)
-hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s)
+// ---- batched ray queries and ambient occlusion ------------------------------------------------------------------------------
+// (instantiated here, after every trace kernel)
+// the instantiation of a kernel family for the scene: the packed filter (k3) needs the bounded reciprocal
+template <class Kernel> static Kernel pt_pick(bool det_bounded, bool q3, Kernel k3, Kernel k0, Kernel unbounded)
+{
+    return det_bounded ? (q3 ? k3 : k0) : unbounded;
+}
+
+// One launch of a kernel whose waves take 64 items each -- LBVH: a persistent grid of at most bvh_blocks workgroups (what the chip
+// holds) with the trace kernel's LDS; brute force: one wave per 64 items, the table kernels' LDS without the pools
+template <class Params>
+static hipError_t pt_launch_search(void (*kernel)(const Params), const Params& p, unsigned nitems, bool bvh, int bvh_blocks, hipStream_t s)
+{
+    const unsigned wg_waves = PT_TRACE_THREADS / 64;
+    unsigned blocks = ((nitems + 63u) / 64u + wg_waves - 1u) / wg_waves;
+    if (bvh && bvh_blocks > 0 && blocks > (unsigned)bvh_blocks) blocks = (unsigned)bvh_blocks;
+    const int ntri = p.t.ntri;
+    const size_t lds = bvh ? ptk_trace_bvh_lds_bytes()
+                           : (size_t)(ntri <= PT_LDS_TRI_MAX ? pt_lds_total<1, false>(ntri) : pt_lds_total<2, false>(ntri)) * sizeof(float);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(PT_TRACE_THREADS), lds, s, p);
+    return hipGetLastError();
+}
+
+hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, bool bvh, bool any, hipStream_t s)
 {
     if (q.nrays == 0) return hipSuccess;
     const bool q3 = quads == 3;
-    const unsigned groups = (q.nrays + 63u) / 64u;   // 64 rays per wave
-    const unsigned wg_waves = PT_TRACE_THREADS / 64;
     void (*kernel)(const PtQueryParams);
-    unsigned blocks = (groups + wg_waves - 1u) / wg_waves;
-    size_t lds;
-    if (bvh) {
-        kernel = det_bounded ? (q3 ? pt_query_bvh_kernel<true, 3> : pt_query_bvh_kernel<true, 0>) : pt_query_bvh_kernel<false, 0>;
-        if (bvh_blocks > 0 && blocks > (unsigned)bvh_blocks) blocks = (unsigned)bvh_blocks;   // persistent: what the chip holds
-        lds = ptk_trace_bvh_lds_bytes();
-    } else if (q.t.ntri <= PT_LDS_TRI_MAX) {
-        kernel = det_bounded ? (q3 ? pt_query_kernel<true, 1, 3> : pt_query_kernel<true, 1, 0>) : pt_query_kernel<false, 1, 0>;
-        lds = (size_t)pt_query_lds_total<1>(q.t.ntri) * sizeof(float);
-    } else {
-        kernel = det_bounded ? pt_query_kernel<true, 2, 0> : pt_query_kernel<false, 2, 0>;
-        lds = (size_t)pt_query_lds_total<2>(q.t.ntri) * sizeof(float);
-    }
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(PT_TRACE_THREADS), lds, s, q);
-    return hipGetLastError();
-}
-
-int ptk_query_bvh_blocks_per_cu(void)
-{
-    int nb = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pt_query_bvh_kernel<true, 3>, PT_TRACE_THREADS, ptk_trace_bvh_lds_bytes());
-    if (e != hipSuccess || nb < 1) nb = 2;
-    return nb;
-}
-
-hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s)
-{
-    const unsigned npix = (unsigned)width * (unsigned)height;
-    if (npix == 0) return hipSuccess;
-    // the renderer's per-image constants (pt_shim.hip: trace_params)
-    const float inv_w = 1.0f / (float)width, inv_h = 1.0f / (float)height, aspect = (float)width / (float)height;
-    hipLaunchKernelGGL(pt_camera_rays_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, s, cam, width, npix, inv_w, inv_h, aspect, frame, rays);
-    return hipGetLastError();
-}
-
-// ---- early-exit occlusion and ambient occlusion ---------------------------------------------------------------------------
-hipError_t ptk_occluded_bvh(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, hipStream_t s)
-{
-    if (q.nrays == 0) return hipSuccess;
-    const unsigned wg_waves = PT_TRACE_THREADS / 64;
-    unsigned blocks = ((q.nrays + 63u) / 64u + wg_waves - 1u) / wg_waves;
-    if (bvh_blocks > 0 && blocks > (unsigned)bvh_blocks) blocks = (unsigned)bvh_blocks;
-    void (*kernel)(const PtQueryParams) =
-        det_bounded ? (quads == 3 ? pt_occluded_bvh_kernel<true, 3> : pt_occluded_bvh_kernel<true, 0>) : pt_occluded_bvh_kernel<false, 0>;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(PT_TRACE_THREADS), ptk_trace_bvh_lds_bytes(), s, q);
-    return hipGetLastError();
+    if (bvh && any) kernel = pt_pick(det_bounded, q3, pt_query_bvh_kernel<true, 3, true>, pt_query_bvh_kernel<true, 0, true>, pt_query_bvh_kernel<false, 0, true>);
+    else if (bvh) kernel = pt_pick(det_bounded, q3, pt_query_bvh_kernel<true, 3, false>, pt_query_bvh_kernel<true, 0, false>, pt_query_bvh_kernel<false, 0, false>);
+    else if (q.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(det_bounded, q3, pt_query_kernel<true, 1, 3>, pt_query_kernel<true, 1, 0>, pt_query_kernel<false, 1, 0>);
+    else kernel = det_bounded ? pt_query_kernel<true, 2, 0> : pt_query_kernel<false, 2, 0>;
+    return pt_launch_search(kernel, q, q.nrays, bvh, bvh_blocks, s);
 }
 
 hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s)
 {
     if (a.nitems == 0) return hipSuccess;
     const bool q3 = quads == 3;
-    const unsigned wg_waves = PT_TRACE_THREADS / 64;
-    unsigned blocks = ((a.nitems + 63u) / 64u + wg_waves - 1u) / wg_waves;   // 64 samples per wave
     void (*kernel)(const PtAoParams);
-    size_t lds;
-    if (bvh) {
-        kernel = det_bounded ? (q3 ? pt_ao_bvh_kernel<true, 3> : pt_ao_bvh_kernel<true, 0>) : pt_ao_bvh_kernel<false, 0>;
-        if (bvh_blocks > 0 && blocks > (unsigned)bvh_blocks) blocks = (unsigned)bvh_blocks;
-        lds = ptk_trace_bvh_lds_bytes();
-    } else if (a.t.ntri <= PT_LDS_TRI_MAX) {
-        kernel = det_bounded ? (q3 ? pt_ao_kernel<true, 1, 3> : pt_ao_kernel<true, 1, 0>) : pt_ao_kernel<false, 1, 0>;
-        lds = (size_t)pt_query_lds_total<1>(a.t.ntri) * sizeof(float);
-    } else {
-        kernel = det_bounded ? pt_ao_kernel<true, 2, 0> : pt_ao_kernel<false, 2, 0>;
-        lds = (size_t)pt_query_lds_total<2>(a.t.ntri) * sizeof(float);
-    }
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(PT_TRACE_THREADS), lds, s, a);
-    return hipGetLastError();
+    if (bvh) kernel = pt_pick(det_bounded, q3, pt_ao_bvh_kernel<true, 3>, pt_ao_bvh_kernel<true, 0>, pt_ao_bvh_kernel<false, 0>);
+    else if (a.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(det_bounded, q3, pt_ao_kernel<true, 1, 3>, pt_ao_kernel<true, 1, 0>, pt_ao_kernel<false, 1, 0>);
+    else kernel = det_bounded ? pt_ao_kernel<true, 2, 0> : pt_ao_kernel<false, 2, 0>;
+    return pt_launch_search(kernel, a, a.nitems, bvh, bvh_blocks, s);
 }
 
 hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s)
@@ -3122,10 +3011,12 @@ hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uin
     return hipGetLastError();
 }
 
-int ptk_ao_bvh_blocks_per_cu(void)
+hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s)
 {
-    int nb = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pt_ao_bvh_kernel<true, 3>, PT_TRACE_THREADS, ptk_trace_bvh_lds_bytes());
-    if (e != hipSuccess || nb < 1) nb = 2;
-    return nb;
+    const unsigned npix = (unsigned)width * (unsigned)height;
+    if (npix == 0) return hipSuccess;
+    // the renderer's per-image constants (pt_shim.hip: image_geometry)
+    const float inv_w = 1.0f / (float)width, inv_h = 1.0f / (float)height, aspect = (float)width / (float)height;
+    hipLaunchKernelGGL(pt_camera_rays_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, s, cam, width, npix, inv_w, inv_h, aspect, frame, rays);
+    return hipGetLastError();
 }

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <utility>
@@ -122,8 +123,7 @@ struct pt_device_s {
     int* bigidx;
     int nbig;
     int bvh_blocks_per_cu;
-    int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query kernel (pt_intersect_rays)
-    int ao_bvh_blocks_per_cu;      // ... and of the LBVH ambient-occlusion kernel (pt_render_ao)
+    int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query and ambient-occlusion kernels (pt_bvh_drive)
     bool bvh_valid;
     unsigned int* det_bound_dev;  // PT_PREP_WORDS device words written by the prep kernel
     // fused-render workspace: the STREAMING renderer.  A render walks its frames in chunks of S frames (as many as a ring slot
@@ -360,7 +360,6 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->blocks_per_cu = ptk_trace_blocks_per_cu(36);
     d->bvh_blocks_per_cu = ptk_trace_bvh_blocks_per_cu();
     d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
-    d->ao_bvh_blocks_per_cu = ptk_ao_bvh_blocks_per_cu();
     *out = d;
     return PT_OK;
 }
@@ -706,6 +705,24 @@ static int check_range(const pt_buffer_s* b, size_t off, size_t bytes, const cha
     if (!b) return fail(PT_ERR_INVALID, "null buffer handle (%s)", what);
     if (off > b->bytes || bytes > b->bytes - off)
         return fail(PT_ERR_RANGE, "%s: range [%zu, +%zu) outside buffer of %zu bytes", what, off, bytes, b->bytes);
+    return PT_OK;
+}
+
+// the argument checks every entry point makes in the same words (null entries: optional buffers the caller left out)
+static int check_same_device(const pt_device_s* d, std::initializer_list<const pt_buffer_s*> bufs)
+{
+    for (const pt_buffer_s* b : bufs)
+        if (b && b->dev != d) return fail(PT_ERR_INVALID, "buffer belongs to another device");
+    return PT_OK;
+}
+static int check_event(const pt_device_s* d, const pt_event_s* ev)
+{
+    return ev && ev->dev != d ? fail(PT_ERR_INVALID, "event belongs to another device") : PT_OK;
+}
+static int check_triangles(const pt_buffer_s* tris, int n)
+{
+    if ((size_t)n * sizeof(PtRawTriangle) > tris->bytes)
+        return fail(PT_ERR_RANGE, "triangle buffer holds %zu bytes, %d triangles need %zu", tris->bytes, n, (size_t)n * sizeof(PtRawTriangle));
     return PT_OK;
 }
 
@@ -1268,6 +1285,17 @@ static int choose_batch(const pt_device_s* d, bool use_bvh, uint32_t npix, int c
     return PT_OK;
 }
 
+// the image-geometry fields of PtTraceParams: the per-image constants and this rank's stripes with their npix local pixels
+static void image_geometry(PtTraceParams& t, int width, int height, int stripe_rows, int n_ranks, int rank, uint32_t npix)
+{
+    t.width = width; t.height = height;
+    t.inv_width = 1.0f / (float)width;     // IEEE quotients: the translation unit is compiled without fast-math
+    t.inv_height = 1.0f / (float)height;
+    t.aspect = (float)width / (float)height;
+    t.stripe_rows = stripe_rows; t.n_ranks = n_ranks; t.rank = rank;
+    t.npix_local = npix;
+}
+
 // what every trace launch of the render is given; render_part's trace() sets the per-launch rest (queue, frames, checkpoints)
 static PtTraceParams trace_params(const pt_device_s* d, const pt_buffer_s* mats, const pt_buffer_s* stats, const pt_render_params& rp,
                                   const PtCamera& cam, uint32_t npix, const PtFilterTable& ft, bool use_bvh, bool use_pmask, int chunk,
@@ -1278,13 +1306,8 @@ static PtTraceParams trace_params(const pt_device_s* d, const pt_buffer_s* mats,
     tp.tris = d->prep;
     tp.mats = (const PtRawMaterial*)mats->dptr;
     tp.stats = stats ? (unsigned long long*)stats->dptr : nullptr;
-    tp.width = rp.width; tp.height = rp.height;
-    tp.inv_width = 1.0f / (float)rp.width;     // IEEE quotients: the translation unit is compiled without fast-math
-    tp.inv_height = 1.0f / (float)rp.height;
-    tp.aspect = (float)rp.width / (float)rp.height;
+    image_geometry(tp, rp.width, rp.height, rp.stripe_rows, rp.n_ranks, rp.rank, npix);
     tp.max_bounces = rp.max_bounces; tp.ntri = rp.num_triangles; tp.nmat = rp.num_materials;
-    tp.stripe_rows = rp.stripe_rows; tp.n_ranks = rp.n_ranks; tp.rank = rp.rank;
-    tp.npix_local = npix;
     tp.batches_per_frame = bpf; tp.batch = batch;
     tp.quad_delta1 = ft.delta1; tp.ray_radius = ft.ray_radius;
     tp.p1tab = ft.p1tab; tp.p1_lo = ft.p1_lo; tp.p1_hi = ft.p1_hi;
@@ -1459,8 +1482,8 @@ static int render_internal(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats,
                            const pt_render_params& rp, const PtCamera& cam, uint32_t pixel_count, pt_buffer_s* stats, pt_event_s* ev)
 {
     if (!tris || !mats || !fb) return fail(PT_ERR_INVALID, "null buffer handle");
-    if (tris->dev != d || mats->dev != d || fb->dev != d || (stats && stats->dev != d))
-        return fail(PT_ERR_INVALID, "buffer belongs to another device");
+    int rc = check_same_device(d, { tris, mats, fb, stats });
+    if (rc) return rc;
     if (rp.width < 1 || rp.height < 1 || rp.frame_begin < 0 || rp.frame_count < 0 || rp.max_bounces < 1 ||
         rp.num_triangles < 0 || rp.num_materials < 1 || rp.stripe_rows < 1 || rp.n_ranks < 1 || rp.rank < 0 ||
         rp.rank >= rp.n_ranks)
@@ -1477,9 +1500,7 @@ static int render_internal(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats,
         npix64 = std::min<uint64_t>(npix64, pixel_count);
     }
     uint32_t npix = (uint32_t)npix64;
-    if ((size_t)rp.num_triangles * sizeof(PtRawTriangle) > tris->bytes)
-        return fail(PT_ERR_RANGE, "triangle buffer holds %zu bytes, %d triangles need %zu", tris->bytes, rp.num_triangles,
-                    (size_t)rp.num_triangles * sizeof(PtRawTriangle));
+    if ((rc = check_triangles(tris, rp.num_triangles))) return rc;
     if ((size_t)rp.num_materials * sizeof(PtRawMaterial) > mats->bytes)
         return fail(PT_ERR_RANGE, "material buffer holds %zu bytes, %d materials need %zu", mats->bytes, rp.num_materials,
                     (size_t)rp.num_materials * sizeof(PtRawMaterial));
@@ -1488,9 +1509,7 @@ static int render_internal(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats,
     if (stats && stats->bytes < PT_STAT_WORDS * sizeof(uint64_t)) return fail(PT_ERR_RANGE, "stats buffer too small");
 
     // a search that was cut short in an earlier render is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
-    int rc = check_traversal(d);
-    if (rc) return rc;
-    if (ev && ev->dev != d) return fail(PT_ERR_INVALID, "event belongs to another device");
+    if ((rc = check_traversal(d)) || (rc = check_event(d, ev))) return rc;
     if (npix == 0 || rp.frame_count == 0) {
         if ((rc = lanes_join(d)) || (rc = event_begin(d, ev))) return rc;
         return event_end(d, ev);
@@ -1581,21 +1600,20 @@ static PtTraceParams search_params(const pt_device_s* d, int num_triangles, bool
     return t;
 }
 
-// pt_intersect_rays / pt_occluded_rays up to the launch: the argument checks, the deferred error, the stream, the scene and the
-// kernel parameters (out_record: bytes per result)
-static int query_begin(pt_device_s* d, pt_buffer_s* triangles, int num_triangles, pt_buffer_s* rays, pt_buffer_s* out, size_t num_rays,
-                       size_t out_record, bool occluded, pt_event_s* ev, PtQueryParams& q, bool& use_bvh, int& quads)
+// pt_intersect_rays and pt_occluded_rays: the argument checks, the deferred error, the stream, the scene, the launch.
+// occluded: 1 / 0 results (int32) instead of pt_hit records; early_exit: (occluded only) through the LBVH the search is the any-hit
+// one, which stops at the first accepted triangle -- brute force keeps the two-pass closest search (a few dozen triangles leave
+// little to stop early from)
+static int query_rays(pt_device_s* d, pt_buffer_s* triangles, int num_triangles, pt_buffer_s* rays, pt_buffer_s* out, size_t num_rays,
+                      bool occluded, bool early_exit, pt_event_s* ev)
 {
     int rc;
     if (!triangles || !rays || !out) return fail(PT_ERR_INVALID, "null buffer handle");
-    if (triangles->dev != d || rays->dev != d || out->dev != d) return fail(PT_ERR_INVALID, "buffer belongs to another device");
-    if (ev && ev->dev != d) return fail(PT_ERR_INVALID, "event belongs to another device");
+    if ((rc = check_same_device(d, { triangles, rays, out })) || (rc = check_event(d, ev))) return rc;
     if (num_triangles < 0) return fail(PT_ERR_INVALID, "num_triangles < 0");
-    if ((size_t)num_triangles * sizeof(PtRawTriangle) > triangles->bytes)
-        return fail(PT_ERR_RANGE, "triangle buffer holds %zu bytes, %d triangles need %zu", triangles->bytes, num_triangles,
-                    (size_t)num_triangles * sizeof(PtRawTriangle));
+    if ((rc = check_triangles(triangles, num_triangles))) return rc;
     if (num_rays > 0x7fffffffu) return fail(PT_ERR_RANGE, "%zu rays: at most 2^31 - 1 per call", num_rays);
-    const size_t ray_bytes = num_rays * sizeof(pt_ray), out_bytes = num_rays * out_record;
+    const size_t ray_bytes = num_rays * sizeof(pt_ray), out_bytes = num_rays * (occluded ? sizeof(int32_t) : sizeof(pt_hit));
     if (ray_bytes > rays->bytes) return fail(PT_ERR_RANGE, "ray buffer holds %zu bytes, %zu rays need %zu", rays->bytes, num_rays, ray_bytes);
     if (out_bytes > out->bytes) return fail(PT_ERR_RANGE, "result buffer holds %zu bytes, %zu results need %zu", out->bytes, num_rays, out_bytes);
     if (num_rays && (((uintptr_t)rays->dptr | (uintptr_t)out->dptr) & 15u)) return fail(PT_ERR_INVALID, "ray and result buffers must be 16-byte aligned");
@@ -1603,15 +1621,23 @@ static int query_begin(pt_device_s* d, pt_buffer_s* triangles, int num_triangles
     // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
     if ((rc = check_traversal(d))) return rc;
     if ((rc = enter_stream(d))) return rc;
-    use_bvh = false;
+    bool use_bvh = false;
     if (num_rays && num_triangles > 0 && (rc = prepare_search(d, triangles, num_triangles, nullptr, use_bvh))) return rc;
-    memset(&q, 0, sizeof q);
-    q.t = search_params(d, num_triangles, use_bvh, quads);
-    q.rays = (const float4*)rays->dptr;
-    q.out = out->dptr;
-    q.nrays = (uint32_t)num_rays;
-    q.occluded = occluded;
-    return PT_OK;
+    if ((rc = event_begin(d, ev))) return rc;
+    if (num_rays) {
+        int quads;
+        PtQueryParams q;
+        memset(&q, 0, sizeof q);
+        q.t = search_params(d, num_triangles, use_bvh, quads);
+        q.rays = (const float4*)rays->dptr;
+        q.out = out->dptr;
+        q.nrays = (uint32_t)num_rays;
+        q.occluded = occluded;
+        HIP_TRY(ptk_query(q, d->prop.multiProcessorCount * d->query_bvh_blocks_per_cu, num_triangles > 0 && d->prep_det_bounded, quads, use_bvh,
+                          early_exit && use_bvh, d->stream));
+    }
+    out->version++;
+    return event_end(d, ev);
 }
 
 extern "C" int pt_intersect_rays(pt_device_t d, pt_buffer_t triangles, int num_triangles, pt_buffer_t rays, pt_buffer_t out,
@@ -1620,39 +1646,15 @@ extern "C" int pt_intersect_rays(pt_device_t d, pt_buffer_t triangles, int num_t
     int rc = use_device(d);
     if (rc) return rc;
     if (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_OCCLUDED) return fail(PT_ERR_INVALID, "mode %d is neither PT_QUERY_CLOSEST nor PT_QUERY_OCCLUDED", mode);
-    PtQueryParams q;
-    bool use_bvh;
-    int quads;
-    if ((rc = query_begin(d, triangles, num_triangles, rays, out, num_rays, mode == PT_QUERY_CLOSEST ? sizeof(pt_hit) : sizeof(int32_t),
-                          mode == PT_QUERY_OCCLUDED, ev, q, use_bvh, quads)))
-        return rc;
-    if ((rc = event_begin(d, ev))) return rc;
-    if (num_rays)
-        HIP_TRY(ptk_query(q, d->prop.multiProcessorCount * d->query_bvh_blocks_per_cu, num_triangles > 0 && d->prep_det_bounded, quads, use_bvh,
-                          d->stream));
-    out->version++;
-    return event_end(d, ev);
+    return query_rays(d, triangles, num_triangles, rays, out, num_rays, mode == PT_QUERY_OCCLUDED, false, ev);
 }
 
-// PT_QUERY_OCCLUDED by a search that stops at the first accepted triangle: the any-hit LBVH kernel; brute force keeps the two-pass
-// closest search (a few dozen triangles leave little to stop early from)
 extern "C" int pt_occluded_rays(pt_device_t d, pt_buffer_t triangles, int num_triangles, pt_buffer_t rays, pt_buffer_t out,
                                 size_t num_rays, pt_event_t ev)
 {
     int rc = use_device(d);
     if (rc) return rc;
-    PtQueryParams q;
-    bool use_bvh;
-    int quads;
-    if ((rc = query_begin(d, triangles, num_triangles, rays, out, num_rays, sizeof(int32_t), true, ev, q, use_bvh, quads))) return rc;
-    if ((rc = event_begin(d, ev))) return rc;
-    if (num_rays) {
-        const bool det_bounded = num_triangles > 0 && d->prep_det_bounded;
-        if (use_bvh) HIP_TRY(ptk_occluded_bvh(q, d->prop.multiProcessorCount * d->query_bvh_blocks_per_cu, det_bounded, quads, d->stream));
-        else HIP_TRY(ptk_query(q, 0, det_bounded, quads, false, d->stream));
-    }
-    out->version++;
-    return event_end(d, ev);
+    return query_rays(d, triangles, num_triangles, rays, out, num_rays, true, true, ev);
 }
 
 // ---- ambient occlusion (include/pt_shim.h) -----------------------------------------------------------------------------------
@@ -1668,8 +1670,7 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
     PtCamera c = reference_camera();
     if (cam && (rc = camera_derive(cam, &c))) return rc;
     if (!triangles || !counts) return fail(PT_ERR_INVALID, "null buffer handle");
-    if (triangles->dev != d || counts->dev != d || (image && image->dev != d)) return fail(PT_ERR_INVALID, "buffer belongs to another device");
-    if (ev && ev->dev != d) return fail(PT_ERR_INVALID, "event belongs to another device");
+    if ((rc = check_same_device(d, { triangles, counts, image })) || (rc = check_event(d, ev))) return rc;
     if (a.width < 1 || a.height < 1 || a.frame_begin < 0 || a.frame_count < 0 || a.num_triangles < 0 || a.rays_per_sample < 1 ||
         a.rays_per_sample > 256 || !(std::isfinite(a.radius) && a.radius > 0.0f) || !std::isfinite(a.miss_value) || a.stripe_rows < 1 ||
         a.n_ranks < 1 || a.rank < 0 || a.rank >= a.n_ranks)
@@ -1683,9 +1684,7 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
         return fail(PT_ERR_RANGE, "(frame_begin + frame_count) x rays_per_sample exceeds 2^32 - 1: the counts could wrap");
     const uint32_t npix = (uint32_t)((uint64_t)pt_local_rows(a.height, a.stripe_rows, a.n_ranks, a.rank) * (uint64_t)a.width);
     const size_t count_bytes = (size_t)npix * 8, image_bytes = (size_t)npix * sizeof(float4);
-    if ((size_t)a.num_triangles * sizeof(PtRawTriangle) > triangles->bytes)
-        return fail(PT_ERR_RANGE, "triangle buffer holds %zu bytes, %d triangles need %zu", triangles->bytes, a.num_triangles,
-                    (size_t)a.num_triangles * sizeof(PtRawTriangle));
+    if ((rc = check_triangles(triangles, a.num_triangles))) return rc;
     if (count_bytes > counts->bytes) return fail(PT_ERR_RANGE, "count buffer holds %zu bytes, %u pixels need %zu", counts->bytes, npix, count_bytes);
     if (image && image_bytes > image->bytes) return fail(PT_ERR_RANGE, "image buffer holds %zu bytes, %u pixels need %zu", image->bytes, npix, image_bytes);
     if ((uintptr_t)counts->dptr & 7u) return fail(PT_ERR_INVALID, "the count buffer must be 8-byte aligned");
@@ -1707,12 +1706,7 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
         PtAoParams p;
         memset(&p, 0, sizeof p);
         p.t = search_params(d, a.num_triangles, use_bvh, quads);
-        p.t.width = a.width; p.t.height = a.height;
-        p.t.inv_width = 1.0f / (float)a.width;     // the renderer's per-image constants (trace_params)
-        p.t.inv_height = 1.0f / (float)a.height;
-        p.t.aspect = (float)a.width / (float)a.height;
-        p.t.stripe_rows = a.stripe_rows; p.t.n_ranks = a.n_ranks; p.t.rank = a.rank;
-        p.t.npix_local = npix;
+        image_geometry(p.t, a.width, a.height, a.stripe_rows, a.n_ranks, a.rank, npix);
         p.cam = c;
         p.counts = (unsigned long long*)counts->dptr;
         p.npix = npix;
@@ -1720,7 +1714,7 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
         p.tlim = a.radius < 1e20f ? a.radius : 1e20f;
         // frame-major samples, fewer than 2^31 per launch
         const int per_launch = (int)std::max<uint32_t>(1u, 0x7fffffffu / npix);
-        const int blocks = d->prop.multiProcessorCount * (use_bvh ? d->ao_bvh_blocks_per_cu : 0);
+        const int blocks = d->prop.multiProcessorCount * (use_bvh ? d->query_bvh_blocks_per_cu : 0);
         for (int64_t done = 0; done < a.frame_count; done += per_launch) {   // (64-bit: done + per_launch may pass 2^31 - 1)
             const int nf = (int)std::min<int64_t>(per_launch, a.frame_count - done);
             p.frame0 = a.frame_begin + (int)done;
@@ -1741,8 +1735,7 @@ extern "C" int pt_camera_rays(pt_device_t d, const pt_camera* cam, int width, in
     PtCamera c = reference_camera();
     if (cam && (rc = camera_derive(cam, &c))) return rc;
     if (!rays) return fail(PT_ERR_INVALID, "null buffer handle");
-    if (rays->dev != d) return fail(PT_ERR_INVALID, "buffer belongs to another device");
-    if (ev && ev->dev != d) return fail(PT_ERR_INVALID, "event belongs to another device");
+    if ((rc = check_same_device(d, { rays })) || (rc = check_event(d, ev))) return rc;
     if (width < 1 || height < 1 || frame < 0) return fail(PT_ERR_INVALID, "invalid image geometry or frame");
     if ((long long)width * height > 0x7fffffffLL) return fail(PT_ERR_INVALID, "image too large");
     const size_t bytes = (size_t)width * (size_t)height * sizeof(pt_ray);
