@@ -432,6 +432,26 @@ int pt_profile_query(pt_device_t dev, int kind, double* total_ms, uint64_t* laun
 int pt_profile_query_union(pt_device_t dev, int kind, double* union_ms);
 int pt_profile_reset(pt_device_t dev);
 
+/* Test hook: a read-only copy of the LBVH that stands for the scene this device prepared last (built by the first render, query or
+ * AO call that searched it through the hierarchy: PT_OPT_ACCEL), for a check of the hierarchy that is independent of the builder
+ * (tests/bvh_check.py).  Frames deferred by PT_OPT_BATCH_FRAMES are submitted first, as by every call that observes the device
+ * (that is the caller's own work: it may prepare a scene and build its hierarchy); then the call waits for the device and looks.
+ * The snapshot itself changes nothing: no preparation, no rebuild (PT_OPT_BVH_BUILD_COUNT stands), no filter anchor moves.  `info` receives the number of 64-byte records in use (eight-child nodes and one-triangle leaves of one
+ * array, record 0 the root: csrc/pt_kernels.h), the grid of the nodes' 16-bit origins, the number of triangles kept out of the
+ * hierarchy and the triangle count of the scene; `records` (may be NULL) receives the records -- record_capacity of them must
+ * fit -- and `big_indices` (may be NULL; room for PT_BVH_SNAPSHOT_BIG_MAX) the indices of the triangles kept out, ascending.
+ * PT_ERR_INVALID when no LBVH stands for the prepared scene, PT_ERR_RANGE when record_capacity is too small (info is still
+ * filled). */
+#define PT_BVH_SNAPSHOT_BIG_MAX 64
+typedef struct pt_bvh_info {
+    uint32_t records;            /* records in use */
+    int32_t num_big;             /* triangles kept out of the hierarchy, 0..PT_BVH_SNAPSHOT_BIG_MAX */
+    int32_t num_triangles;       /* triangles of the prepared scene */
+    float grid_min[3], grid_step[3];   /* a node's origin on axis a is fma(org[a], grid_step[a], grid_min[a]) */
+    int32_t reserved[7];
+} pt_bvh_info;                   /* 64 bytes */
+int pt_bvh_snapshot(pt_device_t dev, pt_bvh_info* info, void* records, size_t record_capacity, int32_t* big_indices);
+
 /* Scatter the gathered per-rank local framebuffers (n_ranks slabs of slab_rows x width
  * float4 each, slab k = rank k) into the full image (height x width float4). */
 int pt_assemble_stripes(pt_device_t dev, pt_buffer_t gathered, pt_buffer_t image, int width,

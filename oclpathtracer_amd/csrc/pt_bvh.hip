@@ -6,11 +6,40 @@
 // over the triangles whose exact test passes, so ANY traversal that applies the same exact test
 // (pt_tri_pass2's arithmetic) to a superset of those triangles and keeps the lexicographic minimum
 // returns the same (t, u, v, index) bit for bit.  The hierarchy only has to be conservative: a
-// node is skipped when the ray misses its box grown by PT_BVH_EPS x (largest |coordinate|).
-// (A binary32 Moeller-Trumbore test can accept a hit that lies outside the triangle by
-// ~1e-6 x distance / cos(incidence); for rays within ~0.05 degrees of a triangle's plane that
-// displacement is unbounded, so no finite box margin is PROVABLY conservative.  The margin covers
-// cos(incidence) >= 1e-2 with a factor 10 to spare; tests compare against brute force.)
+// node is skipped when the ray misses its box grown by the MARGIN
+//     PT_BVH_EPS x (largest |coordinate| of the scene)  +  PT_BVH_RAY_EPS x (largest |coordinate| of the ray's origin).
+// The first term is in the boxes (pt_bvh_refit_kernel), the second is applied per ray by the traversal (pt_bvh_step widens every
+// slab on both sides: a near and a far constant per axis, a few multiplies and FMAs per node visit, nothing per child).  Queries and
+// AO take rays from anywhere and always apply it.  The renderer's paths start at the eye and go on from points of the scene: when
+// the eye's largest |coordinate| is at most PT_BVH_NEAR_EYE = 4 x the scene's, its kernels leave the term out (pt_bvh_step<WIDE =
+// false>: the node step of before, instruction for instruction -- with the term the 10^6-triangle soup rendered 3.4 % slower,
+// profiles/lbvh_far/bench_ab.txt); from farther away they carry it.
+//
+// Why two terms.  A binary32 Moeller-Trumbore test accepts hits that lie outside the triangle; how far depends on the distance D
+// the ray has travelled, not on the scene.  Measured with the CPU oracle alone (tests/test_lbvh_margin_cpu.py: 400 000 rays per
+// row aimed at triangle edges at cos(incidence) 0.01 .. 1, every accepted triangle of every ray; the EXCESS is how far the
+// float64 crossing of the binary32 ray with the triangle's plane lies outside the triangle's box; m = the scene's largest
+// |coordinate|, eps = PT_BVH_EPS m):
+//     D / m     checkerboard in one plane: largest excess      2 000-triangle soup: largest excess (cos >= 0.01)
+//     1         0.0010 eps                                     0
+//     10        0.0052 eps                                     0
+//     100       0.10 eps                                       1.07 eps   (one hit of 372 805)
+//     1 000     0.66 eps                                       80 eps     (142 hits beyond eps)
+//     10 000    10.7 eps    (724 of 219 291 hits beyond eps)   296 eps    (3 295 of 344 490)
+//     100 000   129 eps     (11 575 of 219 047)                4 803 eps  (14 327 of 294 597)
+// On the axis-aligned checkerboard the excess is ~1.2e-7 D whatever the incidence: one to two ulp of the origin's coordinates.
+// On the soup it follows excess x cos / D <= 6e-7 (the ~1e-6 x distance / cos of the triangle test's (u, v)), i.e. up to 6e-5 D
+// at cos = 1e-2.  A margin sized by the scene alone therefore loses hits for origins far outside it -- on the device the
+// scene-only margin lost its first hits at D / m = 1 000 and 45 % of the axis-parallel hits on the checkerboard from 10 000 on
+// (tests/test_gpu_lbvh_far.py) -- and the ray term grows with the origin as the error does: the origin's largest |coordinate| is at
+// least D / sqrt(3) - m, so PT_BVH_RAY_EPS = 1.2e-4 gives at least 6.9e-5 D.  Against the margin with both terms the largest
+// measured excess is 0.0017 (checkerboard) and 0.12 (soup, D / m = 1 000) at cos >= 1e-2: a factor 8 to spare where measured, and
+// no factor to spare against the 6e-5 D envelope at cos = 1e-2 exactly.  The slab arithmetic's own rounding, a few ulp of
+// |origin| ~ 1e-7 |origin|, is a thousandth of the ray term.  For rays within ~0.05 degrees of a triangle's plane (cos < 1e-3)
+// the displacement is unbounded and no finite margin is PROVABLY conservative (the same measurement saw 1.4 x the margin once, at
+// cos 6.8e-4); tests compare against brute force.  A ray that starts inside the scene has a ray term of at most eps; an eye within
+// 4 m is less than 8 m away, inside the table's first two rows (0.0052 eps, 0), which is what the renderer's plain kernels rely on.  The price of
+// a far origin is speed, never a hit: at D / m = 10^4 the ray term is about the scene's size and the search enters most nodes.
 //
 // Build (Karras 2012): 30-bit Morton code of the box centre | triangle index -> 64-bit keys,
 // hipcub radix sort, one thread per internal node finds its range and split, bottom-up box refit

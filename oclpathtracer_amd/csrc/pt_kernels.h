@@ -199,7 +199,12 @@ hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s);
 // bvh: traverse p.bvh instead of the brute-force two-pass search; then `quads` is about the table of the big triangles kept out
 //      of the hierarchy (p.bigtab: 3 = made of quads, p.p1tab / p1_lo / p1_hi / quad_delta1 / ray_radius prepared for IT)
 // tally: (bvh only) the measurement variant that adds the search's work counters to p.stats[2..5]
-hipError_t ptk_trace(const PtTraceParams& p, int num_blocks, bool det_bounded, int quads, bool bvh, bool tally, hipStream_t s);
+// wide: (bvh only) the slabs carry the ray term of the margin, PT_BVH_RAY_EPS x the origin's largest |coordinate|.  Every path starts at
+//       the eye and goes on from points of the scene, so the host leaves the term out (the kernels of before, instruction for instruction)
+//       when the eye's largest |coordinate| is at most PT_BVH_NEAR_EYE x the scene's: there the term is below a third of eps and the
+//       measured excess below 0.01 eps (pt_bvh.hip's table, D / m <= 10).  Queries and AO take rays from anywhere and always carry it.
+hipError_t ptk_trace(const PtTraceParams& p, int num_blocks, bool det_bounded, int quads, bool bvh, bool tally, bool wide, hipStream_t s);
+#define PT_BVH_NEAR_EYE 4.0f
 // out[k] = raw[bigidx[k]], k < nbig <= PT_BVH_BIG_MAX
 hipError_t ptk_bvh_big_raw(const PtRawTriangle* raw, const int* bigidx, int nbig, PtRawTriangle* out, hipStream_t s);
 static inline size_t ptk_bvh_record_count(int ntri) { return 2 * (size_t)(ntri > 0 ? ntri : 0); }  // < ntri nodes + ntri leaves
@@ -207,6 +212,11 @@ size_t ptk_bvh_temp_bytes(int ntri);
 // prep: the prepared records of the same triangles.  bigtab[PT_BVH_BIG_MAX] / bigidx[PT_BVH_BIG_MAX] / *nbig_dev (device memory)
 // receive the triangles kept OUT of the hierarchy (pt_bvh.hip: PT_BVH_BIG_DIV): their prepared records and indices, ascending
 #define PT_BVH_BIG_MAX 64
+// The boxes' margin has a part that follows the RAY: a binary32 hit is displaced by an amount that grows with the distance the
+// ray has travelled, about one to two ulp of its origin's coordinates and more at grazing incidence, which the scene-sized margin
+// PT_BVH_EPS cannot cover for an origin far outside the scene.  The traversal widens every slab by PT_BVH_RAY_EPS x (the origin's
+// largest |coordinate|); the derivation and the measurements are in pt_bvh.hip's header.
+#define PT_BVH_RAY_EPS 1.2e-4f
 // recs[ptk_bvh_record_count(ntri)] (device memory) receives the hierarchy the trace kernel walks, *grid_dev its origin grid
 // *used_dev (device memory, may be null) receives the number of records in use
 hipError_t ptk_bvh_build(const PtRawTriangle* raw, const PtPrepTriangle* prep, int ntri, PtBvh8Node* recs,

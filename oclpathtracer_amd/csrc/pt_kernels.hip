@@ -1641,8 +1641,8 @@ struct PtBvhLane {
 // becomes STRICT: a box wholly beyond tmax has entry = exit = 1 after the clamp (one behind the origin 0 = 0) and must
 // fail; a box that holds a hit point of the ray is entered strictly before it is left (its faces lie PT_BVH_EPS x the scene
 // outside the triangle: pt_bvh.hip), so nothing a triangle needs is lost.  The scaled inverse direction is refreshed whenever
-// tmax shrinks (pt_bvh_round); rounding differences against the unscaled form are ~1e-7 relative, three orders of magnitude
-// inside the boxes' margin.
+// tmax shrinks (pt_bvh_round); rounding differences against the unscaled form are ~1e-7 of the largest coordinate involved --
+// the scene's or the ray origin's -- three orders of magnitude inside the margin's two terms (PT_BVH_EPS, PT_BVH_RAY_EPS).
 PTK_DEV void pt_bvh_scale(PtBvhLane& L, const f3& d)
 {
     // 1/dir for the slab tests only (conservative boxes: the error of v_rcp_f32 is far inside the boxes' margin), clamped
@@ -1789,7 +1789,7 @@ PTK_DEV void pt_bvh_round(const PtTraceParams& P, PtBvhLane& L, PtTail& tl, unsi
 // tested for it alone and change nothing)
 // c_*: the search's work counters, touched by the TALLY instantiations alone.  (Five scalars on purpose: bundled into a struct they move
 // the compiled code of the timed trace kernels, profiles/driver/disasm_comparison.txt.)  A caller that keeps none uses the form below.
-template <bool DET_BOUNDED, bool TALLY, bool ANY = false>
+template <bool DET_BOUNDED, bool TALLY, bool ANY = false, bool WIDE = true>
 PTK_DEV void pt_bvh_step(const PtTraceParams& P, PtBvhLane& L, bool& trav, const f3& o, const f3& d, pt_lds_u32* stk, unsigned* ovf,
                          const pt_lds_u8* nxt, PtTail& tl, unsigned lane, unsigned n_recs, unsigned& c_nodes, unsigned& c_leaves,
                          unsigned long long& c_steps, unsigned long long& c_tsteps, unsigned& c_maxsp, bool any = false)
@@ -1825,7 +1825,21 @@ PTK_DEV void pt_bvh_step(const PtTraceParams& P, PtBvhLane& L, bool& trav, const
             // t = fma(q, step / (d tmax), (origin - o) / (d tmax)); against decoding the box first this differs by a few
             // ulp of |coordinate| / |d|, orders of magnitude inside the boxes' PT_BVH_EPS margin
             const float kx = sx * L.ix, ky = sy * L.iy, kz = sz * L.iz;
-            const float cx = (ox - o.x) * L.ix, cy = (oy - o.y) * L.iy, cz = (oz - o.z) * L.iz;
+            // every slab is widened by w = PT_BVH_RAY_EPS x (the origin's largest |coordinate|) on both sides (pt_kernels.h): the
+            // near planes' constant lies w / |d| earlier, the far planes' w / |d| later.  (While kx, ky, kz are finite, an infinite
+            // w |i| -- an absurdly far origin -- makes the constants -Inf and +Inf, which clamp to 0 and 1: every box is entered.)
+            // WIDE = false: the renderer's kernels when every ray starts in or next to the scene (ptk_trace): w = 0, the plain form.
+            float cnx, cny, cnz, cfx, cfy, cfz;
+            if (WIDE) {
+                const float w = PT_BVH_RAY_EPS * __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(o.x), __builtin_fabsf(o.y)), __builtin_fabsf(o.z));
+                const float wx = w * __builtin_fabsf(L.ix), wy = w * __builtin_fabsf(L.iy), wz = w * __builtin_fabsf(L.iz);
+                const float dx = ox - o.x, dy = oy - o.y, dz = oz - o.z;
+                cnx = pt_fma(dx, L.ix, -wx); cny = pt_fma(dy, L.iy, -wy); cnz = pt_fma(dz, L.iz, -wz);
+                cfx = pt_fma(dx, L.ix, wx); cfy = pt_fma(dy, L.iy, wy); cfz = pt_fma(dz, L.iz, wz);
+            } else {
+                const float cx = (ox - o.x) * L.ix, cy = (oy - o.y) * L.iy, cz = (oz - o.z) * L.iz;
+                cnx = cfx = cx; cny = cfy = cy; cnz = cfz = cz;
+            }
             // near / far planes of all eight children by the direction's signs: qlo x y z = w2.xy w2.zw w3.xy,
             // qhi x y z = w3.zw w4.xy w4.zw (slots 0-3 in the first word, 4-7 in the second)
             const bool px = (L.oct & 1u) != 0u, py = (L.oct & 2u) != 0u, pz = (L.oct & 4u) != 0u;
@@ -1835,9 +1849,9 @@ PTK_DEV void pt_bvh_step(const PtTraceParams& P, PtBvhLane& L, bool& trav, const
 #define PT_B8(lo_, hi_, k) (float)((((k) < 4 ? (lo_) : (hi_)) >> (8 * ((k) & 3))) & 255u)
 #pragma unroll
             for (int k = 7; k >= 0; --k) {  // (MSB first: slot k ends up in bit k)
-                const float tnx = pt_fma_clamp(PT_B8(nx0, nx1, k), kx, cx), tfx = pt_fma_clamp(PT_B8(fx0, fx1, k), kx, cx);
-                const float tny = pt_fma_clamp(PT_B8(ny0, ny1, k), ky, cy), tfy = pt_fma_clamp(PT_B8(fy0, fy1, k), ky, cy);
-                const float tnz = pt_fma_clamp(PT_B8(nz0, nz1, k), kz, cz), tfz = pt_fma_clamp(PT_B8(fz0, fz1, k), kz, cz);
+                const float tnx = pt_fma_clamp(PT_B8(nx0, nx1, k), kx, cnx), tfx = pt_fma_clamp(PT_B8(fx0, fx1, k), kx, cfx);
+                const float tny = pt_fma_clamp(PT_B8(ny0, ny1, k), ky, cny), tfy = pt_fma_clamp(PT_B8(fy0, fy1, k), ky, cfy);
+                const float tnz = pt_fma_clamp(PT_B8(nz0, nz1, k), kz, cnz), tfz = pt_fma_clamp(PT_B8(fz0, fz1, k), kz, cfz);
                 const float tn = __builtin_fmaxf(__builtin_fmaxf(tnx, tny), tnz);  // already within [0, 1] = [0, tmax]
                 const float tf = __builtin_fminf(__builtin_fminf(tfx, tfy), tfz);
                 h = pt_push_flag(h, PT_LANES(tn < tf));
@@ -1952,7 +1966,7 @@ PTK_DEV void pt_bvh_search_start(const PtTraceParams& P, PtBvhLane& L, bool& tra
 
 // BIGQ: the filter of the brute-force search over the big triangles: 0 = independent triangles, 3 = the packed shared-u filter
 // (their table is made of quads -- the Cornell box's walls among a soup -- and the host prepared its pass-1 table)
-template <bool DET_BOUNDED, bool TALLY, int BIGQ>
+template <bool DET_BOUNDED, bool TALLY, int BIGQ, bool WIDE>
 PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
 {
     const unsigned lane = pt_lane_id();
@@ -2034,7 +2048,7 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
             if (stopping) {
                 parked = alive && !trav;
                 if (__ballot(trav) == 0ull) break;   // every lane holds a path between two searches (or none): the checkpoint
-                pt_bvh_step<DET_BOUNDED, TALLY>(P, L, trav, s.o, s.d, stk, ovf, nxt, tl, lane, n_recs, c_nodes, c_leaves, c_steps, c_tsteps, c_maxsp);
+                pt_bvh_step<DET_BOUNDED, TALLY, false, WIDE>(P, L, trav, s.o, s.d, stk, ovf, nxt, tl, lane, n_recs, c_nodes, c_leaves, c_steps, c_tsteps, c_maxsp);
                 continue;
             }
             pt_regenerate_lanes<false>(P, lane, q, s, alive);
@@ -2060,7 +2074,7 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
             }
             if (__ballot(alive) == 0ull) break;
         }
-        pt_bvh_step<DET_BOUNDED, TALLY>(P, L, trav, s.o, s.d, stk, ovf, nxt, tl, lane, n_recs, c_nodes, c_leaves, c_steps, c_tsteps, c_maxsp);
+        pt_bvh_step<DET_BOUNDED, TALLY, false, WIDE>(P, L, trav, s.o, s.d, stk, ovf, nxt, tl, lane, n_recs, c_nodes, c_leaves, c_steps, c_tsteps, c_maxsp);
     }
 
     if (TALLY && P.stats) {
@@ -2100,11 +2114,12 @@ PTK_DEV void pt_trace_bvh_body(const PtTraceParams& P)
 #define PT_BVH_WAVES 5
 #endif
 #define PT_BVH_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(PT_BVH_WAVES, PT_BVH_WAVES)))
-template <bool DET_BOUNDED, bool TALLY, int BIGQ>
+// WIDE: the slabs carry the ray term of the margin (pt_bvh_step); false when the host knows that every ray starts in or next to the scene
+template <bool DET_BOUNDED, bool TALLY, int BIGQ, bool WIDE = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS) PT_BVH_WAVES_ATTR
 void pt_trace_bvh_kernel(const PtTraceParams P)
 {
-    pt_trace_bvh_body<DET_BOUNDED, TALLY, BIGQ>(P);
+    pt_trace_bvh_body<DET_BOUNDED, TALLY, BIGQ, WIDE>(P);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2868,12 +2883,15 @@ hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t ptk_trace(const PtTraceParams& p, int num_blocks, bool det_bounded, int quads, bool bvh, bool tally, hipStream_t s)
+hipError_t ptk_trace(const PtTraceParams& p, int num_blocks, bool det_bounded, int quads, bool bvh, bool tally, bool wide, hipStream_t s)
 {
     // (the order the instantiations appear in is the order of the kernels in the code object)
     const bool q3 = quads == 3;
     void (*kernel)(const PtTraceParams);
-    if (bvh)
+    if (bvh && wide)
+        kernel = tally ? (det_bounded ? (q3 ? pt_trace_bvh_kernel<true, true, 3, true> : pt_trace_bvh_kernel<true, true, 0, true>) : pt_trace_bvh_kernel<false, true, 0, true>)
+                       : (det_bounded ? (q3 ? pt_trace_bvh_kernel<true, false, 3, true> : pt_trace_bvh_kernel<true, false, 0, true>) : pt_trace_bvh_kernel<false, false, 0, true>);
+    else if (bvh)
         kernel = tally ? (det_bounded ? (q3 ? pt_trace_bvh_kernel<true, true, 3> : pt_trace_bvh_kernel<true, true, 0>) : pt_trace_bvh_kernel<false, true, 0>)
                        : (det_bounded ? (q3 ? pt_trace_bvh_kernel<true, false, 3> : pt_trace_bvh_kernel<true, false, 0>) : pt_trace_bvh_kernel<false, false, 0>);
     else if (p.ntri <= PT_LDS_TRI_MAX)

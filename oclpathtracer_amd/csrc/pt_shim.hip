@@ -1147,6 +1147,19 @@ static int ensure_bvh(pt_device_s* d, const pt_buffer_s* tris, int ntri)
     return PT_OK;
 }
 
+// The LBVH trace kernels carry the ray term of the boxes' margin (ptk_trace: wide) unless the eye stands in or next to the scene:
+// its largest |coordinate| at most PT_BVH_NEAR_EYE x the scene's.  (A scene with a non-finite coordinate: always.)
+static bool eye_is_far(const pt_device_s* d, const float eye[3])
+{
+    if (!d->prep_finite) return true;
+    float m = 0.0f, e = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        m = std::max(m, std::max(fabsf(d->prep_lo[a]), fabsf(d->prep_hi[a])));
+        e = std::max(e, fabsf(eye[a]));
+    }
+    return !(e <= PT_BVH_NEAR_EYE * m);
+}
+
 // max |v - eye|_inf over the prepared scene's vertices, from its per-axis extremes: fl(v - e) is monotone in v, so the largest
 // |fl(v - e)| of an axis is reached at its smallest or its largest coordinate -- the same float as a reduction over every
 // vertex.  NaN when a coordinate is not finite.
@@ -1437,7 +1450,7 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
         tp.total_batches = (uint32_t)((uint64_t)bpf * (uint64_t)nf);
         int r = prof_begin(d, PT_PROF_TRACE, st, &pstop);
         if (r) return r;
-        HIP_TRY(ptk_trace(tp, blocks, d->prep_det_bounded, quads, use_bvh, d->opt_tally != 0 && stats != nullptr, st));
+        HIP_TRY(ptk_trace(tp, blocks, d->prep_det_bounded, quads, use_bvh, d->opt_tally != 0 && stats != nullptr, use_bvh && eye_is_far(d, tp.cam.eye), st));
         return prof_end(st, pstop);
     };
     for (int c = 0; c < nchunks; ++c) {
@@ -1835,6 +1848,33 @@ extern "C" int pt_profile_query(pt_device_t d, int kind, double* total_ms, uint6
     *total_ms = sum;
     *launches = d->prof_used[kind];
     return check_traversal(d);
+}
+
+// test hook (include/pt_shim.h): the hierarchy as the kernels read it, copied out; nothing of the device's state moves
+extern "C" int pt_bvh_snapshot(pt_device_t d, pt_bvh_info* info, void* records, size_t record_capacity, int32_t* big_indices)
+{
+    static_assert(sizeof(pt_bvh_info) == 64, "pt_bvh_info layout");
+    static_assert(PT_BVH_SNAPSHOT_BIG_MAX == PT_BVH_BIG_MAX, "the header's bound is the builder's");
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!info) return fail(PT_ERR_INVALID, "pt_bvh_snapshot: info is null");
+    // deferred frames are work the caller has already asked for: they are submitted first (they may prepare a scene and build its
+    // hierarchy), and only then is the state looked at -- the snapshot itself prepares and builds nothing
+    if ((rc = flush_pending(d))) return rc;
+    if ((rc = lanes_join(d))) return rc;
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    if (!d->bvh_valid || !d->bvh) return fail(PT_ERR_INVALID, "no LBVH stands for the prepared scene");
+    memset(info, 0, sizeof *info);
+    info->records = (uint32_t)d->bvh_records;
+    info->num_big = d->nbig;
+    info->num_triangles = d->prep_ntri;
+    for (int a = 0; a < 3; ++a) { info->grid_min[a] = d->bvh_grid.gmin[a]; info->grid_step[a] = d->bvh_grid.gstep[a]; }
+    if (records) {
+        if (record_capacity < d->bvh_records) return fail(PT_ERR_RANGE, "pt_bvh_snapshot: %zu records do not fit %zu", d->bvh_records, record_capacity);
+        if (d->bvh_records) HIP_TRY(hipMemcpy(records, d->bvh, d->bvh_records * sizeof(PtBvh8Node), hipMemcpyDeviceToHost));
+    }
+    if (big_indices && d->nbig > 0) HIP_TRY(hipMemcpy(big_indices, d->bigidx, (size_t)d->nbig * sizeof(int), hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 extern "C" int pt_profile_query_union(pt_device_t d, int kind, double* union_ms)

@@ -96,6 +96,18 @@ class AoParams(_c.Structure):
     ]
 
 
+class BvhInfo(_c.Structure):
+    """pt_bvh_info (64 bytes): what pt_bvh_snapshot says about the LBVH of the prepared scene."""
+
+    _fields_ = [
+        ("records", _c.c_uint32), ("num_big", _c.c_int32), ("num_triangles", _c.c_int32),
+        ("grid_min", _c.c_float * 3), ("grid_step", _c.c_float * 3),
+        ("reserved", _c.c_int32 * 7),
+    ]
+
+
+PT_BVH_SNAPSHOT_BIG_MAX = 64
+
 # every symbol include/pt_shim.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "pt_last_error": (_c.c_char_p, []),
@@ -154,6 +166,7 @@ SIGNATURES = {
     "pt_render_ao": (_c.c_int, [_H, _H, _H, _H, _c.POINTER(AoParams), _c.POINTER(Camera), _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
+    "pt_bvh_snapshot": (_c.c_int, [_H, _c.POINTER(BvhInfo), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "pt_profile_query_union": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double)]),
     "pt_profile_reset": (_c.c_int, [_H]),
     "pt_assemble_stripes": (_c.c_int, [_H, _H, _H, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _H]),

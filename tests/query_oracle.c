@@ -7,6 +7,9 @@
  *     ptor_intersect_world, GenerateColors.cl:137-154) with hitDistance starting at min(tmax, 1e20) instead of 1e20 -- a ray
  *     whose tmax is NaN or <= 0 tests nothing -- plus the winner's (u, v) and material, which ptor_hit does not keep: u and v
  *     restate :96-117 with the oracle's v3 functions;
+ *   - oq_all_hits: the same test over every triangle with hitDistance held at min(tmax, 1e20): every triangle the exact test accepts
+ *     for a ray, not only the closest (the measurement of the LBVH's margin, tests/test_lbvh_margin_cpu.py);
+ *   - oq_get_rays: the origin and the direction ptor_get_ray makes of a ray (the direction every test above really uses);
  *   - oq_camera_rays: ocam_generate_ray's expression up to the argument the reference passes to getRay at :287 (normalised once).
  * Compiled with oracle/Makefile's flags (tests/query_oracle.py).
  */
@@ -61,6 +64,42 @@ void oq_closest(const void* tris_, int ntri, const float* rays, int64_t n, float
         o[4] = rec.p.x; o[5] = rec.p.y; o[6] = rec.p.z;
         oi[7] = t->id;
         o[8] = rec.n.x; o[9] = rec.n.y; o[10] = rec.n.z;
+    }
+}
+
+/* Every (ray, triangle, t) the exact test accepts at 0 < t < min(tmax, 1e20), rays ascending and triangles ascending within a ray.
+ * At most `cap` records are written; the return value is how many there are (call again with more room if it exceeds cap). */
+PTOR_CLONES
+int64_t oq_all_hits(const void* tris_, int ntri, const float* rays, int64_t n, int64_t cap, int64_t* ray_out, int32_t* tri_out, float* t_out)
+{
+    const ptor_triangle* tris = (const ptor_triangle*)tris_;
+    ptor_stats st;
+    memset(&st, 0, sizeof st);
+    int64_t m = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const float* r8 = rays + 8 * k;
+        if (!(r8[3] > 0.0f)) continue;
+        const ptor_ray r = ptor_get_ray(v3_make(r8[0], r8[1], r8[2]), v3_make(r8[4], r8[5], r8[6]));
+        const float hitDistance = r8[3] < 1e20f ? r8[3] : 1e20f;
+        for (int i = 0; i < ntri; i++) {
+            ptor_hit rec;
+            if (!ptor_intersect_triangle(&r, &tris[i], i, &rec, hitDistance, &st)) continue;
+            if (m < cap) { ray_out[m] = k; tri_out[m] = i; t_out[m] = rec.t; }
+            ++m;
+        }
+    }
+    return m;
+}
+
+/* n rays of 8 floats -> n x 6 floats: origin, then the normalised direction of ptor_get_ray */
+void oq_get_rays(const float* rays, int64_t n, float* out)
+{
+    for (int64_t k = 0; k < n; ++k) {
+        const float* r8 = rays + 8 * k;
+        const ptor_ray r = ptor_get_ray(v3_make(r8[0], r8[1], r8[2]), v3_make(r8[4], r8[5], r8[6]));
+        float* o = out + 6 * k;
+        o[0] = r.origin.x; o[1] = r.origin.y; o[2] = r.origin.z;
+        o[3] = r.dir.x; o[4] = r.dir.y; o[5] = r.dir.z;
     }
 }
 

@@ -38,6 +38,10 @@ def lib():
         L.oq_closest.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
         L.oq_camera_rays.restype = ctypes.c_int
         L.oq_camera_rays.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        L.oq_all_hits.restype = ctypes.c_int64
+        L.oq_all_hits.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 3
+        L.oq_get_rays.restype = None
+        L.oq_get_rays.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -52,6 +56,58 @@ def closest(tris: np.ndarray, rays: np.ndarray) -> np.ndarray:
     rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
     out = np.zeros((len(rays), 12), np.float32)
     lib().oq_closest(_ptr(tris) if len(tris) else None, len(tris), _ptr(rays), len(rays), _ptr(out))
+    return out
+
+
+def _blocks(n: int, threads: int):
+    return [b for b in np.array_split(np.arange(n), max(1, min(threads, n // 4096 + 1))) if len(b)]
+
+
+def closest_threads(tris: np.ndarray, rays: np.ndarray, threads: int = 8) -> np.ndarray:
+    """closest() over blocks of rays on several host threads (the library call holds no Python lock): the same records."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    lib()
+    blocks = _blocks(len(rays), threads)
+    if not blocks:
+        return np.zeros((0, 12), np.float32)
+    with ThreadPoolExecutor(len(blocks)) as ex:
+        return np.concatenate(list(ex.map(lambda b: closest(tris, rays[b[0]: b[-1] + 1]), blocks)))
+
+
+def _all_hits_block(tris, rays):
+    cap = max(2 * len(rays), 1024)
+    while True:
+        ray, tri, t = np.zeros(cap, np.int64), np.zeros(cap, np.int32), np.zeros(cap, np.float32)
+        m = lib().oq_all_hits(_ptr(tris) if len(tris) else None, len(tris), _ptr(rays), len(rays), cap, _ptr(ray), _ptr(tri), _ptr(t))
+        if m <= cap:
+            return ray[:m], tri[:m], t[:m]
+        cap = int(m)
+
+
+def all_hits(tris: np.ndarray, rays: np.ndarray, threads: int = 8):
+    """Every (ray, triangle, t) the exact test accepts at 0 < t < min(tmax, 1e20): int64 [M], int32 [M], float32 [M], rays
+    ascending and triangles ascending within a ray."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    tris = np.ascontiguousarray(tris)
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    lib()
+    blocks = _blocks(len(rays), threads)
+    if not blocks:
+        return np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32)
+    with ThreadPoolExecutor(len(blocks)) as ex:
+        parts = list(ex.map(lambda b: _all_hits_block(tris, rays[b[0]: b[-1] + 1]), blocks))
+    return (np.concatenate([p[0] + b[0] for p, b in zip(parts, blocks)]), np.concatenate([p[1] for p in parts]),
+            np.concatenate([p[2] for p in parts]))
+
+
+def get_rays(rays: np.ndarray) -> np.ndarray:
+    """float32 [N, 6]: each ray's origin and the normalised direction the oracle's getRay makes of it."""
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    out = np.zeros((len(rays), 6), np.float32)
+    lib().oq_get_rays(_ptr(rays), len(rays), _ptr(out))
     return out
 
 
