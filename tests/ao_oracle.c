@@ -1,17 +1,15 @@
 /*
  * ao_oracle.c -- the CPU oracle's ambient occlusion in the layout of pt_render_ao.  TEST INFRASTRUCTURE.
  *
- * Includes tests/camera_oracle.c (and through it oracle/pt_oracle.c) whole and composes the estimator of pt_render_ao from the
- * oracle's own operations, in the order the renderer uses them:
+ * Follows tests/camera_oracle.c (and through it oracle/pt_oracle.c, whole) in tests/oracles.c and composes the estimator of
+ * pt_render_ao from the oracle's own operations, in the order the renderer uses them:
  *   - the sample of pixel gid in frame z: seed = gid + hash(z), ocam_generate_ray (GenerateColors.cl:263-288, :308);
  *   - its closest hit: ptor_intersect_triangle over the triangles in ascending order from hitDistance 1e20 (:137-154);
  *   - on a hit: hits += 1, p = rec.p, n = rec.n turned to face the ray (:243), then K times: wi =
  *     ptor_sample_hemisphere_cosine(n, &seed) (:161-172), the ray ptor_get_ray(p + wi 0.01, wi) (:257), and open += 1 unless some
  *     triangle passes ptor_intersect_triangle at 0 < t < min(radius, 1e20).
- * Compiled with oracle/Makefile's flags (tests/ao_oracle.py).
+ * Compiled with oracle/Makefile's flags (tests/oracles.py).
  */
-#include "camera_oracle.c"
-
 /* one sample; returns 1 when the primary ray hits (then *open = its open occlusion rays, and open_k[k] = 1 for each open one
  * when open_k is not NULL), else 0 */
 PTOR_INLINE int oao_sample(const ocam* cam, const ptor_triangle* tris, int ntri, int x, int grow, int W, int H, int frame, int K,

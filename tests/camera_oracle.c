@@ -7,7 +7,7 @@
  *     derived values follow include/pt_shim.h's contract (ocam_derive, the mirror of pt_camera_derive);
  *   - ocam_sample_pixel: ptor_sample_pixel (:490-513), the sample and the gamma fold, with that ray;
  *   - ocam_render: the threaded render over a gid range (ptor_render's driver).
- * Compiled with oracle/Makefile's flags (tests/camera_oracle.py): strict IEEE, no contraction.
+ * Compiled with oracle/Makefile's flags (tests/oracles.py): strict IEEE, no contraction.
  */
 #include "../oracle/pt_oracle.c"
 

@@ -1,5 +1,5 @@
-"""Scenes, ray families and the margin measurement of the far-origin LBVH tests (tests/test_lbvh_margin_cpu.py on the host,
-tests/test_gpu_lbvh_far.py on the device).  TEST INFRASTRUCTURE; everything is generated from fixed seeds.
+"""Ray families and the margin measurement of the far-origin LBVH tests (tests/test_lbvh_margin_cpu.py on the host,
+tests/test_gpu_lbvh_far.py on the device) over two scenes of tests/scenes.py.  TEST INFRASTRUCTURE; fixed seeds throughout.
 
 The LBVH keeps, for every triangle, its box grown by eps = BVH_EPS x (the scene's largest |coordinate|).  That part of the margin
 does not depend on the ray, while the displacement of a binary32 hit does: it grows with the distance the ray has travelled
@@ -10,6 +10,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from scenes import soup, tile_scene
+
 BVH_EPS = 1.2e-4                       # PT_BVH_EPS (csrc/pt_bvh.hip)
 DISTANCES = (1.0, 10.0, 100.0, 1e3, 1e4, 1e5)   # D / m
 FAMILY_RAYS = 100_000
@@ -17,35 +19,7 @@ AIM = 4e-6                             # a ray is aimed within AIM x D / cos of 
 TILE_CAP, SOUP_CAP = 0.125, 0.05       # ... but no farther than half a tile cell / a third of a soup triangle
 
 
-def _dtype():
-    from oclpathtracer_amd import scene
-
-    return scene.TRIANGLE_DTYPE
-
-
-def tile_scene() -> np.ndarray:
-    """A 24 x 24 checkerboard of axis-aligned quads (a,b,c),(c,d,a), cells of 0.25, in the plane y = 0.37 over [-3, 3]^2, every
-    other cell left out: 288 quads = 576 triangles (512 or more: PT_OPT_ACCEL = 0 takes the LBVH too), normals +y."""
-    y = np.float32(0.37)
-    cells = [(i, j) for i in range(24) for j in range(24) if (i + j) % 2 == 0]
-    t = np.zeros(2 * len(cells), _dtype())
-    for k, (i, j) in enumerate(cells):
-        x0, x1, z0, z1 = -3 + 0.25 * i, -3 + 0.25 * (i + 1), -3 + 0.25 * j, -3 + 0.25 * (j + 1)
-        a, b, c, d = (x0, y, z0), (x0, y, z1), (x1, y, z1), (x1, y, z0)
-        t["p1"][2 * k, :3], t["p2"][2 * k, :3], t["p3"][2 * k, :3] = a, b, c
-        t["p1"][2 * k + 1, :3], t["p2"][2 * k + 1, :3], t["p3"][2 * k + 1, :3] = c, d, a
-        t["id"][2 * k: 2 * k + 2] = k % 7
-    return t
-
-
-def soup_scene(n: int = 2000, seed: int = 5) -> np.ndarray:
-    """n triangles of size ~0.15 with centres uniform in [-3, 3]^3."""
-    from lbvh_scenes import soup
-
-    return soup(n, seed)
-
-
-SCENES = {"tile": (tile_scene, TILE_CAP), "soup": (soup_scene, SOUP_CAP)}
+SCENES = {"tile": (tile_scene, TILE_CAP), "soup": (lambda: soup(2000, 5), SOUP_CAP)}
 
 
 def verts(tris) -> np.ndarray:

@@ -1,0 +1,67 @@
+"""Builds and loads tests/libtest_oracles.so: the CPU oracle (oracle/pt_oracle.c) with its camera, query and ambient-occlusion
+restatements (tests/camera_oracle.c, query_oracle.c, ao_oracle.c) as one translation unit, tests/oracles.c.  TEST INFRASTRUCTURE.
+
+``__graft_entry__.build()`` builds it (``python -B tests/camera_oracle.py build``); ``lib()`` builds it again when it is missing
+or older than one of its sources, as ``ptoracle.lib()`` does.  The bindings are tests/camera_oracle.py, query_oracle.py, ao_oracle.py.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libtest_oracles.so")
+_SRCS = [os.path.join(_HERE, f) for f in ("oracles.c", "camera_oracle.c", "query_oracle.c", "ao_oracle.c")] + \
+        [os.path.join(os.path.dirname(_HERE), "oracle", f) for f in ("pt_oracle.c", "ptor_constants.h")]
+# a copy of oracle/Makefile's CFLAGS: strict IEEE, no contraction, no fast-math
+CFLAGS = ["-O2", "-fPIC", "-std=gnu11", "-Wall", "-Wextra", "-Wno-unused-function", "-ffp-contract=off", "-fno-fast-math",
+          "-fno-math-errno", "-pthread"]
+
+_V, _I, _I64, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+_SIGNATURES = {
+    "ocam_derive": (_I, [_V, _V]),
+    "ocam_render": (_I, [_V, _I, _V, _I, _V, _I, _I, _I, _I, _I, _I64, _I64, _I, _V, _V]),
+    "oq_closest": (None, [_V, _I, _V, _I64, _V]),
+    "oq_camera_rays": (_I, [_V, _I, _I, _I, _V]),
+    "oq_all_hits": (_I64, [_V, _I, _V, _I64, _I64, _V, _V, _V]),
+    "oq_get_rays": (None, [_V, _I64, _V]),
+    "oao_render": (_I, [_V, _I, _V] + [_I] * 8 + [_F, _V]),
+    "oao_decisions": (None, [_V, _I, _I, _I, _V, _V, _I64, _I, _F, _V, _V]),
+}
+
+
+def build() -> str:
+    cc = os.environ.get("CC", "gcc")
+    subprocess.check_call([cc] + CFLAGS + ["-shared", "-o", LIB_PATH, _SRCS[0], "-lm", "-lpthread"])
+    return LIB_PATH
+
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in _SRCS):
+            build()
+        L = ctypes.CDLL(LIB_PATH)
+        for name, (res, args) in _SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        _lib = L
+    return _lib
+
+
+def ptr(a):
+    """the data of an array as void*; None (no camera) stays NULL"""
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def cam10(cam):
+    """eye, center, up, fov_y_deg of a Camera (or of any object with those attributes) as float32[10]; None stays None."""
+    if cam is None:
+        return None
+    return np.array(list(cam.eye) + list(cam.center) + list(cam.up) + [cam.fov_y_deg], np.float32)

@@ -2,7 +2,7 @@
  * query_oracle.c -- the CPU oracle's closest hit and camera rays in the layouts of pt_intersect_rays / pt_camera_rays.
  * TEST INFRASTRUCTURE.
  *
- * Includes tests/camera_oracle.c (and through it oracle/pt_oracle.c) whole; the operations are the oracle's own:
+ * Follows tests/camera_oracle.c (and through it oracle/pt_oracle.c, whole) in tests/oracles.c; the operations are the oracle's:
  *   - oq_closest: ptor_get_ray, then ptor_intersect_triangle over the triangles in ascending order (the loop of
  *     ptor_intersect_world, GenerateColors.cl:137-154) with hitDistance starting at min(tmax, 1e20) instead of 1e20 -- a ray
  *     whose tmax is NaN or <= 0 tests nothing -- plus the winner's (u, v) and material, which ptor_hit does not keep: u and v
@@ -11,10 +11,8 @@
  *     for a ray, not only the closest (the measurement of the LBVH's margin, tests/test_lbvh_margin_cpu.py);
  *   - oq_get_rays: the origin and the direction ptor_get_ray makes of a ray (the direction every test above really uses);
  *   - oq_camera_rays: ocam_generate_ray's expression up to the argument the reference passes to getRay at :287 (normalised once).
- * Compiled with oracle/Makefile's flags (tests/query_oracle.py).
+ * Compiled with oracle/Makefile's flags (tests/oracles.py).
  */
-#include "camera_oracle.c"
-
 /* n rays of 8 floats (origin xyz, tmax, dir xyz, reserved) -> n records of 12 words in pt_hit's layout:
  * t, tri, u, v, p xyz, material, n xyz, 0; a miss is t = +inf, tri = -1, material = -1, everything else 0 */
 PTOR_CLONES

@@ -1,0 +1,333 @@
+"""Every generated scene of the test suite, with the rays that query the LBVH's edge cases.  TEST INFRASTRUCTURE; everything is
+generated from fixed seeds, and the order of the draws from a generator is part of each result.
+
+  * building blocks: small, soup, soup_with_duplicates, nested_boxes;
+  * scenes that steer the trace kernels and the LBVH builder: variant, bvh_edge, deep, horizon_tiles, random_quads;
+  * the far-origin scenes (tests/lbvh_far.py has their ray families): tile_scene, soup(2000, 5);
+  * scenes at the edges of what the LBVH takes -- scale, offset, shape, the builder's boundaries -- with rays to query them:
+    scene(name) for name in NAMES (tests/test_lbvh_scale_cpu.py: the oracle's scale identities; tests/test_gpu_lbvh_scenes.py)."""
+from __future__ import annotations
+
+import numpy as np
+
+from oclpathtracer_amd import scene as _scene
+
+SCALES = (-12, -11, -10, -9, 0, 20, 34, 40, 42, 43, 44, 45)   # 2^k; -9 .. 42: the oracle's hits are those of the unscaled scene
+IDENTITY = tuple(k for k in SCALES if -9 <= k <= 42)          # outside: the literal det threshold / overflow thin the hits out
+OFFSETS = (6, 10, 14)
+RAYS = 16384
+
+
+def small(rng, n, centres, size, nmat):
+    """n triangles with p1 at the centres and p2, p3 within `size` of them on every axis; draws p2's offsets, p3's, the ids"""
+    t = np.zeros(n, _scene.TRIANGLE_DTYPE)
+    c = np.asarray(centres, np.float32)
+    t["p1"][:, :3] = c
+    t["p2"][:, :3] = c + rng.uniform(-size, size, (n, 3)).astype(np.float32)
+    t["p3"][:, :3] = c + rng.uniform(-size, size, (n, 3)).astype(np.float32)
+    t["id"] = rng.integers(0, nmat, n)
+    return t
+
+
+def _small_anywhere(rng, n, size=0.05):
+    return small(rng, n, rng.uniform(-3, 3, (n, 3)), size, 7)
+
+
+def soup(n=2000, seed=21, size=0.15):
+    rng = np.random.default_rng(seed)
+    t = np.zeros(n, _scene.TRIANGLE_DTYPE)
+    c = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
+    for f in ("p1", "p2", "p3"):
+        t[f][:, :3] = c + rng.normal(0, size, (n, 3)).astype(np.float32)
+    t["id"] = rng.integers(0, 7, n)
+    return t
+
+
+def soup_with_duplicates(n, seed):
+    t = soup(n, seed)
+    t[n // 2: n // 2 + 40] = t[10:50]                        # duplicates: the lower index wins a tie
+    return t
+
+
+def nested_boxes(copies):
+    """Nested, shrunk copies of the Cornell box: 8 copies are 288 triangles, 13 are 468 (the tiled brute-force kernel's range)"""
+    tris, mats = _scene.load_model()
+    parts = []
+    for c in range(copies):
+        t = tris.copy()
+        k = np.float32(1.0 - 0.06 * c)
+        for f in ("p1", "p2", "p3"):
+            t[f][:, :3] = t[f][:, :3] * k + np.array([0.0, 2.7, -2.8], np.float32) * (np.float32(1.0) - k)
+        parts.append(t)
+    return np.concatenate(parts), mats
+
+
+def variant(kind):
+    """Scenes that steer the shim into each trace-kernel specialisation."""
+    tris, mats = _scene.load_model()
+    tris = tris.copy()
+    if kind == "quads_scaled":      # still (2k, 2k+1) quads, other numbers: quad filter
+        for f in ("p1", "p2", "p3"):
+            tris[f][:, :3] = tris[f][:, :3] * np.float32(0.73) + np.array([0.11, 0.4, -0.2], np.float32)
+    elif kind == "pairs_broken":    # same triangles, rotated by one: no pair is a quad: generic filter
+        tris = np.roll(tris, 1)
+    elif kind == "odd_count":       # 35 triangles
+        tris = tris[:35].copy()
+    elif kind == "huge_extent":     # |e1||e2| > 2e19: exact-division kernel (DET_BOUNDED = false)
+        for f in ("p1", "p2", "p3"):
+            tris[f][:, :3] = tris[f][:, :3] * np.float32(3.0e10)
+    elif kind == "one_triangle":
+        tris = tris[2:3].copy()
+    elif kind == "degenerate":      # zero-area and NaN triangles among the real ones
+        tris[4]["p2"] = tris[4]["p1"]
+        tris[7]["p3"][:3] = np.nan
+    elif kind == "quads_skewed":    # (a,b,c),(c,d,a) pairs far from parallelograms: shared-u filter, wide margins
+        rng = np.random.default_rng(7)
+        tris["p2"][1::2, :3] += rng.uniform(-0.4, 0.4, (len(tris) // 2, 3)).astype(np.float32)
+    elif kind == "quads_tiny":      # the box shrunk to 5 cm in front of the eye: shared-u margins at their floor
+        eye = np.array([0.0, 2.75, 4.0], np.float32)
+        for f in ("p1", "p2", "p3"):
+            tris[f][:, :3] = (tris[f][:, :3] - eye) * np.float32(0.01) + eye + np.array([0.0, 0.0, -0.05], np.float32)
+    elif kind == "quads_detached":  # second triangles translated: e2' == -e2 still, p1' != p3: pair filter only
+        for f in ("p1", "p2", "p3"):
+            tris[f][1::2, :3] += np.array([0.25, -0.125, 0.5], np.float32)
+    elif kind == "quads_nan_second":  # a NaN in the second triangle's e1 only: the pair structure survives
+        tris["p2"][9, 1] = np.nan
+    elif kind == "quads_17":        # an odd number of quads: the packed filter's last table entry is half padding
+        tris = tris[:34].copy()
+    elif kind == "quads_2":         # one pair of quads only
+        tris = tris[4:8].copy()
+    elif kind == "quads_72tri":     # three 32-triangle chunks: the box plus a shrunk copy of itself inside it
+        inner = tris.copy()
+        for f in ("p1", "p2", "p3"):
+            inner[f][:, :3] = inner[f][:, :3] * np.float32(0.4) + np.array([0.3, 1.2, -1.9], np.float32)
+        tris = np.concatenate([tris, inner])
+    elif kind == "quads_far":       # scene far from the eye relative to its size: large radius, small triangles
+        for f in ("p1", "p2", "p3"):
+            tris[f][:, :3] = tris[f][:, :3] * np.float32(4.0) + np.array([0.0, -8.25, -160.0], np.float32)
+    return tris, mats
+
+
+def bvh_edge(kind):
+    """Scenes that steer the LBVH builder into its corner cases (csrc/pt_bvh.hip: radix tree, eight-child collapse, big
+    triangles outside the tree).  One generator serves every draw of a kind."""
+    box, mats = _scene.load_model()
+    rng = np.random.default_rng(99)
+    some = lambda n, centres, size=0.05: small(rng, n, centres, size, len(mats))
+    lo, span = np.array([-2.5, 0.2, -5.2]), np.array([5.0, 5.0, 5.0])
+    if kind == "two":            # the smallest hierarchy: one node, two leaves
+        return box[20:22].copy(), mats
+    if kind == "three":
+        return box[20:23].copy(), mats
+    if kind == "nine":           # one more leaf than a node holds
+        return some(9, lo + span * rng.random((9, 3)), 0.8), mats
+    if kind == "duplicates":     # 300 copies of one triangle (equal Morton codes: the tree splits on the index bits) in the box
+        t = some(1, (lo + span * 0.5)[None, :], 0.6)
+        return np.concatenate([box, np.repeat(t, 300)]), mats
+    if kind == "clustered":      # centres at 1 - 2^-k along the diagonal: every radix split peels one leaf off, a deep chain
+        k = np.arange(1, 25)
+        c = lo[None, :] + span[None, :] * (1.0 - 2.0 ** -k)[:, None]
+        return np.concatenate([box, some(24, c, 0.02), some(400, lo + span * rng.random((400, 3)))]), mats
+    if kind == "many_big":       # more big triangles than the brute-force table holds (64): they all stay in the tree
+        return np.concatenate([box, some(90, lo + span * rng.random((90, 3)), 2.5), some(500, lo + span * rng.random((500, 3)))]), mats
+    if kind == "flat":           # every centre in one plane: one Morton axis carries no information
+        c = lo + span * rng.random((700, 3))
+        c[:, 1] = 2.0
+        return np.concatenate([box, some(700, c)]), mats
+    raise ValueError(kind)
+
+
+def deep():
+    """A radix tree as deep as 30-bit Morton codes allow, then deeper through the index bits: nested clusters at 2^-k of the
+    scene along the diagonal (k = 1 .. 10: every split peels one cluster off), each cluster a bundle of duplicates (equal
+    Morton codes: the tree goes on splitting on the triangle index), inside a random soup that gives every ray work."""
+    box, mats = _scene.load_model()
+    rng = np.random.default_rng(5)
+    lo, span = np.array([-2.5, 0.2, -5.2]), np.array([5.0, 5.0, 5.0])
+    parts = [box]
+    for k in range(1, 11):
+        c = lo + span * (1.0 - 2.0 ** -k)
+        one = small(rng, 1, c[None, :], 0.3 * 2.0 ** -k + 0.01, len(mats))
+        parts.append(np.repeat(one, 40))                    # 40 copies: six more levels on the index bits
+        parts.append(small(rng, 30, c[None, :] + rng.uniform(-1, 1, (30, 3)) * 2.0 ** -k, 0.02, len(mats)))
+    parts.append(small(rng, 1500, lo + span * rng.random((1500, 3)), 0.06, len(mats)))
+    return np.concatenate(parts), mats
+
+
+def horizon_tiles(delta, tile=0.3, glossy_every=3):
+    """Coplanar quads tiling the plane y = eye.y - delta, seen edge-on: the camera (GenerateColors.cl:265-276) looks along -z
+    from (0, 2.75, 4), so the pixel rows just below the image centre meet this plane at cos(incidence) ~ delta / distance,
+    from 1e-1 down to 1e-5 as delta shrinks, and every hit point lies next to the edges of several coplanar tiles -- where
+    binary32's (u, v) of a grazing ray are least certain.  Tiles are smaller than 1/16 of the scene, so they all go INTO the
+    hierarchy; neighbouring tiles have different materials (a wrong tile shows), every third one is glossy (its reflections
+    leave 0.01 above the plane, GenerateColors.cl:257, and graze the next tiles)."""
+    y = np.float32(2.75 - delta)
+    xs = np.arange(-3.0, 3.0, tile, dtype=np.float32)
+    zs = np.arange(-8.0, 3.95, tile, dtype=np.float32)
+    nq = len(xs) * len(zs)
+    tris = np.zeros(2 * nq, _scene.TRIANGLE_DTYPE)
+    mats = np.zeros(8, _scene.MATERIAL_DTYPE)
+    rng = np.random.default_rng(1)
+    for m in range(8):
+        mats[m]["albedo"] = tuple(rng.uniform(0.15, 0.95, 3)) + (1.0,)
+        mats[m]["emissive"] = (30.0, 30.0, 30.0, 1.0) if m == 7 else (0.0, 0.0, 0.0, 1.0)
+        mats[m]["type"] = _scene.SPECULAR if m % glossy_every == 0 else _scene.DIFFUSE
+        mats[m]["roughness"] = np.float32(0.05) if m % glossy_every == 0 else 0.0
+    q = 0
+    s = np.float32(tile)
+    for i, x in enumerate(xs):
+        for j, z in enumerate(zs):
+            a = np.array([x, y, z], np.float32)
+            b = np.array([x, y, z + s], np.float32)
+            c = np.array([x + s, y, z + s], np.float32)
+            d = np.array([x + s, y, z], np.float32)
+            # (a,b,c),(c,d,a) with cross(e2, e1) pointing DOWN: front-facing for rays that come from above (:100)
+            for k, (p1, p2, p3) in enumerate(((a, b, c), (c, d, a))):
+                t = tris[2 * q + k]
+                t["p1"][:3], t["p2"][:3], t["p3"][:3] = p1, p2, p3
+                t["id"] = (i * 5 + j * 3) % 8
+            q += 1
+    return tris, mats
+
+
+def random_quads(seed: int):
+    """Random (a,b,c),(c,d,a) quads around the view volume: parallelograms, perturbed parallelograms,
+    slivers, huge and tiny ones, some facing away; random diffuse / glossy / emissive materials."""
+    rng = np.random.default_rng(seed)
+    nq = int(rng.integers(1, 40))
+    tris = np.zeros(2 * nq, _scene.TRIANGLE_DTYPE)
+    mats = np.zeros(nq, _scene.MATERIAL_DTYPE)
+    scale = np.float32(10.0 ** rng.uniform(-1.5, 1.5))          # scene size: 0.03 ... 30
+    centre = np.array([0.0, 2.75, 4.0], np.float32) + np.array([0.0, 0.0, -1.0], np.float32) * scale * np.float32(1.5)
+    for q in range(nq):
+        a = centre + rng.uniform(-1, 1, 3).astype(np.float32) * scale
+        e1 = rng.uniform(-1, 1, 3).astype(np.float32) * scale * np.float32(10.0 ** rng.uniform(-1.5, 0.5))
+        e2 = rng.uniform(-1, 1, 3).astype(np.float32) * scale * np.float32(10.0 ** rng.uniform(-1.5, 0.5))
+        if rng.random() < 0.7 and np.dot(np.cross(e2, e1), a - np.array([0.0, 2.75, 4.0], np.float32)) < 0:
+            e1, e2 = e2, e1                                      # most quads face the eye (cull test :100)
+        b, c = a + e1, a + e1 + e2
+        d = a + e2
+        if rng.random() < 0.5:                                   # not a parallelogram
+            d = d + rng.uniform(-0.3, 0.3, 3).astype(np.float32) * np.float32(np.abs(e1).max())
+        for k, (p1, p2, p3) in enumerate(((a, b, c), (c, d, a))):
+            t = tris[2 * q + k]
+            t["p1"][:3], t["p2"][:3], t["p3"][:3] = p1, p2, p3
+            t["id"] = q
+        m = mats[q]
+        m["albedo"] = tuple(rng.uniform(0.05, 0.95, 3)) + (1.0,)
+        m["emissive"] = ((30.0, 30.0, 30.0, 1.0) if rng.random() < 0.15 else (0.0, 0.0, 0.0, 1.0))
+        m["type"] = _scene.SPECULAR if rng.random() < 0.3 else _scene.DIFFUSE
+        m["roughness"] = np.float32(10.0 ** rng.uniform(-2.5, -0.3)) if m["type"] == _scene.SPECULAR else 0.0
+    return tris, mats
+
+
+def tile_scene() -> np.ndarray:
+    """A 24 x 24 checkerboard of axis-aligned quads (a,b,c),(c,d,a), cells of 0.25, in the plane y = 0.37 over [-3, 3]^2, every
+    other cell left out: 288 quads = 576 triangles (512 or more: PT_OPT_ACCEL = 0 takes the LBVH too), normals +y."""
+    y = np.float32(0.37)
+    cells = [(i, j) for i in range(24) for j in range(24) if (i + j) % 2 == 0]
+    t = np.zeros(2 * len(cells), _scene.TRIANGLE_DTYPE)
+    for k, (i, j) in enumerate(cells):
+        x0, x1, z0, z1 = -3 + 0.25 * i, -3 + 0.25 * (i + 1), -3 + 0.25 * j, -3 + 0.25 * (j + 1)
+        a, b, c, d = (x0, y, z0), (x0, y, z1), (x1, y, z1), (x1, y, z0)
+        t["p1"][2 * k, :3], t["p2"][2 * k, :3], t["p3"][2 * k, :3] = a, b, c
+        t["p1"][2 * k + 1, :3], t["p2"][2 * k + 1, :3], t["p3"][2 * k + 1, :3] = c, d, a
+        t["id"][2 * k: 2 * k + 2] = k % 7
+    return t
+
+
+def soup_rays(tris, n=RAYS, seed=22):
+    """random rays through [-5, 5]^3, half of them aimed at triangle centroids"""
+    rng = np.random.default_rng(seed)
+    r = np.zeros((n, 8), np.float32)
+    r[:, :3] = rng.uniform(-5, 5, (n, 3))
+    r[:, 3] = 1e20
+    r[:, 4:7] = rng.normal(size=(n, 3))
+    k = rng.integers(0, len(tris), n // 2)
+    cen = (tris["p1"][k, :3].astype(np.float64) + tris["p2"][k, :3] + tris["p3"][k, :3]) / 3
+    r[: n // 2, 4:7] = cen - r[: n // 2, :3]
+    return r
+
+
+def transform(tris, rays, scale=(1.0, 1.0, 1.0), shift=0.0):
+    """vertices and ray origins x scale + shift, rounded to binary32; directions x scale"""
+    s = np.asarray(scale, np.float64)
+    t, r = tris.copy(), rays.copy()
+    for f in ("p1", "p2", "p3"):
+        t[f][:, :3] = (tris[f][:, :3].astype(np.float64) * s + shift).astype(np.float32)
+    r[:, :3] = (rays[:, :3].astype(np.float64) * s + shift).astype(np.float32)
+    r[:, 4:7] = (rays[:, 4:7].astype(np.float64) * s).astype(np.float32)
+    return t, r
+
+
+def scaled(k):
+    t = soup()
+    r = soup_rays(t)
+    s = 2.0 ** k
+    t2, r2 = transform(t, r, (s, s, s))
+    r2[:, 4:7] = r[:, 4:7]                      # (the directions stay: a uniform scale does not turn them)
+    return t2, r2
+
+
+def with_big(nbig, seed=31):
+    """1 000 small triangles and exactly nbig whose longest box side is above 1/16 of the scene's (PT_BVH_BIG_MAX is 64)"""
+    rng = np.random.default_rng(seed)
+    big = _small_anywhere(rng, nbig, 0.05)
+    big["p2"][:, 0] = big["p1"][:, 0] + np.float32(1.5)
+    t = np.concatenate([_small_anywhere(rng, 1000), big])
+    return t[rng.permutation(len(t))]
+
+
+def non_finite(n, seed=41):
+    rng = np.random.default_rng(seed)
+    t = _small_anywhere(rng, n)
+    bad = np.array([np.nan, np.inf, -np.inf], np.float32)
+    t["p1"][np.arange(n), rng.integers(0, 3, n)] = bad[rng.integers(0, 3, n)]
+    return t
+
+
+def shared_point(n=600):
+    """every vertex of every finite triangle is ONE point: the scene's extent is 0 on every axis; a few non-finite ones beside"""
+    t = np.zeros(n, _scene.TRIANGLE_DTYPE)
+    for f in ("p1", "p2", "p3"):
+        t[f][:, :3] = (1.0, 2.0, 3.0)
+    t["p2"][::50, 1] = np.nan
+    return t
+
+
+def scene(name):
+    """(triangles, rays) of a named case"""
+    if name.startswith("scale"):
+        return scaled(int(name[5:]))
+    base = soup()
+    rays = soup_rays(base)
+    if name.startswith("offset"):
+        return transform(base, rays, shift=2.0 ** int(name[6:]))
+    if name == "squeezed":
+        return transform(base, rays, (2.0 ** -20, 1.0, 1.0))
+    if name == "stretched":
+        return transform(base, rays, (1.0, 2.0 ** 20, 1.0))
+    if name == "shared_point":
+        r = rays.copy()
+        r[: RAYS // 2, 4:7] = np.array([1.0, 2.0, 3.0], np.float32) - r[: RAYS // 2, :3]
+        return shared_point(), r
+    if name in ("big64", "big65"):
+        t = with_big(int(name[3:]))
+        return t, soup_rays(t)
+    if name == "none_finite":
+        return non_finite(5), rays
+    if name == "one_finite":
+        t = non_finite(601)
+        t[300] = base[0]
+        r = rays.copy()
+        cen = (base["p1"][0, :3] + base["p2"][0, :3] + base["p3"][0, :3]) / np.float32(3)
+        r[:, 4:7] = cen + np.random.default_rng(5).normal(0, 0.02, (RAYS, 3)).astype(np.float32) - r[:, :3]   # (one side is culled)
+        return t, r
+    if name in ("n511", "n512"):
+        t = soup(int(name[1:]), 51, 0.3)
+        return t, soup_rays(t)
+    raise ValueError(name)
+
+
+NAMES = ["scale%d" % k for k in SCALES] + ["offset%d" % j for j in OFFSETS] + \
+        ["squeezed", "stretched", "shared_point", "big64", "big65", "none_finite", "one_finite", "n511", "n512"]

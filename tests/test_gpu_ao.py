@@ -9,18 +9,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import ao_oracle as ao
 from conftest import ROOT, assert_fb_equal
-from test_gpu_query import SEARCHES, _cornell_rays, _Options, _refill_rays, _soup
+from gpu_support import SEARCHES, cornell_rays, options, refill_rays
+from oclpathtracer_amd import shim
+from scenes import soup_with_duplicates
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ao():
-    import ao_oracle
-
-    ao_oracle.lib()
-    return ao_oracle
 
 
 def _render(device, tris, W, H, frames, K, radius, frame_begin=0, **kw):
@@ -43,20 +38,20 @@ def _check_image(img, counts, K, miss=1.0, what=""):
 
 
 @pytest.mark.parametrize("quad,accel", SEARCHES)
-def test_counts_bit_exact(device, cornell, ao, quad, accel):
+def test_counts_bit_exact(device, cornell, quad, accel):
     tris, _ = cornell
     for W, H in ((64, 64), (40, 24)):
         for radius in (0.5, 1e20):
             want = ao.counts(tris, W, H, 0, 4, 8, radius)
             assert want[..., 1].sum() > 0 and (want[..., 0] < 8 * want[..., 1]).any()
-            with _Options(device, QUAD_FILTER=quad, ACCEL=accel):
+            with options(device, QUAD_FILTER=quad, ACCEL=accel):
                 got, img = _render(device, tris, W, H, 4, 8, radius, stripe_rows=1)
             what = "%dx%d r%g q%d a%d" % (W, H, radius, quad, accel)
             assert np.array_equal(got, want), what + ": counts differ at %d pixels" % int((got != want).any(-1).sum())
             _check_image(img, got, 8, 1.0, what)
 
 
-def test_progressive_equals_one_call_and_frame_zero_overwrites(device, cornell, ao):
+def test_progressive_equals_one_call_and_frame_zero_overwrites(device, cornell):
     from oclpathtracer_amd.ao import AORenderer
 
     tris, _ = cornell
@@ -79,8 +74,8 @@ def test_progressive_equals_one_call_and_frame_zero_overwrites(device, cornell, 
     assert np.array_equal(one, got)
 
 
-def test_cameras_bit_exact_and_rejected_camera_enqueues_nothing(device, cornell, ao):
-    from oclpathtracer_amd import adl, scene, shim
+def test_cameras_bit_exact_and_rejected_camera_enqueues_nothing(device, cornell):
+    from oclpathtracer_amd import adl, scene
     from oclpathtracer_amd.camera import Camera
 
     tris, _ = cornell
@@ -114,7 +109,7 @@ def test_cameras_bit_exact_and_rejected_camera_enqueues_nothing(device, cornell,
 
 
 def test_stripes_equal_the_single_rank_rows(device, cornell):
-    from oclpathtracer_amd import adl, shim
+    from oclpathtracer_amd import adl
     from oclpathtracer_amd.ao import AORenderer
 
     tris, _ = cornell
@@ -158,7 +153,7 @@ def test_soup_lbvh_equals_brute_force(device):
     cam = Camera.fit(tris)
     res = {}
     for accel in (2, 1):
-        with _Options(device, ACCEL=accel):
+        with options(device, ACCEL=accel):
             res[accel], _ = _render(device, tris, 64, 64, 1, 4, 1.0, camera=cam, stripe_rows=1)
     assert res[2][..., 1].sum() > 1000 and (res[2][..., 0] < 4 * res[2][..., 1]).any()
     assert np.array_equal(res[2], res[1])
@@ -172,10 +167,8 @@ def _both(rc, rays):
 
 def _tmax_rays(tris):
     """A hit exactly at tmax, tmax above 1e20, NaN, 0, -0, negative; non-finite and degenerate directions."""
-    from oclpathtracer_amd.query import RayCaster, make_rays  # noqa: F401
-
     rng = np.random.default_rng(5)
-    r = _cornell_rays(rng, 2048, tris)
+    r = cornell_rays(rng, 2048, tris)
     r[0::7, 3] = np.float32(3e20)
     r[1::7, 3] = np.nan
     r[2::7, 3] = 0.0
@@ -195,8 +188,8 @@ def test_occluded_rays_equal_the_occluded_query(device, cornell, quad, accel):
     tris, _ = cornell
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, QUAD_FILTER=quad, ACCEL=accel):
-            rays = _cornell_rays(np.random.default_rng(300 + quad + 10 * accel), 20480, tris)
+        with options(device, QUAD_FILTER=quad, ACCEL=accel):
+            rays = cornell_rays(np.random.default_rng(300 + quad + 10 * accel), 20480, tris)
             want, got = _both(rc, rays)
             assert want.mean() > 0.3 and np.array_equal(got, want)
             # hits exactly at tmax: the closest hit of each ray, then tmax = its t (strict: occluded must be 0)
@@ -221,7 +214,7 @@ def test_occluded_rays_hit_exactly_at_tmax_through_the_hierarchy(device, quad, a
     tmax beat the incumbent."""
     from oclpathtracer_amd.query import RayCaster
 
-    tris = _soup(3000, 81)
+    tris = soup_with_duplicates(3000, 81)
     rng = np.random.default_rng(82)
     n = 1 << 16
     r = np.zeros((n, 8), np.float32)
@@ -230,7 +223,7 @@ def test_occluded_rays_hit_exactly_at_tmax_through_the_hierarchy(device, quad, a
     r[:, 4:7] = rng.normal(size=(n, 3))
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, QUAD_FILTER=quad, ACCEL=accel):
+        with options(device, QUAD_FILTER=quad, ACCEL=accel):
             hits = rc.closest(r)
             hit = hits["tri"] >= 0
             assert hit.sum() > 5000
@@ -253,7 +246,7 @@ def test_occluded_rays_empty_scene_and_edge_on_tiles(device, cornell):
     from oclpathtracer_amd.query import RayCaster
 
     tris, _ = cornell
-    rays = _cornell_rays(np.random.default_rng(8), 1024, tris)
+    rays = cornell_rays(np.random.default_rng(8), 1024, tris)
     rc = RayCaster(device, np.zeros(0, scene.TRIANGLE_DTYPE))
     try:
         assert np.all(rc.occluded(rays, early_exit=True) == 0)
@@ -283,7 +276,7 @@ def test_occluded_rays_empty_scene_and_edge_on_tiles(device, cornell):
     rc = RayCaster(device, g)
     try:
         for accel in (2, 1):
-            with _Options(device, ACCEL=accel):
+            with options(device, ACCEL=accel):
                 want, got = _both(rc, r)
                 assert np.array_equal(got, want), "tiles a%d" % accel
     finally:
@@ -304,13 +297,13 @@ def test_occluded_rays_on_the_soup(device):
     try:
         for tmax in (1.0, 1e20):
             r[:, 3] = tmax
-            with _Options(device, ACCEL=2):
+            with options(device, ACCEL=2):
                 want, got = _both(rc, r)
                 assert np.array_equal(got, want), "soup LBVH tmax %g" % tmax
                 assert 0.01 < want.mean() < 0.999
             small = r[: 1 << 14]
             for quad in (0, 1):
-                with _Options(device, ACCEL=1, QUAD_FILTER=quad):
+                with options(device, ACCEL=1, QUAD_FILTER=quad):
                     bw, bg = _both(rc, small)
                     assert np.array_equal(bg, bw) and np.array_equal(bg, want[: 1 << 14]), "soup brute q%d tmax %g" % (quad, tmax)
     finally:
@@ -320,11 +313,11 @@ def test_occluded_rays_on_the_soup(device):
 def test_occluded_rays_refill_over_more_rays_than_the_grid(device):
     from oclpathtracer_amd.query import RayCaster
 
-    tris = _soup(3000, 71)
-    r = _refill_rays(1 << 20, 73)
+    tris = soup_with_duplicates(3000, 71)
+    r = refill_rays(1 << 20, 73)
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=2):
+        with options(device, ACCEL=2):
             want, got = _both(rc, r)
         assert np.array_equal(got, want) and np.all(got[~(r[:, 3] > 0)] == 0) and got.mean() > 0.05
     finally:
@@ -336,7 +329,7 @@ def test_occluded_rays_through_torch_without_host_sync(device, cornell):
     from oclpathtracer_amd.query import RayCaster
 
     tris, _ = cornell
-    rays = _cornell_rays(np.random.default_rng(61), 8192, tris)
+    rays = cornell_rays(np.random.default_rng(61), 8192, tris)
     rc = RayCaster(device, tris)
     try:
         want = rc.occluded(rays)
@@ -355,15 +348,14 @@ def test_occluded_rays_through_torch_without_host_sync(device, cornell):
 
 
 # ---- with renders, errors, the harness -----------------------------------------------------------------------------------------
-def test_ao_interleaved_with_renders(device, cornell, oracle, ao):
-    from oclpathtracer_amd import shim
+def test_ao_interleaved_with_renders(device, cornell, oracle):
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = cornell
     W = H = 32
     lib = shim.load()
-    rays = _cornell_rays(np.random.default_rng(33), 4096, tris)
-    with _Options(device, ACCEL=2, CHUNK_FRAMES=3):
+    rays = cornell_rays(np.random.default_rng(33), 4096, tris)
+    with options(device, ACCEL=2, CHUNK_FRAMES=3):
         r = Renderer(device, tris, mats, W, H, want_stats=True, stripe_rows=1)
         rc = r.ray_caster()
         a = r.ao_renderer(rays_per_sample=4, radius=0.9)
@@ -389,12 +381,11 @@ def test_ao_interleaved_with_renders(device, cornell, oracle, ao):
 
 
 def test_cut_short_search_is_reported_and_recovers(device):
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.ao import AORenderer
     from oclpathtracer_amd.camera import Camera
     from oclpathtracer_amd.query import RayCaster
 
-    tris = _soup(3000, 41)
+    tris = soup_with_duplicates(3000, 41)
     rng = np.random.default_rng(43)
     n = 4096
     r = np.zeros((n, 8), np.float32)
@@ -402,7 +393,7 @@ def test_cut_short_search_is_reported_and_recovers(device):
     r[:, 3] = 1e20
     r[:, 4:7] = rng.normal(size=(n, 3))
     cam = Camera.fit(tris)
-    with _Options(device, ACCEL=2):
+    with options(device, ACCEL=2):
         rc = RayCaster(device, tris)
         a = AORenderer(device, rc.tbuf, 48, 48, rays_per_sample=4, radius=2.0, camera=cam, num_triangles=len(tris), stripe_rows=1)
         try:
@@ -410,13 +401,10 @@ def test_cut_short_search_is_reported_and_recovers(device):
             a.render(1)
             want_ao = a.read_counts()
             for call in (lambda: rc.occluded(r, early_exit=True), lambda: (a.render(1, 0), a.read_counts())):
-                device.setOption(shim.PT_OPT_BVH_STACK_LIMIT, 1)
-                try:
+                with options(device, BVH_STACK_LIMIT=1):
                     with pytest.raises(shim.ShimError) as e:   # the search is cut short; the observing call reports it
                         call()
                     assert e.value.code == shim.PT_ERR_TRAVERSAL
-                finally:
-                    device.setOption(shim.PT_OPT_BVH_STACK_LIMIT, 64)
                 device.waitForCompletion()                     # the word was cleared by the report
             assert np.array_equal(rc.occluded(r, early_exit=True), want)
             a.render(1, 0)
@@ -426,7 +414,7 @@ def test_cut_short_search_is_reported_and_recovers(device):
             rc.release()
 
 
-def test_cpp_harness_ambient_occlusion(tmp_path, cornell, ao):
+def test_cpp_harness_ambient_occlusion(tmp_path, cornell):
     from oclpathtracer_amd import scene
 
     tris, _ = cornell
@@ -446,8 +434,6 @@ def test_cpp_harness_ambient_occlusion(tmp_path, cornell, ao):
 
 
 def _params(W, H, ntri, **kw):
-    from oclpathtracer_amd import shim
-
     p = shim.AoParams()
     p.width, p.height, p.frame_begin, p.frame_count = W, H, 0, 1
     p.num_triangles, p.rays_per_sample, p.radius, p.miss_value = ntri, 4, 1.0, 1.0
@@ -461,7 +447,7 @@ def _params(W, H, ntri, **kw):
 
 
 def test_c_abi_argument_errors_leave_the_counts_untouched(device, cornell):
-    from oclpathtracer_amd import adl, scene, shim
+    from oclpathtracer_amd import adl, scene
 
     tris, _ = cornell
     lib = shim.load()

@@ -5,17 +5,20 @@ import ctypes
 import math
 import os
 import time
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
 import camera_oracle
 from conftest import GOLDEN, assert_fb_equal
+from gpu_support import options, render
+from oclpathtracer_amd import shim
+from scenes import nested_boxes
 
 pytestmark = pytest.mark.gpu
 
 W, H, FRAMES = 64, 48, 4
+CAMERAS = ["translated", "yawed30", "rolled", "fov20", "fov120", "inside_up", "far"]
 
 
 def _cams():
@@ -35,35 +38,6 @@ def _cams():
     }
 
 
-@contextmanager
-def _options(device, **opts):
-    from oclpathtracer_amd import shim
-
-    lib = shim.load()
-    ids = {k: getattr(shim, "PT_OPT_" + k) for k in opts}
-    old = {k: lib.pt_device_get_option(device._h, i) for k, i in ids.items()}
-    try:
-        for k, v in opts.items():
-            shim.check(lib.pt_device_set_option(device._h, ids[k], int(v)))
-        yield
-    finally:
-        for k, v in old.items():
-            lib.pt_device_set_option(device._h, ids[k], int(v))
-
-
-def _render(device, tris, mats, w, h, frames, cam, depth=16, want_stats=False, **kw):
-    from oclpathtracer_amd.render import Renderer
-
-    r = Renderer(device, tris, mats, w, h, camera=cam, want_stats=want_stats, **kw)
-    try:
-        r.render(frames, max_bounces=depth)
-        got = r.read()
-        st = r.read_stats_raw() if want_stats else None
-    finally:
-        r.release()
-    return got, st
-
-
 MODES = {"brute_masks": dict(ACCEL=1, PRIMARY_MASKS=1), "brute_nomasks": dict(ACCEL=1, PRIMARY_MASKS=0), "lbvh": dict(ACCEL=2)}
 
 
@@ -74,9 +48,9 @@ def test_explicit_reference_camera_is_the_default(device, cornell):
     tris, mats = cornell
     want = np.load(os.path.join(GOLDEN, "cornell_64x64_f8_d16.npy"))
     for name, opts in MODES.items():
-        with _options(device, **opts):
-            none, _ = _render(device, tris, mats, 64, 64, 8, None)
-            ref, _ = _render(device, tris, mats, 64, 64, 8, Camera.reference())
+        with options(device, **opts):
+            none = render(device, tris, mats, 64, 64, 8)
+            ref = render(device, tris, mats, 64, 64, 8, camera=Camera.reference())
         assert_fb_equal(none, want, "cam=NULL, %s" % name)
         assert_fb_equal(ref, want, "reference camera, %s" % name)
 
@@ -92,14 +66,15 @@ def _want(tris, mats, name, cam, depth, w=W, h=H, frames=FRAMES):
 
 
 @pytest.mark.parametrize("depth", [16, 2])
-@pytest.mark.parametrize("name", list(_cams()))
+@pytest.mark.parametrize("name", CAMERAS)
 def test_moved_cameras_match_the_camera_oracle(device, cornell, name, depth):
     tris, mats = cornell
+    assert list(_cams()) == CAMERAS, "CAMERAS must name every camera of _cams(), in its order"
     cam = _cams()[name]
     want, st = _want(tris, mats, name, cam, depth)
     for mode, opts in MODES.items():
-        with _options(device, **opts):
-            got, gst = _render(device, tris, mats, W, H, FRAMES, cam, depth=depth, want_stats=True)
+        with options(device, **opts):
+            got, gst = render(device, tris, mats, W, H, FRAMES, camera=cam, depth=depth, want_stats=True)
         assert_fb_equal(got, want, "%s, depth %d, %s" % (name, depth, mode))
         assert int(gst[0]) == W * H * FRAMES
         assert int(gst[1]) == st["rays"], (name, depth, mode)
@@ -107,20 +82,12 @@ def test_moved_cameras_match_the_camera_oracle(device, cornell, name, depth):
 
 def test_tiled_kernel_with_a_moved_camera(device, cornell):
     """257 ... 511 triangles: the brute-force search with LDS record tiles, seen from a moved camera."""
-    tris, mats = cornell
-    parts = []
-    for c in range(8):
-        t = tris.copy()
-        k = np.float32(1.0 - 0.06 * c)
-        for f in ("p1", "p2", "p3"):
-            t[f][:, :3] = t[f][:, :3] * k + np.array([0.0, 2.7, -2.8], np.float32) * (np.float32(1.0) - k)
-        parts.append(t)
-    big = np.concatenate(parts)
+    big, mats = nested_boxes(8)
     assert 256 < len(big) < 512
     cam = _cams()["yawed30"]
     want, st = camera_oracle.render(big, mats, W, H, 3, cam, want_stats=True)
-    with _options(device, ACCEL=1):
-        got, gst = _render(device, big, mats, W, H, 3, cam, want_stats=True)
+    with options(device, ACCEL=1):
+        got, gst = render(device, big, mats, W, H, 3, camera=cam, want_stats=True)
     assert_fb_equal(got, want, "tiled brute force, moved camera")
     assert int(gst[1]) == st["rays"]
 
@@ -129,7 +96,7 @@ def test_tiled_kernel_with_a_moved_camera(device, cornell):
 def test_checkpointed_chunks_under_a_moved_camera(device, cornell, kernel):
     """PT_OPT_CHUNK_FRAMES 3, 8 frames: three checkpointed launches and a draining one carry paths across launch boundaries
     under a moved camera -- the table kernel on the Cornell box, the LBVH kernel on a soup framed by Camera.fit."""
-    from oclpathtracer_amd import scene, shim
+    from oclpathtracer_amd import scene
     from oclpathtracer_amd.camera import Camera
 
     if kernel == "table":
@@ -139,8 +106,8 @@ def test_checkpointed_chunks_under_a_moved_camera(device, cornell, kernel):
         tris, mats = scene.make_soup(2000)
         cam, opts = Camera.fit(tris, view_dir=(0.4, -0.3, -1.0), aspect=W / H), dict(ACCEL=0)
     want, st = camera_oracle.render(tris, mats, W, H, 8, cam, want_stats=True)
-    with _options(device, CHUNK_FRAMES=3, **opts):
-        got, gst = _render(device, tris, mats, W, H, 8, cam, want_stats=True)
+    with options(device, CHUNK_FRAMES=3, **opts):
+        got, gst = render(device, tris, mats, W, H, 8, camera=cam, want_stats=True)
     assert_fb_equal(got, want, "checkpointed chunks, %s kernel, moved camera" % kernel)
     assert int(gst[shim.PT_STAT_RAYS]) == st["rays"]
     assert int(gst[shim.PT_STAT_CARRIED]) > 0
@@ -153,7 +120,7 @@ def test_stripes_reassemble_to_the_one_device_image(device, cornell, n_ranks):
     tris, mats = cornell
     cam = _cams()["rolled"]
     w, h, frames, stripe = 64, 50, 3, 4
-    one, _ = _render(device, tris, mats, w, h, frames, cam)
+    one = render(device, tris, mats, w, h, frames, camera=cam)
     want = camera_oracle.render(tris, mats, w, h, frames, cam)
     assert_fb_equal(one, want, "one device")
     img = np.full((h, w, 4), np.nan, np.float32)
@@ -173,7 +140,7 @@ def test_stripes_reassemble_to_the_one_device_image(device, cornell, n_ranks):
 def test_camera_changes_in_flight(device, cornell, accel):
     """A, B, A, B into four framebuffers with no wait in between, then A continues the first one's accumulation: every image
     is the oracle's, the LBVH is not rebuilt, the workspace does not grow, and the calls return long before the GPU is done."""
-    from oclpathtracer_amd import adl, shim
+    from oclpathtracer_amd import adl
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = cornell
@@ -184,7 +151,7 @@ def test_camera_changes_in_flight(device, cornell, accel):
     wantA = camera_oracle.render(tris, mats, w, h, F, A)
     wantB = camera_oracle.render(tris, mats, w, h, F, B)
     wantA2 = camera_oracle.render(tris, mats, w, h, F, A, frame_begin=F, fb=wantA.copy())
-    with _options(device, ACCEL=accel):
+    with options(device, ACCEL=accel):
         r = Renderer(device, tris, mats, w, h, camera=A)
         fbs = [r.fb] + [adl.Buffer(device, w * h, adl.float4) for _ in range(3)]
         try:
@@ -217,7 +184,6 @@ def test_camera_changes_in_flight(device, cornell, accel):
 
 
 def test_invalid_camera_is_refused_and_renders_nothing(device, cornell):
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = cornell

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, assert_fb_equal
+from gpu_support import render
 
 pytestmark = pytest.mark.gpu
 
@@ -36,15 +37,8 @@ def _free_port():
 
 
 def _single_gpu_image(device, cornell):
-    from oclpathtracer_amd.render import Renderer
-
     tris, mats = cornell
-    r = Renderer(device, tris, mats, W, H)
-    try:
-        r.render(FRAMES)
-        return r.read()
-    finally:
-        r.release()
+    return render(device, tris, mats, W, H, FRAMES)
 
 
 def test_stripe_image_is_ordered_against_torch_without_host_sync(device, cornell):
@@ -129,16 +123,10 @@ def test_world3_pipelined_with_a_ragged_last_period(device, cornell, tmp_path):
     rank 0 and 1 own one stripe more than rank 2, whose slab is zero-padded in the gather), the pipelined loop, the assembly
     on its own stream.  gloo through the host when fewer than three devices are visible."""
     from oclpathtracer_amd import shim
-    from oclpathtracer_amd.render import Renderer
 
     w, h, frames, stripe = 192, 200, 5, 4
     tris, mats = cornell
-    r = Renderer(device, tris, mats, w, h)
-    try:
-        r.render(frames)
-        want = r.read()
-    finally:
-        r.release()
+    want = render(device, tris, mats, w, h, frames)
     three = shim.load().pt_device_count() >= 3
     got = _run_world(3, "nccl" if three else "gloo", tmp_path, 3 if three else 1, extra=("pipelined",), geom=(w, h, frames, stripe))
     assert_fb_equal(got.reshape(-1, 4), want, "world-3 pipelined, ragged stripes vs one process")
@@ -169,16 +157,9 @@ def test_world4_pipelined_configs2_geometry(device, cornell, tmp_path):
     """Four rank processes on the one MI355X (the box admits six processes on its card; eight ranks are the driver's to start):
     BASELINE configs[2]'s image, bench.py's 4-row stripes, the pipelined loop -- every rank with its own device handle, staging
     ring and render lanes beside the others' -- against the one-process image."""
-    from oclpathtracer_amd.render import Renderer
-
     w, h, frames, stripe = 1024, 1024, 3, 4
     tris, mats = cornell
-    r = Renderer(device, tris, mats, w, h)
-    try:
-        r.render(frames)
-        want = r.read()
-    finally:
-        r.release()
+    want = render(device, tris, mats, w, h, frames)
     got = _run_world(4, "gloo", tmp_path, 1, extra=("pipelined",), geom=(w, h, frames, stripe))
     assert_fb_equal(got.reshape(-1, 4), want, "world-4 pipelined at 1024 x 1024 vs one process")
 

@@ -17,6 +17,9 @@ Each is compared here, ON THE GPU and over EVERY operand it can meet, with the l
 import numpy as np
 import pytest
 
+from conftest import assert_fb_equal
+from gpu_support import render
+
 pytestmark = pytest.mark.gpu
 
 
@@ -74,9 +77,6 @@ def test_fold_on_extreme_radiance_matches_the_oracle(device, oracle, cornell, ca
     """The same through the product path and against the CPU oracle: emitters whose radiance puts the running mean outside
     the range of the short forms (below 2^-80, above 2^80, negative sums clamped at :260, infinities and NaN), rendered
     from frame 0 and resumed from pixels holding arbitrary values."""
-    from conftest import assert_fb_equal
-    from test_gpu_parity import _render_gpu
-
     tris, mats = cornell
     mats = mats.copy()
     em = {"tiny": [3e-27, 1e-33, 2e-25, 0.0, 4e-38, 1e-30],
@@ -89,14 +89,14 @@ def test_fold_on_extreme_radiance_matches_the_oracle(device, oracle, cornell, ca
     W, H, frames = 48, 32, 6
     with np.errstate(all="ignore"):
         want = oracle.render(tris, mats, W, H, frames)
-        got = _render_gpu(device, tris, mats, W, H, frames)
+        got = render(device, tris, mats, W, H, frames)
         assert_fb_equal(got, want, "extreme radiance (%s), from frame 0" % case)
         rng = np.random.default_rng(3)
         junk = (2.0 ** rng.uniform(-140, 120, (W * H, 4))).astype(np.float32)
         junk[rng.random((W * H, 4)) < 0.1] = 0.0
         junk[7, 1], junk[9, 2], junk[11, 0], junk[13, 1] = np.inf, np.nan, -1.5, 1e-45
         want = oracle.render(tris, mats, W, H, 4, frame_begin=3, fb=junk.copy())
-        got = _render_gpu(device, tris, mats, W, H, 4, frame_begin=3, fb_init=junk)
+        got = render(device, tris, mats, W, H, 4, frame_begin=3, fb_init=junk)
         assert_fb_equal(got, want, "extreme radiance (%s), resumed at frame 3" % case)
     if case in ("tiny", "huge"):
         # the scene must really drive the mean out of the regular range
@@ -110,9 +110,7 @@ def test_throughput_quotients_outside_the_short_forms_range_match_the_oracle(dev
     """color * dot / pdf (:253-255) goes through one exact reciprocal and Markstein's correction while the three numerators
     and the pdf are in a guarded range (csrc/pt_device_math.h, pt_div3), through the generic division otherwise: materials
     whose albedo (numerators: tiny, huge, zero, negative, NaN) or roughness (pdf: 1e13 and beyond, 0/0) leave that range."""
-    from conftest import assert_fb_equal
     from oclpathtracer_amd import scene
-    from test_gpu_parity import _render_gpu
 
     tris, mats = cornell
     mats = mats.copy()
@@ -129,6 +127,6 @@ def test_throughput_quotients_outside_the_short_forms_range_match_the_oracle(dev
     W, H, frames = 64, 40, 4
     with np.errstate(all="ignore"):
         want, st = oracle.render(tris, mats, W, H, frames, want_stats=True)
-        got = _render_gpu(device, tris, mats, W, H, frames)
+        got = render(device, tris, mats, W, H, frames)
     assert_fb_equal(got, want, "quotients outside the guarded range (%s)" % case)
     assert st["rays"] > 2 * W * H * frames     # paths do continue past the first hit

@@ -14,9 +14,14 @@ zero 54-67 %, tmax 50 %; soup edge 53-68 %, axis 61-67 %, zero 61-69 %, tmax 50 
 import numpy as np
 import pytest
 
+import ao_oracle
+import camera_oracle
 import lbvh_far as F
+import query_oracle as qo
+import scenes
 from conftest import assert_fb_equal
-from test_gpu_query import _Options, assert_hits_equal
+from gpu_support import assert_hits_equal, options, render
+from oclpathtracer_amd import shim
 
 pytestmark = pytest.mark.gpu
 
@@ -25,8 +30,6 @@ _CASES = {}
 
 def _case(name, dm):
     """(triangles, {family: rays}, {family: oracle records}) of a scene at a distance; the oracle runs once per case."""
-    import query_oracle as qo
-
     if (name, dm) not in _CASES:
         tris, fam = F.families(name, dm, qo.closest_threads)
         _CASES[(name, dm)] = (tris, fam, {k: qo.closest_threads(tris, r) for k, r in fam.items()})
@@ -49,14 +52,13 @@ def _diagnose(rays, got_tri, want, dm, what, limit=6):
 @pytest.mark.parametrize("dm", F.DISTANCES)
 @pytest.mark.parametrize("name", sorted(F.SCENES))
 def test_far_families_bit_exact(device, name, dm, accel):
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.query import RayCaster
 
     tris, fam, wants = _case(name, dm)
     lib = shim.load()
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=accel):
+        with options(device, ACCEL=accel):
             builds = lib.pt_device_get_option(device._h, shim.PT_OPT_BVH_BUILD_COUNT)
             for k in sorted(fam):
                 rays, want = fam[k], wants[k]
@@ -85,7 +87,6 @@ def test_far_families_bit_exact(device, name, dm, accel):
 
 def test_accel_auto_takes_the_lbvh_for_the_tile_scene(device):
     """576 triangles: PT_OPT_ACCEL = 0 walks the hierarchy too, and the farthest family stays exact"""
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.query import RayCaster
 
     tris, fam, wants = _case("tile", 1e5)
@@ -93,7 +94,7 @@ def test_accel_auto_takes_the_lbvh_for_the_tile_scene(device):
     lib = shim.load()
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=0):
+        with options(device, ACCEL=0):
             builds = lib.pt_device_get_option(device._h, shim.PT_OPT_BVH_BUILD_COUNT)
             got = rc.closest(fam["edge"])
             assert lib.pt_device_get_option(device._h, shim.PT_OPT_BVH_BUILD_COUNT) == builds + 1
@@ -109,7 +110,7 @@ def _far_view():
     from oclpathtracer_amd import scene
     from oclpathtracer_amd.camera import Camera
 
-    tris = np.concatenate([F.tile_scene(), F.soup_scene()])
+    tris = np.concatenate([scenes.tile_scene(), scenes.soup(2000, 5)])
     mats = np.zeros(7, scene.MATERIAL_DTYPE)
     rng = np.random.default_rng(2)
     for m in range(7):
@@ -126,9 +127,6 @@ def _far_view():
 
 
 def test_render_from_a_far_camera(device):
-    import camera_oracle
-    from oclpathtracer_amd.render import Renderer
-
     tris, mats, cam = _far_view()
     W, H, frames = 96, 96, 3
     want, st = camera_oracle.render(tris, mats, W, H, frames, cam, want_stats=True)
@@ -136,27 +134,21 @@ def test_render_from_a_far_camera(device):
     assert st["accept"] > 0.2 * W * H * frames, "the camera must frame the scene"
     got = {}
     for accel in (1, 2):
-        with _Options(device, ACCEL=accel):
-            r = Renderer(device, tris, mats, W, H, camera=cam)
-            try:
-                r.render(frames)
-                got[accel] = r.read()
-            finally:
-                r.release()
+        with options(device, ACCEL=accel):
+            got[accel] = render(device, tris, mats, W, H, frames, camera=cam)
     assert_fb_equal(got[2], want, "far camera, LBVH against the oracle")
     assert_fb_equal(got[1], want, "far camera, brute force against the oracle")
     assert_fb_equal(got[2], got[1], "far camera, LBVH against brute force")
 
 
 def test_ambient_occlusion_from_a_far_camera(device):
-    import ao_oracle
     from oclpathtracer_amd.ao import AORenderer
 
     tris, _, cam = _far_view()
     W, H, frames, K, radius = 64, 64, 2, 8, 1.5
     want = ao_oracle.counts(tris, W, H, 0, frames, K, radius, cam=cam)
     assert want[..., 1].sum() > 0.2 * W * H * frames and (want[..., 0] < K * want[..., 1]).any(), "hits, and some of them occluded"
-    with _Options(device, ACCEL=2):
+    with options(device, ACCEL=2):
         r = AORenderer(device, tris, W, H, rays_per_sample=K, radius=radius, camera=cam, stripe_rows=1)
         try:
             r.render(frames, 0)

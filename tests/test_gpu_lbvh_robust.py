@@ -13,62 +13,20 @@ import numpy as np
 import pytest
 
 from conftest import assert_fb_equal, rms_diff
+from gpu_support import options, render
+from oclpathtracer_amd import shim
+from scenes import deep, horizon_tiles
 
 pytestmark = pytest.mark.gpu
 
 
-def _small(rng, n, centres, size, nmat):
-    from oclpathtracer_amd import scene
-
-    t = np.zeros(n, scene.TRIANGLE_DTYPE)
-    c = np.asarray(centres, np.float32)
-    t["p1"][:, :3] = c
-    t["p2"][:, :3] = c + rng.uniform(-size, size, (n, 3)).astype(np.float32)
-    t["p3"][:, :3] = c + rng.uniform(-size, size, (n, 3)).astype(np.float32)
-    t["id"] = rng.integers(0, nmat, n)
-    return t
-
-
 def _render(device, tris, mats, W, H, frames, accel, tally=False):
-    from oclpathtracer_amd import shim
-    from oclpathtracer_amd.render import Renderer
-
-    device.setOption(shim.PT_OPT_ACCEL, accel)
-    if tally:
-        device.setOption(shim.PT_OPT_BVH_TALLY, 1)
-    r = Renderer(device, tris, mats, W, H, want_stats=True)
-    try:
-        r.render(frames)
-        return r.read(), r.read_stats_raw()
-    finally:
-        r.release()
-        device.setOption(shim.PT_OPT_ACCEL, 0)
-        device.setOption(shim.PT_OPT_BVH_TALLY, 0)
-
-
-def _deep_scene():
-    """A radix tree as deep as 30-bit Morton codes allow, then deeper through the index bits: nested clusters at 2^-k of the
-    scene along the diagonal (k = 1 .. 10: every split peels one cluster off), each cluster a bundle of duplicates (equal
-    Morton codes: the tree goes on splitting on the triangle index), inside a random soup that gives every ray work."""
-    from oclpathtracer_amd import scene
-
-    box, mats = scene.load_model()
-    rng = np.random.default_rng(5)
-    lo, span = np.array([-2.5, 0.2, -5.2]), np.array([5.0, 5.0, 5.0])
-    parts = [box]
-    for k in range(1, 11):
-        c = lo + span * (1.0 - 2.0 ** -k)
-        one = _small(rng, 1, c[None, :], 0.3 * 2.0 ** -k + 0.01, len(mats))
-        parts.append(np.repeat(one, 40))                    # 40 copies: six more levels on the index bits
-        parts.append(_small(rng, 30, c[None, :] + rng.uniform(-1, 1, (30, 3)) * 2.0 ** -k, 0.02, len(mats)))
-    parts.append(_small(rng, 1500, lo + span * rng.random((1500, 3)), 0.06, len(mats)))
-    return np.concatenate(parts), mats
+    with options(device, ACCEL=accel, **({"BVH_TALLY": 1} if tally else {})):
+        return render(device, tris, mats, W, H, frames, want_stats=True)
 
 
 def test_deep_hierarchy_is_searched_exactly_and_the_stack_depth_is_reported(device, oracle):
-    from oclpathtracer_amd import shim
-
-    tris, mats = _deep_scene()
+    tris, mats = deep()
     W, H, frames = 48, 40, 3
     want, st = oracle.render(tris, mats, W, H, frames, want_stats=True)
     for accel in (1, 2):
@@ -86,59 +44,55 @@ def test_a_truncated_search_fails_the_render(device, oracle):
     failed with PT_ERR_TRAVERSAL (never return pixels of a search that lost a subtree), and succeed bit-exactly again at full
     capacity.  Renders are asynchronous and no render waits for the device to read the flag: the error is
     DEFERRED to the first call that observes the device -- pt_sync, an event wait, a blocking map, or the next render."""
-    from oclpathtracer_amd import adl, scene, shim
+    from oclpathtracer_amd import adl, scene
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = scene.make_soup(20_000)
     W, H, frames = 64, 32, 2
-    device.setOption(shim.PT_OPT_ACCEL, 2)
-    r = Renderer(device, tris, mats, W, H, want_stats=True)
-    ev = adl.SyncObject(device)
-    try:
-        device.setOption(shim.PT_OPT_BVH_STACK_LIMIT, 1)
-        # (1) pt_sync reports it; the render call itself only enqueues
-        r.render(frames, frame_begin=0)
-        with pytest.raises(shim.ShimError) as err:
-            device.waitForCompletion()
-        assert err.value.code == shim.PT_ERR_TRAVERSAL, err.value
-        assert "stack" in str(err.value)
-        device.waitForCompletion()          # reporting cleared the word: the handle is usable again
-        # (2) an event wait reports it
-        r.render(frames, frame_begin=0, sync=ev)
-        with pytest.raises(shim.ShimError) as err:
-            ev.waitForCompletion()
-        assert err.value.code == shim.PT_ERR_TRAVERSAL, err.value
-        # (3) the next render reports it (and renders nothing): the failed render has certainly finished once a
-        # host-side wait that does NOT check -- a plain stream query through an unrelated event -- has returned
-        r.render(frames, frame_begin=0)
-        fence = adl.SyncObject(device)
-        tmp = adl.Buffer(device, 4, np.int32)
-        tmp.write(np.zeros(4, np.int32), 4, syncObj=fence)   # enqueued behind the render on the handle's stream
-        while not fence.isComplete():
-            pass
-        device.setOption(shim.PT_OPT_BVH_STACK_LIMIT, 64)
-        with pytest.raises(shim.ShimError) as err:
-            r.render(frames, frame_begin=0)
-        assert err.value.code == shim.PT_ERR_TRAVERSAL, err.value
-        tmp.release()
-        fence.release()
-        # (4) a blocking map reports it
-        device.setOption(shim.PT_OPT_BVH_STACK_LIMIT, 1)
-        r.render(frames, frame_begin=0)
-        with pytest.raises(shim.ShimError):
-            r.fb.getHostPtr(blocking=True)
-        device.setOption(shim.PT_OPT_BVH_STACK_LIMIT, 64)
-        r.render(frames, frame_begin=0)
-        got = r.read()
-    finally:
-        device.setOption(shim.PT_OPT_BVH_STACK_LIMIT, 64)
-        device.setOption(shim.PT_OPT_ACCEL, 0)
+    with options(device, ACCEL=2):
+        r = Renderer(device, tris, mats, W, H, want_stats=True)
+        ev = adl.SyncObject(device)
         try:
-            device.waitForCompletion()
-        except shim.ShimError:
-            pass
-        ev.release()
-        r.release()
+            with options(device, BVH_STACK_LIMIT=1):
+                # (1) pt_sync reports it; the render call itself only enqueues
+                r.render(frames, frame_begin=0)
+                with pytest.raises(shim.ShimError) as err:
+                    device.waitForCompletion()
+                assert err.value.code == shim.PT_ERR_TRAVERSAL, err.value
+                assert "stack" in str(err.value)
+                device.waitForCompletion()          # reporting cleared the word: the handle is usable again
+                # (2) an event wait reports it
+                r.render(frames, frame_begin=0, sync=ev)
+                with pytest.raises(shim.ShimError) as err:
+                    ev.waitForCompletion()
+                assert err.value.code == shim.PT_ERR_TRAVERSAL, err.value
+                # (3) the next render reports it (and renders nothing): the failed render has certainly finished once a
+                # host-side wait that does NOT check -- a plain stream query through an unrelated event -- has returned
+                r.render(frames, frame_begin=0)
+                fence = adl.SyncObject(device)
+                tmp = adl.Buffer(device, 4, np.int32)
+                tmp.write(np.zeros(4, np.int32), 4, syncObj=fence)   # enqueued behind the render on the handle's stream
+                while not fence.isComplete():
+                    pass
+            with pytest.raises(shim.ShimError) as err:               # (the limit is back at what it was: the whole stack)
+                r.render(frames, frame_begin=0)
+            assert err.value.code == shim.PT_ERR_TRAVERSAL, err.value
+            tmp.release()
+            fence.release()
+            # (4) a blocking map reports it
+            with options(device, BVH_STACK_LIMIT=1):
+                r.render(frames, frame_begin=0)
+                with pytest.raises(shim.ShimError):
+                    r.fb.getHostPtr(blocking=True)
+            r.render(frames, frame_begin=0)
+            got = r.read()
+        finally:
+            try:
+                device.waitForCompletion()
+            except shim.ShimError:
+                pass
+            ev.release()
+            r.release()
     want = oracle.render(tris, mats, W, H, frames)
     assert_fb_equal(got, want, "after the limit was restored")
     with pytest.raises(shim.ShimError):
@@ -151,7 +105,7 @@ def test_lbvh_renders_do_not_wait_for_the_device(device):
     still rendering: several seconds of LBVH work are enqueued in a fraction of the time they take to run."""
     import time
 
-    from oclpathtracer_amd import scene, shim
+    from oclpathtracer_amd import scene
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = scene.make_soup(100_000)
@@ -172,50 +126,12 @@ def test_lbvh_renders_do_not_wait_for_the_device(device):
     assert t_enqueue < 0.25 * t_total, (t_enqueue, t_total)
 
 
-def _horizon_tiles(delta, tile=0.3, glossy_every=3):
-    """Coplanar quads tiling the plane y = eye.y - delta, seen edge-on: the camera (GenerateColors.cl:265-276) looks along -z
-    from (0, 2.75, 4), so the pixel rows just below the image centre meet this plane at cos(incidence) ~ delta / distance,
-    from 1e-1 down to 1e-5 as delta shrinks, and every hit point lies next to the edges of several coplanar tiles -- where
-    binary32's (u, v) of a grazing ray are least certain.  Tiles are smaller than 1/16 of the scene, so they all go INTO the
-    hierarchy; neighbouring tiles have different materials (a wrong tile shows), every third one is glossy (its reflections
-    leave 0.01 above the plane, GenerateColors.cl:257, and graze the next tiles)."""
-    from oclpathtracer_amd import scene
-
-    y = np.float32(2.75 - delta)
-    xs = np.arange(-3.0, 3.0, tile, dtype=np.float32)
-    zs = np.arange(-8.0, 3.95, tile, dtype=np.float32)
-    nq = len(xs) * len(zs)
-    tris = np.zeros(2 * nq, scene.TRIANGLE_DTYPE)
-    mats = np.zeros(8, scene.MATERIAL_DTYPE)
-    rng = np.random.default_rng(1)
-    for m in range(8):
-        mats[m]["albedo"] = tuple(rng.uniform(0.15, 0.95, 3)) + (1.0,)
-        mats[m]["emissive"] = (30.0, 30.0, 30.0, 1.0) if m == 7 else (0.0, 0.0, 0.0, 1.0)
-        mats[m]["type"] = scene.SPECULAR if m % glossy_every == 0 else scene.DIFFUSE
-        mats[m]["roughness"] = np.float32(0.05) if m % glossy_every == 0 else 0.0
-    q = 0
-    s = np.float32(tile)
-    for i, x in enumerate(xs):
-        for j, z in enumerate(zs):
-            a = np.array([x, y, z], np.float32)
-            b = np.array([x, y, z + s], np.float32)
-            c = np.array([x + s, y, z + s], np.float32)
-            d = np.array([x + s, y, z], np.float32)
-            # (a,b,c),(c,d,a) with cross(e2, e1) pointing DOWN: front-facing for rays that come from above (:100)
-            for k, (p1, p2, p3) in enumerate(((a, b, c), (c, d, a))):
-                t = tris[2 * q + k]
-                t["p1"][:3], t["p2"][:3], t["p3"][:3] = p1, p2, p3
-                t["id"] = (i * 5 + j * 3) % 8
-            q += 1
-    return tris, mats
-
-
 @pytest.mark.parametrize("delta", [0.3, 0.03, 0.003, 0.0003])
 def test_grazing_rays_over_coplanar_tiles(device, oracle, delta):
     """The adversarial case for the boxes' margin.  Bit-exact against the brute-force oracle for BOTH searches; the LBVH's
     documented bar where no margin can be proven (rays within ~0.05 degrees of a plane) is north_star's RMS 1e-4, and the
     number of pixels that differ is printed."""
-    tris, mats = _horizon_tiles(delta)
+    tris, mats = horizon_tiles(delta)
     eye = np.array([0.0, 2.75, 4.0])
     n = np.cross(tris["p3"][0, :3] - tris["p1"][0, :3], tris["p2"][0, :3] - tris["p1"][0, :3])
     assert n[1] < 0 and abs(n[0]) == 0 and abs(n[2]) == 0
@@ -227,7 +143,6 @@ def test_grazing_rays_over_coplanar_tiles(device, oracle, delta):
     got1, _ = _render(device, tris, mats, W, H, frames, 1)
     assert_fb_equal(got1, want, "horizon tiles delta %g, brute force" % delta)
     got2, gst = _render(device, tris, mats, W, H, frames, 2, tally=True)
-    from oclpathtracer_amd import shim
     grazing, rays = int(gst[shim.PT_STAT_BVH_GRAZING]), int(gst[shim.PT_STAT_RAYS])
     print("horizon tiles, delta %g: %d of %d rays ended in a hit at cos(incidence) < 1e-2 (the LBVH's unproven range)" % (delta, grazing, rays))
     if delta <= 0.03:
@@ -242,9 +157,7 @@ def test_grazing_rays_over_coplanar_tiles(device, oracle, delta):
 def test_exposed_triangle_buffer_is_prepared_again(device, oracle, cornell):
     """after pt_buffer_device_ptr the caller may rewrite the triangles behind the ABI -- no version is
     bumped -- so the prepared scene (edges, filter tables, masks, LBVH) must not be served from the cache."""
-    import ctypes
-
-    from oclpathtracer_amd import adl, scene, shim
+    from oclpathtracer_amd import adl, scene
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = cornell
@@ -279,7 +192,7 @@ def test_lbvh_exposure_of_the_configs4_soup(device):
     margin is argued conservative (csrc/pt_bvh.hip).  Randomly oriented triangles put ~1e-4 of the hits there (the projected area of
     a triangle seen at cos c is proportional to c: int_0^0.01 c dc / int_0^1 c dc); the count is printed for the README and bounded.
     That these renders are nevertheless bit-exact against brute force is test_configs4_million_triangle_soup_full_size's business."""
-    from oclpathtracer_amd import scene, shim
+    from oclpathtracer_amd import scene
 
     tris, mats = scene.make_soup(1_000_000)
     _, st = _render(device, tris, mats, 1024, 1024, 8, 0, tally=True)
@@ -293,9 +206,7 @@ def test_exposed_scene_is_built_again_only_when_its_records_changed(device, orac
     """a triangle buffer whose device pointer has been handed out is prepared again for every render -- and used to be BUILT
     again for every render (radix sort, hierarchy, host waits), for the buffer's lifetime.  The prep kernel now returns a checksum of
     the raw records: same contents, same hierarchy; changed contents, a new one."""
-    import ctypes
-
-    from oclpathtracer_amd import adl, scene, shim
+    from oclpathtracer_amd import adl, scene
     from oclpathtracer_amd.render import Renderer
 
     lib = shim.load()

@@ -1,23 +1,23 @@
 """What the LBVH takes as candidates, at the edges: the scale, offset and shape of the scene, the builder's boundaries -- queries
 under PT_OPT_ACCEL = 2 against the CPU oracle and against PT_OPT_ACCEL = 1, bit for bit -- and an independent check of every
 hierarchy the device built (pt_bvh_snapshot, tests/bvh_check.py): structure, containment of every triangle below every box,
-tightness.  The scenes are tests/lbvh_scenes.py's; the oracle's scale identities they lean on are tests/test_lbvh_scale_cpu.py's."""
+tightness.  The scenes are tests/scenes.py's; the oracle's scale identities they lean on are tests/test_lbvh_scale_cpu.py's."""
 import ctypes
 
 import numpy as np
 import pytest
 
 import bvh_check as B
-import lbvh_scenes as S
-from test_gpu_query import _Options, assert_hits_equal
+import query_oracle as qo
+import scenes as S
+from gpu_support import assert_hits_equal, options
+from oclpathtracer_amd import shim
 
 pytestmark = pytest.mark.gpu
 
 
 def snapshot(device):
     """(records uint8 [R, 64], grid_min, grid_step, big indices) of the LBVH that stands for the device's prepared scene"""
-    from oclpathtracer_amd import shim
-
     lib = shim.load()
     info = shim.BvhInfo()
     shim.check(lib.pt_bvh_snapshot(device._h, ctypes.byref(info), None, 0, None))
@@ -30,8 +30,6 @@ def snapshot(device):
 
 def check_hierarchy(device, tris, what):
     """snapshot the hierarchy that stands and hand it to the checker; the snapshot itself must change nothing"""
-    from oclpathtracer_amd import shim
-
     lib = shim.load()
     builds = lib.pt_device_get_option(device._h, shim.PT_OPT_BVH_BUILD_COUNT)
     ws = device.getWorkspaceMemory()
@@ -53,8 +51,6 @@ def _probe_rays(n=64):
 
 @pytest.mark.parametrize("name", S.NAMES)
 def test_scene_through_the_lbvh(device, name):
-    import query_oracle as qo
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.query import RayCaster
 
     tris, rays = S.scene(name)
@@ -76,12 +72,12 @@ def test_scene_through_the_lbvh(device, name):
     rc = RayCaster(device, tris)
     try:
         if name in ("n511", "n512"):                            # PT_OPT_ACCEL = 0: the hierarchy from 512 triangles on
-            with _Options(device, ACCEL=0):
+            with options(device, ACCEL=0):
                 b = count()
                 auto = rc.closest(rays)
                 assert count() - b == (1 if len(tris) >= 512 else 0), name + ": the wrong search ran"
             assert_hits_equal(auto, want, name + " a0")
-        with _Options(device, ACCEL=2):
+        with options(device, ACCEL=2):
             b = count()
             got2 = rc.closest(rays)
             occ = rc.occluded(rays)
@@ -90,7 +86,7 @@ def test_scene_through_the_lbvh(device, name):
             check_hierarchy(device, tris, name)
             if name in ("big64", "big65"):                      # the builder's n > PT_BVH_BIG_MAX and k < PT_BVH_BIG_MAX comparisons sit here
                 assert len(snapshot(device)[3]) == (64 if name == "big64" else 0), name + ": the scene no longer sits on the boundary"
-        with _Options(device, ACCEL=1):
+        with options(device, ACCEL=1):
             got1 = rc.closest(rays)
     finally:
         rc.release()
@@ -105,19 +101,18 @@ def test_scene_through_the_lbvh(device, name):
 
 
 def test_snapshot_refuses_when_no_lbvh_stands(device):
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.query import RayCaster
 
     lib = shim.load()
     tris = S.soup(700, 61)
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=1):
+        with options(device, ACCEL=1):
             rc.closest(_probe_rays())                           # the scene is prepared, no hierarchy is built
         info = shim.BvhInfo()
         assert lib.pt_bvh_snapshot(device._h, ctypes.byref(info), None, 0, None) == shim.PT_ERR_INVALID
         assert lib.pt_bvh_snapshot(device._h, None, None, 0, None) == shim.PT_ERR_INVALID
-        with _Options(device, ACCEL=2):
+        with options(device, ACCEL=2):
             rc.closest(_probe_rays())
             assert lib.pt_bvh_snapshot(device._h, ctypes.byref(info), None, 0, None) == shim.PT_OK and info.records > 700
             small = np.zeros((8, 64), np.uint8)
@@ -128,17 +123,15 @@ def test_snapshot_refuses_when_no_lbvh_stands(device):
 
 
 def _built_scenes():
-    from test_gpu_lbvh_robust import _horizon_tiles
-    from test_gpu_parity import _bvh_edge_scene
     from oclpathtracer_amd import scene
 
     yield "cornell", lambda: scene.load_model()[0]
     for n in (300, 2000, 20000, 200000):
         yield "soup%d" % n, (lambda n=n: scene.make_soup(n)[0])
     for kind in ("two", "three", "nine", "duplicates", "clustered", "many_big", "flat"):
-        yield "edge_" + kind, (lambda kind=kind: _bvh_edge_scene(kind)[0])
+        yield "edge_" + kind, (lambda kind=kind: S.bvh_edge(kind)[0])
     for delta in (0.3, 0.03, 0.003, 0.0003):
-        yield "tiles%g" % delta, (lambda delta=delta: _horizon_tiles(delta)[0])
+        yield "tiles%g" % delta, (lambda delta=delta: S.horizon_tiles(delta)[0])
 
 
 @pytest.mark.parametrize("name", ["cornell", "soup300", "soup2000", "soup20000", "soup200000", "edge_two", "edge_three", "edge_nine",
@@ -151,7 +144,7 @@ def test_built_hierarchy_passes_the_checker(device, name):
     tris = dict(_built_scenes())[name]()
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=2):
+        with options(device, ACCEL=2):
             rc.closest(_probe_rays())
             out = check_hierarchy(device, tris, name)
     finally:

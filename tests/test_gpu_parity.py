@@ -12,27 +12,14 @@ import os
 import numpy as np
 import pytest
 
+import scenes
 from conftest import GOLDEN, assert_fb_equal, rms_diff
+from gpu_support import options, render
+from oclpathtracer_amd import shim
 
 pytestmark = pytest.mark.gpu
 
 RMS_TOL = 1e-4  # BASELINE.json north_star: "pixels within 1e-4 RMS of the OpenCL reference"
-
-
-
-
-def _render_gpu(device, tris, mats, W, H, frames, *, depth=16, frame_begin=0, fb_init=None, **kw):
-    from oclpathtracer_amd import shim
-    from oclpathtracer_amd.render import Renderer
-
-    r = Renderer(device, tris, mats, W, H, **kw)
-    try:
-        if fb_init is not None:
-            r.fb.write(np.ascontiguousarray(fb_init, np.float32), r.local_pixels)
-        r.render(frames, frame_begin=frame_begin, max_bounces=depth)
-        return r.read()
-    finally:
-        r.release()
 
 
 GOLDEN_CASES = ["cornell_64x64_f1_d16", "cornell_64x64_f2_d16", "cornell_64x64_f8_d16", "cornell_64x64_f8_d2",
@@ -45,7 +32,7 @@ def test_fused_render_matches_golden(device, cornell, name):
         meta = json.load(f)[name]
     want = np.load(os.path.join(GOLDEN, name + ".npy"))
     tris, mats = cornell
-    got = _render_gpu(device, tris, mats, meta["W"], meta["H"], meta["frames"], depth=meta["max_bounces"])
+    got = render(device, tris, mats, meta["W"], meta["H"], meta["frames"], depth=meta["max_bounces"])
     assert_fb_equal(got, want, name)
     assert rms_diff(got, want) <= RMS_TOL
 
@@ -58,28 +45,19 @@ def test_fused_render_matches_golden(device, cornell, name):
 def test_fused_render_matches_oracle(device, cornell, oracle, W, H, frames, depth):
     tris, mats = cornell
     want, st = oracle.render(tris, mats, W, H, frames, max_bounces=depth, want_stats=True)
-    from oclpathtracer_amd import shim
-    from oclpathtracer_amd.render import Renderer
-
-    r = Renderer(device, tris, mats, W, H, want_stats=True)
-    try:
-        r.render(frames, max_bounces=depth)
-        got = r.read()
-        gst = r.read_stats()
-    finally:
-        r.release()
+    got, gst = render(device, tris, mats, W, H, frames, depth=depth, want_stats=True)
     assert_fb_equal(got, want, "%dx%d f%d d%d" % (W, H, frames, depth))
     assert rms_diff(got, want) <= RMS_TOL
     # integer work counters: exact
-    assert gst["samples"] == st["samples"] == W * H * frames
-    assert gst["rays"] == st["rays"]
+    assert gst[shim.PT_STAT_SAMPLES] == st["samples"] == W * H * frames
+    assert gst[shim.PT_STAT_RAYS] == st["rays"]
 
 
 def test_configs1_direct_full_size(device, cornell, oracle):
     """BASELINE configs[1]: 512x512, 64 spp, depth cap 2 -- full size, bit-exact."""
     tris, mats = cornell
     want = oracle.render(tris, mats, 512, 512, 64, max_bounces=2)
-    got = _render_gpu(device, tris, mats, 512, 512, 64, depth=2)
+    got = render(device, tris, mats, 512, 512, 64, depth=2)
     assert_fb_equal(got, want, "C2")
 
 
@@ -91,7 +69,7 @@ def test_configs2_full_size_sampled_pixels(device, cornell, oracle):
     tris, mats = cornell
     W = H = 1024
     frames = 256
-    got = _render_gpu(device, tris, mats, W, H, frames).reshape(H * W, 4)
+    got = render(device, tris, mats, W, H, frames).reshape(H * W, 4)
     assert np.all(got[:, 3] == 1.0)
     assert not np.any(got[:, :3] < 0)
     rng = np.random.default_rng(20261004)
@@ -108,32 +86,22 @@ def test_primary_masks_on_and_off(device, cornell, oracle, W, H, frames):
     """PT_OPT_PRIMARY_MASKS: fresh waves of primary rays take their pass-1 survivors from per-pixel candidate masks
     (default) or run the filter like any other ray (0).  Same pixels, same ray counts, at footprints from 1/33 to
     1/200 of the image and aspect ratios 4:1 and 1:3 (the masks' margin grows with the pixel's footprint)."""
-    from oclpathtracer_amd import shim
-    from oclpathtracer_amd.render import Renderer
-
     tris, mats = cornell
     want, st = oracle.render(tris, mats, W, H, frames, want_stats=True)
     for on in (1, 0):
-        device.setOption(shim.PT_OPT_PRIMARY_MASKS, on)
-        r = Renderer(device, tris, mats, W, H, want_stats=True)
-        try:
-            r.render(frames)
-            got, gst = r.read(), r.read_stats()
-        finally:
-            r.release()
-            device.setOption(shim.PT_OPT_PRIMARY_MASKS, 1)
+        with options(device, PRIMARY_MASKS=on):
+            got, gst = render(device, tris, mats, W, H, frames, want_stats=True)
         assert_fb_equal(got, want, "primary masks %d, %dx%d" % (on, W, H))
-        assert gst["rays"] == st["rays"]
+        assert gst[shim.PT_STAT_RAYS] == st["rays"]
 
 
 def test_resume_equals_one_shot(device, cornell):
     """Accumulation is resumable (frame is an argument, GenerateColors.cl:314-321): 3+5 frames in
     two calls == 8 frames in one, and chunked staging == unchunked."""
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = cornell
-    one = _render_gpu(device, tris, mats, 64, 64, 8)
+    one = render(device, tris, mats, 64, 64, 8)
     r = Renderer(device, tris, mats, 64, 64)
     try:
         r.render(3)
@@ -142,11 +110,8 @@ def test_resume_equals_one_shot(device, cornell):
     finally:
         r.release()
     assert_fb_equal(two, one, "resume")
-    device.setOption(shim.PT_OPT_CHUNK_FRAMES, 3)
-    try:
-        chunked = _render_gpu(device, tris, mats, 64, 64, 8)
-    finally:
-        device.setOption(shim.PT_OPT_CHUNK_FRAMES, 0)
+    with options(device, CHUNK_FRAMES=3):
+        chunked = render(device, tris, mats, 64, 64, 8)
     assert_fb_equal(chunked, one, "chunked")
     want = np.load(os.path.join(GOLDEN, "cornell_64x64_f8_d16.npy"))
     assert_fb_equal(one, want, "one-shot vs golden")
@@ -158,12 +123,12 @@ def test_frame1_discards_frame0(device, cornell, oracle):
     tris, mats = cornell
     W = H = 32
     junk = np.random.default_rng(1).random((W * H, 4)).astype(np.float32) * 7
-    a = _render_gpu(device, tris, mats, W, H, 4, frame_begin=1, fb_init=junk)
-    b = _render_gpu(device, tris, mats, W, H, 5)
+    a = render(device, tris, mats, W, H, 4, frame_begin=1, fb_init=junk)
+    b = render(device, tris, mats, W, H, 5)
     assert_fb_equal(a, b, "frame0 discarded")
     # an infinite stored value poisons the pixel: 0 * inf = NaN, on both sides alike
     junk[5, 0] = np.inf
-    got = _render_gpu(device, tris, mats, W, H, 2, frame_begin=1, fb_init=junk)
+    got = render(device, tris, mats, W, H, 2, frame_begin=1, fb_init=junk)
     want = oracle.render(tris, mats, W, H, 2, frame_begin=1, fb=junk.copy())
     assert_fb_equal(got, want, "inf poison")
     assert np.isnan(got[5, 0])
@@ -172,18 +137,14 @@ def test_frame1_discards_frame0(device, cornell, oracle):
 def test_reference_loop_matches_fused_and_oracle(device, cornell, oracle):
     """The RaytraceTest-shaped per-frame Launcher loop (both immediate and with deferred frame
     batching) gives the same bits as the fused call and the oracle."""
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.render import raycast_reference_loop
 
     tris, mats = cornell
     dim, frames = 64, 8
     want = np.load(os.path.join(GOLDEN, "cornell_64x64_f8_d16.npy"))
     for batch in (1, 0):
-        device.setOption(shim.PT_OPT_BATCH_FRAMES, batch)
-        try:
+        with options(device, BATCH_FRAMES=batch):
             got = raycast_reference_loop(device, tris, mats, dim, frames)
-        finally:
-            device.setOption(shim.PT_OPT_BATCH_FRAMES, 1)
         assert_fb_equal(got, want, "reference loop, batch=%d" % batch)
 
 
@@ -191,12 +152,12 @@ def test_reference_loop_matches_fused_and_oracle(device, cornell, oracle):
 def test_stripe_sharding_reassembles_bit_exact(device, cornell, n_ranks, stripe_rows, H):
     """Rows dealt to n_ranks in stripes, each rank rendered separately with GLOBAL pixel ids,
     then assembled on the device == the single-device image."""
-    from oclpathtracer_amd import adl, shim
+    from oclpathtracer_amd import adl
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = cornell
     W, frames = 48, 3
-    full = _render_gpu(device, tris, mats, W, H, frames).reshape(H, W, 4)
+    full = render(device, tris, mats, W, H, frames).reshape(H, W, 4)
     lib = shim.load()
     slab_rows = max(lib.pt_local_rows(H, stripe_rows, n_ranks, r) for r in range(n_ranks))
     gathered = np.zeros((n_ranks, slab_rows, W, 4), np.float32)
@@ -235,15 +196,15 @@ def test_soup_scene_runtime_triangle_count(device, oracle):
     tris, mats = scene.make_soup(2000)
     W, H, frames = 48, 32, 2
     want = oracle.render(tris, mats, W, H, frames)
-    got = _render_gpu(device, tris, mats, W, H, frames)
+    got = render(device, tris, mats, W, H, frames)
     assert_fb_equal(got, want, "soup 2000")
 
 
 def test_tonemap_matches_host_f2c(device, cornell):
-    from oclpathtracer_amd import adl, scene, shim
+    from oclpathtracer_amd import adl, scene
 
     tris, mats = cornell
-    fb = _render_gpu(device, tris, mats, 64, 64, 4)
+    fb = render(device, tris, mats, 64, 64, 4)
     fb[3, 0] = np.nan
     fb[4, 1] = np.inf
     fb[5, 2] = 0.0
@@ -268,54 +229,6 @@ def test_tonemap_matches_host_f2c(device, cornell):
     assert np.array_equal(want, scene.f2c(fb[:, :3]).reshape(-1))   # ... and the product's host-side f2c agrees with it
 
 
-def _variant_scene(kind):
-    """Scenes that steer the shim into each trace-kernel specialisation."""
-    from oclpathtracer_amd import scene
-
-    tris, mats = scene.load_model()
-    tris = tris.copy()
-    if kind == "quads_scaled":      # still (2k, 2k+1) quads, other numbers: quad filter
-        for f in ("p1", "p2", "p3"):
-            tris[f][:, :3] = tris[f][:, :3] * np.float32(0.73) + np.array([0.11, 0.4, -0.2], np.float32)
-    elif kind == "pairs_broken":    # same triangles, rotated by one: no pair is a quad: generic filter
-        tris = np.roll(tris, 1)
-    elif kind == "odd_count":       # 35 triangles
-        tris = tris[:35].copy()
-    elif kind == "huge_extent":     # |e1||e2| > 2e19: exact-division kernel (DET_BOUNDED = false)
-        for f in ("p1", "p2", "p3"):
-            tris[f][:, :3] = tris[f][:, :3] * np.float32(3.0e10)
-    elif kind == "one_triangle":
-        tris = tris[2:3].copy()
-    elif kind == "degenerate":      # zero-area and NaN triangles among the real ones
-        tris[4]["p2"] = tris[4]["p1"]
-        tris[7]["p3"][:3] = np.nan
-    elif kind == "quads_skewed":    # (a,b,c),(c,d,a) pairs far from parallelograms: shared-u filter, wide margins
-        rng = np.random.default_rng(7)
-        tris["p2"][1::2, :3] += rng.uniform(-0.4, 0.4, (len(tris) // 2, 3)).astype(np.float32)
-    elif kind == "quads_tiny":      # the box shrunk to 5 cm in front of the eye: shared-u margins at their floor
-        eye = np.array([0.0, 2.75, 4.0], np.float32)
-        for f in ("p1", "p2", "p3"):
-            tris[f][:, :3] = (tris[f][:, :3] - eye) * np.float32(0.01) + eye + np.array([0.0, 0.0, -0.05], np.float32)
-    elif kind == "quads_detached":  # second triangles translated: e2' == -e2 still, p1' != p3: pair filter only
-        for f in ("p1", "p2", "p3"):
-            tris[f][1::2, :3] += np.array([0.25, -0.125, 0.5], np.float32)
-    elif kind == "quads_nan_second":  # a NaN in the second triangle's e1 only: the pair structure survives
-        tris["p2"][9, 1] = np.nan
-    elif kind == "quads_17":        # an odd number of quads: the packed filter's last table entry is half padding
-        tris = tris[:34].copy()
-    elif kind == "quads_2":         # one pair of quads only
-        tris = tris[4:8].copy()
-    elif kind == "quads_72tri":     # three 32-triangle chunks: the box plus a shrunk copy of itself inside it
-        inner = tris.copy()
-        for f in ("p1", "p2", "p3"):
-            inner[f][:, :3] = inner[f][:, :3] * np.float32(0.4) + np.array([0.3, 1.2, -1.9], np.float32)
-        tris = np.concatenate([tris, inner])
-    elif kind == "quads_far":       # scene far from the eye relative to its size: large radius, small triangles
-        for f in ("p1", "p2", "p3"):
-            tris[f][:, :3] = tris[f][:, :3] * np.float32(4.0) + np.array([0.0, -8.25, -160.0], np.float32)
-    return tris, mats
-
-
 @pytest.mark.parametrize("kind", ["quads_scaled", "pairs_broken", "odd_count", "huge_extent", "one_triangle", "degenerate",
                                   "quads_skewed", "quads_tiny", "quads_detached", "quads_nan_second", "quads_far",
                                   "quads_17", "quads_2", "quads_72tri"])
@@ -323,24 +236,13 @@ def _variant_scene(kind):
 def test_kernel_specialisations_match_oracle(device, oracle, kind, quad_filter):
     """quad_filter = PT_OPT_QUAD_FILTER: 0 = the strongest pass-1 filter the scene allows (packed shared-u for
     quad scenes), 1 = independent triangles."""
-    from oclpathtracer_amd import shim
-
-    tris, mats = _variant_scene(kind)
+    tris, mats = scenes.variant(kind)
     W, H, frames = 64, 48, 3
     want, st = oracle.render(tris, mats, W, H, frames, want_stats=True)
-    from oclpathtracer_amd.render import Renderer
-
-    device.setOption(shim.PT_OPT_QUAD_FILTER, quad_filter)
-    r = Renderer(device, tris, mats, W, H, want_stats=True)
-    try:
-        r.render(frames)
-        got = r.read()
-        gst = r.read_stats()
-    finally:
-        r.release()
-        device.setOption(shim.PT_OPT_QUAD_FILTER, 0)
+    with options(device, QUAD_FILTER=quad_filter):
+        got, gst = render(device, tris, mats, W, H, frames, want_stats=True)
     assert_fb_equal(got, want, kind)
-    assert gst["rays"] == st["rays"]
+    assert gst[shim.PT_STAT_RAYS] == st["rays"]
 
 
 @pytest.mark.parametrize("copies", [8, 13])
@@ -349,28 +251,13 @@ def test_tiled_brute_force_between_the_lds_table_and_the_lbvh(device, oracle, co
     streamed through a per-wave LDS tile (north_star's "LDS staging of triangle tiles"; the reference's loop is
     GenerateColors.cl:137-154 with a runtime count).  Nested, shrunk copies of the Cornell box make MANY lanes hold
     survivors in most chunks, so the tile path (not just the tail) does the work: 288 and 468 triangles."""
-    from oclpathtracer_amd.render import Renderer
-
-    tris, mats = cornell
-    parts = []
-    for c in range(copies):
-        t = tris.copy()
-        k = np.float32(1.0 - 0.06 * c)
-        for f in ("p1", "p2", "p3"):
-            t[f][:, :3] = t[f][:, :3] * k + np.array([0.0, 2.7, -2.8], np.float32) * (np.float32(1.0) - k)
-        parts.append(t)
-    big = np.concatenate(parts)
+    big, mats = scenes.nested_boxes(copies)
     assert 256 < len(big) < 512
     W, H, frames = 64, 48, 3
     want, st = oracle.render(big, mats, W, H, frames, want_stats=True)
-    r = Renderer(device, big, mats, W, H, want_stats=True)
-    try:
-        r.render(frames)
-        got, gst = r.read(), r.read_stats()
-    finally:
-        r.release()
+    got, gst = render(device, big, mats, W, H, frames, want_stats=True)
     assert_fb_equal(got, want, "tiled brute force, %d triangles" % len(big))
-    assert gst["rays"] == st["rays"]
+    assert gst[shim.PT_STAT_RAYS] == st["rays"]
 
 
 @pytest.mark.gpu
@@ -381,111 +268,47 @@ def test_bvh_matches_oracle(device, oracle, kind, ntri):
     Asserted bit for bit -- what the order-free argmin (t, index) argument gives whenever no accepted hit
     lies outside its triangle's grown box; north_star's tolerance (RMS 1e-4) is the documented bar for
     the near-parallel rays that argument cannot cover (csrc/pt_bvh.hip)."""
-    from oclpathtracer_amd import scene, shim
-    from oclpathtracer_amd.render import Renderer
+    from oclpathtracer_amd import scene
 
     if kind == "cornell":
         tris, mats = scene.load_model()
     elif kind == "soup":
         tris, mats = scene.make_soup(ntri)
     else:
-        tris, mats = _variant_scene(kind)
+        tris, mats = scenes.variant(kind)
     W, H, frames = (64, 48, 3) if ntri <= 2000 else (48, 32, 2)
     want, st = oracle.render(tris, mats, W, H, frames, want_stats=True)
-    device.setOption(shim.PT_OPT_ACCEL, 2)
-    r = Renderer(device, tris, mats, W, H, want_stats=True)
-    try:
-        r.render(frames)
-        got = r.read()
-        gst = r.read_stats()
-    finally:
-        r.release()
-        device.setOption(shim.PT_OPT_ACCEL, 0)
+    with options(device, ACCEL=2):
+        got, gst = render(device, tris, mats, W, H, frames, want_stats=True)
     assert rms_diff(got, want) <= 1e-4
     assert_fb_equal(got, want, "bvh %s %d" % (kind, ntri))
-    assert gst["rays"] == st["rays"]
-
-
-def _bvh_edge_scene(kind):
-    """Scenes that steer the LBVH builder into its corner cases (csrc/pt_bvh.hip: radix tree, eight-child collapse, big
-    triangles outside the tree)."""
-    from oclpathtracer_amd import scene
-
-    box, mats = scene.load_model()
-    rng = np.random.default_rng(99)
-
-    def small(n, centres, size=0.05):
-        t = np.zeros(n, scene.TRIANGLE_DTYPE)
-        c = centres.astype(np.float32)
-        t["p1"][:, :3] = c
-        t["p2"][:, :3] = c + rng.uniform(-size, size, (n, 3)).astype(np.float32)
-        t["p3"][:, :3] = c + rng.uniform(-size, size, (n, 3)).astype(np.float32)
-        t["id"] = rng.integers(0, len(mats), n)
-        return t
-
-    lo, span = np.array([-2.5, 0.2, -5.2]), np.array([5.0, 5.0, 5.0])
-    if kind == "two":            # the smallest hierarchy: one node, two leaves
-        return box[20:22].copy(), mats
-    if kind == "three":
-        return box[20:23].copy(), mats
-    if kind == "nine":           # one more leaf than a node holds
-        return small(9, lo + span * rng.random((9, 3)), 0.8), mats
-    if kind == "duplicates":     # 300 copies of one triangle (equal Morton codes: the tree splits on the index bits) in the box
-        t = small(1, (lo + span * 0.5)[None, :], 0.6)
-        return np.concatenate([box, np.repeat(t, 300)]), mats
-    if kind == "clustered":      # centres at 1 - 2^-k along the diagonal: every radix split peels one leaf off, a deep chain
-        k = np.arange(1, 25)
-        c = lo[None, :] + span[None, :] * (1.0 - 2.0 ** -k)[:, None]
-        return np.concatenate([box, small(24, c, 0.02), small(400, lo + span * rng.random((400, 3)))]), mats
-    if kind == "many_big":       # more big triangles than the brute-force table holds (64): they all stay in the tree
-        return np.concatenate([box, small(90, lo + span * rng.random((90, 3)), 2.5), small(500, lo + span * rng.random((500, 3)))]), mats
-    if kind == "flat":           # every centre in one plane: one Morton axis carries no information
-        c = lo + span * rng.random((700, 3))
-        c[:, 1] = 2.0
-        return np.concatenate([box, small(700, c)]), mats
-    raise ValueError(kind)
+    assert gst[shim.PT_STAT_RAYS] == st["rays"]
 
 
 @pytest.mark.parametrize("kind", ["two", "three", "nine", "duplicates", "clustered", "many_big", "flat"])
 def test_bvh_builder_corner_cases_match_oracle(device, oracle, kind):
     """PT_OPT_ACCEL = 2 on scenes chosen for the builder, bit for bit against the brute-force oracle."""
-    from oclpathtracer_amd import shim
-    from oclpathtracer_amd.render import Renderer
-
-    tris, mats = _bvh_edge_scene(kind)
+    tris, mats = scenes.bvh_edge(kind)
     W, H, frames = 48, 40, 3
     want, st = oracle.render(tris, mats, W, H, frames, want_stats=True)
-    device.setOption(shim.PT_OPT_ACCEL, 2)
-    r = Renderer(device, tris, mats, W, H, want_stats=True)
-    try:
-        r.render(frames)
-        got, gst = r.read(), r.read_stats()
-    finally:
-        r.release()
-        device.setOption(shim.PT_OPT_ACCEL, 0)
+    with options(device, ACCEL=2):
+        got, gst = render(device, tris, mats, W, H, frames, want_stats=True)
     assert_fb_equal(got, want, "bvh corner case %s" % kind)
-    assert gst["rays"] == st["rays"]
+    assert gst[shim.PT_STAT_RAYS] == st["rays"]
 
 
 def test_bvh_matches_gpu_brute_force_200k_triangles(device):
     """A soup too large for the CPU oracle: the LBVH against the brute-force kernel on the same GPU."""
-    from oclpathtracer_amd import scene, shim
-    from oclpathtracer_amd.render import Renderer
+    from oclpathtracer_amd import scene
 
     tris, mats = scene.make_soup(200_000)
     W, H, frames = 64, 32, 2
     out = {}
     for accel in (1, 2):
-        device.setOption(shim.PT_OPT_ACCEL, accel)
-        r = Renderer(device, tris, mats, W, H, want_stats=True)
-        try:
-            r.render(frames)
-            out[accel] = (r.read(), r.read_stats())
-        finally:
-            r.release()
-            device.setOption(shim.PT_OPT_ACCEL, 0)
+        with options(device, ACCEL=accel):
+            out[accel] = render(device, tris, mats, W, H, frames, want_stats=True)
     assert_fb_equal(out[2][0], out[1][0], "bvh vs brute force, 200k triangles")
-    assert out[2][1]["rays"] == out[1][1]["rays"]
+    assert out[2][1][shim.PT_STAT_RAYS] == out[1][1][shim.PT_STAT_RAYS]
 
 
 def _erode(mask: np.ndarray) -> np.ndarray:
@@ -539,17 +362,11 @@ def test_gpu_render_matches_reference_jpg(device, cornell):
       * SIGNED mean residual per region (jpg_regions): a systematic error in one surface's shading shows up
         here long before it moves the unsigned mean; every region must be within REGION_TOL of zero."""
     from oclpathtracer_amd import scene
-    from oclpathtracer_amd.render import Renderer
 
     ref = np.load(os.path.join(GOLDEN, "reference_jpg_blocks_64x64.npy")).astype(np.float64)
     tris, mats = cornell
     W, frames, G = 512, 10000, 64
-    r = Renderer(device, tris, mats, W, W)
-    try:
-        r.render(frames)
-        fb = r.read()
-    finally:
-        r.release()
+    fb = render(device, tris, mats, W, W, frames)
     img = scene.f2c(fb[:, :3]).reshape(W, W, 3).astype(np.float64)
     blocks = img.reshape(G, W // G, G, W // G, 3).mean(axis=(1, 3))
     diff = np.abs(blocks - ref)
@@ -587,62 +404,19 @@ def test_gpu_render_matches_reference_jpg(device, cornell):
 REGION_TOL = 1.25  # of 255; measured: profiles/r02/jpg_region_residuals.txt (<= 0.08 in the large mixed regions, <= 0.94 in flat colour areas)
 
 
-def _random_quad_scene(seed: int):
-    """Random (a,b,c),(c,d,a) quads around the view volume: parallelograms, perturbed parallelograms,
-    slivers, huge and tiny ones, some facing away; random diffuse / glossy / emissive materials."""
-    from oclpathtracer_amd import scene
-
-    rng = np.random.default_rng(seed)
-    nq = int(rng.integers(1, 40))
-    tris = np.zeros(2 * nq, scene.TRIANGLE_DTYPE)
-    mats = np.zeros(nq, scene.MATERIAL_DTYPE)
-    scale = np.float32(10.0 ** rng.uniform(-1.5, 1.5))          # scene size: 0.03 ... 30
-    centre = np.array([0.0, 2.75, 4.0], np.float32) + np.array([0.0, 0.0, -1.0], np.float32) * scale * np.float32(1.5)
-    for q in range(nq):
-        a = centre + rng.uniform(-1, 1, 3).astype(np.float32) * scale
-        e1 = rng.uniform(-1, 1, 3).astype(np.float32) * scale * np.float32(10.0 ** rng.uniform(-1.5, 0.5))
-        e2 = rng.uniform(-1, 1, 3).astype(np.float32) * scale * np.float32(10.0 ** rng.uniform(-1.5, 0.5))
-        if rng.random() < 0.7 and np.dot(np.cross(e2, e1), a - np.array([0.0, 2.75, 4.0], np.float32)) < 0:
-            e1, e2 = e2, e1                                      # most quads face the eye (cull test :100)
-        b, c = a + e1, a + e1 + e2
-        d = a + e2
-        if rng.random() < 0.5:                                   # not a parallelogram
-            d = d + rng.uniform(-0.3, 0.3, 3).astype(np.float32) * np.float32(np.abs(e1).max())
-        for k, (p1, p2, p3) in enumerate(((a, b, c), (c, d, a))):
-            t = tris[2 * q + k]
-            t["p1"][:3], t["p2"][:3], t["p3"][:3] = p1, p2, p3
-            t["id"] = q
-        m = mats[q]
-        m["albedo"] = tuple(rng.uniform(0.05, 0.95, 3)) + (1.0,)
-        m["emissive"] = ((30.0, 30.0, 30.0, 1.0) if rng.random() < 0.15 else (0.0, 0.0, 0.0, 1.0))
-        m["type"] = scene.SPECULAR if rng.random() < 0.3 else scene.DIFFUSE
-        m["roughness"] = np.float32(10.0 ** rng.uniform(-2.5, -0.3)) if m["type"] == scene.SPECULAR else 0.0
-    return tris, mats
-
-
 @pytest.mark.parametrize("seed", list(range(12)))
 def test_random_quad_scenes_match_oracle(device, oracle, seed):
     """Fuzz of the scene-dependent machinery: whatever filter mode, slack and kernel variant the shim
     picks for a random quad scene (auto), and with the LBVH forced, pixels and ray counts equal the
     brute-force oracle's."""
-    from oclpathtracer_amd import shim
-    from oclpathtracer_amd.render import Renderer
-
-    tris, mats = _random_quad_scene(1000 + seed)
+    tris, mats = scenes.random_quads(1000 + seed)
     W, H, frames = 48, 40, 3
     want, st = oracle.render(tris, mats, W, H, frames, want_stats=True)
     for accel in (0, 2) if len(tris) >= 2 else (0,):
-        device.setOption(shim.PT_OPT_ACCEL, accel)
-        r = Renderer(device, tris, mats, W, H, want_stats=True)
-        try:
-            r.render(frames)
-            got = r.read()
-            gst = r.read_stats()
-        finally:
-            r.release()
-            device.setOption(shim.PT_OPT_ACCEL, 0)
+        with options(device, ACCEL=accel):
+            got, gst = render(device, tris, mats, W, H, frames, want_stats=True)
         assert_fb_equal(got, want, "random quads seed %d accel %d (%d triangles)" % (seed, accel, len(tris)))
-        assert gst["rays"] == st["rays"]
+        assert gst[shim.PT_STAT_RAYS] == st["rays"]
 
 
 def test_configs3_one_rank_of_eight_full_size(device, cornell, oracle):
@@ -687,20 +461,13 @@ def test_configs4_million_triangle_soup_full_size(device, oracle):
         frame 0: identical bits and ray counts."""
     from concurrent.futures import ThreadPoolExecutor
 
-    from oclpathtracer_amd import scene, shim
-    from oclpathtracer_amd.render import Renderer
+    from oclpathtracer_amd import scene
 
     tris, mats = scene.make_soup(1_000_000)
     W = H = 1024
     frames = 256
-    r = Renderer(device, tris, mats, W, H, want_stats=True)
-    try:
-        r.render(frames)
-        got = r.read()
-        st = r.read_stats()
-    finally:
-        r.release()
-    assert st["samples"] == W * H * frames
+    got, st = render(device, tris, mats, W, H, frames, want_stats=True)
+    assert st[shim.PT_STAT_SAMPLES] == W * H * frames
     assert np.all(got[:, 3] == 1.0)
     assert not np.any(got[:, :3] < 0)
 
@@ -720,17 +487,11 @@ def test_configs4_million_triangle_soup_full_size(device, oracle):
     rows_ab = 64
     out = {}
     for accel in (0, 1):
-        device.setOption(shim.PT_OPT_ACCEL, accel)
-        r = Renderer(device, tris, mats, W, H, n_ranks=H // rows_ab, rank=0, stripe_rows=rows_ab, want_stats=True)
-        try:
-            r.render(1)
-            out[accel] = (r.read(), r.read_stats())
-        finally:
-            r.release()
-            device.setOption(shim.PT_OPT_ACCEL, 0)
+        with options(device, ACCEL=accel):
+            out[accel] = render(device, tris, mats, W, H, 1, n_ranks=H // rows_ab, rank=0, stripe_rows=rows_ab, want_stats=True)
     assert out[0][0].shape == (rows_ab * W, 4)
     assert_fb_equal(out[0][0], out[1][0], "1M-triangle soup, LBVH vs brute force, 65 536 pixels")
-    assert out[0][1]["rays"] == out[1][1]["rays"]
+    assert out[0][1][shim.PT_STAT_RAYS] == out[1][1][shim.PT_STAT_RAYS]
 
 
 def test_bvh_exact_ties_go_to_the_lowest_index(device, oracle, cornell):
@@ -739,9 +500,6 @@ def test_bvh_exact_ties_go_to_the_lowest_index(device, oracle, cornell):
     its strict `t < tmax` (GenerateColors.cl:125,145-151) gives to the lowest index.  The copies carry
     OTHER materials than the originals, so a traversal that resolved ties by visiting order would
     change the image."""
-    from oclpathtracer_amd import scene, shim
-    from oclpathtracer_amd.render import Renderer
-
     tris, mats = cornell
     rng = np.random.default_rng(5)
     copies = np.concatenate([tris[rng.permutation(len(tris))] for _ in range(17)])
@@ -752,17 +510,10 @@ def test_bvh_exact_ties_go_to_the_lowest_index(device, oracle, cornell):
     base = oracle.render(tris, mats, W, H, frames)
     assert np.array_equal(want.view(np.uint32), base.view(np.uint32))  # the oracle itself: copies never win
     for accel in (0, 1):
-        device.setOption(shim.PT_OPT_ACCEL, accel)
-        r = Renderer(device, big, mats, W, H, want_stats=True)
-        try:
-            r.render(frames)
-            got = r.read()
-            gst = r.read_stats()
-        finally:
-            r.release()
-            device.setOption(shim.PT_OPT_ACCEL, 0)
+        with options(device, ACCEL=accel):
+            got, gst = render(device, big, mats, W, H, frames, want_stats=True)
         assert_fb_equal(got, want, "tie scene, accel %d" % accel)
-        assert gst["rays"] == st["rays"]
+        assert gst[shim.PT_STAT_RAYS] == st["rays"]
 
 
 @pytest.mark.parametrize("depth", [1, 3, 40])
@@ -772,7 +523,7 @@ def test_depth_caps_outside_the_baseline_configs(device, cornell, oracle, depth)
     tris, mats = cornell
     W, H, frames = 64, 40, 4
     want = oracle.render(tris, mats, W, H, frames, max_bounces=depth)
-    got = _render_gpu(device, tris, mats, W, H, frames, depth=depth)
+    got = render(device, tris, mats, W, H, frames, depth=depth)
     assert_fb_equal(got.reshape(-1, 4), want, "depth %d" % depth)
 
 

@@ -7,85 +7,14 @@ import ctypes
 import numpy as np
 import pytest
 
+import camera_oracle
+import query_oracle as qo
 from conftest import assert_fb_equal
+from gpu_support import SEARCHES, assert_hits_equal, cornell_rays, options, refill_rays
+from oclpathtracer_amd import shim
+from scenes import horizon_tiles, soup_with_duplicates
 
 pytestmark = pytest.mark.gpu
-
-SEARCHES = [(q, a) for a in (1, 2) for q in (0, 1, 4)]   # (PT_OPT_QUAD_FILTER, PT_OPT_ACCEL)
-
-
-@pytest.fixture(scope="module")
-def qo():
-    import query_oracle
-
-    query_oracle.lib()
-    return query_oracle
-
-
-class _Options:
-    """Set device options for a block and restore what they were."""
-
-    def __init__(self, dev, **opts):
-        from oclpathtracer_amd import shim
-
-        self.dev, self.shim = dev, shim
-        self.opts = {getattr(shim, "PT_OPT_" + k): int(v) for k, v in opts.items()}
-
-    def __enter__(self):
-        lib = self.shim.load()
-        self.old = {k: lib.pt_device_get_option(self.dev._h, k) for k in self.opts}
-        for k, v in self.opts.items():
-            self.dev.setOption(k, v)
-        return self
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            self.dev.setOption(k, int(v))
-
-
-def _words(hits) -> np.ndarray:
-    """pt_hit records (HIT_DTYPE or [N, 12] float32) as float32 [N, 12]."""
-    h = np.asarray(hits)
-    return np.ascontiguousarray(h).view(np.float32).reshape(-1, 12)
-
-
-def assert_hits_equal(got, want, what=""):
-    """t, tri, u, v, p, material, n bit-exact (NaN masks equal), the reserved word ignored."""
-    g, w = _words(got), _words(want)
-    assert g.shape == w.shape, what
-    assert np.array_equal(g[:, 1].view(np.int32), w[:, 1].view(np.int32)), "%s: triangles differ at %s" % (
-        what, np.flatnonzero(g[:, 1].view(np.int32) != w[:, 1].view(np.int32))[:8])
-    assert_fb_equal(g[:, :11], w[:, :11], what)
-
-
-def _cornell_rays(rng, n, tris):
-    """Origins inside the box, on its surfaces and outside it; directions random, axis-aligned, with +-0 components, of
-    lengths 1e-3 .. 1e3."""
-    pts = np.concatenate([tris["p1"][:, :3], tris["p2"][:, :3], tris["p3"][:, :3]])
-    lo, hi = pts.min(0), pts.max(0)
-    k = n // 3
-    inside = rng.uniform(lo + 0.01, hi - 0.01, (k, 3))
-    t = rng.integers(0, len(tris), k)
-    a, b = rng.uniform(0, 1, (2, k, 1))
-    swap = a + b > 1
-    a, b = np.where(swap, 1 - a, a), np.where(swap, 1 - b, b)
-    on = tris["p1"][t, :3] + a * (tris["p2"][t, :3] - tris["p1"][t, :3]) + b * (tris["p3"][t, :3] - tris["p1"][t, :3])
-    outside = rng.uniform(lo - 6.0, hi + 6.0, (n - 2 * k, 3))
-    o = np.concatenate([inside, on, outside]).astype(np.float32)
-    d = rng.normal(size=(n, 3))
-    axis = rng.uniform(size=n) < 0.25                       # axis-aligned, signed zeros in the other components
-    ax = rng.integers(0, 3, n)
-    sgn = np.where(rng.uniform(size=n) < 0.5, -1.0, 1.0)
-    d[axis] = 0.0
-    d[axis, ax[axis]] = sgn[axis]
-    zero = rng.uniform(size=(n, 3)) < 0.1                   # +-0 components elsewhere
-    d[zero] = 0.0
-    d = d.astype(np.float32)
-    d[zero & (rng.uniform(size=(n, 3)) < 0.5)] = np.float32(-0.0)
-    d *= (10.0 ** rng.uniform(-3, 3, (n, 1))).astype(np.float32)
-    r = np.zeros((n, 8), np.float32)
-    r[:, :3], r[:, 3], r[:, 4:7] = o, np.float32(1e20), d
-    return r
 
 
 def _query_both(rc, rays, what):
@@ -99,30 +28,17 @@ def _query_both(rc, rays, what):
     return hits
 
 
-def _soup(n, seed):
-    from oclpathtracer_amd import scene
-
-    rng = np.random.default_rng(seed)
-    tris = np.zeros(n, scene.TRIANGLE_DTYPE)
-    c = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
-    for f in ("p1", "p2", "p3"):
-        tris[f][:, :3] = c + rng.normal(0, 0.15, (n, 3)).astype(np.float32)
-    tris["id"] = rng.integers(0, 7, n)
-    tris[n // 2: n // 2 + 40] = tris[10:50]                  # duplicates: the lower index wins a tie
-    return tris
-
-
 @pytest.mark.parametrize("quad,accel", SEARCHES)
-def test_cornell_random_rays_bit_exact(device, cornell, qo, quad, accel):
+def test_cornell_random_rays_bit_exact(device, cornell, quad, accel):
     from oclpathtracer_amd.query import RayCaster
 
     tris, _ = cornell
-    rays = _cornell_rays(np.random.default_rng(100 + quad + 10 * accel), 20480, tris)
+    rays = cornell_rays(np.random.default_rng(100 + quad + 10 * accel), 20480, tris)
     want = qo.closest(tris, rays)
     assert (want[:, 1].view(np.int32) >= 0).mean() > 0.3
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, QUAD_FILTER=quad, ACCEL=accel):
+        with options(device, QUAD_FILTER=quad, ACCEL=accel):
             got = _query_both(rc, rays, "cornell q%d a%d" % (quad, accel))
     finally:
         rc.release()
@@ -137,7 +53,7 @@ def test_closest_agrees_with_intersect_world(device, cornell, oracle):
     from oclpathtracer_amd.query import RayCaster
 
     tris, _ = cornell
-    rays = _cornell_rays(np.random.default_rng(7), 600, tris)
+    rays = cornell_rays(np.random.default_rng(7), 600, tris)
     rc = RayCaster(device, tris)
     try:
         got = rc.closest(rays)
@@ -152,10 +68,10 @@ def test_closest_agrees_with_intersect_world(device, cornell, oracle):
 
 
 @pytest.mark.parametrize("accel", [1, 2])
-def test_soup_and_duplicates_bit_exact(device, qo, accel):
+def test_soup_and_duplicates_bit_exact(device, accel):
     from oclpathtracer_amd.query import RayCaster
 
-    tris = _soup(3000, 11)
+    tris = soup_with_duplicates(3000, 11)
     rng = np.random.default_rng(12)
     n = 8192
     r = np.zeros((n, 8), np.float32)
@@ -169,7 +85,7 @@ def test_soup_and_duplicates_bit_exact(device, qo, accel):
     want = qo.closest(tris, r)
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=accel):
+        with options(device, ACCEL=accel):
             got = _query_both(rc, r, "soup a%d" % accel)
     finally:
         rc.release()
@@ -177,14 +93,13 @@ def test_soup_and_duplicates_bit_exact(device, qo, accel):
     assert not np.any((got["tri"] >= 1500) & (got["tri"] < 1540)), "a duplicate beat its lower-index original"
 
 
-def test_edge_on_coplanar_tiles_through_the_lbvh(device, qo):
-    from test_gpu_lbvh_robust import _horizon_tiles
+def test_edge_on_coplanar_tiles_through_the_lbvh(device):
     from oclpathtracer_amd.query import RayCaster
 
-    tris, _ = _horizon_tiles(0.003)
+    tris, _ = horizon_tiles(0.003)
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=2):
+        with options(device, ACCEL=2):
             cam = rc.camera_rays(96, 64, 3)
             rays = cam.view(np.float32).reshape(-1, 8).copy()
             rng = np.random.default_rng(3)
@@ -201,11 +116,11 @@ def test_edge_on_coplanar_tiles_through_the_lbvh(device, qo):
 
 
 @pytest.mark.parametrize("accel", [1, 2])
-def test_tmax_is_strict_and_clamped(device, cornell, qo, accel):
+def test_tmax_is_strict_and_clamped(device, cornell, accel):
     from oclpathtracer_amd.query import RayCaster
 
     tris, _ = cornell
-    base = _cornell_rays(np.random.default_rng(21), 4096, tris)
+    base = cornell_rays(np.random.default_rng(21), 4096, tris)
     want = qo.closest(tris, base)
     hit = want[:, 1].view(np.int32) >= 0
     b = base[hit]
@@ -221,7 +136,7 @@ def test_tmax_is_strict_and_clamped(device, cornell, qo, accel):
     rays = np.concatenate([at, above, special])
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=accel):
+        with options(device, ACCEL=accel):
             got = _query_both(rc, rays, "tmax a%d" % accel)
     finally:
         rc.release()
@@ -236,7 +151,7 @@ def test_tmax_is_strict_and_clamped(device, cornell, qo, accel):
 
 
 @pytest.mark.parametrize("accel", [1, 2])
-def test_non_finite_and_degenerate_rays(device, cornell, qo, accel):
+def test_non_finite_and_degenerate_rays(device, cornell, accel):
     from oclpathtracer_amd.query import RayCaster
 
     tris, _ = cornell
@@ -258,7 +173,7 @@ def test_non_finite_and_degenerate_rays(device, cornell, qo, accel):
     r[200:300, 4:7] = rng.normal(size=(100, 3)).astype(np.float32) * np.float32(1e25)   # |dir|^2 overflows
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=accel):
+        with options(device, ACCEL=accel):
             got = _query_both(rc, r, "non-finite a%d" % accel)
     finally:
         rc.release()
@@ -270,7 +185,7 @@ def test_empty_scene_and_zero_rays(device, cornell):
     from oclpathtracer_amd.query import RayCaster
 
     tris, _ = cornell
-    rays = _cornell_rays(np.random.default_rng(9), 512, tris)
+    rays = cornell_rays(np.random.default_rng(9), 512, tris)
     rc = RayCaster(device, np.zeros(0, scene.TRIANGLE_DTYPE))
     try:
         got = _query_both(rc, rays, "empty scene")
@@ -286,7 +201,7 @@ def test_empty_scene_and_zero_rays(device, cornell):
 
 
 def test_c_abi_argument_errors(device, cornell):
-    from oclpathtracer_amd import adl, scene, shim
+    from oclpathtracer_amd import adl, scene
 
     tris, _ = cornell
     lib = shim.load()
@@ -328,7 +243,7 @@ def _moved_cameras():
             Camera(eye=(0.3, 4.5, 2.0), center=(0.0, 0.5, -3.0), up=(0.0, 0.0, -1.0), fov_y_deg=30.0)]
 
 
-def test_camera_rays_are_the_renderers_primary_rays(device, cornell, oracle, qo):
+def test_camera_rays_are_the_renderers_primary_rays(device, cornell, oracle):
     from oclpathtracer_amd.query import RayCaster
 
     tris, mats = cornell
@@ -358,18 +273,16 @@ def test_camera_rays_are_the_renderers_primary_rays(device, cornell, oracle, qo)
         rc.release()
 
 
-def test_queries_interleaved_with_checkpointed_renders(device, cornell, oracle, qo):
-    import camera_oracle
-    from oclpathtracer_amd import shim
+def test_queries_interleaved_with_checkpointed_renders(device, cornell, oracle):
     from oclpathtracer_amd.camera import Camera
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = cornell
     W = H = 32
     lib = shim.load()
-    rays = _cornell_rays(np.random.default_rng(31), 4096, tris)
+    rays = cornell_rays(np.random.default_rng(31), 4096, tris)
     want = qo.closest(tris, rays)
-    with _Options(device, ACCEL=2, CHUNK_FRAMES=3):
+    with options(device, ACCEL=2, CHUNK_FRAMES=3):
         r = Renderer(device, tris, mats, W, H, want_stats=True)
         rc = r.ray_caster()
         try:
@@ -398,11 +311,10 @@ def test_queries_interleaved_with_checkpointed_renders(device, cornell, oracle, 
             r.release()
 
 
-def test_cut_short_search_is_reported_and_recovers(device, qo):
-    from oclpathtracer_amd import shim
+def test_cut_short_search_is_reported_and_recovers(device):
     from oclpathtracer_amd.query import RayCaster
 
-    tris = _soup(3000, 41)
+    tris = soup_with_duplicates(3000, 41)
     rng = np.random.default_rng(42)
     n = 4096
     r = np.zeros((n, 8), np.float32)
@@ -411,15 +323,12 @@ def test_cut_short_search_is_reported_and_recovers(device, qo):
     r[:, 4:7] = rng.normal(size=(n, 3))
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=2):
+        with options(device, ACCEL=2):
             rc.closest(r[:64])                       # scene prepared, hierarchy built
-            device.setOption(shim.PT_OPT_BVH_STACK_LIMIT, 1)
-            try:
+            with options(device, BVH_STACK_LIMIT=1):
                 with pytest.raises(shim.ShimError) as e:
                     rc.closest(r)
                 assert e.value.code == shim.PT_ERR_TRAVERSAL
-            finally:
-                device.setOption(shim.PT_OPT_BVH_STACK_LIMIT, 64)
             device.waitForCompletion()               # the word was cleared by the report
             assert_hits_equal(rc.closest(r), qo.closest(tris, r), "stack limit back at 64")
     finally:
@@ -431,7 +340,7 @@ def test_torch_tensors_in_and_out_without_host_sync(device, cornell):
     from oclpathtracer_amd import query
 
     tris, _ = cornell
-    rays = _cornell_rays(np.random.default_rng(51), 8192, tris)
+    rays = cornell_rays(np.random.default_rng(51), 8192, tris)
     rc = query.RayCaster(device, tris)
     try:
         want = rc.closest(rays)
@@ -457,7 +366,7 @@ def test_torch_tensors_in_and_out_without_host_sync(device, cornell):
         rc.release()
 
 
-def test_configs4_soup_lbvh_matches_brute_force(device, qo):
+def test_configs4_soup_lbvh_matches_brute_force(device):
     from oclpathtracer_amd import scene
     from oclpathtracer_amd.query import RayCaster
 
@@ -472,10 +381,10 @@ def test_configs4_soup_lbvh_matches_brute_force(device, qo):
     r[:, 4:7] = rng.normal(size=(n, 3))
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=2):
+        with options(device, ACCEL=2):
             bvh = rc.closest(r)
             bvh_occ = rc.occluded(r)
-        with _Options(device, ACCEL=1):
+        with options(device, ACCEL=1):
             brute = rc.closest(r)
     finally:
         rc.release()
@@ -485,44 +394,23 @@ def test_configs4_soup_lbvh_matches_brute_force(device, qo):
     assert_hits_equal(bvh[:256], qo.closest(tris, r[:256]), "LBVH vs oracle, 10^6 triangles")
 
 
-def _refill_rays(n, seed):
-    """n random rays through the 3 000-triangle soup, with long runs of rays that search nothing (tmax NaN, 0, -0, negative) and of
-    live ones after them, in every phase of a 64-ray group -- more rays than the LBVH query kernel's persistent grid holds lanes"""
-    rng = np.random.default_rng(seed)
-    r = np.zeros((n, 8), np.float32)
-    r[:, :3] = rng.uniform(-4, 4, (n, 3))
-    r[:, 3] = rng.uniform(0.5, 12.0, n)                          # mostly finite reach: hits and misses both
-    r[rng.uniform(size=n) < 0.3, 3] = 1e20
-    r[:, 4:7] = rng.normal(size=(n, 3))
-    dead = np.array([np.nan, 0.0, -0.0, -1.0, -np.inf], np.float32)
-    pos = 0
-    while pos < n:
-        pos += int(rng.integers(1, 4000))                        # a live stretch
-        run = int(rng.integers(1, 3000))                         # then a run of dead rays, often longer than a refill
-        r[pos: pos + run, 3] = dead[int(rng.integers(0, len(dead)))] if rng.uniform() < 0.7 else \
-            dead[rng.integers(0, len(dead), len(r[pos: pos + run]))]
-        pos += run
-    return r
-
-
-def test_lbvh_refill_over_more_rays_than_the_grid(device, qo):
+def test_lbvh_refill_over_more_rays_than_the_grid(device):
     """The LBVH query kernel's waves serve several groups of rays each (2^20 rays > the persistent grid's lanes) and refill lanes
     from later groups: every ray's result is its own, dead rays miss, and the LBVH agrees with the brute force and the oracle."""
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.query import RayCaster
 
-    tris = _soup(3000, 71)
+    tris = soup_with_duplicates(3000, 71)
     n = 1 << 20
     grid_lanes = shim.load().pt_device_num_cus(device._h) * 5 * 256
     assert n > 2 * grid_lanes, "the test must give every wave of the grid more than one group"
-    r = _refill_rays(n, 72)
+    r = refill_rays(n, 72)
     dead = ~(r[:, 3] > 0)
     assert dead.mean() > 0.2
     rc = RayCaster(device, tris)
     try:
-        with _Options(device, ACCEL=2):
+        with options(device, ACCEL=2):
             bvh = _query_both(rc, r, "refill a2")
-        with _Options(device, ACCEL=1):
+        with options(device, ACCEL=1):
             brute = _query_both(rc, r, "refill a1")
     finally:
         rc.release()
@@ -555,7 +443,7 @@ def test_torch_calls_neither_free_nor_wait(device, cornell):
     from oclpathtracer_amd import query
 
     tris, _ = cornell
-    rays = _cornell_rays(np.random.default_rng(81), 4096, tris)
+    rays = cornell_rays(np.random.default_rng(81), 4096, tris)
     rc = query.RayCaster(device, tris)
     try:
         want = rc.closest(rays)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, assert_fb_equal
+from gpu_support import render
 
 pytestmark = pytest.mark.gpu
 
@@ -349,7 +350,6 @@ def test_progressive_driver_matches_one_shot(device, cornell, oracle):
     arrive in order, never block the producer, and every one equals a one-shot render of its frames --
     the GPU's own AND the CPU oracle's (GenerateColors.cl:314-321 makes a pixel a function of its frames alone)."""
     from oclpathtracer_amd.progressive import ProgressiveRenderer
-    from oclpathtracer_amd.render import Renderer
 
     tris, mats = cornell
     W, H, per_step, steps = 96, 64, 5, 6
@@ -369,11 +369,6 @@ def test_progressive_driver_matches_one_shot(device, cornell, oracle):
         prog.release()
     assert len(snaps) >= 1 and all(f % per_step == 0 for f in snaps)
     for f, img in sorted(snaps.items()):
-        r = Renderer(device, tris, mats, W, H)
-        try:
-            r.render(f)
-            want = r.read()
-        finally:
-            r.release()
+        want = render(device, tris, mats, W, H, f)
         assert_fb_equal(img, want, "progressive snapshot at %d frames" % f)
         assert_fb_equal(img, oracle.render(tris, mats, W, H, f), "progressive snapshot at %d frames vs the oracle" % f)

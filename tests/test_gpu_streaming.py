@@ -11,39 +11,26 @@ import numpy as np
 import pytest
 
 from conftest import assert_fb_equal
+from gpu_support import options, render
+from oclpathtracer_amd import shim
 
 pytestmark = pytest.mark.gpu
 
 MIB = 1 << 20
 
 
-def _render(device, tris, mats, W, H, frames, *, depth=16, begin=0, **opts):
-    """One render through the fused entry point with the given device options; returns (pixels, raw stats)."""
-    from oclpathtracer_amd import shim
-    from oclpathtracer_amd.render import Renderer
+_OPTIONS = {"lanes": "RENDER_LANES", "checkpoint": "CHECKPOINT", "chunk": "CHUNK_FRAMES"}
 
-    names = {"lanes": shim.PT_OPT_RENDER_LANES, "checkpoint": shim.PT_OPT_CHECKPOINT, "chunk": shim.PT_OPT_CHUNK_FRAMES}
-    defaults = {"lanes": 2, "checkpoint": 1, "chunk": 0}
-    for k, v in opts.items():
-        device.setOption(names[k], v)
-    try:
-        r = Renderer(device, tris, mats, W, H, want_stats=True)
-        if begin:
-            r.render(begin, frame_begin=0, max_bounces=depth)
-        r.render(frames, frame_begin=begin, max_bounces=depth)
-        got, st = r.read(), r.read_stats_raw()
-        r.release()
-    finally:
-        for k in opts:
-            device.setOption(names[k], defaults[k])
-    return got, st
+
+def _render(device, tris, mats, W, H, frames, **opts):
+    """One render through the fused entry point with the given device options; returns (pixels, raw stats)."""
+    with options(device, **{_OPTIONS[k]: v for k, v in opts.items()}):
+        return render(device, tris, mats, W, H, frames, want_stats=True)
 
 
 def test_chunking_checkpoints_and_lanes_never_change_a_pixel(device, cornell, oracle):
     """The same 23 frames as ONE launch, as 2-, 3- and 7-frame chunks, with and without checkpoints, on one lane and on two: bit for
     bit the oracle's image, the same ray count -- and the checkpointed runs really did hand paths from launch to launch."""
-    from oclpathtracer_amd import shim
-
     tris, mats = cornell
     W, H, frames = 96, 64, 23
     want, ost = oracle.render(tris, mats, W, H, frames, want_stats=True)
@@ -71,10 +58,19 @@ def test_checkpoints_on_a_launch_with_fewer_batches_than_waves(device, cornell, 
 
 def test_resumed_renders_across_chunk_boundaries(device, cornell, oracle):
     """frame_begin > 0 (GenerateColors.cl:318-320 resumes from the framebuffer) with chunks that do not divide the call."""
+    from oclpathtracer_amd.render import Renderer
+
     tris, mats = cornell
     W, H = 64, 48
     want = oracle.render(tris, mats, W, H, 5 + 17)
-    got, _ = _render(device, tris, mats, W, H, 17, begin=5, chunk=4)
+    with options(device, CHUNK_FRAMES=4):
+        r = Renderer(device, tris, mats, W, H, want_stats=True)
+        try:
+            r.render(5, frame_begin=0)          # no wait in between: the second call starts behind the first one's draining launch
+            r.render(17, frame_begin=5)
+            got = r.read()
+        finally:
+            r.release()
     assert_fb_equal(got, want, "5 frames, then 17 more in chunks of 4")
 
 
@@ -213,8 +209,6 @@ def test_events_complete_with_the_render_and_hand_over_to_other_streams(device, 
 
 def test_option_3_of_abi_version_1_is_still_accepted(device):
     """option id 3 (a kernel-variant switch) was removed without a version bump; version 2 takes its two values again."""
-    from oclpathtracer_amd import shim
-
     lib = shim.load()
     assert lib.pt_abi_version() == 2
     assert lib.pt_device_set_option(device._h, 3, 0) == shim.PT_OK and lib.pt_device_set_option(device._h, 3, 1) == shim.PT_OK
@@ -224,7 +218,6 @@ def test_option_3_of_abi_version_1_is_still_accepted(device):
 
 
 def test_profile_union_counts_overlapped_launches_once(device, cornell):
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = cornell
@@ -263,7 +256,6 @@ def test_a_callers_stream_keeps_plain_stream_order(device, cornell, oracle):
     the framebuffer's neighbour does not start before it (the lanes fork behind the stream and the stream joins them, every render)."""
     import torch
 
-    from oclpathtracer_amd import shim
     from oclpathtracer_amd.render import Renderer
 
     tris, mats = cornell

@@ -7,7 +7,7 @@ single rounding decides a hit, and only parity between device and oracle is asse
 import numpy as np
 import pytest
 
-import lbvh_scenes as S
+import scenes as S
 
 
 @pytest.fixture(scope="module")

@@ -1,17 +1,17 @@
 #!/usr/bin/env python3
-"""Randomised parity campaign on the GPU box: random quad scenes (the generator of tests/test_gpu_parity.py), random image
+"""Randomised parity campaign on the GPU box: random quad scenes (tests/scenes.py's random_quads), random image
 geometries, frame counts, depth caps, stripe splits, search modes and options -- every render compared bit for bit
 (NaN masks equal) with the CPU oracle, ray counts included.  usage: python tools/gpu_fuzz.py [first_seed] [count]"""
-import importlib.util, os, sys, time
+import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 from oclpathtracer_amd import adl, scene, shim
 from oclpathtracer_amd.render import Renderer
 from oracle import ptoracle
+import scenes
+from conftest import assert_fb_equal
 
-spec = importlib.util.spec_from_file_location("tgp", os.path.join(ROOT, "tests", "test_gpu_parity.py"))
-tgp = importlib.util.module_from_spec(spec); spec.loader.exec_module(tgp)
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 5000
 count = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 ptoracle.build()
@@ -26,7 +26,7 @@ for seed in range(first, first + count):
     if kind == 0:
         tris, mats = cornell
     elif kind == 1:
-        tris, mats = tgp._random_quad_scene(seed)
+        tris, mats = scenes.random_quads(seed)
     elif kind == 2:   # nested Cornell copies: 72 ... 468 triangles (chunks, tiled mode)
         parts = []
         for c in range(int(rng.integers(2, 14))):
@@ -58,7 +58,7 @@ for seed in range(first, first + count):
         rays += st["rays"]
     want = fb.reshape(H, W, 4)[rows].reshape(-1, 4) if len(rows) else np.zeros((0, 4), np.float32)
     try:
-        tgp.assert_fb_equal(got, want, "seed %d" % seed)
+        assert_fb_equal(got, want, "seed %d" % seed)
         assert gst["rays"] == rays, (gst["rays"], rays)
     except AssertionError as e:
         bad += 1
