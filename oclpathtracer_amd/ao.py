@@ -47,40 +47,17 @@ class AORenderer:
         if self.local_rows < 0:
             raise ValueError("invalid stripe geometry")
         self.local_pixels = self.local_rows * self.width
-        self.camera, self._cam = None, None
         self._set_camera(camera)
-        self._own_tbuf = not isinstance(triangles, adl.Buffer)
         self.tbuf = self.counts = self.image = None
-        if self._own_tbuf:
-            tris = np.ascontiguousarray(triangles)
-            if tris.dtype != scene.TRIANGLE_DTYPE:
-                raise TypeError("triangles must be a scene.TRIANGLE_DTYPE array or an adl.Buffer")
-            self.num_triangles = len(tris)
-        else:
-            if num_triangles is None:
-                raise ValueError("num_triangles is required with an adl.Buffer of triangles")
-            self.num_triangles = int(num_triangles)
-        if self.num_triangles < 0:
-            raise ValueError("num_triangles < 0")
-        if self._own_tbuf:
-            self.tbuf = adl.Buffer(dev, max(len(tris), 1), scene.TRIANGLE_DTYPE)
-            if len(tris):
-                self.tbuf.write(tris, len(tris))
-        else:
-            self.tbuf = triangles
+        self.tbuf, self.num_triangles, self._own_tbuf = scene.triangle_buffer(dev, triangles, num_triangles)
         n = max(self.local_pixels, 1)
         self.counts = adl.Buffer(dev, 2 * n, np.uint32)
         self.image = adl.Buffer(dev, n, adl.float4)
         self.frames_done = 0
 
     def _set_camera(self, camera: Optional[Camera]) -> None:
-        if camera is not None and not isinstance(camera, Camera):
-            raise TypeError("camera must be an oclpathtracer_amd.camera.Camera or None")
-        cam = camera.to_struct() if camera is not None else None
-        if cam is not None:
-            out = (ctypes.c_float * 16)()
-            shim.check(self._lib.pt_camera_derive(ctypes.byref(cam), out))   # rejected here, before anything is enqueued
-        self.camera, self._cam = camera, cam
+        self._cam = Camera.struct_of(camera)   # rejected here, before anything is enqueued
+        self.camera = camera
 
     def set_camera(self, camera: Optional[Camera]) -> None:
         """AO from ``camera`` from now on (None: the reference's); the next render starts again at frame 0."""

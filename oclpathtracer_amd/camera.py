@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import math
 from dataclasses import dataclass
-from typing import Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -72,6 +72,18 @@ class Camera:
         half = min(half_v, math.atan(math.tan(half_v) * aspect))   # the narrower of the two half-angles
         dist = margin * radius / math.sin(half)
         return cls(tuple(c - dist * v), tuple(c), tuple(up), fov_y_deg)
+
+    @classmethod
+    def struct_of(cls, camera: Optional["Camera"]) -> Optional[shim.Camera]:
+        """What every entry point that takes a camera hands to the library: None (the reference's camera) for None, else the
+        ``pt_camera`` struct of a :class:`Camera`, derived once here so that a bad one is rejected before anything is enqueued."""
+        if camera is None:
+            return None
+        if not isinstance(camera, cls):
+            raise TypeError("camera must be an oclpathtracer_amd.camera.Camera or None")
+        s = camera.to_struct()
+        shim.check(shim.load().pt_camera_derive(ctypes.byref(s), (ctypes.c_float * 16)()))
+        return s
 
     def to_struct(self) -> shim.Camera:
         s = shim.Camera()

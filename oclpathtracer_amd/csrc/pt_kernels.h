@@ -193,17 +193,23 @@ hipError_t ptk_prep_quad_margins(PtPrepTriangle* out, int ntri, float diameter, 
 static inline size_t ptk_p1tab_floats(int ntri) { return (size_t)((ntri / 2 + 1) / 2) * PT_P1_STRIDE; }
 // fills p.pmask (when not null) for the image geometry and the camera of p; needs p.p1tab (quad mode 3) made about p.cam.eye
 hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s);
-// det_bounded: every triangle satisfies |e1|_1*|e2|_1 <= PT_DET_BOUND_MAX (short exact reciprocal valid)
-// quads: 0 = independent triangles (pt_tri_pass1); 3 = ntri is even, every pair (2k, 2k+1) is a quad
-//        (a,b,c),(c,d,a), the margins and the packed table p.p1tab are prepared (pt_quad3_pass1)
-// bvh: traverse p.bvh instead of the brute-force two-pass search; then `quads` is about the table of the big triangles kept out
-//      of the hierarchy (p.bigtab: 3 = made of quads, p.p1tab / p1_lo / p1_hi / quad_delta1 / ray_radius prepared for IT)
+// which search a launch runs (pt_shim.hip: prepare_search decides it, once, for renders, queries and ambient occlusion alike)
+struct PtSearchMode {
+    // traverse p.bvh instead of the brute-force two-pass search; then `quads` is about the table of the big triangles kept out
+    // of the hierarchy (p.bigtab: 3 = made of quads, p.p1tab / p1_lo / p1_hi / quad_delta1 / ray_radius prepared for IT)
+    bool bvh;
+    // every triangle satisfies |e1|_1*|e2|_1 <= PT_DET_BOUND_MAX (short exact reciprocal valid)
+    bool det_bounded;
+    // 0 = independent triangles (pt_tri_pass1); 3 = ntri is even, every pair (2k, 2k+1) is a quad (a,b,c),(c,d,a), the margins
+    // and the packed table p.p1tab are prepared (pt_quad3_pass1)
+    int quads;
+};
 // tally: (bvh only) the measurement variant that adds the search's work counters to p.stats[2..5]
 // wide: (bvh only) the slabs carry the ray term of the margin, PT_BVH_RAY_EPS x the origin's largest |coordinate|.  Every path starts at
 //       the eye and goes on from points of the scene, so the host leaves the term out (the kernels of before, instruction for instruction)
 //       when the eye's largest |coordinate| is at most PT_BVH_NEAR_EYE x the scene's: there the term is below a third of eps and the
 //       measured excess below 0.01 eps (pt_bvh.hip's table, D / m <= 10).  Queries and AO take rays from anywhere and always carry it.
-hipError_t ptk_trace(const PtTraceParams& p, int num_blocks, bool det_bounded, int quads, bool bvh, bool tally, bool wide, hipStream_t s);
+hipError_t ptk_trace(const PtTraceParams& p, int num_blocks, PtSearchMode m, bool tally, bool wide, hipStream_t s);
 #define PT_BVH_NEAR_EYE 4.0f
 // out[k] = raw[bigidx[k]], k < nbig <= PT_BVH_BIG_MAX
 hipError_t ptk_bvh_big_raw(const PtRawTriangle* raw, const int* bigidx, int nbig, PtRawTriangle* out, hipStream_t s);
@@ -245,7 +251,7 @@ struct PtQueryParams {
 // bvh_blocks: the persistent grid of the LBVH kernel (CUs x ptk_query_bvh_blocks_per_cu: the driver's kernels -- closest, any-hit, AO -- are all
 // pinned to five waves per SIMD and use the trace kernel's LDS, so one figure, the closest kernel's, sizes every such grid)
 // any: (bvh and q.occluded only) pt_occluded_rays: an any-hit search, which stops at the first accepted triangle
-hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, bool bvh, bool any, hipStream_t s);
+hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, PtSearchMode m, bool any, hipStream_t s);
 int ptk_query_bvh_blocks_per_cu(void);
 // ambient occlusion (pt_render_ao): t carries the search as PtQueryParams::t does (the filter's anchor in t.cam.eye) and the image
 // geometry (width, inv_width, inv_height, aspect, stripe_rows, n_ranks, rank); cam is the camera
@@ -259,7 +265,7 @@ struct PtAoParams {
     int32_t K;                    // occlusion rays per hit
     float tlim;                   // min(radius, 1e20)
 };
-hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s);
+hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s);
 // image[i] = float4(a, a, a, 1) of counts[i] = {open, hits}: a = open / (K hits), miss_value when hits = 0
 hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s);
 // rays[2 gid], rays[2 gid + 1] = the pt_ray of pixel gid, frame `frame` (the renderer's sample start) for the camera cam

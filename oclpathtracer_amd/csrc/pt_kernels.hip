@@ -2883,22 +2883,22 @@ hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t ptk_trace(const PtTraceParams& p, int num_blocks, bool det_bounded, int quads, bool bvh, bool tally, bool wide, hipStream_t s)
+hipError_t ptk_trace(const PtTraceParams& p, int num_blocks, PtSearchMode m, bool tally, bool wide, hipStream_t s)
 {
     // (the order the instantiations appear in is the order of the kernels in the code object)
-    const bool q3 = quads == 3;
+    const bool q3 = m.quads == 3;
     void (*kernel)(const PtTraceParams);
-    if (bvh && wide)
-        kernel = tally ? (det_bounded ? (q3 ? pt_trace_bvh_kernel<true, true, 3, true> : pt_trace_bvh_kernel<true, true, 0, true>) : pt_trace_bvh_kernel<false, true, 0, true>)
-                       : (det_bounded ? (q3 ? pt_trace_bvh_kernel<true, false, 3, true> : pt_trace_bvh_kernel<true, false, 0, true>) : pt_trace_bvh_kernel<false, false, 0, true>);
-    else if (bvh)
-        kernel = tally ? (det_bounded ? (q3 ? pt_trace_bvh_kernel<true, true, 3> : pt_trace_bvh_kernel<true, true, 0>) : pt_trace_bvh_kernel<false, true, 0>)
-                       : (det_bounded ? (q3 ? pt_trace_bvh_kernel<true, false, 3> : pt_trace_bvh_kernel<true, false, 0>) : pt_trace_bvh_kernel<false, false, 0>);
+    if (m.bvh && wide)
+        kernel = tally ? (m.det_bounded ? (q3 ? pt_trace_bvh_kernel<true, true, 3, true> : pt_trace_bvh_kernel<true, true, 0, true>) : pt_trace_bvh_kernel<false, true, 0, true>)
+                       : (m.det_bounded ? (q3 ? pt_trace_bvh_kernel<true, false, 3, true> : pt_trace_bvh_kernel<true, false, 0, true>) : pt_trace_bvh_kernel<false, false, 0, true>);
+    else if (m.bvh)
+        kernel = tally ? (m.det_bounded ? (q3 ? pt_trace_bvh_kernel<true, true, 3> : pt_trace_bvh_kernel<true, true, 0>) : pt_trace_bvh_kernel<false, true, 0>)
+                       : (m.det_bounded ? (q3 ? pt_trace_bvh_kernel<true, false, 3> : pt_trace_bvh_kernel<true, false, 0>) : pt_trace_bvh_kernel<false, false, 0>);
     else if (p.ntri <= PT_LDS_TRI_MAX)
-        kernel = det_bounded ? (q3 ? pt_trace_kernel<true, 1, 3> : pt_trace_kernel<true, 1, 0>) : pt_trace_kernel<false, 1, 0>;
+        kernel = m.det_bounded ? (q3 ? pt_trace_kernel<true, 1, 3> : pt_trace_kernel<true, 1, 0>) : pt_trace_kernel<false, 1, 0>;
     else
-        kernel = det_bounded ? pt_trace_tiled_kernel<true> : pt_trace_tiled_kernel<false>;
-    const size_t lds = bvh ? ptk_trace_bvh_lds_bytes() : ptk_trace_lds_bytes(p.ntri);
+        kernel = m.det_bounded ? pt_trace_tiled_kernel<true> : pt_trace_tiled_kernel<false>;
+    const size_t lds = m.bvh ? ptk_trace_bvh_lds_bytes() : ptk_trace_lds_bytes(p.ntri);
     hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3(PT_TRACE_THREADS), lds, s, p);
     return hipGetLastError();
 }
@@ -2999,27 +2999,27 @@ static hipError_t pt_launch_search(void (*kernel)(const Params), const Params& p
     return hipGetLastError();
 }
 
-hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, bool det_bounded, int quads, bool bvh, bool any, hipStream_t s)
+hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, PtSearchMode m, bool any, hipStream_t s)
 {
     if (q.nrays == 0) return hipSuccess;
-    const bool q3 = quads == 3;
+    const bool q3 = m.quads == 3;
     void (*kernel)(const PtQueryParams);
-    if (bvh && any) kernel = pt_pick(det_bounded, q3, pt_query_bvh_kernel<true, 3, true>, pt_query_bvh_kernel<true, 0, true>, pt_query_bvh_kernel<false, 0, true>);
-    else if (bvh) kernel = pt_pick(det_bounded, q3, pt_query_bvh_kernel<true, 3, false>, pt_query_bvh_kernel<true, 0, false>, pt_query_bvh_kernel<false, 0, false>);
-    else if (q.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(det_bounded, q3, pt_query_kernel<true, 1, 3>, pt_query_kernel<true, 1, 0>, pt_query_kernel<false, 1, 0>);
-    else kernel = det_bounded ? pt_query_kernel<true, 2, 0> : pt_query_kernel<false, 2, 0>;
-    return pt_launch_search(kernel, q, q.nrays, bvh, bvh_blocks, s);
+    if (m.bvh && any) kernel = pt_pick(m.det_bounded, q3, pt_query_bvh_kernel<true, 3, true>, pt_query_bvh_kernel<true, 0, true>, pt_query_bvh_kernel<false, 0, true>);
+    else if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_query_bvh_kernel<true, 3, false>, pt_query_bvh_kernel<true, 0, false>, pt_query_bvh_kernel<false, 0, false>);
+    else if (q.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_query_kernel<true, 1, 3>, pt_query_kernel<true, 1, 0>, pt_query_kernel<false, 1, 0>);
+    else kernel = m.det_bounded ? pt_query_kernel<true, 2, 0> : pt_query_kernel<false, 2, 0>;
+    return pt_launch_search(kernel, q, q.nrays, m.bvh, bvh_blocks, s);
 }
 
-hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, bool det_bounded, int quads, bool bvh, hipStream_t s)
+hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
 {
     if (a.nitems == 0) return hipSuccess;
-    const bool q3 = quads == 3;
+    const bool q3 = m.quads == 3;
     void (*kernel)(const PtAoParams);
-    if (bvh) kernel = pt_pick(det_bounded, q3, pt_ao_bvh_kernel<true, 3>, pt_ao_bvh_kernel<true, 0>, pt_ao_bvh_kernel<false, 0>);
-    else if (a.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(det_bounded, q3, pt_ao_kernel<true, 1, 3>, pt_ao_kernel<true, 1, 0>, pt_ao_kernel<false, 1, 0>);
-    else kernel = det_bounded ? pt_ao_kernel<true, 2, 0> : pt_ao_kernel<false, 2, 0>;
-    return pt_launch_search(kernel, a, a.nitems, bvh, bvh_blocks, s);
+    if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_ao_bvh_kernel<true, 3>, pt_ao_bvh_kernel<true, 0>, pt_ao_bvh_kernel<false, 0>);
+    else if (a.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_ao_kernel<true, 1, 3>, pt_ao_kernel<true, 1, 0>, pt_ao_kernel<false, 1, 0>);
+    else kernel = m.det_bounded ? pt_ao_kernel<true, 2, 0> : pt_ao_kernel<false, 2, 0>;
+    return pt_launch_search(kernel, a, a.nitems, m.bvh, bvh_blocks, s);
 }
 
 hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s)

@@ -83,12 +83,19 @@ struct PendingFrames {  // deferred GenerateColors launches (PT_OPT_BATCH_FRAMES
     uint32_t pixel_count;
 };
 
+// a device allocation the handle holds for itself, with its size (ws_malloc, ws_free): what pt_device_workspace_memory adds up
+template <class T> struct PtWs {
+    T* p;
+    size_t bytes;
+    operator T*() const { return p; }
+};
+
 // the pass-1 filter of one triangle table (pt_quad3_pass1): the brute-force scene's or the LBVH's table of big triangles
 struct PtFilterTable {
     bool pairs;                 // every (2k, 2k+1) is a quad (a,b,c),(c,d,a), det-bounded: mode 3 if the radius allows
     int quads;                  // 0: independent triangles; 3: pairs, finite radius, margins and the packed table prepared
     float anchor[3]; bool anchor_valid;   // the eye the margins and the packed table were made about (ensure_anchor), since the table was last prepared
-    float* p1tab;               // the packed table
+    PtWs<float> p1tab;          // the packed table
     float delta1, ray_radius, p1_lo, p1_hi;   // the filter's bounds: quad modes 2, 3 (pt_quad2_pass1, pt_quad3_pass1)
 };
 
@@ -99,10 +106,12 @@ struct pt_device_s {
     bool external;           // `stream` is the caller's (pt_device_set_stream)
     uint64_t used, peak;
     int live_buffers;
+    uint64_t workspace;      // device bytes held by this handle for itself (every PtWs below)
     int64_t opt_batch, opt_chunk, opt_profile, opt_quads, opt_accel, opt_tally, opt_pmask, opt_bvh_stack, opt_lanes, opt_carry;
     pt_kernel_s kernels[KERNEL_COUNT];
-    // prepared-scene cache
-    PtPrepTriangle* prep;
+    PendingFrames pending;
+    // ---- the prepared scene, its filter tables and its LBVH (ensure_prep, ensure_bvh, ensure_anchor, prepare_search)
+    PtWs<PtPrepTriangle> prep;
     size_t prep_capacity;  // triangles
     const pt_buffer_s* prep_src;
     uint64_t prep_version;
@@ -110,24 +119,27 @@ struct pt_device_s {
     uint64_t prep_hash;         // checksum of the raw records the prepared scene was made from (pt_prep_kernel)
     bool prep_hash_valid;
     uint64_t scene_gen;         // bumped whenever the prepared scene's CONTENTS changed
-    uint64_t bvh_builds;        // LBVH builds so far (PT_OPT_BVH_BUILD_COUNT)
     bool prep_det_bounded;      // scene extent allows the short exact reciprocal
     bool prep_finite;           // every vertex coordinate of the prepared scene is finite ...
     float prep_lo[3], prep_hi[3];  // ... and these are their per-axis extremes: the radius about any eye (anchor_radius)
+    PtWs<unsigned int> det_bound_dev;  // PT_PREP_WORDS device words written by the prep kernel
+    int blocks_per_cu;          // the table trace kernels' resident workgroups: follows the LDS footprint of the last scene that had triangles
     PtFilterTable scene_filter;    // the prepared scene's (p1tab sized with prep)
     PtFilterTable big_filter;      // the LBVH's table of big triangles (p1tab: ws_big_p1tab, the big triangles' raw records behind it)
-    PtBvh8Node* bvh;             // LBVH of the prepared scene (built on demand: ensure_bvh): its 64-byte records, sized with prep
+    PtWs<PtBvh8Node> bvh;        // LBVH of the prepared scene (built on demand: ensure_bvh): its 64-byte records, sized with prep
     PtBvhGrid bvh_grid;         // the grid of its nodes' origins
     size_t bvh_records;         // records in use (nodes + leaves)
-    PtPrepTriangle* bigtab;     // the triangles kept out of the hierarchy (PT_BVH_BIG_MAX records + indices + count)
-    int* bigidx;
+    PtWs<PtPrepTriangle> bigtab;   // the triangles kept out of the hierarchy (PT_BVH_BIG_MAX records + indices + count)
+    PtWs<int> bigidx;
     int nbig;
+    bool bvh_valid;
+    uint64_t bvh_builds;        // LBVH builds so far (PT_OPT_BVH_BUILD_COUNT)
     int bvh_blocks_per_cu;
     int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query and ambient-occlusion kernels (pt_bvh_drive)
-    bool bvh_valid;
-    unsigned int* det_bound_dev;  // PT_PREP_WORDS device words written by the prep kernel
-    // fused-render workspace: the STREAMING renderer.  A render walks its frames in chunks of S frames (as many as a ring slot
-    // holds) through a ring of two radiance slots; chunk number seq (a running number over all renders of the handle) uses slot
+    unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
+    unsigned int* trav_dev;  // ... as the device addresses it
+    // ---- fused-render workspace: the STREAMING renderer (render_part, plan_chunks, the ring).  A render walks its frames in chunks of
+    // S frames (as many as a ring slot holds) through a ring of two radiance slots; chunk number seq (a running number over all renders of the handle) uses slot
     // seq % 2.  All launches of ONE render go to one lane, in order:
     //     T(0)  T(1) F(0)  T(2) F(1)  ...  T(n-1) F(n-2)  D  F(n-1)
     // T(c) = trace launch of chunk c, CHECKPOINTED (PtTraceParams::carry): it ends the moment its queue has handed out the last
@@ -140,7 +152,7 @@ struct pt_device_s {
     // Consecutive renders ALTERNATE between the two lanes: render k+1's T(0) needs the slot that F(n-2) of render k released, not
     // the one F(n-1) is still to read, so it fills the machine while D of render k runs dry.  The folds of all chunks of all renders
     // form ONE chain (events): every pixel folds its frames in ascending order (GenerateColors.cl:314-321).
-    float* ring;             // PT_RING_SLOTS x ring_slot_bytes: 12 bytes per (frame, pixel) of a chunk
+    PtWs<float> ring;        // PT_RING_SLOTS x ring_slot_bytes: 12 bytes per (frame, pixel) of a chunk
     size_t ring_slot_bytes;
     hipStream_t lane[2];
     hipEvent_t ev_fork;      // recorded on `stream`: what the lanes must wait for before a render's first launches
@@ -152,21 +164,14 @@ struct pt_device_s {
     bool lanes_busy;         // lane work is enqueued that `stream` has not been ordered behind
     bool main_dirty;         // work has been enqueued on `stream` that the lanes have not been ordered behind
     uint64_t chunk_seq, render_seq;
-    uint32_t* carry[2];      // per lane: the checkpoint regions of its renders' trace launches (PT_CARRY_STRIDE_DW dwords per wave)
-    size_t carry_waves;      // waves each of them holds
-    uint2* pmask;            // primary-ray candidate masks of the local pixels (pt_primary_mask_kernel)
-    size_t pmask_pixels;
+    PtWs<uint32_t> carry[2]; // per lane: the checkpoint regions of its renders' trace launches (PT_CARRY_STRIDE_DW dwords per wave)
+    PtWs<uint2> pmask;       // primary-ray candidate masks of the local pixels (pt_primary_mask_kernel), for as many pixels as it holds
     struct { uint64_t scene_gen; int32_t g[7]; PtCamera cam; bool valid; } pmask_key;  // what the masks in hand were made for
-    unsigned int* counters;  // PT_QUEUE_COUNTERS work-queue counters, PT_QUEUE_STRIDE words apart: zero between launches
+    PtWs<unsigned int> counters;  // PT_QUEUE_COUNTERS work-queue counters, PT_QUEUE_STRIDE words apart: zero between launches
     bool counters_dirty;     // a failed call may have left one non-zero
-    unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
-    unsigned int* trav_dev;  // ... as the device addresses it
-    uint64_t workspace;      // device bytes held by this handle for itself
-    int blocks_per_cu;
-    PendingFrames pending;
-    // per-kernel timing (pt_profile_*)
+    // ---- per-kernel timing (pt_profile_*)
     bool prof_on;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>>* prof_pairs;  // [PT_PROF_KINDS]
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pairs[PT_PROF_KINDS];
     size_t prof_used[PT_PROF_KINDS];
 };
 
@@ -204,22 +209,21 @@ static int prof_end(hipStream_t st, hipEvent_t stop)
 
 static int g_init_count = 0;
 
-// device memory the handle holds for itself (pt_device_workspace_memory)
-static hipError_t ws_malloc(pt_device_s* d, void** p, size_t bytes)
+// device memory the handle holds for itself (pt_device_workspace_memory): an allocation carries its size from ws_malloc to ws_free
+template <class T> static hipError_t ws_malloc(pt_device_s* d, PtWs<T>& w, size_t bytes)
 {
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) d->workspace += bytes;
-    else { *p = nullptr; (void)hipGetLastError(); }
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&w.p), bytes);
+    if (e == hipSuccess) { w.bytes = bytes; d->workspace += bytes; }
+    else { w = {}; (void)hipGetLastError(); }
     return e;
 }
-template <class T> static hipError_t ws_malloc(pt_device_s* d, T** p, size_t bytes) { return ws_malloc(d, reinterpret_cast<void**>(p), bytes); }
 
-template <class T> static void ws_free(pt_device_s* d, T*& p, size_t bytes)
+template <class T> static void ws_free(pt_device_s* d, PtWs<T>& w)
 {
-    if (!p) return;
-    hipFree(p);
-    p = nullptr;
-    d->workspace -= bytes;
+    if (!w.p) return;
+    hipFree(w.p);
+    d->workspace -= w.bytes;
+    w = {};
 }
 
 static const size_t WS_BIGTAB = PT_BVH_BIG_MAX * sizeof(PtPrepTriangle);
@@ -263,29 +267,26 @@ extern "C" int pt_device_count(void)
 // everything a device handle owns (also the unwinding path of a pt_device_create that failed half-way)
 static void destroy_device_objects(pt_device_s* d)
 {
-    ws_free(d, d->prep, d->prep_capacity * sizeof(PtPrepTriangle));
-    ws_free(d, d->scene_filter.p1tab, ptk_p1tab_floats((int)d->prep_capacity) * sizeof(float));
-    ws_free(d, d->bvh, ptk_bvh_record_count((int)d->prep_capacity) * sizeof(PtBvh8Node));
-    ws_free(d, d->ring, PT_RING_SLOTS * d->ring_slot_bytes);
-    ws_free(d, d->pmask, d->pmask_pixels * sizeof(uint2));
-    ws_free(d, d->counters, WS_COUNTERS);
-    ws_free(d, d->bigtab, WS_BIGTAB);
-    ws_free(d, d->bigidx, WS_BIGIDX);
-    ws_free(d, d->big_filter.p1tab, ws_big_p1tab());
-    ws_free(d, d->det_bound_dev, WS_DETBOUND);
+    ws_free(d, d->prep);
+    ws_free(d, d->scene_filter.p1tab);
+    ws_free(d, d->bvh);
+    ws_free(d, d->ring);
+    ws_free(d, d->pmask);
+    ws_free(d, d->counters);
+    ws_free(d, d->bigtab);
+    ws_free(d, d->bigidx);
+    ws_free(d, d->big_filter.p1tab);
+    ws_free(d, d->det_bound_dev);
     if (d->trav_host) hipHostFree(d->trav_host);
-    if (d->prof_pairs) {
-        for (int k = 0; k < PT_PROF_KINDS; ++k)
-            for (auto& pr : d->prof_pairs[k]) {
-                hipEventDestroy(pr.first);
-                hipEventDestroy(pr.second);
-            }
-        delete[] d->prof_pairs;
-    }
+    for (auto& v : d->prof_pairs)
+        for (auto& pr : v) {
+            hipEventDestroy(pr.first);
+            hipEventDestroy(pr.second);
+        }
     for (int k = 0; k < 2; ++k) {
         if (d->ev_fold[k]) hipEventDestroy(d->ev_fold[k]);
         if (d->ev_slot[k]) hipEventDestroy(d->ev_slot[k]);
-        ws_free(d, d->carry[k], d->carry_waves * PT_CARRY_STRIDE_DW * sizeof(uint32_t));
+        ws_free(d, d->carry[k]);
         if (d->lane[k]) hipStreamDestroy(d->lane[k]);
     }
     if (d->ev_fork) hipEventDestroy(d->ev_fork);
@@ -302,9 +303,8 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0) return fail(PT_ERR_NO_DEVICE, "no HIP device visible (%s)", hipGetErrorString(e));
     if (device_idx < 0 || device_idx >= n) return fail(PT_ERR_NO_DEVICE, "device index %d out of range [0,%d)", device_idx, n);
-    pt_device_s* d = new (std::nothrow) pt_device_s();
+    pt_device_s* d = new (std::nothrow) pt_device_s();   // value-initialised: every field zero, the profile pairs empty
     if (!d) return fail(PT_ERR_OOM, "host allocation failed");
-    memset(static_cast<void*>(d), 0, sizeof *d);
     d->idx = device_idx;
     if (hipSetDevice(device_idx) != hipSuccess || hipGetDeviceProperties(&d->prop, device_idx) != hipSuccess) {
         delete d;
@@ -322,10 +322,6 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     }
     d->stream = d->own_stream;
     d->opt_batch = 1;
-    d->opt_chunk = 0;
-    d->opt_profile = 0;
-    d->opt_quads = 0;
-    d->opt_accel = 0;
     d->opt_pmask = PT_DEFAULT_PRIMARY_MASKS;
     d->opt_bvh_stack = 64;
     d->opt_lanes = 2;
@@ -334,10 +330,9 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->kernels[KERNEL_FILL] = { KERNEL_FILL, "PtShimTest", "FillKernel" };
     d->kernels[KERNEL_MATH] = { KERNEL_MATH, "PtShimTest", "MathKernel" };
     d->kernels[KERNEL_FOLD_CHECK] = { KERNEL_FOLD_CHECK, "PtShimTest", "FoldCheckKernel" };
-    d->prof_pairs = new std::vector<std::pair<hipEvent_t, hipEvent_t>>[PT_PROF_KINDS];
-    bool ok = ws_malloc(d, &d->bigtab, WS_BIGTAB) == hipSuccess && ws_malloc(d, &d->bigidx, WS_BIGIDX) == hipSuccess &&
-              ws_malloc(d, &d->counters, WS_COUNTERS) == hipSuccess && ws_malloc(d, &d->big_filter.p1tab, ws_big_p1tab()) == hipSuccess &&
-              ws_malloc(d, &d->det_bound_dev, WS_DETBOUND) == hipSuccess;
+    bool ok = ws_malloc(d, d->bigtab, WS_BIGTAB) == hipSuccess && ws_malloc(d, d->bigidx, WS_BIGIDX) == hipSuccess &&
+              ws_malloc(d, d->counters, WS_COUNTERS) == hipSuccess && ws_malloc(d, d->big_filter.p1tab, ws_big_p1tab()) == hipSuccess &&
+              ws_malloc(d, d->det_bound_dev, WS_DETBOUND) == hipSuccess;
     // the render lanes and their events (no timing: they only order streams)
     for (int k = 0; ok && k < 2; ++k)
         ok = hipStreamCreateWithFlags(&d->lane[k], hipStreamNonBlocking) == hipSuccess &&
@@ -366,15 +361,14 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
 
 static int flush_pending(pt_device_s* d);
 
-static int lanes_join(pt_device_s* d);
+static int stream_wait(pt_device_s* d);
 
 extern "C" int pt_device_destroy(pt_device_t d)
 {
     int rc = use_device(d);
     if (rc) return rc;
     rc = flush_pending(d);
-    lanes_join(d);
-    hipStreamSynchronize(d->stream);
+    (void)stream_wait(d);   // (best effort on teardown)
     if (d->live_buffers != 0)
         return fail(PT_ERR_INVALID, "%d buffer(s) of this device are still alive", d->live_buffers);
     destroy_device_objects(d);
@@ -418,6 +412,14 @@ extern "C" int pt_device_num_cus(pt_device_t d) { return d ? d->prop.multiProces
 //         last fork (main_dirty), or the stream is the caller's, who may have enqueued on it without telling us;
 //   join  (lanes_join): `stream` waits for the newest fold -- only when a call needs the renders' results on `stream`, so
 //         that back-to-back renders never meet a join and overlap on the device.
+// THE RULE: whoever enqueues on the handle's stream orders it behind the lanes and marks it dirty, so that the next fork happens.
+// Nobody keeps it by hand; there are two primitives, and every site calls one of them:
+//   stream_enqueue: "I am about to enqueue on the handle's stream": join, main_dirty = true (enter_stream: the entry points' form,
+//                   which submits the deferred frames first);
+//   stream_wait:    "the host waits for everything this handle has enqueued": join, hipStreamSynchronize.  Nothing is enqueued, so
+//                   main_dirty stays as it is: a pt_sync between two renders does not make the second one fork.
+// A bare lanes_join is left only where a call needs the order and enqueues no work on `stream` (event records at most).
+
 // a caller's stream handle: PT_STREAM_LEGACY (the value of HIP's hipStreamLegacy sentinel) is the legacy default stream, which every
 // HIP entry point knows as the null stream (the sentinel itself is not accepted by every runtime version torch ships)
 static hipStream_t as_stream(void* h) { return h == PT_STREAM_LEGACY ? nullptr : (hipStream_t)h; }
@@ -430,14 +432,26 @@ static int lanes_join(pt_device_s* d)
     return PT_OK;
 }
 
-// every entry point that enqueues on, or waits for, the handle's stream: deferred frames are submitted and the stream is
-// ordered behind the lanes first
-static int enter_stream(pt_device_s* d)
+static int stream_enqueue(pt_device_s* d)
 {
-    int rc = flush_pending(d);
-    if (!rc) rc = lanes_join(d);
+    int rc = lanes_join(d);
     d->main_dirty = true;
     return rc;
+}
+
+static int stream_wait(pt_device_s* d)
+{
+    int rc = lanes_join(d);
+    hipError_t e = hipStreamSynchronize(d->stream);   // (after a failed join too: teardown ignores both)
+    if (rc || e == hipSuccess) return rc;
+    return fail(PT_ERR_HIP, "hipStreamSynchronize(d->stream) failed: %s", hipGetErrorString(e));
+}
+
+// every entry point that enqueues on the handle's stream: deferred frames are submitted first
+static int enter_stream(pt_device_s* d)
+{
+    int rc = flush_pending(d), rc2 = stream_enqueue(d);   // (also after a flush that failed: it may have enqueued)
+    return rc ? rc : rc2;
 }
 
 // PT_ERR_TRAVERSAL, deferred (include/pt_shim.h): read -- and clear -- the words the LBVH kernels raise.  Called wherever the
@@ -456,8 +470,7 @@ extern "C" int pt_device_set_stream(pt_device_t d, void* hip_stream)
 {
     int rc = use_device(d);
     if (rc) return rc;
-    if ((rc = enter_stream(d))) return rc;
-    HIP_TRY(hipStreamSynchronize(d->stream));  // keep the one-queue ordering across the switch
+    if ((rc = enter_stream(d)) || (rc = stream_wait(d))) return rc;   // keep the one-queue ordering across the switch
     // NULL restores the handle's own (non-blocking) stream.  The legacy default stream -- what a
     // caller's "stream 0" means -- is named by PT_STREAM_LEGACY and used as HIP's null stream.
     d->stream = hip_stream ? as_stream(hip_stream) : d->own_stream;
@@ -500,8 +513,7 @@ extern "C" int pt_sync(pt_device_t d)
     if (d->pending.active && (d->pending.tris->exposed || d->pending.mats->exposed || d->pending.fb->exposed) &&
         (rc = flush_pending(d)))
         return rc;
-    if ((rc = lanes_join(d))) return rc;
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    if ((rc = stream_wait(d))) return rc;
     return check_traversal(d);
 }
 
@@ -514,10 +526,9 @@ extern "C" int pt_flush(pt_device_t d)
 
 static int free_ring(pt_device_s* d)
 {
-    int rc = lanes_join(d);
+    int rc = stream_wait(d);   // nothing in flight may still write it
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(d->stream));   // nothing in flight may still write it
-    ws_free(d, d->ring, PT_RING_SLOTS * d->ring_slot_bytes);
+    ws_free(d, d->ring);
     d->ring_slot_bytes = 0;
     return PT_OK;
 }
@@ -525,7 +536,7 @@ static int free_ring(pt_device_s* d)
 static int alloc_ring(pt_device_s* d, size_t slot_bytes)
 {
     slot_bytes = (slot_bytes + 255) & ~(size_t)255;
-    hipError_t e = ws_malloc(d, &d->ring, PT_RING_SLOTS * slot_bytes);
+    hipError_t e = ws_malloc(d, d->ring, PT_RING_SLOTS * slot_bytes);
     if (e != hipSuccess) return fail(PT_ERR_OOM, "radiance staging ring (%d x %zu bytes) allocation failed: %s", PT_RING_SLOTS, slot_bytes, hipGetErrorString(e));
     d->ring_slot_bytes = slot_bytes;
     return PT_OK;
@@ -669,8 +680,7 @@ extern "C" int pt_buffer_free(pt_buffer_t b)
     int rc = use_device(d);
     if (rc) return rc;
     if (d->pending.active && (d->pending.tris == b || d->pending.mats == b || d->pending.fb == b)) rc = flush_pending(d);
-    lanes_join(d);
-    hipStreamSynchronize(d->stream);  // nothing in flight may still touch it
+    (void)stream_wait(d);  // nothing in flight may still touch it (best effort)
     if (d->prep_src == b) d->prep_src = nullptr;
     if (b->staging) hipHostFree(b->staging);
     if (b->owned) {
@@ -1041,23 +1051,22 @@ static int ensure_prep(pt_device_s* d, const pt_buffer_s* tris, int ntri)
     if (d->prep_capacity >= (size_t)ntri && d->prep_src == tris && d->prep_version == tris->version && d->prep_ntri == ntri && tris->owned && !tris->exposed)
         return PT_OK;
     // the prepared scene is about to change under whatever the lanes still run: the handle's stream goes behind them
-    int rc = lanes_join(d);
+    int rc = stream_enqueue(d);
     if (rc) return rc;
-    d->main_dirty = true;
     if (d->prep_capacity < (size_t)ntri) {
         HIP_TRY(hipStreamSynchronize(d->stream));
-        ws_free(d, d->prep, d->prep_capacity * sizeof(PtPrepTriangle));
-        ws_free(d, d->scene_filter.p1tab, ptk_p1tab_floats((int)d->prep_capacity) * sizeof(float));
-        ws_free(d, d->bvh, ptk_bvh_record_count((int)d->prep_capacity) * sizeof(PtBvh8Node));
+        ws_free(d, d->prep);
+        ws_free(d, d->scene_filter.p1tab);
+        ws_free(d, d->bvh);
         d->bvh_valid = false;
         d->prep_capacity = 0;
         d->prep_src = nullptr;
         d->prep_hash_valid = false;
         size_t cap = std::max<size_t>((size_t)ntri, 64);
-        hipError_t e = ws_malloc(d, &d->prep, cap * sizeof(PtPrepTriangle));
-        if (e == hipSuccess) e = ws_malloc(d, &d->scene_filter.p1tab, ptk_p1tab_floats((int)cap) * sizeof(float));
+        hipError_t e = ws_malloc(d, d->prep, cap * sizeof(PtPrepTriangle));
+        if (e == hipSuccess) e = ws_malloc(d, d->scene_filter.p1tab, ptk_p1tab_floats((int)cap) * sizeof(float));
         if (e != hipSuccess) {
-            ws_free(d, d->prep, cap * sizeof(PtPrepTriangle));
+            ws_free(d, d->prep);
             return fail(PT_ERR_OOM, "scene workspace allocation failed: %s", hipGetErrorString(e));
         }
         d->prep_capacity = cap;
@@ -1100,11 +1109,10 @@ static int ensure_prep(pt_device_s* d, const pt_buffer_s* tris, int ntri)
 static int ensure_bvh(pt_device_s* d, const pt_buffer_s* tris, int ntri)
 {
     if (d->bvh_valid) return PT_OK;
-    int rc = lanes_join(d);   // (a render through the old hierarchy may still be running)
+    int rc = stream_enqueue(d);   // (a render through the old hierarchy may still be running)
     if (rc) return rc;
-    d->main_dirty = true;
     if (!d->bvh) {
-        hipError_t e = ws_malloc(d, &d->bvh, ptk_bvh_record_count((int)d->prep_capacity) * sizeof(PtBvh8Node));
+        hipError_t e = ws_malloc(d, d->bvh, ptk_bvh_record_count((int)d->prep_capacity) * sizeof(PtBvh8Node));
         if (e != hipSuccess) return fail(PT_ERR_OOM, "BVH allocation failed: %s", hipGetErrorString(e));
     }
     const size_t temp_bytes = ptk_bvh_temp_bytes(ntri);
@@ -1178,7 +1186,7 @@ static float anchor_radius(const pt_device_s* d, const float eye[3])
 // The pass-1 filter of a quad scene (pt_quad3_pass1) is made about an ANCHOR, the render's eye: its error bounds are sized by
 // the scene's radius about it, its packed table holds K = cross(e2, a - eye).  When the eye moves, the margins (pad0 of the
 // prepared records) and the packed table are rewritten by kernels enqueued on the handle's stream, behind the renders in
-// flight (lanes_join: a device-side wait), for table ft -- the brute-force scene's or the LBVH's table of big triangles -- whose
+// flight (stream_enqueue: a device-side wait), for table ft -- the brute-force scene's or the LBVH's table of big triangles -- whose
 // ntri prepared records are tris.  The pairing checks of the scene preparation do not depend on the camera and stand; the LBVH
 // is not touched.  The same eye as the table's does nothing at all.
 static int ensure_anchor(pt_device_s* d, PtFilterTable& ft, PtPrepTriangle* tris, int ntri, const float eye[3])
@@ -1196,9 +1204,8 @@ static int ensure_anchor(pt_device_s* d, PtFilterTable& ft, PtPrepTriangle* tris
         const float delta1 = 128.0f * 5.9604645e-8f * diameter * diameter * 1.001f;
         // mode 3 (pt_quad3_pass1): deltaP = 192 u D^2; first triangle un >= -deltaP, second un <= delta1 + deltaP
         const float deltaP = 192.0f * 5.9604645e-8f * diameter * diameter * 1.001f;
-        int rc = lanes_join(d);   // (a render through the old table may still be running)
+        int rc = stream_enqueue(d);   // (a render through the old table may still be running)
         if (rc) return rc;
-        d->main_dirty = true;
         HIP_TRY(ptk_prep_quad_margins(tris, ntri, diameter, delta1, ft.p1tab, eye, d->stream));
         ft.delta1 = delta1; ft.ray_radius = ray_radius;
         ft.p1_lo = -deltaP; ft.p1_hi = (delta1 + deltaP) * 1.001f;
@@ -1209,13 +1216,28 @@ static int ensure_anchor(pt_device_s* d, PtFilterTable& ft, PtPrepTriangle* tris
     return PT_OK;
 }
 
+// THE search of a render, a query or an ambient-occlusion render, decided here and nowhere else: which one (PtSearchMode, what the
+// launchers take), over which filter table, on what grid
+struct PtSearch {
+    PtSearchMode mode;
+    const PtFilterTable* ft;   // the table the two-pass search runs over: the prepared scene's, or the LBVH's big triangles'
+    int ntri;
+    int driver_blocks;         // the persistent grid of the LBVH driver's kernels (queries, ambient occlusion); 0: brute force
+    bool wide;                 // renders through the LBVH: the eye is far from the scene (eye_is_far), the slabs carry the ray term
+};
+
 // the search and what it reads: the prepared scene, its LBVH, the filter of the table the two-pass search runs over.
 // PT_OPT_ACCEL: 0 = BVH for scenes of PT_BVH_AUTO_MIN triangles or more, 1 = brute force, 2 = BVH (needs >= 2 triangles)
+// PT_OPT_QUAD_FILTER: 0 / 4 = the packed shared-u filter when the table allows it, 1..3 = independent triangles
 // eye: the filter's anchor, the render's eye.  NULL (a ray query, whose origins are anywhere) keeps the anchor the table has, so
-// that a query never rewrites the table under the renders of a moved camera, and makes the reference eye's when it has none
-static int prepare_search(pt_device_s* d, const pt_buffer_s* tris, int ntri, const float* eye, bool& use_bvh)
+// that a query never rewrites the table under the renders of a moved camera, and makes the reference eye's when it has none.
+// An empty scene has nothing to search: neither the prepared scene nor any table is touched
+static int prepare_search(pt_device_s* d, const pt_buffer_s* tris, int ntri, const float* eye, PtSearch& s)
 {
-    use_bvh = ntri >= 2 && (d->opt_accel == 2 || (d->opt_accel == 0 && ntri >= PT_BVH_AUTO_MIN));
+    s = PtSearch();
+    s.ft = &d->scene_filter;
+    if (ntri == 0) return PT_OK;
+    const bool use_bvh = ntri >= 2 && (d->opt_accel == 2 || (d->opt_accel == 0 && ntri >= PT_BVH_AUTO_MIN));
     if (!use_bvh && ntri >= (1 << 26))
         return fail(PT_ERR_INVALID, "the brute-force search packs a triangle index in 26 bits: use PT_OPT_ACCEL 0 or 2 for %d triangles", ntri);
     if (use_bvh && ntri >= (1 << 25))
@@ -1223,12 +1245,31 @@ static int prepare_search(pt_device_s* d, const pt_buffer_s* tris, int ntri, con
     int rc;
     if ((rc = ensure_prep(d, tris, ntri))) return rc;
     if (use_bvh && (rc = ensure_bvh(d, tris, ntri))) return rc;
+    PtFilterTable& ft = use_bvh ? d->big_filter : d->scene_filter;
     const PtCamera ref = reference_camera();
-    if (!eye) {
-        const PtFilterTable& ft = use_bvh ? d->big_filter : d->scene_filter;
-        eye = ft.anchor_valid ? ft.anchor : ref.eye;
-    }
-    return use_bvh ? ensure_anchor(d, d->big_filter, d->bigtab, d->nbig, eye) : ensure_anchor(d, d->scene_filter, d->prep, d->prep_ntri, eye);
+    const float* anchor = eye ? eye : ft.anchor_valid ? ft.anchor : ref.eye;
+    if ((rc = use_bvh ? ensure_anchor(d, ft, d->bigtab, d->nbig, anchor) : ensure_anchor(d, ft, d->prep, d->prep_ntri, anchor))) return rc;
+    s.mode = { use_bvh, d->prep_det_bounded, (d->opt_quads == 0 || d->opt_quads == 4) ? ft.quads : 0 };
+    s.ft = &ft;
+    s.ntri = ntri;
+    s.driver_blocks = use_bvh ? d->prop.multiProcessorCount * d->query_bvh_blocks_per_cu : 0;
+    s.wide = use_bvh && eye && eye_is_far(d, eye);
+    return PT_OK;
+}
+
+// the search fields of a PtTraceParams (for queries and ambient occlusion: PtQueryParams::t, PtAoParams::t): the scene, the filter of
+// the table the two-pass search runs over with its anchor in cam.eye, the LBVH
+static void search_fields(const pt_device_s* d, const PtSearch& s, PtTraceParams& t)
+{
+    const PtFilterTable& ft = *s.ft;
+    t.tris = d->prep;
+    t.ntri = s.ntri;
+    t.quad_delta1 = ft.delta1; t.ray_radius = ft.ray_radius;
+    t.p1tab = ft.p1tab; t.p1_lo = ft.p1_lo; t.p1_hi = ft.p1_hi;
+    memcpy(t.cam.eye, ft.anchor, sizeof t.cam.eye);   // the anchor the table was made about
+    t.bvh = d->bvh; t.bvh_records = (int32_t)d->bvh_records; t.grid = d->bvh_grid;
+    t.bigtab = d->bigtab; t.bigidx = d->bigidx; t.nbig = s.mode.bvh ? d->nbig : 0;
+    t.bvh_flags = d->trav_dev; t.bvh_stack_limit = (int32_t)d->opt_bvh_stack;
 }
 
 // ---- the staging ring: whole frames per chunk, as many as a slot holds -------------------------------------------------
@@ -1259,16 +1300,13 @@ static int refresh_pmask(pt_device_s* d, const pt_render_params& rp, const PtCam
     make = !d->pmask_key.valid || d->pmask_key.scene_gen != d->scene_gen || memcmp(d->pmask_key.g, g, sizeof g) != 0 ||
            memcmp(&d->pmask_key.cam, &cam, sizeof cam) != 0;
     if (!make) return PT_OK;
-    if ((rc = lanes_join(d))) return rc;   // (a render with the old masks may still be running)
-    d->main_dirty = true;
+    if ((rc = stream_enqueue(d))) return rc;   // (a render with the old masks may still be running; render_part launches the new ones)
     d->pmask_key.valid = false;
-    if (d->pmask_pixels < npix) {
+    if (d->pmask.bytes < (size_t)npix * sizeof(uint2)) {
         HIP_TRY(hipStreamSynchronize(d->stream));
-        ws_free(d, d->pmask, d->pmask_pixels * sizeof(uint2));
-        d->pmask_pixels = 0;
-        hipError_t e = ws_malloc(d, &d->pmask, (size_t)npix * sizeof(uint2));
+        ws_free(d, d->pmask);
+        hipError_t e = ws_malloc(d, d->pmask, (size_t)npix * sizeof(uint2));
         if (e != hipSuccess) return fail(PT_ERR_OOM, "primary-mask allocation (%zu bytes) failed: %s", (size_t)npix * sizeof(uint2), hipGetErrorString(e));
-        d->pmask_pixels = npix;
     }
     d->pmask_key.scene_gen = d->scene_gen;
     memcpy(d->pmask_key.g, g, sizeof g);
@@ -1311,28 +1349,22 @@ static void image_geometry(PtTraceParams& t, int width, int height, int stripe_r
 
 // what every trace launch of the render is given; render_part's trace() sets the per-launch rest (queue, frames, checkpoints)
 static PtTraceParams trace_params(const pt_device_s* d, const pt_buffer_s* mats, const pt_buffer_s* stats, const pt_render_params& rp,
-                                  const PtCamera& cam, uint32_t npix, const PtFilterTable& ft, bool use_bvh, bool use_pmask, int chunk,
-                                  uint32_t batch, uint32_t bpf)
+                                  const PtCamera& cam, uint32_t npix, const PtSearch& search, bool use_pmask, int chunk, uint32_t batch, uint32_t bpf)
 {
     PtTraceParams tp;
     memset(&tp, 0, sizeof tp);
-    tp.tris = d->prep;
+    search_fields(d, search, tp);
     tp.mats = (const PtRawMaterial*)mats->dptr;
     tp.stats = stats ? (unsigned long long*)stats->dptr : nullptr;
     image_geometry(tp, rp.width, rp.height, rp.stripe_rows, rp.n_ranks, rp.rank, npix);
-    tp.max_bounces = rp.max_bounces; tp.ntri = rp.num_triangles; tp.nmat = rp.num_materials;
+    tp.max_bounces = rp.max_bounces; tp.nmat = rp.num_materials;
     tp.batches_per_frame = bpf; tp.batch = batch;
-    tp.quad_delta1 = ft.delta1; tp.ray_radius = ft.ray_radius;
-    tp.p1tab = ft.p1tab; tp.p1_lo = ft.p1_lo; tp.p1_hi = ft.p1_hi;
-    tp.bvh = d->bvh; tp.bvh_records = (int32_t)d->bvh_records; tp.grid = d->bvh_grid;
-    tp.bigtab = d->bigtab; tp.bigidx = d->bigidx; tp.nbig = use_bvh ? d->nbig : 0;
-    tp.pmask = use_pmask ? d->pmask : nullptr;
-    tp.bvh_flags = d->trav_dev; tp.bvh_stack_limit = (int32_t)d->opt_bvh_stack;
+    tp.pmask = use_pmask ? d->pmask.p : nullptr;
     tp.slot_frames = (uint32_t)chunk;
     tp.ring_magic = (uint32_t)(0x100000000ull / (2u * (uint32_t)chunk)) + 1u;
     tp.rad = d->ring;
-    tp.rad1 = reinterpret_cast<float*>(reinterpret_cast<char*>(d->ring) + d->ring_slot_bytes);
-    tp.cam = cam;
+    tp.rad1 = reinterpret_cast<float*>(reinterpret_cast<char*>(d->ring.p) + d->ring_slot_bytes);
+    tp.cam = cam;   // (its eye is the table's anchor bit for bit: prepare_search anchored the table there)
     return tp;
 }
 
@@ -1344,9 +1376,8 @@ static int ensure_carry(pt_device_s* d, int blocks)
     if ((size_t)blocks * wg_waves > waves) return fail(PT_ERR_INVALID, "grid larger than the checkpoint regions");
     for (int k = 0; k < 2; ++k)
         if (!d->carry[k]) {   // once per device handle, at its first such render
-            hipError_t e = ws_malloc(d, &d->carry[k], waves * PT_CARRY_STRIDE_DW * sizeof(uint32_t));
+            hipError_t e = ws_malloc(d, d->carry[k], waves * PT_CARRY_STRIDE_DW * sizeof(uint32_t));
             if (e != hipSuccess) return fail(PT_ERR_OOM, "checkpoint buffer allocation failed: %s", hipGetErrorString(e));
-            d->carry_waves = waves;
         }
     return PT_OK;
 }
@@ -1357,26 +1388,23 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
                        uint32_t npix, pt_buffer_s* stats, pt_event_s* ev_start, pt_event_s* ev_stop)
 {
     int rc;
-    bool use_bvh;
-    if ((rc = prepare_search(d, tris, rp.num_triangles, cam.eye, use_bvh))) return rc;
-    const PtFilterTable& ft = use_bvh ? d->big_filter : d->scene_filter;
+    PtSearch search;
+    if ((rc = prepare_search(d, tris, rp.num_triangles, cam.eye, search))) return rc;
+    const bool use_bvh = search.mode.bvh;
     int nchunks, chunk;
     if ((rc = plan_chunks(d, rp.frame_count, npix, nchunks, chunk))) return rc;
-    // PT_OPT_QUAD_FILTER: 0 / 4 = the packed shared-u filter when the table allows it, 1..3 = independent triangles
-    const int quads = (d->opt_quads == 0 || d->opt_quads == 4) ? ft.quads : 0;
-    const bool use_pmask = d->opt_pmask && quads == 3 && !use_bvh && rp.num_triangles <= 64 && d->prep_det_bounded;
+    const bool use_pmask = d->opt_pmask && search.mode.quads == 3 && !use_bvh && rp.num_triangles <= 64 && search.mode.det_bounded;
     bool make_pmask = false;
     if (use_pmask && (rc = refresh_pmask(d, rp, cam, npix, make_pmask))) return rc;
     if (d->counters_dirty) {   // an earlier call failed between a trace launch and the fold that resets its counter
-        if ((rc = lanes_join(d))) return rc;
+        if ((rc = stream_enqueue(d))) return rc;
         HIP_TRY(hipMemsetAsync(d->counters, 0, WS_COUNTERS, d->stream));
-        d->main_dirty = true;
         d->counters_dirty = false;
     }
     uint32_t batch, bpf;
     int blocks;
     if ((rc = choose_batch(d, use_bvh, npix, chunk, batch, bpf, blocks))) return rc;
-    PtTraceParams tp = trace_params(d, mats, stats, rp, cam, npix, ft, use_bvh, use_pmask, chunk, batch, bpf);
+    PtTraceParams tp = trace_params(d, mats, stats, rp, cam, npix, search, use_pmask, chunk, batch, bpf);
     if (make_pmask) {
         HIP_TRY(ptk_primary_masks(tp, d->stream));  // (cheap: one thread per pixel)
         d->pmask_key.valid = true;
@@ -1403,7 +1431,7 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
     d->counters_dirty = true;   // until the last fold of this call is enqueued
     if (ev_start) HIP_TRY(hipEventRecord(ev_start->start, st));
     tp.ring_phase = (uint32_t)((d->chunk_seq & 1u) ? chunk : 0);   // the render's first chunk goes to slot chunk_seq % 2
-    tp.carry = carry ? d->carry[ln] : nullptr;
+    tp.carry = carry ? d->carry[ln].p : nullptr;
     unsigned int* const drain_counter = d->counters + (size_t)(PT_QUEUE_COUNTERS - 1 - ln) * PT_QUEUE_STRIDE;
     unsigned int* prev_counter = nullptr;
     int prev_slot = 0, prev_f0 = 0, prev_nf = 0;
@@ -1450,7 +1478,7 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
         tp.total_batches = (uint32_t)((uint64_t)bpf * (uint64_t)nf);
         int r = prof_begin(d, PT_PROF_TRACE, st, &pstop);
         if (r) return r;
-        HIP_TRY(ptk_trace(tp, blocks, d->prep_det_bounded, quads, use_bvh, d->opt_tally != 0 && stats != nullptr, use_bvh && eye_is_far(d, tp.cam.eye), st));
+        HIP_TRY(ptk_trace(tp, blocks, search.mode, d->opt_tally != 0 && stats != nullptr, search.wide, st));
         return prof_end(st, pstop);
     };
     for (int c = 0; c < nchunks; ++c) {
@@ -1490,6 +1518,18 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
     return PT_OK;
 }
 
+// an image's geometry, this rank's stripes of it and a frame range, as every entry point that takes them checks them; npix: the
+// rank's local pixels
+static int check_image(const char* invalid, int width, int height, int frame_begin, int frame_count, int stripe_rows, int n_ranks, int rank, uint64_t& npix)
+{
+    if (width < 1 || height < 1 || frame_begin < 0 || frame_count < 0 || stripe_rows < 1 || n_ranks < 1 || rank < 0 || rank >= n_ranks)
+        return fail(PT_ERR_INVALID, "%s", invalid);
+    if ((long long)width * height > 0x7fffffffLL) return fail(PT_ERR_INVALID, "image too large");
+    if ((long long)frame_begin + frame_count > 0x7fffffffLL) return fail(PT_ERR_INVALID, "frame index overflow");
+    npix = (uint64_t)pt_local_rows(height, stripe_rows, n_ranks, rank) * (uint64_t)width;
+    return PT_OK;
+}
+
 // pixel_count: 0 = all local pixels; otherwise the first pixel_count local pixels (n_ranks must be 1)
 static int render_internal(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_buffer_s* fb,
                            const pt_render_params& rp, const PtCamera& cam, uint32_t pixel_count, pt_buffer_s* stats, pt_event_s* ev)
@@ -1497,17 +1537,12 @@ static int render_internal(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats,
     if (!tris || !mats || !fb) return fail(PT_ERR_INVALID, "null buffer handle");
     int rc = check_same_device(d, { tris, mats, fb, stats });
     if (rc) return rc;
-    if (rp.width < 1 || rp.height < 1 || rp.frame_begin < 0 || rp.frame_count < 0 || rp.max_bounces < 1 ||
-        rp.num_triangles < 0 || rp.num_materials < 1 || rp.stripe_rows < 1 || rp.n_ranks < 1 || rp.rank < 0 ||
-        rp.rank >= rp.n_ranks)
-        return fail(PT_ERR_INVALID, "invalid render parameters");
+    if (rp.max_bounces < 1 || rp.num_triangles < 0 || rp.num_materials < 1) return fail(PT_ERR_INVALID, "invalid render parameters");
     for (int i = 0; i < 6; ++i)
         if (rp.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
-    if ((long long)rp.width * rp.height > 0x7fffffffLL) return fail(PT_ERR_INVALID, "image too large");
-    if ((long long)rp.frame_begin + rp.frame_count > 0x7fffffffLL) return fail(PT_ERR_INVALID, "frame index overflow");
+    uint64_t npix64;
+    if ((rc = check_image("invalid render parameters", rp.width, rp.height, rp.frame_begin, rp.frame_count, rp.stripe_rows, rp.n_ranks, rp.rank, npix64))) return rc;
     if (rp.max_bounces > 65535) return fail(PT_ERR_INVALID, "max_bounces above 65535 (a parked path packs its bounce count in 16 bits)");
-    int rows = pt_local_rows(rp.height, rp.stripe_rows, rp.n_ranks, rp.rank);
-    uint64_t npix64 = (uint64_t)rows * (uint64_t)rp.width;
     if (pixel_count) {
         if (rp.n_ranks != 1) return fail(PT_ERR_INVALID, "pixel_count needs n_ranks == 1");
         npix64 = std::min<uint64_t>(npix64, pixel_count);
@@ -1593,26 +1628,6 @@ static bool ranges_overlap(const pt_buffer_s* a, size_t abytes, const pt_buffer_
     return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
 }
 
-// the search of a query, AO render or occlusion search over the prepared scene: its fields of PtTraceParams (PtQueryParams::t) --
-// the scene, the filter of the table the two-pass search runs over with its anchor in cam.eye, the LBVH -- and the filter mode,
-// PT_OPT_QUAD_FILTER as for renders (render_part; an empty scene has no table)
-static PtTraceParams search_params(const pt_device_s* d, int num_triangles, bool use_bvh, int& quads)
-{
-    const PtFilterTable& ft = use_bvh ? d->big_filter : d->scene_filter;
-    quads = num_triangles > 0 && (d->opt_quads == 0 || d->opt_quads == 4) ? ft.quads : 0;
-    PtTraceParams t;
-    memset(&t, 0, sizeof t);
-    t.tris = d->prep;
-    t.ntri = num_triangles;
-    t.quad_delta1 = ft.delta1; t.ray_radius = ft.ray_radius;
-    t.p1tab = ft.p1tab; t.p1_lo = ft.p1_lo; t.p1_hi = ft.p1_hi;
-    memcpy(t.cam.eye, ft.anchor, sizeof t.cam.eye);   // the anchor the table was made about
-    t.bvh = d->bvh; t.bvh_records = (int32_t)d->bvh_records; t.grid = d->bvh_grid;
-    t.bigtab = d->bigtab; t.bigidx = d->bigidx; t.nbig = use_bvh ? d->nbig : 0;
-    t.bvh_flags = d->trav_dev; t.bvh_stack_limit = (int32_t)d->opt_bvh_stack;
-    return t;
-}
-
 // pt_intersect_rays and pt_occluded_rays: the argument checks, the deferred error, the stream, the scene, the launch.
 // occluded: 1 / 0 results (int32) instead of pt_hit records; early_exit: (occluded only) through the LBVH the search is the any-hit
 // one, which stops at the first accepted triangle -- brute force keeps the two-pass closest search (a few dozen triangles leave
@@ -1634,20 +1649,18 @@ static int query_rays(pt_device_s* d, pt_buffer_s* triangles, int num_triangles,
     // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
     if ((rc = check_traversal(d))) return rc;
     if ((rc = enter_stream(d))) return rc;
-    bool use_bvh = false;
-    if (num_rays && num_triangles > 0 && (rc = prepare_search(d, triangles, num_triangles, nullptr, use_bvh))) return rc;
+    PtSearch search;
+    if (num_rays && (rc = prepare_search(d, triangles, num_triangles, nullptr, search))) return rc;
     if ((rc = event_begin(d, ev))) return rc;
     if (num_rays) {
-        int quads;
         PtQueryParams q;
         memset(&q, 0, sizeof q);
-        q.t = search_params(d, num_triangles, use_bvh, quads);
+        search_fields(d, search, q.t);
         q.rays = (const float4*)rays->dptr;
         q.out = out->dptr;
         q.nrays = (uint32_t)num_rays;
         q.occluded = occluded;
-        HIP_TRY(ptk_query(q, d->prop.multiProcessorCount * d->query_bvh_blocks_per_cu, num_triangles > 0 && d->prep_det_bounded, quads, use_bvh,
-                          early_exit && use_bvh, d->stream));
+        HIP_TRY(ptk_query(q, search.driver_blocks, search.mode, early_exit && search.mode.bvh, d->stream));
     }
     out->version++;
     return event_end(d, ev);
@@ -1684,18 +1697,16 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
     if (cam && (rc = camera_derive(cam, &c))) return rc;
     if (!triangles || !counts) return fail(PT_ERR_INVALID, "null buffer handle");
     if ((rc = check_same_device(d, { triangles, counts, image })) || (rc = check_event(d, ev))) return rc;
-    if (a.width < 1 || a.height < 1 || a.frame_begin < 0 || a.frame_count < 0 || a.num_triangles < 0 || a.rays_per_sample < 1 ||
-        a.rays_per_sample > 256 || !(std::isfinite(a.radius) && a.radius > 0.0f) || !std::isfinite(a.miss_value) || a.stripe_rows < 1 ||
-        a.n_ranks < 1 || a.rank < 0 || a.rank >= a.n_ranks)
+    if (a.num_triangles < 0 || a.rays_per_sample < 1 || a.rays_per_sample > 256 || !(std::isfinite(a.radius) && a.radius > 0.0f) || !std::isfinite(a.miss_value))
         return fail(PT_ERR_INVALID, "invalid AO parameters");
     for (int i = 0; i < 5; ++i)
         if (a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
-    if ((long long)a.width * a.height > 0x7fffffffLL) return fail(PT_ERR_INVALID, "image too large");
-    if ((long long)a.frame_begin + a.frame_count > 0x7fffffffLL) return fail(PT_ERR_INVALID, "frame index overflow");
+    uint64_t npix64;
+    if ((rc = check_image("invalid AO parameters", a.width, a.height, a.frame_begin, a.frame_count, a.stripe_rows, a.n_ranks, a.rank, npix64))) return rc;
     // open <= frames K and K hits <= frames K: neither uint32 count can wrap
     if (((long long)a.frame_begin + a.frame_count) * a.rays_per_sample > 0xffffffffLL)
         return fail(PT_ERR_RANGE, "(frame_begin + frame_count) x rays_per_sample exceeds 2^32 - 1: the counts could wrap");
-    const uint32_t npix = (uint32_t)((uint64_t)pt_local_rows(a.height, a.stripe_rows, a.n_ranks, a.rank) * (uint64_t)a.width);
+    const uint32_t npix = (uint32_t)npix64;
     const size_t count_bytes = (size_t)npix * 8, image_bytes = (size_t)npix * sizeof(float4);
     if ((rc = check_triangles(triangles, a.num_triangles))) return rc;
     if (count_bytes > counts->bytes) return fail(PT_ERR_RANGE, "count buffer holds %zu bytes, %u pixels need %zu", counts->bytes, npix, count_bytes);
@@ -1710,15 +1721,14 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
         if ((rc = event_begin(d, ev))) return rc;
         return event_end(d, ev);
     }
-    bool use_bvh = false;
-    if (a.num_triangles > 0 && (rc = prepare_search(d, triangles, a.num_triangles, nullptr, use_bvh))) return rc;
+    PtSearch search;
+    if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
     if ((rc = event_begin(d, ev))) return rc;
     if (a.frame_begin == 0) HIP_TRY(hipMemsetAsync(counts->dptr, 0, count_bytes, d->stream));   // the :314-321 rule: frame 0 starts afresh
     if (a.num_triangles > 0) {
-        int quads;
         PtAoParams p;
         memset(&p, 0, sizeof p);
-        p.t = search_params(d, a.num_triangles, use_bvh, quads);
+        search_fields(d, search, p.t);
         image_geometry(p.t, a.width, a.height, a.stripe_rows, a.n_ranks, a.rank, npix);
         p.cam = c;
         p.counts = (unsigned long long*)counts->dptr;
@@ -1727,12 +1737,11 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
         p.tlim = a.radius < 1e20f ? a.radius : 1e20f;
         // frame-major samples, fewer than 2^31 per launch
         const int per_launch = (int)std::max<uint32_t>(1u, 0x7fffffffu / npix);
-        const int blocks = d->prop.multiProcessorCount * (use_bvh ? d->query_bvh_blocks_per_cu : 0);
         for (int64_t done = 0; done < a.frame_count; done += per_launch) {   // (64-bit: done + per_launch may pass 2^31 - 1)
             const int nf = (int)std::min<int64_t>(per_launch, a.frame_count - done);
             p.frame0 = a.frame_begin + (int)done;
             p.nitems = (uint32_t)nf * npix;
-            HIP_TRY(ptk_ao(p, blocks, d->prep_det_bounded, quads, use_bvh, d->stream));
+            HIP_TRY(ptk_ao(p, search.driver_blocks, search.mode, d->stream));
         }
     }
     if (image) HIP_TRY(ptk_ao_resolve((const uint2*)counts->dptr, (float4*)image->dptr, npix, (uint32_t)a.rays_per_sample, a.miss_value, d->stream));
@@ -1749,9 +1758,10 @@ extern "C" int pt_camera_rays(pt_device_t d, const pt_camera* cam, int width, in
     if (cam && (rc = camera_derive(cam, &c))) return rc;
     if (!rays) return fail(PT_ERR_INVALID, "null buffer handle");
     if ((rc = check_same_device(d, { rays })) || (rc = check_event(d, ev))) return rc;
-    if (width < 1 || height < 1 || frame < 0) return fail(PT_ERR_INVALID, "invalid image geometry or frame");
-    if ((long long)width * height > 0x7fffffffLL) return fail(PT_ERR_INVALID, "image too large");
-    const size_t bytes = (size_t)width * (size_t)height * sizeof(pt_ray);
+    uint64_t npix;   // the part of check_image that applies: one frame, no frame range, the whole image as one rank's one stripe
+    if ((rc = check_image("invalid image geometry or frame", width, height, frame, /*frame_count*/ 0, /*stripe_rows*/ 1, /*n_ranks*/ 1, /*rank*/ 0, npix)))
+        return rc;
+    const size_t bytes = (size_t)npix * sizeof(pt_ray);
     if (bytes > rays->bytes) return fail(PT_ERR_RANGE, "ray buffer holds %zu bytes, %d x %d rays need %zu", rays->bytes, width, height, bytes);
     if ((uintptr_t)rays->dptr & 15u) return fail(PT_ERR_INVALID, "the ray buffer must be 16-byte aligned");
     if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
@@ -1826,8 +1836,7 @@ extern "C" int pt_profile_reset(pt_device_t d)
 {
     int rc = use_device(d);
     if (rc) return rc;
-    if ((rc = enter_stream(d))) return rc;
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    if ((rc = enter_stream(d)) || (rc = stream_wait(d))) return rc;
     for (int k = 0; k < PT_PROF_KINDS; ++k) d->prof_used[k] = 0;
     return PT_OK;
 }
@@ -1837,8 +1846,7 @@ extern "C" int pt_profile_query(pt_device_t d, int kind, double* total_ms, uint6
     int rc = use_device(d);
     if (rc) return rc;
     if (kind < 0 || kind >= PT_PROF_KINDS || !total_ms || !launches) return fail(PT_ERR_INVALID, "bad profile query");
-    if ((rc = enter_stream(d))) return rc;
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    if ((rc = enter_stream(d)) || (rc = stream_wait(d))) return rc;
     double sum = 0.0;
     for (size_t i = 0; i < d->prof_used[kind]; ++i) {
         float ms = 0.f;
@@ -1860,9 +1868,7 @@ extern "C" int pt_bvh_snapshot(pt_device_t d, pt_bvh_info* info, void* records, 
     if (!info) return fail(PT_ERR_INVALID, "pt_bvh_snapshot: info is null");
     // deferred frames are work the caller has already asked for: they are submitted first (they may prepare a scene and build its
     // hierarchy), and only then is the state looked at -- the snapshot itself prepares and builds nothing
-    if ((rc = flush_pending(d))) return rc;
-    if ((rc = lanes_join(d))) return rc;
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    if ((rc = flush_pending(d)) || (rc = stream_wait(d))) return rc;
     if (!d->bvh_valid || !d->bvh) return fail(PT_ERR_INVALID, "no LBVH stands for the prepared scene");
     memset(info, 0, sizeof *info);
     info->records = (uint32_t)d->bvh_records;
@@ -1882,8 +1888,7 @@ extern "C" int pt_profile_query_union(pt_device_t d, int kind, double* union_ms)
     int rc = use_device(d);
     if (rc) return rc;
     if (kind < 0 || kind >= PT_PROF_KINDS || !union_ms) return fail(PT_ERR_INVALID, "bad profile query");
-    if ((rc = enter_stream(d))) return rc;
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    if ((rc = enter_stream(d)) || (rc = stream_wait(d))) return rc;
     // launches are recorded in enqueue order and two lanes alternate: [start, stop] intervals relative to the first start,
     // swept in order of their starts
     const size_t n = d->prof_used[kind];
@@ -1979,9 +1984,8 @@ static int launch_generate_colors(pt_device_s* d, const pt_launch_arg* a, int na
     const pt_render_params rp = reference_params(c[0], c[1], c[2], 1, m);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (d->opt_profile) {
-        int jrc = lanes_join(d);   // earlier renders are not part of this launch's time
+        int jrc = stream_enqueue(d);   // earlier renders are not part of this launch's time, and the lanes start behind e0
         if (jrc) return jrc;
-        d->main_dirty = true;      // ... and the lanes start behind e0
         HIP_TRY(hipEventCreate(&e0));
         HIP_TRY(hipEventCreate(&e1));
         HIP_TRY(hipEventRecord(e0, d->stream));

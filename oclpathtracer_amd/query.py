@@ -61,22 +61,7 @@ class RayCaster:
     def __init__(self, dev: adl.Device, triangles, *, num_triangles: Optional[int] = None):
         self.dev = dev
         self._lib = shim.load()
-        self._own_tbuf = not isinstance(triangles, adl.Buffer)
-        if self._own_tbuf:
-            tris = np.ascontiguousarray(triangles)
-            if tris.dtype != scene.TRIANGLE_DTYPE:
-                raise TypeError("triangles must be a scene.TRIANGLE_DTYPE array or an adl.Buffer")
-            self.num_triangles = len(tris)
-            self.tbuf = adl.Buffer(dev, len(tris), scene.TRIANGLE_DTYPE)
-            if len(tris):
-                self.tbuf.write(tris, len(tris))
-        else:
-            if num_triangles is None:
-                raise ValueError("num_triangles is required with an adl.Buffer of triangles")
-            self.num_triangles = int(num_triangles)
-            self.tbuf = triangles
-        if self.num_triangles < 0:
-            raise ValueError("num_triangles < 0")
+        self.tbuf, self.num_triangles, self._own_tbuf = scene.triangle_buffer(dev, triangles, num_triangles)
         self._host = {}    # role -> (adl.Buffer, capacity in bytes): device staging of the numpy path, grown on demand
         self._wrapped = {}  # (address, bytes) -> adl.Buffer: address ranges of caller tensors, wrapped with pt_buffer_wrap (oldest first)
         self._sync = None
@@ -198,9 +183,8 @@ class RayCaster:
         width, height, frame = int(width), int(height), int(frame)
         if width < 1 or height < 1 or frame < 0:
             raise ValueError("invalid image geometry or frame")
-        if camera is not None and not isinstance(camera, Camera):
-            raise TypeError("camera must be an oclpathtracer_amd.camera.Camera or None")
-        cam = ctypes.byref(camera.to_struct()) if camera is not None else None
+        struct = Camera.struct_of(camera)
+        cam = ctypes.byref(struct) if struct is not None else None
         n = width * height
         if as_tensor:
             import torch

@@ -78,7 +78,6 @@ class Renderer:
                  n_ranks: int = 1, rank: int = 0, stripe_rows: int = 16, fb_device_ptr: Optional[int] = None,
                  want_stats: bool = False, camera: Optional[Camera] = None):
         self.dev = dev
-        self.camera, self._cam = None, None
         self._set_camera(camera)
         self.width, self.height = int(width), int(height)
         self.n_ranks, self.rank, self.stripe_rows = int(n_ranks), int(rank), int(stripe_rows)
@@ -123,10 +122,8 @@ class Renderer:
         self.frames_done = frame_begin + frames
 
     def _set_camera(self, camera: Optional[Camera]) -> None:
-        if camera is not None and not isinstance(camera, Camera):
-            raise TypeError("camera must be an oclpathtracer_amd.camera.Camera or None")
+        self._cam = Camera.struct_of(camera)
         self.camera = camera
-        self._cam = camera.to_struct() if camera is not None else None
 
     def set_camera(self, camera: Optional[Camera]) -> None:
         """Render from ``camera`` from now on (None: the reference's).  A moved camera invalidates the running mean

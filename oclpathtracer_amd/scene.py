@@ -174,6 +174,26 @@ def load_model(path: str | None = None, materials=None):
     return triangles, materials
 
 
+def triangle_buffer(dev, triangles, num_triangles=None):
+    """``(buffer, count, owned)`` of what a caster or renderer was given as its triangles: a ``TRIANGLE_DTYPE`` array, uploaded to
+    a buffer of the caller's own, or an ``adl.Buffer`` that already holds them (``num_triangles`` then says how many count)."""
+    from . import adl
+
+    if isinstance(triangles, adl.Buffer):
+        if num_triangles is None:
+            raise ValueError("num_triangles is required with an adl.Buffer of triangles")
+        if int(num_triangles) < 0:
+            raise ValueError("num_triangles < 0")
+        return triangles, int(num_triangles), False
+    tris = np.ascontiguousarray(triangles)
+    if tris.dtype != TRIANGLE_DTYPE:
+        raise TypeError("triangles must be a scene.TRIANGLE_DTYPE array or an adl.Buffer")
+    buf = adl.Buffer(dev, max(len(tris), 1), TRIANGLE_DTYPE)
+    if len(tris):
+        buf.write(tris, len(tris))
+    return buf, len(tris), True
+
+
 def _splitmix64(n: int, seed: int) -> np.ndarray:
     """n successive splitmix64 outputs (vectorised, two buffers reused in place: fresh pages are
     what costs time on a 10^7-element array)."""

@@ -121,6 +121,45 @@ def test_the_staging_ring_is_sized_once_and_a_render_loop_allocates_nothing(corn
         adl.DeviceUtils.deallocate(dev)
 
 
+def test_the_workspace_account_does_not_depend_on_the_path_that_led_to_it(cornell, oracle):
+    """Every workspace allocation carries its own size from its allocation to its free, so what a handle reports depends on what it
+    holds, not on how it came to hold it: the Cornell box and then a 600-triangle soup through the LBVH (the prepared scene regrows
+    from 64 records to 600: records, packed table and hierarchy are freed and allocated again) leave the same account as the two
+    in the opposite order (no regrow).  Then the first checkpointed render adds the two checkpoint regions, once, the same on both."""
+    import scenes
+    from oclpathtracer_amd import adl
+
+    tris, mats = cornell
+    W = H = 64
+    todo = {"cornell": (tris, 0), "soup": (scenes.soup(600), 2)}
+    want = {k: oracle.render(t, mats, W, H, 2) for k, (t, _) in todo.items()}
+    want3 = oracle.render(tris, mats, W, H, 3)
+
+    def visit(order):
+        dev = adl.DeviceUtils.allocate(adl.TYPE_HIP, adl.Config(0))
+        try:
+            dev.reserveStaging(2 * MIB)
+            for k in order:
+                with options(dev, ACCEL=todo[k][1]):
+                    assert_fb_equal(render(dev, todo[k][0], mats, W, H, 2), want[k], "%s, in the order %s" % (k, order))
+            dev.waitForCompletion()
+            account = [dev.getWorkspaceMemory()]
+            for _ in range(2):
+                with options(dev, CHUNK_FRAMES=1):
+                    assert_fb_equal(render(dev, tris, mats, W, H, 3), want3, "three one-frame chunks after %s" % (order,))
+                dev.waitForCompletion()
+                account.append(dev.getWorkspaceMemory())
+            return account
+        finally:
+            adl.DeviceUtils.deallocate(dev)
+
+    a, b = visit(("cornell", "soup")), visit(("soup", "cornell"))
+    print("workspace bytes: %r (Cornell box, soup), %r (soup, Cornell box)" % (a, b))
+    assert a[0] == b[0], "the account depends on the order of the scenes"
+    assert a[1] > a[0] and a[1] - a[0] == b[1] - b[0], "the checkpoint regions of the first chunked render"
+    assert a[2] == a[1] and b[2] == b[1], "a second chunked render moved the account"
+
+
 def test_renders_return_before_the_gpu_has_finished_and_overlap(device, cornell, oracle):
     """Back-to-back renders into two framebuffers (the N-rank loop's two slots): enqueued in a fraction of their run time, and each
     image bit-exact although the next render's first launch ran beside its last, draining one."""
