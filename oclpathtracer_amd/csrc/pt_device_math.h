@@ -119,16 +119,104 @@ PTK_DEV void pt_div3(float& a0, float& a1, float& a2, float b)
     }
 }
 
+// A/B switches of pt_shade's short forms (tools/build_variant.sh: each item's contribution on its own; both on in every shipped build)
+#ifndef PT_GGX_FAST
+#define PT_GGX_FAST 1
+#endif
+#ifndef PT_NEAR1
+#define PT_NEAR1 1
+#endif
+
+// ---- single IEEE quotients of the GGX branch (pt_shade) in the same short form -------------------------------------
+// The window of every operand is [2^-60, 2^60): one unsigned compare each, which negative numbers, +-0, subnormals,
+// infinities and NaN fail.  Inside it y = RN(1/b) is in (2^-60, 2^60], q0 in (2^-120, 2^120) and r a multiple of
+// 2^-107 at least, so nothing leaves the normal range and the significand claim above carries over unchanged; that
+// pt_rcp_fast is exact on the whole of [2^-60, 1e20] -- beyond the [1e-8, 1e20] of tools/ubench -- is checked for every
+// binary32 of that range on gfx950 (pt_shade_check_kernel, mode 3: tests/test_gpu_shade_forms.py, tools/shade_forms.py).  The short
+// form is computed unconditionally and the generic division overwrites it behind an unlikely branch: the usual path
+// holds no copy that merges the two.
+#define PTK_DIV_FAST_LO 0x21800000u /* 2^-60 */
+#define PTK_DIV_FAST_HI 0x5d800000u /* 2^60 */
+PTK_DEV bool pt_div_in_window(unsigned bits) { return (bits - PTK_DIV_FAST_LO) < (PTK_DIV_FAST_HI - PTK_DIV_FAST_LO); }
+
+// a / b; `fast` promises that a and b are in the window
+PTK_DEV float pt_div_guarded(float a, float b, bool fast)
+{
+    float q = pt_div_markstein(a, b, pt_rcp_fast(b));
+    if (__builtin_expect(!fast, 0)) q = a / b;
+    return q;
+}
+
+// a / b for a numerator known to be +0 or in [2^-60, 2^60) (+0 gives q0 = r = q = +0, as 0 / b does)
+PTK_DEV float pt_div_by(float a, float b) { return pt_div_guarded(a, b, pt_div_in_window(__float_as_uint(b))); }
+
+PTK_DEV float pt_div(float a, float b)
+{
+    return pt_div_guarded(a, b, pt_div_in_window(__float_as_uint(a)) && pt_div_in_window(__float_as_uint(b)));
+}
+
+// q0 = a0 / b0 and q1 = a1 / b1 for 0 <= a0 <= a1 (or a1 NaN), two reciprocals (the reference rounds each quotient
+// once), one guard: the largest of (a1, b0, b1) and the smallest of (a0, b0, b1) bound all four
+PTK_DEV void pt_div_pair(float a0, float b0, float a1, float b1, float& q0, float& q1)
+{
+    const unsigned ua0 = __float_as_uint(a0), ua1 = __float_as_uint(a1), ub0 = __float_as_uint(b0), ub1 = __float_as_uint(b1);
+    const unsigned hi = max(max(ua1, ub0), ub1);  // v_max3_u32
+    const unsigned lo = min(min(ua0, ub0), ub1);  // v_min3_u32
+    const bool fast = hi < PTK_DIV_FAST_HI && lo >= PTK_DIV_FAST_LO;
+    q0 = pt_div_markstein(a0, b0, pt_rcp_fast(b0));
+    q1 = pt_div_markstein(a1, b1, pt_rcp_fast(b1));
+    if (__builtin_expect(!fast, 0)) {
+        q0 = a0 / b0;
+        q1 = a1 / b1;
+    }
+}
+
 // normalize(v) = v * (1.0f / sqrtf(dot(v,v)))   (both correctly rounded)
-PTK_DEV f3 normalize3(f3 a)
+PTK_DEV float pt_normalize_factor(float len2)
 {
     // one range check for both short sequences: len2 in [1e-15, 1e30] puts sqrt(len2) in
     // [3.2e-8, 1e15], inside the reciprocal's exact range [1e-8, 1e20]
-    const float len2 = dot3(a, a);
     float inv;
     if (__builtin_expect(len2 >= 1e-15f && len2 <= PTK_SQRT_FAST_MAX, 1)) inv = pt_rcp_fast(pt_sqrt_fast(len2));
     else inv = 1.0f / __builtin_sqrtf(len2);
-    return scale3(a, inv);
+    return inv;
+}
+
+PTK_DEV f3 normalize3(f3 a) { return scale3(a, pt_normalize_factor(dot3(a, a))); }
+
+// ---- the same two roundings for x within 2^-11 of 1, six fma and no transcendental -----------------------------------
+//   g = RN(x/2 + 1/2 + 2^-24)   >= sqrt(x): the residual rr = x - g^2 is never positive (and exact: g is within 2 ulp)
+//   s = RN(g + rr (1/2 + 2^-24))   == RN(sqrt(x)): 1/2 stands for 1 / (2 g), g within 2^-12 of 1, and the excess 2^-24 |rr|
+//                                  pushes an exact tie down, where the neglected -rr^2 / 8 puts the true value
+//   y = RN(2 - s (1 - 2^-24))   1 / s to an ulp, never below it: s = 1 - 2^-24 (all ones) gets 1 + 2^-23, not 1
+//   e = 1 - s y (exact), inv = RN(y + e y)   == RN(1 / s)
+// None of the constants is the obvious one and the argument above is a sketch: the claim rests on comparing EVERY binary32
+// of [1 - 2^-11, 1 + 2^-11] (12 289 values) with 1.0f / sqrtf(x) -- on the CPU (tests/test_shade_near1_cpu.py: fma is fma
+// everywhere) and on gfx950 (pt_shade_check_kernel, mode 1).  With 1/2 and 1 for the constants two values fail (1 - 2^-24 and
+// 1 - 2^-23); with these, the first failures lie just inside 1 -+ 2^-10.
+#define PTK_NEAR1_HALF_WIDTH 0x1p-11f
+PTK_DEV bool pt_is_near1(float x) { return __builtin_fabsf(x - 1.0f) <= PTK_NEAR1_HALF_WIDTH; }   // (x - 1 is exact near 1; NaN: no)
+
+PTK_DEV float pt_rsqrt_near1(float x)
+{
+    const float g = pt_fma(x, 0.5f, 0x1.000002p-1f);
+    const float rr = pt_fma(-g, g, x);
+    const float s = pt_fma(rr, 0x1.000002p-1f, g);
+    const float y = pt_fma(-s, 0x1.fffffep-1f, 2.0f);
+    const float e = pt_fma(-s, y, 1.0f);
+    return pt_fma(e, y, y);
+}
+
+// normalize(v) for a v that is a unit vector up to rounding in the usual case (a sum of orthonormal vectors with weights
+// sin cos, sin sin, cos; a reflected unit vector): when every lane of the wave that is here has its squared length near 1 --
+// one ballot, a wave-uniform branch, no per-lane merge -- the form above; otherwise normalize3's
+PTK_DEV f3 normalize3_unit(f3 a)
+{
+    const float len2 = dot3(a, a);
+#if PT_NEAR1
+    if (__builtin_expect(__ballot(!pt_is_near1(len2)) == 0ull, 1)) return scale3(a, pt_rsqrt_near1(len2));
+#endif
+    return scale3(a, pt_normalize_factor(len2));
 }
 
 // ---- RNG: GenerateColors.cl:47-71 -------------------------------------------------------

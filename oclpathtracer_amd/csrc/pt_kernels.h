@@ -238,6 +238,8 @@ hipError_t ptk_fill_i32(int32_t* dst, int32_t value, int n, hipStream_t s);
 hipError_t ptk_math(const float* in, float* out, int n, hipStream_t s);
 // the fold kernel's short forms against the literal operations (pt_fold_check_kernel); out: 6 counters
 hipError_t ptk_fold_check(unsigned long long* out, int mode, unsigned first, unsigned long long count, hipStream_t s);
+// pt_shade's short forms -- the guarded quotients, 1 / sqrt -- against the literal operations (pt_shade_check_kernel); out: 8 counters
+hipError_t ptk_shade_check(unsigned long long* out, int mode, unsigned first, unsigned long long count, hipStream_t s);
 // batched ray queries (pt_intersect_rays): t carries the search -- the prepared scene (tris, ntri), the filter of the table the
 // two-pass search runs over (quad_delta1 .. p1_hi, its anchor in cam.eye), the LBVH (bvh .. nbig, bvh_flags, bvh_stack_limit);
 // the other fields of t are not read

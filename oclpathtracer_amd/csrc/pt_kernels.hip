@@ -976,14 +976,19 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
         // radicands differ -- diffuse: sqrt(xi), sqrt(1-xi); GGX: sqrt((1-xi)/(xi(r^2-1)+1)), then
         // sqrt(max(0, 1-cos^2))
         float cos_arg = 1.0f - xi;
+#if PT_GGX_FAST
+        // (the numerator needs no guard: xi = (float)s * 2^-32 is in [0, 1], so 1 - xi is +0 or in [2^-24, 1])
+        if (type == 2) cos_arg = pt_div_by(cos_arg, xi * (rough * rough - 1.0f) + 1.0f);
+#else
         if (type == 2) cos_arg = cos_arg / (xi * (rough * rough - 1.0f) + 1.0f);
+#endif
         const float cosTheta = pt_sqrt(cos_arg);
         const float sin_arg = type == 2 ? pt_max(0.0f, 1.0f - cosTheta * cosTheta) : xi;
         const float sinTheta = pt_sqrt(sin_arg);
         f3 a = scale3(scale3(sv, cp), sinTheta);
         f3 b = scale3(scale3(tv, sp), sinTheta);
         f3 c = scale3(n, cosTheta);
-        f3 sdir = normalize3(add3(add3(a, b), c));
+        f3 sdir = normalize3_unit(add3(add3(a, b), c));
 
         f3 wi = sdir;
         f3 color = mk3(0.0f, 0.0f, 0.0f);
@@ -1001,9 +1006,19 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
             if (!(dwin * dwon < 0.0f)) {
                 float r2 = rough * rough;
                 const float gd = cosTheta * cosTheta * (r2 - 1.0f) + 1.0f;
+#if PT_GGX_FAST
+                // gd * gd reaches r^4 (4.1e-9 for the Cornell box's 0.008): inside the window of the short quotients
+                const float D = pt_div(r2 * PTK_INV_PI, gd * gd);  // pow(x, 2.0f) is x*x in PTSPEC (:177)
+                // pdf = D * cosTheta / (4 dot(wo, sdir)) and g = D / (4 dwin dwon) behind one guard: D * cosTheta <= D, for
+                // cosTheta <= 1 or D is NaN -- cos_arg = RN(a / b) with b = RN(1 + RN(xi c)) >= RN(1 - xi) = a for c = RN(r^2 - 1)
+                // in [-1, 0] (rounding is monotonic) and b >= 1 for any other c; a NaN cosTheta makes gd and with it D NaN
+                float g;
+                pt_div_pair(D * cosTheta, 4.0f * dot3(wo, sdir), D, 4.0f * dwin * dwon, pdf, g);
+#else
                 float D = r2 * PTK_INV_PI / (gd * gd);  // pow(x, 2.0f) is x*x in PTSPEC (:177)
                 pdf = D * cosTheta / (4.0f * dot3(wo, sdir));
                 float g = D / (4.0f * dwin * dwon);
+#endif
                 color = mk3(alb.x * g * 2.0f, alb.y * g * 2.0f, alb.z * g * 2.0f);
             }
         }
@@ -1020,7 +1035,7 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
                 finished = true;
             } else {
                 s.o = add3(p, scale3(wi, 0.01f));  // :257
-                s.d = normalize3(wi);
+                s.d = normalize3_unit(wi);
             }
         }
     }
@@ -2395,6 +2410,79 @@ __global__ __launch_bounds__(256) void pt_fold_check_kernel(unsigned long long* 
     if (seen) atomicAdd(out + 4, (unsigned long long)seen);
 }
 
+// pt_shade's short forms against the literal ones, operand by operand (tests/test_gpu_shade_forms.py).  Work-item i of mode
+//   1: x = the binary32 with bits first + i, within 2^-11 of 1: pt_rsqrt_near1(x) against 1.0f / sqrtf(x)                      -> out[1]
+//   2: the guarded quotients against "/".  Numerator and divisor binades 2^-61 .. 2^60 -- the window [2^-60, 2^60) and the first
+//      binade outside on each side -- in every combination (pair i / PT_SHADE_CHECK_SIGS), PT_SHADE_CHECK_SIGS pairs of
+//      significands each: all zeros and all ones in their four combinations, a +0 numerator, arbitrary ones.  pt_div and, where
+//      the numerator is what it asks for, pt_div_by; pt_div_pair with a smaller first numerator (the same times a factor in
+//      [0, 1]: 0, 1 and arbitrary ones) and a second divisor of an arbitrary binade                                           -> out[2]
+//   3: x = those bits, in [2^-60, 1e20]: pt_rcp_fast(x) against 1.0f / x                                                       -> out[3]
+// (There is no mode 0: it was the check of a 1 / sqrt for normalize3 seeded by the square-root iteration's h, which cannot be
+// exact -- DESIGN.md S3.)  out[4] counts the operands that were checked, out[5] those of mode 2 inside the window (the others take
+// the generic division by construction), out[6] is the largest failing operand's bits and out[7] the complement of the smallest's
+// (mode 2: the numerator's).
+#define PT_SHADE_CHECK_BINADES 122
+#define PT_SHADE_CHECK_SIGS 4096
+__global__ __launch_bounds__(256) void pt_shade_check_kernel(unsigned long long* __restrict__ out, int mode, unsigned first,
+                                                             unsigned long long count)
+{
+    unsigned bad = 0, seen = 0, inside = 0, worst_hi = 0, worst_lo = 0;
+    auto differ = [&](float got, float want, float operand) {
+        const bool same = (got != got && want != want) || __float_as_uint(got) == __float_as_uint(want);
+        if (!same) {
+            ++bad;
+            worst_hi = max(worst_hi, __float_as_uint(operand));
+            worst_lo = max(worst_lo, ~__float_as_uint(operand));
+        }
+    };
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        if (mode == 1) {
+            const float x = __uint_as_float(first + (unsigned)i);
+            if (!pt_is_near1(x)) continue;
+            ++seen;
+            differ(pt_rsqrt_near1(x), 1.0f / __builtin_sqrtf(x), x);
+        } else if (mode == 3) {
+            const float x = __uint_as_float(first + (unsigned)i);
+            if (!(x >= 0x1p-60f && x <= PTK_RCP_FAST_MAX)) continue;
+            ++seen;
+            differ(pt_rcp_fast(x), 1.0f / x, x);
+        } else {
+            const unsigned pair = (unsigned)(i / PT_SHADE_CHECK_SIGS), k = (unsigned)(i % PT_SHADE_CHECK_SIGS);
+            if (pair >= PT_SHADE_CHECK_BINADES * PT_SHADE_CHECK_BINADES) continue;
+            const unsigned ea = 127u - 61u + pair / PT_SHADE_CHECK_BINADES, eb = 127u - 61u + pair % PT_SHADE_CHECK_BINADES;
+            uint32_t h = pt_hash_u32(first ^ (uint32_t)i);
+            const unsigned ma = (unsigned)(pt_random_float(h) * 8388608.0f) & 0x7fffffu;
+            const unsigned mb = (unsigned)(pt_random_float(h) * 8388608.0f) & 0x7fffffu;
+            const unsigned mb2 = (unsigned)(pt_random_float(h) * 8388608.0f) & 0x7fffffu;
+            const unsigned eb2 = 127u - 61u + (unsigned)(pt_random_float(h) * (float)PT_SHADE_CHECK_BINADES) % PT_SHADE_CHECK_BINADES;
+            const float c = (k & 7u) == 5u ? 1.0f : (k & 7u) == 6u ? 0.0f : pt_random_float(h);
+            float a = __uint_as_float((ea << 23) | (k == 0u || k == 2u ? 0u : k == 1u || k == 3u ? 0x7fffffu : ma));
+            const float b = __uint_as_float((eb << 23) | (k == 0u || k == 3u ? 0u : k == 1u || k == 2u ? 0x7fffffu : mb));
+            const float b2 = __uint_as_float((eb2 << 23) | mb2);
+            if (k == 4u) a = 0.0f;
+            const bool a_in = pt_div_in_window(__float_as_uint(a)), b_in = pt_div_in_window(__float_as_uint(b));
+            ++seen;
+            inside += a_in && b_in;
+            differ(pt_div(a, b), a / b, a);
+            if (a_in || k == 4u) differ(pt_div_by(a, b), a / b, a);
+            const float a0 = a * c;
+            float q0, q1;
+            pt_div_pair(a0, b, a, b2, q0, q1);
+            differ(q0, a0 / b, a);
+            differ(q1, a / b2, a);
+        }
+    }
+    if (bad) {
+        atomicAdd(out + (mode == 1 ? 1 : mode == 3 ? 3 : 2), (unsigned long long)bad);
+        atomicMax(out + 6, (unsigned long long)worst_hi);
+        atomicMax(out + 7, (unsigned long long)worst_lo);
+    }
+    if (seen) atomicAdd(out + 4, (unsigned long long)seen);
+    if (inside) atomicAdd(out + 5, (unsigned long long)inside);
+}
+
 // ------------------------------------------------------------------------------------------
 // multi-GPU assembly, output stage, shim smoke-test kernel
 // ------------------------------------------------------------------------------------------
@@ -2932,6 +3020,14 @@ hipError_t ptk_fold_check(unsigned long long* out, int mode, unsigned first, uns
     if (count == 0) return hipSuccess;
     const unsigned long long want = (count + 255) / 256;
     hipLaunchKernelGGL(pt_fold_check_kernel, dim3((unsigned)(want < 65536ull ? want : 65536ull)), dim3(256), 0, s, out, mode, first, count);
+    return hipGetLastError();
+}
+
+hipError_t ptk_shade_check(unsigned long long* out, int mode, unsigned first, unsigned long long count, hipStream_t s)
+{
+    if (count == 0) return hipSuccess;
+    const unsigned long long want = (count + 255) / 256;
+    hipLaunchKernelGGL(pt_shade_check_kernel, dim3((unsigned)(want < 65536ull ? want : 65536ull)), dim3(256), 0, s, out, mode, first, count);
     return hipGetLastError();
 }
 

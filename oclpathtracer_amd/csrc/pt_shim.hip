@@ -48,7 +48,7 @@ extern "C" int pt_abi_version(void) { return PT_SHIM_ABI_VERSION; }
 // ------------------------------------------------------------------------------------------
 // objects
 // ------------------------------------------------------------------------------------------
-enum { KERNEL_GENERATE_COLORS = 0, KERNEL_FILL = 1, KERNEL_MATH = 2, KERNEL_FOLD_CHECK = 3, KERNEL_COUNT = 4 };
+enum { KERNEL_GENERATE_COLORS = 0, KERNEL_FILL = 1, KERNEL_MATH = 2, KERNEL_FOLD_CHECK = 3, KERNEL_SHADE_CHECK = 4, KERNEL_COUNT = 5 };
 
 struct pt_kernel_s {
     int id;
@@ -330,6 +330,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->kernels[KERNEL_FILL] = { KERNEL_FILL, "PtShimTest", "FillKernel" };
     d->kernels[KERNEL_MATH] = { KERNEL_MATH, "PtShimTest", "MathKernel" };
     d->kernels[KERNEL_FOLD_CHECK] = { KERNEL_FOLD_CHECK, "PtShimTest", "FoldCheckKernel" };
+    d->kernels[KERNEL_SHADE_CHECK] = { KERNEL_SHADE_CHECK, "PtShimTest", "ShadeCheckKernel" };
     bool ok = ws_malloc(d, d->bigtab, WS_BIGTAB) == hipSuccess && ws_malloc(d, d->bigidx, WS_BIGIDX) == hipSuccess &&
               ws_malloc(d, d->counters, WS_COUNTERS) == hipSuccess && ws_malloc(d, d->big_filter.p1tab, ws_big_p1tab()) == hipSuccess &&
               ws_malloc(d, d->det_bound_dev, WS_DETBOUND) == hipSuccess;
@@ -2063,6 +2064,30 @@ static int launch_fold_check(pt_device_s* d, const pt_launch_arg* a, int nargs, 
     return event_end(d, ev);
 }
 
+static int launch_shade_check(pt_device_s* d, const pt_launch_arg* a, int nargs, pt_event_s* ev)
+{
+    // ShadeCheckKernel(ulong* out, int mode, uint first, ulong count): pt_shade's short forms of "/" and 1 / sqrt against the
+    // literal operations, operand by operand (csrc/pt_kernels.hip, pt_shade_check_kernel); the work-item count of the launch is
+    // ignored, `count` operands are checked
+    if (nargs != 4 || !a[0].is_buffer || a[1].is_buffer || a[1].size != 4 || a[2].is_buffer || a[2].size != 4 || a[3].is_buffer ||
+        a[3].size != 8)
+        return fail(PT_ERR_ARGS, "ShadeCheckKernel expects (buffer, int, uint, ulong)");
+    pt_buffer_s* out = a[0].buffer;
+    if (!out || out->dev != d || out->bytes < 8 * sizeof(unsigned long long)) return fail(PT_ERR_ARGS, "ShadeCheckKernel: bad buffer");
+    int32_t mode;
+    uint32_t first;
+    uint64_t count;
+    memcpy(&mode, a[1].data, 4);
+    memcpy(&first, a[2].data, 4);
+    memcpy(&count, a[3].data, 8);
+    if (mode < 1 || mode > 3) return fail(PT_ERR_ARGS, "ShadeCheckKernel: mode %d", mode);
+    int rc = enter_stream(d);
+    if (rc || (rc = event_begin(d, ev))) return rc;
+    HIP_TRY(ptk_shade_check((unsigned long long*)out->dptr, mode, first, count, d->stream));
+    out->version++;
+    return event_end(d, ev);
+}
+
 extern "C" int pt_launch_2d(pt_device_t d, pt_kernel_t k, const pt_launch_arg* args, int nargs, int ntx, int nty, int lx,
                             int ly, pt_event_t ev, float* ms_out)
 {
@@ -2082,6 +2107,7 @@ extern "C" int pt_launch_2d(pt_device_t d, pt_kernel_t k, const pt_launch_arg* a
     case KERNEL_FILL: return launch_fill(d, args, nargs, n, ev);
     case KERNEL_MATH: return launch_math(d, args, nargs, n, ev);
     case KERNEL_FOLD_CHECK: return launch_fold_check(d, args, nargs, ev);
+    case KERNEL_SHADE_CHECK: return launch_shade_check(d, args, nargs, ev);
     default: return fail(PT_ERR_NOT_FOUND, "unknown kernel id");
     }
 }
