@@ -110,6 +110,11 @@ struct PtTraceParams {
     uint32_t slot_frames;         // S: frames per ring slot = frames per chunk (the render's last chunk may be shorter)
     uint32_t ring_phase;          // 0 or S: which slot the render's first chunk uses
     uint32_t ring_magic;          // floor(2^32 / 2S) + 1: (fl + ring_phase) % 2S by one v_mul_hi_u32 (exact below 65 536)
+    uint32_t rad1_off;            // SHORT form of a sample's radiance address (pt_ring_offset; chosen per render, pt_shim.hip: trace_params): rad1's
+                                  // byte offset from rad -- the two slots are one allocation -- when the whole ring is at most 4 GiB: a path then
+                                  // carries its record's byte offset from rad (unsigned 32 bits), worked out once where the sample starts, and the
+                                  // store is one global_store_dwordx3 against the scalar base.  0 = the LONG form: the ring is larger, a path carries
+                                  // its local pixel and the store forms the 64-bit address from fl
     int32_t max_bounces, ntri, nmat;
     int32_t stripe_rows, n_ranks, rank;
     uint32_t npix_local;

@@ -918,16 +918,32 @@ struct PtPath {
     f3 mask, L;     // throughput and radiance (:225-226)
     uint32_t seed;  // RNG state (:308)
     int bounce;     // loop index i of traceRays (:229)
-    unsigned lp;    // local pixel index
-    unsigned fl;    // frame index inside the chunk
+    unsigned ro;    // where the path's radiance goes, fixed from the sample's first ray to its last (pt_ring_offset): the byte offset of its record
+                    // from the ring's base -- or, when the ring is above 4 GiB (PtTraceParams::rad1_off == 0), its local pixel index
+    unsigned fl;    // frame counted from the render's first (the stop test of a checkpointed launch, the long form's ring slot)
 };
+
+// The record of (local pixel lp, frame `frame` of the render) in the staging ring, as a byte offset from PtTraceParams::rad: entry
+// (frame + phase) % 2S of the ring, the first S entries in slot 0, the others in slot 1, rad1_off bytes further.  Every input is fixed for
+// the render -- a carried path never leaves its render -- so this runs ONCE per sample, at full lane width with `frame` wave-uniform
+// (scalar work but for one multiply-add per lane), and not under the few-lane exec mask of every wave-bounce's store block.  Only the
+// short form (rad1_off != 0): the host chooses it when 2 x slot bytes <= 2^32, so slot * rad1_off + (entry * npix + lp) * 12 + 12 <=
+// 2^32 and nothing wraps.  (Read from the kernarg segment whichever the kernel, as the store's base is: no SGPR is held for it.)
+PTK_DEV unsigned pt_ring_offset(unsigned lp, unsigned frame)
+{
+    const pt_kargs_p KR = pt_kargs();
+    const unsigned fr = frame + KR->ring_phase, S = KR->slot_frames;
+    const unsigned r = fr - __umulhi(fr, KR->ring_magic) * (2u * S);
+    const bool upper = r >= S;
+    return (upper ? KR->rad1_off : 0u) + ((upper ? r - S : r) * KR->npix_local + lp) * 12u;
+}
 
 
 // ---- shade one bounce of a live path (:229-258); on path end store its radiance --------------------
 template <bool DET_BOUNDED, bool LATE>
 PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax, float hu, float hv, int hidx)
 {
-    const pt_kargs_p K = pt_kargs();  // tris, mats, nmat, max_bounces, rad, npix_local: read here, not kept in SGPRs
+    const pt_kargs_p K = pt_kargs();  // tris, mats, nmat, max_bounces: read here, not kept in SGPRs
     bool finished = false;
     if (hidx < 0) {
         const float bg = pt_max(0.45f, 0.0f);
@@ -946,15 +962,20 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
 
         // deferred HitRecord of the closest hit (:127-130): same values as writing it at every
         // acceptance, only the last one is read.
-        const float4 nid = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(PT_ARG(tris) + hidx) + 12);
+        // (both gathers: a 32-bit per-lane byte offset against the wave-uniform base -- global_load v, v_off, s[base:base+1] -- instead of a
+        // 64-bit per-lane address; ntri * 64 and nmat * 64 are below 2^32, pt_shim.hip: render_internal)
+        const float4 nid = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(PT_ARG(tris)) + (size_t)((unsigned)hidx * 64u) + 48);
         const f3 N = mk3(nid.x, nid.y, nid.z);
+        // never fault on a corrupt id: clamped to [0, nmat - 1] (the upper end is scalar work; max, then min: no branch)
+        const int nm1 = PT_ARG(nmat) - 1;
         int mid = __float_as_int(nid.w);
-        mid = mid < 0 ? 0 : (mid >= PT_ARG(nmat) ? PT_ARG(nmat) - 1 : mid);  // never fault on a corrupt id
+        mid = mid < 0 ? 0 : mid;
+        mid = mid > nm1 ? nm1 : mid;
         f3 p = add3(s.o, scale3(s.d, tmax));
         float w = 1.0f - hu - hv;
         f3 n = normalize3(add3(add3(scale3(N, hu), scale3(N, hv)), scale3(N, w)));
 
-        const PtRawMaterial* mat = PT_ARG(mats) + mid;  // :239
+        const PtRawMaterial* mat = reinterpret_cast<const PtRawMaterial*>(reinterpret_cast<const char*>(PT_ARG(mats)) + (size_t)((unsigned)mid * 64u));  // :239
         const float4 alb = *reinterpret_cast<const float4*>(mat->albedo);
         const float4 emi = *reinterpret_cast<const float4*>(mat->emissive);
         const float rough = mat->roughness;
@@ -1045,19 +1066,30 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
         // pmc_r02_summary.txt: 35.2 bytes of HBM traffic per sample against 41.0 with aligned 16-byte records --
         // the L2 cannot hold every partly filled line of the ~900 000 paths in flight until it is complete, and a
         // partly written sector costs a read-modify-write either way; fewer bytes written, fewer sectors touched)
-        // (frame f of the render: entry (f + phase) % 2S of the staging ring, the first S entries in one slot, the others in the other.
-        // Read from the kernarg segment here whichever the kernel: once per finished path, and six SGPRs the LBVH kernel does not have)
+        // Some lane finishes in practically every wave-bounce (a wave retires ~10 of its 64 paths per bounce), so this block issues every
+        // time, under an exec mask of a few lanes: the path brings its record's offset along (PtPath::ro, pt_ring_offset) and the block is
+        // max(L, 0) and one store against the ring's base.  (The base and the form are read from the kernarg segment here whichever the
+        // kernel -- scalar loads, wave-uniform branch -- and hold no SGPR through the loop.)
         const pt_kargs_p KR = pt_kargs();
-        const unsigned fr = s.fl + KR->ring_phase, S = KR->slot_frames;
-        const unsigned r = fr - __umulhi(fr, KR->ring_magic) * (2u * S);
-        float* out = (r < S ? KR->rad : KR->rad1) + ((size_t)(r < S ? r : r - S) * KR->npix_local + s.lp) * 3u;
+        float* const rad = KR->rad;
+        const unsigned rad1_off = KR->rad1_off;   // (both loads in flight together, one wait)
         // (records are 12 bytes apart: the vector type is declared with the 4-byte alignment the address really has)
         typedef float pt_f3v __attribute__((ext_vector_type(3), aligned(4)));
         pt_f3v v;
         v.x = pt_max(s.L.x, 0.0f);
         v.y = pt_max(s.L.y, 0.0f);
         v.z = pt_max(s.L.z, 0.0f);
-        *reinterpret_cast<pt_f3v*>(out) = v;  // one 12-byte store (global_store_dwordx3)
+        if (rad1_off != 0u) {
+            // one 12-byte store (global_store_dwordx3 v_off, v[..], s[base:base+1]); the offset is UNSIGNED: the upper slot of a 4 GiB ring lies above 2^31
+            *reinterpret_cast<pt_f3v*>(reinterpret_cast<char*>(rad) + (size_t)s.ro) = v;
+        } else {
+            // the long form (a ring above 4 GiB): s.ro is the local pixel; frame f of the render is entry (f + phase) % 2S of the ring, the
+            // first S entries in one slot, the others in the other
+            const unsigned fr = s.fl + KR->ring_phase, S = KR->slot_frames;
+            const unsigned r = fr - __umulhi(fr, KR->ring_magic) * (2u * S);
+            float* out = (r < S ? rad : KR->rad1) + ((size_t)(r < S ? r : r - S) * KR->npix_local + s.ro) * 3u;
+            *reinterpret_cast<pt_f3v*>(out) = v;
+        }
         alive = false;
     }
 }
@@ -1152,7 +1184,7 @@ PTK_DEV bool pt_queue_refill(const PtTraceParams& P, unsigned lane, PtWaveQueue&
 }
 
 // The parked-path record: 60 bytes, three float4 and three dwords, wherever a path waits --
-//   [0] o.xyz d.x   [1] d.yz mask.xy   [2] mask.z L.xyz   [3] seed, lp, fl | bounce << 16
+//   [0] o.xyz d.x   [1] d.yz mask.xy   [2] mask.z L.xyz   [3] seed, ro, fl | bounce << 16     (ro: PtPath::ro, where its radiance goes)
 // PtPathSlots says where: float4 word j of record k at A[j fs + k], dword j at W[j ws + k wk].  The pool of a wave (LDS) keeps three
 // float4 arrays of PT_POOL entries (conflict-free b128 accesses) and one array of dword triples.  (64-byte slots would put the
 // workgroup over 160 KB / 8: the LDS is what decides whether 8 workgroups -- 8 waves per SIMD -- fit a CU.)  A carry region keeps
@@ -1175,7 +1207,7 @@ PTK_DEV void pt_path_store(const PtPathSlots& S, unsigned k, const PtPath& s)
     S.vec(1, k) = make_float4(s.d.y, s.d.z, s.mask.x, s.mask.y);
     S.vec(2, k) = make_float4(s.mask.z, s.L.x, s.L.y, s.L.z);
     S.word(0, k) = s.seed;
-    S.word(1, k) = s.lp;
+    S.word(1, k) = s.ro;
     S.word(2, k) = s.fl | ((unsigned)s.bounce << 16);  // both below 65 536 (pt_render_frames checks: the ring has fewer frames)
 }
 
@@ -1188,7 +1220,7 @@ PTK_DEV void pt_path_load(const PtPathSlots& S, unsigned k, PtPath& s)
     s.mask = mk3(a1.z, a1.w, a2.x);
     s.L = mk3(a2.y, a2.z, a2.w);
     s.seed = S.word(0, k);
-    s.lp = S.word(1, k);
+    s.ro = S.word(1, k);
     s.fl = w2 & 0xffffu;
     s.bounce = (int)(w2 >> 16);
 }
@@ -1346,17 +1378,19 @@ PTK_DEV void pt_sample_begin(const PtTraceParams& P, pt_kargs_p K, unsigned x, u
     s.mask = mk3(1.0f, 1.0f, 1.0f);
     s.L = mk3(0.0f, 0.0f, 0.0f);
     s.bounce = 0;
-    s.lp = lp;
+    s.ro = K->rad1_off != 0u ? pt_ring_offset(lp, frame) : lp;   // (from the kernarg segment whichever the kernel, as the store reads it)
     s.fl = frame;
 }
 
 // FRESH phase: every lane is dead (its path parked); the next (up to) 64 samples of the wave's range start
 // in lanes 0.. at bounce 0 -- seed :308, camera ray :310
-// returns true when all 64 lanes started a primary ray
+// returns true when all 64 lanes started a primary ray; pix0 (wave-uniform): lane k's sample is local pixel pix0 + k -- what the primary
+// rays' candidate masks are indexed by (a path does not keep its pixel: PtPath::ro)
 template <bool LATE>
-PTK_DEV bool pt_start_fresh(const PtTraceParams& P, unsigned lane, PtWaveQueue& q, PtPath& s, bool& alive)
+PTK_DEV bool pt_start_fresh(const PtTraceParams& P, unsigned lane, PtWaveQueue& q, PtPath& s, bool& alive, unsigned& pix0)
 {
     const pt_kargs_p K = pt_kargs();
+    pix0 = q.pix;
     const unsigned avail = q.end - q.pix;
     const unsigned count = avail < 64u ? avail : 64u;
     const unsigned W = (unsigned)PT_ARG(width), SR = (unsigned)PT_ARG(stripe_rows);
@@ -1390,7 +1424,7 @@ PTK_DEV PtPath pt_path_idle()  // what a lane without a path holds
     PtPath s;
     s.o = mk3(0.0f, 0.0f, 0.0f); s.d = mk3(0.0f, 0.0f, 1.0f);
     s.mask = mk3(1.0f, 1.0f, 1.0f); s.L = mk3(0.0f, 0.0f, 0.0f);
-    s.seed = 0; s.bounce = 0; s.lp = 0; s.fl = 0;
+    s.seed = 0; s.bounce = 0; s.ro = 0; s.fl = 0;
     return s;
 }
 
@@ -1465,14 +1499,15 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
 
     for (;;) {
         PT_STAMP(t0);
-        bool primary = false;   // (wave-uniform) this bounce is a fresh wave of 64 primary rays
+        bool primary = false;   // (wave-uniform) this bounce is a fresh wave of 64 primary rays ...
+        unsigned pix0 = 0u;     // ... of the local pixels pix0 + lane
         if (__ballot(!alive) != 0ull) {
             if (pool_n == 0u) {
                 const int next = pt_queue_next<true>(P, lane, q, s, alive);
                 if (next != 0) {
                     pt_pool_push(pool, pool_n, s, alive);                // park every live path ...
                     if (next == 2) break;                                // ... for the next launch (a checkpoint) ...
-                    primary = pt_start_fresh<true>(P, lane, q, s, alive);      // ... or start 64 coherent primary rays
+                    primary = pt_start_fresh<true>(P, lane, q, s, alive, pix0);   // ... or start 64 coherent primary rays
                 }
             }
             pt_pool_pop(pool, pool_n, s, alive);           // dead lanes resume parked paths
@@ -1485,7 +1520,7 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         int hidx = -1;
         unsigned p2steps = 0;
         if (QUADS == 3 && DET_BOUNDED && primary && P.pmask != nullptr)
-            p2steps = pt_intersect_primary<DET_BOUNDED, LDS_TABLE>(T, P.tris, ntri, s.o, s.d, alive, tmax, hu, hv, hidx, P.pmask[s.lp], tl, lane,
+            p2steps = pt_intersect_primary<DET_BOUNDED, LDS_TABLE>(T, P.tris, ntri, s.o, s.d, alive, tmax, hu, hv, hidx, P.pmask[pix0 + lane], tl, lane,
                                                                    PT_VALIDATE_FILTER && P.stats ? P.stats + 2 : nullptr);
         else
             p2steps = pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>(T, P.tris, ntri, s.o, s.d, alive, tmax, hu, hv, hidx,

@@ -1365,6 +1365,10 @@ static PtTraceParams trace_params(const pt_device_s* d, const pt_buffer_s* mats,
     tp.ring_magic = (uint32_t)(0x100000000ull / (2u * (uint32_t)chunk)) + 1u;
     tp.rad = d->ring;
     tp.rad1 = reinterpret_cast<float*>(reinterpret_cast<char*>(d->ring.p) + d->ring_slot_bytes);
+    // the form of a sample's radiance address, once per render: a path carries its record's byte offset from the ring's base in 32 bits
+    // while the whole ring is at most 4 GiB (the last record then ends at or below 2^32); a larger ring (pt_device_reserve_staging takes any
+    // size) keeps the long form, which carries the local pixel and forms the 64-bit address at the store
+    tp.rad1_off = (uint64_t)PT_RING_SLOTS * d->ring_slot_bytes <= 0x100000000ull ? (uint32_t)d->ring_slot_bytes : 0u;
     tp.cam = cam;   // (its eye is the table's anchor bit for bit: prepare_search anchored the table there)
     return tp;
 }
@@ -1539,6 +1543,9 @@ static int render_internal(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats,
     int rc = check_same_device(d, { tris, mats, fb, stats });
     if (rc) return rc;
     if (rp.max_bounces < 1 || rp.num_triangles < 0 || rp.num_materials < 1) return fail(PT_ERR_INVALID, "invalid render parameters");
+    // shading gathers the hit's {n, id} and its material by 32-bit byte offsets into the 64-byte records (pt_shade): brute force or LBVH alike
+    if ((uint64_t)rp.num_triangles * 64u > 0xffffffffull || (uint64_t)rp.num_materials * 64u > 0xffffffffull)
+        return fail(PT_ERR_INVALID, "a scene has fewer than 2^26 triangles and 2^26 materials");
     for (int i = 0; i < 6; ++i)
         if (rp.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
     uint64_t npix64;
