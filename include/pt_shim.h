@@ -419,6 +419,61 @@ typedef struct pt_ao_params {
 int pt_render_ao(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t counts, pt_buffer_t image /* may be NULL */,
                  const pt_ao_params* params, const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
 
+/* ---- direct illumination -------------------------------------------------------------------------------------------
+ * The DirectIllumination case the reference's harness declares (test/RaytraceTest.cpp:297-299) with an empty body: the emitted
+ * light of the first hit plus one bounce of light sampled on the scene's emitters, composed of the reference's own steps.  Every
+ * operation is binary32 under the arithmetic contract of the renderer (dot, cross, normalize, sqrt and "/" as there).
+ * A sample of pixel gid = y * width + x in frame z:
+ *  1. seed = gid + hash(z) (GenerateColors.cl:308), the renderer's primary ray (o, d) (:263-288) and its closest hit from 1e20
+ *     (:137-154).  A miss gives L = max(0.45, 0) per channel (:235).
+ *  2. On a hit: m = materials[the triangle's id, clamped into [0, num_materials) as shading clamps it]; E = 1.0f * m.emissive *
+ *     3.0f (:241); p = o + d t (:127); n = the HitRecord normal (:128-130) turned to face the ray (:243); wo = -d.
+ *  3. With nl = num_lights > 0, for k = 0 .. K-1 in order, on the same seed, S starting at 0:
+ *     a. r0, r1, r2 = getRandomFloat(&seed), three times, always drawn whatever follows;
+ *     b. j = lights[min((uint32)(r0 * (float)nl), nl - 1)], clamped into [0, num_triangles): an index out of range in the list
+ *        is defined behaviour, never an out-of-range load;
+ *     c. of triangle j: e1 = p2 - p1, e2 = p3 - p1 (:92-93), N = cross(e2, e1) (:123), nj = normalize(N), area = 0.5f *
+ *        sqrt(dot(N, N)); su = sqrt(r1), b1 = 1.0f - su, b2 = r2 * su, q = (p1 + e1 * b1) + e2 * b2;
+ *     d. dv = q - p, d2 = dot(dv, dv), dist = sqrt(d2), wi = normalize(dv), cs = dot(wi, n), cl = fabs(dot(wi, nj)) (emitters are
+ *        two-sided, as :241 adds emission whichever side is hit).  The sample contributes only when cs > 0.0f && cl > 0.0f
+ *        (false for NaN: q == p, a light of no area) and m.type is 1 or 2 (:220);
+ *     e. the BRDF value: type 1: f = m.albedo * INV_PI (:203); type 2: wh = normalize(wo + wi), ct = dot(wh, n), D =
+ *        distributionGGX(ct, m.roughness) (:174-178); f = 0 when dot(wi, n) * dot(wo, n) < 0 (:211), otherwise g = D / (4.0f *
+ *        dot(wi, n) * dot(wo, n)) and f = (m.albedo * g) * 2.0f (:217);
+ *     f. w = ((cs * cl) / d2) * (area * (float)nl); c = (f * (emissive of materials[id of j, clamped] * 3.0f)) * w per channel;
+ *     g. the shadow ray getRay(p + wi * 0.01f, wi) (:257) with limit tl = min(dist - 0.02f, 1e20f) is occluded when any triangle
+ *        passes the exact test (:96-125) at 0 < t < tl -- the any-hit search of pt_occluded_rays; tl <= 0 searches nothing and is
+ *        open.  (The light lies at t ~ dist - 0.01, beyond the limit: no index is excluded.)  An open ray adds c to S.  A sample
+ *        that does not contribute casts no ray.
+ *  4. L = max(E + S / (float)K, 0) per channel with the reference's max; with num_lights = 0, S = 0: the renderer's radiance at
+ *     max_bounces = 1, bit for bit.
+ *  5. L goes to samples[frame - chunk's first][local pixel][3] (floats) and is folded into the framebuffer by the renderer's own
+ *     fold, frames ascending: float4, the gamma-encoded running mean (:314-321), in the stripe layout of pt_render_params.
+ *     frame_begin = 0 starts afresh; later frames resume the mean the buffer holds.
+ * Sums are ordered per sample and the fold per pixel: the image does not depend on which lane or launch ran what.
+ * samples: the caller's workspace, at least one frame (local pixels x 12 bytes).  The call walks its frames in chunks of
+ * min(frames left, floor(bytes / (local pixels x 12)), floor((2^31 - 1) / local pixels)) frames: one launch and one fold per
+ * chunk, on the handle's stream.  Direct renders behave like AO renders and queries: behind renders in flight, asynchronous (ev);
+ * the scene, LBVH and filter tables as a query uses them (no anchor move, no rebuild); once the scene is prepared no allocation
+ * and no wait; PT_OPT_ACCEL and PT_OPT_QUAD_FILTER choose the search; a cut-short LBVH search raises PT_ERR_TRAVERSAL (deferred).
+ * num_triangles = 0 renders the background.
+ * Errors come before anything is enqueued and leave the framebuffer untouched: PT_ERR_INVALID for a field out of range
+ * (num_materials < 1, light_samples outside 1..256, num_lights < 0 or >= 2^24 -- (float)nl must be exact --, num_lights > 0 with
+ * lights NULL), a reserved field not 0, a camera pt_camera_derive rejects, the framebuffer not 16-byte or samples / lights not
+ * 4-byte aligned, samples, framebuffer and lights overlapping, a buffer of another device, frame_begin + frame_count or width x
+ * height above 2^31 - 1; PT_ERR_RANGE for a buffer too small. */
+typedef struct pt_direct_params {
+    int32_t width, height, frame_begin, frame_count;   /* the image; frame_begin 0 = the framebuffer is overwritten; frame_count 0 enqueues nothing */
+    int32_t num_triangles, num_materials, num_lights;  /* num_triangles >= 0, num_materials >= 1, 0 <= num_lights < 2^24 */
+    int32_t light_samples;                             /* K, 1..256 */
+    int32_t stripe_rows, n_ranks, rank;                /* image sharding exactly as pt_render_params */
+    int32_t reserved[5];                               /* must be 0 */
+} pt_direct_params;                                    /* 64 bytes */
+int pt_render_direct(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                     pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, pt_buffer_t samples /* workspace */,
+                     pt_buffer_t framebuffer, const pt_direct_params* params, const pt_camera* cam /* NULL = the reference's */,
+                     pt_event_t ev);
+
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.
  * pt_profile_query synchronises the stream and returns the summed duration and launch count

@@ -275,6 +275,24 @@ struct PtAoParams {
 hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s);
 // image[i] = float4(a, a, a, 1) of counts[i] = {open, hits}: a = open / (K hits), miss_value when hits = 0
 hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s);
+// direct illumination (pt_render_direct): t carries the search and the image geometry as PtAoParams::t does, and the materials
+// (mats, nmat >= 1); cam is the camera.  One launch writes the radiance of nitems samples, frame-major from frame0 on, 12 bytes each,
+// which ptk_fold folds into the framebuffer (PtFoldParams::rad = samples, frame_begin = frame0)
+struct PtDirectParams {
+    PtTraceParams t;
+    PtCamera cam;
+    const int32_t* lights;        // [nl] triangle indices, clamped into [0, ntri) where they are used; not read when nl = 0
+    float* samples;               // [nitems][3] max(E + S / K, 0)
+    uint32_t npix;                // local pixels
+    uint32_t nitems;              // samples of this launch: item = f * npix + local pixel (< 2^31)
+    int32_t frame0;               // the frame of item 0
+    int32_t K;                    // light samples per hit
+    int32_t nl;                   // lights in the list, 0 .. 2^24 - 1 ((float)nl is exact)
+};
+// bvh_blocks: the persistent grid of the LBVH kernel, CUs x ptk_direct_bvh_blocks_per_cu -- the kernel runs on the driver but at four waves
+// per SIMD, so ptk_query_bvh_blocks_per_cu's premise (five waves) does not hold for it
+hipError_t ptk_direct(const PtDirectParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s);
+int ptk_direct_bvh_blocks_per_cu(void);
 // rays[2 gid], rays[2 gid + 1] = the pt_ray of pixel gid, frame `frame` (the renderer's sample start) for the camera cam
 hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s);
 // dynamic LDS of a trace workgroup (pt_kernels.hip: pt_lds_total, pt_bvh_lds_total)

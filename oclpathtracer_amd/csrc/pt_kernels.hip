@@ -2826,17 +2826,23 @@ __global__ __launch_bounds__(256) void pt_camera_rays_kernel(const PtCamera cam,
 // (n, &seed) (:161-172) about the HitRecord normal turned to face the ray (:243), each an any-hit search at 0 < t < min(radius, 1e20).
 // counts[lp] += open | hits << 32: hits = 1 for a primary hit, open = the occlusion rays that hit nothing.
 
-// the sample's start: its local pixel and its primary ray (pt_sample_begin's seed and camera ray, for the AO parameters)
-PTK_DEV void pt_ao_begin(const PtAoParams& A, unsigned item, unsigned& lp, uint32_t& seed, f3& o, f3& d)
+// the start of sample `item` of a frame-major launch over npix local pixels from frame frame0 on (item = f * npix + local pixel): its
+// local pixel and its primary ray (pt_sample_begin's seed and camera ray) -- ambient occlusion and direct illumination alike
+PTK_DEV void pt_item_begin(const PtTraceParams& P, const PtCamera& cam, unsigned npix, int frame0, unsigned item, unsigned& lp, uint32_t& seed,
+                           f3& o, f3& d)
 {
-    const PtTraceParams& P = A.t;
-    const unsigned f = item / A.npix;
-    lp = item - f * A.npix;
+    const unsigned f = item / npix;
+    lp = item - f * npix;
     unsigned x, grow;
     pt_pixel_xy<false>(P, nullptr, lp, x, grow);
     const unsigned gid = grow * (unsigned)P.width + x;
-    seed = gid + pt_hash_u32((uint32_t)(A.frame0 + (int)f));
-    pt_generate_ray((int)x, (int)grow, P.inv_width, P.inv_height, P.aspect, PT_CAM_K(A.cam), seed, o, d);
+    seed = gid + pt_hash_u32((uint32_t)(frame0 + (int)f));
+    pt_generate_ray((int)x, (int)grow, P.inv_width, P.inv_height, P.aspect, PT_CAM_K(cam), seed, o, d);
+}
+
+PTK_DEV void pt_ao_begin(const PtAoParams& A, unsigned item, unsigned& lp, uint32_t& seed, f3& o, f3& d)
+{
+    pt_item_begin(A.t, A.cam, A.npix, A.frame0, item, lp, seed, o, d);
 }
 
 // the primary hit's point and normal: the HitRecord's, turned to face the ray as at :243
@@ -2965,6 +2971,222 @@ __global__ __launch_bounds__(256) void pt_ao_resolve_kernel(const uint2* __restr
     const uint2 c = counts[i];
     const float a = c.y > 0u ? (float)c.x / (float)(K * c.y) : miss_value;
     image[i] = make_float4(a, a, a, 1.0f);
+}
+
+// ------------------------------------------------------------------------------------------
+// direct illumination (pt_render_direct)
+// ------------------------------------------------------------------------------------------
+// One work item is one sample, as for ambient occlusion (pt_item_begin): the renderer's primary ray and its closest hit from tmax
+// 1e20; a miss stores the background (:235).  On a hit, K light samples on the same seed (include/pt_shim.h states every expression
+// and its order): three uniforms, a light triangle of the list, a point on it, the BRDF value at the direction to it (pt_shade's
+// expressions for f, not its sampling), the geometry term, and a shadow ray getRay(p + wi 0.01, wi) (:257) that an any-hit search
+// at 0 < t < min(dist - 0.02, 1e20) finds occluded or open.  samples[item] = max(E + S / K, 0), 12 bytes; pt_fold_kernel folds them.
+// Between the rays of a sample a lane holds the surface (p, n, wo), the hit's material INDEX -- the material is gathered again
+// per light sample and for E, which costs a load and saves eight registers across the searches -- the sum S and the contribution
+// c that the ray under way decides about.
+
+typedef float pt_f3v __attribute__((ext_vector_type(3), aligned(4)));   // (records are 12 bytes apart)
+
+PTK_DEV void pt_direct_store(const PtDirectParams& D, unsigned item, const f3& L)
+{
+    pt_f3v v;
+    v.x = L.x; v.y = L.y; v.z = L.z;
+    *reinterpret_cast<pt_f3v*>(D.samples + (size_t)item * 3u) = v;
+}
+
+// a 64-byte record's 16 bytes at byte offset `off`: a 32-bit per-lane offset against the wave-uniform base (pt_shade's gathers; the
+// host keeps ntri * 64 and nmat * 64 below 2^32)
+PTK_DEV float4 pt_rec16(const void* base, unsigned index, unsigned off)
+{
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + (size_t)(index * 64u + off));
+}
+
+PTK_DEV unsigned pt_clamp_index(int v, int n)   // into [0, n - 1], n >= 1: never an out-of-range load
+{
+    v = v < 0 ? 0 : v;
+    return (unsigned)(v > n - 1 ? n - 1 : v);
+}
+
+// the primary hit: the HitRecord's point and normal, the normal turned to face the ray (:243), wo = -d, the material's index
+// clamped as pt_shade clamps it
+PTK_DEV void pt_direct_surface(const PtDirectParams& D, const f3& o, const f3& d, float t, float hu, float hv, int hidx, f3& p, f3& n, f3& wo,
+                               unsigned& mid)
+{
+    const float id = pt_hit_record(D.t.tris, hidx, o, d, t, hu, hv, p, n);
+    n = dot3(n, d) < 0.0f ? n : scale3(n, -1.0f);
+    wo = neg3(d);
+    mid = pt_clamp_index(__float_as_int(id), D.t.nmat);
+}
+
+// Light sample k of the sample at (p, n, wo) on material mid (steps a-g of the contract).  True when it contributes: then c is its
+// contribution if the shadow ray (o, d) is open, and tl the ray's limit (not above 0: nothing is searched, the ray is open).  The
+// three uniforms are drawn whatever follows.  The quotients are pt_div's: the short form inside its guarded window, the generic
+// division outside it -- the IEEE quotient either way.
+PTK_DEV bool pt_direct_light(const PtDirectParams& D, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed, f3& c, f3& o, f3& d,
+                             float& tl)
+{
+    const float r0 = pt_random_float(seed), r1 = pt_random_float(seed), r2 = pt_random_float(seed);
+    const float nlf = (float)D.nl;
+    unsigned li = (unsigned)(r0 * nlf);
+    li = li > (unsigned)D.nl - 1u ? (unsigned)D.nl - 1u : li;
+    const unsigned j = pt_clamp_index(D.lights[li], D.t.ntri);
+    // the light's prepared record: p1, e1 = p2 - p1, e2 = p3 - p1, N = cross(e2, e1) (:92-93, :123; computed once per upload, the same bits)
+    const float4 ra = pt_rec16(D.t.tris, j, 0u), rb = pt_rec16(D.t.tris, j, 16u), rc = pt_rec16(D.t.tris, j, 32u), nid = pt_rec16(D.t.tris, j, 48u);
+    const f3 p1 = mk3(ra.x, ra.y, ra.z), e1 = mk3(ra.w, rb.x, rb.y), e2 = mk3(rb.z, rb.w, rc.x), N = mk3(nid.x, nid.y, nid.z);
+    const float N2 = dot3(N, N);
+    const f3 nj = scale3(N, pt_normalize_factor(N2));
+    const float area = 0.5f * pt_sqrt(N2);
+    const float su = pt_sqrt(r1), b1 = 1.0f - su, b2 = r2 * su;
+    const f3 q = add3(add3(p1, scale3(e1, b1)), scale3(e2, b2));
+    const f3 dv = sub3(q, p);
+    const float d2 = dot3(dv, dv);
+    const float dist = pt_sqrt(d2);
+    const f3 wi = scale3(dv, pt_normalize_factor(d2));
+    const float cs = dot3(wi, n), cl = __builtin_fabsf(dot3(wi, nj));
+    if (!(cs > 0.0f && cl > 0.0f)) return false;   // (false for NaN: q == p, a light of no area)
+    const float4 alb = pt_rec16(D.t.mats, mid, 0u), rt = pt_rec16(D.t.mats, mid, 32u);   // albedo | roughness, type
+    const int type = __float_as_int(rt.y);
+    f3 f;
+    if (type == 1) {   // :203
+        f = mk3(alb.x * PTK_INV_PI, alb.y * PTK_INV_PI, alb.z * PTK_INV_PI);
+    } else if (type == 2) {   // :205-217 at the half vector of wo and wi
+        const f3 wh = normalize3(add3(wo, wi));
+        const float ct = dot3(wh, n);
+        const float r2g = rt.x * rt.x;
+        const float gd = ct * ct * (r2g - 1.0f) + 1.0f;
+        const float Dg = pt_div(r2g * PTK_INV_PI, gd * gd);   // pow(x, 2.0f) is x*x in PTSPEC (:177)
+        const float dwon = dot3(wo, n);
+        if (cs * dwon < 0.0f) {   // :211
+            f = mk3(0.0f, 0.0f, 0.0f);
+        } else {
+            const float g = pt_div(Dg, 4.0f * cs * dwon);
+            f = mk3(alb.x * g * 2.0f, alb.y * g * 2.0f, alb.z * g * 2.0f);
+        }
+    } else {
+        return false;   // :220
+    }
+    const float4 emj = pt_rec16(D.t.mats, pt_clamp_index(__float_as_int(nid.w), D.t.nmat), 16u);
+    const float w = pt_div(cs * cl, d2) * (area * nlf);
+    c = mk3((f.x * (emj.x * 3.0f)) * w, (f.y * (emj.y * 3.0f)) * w, (f.z * (emj.z * 3.0f)) * w);
+    o = add3(p, scale3(wi, 0.01f));   // :257
+    d = normalize3(wi);
+    tl = dist - 0.02f;
+    tl = tl < 1e20f ? tl : 1e20f;
+    return true;
+}
+
+// the sample's radiance max(E + S / K, 0), E = 1.0f * emissive * 3.0f of the hit's material (:241)
+PTK_DEV f3 pt_direct_radiance(const PtDirectParams& D, unsigned mid, const f3& S)
+{
+    const float4 emi = pt_rec16(D.t.mats, mid, 16u);
+    const float Kf = (float)D.K;
+    return mk3(pt_max(emi.x * 3.0f + S.x / Kf, 0.0f), pt_max(emi.y * 3.0f + S.y / Kf, 0.0f), pt_max(emi.z * 3.0f + S.z / Kf, 0.0f));
+}
+
+// brute force: one wave = 64 consecutive samples; the primary search, then the K shadow rays of the lanes whose light sample
+// contributes, all in step (pt_ao_kernel's shape); a light sample no lane of the wave casts a ray for costs no search
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDirectParams D)
+{
+    const PtTraceParams& P = D.t;
+    const unsigned lane = pt_lane_id();
+    const int ntri = P.ntri;
+    PtTail tl = pt_table_wg_setup<LDS_TABLE>(P, lane);
+    const f3 anchor = mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]);
+    const unsigned item = pt_wave() * 64u + lane;
+    const bool act = item < D.nitems;
+    unsigned lp = 0u;
+    uint32_t seed = 0u;
+    f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f);
+    if (act) pt_item_begin(P, D.cam, D.npix, D.frame0, item, lp, seed, o, d);
+    float tmax = 1e20f, hu = 0.0f, hv = 0.0f;
+    int hidx = -1;
+    pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, act, tmax, hu, hv, hidx,
+                                                         P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+    const bool hit = act & (hidx >= 0);
+    const float bg = pt_max(0.45f, 0.0f);   // :235
+    f3 L = mk3(bg, bg, bg);
+    if (__ballot(hit) != 0ull) {
+        f3 p = o, n = d, wo = d, S = mk3(0.0f, 0.0f, 0.0f);
+        unsigned mid = 0u;
+        if (hit) pt_direct_surface(D, o, d, tmax, hu, hv, hidx, p, n, wo, mid);
+        for (int k = 0; k < D.K && D.nl > 0; ++k) {
+            f3 c = mk3(0.0f, 0.0f, 0.0f);
+            float tlim = 0.0f;
+            bool cast = false;
+            if (hit) cast = pt_direct_light(D, p, n, wo, mid, seed, c, o, d, tlim);
+            const bool live = cast & (tlim > 0.0f);
+            bool occluded = false;
+            if (__ballot(live) != 0ull) {
+                float t = live ? tlim : 0.0f, su = 0.0f, sv = 0.0f;
+                int sidx = -1;
+                pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, live, t, su, sv, sidx,
+                                                                     P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+                occluded = live & (sidx >= 0) & (t < tlim);   // pt_query_store's occlusion test
+            }
+            if (cast & !occluded) S = add3(S, c);
+        }
+        if (hit) L = pt_direct_radiance(D, mid, S);
+    }
+    if (act) pt_direct_store(D, item, L);
+}
+
+// LBVH (pt_bvh_drive): one item = one sample; the lane runs its searches one after the other -- the primary ray's closest search,
+// then the any-hit searches of the light samples that contribute -- and is free when the sample is stored.  A light sample that
+// does not contribute is passed over inside next_ray: it costs the lane no refill
+struct PtDirectWork {
+    static constexpr bool ANY = true;
+    const PtDirectParams& D;
+    unsigned n;
+    int k;           // the current ray: -1 = the primary, 0 .. K-1 = the shadow ray of light sample k
+    unsigned item, mid;
+    uint32_t seed;
+    float tl;        // the shadow ray's limit
+    f3 o, d, p, nrm, wo, S, c;
+    PTK_DEV void begin(unsigned item_)
+    {
+        unsigned lp;
+        item = item_;
+        pt_item_begin(D.t, D.cam, D.npix, D.frame0, item, lp, seed, o, d);
+        k = -1;
+    }
+    PTK_DEV bool next_ray(const PtBvhLane& L)
+    {
+        if (k < 0) {
+            if (L.hidx < 0) {
+                const float bg = pt_max(0.45f, 0.0f);   // :235
+                pt_direct_store(D, item, mk3(bg, bg, bg));
+                return false;
+            }
+            pt_direct_surface(D, o, d, L.tmax, L.hu, L.hv, L.hidx, p, nrm, wo, mid);
+            S = mk3(0.0f, 0.0f, 0.0f);
+        } else if (L.hidx < 0) {   // (an any-hit search: L.hidx >= 0 alone says occluded; a ray that searched nothing is open)
+            S = add3(S, c);
+        }
+        if (D.nl > 0)
+            while (++k < D.K)
+                if (pt_direct_light(D, p, nrm, wo, mid, seed, c, o, d, tl)) return true;
+        pt_direct_store(D, item, pt_direct_radiance(D, mid, S));
+        return false;
+    }
+    PTK_DEV const f3& org() const { return o; }
+    PTK_DEV const f3& dir() const { return d; }
+    PTK_DEV float limit() const { return k < 0 ? 1e20f : tl; }
+    PTK_DEV bool live() const { return k < 0 || tl > 0.0f; }
+    PTK_DEV bool any() const { return k >= 0; }
+};
+
+// Four waves per SIMD (128 VGPRs), not the five of the driver's other kernels: a sample's state between its rays is 25 registers
+// against ambient occlusion's 16, and at five waves (96 VGPRs) the kernel spills 19 of them (profiles/direct/kernel_resources.txt).
+// Its persistent grid is therefore its own figure, ptk_direct_bvh_blocks_per_cu, not ptk_query_bvh_blocks_per_cu
+#define PT_DIRECT_BVH_WAVES 4
+template <bool DET_BOUNDED, int BIGQ>
+__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_DIRECT_BVH_WAVES, PT_DIRECT_BVH_WAVES)))
+void pt_direct_bvh_kernel(const PtDirectParams D)
+{
+    const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
+    PtDirectWork W = { D, D.nitems, -1, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0 };
+    pt_bvh_drive<DET_BOUNDED, BIGQ>(D.t, W);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3152,6 +3374,19 @@ hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream
     else kernel = m.det_bounded ? pt_ao_kernel<true, 2, 0> : pt_ao_kernel<false, 2, 0>;
     return pt_launch_search(kernel, a, a.nitems, m.bvh, bvh_blocks, s);
 }
+
+hipError_t ptk_direct(const PtDirectParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
+{
+    if (a.nitems == 0) return hipSuccess;
+    const bool q3 = m.quads == 3;
+    void (*kernel)(const PtDirectParams);
+    if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_direct_bvh_kernel<true, 3>, pt_direct_bvh_kernel<true, 0>, pt_direct_bvh_kernel<false, 0>);
+    else if (a.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_direct_kernel<true, 1, 3>, pt_direct_kernel<true, 1, 0>, pt_direct_kernel<false, 1, 0>);
+    else kernel = m.det_bounded ? pt_direct_kernel<true, 2, 0> : pt_direct_kernel<false, 2, 0>;
+    return pt_launch_search(kernel, a, a.nitems, m.bvh, bvh_blocks, s);
+}
+
+int ptk_direct_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_direct_bvh_kernel<true, 3>, ptk_trace_bvh_lds_bytes()); }
 
 hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s)
 {

@@ -136,6 +136,7 @@ struct pt_device_s {
     uint64_t bvh_builds;        // LBVH builds so far (PT_OPT_BVH_BUILD_COUNT)
     int bvh_blocks_per_cu;
     int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query and ambient-occlusion kernels (pt_bvh_drive)
+    int direct_bvh_blocks_per_cu;  // ... and of the direct-illumination kernel, which runs at four waves per SIMD
     unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
     unsigned int* trav_dev;  // ... as the device addresses it
     // ---- fused-render workspace: the STREAMING renderer (render_part, plan_chunks, the ring).  A render walks its frames in chunks of
@@ -356,6 +357,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->blocks_per_cu = ptk_trace_blocks_per_cu(36);
     d->bvh_blocks_per_cu = ptk_trace_bvh_blocks_per_cu();
     d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
+    d->direct_bvh_blocks_per_cu = ptk_direct_bvh_blocks_per_cu();
     *out = d;
     return PT_OK;
 }
@@ -1755,6 +1757,91 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
     if (image) HIP_TRY(ptk_ao_resolve((const uint2*)counts->dptr, (float4*)image->dptr, npix, (uint32_t)a.rays_per_sample, a.miss_value, d->stream));
     counts->version++;
     if (image) image->version++;
+    return event_end(d, ev);
+}
+
+// ---- direct illumination (include/pt_shim.h) -----------------------------------------------------------------------------------
+static_assert(sizeof(pt_direct_params) == 64, "pt_direct_params layout");
+
+extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
+                                pt_buffer_t framebuffer, const pt_direct_params* params, const pt_camera* cam, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
+    const pt_direct_params a = *params;
+    PtCamera c = reference_camera();
+    if (cam && (rc = camera_derive(cam, &c))) return rc;
+    if (!triangles || !materials || !samples || !framebuffer) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { triangles, materials, lights, samples, framebuffer })) || (rc = check_event(d, ev))) return rc;
+    if (a.num_triangles < 0 || a.num_materials < 1 || a.num_lights < 0 || a.light_samples < 1 || a.light_samples > 256)
+        return fail(PT_ERR_INVALID, "invalid direct-illumination parameters");
+    if (a.num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
+    if (a.num_lights > 0 && !lights) return fail(PT_ERR_INVALID, "num_lights > 0 needs a light list");
+    // the light's record and the materials are gathered by 32-bit byte offsets into the 64-byte records, as shading gathers them
+    if ((uint64_t)a.num_triangles * 64u > 0xffffffffull || (uint64_t)a.num_materials * 64u > 0xffffffffull)
+        return fail(PT_ERR_INVALID, "a scene has fewer than 2^26 triangles and 2^26 materials");
+    for (int i = 0; i < 5; ++i)
+        if (a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    uint64_t npix64;
+    if ((rc = check_image("invalid direct-illumination parameters", a.width, a.height, a.frame_begin, a.frame_count, a.stripe_rows, a.n_ranks, a.rank, npix64)))
+        return rc;
+    const uint32_t npix = (uint32_t)npix64;
+    const size_t frame_bytes = (size_t)npix * 12, fb_bytes = (size_t)npix * sizeof(float4), light_bytes = (size_t)a.num_lights * sizeof(int32_t);
+    if ((rc = check_triangles(triangles, a.num_triangles))) return rc;
+    if ((size_t)a.num_materials * sizeof(PtRawMaterial) > materials->bytes)
+        return fail(PT_ERR_RANGE, "material buffer holds %zu bytes, %d materials need %zu", materials->bytes, a.num_materials,
+                    (size_t)a.num_materials * sizeof(PtRawMaterial));
+    if (lights && light_bytes > lights->bytes) return fail(PT_ERR_RANGE, "light list holds %zu bytes, %d lights need %zu", lights->bytes, a.num_lights, light_bytes);
+    if (frame_bytes > samples->bytes) return fail(PT_ERR_RANGE, "sample workspace holds %zu bytes, one frame of %u pixels needs %zu", samples->bytes, npix, frame_bytes);
+    if (fb_bytes > framebuffer->bytes) return fail(PT_ERR_RANGE, "framebuffer holds %zu bytes, %u pixels need %zu", framebuffer->bytes, npix, fb_bytes);
+    if ((uintptr_t)samples->dptr & 3u) return fail(PT_ERR_INVALID, "the sample workspace must be 4-byte aligned");
+    if ((uintptr_t)framebuffer->dptr & 15u) return fail(PT_ERR_INVALID, "the framebuffer must be 16-byte aligned");
+    if (lights && a.num_lights > 0 && ((uintptr_t)lights->dptr & 3u)) return fail(PT_ERR_INVALID, "the light list must be 4-byte aligned");
+    if (ranges_overlap(samples, samples->bytes, framebuffer, fb_bytes)) return fail(PT_ERR_INVALID, "the sample workspace and the framebuffer overlap");
+    if (lights && (ranges_overlap(lights, light_bytes, samples, samples->bytes) || ranges_overlap(lights, light_bytes, framebuffer, fb_bytes)))
+        return fail(PT_ERR_INVALID, "the light list overlaps the sample workspace or the framebuffer");
+    // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
+    if ((rc = check_traversal(d))) return rc;
+    if ((rc = enter_stream(d))) return rc;
+    if (a.frame_count == 0 || npix == 0) {
+        if ((rc = event_begin(d, ev))) return rc;
+        return event_end(d, ev);
+    }
+    PtSearch search;
+    if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
+    if ((rc = event_begin(d, ev))) return rc;
+    PtDirectParams p;
+    memset(&p, 0, sizeof p);
+    search_fields(d, search, p.t);   // (an empty scene: the brute-force form over zero triangles, every sample the background)
+    image_geometry(p.t, a.width, a.height, a.stripe_rows, a.n_ranks, a.rank, npix);
+    p.t.mats = (const PtRawMaterial*)materials->dptr;
+    p.t.nmat = a.num_materials;
+    p.cam = c;
+    p.lights = a.num_lights > 0 ? (const int32_t*)lights->dptr : nullptr;
+    p.samples = (float*)samples->dptr;
+    p.npix = npix;
+    p.K = a.light_samples;
+    p.nl = a.num_lights;
+    PtFoldParams fp;
+    memset(&fp, 0, sizeof fp);
+    fp.rad = p.samples;
+    fp.fb = (float4*)framebuffer->dptr;
+    fp.npix_local = npix;
+    const int bvh_blocks = search.mode.bvh ? d->prop.multiProcessorCount * d->direct_bvh_blocks_per_cu : 0;   // (its own grid: pt_kernels.h)
+    // whole frames per chunk: what the workspace holds, fewer than 2^31 samples per launch; a launch, then its fold
+    const int64_t per_chunk = (int64_t)std::min<uint64_t>(samples->bytes / frame_bytes, 0x7fffffffu / npix);
+    for (int64_t done = 0; done < a.frame_count; done += per_chunk) {
+        const int nf = (int)std::min<int64_t>(per_chunk, a.frame_count - done);
+        p.frame0 = a.frame_begin + (int)done;
+        p.nitems = (uint32_t)nf * npix;
+        HIP_TRY(ptk_direct(p, bvh_blocks, search.mode, d->stream));
+        fp.frame_begin = p.frame0;
+        fp.frame_count = nf;
+        HIP_TRY(ptk_fold(fp, d->stream));
+    }
+    samples->version++;
+    framebuffer->version++;
     return event_end(d, ev);
 }
 

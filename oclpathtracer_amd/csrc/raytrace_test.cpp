@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <chrono>
 #include <cmath>
@@ -357,6 +357,69 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
     }
 }
 
+// TEST_F(DeviceTest, DirectIllumination): the reference declares the case with an empty body (RaytraceTest.cpp:297-299).  Here it
+// renders the scene lit directly by its emitters through pt_render_direct -- dim x dim, --frames frames, K = 4 light samples; the
+// light list is built here: the triangles whose material has an emissive component above 0, ascending -- and writes
+// directIllumination_<version>.ppm through pt_tonemap_ppm, as RayCast writes its image.  Run only when asked for (--only).
+static void test_DirectIllumination(DeviceTest& f, const Options& o)
+{
+    Device* m_d = f.m_d;
+    std::vector<Triangle> triangles;
+    std::vector<Material> materials;
+    if (!loadModel(o.scene.c_str(), triangles, materials)) {
+        std::printf("Error loading model !!\n");
+        ++g_failures;
+        return;
+    }
+    std::vector<int> lights;
+    for (size_t i = 0; i < triangles.size(); i++) {
+        const int id = triangles[i].id;
+        if (id < 0 || (size_t)id >= materials.size()) continue;
+        const Material& m = materials[(size_t)id];
+        if (m.emissive.x > 0.0f || m.emissive.y > 0.0f || m.emissive.z > 0.0f) lights.push_back((int)i);
+    }
+    const int dimension = o.dim;
+    const size_t npix = (size_t)dimension * dimension;
+    const int chunk = o.frames < 8 ? (o.frames < 1 ? 1 : o.frames) : 8;   // frames per launch: the workspace
+    Buffer<Triangle> tBuffer(m_d, triangles.size());
+    Buffer<Material> mBuffer(m_d, materials.size());
+    Buffer<int> lBuffer(m_d, lights.size() ? lights.size() : 1);
+    Buffer<float> samples(m_d, 3 * npix * (size_t)chunk);
+    Buffer<float4_t> image(m_d, npix);
+    Buffer<int> rgb(m_d, 3 * npix);
+    tBuffer.write(triangles.data(), triangles.size());
+    mBuffer.write(materials.data(), materials.size());
+    if (!lights.empty()) lBuffer.write(lights.data(), lights.size());
+    pt_direct_params p;
+    std::memset(&p, 0, sizeof p);
+    p.width = dimension; p.height = dimension;
+    p.frame_begin = 0; p.frame_count = o.frames;
+    p.num_triangles = (int)triangles.size();
+    p.num_materials = (int)materials.size();
+    p.num_lights = (int)lights.size();
+    p.light_samples = 4;
+    p.stripe_rows = 1; p.n_ranks = 1; p.rank = 0;
+    auto t0 = std::chrono::steady_clock::now();
+    IASSERT(pt_render_direct(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lights.empty() ? 0 : lBuffer.m_handle, samples.m_handle,
+                             image.m_handle, &p, 0, 0) == PT_OK);
+    IASSERT(pt_tonemap_ppm(m_d->m_handle, image.m_handle, rgb.m_handle, npix, 0) == PT_OK);
+    std::vector<int> h(3 * npix, 0);
+    rgb.read(h.data(), 3 * npix);
+    DeviceUtils::waitForCompletion(m_d);
+    double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::printf("DirectIllumination: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", dimension, dimension, o.frames, (int)lights.size(), secs);
+    char path[512];
+    f.getFilePath(o.outDir.c_str(), "directIllumination", "ppm", path, sizeof path);
+    FILE* fp = std::fopen(path, "w");
+    IASSERT(fp != 0);
+    if (fp) {
+        std::fprintf(fp, "P3\n%d %d\n%d\n", dimension, dimension, 255);
+        for (size_t i = 0; i < npix; i++) std::fprintf(fp, "%d %d %d ", h[3 * i], h[3 * i + 1], h[3 * i + 2]);
+        std::fclose(fp);
+        std::printf("wrote %s\n", path);
+    }
+}
+
 int main(int argc, char** argv)
 {
     Options o;
@@ -376,10 +439,10 @@ int main(int argc, char** argv)
     if (o.dim < 1 || o.frames < 0) { std::fprintf(stderr, "bad --dim/--frames\n"); return 2; }
     struct { const char* name; int kind; } tests[] = { { "initialize", 0 }, { "deviceInfo", 1 }, { "MemoryAllocation", 2 }, { "writeRead", 3 },
                                                        { "getHostPtr", 4 }, { "kernelExecution", 5 }, { "RayCast", 6 },
-                                                       { "AmbientOcclusion", 7 } };
+                                                       { "AmbientOcclusion", 7 }, { "DirectIllumination", 8 } };
     for (auto& t : tests) {
         if (!o.only.empty() && o.only != t.name) continue;
-        if (o.only.empty() && t.kind == 7) continue;   // AmbientOcclusion runs only when asked for: the default run is RaytraceTest's seven cases
+        if (o.only.empty() && t.kind >= 7) continue;   // AmbientOcclusion and DirectIllumination run only when asked for: the default run is RaytraceTest's seven cases
         std::printf("[ RUN      ] DeviceTest.%s\n", t.name);
         int before = g_failures;
         DeviceTest f;
@@ -392,6 +455,7 @@ int main(int argc, char** argv)
         case 5: test_kernelExecution(f); break;
         case 6: test_RayCast(f, o); break;
         case 7: test_AmbientOcclusion(f, o); break;
+        case 8: test_DirectIllumination(f, o); break;
         default: break;
         }
         f.TearDown();

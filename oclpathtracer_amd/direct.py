@@ -1,0 +1,156 @@
+"""Direct illumination on the device (``pt_render_direct``): the DirectIllumination case the reference's harness declares, built
+from the reference's own steps -- its RNG stream, camera, triangle test, BRDF expressions and gamma running mean.
+
+A sample of a pixel traces the renderer's primary ray; a miss is the background.  On a hit the sample takes the emitted light of
+the surface and ``light_samples`` (K) points on the scene's emitters: a light triangle chosen uniformly from the light list, a
+point chosen uniformly on it, the BRDF value towards it, the geometry term, and a shadow ray that an any-hit search finds occluded
+or open.  The result is the renderer's framebuffer -- with no lights it is the renderer's image at ``max_bounces=1`` bit for bit.
+``include/pt_shim.h`` states every expression.  All compute is HIP in libptshim.so; nothing here has a CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import numpy as np
+
+from . import adl, scene, shim
+from .camera import Camera
+
+_WORKSPACE_BYTES = 64 << 20   # the default workspace holds as many whole frames as fit in this, at most 64
+
+
+def _check_lights(lights, num_triangles: int) -> np.ndarray:
+    a = np.asarray(lights)
+    if a.dtype.kind not in "iu":
+        raise TypeError("lights must be an array of integers (triangle indices)")
+    if a.ndim != 1:
+        raise ValueError("lights must be one-dimensional")
+    if len(a) >= 1 << 24:
+        raise ValueError("at most 2^24 - 1 lights")
+    if len(a) and (int(a.min()) < 0 or int(a.max()) >= num_triangles):
+        raise ValueError("a light index lies outside [0, %d)" % num_triangles)
+    return np.ascontiguousarray(a, np.int32)
+
+
+class DirectRenderer:
+    """Direct illumination of a ``width`` x ``height`` image of ``triangles`` with ``materials`` on ``dev``.
+
+    ``triangles`` / ``materials``: ``scene.TRIANGLE_DTYPE`` / ``scene.MATERIAL_DTYPE`` arrays (uploaded to buffers of this
+    renderer's), or ``adl.Buffer``s that already hold them -- a renderer's own (``Renderer.direct_renderer``), so that both share
+    one prepared scene and one LBVH (``num_triangles`` / ``num_materials`` then say how many records count, and ``lights`` must
+    be given).  ``lights``: the triangle indices light samples are drawn from, each with the same probability (None:
+    ``scene.emitters``); an empty list leaves the emitted light alone.  ``chunk_frames`` sizes the sample workspace: that many
+    frames are traced by one launch and folded by the next.  ``stripe_rows`` / ``n_ranks`` / ``rank`` select the rows this device
+    owns, as for ``Renderer``.  The search follows the device's options exactly as renders do."""
+
+    def __init__(self, dev: adl.Device, triangles, materials, width: int, height: int, *, light_samples: int = 1, lights=None,
+                 camera: Optional[Camera] = None, num_triangles: Optional[int] = None, num_materials: Optional[int] = None,
+                 stripe_rows: int = 16, n_ranks: int = 1, rank: int = 0, chunk_frames: Optional[int] = None):
+        self.dev = dev
+        self._lib = shim.load()
+        self.width, self.height = int(width), int(height)
+        self.light_samples = int(light_samples)
+        self.stripe_rows, self.n_ranks, self.rank = int(stripe_rows), int(n_ranks), int(rank)
+        if self.width < 1 or self.height < 1 or self.width * self.height > 0x7fffffff:
+            raise ValueError("invalid image size %dx%d" % (self.width, self.height))
+        if not 1 <= self.light_samples <= 256:
+            raise ValueError("light_samples must lie in 1..256")
+        if chunk_frames is not None and int(chunk_frames) < 1:
+            raise ValueError("chunk_frames must be at least 1")
+        self.local_rows = self._lib.pt_local_rows(self.height, self.stripe_rows, self.n_ranks, self.rank)
+        if self.local_rows < 0:
+            raise ValueError("invalid stripe geometry")
+        self.local_pixels = self.local_rows * self.width
+        self._set_camera(camera)
+        self.tbuf = self.mbuf = self.lbuf = self.samples = self.fb = None
+        self._own_tbuf = self._own_mbuf = False
+        # everything about the scene that can be refused is refused before the first device call
+        t_host = isinstance(triangles, np.ndarray)
+        m_host = isinstance(materials, np.ndarray)
+        if not (t_host or isinstance(triangles, adl.Buffer)) or (t_host and triangles.dtype != scene.TRIANGLE_DTYPE):
+            raise TypeError("triangles must be a scene.TRIANGLE_DTYPE array or an adl.Buffer")
+        if not (m_host or isinstance(materials, adl.Buffer)) or (m_host and materials.dtype != scene.MATERIAL_DTYPE):
+            raise TypeError("materials must be a scene.MATERIAL_DTYPE array or an adl.Buffer")
+        if not t_host and num_triangles is None:
+            raise ValueError("num_triangles is required with an adl.Buffer of triangles")
+        if not m_host and num_materials is None:
+            raise ValueError("num_materials is required with an adl.Buffer of materials")
+        ntri = len(triangles) if t_host else int(num_triangles)
+        nmat = len(materials) if m_host else int(num_materials)
+        if ntri < 0 or nmat < 1:
+            raise ValueError("a scene needs num_triangles >= 0 and at least one material")
+        if lights is None:
+            if not (t_host and m_host):
+                raise ValueError("lights must be given with adl.Buffers of triangles or materials (scene.emitters derives them)")
+            lights = scene.emitters(triangles, materials)
+        self.lights = _check_lights(lights, ntri)
+        self.num_materials = nmat
+
+        self.tbuf, self.num_triangles, self._own_tbuf = scene.triangle_buffer(dev, triangles, num_triangles)
+        if m_host:
+            self.mbuf, self._own_mbuf = adl.Buffer(dev, nmat, scene.MATERIAL_DTYPE), True
+            self.mbuf.write(np.ascontiguousarray(materials), nmat)
+        else:
+            self.mbuf = materials
+        self.lbuf = adl.Buffer(dev, max(len(self.lights), 1), np.int32)
+        if len(self.lights):
+            self.lbuf.write(self.lights, len(self.lights))
+        n = max(self.local_pixels, 1)
+        if chunk_frames is None:
+            chunk_frames = max(1, min(64, _WORKSPACE_BYTES // (12 * n)))
+        self.chunk_frames = int(chunk_frames)
+        self.samples = adl.Buffer(dev, 3 * n * self.chunk_frames, np.float32)
+        self.fb = adl.Buffer(dev, n, adl.float4)
+        self.frames_done = 0
+
+    def _set_camera(self, camera: Optional[Camera]) -> None:
+        self._cam = Camera.struct_of(camera)   # rejected here, before anything is enqueued
+        self.camera = camera
+
+    def set_camera(self, camera: Optional[Camera]) -> None:
+        """Render from ``camera`` from now on (None: the reference's); the next render starts again at frame 0."""
+        self._set_camera(camera)
+        self.frames_done = 0
+
+    def params(self, frames: int, frame_begin: int) -> shim.DirectParams:
+        p = shim.DirectParams()
+        p.width, p.height = self.width, self.height
+        p.frame_begin, p.frame_count = frame_begin, frames
+        p.num_triangles, p.num_materials, p.num_lights = self.num_triangles, self.num_materials, len(self.lights)
+        p.light_samples = self.light_samples
+        p.stripe_rows, p.n_ranks, p.rank = self.stripe_rows, self.n_ranks, self.rank
+        return p
+
+    def render(self, frames: int, frame_begin: Optional[int] = None, sync: Optional[adl.SyncObject] = None) -> None:
+        """Enqueue frames [frame_begin, frame_begin + frames) (default: continue after the last call); frame_begin 0 starts the
+        running mean afresh."""
+        if frame_begin is None:
+            frame_begin = self.frames_done
+        frames, frame_begin = int(frames), int(frame_begin)
+        if frames < 0 or frame_begin < 0 or frame_begin + frames > 0x7fffffff:
+            raise ValueError("invalid frame range [%d, %d)" % (frame_begin, frame_begin + frames))
+        p = self.params(frames, frame_begin)
+        shim.check(self._lib.pt_render_direct(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
+                                              self.samples._h, self.fb._h, ctypes.byref(p),
+                                              ctypes.byref(self._cam) if self._cam is not None else None,
+                                              sync._h if sync is not None else None))
+        self.frames_done = frame_begin + frames
+
+    def read(self) -> np.ndarray:
+        """Local framebuffer as (local_rows * width, 4) float32, the renderer's layout (synchronises)."""
+        out = np.zeros((self.local_pixels, 4), np.float32)
+        if self.local_pixels:
+            self.fb.read(out, self.local_pixels)
+        self.dev.waitForCompletion()
+        return out
+
+    def release(self) -> None:
+        for b in (self.lbuf, self.samples, self.fb):
+            if b is not None:
+                b.release()
+        if self._own_tbuf and self.tbuf is not None:
+            self.tbuf.release()
+        if self._own_mbuf and self.mbuf is not None:
+            self.mbuf.release()
+        self.tbuf = self.mbuf = self.lbuf = self.samples = self.fb = None

@@ -173,6 +173,29 @@ class Renderer:
         return AORenderer(self.dev, self.tbuf, kw.pop("width", self.width), kw.pop("height", self.height),
                           num_triangles=kw.pop("num_triangles", self.num_triangles), **kw)
 
+    def direct_renderer(self, **kw):
+        """A :class:`direct.DirectRenderer` of this renderer's image over its triangle and material buffers (keyword arguments:
+        DirectRenderer's; the image size, camera and sharding default to this renderer's): direct-illumination renders and renders
+        share the device's prepared scene and LBVH.  Without ``lights`` the list is ``scene.emitters`` of the scene read back from
+        the buffers (which waits for the device, once).  Release it before the renderer."""
+        from .direct import DirectRenderer
+
+        kw.setdefault("camera", self.camera)
+        kw.setdefault("stripe_rows", self.stripe_rows)
+        kw.setdefault("n_ranks", self.n_ranks)
+        kw.setdefault("rank", self.rank)
+        if kw.get("lights") is None:
+            tris = np.zeros(self.num_triangles, scene.TRIANGLE_DTYPE)
+            mats = np.zeros(self.num_materials, scene.MATERIAL_DTYPE)
+            if self.num_triangles:
+                self.tbuf.read(tris, self.num_triangles)
+            if self.num_materials:
+                self.mbuf.read(mats, self.num_materials)
+            self.dev.waitForCompletion()
+            kw["lights"] = scene.emitters(tris, mats)
+        return DirectRenderer(self.dev, self.tbuf, self.mbuf, kw.pop("width", self.width), kw.pop("height", self.height),
+                              num_triangles=self.num_triangles, num_materials=self.num_materials, **kw)
+
     def global_rows(self) -> np.ndarray:
         """Global row index of every local row (ascending)."""
         rows = np.arange(self.height)

@@ -194,6 +194,21 @@ def triangle_buffer(dev, triangles, num_triangles=None):
     return buf, len(tris), True
 
 
+def emitters(triangles: np.ndarray, materials: np.ndarray) -> np.ndarray:
+    """The light list of direct illumination (``pt_render_direct``): the ascending indices (int32) of the triangles whose material
+    has an emissive r, g or b component above 0.  A triangle whose material id is out of range emits nothing."""
+    tris = np.asarray(triangles)
+    mats = np.asarray(materials)
+    if tris.dtype != TRIANGLE_DTYPE or mats.dtype != MATERIAL_DTYPE:
+        raise TypeError("emitters needs scene.TRIANGLE_DTYPE triangles and scene.MATERIAL_DTYPE materials")
+    emits = (mats["emissive"][:, :3] > 0).any(axis=1) if len(mats) else np.zeros(0, bool)
+    ids = tris["id"].astype(np.int64)
+    ok = (ids >= 0) & (ids < len(mats))
+    lit = np.zeros(len(tris), bool)
+    lit[ok] = emits[ids[ok]]
+    return np.flatnonzero(lit).astype(np.int32)
+
+
 def _splitmix64(n: int, seed: int) -> np.ndarray:
     """n successive splitmix64 outputs (vectorised, two buffers reused in place: fresh pages are
     what costs time on a 10^7-element array)."""
