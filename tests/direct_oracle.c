@@ -18,6 +18,20 @@
  */
 enum { ODI_NONE = 0, ODI_OCCLUDED = 1, ODI_OPEN = 2 };
 
+/* Why a light sample ended as it did (odi_details).  ODI_NONE splits into NOT_DRAWN (the primary ray missed or the list is empty:
+ * no uniforms are drawn), NOT_FACING (cs <= 0), EDGE_ON (cl <= 0, cs > 0, both finite), NAN (cs or cl NaN) and OTHER_TYPE (:220);
+ * ODI_OPEN into OPEN_UNSEARCHED (tl <= 0: nothing is searched) and OPEN; ODI_OCCLUDED stays. */
+enum { ODI_R_NOT_DRAWN = 0, ODI_R_NOT_FACING = 1, ODI_R_EDGE_ON = 2, ODI_R_NAN = 3, ODI_R_OTHER_TYPE = 4, ODI_R_OPEN_UNSEARCHED = 5,
+       ODI_R_OPEN = 6, ODI_R_OCCLUDED = 7 };
+
+/* odi_sample's optional account of a sample: *flipped = the normal was negated at :243; per light sample its reason code and d2
+ * (-1 where the sample was not drawn) */
+typedef struct odi_why {
+    uint8_t* flipped;
+    uint8_t* reason;   /* [K] */
+    float* d2;         /* [K] */
+} odi_why;
+
 /* ptor_sample_pixel's accumulation (pt_oracle.c:500-513) of the sample radiance c of frame `frame` into px */
 PTOR_INLINE void odi_fold(float* px, v3 c, int frame)
 {
@@ -39,9 +53,10 @@ PTOR_INLINE void odi_fold(float* px, v3 c, int frame)
 
 PTOR_INLINE int odi_clampi(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
-/* one sample: its radiance L; *hit = the primary ray hit; dec (may be NULL): per light sample ODI_NONE / ODI_OCCLUDED / ODI_OPEN */
+/* one sample: its radiance L; *hit = the primary ray hit; dec (may be NULL): per light sample ODI_NONE / ODI_OCCLUDED / ODI_OPEN;
+ * why (may be NULL): the reasons behind them */
 PTOR_INLINE v3 odi_sample(const ocam* cam, const ptor_triangle* tris, int ntri, const ptor_material* mats, const int32_t* lights,
-                          int nl, int x, int grow, int W, int H, int frame, int K, int* hit, uint8_t* dec)
+                          int nl, int x, int grow, int W, int H, int frame, int K, int* hit, uint8_t* dec, const odi_why* why)
 {
     ptor_stats st;
     memset(&st, 0, sizeof st);
@@ -51,6 +66,11 @@ PTOR_INLINE v3 odi_sample(const ocam* cam, const ptor_triangle* tris, int ntri, 
     ptor_hit rec;
     memset(&rec, 0, sizeof rec);
     if (dec) memset(dec, ODI_NONE, (size_t)K);
+    if (why) {
+        *why->flipped = 0;
+        memset(why->reason, ODI_R_NOT_DRAWN, (size_t)K);
+        for (int k = 0; k < K; ++k) why->d2[k] = -1.0f;
+    }
     *hit = ptor_intersect_world(&r, tris, ntri, &rec, &st);
     if (!*hit) {
         const float bg = ptor_max(0.45f, 0.0f);   /* :235 */
@@ -59,7 +79,9 @@ PTOR_INLINE v3 odi_sample(const ocam* cam, const ptor_triangle* tris, int ntri, 
     const ptor_material* m = &mats[tris[rec.tri].id];
     const v3 E = v3_make(1.0f * m->emissive[0] * 3.0f, 1.0f * m->emissive[1] * 3.0f, 1.0f * m->emissive[2] * 3.0f);   /* :241 */
     const v3 p = rec.p;
-    const v3 n = v3_dot(rec.n, r.dir) < 0.0f ? rec.n : v3_scale(rec.n, -1.0f);   /* :243 */
+    const int facing = v3_dot(rec.n, r.dir) < 0.0f;
+    const v3 n = facing ? rec.n : v3_scale(rec.n, -1.0f);   /* :243 */
+    if (why) *why->flipped = (uint8_t)!facing;
     const v3 wo = v3_neg(r.dir);
     const v3 albedo = v3_make(m->albedo[0], m->albedo[1], m->albedo[2]);
     v3 S = v3_make(0.0f, 0.0f, 0.0f);
@@ -82,7 +104,11 @@ PTOR_INLINE v3 odi_sample(const ocam* cam, const ptor_triangle* tris, int ntri, 
         const float dist = sqrtf(d2);
         const v3 wi = v3_normalize(dv);
         const float cs = v3_dot(wi, n), cl = fabsf(v3_dot(wi, nj));
-        if (!(cs > 0.0f && cl > 0.0f)) continue;
+        if (why) why->d2[k] = d2;
+        if (!(cs > 0.0f && cl > 0.0f)) {
+            if (why) why->reason[k] = (cs != cs || cl != cl) ? ODI_R_NAN : (cs <= 0.0f ? ODI_R_NOT_FACING : ODI_R_EDGE_ON);
+            continue;
+        }
         v3 f;
         if (m->type == PTOR_DIFFUSE) {
             f = v3_scale(albedo, PTOR_INV_PI);   /* :203 */
@@ -97,6 +123,7 @@ PTOR_INLINE v3 odi_sample(const ocam* cam, const ptor_triangle* tris, int ntri, 
                 f = v3_scale(v3_scale(albedo, g), 2.0f);   /* :217 */
             }
         } else {
+            if (why) why->reason[k] = ODI_R_OTHER_TYPE;
             continue;   /* :220 */
         }
         const ptor_material* mj = &mats[tj->id];
@@ -112,6 +139,7 @@ PTOR_INLINE v3 odi_sample(const ocam* cam, const ptor_triangle* tris, int ntri, 
             for (int i = 0; i < ntri && !occluded; i++) occluded = ptor_intersect_triangle(&s, &tris[i], i, &srec, tl, &st);
         }
         if (dec) dec[k] = occluded ? ODI_OCCLUDED : ODI_OPEN;
+        if (why) why->reason[k] = occluded ? ODI_R_OCCLUDED : (tl > 0.0f ? ODI_R_OPEN : ODI_R_OPEN_UNSEARCHED);
         if (!occluded) S = v3_add(S, c);
     }
     const float Kf = (float)K;
@@ -143,7 +171,7 @@ int odi_render(const void* tris_, int ntri, const void* mats_, const int32_t* li
             for (int f = 0; f < frame_count; ++f) {
                 int hit;
                 const v3 L = odi_sample(&c, (const ptor_triangle*)tris_, ntri, (const ptor_material*)mats_, lights, nl, x, grow, W, H,
-                                        frame_begin + f, K, &hit, 0);
+                                        frame_begin + f, K, &hit, 0, 0);
                 odi_fold(fb + 4 * lp, L, frame_begin + f);
             }
     }
@@ -160,9 +188,29 @@ int odi_decisions(const void* tris_, int ntri, const void* mats_, const int32_t*
     for (int64_t i = 0; i < n; ++i) {
         int h;
         const v3 L = odi_sample(&c, (const ptor_triangle*)tris_, ntri, (const ptor_material*)mats_, lights, nl, gid[i] % W, gid[i] / W,
-                                W, H, frame[i], K, &h, dec + i * K);
+                                W, H, frame[i], K, &h, dec + i * K, 0);
         hit[i] = (uint8_t)h;
         if (radiance) { radiance[3 * i] = L.x; radiance[3 * i + 1] = L.y; radiance[3 * i + 2] = L.z; }
+    }
+    return 0;
+}
+
+/* n samples (gid[i], frame[i]): hit[i], flipped[i], reason[i * K + k] = ODI_R_* and d2[i * K + k] of light sample k,
+ * radiance[i * 3 ..] = L */
+PTOR_CLONES
+int odi_details(const void* tris_, int ntri, const void* mats_, const int32_t* lights, int nl, const float* cam10, int W, int H,
+                const int32_t* gid, const int32_t* frame, int64_t n, int K, uint8_t* hit, uint8_t* flipped, uint8_t* reason, float* d2,
+                float* radiance)
+{
+    ocam c;
+    if (odi_camera(cam10, &c) != 0) return -1;
+    for (int64_t i = 0; i < n; ++i) {
+        int h;
+        const odi_why why = { flipped + i, reason + i * K, d2 + i * K };
+        const v3 L = odi_sample(&c, (const ptor_triangle*)tris_, ntri, (const ptor_material*)mats_, lights, nl, gid[i] % W, gid[i] / W,
+                                W, H, frame[i], K, &h, 0, &why);
+        hit[i] = (uint8_t)h;
+        radiance[3 * i] = L.x; radiance[3 * i + 1] = L.y; radiance[3 * i + 2] = L.z;
     }
     return 0;
 }

@@ -1,6 +1,6 @@
 """Builds, loads and binds tests/libtest_direct_oracle.so: the CPU oracle's direct illumination (tests/direct_oracle.c through the
 translation unit tests/direct_oracles.c, which includes tests/oracles.c whole) -- the framebuffer of pt_render_direct, and the
-per-light-sample decisions behind it.  TEST INFRASTRUCTURE.
+per-light-sample decisions behind it with their reasons.  TEST INFRASTRUCTURE.
 
 ``__graft_entry__.build()`` builds it (``python -B tests/direct_oracle.py build``); ``lib()`` builds it again when it is missing or
 older than one of its sources, as ``oracles.lib()`` does.
@@ -22,11 +22,17 @@ LIB_PATH = os.path.join(_HERE, "libtest_direct_oracle.so")
 _SRCS = [os.path.join(_HERE, f) for f in ("direct_oracles.c", "direct_oracle.c")] + list(oracles._SRCS)
 
 NONE, OCCLUDED, OPEN = 0, 1, 2   # the decisions of a light sample (direct_oracle.c: ODI_*)
+# why (direct_oracle.c: ODI_R_*): NONE is NOT_DRAWN (the primary ray missed, or no lights), NOT_FACING (cs <= 0), EDGE_ON (cl <= 0),
+# NAN (cs or cl NaN) or OTHER_TYPE (:220); OPEN is OPEN_UNSEARCHED (tl <= 0) or R_OPEN; OCCLUDED is R_OCCLUDED
+NOT_DRAWN, NOT_FACING, EDGE_ON, NAN, OTHER_TYPE, OPEN_UNSEARCHED, R_OPEN, R_OCCLUDED = range(8)
+REASONS = ("NOT_DRAWN", "NOT_FACING", "EDGE_ON", "NAN", "OTHER_TYPE", "OPEN_UNSEARCHED", "OPEN", "OCCLUDED")
+DECISION_OF = np.array([NONE, NONE, NONE, NONE, NONE, OPEN, OPEN, OCCLUDED], np.uint8)   # reason code -> decision
 
 _V, _I, _I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
 _SIGNATURES = {
     "odi_render": (_I, [_V, _I, _V, _V, _I, _V] + [_I] * 8 + [_V]),
     "odi_decisions": (_I, [_V, _I, _V, _V, _I, _V, _I, _I, _V, _V, _I64, _I, _V, _V, _V]),
+    "odi_details": (_I, [_V, _I, _V, _V, _I, _V, _I, _I, _V, _V, _I64, _I, _V, _V, _V, _V, _V]),
 }
 
 
@@ -89,6 +95,32 @@ def decisions(tris, mats, W, H, gid, frame, K, *, lights=None, cam=None):
     if rc != 0:
         raise ValueError("odi_decisions rejected the camera")
     return hit, dec, rad
+
+
+def details(tris, mats, W, H, gid, frame, K, *, lights=None, cam=None):
+    """Per sample (gid[i], frame[i]): hit and flipped (uint8 [n]: the normal was negated at :243), the reason code of each light
+    sample (uint8 [n, K], see REASONS; DECISION_OF[reason] is what ``decisions`` returns) with its d2 (float32 [n, K], -1 where
+    no sample was drawn) and the sample's radiance L (float32 [n, 3])."""
+    tris, mats = np.ascontiguousarray(tris), np.ascontiguousarray(mats)
+    li = _lights(tris, mats, lights)
+    gid = np.ascontiguousarray(gid, np.int32)
+    frame = np.ascontiguousarray(frame, np.int32)
+    n = len(gid)
+    hit, flipped = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    reason = np.zeros((n, K), np.uint8)
+    d2 = np.zeros((n, K), np.float32)
+    rad = np.zeros((n, 3), np.float32)
+    c = cam10(cam)
+    rc = lib().odi_details(ptr(tris) if len(tris) else None, len(tris), ptr(mats), ptr(li) if len(li) else None, len(li), ptr(c),
+                           W, H, ptr(gid), ptr(frame), n, K, ptr(hit), ptr(flipped), ptr(reason), ptr(d2), ptr(rad))
+    if rc != 0:
+        raise ValueError("odi_details rejected the camera")
+    return hit, flipped, reason, d2, rad
+
+
+def count_reasons(reason):
+    """{name: how many light samples ended for that reason}"""
+    return {name: int((reason == k).sum()) for k, name in enumerate(REASONS)}
 
 
 if __name__ == "__main__":

@@ -5,7 +5,10 @@ generated from fixed seeds, and the order of the draws from a generator is part 
   * scenes that steer the trace kernels and the LBVH builder: variant, bvh_edge, deep, horizon_tiles, random_quads;
   * the far-origin scenes (tests/lbvh_far.py has their ray families): tile_scene, soup(2000, 5);
   * scenes at the edges of what the LBVH takes -- scale, offset, shape, the builder's boundaries -- with rays to query them:
-    scene(name) for name in NAMES (tests/test_lbvh_scale_cpu.py: the oracle's scale identities; tests/test_gpu_lbvh_scenes.py)."""
+    scene(name) for name in NAMES (tests/test_lbvh_scale_cpu.py: the oracle's scale identities; tests/test_gpu_lbvh_scenes.py);
+  * scenes at the edges of direct illumination's light sample, each (tris, mats, lights, camera or None): direct_scaled,
+    direct_light_list, direct_other_type, direct_from_behind (tests/test_direct_cpu.py proves that each reaches its edge,
+    tests/test_gpu_direct_edges.py renders them); glossy_room, the GGX branch at every roughness a guard can meet."""
 from __future__ import annotations
 
 import numpy as np
@@ -331,3 +334,93 @@ def scene(name):
 
 NAMES = ["scale%d" % k for k in SCALES] + ["offset%d" % j for j in OFFSETS] + \
         ["squeezed", "stretched", "shared_point", "big64", "big65", "none_finite", "one_finite", "n511", "n512"]
+
+
+# ---- direct illumination: the light sample's edges ------------------------------------------------------------------------------
+def direct_scaled(copies, k):
+    """nested_boxes(copies) and the reference camera times 2^k (exact): the facing decisions stay, 0.01 and 0.02 do not scale, so
+    at small k shadow rays have tl <= 0 and search nothing (at k = -9 all of them: the scene is smaller than 0.02)."""
+    from oclpathtracer_amd.camera import Camera
+
+    tris, mats = nested_boxes(copies)
+    s = np.float32(2.0 ** k)
+    for f in ("p1", "p2", "p3"):
+        tris[f][:, :3] = tris[f][:, :3] * s
+    ref = Camera.reference()
+    cam = Camera(eye=tuple(np.float32(v) * s for v in ref.eye), center=tuple(np.float32(v) * s for v in ref.center), up=ref.up,
+                 fov_y_deg=ref.fov_y_deg)
+    return tris, mats, _scene.emitters(tris, mats), cam
+
+
+MIXED_SCALE = -7   # the k at which direct_scaled(10 or 15, k) has occluded, searched-open and unsearched shadow rays side by side
+
+LIGHT_LIST = (36, 10, 10, 36, 3, 11)
+
+
+def direct_light_list(lights=LIGHT_LIST):
+    """The Cornell box plus triangle 36, a copy of light triangle 10 with p2 = p1 (no area: nj and cl are NaN); the default list is
+    degenerate, duplicated, unsorted and holds a wall (3), which is sampled, casts its shadow ray and contributes 0."""
+    tris, mats = _scene.load_model()
+    extra = tris[10:11].copy()
+    extra["p2"] = extra["p1"]
+    tris = np.concatenate([tris, extra])
+    assert len(tris) == 37
+    return tris, mats, np.asarray(lights, np.int32), None
+
+
+def direct_other_type():
+    """The Cornell box with every diffuse material's type set to 3: neither branch of the BRDF (:220), all 3K uniforms drawn"""
+    tris, mats = _scene.load_model()
+    mats = mats.copy()
+    diffuse = mats["type"] == _scene.DIFFUSE
+    assert int(diffuse.sum()) == 8
+    mats["type"][diffuse] = 3
+    return tris, mats, _scene.emitters(tris, mats), None
+
+
+BEHIND_EYE, BEHIND_CENTER = (0.0, 2.75, -10.0), (0.0, 2.75, -2.8)   # behind the back wall, looking at the box's middle
+
+
+def direct_from_behind():
+    """The Cornell box from outside: primary rays meet walls from their back, where the normal is negated (:243)"""
+    from oclpathtracer_amd.camera import Camera
+
+    tris, mats = _scene.load_model()
+    return tris, mats, _scene.emitters(tris, mats), Camera(eye=BEHIND_EYE, center=BEHIND_CENTER, up=(0.0, 1.0, 0.0), fov_y_deg=60.0)
+
+
+# Roughnesses of the glossy room, on both sides of every guard edge of the GGX branch that a roughness moves:
+#   1 - xi over b = xi (r^2 - 1) + 1, b in [2^-60, 2^60):      b reaches r^2 for r > 1: r = 2^30;  for r < 2^-12, r^2 - 1 rounds
+#                                                              to -1 and b is 1 - xi, +0 (xi = 1) included
+#   r^2 / pi over gd^2, both in [2^-60, 2^60):                 r^2 / pi = 2^-60 at r = sqrt(pi) 2^-30, 2^60 at r = sqrt(pi) 2^30;
+#                                                              gd^2 reaches r^4 for r > 1: r = 2^15 (and r^4 for 2^-12 < r < 1)
+#   D cos / 4 dot(wo, wh) and D / 4 dwin dwon, D < 2^60:       D reaches 1 / (pi r^2): r = 2^-30 / sqrt(pi)
+# and r = 1 (gd == 1 exactly), the Cornell box's own 0.008, the smallest r whose r^4 is a normal number, 0 (D = 0 / 0).
+_SQRT_PI = float(np.sqrt(np.pi))
+ROUGHNESS = [1.0, 0.008, float(np.nextafter(np.float32(2.0 ** -31.5), np.float32(1.0))), 0.0,
+             2.0 ** 30 * 0.99, 2.0 ** 30 * 1.01,
+             _SQRT_PI * 2.0 ** -30 * 0.99, _SQRT_PI * 2.0 ** -30 * 1.01, _SQRT_PI * 2.0 ** 30 * 0.99, _SQRT_PI * 2.0 ** 30 * 1.01,
+             2.0 ** 15 * 0.99, 2.0 ** 15 * 1.01, 2.0 ** -12 * 0.99, 2.0 ** -12 * 1.01,
+             2.0 ** -30 / _SQRT_PI * 0.99, 2.0 ** -30 / _SQRT_PI * 1.01, 0.3]
+
+
+GLOSSY_SHIFTS = (0, 1, 4, 13)
+
+
+def glossy_room(shift=0):
+    """The Cornell box with every surface but the light a GGX one, a roughness of ROUGHNESS each: the k-th such material takes
+    ROUGHNESS[(k + shift) % 17].  The reference camera sees seven of them lit by the light; GLOSSY_SHIFTS brings every roughness
+    onto one of those seven (direct illumination's GGX branch, tests/test_direct_cpu.py)."""
+    tris, mats = _scene.load_model()
+    mats = mats.copy()
+    k = 0
+    for m in mats:
+        if m["emissive"][0] != 0.0:
+            continue
+        m["type"] = _scene.SPECULAR
+        m["roughness"] = np.float32(ROUGHNESS[(k + shift) % len(ROUGHNESS)])
+        if m["albedo"][0] > 0.6:
+            m["albedo"] = (0.5, 0.35, 0.05, 0.0)   # (a GGX weight is 2 albedo g dwin / pdf: keep long paths finite)
+        k += 1
+    assert k >= len(ROUGHNESS)
+    return tris, mats

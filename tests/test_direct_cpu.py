@@ -288,3 +288,255 @@ def test_restatement_agrees_with_a_float64_model(cornell):
     assert decided.sum() >= 0.98 * both.sum() * K   # (the light fills about 1 % of the image)
     for what in (do.NONE, do.OCCLUDED, do.OPEN):
         assert (dec32[decided] == what).sum() > 100, what
+
+
+# ---- each input of tests/test_gpu_direct_edges.py reaches its edge ----------------------------------------------------------------
+# The restatement alone, no GPU: a bit-exact comparison on an input that never reaches the edge it is named for proves nothing, so
+# every floor below is a condition on the input (tests/scenes.py), not a measurement of the code under test.
+def _details(scene4, W, H, K, frame=0):
+    import direct_oracle as do
+
+    tris, mats, lights, cam = scene4
+    gid = np.arange(W * H)
+    hit, flipped, reason, d2, L = do.details(tris, mats, W, H, gid, np.full(W * H, frame), K, lights=lights, cam=cam)
+    counts = do.count_reasons(reason)
+    print("%dx%d K%d frame %d: hit %d flipped %d %s" % (W, H, K, frame, int(hit.sum()), int(flipped.sum()), counts))
+    return hit, flipped, reason, d2, L, counts
+
+
+def _hit_material(scene4, W, H, frame=0):
+    """the material index of each sample's primary hit (-1: a miss), by the oracle's closest hit of the oracle's camera rays"""
+    import query_oracle
+
+    tris, _, _, cam = scene4
+    rec = query_oracle.closest(tris, query_oracle.camera_rays(W, H, frame, cam))
+    tri = rec[:, 1].copy().view(np.int32)
+    return np.where(tri >= 0, tris["id"][np.maximum(tri, 0)], -1), tri
+
+
+def _light_entries(W, H, K, nl, frame=0):
+    """which entry of the light list each light sample draws (int [W * H, K]), recomputed from the seed: float64 camera and RNG
+    of tests/f64_model.py, whose uniforms are the binary32 values, and the contract's min((uint32)(r0 * (float)nl), nl - 1)"""
+    import f64_model as m
+
+    gid = np.arange(W * H, dtype=np.int64)
+    seed = (gid.astype(np.uint64) + m.hash_u32(np.full(W * H, frame, np.uint64))) & np.uint64(0xFFFFFFFF)
+    _, _, seed = m.generate_ray((gid % W).astype(np.float64), (gid // W).astype(np.float64), W, H, seed)
+    li = np.zeros((W * H, K), np.int64)
+    for k in range(K):
+        seed, r0 = m.random_float(seed)
+        seed, _ = m.random_float(seed)
+        seed, _ = m.random_float(seed)
+        li[:, k] = np.minimum((np.float32(r0) * np.float32(nl)).astype(np.uint32), nl - 1)
+    return li
+
+
+def _emitted(mats, mid):
+    """max(E, 0), E = 1.0f * emissive * 3.0f of material mid, per sample [n, 3]"""
+    return np.maximum(np.float32(1.0) * mats["emissive"][mid, :3] * np.float32(3.0), np.float32(0.0))
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
+
+
+def test_reason_codes_give_the_decisions(cornell):
+    """odi_details' reason codes fold back into odi_decisions' three decisions, with the same hits and the same radiance"""
+    import direct_oracle as do
+
+    tris, mats = cornell
+    W = H = 64
+    gid = np.tile(np.arange(W * H), 2)
+    frame = np.repeat(np.arange(2), W * H)
+    hit, flipped, reason, d2, L = do.details(tris, mats, W, H, gid, frame, 4)
+    hit2, dec, L2 = do.decisions(tris, mats, W, H, gid, frame, 4)
+    assert np.array_equal(hit, hit2) and np.array_equal(do.DECISION_OF[reason], dec) and _same_bits(L, L2)
+    counts = do.count_reasons(reason[: W * H])
+    print("Cornell 64x64 K 4 frame 0:", counts)
+    assert counts["NOT_FACING"] + counts["EDGE_ON"] + counts["NAN"] + counts["OTHER_TYPE"] + counts["NOT_DRAWN"] > 1000
+    assert counts["OCCLUDED"] > 500 and counts["OPEN"] > 5000 and counts["OPEN_UNSEARCHED"] == 0
+    assert np.all((d2 >= 0) == (reason != do.NOT_DRAWN))
+    # the triangle test is one-sided (:100 passes det = dot(d, cross(e2, e1)) > 0 only), so the HitRecord normal of every hit
+    # points along the ray and :243 negates it on EVERY hit: `flipped` is `hit`, from any camera
+    assert np.array_equal(flipped, hit)
+
+
+def test_a_scene_smaller_than_the_offsets_searches_nothing():
+    """The Cornell box times 2^-9: its diameter, about 9.6 * 2^-9 = 0.019, is below 0.02, so every contributing light sample has
+    tl = dist - 0.02 < 0: nothing is searched and nothing is occluded (measured: OPEN_UNSEARCHED 14269, NOT_FACING 2115)."""
+    from scenes import direct_scaled
+
+    hit, _, _, d2, _, counts = _details(direct_scaled(1, -9), 64, 64, 4)
+    assert hit.all()
+    assert counts["OCCLUDED"] == 0 and counts["OPEN"] == 0 and counts["OPEN_UNSEARCHED"] > 10000, counts
+    assert d2.max() < 0.02 * 0.02
+
+
+@pytest.mark.parametrize("copies", [15, 10])
+def test_the_mixed_scale_has_searched_and_unsearched_shadow_rays(copies):
+    """nested_boxes times 2^-7, 32 x 32, K = 3: shadow rays that are occluded, open after a search and open without one, side by
+    side in one wave (and in one lane's sample after the other under the LBVH).  Measured, OCCLUDED / OPEN / OPEN_UNSEARCHED:
+    15 copies 902 / 1005 / 660 at k = -7 (k = -6: 1467 / 1023 / 77; k = -8: 1 / 159 / 2407); 10 copies 829 / 1101 / 541 at
+    k = -7 (k = -6: 1487 / 958 / 26; k = -8: 0 / 235 / 2236)."""
+    from scenes import MIXED_SCALE, direct_scaled
+
+    assert MIXED_SCALE == -7
+    _, _, _, _, _, counts = _details(direct_scaled(copies, MIXED_SCALE), 32, 32, 3)
+    assert min(counts["OCCLUDED"], counts["OPEN"], counts["OPEN_UNSEARCHED"]) >= 100, counts
+    _, _, _, _, _, unsearched = _details(direct_scaled(copies, -9), 32, 32, 3)     # (the other scale the GPU tests render)
+    assert unsearched["OCCLUDED"] == 0 and unsearched["OPEN"] == 0 and unsearched["OPEN_UNSEARCHED"] > 2000, unsearched
+
+
+def test_scaling_keeps_the_facing_decisions():
+    """the scale is a power of two, so cs and cl keep their signs: the same light samples are NOT_FACING at every scale the
+    exact triangle test's literal threshold leaves the primary hits alone (2^-9 and above, scenes.IDENTITY)"""
+    import direct_oracle as do
+    from scenes import direct_scaled
+
+    ref = _details(direct_scaled(15, 0), 32, 32, 3)
+    for k in (-7, -9):
+        got = _details(direct_scaled(15, k), 32, 32, 3)
+        assert np.array_equal(got[0], ref[0])
+        assert np.array_equal(got[2] == do.NOT_FACING, ref[2] == do.NOT_FACING)
+
+
+def test_the_light_list_reaches_its_edges():
+    """[36, 10, 10, 36, 3, 11] on the 37-triangle scene, 64 x 64, K = 4: the two entries without area end as NAN (measured
+    5528 of 16384), the wall (entry 4, triangle 3) is sampled, casts its shadow rays (measured: drawn 2722 times, OPEN 1418 +
+    OCCLUDED 476 of them) and contributes exactly 0."""
+    import direct_oracle as do
+    from scenes import LIGHT_LIST, direct_light_list
+
+    W = H = 64
+    K = 4
+    sc = direct_light_list()
+    tris, mats, lights, _ = sc
+    assert tuple(lights) == LIGHT_LIST == (36, 10, 10, 36, 3, 11)
+    hit, _, reason, d2, L, counts = _details(sc, W, H, K)
+    assert hit.all() and counts["NAN"] >= 4000, counts
+    entry = _light_entries(W, H, K, len(lights))
+    chosen = lights[entry]
+    assert np.all((reason == do.NAN) == (chosen == 36)), "exactly the samples of the triangle without area are NaN"
+    wall = chosen == 3
+    cast = wall & ((reason == do.R_OPEN) | (reason == do.R_OCCLUDED))
+    print("entry 3 drawn %d times: OPEN %d OCCLUDED %d" % (int(wall.sum()), int((wall & (reason == do.R_OPEN)).sum()),
+                                                           int((wall & (reason == do.R_OCCLUDED)).sum())))
+    assert int(cast.sum()) >= 1000
+    # the same draws with the wall as the only light: the same points q, so the same d2 and the same reasons
+    _, _, reason3, d23, _ = do.details(tris, mats, W, H, np.arange(W * H), np.zeros(W * H), K, lights=np.array([3], np.int32))
+    assert np.array_equal(reason[wall], reason3[wall]) and _same_bits(d2[wall], d23[wall])
+    # its contribution is 0: a sample whose every open shadow ray went to the wall holds the emitted light alone
+    only_wall = (wall | (do.DECISION_OF[reason] != do.OPEN)).all(axis=1) & (wall & (reason == do.R_OPEN)).any(axis=1)
+    mid, _ = _hit_material(sc, W, H)
+    assert int(only_wall.sum()) >= 100 and _same_bits(L[only_wall], _emitted(mats, mid[only_wall]))
+
+
+def test_a_list_of_the_light_without_area_alone_is_no_list_at_all():
+    """[36]: every light sample is NAN and the radiance is that of num_lights = 0, bit for bit (nl = 1: r0 * 1.0f < 1)"""
+    import direct_oracle as do
+    from scenes import direct_light_list
+
+    W = H = 64
+    sc = direct_light_list([36])
+    hit, _, reason, _, L, counts = _details(sc, W, H, 4)
+    assert hit.all() and (reason == do.NAN).all(), counts
+    none = do.details(sc[0], sc[1], W, H, np.arange(W * H), np.zeros(W * H), 4, lights=np.zeros(0, np.int32))
+    assert (none[2] == do.NOT_DRAWN).all() and _same_bits(L, none[4])
+
+
+def test_other_lists_of_the_same_scene():
+    """[10] (nl = 1) and arange(37) (a list as long as the scene: every triangle a light, most of them not emitters).  Measured:
+    [10]: NOT_FACING 2564, OPEN 12642, OCCLUDED 1178; arange(37): NOT_FACING 2799, NAN 415, OPEN 6272, OCCLUDED 6898."""
+    import direct_oracle as do
+    from scenes import direct_light_list
+
+    _, _, reason, _, _, one = _details(direct_light_list([10]), 64, 64, 4)
+    assert one["OPEN"] > 5000 and one["OCCLUDED"] > 500 and one["NAN"] == 0, one
+    sc = direct_light_list(np.arange(37))
+    _, _, reason, _, _, every = _details(sc, 64, 64, 4)
+    entry = _light_entries(64, 64, 4, 37)
+    assert len(np.unique(entry)) == 37, "every entry of the list is drawn"
+    assert np.all((reason == do.NAN) == (entry == 36))
+    assert every["OPEN"] > 3000 and every["OCCLUDED"] > 3000 and every["NAN"] >= 100, every
+
+
+def test_a_material_of_another_type_takes_no_light(cornell):
+    """types 1 -> 3: measured OTHER_TYPE 13212, NOT_FACING 2091, OPEN 1081 (the glossy surfaces keep their light)"""
+    import direct_oracle as do
+    from scenes import direct_other_type
+
+    sc = direct_other_type()
+    tris, mats, _, _ = sc
+    hit, _, reason, d2, L, counts = _details(sc, 64, 64, 4)
+    assert counts["OTHER_TYPE"] >= 10000, counts
+    mid, _ = _hit_material(sc, 64, 64)
+    assert hit.all() and (mid >= 0).all()
+    other = mats["type"][mid] == 3
+    assert int(other.sum()) > 2500 and _same_bits(L[other], _emitted(mats, mid[other]))
+    assert counts["OPEN"] + counts["OCCLUDED"] >= 500, counts      # (and the other surfaces still cast shadow rays beside them)
+    # the draws go on: every light sample's point, hence its d2, is that of the unchanged scene (within a sample the material is
+    # one, so nothing a sample WRITES shows whether the uniforms after an OTHER_TYPE light sample were drawn: only the restatement's
+    # own account can be held to the contract here)
+    plain = do.details(tris, cornell[1], 64, 64, np.arange(64 * 64), np.zeros(64 * 64), 4)
+    assert _same_bits(plain[3], d2)
+
+
+def test_the_camera_outside_the_box():
+    """From (0, 2.75, -10), behind the back wall.  The triangle test is one-sided (:100), so a wall met from its back is passed
+    through and every hit -- from this camera as from the reference's -- has its HitRecord normal along the ray: :243 negates on
+    every hit, the un-negated side is reached by no ray.  The box's triangles do not "face both ways"; of the cameras tried
+    around the box this one gave the most flipped hits that also cast shadow rays.  Measured, 64 x 64, K = 4: hit = flipped =
+    3592, 3061 of them with an OPEN or OCCLUDED light sample; NOT_DRAWN 2016 (504 misses), NOT_FACING 2617, OPEN 10022,
+    OCCLUDED 1729."""
+    import direct_oracle as do
+    from scenes import direct_from_behind
+
+    hit, flipped, reason, _, _, counts = _details(direct_from_behind(), 64, 64, 4)
+    cast = ((reason == do.R_OPEN) | (reason == do.R_OCCLUDED)).any(axis=1)
+    print("flipped %d, with a shadow ray %d" % (int(flipped.sum()), int((cast & (flipped == 1)).sum())))
+    assert int(flipped.sum()) >= 500 and int((cast & (flipped == 1)).sum()) >= 100
+    assert np.array_equal(flipped, hit)
+    assert 100 < int((hit == 0).sum()) < 64 * 64 - 500      # hits and misses share waves
+
+
+def test_the_glossy_room_lights_every_roughness():
+    """64 x 48, K = 4, frames 0 and 1 (what tests/test_gpu_direct_edges.py renders): an OPEN light sample on a surface of each of
+    the 17 roughnesses.  The reference camera sees seven of the room's 17 glossy materials lit (the others are behind it, face
+    away from the light or are the ceiling the light lies in), so glossy_room() alone reaches 7 roughnesses; the four rooms of
+    GLOSSY_SHIFTS = (0, 1, 4, 13) move every roughness onto one of the seven.  Measured per room, samples with an OPEN light
+    sample on the seven lit materials: 55, 325, 376, 685, 849, 1233, 1303; NaN radiance components: 0 in all four rooms
+    (r = 0 gives D = 0 / 0 only at ct == 1 exactly, which no sample meets)."""
+    import direct_oracle as do
+    from scenes import GLOSSY_SHIFTS, ROUGHNESS, glossy_room
+
+    W, H, K = 64, 48, 4
+    assert GLOSSY_SHIFTS[0] == 0
+    lit_samples = {float(np.float32(r)): 0 for r in ROUGHNESS}
+    assert len(lit_samples) == len(ROUGHNESS) == 17
+    for shift in GLOSSY_SHIFTS:
+        tris, mats = glossy_room(shift)
+        sc = (tris, mats, None, None)
+        nan = 0
+        for frame in (0, 1):
+            hit, _, reason, _, L, _ = _details(sc, W, H, K, frame)
+            mid, _ = _hit_material(sc, W, H, frame)
+            assert np.array_equal(mid >= 0, hit == 1)
+            lit = (reason == do.R_OPEN).any(axis=1)
+            nan += int(np.isnan(L).sum())
+            for r in lit_samples:
+                on = (mid >= 0) & (mats["type"][np.maximum(mid, 0)] == 2) & (mats["roughness"][np.maximum(mid, 0)] == np.float32(r))
+                lit_samples[r] += int((on & lit).sum())
+        print("shift %d: nan count %d" % (shift, nan))
+    print("samples with an OPEN light sample, per roughness:", lit_samples)
+    assert all(v >= 1 for v in lit_samples.values()), lit_samples
+
+
+def test_a_five_by_three_image_has_every_decision(cornell):
+    """15 samples, one partial wave: 11 hit; NOT_FACING 1, OCCLUDED 4, OPEN 39 (and 16 light samples of the 4 misses not drawn)"""
+    import direct_oracle as do
+
+    tris, mats = cornell
+    hit, _, reason, _, _, counts = _details((tris, mats, None, None), 5, 3, 4)
+    dec = do.DECISION_OF[reason]
+    assert 0 < int(hit.sum()) < 15
+    assert all((dec[hit == 1] == k).any() for k in (do.NONE, do.OCCLUDED, do.OPEN)), counts

@@ -17,6 +17,7 @@ import pytest
 from conftest import assert_fb_equal
 from gpu_support import options, render
 from oclpathtracer_amd import shim
+from scenes import ROUGHNESS, glossy_room   # (the roughnesses on both sides of every guard edge: tests/scenes.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -76,40 +77,6 @@ def test_guarded_quotients_equal_ieee_division_on_both_sides_of_every_guard(devi
     assert res[4] == BINADES * BINADES * SIGS
     assert res[5] == (BINADES - 2) * (BINADES - 2) * (SIGS - 1)   # (the +0 numerator is outside it)
     assert res[2] == 0
-
-
-# Roughnesses of the glossy room, on both sides of every guard edge of the GGX branch that a roughness moves:
-#   1 - xi over b = xi (r^2 - 1) + 1, b in [2^-60, 2^60):      b reaches r^2 for r > 1: r = 2^30;  for r < 2^-12, r^2 - 1 rounds
-#                                                              to -1 and b is 1 - xi, +0 (xi = 1) included
-#   r^2 / pi over gd^2, both in [2^-60, 2^60):                 r^2 / pi = 2^-60 at r = sqrt(pi) 2^-30, 2^60 at r = sqrt(pi) 2^30;
-#                                                              gd^2 reaches r^4 for r > 1: r = 2^15 (and r^4 for 2^-12 < r < 1)
-#   D cos / 4 dot(wo, wh) and D / 4 dwin dwon, D < 2^60:       D reaches 1 / (pi r^2): r = 2^-30 / sqrt(pi)
-# and r = 1 (gd == 1 exactly), the Cornell box's own 0.008, the smallest r whose r^4 is a normal number, 0 (D = 0 / 0).
-_SQRT_PI = float(np.sqrt(np.pi))
-ROUGHNESS = [1.0, 0.008, float(np.nextafter(np.float32(2.0 ** -31.5), np.float32(1.0))), 0.0,
-             2.0 ** 30 * 0.99, 2.0 ** 30 * 1.01,
-             _SQRT_PI * 2.0 ** -30 * 0.99, _SQRT_PI * 2.0 ** -30 * 1.01, _SQRT_PI * 2.0 ** 30 * 0.99, _SQRT_PI * 2.0 ** 30 * 1.01,
-             2.0 ** 15 * 0.99, 2.0 ** 15 * 1.01, 2.0 ** -12 * 0.99, 2.0 ** -12 * 1.01,
-             2.0 ** -30 / _SQRT_PI * 0.99, 2.0 ** -30 / _SQRT_PI * 1.01, 0.3]
-
-
-def glossy_room():
-    """The Cornell box with every surface but the light a GGX one, a roughness of ROUGHNESS each"""
-    from oclpathtracer_amd import scene
-
-    tris, mats = scene.load_model()
-    mats = mats.copy()
-    k = 0
-    for m in mats:
-        if m["emissive"][0] != 0.0:
-            continue
-        m["type"] = scene.SPECULAR
-        m["roughness"] = np.float32(ROUGHNESS[k % len(ROUGHNESS)])
-        if m["albedo"][0] > 0.6:
-            m["albedo"] = (0.5, 0.35, 0.05, 0.0)   # (a GGX weight is 2 albedo g dwin / pdf: keep long paths finite)
-        k += 1
-    assert k >= len(ROUGHNESS)
-    return tris, mats
 
 
 def test_smallest_roughness_with_a_normal_fourth_power():
