@@ -474,6 +474,51 @@ int pt_render_direct(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materia
                      pt_buffer_t framebuffer, const pt_direct_params* params, const pt_camera* cam /* NULL = the reference's */,
                      pt_event_t ev);
 
+/* ---- indirect illumination -----------------------------------------------------------------------------------------
+ * The IndirectIllumination case the reference's harness declares (test/RaytraceTest.cpp:301-303) with an empty body: the
+ * renderer's multi-bounce walk (traceRays, GenerateColors.cl:223-261) with direct illumination's light sample taken at every
+ * vertex of the path, not only the first.  Every operation is binary32 under the arithmetic contract of the renderer.
+ * A sample of pixel gid in frame z, with B = max_bounces >= 1, K = light_samples and nl = num_lights:
+ *  1. The seed, the primary ray (o, d) and the camera are exactly those of pt_render_direct step 1.  L = 0 and mask = 1 per channel.
+ *  2. For i = 0 .. B-1: the closest hit of (o, d) from 1e20 (:137-154).  A miss gives L += mask * max(0.45, 0) (:235) and the path
+ *     ends.  On a hit, in this order:
+ *     a. the surface: m, p, n (turned to face the ray, :243) and wo = -d as in pt_render_direct step 2, the material's index clamped;
+ *     b. the emission L.c = L.c + mask.c * m.emissive.c * 3.0f (:241, in that order), applied when i == 0 or nl == 0.  With a
+ *        light list the emitted light of later vertices is what step c of the vertex before has sampled already, so it is not
+ *        added a second time: THE LIST MUST HOLD EVERY EMISSIVE TRIANGLE of the scene for the image to be unbiased (the emitters
+ *        of scene.emitters; a shorter list loses the light of the triangles left out at every vertex but the first);
+ *     c. the light samples, when nl > 0: S = 0; K light samples on the same seed exactly as pt_render_direct steps 3a-3g at the
+ *        vertex (p, n, wo, m) -- three uniforms always drawn per sample, the shadow ray through the any-hit search, an open ray
+ *        adds c to S --; then L.c = L.c + mask.c * (S.c / (float)K);
+ *     d. the BRDF sample: Brdf (:195-221) as the renderer shades it, two uniforms (phi first), giving wi, pdf and color;
+ *        pdf <= 0 ends the path (:251); otherwise mask.c *= (color.c * dot(wi, n)) / pdf (three IEEE quotients, :253-255) and the
+ *        next ray is getRay(p + wi * 0.01f, wi) (:257).  At i == B-1 the draw cannot be observed and may be skipped.
+ *  3. L = max(L, 0) per channel with the reference's max (:260).
+ *  4. L goes to the samples workspace and is folded by the renderer's fold exactly as pt_render_direct step 5; the chunks, the
+ *     stripe layout and the frame_begin = 0 rule are direct's.
+ * Light samples come before the BRDF sample at every vertex.  Two identities follow:
+ *  - nl == 0: no light uniform is drawn, and the framebuffer is pt_render_frames' at the same max_bounces, bit for bit;
+ *  - B == 1: the framebuffer is pt_render_direct's, bit for bit -- for emission that is not negative: with an emissive component
+ *    of -0 direct forms E + S / K from E = -0 where this forms 0 + E = +0 first; that case is excluded.
+ * Not done here: multiple importance sampling (a BRDF ray that finds a light adds nothing at i > 0, so glossy surfaces next to
+ * a light are noisy), light choice by power, Russian roulette.
+ * Behaviour: pt_render_direct's, word for word -- the handle's stream, behind renders in flight, asynchronous (ev); the prepared
+ * scene, LBVH and filter tables as a query uses them; no allocation and no wait once the scene is prepared; PT_OPT_ACCEL and
+ * PT_OPT_QUAD_FILTER choose the search; PT_ERR_TRAVERSAL is deferred; num_triangles = 0 renders the background.  Errors are
+ * pt_render_direct's, before anything is enqueued, plus PT_ERR_INVALID for max_bounces outside 1..65535. */
+typedef struct pt_indirect_params {
+    int32_t width, height, frame_begin, frame_count;   /* as pt_direct_params */
+    int32_t num_triangles, num_materials, num_lights;
+    int32_t light_samples;                             /* K, 1..256, per vertex */
+    int32_t stripe_rows, n_ranks, rank;
+    int32_t max_bounces;                               /* B, 1..65535 */
+    int32_t reserved[4];                               /* must be 0 */
+} pt_indirect_params;                                  /* 64 bytes */
+int pt_render_indirect(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                       pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, pt_buffer_t samples /* workspace */,
+                       pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam /* NULL = the reference's */,
+                       pt_event_t ev);
+
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.
  * pt_profile_query synchronises the stream and returns the summed duration and launch count

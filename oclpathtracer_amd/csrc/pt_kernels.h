@@ -293,6 +293,15 @@ struct PtDirectParams {
 // per SIMD, so ptk_query_bvh_blocks_per_cu's premise (five waves) does not hold for it
 hipError_t ptk_direct(const PtDirectParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s);
 int ptk_direct_bvh_blocks_per_cu(void);
+// indirect illumination (pt_render_indirect): direct illumination's launch with the path's depth.  samples[item] = max(L, 0) of the
+// whole path; everything else is as PtDirectParams says (the helpers of both take its PtDirectParams)
+struct PtIndirectParams {
+    PtDirectParams d;
+    int32_t B;                    // max_bounces, 1 .. 65535
+};
+// bvh_blocks: CUs x ptk_indirect_bvh_blocks_per_cu -- the LBVH kernel's own occupancy (a path's state is larger than a direct sample's)
+hipError_t ptk_indirect(const PtIndirectParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s);
+int ptk_indirect_bvh_blocks_per_cu(void);
 // rays[2 gid], rays[2 gid + 1] = the pt_ray of pixel gid, frame `frame` (the renderer's sample start) for the camera cam
 hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s);
 // dynamic LDS of a trace workgroup (pt_kernels.hip: pt_lds_total, pt_bvh_lds_total)

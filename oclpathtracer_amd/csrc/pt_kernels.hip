@@ -3190,6 +3190,240 @@ void pt_direct_bvh_kernel(const PtDirectParams D)
 }
 
 // ------------------------------------------------------------------------------------------
+// indirect illumination (pt_render_indirect)
+// ------------------------------------------------------------------------------------------
+// The renderer's multi-bounce walk (traceRays, :223-261) with direct illumination's light sample taken at every vertex
+// (include/pt_shim.h states every step and its order).  One work item is one sample (pt_item_begin).  For i = 0 .. B-1: the closest
+// hit from 1e20; a miss adds mask * max(0.45, 0) and ends the path.  On a hit: the surface (pt_direct_surface), the emission when
+// i == 0 or there are no lights, K light samples (pt_direct_light) whose open shadow rays sum to S and L += mask * (S / K), then the
+// BRDF sample (pt_indirect_bounce), which ends the path at pdf <= 0 and otherwise scales mask and gives the next ray.
+// samples[item] = max(L, 0); pt_fold_kernel folds them.
+
+// The BRDF sample at the vertex (p, n, wo) on material mid: Brdf (:195-221) and :251-257 as pt_shade states them -- the same draws
+// (phi, then the second uniform), the same shared sqrt pair, the same guarded short quotients (pt_div_by, pt_div, pt_div_pair,
+// pt_div3) and near-1 normalisations (normalize3_unit).  A second statement of pt_shade's bounce, kept apart so that the renderer's
+// kernels do not move; with no lights the two must agree bit for bit (tests/test_gpu_indirect.py).  False: pdf <= 0, the path ends
+// (:251); true: mask has taken the bounce's three quotients and (o, d) is the next ray (:257).  The material is gathered by its index
+// (pt_direct_light's gathers): nothing of it is held across a search.
+PTK_DEV bool pt_indirect_bounce(const PtDirectParams& D, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed, f3& mask, f3& o,
+                                f3& d)
+{
+    const float phi = PTK_TWO_PI * pt_random_float(seed);
+    const float xi = pt_random_float(seed);
+    float sp, cp;
+    pt_sincos(phi, sp, cp);
+    const float4 alb = pt_rec16(D.t.mats, mid, 0u), rt = pt_rec16(D.t.mats, mid, 32u);   // albedo | roughness, type
+    const float rough = rt.x;
+    const int type = __float_as_int(rt.y);
+
+    // sampleHemisphereCosine (:161-172) and sampleGGX (:180-192) share everything except (sinTheta, cosTheta)
+    const f3 axis = __builtin_fabsf(n.x) > 0.001f ? mk3(0.0f, 1.0f, 0.0f) : mk3(1.0f, 0.0f, 0.0f);
+    const f3 tv = normalize3(cross3(axis, n));
+    const f3 sv = cross3(n, tv);
+    float cos_arg = 1.0f - xi;
+    if (type == 2) cos_arg = pt_div_by(cos_arg, xi * (rough * rough - 1.0f) + 1.0f);   // (1 - xi is +0 or in [2^-24, 1]: pt_shade)
+    const float cosTheta = pt_sqrt(cos_arg);
+    const float sin_arg = type == 2 ? pt_max(0.0f, 1.0f - cosTheta * cosTheta) : xi;
+    const float sinTheta = pt_sqrt(sin_arg);
+    const f3 a = scale3(scale3(sv, cp), sinTheta);
+    const f3 b = scale3(scale3(tv, sp), sinTheta);
+    const f3 c = scale3(n, cosTheta);
+    const f3 sdir = normalize3_unit(add3(add3(a, b), c));
+
+    f3 wi = sdir;
+    f3 color = mk3(0.0f, 0.0f, 0.0f);
+    float pdf = 0.0f;
+    float dwin = 0.0f;
+    if (type == 1) {   // DIFFUSE (:197-204)
+        dwin = dot3(wi, n);
+        pdf = dwin * PTK_INV_PI;
+        color = mk3(alb.x * PTK_INV_PI, alb.y * PTK_INV_PI, alb.z * PTK_INV_PI);
+    } else if (type == 2) {   // SPECULAR (:205-218)
+        const float k2 = 2.0f * dot3(wo, sdir);
+        wi = add3(neg3(wo), scale3(sdir, k2));   // reflect(wo, wh) (:156-159)
+        dwin = dot3(wi, n);
+        const float dwon = dot3(wo, n);
+        if (!(dwin * dwon < 0.0f)) {
+            const float r2 = rough * rough;
+            const float gd = cosTheta * cosTheta * (r2 - 1.0f) + 1.0f;
+            const float Dg = pt_div(r2 * PTK_INV_PI, gd * gd);   // pow(x, 2.0f) is x*x in PTSPEC (:177)
+            float g;
+            pt_div_pair(Dg * cosTheta, 4.0f * dot3(wo, sdir), Dg, 4.0f * dwin * dwon, pdf, g);   // (one guard for both: pt_shade)
+            color = mk3(alb.x * g * 2.0f, alb.y * g * 2.0f, alb.z * g * 2.0f);
+        }
+    }
+    if (pdf <= 0.0f) return false;   // :251
+    float qx = color.x * dwin, qy = color.y * dwin, qz = color.z * dwin;
+    pt_div3(qx, qy, qz, pdf);   // the three IEEE quotients of :253-255
+    mask.x = mask.x * qx;
+    mask.y = mask.y * qy;
+    mask.z = mask.z * qz;
+    o = add3(p, scale3(wi, 0.01f));   // :257
+    d = normalize3_unit(wi);
+    return true;
+}
+
+// :241, in that order
+PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f3& mask, f3& L)
+{
+    const float4 emi = pt_rec16(D.t.mats, mid, 16u);
+    L.x = L.x + mask.x * emi.x * 3.0f;
+    L.y = L.y + mask.y * emi.y * 3.0f;
+    L.z = L.z + mask.z * emi.z * 3.0f;
+}
+
+// L += mask * (S / K) of a vertex's light samples
+PTK_DEV void pt_indirect_lit(const PtDirectParams& D, const f3& mask, const f3& S, f3& L)
+{
+    const float Kf = (float)D.K;
+    L.x = L.x + mask.x * (S.x / Kf);
+    L.y = L.y + mask.y * (S.y / Kf);
+    L.z = L.z + mask.z * (S.z / Kf);
+}
+
+PTK_DEV void pt_indirect_store(const PtDirectParams& D, unsigned item, const f3& L)   // :260
+{
+    pt_direct_store(D, item, mk3(pt_max(L.x, 0.0f), pt_max(L.y, 0.0f), pt_max(L.z, 0.0f)));
+}
+
+// brute force: one wave = 64 consecutive samples, pt_direct_kernel's shape inside a loop over the bounces.  The wave searches in step
+// with the lanes still alive and leaves the loop when none is; a light sample no lane casts a ray for costs no search.  Lanes whose
+// path has ended are NOT given new samples: the wave runs as long as its longest path (DESIGN.md S4 states the cost).
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtIndirectParams I)
+{
+    const PtDirectParams& D = I.d;
+    const PtTraceParams& P = D.t;
+    const unsigned lane = pt_lane_id();
+    const int ntri = P.ntri;
+    PtTail tl = pt_table_wg_setup<LDS_TABLE>(P, lane);
+    const f3 anchor = mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]);
+    const unsigned item = pt_wave() * 64u + lane;
+    const bool act = item < D.nitems;
+    unsigned lp = 0u;
+    uint32_t seed = 0u;
+    f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f);
+    if (act) pt_item_begin(P, D.cam, D.npix, D.frame0, item, lp, seed, o, d);
+    f3 L = mk3(0.0f, 0.0f, 0.0f), mask = mk3(1.0f, 1.0f, 1.0f);
+    bool alive = act;
+    for (int i = 0; i < I.B; ++i) {
+        float tmax = 1e20f, hu = 0.0f, hv = 0.0f;
+        int hidx = -1;
+        pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, alive, tmax, hu, hv, hidx,
+                                                             P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+        const bool hit = alive & (hidx >= 0);
+        if (alive & !hit) L = add3(L, scale3(mask, pt_max(0.45f, 0.0f)));   // :235
+        alive = hit;
+        if (__ballot(hit) == 0ull) break;
+        f3 p = o, n = d, wo = d;
+        unsigned mid = 0u;
+        if (hit) {
+            pt_direct_surface(D, o, d, tmax, hu, hv, hidx, p, n, wo, mid);
+            if (i == 0 || D.nl == 0) pt_indirect_emission(D, mid, mask, L);
+        }
+        if (D.nl > 0) {
+            f3 S = mk3(0.0f, 0.0f, 0.0f);
+            for (int k = 0; k < D.K; ++k) {
+                f3 c = mk3(0.0f, 0.0f, 0.0f);
+                float tlim = 0.0f;
+                bool cast = false;
+                if (hit) cast = pt_direct_light(D, p, n, wo, mid, seed, c, o, d, tlim);
+                const bool live = cast & (tlim > 0.0f);
+                bool occluded = false;
+                if (__ballot(live) != 0ull) {
+                    float t = live ? tlim : 0.0f, su = 0.0f, sv = 0.0f;
+                    int sidx = -1;
+                    pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, live, t, su, sv, sidx,
+                                                                         P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+                    occluded = live & (sidx >= 0) & (t < tlim);   // pt_query_store's occlusion test
+                }
+                if (cast & !occluded) S = add3(S, c);
+            }
+            if (hit) pt_indirect_lit(D, mask, S, L);
+        }
+        if (i == I.B - 1) break;   // (the last vertex's draw cannot be observed)
+        if (hit) alive = pt_indirect_bounce(D, p, n, wo, mid, seed, mask, o, d);
+        if (__ballot(alive) == 0ull) break;
+    }
+    if (act) pt_indirect_store(D, item, L);
+}
+
+// LBVH (pt_bvh_drive): one item = one sample; the lane walks its path as a sequence of searches -- per vertex the closest search, then
+// the any-hit searches of the light samples that contribute -- and is free only when the sample is stored.  next_ray is the state
+// machine between two searches: a closest result leads to the surface, the emission and the first contributing light sample; an
+// any-hit result to the next contributing one; after the last comes the BRDF sample and the next closest search, or the store.
+// Between searches a lane holds PtDirectWork's state (the surface p, n, wo, the material's INDEX, S, c) and mask, L and the bounce.
+// wo is the negated incoming direction, which the shadow rays overwrite in d, so it is kept; o is dead while p is live.
+struct PtIndirectWork {
+    static constexpr bool ANY = true;
+    const PtIndirectParams& I;
+    unsigned n;
+    int k;           // the current ray: -1 = the vertex's closest search, 0 .. K-1 = the shadow ray of light sample k
+    int bounce;      // loop index i of traceRays (:229)
+    unsigned item, mid;
+    uint32_t seed;
+    float tl;        // the shadow ray's limit
+    f3 o, d, p, nrm, wo, S, c, mask, L;
+    PTK_DEV void begin(unsigned item_)
+    {
+        unsigned lp;
+        item = item_;
+        pt_item_begin(I.d.t, I.d.cam, I.d.npix, I.d.frame0, item, lp, seed, o, d);
+        k = -1;
+        bounce = 0;
+        mask = mk3(1.0f, 1.0f, 1.0f);
+        L = mk3(0.0f, 0.0f, 0.0f);
+    }
+    PTK_DEV bool next_ray(const PtBvhLane& R)
+    {
+        const PtDirectParams& D = I.d;
+        if (k < 0) {
+            if (R.hidx < 0) {
+                L = add3(L, scale3(mask, pt_max(0.45f, 0.0f)));   // :235
+                pt_indirect_store(D, item, L);
+                return false;
+            }
+            pt_direct_surface(D, o, d, R.tmax, R.hu, R.hv, R.hidx, p, nrm, wo, mid);
+            if (bounce == 0 || D.nl == 0) pt_indirect_emission(D, mid, mask, L);
+            S = mk3(0.0f, 0.0f, 0.0f);
+        } else if (R.hidx < 0) {   // (an any-hit search: R.hidx >= 0 alone says occluded; a ray that searched nothing is open)
+            S = add3(S, c);
+        }
+        if (D.nl > 0) {
+            while (++k < D.K)
+                if (pt_direct_light(D, p, nrm, wo, mid, seed, c, o, d, tl)) return true;
+            pt_indirect_lit(D, mask, S, L);
+        }
+        if (++bounce < I.B && pt_indirect_bounce(D, p, nrm, wo, mid, seed, mask, o, d)) {
+            k = -1;
+            return true;
+        }
+        pt_indirect_store(D, item, L);
+        return false;
+    }
+    PTK_DEV const f3& org() const { return o; }
+    PTK_DEV const f3& dir() const { return d; }
+    PTK_DEV float limit() const { return k < 0 ? 1e20f : tl; }
+    PTK_DEV bool live() const { return k < 0 || tl > 0.0f; }
+    PTK_DEV bool any() const { return k >= 0; }
+};
+
+// Three waves per SIMD (168 VGPRs), chosen from the compiler's resource report (profiles/indirect/kernel_resources.txt): a path's
+// state between its searches is 33 registers against direct's 25, and at direct's four waves (128 VGPRs) the kernel spills 25 of
+// them to scratch; at three it uses 158-159 and spills none.  Its persistent grid is its own figure, ptk_indirect_bvh_blocks_per_cu
+#ifndef PT_INDIRECT_BVH_WAVES   // (tools/kernel_resources.sh -DPT_INDIRECT_BVH_WAVES=4 reads the other choice)
+#define PT_INDIRECT_BVH_WAVES 3
+#endif
+template <bool DET_BOUNDED, int BIGQ>
+__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_INDIRECT_BVH_WAVES, PT_INDIRECT_BVH_WAVES)))
+void pt_indirect_bvh_kernel(const PtIndirectParams I)
+{
+    const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
+    PtIndirectWork W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0 };
+    pt_bvh_drive<DET_BOUNDED, BIGQ>(I.d.t, W);
+}
+
+// ------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------
 hipError_t ptk_prep_triangles(const PtRawTriangle* raw, PtPrepTriangle* out, int ntri, unsigned int* det_bound_bits,
@@ -3337,15 +3571,14 @@ template <class Kernel> static Kernel pt_pick(bool det_bounded, bool q3, Kernel 
     return det_bounded ? (q3 ? k3 : k0) : unbounded;
 }
 
-// One launch of a kernel whose waves take 64 items each -- LBVH: a persistent grid of at most bvh_blocks workgroups (what the chip
+// One launch of a kernel whose waves take 64 items each over a scene of ntri triangles -- LBVH: a persistent grid of at most bvh_blocks workgroups (what the chip
 // holds) with the trace kernel's LDS; brute force: one wave per 64 items, the table kernels' LDS without the pools
 template <class Params>
-static hipError_t pt_launch_search(void (*kernel)(const Params), const Params& p, unsigned nitems, bool bvh, int bvh_blocks, hipStream_t s)
+static hipError_t pt_launch_search(void (*kernel)(const Params), const Params& p, int ntri, unsigned nitems, bool bvh, int bvh_blocks, hipStream_t s)
 {
     const unsigned wg_waves = PT_TRACE_THREADS / 64;
     unsigned blocks = ((nitems + 63u) / 64u + wg_waves - 1u) / wg_waves;
     if (bvh && bvh_blocks > 0 && blocks > (unsigned)bvh_blocks) blocks = (unsigned)bvh_blocks;
-    const int ntri = p.t.ntri;
     const size_t lds = bvh ? ptk_trace_bvh_lds_bytes()
                            : (size_t)(ntri <= PT_LDS_TRI_MAX ? pt_lds_total<1, false>(ntri) : pt_lds_total<2, false>(ntri)) * sizeof(float);
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(PT_TRACE_THREADS), lds, s, p);
@@ -3361,7 +3594,7 @@ hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, PtSearchMode m, boo
     else if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_query_bvh_kernel<true, 3, false>, pt_query_bvh_kernel<true, 0, false>, pt_query_bvh_kernel<false, 0, false>);
     else if (q.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_query_kernel<true, 1, 3>, pt_query_kernel<true, 1, 0>, pt_query_kernel<false, 1, 0>);
     else kernel = m.det_bounded ? pt_query_kernel<true, 2, 0> : pt_query_kernel<false, 2, 0>;
-    return pt_launch_search(kernel, q, q.nrays, m.bvh, bvh_blocks, s);
+    return pt_launch_search(kernel, q, q.t.ntri, q.nrays, m.bvh, bvh_blocks, s);
 }
 
 hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
@@ -3372,7 +3605,7 @@ hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream
     if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_ao_bvh_kernel<true, 3>, pt_ao_bvh_kernel<true, 0>, pt_ao_bvh_kernel<false, 0>);
     else if (a.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_ao_kernel<true, 1, 3>, pt_ao_kernel<true, 1, 0>, pt_ao_kernel<false, 1, 0>);
     else kernel = m.det_bounded ? pt_ao_kernel<true, 2, 0> : pt_ao_kernel<false, 2, 0>;
-    return pt_launch_search(kernel, a, a.nitems, m.bvh, bvh_blocks, s);
+    return pt_launch_search(kernel, a, a.t.ntri, a.nitems, m.bvh, bvh_blocks, s);
 }
 
 hipError_t ptk_direct(const PtDirectParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
@@ -3383,10 +3616,23 @@ hipError_t ptk_direct(const PtDirectParams& a, int bvh_blocks, PtSearchMode m, h
     if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_direct_bvh_kernel<true, 3>, pt_direct_bvh_kernel<true, 0>, pt_direct_bvh_kernel<false, 0>);
     else if (a.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_direct_kernel<true, 1, 3>, pt_direct_kernel<true, 1, 0>, pt_direct_kernel<false, 1, 0>);
     else kernel = m.det_bounded ? pt_direct_kernel<true, 2, 0> : pt_direct_kernel<false, 2, 0>;
-    return pt_launch_search(kernel, a, a.nitems, m.bvh, bvh_blocks, s);
+    return pt_launch_search(kernel, a, a.t.ntri, a.nitems, m.bvh, bvh_blocks, s);
 }
 
 int ptk_direct_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_direct_bvh_kernel<true, 3>, ptk_trace_bvh_lds_bytes()); }
+
+hipError_t ptk_indirect(const PtIndirectParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
+{
+    if (a.d.nitems == 0) return hipSuccess;
+    const bool q3 = m.quads == 3;
+    void (*kernel)(const PtIndirectParams);
+    if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3>, pt_indirect_bvh_kernel<true, 0>, pt_indirect_bvh_kernel<false, 0>);
+    else if (a.d.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_kernel<true, 1, 3>, pt_indirect_kernel<true, 1, 0>, pt_indirect_kernel<false, 1, 0>);
+    else kernel = m.det_bounded ? pt_indirect_kernel<true, 2, 0> : pt_indirect_kernel<false, 2, 0>;
+    return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, m.bvh, bvh_blocks, s);
+}
+
+int ptk_indirect_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3>, ptk_trace_bvh_lds_bytes()); }
 
 hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s)
 {

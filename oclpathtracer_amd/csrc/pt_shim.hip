@@ -137,6 +137,7 @@ struct pt_device_s {
     int bvh_blocks_per_cu;
     int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query and ambient-occlusion kernels (pt_bvh_drive)
     int direct_bvh_blocks_per_cu;  // ... and of the direct-illumination kernel, which runs at four waves per SIMD
+    int indirect_bvh_blocks_per_cu;   // ... and of the indirect-illumination kernel, at its own occupancy
     unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
     unsigned int* trav_dev;  // ... as the device addresses it
     // ---- fused-render workspace: the STREAMING renderer (render_part, plan_chunks, the ring).  A render walks its frames in chunks of
@@ -358,6 +359,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->bvh_blocks_per_cu = ptk_trace_bvh_blocks_per_cu();
     d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
     d->direct_bvh_blocks_per_cu = ptk_direct_bvh_blocks_per_cu();
+    d->indirect_bvh_blocks_per_cu = ptk_indirect_bvh_blocks_per_cu();
     *out = d;
     return PT_OK;
 }
@@ -1762,29 +1764,28 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
 
 // ---- direct illumination (include/pt_shim.h) -----------------------------------------------------------------------------------
 static_assert(sizeof(pt_direct_params) == 64, "pt_direct_params layout");
+static_assert(sizeof(pt_indirect_params) == 64, "pt_indirect_params layout");
 
-extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
-                                pt_buffer_t framebuffer, const pt_direct_params* params, const pt_camera* cam, pt_event_t ev)
+// pt_render_direct and pt_render_indirect: one validation, one chunk loop.  `a`: the fields the two parameter blocks share (each
+// entry point has looked at its own reserved ones).  max_bounces: 0 = direct illumination (its own kernels), otherwise the depth of
+// an indirect render.  what: the message for a field out of range
+static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples, pt_buffer_t framebuffer,
+                      const pt_direct_params& a, int max_bounces, const char* what, const pt_camera* cam, pt_event_t ev)
 {
-    int rc = use_device(d);
-    if (rc) return rc;
-    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
-    const pt_direct_params a = *params;
+    int rc;
     PtCamera c = reference_camera();
     if (cam && (rc = camera_derive(cam, &c))) return rc;
     if (!triangles || !materials || !samples || !framebuffer) return fail(PT_ERR_INVALID, "null buffer handle");
     if ((rc = check_same_device(d, { triangles, materials, lights, samples, framebuffer })) || (rc = check_event(d, ev))) return rc;
     if (a.num_triangles < 0 || a.num_materials < 1 || a.num_lights < 0 || a.light_samples < 1 || a.light_samples > 256)
-        return fail(PT_ERR_INVALID, "invalid direct-illumination parameters");
+        return fail(PT_ERR_INVALID, "%s", what);
     if (a.num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
     if (a.num_lights > 0 && !lights) return fail(PT_ERR_INVALID, "num_lights > 0 needs a light list");
     // the light's record and the materials are gathered by 32-bit byte offsets into the 64-byte records, as shading gathers them
     if ((uint64_t)a.num_triangles * 64u > 0xffffffffull || (uint64_t)a.num_materials * 64u > 0xffffffffull)
         return fail(PT_ERR_INVALID, "a scene has fewer than 2^26 triangles and 2^26 materials");
-    for (int i = 0; i < 5; ++i)
-        if (a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
     uint64_t npix64;
-    if ((rc = check_image("invalid direct-illumination parameters", a.width, a.height, a.frame_begin, a.frame_count, a.stripe_rows, a.n_ranks, a.rank, npix64)))
+    if ((rc = check_image(what, a.width, a.height, a.frame_begin, a.frame_count, a.stripe_rows, a.n_ranks, a.rank, npix64)))
         return rc;
     const uint32_t npix = (uint32_t)npix64;
     const size_t frame_bytes = (size_t)npix * 12, fb_bytes = (size_t)npix * sizeof(float4), light_bytes = (size_t)a.num_lights * sizeof(int32_t);
@@ -1811,8 +1812,10 @@ extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_
     PtSearch search;
     if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
     if ((rc = event_begin(d, ev))) return rc;
-    PtDirectParams p;
-    memset(&p, 0, sizeof p);
+    PtIndirectParams ip;
+    memset(&ip, 0, sizeof ip);
+    ip.B = max_bounces;
+    PtDirectParams& p = ip.d;
     search_fields(d, search, p.t);   // (an empty scene: the brute-force form over zero triangles, every sample the background)
     image_geometry(p.t, a.width, a.height, a.stripe_rows, a.n_ranks, a.rank, npix);
     p.t.mats = (const PtRawMaterial*)materials->dptr;
@@ -1828,14 +1831,15 @@ extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_
     fp.rad = p.samples;
     fp.fb = (float4*)framebuffer->dptr;
     fp.npix_local = npix;
-    const int bvh_blocks = search.mode.bvh ? d->prop.multiProcessorCount * d->direct_bvh_blocks_per_cu : 0;   // (its own grid: pt_kernels.h)
+    const int bvh_blocks = !search.mode.bvh ? 0   // (each kernel its own grid: pt_kernels.h)
+                                            : d->prop.multiProcessorCount * (max_bounces > 0 ? d->indirect_bvh_blocks_per_cu : d->direct_bvh_blocks_per_cu);
     // whole frames per chunk: what the workspace holds, fewer than 2^31 samples per launch; a launch, then its fold
     const int64_t per_chunk = (int64_t)std::min<uint64_t>(samples->bytes / frame_bytes, 0x7fffffffu / npix);
     for (int64_t done = 0; done < a.frame_count; done += per_chunk) {
         const int nf = (int)std::min<int64_t>(per_chunk, a.frame_count - done);
         p.frame0 = a.frame_begin + (int)done;
         p.nitems = (uint32_t)nf * npix;
-        HIP_TRY(ptk_direct(p, bvh_blocks, search.mode, d->stream));
+        HIP_TRY(max_bounces > 0 ? ptk_indirect(ip, bvh_blocks, search.mode, d->stream) : ptk_direct(p, bvh_blocks, search.mode, d->stream));
         fp.frame_begin = p.frame0;
         fp.frame_count = nf;
         HIP_TRY(ptk_fold(fp, d->stream));
@@ -1843,6 +1847,38 @@ extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_
     samples->version++;
     framebuffer->version++;
     return event_end(d, ev);
+}
+
+extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
+                                pt_buffer_t framebuffer, const pt_direct_params* params, const pt_camera* cam, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
+    const pt_direct_params a = *params;
+    for (int i = 0; i < 5; ++i)
+        if (a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    return render_lit(d, triangles, materials, lights, samples, framebuffer, a, 0, "invalid direct-illumination parameters", cam, ev);
+}
+
+// ---- indirect illumination (include/pt_shim.h) ---------------------------------------------------------------------------------
+extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
+                                  pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
+    const pt_indirect_params b = *params;
+    if (b.max_bounces < 1 || b.max_bounces > 65535) return fail(PT_ERR_INVALID, "max_bounces must lie in 1..65535");
+    for (int i = 0; i < 4; ++i)
+        if (b.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    pt_direct_params a;   // the shared fields, in direct's block
+    memset(&a, 0, sizeof a);
+    a.width = b.width; a.height = b.height; a.frame_begin = b.frame_begin; a.frame_count = b.frame_count;
+    a.num_triangles = b.num_triangles; a.num_materials = b.num_materials; a.num_lights = b.num_lights;
+    a.light_samples = b.light_samples;
+    a.stripe_rows = b.stripe_rows; a.n_ranks = b.n_ranks; a.rank = b.rank;
+    return render_lit(d, triangles, materials, lights, samples, framebuffer, a, b.max_bounces, "invalid indirect-illumination parameters", cam, ev);
 }
 
 extern "C" int pt_camera_rays(pt_device_t d, const pt_camera* cam, int width, int height, int frame, pt_buffer_t rays, pt_event_t ev)

@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination | --only IndirectIllumination]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <chrono>
 #include <cmath>
@@ -361,7 +361,11 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
 // renders the scene lit directly by its emitters through pt_render_direct -- dim x dim, --frames frames, K = 4 light samples; the
 // light list is built here: the triangles whose material has an emissive component above 0, ascending -- and writes
 // directIllumination_<version>.ppm through pt_tonemap_ppm, as RayCast writes its image.  Run only when asked for (--only).
-static void test_DirectIllumination(DeviceTest& f, const Options& o)
+//
+// TEST_F(DeviceTest, IndirectIllumination): likewise declared empty (RaytraceTest.cpp:301-303).  Here it is the same scene through
+// pt_render_indirect -- paths of 16 bounces, K = 1 light sample at every vertex -- written to indirectIllumination_<version>.ppm.
+// bounces: 0 = DirectIllumination, otherwise IndirectIllumination at that depth.
+static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
 {
     Device* m_d = f.m_d;
     std::vector<Triangle> triangles;
@@ -397,19 +401,35 @@ static void test_DirectIllumination(DeviceTest& f, const Options& o)
     p.num_triangles = (int)triangles.size();
     p.num_materials = (int)materials.size();
     p.num_lights = (int)lights.size();
-    p.light_samples = 4;
+    p.light_samples = bounces ? 1 : 4;
     p.stripe_rows = 1; p.n_ranks = 1; p.rank = 0;
+    pt_indirect_params q;   // the same fields, and the depth
+    std::memset(&q, 0, sizeof q);
+    q.width = p.width; q.height = p.height;
+    q.frame_begin = p.frame_begin; q.frame_count = p.frame_count;
+    q.num_triangles = p.num_triangles; q.num_materials = p.num_materials; q.num_lights = p.num_lights;
+    q.light_samples = p.light_samples;
+    q.stripe_rows = 1; q.n_ranks = 1; q.rank = 0;
+    q.max_bounces = bounces;
     auto t0 = std::chrono::steady_clock::now();
-    IASSERT(pt_render_direct(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lights.empty() ? 0 : lBuffer.m_handle, samples.m_handle,
-                             image.m_handle, &p, 0, 0) == PT_OK);
+    if (bounces)
+        IASSERT(pt_render_indirect(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lights.empty() ? 0 : lBuffer.m_handle, samples.m_handle,
+                                   image.m_handle, &q, 0, 0) == PT_OK);
+    else
+        IASSERT(pt_render_direct(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lights.empty() ? 0 : lBuffer.m_handle, samples.m_handle,
+                                 image.m_handle, &p, 0, 0) == PT_OK);
     IASSERT(pt_tonemap_ppm(m_d->m_handle, image.m_handle, rgb.m_handle, npix, 0) == PT_OK);
     std::vector<int> h(3 * npix, 0);
     rgb.read(h.data(), 3 * npix);
     DeviceUtils::waitForCompletion(m_d);
     double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    std::printf("DirectIllumination: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", dimension, dimension, o.frames, (int)lights.size(), secs);
+    if (bounces)
+        std::printf("IndirectIllumination: %d x %d x %d frames, %d bounces, K = 1, %d lights in %.3f s\n", dimension, dimension, o.frames, bounces,
+                    (int)lights.size(), secs);
+    else
+        std::printf("DirectIllumination: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", dimension, dimension, o.frames, (int)lights.size(), secs);
     char path[512];
-    f.getFilePath(o.outDir.c_str(), "directIllumination", "ppm", path, sizeof path);
+    f.getFilePath(o.outDir.c_str(), bounces ? "indirectIllumination" : "directIllumination", "ppm", path, sizeof path);
     FILE* fp = std::fopen(path, "w");
     IASSERT(fp != 0);
     if (fp) {
@@ -439,10 +459,10 @@ int main(int argc, char** argv)
     if (o.dim < 1 || o.frames < 0) { std::fprintf(stderr, "bad --dim/--frames\n"); return 2; }
     struct { const char* name; int kind; } tests[] = { { "initialize", 0 }, { "deviceInfo", 1 }, { "MemoryAllocation", 2 }, { "writeRead", 3 },
                                                        { "getHostPtr", 4 }, { "kernelExecution", 5 }, { "RayCast", 6 },
-                                                       { "AmbientOcclusion", 7 }, { "DirectIllumination", 8 } };
+                                                       { "AmbientOcclusion", 7 }, { "DirectIllumination", 8 }, { "IndirectIllumination", 9 } };
     for (auto& t : tests) {
         if (!o.only.empty() && o.only != t.name) continue;
-        if (o.only.empty() && t.kind >= 7) continue;   // AmbientOcclusion and DirectIllumination run only when asked for: the default run is RaytraceTest's seven cases
+        if (o.only.empty() && t.kind >= 7) continue;   // AmbientOcclusion, DirectIllumination and IndirectIllumination run only when asked for: the default run is RaytraceTest's seven cases
         std::printf("[ RUN      ] DeviceTest.%s\n", t.name);
         int before = g_failures;
         DeviceTest f;
@@ -455,7 +475,8 @@ int main(int argc, char** argv)
         case 5: test_kernelExecution(f); break;
         case 6: test_RayCast(f, o); break;
         case 7: test_AmbientOcclusion(f, o); break;
-        case 8: test_DirectIllumination(f, o); break;
+        case 8: test_Illumination(f, o, 0); break;
+        case 9: test_Illumination(f, o, 16); break;
         default: break;
         }
         f.TearDown();

@@ -113,8 +113,12 @@ class DirectRenderer:
         self._set_camera(camera)
         self.frames_done = 0
 
-    def params(self, frames: int, frame_begin: int) -> shim.DirectParams:
-        p = shim.DirectParams()
+    # what a renderer with the same buffers and another entry point changes (indirect.IndirectRenderer)
+    _PARAMS = shim.DirectParams
+    _ENTRY = "pt_render_direct"
+
+    def params(self, frames: int, frame_begin: int):
+        p = self._PARAMS()
         p.width, p.height = self.width, self.height
         p.frame_begin, p.frame_count = frame_begin, frames
         p.num_triangles, p.num_materials, p.num_lights = self.num_triangles, self.num_materials, len(self.lights)
@@ -131,10 +135,10 @@ class DirectRenderer:
         if frames < 0 or frame_begin < 0 or frame_begin + frames > 0x7fffffff:
             raise ValueError("invalid frame range [%d, %d)" % (frame_begin, frame_begin + frames))
         p = self.params(frames, frame_begin)
-        shim.check(self._lib.pt_render_direct(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
-                                              self.samples._h, self.fb._h, ctypes.byref(p),
-                                              ctypes.byref(self._cam) if self._cam is not None else None,
-                                              sync._h if sync is not None else None))
+        shim.check(getattr(self._lib, self._ENTRY)(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
+                                                   self.samples._h, self.fb._h, ctypes.byref(p),
+                                                   ctypes.byref(self._cam) if self._cam is not None else None,
+                                                   sync._h if sync is not None else None))
         self.frames_done = frame_begin + frames
 
     def read(self) -> np.ndarray:

@@ -180,6 +180,16 @@ class Renderer:
         the buffers (which waits for the device, once).  Release it before the renderer."""
         from .direct import DirectRenderer
 
+        return self._lit_renderer(DirectRenderer, kw)
+
+    def indirect_renderer(self, **kw):
+        """An :class:`indirect.IndirectRenderer` over this renderer's buffers, as :meth:`direct_renderer` gives a DirectRenderer
+        (keyword arguments: IndirectRenderer's, ``max_bounces`` among them)."""
+        from .indirect import IndirectRenderer
+
+        return self._lit_renderer(IndirectRenderer, kw)
+
+    def _lit_renderer(self, cls, kw):
         kw.setdefault("camera", self.camera)
         kw.setdefault("stripe_rows", self.stripe_rows)
         kw.setdefault("n_ranks", self.n_ranks)
@@ -193,8 +203,8 @@ class Renderer:
                 self.mbuf.read(mats, self.num_materials)
             self.dev.waitForCompletion()
             kw["lights"] = scene.emitters(tris, mats)
-        return DirectRenderer(self.dev, self.tbuf, self.mbuf, kw.pop("width", self.width), kw.pop("height", self.height),
-                              num_triangles=self.num_triangles, num_materials=self.num_materials, **kw)
+        return cls(self.dev, self.tbuf, self.mbuf, kw.pop("width", self.width), kw.pop("height", self.height),
+                   num_triangles=self.num_triangles, num_materials=self.num_materials, **kw)
 
     def global_rows(self) -> np.ndarray:
         """Global row index of every local row (ascending)."""

@@ -110,6 +110,21 @@ class DirectParams(_c.Structure):
     ]
 
 
+class IndirectParams(_c.Structure):
+    """pt_indirect_params (64 bytes): DirectParams' fields (K light samples per vertex) and the path's depth max_bounces; reserved
+    must be 0."""
+
+    _fields_ = [
+        ("width", _c.c_int32), ("height", _c.c_int32),
+        ("frame_begin", _c.c_int32), ("frame_count", _c.c_int32),
+        ("num_triangles", _c.c_int32), ("num_materials", _c.c_int32), ("num_lights", _c.c_int32),
+        ("light_samples", _c.c_int32),
+        ("stripe_rows", _c.c_int32), ("n_ranks", _c.c_int32), ("rank", _c.c_int32),
+        ("max_bounces", _c.c_int32),
+        ("reserved", _c.c_int32 * 4),
+    ]
+
+
 class BvhInfo(_c.Structure):
     """pt_bvh_info (64 bytes): what pt_bvh_snapshot says about the LBVH of the prepared scene."""
 
@@ -179,6 +194,7 @@ SIGNATURES = {
     "pt_occluded_rays": (_c.c_int, [_H, _H, _c.c_int, _H, _H, _c.c_size_t, _H]),
     "pt_render_ao": (_c.c_int, [_H, _H, _H, _H, _c.POINTER(AoParams), _c.POINTER(Camera), _H]),
     "pt_render_direct": (_c.c_int, [_H, _H, _H, _H, _H, _H, _c.POINTER(DirectParams), _c.POINTER(Camera), _H]),
+    "pt_render_indirect": (_c.c_int, [_H, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Camera), _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_bvh_snapshot": (_c.c_int, [_H, _c.POINTER(BvhInfo), _c.c_void_p, _c.c_size_t, _c.c_void_p]),

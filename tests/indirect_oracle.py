@@ -1,0 +1,101 @@
+"""Builds, loads and binds tests/libtest_indirect_oracle.so: the CPU oracle's path tracing with light sampling at every vertex
+(tests/indirect_oracle.c through the translation unit tests/indirect_oracles.c, which includes tests/direct_oracles.c whole) -- the
+framebuffer of pt_render_indirect, and per sample the radiance before the fold, the vertices the path reached and why it ended.
+TEST INFRASTRUCTURE.
+
+``__graft_entry__.build()`` builds it (``python -B tests/indirect_oracle.py build``); ``lib()`` builds it again when it is missing
+or older than one of its sources, as ``direct_oracle.lib()`` does.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+import direct_oracle
+import oracles
+from oracles import cam10, ptr
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libtest_indirect_oracle.so")
+_SRCS = [os.path.join(_HERE, f) for f in ("indirect_oracles.c", "indirect_oracle.c")] + list(direct_oracle._SRCS)
+
+END_MISS, END_PDF, END_DEPTH = 0, 1, 2   # why a path ended (indirect_oracle.c: OII_END_*)
+
+_V, _I, _I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+_SIGNATURES = {
+    "oii_render": (_I, [_V, _I, _V, _V, _I, _V] + [_I] * 9 + [_V]),
+    "oii_samples": (_I, [_V, _I, _V, _V, _I, _V, _I, _I, _V, _V, _I64, _I, _I, _V, _V, _V, _V]),
+}
+
+
+def build() -> str:
+    cc = os.environ.get("CC", "gcc")
+    subprocess.check_call([cc] + oracles.CFLAGS + ["-shared", "-o", LIB_PATH, _SRCS[0], "-lm", "-lpthread"])
+    return LIB_PATH
+
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in _SRCS):
+            build()
+        L = ctypes.CDLL(LIB_PATH)
+        for name, (res, args) in _SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        _lib = L
+    return _lib
+
+
+def render(tris, mats, W, H, frame_begin, frame_count, K, B, *, lights=None, cam=None, stripe_rows=1, n_ranks=1, rank=0, start=None):
+    """float32 [local pixels, 4]: frames [frame_begin, frame_begin + frame_count) at ``B`` bounces and ``K`` light samples per
+    vertex folded into ``start`` (or zeros); None when the camera is rejected.  lights: the light list (None = scene.emitters);
+    cam: a Camera (None = the reference's)."""
+    tris, mats = np.ascontiguousarray(tris), np.ascontiguousarray(mats)
+    li = direct_oracle._lights(tris, mats, lights)
+    rows = sum(1 for r in range(H) if (r // stripe_rows) % n_ranks == rank)
+    fb = np.zeros((rows * W, 4), np.float32) if start is None else np.array(start, np.float32).reshape(rows * W, 4).copy()
+    c = cam10(cam)
+    rc = lib().oii_render(ptr(tris) if len(tris) else None, len(tris), ptr(mats), ptr(li) if len(li) else None, len(li), ptr(c),
+                          W, H, stripe_rows, n_ranks, rank, frame_begin, frame_count, K, B, ptr(fb))
+    return None if rc != 0 else fb
+
+
+def samples(tris, mats, W, H, gid, frame, K, B, *, lights=None, cam=None):
+    """Per sample (gid[i], frame[i]): the radiance before the fold (float32 [n, 3]), the vertices the path reached (int32 [n]), why
+    it ended (uint8 [n]: END_MISS, END_PDF, END_DEPTH) and the light samples at vertices >= 2 whose shadow ray was open / occluded
+    (int32 [n, 2])."""
+    tris, mats = np.ascontiguousarray(tris), np.ascontiguousarray(mats)
+    li = direct_oracle._lights(tris, mats, lights)
+    gid = np.ascontiguousarray(gid, np.int32)
+    frame = np.ascontiguousarray(frame, np.int32)
+    n = len(gid)
+    rad = np.zeros((n, 3), np.float32)
+    vertices = np.zeros(n, np.int32)
+    end = np.zeros(n, np.uint8)
+    later = np.zeros((n, 2), np.int32)
+    c = cam10(cam)
+    rc = lib().oii_samples(ptr(tris) if len(tris) else None, len(tris), ptr(mats), ptr(li) if len(li) else None, len(li), ptr(c),
+                           W, H, ptr(gid), ptr(frame), n, K, B, ptr(rad), ptr(vertices), ptr(end), ptr(later))
+    if rc != 0:
+        raise ValueError("oii_samples rejected the camera")
+    return rad, vertices, end, later
+
+
+def all_samples(W, H, frames, frame_begin=0):
+    """(gid, frame) of every sample of ``frames`` frames, frame-major -- the order of the device's sample workspace"""
+    gid = np.tile(np.arange(W * H, dtype=np.int32), frames)
+    frame = np.repeat(np.arange(frame_begin, frame_begin + frames, dtype=np.int32), W * H)
+    return gid, frame
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "build":
+        build()

@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""Informational: samples/s of indirect illumination on the device (pt_render_indirect) on the Cornell box, 1024^2, 16 frames,
+B = 16 bounces -- K = 0 (no light list: the renderer's estimator through the lock-step brute-force kernel) and K = 1 (one light
+sample per vertex) -- beside pt_render_frames at the same size and depth in the same process.  Each leg is warmed up once at its
+own shape (scene preparation, code objects), then run ONCE: a host clock around the enqueue and the device synchronise that ends
+it.  The sample workspace holds all 16 frames, so an indirect render is one launch and one fold.
+The K = 0 figure against the renderer's is what the brute-force kernel's missing lane regeneration costs.
+usage: python tools/indirect_rates.py [out.txt]"""
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+from oclpathtracer_amd import adl, scene  # noqa: E402
+from oclpathtracer_amd.indirect import IndirectRenderer  # noqa: E402
+from oclpathtracer_amd.render import Renderer  # noqa: E402
+
+out_path = sys.argv[1] if len(sys.argv) > 1 else None
+W = H = 1024
+FRAMES, B = 16, 16
+
+
+def emit(line):
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "a") as f:
+            f.write(line + "\n")
+
+
+def once(dev, render):
+    render()                       # warm-up, same shape
+    dev.waitForCompletion()
+    t0 = time.perf_counter()
+    render()
+    dev.waitForCompletion()
+    return time.perf_counter() - t0
+
+
+def report(name, t):
+    n = W * H * FRAMES
+    emit("%-44s %9.3f ms  %9.1f Msamples/s" % (name, t * 1e3, n / t / 1e6))
+    return n / t
+
+
+assert adl.init()
+dev = adl.DeviceUtils.allocate()
+try:
+    tris, mats = scene.load_model()
+    emit("%s; Cornell box, %d x %d, %d frames, B = %d; one warm-up and one timed run per leg" % (dev.getDeviceName(), W, H, FRAMES, B))
+    r = Renderer(dev, tris, mats, W, H, stripe_rows=1)
+    try:
+        base = report("pt_render_frames", once(dev, lambda: r.render(FRAMES, frame_begin=0, max_bounces=B)))
+    finally:
+        r.release()
+    for name, K, lights in (("pt_render_indirect K = 0 (no lights)", 1, np.zeros(0, np.int32)), ("pt_render_indirect K = 1", 1, None)):
+        ir = IndirectRenderer(dev, tris, mats, W, H, light_samples=K, lights=lights, max_bounces=B, stripe_rows=1, chunk_frames=FRAMES)
+        try:
+            rate = report(name, once(dev, lambda: ir.render(FRAMES, 0)))
+            emit("%-44s %9.3f of pt_render_frames' rate" % ("", rate / base))
+        finally:
+            ir.release()
+finally:
+    adl.DeviceUtils.deallocate(dev)
