@@ -118,6 +118,12 @@ def details(tris, mats, W, H, gid, frame, K, *, lights=None, cam=None):
     return hit, flipped, reason, d2, rad
 
 
+def local_gids(W, H, stripe_rows=1, n_ranks=1, rank=0):
+    """the global pixel index of every local pixel of ``rank`` in the stripe layout, in the framebuffer's order"""
+    rows = [r for r in range(H) if (r // stripe_rows) % n_ranks == rank]
+    return (np.asarray(rows, np.int64)[:, None] * W + np.arange(W)[None, :]).reshape(-1)
+
+
 def count_reasons(reason):
     """{name: how many light samples ended for that reason}"""
     return {name: int((reason == k).sum()) for k, name in enumerate(REASONS)}

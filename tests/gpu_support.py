@@ -1,5 +1,5 @@
-"""What the GPU test modules share: device options for a block, one render through the fused entry point, the comparison of hit
-records and the ray generators of the query tests.  TEST INFRASTRUCTURE (an ordinary module: every assert carries its message)."""
+"""What the GPU test modules share: device options for a block, one render through the fused entry point, one direct or indirect
+render with its sample workspace, the comparison of hit records and the ray generators of the query tests.  TEST INFRASTRUCTURE (an ordinary module: every assert carries its message)."""
 from contextlib import contextmanager
 
 import numpy as np
@@ -36,6 +36,29 @@ def render(device, tris, mats, W, H, frames, *, depth=16, frame_begin=0, fb_init
         r.render(frames, frame_begin=frame_begin, max_bounces=depth)
         got = r.read()
         return (got, r.read_stats_raw()) if want_stats else got
+    finally:
+        r.release()
+
+
+def lit_with_samples(device, scene4, W, H, frames, K, chunk_frames=None, max_bounces=None, **kw):
+    """One DirectRenderer -- with max_bounces an IndirectRenderer -- on (tris, mats, lights, camera), whose workspace holds every
+    frame of the call (chunk_frames >= frames unless given), one render from frame 0: the framebuffer [local pixels, 4] and the
+    whole sample workspace [chunk_frames, local pixels, 3]."""
+    from oclpathtracer_amd.direct import DirectRenderer
+    from oclpathtracer_amd.indirect import IndirectRenderer
+
+    tris, mats, lights, cam = scene4
+    kw.setdefault("stripe_rows", 1)
+    kw.update(light_samples=K, lights=lights, camera=cam, chunk_frames=max(frames, 1) if chunk_frames is None else chunk_frames)
+    r = DirectRenderer(device, tris, mats, W, H, **kw) if max_bounces is None else \
+        IndirectRenderer(device, tris, mats, W, H, max_bounces=max_bounces, **kw)
+    try:
+        r.render(frames, 0)
+        fb = r.read()
+        ws = np.zeros((r.chunk_frames, r.local_pixels, 3), np.float32)
+        r.samples.read(ws, ws.size)
+        device.waitForCompletion()
+        return fb, ws
     finally:
         r.release()
 

@@ -16,6 +16,8 @@
  *   - L = max(L, 0) (:260), folded by odi_fold.
  * Two identities pin this to the statements it repeats (tests/test_indirect_cpu.py): with no lights the image is ptor_render's at
  * the same depth, and at B = 1 it is odi_render's, both bit for bit.
+ * oii_details reports, from that same walk, what happened at each of a path's first vertices (tests/test_indirect_cpu.py proves with
+ * it that each input of tests/test_gpu_indirect_edges.py reaches the edge it is rendered for).
  * Compiled with oracle/Makefile's flags (tests/indirect_oracle.py).
  */
 enum { OII_END_MISS = 0, OII_END_PDF = 1, OII_END_DEPTH = 2 };
@@ -24,12 +26,26 @@ enum { OII_END_MISS = 0, OII_END_PDF = 1, OII_END_DEPTH = 2 };
 typedef struct oii_info {
     int vertices;         /* closest hits: the vertices the path reached, 0 .. B */
     int end;              /* OII_END_* */
+    int end_at;           /* the loop index i at which the path ended: the search that missed, the vertex whose pdf <= 0, or B - 1 */
     int later_open;       /* light samples at a vertex >= 2 (i >= 1) whose shadow ray was open ... */
     int later_occluded;   /* ... and occluded */
 } oii_info;
 
-/* light sample at the vertex (p, n, wo) of material m: odi_sample's loop body.  Returns ODI_NONE (no contribution; the three uniforms
- * are drawn all the same), ODI_OCCLUDED, or ODI_OPEN with *c the contribution */
+/* oii_sample's optional account of the first V vertices of a path (oii_details): per vertex the hit's material type (0 = the path
+ * has no such vertex) and index, whether the normal was negated at :243, whether the hit triangle's material is emissive, and the
+ * ODI_R_* reason code of each of its K light samples (ODI_R_NOT_DRAWN where none was drawn).  The caller clears the arrays. */
+typedef struct oii_why {
+    int V;
+    uint8_t* mtype;      /* [V] */
+    int32_t* material;   /* [V] */
+    uint8_t* flipped;    /* [V] */
+    uint8_t* emissive;   /* [V] */
+    uint8_t* reason;     /* [V * K] */
+} oii_why;
+
+/* light sample at the vertex (p, n, wo) of material m: odi_sample's loop body.  Returns its ODI_R_* reason code (direct_oracle.c):
+ * NOT_FACING, EDGE_ON, NAN and OTHER_TYPE contribute nothing (the three uniforms are drawn all the same), OCCLUDED neither;
+ * OPEN_UNSEARCHED (tl <= 0: nothing is searched) and OPEN contribute *c */
 PTOR_INLINE int oii_light(const ptor_triangle* tris, int ntri, const ptor_material* mats, const int32_t* lights, int nl,
                           const ptor_material* m, v3 p, v3 n, v3 wo, uint32_t* seed, v3* c_out, ptor_stats* st)
 {
@@ -52,7 +68,7 @@ PTOR_INLINE int oii_light(const ptor_triangle* tris, int ntri, const ptor_materi
     const float dist = sqrtf(d2);
     const v3 wi = v3_normalize(dv);
     const float cs = v3_dot(wi, n), cl = fabsf(v3_dot(wi, nj));
-    if (!(cs > 0.0f && cl > 0.0f)) return ODI_NONE;
+    if (!(cs > 0.0f && cl > 0.0f)) return (cs != cs || cl != cl) ? ODI_R_NAN : (cs <= 0.0f ? ODI_R_NOT_FACING : ODI_R_EDGE_ON);
     v3 f;
     if (m->type == PTOR_DIFFUSE) {
         f = v3_scale(albedo, PTOR_INV_PI);   /* :203 */
@@ -67,7 +83,7 @@ PTOR_INLINE int oii_light(const ptor_triangle* tris, int ntri, const ptor_materi
             f = v3_scale(v3_scale(albedo, g), 2.0f);   /* :217 */
         }
     } else {
-        return ODI_NONE;   /* :220 */
+        return ODI_R_OTHER_TYPE;   /* :220 */
     }
     const ptor_material* mj = &mats[tj->id];
     const float w = ((cs * cl) / d2) * (area * (float)nl);
@@ -80,12 +96,12 @@ PTOR_INLINE int oii_light(const ptor_triangle* tris, int ntri, const ptor_materi
         ptor_hit srec;
         for (int i = 0; i < ntri && !occluded; i++) occluded = ptor_intersect_triangle(&s, &tris[i], i, &srec, tl, st);
     }
-    return occluded ? ODI_OCCLUDED : ODI_OPEN;
+    return occluded ? ODI_R_OCCLUDED : (tl > 0.0f ? ODI_R_OPEN : ODI_R_OPEN_UNSEARCHED);
 }
 
-/* one sample: its radiance L before the fold; info (may be NULL) */
+/* one sample: its radiance L before the fold; info and why (each may be NULL) are accounts of the same walk */
 PTOR_INLINE v3 oii_sample(const ocam* cam, const ptor_triangle* tris, int ntri, const ptor_material* mats, const int32_t* lights,
-                          int nl, int x, int grow, int W, int H, int frame, int K, int B, oii_info* info)
+                          int nl, int x, int grow, int W, int H, int frame, int K, int B, oii_info* info, const oii_why* why)
 {
     ptor_stats st;
     memset(&st, 0, sizeof st);
@@ -96,13 +112,14 @@ PTOR_INLINE v3 oii_sample(const ocam* cam, const ptor_triangle* tris, int ntri, 
     v3 mask = v3_make(1.0f, 1.0f, 1.0f);
     const float bg = ptor_max(0.45f, 0.0f);   /* :235 */
     const float Kf = (float)K;
-    oii_info acc = { 0, OII_END_DEPTH, 0, 0 };
+    oii_info acc = { 0, OII_END_DEPTH, B - 1, 0, 0 };
     for (int i = 0; i < B; ++i) {
         ptor_hit rec;
         memset(&rec, 0, sizeof rec);
         if (!ptor_intersect_world(&r, tris, ntri, &rec, &st)) {
             L = v3_add(L, v3_scale(mask, bg));
             acc.end = OII_END_MISS;
+            acc.end_at = i;
             break;
         }
         acc.vertices++;
@@ -112,16 +129,26 @@ PTOR_INLINE v3 oii_sample(const ocam* cam, const ptor_triangle* tris, int ntri, 
             L.y = L.y + mask.y * m->emissive[1] * 3.0f;
             L.z = L.z + mask.z * m->emissive[2] * 3.0f;
         }
-        const v3 n = v3_dot(rec.n, r.dir) < 0.0f ? rec.n : v3_scale(rec.n, -1.0f);   /* :243 */
+        const int facing = v3_dot(rec.n, r.dir) < 0.0f;
+        const v3 n = facing ? rec.n : v3_scale(rec.n, -1.0f);   /* :243 */
         const v3 wo = v3_neg(r.dir);
+        const int told = why && i < why->V;
+        if (told) {
+            why->mtype[i] = (uint8_t)m->type;
+            why->material[i] = (int32_t)tris[rec.tri].id;
+            why->flipped[i] = (uint8_t)!facing;
+            why->emissive[i] = (uint8_t)(m->emissive[0] > 0.0f || m->emissive[1] > 0.0f || m->emissive[2] > 0.0f);
+        }
         if (nl > 0) {
             v3 S = v3_make(0.0f, 0.0f, 0.0f);
             for (int k = 0; k < K; ++k) {
                 v3 c = v3_make(0.0f, 0.0f, 0.0f);
-                const int dec = oii_light(tris, ntri, mats, lights, nl, m, rec.p, n, wo, &seed, &c, &st);
-                if (dec == ODI_OPEN) S = v3_add(S, c);
-                if (i >= 1 && dec == ODI_OPEN) acc.later_open++;
-                if (i >= 1 && dec == ODI_OCCLUDED) acc.later_occluded++;
+                const int why_k = oii_light(tris, ntri, mats, lights, nl, m, rec.p, n, wo, &seed, &c, &st);
+                const int open = why_k == ODI_R_OPEN || why_k == ODI_R_OPEN_UNSEARCHED;
+                if (open) S = v3_add(S, c);
+                if (i >= 1 && open) acc.later_open++;
+                if (i >= 1 && why_k == ODI_R_OCCLUDED) acc.later_occluded++;
+                if (told) why->reason[i * K + k] = (uint8_t)why_k;
             }
             L.x = L.x + mask.x * (S.x / Kf);
             L.y = L.y + mask.y * (S.y / Kf);
@@ -133,6 +160,7 @@ PTOR_INLINE v3 oii_sample(const ocam* cam, const ptor_triangle* tris, int ntri, 
         const v3 color = ptor_brdf(wo, &wi, &pdf, n, m, &seed, &st);
         if (pdf <= 0.0f) {   /* :251 */
             acc.end = OII_END_PDF;
+            acc.end_at = i;
             break;
         }
         const float d = v3_dot(wi, n);
@@ -159,7 +187,7 @@ int oii_render(const void* tris_, int ntri, const void* mats_, const int32_t* li
         for (int x = 0; x < W; ++x, ++lp)
             for (int f = 0; f < frame_count; ++f) {
                 const v3 L = oii_sample(&c, (const ptor_triangle*)tris_, ntri, (const ptor_material*)mats_, lights, nl, x, grow, W, H,
-                                        frame_begin + f, K, B, 0);
+                                        frame_begin + f, K, B, 0, 0);
                 odi_fold(fb + 4 * lp, L, frame_begin + f);
             }
     }
@@ -178,12 +206,41 @@ int oii_samples(const void* tris_, int ntri, const void* mats_, const int32_t* l
     for (int64_t i = 0; i < n; ++i) {
         oii_info info;
         const v3 L = oii_sample(&c, (const ptor_triangle*)tris_, ntri, (const ptor_material*)mats_, lights, nl, gid[i] % W, gid[i] / W,
-                                W, H, frame[i], K, B, &info);
+                                W, H, frame[i], K, B, &info, 0);
         radiance[3 * i] = L.x; radiance[3 * i + 1] = L.y; radiance[3 * i + 2] = L.z;
         vertices[i] = info.vertices;
         end[i] = (uint8_t)info.end;
         later[2 * i] = info.later_open;
         later[2 * i + 1] = info.later_occluded;
+    }
+    return 0;
+}
+
+/* n samples (gid[i], frame[i]), the first V = min(B, 8) vertices of each: mtype[i * V + v] (0 = no such vertex), material (the
+ * index, -1 = no such vertex), flipped and emissive likewise, reason[(i * V + v) * K + k] = ODI_R_* of light sample k at vertex v; end[i * 2 ..] = {OII_END_*, the loop
+ * index it happened at}, radiance[i * 3 ..] = L before the fold, nonfinite[i] = a component of L is NaN or infinite */
+PTOR_CLONES
+int oii_details(const void* tris_, int ntri, const void* mats_, const int32_t* lights, int nl, const float* cam10, int W, int H,
+                const int32_t* gid, const int32_t* frame, int64_t n, int K, int B, uint8_t* mtype, int32_t* material, uint8_t* flipped,
+                uint8_t* emissive, uint8_t* reason, int32_t* end, float* radiance, uint8_t* nonfinite)
+{
+    ocam c;
+    if (odi_camera(cam10, &c) != 0) return -1;
+    const int V = B < 8 ? B : 8;
+    memset(mtype, 0, (size_t)(n * V));
+    for (int64_t i = 0; i < n * V; ++i) material[i] = -1;
+    memset(flipped, 0, (size_t)(n * V));
+    memset(emissive, 0, (size_t)(n * V));
+    memset(reason, ODI_R_NOT_DRAWN, (size_t)(n * V * K));
+    for (int64_t i = 0; i < n; ++i) {
+        oii_info info;
+        const oii_why why = { V, mtype + i * V, material + i * V, flipped + i * V, emissive + i * V, reason + i * V * K };
+        const v3 L = oii_sample(&c, (const ptor_triangle*)tris_, ntri, (const ptor_material*)mats_, lights, nl, gid[i] % W, gid[i] / W,
+                                W, H, frame[i], K, B, &info, &why);
+        radiance[3 * i] = L.x; radiance[3 * i + 1] = L.y; radiance[3 * i + 2] = L.z;
+        end[2 * i] = info.end;
+        end[2 * i + 1] = info.end_at;
+        nonfinite[i] = (uint8_t)!(isfinite(L.x) && isfinite(L.y) && isfinite(L.z));
     }
     return 0;
 }

@@ -1,7 +1,7 @@
 """Builds, loads and binds tests/libtest_indirect_oracle.so: the CPU oracle's path tracing with light sampling at every vertex
 (tests/indirect_oracle.c through the translation unit tests/indirect_oracles.c, which includes tests/direct_oracles.c whole) -- the
-framebuffer of pt_render_indirect, and per sample the radiance before the fold, the vertices the path reached and why it ended.
-TEST INFRASTRUCTURE.
+framebuffer of pt_render_indirect, and per sample the radiance before the fold, the vertices the path reached and why it ended
+(``samples``), or what happened at each of its first vertices (``details``).  TEST INFRASTRUCTURE.
 
 ``__graft_entry__.build()`` builds it (``python -B tests/indirect_oracle.py build``); ``lib()`` builds it again when it is missing
 or older than one of its sources, as ``direct_oracle.lib()`` does.
@@ -29,6 +29,7 @@ _V, _I, _I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
 _SIGNATURES = {
     "oii_render": (_I, [_V, _I, _V, _V, _I, _V] + [_I] * 9 + [_V]),
     "oii_samples": (_I, [_V, _I, _V, _V, _I, _V, _I, _I, _V, _V, _I64, _I, _I, _V, _V, _V, _V]),
+    "oii_details": (_I, [_V, _I, _V, _V, _I, _V, _I, _I, _V, _V, _I64, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V]),
 }
 
 
@@ -87,6 +88,36 @@ def samples(tris, mats, W, H, gid, frame, K, B, *, lights=None, cam=None):
     if rc != 0:
         raise ValueError("oii_samples rejected the camera")
     return rad, vertices, end, later
+
+
+DETAIL_VERTICES = 8   # details() reports the first min(B, 8) vertices of a path
+
+
+def details(tris, mats, W, H, gid, frame, K, B, *, lights=None, cam=None):
+    """Per sample (gid[i], frame[i]), for the first V = min(B, 8) vertices of its path: the hit's material type (uint8 [n, V], 0 =
+    the path has no such vertex), whether the normal was negated at :243 and whether the hit triangle's material is emissive (uint8
+    [n, V] each), and the reason code of each light sample (uint8 [n, V, K]: direct_oracle's NOT_DRAWN .. R_OCCLUDED); then why the
+    path ended and the loop index it happened at (int32 [n, 2]: END_*, i -- the search that missed, the vertex whose pdf <= 0, or
+    B - 1), the radiance before the fold (float32 [n, 3]), whether a component of it is NaN or infinite (uint8 [n]), and last the
+    hit's material index per vertex (int32 [n, V], -1 = no such vertex)."""
+    tris, mats = np.ascontiguousarray(tris), np.ascontiguousarray(mats)
+    li = direct_oracle._lights(tris, mats, lights)
+    gid = np.ascontiguousarray(gid, np.int32)
+    frame = np.ascontiguousarray(frame, np.int32)
+    n, V = len(gid), min(B, DETAIL_VERTICES)
+    mtype, flipped, emissive = (np.zeros((n, V), np.uint8) for _ in range(3))
+    material = np.zeros((n, V), np.int32)
+    reason = np.zeros((n, V, K), np.uint8)
+    end = np.zeros((n, 2), np.int32)
+    rad = np.zeros((n, 3), np.float32)
+    nonfinite = np.zeros(n, np.uint8)
+    c = cam10(cam)
+    rc = lib().oii_details(ptr(tris) if len(tris) else None, len(tris), ptr(mats), ptr(li) if len(li) else None, len(li), ptr(c),
+                           W, H, ptr(gid), ptr(frame), n, K, B, ptr(mtype), ptr(material), ptr(flipped), ptr(emissive), ptr(reason), ptr(end),
+                           ptr(rad), ptr(nonfinite))
+    if rc != 0:
+        raise ValueError("oii_details rejected the camera")
+    return mtype, flipped, emissive, reason, end, rad, nonfinite, material
 
 
 def all_samples(W, H, frames, frame_begin=0):

@@ -8,7 +8,9 @@ generated from fixed seeds, and the order of the draws from a generator is part 
     scene(name) for name in NAMES (tests/test_lbvh_scale_cpu.py: the oracle's scale identities; tests/test_gpu_lbvh_scenes.py);
   * scenes at the edges of direct illumination's light sample, each (tris, mats, lights, camera or None): direct_scaled,
     direct_light_list, direct_other_type, direct_from_behind (tests/test_direct_cpu.py proves that each reaches its edge,
-    tests/test_gpu_direct_edges.py renders them); glossy_room, the GGX branch at every roughness a guard can meet."""
+    tests/test_gpu_direct_edges.py renders them); glossy_room, the GGX branch at every roughness a guard can meet (and, with
+    FINITE_ROUGHNESS, at every one that keeps a multi-bounce path finite); edge_scene(name) names them all for the edge tests of
+    direct and indirect illumination."""
 from __future__ import annotations
 
 import numpy as np
@@ -406,11 +408,17 @@ ROUGHNESS = [1.0, 0.008, float(np.nextafter(np.float32(2.0 ** -31.5), np.float32
 
 GLOSSY_SHIFTS = (0, 1, 4, 13)
 
+# The roughnesses that keep a multi-bounce path finite.  The six others (indices 2, 3, 6, 7, 14, 15, all below 2e-9) turn every
+# sample whose path bounces on them into NaN -- the BRDF sample's D is 0 / 0 or inf / inf there -- and a bit-exact comparison of a
+# NaN sees nothing of the path after it (tests/test_indirect_cpu.py has the counts).
+FINITE_ROUGHNESS = [ROUGHNESS[k] for k in (0, 1, 4, 5, 8, 9, 10, 11, 12, 13, 16)]
 
-def glossy_room(shift=0):
-    """The Cornell box with every surface but the light a GGX one, a roughness of ROUGHNESS each: the k-th such material takes
-    ROUGHNESS[(k + shift) % 17].  The reference camera sees seven of them lit by the light; GLOSSY_SHIFTS brings every roughness
-    onto one of those seven (direct illumination's GGX branch, tests/test_direct_cpu.py)."""
+
+def glossy_room(shift=0, roughness=ROUGHNESS):
+    """The Cornell box with every surface but the light a GGX one, a roughness of ``roughness`` each: the k-th such material takes
+    roughness[(k + shift) % len(roughness)].  The reference camera sees seven of them lit by the light; GLOSSY_SHIFTS brings every
+    one of ROUGHNESS onto one of those seven (direct illumination's GGX branch, tests/test_direct_cpu.py), FINITE_SHIFTS every one
+    of FINITE_ROUGHNESS onto a surface that a path's later vertices meet lit (indirect illumination, tests/test_indirect_cpu.py)."""
     tris, mats = _scene.load_model()
     mats = mats.copy()
     k = 0
@@ -418,9 +426,41 @@ def glossy_room(shift=0):
         if m["emissive"][0] != 0.0:
             continue
         m["type"] = _scene.SPECULAR
-        m["roughness"] = np.float32(ROUGHNESS[(k + shift) % len(ROUGHNESS)])
+        m["roughness"] = np.float32(roughness[(k + shift) % len(roughness)])
         if m["albedo"][0] > 0.6:
             m["albedo"] = (0.5, 0.35, 0.05, 0.0)   # (a GGX weight is 2 albedo g dwin / pdf: keep long paths finite)
         k += 1
-    assert k >= len(ROUGHNESS)
+    assert k >= len(roughness)
     return tris, mats
+
+
+# The smallest set of shifts that brings every FINITE_ROUGHNESS onto a surface where a path takes an OPEN light sample at a vertex
+# i >= 1 (40 x 24, 3 frames, at K 1 / B 4 and at K 2 / B 6): no single shift of 0 .. 10 does, fifteen pairs do, and of those (5, 8)
+# leaves its rarest roughness the most such samples (15; tests/test_indirect_cpu.py counts them again).
+FINITE_SHIFTS = (5, 8)
+
+_EDGE_SCENES = {}
+
+
+def edge_scene(name):
+    """(name, (tris, mats, lights or None, camera or None)) of a named input of the illumination edge tests, each built once:
+    cornell, nested:COPIES, scaled:COPIES,K, lights:list|36|10|all, glossy:SHIFT, finite:SHIFT, other_type, from_behind"""
+    if name not in _EDGE_SCENES:
+        kind, _, arg = name.partition(":")
+        if kind == "cornell":
+            sc = _scene.load_model() + (None, None)
+        elif kind == "nested":
+            sc = nested_boxes(int(arg)) + (None, None)
+        elif kind == "scaled":
+            copies, k = arg.split(",")
+            sc = direct_scaled(int(copies), int(k))
+        elif kind == "lights":
+            sc = direct_light_list(*{"list": (), "36": ([36],), "10": ([10],), "all": (np.arange(37),)}[arg])
+        elif kind == "glossy":
+            sc = glossy_room(int(arg)) + (None, None)
+        elif kind == "finite":
+            sc = glossy_room(int(arg), FINITE_ROUGHNESS) + (None, None)
+        else:
+            sc = {"other_type": direct_other_type, "from_behind": direct_from_behind}[kind]()
+        _EDGE_SCENES[name] = sc
+    return name, _EDGE_SCENES[name]

@@ -14,36 +14,10 @@ import pytest
 
 import direct_oracle as do
 from conftest import assert_fb_equal
-from gpu_support import SEARCHES, options
-from scenes import (GLOSSY_SHIFTS, MIXED_SCALE, direct_from_behind, direct_light_list, direct_other_type, direct_scaled, glossy_room,
-                    nested_boxes)
+from gpu_support import SEARCHES, lit_with_samples, options
+from scenes import GLOSSY_SHIFTS, MIXED_SCALE, edge_scene
 
 pytestmark = pytest.mark.gpu
-
-
-def _local_gids(W, H, stripe_rows=1, n_ranks=1, rank=0):
-    rows = [r for r in range(H) if (r // stripe_rows) % n_ranks == rank]
-    return (np.asarray(rows, np.int64)[:, None] * W + np.arange(W)[None, :]).reshape(-1)
-
-
-def direct_with_samples(device, scene4, W, H, frames, K, chunk_frames=None, **kw):
-    """One DirectRenderer whose workspace holds every frame of the call (chunk_frames >= frames unless given), one render from
-    frame 0: the framebuffer [local pixels, 4] and the whole sample workspace [chunk_frames, local pixels, 3]."""
-    from oclpathtracer_amd.direct import DirectRenderer
-
-    tris, mats, lights, cam = scene4
-    kw.setdefault("stripe_rows", 1)
-    r = DirectRenderer(device, tris, mats, W, H, light_samples=K, lights=lights, camera=cam,
-                       chunk_frames=max(frames, 1) if chunk_frames is None else chunk_frames, **kw)
-    try:
-        r.render(frames, 0)
-        fb = r.read()
-        ws = np.zeros((r.chunk_frames, r.local_pixels, 3), np.float32)
-        r.samples.read(ws, ws.size)
-        device.waitForCompletion()
-        return fb, ws
-    finally:
-        r.release()
 
 
 _WANT = {}
@@ -54,7 +28,7 @@ def wanted(key, scene4, W, H, frames, K, **stripes):
     k = (key, W, H, frames, K, tuple(sorted(stripes.items())))
     if k not in _WANT:
         tris, mats, lights, cam = scene4
-        gid = _local_gids(W, H, **stripes)
+        gid = do.local_gids(W, H, **stripes)
         fb = do.render(tris, mats, W, H, 0, frames, K, lights=lights, cam=cam, **stripes)
         L = do.details(tris, mats, W, H, np.tile(gid, frames), np.repeat(np.arange(frames), len(gid)), K, lights=lights, cam=cam)[4]
         L = L.reshape(frames, len(gid), 3)
@@ -67,41 +41,16 @@ def wanted(key, scene4, W, H, frames, K, **stripes):
 def check(device, key, scene4, W, H, frames, K, what, **stripes):
     """render; the workspace against the restatement's radiance, the framebuffer against its image"""
     want_fb, want_L = wanted(key, scene4, W, H, frames, K, **stripes)
-    fb, ws = direct_with_samples(device, scene4, W, H, frames, K, **stripes)
+    fb, ws = lit_with_samples(device, scene4, W, H, frames, K, **stripes)
     assert ws.shape == want_L.shape, what
     assert_fb_equal(ws, want_L, what + ": radiance before the fold")
     assert_fb_equal(fb, want_fb, what + ": framebuffer")
 
 
-_SCENES = {}
-
-
-def _scene(name):
-    """(key, scene) of a named input, the scene built once"""
-    if name not in _SCENES:
-        kind, _, arg = name.partition(":")
-        if kind == "cornell":
-            from oclpathtracer_amd import scene
-
-            _SCENES[name] = scene.load_model() + (None, None)
-        elif kind == "nested":
-            _SCENES[name] = nested_boxes(int(arg)) + (None, None)
-        elif kind == "scaled":
-            copies, k = arg.split(",")
-            _SCENES[name] = direct_scaled(int(copies), int(k))
-        elif kind == "lights":
-            _SCENES[name] = direct_light_list(*{"list": (), "36": ([36],), "10": ([10],), "all": (np.arange(37),)}[arg])
-        elif kind == "glossy":
-            _SCENES[name] = glossy_room(int(arg)) + (None, None)
-        else:
-            _SCENES[name] = {"other_type": direct_other_type, "from_behind": direct_from_behind}[kind]()
-    return name, _SCENES[name]
-
-
 # ---- a. the radiance before the fold, on the inputs of tests/test_gpu_direct.py ---------------------------------------------------
 @pytest.mark.parametrize("quad,accel", SEARCHES)
 def test_cornell_radiance_before_the_fold(device, quad, accel):
-    key, sc = _scene("cornell")
+    key, sc = edge_scene("cornell")
     for W, H in ((64, 64), (40, 24)):
         for K in (1, 4):
             with options(device, QUAD_FILTER=quad, ACCEL=accel):
@@ -111,7 +60,7 @@ def test_cornell_radiance_before_the_fold(device, quad, accel):
 @pytest.mark.parametrize("copies,accel", [(10, 1), (15, 0), (15, 2), (15, 1)])
 def test_nested_boxes_radiance_before_the_fold(device, copies, accel):
     """10 copies: the tiled brute-force table; 15: the LBVH (automatic and forced) and brute force over 540 triangles"""
-    key, sc = _scene("nested:%d" % copies)
+    key, sc = edge_scene("nested:%d" % copies)
     with options(device, ACCEL=accel):
         check(device, key, sc, 32, 32, 2, 3, "nested_boxes(%d) accel %d" % (copies, accel))
 
@@ -120,8 +69,8 @@ def test_nested_boxes_radiance_before_the_fold(device, copies, accel):
 @pytest.mark.parametrize("accel", [1, 2])
 def test_stripes_hold_the_ranks_local_pixels(device, accel):
     """40 x 31 = 1 240 pixels: a partial last wave, checked against the restatement as a whole and rank by rank (rows of 5 over
-    3 ranks: 15, 10 and 6 local rows -- 600, 400 and 240 local pixels, the last two with partial waves of their own)"""
-    key, sc = _scene("cornell")
+    3 ranks: 11, 10 and 10 local rows -- 440, 400 and 400 local pixels, each with a partial wave of its own)"""
+    key, sc = edge_scene("cornell")
     with options(device, ACCEL=accel):
         check(device, key, sc, 40, 31, 2, 2, "one rank, accel %d" % accel, stripe_rows=5)
         for rank in range(3):
@@ -131,10 +80,10 @@ def test_stripes_hold_the_ranks_local_pixels(device, accel):
 def test_a_later_chunk_overwrites_slot_zero(device):
     """5 frames through a workspace of 2: launches of frames (0, 1), (2, 3), (4); slot 0 then holds frame 4 (slot 1 is not
     promised), and the framebuffer all five"""
-    key, sc = _scene("cornell")
+    key, sc = edge_scene("cornell")
     W, H, K = 40, 31, 2
     want_fb, want_L = wanted(key, sc, W, H, 5, K)
-    fb, ws = direct_with_samples(device, sc, W, H, 5, K, chunk_frames=2)
+    fb, ws = lit_with_samples(device, sc, W, H, 5, K, chunk_frames=2)
     assert ws.shape == (2, W * H, 3)
     assert_fb_equal(ws[0], want_L[4], "slot 0 holds the last chunk's frame")
     assert_fb_equal(fb, want_fb, "five frames in chunks of two")
@@ -143,7 +92,7 @@ def test_a_later_chunk_overwrites_slot_zero(device):
 # ---- c. every scene of tests/scenes.py's direct_* family ------------------------------------------------------------------------------
 @pytest.mark.parametrize("k", [MIXED_SCALE, -9])
 def test_scaled_tiled_table(device, k):
-    key, sc = _scene("scaled:10,%d" % k)
+    key, sc = edge_scene("scaled:10,%d" % k)
     with options(device, ACCEL=1):
         check(device, key, sc, 32, 32, 2, 3, "direct_scaled(10, %d), tiled brute force" % k)
 
@@ -154,7 +103,7 @@ def test_scaled_lbvh_and_brute_force(device, k, accel):
     """At the mixed scale a lane's shadow rays are searched, then not, then searched again: a fresh ray that searches nothing must
     end as a miss at the next refill -- were it to keep the hit of the ray before it (the primary hit, or an occluded shadow
     ray's), it would read as occluded and its light would be missing from the radiance.  At 2^-9 nothing is searched at all."""
-    key, sc = _scene("scaled:15,%d" % k)
+    key, sc = edge_scene("scaled:15,%d" % k)
     with options(device, ACCEL=accel):
         check(device, key, sc, 32, 32, 2, 3, "direct_scaled(15, %d), accel %d" % (k, accel))
 
@@ -163,7 +112,7 @@ def test_scaled_lbvh_and_brute_force(device, k, accel):
 @pytest.mark.parametrize("name", ["lights:list", "lights:36", "lights:10", "lights:all", "other_type", "from_behind", "scaled:1,-9"])
 def test_edge_scenes(device, name, quad, accel):
     """the 36- and 37-triangle scenes, 64 x 64, K = 4, two frames, over every search"""
-    key, sc = _scene(name)
+    key, sc = edge_scene(name)
     with options(device, QUAD_FILTER=quad, ACCEL=accel):
         check(device, key, sc, 64, 64, 2, 4, "%s q%d a%d" % (name, quad, accel))
 
@@ -172,7 +121,7 @@ def test_edge_scenes(device, name, quad, accel):
 @pytest.mark.parametrize("accel", [1, 2])
 @pytest.mark.parametrize("K", [1, 256])
 def test_light_samples_at_their_limits(device, K, accel):
-    key, sc = _scene("cornell")
+    key, sc = edge_scene("cornell")
     with options(device, ACCEL=accel):
         check(device, key, sc, 16, 16, 1, K, "K %d accel %d" % (K, accel))
 
@@ -183,14 +132,14 @@ SMALL = [(5, 3), (1, 1), (13, 5)]   # 15 samples: one partial wave; one sample; 
 
 @pytest.mark.parametrize("quad,accel", SEARCHES)
 def test_small_images_of_the_cornell_box(device, quad, accel):
-    key, sc = _scene("cornell")
+    key, sc = edge_scene("cornell")
     for W, H in SMALL:
         with options(device, QUAD_FILTER=quad, ACCEL=accel):
             check(device, key, sc, W, H, 2, 4, "%dx%d q%d a%d" % (W, H, quad, accel))
 
 
 def test_small_images_through_the_lbvh(device):
-    key, sc = _scene("nested:15")
+    key, sc = edge_scene("nested:15")
     for W, H in SMALL:
         with options(device, ACCEL=2):
             check(device, key, sc, W, H, 2, 4, "nested_boxes(15) %dx%d" % (W, H))
@@ -201,7 +150,7 @@ def test_small_images_through_the_lbvh(device):
 @pytest.mark.parametrize("shift", GLOSSY_SHIFTS)
 def test_glossy_rooms(device, shift, accel):
     """pt_direct_light's three quotients and max(E + S / K, 0) with the roughnesses on both sides of every guard, r = 0 included"""
-    key, sc = _scene("glossy:%d" % shift)
+    key, sc = edge_scene("glossy:%d" % shift)
     with np.errstate(all="ignore"):
         with options(device, ACCEL=accel):
             check(device, key, sc, 64, 48, 2, 4, "glossy_room(%d) accel %d" % (shift, accel))

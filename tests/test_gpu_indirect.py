@@ -130,17 +130,26 @@ def test_lbvh_against_the_restatement_and_brute_force(device, lbvh_scene):
 
 def test_lbvh_refill_over_more_samples_than_the_grid(device, lbvh_scene):
     """More samples than the persistent grid holds lanes (at most five workgroups of 256 per CU, the driver's other kernels' figure;
-    this kernel runs fewer), so lanes whose path has ended take further samples while their neighbours are in mid-path."""
+    this kernel runs fewer), so lanes whose path has ended take further samples while their neighbours are in mid-path.  An error
+    common to the LBVH and brute force passes their comparison, so every 7th sample and every sample past the grid's lanes is also
+    compared with the restatement, before the fold; at K = 2 a refilled lane's path has light samples that cast no ray between
+    those that do."""
     tris, mats = lbvh_scene
     lanes = shim.load().pt_device_num_cus(device._h) * 5 * 256
     Wb = 768
     Hb = lanes // Wb + 64
     assert Wb * Hb > lanes
-    res = {}
-    for accel in (2, 1):
-        with options(device, ACCEL=accel):
-            res[accel] = _indirect(device, tris, mats, Wb, Hb, 1, 1, 3, chunk_frames=1)
-    assert_fb_equal(res[2], res[1], "refill: LBVH against brute force")
+    gid = np.arange(Wb * Hb)
+    gid = gid[(gid % 7 == 0) | (gid >= lanes)]
+    for K in (1, 2):
+        res = {}
+        for accel in (2, 1):
+            with options(device, ACCEL=accel):
+                res[accel] = _indirect(device, tris, mats, Wb, Hb, 1, K, 3, chunk_frames=1, want_samples=True)
+        assert_fb_equal(res[2][0], res[1][0], "refill, K %d: LBVH against brute force" % K)
+        want = io.samples(tris, mats, Wb, Hb, gid, np.zeros(len(gid), np.int32), K, 3)[0]
+        for accel in (2, 1):
+            assert_fb_equal(res[accel][1][gid], want, "refill, K %d, accel %d: radiance before the fold" % (K, accel))
 
 
 @pytest.mark.parametrize("shift", GLOSSY_SHIFTS)
