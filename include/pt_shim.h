@@ -553,6 +553,16 @@ typedef struct pt_bvh_info {
 } pt_bvh_info;                   /* 64 bytes */
 int pt_bvh_snapshot(pt_device_t dev, pt_bvh_info* info, void* records, size_t record_capacity, int32_t* big_indices);
 
+/* Test hook: a read-only copy of the primary-ray candidate masks this device made last (PT_OPT_PRIMARY_MASKS: quad scenes of up
+ * to 64 triangles on the brute-force path; one pair of 32-bit words per LOCAL pixel, in the framebuffer's order -- word c holds
+ * triangles [32 c, 32 c + n), n = min(32, num_triangles - 32 c), triangle 32 c + j at bit n - 1 - j; a set bit = pass 2 tests the
+ * triangle for that pixel's primary rays).  Frames deferred by PT_OPT_BATCH_FRAMES are submitted first; then the call waits for
+ * the renders in flight and copies.  It changes nothing: no masks are made, no scene is prepared.  `num_pixels` receives the number
+ * of local pixels the table stands for; `masks` (may be NULL) receives 8 bytes per pixel -- `capacity` pixels must fit.
+ * PT_ERR_INVALID when no table stands (no render has used masks yet, or its scene has been replaced), PT_ERR_RANGE when
+ * capacity is too small (num_pixels is still filled). */
+int pt_primary_mask_snapshot(pt_device_t dev, uint32_t* num_pixels, void* masks, size_t capacity);
+
 /* Scatter the gathered per-rank local framebuffers (n_ranks slabs of slab_rows x width
  * float4 each, slab k = rank k) into the full image (height x width float4). */
 int pt_assemble_stripes(pt_device_t dev, pt_buffer_t gathered, pt_buffer_t image, int width,

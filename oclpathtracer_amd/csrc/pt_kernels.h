@@ -196,7 +196,8 @@ hipError_t ptk_prep_triangles(const PtRawTriangle* raw, PtPrepTriangle* out, int
 hipError_t ptk_prep_quad_margins(PtPrepTriangle* out, int ntri, float diameter, float delta1, float* p1tab, const float anchor[3], hipStream_t s);
 #define PT_P1_STRIDE 24  // floats per quad pair: nx ny nz e2x e2y e2z Kx Ky Kz dhi, each {quad 2p, quad 2p+1}, 4 pad
 static inline size_t ptk_p1tab_floats(int ntri) { return (size_t)((ntri / 2 + 1) / 2) * PT_P1_STRIDE; }
-// fills p.pmask (when not null) for the image geometry and the camera of p; needs p.p1tab (quad mode 3) made about p.cam.eye
+// fills p.pmask (when not null) for the image geometry and the camera of p from the prepared records p.tris: per pixel the triangles
+// whose whole exact test (:96-125) some primary ray of the pixel can pass
 hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s);
 // which search a launch runs (pt_shim.hip: prepare_search decides it, once, for renders, queries and ambient occlusion alike)
 struct PtSearchMode {

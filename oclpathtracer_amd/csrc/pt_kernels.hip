@@ -258,22 +258,46 @@ PTK_DEV void pt_generate_ray(int xc, int yc, float inv_w, float inv_h, float asp
 //     sphere from outside the ball of radius 1 - 1e-6 is (1 + 1e-6)-Lipschitz: together a factor below 1 + 4e-6;
 //     eps = 1.01 h + 4e-6 covers it with room to spare (the 1.01 alone is 2 500 times the 4e-6 needed), and its additive
 //     4e-6 covers the rounding of the reference's own ray set-up (three normalisations of a unit-length vector).
-// Hence |un(d) - un(d_c)| <= eps |K|_1 =: rho_u and |T(d) - T(d_c)| <= eps |n'|_1 =: rho_T for every ray of the
-// pixel, and a (ray, quad) pair pass 1 would keep -- |un| <= T, un >= lo (first triangle), un <= hi (second),
-// each evaluated in binary32 within deltaP of the real value -- has |un(d_c)| <= T(d_c) + rho_u + rho_T + 4 deltaP
-// and the matching one-sided bounds.  One thread per local pixel writes the two 32-bit chunk masks in pass 1's
-// own bit order; a FRESH wave of primary rays then loads its masks instead of running pass 1 (which is a third
-// of a bounce).  Everything downstream (the exact tests of pass 2) is unchanged, so the pixels are too;
-// tools/validate_filter.py counts violations of the cached masks like those of any other filter.
+// A primary ray's origin is the eye bit for bit, so for triangle {p1, e1, e2} the reference's tvec = fl(eye - p1), its
+// qvec = fl_cross(tvec, e1) and the numerator of t, tn = fl_dot(e2, qvec), are per-triangle CONSTANTS -- formed here by the
+// very operations of pt_tri_pass2, hence the same bits -- and the other three numerators are LINEAR in the direction:
+//     det(d) = d . Kd,  Kd = e2 x e1        un(d) = d . Ku,  Ku = e2 x tvec        vn(d) = d . qvec
+// The reference accepts a pair (:96-125) only if det >= 1e-8, u >= 0, v >= 0, u + v <= 1 and 0 < t < 1e20, with
+// u = fl(un inv), v = fl(vn inv), t = fl(tn inv), inv = RN(1 / det) > 0.  In terms of ITS floats un_ref, vn_ref, det_ref:
+//     u >= 0 (or -0)   =>  un_ref >= -1e-24        (pt_tri_pass1: below that the product is a negative non-zero float)
+//     v >= 0           =>  vn_ref >= -1e-24        (the same)
+//     fl(u + v) <= 1   =>  un_ref + vn_ref <= det_ref * 1.000001   (three roundings and RN(1 / det), each 1 - 2^-24; an
+//                          underflowing product loses at most 2^-150)
+//     t > 0            =>  tn > 0                  (inv > 0: the sign of t is the sign of the constant; no footprint term)
+// (u <= 1 follows from v >= 0 and u + v <= 1; t < 1e20 is left to pass 2.)
+// What this kernel evaluates is X_c = fl_dot(d_c, fl_cross(.,.)) at the centre direction.  With S = |a|_1 |b|_1 for the form
+// a . (d x b), u = 2^-24 and |d|_2^2 <= 1.001 (a thrice-normalised direction):
+//     the reference:  a cross product's component is one product and one fma, |error| <= u (|x y| + |component|) <= 2.1 u S';
+//                     a three-term fma dot errs by <= 3.01 u sum|x_i y_i|.  det_ref and un_ref (dot of a, the cross of d and
+//                     b: S' = |b|_1, |pvec_k| <= 1.001 |b|_1) are within (2.1 + 3.02) u S of the real form, vn_ref (dot of
+//                     d, |d|_1 <= 1.74, and a cross of constants) within (1.74 * 2.1 + 3.02) u S:           < 7 u S
+//     here:           dot of d_c and a cross of constants, as vn_ref:                                      < 7 u S
+//     the footprint:  |X(d) - X(d_c)| <= eps |K_real|_1 <= eps (|K_float|_1 + 6.3 u S)
+//     the comparisons below: a sum of two of these floats errs by <= u (|X_c| + rho) with |X_c| <= 1.001 S:  < 2 u S each
+// Together |X_ref(d) - X_c| <= eps |K|_1 + (32 + 8 eps) u S =: rho for every ray d of the pixel (32 against the 20 needed),
+// inflated by 0.1 % against the roundings of forming it, plus an absolute 2e-24 that covers the -1e-24 above and every
+// underflow.  The bit is cleared only when one of the five conditions then fails for ALL of the footprint; every comparison
+// is written so that a NaN keeps the bit.  One thread per local pixel writes the two 32-bit chunk masks in pass 1's own bit
+// order; a FRESH wave of primary rays then loads its masks instead of running pass 1 (which is a third of a bounce), and
+// its pass 2 meets about 1.2 candidates per ray instead of 3 (oracle, Cornell box: 17.0 of 36 pairs culled, 15.9 fail u,
+// 1.8 fail v, 1.2 accepted).  Everything downstream (the exact tests of pass 2) is unchanged, so the pixels are too;
+// tools/validate_filter.py counts violations of the cached masks -- pairs the reference ACCEPTS but a mask dropped --
+// like those of any other filter.
 struct PtMaskParams {
-    const float* p1tab;
+    const PtPrepTriangle* tris;   // the prepared records {p1, e1, e2}
     uint2* out;
     int32_t width, height, ntri;
     int32_t stripe_rows, n_ranks, rank;
     uint32_t npix_local;
-    float p1_lo, p1_hi;
-    PtCamera cam;   // the render's (and the anchor of p1tab)
+    PtCamera cam;   // the render's
 };
+
+PTK_DEV float pt_norm1(const f3& a) { return __builtin_fabsf(a.x) + __builtin_fabsf(a.y) + __builtin_fabsf(a.z); }
 
 __global__ void pt_primary_mask_kernel(const PtMaskParams P)
 {
@@ -292,27 +316,29 @@ __global__ void pt_primary_mask_kernel(const PtMaskParams P)
     const float hx = cam.angle * ((float)P.width / (float)P.height) / (float)P.width;
     const float hy = cam.angle / (float)P.height;
     const float eps = __builtin_sqrtf(hx * hx + hy * hy) * 1.01f + 4e-6f;
-    const float E = -4.0f * P.p1_lo;  // 4 deltaP
-    const int nquads = P.ntri / 2;
+    const float uS = (32.0f + 8.0f * eps) * 5.9604645e-8f;  // (32 + 8 eps) u
+    const float A = 2e-24f;
     unsigned m[2] = { 0u, 0u };
-    for (int q = 0; q < nquads; ++q) {
-        const float* tp = P.p1tab + (size_t)(q >> 1) * PT_P1_STRIDE;  // nx ny nz e2x e2y e2z Kx Ky Kz dhi, {quad 2p, quad 2p+1}
-        const int h = q & 1;
-        const float nx = tp[0 + h], ny = tp[2 + h], nz = tp[4 + h];
-        const float kx = tp[12 + h], ky = tp[14 + h], kz = tp[16 + h];
-        const float dhi = tp[18 + h];
-        const float Tc = pt_fma(dc.z, nz, pt_fma(dc.y, ny, dc.x * nx)) + dhi;
-        const float uc = -pt_fma(dc.z, kz, pt_fma(dc.y, ky, dc.x * kx));
-        const float rho_u = eps * (__builtin_fabsf(kx) + __builtin_fabsf(ky) + __builtin_fabsf(kz)) * 1.001f;
-        const float rho_T = eps * (__builtin_fabsf(nx) + __builtin_fabsf(ny) + __builtin_fabsf(nz)) * 1.001f;
+    for (int j = 0; j < P.ntri; ++j) {
+        const PtPrepTriangle* t = P.tris + j;
+        const f3 e1 = mk3(t->e1[0], t->e1[1], t->e1[2]), e2 = mk3(t->e2[0], t->e2[1], t->e2[2]);
+        const f3 tv = mk3(o.x - t->p1[0], o.y - t->p1[1], o.z - t->p1[2]);  // o is the eye, bit for bit
+        const f3 Kd = cross3(e2, e1), Ku = cross3(e2, tv), qv = cross3(tv, e1);
+        const float tn = dot3(e2, qv);  // :122's numerator, the bits of pt_tri_pass2
+        const float detc = dot3(dc, Kd), unc = dot3(dc, Ku), vnc = dot3(dc, qv);
+        const float a1 = pt_norm1(e1), a2 = pt_norm1(e2), at = pt_norm1(tv);
+        const float rho_d = (eps * pt_norm1(Kd) + uS * (a1 * a2)) * 1.001f + A;
+        const float rho_u = (eps * pt_norm1(Ku) + uS * (at * a2)) * 1.001f + A;
+        const float rho_v = (eps * pt_norm1(qv) + uS * (at * a1)) * 1.001f + A;
         // NaNs fail every comparison and are kept, as in pass 1
-        const bool in = !(__builtin_fabsf(uc) > (Tc + rho_u + rho_T + E) * 1.001f);
-        const bool fa = in & !(uc + (rho_u + E) * 1.001f < P.p1_lo);
-        const bool fb = in & !(uc - (rho_u + E) * 1.001f > P.p1_hi);
-        const int j = 2 * q, c = j >> 5;
+        const bool keep = !(detc + rho_d < 0.999e-8f)                                       // :100
+                        & !(unc + rho_u < 0.0f)                                             // :109, u >= 0
+                        & !(vnc + rho_v < 0.0f)                                             // :117, v >= 0
+                        & !((unc - rho_u) + (vnc - rho_v) > (detc + rho_d) * 1.000002f)     // :117, u + v <= 1
+                        & !(tn <= 0.0f);                                                    // :125, t > 0
+        const int c = j >> 5;
         const int nc = P.ntri - 32 * c < 32 ? P.ntri - 32 * c : 32;
-        m[c] |= (fa ? 1u : 0u) << (nc - 1 - (j & 31));
-        m[c] |= (fb ? 1u : 0u) << (nc - 2 - (j & 31));
+        m[c] |= (keep ? 1u : 0u) << (nc - 1 - (j & 31));
     }
     P.out[lp] = make_uint2(m[0], m[1]);
 }
@@ -880,7 +906,7 @@ PTK_DEV unsigned pt_intersect_primary(pt_const_f32p T, const PtPrepTriangle* tri
         const int n = ntri - base < 32 ? ntri - base : 32;
         unsigned m = base == 0 ? pm.x : pm.y;
 #if PT_VALIDATE_FILTER
-        if (alive && vstat) {  // the reference predicate of :100 and :109 must never accept a pair the mask dropped
+        if (alive && vstat) {  // the reference's whole test (:96-125, against the initial tmax of :141) must never accept a pair the mask dropped
             unsigned mx = 0u;
             for (int jj = 0; jj < n; ++jj) {
                 const PtTriRec r = pt_load_tri(T, base + jj);
@@ -893,6 +919,13 @@ PTK_DEV unsigned pt_intersect_primary(pt_const_f32p T, const PtPrepTriangle* tri
                 float tvx = o.x - r.p1x, tvy = o.y - r.p1y, tvz = o.z - r.p1z;
                 float u = pt_fma(tvz, pvz, pt_fma(tvy, pvy, tvx * pvx)) * inv_det;
                 keep = keep && !(u < 0.0f || u > 1.0f);
+                float qvx = pt_fma(tvy, r.e1z, -(tvz * r.e1y));
+                float qvy = pt_fma(tvz, r.e1x, -(tvx * r.e1z));
+                float qvz = pt_fma(tvx, r.e1y, -(tvy * r.e1x));
+                float v = pt_fma(d.z, qvz, pt_fma(d.y, qvy, d.x * qvx)) * inv_det;
+                keep = keep && !(v < 0.0f || u + v > 1.0f);
+                float tt = pt_fma(r.e2z, qvz, pt_fma(r.e2y, qvy, r.e2x * qvx)) * inv_det;
+                keep = keep && (tt > 0.0f && tt < 1e20f);
                 mx |= (keep ? 1u : 0u) << (n - 1 - jj);
             }
             atomicAdd(&vstat[0], (unsigned long long)n);
@@ -3451,12 +3484,11 @@ hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s)
 {
     if (!p.pmask || p.npix_local == 0) return hipSuccess;
     PtMaskParams m;
-    m.p1tab = p.p1tab;
+    m.tris = p.tris;
     m.out = const_cast<uint2*>(p.pmask);
     m.width = p.width; m.height = p.height; m.ntri = p.ntri;
     m.stripe_rows = p.stripe_rows; m.n_ranks = p.n_ranks; m.rank = p.rank;
     m.npix_local = p.npix_local;
-    m.p1_lo = p.p1_lo; m.p1_hi = p.p1_hi;
     m.cam = p.cam;
     hipLaunchKernelGGL(pt_primary_mask_kernel, dim3((p.npix_local + 255u) / 256u), dim3(256), 0, s, m);
     return hipGetLastError();

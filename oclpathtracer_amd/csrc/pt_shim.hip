@@ -1415,7 +1415,7 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
     if ((rc = choose_batch(d, use_bvh, npix, chunk, batch, bpf, blocks))) return rc;
     PtTraceParams tp = trace_params(d, mats, stats, rp, cam, npix, search, use_pmask, chunk, batch, bpf);
     if (make_pmask) {
-        HIP_TRY(ptk_primary_masks(tp, d->stream));  // (cheap: one thread per pixel)
+        HIP_TRY(ptk_primary_masks(tp, d->stream));  // (once per scene, camera and image geometry: one thread per pixel)
         d->pmask_key.valid = true;
     }
     // checkpointed launches (PtTraceParams::carry): the table kernels stop at a fresh-phase boundary, the LBVH kernel between two searches
@@ -2011,6 +2011,24 @@ extern "C" int pt_bvh_snapshot(pt_device_t d, pt_bvh_info* info, void* records, 
         if (d->bvh_records) HIP_TRY(hipMemcpy(records, d->bvh, d->bvh_records * sizeof(PtBvh8Node), hipMemcpyDeviceToHost));
     }
     if (big_indices && d->nbig > 0) HIP_TRY(hipMemcpy(big_indices, d->bigidx, (size_t)d->nbig * sizeof(int), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// test hook (include/pt_shim.h): the primary-ray candidate masks as the trace kernel reads them, copied out
+extern "C" int pt_primary_mask_snapshot(pt_device_t d, uint32_t* num_pixels, void* masks, size_t capacity)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!num_pixels) return fail(PT_ERR_INVALID, "pt_primary_mask_snapshot: num_pixels is null");
+    if ((rc = flush_pending(d)) || (rc = stream_wait(d))) return rc;   // (the masks are made on the handle's stream, read by the lanes)
+    if (!d->pmask_key.valid || d->pmask_key.scene_gen != d->scene_gen || !d->pmask.p)
+        return fail(PT_ERR_INVALID, "no primary-ray masks stand for the prepared scene");
+    const size_t npix = (size_t)(uint32_t)d->pmask_key.g[5];
+    *num_pixels = (uint32_t)npix;
+    if (masks) {
+        if (capacity < npix) return fail(PT_ERR_RANGE, "pt_primary_mask_snapshot: %zu pixels do not fit %zu", npix, capacity);
+        if (npix) HIP_TRY(hipMemcpy(masks, d->pmask.p, npix * sizeof(uint2), hipMemcpyDeviceToHost));
+    }
     return PT_OK;
 }
 

@@ -198,6 +198,7 @@ SIGNATURES = {
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_bvh_snapshot": (_c.c_int, [_H, _c.POINTER(BvhInfo), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "pt_primary_mask_snapshot": (_c.c_int, [_H, _c.POINTER(_c.c_uint32), _c.c_void_p, _c.c_size_t]),
     "pt_profile_query_union": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double)]),
     "pt_profile_reset": (_c.c_int, [_H]),
     "pt_assemble_stripes": (_c.c_int, [_H, _H, _H, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _H]),

@@ -2,7 +2,9 @@
 """Diagnostic: empirical check of the pass-1 conservative filter (needs the PT_VALIDATE_FILTER=1
 build).  For every (ray, triangle) pair actually traced, the reference's predicate of
 GenerateColors.cl:100,109 (literal form, IEEE division) is evaluated beside the filter; a pair the
-reference keeps but the filter dropped is a VIOLATION and must never occur.
+reference keeps but the filter dropped is a VIOLATION and must never occur.  The cached masks of primary
+rays (pt_primary_mask_kernel) are held to the whole test of :96-125 instead: for them "the reference keeps"
+means the reference ACCEPTS the pair (det, u, v, u + v, 0 < t < 1e20), and both kinds add to the same counters.
 usage: PT_SHIM_LIB=.../libptshim_validate.so python tools/validate_filter.py [scene] [W H spp] [quad_filter] [camera]
 (make -C oclpathtracer_amd/csrc ../libptshim_validate.so; quad_filter = PT_OPT_QUAD_FILTER, 0 = auto;
 camera = "ex,ey,ez,cx,cy,cz[,fov[,ux,uy,uz]]": eye, center, field of view, up -- the filters' anchor moves with the eye)"""
