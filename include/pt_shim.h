@@ -501,7 +501,7 @@ int pt_render_direct(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materia
  *  - B == 1: the framebuffer is pt_render_direct's, bit for bit -- for emission that is not negative: with an emissive component
  *    of -0 direct forms E + S / K from E = -0 where this forms 0 + E = +0 first; that case is excluded.
  * Not done here: multiple importance sampling (a BRDF ray that finds a light adds nothing at i > 0, so glossy surfaces next to
- * a light are noisy), light choice by power, Russian roulette.
+ * a light are noisy; pt_render_indirect_mis below does it), light choice by power, Russian roulette.
  * Behaviour: pt_render_direct's, word for word -- the handle's stream, behind renders in flight, asynchronous (ev); the prepared
  * scene, LBVH and filter tables as a query uses them; no allocation and no wait once the scene is prepared; PT_OPT_ACCEL and
  * PT_OPT_QUAD_FILTER choose the search; PT_ERR_TRAVERSAL is deferred; num_triangles = 0 renders the background.  Errors are
@@ -518,6 +518,59 @@ int pt_render_indirect(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t mater
                        pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, pt_buffer_t samples /* workspace */,
                        pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam /* NULL = the reference's */,
                        pt_event_t ev);
+
+/* ---- indirect illumination with multiple importance sampling ---------------------------------------------------------
+ * pt_render_indirect's estimator with the balance heuristic between its two ways of finding a light: the light samples of a
+ * vertex and the BRDF ray that leaves it.  A BRDF ray that runs into an emissive triangle at i > 0 adds its emission again,
+ * and both contributions carry weights that sum to 1 for a direction that finds the front of a listed triangle, so glossy
+ * surfaces next to a light stop being noisy.  A new estimator beside the old one: pt_render_indirect is unchanged.
+ *
+ * pt_light_counts writes counts[t] = the number of entries of lights[0 .. num_lights) whose index, clamped into [0,
+ * num_triangles) as pt_render_direct step 3b clamps it, equals t.  counts: the caller's int32[num_triangles].  One clear and one
+ * small kernel on the handle's stream, behind renders in flight, asynchronous (ev); nothing is allocated; num_lights = 0 clears;
+ * num_triangles = 0 enqueues nothing.  Errors, before anything is enqueued: PT_ERR_INVALID for counts NULL, num_lights > 0 with
+ * lights NULL, a negative size, num_lights >= 2^24, lights or counts not 4-byte aligned, the two overlapping, a buffer of another
+ * device; PT_ERR_RANGE for a buffer too small.
+ *
+ * pt_render_indirect_mis takes pt_render_indirect's arguments and parameter block (all four reserved words 0) and light_counts,
+ * an int32[num_triangles] as pt_light_counts writes it for the same list.  The estimator is pt_render_indirect's steps 1-4 with the
+ * following changes, ALL OF THEM ONLY WHEN nl > 0; with K = light_samples, B = max_bounces, and every "/" an IEEE division:
+ *  - A path carries one more value, pb: the pdf of the BRDF sample that made the current ray (step 2d's pdf, stored after the
+ *    pdf <= 0 test).
+ *  - A light sample (pt_render_direct steps 3a-3g, at any vertex) also forms sl = dot(wi, nj), so that cl = fabs(sl), and the
+ *    density of the vertex's BRDF sample towards wi: type 1: pbl = cs * INV_PI (:201); type 2: pbl = D * ct / (4.0f * dot(wo, wh))
+ *    (:215) from step 3e's wh, ct and D (formed whether or not :211 sets f = 0).  When i < B - 1 and sl > 0.0f, after step 3f:
+ *    a = area * (float)nl; pe = d2 / (cl * a); kp = (float)K * pe; w = w * (kp / (kp * (float)counts[j] + pbl)).  Otherwise w is
+ *    step 3f's, unchanged: at the last vertex no BRDF ray follows, and with sl <= 0 the vertex sees the light's back, the side the
+ *    one-sided triangle test (:100) lets no ray hit, so no BRDF ray can share that sample's weight.  Both rules are part of the
+ *    estimator, not options: without either the weights no longer sum to 1.
+ *  - The emission at a later vertex: when i >= 1 and any component of m.emissive is != 0, with h the triangle hit, t the hit's
+ *    distance, d the ray's direction and N = cross(e2, e1) of triangle h (:123): areah = 0.5f * sqrt(dot(N, N)); clh = fabs(dot(d,
+ *    normalize(N))); tt = t + 0.01f (the ray began 0.01 off the vertex before, :257, so both techniques form pe from the same
+ *    distance); pe = (tt * tt) / (clh * (areah * (float)nl)); wb = pb / (((float)K * pe) * (float)counts[h] + pb); L.c = L.c +
+ *    ((mask.c * m.emissive.c) * 3.0f) * wb.  A hit on a material with no emissive component reads no count and adds nothing.  At
+ *    i == 0 the emission is added as in step 2b.
+ * Why the weights partition: for a direction that finds the front of triangle h, the counts[h] list entries that name it give the
+ * light samples the density kp each against the BRDF's p, and counts[h] * kp / (kp * counts[h] + p) + p / (kp * counts[h] + p) = 1.
+ * Because the count is per triangle, a duplicated entry, a missing emitter (counts[h] = 0: wb = 1, the BRDF ray carries all of it)
+ * or an unsorted list leave the image unbiased AT EVERY VERTEX BUT THE LAST, where the light samples are unweighted and nothing
+ * follows: there a duplicated entry still counts twice and an emitter missing from the list is still lost.  pt_render_indirect's
+ * rule that the list must hold every emissive triangle is relaxed to that last vertex only.
+ * Not changed by this: the bounded but large weight of a light sample that sees a light from its back at a short distance (a
+ * ceiling vertex above a light that hangs just below it).
+ * Identities: nl == 0: light_counts may be NULL and is not read, and the framebuffer is pt_render_frames' at the same
+ * max_bounces, bit for bit; B == 1: the only vertex is the last, and the framebuffer is pt_render_direct's, bit for bit (under
+ * pt_render_indirect's exclusion of an emissive component of -0).
+ * Behaviour and errors: pt_render_indirect's, word for word -- one validation, one chunk loop, one fold --, plus, when num_lights
+ * > 0: PT_ERR_INVALID for light_counts NULL, not 4-byte aligned, of another device, or overlapping samples, framebuffer or lights;
+ * PT_ERR_RANGE for light_counts smaller than num_triangles x 4 bytes. */
+int pt_light_counts(pt_device_t dev, pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, int num_lights, int num_triangles,
+                    pt_buffer_t counts /* int32[num_triangles] */, pt_event_t ev);
+int pt_render_indirect_mis(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                           pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */,
+                           pt_buffer_t light_counts /* int32[num_triangles]; may be NULL when num_lights is 0 */,
+                           pt_buffer_t samples /* workspace */, pt_buffer_t framebuffer, const pt_indirect_params* params,
+                           const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
 
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.

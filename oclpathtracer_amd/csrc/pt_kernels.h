@@ -300,9 +300,18 @@ struct PtIndirectParams {
     PtDirectParams d;
     int32_t B;                    // max_bounces, 1 .. 65535
 };
-// bvh_blocks: CUs x ptk_indirect_bvh_blocks_per_cu -- the LBVH kernel's own occupancy (a path's state is larger than a direct sample's)
-hipError_t ptk_indirect(const PtIndirectParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s);
+// pt_render_indirect_mis: the MIS = true instantiations take this block, the others PtIndirectParams as before (their code does not move)
+struct PtIndirectMisParams : PtIndirectParams {
+    const int32_t* counts;        // [ntri] list entries per triangle (ptk_light_counts); not read when nl = 0
+};
+// bvh_blocks: CUs x ptk_indirect_bvh_blocks_per_cu -- the LBVH kernel's own occupancy (a path's state is larger than a direct sample's).
+// mis: pt_render_indirect_mis's estimator (the MIS = true instantiations of the same kernels); bvh_blocks is then CUs x
+// ptk_indirect_mis_bvh_blocks_per_cu
+hipError_t ptk_indirect(const PtIndirectMisParams& a, int bvh_blocks, PtSearchMode m, bool mis, hipStream_t s);
 int ptk_indirect_bvh_blocks_per_cu(void);
+int ptk_indirect_mis_bvh_blocks_per_cu(void);
+// counts[t] = the entries of lights[0 .. nl) whose index, clamped into [0, ntri), is t: one clear, one kernel of vector atomics
+hipError_t ptk_light_counts(const int32_t* lights, int nl, int ntri, int32_t* counts, hipStream_t s);
 // rays[2 gid], rays[2 gid + 1] = the pt_ray of pixel gid, frame `frame` (the renderer's sample start) for the camera cam
 hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s);
 // dynamic LDS of a trace workgroup (pt_kernels.hip: pt_lds_total, pt_bvh_lds_total)

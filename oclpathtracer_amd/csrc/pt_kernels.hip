@@ -29,6 +29,8 @@
 
 #include "pt_device_math.h"
 
+#include <type_traits>
+
 typedef const __attribute__((address_space(4))) float* pt_const_f32p;  // scalar (SMEM) loads
 
 PTK_DEV unsigned pt_lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
@@ -3055,8 +3057,12 @@ PTK_DEV void pt_direct_surface(const PtDirectParams& D, const f3& o, const f3& d
 // contribution if the shadow ray (o, d) is open, and tl the ray's limit (not above 0: nothing is searched, the ray is open).  The
 // three uniforms are drawn whatever follows.  The quotients are pt_div's: the short form inside its guarded window, the generic
 // division outside it -- the IEEE quotient either way.
+// MIS (pt_render_indirect_mis): with `weigh` (the vertex is not the path's last) and the light's front towards the vertex (sl > 0) the
+// weight takes the balance factor kp / (kp counts[j] + pbl) against the BRDF's density pbl towards wi; these quotients are the
+// generic IEEE division (their operands have no proven window).  MIS = false is the code of pt_render_direct and pt_render_indirect.
+template <bool MIS = false>
 PTK_DEV bool pt_direct_light(const PtDirectParams& D, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed, f3& c, f3& o, f3& d,
-                             float& tl)
+                             float& tl, const int32_t* counts = nullptr, bool weigh = false)
 {
     const float r0 = pt_random_float(seed), r1 = pt_random_float(seed), r2 = pt_random_float(seed);
     const float nlf = (float)D.nl;
@@ -3075,19 +3081,22 @@ PTK_DEV bool pt_direct_light(const PtDirectParams& D, const f3& p, const f3& n, 
     const float d2 = dot3(dv, dv);
     const float dist = pt_sqrt(d2);
     const f3 wi = scale3(dv, pt_normalize_factor(d2));
-    const float cs = dot3(wi, n), cl = __builtin_fabsf(dot3(wi, nj));
+    const float cs = dot3(wi, n), sl = dot3(wi, nj), cl = __builtin_fabsf(sl);
     if (!(cs > 0.0f && cl > 0.0f)) return false;   // (false for NaN: q == p, a light of no area)
     const float4 alb = pt_rec16(D.t.mats, mid, 0u), rt = pt_rec16(D.t.mats, mid, 32u);   // albedo | roughness, type
     const int type = __float_as_int(rt.y);
     f3 f;
+    float pbl = 0.0f;   // (MIS) the BRDF sample's density towards wi
     if (type == 1) {   // :203
         f = mk3(alb.x * PTK_INV_PI, alb.y * PTK_INV_PI, alb.z * PTK_INV_PI);
+        if constexpr (MIS) pbl = cs * PTK_INV_PI;   // :201
     } else if (type == 2) {   // :205-217 at the half vector of wo and wi
         const f3 wh = normalize3(add3(wo, wi));
         const float ct = dot3(wh, n);
         const float r2g = rt.x * rt.x;
         const float gd = ct * ct * (r2g - 1.0f) + 1.0f;
         const float Dg = pt_div(r2g * PTK_INV_PI, gd * gd);   // pow(x, 2.0f) is x*x in PTSPEC (:177)
+        if constexpr (MIS) pbl = Dg * ct / (4.0f * dot3(wo, wh));   // :215
         const float dwon = dot3(wo, n);
         if (cs * dwon < 0.0f) {   // :211
             f = mk3(0.0f, 0.0f, 0.0f);
@@ -3099,7 +3108,15 @@ PTK_DEV bool pt_direct_light(const PtDirectParams& D, const f3& p, const f3& n, 
         return false;   // :220
     }
     const float4 emj = pt_rec16(D.t.mats, pt_clamp_index(__float_as_int(nid.w), D.t.nmat), 16u);
-    const float w = pt_div(cs * cl, d2) * (area * nlf);
+    float w = pt_div(cs * cl, d2) * (area * nlf);
+    if constexpr (MIS) {
+        if (weigh && sl > 0.0f) {
+            const float a = area * nlf;
+            const float pe = d2 / (cl * a);
+            const float kp = (float)D.K * pe;
+            w = w * (kp / (kp * (float)counts[j] + pbl));
+        }
+    }
     c = mk3((f.x * (emj.x * 3.0f)) * w, (f.y * (emj.y * 3.0f)) * w, (f.z * (emj.z * 3.0f)) * w);
     o = add3(p, scale3(wi, 0.01f));   // :257
     d = normalize3(wi);
@@ -3231,6 +3248,10 @@ void pt_direct_bvh_kernel(const PtDirectParams D)
 // i == 0 or there are no lights, K light samples (pt_direct_light) whose open shadow rays sum to S and L += mask * (S / K), then the
 // BRDF sample (pt_indirect_bounce), which ends the path at pdf <= 0 and otherwise scales mask and gives the next ray.
 // samples[item] = max(L, 0); pt_fold_kernel folds them.
+// MIS (pt_render_indirect_mis) is a compile-time flag of the same kernels: the light samples of every vertex but the last are
+// weighted against the BRDF sample (pt_direct_light<true>), the path carries that sample's pdf (pb), and a later vertex on an emitter
+// adds its emission weighted the other way (pt_indirect_emission_mis).  The MIS = false instantiations are pt_render_indirect's code,
+// instruction for instruction (profiles/mis/disasm_comparison.txt); they take PtIndirectParams, the others PtIndirectMisParams.
 
 // The BRDF sample at the vertex (p, n, wo) on material mid: Brdf (:195-221) and :251-257 as pt_shade states them -- the same draws
 // (phi, then the second uniform), the same shared sqrt pair, the same guarded short quotients (pt_div_by, pt_div, pt_div_pair,
@@ -3238,8 +3259,9 @@ void pt_direct_bvh_kernel(const PtDirectParams D)
 // kernels do not move; with no lights the two must agree bit for bit (tests/test_gpu_indirect.py).  False: pdf <= 0, the path ends
 // (:251); true: mask has taken the bounce's three quotients and (o, d) is the next ray (:257).  The material is gathered by its index
 // (pt_direct_light's gathers): nothing of it is held across a search.
+template <bool MIS = false>
 PTK_DEV bool pt_indirect_bounce(const PtDirectParams& D, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed, f3& mask, f3& o,
-                                f3& d)
+                                f3& d, float* pb = nullptr)
 {
     const float phi = PTK_TWO_PI * pt_random_float(seed);
     const float xi = pt_random_float(seed);
@@ -3286,6 +3308,7 @@ PTK_DEV bool pt_indirect_bounce(const PtDirectParams& D, const f3& p, const f3& 
         }
     }
     if (pdf <= 0.0f) return false;   // :251
+    if constexpr (MIS) *pb = pdf;   // (MIS: the path carries it to the next vertex's emission)
     float qx = color.x * dwin, qy = color.y * dwin, qz = color.z * dwin;
     pt_div3(qx, qy, qz, pdf);   // the three IEEE quotients of :253-255
     mask.x = mask.x * qx;
@@ -3296,6 +3319,15 @@ PTK_DEV bool pt_indirect_bounce(const PtDirectParams& D, const f3& p, const f3& 
     return true;
 }
 
+// pt_light_counts: counts[t] = the list entries that name triangle t, each clamped as pt_direct_light clamps it (the host has cleared
+// counts; ntri >= 1).  One vector atomic per entry
+__global__ __launch_bounds__(256) void pt_light_counts_kernel(const int32_t* __restrict__ lights, int nl, int ntri, int32_t* __restrict__ counts)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)nl) return;
+    atomicAdd(counts + pt_clamp_index(lights[i], ntri), 1);
+}
+
 // :241, in that order
 PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f3& mask, f3& L)
 {
@@ -3303,6 +3335,33 @@ PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f
     L.x = L.x + mask.x * emi.x * 3.0f;
     L.y = L.y + mask.y * emi.y * 3.0f;
     L.z = L.z + mask.z * emi.z * 3.0f;
+}
+
+// the parameter block of an instantiation, and its counts (none without MIS)
+template <bool MIS> using PtIndirectArgs = std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>;
+PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectParams&) { return nullptr; }
+PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectMisParams& I) { return I.counts; }
+
+// (MIS) the emission of a vertex i >= 1, found by the BRDF ray (o, d) at distance t, weighted against the light samples of the vertex
+// before: pe is the density those give the same point -- from the hit triangle's record N = cross(e2, e1), its own distance
+// tt = t + 0.01f (the ray began 0.01 off that vertex, :257) and its count --, pb the density of the BRDF sample that made the ray.
+// A material with no emissive component reads no count and adds nothing
+PTK_DEV void pt_indirect_emission_mis(const PtDirectParams& D, const int32_t* counts, unsigned mid, int hidx, const f3& d, float t, float pb,
+                                      const f3& mask, f3& L)
+{
+    const float4 emi = pt_rec16(D.t.mats, mid, 16u);
+    if (!(emi.x != 0.0f || emi.y != 0.0f || emi.z != 0.0f)) return;
+    const float4 nid = pt_rec16(D.t.tris, (unsigned)hidx, 48u);
+    const f3 N = mk3(nid.x, nid.y, nid.z);
+    const float N2 = dot3(N, N);
+    const float areah = 0.5f * pt_sqrt(N2);
+    const float clh = __builtin_fabsf(dot3(d, scale3(N, pt_normalize_factor(N2))));
+    const float tt = t + 0.01f;
+    const float pe = (tt * tt) / (clh * (areah * (float)D.nl));
+    const float wb = pb / (((float)D.K * pe) * (float)counts[hidx] + pb);
+    L.x = L.x + ((mask.x * emi.x) * 3.0f) * wb;
+    L.y = L.y + ((mask.y * emi.y) * 3.0f) * wb;
+    L.z = L.z + ((mask.z * emi.z) * 3.0f) * wb;
 }
 
 // L += mask * (S / K) of a vertex's light samples
@@ -3322,8 +3381,8 @@ PTK_DEV void pt_indirect_store(const PtDirectParams& D, unsigned item, const f3&
 // brute force: one wave = 64 consecutive samples, pt_direct_kernel's shape inside a loop over the bounces.  The wave searches in step
 // with the lanes still alive and leaves the loop when none is; a light sample no lane casts a ray for costs no search.  Lanes whose
 // path has ended are NOT given new samples: the wave runs as long as its longest path (DESIGN.md S4 states the cost).
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
-__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtIndirectParams I)
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS = false>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtIndirectArgs<MIS> I)
 {
     const PtDirectParams& D = I.d;
     const PtTraceParams& P = D.t;
@@ -3338,6 +3397,7 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
     f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f);
     if (act) pt_item_begin(P, D.cam, D.npix, D.frame0, item, lp, seed, o, d);
     f3 L = mk3(0.0f, 0.0f, 0.0f), mask = mk3(1.0f, 1.0f, 1.0f);
+    [[maybe_unused]] float pb = 0.0f;   // (MIS) the pdf of the BRDF sample that made the current ray
     bool alive = act;
     for (int i = 0; i < I.B; ++i) {
         float tmax = 1e20f, hu = 0.0f, hv = 0.0f;
@@ -3353,6 +3413,7 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
         if (hit) {
             pt_direct_surface(D, o, d, tmax, hu, hv, hidx, p, n, wo, mid);
             if (i == 0 || D.nl == 0) pt_indirect_emission(D, mid, mask, L);
+            else if constexpr (MIS) pt_indirect_emission_mis(D, pt_indirect_counts(I), mid, hidx, d, tmax, pb, mask, L);
         }
         if (D.nl > 0) {
             f3 S = mk3(0.0f, 0.0f, 0.0f);
@@ -3360,7 +3421,7 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
                 f3 c = mk3(0.0f, 0.0f, 0.0f);
                 float tlim = 0.0f;
                 bool cast = false;
-                if (hit) cast = pt_direct_light(D, p, n, wo, mid, seed, c, o, d, tlim);
+                if (hit) cast = pt_direct_light<MIS>(D, p, n, wo, mid, seed, c, o, d, tlim, pt_indirect_counts(I), i < I.B - 1);
                 const bool live = cast & (tlim > 0.0f);
                 bool occluded = false;
                 if (__ballot(live) != 0ull) {
@@ -3375,7 +3436,7 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
             if (hit) pt_indirect_lit(D, mask, S, L);
         }
         if (i == I.B - 1) break;   // (the last vertex's draw cannot be observed)
-        if (hit) alive = pt_indirect_bounce(D, p, n, wo, mid, seed, mask, o, d);
+        if (hit) alive = pt_indirect_bounce<MIS>(D, p, n, wo, mid, seed, mask, o, d, &pb);
         if (__ballot(alive) == 0ull) break;
     }
     if (act) pt_indirect_store(D, item, L);
@@ -3387,9 +3448,12 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
 // any-hit result to the next contributing one; after the last comes the BRDF sample and the next closest search, or the store.
 // Between searches a lane holds PtDirectWork's state (the surface p, n, wo, the material's INDEX, S, c) and mask, L and the bounce.
 // wo is the negated incoming direction, which the shadow rays overwrite in d, so it is kept; o is dead while p is live.
+// With MIS a lane also holds pb from the BRDF sample to the next closest hit, across that search: 34 registers.  The counts and the
+// emitter's record are gathered where they are used, as the materials are.
+template <bool MIS = false>
 struct PtIndirectWork {
     static constexpr bool ANY = true;
-    const PtIndirectParams& I;
+    const PtIndirectArgs<MIS>& I;
     unsigned n;
     int k;           // the current ray: -1 = the vertex's closest search, 0 .. K-1 = the shadow ray of light sample k
     int bounce;      // loop index i of traceRays (:229)
@@ -3397,6 +3461,7 @@ struct PtIndirectWork {
     uint32_t seed;
     float tl;        // the shadow ray's limit
     f3 o, d, p, nrm, wo, S, c, mask, L;
+    float pb;        // (MIS; otherwise never touched) the pdf of the BRDF sample that made the current ray
     PTK_DEV void begin(unsigned item_)
     {
         unsigned lp;
@@ -3418,16 +3483,20 @@ struct PtIndirectWork {
             }
             pt_direct_surface(D, o, d, R.tmax, R.hu, R.hv, R.hidx, p, nrm, wo, mid);
             if (bounce == 0 || D.nl == 0) pt_indirect_emission(D, mid, mask, L);
+            else if constexpr (MIS) pt_indirect_emission_mis(D, pt_indirect_counts(I), mid, R.hidx, d, R.tmax, pb, mask, L);
             S = mk3(0.0f, 0.0f, 0.0f);
         } else if (R.hidx < 0) {   // (an any-hit search: R.hidx >= 0 alone says occluded; a ray that searched nothing is open)
             S = add3(S, c);
         }
         if (D.nl > 0) {
             while (++k < D.K)
-                if (pt_direct_light(D, p, nrm, wo, mid, seed, c, o, d, tl)) return true;
+                if (pt_direct_light<MIS>(D, p, nrm, wo, mid, seed, c, o, d, tl, pt_indirect_counts(I), bounce < I.B - 1)) return true;
             pt_indirect_lit(D, mask, S, L);
         }
-        if (++bounce < I.B && pt_indirect_bounce(D, p, nrm, wo, mid, seed, mask, o, d)) {
+        bool on;
+        if constexpr (MIS) on = ++bounce < I.B && pt_indirect_bounce<true>(D, p, nrm, wo, mid, seed, mask, o, d, &pb);
+        else on = ++bounce < I.B && pt_indirect_bounce(D, p, nrm, wo, mid, seed, mask, o, d);
+        if (on) {
             k = -1;
             return true;
         }
@@ -3443,16 +3512,18 @@ struct PtIndirectWork {
 
 // Three waves per SIMD (168 VGPRs), chosen from the compiler's resource report (profiles/indirect/kernel_resources.txt): a path's
 // state between its searches is 33 registers against direct's 25, and at direct's four waves (128 VGPRs) the kernel spills 25 of
-// them to scratch; at three it uses 158-159 and spills none.  Its persistent grid is its own figure, ptk_indirect_bvh_blocks_per_cu
+// them to scratch; at three it uses 158-159 and spills none.  Its persistent grid is its own figure, ptk_indirect_bvh_blocks_per_cu.
+// The MIS instantiations use 163-164 of the 168 at the same three waves and spill none either (profiles/mis/kernel_resources.txt);
+// their grid figure is ptk_indirect_mis_bvh_blocks_per_cu (the same occupancy, asked of their own code objects)
 #ifndef PT_INDIRECT_BVH_WAVES   // (tools/kernel_resources.sh -DPT_INDIRECT_BVH_WAVES=4 reads the other choice)
 #define PT_INDIRECT_BVH_WAVES 3
 #endif
-template <bool DET_BOUNDED, int BIGQ>
+template <bool DET_BOUNDED, int BIGQ, bool MIS = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_INDIRECT_BVH_WAVES, PT_INDIRECT_BVH_WAVES)))
-void pt_indirect_bvh_kernel(const PtIndirectParams I)
+void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS> I)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtIndirectWork W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0 };
+    PtIndirectWork<MIS> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(I.d.t, W);
 }
 
@@ -3653,18 +3724,35 @@ hipError_t ptk_direct(const PtDirectParams& a, int bvh_blocks, PtSearchMode m, h
 
 int ptk_direct_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_direct_bvh_kernel<true, 3>, ptk_trace_bvh_lds_bytes()); }
 
-hipError_t ptk_indirect(const PtIndirectParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
+hipError_t ptk_indirect(const PtIndirectMisParams& a, int bvh_blocks, PtSearchMode m, bool mis, hipStream_t s)
 {
     if (a.d.nitems == 0) return hipSuccess;
     const bool q3 = m.quads == 3;
+    if (mis) {
+        void (*kernel)(const PtIndirectMisParams);
+        if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3, true>, pt_indirect_bvh_kernel<true, 0, true>, pt_indirect_bvh_kernel<false, 0, true>);
+        else if (a.d.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_kernel<true, 1, 3, true>, pt_indirect_kernel<true, 1, 0, true>, pt_indirect_kernel<false, 1, 0, true>);
+        else kernel = m.det_bounded ? pt_indirect_kernel<true, 2, 0, true> : pt_indirect_kernel<false, 2, 0, true>;
+        return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, m.bvh, bvh_blocks, s);
+    }
     void (*kernel)(const PtIndirectParams);
     if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3>, pt_indirect_bvh_kernel<true, 0>, pt_indirect_bvh_kernel<false, 0>);
     else if (a.d.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_kernel<true, 1, 3>, pt_indirect_kernel<true, 1, 0>, pt_indirect_kernel<false, 1, 0>);
     else kernel = m.det_bounded ? pt_indirect_kernel<true, 2, 0> : pt_indirect_kernel<false, 2, 0>;
-    return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, m.bvh, bvh_blocks, s);
+    return pt_launch_search(kernel, static_cast<const PtIndirectParams&>(a), a.d.t.ntri, a.d.nitems, m.bvh, bvh_blocks, s);
+}
+
+hipError_t ptk_light_counts(const int32_t* lights, int nl, int ntri, int32_t* counts, hipStream_t s)
+{
+    if (ntri <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)ntri * sizeof(int32_t), s);
+    if (e != hipSuccess || nl <= 0) return e;
+    hipLaunchKernelGGL(pt_light_counts_kernel, dim3(((unsigned)nl + 255u) / 256u), dim3(256), 0, s, lights, nl, ntri, counts);
+    return hipGetLastError();
 }
 
 int ptk_indirect_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3>, ptk_trace_bvh_lds_bytes()); }
+int ptk_indirect_mis_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true>, ptk_trace_bvh_lds_bytes()); }
 
 hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s)
 {

@@ -138,6 +138,7 @@ struct pt_device_s {
     int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query and ambient-occlusion kernels (pt_bvh_drive)
     int direct_bvh_blocks_per_cu;  // ... and of the direct-illumination kernel, which runs at four waves per SIMD
     int indirect_bvh_blocks_per_cu;   // ... and of the indirect-illumination kernel, at its own occupancy
+    int indirect_mis_bvh_blocks_per_cu;   // ... and of its MIS instantiation
     unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
     unsigned int* trav_dev;  // ... as the device addresses it
     // ---- fused-render workspace: the STREAMING renderer (render_part, plan_chunks, the ring).  A render walks its frames in chunks of
@@ -360,6 +361,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
     d->direct_bvh_blocks_per_cu = ptk_direct_bvh_blocks_per_cu();
     d->indirect_bvh_blocks_per_cu = ptk_indirect_bvh_blocks_per_cu();
+    d->indirect_mis_bvh_blocks_per_cu = ptk_indirect_mis_bvh_blocks_per_cu();
     *out = d;
     return PT_OK;
 }
@@ -1766,21 +1768,24 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
 static_assert(sizeof(pt_direct_params) == 64, "pt_direct_params layout");
 static_assert(sizeof(pt_indirect_params) == 64, "pt_indirect_params layout");
 
-// pt_render_direct and pt_render_indirect: one validation, one chunk loop.  `a`: the fields the two parameter blocks share (each
-// entry point has looked at its own reserved ones).  max_bounces: 0 = direct illumination (its own kernels), otherwise the depth of
-// an indirect render.  what: the message for a field out of range
-static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples, pt_buffer_t framebuffer,
-                      const pt_direct_params& a, int max_bounces, const char* what, const pt_camera* cam, pt_event_t ev)
+// pt_render_direct, pt_render_indirect and pt_render_indirect_mis: one validation, one chunk loop.  `a`: the fields the parameter
+// blocks share (each entry point has looked at its own reserved ones).  max_bounces: 0 = direct illumination (its own kernels),
+// otherwise the depth of an indirect render.  mis: the MIS estimator, which reads light_counts (NULL otherwise).  what: the message
+// for a field out of range
+static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts, bool mis,
+                      pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params& a, int max_bounces, const char* what,
+                      const pt_camera* cam, pt_event_t ev)
 {
     int rc;
     PtCamera c = reference_camera();
     if (cam && (rc = camera_derive(cam, &c))) return rc;
     if (!triangles || !materials || !samples || !framebuffer) return fail(PT_ERR_INVALID, "null buffer handle");
-    if ((rc = check_same_device(d, { triangles, materials, lights, samples, framebuffer })) || (rc = check_event(d, ev))) return rc;
+    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer })) || (rc = check_event(d, ev))) return rc;
     if (a.num_triangles < 0 || a.num_materials < 1 || a.num_lights < 0 || a.light_samples < 1 || a.light_samples > 256)
         return fail(PT_ERR_INVALID, "%s", what);
     if (a.num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
     if (a.num_lights > 0 && !lights) return fail(PT_ERR_INVALID, "num_lights > 0 needs a light list");
+    if (mis && a.num_lights > 0 && !light_counts) return fail(PT_ERR_INVALID, "num_lights > 0 needs the light counts (pt_light_counts)");
     // the light's record and the materials are gathered by 32-bit byte offsets into the 64-byte records, as shading gathers them
     if ((uint64_t)a.num_triangles * 64u > 0xffffffffull || (uint64_t)a.num_materials * 64u > 0xffffffffull)
         return fail(PT_ERR_INVALID, "a scene has fewer than 2^26 triangles and 2^26 materials");
@@ -1802,6 +1807,15 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     if (ranges_overlap(samples, samples->bytes, framebuffer, fb_bytes)) return fail(PT_ERR_INVALID, "the sample workspace and the framebuffer overlap");
     if (lights && (ranges_overlap(lights, light_bytes, samples, samples->bytes) || ranges_overlap(lights, light_bytes, framebuffer, fb_bytes)))
         return fail(PT_ERR_INVALID, "the light list overlaps the sample workspace or the framebuffer");
+    if (mis && a.num_lights > 0) {   // (with no lights the counts are not read)
+        const size_t count_bytes = (size_t)a.num_triangles * sizeof(int32_t);
+        if (count_bytes > light_counts->bytes)
+            return fail(PT_ERR_RANGE, "light counts hold %zu bytes, %d triangles need %zu", light_counts->bytes, a.num_triangles, count_bytes);
+        if ((uintptr_t)light_counts->dptr & 3u) return fail(PT_ERR_INVALID, "the light counts must be 4-byte aligned");
+        if (ranges_overlap(light_counts, count_bytes, samples, samples->bytes) || ranges_overlap(light_counts, count_bytes, framebuffer, fb_bytes) ||
+            ranges_overlap(light_counts, count_bytes, lights, light_bytes))
+            return fail(PT_ERR_INVALID, "the light counts overlap the sample workspace, the framebuffer or the light list");
+    }
     // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
     if ((rc = check_traversal(d))) return rc;
     if ((rc = enter_stream(d))) return rc;
@@ -1812,7 +1826,7 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     PtSearch search;
     if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
     if ((rc = event_begin(d, ev))) return rc;
-    PtIndirectParams ip;
+    PtIndirectMisParams ip;
     memset(&ip, 0, sizeof ip);
     ip.B = max_bounces;
     PtDirectParams& p = ip.d;
@@ -1826,20 +1840,22 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     p.npix = npix;
     p.K = a.light_samples;
     p.nl = a.num_lights;
+    ip.counts = mis && a.num_lights > 0 ? (const int32_t*)light_counts->dptr : nullptr;
     PtFoldParams fp;
     memset(&fp, 0, sizeof fp);
     fp.rad = p.samples;
     fp.fb = (float4*)framebuffer->dptr;
     fp.npix_local = npix;
     const int bvh_blocks = !search.mode.bvh ? 0   // (each kernel its own grid: pt_kernels.h)
-                                            : d->prop.multiProcessorCount * (max_bounces > 0 ? d->indirect_bvh_blocks_per_cu : d->direct_bvh_blocks_per_cu);
+                                            : d->prop.multiProcessorCount * (mis ? d->indirect_mis_bvh_blocks_per_cu
+                                                                                 : max_bounces > 0 ? d->indirect_bvh_blocks_per_cu : d->direct_bvh_blocks_per_cu);
     // whole frames per chunk: what the workspace holds, fewer than 2^31 samples per launch; a launch, then its fold
     const int64_t per_chunk = (int64_t)std::min<uint64_t>(samples->bytes / frame_bytes, 0x7fffffffu / npix);
     for (int64_t done = 0; done < a.frame_count; done += per_chunk) {
         const int nf = (int)std::min<int64_t>(per_chunk, a.frame_count - done);
         p.frame0 = a.frame_begin + (int)done;
         p.nitems = (uint32_t)nf * npix;
-        HIP_TRY(max_bounces > 0 ? ptk_indirect(ip, bvh_blocks, search.mode, d->stream) : ptk_direct(p, bvh_blocks, search.mode, d->stream));
+        HIP_TRY(max_bounces > 0 ? ptk_indirect(ip, bvh_blocks, search.mode, mis, d->stream) : ptk_direct(p, bvh_blocks, search.mode, d->stream));
         fp.frame_begin = p.frame0;
         fp.frame_count = nf;
         HIP_TRY(ptk_fold(fp, d->stream));
@@ -1858,12 +1874,13 @@ extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_
     const pt_direct_params a = *params;
     for (int i = 0; i < 5; ++i)
         if (a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
-    return render_lit(d, triangles, materials, lights, samples, framebuffer, a, 0, "invalid direct-illumination parameters", cam, ev);
+    return render_lit(d, triangles, materials, lights, nullptr, false, samples, framebuffer, a, 0, "invalid direct-illumination parameters", cam, ev);
 }
 
 // ---- indirect illumination (include/pt_shim.h) ---------------------------------------------------------------------------------
-extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
-                                  pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
+// pt_render_indirect and pt_render_indirect_mis: the same parameter block, the same checks of it
+static int render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts, bool mis,
+                           pt_buffer_t samples, pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
 {
     int rc = use_device(d);
     if (rc) return rc;
@@ -1878,7 +1895,42 @@ extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffe
     a.num_triangles = b.num_triangles; a.num_materials = b.num_materials; a.num_lights = b.num_lights;
     a.light_samples = b.light_samples;
     a.stripe_rows = b.stripe_rows; a.n_ranks = b.n_ranks; a.rank = b.rank;
-    return render_lit(d, triangles, materials, lights, samples, framebuffer, a, b.max_bounces, "invalid indirect-illumination parameters", cam, ev);
+    return render_lit(d, triangles, materials, lights, light_counts, mis, samples, framebuffer, a, b.max_bounces,
+                      "invalid indirect-illumination parameters", cam, ev);
+}
+
+extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
+                                  pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
+{
+    return render_indirect(d, triangles, materials, lights, nullptr, false, samples, framebuffer, params, cam, ev);
+}
+
+extern "C" int pt_render_indirect_mis(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts,
+                                      pt_buffer_t samples, pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam,
+                                      pt_event_t ev)
+{
+    return render_indirect(d, triangles, materials, lights, light_counts, true, samples, framebuffer, params, cam, ev);
+}
+
+extern "C" int pt_light_counts(pt_device_t d, pt_buffer_t lights, int num_lights, int num_triangles, pt_buffer_t counts, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!counts) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { lights, counts })) || (rc = check_event(d, ev))) return rc;
+    if (num_lights < 0 || num_triangles < 0) return fail(PT_ERR_INVALID, "invalid light-count parameters");
+    if (num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
+    if (num_lights > 0 && !lights) return fail(PT_ERR_INVALID, "num_lights > 0 needs a light list");
+    const size_t light_bytes = (size_t)num_lights * sizeof(int32_t), count_bytes = (size_t)num_triangles * sizeof(int32_t);
+    if (lights && light_bytes > lights->bytes) return fail(PT_ERR_RANGE, "light list holds %zu bytes, %d lights need %zu", lights->bytes, num_lights, light_bytes);
+    if (count_bytes > counts->bytes) return fail(PT_ERR_RANGE, "light counts hold %zu bytes, %d triangles need %zu", counts->bytes, num_triangles, count_bytes);
+    if (count_bytes && ((uintptr_t)counts->dptr & 3u)) return fail(PT_ERR_INVALID, "the light counts must be 4-byte aligned");
+    if (lights && num_lights > 0 && ((uintptr_t)lights->dptr & 3u)) return fail(PT_ERR_INVALID, "the light list must be 4-byte aligned");
+    if (lights && ranges_overlap(lights, light_bytes, counts, count_bytes)) return fail(PT_ERR_INVALID, "the light list and the light counts overlap");
+    if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
+    HIP_TRY(ptk_light_counts(num_lights > 0 ? (const int32_t*)lights->dptr : nullptr, num_lights, num_triangles, (int32_t*)counts->dptr, d->stream));
+    counts->version++;
+    return event_end(d, ev);
 }
 
 extern "C" int pt_camera_rays(pt_device_t d, const pt_camera* cam, int width, int height, int frame, pt_buffer_t rays, pt_event_t ev)

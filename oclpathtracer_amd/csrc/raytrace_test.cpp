@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination | --only IndirectIllumination]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination | --only IndirectIllumination [--mis]]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <chrono>
 #include <cmath>
@@ -117,7 +117,7 @@ static bool loadModel(const char* filepath, std::vector<Triangle>& tBuffer, std:
 // ---- fixture -------------------------------------------------------------------------------------
 struct Options {
     int deviceIdx = 0, dim = 512, frames = 10000;
-    bool batch = true;
+    bool batch = true, mis = false;   // mis: IndirectIllumination through pt_render_indirect_mis
     std::string scene = "cornellbox.bin", outDir = ".", dump, only;
 };
 
@@ -364,6 +364,8 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
 //
 // TEST_F(DeviceTest, IndirectIllumination): likewise declared empty (RaytraceTest.cpp:301-303).  Here it is the same scene through
 // pt_render_indirect -- paths of 16 bounces, K = 1 light sample at every vertex -- written to indirectIllumination_<version>.ppm.
+// With --mis it is pt_render_indirect_mis -- the same paths with multiple importance sampling, the light counts made by
+// pt_light_counts -- written to indirectIllumination_<version>_mis.ppm.
 // bounces: 0 = DirectIllumination, otherwise IndirectIllumination at that depth.
 static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
 {
@@ -388,6 +390,7 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     Buffer<Triangle> tBuffer(m_d, triangles.size());
     Buffer<Material> mBuffer(m_d, materials.size());
     Buffer<int> lBuffer(m_d, lights.size() ? lights.size() : 1);
+    Buffer<int> cBuffer(m_d, triangles.size() ? triangles.size() : 1);   // (--mis) list entries per triangle
     Buffer<float> samples(m_d, 3 * npix * (size_t)chunk);
     Buffer<float4_t> image(m_d, npix);
     Buffer<int> rgb(m_d, 3 * npix);
@@ -412,7 +415,12 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     q.stripe_rows = 1; q.n_ranks = 1; q.rank = 0;
     q.max_bounces = bounces;
     auto t0 = std::chrono::steady_clock::now();
-    if (bounces)
+    const bool mis = bounces && o.mis;
+    if (mis) {
+        IASSERT(pt_light_counts(m_d->m_handle, lights.empty() ? 0 : lBuffer.m_handle, (int)lights.size(), (int)triangles.size(), cBuffer.m_handle, 0) == PT_OK);
+        IASSERT(pt_render_indirect_mis(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lights.empty() ? 0 : lBuffer.m_handle, cBuffer.m_handle,
+                                       samples.m_handle, image.m_handle, &q, 0, 0) == PT_OK);
+    } else if (bounces)
         IASSERT(pt_render_indirect(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lights.empty() ? 0 : lBuffer.m_handle, samples.m_handle,
                                    image.m_handle, &q, 0, 0) == PT_OK);
     else
@@ -424,12 +432,13 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     DeviceUtils::waitForCompletion(m_d);
     double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (bounces)
-        std::printf("IndirectIllumination: %d x %d x %d frames, %d bounces, K = 1, %d lights in %.3f s\n", dimension, dimension, o.frames, bounces,
-                    (int)lights.size(), secs);
+        std::printf("IndirectIllumination%s: %d x %d x %d frames, %d bounces, K = 1, %d lights in %.3f s\n", mis ? " (MIS)" : "", dimension, dimension,
+                    o.frames, bounces, (int)lights.size(), secs);
     else
         std::printf("DirectIllumination: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", dimension, dimension, o.frames, (int)lights.size(), secs);
     char path[512];
     f.getFilePath(o.outDir.c_str(), bounces ? "indirectIllumination" : "directIllumination", "ppm", path, sizeof path);
+    if (mis && std::strlen(path) + 5 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_mis.ppm");
     FILE* fp = std::fopen(path, "w");
     IASSERT(fp != 0);
     if (fp) {
@@ -454,6 +463,7 @@ int main(int argc, char** argv)
         else if (a == "--dump") o.dump = next();
         else if (a == "--only") o.only = next();
         else if (a == "--no-batch") o.batch = false;
+        else if (a == "--mis") o.mis = true;
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (o.dim < 1 || o.frames < 0) { std::fprintf(stderr, "bad --dim/--frames\n"); return 2; }

@@ -134,12 +134,15 @@ class DirectRenderer:
         frames, frame_begin = int(frames), int(frame_begin)
         if frames < 0 or frame_begin < 0 or frame_begin + frames > 0x7fffffff:
             raise ValueError("invalid frame range [%d, %d)" % (frame_begin, frame_begin + frames))
-        p = self.params(frames, frame_begin)
-        shim.check(getattr(self._lib, self._ENTRY)(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
-                                                   self.samples._h, self.fb._h, ctypes.byref(p),
-                                                   ctypes.byref(self._cam) if self._cam is not None else None,
-                                                   sync._h if sync is not None else None))
+        shim.check(self._call(self.params(frames, frame_begin), sync))
         self.frames_done = frame_begin + frames
+
+    def _call(self, p, sync) -> int:
+        """the entry point's return code (a renderer with another argument list overrides this)"""
+        return getattr(self._lib, self._ENTRY)(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
+                                               self.samples._h, self.fb._h, ctypes.byref(p),
+                                               ctypes.byref(self._cam) if self._cam is not None else None,
+                                               sync._h if sync is not None else None)
 
     def read(self) -> np.ndarray:
         """Local framebuffer as (local_rows * width, 4) float32, the renderer's layout (synchronises)."""

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Informational: samples/s of indirect illumination on the device (pt_render_indirect) on the Cornell box, 1024^2, 16 frames,
-B = 16 bounces -- K = 0 (no light list: the renderer's estimator through the lock-step brute-force kernel) and K = 1 (one light
-sample per vertex) -- beside pt_render_frames at the same size and depth in the same process.  Each leg is warmed up once at its
+B = 16 bounces -- K = 0 (no light list: the renderer's estimator through the lock-step brute-force kernel), K = 1 and K = 4 light
+samples per vertex, each of the latter two also with multiple importance sampling (pt_render_indirect_mis, the "mis" rows), and
+K = 1 of both estimators through the LBVH kernels (PT_OPT_ACCEL 2), which the 36-triangle scene does not take by itself -- beside
+pt_render_frames at the same size and depth in the same process.  Each leg is warmed up once at its
 own shape (scene preparation, code objects), then run ONCE: a host clock around the enqueue and the device synchronise that ends
 it.  The sample workspace holds all 16 frames, so an indirect render is one launch and one fold.
 The K = 0 figure against the renderer's is what the brute-force kernel's missing lane regeneration costs.
@@ -14,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
-from oclpathtracer_amd import adl, scene  # noqa: E402
+from oclpathtracer_amd import adl, scene, shim  # noqa: E402
 from oclpathtracer_amd.indirect import IndirectRenderer  # noqa: E402
 from oclpathtracer_amd.render import Renderer  # noqa: E402
 
@@ -55,12 +57,22 @@ try:
         base = report("pt_render_frames", once(dev, lambda: r.render(FRAMES, frame_begin=0, max_bounces=B)))
     finally:
         r.release()
-    for name, K, lights in (("pt_render_indirect K = 0 (no lights)", 1, np.zeros(0, np.int32)), ("pt_render_indirect K = 1", 1, None)):
-        ir = IndirectRenderer(dev, tris, mats, W, H, light_samples=K, lights=lights, max_bounces=B, stripe_rows=1, chunk_frames=FRAMES)
+    plain = {}
+    for name, K, lights, mis, accel in (("pt_render_indirect K = 0 (no lights)", 1, np.zeros(0, np.int32), False, 0),
+                                        ("pt_render_indirect K = 1", 1, None, False, 0), ("pt_render_indirect_mis K = 1", 1, None, True, 0),
+                                        ("pt_render_indirect K = 4", 4, None, False, 0), ("pt_render_indirect_mis K = 4", 4, None, True, 0),
+                                        ("pt_render_indirect K = 1, LBVH", 1, None, False, 2), ("pt_render_indirect_mis K = 1, LBVH", 1, None, True, 2)):
+        dev.setOption(shim.PT_OPT_ACCEL, accel)
+        ir = IndirectRenderer(dev, tris, mats, W, H, light_samples=K, lights=lights, max_bounces=B, stripe_rows=1, chunk_frames=FRAMES, mis=mis)
         try:
             rate = report(name, once(dev, lambda: ir.render(FRAMES, 0)))
             emit("%-44s %9.3f of pt_render_frames' rate" % ("", rate / base))
+            if mis:
+                emit("%-44s %9.3f of the plain estimator's rate at the same K and search" % ("", rate / plain[K, accel]))
+            elif lights is None:
+                plain[K, accel] = rate
         finally:
             ir.release()
+            dev.setOption(shim.PT_OPT_ACCEL, 0)
 finally:
     adl.DeviceUtils.deallocate(dev)
