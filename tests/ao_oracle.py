@@ -5,7 +5,12 @@ from __future__ import annotations
 
 import numpy as np
 
-from oracles import cam10, lib, ptr
+from oracles import F, I, I64, V, cam10, declare, lib, ptr
+
+declare({
+    "oao_render": (I, [V, I, V] + [I] * 8 + [F, V]),
+    "oao_decisions": (None, [V, I, I, I, V, V, I64, I, F, V, V]),
+})
 
 
 def counts(tris, W, H, frame_begin, frame_count, K, radius, cam=None, stripe_rows=1, n_ranks=1, rank=0, start=None):

@@ -1,16 +1,17 @@
-"""ctypes binding of tests/camera_oracle.c: the CPU oracle seen from any camera.  TEST INFRASTRUCTURE.
-
-``python -B tests/camera_oracle.py build`` (what ``__graft_entry__.build()`` runs) builds the library of all three oracle
-restatements, tests/oracles.py's.
+"""ctypes binding of tests/camera_oracle.c: the CPU oracle seen from any camera.  TEST INFRASTRUCTURE (the library: tests/oracles.py).
 """
 from __future__ import annotations
 
 import os
-import sys
 
 import numpy as np
 
-from oracles import build, cam10, lib, ptr
+from oracles import I, I64, V, cam10, declare, lib, ptr
+
+declare({
+    "ocam_derive": (I, [V, V]),
+    "ocam_render": (I, [V, I, V, I, V, I, I, I, I, I, I64, I64, I, V, V]),
+})
 
 
 def derive(eye, center, up, fov_y_deg):
@@ -44,8 +45,3 @@ def render(tris, mats, W, H, frames, cam, *, frame_begin=0, max_bounces=16, fb=N
     if want_stats:
         return fb, dict(zip(ptoracle.STATS_FIELDS, (int(v) for v in st)))
     return fb
-
-
-if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "build":
-        build()

@@ -1,7 +1,7 @@
 /*
  * direct_oracle.c -- the CPU oracle's direct illumination in the layout of pt_render_direct.  TEST INFRASTRUCTURE.
  *
- * Follows tests/oracles.c (tests/direct_oracles.c includes it whole: oracle/pt_oracle.c and the camera restatement come as its
+ * Follows tests/ao_oracle.c in tests/oracles.c (oracle/pt_oracle.c and the camera restatement come as that unit's
  * statics) and composes the estimator of pt_render_direct (include/pt_shim.h) from the oracle's own operations, in the order the
  * contract states them:
  *   - the sample of pixel gid in frame z: seed = gid + hash(z), ocam_generate_ray (GenerateColors.cl:263-288, :308), its closest
@@ -14,7 +14,7 @@
  * The fold: ptor_sample_pixel traces its own radiance and cannot be handed one, so odi_fold below is its accumulation with the
  * radiance as an argument, statement for statement, as ocam_sample_pixel's is; test_direct_cpu.py pins it to ocam_render with
  * num_lights = 0, where the two must agree bit for bit.
- * Compiled with oracle/Makefile's flags (tests/direct_oracle.py).
+ * Compiled with oracle/Makefile's flags (tests/oracles.py).
  */
 enum { ODI_NONE = 0, ODI_OCCLUDED = 1, ODI_OPEN = 2 };
 

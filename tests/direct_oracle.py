@@ -1,25 +1,11 @@
-"""Builds, loads and binds tests/libtest_direct_oracle.so: the CPU oracle's direct illumination (tests/direct_oracle.c through the
-translation unit tests/direct_oracles.c, which includes tests/oracles.c whole) -- the framebuffer of pt_render_direct, and the
-per-light-sample decisions behind it with their reasons.  TEST INFRASTRUCTURE.
-
-``__graft_entry__.build()`` builds it (``python -B tests/direct_oracle.py build``); ``lib()`` builds it again when it is missing or
-older than one of its sources, as ``oracles.lib()`` does.
+"""ctypes binding of tests/direct_oracle.c: the CPU oracle's direct illumination -- the framebuffer of pt_render_direct, and the
+per-light-sample decisions behind it with their reasons.  TEST INFRASTRUCTURE (the library: tests/oracles.py).
 """
 from __future__ import annotations
 
-import ctypes
-import os
-import subprocess
-import sys
-
 import numpy as np
 
-import oracles
-from oracles import cam10, ptr
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libtest_direct_oracle.so")
-_SRCS = [os.path.join(_HERE, f) for f in ("direct_oracles.c", "direct_oracle.c")] + list(oracles._SRCS)
+from oracles import I, I64, V, cam10, declare, lib, ptr
 
 NONE, OCCLUDED, OPEN = 0, 1, 2   # the decisions of a light sample (direct_oracle.c: ODI_*)
 # why (direct_oracle.c: ODI_R_*): NONE is NOT_DRAWN (the primary ray missed, or no lights), NOT_FACING (cs <= 0), EDGE_ON (cl <= 0),
@@ -28,34 +14,11 @@ NOT_DRAWN, NOT_FACING, EDGE_ON, NAN, OTHER_TYPE, OPEN_UNSEARCHED, R_OPEN, R_OCCL
 REASONS = ("NOT_DRAWN", "NOT_FACING", "EDGE_ON", "NAN", "OTHER_TYPE", "OPEN_UNSEARCHED", "OPEN", "OCCLUDED")
 DECISION_OF = np.array([NONE, NONE, NONE, NONE, NONE, OPEN, OPEN, OCCLUDED], np.uint8)   # reason code -> decision
 
-_V, _I, _I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-_SIGNATURES = {
-    "odi_render": (_I, [_V, _I, _V, _V, _I, _V] + [_I] * 8 + [_V]),
-    "odi_decisions": (_I, [_V, _I, _V, _V, _I, _V, _I, _I, _V, _V, _I64, _I, _V, _V, _V]),
-    "odi_details": (_I, [_V, _I, _V, _V, _I, _V, _I, _I, _V, _V, _I64, _I, _V, _V, _V, _V, _V]),
-}
-
-
-def build() -> str:
-    cc = os.environ.get("CC", "gcc")
-    subprocess.check_call([cc] + oracles.CFLAGS + ["-shared", "-o", LIB_PATH, _SRCS[0], "-lm", "-lpthread"])
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in _SRCS):
-            build()
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = L
-    return _lib
+declare({
+    "odi_render": (I, [V, I, V, V, I, V] + [I] * 8 + [V]),
+    "odi_decisions": (I, [V, I, V, V, I, V, I, I, V, V, I64, I, V, V, V]),
+    "odi_details": (I, [V, I, V, V, I, V, I, I, V, V, I64, I, V, V, V, V, V]),
+})
 
 
 def _lights(tris, mats, lights):
@@ -124,11 +87,26 @@ def local_gids(W, H, stripe_rows=1, n_ranks=1, rank=0):
     return (np.asarray(rows, np.int64)[:, None] * W + np.arange(W)[None, :]).reshape(-1)
 
 
+def sample_ids(W, H, frames, **stripes):
+    """(gid, frame) of every local sample of ``frames`` frames, frame-major -- the order of the device's sample workspace"""
+    gid = local_gids(W, H, **stripes)
+    return np.tile(gid, frames), np.repeat(np.arange(frames), len(gid))
+
+
+_ONCE = {}
+
+
+def once(make, *case, **stripes):
+    """``make(*case, **stripes)`` -- the restatement's (framebuffer, radiance) of a case, or any tuple of arrays -- computed once per
+    (make, case, stripes), shared by every test that asks, read-only"""
+    k = (make, case, tuple(sorted(stripes.items())))
+    if k not in _ONCE:
+        _ONCE[k] = tuple(make(*case, **stripes))
+        for a in _ONCE[k]:
+            a.setflags(write=False)
+    return _ONCE[k]
+
+
 def count_reasons(reason):
     """{name: how many light samples ended for that reason}"""
     return {name: int((reason == k).sum()) for k, name in enumerate(REASONS)}
-
-
-if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "build":
-        build()

@@ -1,10 +1,16 @@
-"""What the GPU test modules share: device options for a block, one render through the fused entry point, one direct or indirect
-render with its sample workspace, the comparison of hit records and the ray generators of the query tests.  TEST INFRASTRUCTURE (an ordinary module: every assert carries its message)."""
+"""What the GPU test modules share: device options for a block, one render through the fused entry point, one direct, indirect or MIS
+render with its sample workspace, the raw C-ABI harness of those three entry points with the argument errors they share, a search cut
+short and reported, a run of the C++ harness, the comparison of hit records and the ray generators of the query tests.
+TEST INFRASTRUCTURE (an ordinary module: every assert carries its message)."""
+import ctypes
+import os
+import subprocess
 from contextlib import contextmanager
 
 import numpy as np
+import pytest
 
-from conftest import assert_fb_equal
+from conftest import ROOT, assert_fb_equal
 from oclpathtracer_amd import shim
 
 SEARCHES = [(q, a) for a in (1, 2) for q in (0, 1, 4)]   # (PT_OPT_QUAD_FILTER, PT_OPT_ACCEL)
@@ -40,10 +46,10 @@ def render(device, tris, mats, W, H, frames, *, depth=16, frame_begin=0, fb_init
         r.release()
 
 
-def lit_with_samples(device, scene4, W, H, frames, K, chunk_frames=None, max_bounces=None, **kw):
-    """One DirectRenderer -- with max_bounces an IndirectRenderer -- on (tris, mats, lights, camera), whose workspace holds every
-    frame of the call (chunk_frames >= frames unless given), one render from frame 0: the framebuffer [local pixels, 4] and the
-    whole sample workspace [chunk_frames, local pixels, 3]."""
+def lit_with_samples(device, scene4, W, H, frames, K, chunk_frames=None, max_bounces=None, mis=False, frame_begin=0, **kw):
+    """One DirectRenderer -- with max_bounces an IndirectRenderer, with mis its MIS estimator -- on (tris, mats, lights, camera), whose
+    workspace holds every frame of the call (chunk_frames >= frames unless given), one render from frame_begin: the framebuffer
+    [local pixels, 4] and the whole sample workspace [chunk_frames, local pixels, 3]."""
     from oclpathtracer_amd.direct import DirectRenderer
     from oclpathtracer_amd.indirect import IndirectRenderer
 
@@ -51,9 +57,9 @@ def lit_with_samples(device, scene4, W, H, frames, K, chunk_frames=None, max_bou
     kw.setdefault("stripe_rows", 1)
     kw.update(light_samples=K, lights=lights, camera=cam, chunk_frames=max(frames, 1) if chunk_frames is None else chunk_frames)
     r = DirectRenderer(device, tris, mats, W, H, **kw) if max_bounces is None else \
-        IndirectRenderer(device, tris, mats, W, H, max_bounces=max_bounces, **kw)
+        IndirectRenderer(device, tris, mats, W, H, max_bounces=max_bounces, mis=mis, **kw)
     try:
-        r.render(frames, 0)
+        r.render(frames, frame_begin)
         fb = r.read()
         ws = np.zeros((r.chunk_frames, r.local_pixels, 3), np.float32)
         r.samples.read(ws, ws.size)
@@ -61,6 +67,157 @@ def lit_with_samples(device, scene4, W, H, frames, K, chunk_frames=None, max_bou
         return fb, ws
     finally:
         r.release()
+
+
+class LitBuffers:
+    """The buffers of one raw call of ``entry`` -- "pt_render_direct", "pt_render_indirect" or "pt_render_indirect_mis" -- and its
+    parameter blocks.  The framebuffer starts as a sentinel; for MIS the counts (``cb``) are the list's, made by pt_light_counts."""
+
+    def __init__(self, entry, device, tris, mats, W, H, lights=(10, 11), frames=1, pad=4):
+        from oclpathtracer_amd import adl, scene
+
+        self.entry, self.device, self.lib = entry, device, shim.load()
+        self.W, self.H, self.ntri, self.nmat = W, H, len(tris), len(mats)
+        self.tb = adl.Buffer(device, len(tris), scene.TRIANGLE_DTYPE)
+        self.mb = adl.Buffer(device, len(mats), scene.MATERIAL_DTYPE)
+        self.lb = adl.Buffer(device, max(len(lights), 1), np.int32)
+        self.cb = adl.Buffer(device, len(tris), np.int32) if entry == "pt_render_indirect_mis" else None
+        self.sb = adl.Buffer(device, 3 * W * H * frames, np.float32)
+        self.fb = adl.Buffer(device, W * H + pad, adl.float4)
+        self.tb.write(tris, len(tris))
+        self.mb.write(mats, len(mats))
+        if len(lights):
+            self.lb.write(np.asarray(lights, np.int32), len(lights))
+        self.sentinel = np.full((W * H + pad, 4), np.float32(-7.25), np.float32)
+        self.fb.write(self.sentinel, len(self.sentinel))
+        if self.cb is not None:
+            assert self.lib.pt_light_counts(device._h, self.lb._h, len(lights), len(tris), self.cb._h, None) == shim.PT_OK
+
+    def params(self, nl, **kw):
+        """the block of one frame from 0, ``nl`` lights, 2 light samples, one rank -- and 3 bounces in the indirect block; then
+        ``kw``, where reserved=k sets reserved[k]"""
+        p = shim.DirectParams() if self.entry == "pt_render_direct" else shim.IndirectParams()
+        p.width, p.height, p.frame_begin, p.frame_count = self.W, self.H, 0, 1
+        p.num_triangles, p.num_materials, p.num_lights, p.light_samples = self.ntri, self.nmat, nl, 2
+        p.stripe_rows, p.n_ranks, p.rank = 1, 1, 0
+        if self.entry != "pt_render_direct":
+            p.max_bounces = 3
+        for k, v in kw.items():
+            if k == "reserved":
+                p.reserved[v] = 1
+            else:
+                setattr(p, k, v)
+        return p
+
+    def call(self, p, cam=None, **over):
+        """the entry point on these buffers, each replaced by what ``over`` names for it (None: a NULL handle)"""
+        names = ("tb", "mb", "lb", "sb", "fb") if self.cb is None else ("tb", "mb", "lb", "cb", "sb", "fb")
+        bufs = [over.get(name, getattr(self, name)) for name in names]
+        return getattr(self.lib, self.entry)(self.device._h, *[b._h if b is not None else None for b in bufs],
+                                             ctypes.byref(p) if p is not None else None, cam, None)
+
+    def read(self, buf=None, like=None):
+        out = np.zeros_like(self.sentinel if like is None else like)
+        (self.fb if buf is None else buf).read(out, len(out) if buf is None else out.size)   # (float4 records; scalars otherwise)
+        self.device.waitForCompletion()
+        return out
+
+    def assert_untouched(self):
+        assert np.array_equal(self.read(), self.sentinel), "the framebuffer was touched"
+
+    def release(self):
+        for b in (self.tb, self.mb, self.lb, self.cb, self.sb, self.fb):
+            if b is not None:
+                b.release()
+
+
+def assert_lit_argument_errors(b):
+    """What render_lit rejects for every entry point, on a LitBuffers of two lights: each field of the block out of range, a NULL
+    block or handle, a workspace of another device or a float short, a camera of 180 degrees, a misaligned framebuffer, workspace and
+    framebuffer overlapping -- each with its code, and the framebuffer untouched after all of them."""
+    from oclpathtracer_amd import adl
+
+    device, W, H = b.device, b.W, b.H
+    E_INV, E_RANGE = shim.PT_ERR_INVALID, shim.PT_ERR_RANGE
+    cases = [(dict(width=0), E_INV), (dict(height=-1), E_INV), (dict(frame_begin=-1), E_INV), (dict(frame_count=-1), E_INV),
+             (dict(num_triangles=-1), E_INV), (dict(num_materials=0), E_INV), (dict(num_lights=-1), E_INV),
+             (dict(num_lights=1 << 24), E_INV), (dict(light_samples=0), E_INV), (dict(light_samples=257), E_INV),
+             (dict(stripe_rows=0), E_INV), (dict(n_ranks=0), E_INV), (dict(rank=1), E_INV), (dict(rank=-1), E_INV),
+             (dict(frame_begin=0x7fffffff, frame_count=1), E_INV), (dict(width=65536, height=32768), E_INV),
+             (dict(num_triangles=b.ntri + 1), E_RANGE), (dict(num_materials=b.nmat + 1), E_RANGE), (dict(num_lights=3), E_RANGE),
+             (dict(width=W + 16), E_RANGE)]
+    for kw, code in cases:
+        assert b.call(b.params(2, **kw)) == code, kw
+    p = b.params(2)
+    assert b.call(None) == E_INV
+    for name in ("tb", "mb", "sb", "fb"):
+        assert b.call(p, **{name: None}) == E_INV, name
+    assert b.call(p, lb=None) == E_INV                                    # num_lights > 0 needs the list
+    other = adl.DeviceUtils.allocate(adl.TYPE_HIP, adl.Config(0))
+    ob = adl.Buffer(other, 3 * W * H, np.float32)
+    small = adl.Buffer(device, 3 * W * H - 1, np.float32)
+    big = adl.Buffer(device, 64 * W * H, np.uint8)
+    try:
+        assert b.call(p, sb=ob) == E_INV                                  # a buffer of another device
+        assert b.call(p, sb=small) == E_RANGE                             # less than one frame of workspace
+        bad = shim.Camera()
+        b.lib.pt_camera_reference(ctypes.byref(bad))
+        bad.fov_y_deg = 180.0
+        assert b.call(p, cam=ctypes.byref(bad)) == E_INV
+
+        def wrap(off, nbytes):                                            # sub-ranges of one allocation
+            w = adl.Buffer()
+            w.setRawPtr(device, big.m_ptr + off, nbytes)
+            return w
+        f8, s0, f0 = wrap(12 * W * H + 8, 16 * W * H), wrap(0, 12 * W * H), wrap(12 * W * H - 16, 16 * W * H)
+        try:
+            assert b.call(p, sb=s0, fb=f8) == E_INV                       # framebuffer not 16-byte aligned
+            assert b.call(p, sb=s0, fb=f0) == E_INV                       # overlap
+        finally:
+            for w in (f8, s0, f0):
+                w.release()
+    finally:
+        big.release()
+        small.release()
+        ob.release()
+        adl.DeviceUtils.deallocate(other)
+    b.assert_untouched()
+
+
+def assert_cut_short_search_is_reported(device, make):
+    """``make()``: a renderer over a scene of 512 triangles or more.  With the LBVH's stack limited to one entry its search is cut
+    short; the observing call reports it, the report clears the word, and the next render is the first one's again."""
+    with options(device, ACCEL=2):
+        d = make()
+        try:
+            d.render(1)
+            want = d.read()
+            with options(device, BVH_STACK_LIMIT=1):
+                with pytest.raises(shim.ShimError) as e:   # the search is cut short; the observing call reports it
+                    d.render(1, 0)
+                    d.read()
+                assert e.value.code == shim.PT_ERR_TRAVERSAL
+            device.waitForCompletion()                     # the word was cleared by the report
+            d.render(1, 0)
+            assert_fb_equal(d.read(), want, "after the report")
+        finally:
+            d.release()
+
+
+def harness_ppm(tmp_path, dim, frames, *only):
+    """raytrace_test --only ``only`` (a fixture test's name, then its flags) at dim x dim on the Cornell box: one test ran and passed
+    and wrote one PPM of that size.  Returns (stdout, the PPM's file name, its pixels int64 [dim * dim, 3])."""
+    exe = os.path.join(ROOT, "oclpathtracer_amd", "raytrace_test")
+    scene_path = os.path.join(ROOT, "oclpathtracer_amd", "data", "cornellbox.bin")
+    r = subprocess.run([exe, "--only", *only, "--dim", str(dim), "--frames", str(frames), "--scene", scene_path,
+                        "--out-dir", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.count("[       OK ]") == 1 and "FAILED" not in r.stdout, r.stdout
+    ppm = [f for f in os.listdir(tmp_path) if f.endswith(".ppm")]
+    assert len(ppm) == 1, ppm
+    toks = open(os.path.join(tmp_path, ppm[0])).read().split()
+    assert toks[:4] == ["P3", str(dim), str(dim), "255"], toks[:4]
+    return r.stdout, ppm[0], np.array(toks[4:], np.int64).reshape(-1, 3)
 
 
 def words(hits) -> np.ndarray:

@@ -60,31 +60,20 @@ def scene_of(name):
     return clamped_scene() if name == "cornell:clamped" else edge_scene(name)
 
 
-def sample_ids(W, H, frames, **stripes):
-    """(gid, frame) of every local sample of ``frames`` frames, frame-major -- the order of the device's sample workspace"""
-    gid = do.local_gids(W, H, **stripes)
-    return np.tile(gid, frames), np.repeat(np.arange(frames), len(gid))
-
-
-_WANT = {}
+def _want(name, W, H, frames, K, B, **stripes):
+    tris, mats, lights, cam = scene_of(name)[1]
+    gid, frame = do.sample_ids(W, H, frames, **stripes)
+    return (io.render(tris, mats, W, H, 0, frames, K, B, lights=lights, cam=cam, **stripes),
+            io.samples(tris, mats, W, H, gid, frame, K, B, lights=lights, cam=cam)[0].reshape(frames, -1, 3))
 
 
 def wanted(name, W, H, frames, K, B, **stripes):
     """the restatement's (framebuffer, radiance [frames, local pixels, 3]) of a case: computed once, shared, read-only"""
-    k = (name, W, H, frames, K, B, tuple(sorted(stripes.items())))
-    if k not in _WANT:
-        tris, mats, lights, cam = scene_of(name)[1]
-        gid, frame = sample_ids(W, H, frames, **stripes)
-        fb = io.render(tris, mats, W, H, 0, frames, K, B, lights=lights, cam=cam, **stripes)
-        L = io.samples(tris, mats, W, H, gid, frame, K, B, lights=lights, cam=cam)[0].reshape(frames, -1, 3)
-        for a in (fb, L):
-            a.setflags(write=False)
-        _WANT[k] = (fb, L)
-    return _WANT[k]
+    return do.once(_want, name, W, H, frames, K, B, **stripes)
 
 
 def details(name, W, H, frames, K, B, **stripes):
     """io.details of every local sample of a case"""
     tris, mats, lights, cam = scene_of(name)[1]
-    gid, frame = sample_ids(W, H, frames, **stripes)
+    gid, frame = do.sample_ids(W, H, frames, **stripes)
     return io.details(tris, mats, W, H, gid, frame, K, B, lights=lights, cam=cam)

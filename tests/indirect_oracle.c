@@ -2,8 +2,8 @@
  * indirect_oracle.c -- the CPU oracle's path tracing with light sampling at every vertex, in the layout of pt_render_indirect.
  * TEST INFRASTRUCTURE.
  *
- * Follows tests/direct_oracle.c (tests/indirect_oracles.c includes direct_oracles.c whole: oracle/pt_oracle.c, the camera
- * restatement and direct illumination's come as its statics) and composes the estimator of pt_render_indirect (include/pt_shim.h)
+ * Follows tests/direct_oracle.c in tests/oracles.c (oracle/pt_oracle.c, the camera restatement and direct
+ * illumination's come as that unit's statics) and composes the estimator of pt_render_indirect (include/pt_shim.h)
  * from the oracle's own operations, in the order the contract states them:
  *   - the sample of pixel gid in frame z: seed = gid + hash(z), ocam_generate_ray (GenerateColors.cl:263-288, :308), L = 0,
  *     mask = 1;
@@ -18,7 +18,7 @@
  * the same depth, and at B = 1 it is odi_render's, both bit for bit.
  * oii_details reports, from that same walk, what happened at each of a path's first vertices (tests/test_indirect_cpu.py proves with
  * it that each input of tests/test_gpu_indirect_edges.py reaches the edge it is rendered for).
- * Compiled with oracle/Makefile's flags (tests/indirect_oracle.py).
+ * Compiled with oracle/Makefile's flags (tests/oracles.py).
  */
 enum { OII_END_MISS = 0, OII_END_PDF = 1, OII_END_DEPTH = 2 };
 

@@ -1,58 +1,21 @@
-"""Builds, loads and binds tests/libtest_indirect_oracle.so: the CPU oracle's path tracing with light sampling at every vertex
-(tests/indirect_oracle.c through the translation unit tests/indirect_oracles.c, which includes tests/direct_oracles.c whole) -- the
-framebuffer of pt_render_indirect, and per sample the radiance before the fold, the vertices the path reached and why it ended
-(``samples``), or what happened at each of its first vertices (``details``).  TEST INFRASTRUCTURE.
-
-``__graft_entry__.build()`` builds it (``python -B tests/indirect_oracle.py build``); ``lib()`` builds it again when it is missing
-or older than one of its sources, as ``direct_oracle.lib()`` does.
+"""ctypes binding of tests/indirect_oracle.c: the CPU oracle's path tracing with light sampling at every vertex -- the framebuffer of
+pt_render_indirect, and per sample the radiance before the fold, the vertices the path reached and why it ended (``samples``), or
+what happened at each of its first vertices (``details``).  TEST INFRASTRUCTURE (the library: tests/oracles.py).
 """
 from __future__ import annotations
-
-import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 
 import direct_oracle
-import oracles
-from oracles import cam10, ptr
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libtest_indirect_oracle.so")
-_SRCS = [os.path.join(_HERE, f) for f in ("indirect_oracles.c", "indirect_oracle.c")] + list(direct_oracle._SRCS)
+from oracles import I, I64, V, cam10, declare, lib, ptr
 
 END_MISS, END_PDF, END_DEPTH = 0, 1, 2   # why a path ended (indirect_oracle.c: OII_END_*)
 
-_V, _I, _I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-_SIGNATURES = {
-    "oii_render": (_I, [_V, _I, _V, _V, _I, _V] + [_I] * 9 + [_V]),
-    "oii_samples": (_I, [_V, _I, _V, _V, _I, _V, _I, _I, _V, _V, _I64, _I, _I, _V, _V, _V, _V]),
-    "oii_details": (_I, [_V, _I, _V, _V, _I, _V, _I, _I, _V, _V, _I64, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V]),
-}
-
-
-def build() -> str:
-    cc = os.environ.get("CC", "gcc")
-    subprocess.check_call([cc] + oracles.CFLAGS + ["-shared", "-o", LIB_PATH, _SRCS[0], "-lm", "-lpthread"])
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in _SRCS):
-            build()
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = L
-    return _lib
+declare({
+    "oii_render": (I, [V, I, V, V, I, V] + [I] * 9 + [V]),
+    "oii_samples": (I, [V, I, V, V, I, V, I, I, V, V, I64, I, I, V, V, V, V]),
+    "oii_details": (I, [V, I, V, V, I, V, I, I, V, V, I64, I, I, V, V, V, V, V, V, V, V]),
+})
 
 
 def render(tris, mats, W, H, frame_begin, frame_count, K, B, *, lights=None, cam=None, stripe_rows=1, n_ranks=1, rank=0, start=None):
@@ -125,8 +88,3 @@ def all_samples(W, H, frames, frame_begin=0):
     gid = np.tile(np.arange(W * H, dtype=np.int32), frames)
     frame = np.repeat(np.arange(frame_begin, frame_begin + frames, dtype=np.int32), W * H)
     return gid, frame
-
-
-if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "build":
-        build()

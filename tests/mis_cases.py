@@ -50,32 +50,21 @@ def lights_of(scene, name):
     return np.asarray(LISTS[name], np.int32)
 
 
-def sample_ids(Ws, Hs, frames, **stripes):
-    """(gid, frame) of every local sample of ``frames`` frames, frame-major -- the order of the device's sample workspace"""
-    gid = do.local_gids(Ws, Hs, **stripes)
-    return np.tile(gid, frames), np.repeat(np.arange(frames), len(gid))
-
-
-_WANT = {}
+def _want(scene, lights, Ws, Hs, frames, K, B, **stripes):
+    tris, mats, _, cam = edge_scene(scene)[1]
+    li = lights_of(scene, lights)
+    gid, frame = do.sample_ids(Ws, Hs, frames, **stripes)
+    return (mo.render(tris, mats, Ws, Hs, 0, frames, K, B, lights=li, cam=cam, **stripes),
+            mo.samples(tris, mats, Ws, Hs, gid, frame, K, B, lights=li, cam=cam)[0].reshape(frames, -1, 3))
 
 
 def wanted(scene, lights, Ws, Hs, frames, K, B, **stripes):
     """the restatement's (framebuffer, radiance [frames, local pixels, 3]) of a case: computed once, shared, read-only"""
-    k = (scene, lights, Ws, Hs, frames, K, B, tuple(sorted(stripes.items())))
-    if k not in _WANT:
-        tris, mats, _, cam = edge_scene(scene)[1]
-        li = lights_of(scene, lights)
-        gid, frame = sample_ids(Ws, Hs, frames, **stripes)
-        fb = mo.render(tris, mats, Ws, Hs, 0, frames, K, B, lights=li, cam=cam, **stripes)
-        L = mo.samples(tris, mats, Ws, Hs, gid, frame, K, B, lights=li, cam=cam)[0].reshape(frames, -1, 3)
-        for a in (fb, L):
-            a.setflags(write=False)
-        _WANT[k] = (fb, L)
-    return _WANT[k]
+    return do.once(_want, scene, lights, Ws, Hs, frames, K, B, **stripes)
 
 
 def details(scene, lights, Ws, Hs, frames, K, B, **stripes):
     """mo.details of every local sample of a case"""
     tris, mats, _, cam = edge_scene(scene)[1]
-    gid, frame = sample_ids(Ws, Hs, frames, **stripes)
+    gid, frame = do.sample_ids(Ws, Hs, frames, **stripes)
     return mo.details(tris, mats, Ws, Hs, gid, frame, K, B, lights=lights_of(scene, lights), cam=cam)

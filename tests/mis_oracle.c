@@ -2,8 +2,8 @@
  * mis_oracle.c -- the CPU oracle's path tracing with light sampling at every vertex AND multiple importance sampling, in the layout
  * of pt_render_indirect_mis.  TEST INFRASTRUCTURE.
  *
- * The walk of oii_sample (tests/indirect_oracle.c; tests/mis_oracles.c includes indirect_oracles.c whole, so the oracle, the camera
- * and both illumination restatements come as its statics) with the changes pt_render_indirect_mis states (include/pt_shim.h), all
+ * The walk of oii_sample (tests/indirect_oracle.c, which it follows in tests/oracles.c, so the oracle, the camera
+ * and both illumination restatements come as that unit's statics) with the changes pt_render_indirect_mis states (include/pt_shim.h), all
  * of them only when nl > 0, and counts[t] = the number of list entries that name triangle t as an input:
  *   - a path carries pb, the pdf of the BRDF sample that made the current ray;
  *   - a light sample (omi_light is oii_light's body with three more values) also forms sl = dot(wi, nj) -- cl = fabs(sl) -- and the
@@ -15,7 +15,7 @@
  *     before, :257), so that both techniques form the same pe for the same direction.
  * Two identities pin it (tests/test_mis_cpu.py): with no lights the image is ptor_render's, at B = 1 it is odi_render's, bit for bit;
  * and a sample with no weighted light sample and no later emissive hit is oii_sample's, bit for bit.
- * Compiled with oracle/Makefile's flags (tests/mis_oracle.py).
+ * Compiled with oracle/Makefile's flags (tests/oracles.py).
  */
 enum { OMI_W_NONE = 0, OMI_W_WEIGHTED = 1, OMI_W_LAST_VERTEX = 2, OMI_W_BACK_SIDE = 3 };
 

@@ -1,63 +1,28 @@
-"""Builds, loads and binds tests/libtest_mis_oracle.so: the CPU oracle's path tracing with light sampling at every vertex and
-multiple importance sampling (tests/mis_oracle.c through the translation unit tests/mis_oracles.c, which includes
-tests/indirect_oracles.c whole) -- the framebuffer of pt_render_indirect_mis, and per sample the radiance before the fold with what
+"""ctypes binding of tests/mis_oracle.c: the CPU oracle's path tracing with light sampling at every vertex and multiple importance
+sampling -- the framebuffer of pt_render_indirect_mis, and per sample the radiance before the fold with what
 ``indirect_oracle.samples`` says and the sample's weighted light samples and later emissive hits (``samples``), or what happened at
 each of its first vertices (``details``).  ``counts`` is an input of every entry point, as it is of the device's: None makes it of
-the list as pt_light_counts does (``light_counts``).  TEST INFRASTRUCTURE.
-
-``__graft_entry__.build()`` builds it (``python -B tests/mis_oracle.py build``); ``lib()`` builds it again when it is missing or
-older than one of its sources, as ``indirect_oracle.lib()`` does.
+the list as pt_light_counts does (``light_counts``).  TEST INFRASTRUCTURE (the library: tests/oracles.py).
 """
 from __future__ import annotations
 
-import ctypes
 import os
-import subprocess
-import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 import direct_oracle
 import indirect_oracle
-import oracles
 from indirect_oracle import DETAIL_VERTICES, all_samples   # noqa: F401  (the same sample order and vertex window)
-from oracles import cam10, ptr
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libtest_mis_oracle.so")
-_SRCS = [os.path.join(_HERE, f) for f in ("mis_oracles.c", "mis_oracle.c")] + list(indirect_oracle._SRCS)
+from oracles import I, I64, V, cam10, declare, lib, ptr
 
 W_NONE, WEIGHTED, LAST_VERTEX, BACK_SIDE = 0, 1, 2, 3   # what became of a light sample's weight (mis_oracle.c: OMI_W_*)
 
-_V, _I, _I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-_SIGNATURES = {
-    "omi_render": (_I, [_V, _I, _V, _V, _I, _V, _V] + [_I] * 9 + [_V]),
-    "omi_samples": (_I, [_V, _I, _V, _V, _I, _V, _V, _I, _I, _V, _V, _I64, _I, _I] + [_V] * 5),
-    "omi_details": (_I, [_V, _I, _V, _V, _I, _V, _V, _I, _I, _V, _V, _I64, _I, _I] + [_V] * 11),
-}
-
-
-def build() -> str:
-    cc = os.environ.get("CC", "gcc")
-    subprocess.check_call([cc] + oracles.CFLAGS + ["-shared", "-o", LIB_PATH, _SRCS[0], "-lm", "-lpthread"])
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in _SRCS):
-            build()
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = L
-    return _lib
+declare({
+    "omi_render": (I, [V, I, V, V, I, V, V] + [I] * 9 + [V]),
+    "omi_samples": (I, [V, I, V, V, I, V, V, I, I, V, V, I64, I, I] + [V] * 5),
+    "omi_details": (I, [V, I, V, V, I, V, V, I, I, V, V, I64, I, I] + [V] * 11),
+})
 
 
 def light_counts(lights, num_triangles) -> np.ndarray:
@@ -147,9 +112,9 @@ THREADS = max(1, min(16, os.cpu_count() or 1))
 def radiance_frames(tris, mats, W, H, frame_begin, frames, K, B, *, lights=None, counts=None, mis=True):
     """float64 [frames, W * H, 3]: the radiance before the fold of every sample of frames [frame_begin, frame_begin + frames), of
     this restatement or (``mis=False``) of ``indirect_oracle``.  A sample depends on nothing but its pixel and frame, so the frames
-    are computed in slices on threads (the libraries hold no state; ctypes releases the interpreter) -- the result is that of one
+    are computed in slices on threads (the library holds no state; ctypes releases the interpreter) -- the result is that of one
     call."""
-    lib(), indirect_oracle.lib()
+    lib()   # loaded before the threads start
 
     def run(span):
         gid, frame = all_samples(W, H, span[1] - span[0], span[0])
@@ -162,8 +127,3 @@ def radiance_frames(tris, mats, W, H, frame_begin, frames, K, B, *, lights=None,
     with ThreadPoolExecutor(THREADS) as ex:
         parts = list(ex.map(run, spans))
     return np.concatenate(parts).astype(np.float64).reshape(frames, W * H, 3)
-
-
-if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "build":
-        build()

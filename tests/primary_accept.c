@@ -1,17 +1,15 @@
 /*
  * primary_accept.c -- which triangles the reference's test accepts for a sample's PRIMARY ray.  TEST INFRASTRUCTURE.
  *
- * Built like camera_oracle.c, which it includes whole (and with it oracle/pt_oracle.c: the RNG, the ray set-up and the v3
+ * Follows camera_oracle.c in tests/oracles.c (and with it oracle/pt_oracle.c: the RNG, the ray set-up and the v3
  * math come as their statics, unchanged).  It adds one thing: intersectWorld's loop (GenerateColors.cl:137-154) over
  * intersectTriangle (:89-135) for the first ray of sample (gid, frame), restated so that it REPORTS, per triangle, how far
  * the test got instead of keeping the closest hit only:
  *   - accepted: the call returned true (:125 against the running hitDistance of :141-151) -- ptor_stats' `accept`;
  *   - reach_u:  the call got past the cull (:100) and the u test (:109) -- ptor_stats' `rej_v + reach_t`.
  * Triangle j is bit j of a 64-bit set (scenes of up to 64 triangles).  Compiled with oracle/Makefile's flags
- * (tests/primary_accept.py): strict IEEE, no contraction.
+ * (tests/oracles.py): strict IEEE, no contraction.
  */
-#include "camera_oracle.c"
-
 static void opa_sample(const ocam* cam, const ptor_triangle* tris, int ntri, int gid, int W, int H, int frame,
                        uint64_t* accepted, uint64_t* reach_u)
 {

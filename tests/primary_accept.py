@@ -1,53 +1,15 @@
-"""Builds, loads and binds tests/libtest_primary_accept.so (tests/primary_accept.c, which includes tests/camera_oracle.c whole): per
-pixel the triangles the reference's test ACCEPTS for a sample's primary ray, and those that only pass the cull and the u test.
-TEST INFRASTRUCTURE.
-
-``__graft_entry__.build()`` builds it (``python -B tests/primary_accept.py build``); ``lib()`` builds it again when it is missing or
-older than one of its sources, as ``oracles.lib()`` does.
+"""ctypes binding of tests/primary_accept.c: per pixel the triangles the reference's test ACCEPTS for a sample's primary ray, and those
+that only pass the cull and the u test.  TEST INFRASTRUCTURE (the library: tests/oracles.py).
 """
 from __future__ import annotations
 
-import ctypes
-import os
-import subprocess
-import sys
-
 import numpy as np
 
-import oracles
-from oracles import cam10, ptr
+from oracles import I, I64, V, cam10, declare, lib, ptr
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libtest_primary_accept.so")
-_SRCS = [os.path.join(_HERE, f) for f in ("primary_accept.c", "camera_oracle.c")] + \
-        [os.path.join(os.path.dirname(_HERE), "oracle", f) for f in ("pt_oracle.c", "ptor_constants.h")]
-
-_V, _I, _I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-_SIGNATURES = {
-    "opa_union": (_I, [_V, _I, _V, _I, _I, _I, _I, _V, _I64, _V, _V, _V]),
-}
-
-
-def build() -> str:
-    cc = os.environ.get("CC", "gcc")
-    subprocess.check_call([cc] + oracles.CFLAGS + ["-shared", "-o", LIB_PATH, _SRCS[0], "-lm", "-lpthread"])
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in _SRCS):
-            build()
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = L
-    return _lib
+declare({
+    "opa_union": (I, [V, I, V, I, I, I, I, V, I64, V, V, V]),
+})
 
 
 def union(tris, W, H, frames, *, cam=None, gid=None, frame_begin=0):
@@ -84,8 +46,3 @@ def mask_bits(snapshot, ntri) -> np.ndarray:
         bit = (snap[:, c] >> np.uint32(n - 1 - (j & 31))) & np.uint32(1)
         out |= bit.astype(np.uint64) << np.uint64(j)
     return out
-
-
-if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "build":
-        build()

@@ -5,7 +5,14 @@ from __future__ import annotations
 
 import numpy as np
 
-from oracles import cam10, lib, ptr
+from oracles import I, I64, V, cam10, declare, lib, ptr
+
+declare({
+    "oq_closest": (None, [V, I, V, I64, V]),
+    "oq_camera_rays": (I, [V, I, I, I, V]),
+    "oq_all_hits": (I64, [V, I, V, I64, I64, V, V, V]),
+    "oq_get_rays": (None, [V, I64, V]),
+})
 
 
 def closest(tris: np.ndarray, rays: np.ndarray) -> np.ndarray:

@@ -3,15 +3,13 @@
 The counts {open, hits} are compared with tests/ao_oracle.c, which composes the estimator from the CPU oracle's own camera ray,
 triangle test (ascending loop) and hemisphere sampling; pt_occluded_rays is compared with pt_intersect_rays(PT_QUERY_OCCLUDED)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import ao_oracle as ao
-from conftest import ROOT, assert_fb_equal
-from gpu_support import SEARCHES, cornell_rays, options, refill_rays
+from conftest import assert_fb_equal
+from gpu_support import SEARCHES, cornell_rays, harness_ppm, options, refill_rays
 from oclpathtracer_amd import shim
 from scenes import soup_with_duplicates
 
@@ -418,19 +416,11 @@ def test_cpp_harness_ambient_occlusion(tmp_path, cornell):
     from oclpathtracer_amd import scene
 
     tris, _ = cornell
-    exe = os.path.join(ROOT, "oclpathtracer_amd", "raytrace_test")
-    scene_path = os.path.join(ROOT, "oclpathtracer_amd", "data", "cornellbox.bin")
-    r = subprocess.run([exe, "--only", "AmbientOcclusion", "--dim", "64", "--frames", "4", "--scene", scene_path,
-                        "--out-dir", str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.count("[       OK ]") == 1 and "FAILED" not in r.stdout
-    ppm = [f for f in os.listdir(tmp_path) if f.endswith(".ppm")]
-    assert len(ppm) == 1 and ppm[0].startswith("ambientOcclusion_")
+    _, name, pixels = harness_ppm(tmp_path, 64, 4, "AmbientOcclusion")
+    assert name.startswith("ambientOcclusion_")
     from oclpathtracer_amd.ao import resolve
     a = resolve(ao.counts(tris, 64, 64, 0, 4, 16, 1.0), 16, 1.0).reshape(-1)
-    toks = open(os.path.join(tmp_path, ppm[0])).read().split()
-    assert toks[:4] == ["P3", "64", "64", "255"]
-    assert np.array_equal(np.array(toks[4:], np.int64).reshape(-1, 3), scene.f2c(np.stack([a, a, a], 1)))
+    assert np.array_equal(pixels, scene.f2c(np.stack([a, a, a], 1)))
 
 
 def _params(W, H, ntri, **kw):

@@ -4,43 +4,39 @@ The framebuffer is compared with tests/direct_oracle.c, which composes the estim
 triangle test (ascending loop), BRDF expressions and gamma fold; with no lights it is compared with the fused renderer at one
 bounce, which needs no restatement."""
 import ctypes
-import os
-import subprocess
+from functools import partial
 
 import numpy as np
 import pytest
 
 import direct_oracle as do
-from conftest import ROOT, assert_fb_equal
-from gpu_support import SEARCHES, options, render
+from conftest import assert_fb_equal
+from gpu_support import (SEARCHES, LitBuffers, assert_cut_short_search_is_reported, assert_lit_argument_errors, harness_ppm,
+                         lit_with_samples, options, render)
 from oclpathtracer_amd import shim
-from scenes import nested_boxes
+from scenes import edge_scene, nested_boxes
 
 pytestmark = pytest.mark.gpu
 
 NONE = np.zeros(0, np.int32)
 
 
-def _direct(device, tris, mats, W, H, frames, K, frame_begin=0, **kw):
-    from oclpathtracer_amd.direct import DirectRenderer
+def _direct(device, tris, mats, W, H, frames, K, lights=None, camera=None, **kw):
+    return lit_with_samples(device, (tris, mats, lights, camera), W, H, frames, K, **kw)[0]
 
-    kw.setdefault("stripe_rows", 1)
-    r = DirectRenderer(device, tris, mats, W, H, light_samples=K, **kw)
-    try:
-        r.render(frames, frame_begin)
-        return r.read()
-    finally:
-        r.release()
+
+_Buffers = partial(LitBuffers, "pt_render_direct")
+
+
+def _image(W, H, K):
+    tris, mats, _, _ = edge_scene("cornell")[1]
+    return (do.render(tris, mats, W, H, 0, 4, K),)
 
 
 @pytest.fixture(scope="module")
-def cornell_want(cornell):
+def cornell_want():
     """the restatement's images of the Cornell box, 4 frames: computed once, shared, never written to"""
-    tris, mats = cornell
-    want = {(W, H, K): do.render(tris, mats, W, H, 0, 4, K) for W, H in ((64, 64), (40, 24)) for K in (1, 4)}
-    for a in want.values():
-        a.setflags(write=False)
-    return want
+    return {(W, H, K): do.once(_image, W, H, K)[0] for W, H in ((64, 64), (40, 24)) for K in (1, 4)}
 
 
 @pytest.mark.parametrize("quad,accel", SEARCHES)
@@ -102,7 +98,7 @@ def test_progressive_frame_zero_cameras_and_a_rejected_camera(device, cornell):
         bad = shim.Camera()
         lib.pt_camera_reference(ctypes.byref(bad))
         bad.center[:] = bad.eye[:]
-        assert b.call(_params(W, H, len(tris), len(mats), 2), cam=ctypes.byref(bad)) == shim.PT_ERR_INVALID
+        assert b.call(b.params(2), cam=ctypes.byref(bad)) == shim.PT_ERR_INVALID
         b.assert_untouched()
     finally:
         b.release()
@@ -166,58 +162,6 @@ def test_lbvh_refill_over_more_samples_than_the_grid(device, lbvh_scene):
 
 
 # ---- the raw C ABI ------------------------------------------------------------------------------------------------------------
-def _params(W, H, ntri, nmat, nl, **kw):
-    p = shim.DirectParams()
-    p.width, p.height, p.frame_begin, p.frame_count = W, H, 0, 1
-    p.num_triangles, p.num_materials, p.num_lights, p.light_samples = ntri, nmat, nl, 2
-    p.stripe_rows, p.n_ranks, p.rank = 1, 1, 0
-    for k, v in kw.items():
-        if k == "reserved":
-            p.reserved[v] = 1
-        else:
-            setattr(p, k, v)
-    return p
-
-
-class _Buffers:
-    """the buffers of one raw pt_render_direct call; the framebuffer starts as a sentinel"""
-
-    def __init__(self, device, tris, mats, W, H, lights=(10, 11), frames=1, pad=4):
-        from oclpathtracer_amd import adl, scene
-
-        self.device, self.lib, self.n = device, shim.load(), W * H
-        self.tb = adl.Buffer(device, len(tris), scene.TRIANGLE_DTYPE)
-        self.mb = adl.Buffer(device, len(mats), scene.MATERIAL_DTYPE)
-        self.lb = adl.Buffer(device, max(len(lights), 1), np.int32)
-        self.sb = adl.Buffer(device, 3 * W * H * frames, np.float32)
-        self.fb = adl.Buffer(device, W * H + pad, adl.float4)
-        self.tb.write(tris, len(tris))
-        self.mb.write(mats, len(mats))
-        if len(lights):
-            self.lb.write(np.asarray(lights, np.int32), len(lights))
-        self.sentinel = np.full((W * H + pad, 4), np.float32(-7.25), np.float32)
-        self.fb.write(self.sentinel, len(self.sentinel))
-
-    def call(self, p, cam=None, **over):
-        h = lambda name: over[name] if name in over else getattr(self, name)
-        ptr = lambda b: b._h if b is not None else None
-        return self.lib.pt_render_direct(self.device._h, ptr(h("tb")), ptr(h("mb")), ptr(h("lb")), ptr(h("sb")), ptr(h("fb")),
-                                         ctypes.byref(p) if p is not None else None, cam, None)
-
-    def read(self):
-        out = np.zeros_like(self.sentinel)
-        self.fb.read(out, len(out))
-        self.device.waitForCompletion()
-        return out
-
-    def assert_untouched(self):
-        assert np.array_equal(self.read(), self.sentinel), "the framebuffer was touched"
-
-    def release(self):
-        for b in (self.tb, self.mb, self.lb, self.sb, self.fb):
-            b.release()
-
-
 def test_light_indices_out_of_range_are_clamped(device, cornell):
     """Python refuses such a list; through the C ABI it is defined behaviour: each index is clamped into [0, num_triangles)."""
     tris, mats = cornell
@@ -228,7 +172,7 @@ def test_light_indices_out_of_range_are_clamped(device, cornell):
     for lights in (raw, clamped):
         b = _Buffers(device, tris, mats, W, H, lights=lights, pad=0)
         try:
-            assert b.call(_params(W, H, ntri, len(mats), 4)) == shim.PT_OK
+            assert b.call(b.params(4)) == shim.PT_OK
             out.append(b.read())
         finally:
             b.release()
@@ -272,83 +216,21 @@ def test_cut_short_search_is_reported_and_recovers(device, lbvh_scene):
     from oclpathtracer_amd.direct import DirectRenderer
 
     tris, mats = lbvh_scene
-    with options(device, ACCEL=2):
-        d = DirectRenderer(device, tris, mats, 48, 48, light_samples=2, stripe_rows=1)
-        try:
-            d.render(1)
-            want = d.read()
-            with options(device, BVH_STACK_LIMIT=1):
-                with pytest.raises(shim.ShimError) as e:   # the search is cut short; the observing call reports it
-                    d.render(1, 0)
-                    d.read()
-                assert e.value.code == shim.PT_ERR_TRAVERSAL
-            device.waitForCompletion()                     # the word was cleared by the report
-            d.render(1, 0)
-            assert_fb_equal(d.read(), want, "after the report")
-        finally:
-            d.release()
+    assert_cut_short_search_is_reported(device, lambda: DirectRenderer(device, tris, mats, 48, 48, light_samples=2, stripe_rows=1))
 
 
 def test_c_abi_argument_errors_leave_the_framebuffer_untouched(device, cornell):
-    from oclpathtracer_amd import adl
-
     tris, mats = cornell
-    W, H = 16, 8
-    ntri, nmat = len(tris), len(mats)
-    E_INV, E_RANGE = shim.PT_ERR_INVALID, shim.PT_ERR_RANGE
-    b = _Buffers(device, tris, mats, W, H)
-    other = adl.DeviceUtils.allocate(adl.TYPE_HIP, adl.Config(0))
-    ob = adl.Buffer(other, 3 * W * H, np.float32)
+    b = _Buffers(device, tris, mats, 16, 8)
     try:
-        cases = [(dict(width=0), E_INV), (dict(height=-1), E_INV), (dict(frame_begin=-1), E_INV), (dict(frame_count=-1), E_INV),
-                 (dict(num_triangles=-1), E_INV), (dict(num_materials=0), E_INV), (dict(num_lights=-1), E_INV),
-                 (dict(num_lights=1 << 24), E_INV), (dict(light_samples=0), E_INV), (dict(light_samples=257), E_INV),
-                 (dict(stripe_rows=0), E_INV), (dict(n_ranks=0), E_INV), (dict(rank=1), E_INV), (dict(rank=-1), E_INV),
-                 (dict(reserved=0), E_INV), (dict(reserved=4), E_INV), (dict(frame_begin=0x7fffffff, frame_count=1), E_INV),
-                 (dict(width=65536, height=32768), E_INV),
-                 (dict(num_triangles=ntri + 1), E_RANGE), (dict(num_materials=nmat + 1), E_RANGE), (dict(num_lights=3), E_RANGE),
-                 (dict(width=W + 16), E_RANGE)]
-        for kw, code in cases:
-            assert b.call(_params(W, H, ntri, nmat, 2, **kw)) == code, kw
-        p = _params(W, H, ntri, nmat, 2)
-        assert b.call(None) == E_INV
-        for name in ("tb", "mb", "sb", "fb"):
-            assert b.call(p, **{name: None}) == E_INV, name
-        assert b.call(p, lb=None) == E_INV                                    # num_lights > 0 needs the list
-        assert b.call(p, sb=ob) == E_INV                                      # a buffer of another device
-        small = adl.Buffer(device, 3 * W * H - 1, np.float32)
-        try:
-            assert b.call(p, sb=small) == E_RANGE                             # less than one frame of workspace
-        finally:
-            small.release()
-        bad = shim.Camera()
-        b.lib.pt_camera_reference(ctypes.byref(bad))
-        bad.fov_y_deg = 180.0
-        assert b.call(p, cam=ctypes.byref(bad)) == E_INV
-        # a misaligned framebuffer, workspace and framebuffer overlapping: sub-ranges of one allocation
-        big = adl.Buffer(device, 64 * W * H, np.uint8)
-        try:
-            def wrap(off, nbytes):
-                w = adl.Buffer()
-                w.setRawPtr(device, big.m_ptr + off, nbytes)
-                return w
-            f8, s0, f0 = wrap(12 * W * H + 8, 16 * W * H), wrap(0, 12 * W * H), wrap(12 * W * H - 16, 16 * W * H)
-            try:
-                assert b.call(p, sb=s0, fb=f8) == E_INV                       # framebuffer not 16-byte aligned
-                assert b.call(p, sb=s0, fb=f0) == E_INV                       # overlap
-            finally:
-                for w in (f8, s0, f0):
-                    w.release()
-        finally:
-            big.release()
-        b.assert_untouched()
-        assert b.call(p) == shim.PT_OK
-        assert b.call(_params(W, H, ntri, nmat, 0), lb=None) == shim.PT_OK     # no lights, no list
+        for k in range(5):
+            assert b.call(b.params(2, reserved=k)) == shim.PT_ERR_INVALID, k
+        assert_lit_argument_errors(b)
+        assert b.call(b.params(2)) == shim.PT_OK
+        assert b.call(b.params(0), lb=None) == shim.PT_OK                     # no lights, no list
         device.waitForCompletion()
     finally:
         b.release()
-        ob.release()
-        adl.DeviceUtils.deallocate(other)
 
 
 def test_empty_scene_renders_the_background(device, cornell):
@@ -365,15 +247,7 @@ def test_cpp_harness_direct_illumination(tmp_path, cornell):
     from oclpathtracer_amd import scene
 
     tris, mats = cornell
-    exe = os.path.join(ROOT, "oclpathtracer_amd", "raytrace_test")
-    scene_path = os.path.join(ROOT, "oclpathtracer_amd", "data", "cornellbox.bin")
-    r = subprocess.run([exe, "--only", "DirectIllumination", "--dim", "64", "--frames", "4", "--scene", scene_path,
-                        "--out-dir", str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.count("[       OK ]") == 1 and "FAILED" not in r.stdout and "DirectIllumination:" in r.stdout
-    ppm = [f for f in os.listdir(tmp_path) if f.endswith(".ppm")]
-    assert len(ppm) == 1 and ppm[0].startswith("directIllumination_")
+    out, name, pixels = harness_ppm(tmp_path, 64, 4, "DirectIllumination")
+    assert "DirectIllumination:" in out and name.startswith("directIllumination_")
     want = do.render(tris, mats, 64, 64, 0, 4, 4)
-    toks = open(os.path.join(tmp_path, ppm[0])).read().split()
-    assert toks[:4] == ["P3", "64", "64", "255"]
-    assert np.array_equal(np.array(toks[4:], np.int64).reshape(-1, 3), scene.f2c(want[:, :3]))
+    assert np.array_equal(pixels, scene.f2c(want[:, :3]))

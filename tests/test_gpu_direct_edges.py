@@ -20,27 +20,21 @@ from scenes import GLOSSY_SHIFTS, MIXED_SCALE, edge_scene
 pytestmark = pytest.mark.gpu
 
 
-_WANT = {}
+def _want(name, W, H, frames, K, **stripes):
+    tris, mats, lights, cam = edge_scene(name)[1]
+    gid, frame = do.sample_ids(W, H, frames, **stripes)
+    return (do.render(tris, mats, W, H, 0, frames, K, lights=lights, cam=cam, **stripes),
+            do.details(tris, mats, W, H, gid, frame, K, lights=lights, cam=cam)[4].reshape(frames, -1, 3))
 
 
-def wanted(key, scene4, W, H, frames, K, **stripes):
-    """the restatement's (framebuffer, radiance [frames, local pixels, 3]) of an input: computed once per key, shared, read-only"""
-    k = (key, W, H, frames, K, tuple(sorted(stripes.items())))
-    if k not in _WANT:
-        tris, mats, lights, cam = scene4
-        gid = do.local_gids(W, H, **stripes)
-        fb = do.render(tris, mats, W, H, 0, frames, K, lights=lights, cam=cam, **stripes)
-        L = do.details(tris, mats, W, H, np.tile(gid, frames), np.repeat(np.arange(frames), len(gid)), K, lights=lights, cam=cam)[4]
-        L = L.reshape(frames, len(gid), 3)
-        for a in (fb, L):
-            a.setflags(write=False)
-        _WANT[k] = (fb, L)
-    return _WANT[k]
+def wanted(key, W, H, frames, K, **stripes):
+    """the restatement's (framebuffer, radiance [frames, local pixels, 3]) of a named input: computed once, shared, read-only"""
+    return do.once(_want, key, W, H, frames, K, **stripes)
 
 
 def check(device, key, scene4, W, H, frames, K, what, **stripes):
     """render; the workspace against the restatement's radiance, the framebuffer against its image"""
-    want_fb, want_L = wanted(key, scene4, W, H, frames, K, **stripes)
+    want_fb, want_L = wanted(key, W, H, frames, K, **stripes)
     fb, ws = lit_with_samples(device, scene4, W, H, frames, K, **stripes)
     assert ws.shape == want_L.shape, what
     assert_fb_equal(ws, want_L, what + ": radiance before the fold")
@@ -82,7 +76,7 @@ def test_a_later_chunk_overwrites_slot_zero(device):
     promised), and the framebuffer all five"""
     key, sc = edge_scene("cornell")
     W, H, K = 40, 31, 2
-    want_fb, want_L = wanted(key, sc, W, H, 5, K)
+    want_fb, want_L = wanted(key, W, H, 5, K)
     fb, ws = lit_with_samples(device, sc, W, H, 5, K, chunk_frames=2)
     assert ws.shape == (2, W * H, 3)
     assert_fb_equal(ws[0], want_L[4], "slot 0 holds the last chunk's frame")

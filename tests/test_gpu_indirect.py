@@ -5,15 +5,16 @@ tests/indirect_oracle.c, which composes the estimator from the CPU oracle's own 
 lights the image is the fused renderer's at the same depth (the second statement of the bounce against pt_shade), at one bounce
 it is DirectRenderer's."""
 import ctypes
-import os
-import subprocess
+from functools import partial
 
 import numpy as np
 import pytest
 
+import indirect_edges as ie
 import indirect_oracle as io
-from conftest import ROOT, assert_fb_equal
-from gpu_support import SEARCHES, options, render
+from conftest import assert_fb_equal
+from gpu_support import (SEARCHES, LitBuffers, assert_cut_short_search_is_reported, assert_lit_argument_errors, harness_ppm,
+                         lit_with_samples, options, render)
 from indirect_scenes import lbvh_boxes, tiled_boxes
 from oclpathtracer_amd import shim
 from scenes import GLOSSY_SHIFTS, glossy_room
@@ -25,41 +26,23 @@ W, H = 40, 24
 CASES = ((16, 1), (3, 4))   # (B, K)
 FRAMES = 4
 
-
-def _indirect(device, tris, mats, W, H, frames, K, B, frame_begin=0, want_samples=False, **kw):
-    from oclpathtracer_amd.indirect import IndirectRenderer
-
-    kw.setdefault("stripe_rows", 1)
-    r = IndirectRenderer(device, tris, mats, W, H, light_samples=K, max_bounces=B, **kw)
-    try:
-        r.render(frames, frame_begin)
-        fb = r.read()
-        if not want_samples:
-            return fb
-        assert r.chunk_frames >= frames
-        s = np.zeros(3 * r.local_pixels * frames, np.float32)
-        r.samples.read(s, len(s))
-        device.waitForCompletion()
-        return fb, s.reshape(-1, 3)
-    finally:
-        r.release()
+_Buffers = partial(LitBuffers, "pt_render_indirect")
 
 
-def _want(tris, mats, W, H, frames, K, B, **kw):
-    """the restatement's framebuffer and its radiance before the fold, frame-major as the workspace holds it"""
-    gid, frame = io.all_samples(W, H, frames)
-    return io.render(tris, mats, W, H, 0, frames, K, B, **kw), io.samples(tris, mats, W, H, gid, frame, K, B, **kw)[0]
+def _indirect(device, tris, mats, W, H, frames, K, B, want_samples=False, lights=None, camera=None, **kw):
+    fb, ws = lit_with_samples(device, (tris, mats, lights, camera), W, H, frames, K, max_bounces=B, **kw)
+    return (fb, ws[:frames].reshape(-1, 3)) if want_samples else fb
+
+
+def _want(name, frames, K, B):
+    """the restatement's framebuffer and its radiance before the fold, frame-major as the workspace holds it, of a scene of
+    scenes.edge_scene: computed once, shared, never written to"""
+    return ie.wanted(name, W, H, frames, K, B)
 
 
 @pytest.fixture(scope="module")
-def cornell_want(cornell):
-    """the restatement's images and radiances of the Cornell box: computed once, shared, never written to"""
-    tris, mats = cornell
-    want = {(B, K): _want(tris, mats, W, H, FRAMES, K, B) for B, K in CASES}
-    for fb, rad in want.values():
-        fb.setflags(write=False)
-        rad.setflags(write=False)
-    return want
+def cornell_want():
+    return {(B, K): _want("cornell", FRAMES, K, B) for B, K in CASES}
 
 
 @pytest.mark.parametrize("quad,accel", SEARCHES)
@@ -78,7 +61,7 @@ def test_bit_exact_against_the_restatement(device, cornell, cornell_want, quad, 
 
 def test_tiled_brute_force(device):
     tris, mats = tiled_boxes()
-    want_fb, want_rad = _want(tris, mats, W, H, 2, 2, 4)
+    want_fb, want_rad = _want("nested:10", 2, 2, 4)
     with options(device, ACCEL=1):
         fb, rad = _indirect(device, tris, mats, W, H, 2, 2, 4, want_samples=True)
     assert_fb_equal(rad, want_rad, "tiled brute force: radiance before the fold")
@@ -114,7 +97,7 @@ def lbvh_scene():
 
 def test_lbvh_against_the_restatement_and_brute_force(device, lbvh_scene):
     tris, mats = lbvh_scene
-    want_fb, want_rad = _want(tris, mats, W, H, 2, 2, 4)
+    want_fb, want_rad = _want("nested:15", 2, 2, 4)
     res = {}
     for accel in (0, 2, 1):
         with options(device, ACCEL=accel):
@@ -156,7 +139,7 @@ def test_lbvh_refill_over_more_samples_than_the_grid(device, lbvh_scene):
 def test_glossy_room(device, shift):
     """the BRDF step's guarded quotients at every roughness edge, feeding light samples at later vertices"""
     tris, mats = glossy_room(shift)
-    want_fb, want_rad = _want(tris, mats, W, H, 3, 1, 4)
+    want_fb, want_rad = _want("glossy:%d" % shift, 3, 1, 4)
     fb, rad = _indirect(device, tris, mats, W, H, 3, 1, 4, want_samples=True)
     assert_fb_equal(rad, want_rad, "glossy room %d: radiance before the fold" % shift)
     assert_fb_equal(fb, want_fb, "glossy room %d" % shift)
@@ -187,7 +170,7 @@ def test_progressive_frame_zero_cameras_and_a_rejected_camera(device, cornell):
         bad = shim.Camera()
         b.lib.pt_camera_reference(ctypes.byref(bad))
         bad.center[:] = bad.eye[:]
-        assert b.call(_params(W, H, len(tris), len(mats), 2), cam=ctypes.byref(bad)) == shim.PT_ERR_INVALID
+        assert b.call(b.params(2), cam=ctypes.byref(bad)) == shim.PT_ERR_INVALID
         b.assert_untouched()
     finally:
         b.release()
@@ -249,142 +232,28 @@ def test_interleaved_with_renders_direct_and_ao(device, cornell, oracle):
 
 
 # ---- the raw C ABI ------------------------------------------------------------------------------------------------------------
-def _params(W, H, ntri, nmat, nl, **kw):
-    p = shim.IndirectParams()
-    p.width, p.height, p.frame_begin, p.frame_count = W, H, 0, 1
-    p.num_triangles, p.num_materials, p.num_lights, p.light_samples = ntri, nmat, nl, 2
-    p.stripe_rows, p.n_ranks, p.rank = 1, 1, 0
-    p.max_bounces = 3
-    for k, v in kw.items():
-        if k == "reserved":
-            p.reserved[v] = 1
-        else:
-            setattr(p, k, v)
-    return p
-
-
-class _Buffers:
-    """the buffers of one raw pt_render_indirect call; the framebuffer starts as a sentinel"""
-
-    def __init__(self, device, tris, mats, W, H, lights=(10, 11), pad=4):
-        from oclpathtracer_amd import adl, scene
-
-        self.device, self.lib = device, shim.load()
-        self.tb = adl.Buffer(device, len(tris), scene.TRIANGLE_DTYPE)
-        self.mb = adl.Buffer(device, len(mats), scene.MATERIAL_DTYPE)
-        self.lb = adl.Buffer(device, max(len(lights), 1), np.int32)
-        self.sb = adl.Buffer(device, 3 * W * H, np.float32)
-        self.fb = adl.Buffer(device, W * H + pad, adl.float4)
-        self.tb.write(tris, len(tris))
-        self.mb.write(mats, len(mats))
-        self.lb.write(np.asarray(lights, np.int32), len(lights))
-        self.sentinel = np.full((W * H + pad, 4), np.float32(-7.25), np.float32)
-        self.fb.write(self.sentinel, len(self.sentinel))
-
-    def call(self, p, cam=None, **over):
-        h = lambda name: over[name] if name in over else getattr(self, name)
-        ptr = lambda b: b._h if b is not None else None
-        return self.lib.pt_render_indirect(self.device._h, ptr(h("tb")), ptr(h("mb")), ptr(h("lb")), ptr(h("sb")), ptr(h("fb")),
-                                           ctypes.byref(p) if p is not None else None, cam, None)
-
-    def read(self):
-        out = np.zeros_like(self.sentinel)
-        self.fb.read(out, len(out))
-        self.device.waitForCompletion()
-        return out
-
-    def assert_untouched(self):
-        assert np.array_equal(self.read(), self.sentinel), "the framebuffer was touched"
-
-    def release(self):
-        for b in (self.tb, self.mb, self.lb, self.sb, self.fb):
-            b.release()
-
-
 def test_c_abi_argument_errors_leave_the_framebuffer_untouched(device, cornell):
-    from oclpathtracer_amd import adl
-
     tris, mats = cornell
-    Ws, Hs = 16, 8
-    ntri, nmat = len(tris), len(mats)
-    E_INV, E_RANGE = shim.PT_ERR_INVALID, shim.PT_ERR_RANGE
-    b = _Buffers(device, tris, mats, Ws, Hs)
-    other = adl.DeviceUtils.allocate(adl.TYPE_HIP, adl.Config(0))
-    ob = adl.Buffer(other, 3 * Ws * Hs, np.float32)
+    E_INV = shim.PT_ERR_INVALID
+    b = _Buffers(device, tris, mats, 16, 8)
     try:
-        cases = [(dict(max_bounces=0), E_INV), (dict(max_bounces=65536), E_INV), (dict(max_bounces=-1), E_INV),
-                 (dict(reserved=0), E_INV), (dict(reserved=3), E_INV),
-                 # direct illumination's list
-                 (dict(width=0), E_INV), (dict(height=-1), E_INV), (dict(frame_begin=-1), E_INV), (dict(frame_count=-1), E_INV),
-                 (dict(num_triangles=-1), E_INV), (dict(num_materials=0), E_INV), (dict(num_lights=-1), E_INV),
-                 (dict(num_lights=1 << 24), E_INV), (dict(light_samples=0), E_INV), (dict(light_samples=257), E_INV),
-                 (dict(stripe_rows=0), E_INV), (dict(n_ranks=0), E_INV), (dict(rank=1), E_INV), (dict(rank=-1), E_INV),
-                 (dict(frame_begin=0x7fffffff, frame_count=1), E_INV), (dict(width=65536, height=32768), E_INV),
-                 (dict(num_triangles=ntri + 1), E_RANGE), (dict(num_materials=nmat + 1), E_RANGE), (dict(num_lights=3), E_RANGE),
-                 (dict(width=Ws + 16), E_RANGE)]
-        for kw, code in cases:
-            assert b.call(_params(Ws, Hs, ntri, nmat, 2, **kw)) == code, kw
-        p = _params(Ws, Hs, ntri, nmat, 2)
-        assert b.call(None) == E_INV
-        for name in ("tb", "mb", "sb", "fb"):
-            assert b.call(p, **{name: None}) == E_INV, name
-        assert b.call(p, lb=None) == E_INV                                    # num_lights > 0 needs the list
-        assert b.call(p, sb=ob) == E_INV                                      # a buffer of another device
-        small = adl.Buffer(device, 3 * Ws * Hs - 1, np.float32)
-        try:
-            assert b.call(p, sb=small) == E_RANGE                             # less than one frame of workspace
-        finally:
-            small.release()
-        bad = shim.Camera()
-        b.lib.pt_camera_reference(ctypes.byref(bad))
-        bad.fov_y_deg = 180.0
-        assert b.call(p, cam=ctypes.byref(bad)) == E_INV
-        # a misaligned framebuffer, workspace and framebuffer overlapping: sub-ranges of one allocation
-        big = adl.Buffer(device, 64 * Ws * Hs, np.uint8)
-        try:
-            def wrap(off, nbytes):
-                w = adl.Buffer()
-                w.setRawPtr(device, big.m_ptr + off, nbytes)
-                return w
-            f8, s0, f0 = wrap(12 * Ws * Hs + 8, 16 * Ws * Hs), wrap(0, 12 * Ws * Hs), wrap(12 * Ws * Hs - 16, 16 * Ws * Hs)
-            try:
-                assert b.call(p, sb=s0, fb=f8) == E_INV                       # framebuffer not 16-byte aligned
-                assert b.call(p, sb=s0, fb=f0) == E_INV                       # overlap
-            finally:
-                for w in (f8, s0, f0):
-                    w.release()
-        finally:
-            big.release()
-        b.assert_untouched()
+        for kw in [dict(max_bounces=0), dict(max_bounces=65536), dict(max_bounces=-1)] + [dict(reserved=k) for k in range(4)]:
+            assert b.call(b.params(2, **kw)) == E_INV, kw
+        assert_lit_argument_errors(b)
         for ok in (dict(max_bounces=1), dict(max_bounces=65535, num_triangles=0, num_lights=0)):   # the ends of the range are valid
-            assert b.call(_params(Ws, Hs, ntri, nmat, 2, **ok)) == shim.PT_OK, ok
-        assert b.call(_params(Ws, Hs, ntri, nmat, 0), lb=None) == shim.PT_OK   # no lights, no list
+            assert b.call(b.params(2, **ok)) == shim.PT_OK, ok
+        assert b.call(b.params(0), lb=None) == shim.PT_OK                     # no lights, no list
         device.waitForCompletion()
     finally:
         b.release()
-        ob.release()
-        adl.DeviceUtils.deallocate(other)
 
 
 def test_cut_short_search_is_reported_and_recovers(device, lbvh_scene):
     from oclpathtracer_amd.indirect import IndirectRenderer
 
     tris, mats = lbvh_scene
-    with options(device, ACCEL=2):
-        d = IndirectRenderer(device, tris, mats, W, H, light_samples=1, max_bounces=3, stripe_rows=1)
-        try:
-            d.render(1)
-            want = d.read()
-            with options(device, BVH_STACK_LIMIT=1):
-                with pytest.raises(shim.ShimError) as e:   # the search is cut short; the observing call reports it
-                    d.render(1, 0)
-                    d.read()
-                assert e.value.code == shim.PT_ERR_TRAVERSAL
-            device.waitForCompletion()                     # the word was cleared by the report
-            d.render(1, 0)
-            assert_fb_equal(d.read(), want, "after the report")
-        finally:
-            d.release()
+    assert_cut_short_search_is_reported(
+        device, lambda: IndirectRenderer(device, tris, mats, W, H, light_samples=1, max_bounces=3, stripe_rows=1))
 
 
 def test_empty_scene_renders_the_background(device, cornell):
@@ -401,15 +270,7 @@ def test_cpp_harness_indirect_illumination(tmp_path, cornell):
     from oclpathtracer_amd import scene
 
     tris, mats = cornell
-    exe = os.path.join(ROOT, "oclpathtracer_amd", "raytrace_test")
-    scene_path = os.path.join(ROOT, "oclpathtracer_amd", "data", "cornellbox.bin")
-    r = subprocess.run([exe, "--only", "IndirectIllumination", "--dim", "32", "--frames", "3", "--scene", scene_path,
-                        "--out-dir", str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.count("[       OK ]") == 1 and "FAILED" not in r.stdout and "IndirectIllumination:" in r.stdout
-    ppm = [f for f in os.listdir(tmp_path) if f.endswith(".ppm")]
-    assert len(ppm) == 1 and ppm[0].startswith("indirectIllumination_")
+    out, name, pixels = harness_ppm(tmp_path, 32, 3, "IndirectIllumination")
+    assert "IndirectIllumination:" in out and name.startswith("indirectIllumination_")
     want = io.render(tris, mats, 32, 32, 0, 3, 1, 16)
-    toks = open(os.path.join(tmp_path, ppm[0])).read().split()
-    assert toks[:4] == ["P3", "32", "32", "255"]
-    assert np.array_equal(np.array(toks[4:], np.int64).reshape(-1, 3), scene.f2c(want[:, :3]))
+    assert np.array_equal(pixels, scene.f2c(want[:, :3]))

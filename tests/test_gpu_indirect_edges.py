@@ -10,7 +10,7 @@ import pytest
 
 import indirect_edges as ie
 from conftest import assert_fb_equal
-from gpu_support import SEARCHES, lit_with_samples, options
+from gpu_support import SEARCHES, LitBuffers, lit_with_samples, options
 from oclpathtracer_amd import shim
 from scenes import FINITE_SHIFTS, MIXED_SCALE
 
@@ -146,20 +146,16 @@ def test_light_samples_and_bounces_at_their_limits(device, K, B, accel):
 
 # ---- light indices out of range, through the raw C ABI --------------------------------------------------------------------------------
 def test_light_indices_are_clamped_where_they_are_used(device):
-    from test_gpu_indirect import _Buffers, _params
-
     W, H, frames, K, B = ie.CLAMPED_SIZE
     name, (tris, mats, clamped, _) = ie.clamped_scene()
     raw = ie.clamped_raw(len(tris))
     assert clamped.tolist() == [0, 10, len(tris) - 1, 11]
     want_fb, want_L = ie.wanted(name, W, H, frames, K, B)
-    b = _Buffers(device, tris, mats, W, H, lights=raw, pad=0)
+    b = LitBuffers("pt_render_indirect", device, tris, mats, W, H, lights=raw, frames=frames, pad=0)
     try:
-        assert b.call(_params(W, H, len(tris), len(mats), len(raw), light_samples=K, max_bounces=B, frame_count=frames)) == shim.PT_OK
+        assert b.call(b.params(len(raw), light_samples=K, max_bounces=B, frame_count=frames)) == shim.PT_OK
         fb = b.read()
-        ws = np.zeros((frames, W * H, 3), np.float32)
-        b.sb.read(ws, ws.size)
-        device.waitForCompletion()
+        ws = b.read(b.sb, np.zeros((frames, W * H, 3), np.float32))
     finally:
         b.release()
     assert_fb_equal(ws, want_L, "clamped lights: radiance before the fold")

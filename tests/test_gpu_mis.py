@@ -5,9 +5,7 @@ equal: the sample workspace with the radiance before the fold, and the framebuff
 inputs, that weighted, last-vertex and back-side light samples and later hits on emitters with counts of 0, 1 and 2 all occur, and
 that no sample holds a NaN.  The identities need no restatement: with no lights the image is the fused renderer's, at one bounce it
 is DirectRenderer's, and a plain IndirectRenderer beside a MIS one is unmoved."""
-import ctypes
-import os
-import subprocess
+from functools import partial
 
 import numpy as np
 import pytest
@@ -15,8 +13,8 @@ import pytest
 import indirect_oracle as io
 import mis_cases as mc
 import mis_oracle as mo
-from conftest import ROOT, assert_fb_equal
-from gpu_support import SEARCHES, options, render
+from conftest import assert_fb_equal
+from gpu_support import SEARCHES, LitBuffers, assert_lit_argument_errors, harness_ppm, lit_with_samples, options, render
 from indirect_edges import clamped_raw
 from oclpathtracer_amd import shim
 from scenes import edge_scene
@@ -27,23 +25,13 @@ NONE = np.zeros(0, np.int32)
 W, H, FRAMES = mc.W, mc.H, mc.FRAMES
 
 
-def _mis(device, scene, lights, Ws, Hs, frames, K, B, frame_begin=0, mis=True, **kw):
-    """one IndirectRenderer(mis=True) on a named scene, one render: (framebuffer, workspace [chunk_frames, local pixels, 3])"""
-    from oclpathtracer_amd.indirect import IndirectRenderer
+_Buffers = partial(LitBuffers, "pt_render_indirect_mis")
 
+
+def _mis(device, scene, lights, Ws, Hs, frames, K, B, **kw):
+    """one IndirectRenderer(mis=True) on a named scene, one render: (framebuffer, workspace [chunk_frames, local pixels, 3])"""
     tris, mats, _, cam = edge_scene(scene)[1]
-    kw.setdefault("stripe_rows", 1)
-    kw.setdefault("chunk_frames", max(frames, 1))
-    r = IndirectRenderer(device, tris, mats, Ws, Hs, light_samples=K, max_bounces=B, mis=mis, lights=mc.lights_of(scene, lights), camera=cam, **kw)
-    try:
-        r.render(frames, frame_begin)
-        fb = r.read()
-        ws = np.zeros((r.chunk_frames, r.local_pixels, 3), np.float32)
-        r.samples.read(ws, ws.size)
-        device.waitForCompletion()
-        return fb, ws
-    finally:
-        r.release()
+    return lit_with_samples(device, (tris, mats, mc.lights_of(scene, lights), cam), Ws, Hs, frames, K, max_bounces=B, mis=True, **kw)
 
 
 def _compare(device, scene, lights, Ws, Hs, frames, K, B, what, **stripes):
@@ -137,64 +125,6 @@ def test_light_lists(device, name):
 
 
 # ---- the raw C ABI ---------------------------------------------------------------------------------------------------------------
-def _params(Ws, Hs, ntri, nmat, nl, **kw):
-    p = shim.IndirectParams()
-    p.width, p.height, p.frame_begin, p.frame_count = Ws, Hs, 0, 1
-    p.num_triangles, p.num_materials, p.num_lights, p.light_samples = ntri, nmat, nl, 2
-    p.stripe_rows, p.n_ranks, p.rank = 1, 1, 0
-    p.max_bounces = 3
-    for k, v in kw.items():
-        if k == "reserved":
-            p.reserved[v] = 1
-        else:
-            setattr(p, k, v)
-    return p
-
-
-class _Buffers:
-    """the buffers of one raw pt_render_indirect_mis call; the framebuffer starts as a sentinel, the counts are the list's"""
-
-    def __init__(self, device, tris, mats, Ws, Hs, lights=(10, 11), frames=1, pad=4):
-        from oclpathtracer_amd import adl, scene
-
-        self.device, self.lib = device, shim.load()
-        self.nl, self.ntri = len(lights), len(tris)
-        self.tb = adl.Buffer(device, len(tris), scene.TRIANGLE_DTYPE)
-        self.mb = adl.Buffer(device, len(mats), scene.MATERIAL_DTYPE)
-        self.lb = adl.Buffer(device, max(len(lights), 1), np.int32)
-        self.cb = adl.Buffer(device, len(tris), np.int32)
-        self.sb = adl.Buffer(device, 3 * Ws * Hs * frames, np.float32)
-        self.fb = adl.Buffer(device, Ws * Hs + pad, adl.float4)
-        self.tb.write(tris, len(tris))
-        self.mb.write(mats, len(mats))
-        self.lb.write(np.asarray(lights, np.int32), len(lights))
-        self.sentinel = np.full((Ws * Hs + pad, 4), np.float32(-7.25), np.float32)
-        self.fb.write(self.sentinel, len(self.sentinel))
-        assert self.count() == shim.PT_OK
-
-    def count(self):
-        return self.lib.pt_light_counts(self.device._h, self.lb._h, self.nl, self.ntri, self.cb._h, None)
-
-    def call(self, p, cam=None, **over):
-        h = lambda name: over[name] if name in over else getattr(self, name)
-        ptr = lambda b: b._h if b is not None else None
-        return self.lib.pt_render_indirect_mis(self.device._h, ptr(h("tb")), ptr(h("mb")), ptr(h("lb")), ptr(h("cb")), ptr(h("sb")),
-                                               ptr(h("fb")), ctypes.byref(p) if p is not None else None, cam, None)
-
-    def read(self, buf=None, like=None):
-        out = np.zeros_like(self.sentinel if like is None else like)
-        (self.fb if buf is None else buf).read(out, len(out) if buf is None else out.size)   # (float4 records; scalars otherwise)
-        self.device.waitForCompletion()
-        return out
-
-    def assert_untouched(self):
-        assert np.array_equal(self.read(), self.sentinel), "the framebuffer was touched"
-
-    def release(self):
-        for b in (self.tb, self.mb, self.lb, self.cb, self.sb, self.fb):
-            b.release()
-
-
 def test_indices_out_of_range_are_clamped_in_list_and_counts(device, cornell):
     """[-1, 10, ntri + 5, 11] through the C ABI, the counts made by pt_light_counts from that same list: the image of [0, 10, 35, 11]"""
     tris, mats = cornell
@@ -204,7 +134,7 @@ def test_indices_out_of_range_are_clamped_in_list_and_counts(device, cornell):
     b = _Buffers(device, tris, mats, W, H, lights=raw, frames=FRAMES, pad=0)
     try:
         assert b.read(b.cb, np.zeros(len(tris), np.int32)).tolist() == mo.light_counts(raw, len(tris)).tolist()
-        p = _params(W, H, len(tris), len(mats), len(raw), frame_count=FRAMES, light_samples=K, max_bounces=B)
+        p = b.params(len(raw), frame_count=FRAMES, light_samples=K, max_bounces=B)
         assert b.call(p) == shim.PT_OK
         assert_fb_equal(b.read(), want_fb, "clamped list")
         assert_fb_equal(b.read(b.sb, np.zeros((FRAMES * W * H, 3), np.float32)), want_rad.reshape(-1, 3), "clamped list: radiance before the fold")
@@ -269,7 +199,7 @@ def test_no_lights_and_null_counts_is_the_renderer(device, cornell, B):
     want = render(device, tris, mats, W, H, FRAMES, depth=B, stripe_rows=1)
     b = _Buffers(device, tris, mats, W, H, frames=FRAMES, pad=0)
     try:
-        p = _params(W, H, len(tris), len(mats), 0, frame_count=FRAMES, light_samples=4, max_bounces=B)
+        p = b.params(0, frame_count=FRAMES, light_samples=4, max_bounces=B)
         assert b.call(p, lb=None, cb=None) == shim.PT_OK
         assert_fb_equal(b.read(), want, "no lights, NULL counts against Renderer.render(max_bounces=%d)" % B)
     finally:
@@ -327,7 +257,7 @@ def test_argument_errors_leave_the_framebuffer_untouched(device, cornell):
 
     tris, mats = cornell
     Ws, Hs = 16, 8
-    ntri, nmat = len(tris), len(mats)
+    ntri = len(tris)
     E_INV, E_RANGE = shim.PT_ERR_INVALID, shim.PT_ERR_RANGE
     b = _Buffers(device, tris, mats, Ws, Hs)
     other = adl.DeviceUtils.allocate(adl.TYPE_HIP, adl.Config(0))
@@ -335,7 +265,7 @@ def test_argument_errors_leave_the_framebuffer_untouched(device, cornell):
     short = adl.Buffer(device, ntri - 1, np.int32)
     big = adl.Buffer(device, 12 * Ws * Hs + 4 * ntri + 16, np.uint8)
     try:
-        p = _params(Ws, Hs, ntri, nmat, 2)
+        p = b.params(2)
         assert b.call(p, cb=None) == E_INV                                    # NULL counts with nl > 0
         assert b.call(p, cb=short) == E_RANGE                                 # one triangle short
         assert b.call(p, cb=oc) == E_INV                                      # counts of another device
@@ -352,18 +282,11 @@ def test_argument_errors_leave_the_framebuffer_untouched(device, cornell):
             for w in (s0, c_in, c_odd):
                 w.release()
         assert b.call(p, cb=b.lb) == E_RANGE                                  # (the list as counts: too small before it overlaps)
-        for k in range(4):
-            assert b.call(_params(Ws, Hs, ntri, nmat, 2, reserved=k)) == E_INV, k
-        for kw in (dict(max_bounces=0), dict(max_bounces=65536), dict(max_bounces=-1), dict(light_samples=0), dict(num_lights=1 << 24),
-                   dict(num_lights=-1), dict(width=0)):
-            assert b.call(_params(Ws, Hs, ntri, nmat, 2, **kw)) == E_INV, kw
-        assert b.call(_params(Ws, Hs, ntri, nmat, 3)) == E_RANGE                # the list too short
-        assert b.call(None) == E_INV
-        for name in ("tb", "mb", "sb", "fb"):
-            assert b.call(p, **{name: None}) == E_INV, name
-        b.assert_untouched()
+        for kw in [dict(max_bounces=0), dict(max_bounces=65536), dict(max_bounces=-1)] + [dict(reserved=k) for k in range(4)]:
+            assert b.call(b.params(2, **kw)) == E_INV, kw
+        assert_lit_argument_errors(b)                                         # what every entry point rejects, the framebuffer untouched
         for ok in (dict(max_bounces=1), dict(max_bounces=65535, num_triangles=0, num_lights=0)):   # the ends of the range are valid
-            assert b.call(_params(Ws, Hs, ntri, nmat, 2, **ok)) == shim.PT_OK, ok
+            assert b.call(b.params(2, **ok)) == shim.PT_OK, ok
         device.waitForCompletion()
     finally:
         b.release()
@@ -377,15 +300,7 @@ def test_cpp_harness_mis(tmp_path, cornell):
     from oclpathtracer_amd import scene
 
     tris, mats = cornell
-    exe = os.path.join(ROOT, "oclpathtracer_amd", "raytrace_test")
-    scene_path = os.path.join(ROOT, "oclpathtracer_amd", "data", "cornellbox.bin")
-    r = subprocess.run([exe, "--only", "IndirectIllumination", "--mis", "--dim", "32", "--frames", "3", "--scene", scene_path,
-                        "--out-dir", str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.count("[       OK ]") == 1 and "FAILED" not in r.stdout and "IndirectIllumination (MIS):" in r.stdout
-    ppm = [f for f in os.listdir(tmp_path) if f.endswith(".ppm")]
-    assert len(ppm) == 1 and ppm[0].startswith("indirectIllumination_") and ppm[0].endswith("_mis.ppm")
+    out, name, pixels = harness_ppm(tmp_path, 32, 3, "IndirectIllumination", "--mis")
+    assert "IndirectIllumination (MIS):" in out and name.startswith("indirectIllumination_") and name.endswith("_mis.ppm")
     want = mo.render(tris, mats, 32, 32, 0, 3, 1, 16)
-    toks = open(os.path.join(tmp_path, ppm[0])).read().split()
-    assert toks[:4] == ["P3", "32", "32", "255"]
-    assert np.array_equal(np.array(toks[4:], np.int64).reshape(-1, 3), scene.f2c(want[:, :3]))
+    assert np.array_equal(pixels, scene.f2c(want[:, :3]))

@@ -245,7 +245,7 @@ def test_the_light_lists_reach_their_edges_at_later_vertices():
     assert tuple(lights) == LIGHT_LIST and LIGHT_LIST[4] == 3
     no_wall = np.array(LIGHT_LIST, np.int32)
     no_wall[4] = 36
-    gid, frame = ie.sample_ids(Wn, Hn, frames)
+    gid, frame = do.sample_ids(Wn, Hn, frames)
     reason2 = io.details(tris, mats, Wn, Hn, gid, frame, K, B, lights=no_wall)[3]
     assert np.array_equal(reason == do.NOT_DRAWN, reason2 == do.NOT_DRAWN), "the paths do not depend on the list"
     wall = (reason2 == do.NAN) & (reason != do.NAN)
@@ -343,7 +343,7 @@ def test_the_limits_of_k_and_b(cornell):
     assert ie.LIMITS_KB == ((1, 3), (256, 3), (1, 65535), (1, 64))
     for a, b in zip(ie.wanted("cornell", Wl, Hl, frames, 1, 65535), ie.wanted("cornell", Wl, Hl, frames, 1, 64)):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    gid, frame = ie.sample_ids(Wl, Hl, frames)
+    gid, frame = do.sample_ids(Wl, Hl, frames)
     longest = int(io.samples(tris, mats, Wl, Hl, gid, frame, 1, 65535)[1].max())
     print("the longest path has %d vertices" % longest)
     assert 16 < longest < 64
