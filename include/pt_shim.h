@@ -501,7 +501,8 @@ int pt_render_direct(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materia
  *  - B == 1: the framebuffer is pt_render_direct's, bit for bit -- for emission that is not negative: with an emissive component
  *    of -0 direct forms E + S / K from E = -0 where this forms 0 + E = +0 first; that case is excluded.
  * Not done here: multiple importance sampling (a BRDF ray that finds a light adds nothing at i > 0, so glossy surfaces next to
- * a light are noisy; pt_render_indirect_mis below does it), light choice by power, Russian roulette.
+ * a light are noisy; pt_render_indirect_mis below does it), light choice by power (every entry of the list is as likely as every
+ * other; pt_render_indirect_power below does it), Russian roulette.
  * Behaviour: pt_render_direct's, word for word -- the handle's stream, behind renders in flight, asynchronous (ev); the prepared
  * scene, LBVH and filter tables as a query uses them; no allocation and no wait once the scene is prepared; PT_OPT_ACCEL and
  * PT_OPT_QUAD_FILTER choose the search; PT_ERR_TRAVERSAL is deferred; num_triangles = 0 renders the background.  Errors are
@@ -571,6 +572,70 @@ int pt_render_indirect_mis(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t m
                            pt_buffer_t light_counts /* int32[num_triangles]; may be NULL when num_lights is 0 */,
                            pt_buffer_t samples /* workspace */, pt_buffer_t framebuffer, const pt_indirect_params* params,
                            const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
+
+/* ---- light choice by power ---------------------------------------------------------------------------------------------
+ * A second way to choose the light of a light sample, beside the uniform one, which is unchanged: entry i of the list is chosen in
+ * proportion to the power its triangle emits, area x emission, so that one bright panel among many small dim emitters receives the
+ * samples its light deserves.  The choice goes through a table that pt_light_table builds on the device, once per list.
+ *
+ * THE TABLE is integer on purpose: a float prefix sum depends on the order of the scan, an integer one does not, so the device may
+ * scan in any order and still equal a sequential restatement bit for bit.  For entry i of lights[0 .. nl), nl = num_lights:
+ *  1. j = lights[i] clamped into [0, num_triangles) as pt_render_direct step 3b clamps it; area = 0.5f * sqrt(dot(N, N)), N =
+ *     cross(e2, e1), of triangle j as step 3c forms it; em = the emissive of materials[id of j, clamped into [0, num_materials)];
+ *  2. p_i = area * ((em.x + em.y) + em.z), counted as 0 unless p_i > 0.0f && p_i < INFINITY (false for NaN, a light of no area, an
+ *     entry that is no emitter);
+ *  3. pmax = the largest p_i (of non-NaN floats: independent of the order);
+ *  4. q_i = 0 when p_i is 0, otherwise max(1u, (uint32)((p_i / pmax) * 65536.0f)) with the IEEE "/": 1 .. 65536, and the floor of 1
+ *     means that no emitter of positive power has probability 0;
+ *  5. cdf[0] = 0, cdf[i + 1] = cdf[i] + q_i in uint64; total = cdf[nl] < 2^40;
+ *  6. tri_q[t], a uint32 per triangle: the q of the entries that name t (they have one p, hence one q), 0 for a triangle no entry
+ *     names.
+ * cdf: the caller's buffer of pt_light_table_bytes(num_lights) bytes (0 for a num_lights out of range), at least 8 x (nl + 1): words
+ * 0 .. nl are the cdf, whatever lies behind them is the build's scratch and unspecified.  tri_q: the caller's uint32[num_triangles].
+ * triangles and materials are the scene's buffers as the render entry points take them.  Behaviour is pt_light_counts': one clear and
+ * a few small kernels on the handle's stream, behind renders in flight, asynchronous (ev); nothing is allocated.  num_lights = 0
+ * writes cdf[0] = 0 and clears tri_q; num_triangles = 0 writes a cdf of zeros.  Errors, before anything is enqueued: PT_ERR_INVALID for
+ * a NULL handle (lights may be NULL when num_lights is 0), a negative size, num_materials < 1, num_lights >= 2^24, cdf not 8-byte or
+ * tri_q / lights not 4-byte aligned, cdf or tri_q overlapping each other or an input, a buffer of another device; PT_ERR_RANGE for a
+ * buffer too small.
+ *
+ * THE LIGHT SAMPLE with the table is pt_render_direct's steps 3a-3g with two changes:
+ *  3b. u = min((uint32)(r0 * 16777216.0f), 16777215u) (getRandomFloat can return 1.0); x = (u * total) >> 24 in uint64 (u < 2^24 and
+ *      total < 2^40: the product is below 2^64); i = the entry with cdf[i] <= x < cdf[i + 1] (binary search; an entry of q = 0 is
+ *      never it); j = lights[i], clamped as before.  With total == 0 the three uniforms are drawn, the sample does not contribute
+ *      and no ray is cast.
+ *  3f. inv = (float)total / (float)(cdf[i + 1] - cdf[i]) (conversions to nearest, the IEEE "/"); w = ((cs * cl) / d2) * (area * inv):
+ *      inv stands where (float)nl stood.
+ * What the 24-bit uniform means: entry i is chosen for the u in [ceil(2^24 cdf[i] / total), ceil(2^24 cdf[i + 1] / total)), so the
+ * probability with which it is really chosen differs from q_i / total, the one the weight assumes, by at most 2^-24 absolute -- the
+ * granularity the uniform choice already has (its (uint32)(r0 * nl) of a 24-bit r0).
+ * MIS keeps pt_render_indirect_mis' formulas and its two rules (the last vertex, sl <= 0): a = area * inv, so pe, kp and counts[j]
+ * work as there; the later hit on an emissive triangle h forms, when counts[h] > 0, inv_h = (float)total / (float)tri_q[h] and puts
+ * it where (float)nl stands in pe; with counts[h] == 0, wb = 1 and the table is not read.
+ *
+ * pt_render_direct_power and pt_render_indirect_power take their parents' arguments and parameter blocks (reserved words 0) and the
+ * table; the indirect one also mis (0: pt_render_indirect's estimator, 1: pt_render_indirect_mis') and light_counts, which may be
+ * NULL when mis == 0 or num_lights == 0.  Identities: a list of entries of bit-equal power whose number is a power of two dividing
+ * 2^24 gives inv = nl and i = floor(u nl / 2^24) exactly: the parent's image bit for bit; num_lights == 0: the table may be NULL and is
+ * not read, and the image is pt_render_frames'; B == 1: the indirect image is pt_render_direct_power's.
+ * Behaviour and errors: the parents', word for word -- one validation, one chunk loop, one fold --, plus, when num_lights > 0:
+ * PT_ERR_INVALID for cdf or tri_q NULL, cdf not 8-byte or tri_q not 4-byte aligned, of another device, or overlapping each other,
+ * samples, framebuffer, lights or light_counts; PT_ERR_RANGE for cdf smaller than 8 x (num_lights + 1) bytes or tri_q smaller than
+ * num_triangles x 4 bytes; PT_ERR_INVALID for mis other than 0 or 1. */
+size_t pt_light_table_bytes(int num_lights);
+int pt_light_table(pt_device_t dev, pt_buffer_t triangles, int num_triangles, pt_buffer_t materials, int num_materials,
+                   pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, int num_lights,
+                   pt_buffer_t cdf /* pt_light_table_bytes(num_lights) bytes */, pt_buffer_t tri_q /* uint32[num_triangles] */, pt_event_t ev);
+int pt_render_direct_power(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                           pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, pt_buffer_t cdf, pt_buffer_t tri_q /* may be NULL when 0 */,
+                           pt_buffer_t samples /* workspace */, pt_buffer_t framebuffer, const pt_direct_params* params,
+                           const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
+int pt_render_indirect_power(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                             pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, int mis,
+                             pt_buffer_t light_counts /* int32[num_triangles]; may be NULL when mis or num_lights is 0 */,
+                             pt_buffer_t cdf, pt_buffer_t tri_q /* may be NULL when num_lights is 0 */, pt_buffer_t samples /* workspace */,
+                             pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam /* NULL = the reference's */,
+                             pt_event_t ev);
 
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.

@@ -312,6 +312,33 @@ int ptk_indirect_bvh_blocks_per_cu(void);
 int ptk_indirect_mis_bvh_blocks_per_cu(void);
 // counts[t] = the entries of lights[0 .. nl) whose index, clamped into [0, ntri), is t: one clear, one kernel of vector atomics
 hipError_t ptk_light_counts(const int32_t* lights, int nl, int ntri, int32_t* counts, hipStream_t s);
+// light choice by power (pt_render_direct_power, pt_render_indirect_power): the POWER = true instantiations take these blocks, every
+// other instantiation its block as before (their code does not move).  cdf: uint64[nl + 1], tri_q: uint32[ntri], as pt_light_table
+// writes them; neither is read when nl = 0
+struct PtDirectPowerParams : PtDirectParams {
+    const uint64_t* cdf;
+    const uint32_t* tri_q;
+};
+struct PtIndirectPowerParams : PtIndirectMisParams {
+    const uint64_t* cdf;
+    const uint32_t* tri_q;
+};
+// bvh_blocks: CUs x ptk_direct_power_bvh_blocks_per_cu / ptk_indirect_power_bvh_blocks_per_cu(mis): each LBVH kernel's own figure
+hipError_t ptk_direct_power(const PtDirectPowerParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s);
+hipError_t ptk_indirect_power(const PtIndirectPowerParams& a, int bvh_blocks, PtSearchMode m, bool mis, hipStream_t s);
+int ptk_direct_power_bvh_blocks_per_cu(void);
+int ptk_indirect_power_bvh_blocks_per_cu(bool mis);
+// pt_light_table: the selection table of lights[0 .. nl) over the RAW records (the prepared ones hold the same e1, e2 and N bit for
+// bit: pt_prep_kernel).  cdf: PT_LIGHT_TABLE_WORDS(nl) uint64 -- cdf[0 .. nl], then the build's scratch: the largest power's bits and
+// one sum per tile of PT_LIGHT_SCAN_TILE entries; tri_q: uint32[ntri].  One clear, then four kernels (weights and their maximum;
+// quantise and tile sums; the scan of the tile sums; the scan of the tiles); nl = 0 or ntri = 0 only clears
+#define PT_LIGHT_SCAN_BLOCK 256
+#define PT_LIGHT_SCAN_ITEMS 8
+#define PT_LIGHT_SCAN_TILE (PT_LIGHT_SCAN_BLOCK * PT_LIGHT_SCAN_ITEMS)
+#define PT_LIGHT_TABLE_TILES(nl) (((size_t)(nl) + PT_LIGHT_SCAN_TILE - 1) / PT_LIGHT_SCAN_TILE)
+#define PT_LIGHT_TABLE_WORDS(nl) ((size_t)(nl) + 2 + PT_LIGHT_TABLE_TILES(nl))
+hipError_t ptk_light_table(const PtRawTriangle* tris, int ntri, const PtRawMaterial* mats, int nmat, const int32_t* lights, int nl,
+                           uint64_t* cdf, uint32_t* tri_q, hipStream_t s);
 // rays[2 gid], rays[2 gid + 1] = the pt_ray of pixel gid, frame `frame` (the renderer's sample start) for the camera cam
 hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s);
 // dynamic LDS of a trace workgroup (pt_kernels.hip: pt_lds_total, pt_bvh_lds_total)

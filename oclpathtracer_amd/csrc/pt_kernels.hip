@@ -3060,14 +3060,42 @@ PTK_DEV void pt_direct_surface(const PtDirectParams& D, const f3& o, const f3& d
 // MIS (pt_render_indirect_mis): with `weigh` (the vertex is not the path's last) and the light's front towards the vertex (sl > 0) the
 // weight takes the balance factor kp / (kp counts[j] + pbl) against the BRDF's density pbl towards wi; these quotients are the
 // generic IEEE division (their operands have no proven window).  MIS = false is the code of pt_render_direct and pt_render_indirect.
-template <bool MIS = false>
+// POWER (pt_render_direct_power, pt_render_indirect_power): the entry is chosen through pt_light_table's cdf -- x = (u total) >> 24 of
+// the 24-bit uniform u, the entry with cdf[i] <= x < cdf[i + 1] by binary search -- and total / q_i stands where (float)nl stands in the
+// weight; an empty table (total = 0) contributes nothing.  The search's temporaries die before the light's record is gathered.
+// POWER = false is the uniform choice, the parent's code.
+PTK_DEV float pt_light_table_inv(const uint64_t* cdf, int nl, float r0, unsigned& li)
+{
+    const uint64_t total = cdf[nl];
+    li = 0u;
+    if (total == 0ull) return 0.0f;   // (an empty table: nothing is searched)
+    unsigned u = (unsigned)(r0 * 16777216.0f);   // (getRandomFloat can return 1.0)
+    u = u > 16777215u ? 16777215u : u;
+    const uint64_t x = ((uint64_t)u * total) >> 24;   // < total < 2^40: the product stays below 2^64
+    unsigned lo = 0u, hi = (unsigned)nl;              // cdf[lo] <= x < cdf[hi]
+    while (hi - lo > 1u) {
+        const unsigned m = (lo + hi) >> 1;
+        if (cdf[m] <= x) lo = m; else hi = m;
+    }
+    li = lo;
+    return (float)total / (float)(cdf[lo + 1u] - cdf[lo]);   // >= 1
+}
+
+template <bool MIS = false, bool POWER = false>
 PTK_DEV bool pt_direct_light(const PtDirectParams& D, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed, f3& c, f3& o, f3& d,
-                             float& tl, const int32_t* counts = nullptr, bool weigh = false)
+                             float& tl, const int32_t* counts = nullptr, bool weigh = false, const uint64_t* cdf = nullptr)
 {
     const float r0 = pt_random_float(seed), r1 = pt_random_float(seed), r2 = pt_random_float(seed);
-    const float nlf = (float)D.nl;
-    unsigned li = (unsigned)(r0 * nlf);
-    li = li > (unsigned)D.nl - 1u ? (unsigned)D.nl - 1u : li;
+    float nlf;       // the reciprocal of the probability of the entry chosen: nl, or total / q_i
+    unsigned li;
+    if constexpr (POWER) {
+        nlf = pt_light_table_inv(cdf, D.nl, r0, li);
+        if (nlf == 0.0f) return false;   // (total = 0: the three uniforms are drawn, no ray is cast)
+    } else {
+        nlf = (float)D.nl;
+        li = (unsigned)(r0 * nlf);
+        li = li > (unsigned)D.nl - 1u ? (unsigned)D.nl - 1u : li;
+    }
     const unsigned j = pt_clamp_index(D.lights[li], D.t.ntri);
     // the light's prepared record: p1, e1 = p2 - p1, e2 = p3 - p1, N = cross(e2, e1) (:92-93, :123; computed once per upload, the same bits)
     const float4 ra = pt_rec16(D.t.tris, j, 0u), rb = pt_rec16(D.t.tris, j, 16u), rc = pt_rec16(D.t.tris, j, 32u), nid = pt_rec16(D.t.tris, j, 48u);
@@ -3134,9 +3162,15 @@ PTK_DEV f3 pt_direct_radiance(const PtDirectParams& D, unsigned mid, const f3& S
 }
 
 // brute force: one wave = 64 consecutive samples; the primary search, then the K shadow rays of the lanes whose light sample
-// contributes, all in step (pt_ao_kernel's shape); a light sample no lane of the wave casts a ray for costs no search
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
-__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDirectParams D)
+// contributes, all in step (pt_ao_kernel's shape); a light sample no lane of the wave casts a ray for costs no search.
+// POWER: the light is chosen through pt_light_table's cdf (pt_direct_light<false, true>); such an instantiation takes
+// PtDirectPowerParams, the others PtDirectParams as before
+template <bool POWER> using PtDirectArgs = std::conditional_t<POWER, PtDirectPowerParams, PtDirectParams>;
+PTK_DEV const uint64_t* pt_light_cdf(const PtDirectParams&) { return nullptr; }
+PTK_DEV const uint64_t* pt_light_cdf(const PtDirectPowerParams& D) { return D.cdf; }
+
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool POWER = false>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDirectArgs<POWER> D)
 {
     const PtTraceParams& P = D.t;
     const unsigned lane = pt_lane_id();
@@ -3164,7 +3198,8 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDir
             f3 c = mk3(0.0f, 0.0f, 0.0f);
             float tlim = 0.0f;
             bool cast = false;
-            if (hit) cast = pt_direct_light(D, p, n, wo, mid, seed, c, o, d, tlim);
+            if constexpr (POWER) { if (hit) cast = pt_direct_light<false, true>(D, p, n, wo, mid, seed, c, o, d, tlim, nullptr, false, pt_light_cdf(D)); }
+            else if (hit) cast = pt_direct_light(D, p, n, wo, mid, seed, c, o, d, tlim);
             const bool live = cast & (tlim > 0.0f);
             bool occluded = false;
             if (__ballot(live) != 0ull) {
@@ -3184,9 +3219,10 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDir
 // LBVH (pt_bvh_drive): one item = one sample; the lane runs its searches one after the other -- the primary ray's closest search,
 // then the any-hit searches of the light samples that contribute -- and is free when the sample is stored.  A light sample that
 // does not contribute is passed over inside next_ray: it costs the lane no refill
+template <bool POWER = false>
 struct PtDirectWork {
     static constexpr bool ANY = true;
-    const PtDirectParams& D;
+    const PtDirectArgs<POWER>& D;
     unsigned n;
     int k;           // the current ray: -1 = the primary, 0 .. K-1 = the shadow ray of light sample k
     unsigned item, mid;
@@ -3214,8 +3250,10 @@ struct PtDirectWork {
             S = add3(S, c);
         }
         if (D.nl > 0)
-            while (++k < D.K)
-                if (pt_direct_light(D, p, nrm, wo, mid, seed, c, o, d, tl)) return true;
+            while (++k < D.K) {
+                if constexpr (POWER) { if (pt_direct_light<false, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, nullptr, false, pt_light_cdf(D))) return true; }
+                else if (pt_direct_light(D, p, nrm, wo, mid, seed, c, o, d, tl)) return true;
+            }
         pt_direct_store(D, item, pt_direct_radiance(D, mid, S));
         return false;
     }
@@ -3230,12 +3268,12 @@ struct PtDirectWork {
 // against ambient occlusion's 16, and at five waves (96 VGPRs) the kernel spills 19 of them (profiles/direct/kernel_resources.txt).
 // Its persistent grid is therefore its own figure, ptk_direct_bvh_blocks_per_cu, not ptk_query_bvh_blocks_per_cu
 #define PT_DIRECT_BVH_WAVES 4
-template <bool DET_BOUNDED, int BIGQ>
+template <bool DET_BOUNDED, int BIGQ, bool POWER = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_DIRECT_BVH_WAVES, PT_DIRECT_BVH_WAVES)))
-void pt_direct_bvh_kernel(const PtDirectParams D)
+void pt_direct_bvh_kernel(const PtDirectArgs<POWER> D)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtDirectWork W = { D, D.nitems, -1, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0 };
+    PtDirectWork<POWER> W = { D, D.nitems, -1, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0 };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(D.t, W);
 }
 
@@ -3328,6 +3366,124 @@ __global__ __launch_bounds__(256) void pt_light_counts_kernel(const int32_t* __r
     atomicAdd(counts + pt_clamp_index(lights[i], ntri), 1);
 }
 
+// ---- pt_light_table: the selection table of light choice by power (include/pt_shim.h states every expression) ----
+// The weight of entry i is integer once quantised, so the sums do not depend on the order of the scan.  Four kernels behind a clear:
+//   pt_light_weight_kernel    p_i of every entry, and their maximum by a vector atomic max on the float's bits (p_i > 0: the bits order as
+//                             the values do);
+//   pt_light_quantise_kernel  p_i again (the same bits), q_i, tri_q[j] = q_i (entries that name one triangle store one value), q_i parked
+//                             in cdf[i + 1], and the sum of each tile of PT_LIGHT_SCAN_TILE entries;
+//   pt_light_tiles_kernel     one workgroup: the tile sums become the tiles' offsets; cdf[0] = 0;
+//   pt_light_scan_kernel      each tile's running sum from its offset, in place.
+// A thread owns PT_LIGHT_SCAN_ITEMS consecutive entries, a workgroup one tile.
+
+// p_i of the contract: area * ((em.x + em.y) + em.z) of the entry's triangle, 0 unless positive and finite
+PTK_DEV float pt_light_power(const PtRawTriangle* __restrict__ tris, int ntri, const PtRawMaterial* __restrict__ mats, int nmat, int index)
+{
+    const PtRawTriangle& t = tris[pt_clamp_index(index, ntri)];
+    const f3 p1 = mk3(t.p1[0], t.p1[1], t.p1[2]);
+    const f3 e1 = sub3(mk3(t.p2[0], t.p2[1], t.p2[2]), p1), e2 = sub3(mk3(t.p3[0], t.p3[1], t.p3[2]), p1);   // :92-93
+    const f3 N = cross3(e2, e1);                                                                           // :123
+    const float area = 0.5f * pt_sqrt(dot3(N, N));
+    const float* em = mats[pt_clamp_index(t.id, nmat)].emissive;
+    const float pw = area * ((em[0] + em[1]) + em[2]);
+    return pw > 0.0f && pw < __builtin_inff() ? pw : 0.0f;
+}
+
+PTK_DEV uint32_t pt_light_quantum(float pw, float pmax)
+{
+    if (!(pw > 0.0f)) return 0u;
+    const uint32_t q = (uint32_t)((pw / pmax) * 65536.0f);
+    return q > 1u ? q : 1u;
+}
+
+__global__ __launch_bounds__(PT_LIGHT_SCAN_BLOCK) void pt_light_weight_kernel(const PtRawTriangle* __restrict__ tris, int ntri,
+                                                                              const PtRawMaterial* __restrict__ mats, int nmat,
+                                                                              const int32_t* __restrict__ lights, int nl, uint32_t* __restrict__ pmax_bits)
+{
+    const unsigned i = blockIdx.x * PT_LIGHT_SCAN_BLOCK + threadIdx.x;
+    if (i >= (unsigned)nl) return;
+    const float pw = pt_light_power(tris, ntri, mats, nmat, lights[i]);
+    if (pw > 0.0f) atomicMax(pmax_bits, __float_as_uint(pw));
+}
+
+// the workgroup's exclusive prefix sum of v over its PT_LIGHT_SCAN_BLOCK threads (Hillis-Steele in LDS); *total = the sum of all
+PTK_DEV uint64_t pt_light_block_scan(uint64_t v, uint64_t* lds, uint64_t* total)
+{
+    const unsigned t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (unsigned off = 1u; off < PT_LIGHT_SCAN_BLOCK; off <<= 1) {
+        const uint64_t add = t >= off ? lds[t - off] : 0ull;
+        __syncthreads();
+        lds[t] += add;
+        __syncthreads();
+    }
+    const uint64_t incl = lds[t];
+    *total = lds[PT_LIGHT_SCAN_BLOCK - 1];
+    __syncthreads();   // (lds may be used again)
+    return incl - v;
+}
+
+__global__ __launch_bounds__(PT_LIGHT_SCAN_BLOCK) void pt_light_quantise_kernel(const PtRawTriangle* __restrict__ tris, int ntri,
+                                                                                const PtRawMaterial* __restrict__ mats, int nmat,
+                                                                                const int32_t* __restrict__ lights, int nl,
+                                                                                const uint32_t* __restrict__ pmax_bits, uint64_t* __restrict__ cdf,
+                                                                                uint32_t* __restrict__ tri_q, uint64_t* __restrict__ tile_sums)
+{
+    __shared__ uint64_t lds[PT_LIGHT_SCAN_BLOCK];
+    const float pmax = __uint_as_float(*pmax_bits);
+    const unsigned first = blockIdx.x * PT_LIGHT_SCAN_TILE + threadIdx.x * PT_LIGHT_SCAN_ITEMS;
+    uint64_t sum = 0ull;
+    for (unsigned k = 0; k < PT_LIGHT_SCAN_ITEMS; ++k) {
+        const unsigned i = first + k;
+        if (i >= (unsigned)nl) break;
+        const int index = lights[i];
+        const uint32_t q = pt_light_quantum(pt_light_power(tris, ntri, mats, nmat, index), pmax);
+        tri_q[pt_clamp_index(index, ntri)] = q;
+        cdf[i + 1u] = q;
+        sum += q;
+    }
+    uint64_t total;
+    pt_light_block_scan(sum, lds, &total);
+    if (threadIdx.x == 0u) tile_sums[blockIdx.x] = total;
+}
+
+// one workgroup: tile_sums[0 .. ntiles) become exclusive prefix sums
+__global__ __launch_bounds__(PT_LIGHT_SCAN_BLOCK) void pt_light_tiles_kernel(uint64_t* __restrict__ tile_sums, unsigned ntiles, uint64_t* __restrict__ cdf)
+{
+    __shared__ uint64_t lds[PT_LIGHT_SCAN_BLOCK];
+    const unsigned per = (ntiles + PT_LIGHT_SCAN_BLOCK - 1u) / PT_LIGHT_SCAN_BLOCK;
+    const unsigned first = threadIdx.x * per, end = first + per < ntiles ? first + per : ntiles;
+    uint64_t sum = 0ull;
+    for (unsigned i = first; i < end; ++i) sum += tile_sums[i];
+    uint64_t total;
+    uint64_t run = pt_light_block_scan(sum, lds, &total);
+    for (unsigned i = first; i < end; ++i) {
+        const uint64_t v = tile_sums[i];
+        tile_sums[i] = run;
+        run += v;
+    }
+    if (threadIdx.x == 0u) cdf[0] = 0ull;
+}
+
+__global__ __launch_bounds__(PT_LIGHT_SCAN_BLOCK) void pt_light_scan_kernel(uint64_t* __restrict__ cdf, int nl, const uint64_t* __restrict__ tile_sums)
+{
+    __shared__ uint64_t lds[PT_LIGHT_SCAN_BLOCK];
+    const unsigned first = blockIdx.x * PT_LIGHT_SCAN_TILE + threadIdx.x * PT_LIGHT_SCAN_ITEMS;
+    uint64_t q[PT_LIGHT_SCAN_ITEMS];
+    uint64_t sum = 0ull;
+    for (unsigned k = 0; k < PT_LIGHT_SCAN_ITEMS; ++k) {
+        q[k] = first + k < (unsigned)nl ? cdf[first + k + 1u] : 0ull;
+        sum += q[k];
+    }
+    uint64_t total;
+    uint64_t run = tile_sums[blockIdx.x] + pt_light_block_scan(sum, lds, &total);
+    for (unsigned k = 0; k < PT_LIGHT_SCAN_ITEMS; ++k) {
+        run += q[k];
+        if (first + k < (unsigned)nl) cdf[first + k + 1u] = run;
+    }
+}
+
 // :241, in that order
 PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f3& mask, f3& L)
 {
@@ -3338,16 +3494,23 @@ PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f
 }
 
 // the parameter block of an instantiation, and its counts (none without MIS)
-template <bool MIS> using PtIndirectArgs = std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>;
+template <bool MIS, bool POWER = false>
+using PtIndirectArgs = std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>;
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectParams&) { return nullptr; }
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectMisParams& I) { return I.counts; }
+PTK_DEV const uint64_t* pt_light_cdf(const PtIndirectParams&) { return nullptr; }
+PTK_DEV const uint64_t* pt_light_cdf(const PtIndirectPowerParams& I) { return I.cdf; }
+PTK_DEV const uint32_t* pt_light_tri_q(const PtIndirectParams&) { return nullptr; }
+PTK_DEV const uint32_t* pt_light_tri_q(const PtIndirectPowerParams& I) { return I.tri_q; }
 
 // (MIS) the emission of a vertex i >= 1, found by the BRDF ray (o, d) at distance t, weighted against the light samples of the vertex
 // before: pe is the density those give the same point -- from the hit triangle's record N = cross(e2, e1), its own distance
 // tt = t + 0.01f (the ray began 0.01 off that vertex, :257) and its count --, pb the density of the BRDF sample that made the ray.
-// A material with no emissive component reads no count and adds nothing
+// A material with no emissive component reads no count and adds nothing.  POWER: total / tri_q[h] stands where (float)nl stands, formed
+// when counts[h] > 0; with counts[h] = 0 the weight is 1 and the table is not read
+template <bool POWER = false>
 PTK_DEV void pt_indirect_emission_mis(const PtDirectParams& D, const int32_t* counts, unsigned mid, int hidx, const f3& d, float t, float pb,
-                                      const f3& mask, f3& L)
+                                      const f3& mask, f3& L, const uint64_t* cdf = nullptr, const uint32_t* tri_q = nullptr)
 {
     const float4 emi = pt_rec16(D.t.mats, mid, 16u);
     if (!(emi.x != 0.0f || emi.y != 0.0f || emi.z != 0.0f)) return;
@@ -3357,8 +3520,19 @@ PTK_DEV void pt_indirect_emission_mis(const PtDirectParams& D, const int32_t* co
     const float areah = 0.5f * pt_sqrt(N2);
     const float clh = __builtin_fabsf(dot3(d, scale3(N, pt_normalize_factor(N2))));
     const float tt = t + 0.01f;
-    const float pe = (tt * tt) / (clh * (areah * (float)D.nl));
-    const float wb = pb / (((float)D.K * pe) * (float)counts[hidx] + pb);
+    float wb;
+    if constexpr (POWER) {
+        const int cnt = counts[hidx];
+        wb = 1.0f;
+        if (cnt > 0) {
+            const float invh = (float)cdf[D.nl] / (float)tri_q[hidx];
+            const float pe = (tt * tt) / (clh * (areah * invh));
+            wb = pb / (((float)D.K * pe) * (float)cnt + pb);
+        }
+    } else {
+        const float pe = (tt * tt) / (clh * (areah * (float)D.nl));
+        wb = pb / (((float)D.K * pe) * (float)counts[hidx] + pb);
+    }
     L.x = L.x + ((mask.x * emi.x) * 3.0f) * wb;
     L.y = L.y + ((mask.y * emi.y) * 3.0f) * wb;
     L.z = L.z + ((mask.z * emi.z) * 3.0f) * wb;
@@ -3381,8 +3555,8 @@ PTK_DEV void pt_indirect_store(const PtDirectParams& D, unsigned item, const f3&
 // brute force: one wave = 64 consecutive samples, pt_direct_kernel's shape inside a loop over the bounces.  The wave searches in step
 // with the lanes still alive and leaves the loop when none is; a light sample no lane casts a ray for costs no search.  Lanes whose
 // path has ended are NOT given new samples: the wave runs as long as its longest path (DESIGN.md S4 states the cost).
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtIndirectArgs<MIS> I)
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS = false, bool POWER = false>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtIndirectArgs<MIS, POWER> I)
 {
     const PtDirectParams& D = I.d;
     const PtTraceParams& P = D.t;
@@ -3413,6 +3587,7 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
         if (hit) {
             pt_direct_surface(D, o, d, tmax, hu, hv, hidx, p, n, wo, mid);
             if (i == 0 || D.nl == 0) pt_indirect_emission(D, mid, mask, L);
+            else if constexpr (MIS && POWER) pt_indirect_emission_mis<true>(D, pt_indirect_counts(I), mid, hidx, d, tmax, pb, mask, L, pt_light_cdf(I), pt_light_tri_q(I));
             else if constexpr (MIS) pt_indirect_emission_mis(D, pt_indirect_counts(I), mid, hidx, d, tmax, pb, mask, L);
         }
         if (D.nl > 0) {
@@ -3421,7 +3596,8 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
                 f3 c = mk3(0.0f, 0.0f, 0.0f);
                 float tlim = 0.0f;
                 bool cast = false;
-                if (hit) cast = pt_direct_light<MIS>(D, p, n, wo, mid, seed, c, o, d, tlim, pt_indirect_counts(I), i < I.B - 1);
+                if constexpr (POWER) { if (hit) cast = pt_direct_light<MIS, true>(D, p, n, wo, mid, seed, c, o, d, tlim, pt_indirect_counts(I), i < I.B - 1, pt_light_cdf(I)); }
+                else if (hit) cast = pt_direct_light<MIS>(D, p, n, wo, mid, seed, c, o, d, tlim, pt_indirect_counts(I), i < I.B - 1);
                 const bool live = cast & (tlim > 0.0f);
                 bool occluded = false;
                 if (__ballot(live) != 0ull) {
@@ -3450,10 +3626,10 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
 // wo is the negated incoming direction, which the shadow rays overwrite in d, so it is kept; o is dead while p is live.
 // With MIS a lane also holds pb from the BRDF sample to the next closest hit, across that search: 34 registers.  The counts and the
 // emitter's record are gathered where they are used, as the materials are.
-template <bool MIS = false>
+template <bool MIS = false, bool POWER = false>
 struct PtIndirectWork {
     static constexpr bool ANY = true;
-    const PtIndirectArgs<MIS>& I;
+    const PtIndirectArgs<MIS, POWER>& I;
     unsigned n;
     int k;           // the current ray: -1 = the vertex's closest search, 0 .. K-1 = the shadow ray of light sample k
     int bounce;      // loop index i of traceRays (:229)
@@ -3483,14 +3659,17 @@ struct PtIndirectWork {
             }
             pt_direct_surface(D, o, d, R.tmax, R.hu, R.hv, R.hidx, p, nrm, wo, mid);
             if (bounce == 0 || D.nl == 0) pt_indirect_emission(D, mid, mask, L);
+            else if constexpr (MIS && POWER) pt_indirect_emission_mis<true>(D, pt_indirect_counts(I), mid, R.hidx, d, R.tmax, pb, mask, L, pt_light_cdf(I), pt_light_tri_q(I));
             else if constexpr (MIS) pt_indirect_emission_mis(D, pt_indirect_counts(I), mid, R.hidx, d, R.tmax, pb, mask, L);
             S = mk3(0.0f, 0.0f, 0.0f);
         } else if (R.hidx < 0) {   // (an any-hit search: R.hidx >= 0 alone says occluded; a ray that searched nothing is open)
             S = add3(S, c);
         }
         if (D.nl > 0) {
-            while (++k < D.K)
-                if (pt_direct_light<MIS>(D, p, nrm, wo, mid, seed, c, o, d, tl, pt_indirect_counts(I), bounce < I.B - 1)) return true;
+            while (++k < D.K) {
+                if constexpr (POWER) { if (pt_direct_light<MIS, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, pt_indirect_counts(I), bounce < I.B - 1, pt_light_cdf(I))) return true; }
+                else if (pt_direct_light<MIS>(D, p, nrm, wo, mid, seed, c, o, d, tl, pt_indirect_counts(I), bounce < I.B - 1)) return true;
+            }
             pt_indirect_lit(D, mask, S, L);
         }
         bool on;
@@ -3518,12 +3697,12 @@ struct PtIndirectWork {
 #ifndef PT_INDIRECT_BVH_WAVES   // (tools/kernel_resources.sh -DPT_INDIRECT_BVH_WAVES=4 reads the other choice)
 #define PT_INDIRECT_BVH_WAVES 3
 #endif
-template <bool DET_BOUNDED, int BIGQ, bool MIS = false>
+template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_INDIRECT_BVH_WAVES, PT_INDIRECT_BVH_WAVES)))
-void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS> I)
+void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER> I)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtIndirectWork<MIS> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
+    PtIndirectWork<MIS, POWER> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(I.d.t, W);
 }
 
@@ -3723,6 +3902,61 @@ hipError_t ptk_direct(const PtDirectParams& a, int bvh_blocks, PtSearchMode m, h
 }
 
 int ptk_direct_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_direct_bvh_kernel<true, 3>, ptk_trace_bvh_lds_bytes()); }
+
+hipError_t ptk_direct_power(const PtDirectPowerParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
+{
+    if (a.nitems == 0) return hipSuccess;
+    const bool q3 = m.quads == 3;
+    void (*kernel)(const PtDirectPowerParams);
+    if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_direct_bvh_kernel<true, 3, true>, pt_direct_bvh_kernel<true, 0, true>, pt_direct_bvh_kernel<false, 0, true>);
+    else if (a.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_direct_kernel<true, 1, 3, true>, pt_direct_kernel<true, 1, 0, true>, pt_direct_kernel<false, 1, 0, true>);
+    else kernel = m.det_bounded ? pt_direct_kernel<true, 2, 0, true> : pt_direct_kernel<false, 2, 0, true>;
+    return pt_launch_search(kernel, a, a.t.ntri, a.nitems, m.bvh, bvh_blocks, s);
+}
+
+int ptk_direct_power_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_direct_bvh_kernel<true, 3, true>, ptk_trace_bvh_lds_bytes()); }
+
+hipError_t ptk_indirect_power(const PtIndirectPowerParams& a, int bvh_blocks, PtSearchMode m, bool mis, hipStream_t s)
+{
+    if (a.d.nitems == 0) return hipSuccess;
+    const bool q3 = m.quads == 3;
+    void (*kernel)(const PtIndirectPowerParams);
+    if (mis) {
+        if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3, true, true>, pt_indirect_bvh_kernel<true, 0, true, true>, pt_indirect_bvh_kernel<false, 0, true, true>);
+        else if (a.d.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_kernel<true, 1, 3, true, true>, pt_indirect_kernel<true, 1, 0, true, true>, pt_indirect_kernel<false, 1, 0, true, true>);
+        else kernel = m.det_bounded ? pt_indirect_kernel<true, 2, 0, true, true> : pt_indirect_kernel<false, 2, 0, true, true>;
+    } else {
+        if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3, false, true>, pt_indirect_bvh_kernel<true, 0, false, true>, pt_indirect_bvh_kernel<false, 0, false, true>);
+        else if (a.d.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_kernel<true, 1, 3, false, true>, pt_indirect_kernel<true, 1, 0, false, true>, pt_indirect_kernel<false, 1, 0, false, true>);
+        else kernel = m.det_bounded ? pt_indirect_kernel<true, 2, 0, false, true> : pt_indirect_kernel<false, 2, 0, false, true>;
+    }
+    return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, m.bvh, bvh_blocks, s);
+}
+
+int ptk_indirect_power_bvh_blocks_per_cu(bool mis)
+{
+    return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, true>, ptk_trace_bvh_lds_bytes())
+               : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, true>, ptk_trace_bvh_lds_bytes());
+}
+
+hipError_t ptk_light_table(const PtRawTriangle* tris, int ntri, const PtRawMaterial* mats, int nmat, const int32_t* lights, int nl,
+                           uint64_t* cdf, uint32_t* tri_q, hipStream_t s)
+{
+    hipError_t e = hipSuccess;
+    if (ntri > 0 && (e = hipMemsetAsync(tri_q, 0, (size_t)ntri * sizeof(uint32_t), s)) != hipSuccess) return e;
+    if (nl == 0 || ntri == 0) return hipMemsetAsync(cdf, 0, ((size_t)nl + 1) * sizeof(uint64_t), s);   // (no triangle to name: every q is 0)
+    const unsigned ntiles = (unsigned)PT_LIGHT_TABLE_TILES(nl);
+    uint64_t* pmax = cdf + (size_t)nl + 1;   // the build's scratch, behind the specified part: the maximum's bits, then the tile sums
+    uint64_t* tile_sums = pmax + 1;
+    if ((e = hipMemsetAsync(pmax, 0, sizeof(uint64_t), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(pt_light_weight_kernel, dim3(((unsigned)nl + PT_LIGHT_SCAN_BLOCK - 1u) / PT_LIGHT_SCAN_BLOCK), dim3(PT_LIGHT_SCAN_BLOCK), 0, s,
+                       tris, ntri, mats, nmat, lights, nl, reinterpret_cast<uint32_t*>(pmax));
+    hipLaunchKernelGGL(pt_light_quantise_kernel, dim3(ntiles), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, tris, ntri, mats, nmat, lights, nl,
+                       reinterpret_cast<const uint32_t*>(pmax), cdf, tri_q, tile_sums);
+    hipLaunchKernelGGL(pt_light_tiles_kernel, dim3(1), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, tile_sums, ntiles, cdf);
+    hipLaunchKernelGGL(pt_light_scan_kernel, dim3(ntiles), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, cdf, nl, tile_sums);
+    return hipGetLastError();
+}
 
 hipError_t ptk_indirect(const PtIndirectMisParams& a, int bvh_blocks, PtSearchMode m, bool mis, hipStream_t s)
 {

@@ -139,6 +139,7 @@ struct pt_device_s {
     int direct_bvh_blocks_per_cu;  // ... and of the direct-illumination kernel, which runs at four waves per SIMD
     int indirect_bvh_blocks_per_cu;   // ... and of the indirect-illumination kernel, at its own occupancy
     int indirect_mis_bvh_blocks_per_cu;   // ... and of its MIS instantiation
+    int direct_power_bvh_blocks_per_cu, indirect_power_bvh_blocks_per_cu, indirect_power_mis_bvh_blocks_per_cu;   // ... and of the POWER ones
     unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
     unsigned int* trav_dev;  // ... as the device addresses it
     // ---- fused-render workspace: the STREAMING renderer (render_part, plan_chunks, the ring).  A render walks its frames in chunks of
@@ -362,6 +363,9 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->direct_bvh_blocks_per_cu = ptk_direct_bvh_blocks_per_cu();
     d->indirect_bvh_blocks_per_cu = ptk_indirect_bvh_blocks_per_cu();
     d->indirect_mis_bvh_blocks_per_cu = ptk_indirect_mis_bvh_blocks_per_cu();
+    d->direct_power_bvh_blocks_per_cu = ptk_direct_power_bvh_blocks_per_cu();
+    d->indirect_power_bvh_blocks_per_cu = ptk_indirect_power_bvh_blocks_per_cu(false);
+    d->indirect_power_mis_bvh_blocks_per_cu = ptk_indirect_power_bvh_blocks_per_cu(true);
     *out = d;
     return PT_OK;
 }
@@ -1768,24 +1772,28 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
 static_assert(sizeof(pt_direct_params) == 64, "pt_direct_params layout");
 static_assert(sizeof(pt_indirect_params) == 64, "pt_indirect_params layout");
 
-// pt_render_direct, pt_render_indirect and pt_render_indirect_mis: one validation, one chunk loop.  `a`: the fields the parameter
-// blocks share (each entry point has looked at its own reserved ones).  max_bounces: 0 = direct illumination (its own kernels),
-// otherwise the depth of an indirect render.  mis: the MIS estimator, which reads light_counts (NULL otherwise).  what: the message
+// pt_render_direct, pt_render_indirect, pt_render_indirect_mis and the two _power entry points: one validation, one chunk loop.
+// `a`: the fields the parameter blocks share (each entry point has looked at its own reserved ones).  max_bounces: 0 = direct
+// illumination (its own kernels), otherwise the depth of an indirect render.  mis: the MIS estimator, which reads light_counts (NULL
+// otherwise).  table: NULL = the uniform choice, otherwise {cdf, tri_q} of pt_light_table, the choice by power.  what: the message
 // for a field out of range
 static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts, bool mis,
                       pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params& a, int max_bounces, const char* what,
-                      const pt_camera* cam, pt_event_t ev)
+                      const pt_camera* cam, pt_event_t ev, const pt_buffer_t* table = nullptr)
 {
+    const bool power = table != nullptr;
+    pt_buffer_t cdf = power ? table[0] : nullptr, tri_q = power ? table[1] : nullptr;
     int rc;
     PtCamera c = reference_camera();
     if (cam && (rc = camera_derive(cam, &c))) return rc;
     if (!triangles || !materials || !samples || !framebuffer) return fail(PT_ERR_INVALID, "null buffer handle");
-    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer })) || (rc = check_event(d, ev))) return rc;
+    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer, cdf, tri_q })) || (rc = check_event(d, ev))) return rc;
     if (a.num_triangles < 0 || a.num_materials < 1 || a.num_lights < 0 || a.light_samples < 1 || a.light_samples > 256)
         return fail(PT_ERR_INVALID, "%s", what);
     if (a.num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
     if (a.num_lights > 0 && !lights) return fail(PT_ERR_INVALID, "num_lights > 0 needs a light list");
     if (mis && a.num_lights > 0 && !light_counts) return fail(PT_ERR_INVALID, "num_lights > 0 needs the light counts (pt_light_counts)");
+    if (power && a.num_lights > 0 && !(cdf && tri_q)) return fail(PT_ERR_INVALID, "num_lights > 0 needs the light table (pt_light_table)");
     // the light's record and the materials are gathered by 32-bit byte offsets into the 64-byte records, as shading gathers them
     if ((uint64_t)a.num_triangles * 64u > 0xffffffffull || (uint64_t)a.num_materials * 64u > 0xffffffffull)
         return fail(PT_ERR_INVALID, "a scene has fewer than 2^26 triangles and 2^26 materials");
@@ -1816,6 +1824,19 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
             ranges_overlap(light_counts, count_bytes, lights, light_bytes))
             return fail(PT_ERR_INVALID, "the light counts overlap the sample workspace, the framebuffer or the light list");
     }
+    if (power && a.num_lights > 0) {   // (with no lights the table is not read)
+        const size_t cdf_bytes = ((size_t)a.num_lights + 1) * sizeof(uint64_t), q_bytes = (size_t)a.num_triangles * sizeof(uint32_t);
+        if (cdf_bytes > cdf->bytes) return fail(PT_ERR_RANGE, "the light table's cdf holds %zu bytes, %d lights need %zu", cdf->bytes, a.num_lights, cdf_bytes);
+        if (q_bytes > tri_q->bytes) return fail(PT_ERR_RANGE, "the light table's tri_q holds %zu bytes, %d triangles need %zu", tri_q->bytes, a.num_triangles, q_bytes);
+        if ((uintptr_t)cdf->dptr & 7u) return fail(PT_ERR_INVALID, "the light table's cdf must be 8-byte aligned");
+        if (q_bytes && ((uintptr_t)tri_q->dptr & 3u)) return fail(PT_ERR_INVALID, "the light table's tri_q must be 4-byte aligned");
+        const pt_buffer_s* others[] = { samples, framebuffer, lights, mis ? light_counts : nullptr };
+        const size_t other_bytes[] = { samples->bytes, fb_bytes, light_bytes, (size_t)a.num_triangles * sizeof(int32_t) };
+        for (int i = 0; i < 4; ++i)
+            if (others[i] && (ranges_overlap(cdf, cdf_bytes, others[i], other_bytes[i]) || ranges_overlap(tri_q, q_bytes, others[i], other_bytes[i])))
+                return fail(PT_ERR_INVALID, "the light table overlaps the sample workspace, the framebuffer, the light list or the light counts");
+        if (ranges_overlap(cdf, cdf_bytes, tri_q, q_bytes)) return fail(PT_ERR_INVALID, "the light table's cdf and tri_q overlap");
+    }
     // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
     if ((rc = check_traversal(d))) return rc;
     if ((rc = enter_stream(d))) return rc;
@@ -1826,7 +1847,7 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     PtSearch search;
     if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
     if ((rc = event_begin(d, ev))) return rc;
-    PtIndirectMisParams ip;
+    PtIndirectPowerParams ip;
     memset(&ip, 0, sizeof ip);
     ip.B = max_bounces;
     PtDirectParams& p = ip.d;
@@ -1841,21 +1862,32 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     p.K = a.light_samples;
     p.nl = a.num_lights;
     ip.counts = mis && a.num_lights > 0 ? (const int32_t*)light_counts->dptr : nullptr;
+    ip.cdf = power && a.num_lights > 0 ? (const uint64_t*)cdf->dptr : nullptr;
+    ip.tri_q = power && a.num_lights > 0 ? (const uint32_t*)tri_q->dptr : nullptr;
+    PtDirectPowerParams dp;   // (direct by power: direct's block and the table)
+    memset(&dp, 0, sizeof dp);
     PtFoldParams fp;
     memset(&fp, 0, sizeof fp);
     fp.rad = p.samples;
     fp.fb = (float4*)framebuffer->dptr;
     fp.npix_local = npix;
-    const int bvh_blocks = !search.mode.bvh ? 0   // (each kernel its own grid: pt_kernels.h)
-                                            : d->prop.multiProcessorCount * (mis ? d->indirect_mis_bvh_blocks_per_cu
-                                                                                 : max_bounces > 0 ? d->indirect_bvh_blocks_per_cu : d->direct_bvh_blocks_per_cu);
+    const int per_cu = power ? (mis ? d->indirect_power_mis_bvh_blocks_per_cu
+                                    : max_bounces > 0 ? d->indirect_power_bvh_blocks_per_cu : d->direct_power_bvh_blocks_per_cu)
+                             : (mis ? d->indirect_mis_bvh_blocks_per_cu : max_bounces > 0 ? d->indirect_bvh_blocks_per_cu : d->direct_bvh_blocks_per_cu);
+    const int bvh_blocks = !search.mode.bvh ? 0 : d->prop.multiProcessorCount * per_cu;   // (each kernel its own grid: pt_kernels.h)
     // whole frames per chunk: what the workspace holds, fewer than 2^31 samples per launch; a launch, then its fold
     const int64_t per_chunk = (int64_t)std::min<uint64_t>(samples->bytes / frame_bytes, 0x7fffffffu / npix);
     for (int64_t done = 0; done < a.frame_count; done += per_chunk) {
         const int nf = (int)std::min<int64_t>(per_chunk, a.frame_count - done);
         p.frame0 = a.frame_begin + (int)done;
         p.nitems = (uint32_t)nf * npix;
-        HIP_TRY(max_bounces > 0 ? ptk_indirect(ip, bvh_blocks, search.mode, mis, d->stream) : ptk_direct(p, bvh_blocks, search.mode, d->stream));
+        if (power && max_bounces == 0) {
+            static_cast<PtDirectParams&>(dp) = p;
+            dp.cdf = ip.cdf;
+            dp.tri_q = ip.tri_q;
+        }
+        HIP_TRY(power ? (max_bounces > 0 ? ptk_indirect_power(ip, bvh_blocks, search.mode, mis, d->stream) : ptk_direct_power(dp, bvh_blocks, search.mode, d->stream))
+                      : (max_bounces > 0 ? ptk_indirect(ip, bvh_blocks, search.mode, mis, d->stream) : ptk_direct(p, bvh_blocks, search.mode, d->stream)));
         fp.frame_begin = p.frame0;
         fp.frame_count = nf;
         HIP_TRY(ptk_fold(fp, d->stream));
@@ -1880,7 +1912,8 @@ extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_
 // ---- indirect illumination (include/pt_shim.h) ---------------------------------------------------------------------------------
 // pt_render_indirect and pt_render_indirect_mis: the same parameter block, the same checks of it
 static int render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts, bool mis,
-                           pt_buffer_t samples, pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
+                           pt_buffer_t samples, pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev,
+                           const pt_buffer_t* table = nullptr)
 {
     int rc = use_device(d);
     if (rc) return rc;
@@ -1896,7 +1929,7 @@ static int render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t mat
     a.light_samples = b.light_samples;
     a.stripe_rows = b.stripe_rows; a.n_ranks = b.n_ranks; a.rank = b.rank;
     return render_lit(d, triangles, materials, lights, light_counts, mis, samples, framebuffer, a, b.max_bounces,
-                      "invalid indirect-illumination parameters", cam, ev);
+                      "invalid indirect-illumination parameters", cam, ev, table);
 }
 
 extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
@@ -1910,6 +1943,71 @@ extern "C" int pt_render_indirect_mis(pt_device_t d, pt_buffer_t triangles, pt_b
                                       pt_event_t ev)
 {
     return render_indirect(d, triangles, materials, lights, light_counts, true, samples, framebuffer, params, cam, ev);
+}
+
+// ---- light choice by power (include/pt_shim.h) -----------------------------------------------------------------------------------
+extern "C" int pt_render_direct_power(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t cdf,
+                                      pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params* params,
+                                      const pt_camera* cam, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
+    const pt_direct_params a = *params;
+    for (int i = 0; i < 5; ++i)
+        if (a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    const pt_buffer_t table[2] = { cdf, tri_q };
+    return render_lit(d, triangles, materials, lights, nullptr, false, samples, framebuffer, a, 0, "invalid direct-illumination parameters", cam, ev, table);
+}
+
+extern "C" int pt_render_indirect_power(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
+                                        pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples,
+                                        pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
+{
+    if (mis != 0 && mis != 1) return fail(PT_ERR_INVALID, "mis must be 0 or 1");
+    const pt_buffer_t table[2] = { cdf, tri_q };
+    return render_indirect(d, triangles, materials, lights, mis ? light_counts : nullptr, mis != 0, samples, framebuffer, params, cam, ev, table);
+}
+
+extern "C" size_t pt_light_table_bytes(int num_lights)
+{
+    return num_lights < 0 || num_lights >= (1 << 24) ? 0 : PT_LIGHT_TABLE_WORDS(num_lights) * sizeof(uint64_t);
+}
+
+extern "C" int pt_light_table(pt_device_t d, pt_buffer_t triangles, int num_triangles, pt_buffer_t materials, int num_materials,
+                              pt_buffer_t lights, int num_lights, pt_buffer_t cdf, pt_buffer_t tri_q, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!triangles || !materials || !cdf || !tri_q) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { triangles, materials, lights, cdf, tri_q })) || (rc = check_event(d, ev))) return rc;
+    if (num_lights < 0 || num_triangles < 0 || num_materials < 1) return fail(PT_ERR_INVALID, "invalid light-table parameters");
+    if (num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
+    if (num_lights > 0 && !lights) return fail(PT_ERR_INVALID, "num_lights > 0 needs a light list");
+    const size_t light_bytes = (size_t)num_lights * sizeof(int32_t), cdf_bytes = pt_light_table_bytes(num_lights),
+                 q_bytes = (size_t)num_triangles * sizeof(uint32_t);
+    if ((rc = check_triangles(triangles, num_triangles))) return rc;
+    if ((size_t)num_materials * sizeof(PtRawMaterial) > materials->bytes)
+        return fail(PT_ERR_RANGE, "material buffer holds %zu bytes, %d materials need %zu", materials->bytes, num_materials,
+                    (size_t)num_materials * sizeof(PtRawMaterial));
+    if (lights && light_bytes > lights->bytes) return fail(PT_ERR_RANGE, "light list holds %zu bytes, %d lights need %zu", lights->bytes, num_lights, light_bytes);
+    if (cdf_bytes > cdf->bytes) return fail(PT_ERR_RANGE, "the light table's cdf holds %zu bytes, %d lights need %zu (pt_light_table_bytes)", cdf->bytes, num_lights, cdf_bytes);
+    if (q_bytes > tri_q->bytes) return fail(PT_ERR_RANGE, "the light table's tri_q holds %zu bytes, %d triangles need %zu", tri_q->bytes, num_triangles, q_bytes);
+    if ((uintptr_t)cdf->dptr & 7u) return fail(PT_ERR_INVALID, "the light table's cdf must be 8-byte aligned");
+    if (q_bytes && ((uintptr_t)tri_q->dptr & 3u)) return fail(PT_ERR_INVALID, "the light table's tri_q must be 4-byte aligned");
+    if (lights && num_lights > 0 && ((uintptr_t)lights->dptr & 3u)) return fail(PT_ERR_INVALID, "the light list must be 4-byte aligned");
+    const pt_buffer_s* in[] = { triangles, materials, lights };
+    const size_t in_bytes[] = { (size_t)num_triangles * sizeof(PtRawTriangle), (size_t)num_materials * sizeof(PtRawMaterial), light_bytes };
+    for (int i = 0; i < 3; ++i)
+        if (in[i] && (ranges_overlap(cdf, cdf_bytes, in[i], in_bytes[i]) || ranges_overlap(tri_q, q_bytes, in[i], in_bytes[i])))
+            return fail(PT_ERR_INVALID, "the light table overlaps the triangles, the materials or the light list");
+    if (ranges_overlap(cdf, cdf_bytes, tri_q, q_bytes)) return fail(PT_ERR_INVALID, "the light table's cdf and tri_q overlap");
+    if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
+    HIP_TRY(ptk_light_table((const PtRawTriangle*)triangles->dptr, num_triangles, (const PtRawMaterial*)materials->dptr, num_materials,
+                            num_lights > 0 ? (const int32_t*)lights->dptr : nullptr, num_lights, (uint64_t*)cdf->dptr, (uint32_t*)tri_q->dptr, d->stream));
+    cdf->version++;
+    tri_q->version++;
+    return event_end(d, ev);
 }
 
 extern "C" int pt_light_counts(pt_device_t d, pt_buffer_t lights, int num_lights, int num_triangles, pt_buffer_t counts, pt_event_t ev)

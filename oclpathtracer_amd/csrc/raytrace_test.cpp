@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination | --only IndirectIllumination [--mis]]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power] | --only IndirectIllumination [--mis] [--lights power]]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <chrono>
 #include <cmath>
@@ -118,6 +118,7 @@ static bool loadModel(const char* filepath, std::vector<Triangle>& tBuffer, std:
 struct Options {
     int deviceIdx = 0, dim = 512, frames = 10000;
     bool batch = true, mis = false;   // mis: IndirectIllumination through pt_render_indirect_mis
+    bool power = false;               // --lights power: DirectIllumination / IndirectIllumination choose their lights by power
     std::string scene = "cornellbox.bin", outDir = ".", dump, only;
 };
 
@@ -366,6 +367,8 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
 // pt_render_indirect -- paths of 16 bounces, K = 1 light sample at every vertex -- written to indirectIllumination_<version>.ppm.
 // With --mis it is pt_render_indirect_mis -- the same paths with multiple importance sampling, the light counts made by
 // pt_light_counts -- written to indirectIllumination_<version>_mis.ppm.
+// With --lights power either case chooses its lights in proportion to their emitted power (pt_render_direct_power,
+// pt_render_indirect_power, the table made by pt_light_table) and the file's name ends in _power.ppm (_mis_power.ppm with --mis).
 // bounces: 0 = DirectIllumination, otherwise IndirectIllumination at that depth.
 static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
 {
@@ -391,6 +394,8 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     Buffer<Material> mBuffer(m_d, materials.size());
     Buffer<int> lBuffer(m_d, lights.size() ? lights.size() : 1);
     Buffer<int> cBuffer(m_d, triangles.size() ? triangles.size() : 1);   // (--mis) list entries per triangle
+    Buffer<unsigned long long> cdf(m_d, pt_light_table_bytes((int)lights.size()) / 8);   // (--lights power) the selection table
+    Buffer<unsigned int> triq(m_d, triangles.size() ? triangles.size() : 1);
     Buffer<float> samples(m_d, 3 * npix * (size_t)chunk);
     Buffer<float4_t> image(m_d, npix);
     Buffer<int> rgb(m_d, 3 * npix);
@@ -416,7 +421,18 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     q.max_bounces = bounces;
     auto t0 = std::chrono::steady_clock::now();
     const bool mis = bounces && o.mis;
-    if (mis) {
+    pt_buffer_t lh = lights.empty() ? 0 : lBuffer.m_handle;
+    if (o.power) {
+        IASSERT(pt_light_table(m_d->m_handle, tBuffer.m_handle, p.num_triangles, mBuffer.m_handle, p.num_materials, lh, p.num_lights, cdf.m_handle,
+                               triq.m_handle, 0) == PT_OK);
+        if (mis) IASSERT(pt_light_counts(m_d->m_handle, lh, p.num_lights, p.num_triangles, cBuffer.m_handle, 0) == PT_OK);
+        if (bounces)
+            IASSERT(pt_render_indirect_power(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0, cdf.m_handle,
+                                             triq.m_handle, samples.m_handle, image.m_handle, &q, 0, 0) == PT_OK);
+        else
+            IASSERT(pt_render_direct_power(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cdf.m_handle, triq.m_handle, samples.m_handle,
+                                           image.m_handle, &p, 0, 0) == PT_OK);
+    } else if (mis) {
         IASSERT(pt_light_counts(m_d->m_handle, lights.empty() ? 0 : lBuffer.m_handle, (int)lights.size(), (int)triangles.size(), cBuffer.m_handle, 0) == PT_OK);
         IASSERT(pt_render_indirect_mis(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lights.empty() ? 0 : lBuffer.m_handle, cBuffer.m_handle,
                                        samples.m_handle, image.m_handle, &q, 0, 0) == PT_OK);
@@ -432,13 +448,15 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     DeviceUtils::waitForCompletion(m_d);
     double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (bounces)
-        std::printf("IndirectIllumination%s: %d x %d x %d frames, %d bounces, K = 1, %d lights in %.3f s\n", mis ? " (MIS)" : "", dimension, dimension,
-                    o.frames, bounces, (int)lights.size(), secs);
+        std::printf("IndirectIllumination%s%s: %d x %d x %d frames, %d bounces, K = 1, %d lights in %.3f s\n", mis ? " (MIS)" : "",
+                    o.power ? " (lights by power)" : "", dimension, dimension, o.frames, bounces, (int)lights.size(), secs);
     else
-        std::printf("DirectIllumination: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", dimension, dimension, o.frames, (int)lights.size(), secs);
+        std::printf("DirectIllumination%s: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", o.power ? " (lights by power)" : "", dimension, dimension,
+                    o.frames, (int)lights.size(), secs);
     char path[512];
     f.getFilePath(o.outDir.c_str(), bounces ? "indirectIllumination" : "directIllumination", "ppm", path, sizeof path);
     if (mis && std::strlen(path) + 5 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_mis.ppm");
+    if (o.power && std::strlen(path) + 7 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_power.ppm");
     FILE* fp = std::fopen(path, "w");
     IASSERT(fp != 0);
     if (fp) {
@@ -464,6 +482,11 @@ int main(int argc, char** argv)
         else if (a == "--only") o.only = next();
         else if (a == "--no-batch") o.batch = false;
         else if (a == "--mis") o.mis = true;
+        else if (a == "--lights") {
+            const std::string v = next();
+            if (v != "uniform" && v != "power") { std::fprintf(stderr, "--lights takes uniform or power\n"); return 2; }
+            o.power = v == "power";
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (o.dim < 1 || o.frames < 0) { std::fprintf(stderr, "bad --dim/--frames\n"); return 2; }

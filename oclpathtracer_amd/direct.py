@@ -5,6 +5,9 @@ A sample of a pixel traces the renderer's primary ray; a miss is the background.
 the surface and ``light_samples`` (K) points on the scene's emitters: a light triangle chosen uniformly from the light list, a
 point chosen uniformly on it, the BRDF value towards it, the geometry term, and a shadow ray that an any-hit search finds occluded
 or open.  The result is the renderer's framebuffer -- with no lights it is the renderer's image at ``max_bounces=1`` bit for bit.
+``light_choice="power"`` chooses the light triangle in proportion to the power it emits instead (``pt_render_direct_power``, through a
+table built once on the device by ``pt_light_table``): the same expectation, and far less noise where the emitters differ in size
+or brightness.
 ``include/pt_shim.h`` states every expression.  All compute is HIP in libptshim.so; nothing here has a CPU fallback.
 """
 from __future__ import annotations
@@ -39,14 +42,20 @@ class DirectRenderer:
     ``triangles`` / ``materials``: ``scene.TRIANGLE_DTYPE`` / ``scene.MATERIAL_DTYPE`` arrays (uploaded to buffers of this
     renderer's), or ``adl.Buffer``s that already hold them -- a renderer's own (``Renderer.direct_renderer``), so that both share
     one prepared scene and one LBVH (``num_triangles`` / ``num_materials`` then say how many records count, and ``lights`` must
-    be given).  ``lights``: the triangle indices light samples are drawn from, each with the same probability (None:
-    ``scene.emitters``); an empty list leaves the emitted light alone.  ``chunk_frames`` sizes the sample workspace: that many
+    be given).  ``lights``: the triangle indices light samples are drawn from (None: ``scene.emitters``); an empty list leaves the
+    emitted light alone.  ``light_choice``: ``"uniform"`` -- every entry of the list with the same probability -- or ``"power"`` --
+    in proportion to area x emission; the renderer then owns the selection table.  ``chunk_frames`` sizes the sample workspace: that many
     frames are traced by one launch and folded by the next.  ``stripe_rows`` / ``n_ranks`` / ``rank`` select the rows this device
     owns, as for ``Renderer``.  The search follows the device's options exactly as renders do."""
 
     def __init__(self, dev: adl.Device, triangles, materials, width: int, height: int, *, light_samples: int = 1, lights=None,
                  camera: Optional[Camera] = None, num_triangles: Optional[int] = None, num_materials: Optional[int] = None,
-                 stripe_rows: int = 16, n_ranks: int = 1, rank: int = 0, chunk_frames: Optional[int] = None):
+                 stripe_rows: int = 16, n_ranks: int = 1, rank: int = 0, chunk_frames: Optional[int] = None,
+                 light_choice: str = "uniform"):
+        if light_choice not in ("uniform", "power"):
+            raise ValueError('light_choice must be "uniform" or "power"')
+        self.light_choice = light_choice
+        self.cdf = self.tri_q = None
         self.dev = dev
         self._lib = shim.load()
         self.width, self.height = int(width), int(height)
@@ -103,6 +112,20 @@ class DirectRenderer:
         self.samples = adl.Buffer(dev, 3 * n * self.chunk_frames, np.float32)
         self.fb = adl.Buffer(dev, n, adl.float4)
         self.frames_done = 0
+        if self.light_choice == "power":
+            try:
+                self._build_table()
+            except Exception:
+                self.release()
+                raise
+
+    def _build_table(self) -> None:
+        """the selection table of the list, built once on the device (pt_light_table) into buffers of this renderer's"""
+        nl = len(self.lights)
+        self.cdf = adl.Buffer(self.dev, self._lib.pt_light_table_bytes(nl) // 8, np.uint64)
+        self.tri_q = adl.Buffer(self.dev, max(self.num_triangles, 1), np.uint32)
+        shim.check(self._lib.pt_light_table(self.dev._h, self.tbuf._h, self.num_triangles, self.mbuf._h, self.num_materials,
+                                            self.lbuf._h if nl else None, nl, self.cdf._h, self.tri_q._h, None))
 
     def _set_camera(self, camera: Optional[Camera]) -> None:
         self._cam = Camera.struct_of(camera)   # rejected here, before anything is enqueued
@@ -139,6 +162,11 @@ class DirectRenderer:
 
     def _call(self, p, sync) -> int:
         """the entry point's return code (a renderer with another argument list overrides this)"""
+        if self.light_choice == "power":
+            return self._lib.pt_render_direct_power(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
+                                                    self.cdf._h, self.tri_q._h, self.samples._h, self.fb._h, ctypes.byref(p),
+                                                    ctypes.byref(self._cam) if self._cam is not None else None,
+                                                    sync._h if sync is not None else None)
         return getattr(self._lib, self._ENTRY)(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
                                                self.samples._h, self.fb._h, ctypes.byref(p),
                                                ctypes.byref(self._cam) if self._cam is not None else None,
@@ -153,9 +181,10 @@ class DirectRenderer:
         return out
 
     def release(self) -> None:
-        for b in (self.lbuf, self.samples, self.fb):
+        for b in (self.lbuf, self.samples, self.fb, self.cdf, self.tri_q):
             if b is not None:
                 b.release()
+        self.cdf = self.tri_q = None
         if self._own_tbuf and self.tbuf is not None:
             self.tbuf.release()
         if self._own_mbuf and self.mbuf is not None:

@@ -15,6 +15,9 @@ sample (DESIGN.md S4 has the measured ratios and rates).  The weights use the nu
 renderer counts once on the device (``pt_light_counts``) into a buffer it owns; they make the image robust to a duplicated,
 unsorted or incomplete list at every vertex but the path's last.  Both identities above hold with ``mis=True`` as well.
 
+``light_choice="power"`` chooses the light of every light sample in proportion to its emitted power, as for ``DirectRenderer``
+(``pt_render_indirect_power``; with ``mis=True`` the weights use the table's probabilities).  Both identities hold with it as well.
+
 ``include/pt_shim.h`` states every step.  All compute is HIP in libptshim.so.
 """
 from __future__ import annotations
@@ -57,6 +60,12 @@ class IndirectRenderer(DirectRenderer):
         return p
 
     def _call(self, p, sync) -> int:
+        if self.light_choice == "power":
+            return self._lib.pt_render_indirect_power(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
+                                                      int(self.mis), self.counts._h if self.mis else None, self.cdf._h, self.tri_q._h,
+                                                      self.samples._h, self.fb._h, ctypes.byref(p),
+                                                      ctypes.byref(self._cam) if self._cam is not None else None,
+                                                      sync._h if sync is not None else None)
         if not self.mis:
             return super()._call(p, sync)
         return self._lib.pt_render_indirect_mis(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,

@@ -197,6 +197,10 @@ SIGNATURES = {
     "pt_render_indirect": (_c.c_int, [_H, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Camera), _H]),
     "pt_light_counts": (_c.c_int, [_H, _H, _c.c_int, _c.c_int, _H, _H]),
     "pt_render_indirect_mis": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Camera), _H]),
+    "pt_light_table_bytes": (_c.c_size_t, [_c.c_int]),
+    "pt_light_table": (_c.c_int, [_H, _H, _c.c_int, _H, _c.c_int, _H, _c.c_int, _H, _H, _H]),
+    "pt_render_direct_power": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(DirectParams), _c.POINTER(Camera), _H]),
+    "pt_render_indirect_power": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Camera), _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_bvh_snapshot": (_c.c_int, [_H, _c.POINTER(BvhInfo), _c.c_void_p, _c.c_size_t, _c.c_void_p]),

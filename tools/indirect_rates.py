@@ -7,7 +7,9 @@ pt_render_frames at the same size and depth in the same process.  Each leg is wa
 own shape (scene preparation, code objects), then run ONCE: a host clock around the enqueue and the device synchronise that ends
 it.  The sample workspace holds all 16 frames, so an indirect render is one launch and one fold.
 The K = 0 figure against the renderer's is what the brute-force kernel's missing lane regeneration costs.
-usage: python tools/indirect_rates.py [out.txt]"""
+With --lights power the legs are those of light choice by power instead: K = 1 and K = 4, plain and MIS, each with the uniform choice
+and with the choice by power (pt_render_indirect_power) -- the same warm-up and single timed run per leg.
+usage: python tools/indirect_rates.py [--lights power] [out.txt]"""
 import os
 import sys
 import time
@@ -20,6 +22,11 @@ from oclpathtracer_amd import adl, scene, shim  # noqa: E402
 from oclpathtracer_amd.indirect import IndirectRenderer  # noqa: E402
 from oclpathtracer_amd.render import Renderer  # noqa: E402
 
+power = "--lights" in sys.argv
+if power:
+    at = sys.argv.index("--lights")
+    assert sys.argv[at + 1: at + 2] == ["power"], "--lights takes power"
+    del sys.argv[at: at + 2]
 out_path = sys.argv[1] if len(sys.argv) > 1 else None
 W = H = 1024
 FRAMES, B = 16, 16
@@ -57,6 +64,21 @@ try:
         base = report("pt_render_frames", once(dev, lambda: r.render(FRAMES, frame_begin=0, max_bounces=B)))
     finally:
         r.release()
+    if power:
+        for K in (1, 4):
+            for mis in (False, True):
+                uniform = None
+                for choice in ("uniform", "power"):
+                    ir = IndirectRenderer(dev, tris, mats, W, H, light_samples=K, max_bounces=B, stripe_rows=1, chunk_frames=FRAMES, mis=mis, light_choice=choice)
+                    try:
+                        entry = "pt_render_indirect_power mis = %d" % mis if choice == "power" else "pt_render_indirect_mis" if mis else "pt_render_indirect"
+                        rate = report("%s K = %d" % (entry, K), once(dev, lambda: ir.render(FRAMES, 0)))
+                        if choice == "power":
+                            emit("%-44s %9.3f of the uniform choice's rate at the same K and estimator" % ("", rate / uniform))
+                        uniform = rate
+                    finally:
+                        ir.release()
+        sys.exit(0)
     plain = {}
     for name, K, lights, mis, accel in (("pt_render_indirect K = 0 (no lights)", 1, np.zeros(0, np.int32), False, 0),
                                         ("pt_render_indirect K = 1", 1, None, False, 0), ("pt_render_indirect_mis K = 1", 1, None, True, 0),
