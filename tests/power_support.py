@@ -1,6 +1,7 @@
-"""What tests/test_gpu_power.py needs beside gpu_support: the raw C-ABI harness of pt_render_direct_power and pt_render_indirect_power
-(gpu_support.LitBuffers with the table's two buffers and the new argument lists), a raw pt_light_table call, and one render through the
-Python renderers with ``light_choice="power"``.  TEST INFRASTRUCTURE (an ordinary module: every assert carries its message)."""
+"""What tests/test_gpu_power.py and tests/test_gpu_light_scale.py need beside gpu_support: the raw C-ABI harness of
+pt_render_direct_power and pt_render_indirect_power (gpu_support.LitBuffers with the table's two buffers and the new argument lists), a
+raw pt_light_table call with its comparison against the restatement, and one render through the Python renderers with
+``light_choice="power"``.  TEST INFRASTRUCTURE (an ordinary module: every assert carries its message)."""
 import ctypes
 
 import numpy as np
@@ -49,6 +50,17 @@ def device_table(device, tris, mats, lights, num_triangles=None, tables=None):
     finally:
         for b in (tb, mb, lb) + (() if tables else (qb, tq)):
             b.release()
+
+
+def assert_table(device, tris, mats, lights, what, want=None, **kw):
+    """pt_light_table of the list (``device_table``) is the restatement's, cdf[0 .. nl] and tri_q bit for bit.  want: the restatement's
+    (cdf, tri_q) where the caller has it already.  Returns the device's pair."""
+    rc, cdf, tri_q = device_table(device, tris, mats, lights, **kw)
+    assert rc == shim.PT_OK, what
+    want_cdf, want_q = po.table(tris, mats, lights) if want is None else want
+    assert np.array_equal(cdf, want_cdf), "%s: cdf differs first at %s" % (what, np.flatnonzero(cdf != want_cdf)[:4])
+    assert np.array_equal(tri_q, want_q), "%s: tri_q differs at %s" % (what, np.flatnonzero(tri_q != want_q)[:4])
+    return cdf, tri_q
 
 
 class PowerBuffers(LitBuffers):

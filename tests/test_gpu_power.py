@@ -4,7 +4,8 @@ The table -- cdf[0 .. nl] and tri_q -- is compared with tests/power_oracle.c for
 Every render of tests/power_cases.py -- at most 40 x 24 x 3 frames per call -- is compared twice with the restatement, NaN masks equal:
 the sample workspace with the radiance before the fold, and the framebuffer.  tests/test_power_cpu.py proves, on these very inputs, that
 q = 1 entries, the first and the last entry and an entry behind a q = 0 one are chosen, that the empty table is met and that the MIS
-estimator's later hits read tri_q at counts of 1 and 2.  The identities need no restatement."""
+estimator's later hits read tri_q at counts of 1 and 2.  The identities need no restatement.  Lists of more than 70 020 entries, totals
+from 2^32 on and the numeric domain of the powers are tests/test_gpu_light_scale.py's."""
 import numpy as np
 import pytest
 
@@ -15,7 +16,7 @@ from conftest import assert_fb_equal
 from gpu_support import SEARCHES, assert_lit_argument_errors, harness_ppm, lit_with_samples, options, render
 from indirect_edges import clamped_raw
 from oclpathtracer_amd import scene, shim
-from power_support import PowerBuffers, device_table, power_with_samples
+from power_support import PowerBuffers, assert_table as _assert_table, power_with_samples
 from scenes import edge_scene
 
 pytestmark = pytest.mark.gpu
@@ -27,14 +28,6 @@ BLOCK, TILE = 256, 2048   # csrc/pt_kernels.h: PT_LIGHT_SCAN_BLOCK, PT_LIGHT_SCA
 
 
 # ---- the table -------------------------------------------------------------------------------------------------------------------
-def _assert_table(device, tris, mats, lights, what, **kw):
-    rc, cdf, tri_q = device_table(device, tris, mats, lights, **kw)
-    assert rc == shim.PT_OK, what
-    want_cdf, want_q = po.table(tris, mats, lights)
-    assert np.array_equal(cdf, want_cdf), "%s: cdf differs first at %s" % (what, np.flatnonzero(cdf != want_cdf)[:4])
-    assert np.array_equal(tri_q, want_q), "%s: tri_q differs at %s" % (what, np.flatnonzero(tri_q != want_q)[:4])
-
-
 def test_table_of_the_scenes_lists(device, cornell):
     tris, mats = cornell
     _assert_table(device, tris, mats, scene.emitters(tris, mats), "the Cornell emitters")

@@ -1,6 +1,9 @@
 """Light choice by power on the CPU: the restatement (tests/power_oracle.c) against hand-made tables, against its parents where
-they must agree, on the edges the GPU module renders, and as an estimator -- unbiased against the uniform choice, and with the variance
-gain DESIGN.md S4 states.  No GPU."""
+they must agree, on the edges the GPU modules render, and as an estimator -- unbiased against the uniform choice, and with the variance
+gain DESIGN.md S4 states.  The inputs of tests/test_gpu_light_scale.py are proved here to be what they are for: lists of 524 289 and
+2^24 - 1 entries whose table passes 2^32 inside a tile, has 257 tiles, and is read by the renders at entries above 2^16 and 2^23 and
+at counts above 2^15; and power_scenes.power_sweep, whose quanta are checked against numpy's float32 arithmetic and whose q = 0 entries
+against causes found in float64 from the scene alone.  No GPU."""
 import numpy as np
 import pytest
 
@@ -136,6 +139,186 @@ def test_every_gpu_input_is_finite():
     for mode in pc.MODES:
         for name in pc.BIG:
             assert not np.isnan(pc.wanted(mode, name, None, W, H, FRAMES, *pc.BIG_KB)[1]).any()
+
+
+# ---- reachability: the long lists (tests/test_gpu_light_scale.py renders them) ---------------------------------------------------
+TILE = 2048   # csrc/pt_kernels.h: PT_LIGHT_SCAN_TILE
+LW, LH = pc.W, pc.H
+# measured at 40 x 24, K 4, B 4 on "long" (3 frames): light samples whose entry has cdf[entry] >= 2^32: 4597 (direct) / 12783 / 12783,
+# whose entry is >= 2^16: 7241 / 20048 / 20048, whose entry follows a q = 0 one: 103 / 249 / 249.  On "max" (2 frames): entries >= 2^23:
+# 2788 / 7613 / 7613; on "panels": 2788 / 7612 / 7612.  The floors are half of that.
+_LONG_FLOORS = {po.DIRECT: (2298, 3620, 51), po.INDIRECT: (6391, 10024, 124), po.MIS: (6391, 10024, 124)}
+_MAX_FLOORS = {po.DIRECT: 1394, po.INDIRECT: 3806, po.MIS: 3806}
+
+
+def test_the_long_list_passes_two_to_the_32_inside_a_tile():
+    """total 9 692 185 602, which binary32 cannot hold; 257 tiles; the running sum passes 2^32 at entry 232 375, the 952nd of its tile;
+    143 tiles start at or above 2^32 (the floor: half)"""
+    cdf, tri_q, counts = pc.table_of("unequal", "long")
+    total = int(cdf[-1])
+    assert len(cdf) == ps.LONG + 1 and total >= 1 << 32 and int(np.float32(total)) != total
+    offsets = cdf[:-1:TILE]                                           # what pt_light_tiles_kernel leaves in tile_sums
+    assert len(offsets) == 257
+    first = int(np.searchsorted(cdf, 1 << 32)) - 1                    # the entry whose q carries the sum over 2^32
+    assert 0 < first % TILE < TILE - 1 and int(cdf[first]) < 1 << 32 < int(cdf[first + 1])
+    assert int((offsets >= 1 << 32).sum()) >= 71
+    qs = np.diff(cdf.astype(np.int64))
+    assert (qs == 0).any() and (qs == 1).any() and (qs == 65536).sum() > ps.LONG // 5 and int(counts.max()) >= 1 << 15
+
+
+@pytest.mark.parametrize("mode", pc.MODES, ids=[pc.MODE_NAMES[m] for m in pc.MODES])
+def test_the_long_list_is_read_above_two_to_the_32(mode):
+    """the choice reads cdf values of more than 32 bits, entries above 2^16 (a search of more than 16 levels) and entries behind a q = 0
+    one; the MIS estimator's later hits read counts of 75 354"""
+    (rad, entry, q, reason, later), li = pc.details(mode, "unequal", "long", LW, LH, pc.FRAMES, *pc.LONG_KB)
+    cdf = pc.table_of("unequal", "long")[0]
+    qs = np.diff(cdf.astype(np.int64))
+    chosen = entry[entry >= 0].astype(np.int64)
+    wide, far, behind = _LONG_FLOORS[mode]
+    assert (qs[chosen] > 0).all() and (q[entry >= 0] == qs[chosen]).all()
+    assert int((cdf[chosen] >= 1 << 32).sum()) >= wide and int((chosen >= 1 << 16).sum()) >= far
+    assert int((qs[chosen[chosen > 0] - 1] == 0).sum()) >= behind
+    assert not np.isnan(rad).any()
+    if mode == po.MIS:
+        assert int(later.max()) >= 1 << 15                            # (measured 75 354)
+    assert not np.isnan(pc.wanted_uniform(mode, "unequal", "long", LW, LH, pc.FRAMES, *pc.LONG_KB)[1]).any()
+
+
+@pytest.mark.parametrize("mode", pc.MODES, ids=[pc.MODE_NAMES[m] for m in pc.MODES])
+@pytest.mark.parametrize("name", ["max", "panels"])
+def test_the_longest_lists_are_read_above_two_to_the_23(mode, name):
+    (rad, entry, q, reason, later), li = pc.details(mode, "unequal", name, LW, LH, pc.MAX_FRAMES, *pc.LONG_KB)
+    assert len(li) == ps.MAX == (1 << 24) - 1
+    assert int((entry >= 1 << 23).sum()) >= _MAX_FLOORS[mode] and not np.isnan(rad).any()
+
+
+def test_the_all_panel_list_has_the_largest_total_the_abi_admits():
+    cdf = pc.table_of("unequal", "panels")[0]
+    assert int(cdf[-1]) == (1 << 40) - 65536 and (np.diff(cdf) == 65536).all()
+    assert ((1 << 24) - 1) * int(cdf[-1]) < 1 << 64                   # the largest u times the largest total: pt_light_table_inv's product
+    total = int(pc.table_of("unequal", "max")[0][-1])
+    assert total >= 1 << 32 and int(np.float32(total)) != total      # (310 454 888 398)
+
+
+# ---- reachability: the numeric domain of the table's powers and quanta (power_scenes.power_sweep) -------------------------------
+FLT_MAX, FLT_MIN, FLT_TRUE_MIN = float(np.finfo(np.float32).max), 2.0 ** -126, 2.0 ** -149
+
+
+def _f32_fma(a, b, c):
+    """fma on float32 arrays through float64: the product is exact there, the sum is rounded to 53 bits and then to 24 -- the fused
+    result except where the 53-bit sum falls on a tie of binary32, which none of these inputs does (the tables below would differ)"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def _sweep_power32(tris, mats):
+    """p_i of every triangle in numpy's float32 arithmetic: include/pt_shim.h's expressions, a second opinion on power_oracle.c"""
+    with np.errstate(all="ignore"):
+        p1, p2, p3 = (tris[k][:, :3] for k in ("p1", "p2", "p3"))
+        a, b = p3 - p1, p2 - p1                                       # N = cross(e2, e1)
+        N = [_f32_fma(a[:, i], b[:, j], -(a[:, j] * b[:, i])) for i, j in ((1, 2), (2, 0), (0, 1))]
+        n2 = _f32_fma(N[2], N[2], _f32_fma(N[1], N[1], N[0] * N[0]))
+        area = np.float32(0.5) * np.sqrt(n2)
+        em = mats["emissive"][np.clip(tris["id"], 0, len(mats) - 1)]
+        pw = area * ((em[:, 0] + em[:, 1]) + em[:, 2])
+        assert pw.dtype == np.float32
+        return np.where((pw > 0) & (pw < np.inf), pw, np.float32(0))
+
+
+def _sweep_tables():
+    tris, mats, lists = ps.power_sweep()
+    return {name: po.table(tris, mats, li) for name, li in lists.items()}
+
+
+def test_the_sweeps_quanta_are_numpys():
+    """every q of every list: floor(pw / pmax x 65536) in float32, at least 1 where pw > 0; and tri_q the q of the entries that name the
+    triangle"""
+    tris, mats, lists = ps.power_sweep()
+    pw32 = _sweep_power32(tris, mats)
+    for name, (cdf, tri_q) in _sweep_tables().items():
+        j = np.clip(lists[name], 0, len(tris) - 1)
+        p = pw32[j]
+        with np.errstate(all="ignore"):
+            q = np.floor((p / p.max()) * np.float32(65536.0)).astype(np.int64) if p.max() > 0 else np.zeros(len(p), np.int64)
+        q = np.where(p > 0, np.maximum(q, 1), 0)
+        assert np.array_equal(np.diff(cdf.astype(np.int64)), q), name
+        want = np.zeros(len(tris), np.int64)
+        want[j] = q
+        assert np.array_equal(tri_q, want), name
+
+
+def test_the_sweep_covers_the_quantum():
+    """over all lists: 3567 entries with 1 < q < 65536, 1601 distinct q, 599 entries whose q is a power of two other than 1 and 65536;
+    3126 q = 1 entries of positive power whose quotient pw / pmax is subnormal or zero; the list "subnormal" has
+    a subnormal pmax and 90 entries with 1 < q < 65536; "zeros" has 602 entries.  The floors: 2000, 500 and 32 as the scene was
+    specified; half the measured otherwise"""
+    tris, mats, lists = ps.power_sweep()
+    pw32 = _sweep_power32(tris, mats)
+    tables = _sweep_tables()
+    qs = np.concatenate([np.diff(cdf.astype(np.int64)) for cdf, _ in tables.values()])
+    mid = qs[(qs > 1) & (qs < 65536)]
+    print("1 < q < 65536:", len(mid), "distinct q:", len(np.unique(qs)), "powers of two:", int((mid & (mid - 1) == 0).sum()))
+    assert len(mid) >= 2000 and len(np.unique(qs)) >= 500 and int((mid & (mid - 1) == 0).sum()) >= 32
+    underflowed = 0
+    for name, (cdf, _) in tables.items():
+        p = pw32[np.clip(lists[name], 0, len(tris) - 1)]
+        with np.errstate(all="ignore"):
+            quotient = p / p.max() if p.max() > 0 else np.ones_like(p)
+        low = (p > 0) & (quotient < np.float32(FLT_MIN))
+        assert (np.diff(cdf.astype(np.int64))[low] == 1).all(), name
+        underflowed += int(low.sum())
+    print("q = 1 through a subnormal or zero quotient:", underflowed)
+    assert underflowed >= 1563
+    p = pw32[lists["subnormal"]]
+    q = np.diff(tables["subnormal"][0].astype(np.int64))
+    print("the subnormal list: pmax", p.max(), "1 < q < 65536:", int(((q > 1) & (q < 65536)).sum()))
+    assert 0 < p.max() < np.float32(FLT_MIN) and int(((q > 1) & (q < 65536)).sum()) >= 45
+    assert pw32[np.clip(lists["floor"], 0, len(tris) - 1)].max() > 2.0 ** 120
+    assert (np.diff(tables["zeros"][0]) == 0).all() and int(tables["zeros"][0][-1]) == 0 and len(lists["zeros"]) >= 301
+    assert lists["all"].min() < 0 and lists["all"].max() >= len(tris) and set(range(len(tris))) <= set(np.clip(lists["all"], 0, len(tris) - 1).tolist())
+
+
+# measured: the triangles named by some list whose q is 0 there for each cause, found in float64 from the scene alone.  The floors: half
+# (measured: 45, 60, 49, 144, 47, 32, 60, 214)
+_CAUSES = {"nan": 22, "infinity": 30, "overflowed sum": 24, "overflowed area": 72, "negative sum": 23, "zero area": 16, "zero emission": 30,
+           "underflowed area": 107}
+
+
+def _sweep_causes(tris, mats):
+    """{cause: bool [ntri]}: why a triangle has no positive finite power, from the records in float64 -- nothing of the restatement"""
+    em = mats["emissive"][np.clip(tris["id"], 0, len(mats) - 1), :3].astype(np.float64)
+    p1, p2, p3 = (tris[k][:, :3].astype(np.float64) for k in ("p1", "p2", "p3"))
+    with np.errstate(all="ignore"):
+        n2 = (np.cross(p3 - p1, p2 - p1) ** 2).sum(axis=1)
+        s = em.sum(axis=1)
+    finite = np.isfinite(em).all(axis=1)
+    lit = finite & (s > 0) & (s <= FLT_MAX)                          # a positive finite emission sum (exact in float64)
+    return {"nan": np.isnan(em).any(axis=1), "infinity": np.isinf(em).any(axis=1) & ~np.isnan(em).any(axis=1),
+            "overflowed sum": finite & (s > 1.5 * FLT_MAX), "negative sum": finite & (s < 0), "zero emission": (em == 0).all(axis=1),
+            "zero area": lit & (n2 == 0), "overflowed area": lit & (n2 > 4 * FLT_MAX),
+            "underflowed area": lit & (n2 > 0) & (n2 < FLT_TRUE_MIN / 4)}, n2
+
+
+def test_the_sweep_reaches_every_cause_of_q_zero_and_both_ends_of_the_square_roots_window():
+    """triangles without power, by cause (float64, from the scene alone): NaN 45, infinity 60, an overflowed sum 49, an overflowed area
+    144, a negative sum 47, no area 32, no emission 60, an underflowed area 214 -- the restatement gives each q = 0, and 3348 others a
+    q > 0; dot(N, N) within a factor 4 below / above 1e-30: 17 / 31, of 1e30: 20 / 10, subnormal: 286.  The floors are half of that"""
+    tris, mats, lists = ps.power_sweep()
+    causes, n2 = _sweep_causes(tris, mats)
+    tri_q = _sweep_tables()["all"][1]                                # every triangle is named by "all"
+    for name, floor in _CAUSES.items():
+        print(name, int(causes[name].sum()))
+        assert int(causes[name].sum()) >= floor, name
+        assert (tri_q[causes[name]] == 0).all(), name
+    assert int((tri_q > 0).sum()) >= 2000                            # (measured 3348) and the rest has a power
+    # dot(N, N) within a factor 4 below and above each end of pt_sqrt's window, and in the subnormals: measured 17, 31, 20, 10 and 286
+    near = [int(((n2 >= lo) & (n2 < hi)).sum()) for lo, hi in ((0.25e-30, 1e-30), (1e-30, 4e-30), (0.25e30, 1e30), (1e30, 4e30),
+                                                                 (FLT_TRUE_MIN, FLT_MIN))]
+    print("dot(N, N) about 1e-30, about 1e30, subnormal:", near)
+    assert all(n >= f for n, f in zip(near, (8, 15, 10, 5, 143))), near
+    ids = tris["id"]
+    assert (ids < 0).sum() >= 32 and (ids >= len(mats)).sum() >= 32   # material indices clamped at both ends
+    flat = np.arange(len(tris)) % 2 == 0
+    assert (tris["p1"][flat, :3] == 0).all() and (np.abs(tris["p1"][~flat, :3]) > 0).all()
 
 
 # ---- the estimator -----------------------------------------------------------------------------------------------------------------
