@@ -637,6 +637,60 @@ int pt_render_indirect_power(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t
                              pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam /* NULL = the reference's */,
                              pt_event_t ev);
 
+/* ---- sample moments: per-pixel noise estimates of the lit renders -----------------------------------------------------------
+ * Every lit entry point (pt_render_direct, pt_render_indirect and their _mis / _power forms) leaves each sample's linear radiance in
+ * the caller's workspace, samples[frame - call's first][local pixel][3], before the fold.  These calls take the first and second
+ * moments per pixel from that workspace on the device, and from the moments a per-pixel variance map and an image-wide noise figure
+ * that is read back in 48 bytes.  No reference counterpart; no existing kernel, entry point or image changes.  The workspace holds
+ * the frames of the LAST chunk of a render call (pt_render_direct step 5), so a caller who wants every frame counted renders at most as
+ * many frames per call as the workspace holds and calls pt_sample_moments after each.
+ *
+ * pt_sample_moments, per pixel p of num_pixels (one lane per pixel; the frames are NOT split over lanes and merged):
+ *  1. with reset != 0 the record starts from zeros and the buffer's old contents are not read; otherwise from moments[p];
+ *  2. for f = 0 .. frame_count - 1 IN ASCENDING ORDER, with (x, y, z) = samples[f][p][0..2] (binary32):
+ *     - all three finite: n = n + 1; per channel v: sum = sum + (double)v and sum2 = sum2 + (double)v * (double)v, each operation
+ *       rounded on its own in binary64 (the product of two converted binary32 values is exact in binary64, so contraction could not
+ *       change it);
+ *     - otherwise (a NaN or an infinity in any channel): rejected = rejected + 1 and nothing else changes;
+ *  3. the record is written back.  n and rejected wrap modulo 2^32.
+ * The order over the frames is part of the contract: the sums equal a sequential restatement bit for bit, and two calls of a and b
+ * frames equal one call of a + b frames.  Sums, not Welford's recurrence: sums of different calls, chunks or ranks merge exactly (add
+ * them) and need no division per sample.  The price: pt_moments_resolve forms sum2 - sum * mean, which cancels when a pixel's variance
+ * lies below about n * 2^-53 of its squared mean; such a pixel resolves to a variance of 0, or to a rounding residue of that size where
+ * the difference happens to come out positive -- never to a negative one.
+ *
+ * pt_moments_resolve, per pixel, in binary64 with every operation rounded on its own (no contraction) and the IEEE "/":
+ *  1. per channel: m = n > 0 ? sum / (double)n : 0;  with n >= 2: t = sum * m; d = sum2 - t; v = d / (double)(n - 1); v = v > 0 ? v : +0
+ *     (the unbiased sample variance);  with n < 2: v = 0;
+ *  2. noise (may be NULL): struct { float var[3]; uint32_t n; }[num_pixels], 16 bytes each: var = (float)v, rounded once;
+ *  3. summary (may be NULL): the caller's buffer of pt_moments_summary_bytes(num_pixels) bytes.  Its first 48 bytes receive a
+ *     pt_noise_summary; what lies behind them is the build's scratch and unspecified (nothing is allocated: pt_light_table's pattern).
+ *     A pixel with n >= 2 contributes a = (v.x + v.y) + v.z to var_sum, b = ((v.x / n) + (v.y / n)) + (v.z / n) to se2_sum (the squared
+ *     standard error of its mean), c = ((m.x * m.x) + (m.y * m.y)) + (m.z * m.z) to mean2_sum and 1 to pixels; every other pixel
+ *     contributes +0 and is not counted.  samples and rejected sum n and rejected over ALL pixels (uint64).
+ *     The three floating sums are taken by a FIXED TREE, so that the device's order is specified and a restatement can follow it: the
+ *     per-pixel values are padded with +0 to the next power of two, and each level is x'[i] = x[2 i] + x[2 i + 1] until one value is
+ *     left.  (The device reduces tiles of 2 048 pixels by adjacent-pair butterflies and runs the same kernel on the tile sums: exactly
+ *     this tree -- every contribution is >= +0, so further padding with +0 changes nothing.  Three launches cover 2^32 - 1 pixels.)
+ * From the summary: the mean variance per sample and channel is var_sum / (3 pixels); sqrt(se2_sum / mean2_sum) is the image's
+ * relative standard error, the figure a progressive render stops on.
+ *
+ * Behaviour of both calls is pt_light_counts': the handle's stream, behind renders in flight, asynchronous (ev); nothing is
+ * allocated and the host waits for nothing; the version of each buffer written is bumped.  frame_count = 0 or num_pixels = 0 runs no
+ * kernel and touches no buffer, whatever reset says.
+ * Errors, before anything is enqueued: PT_ERR_INVALID for a NULL handle (noise and summary may be NULL), a negative frame_count,
+ * moments or summary not 8-byte aligned, noise not 16-byte aligned, samples not 4-byte aligned, any two of the buffers overlapping, a
+ * buffer of another device; PT_ERR_RANGE for a buffer too small (samples: frame_count x num_pixels x 12 bytes; moments: num_pixels x
+ * 56; noise: num_pixels x 16; summary: pt_moments_summary_bytes(num_pixels)). */
+typedef struct pt_pixel_moments { double sum[3]; double sum2[3]; uint32_t n; uint32_t rejected; } pt_pixel_moments;   /* 56 bytes */
+typedef struct pt_noise_summary { double var_sum, se2_sum, mean2_sum; uint64_t pixels, samples, rejected; } pt_noise_summary;   /* 48 bytes */
+int pt_sample_moments(pt_device_t dev, pt_buffer_t samples /* float[frame_count][num_pixels][3] */,
+                      pt_buffer_t moments /* pt_pixel_moments[num_pixels] */, uint32_t num_pixels, int32_t frame_count, int reset,
+                      pt_event_t ev);
+size_t pt_moments_summary_bytes(uint32_t num_pixels);
+int pt_moments_resolve(pt_device_t dev, pt_buffer_t moments /* pt_pixel_moments[num_pixels] */, uint32_t num_pixels,
+                       pt_buffer_t noise /* may be NULL */, pt_buffer_t summary /* may be NULL */, pt_event_t ev);
+
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.
  * pt_profile_query synchronises the stream and returns the summed duration and launch count

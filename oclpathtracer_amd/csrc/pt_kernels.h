@@ -339,6 +339,25 @@ int ptk_indirect_power_bvh_blocks_per_cu(bool mis);
 #define PT_LIGHT_TABLE_WORDS(nl) ((size_t)(nl) + 2 + PT_LIGHT_TABLE_TILES(nl))
 hipError_t ptk_light_table(const PtRawTriangle* tris, int ntri, const PtRawMaterial* mats, int nmat, const int32_t* lights, int nl,
                            uint64_t* cdf, uint32_t* tri_q, hipStream_t s);
+// sample moments (pt_sample_moments, pt_moments_resolve): the records of include/pt_shim.h
+struct PtPixelMoments {           // pt_pixel_moments, 56 bytes
+    double sum[3], sum2[3];
+    uint32_t n, rejected;
+};
+struct PtNoiseSummary {           // pt_noise_summary, 48 bytes
+    double var_sum, se2_sum, mean2_sum;
+    uint64_t pixels, samples, rejected;
+};
+#define PT_MOMENTS_UNROLL 8       // frames whose loads the accumulate kernel keeps in flight
+#define PT_MOMENTS_TILE 2048      // elements a workgroup of the resolve kernel reduces: 2048^3 >= 2^32, three levels at the most
+#define PT_MOMENTS_TILES(n) (((size_t)(n) + PT_MOMENTS_TILE - 1) / PT_MOMENTS_TILE)
+// the summary buffer: record 0 the result, then the sums of level 0's tiles, then those of level 1's (the third level is one tile)
+#define PT_MOMENTS_SUMMARY_RECORDS(n) ((size_t)1 + PT_MOMENTS_TILES(n) + PT_MOMENTS_TILES(PT_MOMENTS_TILES(n)))
+// moments[p] (from zeros when reset) takes samples[f][p][0..2], f = 0 .. frames - 1 ascending; one lane per pixel, one launch
+hipError_t ptk_sample_moments(const float* samples, PtPixelMoments* moments, uint32_t npix, int32_t frames, bool reset, hipStream_t s);
+// noise (may be NULL): {float var[3]; uint32 n}[npix]; summary (may be NULL): PT_MOMENTS_SUMMARY_RECORDS(npix) records, the result in
+// record 0.  One launch per level of 2048-element tiles
+hipError_t ptk_moments_resolve(const PtPixelMoments* moments, uint32_t npix, void* noise, PtNoiseSummary* summary, hipStream_t s);
 // rays[2 gid], rays[2 gid + 1] = the pt_ray of pixel gid, frame `frame` (the renderer's sample start) for the camera cam
 hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s);
 // dynamic LDS of a trace workgroup (pt_kernels.hip: pt_lds_total, pt_bvh_lds_total)

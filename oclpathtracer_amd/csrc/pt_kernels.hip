@@ -3706,6 +3706,156 @@ void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER> I)
     pt_bvh_drive<DET_BOUNDED, BIGQ>(I.d.t, W);
 }
 
+// ---- sample moments (pt_sample_moments, pt_moments_resolve; include/pt_shim.h states every step) ----
+// pt_sample_moments_kernel: one lane per pixel, so that the pixel's sums are taken over the frames in ascending order by one lane and
+// equal a sequential restatement bit for bit.  Consecutive lanes read consecutive 12-byte records (768 contiguous bytes per wave and
+// frame).  A 256 x 256 image is four waves per CU: the loads of PT_MOMENTS_UNROLL frames are issued before the first of them is
+// used, so that the kernel waits for memory once per eight frames, not once per frame.  The 56-byte record is read (unless reset) and
+// written once per call.
+PTK_DEV bool pt_moments_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+struct PtMomentsAcc {
+    double s0, s1, s2, q0, q1, q2;
+    uint32_t n, rejected;
+};
+
+// the product of two converted binary32 values is exact in binary64: contraction could not change q
+PTK_DEV void pt_moments_add(PtMomentsAcc& a, float x, float y, float z)
+{
+    if (pt_moments_finite(x) && pt_moments_finite(y) && pt_moments_finite(z)) {
+        const double dx = (double)x, dy = (double)y, dz = (double)z;
+        a.n += 1u;
+        a.s0 = a.s0 + dx;
+        a.s1 = a.s1 + dy;
+        a.s2 = a.s2 + dz;
+        a.q0 = a.q0 + dx * dx;
+        a.q1 = a.q1 + dy * dy;
+        a.q2 = a.q2 + dz * dz;
+    } else {
+        a.rejected += 1u;
+    }
+}
+
+__global__ __launch_bounds__(256) void pt_sample_moments_kernel(const float* __restrict__ samples, PtPixelMoments* __restrict__ moments,
+                                                                uint32_t npix, int32_t frames, int reset)
+{
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= npix) return;
+    PtMomentsAcc a = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0u, 0u };
+    if (!reset) {
+        const PtPixelMoments& m = moments[p];
+        a.s0 = m.sum[0], a.s1 = m.sum[1], a.s2 = m.sum[2];
+        a.q0 = m.sum2[0], a.q1 = m.sum2[1], a.q2 = m.sum2[2];
+        a.n = m.n, a.rejected = m.rejected;
+    }
+    const size_t stride = (size_t)npix * 3u;                 // floats per frame
+    const float* src = samples + (size_t)p * 3u;
+    int32_t f = 0;
+    for (; f + PT_MOMENTS_UNROLL <= frames; f += PT_MOMENTS_UNROLL) {
+        float v[PT_MOMENTS_UNROLL][3];
+#pragma unroll
+        for (int k = 0; k < PT_MOMENTS_UNROLL; ++k) {
+            const float* r = src + (size_t)k * stride;
+            v[k][0] = r[0], v[k][1] = r[1], v[k][2] = r[2];
+        }
+#pragma unroll
+        for (int k = 0; k < PT_MOMENTS_UNROLL; ++k) pt_moments_add(a, v[k][0], v[k][1], v[k][2]);
+        src += (size_t)PT_MOMENTS_UNROLL * stride;
+    }
+    for (; f < frames; ++f) {
+        pt_moments_add(a, src[0], src[1], src[2]);
+        src += stride;
+    }
+    PtPixelMoments& o = moments[p];
+    o.sum[0] = a.s0, o.sum[1] = a.s1, o.sum[2] = a.s2;
+    o.sum2[0] = a.q0, o.sum2[1] = a.q1, o.sum2[2] = a.q2;
+    o.n = a.n, o.rejected = a.rejected;
+}
+
+// pt_moments_resolve_kernel: a workgroup owns a tile of PT_MOMENTS_TILE consecutive elements and reduces it by adjacent-pair
+// butterflies -- eleven levels of x'[i] = x[2 i] + x[2 i + 1] over the tile padded with +0 --, which is the fixed tree of the contract
+// for the tile; the same kernel run on the tile sums continues the tree.  (A level's pair sum is formed in both lanes of the pair,
+// from the same two operands: IEEE addition commutes.)  Level 0 (moments != NULL) resolves the pixels' records -- and writes `noise`
+// when given --; later levels (in != NULL) read the sums of the level before.  The three counters are integers: any order.
+// out == NULL (noise only) reduces nothing.
+PTK_DEV double pt_moments_pair(double x, int lane_mask) { return x + __shfl_xor(x, lane_mask, 64); }
+PTK_DEV unsigned long long pt_moments_pair(unsigned long long x, int lane_mask) { return x + __shfl_xor(x, lane_mask, 64); }
+
+__global__ __launch_bounds__(256) void pt_moments_resolve_kernel(const PtPixelMoments* __restrict__ moments, const PtNoiseSummary* __restrict__ in,
+                                                                 uint32_t count, uint4* __restrict__ noise, PtNoiseSummary* __restrict__ out)
+{
+    constexpr unsigned ROUNDS = PT_MOMENTS_TILE / 256u, PARTS = PT_MOMENTS_TILE / 64u;   // 8 rounds of 256 elements; 32 wave sums
+    __shared__ double lds_f[3][PARTS];
+    __shared__ unsigned long long lds_u[3][PARTS];
+    const uint32_t tile = blockIdx.x * PT_MOMENTS_TILE;
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (unsigned r = 0; r < ROUNDS; ++r) {
+        const uint32_t i = tile + r * 256u + threadIdx.x;
+        double a = 0.0, b = 0.0, c = 0.0;
+        unsigned long long px = 0ull, ns = 0ull, rj = 0ull;
+        if (i < count) {
+            if (moments) {
+                const PtPixelMoments& m = moments[i];
+                const uint32_t n = m.n;
+                const double nd = (double)n;
+                double mean[3], var[3] = { 0.0, 0.0, 0.0 };
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    mean[ch] = n ? m.sum[ch] / nd : 0.0;
+                    if (n >= 2u) {
+                        const double t = m.sum[ch] * mean[ch];
+                        const double d = m.sum2[ch] - t;
+                        const double v = d / (double)(n - 1u);
+                        var[ch] = v > 0.0 ? v : 0.0;
+                    }
+                }
+                if (noise) noise[i] = make_uint4(__float_as_uint((float)var[0]), __float_as_uint((float)var[1]), __float_as_uint((float)var[2]), n);
+                if (n >= 2u) {
+                    a = (var[0] + var[1]) + var[2];
+                    b = ((var[0] / nd) + (var[1] / nd)) + (var[2] / nd);
+                    c = ((mean[0] * mean[0]) + (mean[1] * mean[1])) + (mean[2] * mean[2]);
+                    px = 1ull;
+                }
+                ns = n;
+                rj = m.rejected;
+            } else {
+                const PtNoiseSummary& s = in[i];
+                a = s.var_sum, b = s.se2_sum, c = s.mean2_sum;
+                px = s.pixels, ns = s.samples, rj = s.rejected;
+            }
+        }
+        if (!out) continue;
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+            a = pt_moments_pair(a, k), b = pt_moments_pair(b, k), c = pt_moments_pair(c, k);
+            px = pt_moments_pair(px, k), ns = pt_moments_pair(ns, k), rj = pt_moments_pair(rj, k);
+        }
+        if (lane == 0u) {
+            const unsigned part = r * 4u + wave;
+            lds_f[0][part] = a, lds_f[1][part] = b, lds_f[2][part] = c;
+            lds_u[0][part] = px, lds_u[1][part] = ns, lds_u[2][part] = rj;
+        }
+    }
+    if (!out) return;
+    __syncthreads();
+    if (wave != 0u) return;
+    // the 32 wave sums, padded with +0 to the wave: five more levels
+    const bool live = lane < PARTS;
+    double a = live ? lds_f[0][lane & (PARTS - 1u)] : 0.0, b = live ? lds_f[1][lane & (PARTS - 1u)] : 0.0, c = live ? lds_f[2][lane & (PARTS - 1u)] : 0.0;
+    unsigned long long px = live ? lds_u[0][lane & (PARTS - 1u)] : 0ull, ns = live ? lds_u[1][lane & (PARTS - 1u)] : 0ull,
+                       rj = live ? lds_u[2][lane & (PARTS - 1u)] : 0ull;
+#pragma unroll
+    for (int k = 1; k < (int)PARTS; k <<= 1) {
+        a = pt_moments_pair(a, k), b = pt_moments_pair(b, k), c = pt_moments_pair(c, k);
+        px = pt_moments_pair(px, k), ns = pt_moments_pair(ns, k), rj = pt_moments_pair(rj, k);
+    }
+    if (lane == 0u) {
+        PtNoiseSummary& o = out[blockIdx.x];
+        o.var_sum = a, o.se2_sum = b, o.mean2_sum = c;
+        o.pixels = px, o.samples = ns, o.rejected = rj;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------
@@ -3983,6 +4133,34 @@ hipError_t ptk_light_counts(const int32_t* lights, int nl, int ntri, int32_t* co
     if (e != hipSuccess || nl <= 0) return e;
     hipLaunchKernelGGL(pt_light_counts_kernel, dim3(((unsigned)nl + 255u) / 256u), dim3(256), 0, s, lights, nl, ntri, counts);
     return hipGetLastError();
+}
+
+hipError_t ptk_sample_moments(const float* samples, PtPixelMoments* moments, uint32_t npix, int32_t frames, bool reset, hipStream_t s)
+{
+    if (npix == 0u || frames <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pt_sample_moments_kernel, dim3((unsigned)(((uint64_t)npix + 255u) / 256u)), dim3(256), 0, s, samples, moments, npix, frames, reset ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t ptk_moments_resolve(const PtPixelMoments* moments, uint32_t npix, void* noise, PtNoiseSummary* summary, hipStream_t s)
+{
+    if (npix == 0u || (!noise && !summary)) return hipSuccess;
+    // level 0 over the pixels; while more than one tile sum is left, the same kernel over the sums (summary[1 ..]: the scratch)
+    uint32_t tiles = (uint32_t)PT_MOMENTS_TILES(npix);
+    PtNoiseSummary* scratch = summary ? summary + 1 : nullptr;
+    PtNoiseSummary* out = !summary ? nullptr : tiles == 1u ? summary : scratch;
+    hipLaunchKernelGGL(pt_moments_resolve_kernel, dim3(tiles), dim3(256), 0, s, moments, (const PtNoiseSummary*)nullptr, npix, (uint4*)noise, out);
+    hipError_t e = hipGetLastError();
+    while (e == hipSuccess && summary && tiles > 1u) {
+        const PtNoiseSummary* in = out;
+        const uint32_t count = tiles;
+        tiles = (uint32_t)PT_MOMENTS_TILES(count);
+        scratch += count;
+        out = tiles == 1u ? summary : scratch;
+        hipLaunchKernelGGL(pt_moments_resolve_kernel, dim3(tiles), dim3(256), 0, s, (const PtPixelMoments*)nullptr, in, count, (uint4*)nullptr, out);
+        e = hipGetLastError();
+    }
+    return e;
 }
 
 int ptk_indirect_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3>, ptk_trace_bvh_lds_bytes()); }

@@ -2031,6 +2031,65 @@ extern "C" int pt_light_counts(pt_device_t d, pt_buffer_t lights, int num_lights
     return event_end(d, ev);
 }
 
+// ---- sample moments (include/pt_shim.h) ---------------------------------------------------------------------------------
+static_assert(sizeof(pt_pixel_moments) == 56 && sizeof(PtPixelMoments) == 56 && sizeof(pt_noise_summary) == 48 && sizeof(PtNoiseSummary) == 48,
+              "moment record layout");
+
+extern "C" int pt_sample_moments(pt_device_t d, pt_buffer_t samples, pt_buffer_t moments, uint32_t num_pixels, int32_t frame_count,
+                                 int reset, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!samples || !moments) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { samples, moments })) || (rc = check_event(d, ev))) return rc;
+    if (frame_count < 0) return fail(PT_ERR_INVALID, "frame_count < 0");
+    const size_t moment_bytes = (size_t)num_pixels * sizeof(pt_pixel_moments);
+    const size_t frame_bytes = (size_t)num_pixels * 3u * sizeof(float);
+    if (frame_bytes && (size_t)frame_count > samples->bytes / frame_bytes)
+        return fail(PT_ERR_RANGE, "sample buffer holds %zu bytes, %d frames of %u pixels need more", samples->bytes, frame_count, num_pixels);
+    const size_t sample_bytes = frame_bytes * (size_t)frame_count;
+    if (moment_bytes > moments->bytes) return fail(PT_ERR_RANGE, "moments hold %zu bytes, %u pixels need %zu", moments->bytes, num_pixels, moment_bytes);
+    if ((uintptr_t)moments->dptr & 7u) return fail(PT_ERR_INVALID, "the moments must be 8-byte aligned");
+    if ((uintptr_t)samples->dptr & 3u) return fail(PT_ERR_INVALID, "the samples must be 4-byte aligned");
+    if (ranges_overlap(samples, sample_bytes, moments, moment_bytes)) return fail(PT_ERR_INVALID, "the samples and the moments overlap");
+    if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
+    if (num_pixels && frame_count) {
+        HIP_TRY(ptk_sample_moments((const float*)samples->dptr, (PtPixelMoments*)moments->dptr, num_pixels, frame_count, reset != 0, d->stream));
+        moments->version++;
+    }
+    return event_end(d, ev);
+}
+
+extern "C" size_t pt_moments_summary_bytes(uint32_t num_pixels) { return PT_MOMENTS_SUMMARY_RECORDS(num_pixels) * sizeof(pt_noise_summary); }
+
+extern "C" int pt_moments_resolve(pt_device_t d, pt_buffer_t moments, uint32_t num_pixels, pt_buffer_t noise, pt_buffer_t summary, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!moments) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { moments, noise, summary })) || (rc = check_event(d, ev))) return rc;
+    const size_t moment_bytes = (size_t)num_pixels * sizeof(pt_pixel_moments), noise_bytes = (size_t)num_pixels * 16u,
+                 summary_bytes = pt_moments_summary_bytes(num_pixels);
+    if (moment_bytes > moments->bytes) return fail(PT_ERR_RANGE, "moments hold %zu bytes, %u pixels need %zu", moments->bytes, num_pixels, moment_bytes);
+    if (noise && noise_bytes > noise->bytes) return fail(PT_ERR_RANGE, "the noise map holds %zu bytes, %u pixels need %zu", noise->bytes, num_pixels, noise_bytes);
+    if (summary && summary_bytes > summary->bytes)
+        return fail(PT_ERR_RANGE, "the summary holds %zu bytes, %u pixels need %zu (pt_moments_summary_bytes)", summary->bytes, num_pixels, summary_bytes);
+    if ((uintptr_t)moments->dptr & 7u) return fail(PT_ERR_INVALID, "the moments must be 8-byte aligned");
+    if (noise && ((uintptr_t)noise->dptr & 15u)) return fail(PT_ERR_INVALID, "the noise map must be 16-byte aligned");
+    if (summary && ((uintptr_t)summary->dptr & 7u)) return fail(PT_ERR_INVALID, "the summary must be 8-byte aligned");
+    if ((noise && ranges_overlap(moments, moment_bytes, noise, noise_bytes)) || (summary && ranges_overlap(moments, moment_bytes, summary, summary_bytes)) ||
+        (noise && summary && ranges_overlap(noise, noise_bytes, summary, summary_bytes)))
+        return fail(PT_ERR_INVALID, "the moments, the noise map and the summary overlap");
+    if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
+    if (num_pixels && (noise || summary)) {
+        HIP_TRY(ptk_moments_resolve((const PtPixelMoments*)moments->dptr, num_pixels, noise ? noise->dptr : nullptr,
+                                    summary ? (PtNoiseSummary*)summary->dptr : nullptr, d->stream));
+        if (noise) noise->version++;
+        if (summary) summary->version++;
+    }
+    return event_end(d, ev);
+}
+
 extern "C" int pt_camera_rays(pt_device_t d, const pt_camera* cam, int width, int height, int frame, pt_buffer_t rays, pt_event_t ev)
 {
     int rc = use_device(d);

@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power] | --only IndirectIllumination [--mis] [--lights power]]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power] | --only IndirectIllumination [--mis] [--lights power]] [--noise]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <chrono>
 #include <cmath>
@@ -119,6 +119,7 @@ struct Options {
     int deviceIdx = 0, dim = 512, frames = 10000;
     bool batch = true, mis = false;   // mis: IndirectIllumination through pt_render_indirect_mis
     bool power = false;               // --lights power: DirectIllumination / IndirectIllumination choose their lights by power
+    bool noise = false;               // --noise: DirectIllumination / IndirectIllumination print the image's noise summary
     std::string scene = "cornellbox.bin", outDir = ".", dump, only;
 };
 
@@ -369,6 +370,8 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
 // pt_light_counts -- written to indirectIllumination_<version>_mis.ppm.
 // With --lights power either case chooses its lights in proportion to their emitted power (pt_render_direct_power,
 // pt_render_indirect_power, the table made by pt_light_table) and the file's name ends in _power.ppm (_mis_power.ppm with --mis).
+// With --noise either case renders in calls of at most as many frames as the workspace holds, takes the samples' moments after each
+// (pt_sample_moments) and prints one more line, after the case's own: the summary of pt_moments_resolve.  The image is the same.
 // bounces: 0 = DirectIllumination, otherwise IndirectIllumination at that depth.
 static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
 {
@@ -422,26 +425,35 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     auto t0 = std::chrono::steady_clock::now();
     const bool mis = bounces && o.mis;
     pt_buffer_t lh = lights.empty() ? 0 : lBuffer.m_handle;
-    if (o.power) {
+    if (o.power)
         IASSERT(pt_light_table(m_d->m_handle, tBuffer.m_handle, p.num_triangles, mBuffer.m_handle, p.num_materials, lh, p.num_lights, cdf.m_handle,
                                triq.m_handle, 0) == PT_OK);
-        if (mis) IASSERT(pt_light_counts(m_d->m_handle, lh, p.num_lights, p.num_triangles, cBuffer.m_handle, 0) == PT_OK);
-        if (bounces)
-            IASSERT(pt_render_indirect_power(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0, cdf.m_handle,
-                                             triq.m_handle, samples.m_handle, image.m_handle, &q, 0, 0) == PT_OK);
-        else
-            IASSERT(pt_render_direct_power(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cdf.m_handle, triq.m_handle, samples.m_handle,
-                                           image.m_handle, &p, 0, 0) == PT_OK);
-    } else if (mis) {
-        IASSERT(pt_light_counts(m_d->m_handle, lights.empty() ? 0 : lBuffer.m_handle, (int)lights.size(), (int)triangles.size(), cBuffer.m_handle, 0) == PT_OK);
-        IASSERT(pt_render_indirect_mis(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lights.empty() ? 0 : lBuffer.m_handle, cBuffer.m_handle,
-                                       samples.m_handle, image.m_handle, &q, 0, 0) == PT_OK);
-    } else if (bounces)
-        IASSERT(pt_render_indirect(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lights.empty() ? 0 : lBuffer.m_handle, samples.m_handle,
-                                   image.m_handle, &q, 0, 0) == PT_OK);
-    else
-        IASSERT(pt_render_direct(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lights.empty() ? 0 : lBuffer.m_handle, samples.m_handle,
-                                 image.m_handle, &p, 0, 0) == PT_OK);
+    if (mis) IASSERT(pt_light_counts(m_d->m_handle, lh, p.num_lights, p.num_triangles, cBuffer.m_handle, 0) == PT_OK);
+    // frames [first, first + count) through the case's entry point
+    auto render = [&](int first, int count) {
+        p.frame_begin = q.frame_begin = first;
+        p.frame_count = q.frame_count = count;
+        if (o.power && bounces)
+            return pt_render_indirect_power(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0, cdf.m_handle,
+                                            triq.m_handle, samples.m_handle, image.m_handle, &q, 0, 0);
+        if (o.power)
+            return pt_render_direct_power(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cdf.m_handle, triq.m_handle, samples.m_handle,
+                                          image.m_handle, &p, 0, 0);
+        if (mis)
+            return pt_render_indirect_mis(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cBuffer.m_handle, samples.m_handle, image.m_handle, &q, 0, 0);
+        if (bounces) return pt_render_indirect(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, samples.m_handle, image.m_handle, &q, 0, 0);
+        return pt_render_direct(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, samples.m_handle, image.m_handle, &p, 0, 0);
+    };
+    Buffer<pt_pixel_moments> moments(m_d, o.noise ? npix : 0);
+    Buffer<unsigned char> summary(m_d, o.noise ? pt_moments_summary_bytes((uint32_t)npix) : 0);
+    if (o.noise && o.frames > 0) {
+        for (int first = 0; first < o.frames; first += chunk) {
+            const int count = o.frames - first < chunk ? o.frames - first : chunk;
+            IASSERT(render(first, count) == PT_OK);
+            IASSERT(pt_sample_moments(m_d->m_handle, samples.m_handle, moments.m_handle, (uint32_t)npix, count, first == 0, 0) == PT_OK);
+        }
+    } else
+        IASSERT(render(0, o.frames) == PT_OK);
     IASSERT(pt_tonemap_ppm(m_d->m_handle, image.m_handle, rgb.m_handle, npix, 0) == PT_OK);
     std::vector<int> h(3 * npix, 0);
     rgb.read(h.data(), 3 * npix);
@@ -453,6 +465,18 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     else
         std::printf("DirectIllumination%s: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", o.power ? " (lights by power)" : "", dimension, dimension,
                     o.frames, (int)lights.size(), secs);
+    if (o.noise) {
+        pt_noise_summary ns;
+        std::memset(&ns, 0, sizeof ns);
+        if (o.frames > 0) {
+            IASSERT(pt_moments_resolve(m_d->m_handle, moments.m_handle, (uint32_t)npix, 0, summary.m_handle, 0) == PT_OK);
+            summary.read((unsigned char*)&ns, sizeof ns);
+            DeviceUtils::waitForCompletion(m_d);
+        }
+        std::printf("noise: variance_per_sample %.17g relative_error %.17g pixels %llu samples %llu rejected %llu\n",
+                    ns.var_sum / (3.0 * (double)ns.pixels), std::sqrt(ns.se2_sum / ns.mean2_sum), (unsigned long long)ns.pixels,
+                    (unsigned long long)ns.samples, (unsigned long long)ns.rejected);
+    }
     char path[512];
     f.getFilePath(o.outDir.c_str(), bounces ? "indirectIllumination" : "directIllumination", "ppm", path, sizeof path);
     if (mis && std::strlen(path) + 5 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_mis.ppm");
@@ -482,6 +506,7 @@ int main(int argc, char** argv)
         else if (a == "--only") o.only = next();
         else if (a == "--no-batch") o.batch = false;
         else if (a == "--mis") o.mis = true;
+        else if (a == "--noise") o.noise = true;
         else if (a == "--lights") {
             const std::string v = next();
             if (v != "uniform" && v != "power") { std::fprintf(stderr, "--lights takes uniform or power\n"); return 2; }

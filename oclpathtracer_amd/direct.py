@@ -8,10 +8,14 @@ or open.  The result is the renderer's framebuffer -- with no lights it is the r
 ``light_choice="power"`` chooses the light triangle in proportion to the power it emits instead (``pt_render_direct_power``, through a
 table built once on the device by ``pt_light_table``): the same expectation, and far less noise where the emitters differ in size
 or brightness.
+``moments=True`` keeps per-pixel noise estimates beside the image: after every call the first and second moments of the samples'
+linear radiance are taken from the workspace on the device (``pt_sample_moments``), and ``variance()``, ``noise()`` and
+``render_until()`` read them -- a variance map, an image-wide figure of 48 bytes, and a render that stops at a noise level.
 ``include/pt_shim.h`` states every expression.  All compute is HIP in libptshim.so; nothing here has a CPU fallback.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import Optional
 
@@ -21,6 +25,11 @@ from . import adl, scene, shim
 from .camera import Camera
 
 _WORKSPACE_BYTES = 64 << 20   # the default workspace holds as many whole frames as fit in this, at most 64
+
+# what noise() returns: the mean over pixels and channels of the unbiased variance of one sample's linear radiance; the image's
+# relative standard error sqrt(sum of the pixels' squared standard errors / sum of their squared means); the pixels with at least two
+# finite samples (the only ones both figures count); the finite samples and the samples rejected for a NaN or an infinity, all pixels
+Noise = collections.namedtuple("Noise", "variance_per_sample relative_error pixels samples rejected")
 
 
 def _check_lights(lights, num_triangles: int) -> np.ndarray:
@@ -46,16 +55,21 @@ class DirectRenderer:
     emitted light alone.  ``light_choice``: ``"uniform"`` -- every entry of the list with the same probability -- or ``"power"`` --
     in proportion to area x emission; the renderer then owns the selection table.  ``chunk_frames`` sizes the sample workspace: that many
     frames are traced by one launch and folded by the next.  ``stripe_rows`` / ``n_ranks`` / ``rank`` select the rows this device
-    owns, as for ``Renderer``.  The search follows the device's options exactly as renders do."""
+    owns, as for ``Renderer``.  The search follows the device's options exactly as renders do.  ``moments``: keep per-pixel moments
+    of the samples (``variance``, ``noise``, ``render_until``); the image is the same bit for bit, ``render`` issues its frames as calls
+    of at most ``chunk_frames`` frames, each followed by ``pt_sample_moments``, and accepts ``frame_begin`` 0 or ``frames_done`` only."""
 
     def __init__(self, dev: adl.Device, triangles, materials, width: int, height: int, *, light_samples: int = 1, lights=None,
                  camera: Optional[Camera] = None, num_triangles: Optional[int] = None, num_materials: Optional[int] = None,
                  stripe_rows: int = 16, n_ranks: int = 1, rank: int = 0, chunk_frames: Optional[int] = None,
-                 light_choice: str = "uniform"):
+                 light_choice: str = "uniform", moments: bool = False):
         if light_choice not in ("uniform", "power"):
             raise ValueError('light_choice must be "uniform" or "power"')
         self.light_choice = light_choice
         self.cdf = self.tri_q = None
+        self.moments = bool(moments)
+        self.mom = self.summary = self.noise_map = None
+        self._moments_valid = False   # the moments buffer holds this image's sums (a call from frame 0 has reset it)
         self.dev = dev
         self._lib = shim.load()
         self.width, self.height = int(width), int(height)
@@ -112,12 +126,15 @@ class DirectRenderer:
         self.samples = adl.Buffer(dev, 3 * n * self.chunk_frames, np.float32)
         self.fb = adl.Buffer(dev, n, adl.float4)
         self.frames_done = 0
-        if self.light_choice == "power":
-            try:
+        try:
+            if self.moments:
+                self.mom = adl.Buffer(dev, n * ctypes.sizeof(shim.PixelMoments), np.uint8)
+                self.summary = adl.Buffer(dev, self._lib.pt_moments_summary_bytes(n), np.uint8)
+            if self.light_choice == "power":
                 self._build_table()
-            except Exception:
-                self.release()
-                raise
+        except Exception:
+            self.release()
+            raise
 
     def _build_table(self) -> None:
         """the selection table of the list, built once on the device (pt_light_table) into buffers of this renderer's"""
@@ -135,6 +152,7 @@ class DirectRenderer:
         """Render from ``camera`` from now on (None: the reference's); the next render starts again at frame 0."""
         self._set_camera(camera)
         self.frames_done = 0
+        self._moments_valid = False
 
     # what a renderer with the same buffers and another entry point changes (indirect.IndirectRenderer)
     _PARAMS = shim.DirectParams
@@ -151,13 +169,28 @@ class DirectRenderer:
 
     def render(self, frames: int, frame_begin: Optional[int] = None, sync: Optional[adl.SyncObject] = None) -> None:
         """Enqueue frames [frame_begin, frame_begin + frames) (default: continue after the last call); frame_begin 0 starts the
-        running mean afresh."""
+        running mean afresh.  With ``moments`` the frames go out as calls of at most ``chunk_frames`` frames, each followed by the
+        moments of its samples, and frame_begin must be 0 or ``frames_done``: a frame rendered twice would be counted twice."""
         if frame_begin is None:
             frame_begin = self.frames_done
         frames, frame_begin = int(frames), int(frame_begin)
         if frames < 0 or frame_begin < 0 or frame_begin + frames > 0x7fffffff:
             raise ValueError("invalid frame range [%d, %d)" % (frame_begin, frame_begin + frames))
-        shim.check(self._call(self.params(frames, frame_begin), sync))
+        if self.moments and frames > 0:
+            if frame_begin not in (0, self.frames_done):
+                raise ValueError("with moments a render starts at frame 0 or at frames_done (%d), not at %d" % (self.frames_done, frame_begin))
+            first, end = frame_begin, frame_begin + frames
+            while first < end:
+                k = min(self.chunk_frames, end - first)
+                shim.check(self._call(self.params(k, first), sync if first + k == end else None))
+                if self.local_pixels:
+                    shim.check(self._lib.pt_sample_moments(self.dev._h, self.samples._h, self.mom._h, self.local_pixels, k, int(first == 0), None))
+                first += k
+            self._moments_valid = True
+        else:
+            shim.check(self._call(self.params(frames, frame_begin), sync))
+            if frame_begin == 0:
+                self._moments_valid = False   # (no frames from 0: the image starts afresh, and so do the figures)
         self.frames_done = frame_begin + frames
 
     def _call(self, p, sync) -> int:
@@ -180,11 +213,59 @@ class DirectRenderer:
         self.dev.waitForCompletion()
         return out
 
+    def _need_moments(self) -> None:
+        if not self.moments:
+            raise RuntimeError("this renderer keeps no moments: construct it with moments=True")
+
+    def variance(self):
+        """The unbiased variance of one sample's linear radiance, per local pixel and channel, from every frame rendered since the
+        last start at frame 0: ``(var float32 [local_pixels, 3], n uint32 [local_pixels])``, n the pixel's finite samples (a pixel
+        with n < 2 has variance 0).  Resolved on the device (``pt_moments_resolve``); synchronises."""
+        self._need_moments()
+        rec = np.zeros((self.local_pixels, 4), np.float32)
+        if self.local_pixels and self._moments_valid:
+            if self.noise_map is None:
+                self.noise_map = adl.Buffer(self.dev, self.local_pixels, adl.float4)
+            shim.check(self._lib.pt_moments_resolve(self.dev._h, self.mom._h, self.local_pixels, self.noise_map._h, None, None))
+            self.noise_map.read(rec, self.local_pixels)
+            self.dev.waitForCompletion()
+        return np.ascontiguousarray(rec[:, :3]), np.ascontiguousarray(rec[:, 3]).view(np.uint32)
+
+    def noise(self) -> Noise:
+        """The image-wide noise figures (``Noise``) of the frames rendered since the last start at frame 0, reduced on the device and
+        read back in 48 bytes; synchronises.  Without a pixel of two finite samples both figures are NaN."""
+        self._need_moments()
+        words = np.zeros(6, np.uint64)
+        if self.local_pixels and self._moments_valid:
+            shim.check(self._lib.pt_moments_resolve(self.dev._h, self.mom._h, self.local_pixels, None, self.summary._h, None))
+            self.summary.read(words, words.nbytes)
+            self.dev.waitForCompletion()
+        var_sum, se2_sum, mean2_sum = words[:3].view(np.float64)
+        pixels, samples, rejected = (int(w) for w in words[3:])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            per_sample = float(var_sum / np.float64(3 * pixels))
+            relative = float(np.sqrt(se2_sum / mean2_sum))
+        return Noise(per_sample, relative, pixels, samples, rejected)
+
+    def render_until(self, relative_error: float, max_frames: int, check_every: Optional[int] = None) -> int:
+        """Render on from ``frames_done``, ``check_every`` frames at a time (default ``chunk_frames``), until ``noise().relative_error``
+        lies below ``relative_error`` or ``max_frames`` frames are done; returns ``frames_done``.  Every check reads the 48 bytes of the
+        summary back: ONE HOST WAIT PER CHECK, so a small ``check_every`` serialises the host with the device."""
+        self._need_moments()
+        step = self.chunk_frames if check_every is None else int(check_every)
+        if step < 1:
+            raise ValueError("check_every must be at least 1")
+        while self.frames_done < int(max_frames):
+            self.render(min(step, int(max_frames) - self.frames_done))
+            if self.noise().relative_error < relative_error:
+                break
+        return self.frames_done
+
     def release(self) -> None:
-        for b in (self.lbuf, self.samples, self.fb, self.cdf, self.tri_q):
+        for b in (self.lbuf, self.samples, self.fb, self.cdf, self.tri_q, self.mom, self.summary, self.noise_map):
             if b is not None:
                 b.release()
-        self.cdf = self.tri_q = None
+        self.cdf = self.tri_q = self.mom = self.summary = self.noise_map = None
         if self._own_tbuf and self.tbuf is not None:
             self.tbuf.release()
         if self._own_mbuf and self.mbuf is not None:

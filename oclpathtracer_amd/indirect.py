@@ -33,7 +33,8 @@ from .render import BOUNCES
 
 class IndirectRenderer(DirectRenderer):
     """``DirectRenderer`` (its arguments, buffers, ``render`` / ``read`` / ``release``) with paths of up to ``max_bounces``
-    vertices and ``light_samples`` light samples at each of them; ``mis``: with multiple importance sampling."""
+    vertices and ``light_samples`` light samples at each of them; ``mis``: with multiple importance sampling.  ``moments=True`` and its
+    ``variance`` / ``noise`` / ``render_until`` are ``DirectRenderer``'s, under every estimator."""
 
     _PARAMS = shim.IndirectParams
     _ENTRY = "pt_render_indirect"

@@ -137,6 +137,20 @@ class BvhInfo(_c.Structure):
 
 PT_BVH_SNAPSHOT_BIG_MAX = 64
 
+
+class PixelMoments(_c.Structure):
+    """pt_pixel_moments (56 bytes): per channel the sum and the sum of squares of a pixel's finite samples, their number, and the
+    number of samples rejected for a NaN or an infinity."""
+
+    _fields_ = [("sum", _c.c_double * 3), ("sum2", _c.c_double * 3), ("n", _c.c_uint32), ("rejected", _c.c_uint32)]
+
+
+class NoiseSummary(_c.Structure):
+    """pt_noise_summary (48 bytes): the first record of pt_moments_resolve's summary buffer."""
+
+    _fields_ = [("var_sum", _c.c_double), ("se2_sum", _c.c_double), ("mean2_sum", _c.c_double),
+                ("pixels", _c.c_uint64), ("samples", _c.c_uint64), ("rejected", _c.c_uint64)]
+
 # every symbol include/pt_shim.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "pt_last_error": (_c.c_char_p, []),
@@ -201,6 +215,9 @@ SIGNATURES = {
     "pt_light_table": (_c.c_int, [_H, _H, _c.c_int, _H, _c.c_int, _H, _c.c_int, _H, _H, _H]),
     "pt_render_direct_power": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(DirectParams), _c.POINTER(Camera), _H]),
     "pt_render_indirect_power": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Camera), _H]),
+    "pt_sample_moments": (_c.c_int, [_H, _H, _H, _c.c_uint32, _c.c_int32, _c.c_int, _H]),
+    "pt_moments_summary_bytes": (_c.c_size_t, [_c.c_uint32]),
+    "pt_moments_resolve": (_c.c_int, [_H, _H, _c.c_uint32, _H, _H, _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_bvh_snapshot": (_c.c_int, [_H, _c.POINTER(BvhInfo), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
