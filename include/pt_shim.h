@@ -502,7 +502,8 @@ int pt_render_direct(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materia
  *    of -0 direct forms E + S / K from E = -0 where this forms 0 + E = +0 first; that case is excluded.
  * Not done here: multiple importance sampling (a BRDF ray that finds a light adds nothing at i > 0, so glossy surfaces next to
  * a light are noisy; pt_render_indirect_mis below does it), light choice by power (every entry of the list is as likely as every
- * other; pt_render_indirect_power below does it), Russian roulette.
+ * other; pt_render_indirect_power below does it), Russian roulette (every path walks all max_bounces vertices unless it misses or
+ * draws pdf <= 0; pt_render_indirect_rr below does it).
  * Behaviour: pt_render_direct's, word for word -- the handle's stream, behind renders in flight, asynchronous (ev); the prepared
  * scene, LBVH and filter tables as a query uses them; no allocation and no wait once the scene is prepared; PT_OPT_ACCEL and
  * PT_OPT_QUAD_FILTER choose the search; PT_ERR_TRAVERSAL is deferred; num_triangles = 0 renders the background.  Errors are
@@ -636,6 +637,47 @@ int pt_render_indirect_power(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t
                              pt_buffer_t cdf, pt_buffer_t tri_q /* may be NULL when num_lights is 0 */, pt_buffer_t samples /* workspace */,
                              pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam /* NULL = the reference's */,
                              pt_event_t ev);
+
+/* ---- Russian roulette ----------------------------------------------------------------------------------------------------
+ * The four indirect estimators -- pt_render_indirect, pt_render_indirect_mis, pt_render_indirect_power with mis 0 and 1 -- with paths
+ * that may end early at random and are reweighted so that the expectation stays what it was: at the headline depth most of a
+ * sample's searches are otherwise spent on vertices whose throughput is a few percent.  New estimators beside the old ones, which
+ * are unchanged.  One entry point covers the four: mis as pt_render_indirect_power takes it; cdf and tri_q both NULL = the uniform
+ * choice, both given = the choice by power.
+ * The estimator is its parent's steps 1-4 with one addition at the end of step 2d, parameterised by R = first_bounce >= 1 and cap =
+ * max_survival in (0, 1], B = max_bounces.  After the BRDF sample of vertex i has passed its pdf <= 0 test and mask has taken its
+ * three quotients, the roulette applies when i + 1 >= R and i < B - 1 (at the last vertex nothing is drawn, as before).  When it
+ * applies:
+ *  1. r = getRandomFloat(&seed), drawn whatever follows;
+ *  2. s = max(mask.x, max(mask.y, mask.z)) with the reference's max ((a < b) ? b : a); q = min(s, cap), the reference's min ((cap <
+ *     s) ? cap : s).  A NaN mask.x, or NaN in both other channels, makes q NaN;
+ *  3. q >= 1.0f: the path goes on with mask unchanged (getRandomFloat can return 1.0: r < q would wrongly end a path that must live);
+ *  4. otherwise the path goes on if and only if r < q -- false for a NaN q, false for q <= 0 --, with mask.c = mask.c / q per channel:
+ *     three IEEE divisions;
+ *  5. a path that does not go on ends as a pdf <= 0 path does: L is stored (step 3).
+ * With MIS, pb stays step 2d's pdf: it is NOT multiplied by q, and the light samples of vertex i are taken before the roulette.  Why
+ * the weights still partition: for a direction that finds the front of triangle h, the light samples of vertex i carry counts[h] *
+ * kp / (kp * counts[h] + p) of the light h sends along it, whatever the roulette does afterwards; the BRDF ray survives with
+ * probability q and its contribution at vertex i + 1 is mask / q times the emission times wb = p / (kp * counts[h] + p), whose
+ * expectation over the roulette is the unplayed path's mask * emission * wb.  The two weights are formed from the same p and kp as
+ * without roulette and sum to 1; scaling pb by q would compare the BRDF sample's density in one measure with the light samples' in
+ * another and break the partition.
+ * Identities: R >= B: no roulette is played, no extra uniform is drawn, and the framebuffer is the parent's, bit for bit, for all
+ * four estimators; num_lights == 0 and R >= B: it is pt_render_frames' at the same max_bounces.
+ * Behaviour and errors: the parents', word for word -- one validation, one chunk loop, one fold, the handle's stream, the deferred
+ * PT_ERR_TRAVERSAL --, plus, before anything is enqueued: PT_ERR_INVALID for roulette NULL, first_bounce < 1, max_survival NaN or
+ * outside (0, 1], a reserved word of pt_roulette not 0, and exactly one of cdf / tri_q NULL while num_lights > 0. */
+typedef struct pt_roulette {
+    int32_t first_bounce;   /* R >= 1: vertex i plays when i + 1 >= R (R >= max_bounces: never) */
+    float max_survival;     /* cap, in (0, 1] */
+    int32_t reserved[2];    /* must be 0 */
+} pt_roulette;              /* 16 bytes */
+int pt_render_indirect_rr(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                          pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, int mis,
+                          pt_buffer_t light_counts /* int32[num_triangles]; may be NULL when mis or num_lights is 0 */,
+                          pt_buffer_t cdf, pt_buffer_t tri_q /* both NULL = the uniform choice */, pt_buffer_t samples /* workspace */,
+                          pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_roulette* roulette,
+                          const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
 
 /* ---- sample moments: per-pixel noise estimates of the lit renders -----------------------------------------------------------
  * Every lit entry point (pt_render_direct, pt_render_indirect and their _mis / _power forms) leaves each sample's linear radiance in

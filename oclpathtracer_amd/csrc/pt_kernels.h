@@ -328,6 +328,18 @@ hipError_t ptk_direct_power(const PtDirectPowerParams& a, int bvh_blocks, PtSear
 hipError_t ptk_indirect_power(const PtIndirectPowerParams& a, int bvh_blocks, PtSearchMode m, bool mis, hipStream_t s);
 int ptk_direct_power_bvh_blocks_per_cu(void);
 int ptk_indirect_power_bvh_blocks_per_cu(bool mis);
+// Russian roulette (pt_render_indirect_rr): the RR = true instantiations take this block, whichever of the four estimators they are
+// (counts, cdf and tri_q are null where the estimator does not read them); every other instantiation its block as before.  R and cap
+// are wave-uniform: they add no per-lane state
+struct PtIndirectRrParams : PtIndirectPowerParams {
+    int32_t R;                    // first_bounce >= 1: the roulette is played at vertex i when i + 1 >= R and i < B - 1
+    float cap;                    // max_survival in (0, 1]
+};
+// One launch of the roulette kernels.  LBVH (m.bvh): pt_indirect_bvh_kernel's RR = true instantiations on the persistent grid of
+// bvh_blocks = CUs x ptk_indirect_rr_bvh_blocks_per_cu(mis, power) workgroups.  Brute force: pt_indirect_rr_kernel, one wave per
+// PT_RR_RUN (pt_constants.h) consecutive items, which refills its dead lanes from its run
+hipError_t ptk_indirect_rr(const PtIndirectRrParams& a, int bvh_blocks, PtSearchMode m, bool mis, bool power, hipStream_t s);
+int ptk_indirect_rr_bvh_blocks_per_cu(bool mis, bool power);
 // pt_light_table: the selection table of lights[0 .. nl) over the RAW records (the prepared ones hold the same e1, e2 and N bit for
 // bit: pt_prep_kernel).  cdf: PT_LIGHT_TABLE_WORDS(nl) uint64 -- cdf[0 .. nl], then the build's scratch: the largest power's bits and
 // one sum per tile of PT_LIGHT_SCAN_TILE entries; tri_q: uint32[ntri].  One clear, then four kernels (weights and their maximum;

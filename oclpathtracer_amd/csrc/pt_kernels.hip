@@ -3494,8 +3494,8 @@ PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f
 }
 
 // the parameter block of an instantiation, and its counts (none without MIS)
-template <bool MIS, bool POWER = false>
-using PtIndirectArgs = std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>;
+template <bool MIS, bool POWER = false, bool RR = false>
+using PtIndirectArgs = std::conditional_t<RR, PtIndirectRrParams, std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>>;
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectParams&) { return nullptr; }
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectMisParams& I) { return I.counts; }
 PTK_DEV const uint64_t* pt_light_cdf(const PtIndirectParams&) { return nullptr; }
@@ -3550,6 +3550,24 @@ PTK_DEV void pt_indirect_lit(const PtDirectParams& D, const f3& mask, const f3& 
 PTK_DEV void pt_indirect_store(const PtDirectParams& D, unsigned item, const f3& L)   // :260
 {
     pt_direct_store(D, item, mk3(pt_max(L.x, 0.0f), pt_max(L.y, 0.0f), pt_max(L.z, 0.0f)));
+}
+
+// Russian roulette (pt_render_indirect_rr, whose contract states every step) at a vertex where it applies -- the caller has checked
+// i + 1 >= R and i < B - 1 --, after pt_indirect_bounce has returned true: the uniform is drawn whatever follows; q = min(max channel
+// of mask, cap) with the reference's max and min (a NaN in mask.x, or in both others, makes q NaN); q >= 1 leaves the path as it is
+// (the uniform can be 1.0); otherwise the path goes on when r < q -- false for a NaN q and for q <= 0 -- with mask / q, three IEEE
+// divisions (q has no proven window: no short form).  False: the path ends as a pdf <= 0 path does
+PTK_DEV bool pt_roulette(float cap, uint32_t& seed, f3& mask)
+{
+    const float r = pt_random_float(seed);
+    const float s = pt_max(mask.x, pt_max(mask.y, mask.z));
+    const float q = cap < s ? cap : s;
+    if (q >= 1.0f) return true;
+    if (!(r < q)) return false;
+    mask.x = mask.x / q;
+    mask.y = mask.y / q;
+    mask.z = mask.z / q;
+    return true;
 }
 
 // brute force: one wave = 64 consecutive samples, pt_direct_kernel's shape inside a loop over the bounces.  The wave searches in step
@@ -3618,6 +3636,103 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
     if (act) pt_indirect_store(D, item, L);
 }
 
+// Brute force with Russian roulette (pt_render_indirect_rr): a NEW kernel beside pt_indirect_kernel, which stays as it is.  Roulette
+// shortens the average path, hardly the longest of 64, so in a kernel that walks 64 samples in lock step it would only empty the exec
+// mask.  Here a wave owns a contiguous RUN of PT_RR_RUN items, [run0, end), and REFILLS: at the top of every iteration the lanes whose
+// path has ended and been stored take the next unstarted items of the run, in lane order (a ballot of the dead lanes and its mbcnt
+// prefix: no atomics, no state shared between waves).  A sample's value depends on its item alone (pt_item_begin: the pixel and the
+// frame give the seed; pt_indirect_store: samples[item]), so which lane walks it changes no bit.  The bounce index is per lane.  The
+// searches, the light samples and the bounce are pt_indirect_kernel's calls in its order.
+// Termination: an iteration starts with at least one live lane (else the wave leaves: no lane alive means the refill found the run
+// exhausted), and every live lane either ends its path in it or raises its bounce, which is below B; every refill raises `next`,
+// which is at most `end`.  So a wave runs at most PT_RR_RUN * B iterations.  No spin, no persistent grid.
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS, bool POWER>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_rr_kernel(const PtIndirectRrParams I)
+{
+    static_assert(PT_RR_RUN % 64 == 0 && PT_RR_RUN >= 64, "a run is whole waves of items");
+    const PtDirectParams& D = I.d;
+    const PtTraceParams& P = D.t;
+    const unsigned lane = pt_lane_id();
+    const int ntri = P.ntri;
+    PtTail tl = pt_table_wg_setup<LDS_TABLE>(P, lane);
+    const f3 anchor = mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]);
+    // the run (wave-uniform): nitems < 2^31 and the grid is ceil(nitems / PT_RR_RUN) waves rounded up to workgroups, so run0 fits
+    const unsigned run0 = pt_wave() * (unsigned)PT_RR_RUN;
+    unsigned next = run0 < D.nitems ? run0 : D.nitems;
+    const unsigned end = D.nitems - next < (unsigned)PT_RR_RUN ? D.nitems : next + (unsigned)PT_RR_RUN;
+    unsigned item = 0u;
+    uint32_t seed = 0u;
+    int i = 0;   // the lane's bounce: loop index i of traceRays (:229)
+    f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f);
+    f3 L = mk3(0.0f, 0.0f, 0.0f), mask = mk3(1.0f, 1.0f, 1.0f);
+    [[maybe_unused]] float pb = 0.0f;   // (MIS) the pdf of the BRDF sample that made the current ray
+    bool alive = false;
+    for (;;) {
+        // refill: the dead lane of rank r among the dead takes item next + r while the run lasts
+        const unsigned long long dead = __ballot(!alive);
+        if (!alive) {
+            const unsigned it = next + pt_mbcnt(dead);
+            if (it < end) {
+                unsigned lp;
+                item = it;
+                pt_item_begin(P, D.cam, D.npix, D.frame0, item, lp, seed, o, d);
+                L = mk3(0.0f, 0.0f, 0.0f);
+                mask = mk3(1.0f, 1.0f, 1.0f);
+                i = 0;
+                alive = true;
+            }
+        }
+        const unsigned ndead = (unsigned)__popcll(dead);
+        next = end - next < ndead ? end : next + ndead;
+        if (__ballot(alive) == 0ull) break;   // the run is exhausted and every path stored
+
+        float tmax = 1e20f, hu = 0.0f, hv = 0.0f;
+        int hidx = -1;
+        pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, alive, tmax, hu, hv, hidx,
+                                                             P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+        const bool hit = alive & (hidx >= 0);
+        if (alive & !hit) L = add3(L, scale3(mask, pt_max(0.45f, 0.0f)));   // :235
+        f3 p = o, n = d, wo = d;
+        unsigned mid = 0u;
+        if (hit) {
+            pt_direct_surface(D, o, d, tmax, hu, hv, hidx, p, n, wo, mid);
+            if (i == 0 || D.nl == 0) pt_indirect_emission(D, mid, mask, L);
+            else if constexpr (MIS && POWER) pt_indirect_emission_mis<true>(D, I.counts, mid, hidx, d, tmax, pb, mask, L, I.cdf, I.tri_q);
+            else if constexpr (MIS) pt_indirect_emission_mis(D, I.counts, mid, hidx, d, tmax, pb, mask, L);
+        }
+        if (D.nl > 0 && __ballot(hit) != 0ull) {
+            f3 S = mk3(0.0f, 0.0f, 0.0f);
+            for (int k = 0; k < D.K; ++k) {
+                f3 c = mk3(0.0f, 0.0f, 0.0f);
+                float tlim = 0.0f;
+                bool cast = false;
+                if constexpr (POWER) { if (hit) cast = pt_direct_light<MIS, true>(D, p, n, wo, mid, seed, c, o, d, tlim, I.counts, i < I.B - 1, I.cdf); }
+                else if (hit) cast = pt_direct_light<MIS>(D, p, n, wo, mid, seed, c, o, d, tlim, I.counts, i < I.B - 1);
+                const bool live = cast & (tlim > 0.0f);
+                bool occluded = false;
+                if (__ballot(live) != 0ull) {
+                    float t = live ? tlim : 0.0f, su = 0.0f, sv = 0.0f;
+                    int sidx = -1;
+                    pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, live, t, su, sv, sidx,
+                                                                         P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+                    occluded = live & (sidx >= 0) & (t < tlim);   // pt_query_store's occlusion test
+                }
+                if (cast & !occluded) S = add3(S, c);
+            }
+            if (hit) pt_indirect_lit(D, mask, S, L);
+        }
+        // the BRDF sample and the roulette of vertex i; at the last vertex nothing is drawn
+        bool on = false;
+        if (hit && i < I.B - 1) {
+            on = pt_indirect_bounce<MIS>(D, p, n, wo, mid, seed, mask, o, d, &pb);
+            if (on && i + 1 >= I.R) on = pt_roulette(I.cap, seed, mask);
+        }
+        if (alive & !on) pt_indirect_store(D, item, L);   // a miss, pdf <= 0, the roulette, or the depth
+        alive = on;
+        ++i;
+    }
+}
+
 // LBVH (pt_bvh_drive): one item = one sample; the lane walks its path as a sequence of searches -- per vertex the closest search, then
 // the any-hit searches of the light samples that contribute -- and is free only when the sample is stored.  next_ray is the state
 // machine between two searches: a closest result leads to the surface, the emission and the first contributing light sample; an
@@ -3626,10 +3741,10 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
 // wo is the negated incoming direction, which the shadow rays overwrite in d, so it is kept; o is dead while p is live.
 // With MIS a lane also holds pb from the BRDF sample to the next closest hit, across that search: 34 registers.  The counts and the
 // emitter's record are gathered where they are used, as the materials are.
-template <bool MIS = false, bool POWER = false>
+template <bool MIS = false, bool POWER = false, bool RR = false>
 struct PtIndirectWork {
     static constexpr bool ANY = true;
-    const PtIndirectArgs<MIS, POWER>& I;
+    const PtIndirectArgs<MIS, POWER, RR>& I;
     unsigned n;
     int k;           // the current ray: -1 = the vertex's closest search, 0 .. K-1 = the shadow ray of light sample k
     int bounce;      // loop index i of traceRays (:229)
@@ -3675,6 +3790,9 @@ struct PtIndirectWork {
         bool on;
         if constexpr (MIS) on = ++bounce < I.B && pt_indirect_bounce<true>(D, p, nrm, wo, mid, seed, mask, o, d, &pb);
         else on = ++bounce < I.B && pt_indirect_bounce(D, p, nrm, wo, mid, seed, mask, o, d);
+        if constexpr (RR) {   // (the vertex is i = bounce - 1: i + 1 >= R, and on says i < B - 1)
+            if (on && bounce >= I.R) on = pt_roulette(I.cap, seed, mask);
+        }
         if (on) {
             k = -1;
             return true;
@@ -3697,12 +3815,14 @@ struct PtIndirectWork {
 #ifndef PT_INDIRECT_BVH_WAVES   // (tools/kernel_resources.sh -DPT_INDIRECT_BVH_WAVES=4 reads the other choice)
 #define PT_INDIRECT_BVH_WAVES 3
 #endif
-template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false>
+// The RR = true instantiations (Russian roulette, pt_roulette in next_ray) take PtIndirectRrParams and keep the three waves: R and cap are
+// scalar, the roulette's r, s and q die where they are used (profiles/roulette/kernel_resources.txt has the compiler's figures)
+template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false, bool RR = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_INDIRECT_BVH_WAVES, PT_INDIRECT_BVH_WAVES)))
-void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER> I)
+void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER, RR> I)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtIndirectWork<MIS, POWER> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
+    PtIndirectWork<MIS, POWER, RR> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(I.d.t, W);
 }
 
@@ -4081,6 +4201,43 @@ hipError_t ptk_indirect_power(const PtIndirectPowerParams& a, int bvh_blocks, Pt
         else kernel = m.det_bounded ? pt_indirect_kernel<true, 2, 0, false, true> : pt_indirect_kernel<false, 2, 0, false, true>;
     }
     return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, m.bvh, bvh_blocks, s);
+}
+
+// the roulette kernels of one (MIS, POWER) estimator: pt_pick's shape, as ptk_indirect_power has it
+template <bool MIS, bool POWER>
+static hipError_t pt_launch_indirect_rr(const PtIndirectRrParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
+{
+    const bool q3 = m.quads == 3;
+    void (*kernel)(const PtIndirectRrParams);
+    if (m.bvh) {
+        kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3, MIS, POWER, true>, pt_indirect_bvh_kernel<true, 0, MIS, POWER, true>,
+                         pt_indirect_bvh_kernel<false, 0, MIS, POWER, true>);
+        return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, true, bvh_blocks, s);
+    }
+    const int ntri = a.d.t.ntri;
+    if (ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_rr_kernel<true, 1, 3, MIS, POWER>, pt_indirect_rr_kernel<true, 1, 0, MIS, POWER>,
+                                                 pt_indirect_rr_kernel<false, 1, 0, MIS, POWER>);
+    else kernel = m.det_bounded ? pt_indirect_rr_kernel<true, 2, 0, MIS, POWER> : pt_indirect_rr_kernel<false, 2, 0, MIS, POWER>;
+    // one wave per run of PT_RR_RUN items, the table kernels' LDS without the pools (pt_launch_search's brute-force form)
+    const unsigned wg_waves = PT_TRACE_THREADS / 64;
+    const unsigned waves = (a.d.nitems + (unsigned)PT_RR_RUN - 1u) / (unsigned)PT_RR_RUN;
+    const size_t lds = (size_t)(ntri <= PT_LDS_TRI_MAX ? pt_lds_total<1, false>(ntri) : pt_lds_total<2, false>(ntri)) * sizeof(float);
+    hipLaunchKernelGGL(kernel, dim3((waves + wg_waves - 1u) / wg_waves), dim3(PT_TRACE_THREADS), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t ptk_indirect_rr(const PtIndirectRrParams& a, int bvh_blocks, PtSearchMode m, bool mis, bool power, hipStream_t s)
+{
+    if (a.d.nitems == 0) return hipSuccess;
+    if (power) return mis ? pt_launch_indirect_rr<true, true>(a, bvh_blocks, m, s) : pt_launch_indirect_rr<false, true>(a, bvh_blocks, m, s);
+    return mis ? pt_launch_indirect_rr<true, false>(a, bvh_blocks, m, s) : pt_launch_indirect_rr<false, false>(a, bvh_blocks, m, s);
+}
+
+int ptk_indirect_rr_bvh_blocks_per_cu(bool mis, bool power)
+{
+    const size_t lds = ptk_trace_bvh_lds_bytes();
+    if (power) return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, true, true>, lds) : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, true, true>, lds);
+    return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, false, true>, lds) : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, false, true>, lds);
 }
 
 int ptk_indirect_power_bvh_blocks_per_cu(bool mis)

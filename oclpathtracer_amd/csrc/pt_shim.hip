@@ -140,6 +140,7 @@ struct pt_device_s {
     int indirect_bvh_blocks_per_cu;   // ... and of the indirect-illumination kernel, at its own occupancy
     int indirect_mis_bvh_blocks_per_cu;   // ... and of its MIS instantiation
     int direct_power_bvh_blocks_per_cu, indirect_power_bvh_blocks_per_cu, indirect_power_mis_bvh_blocks_per_cu;   // ... and of the POWER ones
+    int indirect_rr_bvh_blocks_per_cu[2][2];   // ... and of the roulette ones, [mis][power]
     unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
     unsigned int* trav_dev;  // ... as the device addresses it
     // ---- fused-render workspace: the STREAMING renderer (render_part, plan_chunks, the ring).  A render walks its frames in chunks of
@@ -366,6 +367,8 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->direct_power_bvh_blocks_per_cu = ptk_direct_power_bvh_blocks_per_cu();
     d->indirect_power_bvh_blocks_per_cu = ptk_indirect_power_bvh_blocks_per_cu(false);
     d->indirect_power_mis_bvh_blocks_per_cu = ptk_indirect_power_bvh_blocks_per_cu(true);
+    for (int mis = 0; mis < 2; ++mis)
+        for (int power = 0; power < 2; ++power) d->indirect_rr_bvh_blocks_per_cu[mis][power] = ptk_indirect_rr_bvh_blocks_per_cu(mis != 0, power != 0);
     *out = d;
     return PT_OK;
 }
@@ -1776,10 +1779,10 @@ static_assert(sizeof(pt_indirect_params) == 64, "pt_indirect_params layout");
 // `a`: the fields the parameter blocks share (each entry point has looked at its own reserved ones).  max_bounces: 0 = direct
 // illumination (its own kernels), otherwise the depth of an indirect render.  mis: the MIS estimator, which reads light_counts (NULL
 // otherwise).  table: NULL = the uniform choice, otherwise {cdf, tri_q} of pt_light_table, the choice by power.  what: the message
-// for a field out of range
+// for a field out of range.  rr: NULL, or the roulette of pt_render_indirect_rr (checked by it; max_bounces > 0): the launch is ptk_indirect_rr
 static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts, bool mis,
                       pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params& a, int max_bounces, const char* what,
-                      const pt_camera* cam, pt_event_t ev, const pt_buffer_t* table = nullptr)
+                      const pt_camera* cam, pt_event_t ev, const pt_buffer_t* table = nullptr, const pt_roulette* rr = nullptr)
 {
     const bool power = table != nullptr;
     pt_buffer_t cdf = power ? table[0] : nullptr, tri_q = power ? table[1] : nullptr;
@@ -1847,9 +1850,13 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     PtSearch search;
     if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
     if ((rc = event_begin(d, ev))) return rc;
-    PtIndirectPowerParams ip;
+    PtIndirectRrParams ip;   // (every indirect block is a base of it)
     memset(&ip, 0, sizeof ip);
     ip.B = max_bounces;
+    if (rr) {
+        ip.R = rr->first_bounce;
+        ip.cap = rr->max_survival;
+    }
     PtDirectParams& p = ip.d;
     search_fields(d, search, p.t);   // (an empty scene: the brute-force form over zero triangles, every sample the background)
     image_geometry(p.t, a.width, a.height, a.stripe_rows, a.n_ranks, a.rank, npix);
@@ -1871,7 +1878,8 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     fp.rad = p.samples;
     fp.fb = (float4*)framebuffer->dptr;
     fp.npix_local = npix;
-    const int per_cu = power ? (mis ? d->indirect_power_mis_bvh_blocks_per_cu
+    const int per_cu = rr ? d->indirect_rr_bvh_blocks_per_cu[mis][power] :
+                       power ? (mis ? d->indirect_power_mis_bvh_blocks_per_cu
                                     : max_bounces > 0 ? d->indirect_power_bvh_blocks_per_cu : d->direct_power_bvh_blocks_per_cu)
                              : (mis ? d->indirect_mis_bvh_blocks_per_cu : max_bounces > 0 ? d->indirect_bvh_blocks_per_cu : d->direct_bvh_blocks_per_cu);
     const int bvh_blocks = !search.mode.bvh ? 0 : d->prop.multiProcessorCount * per_cu;   // (each kernel its own grid: pt_kernels.h)
@@ -1886,7 +1894,8 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
             dp.cdf = ip.cdf;
             dp.tri_q = ip.tri_q;
         }
-        HIP_TRY(power ? (max_bounces > 0 ? ptk_indirect_power(ip, bvh_blocks, search.mode, mis, d->stream) : ptk_direct_power(dp, bvh_blocks, search.mode, d->stream))
+        HIP_TRY(rr ? ptk_indirect_rr(ip, bvh_blocks, search.mode, mis, power, d->stream) :
+                power ? (max_bounces > 0 ? ptk_indirect_power(ip, bvh_blocks, search.mode, mis, d->stream) : ptk_direct_power(dp, bvh_blocks, search.mode, d->stream))
                       : (max_bounces > 0 ? ptk_indirect(ip, bvh_blocks, search.mode, mis, d->stream) : ptk_direct(p, bvh_blocks, search.mode, d->stream)));
         fp.frame_begin = p.frame0;
         fp.frame_count = nf;
@@ -1913,7 +1922,7 @@ extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_
 // pt_render_indirect and pt_render_indirect_mis: the same parameter block, the same checks of it
 static int render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts, bool mis,
                            pt_buffer_t samples, pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev,
-                           const pt_buffer_t* table = nullptr)
+                           const pt_buffer_t* table = nullptr, const pt_roulette* rr = nullptr)
 {
     int rc = use_device(d);
     if (rc) return rc;
@@ -1929,7 +1938,7 @@ static int render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t mat
     a.light_samples = b.light_samples;
     a.stripe_rows = b.stripe_rows; a.n_ranks = b.n_ranks; a.rank = b.rank;
     return render_lit(d, triangles, materials, lights, light_counts, mis, samples, framebuffer, a, b.max_bounces,
-                      "invalid indirect-illumination parameters", cam, ev, table);
+                      "invalid indirect-illumination parameters", cam, ev, table, rr);
 }
 
 extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
@@ -1967,6 +1976,27 @@ extern "C" int pt_render_indirect_power(pt_device_t d, pt_buffer_t triangles, pt
     if (mis != 0 && mis != 1) return fail(PT_ERR_INVALID, "mis must be 0 or 1");
     const pt_buffer_t table[2] = { cdf, tri_q };
     return render_indirect(d, triangles, materials, lights, mis ? light_counts : nullptr, mis != 0, samples, framebuffer, params, cam, ev, table);
+}
+
+// ---- Russian roulette (include/pt_shim.h) ------------------------------------------------------------------------------------------
+static_assert(sizeof(pt_roulette) == 16, "pt_roulette layout");
+
+extern "C" int pt_render_indirect_rr(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
+                                     pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
+                                     const pt_indirect_params* params, const pt_roulette* roulette, const pt_camera* cam, pt_event_t ev)
+{
+    if (mis != 0 && mis != 1) return fail(PT_ERR_INVALID, "mis must be 0 or 1");
+    if (!roulette) return fail(PT_ERR_INVALID, "roulette == NULL");
+    const pt_roulette r = *roulette;
+    if (r.first_bounce < 1) return fail(PT_ERR_INVALID, "first_bounce must be at least 1");
+    if (!(r.max_survival > 0.0f && r.max_survival <= 1.0f)) return fail(PT_ERR_INVALID, "max_survival must lie in (0, 1]");   // (false for NaN)
+    if (r.reserved[0] != 0 || r.reserved[1] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    const bool power = cdf || tri_q;   // both NULL: the uniform choice
+    if (params && params->num_lights > 0 && power && !(cdf && tri_q))
+        return fail(PT_ERR_INVALID, "the light table is cdf AND tri_q (pt_light_table), or neither for the uniform choice");
+    const pt_buffer_t table[2] = { cdf, tri_q };
+    return render_indirect(d, triangles, materials, lights, mis ? light_counts : nullptr, mis != 0, samples, framebuffer, params, cam, ev,
+                           power ? table : nullptr, &r);
 }
 
 extern "C" size_t pt_light_table_bytes(int num_lights)

@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power] | --only IndirectIllumination [--mis] [--lights power]] [--noise]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power] | --only IndirectIllumination [--mis] [--lights power] [--roulette R[,cap]]] [--noise]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <chrono>
 #include <cmath>
@@ -119,6 +119,8 @@ struct Options {
     int deviceIdx = 0, dim = 512, frames = 10000;
     bool batch = true, mis = false;   // mis: IndirectIllumination through pt_render_indirect_mis
     bool power = false;               // --lights power: DirectIllumination / IndirectIllumination choose their lights by power
+    int rrFirst = 0;                  // --roulette R[,cap]: IndirectIllumination through pt_render_indirect_rr (0 = no roulette)
+    float rrCap = 0.95f;
     bool noise = false;               // --noise: DirectIllumination / IndirectIllumination print the image's noise summary
     std::string scene = "cornellbox.bin", outDir = ".", dump, only;
 };
@@ -370,6 +372,8 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
 // pt_light_counts -- written to indirectIllumination_<version>_mis.ppm.
 // With --lights power either case chooses its lights in proportion to their emitted power (pt_render_direct_power,
 // pt_render_indirect_power, the table made by pt_light_table) and the file's name ends in _power.ppm (_mis_power.ppm with --mis).
+// With --roulette R[,cap] IndirectIllumination goes through pt_render_indirect_rr -- Russian roulette from vertex R on with survival at
+// most cap (0.95 unless given), under --mis and --lights power as they are set -- and the file's name gains _rr before .ppm.
 // With --noise either case renders in calls of at most as many frames as the workspace holds, takes the samples' moments after each
 // (pt_sample_moments) and prints one more line, after the case's own: the summary of pt_moments_resolve.  The image is the same.
 // bounces: 0 = DirectIllumination, otherwise IndirectIllumination at that depth.
@@ -424,6 +428,11 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     q.max_bounces = bounces;
     auto t0 = std::chrono::steady_clock::now();
     const bool mis = bounces && o.mis;
+    const bool rr = bounces && o.rrFirst > 0;
+    pt_roulette roulette;
+    std::memset(&roulette, 0, sizeof roulette);
+    roulette.first_bounce = o.rrFirst;
+    roulette.max_survival = o.rrCap;
     pt_buffer_t lh = lights.empty() ? 0 : lBuffer.m_handle;
     if (o.power)
         IASSERT(pt_light_table(m_d->m_handle, tBuffer.m_handle, p.num_triangles, mBuffer.m_handle, p.num_materials, lh, p.num_lights, cdf.m_handle,
@@ -433,6 +442,9 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     auto render = [&](int first, int count) {
         p.frame_begin = q.frame_begin = first;
         p.frame_count = q.frame_count = count;
+        if (rr)
+            return pt_render_indirect_rr(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0,
+                                         o.power ? cdf.m_handle : 0, o.power ? triq.m_handle : 0, samples.m_handle, image.m_handle, &q, &roulette, 0, 0);
         if (o.power && bounces)
             return pt_render_indirect_power(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0, cdf.m_handle,
                                             triq.m_handle, samples.m_handle, image.m_handle, &q, 0, 0);
@@ -459,9 +471,12 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     rgb.read(h.data(), 3 * npix);
     DeviceUtils::waitForCompletion(m_d);
     double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (bounces)
-        std::printf("IndirectIllumination%s%s: %d x %d x %d frames, %d bounces, K = 1, %d lights in %.3f s\n", mis ? " (MIS)" : "",
-                    o.power ? " (lights by power)" : "", dimension, dimension, o.frames, bounces, (int)lights.size(), secs);
+    if (bounces) {
+        char rrText[64] = "";
+        if (rr) std::snprintf(rrText, sizeof rrText, " (roulette from %d, at most %g)", o.rrFirst, (double)o.rrCap);
+        std::printf("IndirectIllumination%s%s%s: %d x %d x %d frames, %d bounces, K = 1, %d lights in %.3f s\n", mis ? " (MIS)" : "",
+                    o.power ? " (lights by power)" : "", rrText, dimension, dimension, o.frames, bounces, (int)lights.size(), secs);
+    }
     else
         std::printf("DirectIllumination%s: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", o.power ? " (lights by power)" : "", dimension, dimension,
                     o.frames, (int)lights.size(), secs);
@@ -481,6 +496,7 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     f.getFilePath(o.outDir.c_str(), bounces ? "indirectIllumination" : "directIllumination", "ppm", path, sizeof path);
     if (mis && std::strlen(path) + 5 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_mis.ppm");
     if (o.power && std::strlen(path) + 7 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_power.ppm");
+    if (rr && std::strlen(path) + 4 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_rr.ppm");
     FILE* fp = std::fopen(path, "w");
     IASSERT(fp != 0);
     if (fp) {
@@ -507,6 +523,16 @@ int main(int argc, char** argv)
         else if (a == "--no-batch") o.batch = false;
         else if (a == "--mis") o.mis = true;
         else if (a == "--noise") o.noise = true;
+        else if (a == "--roulette") {
+            const std::string v = next();
+            char* end = 0;
+            o.rrFirst = (int)std::strtol(v.c_str(), &end, 10);
+            if (end && *end == ',') o.rrCap = std::strtof(end + 1, &end);
+            if (o.rrFirst < 1 || !end || *end != 0 || !(o.rrCap > 0.0f && o.rrCap <= 1.0f)) {
+                std::fprintf(stderr, "--roulette takes R[,cap] with R >= 1 and cap in (0, 1]\n");
+                return 2;
+            }
+        }
         else if (a == "--lights") {
             const std::string v = next();
             if (v != "uniform" && v != "power") { std::fprintf(stderr, "--lights takes uniform or power\n"); return 2; }

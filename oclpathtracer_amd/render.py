@@ -184,7 +184,7 @@ class Renderer:
 
     def indirect_renderer(self, **kw):
         """An :class:`indirect.IndirectRenderer` over this renderer's buffers, as :meth:`direct_renderer` gives a DirectRenderer
-        (keyword arguments: IndirectRenderer's, ``max_bounces``, ``mis``, ``light_choice`` and ``moments`` among them)."""
+        (keyword arguments: IndirectRenderer's, ``max_bounces``, ``mis``, ``light_choice``, ``roulette`` and ``moments`` among them)."""
         from .indirect import IndirectRenderer
 
         return self._lit_renderer(IndirectRenderer, kw)

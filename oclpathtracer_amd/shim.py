@@ -138,6 +138,13 @@ class BvhInfo(_c.Structure):
 PT_BVH_SNAPSHOT_BIG_MAX = 64
 
 
+class Roulette(_c.Structure):
+    """pt_roulette (16 bytes): the Russian roulette of pt_render_indirect_rr -- played from vertex first_bounce on (counted from 1), with
+    survival probability min(largest channel of the throughput, max_survival); reserved must be 0."""
+
+    _fields_ = [("first_bounce", _c.c_int32), ("max_survival", _c.c_float), ("reserved", _c.c_int32 * 2)]
+
+
 class PixelMoments(_c.Structure):
     """pt_pixel_moments (56 bytes): per channel the sum and the sum of squares of a pixel's finite samples, their number, and the
     number of samples rejected for a NaN or an infinity."""
@@ -215,6 +222,8 @@ SIGNATURES = {
     "pt_light_table": (_c.c_int, [_H, _H, _c.c_int, _H, _c.c_int, _H, _c.c_int, _H, _H, _H]),
     "pt_render_direct_power": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(DirectParams), _c.POINTER(Camera), _H]),
     "pt_render_indirect_power": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Camera), _H]),
+    "pt_render_indirect_rr": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Roulette),
+                                         _c.POINTER(Camera), _H]),
     "pt_sample_moments": (_c.c_int, [_H, _H, _H, _c.c_uint32, _c.c_int32, _c.c_int, _H]),
     "pt_moments_summary_bytes": (_c.c_size_t, [_c.c_uint32]),
     "pt_moments_resolve": (_c.c_int, [_H, _H, _c.c_uint32, _H, _H, _H]),

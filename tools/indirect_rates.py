@@ -9,7 +9,13 @@ it.  The sample workspace holds all 16 frames, so an indirect render is one laun
 The K = 0 figure against the renderer's is what the brute-force kernel's missing lane regeneration costs.
 With --lights power the legs are those of light choice by power instead: K = 1 and K = 4, plain and MIS, each with the uniform choice
 and with the choice by power (pt_render_indirect_power) -- the same warm-up and single timed run per leg.
-usage: python tools/indirect_rates.py [--lights power] [out.txt]"""
+With --roulette the legs are those of Russian roulette (pt_render_indirect_rr, R = 3 and cap = 0.95 unless --roulette-setting R,cap says
+otherwise): on the Cornell box and on the 10^6-triangle soup with every 64th material emissive, K = 0 (no lights), 1 and 4, plain and
+MIS, three renders each in the same process -- the parent entry point, pt_render_indirect_rr with first_bounce = B (no roulette is
+played: on the Cornell box the parent's image by the REFILLING brute-force kernel, so its rate against the parent's is what the missing
+lane regeneration costs) and pt_render_indirect_rr with the roulette.  Each also renders once with moments=True, and the leg reports
+efficiency = 1 / (variance per sample x time per sample) without and with roulette.
+usage: python tools/indirect_rates.py [--lights power | --roulette [--roulette-setting R,cap]] [out.txt]"""
 import os
 import sys
 import time
@@ -26,6 +32,14 @@ power = "--lights" in sys.argv
 if power:
     at = sys.argv.index("--lights")
     assert sys.argv[at + 1: at + 2] == ["power"], "--lights takes power"
+    del sys.argv[at: at + 2]
+roulette = "--roulette" in sys.argv
+if roulette:
+    sys.argv.remove("--roulette")
+RR_SETTING = (3, 0.95)
+if "--roulette-setting" in sys.argv:
+    at = sys.argv.index("--roulette-setting")
+    RR_SETTING = (int(sys.argv[at + 1].split(",")[0]), float(sys.argv[at + 1].split(",")[1]))
     del sys.argv[at: at + 2]
 out_path = sys.argv[1] if len(sys.argv) > 1 else None
 W = H = 1024
@@ -54,9 +68,44 @@ def report(name, t):
     return n / t
 
 
+def roulette_legs(dev):
+    from oclpathtracer_amd.indirect import Roulette
+
+    soup_t, soup_m = scene.make_soup()
+    soup_m["emissive"][18::64, :3] = 30.0          # every 64th soup material emits (tools/direct_rates.py's soup)
+    emit("%s; %d x %d, %d frames, B = %d, roulette R = %d cap = %g; one warm-up and one timed run per render; variance per sample from the "
+         "renderer's moments over the same %d frames" % ((dev.getDeviceName(), W, H, FRAMES, B) + RR_SETTING + (FRAMES,)))
+    for scene_name, (t, m) in (("Cornell box", scene.load_model()), ("soup, %d triangles" % len(soup_t), (soup_t, soup_m))):
+        for K, mis in ((0, False), (1, False), (1, True), (4, False), (4, True)):
+            lights = np.zeros(0, np.int32) if K == 0 else None
+            fig = {}
+            for what, rr in (("parent entry point", None), ("rr, first_bounce = B (no roulette)", Roulette(B, 1.0)), ("rr, roulette", Roulette(*RR_SETTING))):
+                kw = dict(light_samples=max(K, 1), lights=lights, max_bounces=B, stripe_rows=1, chunk_frames=FRAMES, mis=mis, roulette=rr)
+                ir = IndirectRenderer(dev, t, m, W, H, **kw)
+                im = IndirectRenderer(dev, t, m, W, H, moments=True, **kw)
+                try:
+                    sec = once(dev, lambda: ir.render(FRAMES, 0))
+                    im.render(FRAMES, 0)
+                    var = im.noise().variance_per_sample
+                finally:
+                    ir.release()
+                    im.release()
+                name = "%s K = %d%s: %s" % (scene_name, K, " MIS" if mis else "", what)
+                rate = W * H * FRAMES / sec
+                fig[what] = (rate, var)
+                emit("%-72s %9.3f ms  %9.1f Msamples/s  variance per sample %-11.5g efficiency %.5g" % (name, sec * 1e3, rate / 1e6, var, rate / var))
+            parent = fig["parent entry point"]
+            for what in list(fig)[1:]:
+                emit("%-72s %9.3f of the parent's rate, %.3f of its variance per sample, %.3f of its efficiency"
+                     % ("", fig[what][0] / parent[0], fig[what][1] / parent[1], (fig[what][0] / fig[what][1]) / (parent[0] / parent[1])))
+
+
 assert adl.init()
 dev = adl.DeviceUtils.allocate()
 try:
+    if roulette:
+        roulette_legs(dev)
+        sys.exit(0)
     tris, mats = scene.load_model()
     emit("%s; Cornell box, %d x %d, %d frames, B = %d; one warm-up and one timed run per leg" % (dev.getDeviceName(), W, H, FRAMES, B))
     r = Renderer(dev, tris, mats, W, H, stripe_rows=1)

@@ -11,7 +11,10 @@ Rates (second output file): every one of those renders timed with and without mo
 around the enqueue and the synchronise that ends it; the first run of each pair is a warm-up and is not counted), and
 pt_sample_moments alone by device events on a full workspace against the time its bytes need at 6.29 TB/s (the samples it reads, 12 B
 each, plus the 56-byte record read and written per pixel).
-No figure is gated.  usage: python tools/variance_rates.py [variance.txt [rates.txt]] [--frames N] [--sizes 256,1024]"""
+With --roulette the legs are Russian roulette's instead (IndirectRenderer(roulette=Roulette(3, 0.95))): Cornell box, B = 16, K = 1 and 4,
+plain and MIS, without against with roulette -- the variance per sample, its ratio, and the efficiency 1 / (variance per sample x time
+per sample) of both from the timed renders without moments.
+No figure is gated.  usage: python tools/variance_rates.py [variance.txt [rates.txt]] [--frames N] [--sizes 256,1024] [--roulette]"""
 import os
 import sys
 import time
@@ -38,6 +41,9 @@ def option(name, default):
     return default
 
 
+ROULETTE = "--roulette" in args
+if ROULETTE:
+    args.remove("--roulette")
 FRAMES = int(option("--frames", 256))
 SIZES = [int(s) for s in str(option("--sizes", "256,1024")).split(",")]
 REPS = 3
@@ -77,6 +83,7 @@ def leg(dev, name, make, size):
              % (name, size, a * 1e3, n / a / 1e6, b * 1e3, n / b / 1e6, b / a, -(-FRAMES // with_m.chunk_frames), with_m.chunk_frames))
         emit(var_path, "%-58s %5d^2  variance_per_sample %-12.6g relative_error %-10.4g pixels %d samples %d rejected %d"
              % (name, size, fig.variance_per_sample, fig.relative_error, fig.pixels, fig.samples, fig.rejected))
+        leg.seconds_per_sample = a / n       # (of the render without moments: what the efficiency figures use)
         return fig
     finally:
         with_m.release()
@@ -116,6 +123,24 @@ try:
     emit(var_path, head)
     emit(rate_path, head + "; medians of %d alternating runs after one warm-up pair" % REPS)
     tris, mats = scene.load_model()
+    if ROULETTE:
+        from oclpathtracer_amd.indirect import Roulette
+
+        for size in SIZES:
+            for K in (1, 4):
+                for mis in (False, True):
+                    fig, eff = {}, {}
+                    for rr in (None, Roulette(3, 0.95)):
+                        name = "Cornell box K = %d %s, %s" % (K, "MIS" if mis else "plain", "roulette from 3, at most 0.95" if rr else "no roulette")
+                        fig[rr] = leg(dev, name, lambda s, m: IndirectRenderer(dev, tris, mats, s, s, max_bounces=16, light_samples=K, mis=mis, roulette=rr,
+                                                                               stripe_rows=1, moments=m), size)
+                        eff[rr] = 1.0 / (fig[rr].variance_per_sample * leg.seconds_per_sample)
+                        emit(var_path, "%-58s %5d^2  efficiency %.5g per second" % (name, size, eff[rr]))
+                    rr = Roulette(3, 0.95)
+                    ratio("Cornell box K = %d %s roulette / none" % (K, "MIS" if mis else "plain"), fig[rr], fig[None], size)
+                    emit(var_path, "%-58s %5d^2  efficiency ratio %.4g" % ("Cornell box K = %d %s roulette / none" % (K, "MIS" if mis else "plain"), size,
+                                                                            eff[rr] / eff[None]))
+        sys.exit(0)
     for size in SIZES:
         for K in (1, 4):
             fig = {}
