@@ -383,6 +383,9 @@ PTK_DEV PtTriRec pt_load_tri(pt_const_f32p T, int i)
 // the conjunction is then an s_and_b64), never as per-lane booleans.
 typedef unsigned long long pt_lanes;
 #define PT_LANES(cond) __builtin_amdgcn_ballot_w64(cond)
+// the other direction: this lane's bit of a wave-uniform mask as a condition -- the mask itself becomes the exec mask or the select's
+// condition operand, no per-lane 0/1 is formed
+#define PT_ON(mask) __builtin_amdgcn_inverse_ballot_w64(mask)
 PTK_DEV unsigned pt_push_flag(unsigned m, pt_lanes c)
 {
     unsigned long long carry_out;
@@ -774,7 +777,17 @@ PTK_DEV void pt_quad3_pass1(pt_const_f32p t, const PtRay3& r, pt_f2& un, pt_f2& 
 #endif
 
 // QUADS: 0 = independent triangles (pt_tri_pass1), 3 = packed shared-u filter (pt_quad3_pass1)
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
+// UNIT_DIR: the caller vouches for |d|^2 <= 1.001, the shared-u bound's assumption about the direction, and the filter does not test
+// it.  Only pt_trace_body does: every direction a path of the trace kernels holds is the output of normalize3 / normalize3_unit
+// (pt_generate_ray, the two exits of pt_shade_path) -- a correctly rounded quotient or product per component, |d|^2 within 1 +- 4e-7 --
+// or that of pt_path_idle, and a parked or carried path brings those same bits back (pt_path_store / pt_path_load move dwords).  What
+// normalising can make instead of a unit vector: the zero vector (|d|^2 = 0 passed the test anyway); a NaN component (a zero or NaN
+// vector normalised), which makes un NaN for every quad -- it fails every comparison of the filter and is kept; an infinite component
+// (a non-zero vector whose squared length underflows), with which the exact test's det is +-inf or NaN and its t = x * RN(1 / det) is
+// +-0 or NaN for every triangle: the reference accepts no hit for such a ray, so nothing the filter drops is missed.  Rays that
+// callers supply or kernels derive (queries, AO, the lit renderers, the LBVH kernels' big-triangle table) keep the test.  The origin's
+// half of `tame` is tested everywhere.
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool UNIT_DIR = false>
 PTK_DEV unsigned pt_intersect_two_pass(pt_const_f32p T, const PtPrepTriangle* tris, int ntri, const f3& o, const f3& d,
                                        bool alive, float& tmax, float& hu, float& hv, int& hidx,
                                        float delta1, float ray_radius, pt_const_f32p p1tab, float p1_lo, float p1_hi, const f3& anchor,
@@ -798,9 +811,14 @@ PTK_DEV unsigned pt_intersect_two_pass(pt_const_f32p T, const PtPrepTriangle* tr
         r3v.dxy = pt_f2{ d.x, d.y }; r3v.dzMx = pt_f2{ d.z, M.x }; r3v.Myz = pt_f2{ M.y, M.z };
     }
     if (QUADS == 3 && DET_BOUNDED) {
-        float dd = pt_fma(d.z, d.z, pt_fma(d.y, d.y, d.x * d.x));
-        tame = (dd <= 1.001f) & (__builtin_fabsf(o.x - anchor.x) <= ray_radius) &
-               (__builtin_fabsf(o.y - anchor.y) <= ray_radius) & (__builtin_fabsf(o.z - anchor.z) <= ray_radius);
+        if (UNIT_DIR) {
+            tame = (__builtin_fabsf(o.x - anchor.x) <= ray_radius) & (__builtin_fabsf(o.y - anchor.y) <= ray_radius) &
+                   (__builtin_fabsf(o.z - anchor.z) <= ray_radius);
+        } else {
+            float dd = pt_fma(d.z, d.z, pt_fma(d.y, d.y, d.x * d.x));
+            tame = (dd <= 1.001f) & (__builtin_fabsf(o.x - anchor.x) <= ray_radius) &
+                   (__builtin_fabsf(o.y - anchor.y) <= ray_radius) & (__builtin_fabsf(o.z - anchor.z) <= ray_radius);
+        }
     }
     for (int base = 0; base < ntri; base += 32) {
         const int n = ntri - base < 32 ? ntri - base : 32;
@@ -975,8 +993,10 @@ PTK_DEV unsigned pt_ring_offset(unsigned lp, unsigned frame)
 
 
 // ---- shade one bounce of a live path (:229-258); on path end store its radiance --------------------
+// Returns true when the path has finished (its radiance is stored, what is left in `s` is dead).  The caller decides how it keeps
+// "alive": the table kernels as a wave-uniform lane mask (pt_trace_body), the LBVH kernel as a per-lane flag (pt_shade below).
 template <bool DET_BOUNDED, bool LATE>
-PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax, float hu, float hv, int hidx)
+PTK_DEV bool pt_shade_path(const PtTraceParams& P, PtPath& s, float tmax, float hu, float hv, int hidx)
 {
     const pt_kargs_p K = pt_kargs();  // tris, mats, nmat, max_bounces: read here, not kept in SGPRs
     bool finished = false;
@@ -1125,8 +1145,15 @@ PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax
             float* out = (r < S ? rad : KR->rad1) + ((size_t)(r < S ? r : r - S) * KR->npix_local + s.ro) * 3u;
             *reinterpret_cast<pt_f3v*>(out) = v;
         }
-        alive = false;
     }
+    return finished;
+}
+
+// the same with a per-lane flag that a finished path clears (the LBVH kernel's call site)
+template <bool DET_BOUNDED, bool LATE>
+PTK_DEV void pt_shade(const PtTraceParams& P, PtPath& s, bool& alive, float tmax, float hu, float hv, int hidx)
+{
+    if (pt_shade_path<DET_BOUNDED, LATE>(P, s, tmax, hu, hv, hidx)) alive = false;
 }
 
 // (n_rays, n_samples: wave-uniform tallies kept in SGPRs -- popcounts of the lanes that shaded / finished; as per-lane counters they
@@ -1260,20 +1287,21 @@ PTK_DEV void pt_path_load(const PtPathSlots& S, unsigned k, PtPath& s)
     s.bounce = (int)(w2 >> 16);
 }
 
-PTK_DEV void pt_pool_push(float4* pool, unsigned& pool_n, const PtPath& s, bool& alive)
+// (alive: the wave's live lanes as a lane mask, here and in pt_pool_pop / pt_start_fresh -- see pt_trace_body)
+PTK_DEV void pt_pool_push(float4* pool, unsigned& pool_n, const PtPath& s, pt_lanes& alive)
 {
-    const unsigned long long live = __ballot(alive);
-    if (alive) {
+    const pt_lanes live = alive;
+    if (PT_ON(live)) {
         const unsigned k = pool_n + pt_mbcnt(live);
         pt_path_store(pt_pool_slots(pool), k, s);
     }
     pool_n += (unsigned)__popcll(live);
-    alive = false;
+    alive = 0ull;
 }
 
-PTK_DEV void pt_pool_pop(float4* pool, unsigned& pool_n, PtPath& s, bool& alive)
+PTK_DEV void pt_pool_pop(float4* pool, unsigned& pool_n, PtPath& s, pt_lanes& alive)
 {
-    const unsigned long long need = __ballot(!alive);
+    const pt_lanes need = ~alive;
     const unsigned n_need = (unsigned)__popcll(need);
     const unsigned take = n_need < pool_n ? n_need : pool_n;
     if (take == 0u) return;
@@ -1283,11 +1311,12 @@ PTK_DEV void pt_pool_pop(float4* pool, unsigned& pool_n, PtPath& s, bool& alive)
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const unsigned rank = pt_mbcnt(need);
-    if (!alive && rank < take) {
+    const pt_lanes taking = need & PT_LANES(rank < take);   // the first `take` dead lanes
+    if (PT_ON(taking)) {
         const unsigned k = pool_n - 1u - rank;
         pt_path_load(pt_pool_slots(pool), k, s);
-        alive = true;
     }
+    alive |= taking;
     pool_n -= take;
     // reads of the slots just released must complete before a later push overwrites them: same in-order queue
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1368,7 +1397,7 @@ PTK_DEV void pt_carry_load(const PtTraceParams& P, uint32_t* region, unsigned la
 // own, polled by one lane per wave and fresh phase), and this wave holds nothing of the PREVIOUS launch's chunk any more, whose
 // fold follows this launch.
 template <bool LATE>
-PTK_DEV int pt_queue_next(const PtTraceParams& P, unsigned lane, PtWaveQueue& q, const PtPath& s, bool alive)
+PTK_DEV int pt_queue_next(const PtTraceParams& P, unsigned lane, PtWaveQueue& q, const PtPath& s, pt_lanes alive)
 {
     const pt_kargs_p K = pt_kargs();
     unsigned empty_mask = 0u;
@@ -1376,7 +1405,7 @@ PTK_DEV int pt_queue_next(const PtTraceParams& P, unsigned lane, PtWaveQueue& q,
         if (lane == 0u) empty_mask = __hip_atomic_load(PT_ARG(batch_counter) + PT_QUEUE_STOP_WORD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         empty_mask = (unsigned)__builtin_amdgcn_readfirstlane(empty_mask);
         // (of the previous chunk: a batch under way, paths in lanes -- the pool is empty)
-        if (empty_mask == (1u << PT_QUEUE_SHARDS) - 1u && !(q.pix != q.end && q.frame < PT_ARG(chunk_f0)) && __ballot(alive && s.fl < PT_ARG(chunk_f0)) == 0ull)
+        if (empty_mask == (1u << PT_QUEUE_SHARDS) - 1u && !(q.pix != q.end && q.frame < PT_ARG(chunk_f0)) && (alive & PT_LANES(s.fl < PT_ARG(chunk_f0))) == 0ull)
             return 2;
     }
     return pt_queue_refill<LATE>(P, lane, q, empty_mask) ? 1 : 0;
@@ -1422,7 +1451,7 @@ PTK_DEV void pt_sample_begin(const PtTraceParams& P, pt_kargs_p K, unsigned x, u
 // returns true when all 64 lanes started a primary ray; pix0 (wave-uniform): lane k's sample is local pixel pix0 + k -- what the primary
 // rays' candidate masks are indexed by (a path does not keep its pixel: PtPath::ro)
 template <bool LATE>
-PTK_DEV bool pt_start_fresh(const PtTraceParams& P, unsigned lane, PtWaveQueue& q, PtPath& s, bool& alive, unsigned& pix0)
+PTK_DEV bool pt_start_fresh(const PtTraceParams& P, unsigned lane, PtWaveQueue& q, PtPath& s, pt_lanes& alive, unsigned& pix0)
 {
     const pt_kargs_p K = pt_kargs();
     pix0 = q.pix;
@@ -1441,8 +1470,8 @@ PTK_DEV bool pt_start_fresh(const PtTraceParams& P, unsigned lane, PtWaveQueue& 
             grow = pt_stripe_row<LATE>(P, K, sl, within);
         }
         pt_sample_begin<LATE>(P, K, x, grow, q.pix + lane, q.frame, s);
-        alive = true;
     }
+    alive = count == 64u ? ~0ull : (1ull << count) - 1ull;   // lanes 0 .. count - 1 (every lane was dead: scalar work)
     q.pix += count;
     q.col += count;
     while (q.col >= W) {
@@ -1503,6 +1532,9 @@ template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ 
 template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ unsigned pt_lds_tiles(int ntri) { return pt_lds_tails<LDS_TABLE, POOLS>(ntri) + (PT_TRACE_THREADS / 64) * pt_lds_tail_dw<LDS_TABLE>(); }
 template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ unsigned pt_lds_total(int ntri) { return pt_lds_tiles<LDS_TABLE, POOLS>(ntri) + (LDS_TABLE == 2 ? (PT_TRACE_THREADS / 64) * PT_LDS_TILE_DW : 0u); }
 
+#ifndef PT_TRACE_UNIT_DIR
+#define PT_TRACE_UNIT_DIR 1  // 0: the trace kernels' filter tests |d|^2 as every other kernel's does (A/B builds, tools/build_variant.sh)
+#endif
 template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
 PTK_DEV void pt_trace_body(const PtTraceParams& P)
 {
@@ -1521,12 +1553,19 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
                              pt_lds_tiles<LDS_TABLE>(ntri) + (threadIdx.x >> 6) * PT_LDS_TILE_DW, lane);
 
     PtWaveQueue q = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };   // wave-uniform (SGPRs)
-    bool alive = false;
+    // Which lanes hold a live path: a wave-uniform LANE MASK (an SGPR pair), changed by scalar instructions where paths park, resume,
+    // start and finish, and used as it is where lanes are selected by it (PT_ON) -- not a per-lane 0/1 in a VGPR that every such
+    // place first compares into a mask and selects back out of one.
+    pt_lanes alive = 0ull;
     PtPath s = pt_path_idle();
     unsigned n_rays = 0, n_samples = 0, n_carried = 0;   // (n_carried: samples this wave's checkpoints have handed on, PT_STAT_CARRIED)
     // checkpointed launches: resume what the previous launch of the render left in this wave's region
     const unsigned wave = pt_wave();
-    if (wave < P.carry_in_waves) pt_carry_load<true>(P, pt_carry_region(P.carry, wave), lane, s, alive, q, n_rays, n_samples, n_carried);
+    if (wave < P.carry_in_waves) {
+        bool resumed = false;
+        pt_carry_load<true>(P, pt_carry_region(P.carry, wave), lane, s, resumed, q, n_rays, n_samples, n_carried);
+        alive = PT_LANES(resumed);
+    }
     q.g = wave & (PT_QUEUE_SHARDS - 1u);   // the wave's first shard of this launch's queue
 #if PT_STAMPS
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, c_regen = 0, c_loop = 0, c_shade = 0, c_iters = 0, c_steps = 0, c_p1 = 0;
@@ -1536,7 +1575,7 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         PT_STAMP(t0);
         bool primary = false;   // (wave-uniform) this bounce is a fresh wave of 64 primary rays ...
         unsigned pix0 = 0u;     // ... of the local pixels pix0 + lane
-        if (__ballot(!alive) != 0ull) {
+        if (~alive != 0ull) {
             if (pool_n == 0u) {
                 const int next = pt_queue_next<true>(P, lane, q, s, alive);
                 if (next != 0) {
@@ -1547,7 +1586,7 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
             }
             pt_pool_pop(pool, pool_n, s, alive);           // dead lanes resume parked paths
         }
-        if (__ballot(alive) == 0ull) break;
+        if (alive == 0ull) break;
         PT_STAMP(t1);
 
         // ---- intersectWorld (:137-154) ------------------------------------------------------
@@ -1555,10 +1594,10 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         int hidx = -1;
         unsigned p2steps = 0;
         if (QUADS == 3 && DET_BOUNDED && primary && P.pmask != nullptr)
-            p2steps = pt_intersect_primary<DET_BOUNDED, LDS_TABLE>(T, P.tris, ntri, s.o, s.d, alive, tmax, hu, hv, hidx, P.pmask[pix0 + lane], tl, lane,
+            p2steps = pt_intersect_primary<DET_BOUNDED, LDS_TABLE>(T, P.tris, ntri, s.o, s.d, PT_ON(alive), tmax, hu, hv, hidx, P.pmask[pix0 + lane], tl, lane,
                                                                    PT_VALIDATE_FILTER && P.stats ? P.stats + 2 : nullptr);
         else
-            p2steps = pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>(T, P.tris, ntri, s.o, s.d, alive, tmax, hu, hv, hidx,
+            p2steps = pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS, PT_TRACE_UNIT_DIR != 0>(T, P.tris, ntri, s.o, s.d, PT_ON(alive), tmax, hu, hv, hidx,
                                                                                           P.quad_delta1, P.ray_radius,
                                                                                           (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, pt_anchor(), tl, lane,
                                                                                           PT_VALIDATE_FILTER && P.stats ? P.stats + 2 : nullptr,
@@ -1575,10 +1614,12 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
 #endif
 
         PT_STAMP(t2);
-        const unsigned long long shaded = __ballot(alive);
-        n_rays += (unsigned)__popcll(shaded);
-        if (alive) pt_shade<DET_BOUNDED, true>(P, s, alive, tmax, hu, hv, hidx);
-        n_samples += (unsigned)__popcll(shaded & ~__ballot(alive));   // (a path leaves pt_shade dead only when it has finished)
+        n_rays += (unsigned)__popcll(alive);
+        bool finished = false;
+        if (PT_ON(alive)) finished = pt_shade_path<DET_BOUNDED, true>(P, s, tmax, hu, hv, hidx);
+        const pt_lanes done = PT_LANES(finished);   // (a dead lane did not shade: its bit is 0)
+        n_samples += (unsigned)__popcll(done);
+        alive &= ~done;
 #if PT_STAMPS
         PT_STAMP(t3);
         c_regen += t1 - t0; c_loop += t2 - t1; c_shade += t3 - t2; c_iters++;

@@ -8,8 +8,15 @@ at the stamps, classifies every instruction between two stamps, and prints per c
     sum over phases of  (time share of the phase) x (class's share of the phase's VALU instructions)
 i.e. an estimate of the class's share of the loop's VALU issue -- exact if a phase's instructions all ran equally often (inner loops
 make it an estimate; the phases are cut so that each is dominated by one loop body).
-usage: python tools/isa_histogram.py [regen%% pass1%% pass2%% shade%%]   (default: the shares of profiles/r04/stamps_r04.txt if present)"""
-import os, re, subprocess, sys
+usage: python tools/isa_histogram.py [regen%% pass1%% pass2%% shade%%]   (default: the shares of profiles/r04/stamps_r04.txt if present)
+
+       python tools/isa_histogram.py --moves [--parent-src <a checkout's csrc>]
+The MOVE CLASS of the bounce loop of the SHIPPED build (not the PT_STAMPS one): every v_mov*, v_readlane, v_writelane, v_readfirstlane and
+v_accvgpr* of the loop with its phase, its cause and whether a default configs[2] render executes it, priced with
+profiles/r01/ubench_issue.log -- with --parent-src the same for another checkout's sources, the two summaries side by side.  The build
+carries line tables (-gline-tables-only: the instruction stream is the shipped one, which the listing's count lets one check); a basic
+block's phase is the phase of the source lines most of its instructions come from.  This mode reads assembly for these instructions only."""
+import os, re, struct, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "oclpathtracer_amd", "csrc")
 ASM = "/tmp/pt_kernels_stamps.s"
@@ -80,5 +87,178 @@ def main():
     for c, v in sorted(hist.items(), key=lambda x: -x[1]):
         print("   %-52s %5.1f %%" % (c, 100.0 * v / tot))
 
+# ---- the move class of the shipped build's bounce loop (--moves) -------------------------------------------------------------------
+# cycles per wave-instruction at 8 waves per SIMD (profiles/r01/ubench_issue.log): v_mov_b32 v,v 2.38 (a constant source is priced the
+# same; a 64-bit move as two), v_mov_b32 v,s 4.38, a lane access 4.39
+PRICE = {"constant": 2.38, "vgpr": 2.38, "sgpr": 4.38, "lane": 4.39}
+PHASES = ("regeneration", "pass 1", "pass 2", "shading")
+REGEN_FN = re.compile(r"pt_(queue_|pool_|path_|start_fresh|sample_begin|generate_ray|camera_|pixel_|stripe_row|ring_offset|carry_|mbcnt|hash)")
+PASS1_FN = re.compile(r"pt_(quad3_pass1|pk_|push_flag|tri_pass1|load_tri)")
+PASS2_FN = re.compile(r"pt_(pass2_|tri_pass2|tail_|tri_candidate|fetch_rec|from_lane|stage_tile|intersect_primary)")
+SHADE_FN = re.compile(r"pt_shade")
+
+def source_phases(src):
+    """line of pt_kernels.hip -> phase, from the function the line is in (and, inside the loop's own functions, from where in them)"""
+    lines = open(os.path.join(src, "pt_kernels.hip")).read().split("\n")
+    phase, fn, mark = {}, None, None
+    for i, l in enumerate(lines, 1):
+        m = re.match(r"^(?:PTK_DEV|void|__global__)[^;=]*?\b(pt_\w+)\s*\(", l)
+        if m and not l.rstrip().endswith(";"): fn, mark = m.group(1), None
+        if fn is None: continue
+        if fn == "pt_intersect_two_pass":
+            if "if (!alive) m = 0u" in l: mark = "pass 2"
+            phase[i] = mark or "pass 1"
+        elif fn == "pt_trace_body":
+            if "PT_STAMP(t1)" in l: mark = "pass 2"       # (the search's call: its set-up and whatever is left of it there)
+            if "PT_STAMP(t2)" in l: mark = "shading"
+            phase[i] = mark or "regeneration"
+        elif SHADE_FN.match(fn): phase[i] = "shading"
+        elif PASS1_FN.match(fn): phase[i] = "pass 1"
+        elif PASS2_FN.match(fn): phase[i] = "pass 2"
+        elif REGEN_FN.match(fn): phase[i] = "regeneration"
+    # the long form of the finished path's store (a ring above 4 GiB): never taken by a default render
+    longform = set()
+    for i, l in enumerate(lines, 1):
+        if "const unsigned fr = s.fl + KR->ring_phase" in l: longform.update(range(i - 3, i + 4))
+    return phase, longform
+
+def const_name(s):
+    if re.match(r"^0x[0-9a-f]+$", s):
+        v = int(s, 16)
+        return "%s (%.9g as binary32)" % (s, struct.unpack("<f", struct.pack("<I", v & 0xffffffff))[0])
+    return s
+
+def regs_of(operand):
+    """the 32-bit VGPRs an operand names"""
+    m = re.match(r"^[-|]*v(\d+)", operand)
+    if m: return {int(m.group(1))}
+    m = re.match(r"^[-|]*v\[(\d+):(\d+)\]", operand)
+    return set(range(int(m.group(1)), int(m.group(2)) + 1)) if m else set()
+
+def move_audit(src):
+    asm = "/tmp/pt_kernels_moves_%d.s" % os.getpid()
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
+           "-gline-tables-only", "--cuda-device-only", "-S", "-o", asm, "pt_kernels.hip"]
+    subprocess.run(cmd, cwd=src, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    t = open(asm).read(); os.remove(asm)
+    a = t.index(KERNEL + ":"); b = t.index(".Lfunc_end", a)
+    phase_of, longform = source_phases(src)
+    # instructions with their block, the block's loop note and their source lines (the .loc chain, innermost first)
+    ins, blocks, cur, loc = [], [], None, []
+    for l in t[a:b].split("\n"):
+        s = l.strip()
+        m = re.match(r"^(\.LBB\d+_\d+:|; %bb\.\d+:)\s*(;.*)?$", s)
+        if m:
+            cur = {"name": m.group(1).rstrip(":"), "note": m.group(2) or "", "labelled": s.startswith(".L"), "ins": []}
+            blocks.append(cur); continue
+        if s.startswith(";") and cur is not None and not cur["ins"] and not s.startswith(";;"):
+            cur["note"] += " " + s; continue
+        if s.startswith(".loc"):
+            c = s.split(";", 1)[1] if ";" in s else ""
+            loc = [int(x) for x in re.findall(r"pt_kernels\.hip:(\d+)", c)]; continue
+        m = re.match(r"^([a-z_0-9]+)\s*(.*?)(?:\s*;.*)?$", s)
+        if not m or s.startswith(".") or s.startswith(";") or cur is None: continue
+        d = {"op": m.group(1), "args": [x.strip() for x in m.group(2).split(",")] if m.group(2) else [], "loc": loc, "block": cur}
+        cur["ins"].append(d); ins.append(d)
+    n_total = len(ins)
+    # the bounce loop: the depth-1 loop with the most blocks
+    hdrs = {}
+    for bl in blocks:
+        for h in re.findall(r"(?:Header=|Parent Loop )(BB\d+_\d+)", bl["note"]): hdrs[h] = hdrs.get(h, 0) + 1
+    loop = max(hdrs, key=hdrs.get)
+    inloop = [bl for bl in blocks if loop in bl["note"] or bl["name"] == ".L" + loop]
+    # phase and path of every block
+    prev_phase, prev_off = "regeneration", None
+    for bl in inloop:
+        votes = {}
+        for d in bl["ins"]:
+            for ln in d["loc"]:
+                if ln in phase_of: votes[phase_of[ln]] = votes.get(phase_of[ln], 0) + 1; break
+        bl["phase"] = max(votes, key=votes.get) if votes else prev_phase
+        ops = [d["op"] for d in bl["ins"]]
+        off = None
+        if any("_f64" in o for o in ops) and bl["phase"] == "shading": off = "binary64 sincos arm"
+        elif any(o.startswith(("v_div_scale", "v_div_fmas", "v_div_fixup")) for o in ops): off = "generic division"
+        elif any(ln in longform for d in bl["ins"] for ln in d["loc"][:1]) and sum(1 for d in bl["ins"] if d["loc"][:1] and d["loc"][0] in longform) * 2 > len(bl["ins"]): off = "long ring form"
+        elif not bl["labelled"] and prev_off: off = prev_off          # reached only by falling out of a block that is not taken
+        bl["off"] = off
+        prev_phase, prev_off = bl["phase"], off
+    # every instruction of the class, with its cause (a lane access with an immediate lane number is a spill or its reload)
+    rows = []
+    for bl in inloop:
+        for k, d in enumerate(bl["ins"]):
+            op, args = d["op"], d["args"]
+            if not re.match(r"v_(mov_|readlane|writelane|readfirstlane|accvgpr)", op): continue
+            if op.startswith("v_mov"):
+                srcop = args[1]
+                dst = regs_of(args[0])
+                user = "?"
+                for e in bl["ins"][k + 1:]:
+                    if any(regs_of(x) & dst for x in e["args"][1:]) or (e["op"].startswith(("global_store", "ds_write", "v_cmp", "v_writelane")) and any(regs_of(x) & dst for x in e["args"])):
+                        user = e["op"]; break
+                    if regs_of(e["args"][0]) >= dst if e["args"] else False: user = "(redefined: " + e["op"] + ")"; break
+                if user == "?": user = "a later block"
+                if re.match(r"^[-|]*v", srcop):
+                    definer = "live into the block"
+                    for e in reversed(bl["ins"][:k]):
+                        if e["args"] and regs_of(e["args"][0]) & regs_of(srcop): definer = "result of " + e["op"]; break
+                    kind, cause = "vgpr", "phi / two-address copy of %s (%s) for %s" % (srcop, definer, user)
+                elif re.match(r"^(s\d+|s\[|vcc|exec|m0)", srcop): kind, cause = "sgpr", "SGPR -> VGPR copy of %s for %s" % (srcop, user)
+                else: kind, cause = "constant", "constant %s for %s" % (const_name(srcop), user)
+                n = 2 if "b64" in op else 1
+            else:
+                n = 1; kind = "lane"
+                lane = args[2] if len(args) > 2 else ""
+                if op == "v_readfirstlane_b32": cause = "readfirstlane of %s (wave-uniform value from a VGPR)" % args[1]
+                elif op.startswith("v_accvgpr"): cause = "AGPR move"
+                elif re.match(r"^\d+$", lane): cause = ("spill of %s to lane %s of %s" % (args[1], lane, args[0])) if op.startswith("v_writelane") else ("reload of %s from lane %s of %s" % (args[0], lane, args[1]))
+                else: cause = "lane access chosen at run time (%s): the algorithm's own, not a spill" % lane
+            rows.append({"phase": bl["phase"], "off": bl["off"], "kind": kind, "n": n, "text": "%s %s" % (op, ", ".join(args)), "cause": cause,
+                         "block": bl["name"], "src": "pt_kernels.hip:%d" % d["loc"][0] if d["loc"] else "-",
+                         "spill": cause.startswith(("spill of", "reload of"))})
+    return {"rows": rows, "n_total": n_total, "loop": loop, "n_loop": sum(len(bl["ins"]) for bl in inloop), "n_blocks": len(inloop)}
+
+def summarise(A):
+    S = {}
+    for r in A["rows"]:
+        cause = {"constant": "constant materialised", "sgpr": "SGPR -> VGPR copy", "vgpr": "phi / two-address copy"}.get(r["kind"]) or \
+                ("SGPR spill / reload" if r["spill"] else "lane access (algorithm)")
+        k = (r["phase"], cause, "default path" if not r["off"] else "not taken: " + r["off"])
+        c = S.setdefault(k, [0, 0.0]); c[0] += 1; c[1] += r["n"] * PRICE[r["kind"]]
+    return S
+
+def moves_main(argv):
+    here = move_audit(SRC)
+    parent = move_audit(argv[argv.index("--parent-src") + 1]) if "--parent-src" in argv else None
+    print("The move class of the bounce loop of pt_trace_kernel<true,1,3>, shipped build (tools/isa_histogram.py --moves; no GPU: static counts).")
+    print("Prices per wave-instruction at 8 waves per SIMD (profiles/r01/ubench_issue.log): v_mov v,v or v,constant %.2f cycles (a 64-bit move as two),"
+          % PRICE["vgpr"])
+    print("v_mov v,s %.2f, v_readlane / v_writelane / v_readfirstlane %.2f.  An instruction inside an inner loop is counted once, as written." % (PRICE["sgpr"], PRICE["lane"]))
+    sides = [("parent", parent), ("change", here)] if parent else [("this tree", here)]
+    for name, A in sides:
+        print("%s: kernel %d instructions, bounce loop (header %s) %d instructions in %d blocks, %d of the class" % (name, A["n_total"], A["loop"], A["n_loop"], A["n_blocks"], len(A["rows"])))
+    S = [summarise(A) for _, A in sides]
+    keys = sorted(set().union(*S), key=lambda k: (PHASES.index(k[0]), k[2] != "default path", k[1], k[2]))
+    print("\n%-13s %-26s %-34s" % ("phase", "cause", "path") + "".join("  %8s %7s" % (n, "cycles") for n, _ in sides))
+    tot = [[0, 0.0, 0, 0.0] for _ in sides]
+    for k in keys:
+        line = "%-13s %-26s %-34s" % k
+        for j, s in enumerate(S):
+            c = s.get(k, [0, 0.0]); line += "  %8d %7.1f" % (c[0], c[1])
+            o = 0 if k[2] == "default path" else 2
+            tot[j][o] += c[0]; tot[j][o + 1] += c[1]
+        print(line)
+    print("%-75s" % "total on the default path" + "".join("  %8d %7.1f" % (x[0], x[1]) for x in tot))
+    print("%-75s" % "total behind branches a default render never takes" + "".join("  %8d %7.1f" % (x[2], x[3]) for x in tot))
+    for j, (name, A) in enumerate(sides):
+        sp = [r for r in A["rows"] if r["spill"]]
+        print("%s: %d spill / reload lane accesses in the loop, %d of them on the default path" % (name, len(sp), sum(1 for r in sp if not r["off"])))
+    for name, A in sides:
+        print("\n---- %s: every instruction of the class, in program order ----" % name)
+        print("%-12s %-24s %-11s %-16s %-46s %s" % ("phase", "path", "block", "source", "instruction", "cause"))
+        for r in A["rows"]:
+            print("%-12s %-24s %-11s %-16s %-46s %s" % (r["phase"], r["off"] or "default", r["block"], r["src"].replace("pt_kernels.hip", ""), r["text"][:46], r["cause"]))
+
 if __name__ == "__main__":
-    main()
+    if "--moves" in sys.argv: moves_main(sys.argv)
+    else: main()
