@@ -164,7 +164,10 @@ enum pt_option {
     /* 1 (default): for quad scenes of up to 64 triangles on the brute-force path, every render first computes,
      * per pixel, a conservative candidate set of triangles its primary rays can meet (the camera is fixed:
      * GenerateColors.cl:265-272), and waves of fresh primary rays skip the pass-1 filter.  0 = off (A/B timing,
-     * parity tests).  Identical pixels either way. */
+     * parity tests).  Identical pixels either way.  The sets are bounded over half a pixel around the pixel's centre ray, which
+     * holds only while the float roundings of a pixel's image-plane point stay a small part of a pixel: masks are made for
+     * images with width^2 + height^2 <= 7626^2 (every image of up to 4096 x 4096); a larger image renders as under 0 and
+     * no table stands for it (pt_primary_mask_snapshot). */
     PT_OPT_PRIMARY_MASKS = 7,
     /* test hook of the LBVH's overflow report: the number of stack entries a ray's search may use (1..64; default 64,
      * which no hierarchy built by the library can exceed).  A search that needs more raises the sticky word behind

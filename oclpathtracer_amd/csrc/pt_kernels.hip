@@ -260,6 +260,13 @@ PTK_DEV void pt_generate_ray(int xc, int yc, float inv_w, float inv_h, float asp
 //     sphere from outside the ball of radius 1 - 1e-6 is (1 + 1e-6)-Lipschitz: together a factor below 1 + 4e-6;
 //     eps = 1.01 h + 4e-6 covers it with room to spare (the 1.01 alone is 2 500 times the 4e-6 needed), and its additive
 //     4e-6 covers the rounding of the reference's own ray set-up (three normalisations of a unit-length vector).
+// PREMISE: dx and dmy above are half a pixel, that is, the image-plane point a kernel computes -- fl(fl(xc + r) - 0.5) of
+// pt_pixel_jitter through the first two lines of pt_camera_aim -- is the real one to a small part of a pixel.  Those
+// roundings are 2^-24-relative to the pixel COORDINATE: 12 of them between a sample and this kernel's centre, 24 2^-24 angle
+// (aspect^2 + 1)^(1/2) on the image plane, against the 0.0099 h the 1.01 has to give (h = 2^(1/2) angle / H: pixels are
+// square).  From column 2^23 on a jittered x is not even in its own pixel.  The HOST therefore launches this kernel only
+// for images with W^2 + H^2 <= 7626^2 (pmask_footprint_holds, pt_shim.hip, where the roundings are counted one by one);
+// every other render runs pass 1 for its primary rays, as under PT_OPT_PRIMARY_MASKS 0.
 // A primary ray's origin is the eye bit for bit, so for triangle {p1, e1, e2} the reference's tvec = fl(eye - p1), its
 // qvec = fl_cross(tvec, e1) and the numerator of t, tn = fl_dot(e2, qvec), are per-triangle CONSTANTS -- formed here by the
 // very operations of pt_tri_pass2, hence the same bits -- and the other three numerators are LINEAR in the direction:
@@ -2360,8 +2367,9 @@ __global__ __launch_bounds__(256) void pt_fold_kernel(const PtFoldParams P)
         tab[w][i] = w == 0 ? pt_pow_logc_tab[i] : w == 1 ? pt_pow_logl_tab[i] : pt_pow_exp2_tab[i];
     }
     {
-        // only the frames of this launch
-        const int z0 = P.frame_begin, z1 = min(P.frame_begin + P.frame_count, PT_FOLD_RCP_N);
+        // only the frames of this launch (z0 is clamped: frame_begin + threadIdx.x must not pass 2^31 - 1 -- wrapped to a negative
+        // k, the loop below ran 8 M times per thread and stored over the pow tables)
+        const int z0 = min(P.frame_begin, PT_FOLD_RCP_N), z1 = min(P.frame_begin + P.frame_count, PT_FOLD_RCP_N);
         for (int k = z0 + (int)threadIdx.x; k < z1; k += 256) rcp_z[k] = 1.0f / (float)k;
     }
     __syncthreads();

@@ -1328,6 +1328,27 @@ static int refresh_pmask(pt_device_s* d, const pt_render_params& rp, const PtCam
     return PT_OK;
 }
 
+// The masks' footprint bound (the comment above pt_primary_mask_kernel) takes every ray of a pixel to lie within
+// eps = 1.01 h + 4e-6 of the centre ray, h = half a pixel's diagonal on the image plane: that needs the image-plane point the
+// kernels compute to be the real one to a small part of a pixel.  It is not on a very large image.  With u = 2^-24 and a pixel
+// coordinate of at most W, each of these roundings moves the point by at most u W pixels (to first order; W < 2^24, so (float)xc
+// is exact):
+//     pt_pixel_jitter:              fl(xc + r), fl(. - 0.5)                                                        2
+//     pt_camera_aim's first line:   fl(x + 0.5); inv_w = RN(1 / W) and the product by it, 2; fl(2 c - 1), half (the value
+//                                   is at most 1 where the image is 2 wide); the product by angle, half; aspect = RN(W / H)
+//                                   and the product by it, 2 halves                                                5
+// -- 7 for a sample and 5 for the mask kernel's centre (it has no jitter), 12 u W pixels of 2 angle aspect / W each: 24 u angle
+// aspect between the two in x, and no more in y (the second line has no aspect): at most 24 u angle (aspect^2 + 1)^(1/2).
+// The bound has 1.01 / (1 + 4e-6) - 1 > 0.0099 of h to give, and pixels are square (aspect / W = 1 / H), h = 2^(1/2) angle / H:
+// the premise holds while 24 u (W^2 + H^2)^(1/2) <= 0.0099 2^(1/2).  Masks are made while 28 u (W^2 + H^2)^(1/2) <= 0.009 2^(1/2),
+// W^2 + H^2 <= 7626^2 -- the margin covers the second-order terms, aspect's own rounding and the float evaluation of eps; the
+// additive 4e-6 is not drawn on.  Every image of up to 4096 x 4096 keeps its masks; a larger one renders as under
+// PT_OPT_PRIMARY_MASKS 0 (pass 1 for primary rays too).
+static bool pmask_footprint_holds(int width, int height)
+{
+    return (double)width * width + (double)height * height <= 7626.0 * 7626.0;
+}
+
 // Samples per work-queue grab.  A wave that finds the queue empty idles until the last wave is
 // done, on average for half a batch: large batches (fewer atomics) when every wave gets many of
 // them, smaller ones when the launch is short (a rank's share of a multi-GPU render, small images).
@@ -1411,7 +1432,9 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
     const bool use_bvh = search.mode.bvh;
     int nchunks, chunk;
     if ((rc = plan_chunks(d, rp.frame_count, npix, nchunks, chunk))) return rc;
-    const bool use_pmask = d->opt_pmask && search.mode.quads == 3 && !use_bvh && rp.num_triangles <= 64 && search.mode.det_bounded;
+    const bool want_pmask = d->opt_pmask && search.mode.quads == 3 && !use_bvh && rp.num_triangles <= 64 && search.mode.det_bounded;
+    const bool use_pmask = want_pmask && pmask_footprint_holds(rp.width, rp.height);
+    if (want_pmask && !use_pmask) d->pmask_key.valid = false;   // declined: no table stands for this render (pt_primary_mask_snapshot)
     bool make_pmask = false;
     if (use_pmask && (rc = refresh_pmask(d, rp, cam, npix, make_pmask))) return rc;
     if (d->counters_dirty) {   // an earlier call failed between a trace launch and the fold that resets its counter

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
+import direct_oracle
 from oracles import F, I, I64, V, cam10, declare, lib, ptr
 
 declare({
@@ -17,7 +18,7 @@ def counts(tris, W, H, frame_begin, frame_count, K, radius, cam=None, stripe_row
     """uint32 [local rows, W, 2] {open, hits} over frames [frame_begin, frame_begin + frame_count), added to `start` (or zeros);
     None when the camera is rejected.  cam: a Camera (None = the reference's)."""
     tris = np.ascontiguousarray(tris)
-    rows = sum(1 for r in range(H) if (r // stripe_rows) % n_ranks == rank)
+    rows = direct_oracle.local_row_count(H, stripe_rows, n_ranks, rank)
     out = np.zeros((rows, W, 2), np.uint32) if start is None else np.array(start, np.uint32).reshape(rows, W, 2).copy()
     c = cam10(cam)
     rc = lib().oao_render(ptr(tris) if len(tris) else None, len(tris), ptr(c), W, H, stripe_rows, n_ranks,

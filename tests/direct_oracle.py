@@ -34,7 +34,7 @@ def render(tris, mats, W, H, frame_begin, frame_count, K, *, lights=None, cam=No
     camera is rejected.  lights: the light list (None = scene.emitters); cam: a Camera (None = the reference's)."""
     tris, mats = np.ascontiguousarray(tris), np.ascontiguousarray(mats)
     li = _lights(tris, mats, lights)
-    rows = sum(1 for r in range(H) if (r // stripe_rows) % n_ranks == rank)
+    rows = local_row_count(H, stripe_rows, n_ranks, rank)
     fb = np.zeros((rows * W, 4), np.float32) if start is None else np.array(start, np.float32).reshape(rows * W, 4).copy()
     c = cam10(cam)
     rc = lib().odi_render(ptr(tris) if len(tris) else None, len(tris), ptr(mats), ptr(li) if len(li) else None, len(li), ptr(c),
@@ -81,10 +81,26 @@ def details(tris, mats, W, H, gid, frame, K, *, lights=None, cam=None):
     return hit, flipped, reason, d2, rad
 
 
+def local_row_count(H, stripe_rows=1, n_ranks=1, rank=0):
+    """how many of the image's H rows ``rank`` owns in the stripe layout, in closed form (no walk over the rows: H reaches 2^31 - 1):
+    stripe_rows for every whole period of stripe_rows * n_ranks rows, and of the last, partial period what lies in this rank's stripe"""
+    period = stripe_rows * n_ranks
+    full, rem = divmod(H, period)
+    return full * stripe_rows + min(stripe_rows, max(0, rem - rank * stripe_rows))
+
+
+def local_rows(H, stripe_rows=1, n_ranks=1, rank=0):
+    """the global row of every local row of ``rank`` (int64, ascending), in closed form: stripe k of the rank begins at row
+    (k * n_ranks + rank) * stripe_rows, and the image's last stripe may be cut short"""
+    n = local_row_count(H, stripe_rows, n_ranks, rank)
+    k = np.arange(-(-n // stripe_rows), dtype=np.int64)
+    rows = ((k * n_ranks + rank) * stripe_rows)[:, None] + np.arange(stripe_rows, dtype=np.int64)[None, :]
+    return rows.reshape(-1)[:n]
+
+
 def local_gids(W, H, stripe_rows=1, n_ranks=1, rank=0):
     """the global pixel index of every local pixel of ``rank`` in the stripe layout, in the framebuffer's order"""
-    rows = [r for r in range(H) if (r // stripe_rows) % n_ranks == rank]
-    return (np.asarray(rows, np.int64)[:, None] * W + np.arange(W)[None, :]).reshape(-1)
+    return (local_rows(H, stripe_rows, n_ranks, rank)[:, None] * W + np.arange(W)[None, :]).reshape(-1)
 
 
 def sample_ids(W, H, frames, **stripes):

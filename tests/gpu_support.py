@@ -46,10 +46,10 @@ def render(device, tris, mats, W, H, frames, *, depth=16, frame_begin=0, fb_init
         r.release()
 
 
-def lit_with_samples(device, scene4, W, H, frames, K, chunk_frames=None, max_bounces=None, mis=False, frame_begin=0, **kw):
+def lit_with_samples(device, scene4, W, H, frames, K, chunk_frames=None, max_bounces=None, mis=False, frame_begin=0, fb_init=None, **kw):
     """One DirectRenderer -- with max_bounces an IndirectRenderer, with mis its MIS estimator -- on (tris, mats, lights, camera), whose
-    workspace holds every frame of the call (chunk_frames >= frames unless given), one render from frame_begin: the framebuffer
-    [local pixels, 4] and the whole sample workspace [chunk_frames, local pixels, 3]."""
+    workspace holds every frame of the call (chunk_frames >= frames unless given), one render from frame_begin (into fb_init, when
+    given: the image to resume): the framebuffer [local pixels, 4] and the whole sample workspace [chunk_frames, local pixels, 3]."""
     from oclpathtracer_amd.direct import DirectRenderer
     from oclpathtracer_amd.indirect import IndirectRenderer
 
@@ -59,6 +59,8 @@ def lit_with_samples(device, scene4, W, H, frames, K, chunk_frames=None, max_bou
     r = DirectRenderer(device, tris, mats, W, H, **kw) if max_bounces is None else \
         IndirectRenderer(device, tris, mats, W, H, max_bounces=max_bounces, mis=mis, **kw)
     try:
+        if fb_init is not None:
+            r.fb.write(np.ascontiguousarray(fb_init, np.float32), r.local_pixels)
         r.render(frames, frame_begin)
         fb = r.read()
         ws = np.zeros((r.chunk_frames, r.local_pixels, 3), np.float32)

@@ -24,7 +24,7 @@ def render(tris, mats, W, H, frame_begin, frame_count, K, B, *, lights=None, cam
     cam: a Camera (None = the reference's)."""
     tris, mats = np.ascontiguousarray(tris), np.ascontiguousarray(mats)
     li = direct_oracle._lights(tris, mats, lights)
-    rows = sum(1 for r in range(H) if (r // stripe_rows) % n_ranks == rank)
+    rows = direct_oracle.local_row_count(H, stripe_rows, n_ranks, rank)
     fb = np.zeros((rows * W, 4), np.float32) if start is None else np.array(start, np.float32).reshape(rows * W, 4).copy()
     c = cam10(cam)
     rc = lib().oii_render(ptr(tris) if len(tris) else None, len(tris), ptr(mats), ptr(li) if len(li) else None, len(li), ptr(c),

@@ -51,7 +51,7 @@ def render(tris, mats, W, H, frame_begin, frame_count, K, B, *, lights=None, cou
     """float32 [local pixels, 4]: ``indirect_oracle.render`` for the MIS estimator.  counts: int32 [num_triangles] (None = made of
     the list)."""
     tris, mats, li, cn = _inputs(tris, mats, lights, counts)
-    rows = sum(1 for r in range(H) if (r // stripe_rows) % n_ranks == rank)
+    rows = direct_oracle.local_row_count(H, stripe_rows, n_ranks, rank)
     fb = np.zeros((rows * W, 4), np.float32) if start is None else np.array(start, np.float32).reshape(rows * W, 4).copy()
     c = cam10(cam)
     rc = lib().omi_render(_p(tris), len(tris), ptr(mats), _p(li), len(li), _p(cn), ptr(c), W, H, stripe_rows, n_ranks, rank,

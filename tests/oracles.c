@@ -9,3 +9,4 @@
 #include "indirect_oracle.c"
 #include "mis_oracle.c"
 #include "primary_accept.c"
+#include "extent_oracle.c"

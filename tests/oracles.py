@@ -1,10 +1,10 @@
 """Builds and loads tests/libtest_oracles.so: the CPU oracle (oracle/pt_oracle.c) with every restatement of it -- the camera, query and
-ambient-occlusion ones, direct and indirect illumination, multiple importance sampling and the primary rays' accepted sets -- as one
+ambient-occlusion ones, direct and indirect illumination, multiple importance sampling, the primary rays' accepted sets and the windowed render of very large images -- as one
 translation unit, tests/oracles.c.  TEST INFRASTRUCTURE.
 
 ``__graft_entry__.build()`` builds it (``python -B tests/oracles.py build``); ``lib()`` builds it again when it is missing or older
 than one of its sources, as ``ptoracle.lib()`` does.  The bindings are tests/camera_oracle.py, query_oracle.py, ao_oracle.py,
-direct_oracle.py, indirect_oracle.py, mis_oracle.py and primary_accept.py: each declares its entry points here (``declare``).
+direct_oracle.py, indirect_oracle.py, mis_oracle.py, primary_accept.py and extent_oracle.py: each declares its entry points here (``declare``).
 """
 from __future__ import annotations
 
@@ -18,7 +18,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtest_oracles.so")
 _SRCS = [os.path.join(_HERE, f) for f in ("oracles.c", "camera_oracle.c", "query_oracle.c", "ao_oracle.c", "direct_oracle.c",
-                                          "indirect_oracle.c", "mis_oracle.c", "primary_accept.c")] + \
+                                          "indirect_oracle.c", "mis_oracle.c", "primary_accept.c", "extent_oracle.c")] + \
         [os.path.join(os.path.dirname(_HERE), "oracle", f) for f in ("pt_oracle.c", "ptor_constants.h")]
 # a copy of oracle/Makefile's CFLAGS: strict IEEE, no contraction, no fast-math
 CFLAGS = ["-O2", "-fPIC", "-std=gnu11", "-Wall", "-Wextra", "-Wno-unused-function", "-ffp-contract=off", "-fno-fast-math",

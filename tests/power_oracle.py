@@ -89,7 +89,7 @@ def render(mode, tris, mats, W, H, frame_begin, frame_count, K, B=1, *, lights=N
     """float32 [local pixels, 4]: the framebuffer of pt_render_direct_power (``mode`` DIRECT) or pt_render_indirect_power (INDIRECT, MIS)
     in ``mis_oracle.render``'s layout.  counts / tab: None = made of the list."""
     tris, mats, li, cn, cdf, tri_q = _inputs(tris, mats, lights, counts, tab)
-    rows = sum(1 for r in range(H) if (r // stripe_rows) % n_ranks == rank)
+    rows = direct_oracle.local_row_count(H, stripe_rows, n_ranks, rank)
     fb = np.zeros((rows * W, 4), np.float32) if start is None else np.array(start, np.float32).reshape(rows * W, 4).copy()
     c = cam10(cam)
     rc = lib().opw_render(mode, _p(tris), len(tris), ptr(mats), _p(li), len(li), ptr(cdf), _p(tri_q), _p(cn), ptr(c), W, H, stripe_rows,
