@@ -736,6 +736,85 @@ size_t pt_moments_summary_bytes(uint32_t num_pixels);
 int pt_moments_resolve(pt_device_t dev, pt_buffer_t moments /* pt_pixel_moments[num_pixels] */, uint32_t num_pixels,
                        pt_buffer_t noise /* may be NULL */, pt_buffer_t summary /* may be NULL */, pt_event_t ev);
 
+/* ---- adaptive sampling: later frames only for the pixels that are still noisy ---------------------------------------------
+ * The moments are per pixel; these calls act on them per pixel.  pt_adaptive_select turns the moments into a LIST of the pixels
+ * whose mean is not yet good enough, pt_render_indirect_pixels renders further frames of the listed pixels only, each continuing from
+ * its own frame number, and pt_sample_moments_pixels counts those samples.  No reference counterpart; no existing kernel, entry
+ * point or image changes.  A pixel's samples depend on its global id and the frame number alone, and its fold chain on its own frames
+ * in ascending order, so THE IDENTITY holds: after any sequence of these calls, pixel p of the framebuffer holds exactly the bits a
+ * uniform render (pt_render_indirect_rr over frames [0, n_p)) holds for p, n_p being the number of samples p has received.
+ *
+ * A LIST is a buffer: bytes 0-15 {uint32 count; uint32 reserved[3]}, then pt_pixel_slot[count], 8 bytes each: the LOCAL pixel and the
+ * number of its next frame.
+ *
+ * pt_adaptive_select, per local pixel p of num_pixels, from its record moments[p] (pt_pixel_moments):
+ *  1. taken = (uint64)n + (uint64)rejected;
+ *  2. with n >= 2, in binary64, every operation rounded on its own (no contraction), the IEEE "/" -- pt_moments_resolve's step 1 and
+ *     its se2_sum and mean2_sum terms, expression for expression: per channel m = sum / (double)n; t = sum * m; d = sum2 - t;
+ *     v = d / (double)(n - 1); v = v > 0 ? v : +0;  b = ((v.x / n) + (v.y / n)) + (v.z / n);  c = ((m.x * m.x) + (m.y * m.y)) +
+ *     (m.z * m.z);
+ *  3. p is ACTIVE iff taken < max_samples && (n < min_samples || (n >= 2 && b > tol2 * (c + floor2))).  The inequality is strict,
+ *     and a comparison with a NaN is false (a sum that has overflowed, tol2 = 0 against c = infinity: inactive);
+ *  4. the list receives count = the number of active pixels, reserved = 0, and the active pixels' slots IN ASCENDING ORDER OF p:
+ *     {pixel = p, frame = (uint32)taken}.
+ * list: the caller's buffer of pt_adaptive_list_bytes(num_pixels) bytes; what lies behind the slots is the build's scratch and
+ * unspecified (nothing is allocated: pt_light_table's pattern).  The compaction is ordered -- per-tile counts, their scan, a scatter
+ * -- and all integer, so the list does not depend on the order of the scan.  The moments are only read.  num_pixels = 0 writes a
+ * header of zeros.  Behaviour is pt_moments_resolve's: the handle's stream, asynchronous (ev), no allocation, no wait.
+ * Errors, before anything is enqueued: PT_ERR_INVALID for a NULL handle, rule NULL, tol2 or floor2 negative or NaN, a reserved
+ * field not 0, moments or list not 8-byte aligned, the two overlapping, a buffer of another device; PT_ERR_RANGE for a buffer too small
+ * (moments: num_pixels x 56; list: pt_adaptive_list_bytes(num_pixels)).
+ *
+ * pt_render_indirect_pixels takes pt_render_indirect_rr's arguments -- through the same validation -- plus list and num_listed, the
+ * count the HOST has read from the list's header: the device never reads the count.  num_listed must not exceed the local pixel
+ * count.  With npix = the local pixels and F = params->frame_count, the frames PER LISTED PIXEL, item i of a launch is frame f = i /
+ * num_listed of slot j = i % num_listed:
+ *  1. its local pixel is min(slot[j].pixel, npix - 1): an out-of-range slot is defined behaviour, as a light index is, never an
+ *     out-of-range access;
+ *  2. its frame number is z = (slot[j].frame + params->frame_begin + f) & 0x7fffffff (f counted from the call's first frame);
+ *  3. from there on it is pt_render_indirect_rr's sample of that pixel in frame z: the stripe mapping to the global pixel id, seed = gid
+ *     + hash(z), the primary ray, the same walk with the same estimator (mis; cdf and tri_q; the roulette);
+ *  4. the sample goes to samples[i]: the workspace is laid out [frames][num_listed][3], pt_render_direct step 5's with num_listed for
+ *     the local pixels.  The frames are walked in chunks of min(frames left, floor(bytes / (num_listed x 12)), floor((2^31 - 1) /
+ *     num_listed)); the workspace must hold one frame of the list;
+ *  5. each chunk is followed by a LIST FOLD: one lane per (slot, channel) folds samples[f][j], f ascending, into framebuffer[the slot's
+ *     pixel] by the renderer's fold with the frame numbers of step 2.  A frame number 0 overwrites the pixel, as frame 0 does in every
+ *     render; every other one resumes the mean the pixel holds.
+ * Pixels that are not listed are neither read nor written.  THE SLOTS MUST NAME DISTINCT PIXELS (pt_adaptive_select's do): duplicates,
+ * which out-of-range slots clamped to the last pixel also are, race in the fold, so the pixel's VALUE is undefined -- but there is
+ * never an out-of-range access.  roulette may not be NULL: first_bounce >= max_bounces plays none, so all four estimators are reached
+ * with and without roulette through this one entry point; max_bounces = 1 is direct illumination.  The stream, the prepared scene, the
+ * deferred PT_ERR_TRAVERSAL: pt_render_indirect_rr's.  frame_count = 0 or num_listed = 0 enqueues nothing.
+ * Errors: pt_render_indirect_rr's (the workspace: one frame of num_listed pixels), plus PT_ERR_INVALID for list NULL, of another
+ * device, not 8-byte aligned, overlapping the workspace or the framebuffer, num_listed above the local pixel count; PT_ERR_RANGE for a
+ * list smaller than 16 + num_listed x 8 bytes.
+ *
+ * pt_sample_moments_pixels: moments[min(slot[j].pixel, P - 1)], P = the whole records the moments buffer holds (floor(bytes / 56): the
+ * local pixels of a buffer sized for them), takes samples[f][j][0..2] for f = 0 .. frame_count - 1 ascending by pt_sample_moments' step
+ * 2; one lane per listed pixel; it never resets.  Records that are not listed are neither read nor written.  Behaviour and errors are
+ * pt_sample_moments', plus PT_ERR_INVALID for list NULL, not 8-byte aligned, overlapping, num_listed > P and PT_ERR_RANGE for a list
+ * smaller than 16 + num_listed x 8 bytes. */
+typedef struct pt_adaptive_rule {
+    double tol2;             /* >= 0: the squared relative standard error a pixel must reach */
+    double floor2;           /* >= 0: added to the squared mean, so that a black pixel can stop */
+    uint32_t min_samples;    /* a pixel with fewer finite samples is active whatever its variance */
+    uint32_t max_samples;    /* a pixel that has received this many samples (finite or rejected) is inactive */
+    uint32_t reserved[2];    /* must be 0 */
+} pt_adaptive_rule;          /* 32 bytes */
+typedef struct pt_pixel_slot { uint32_t pixel; uint32_t frame; } pt_pixel_slot;   /* local pixel, its next frame number */
+size_t pt_adaptive_list_bytes(uint32_t num_pixels);
+int pt_adaptive_select(pt_device_t dev, pt_buffer_t moments /* pt_pixel_moments[num_pixels] */, uint32_t num_pixels,
+                       const pt_adaptive_rule* rule, pt_buffer_t list /* pt_adaptive_list_bytes(num_pixels) bytes */, pt_event_t ev);
+int pt_render_indirect_pixels(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                              pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, int mis,
+                              pt_buffer_t light_counts /* int32[num_triangles]; may be NULL when mis or num_lights is 0 */,
+                              pt_buffer_t cdf, pt_buffer_t tri_q /* both NULL = the uniform choice */, pt_buffer_t samples /* workspace */,
+                              pt_buffer_t framebuffer, pt_buffer_t list, uint32_t num_listed, const pt_indirect_params* params,
+                              const pt_roulette* roulette, const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
+int pt_sample_moments_pixels(pt_device_t dev, pt_buffer_t samples /* float[frame_count][num_listed][3] */,
+                             pt_buffer_t moments /* pt_pixel_moments[] */, pt_buffer_t list, uint32_t num_listed, int32_t frame_count,
+                             pt_event_t ev);
+
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.
  * pt_profile_query synchronises the stream and returns the summed duration and launch count

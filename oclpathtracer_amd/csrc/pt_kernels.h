@@ -340,6 +340,39 @@ struct PtIndirectRrParams : PtIndirectPowerParams {
 // PT_RR_RUN (pt_constants.h) consecutive items, which refills its dead lanes from its run
 hipError_t ptk_indirect_rr(const PtIndirectRrParams& a, int bvh_blocks, PtSearchMode m, bool mis, bool power, hipStream_t s);
 int ptk_indirect_rr_bvh_blocks_per_cu(bool mis, bool power);
+// adaptive sampling (pt_render_indirect_pixels): the LIST = true instantiations of the roulette kernels take this block, every other
+// instantiation its block as before.  A launch runs over a LIST of pixels: d.npix is the number of listed pixels, item = f * d.npix + j
+// is frame f of slot j, whose local pixel is min(slots[j].x, d.t.npix_local - 1) and whose frame number is (slots[j].y + frame_off + f)
+// & 0x7fffffff; d.frame0 is not read.  The sample is stored at samples[item] as before
+struct PtIndirectListParams : PtIndirectRrParams {
+    const uint2* slots;           // [d.npix] pt_pixel_slot {pixel, frame}
+    uint32_t frame_off;           // the frames every listed pixel has received from this call already
+};
+hipError_t ptk_indirect_list(const PtIndirectListParams& a, int bvh_blocks, PtSearchMode m, bool mis, bool power, hipStream_t s);
+int ptk_indirect_list_bvh_blocks_per_cu(bool mis, bool power);
+// the fold of a list launch: one lane per (slot j, channel) folds rad[f][j], f = 0 .. frame_count - 1 ascending, into fb[the slot's
+// pixel] with the slot's own frame numbers (pt_fold_frame); pixels that are not listed are neither read nor written
+struct PtFoldListParams {
+    const float* rad;             // [frame_count][num_listed][3]
+    float4* fb;                   // [npix_local]
+    const uint2* slots;           // [num_listed]
+    uint32_t num_listed, npix_local;
+    uint32_t frame_off;
+    int32_t frame_count;
+};
+hipError_t ptk_fold_list(const PtFoldListParams& p, hipStream_t s);
+// moments[the pixel of slot j] takes samples[f][j][0..2], f = 0 .. frames - 1 ascending; one lane per slot; never resets
+struct PtPixelMoments;
+hipError_t ptk_sample_moments_list(const float* samples, PtPixelMoments* moments, const uint2* slots, uint32_t num_listed, uint32_t npix,
+                                   int32_t frames, hipStream_t s);
+// pt_adaptive_select: list = {uint32 count, 0, 0, 0}, then the slots of the active pixels in ascending order, then the build's
+// scratch: one uint64 per tile of PT_LIGHT_SCAN_TILE pixels.  Three kernels: per-tile counts, their scan, the scatter
+struct PtAdaptiveRule {
+    double tol2, floor2;
+    uint32_t min_samples, max_samples;
+};
+#define PT_ADAPTIVE_LIST_BYTES(n) ((size_t)16 + (size_t)(n) * 8 + PT_LIGHT_TABLE_TILES(n) * 8)
+hipError_t ptk_adaptive_select(const PtPixelMoments* moments, uint32_t npix, const PtAdaptiveRule& rule, void* list, hipStream_t s);
 // pt_light_table: the selection table of lights[0 .. nl) over the RAW records (the prepared ones hold the same e1, e2 and N bit for
 // bit: pt_prep_kernel).  cdf: PT_LIGHT_TABLE_WORDS(nl) uint64 -- cdf[0 .. nl], then the build's scratch: the largest power's bits and
 // one sum per tile of PT_LIGHT_SCAN_TILE entries; tri_q: uint32[ntri].  One clear, then four kernels (weights and their maximum;

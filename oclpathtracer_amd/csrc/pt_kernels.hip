@@ -3543,8 +3543,8 @@ PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f
 }
 
 // the parameter block of an instantiation, and its counts (none without MIS)
-template <bool MIS, bool POWER = false, bool RR = false>
-using PtIndirectArgs = std::conditional_t<RR, PtIndirectRrParams, std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>>;
+template <bool MIS, bool POWER = false, bool RR = false, bool LIST = false>
+using PtIndirectArgs = std::conditional_t<LIST, PtIndirectListParams, std::conditional_t<RR, PtIndirectRrParams, std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>>>;
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectParams&) { return nullptr; }
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectMisParams& I) { return I.counts; }
 PTK_DEV const uint64_t* pt_light_cdf(const PtIndirectParams&) { return nullptr; }
@@ -3685,6 +3685,23 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
     if (act) pt_indirect_store(D, item, L);
 }
 
+// the start of item `item` of a LIST launch (PtIndirectListParams; pt_render_indirect_pixels): frame f = item / listed pixels of slot
+// j = item % listed pixels -- one 8-byte vector load, consecutive lanes consecutive slots --, the slot's pixel clamped into the local
+// image (an out-of-range slot is defined behaviour, as a light index is), its own frame number; from there on pt_item_begin's sample
+PTK_DEV void pt_list_item_begin(const PtIndirectListParams& I, unsigned item, unsigned& lp, uint32_t& seed, f3& o, f3& d)
+{
+    const PtTraceParams& P = I.d.t;
+    const unsigned f = item / I.d.npix;
+    const uint2 slot = I.slots[item - f * I.d.npix];
+    lp = slot.x < P.npix_local ? slot.x : P.npix_local - 1u;
+    const uint32_t frame = (slot.y + I.frame_off + f) & 0x7fffffffu;
+    unsigned x, grow;
+    pt_pixel_xy<false>(P, nullptr, lp, x, grow);
+    const unsigned gid = grow * (unsigned)P.width + x;
+    seed = gid + pt_hash_u32(frame);
+    pt_generate_ray((int)x, (int)grow, P.inv_width, P.inv_height, P.aspect, PT_CAM_K(I.d.cam), seed, o, d);
+}
+
 // Brute force with Russian roulette (pt_render_indirect_rr): a NEW kernel beside pt_indirect_kernel, which stays as it is.  Roulette
 // shortens the average path, hardly the longest of 64, so in a kernel that walks 64 samples in lock step it would only empty the exec
 // mask.  Here a wave owns a contiguous RUN of PT_RR_RUN items, [run0, end), and REFILLS: at the top of every iteration the lanes whose
@@ -3695,8 +3712,9 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
 // Termination: an iteration starts with at least one live lane (else the wave leaves: no lane alive means the refill found the run
 // exhausted), and every live lane either ends its path in it or raises its bounce, which is below B; every refill raises `next`,
 // which is at most `end`.  So a wave runs at most PT_RR_RUN * B iterations.  No spin, no persistent grid.
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS, bool POWER>
-__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_rr_kernel(const PtIndirectRrParams I)
+// LIST (pt_render_indirect_pixels): the items are frames of a list of pixels; only the sample's start differs (pt_list_item_begin)
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS, bool POWER, bool LIST = false>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST> I)
 {
     static_assert(PT_RR_RUN % 64 == 0 && PT_RR_RUN >= 64, "a run is whole waves of items");
     const PtDirectParams& D = I.d;
@@ -3724,7 +3742,8 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_rr_kernel(const 
             if (it < end) {
                 unsigned lp;
                 item = it;
-                pt_item_begin(P, D.cam, D.npix, D.frame0, item, lp, seed, o, d);
+                if constexpr (LIST) pt_list_item_begin(I, item, lp, seed, o, d);
+                else pt_item_begin(P, D.cam, D.npix, D.frame0, item, lp, seed, o, d);
                 L = mk3(0.0f, 0.0f, 0.0f);
                 mask = mk3(1.0f, 1.0f, 1.0f);
                 i = 0;
@@ -3790,10 +3809,11 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_rr_kernel(const 
 // wo is the negated incoming direction, which the shadow rays overwrite in d, so it is kept; o is dead while p is live.
 // With MIS a lane also holds pb from the BRDF sample to the next closest hit, across that search: 34 registers.  The counts and the
 // emitter's record are gathered where they are used, as the materials are.
-template <bool MIS = false, bool POWER = false, bool RR = false>
+template <bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false>
 struct PtIndirectWork {
+    static_assert(RR || !LIST, "a list launch is a roulette launch");
     static constexpr bool ANY = true;
-    const PtIndirectArgs<MIS, POWER, RR>& I;
+    const PtIndirectArgs<MIS, POWER, RR, LIST>& I;
     unsigned n;
     int k;           // the current ray: -1 = the vertex's closest search, 0 .. K-1 = the shadow ray of light sample k
     int bounce;      // loop index i of traceRays (:229)
@@ -3806,7 +3826,8 @@ struct PtIndirectWork {
     {
         unsigned lp;
         item = item_;
-        pt_item_begin(I.d.t, I.d.cam, I.d.npix, I.d.frame0, item, lp, seed, o, d);
+        if constexpr (LIST) pt_list_item_begin(I, item, lp, seed, o, d);
+        else pt_item_begin(I.d.t, I.d.cam, I.d.npix, I.d.frame0, item, lp, seed, o, d);
         k = -1;
         bounce = 0;
         mask = mk3(1.0f, 1.0f, 1.0f);
@@ -3866,12 +3887,14 @@ struct PtIndirectWork {
 #endif
 // The RR = true instantiations (Russian roulette, pt_roulette in next_ray) take PtIndirectRrParams and keep the three waves: R and cap are
 // scalar, the roulette's r, s and q die where they are used (profiles/roulette/kernel_resources.txt has the compiler's figures)
-template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false, bool RR = false>
+// The LIST = true instantiations (pt_render_indirect_pixels) take PtIndirectListParams: the slot is loaded and dies in begin(), the
+// pointer and the offset are scalar (profiles/adaptive/kernel_resources.txt)
+template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_INDIRECT_BVH_WAVES, PT_INDIRECT_BVH_WAVES)))
-void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER, RR> I)
+void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER, RR, LIST> I)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtIndirectWork<MIS, POWER, RR> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
+    PtIndirectWork<MIS, POWER, RR, LIST> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(I.d.t, W);
 }
 
@@ -4025,9 +4048,184 @@ __global__ __launch_bounds__(256) void pt_moments_resolve_kernel(const PtPixelMo
     }
 }
 
+// ---- adaptive sampling (pt_adaptive_select, pt_render_indirect_pixels, pt_sample_moments_pixels; include/pt_shim.h) ----
+// the pixel a slot names, clamped into the local image: an out-of-range slot is defined behaviour, never an out-of-range access
+PTK_DEV uint32_t pt_slot_pixel(uint2 slot, uint32_t npix) { return slot.x < npix ? slot.x : npix - 1u; }
+
+// pt_fold_list_kernel: pt_fold_kernel's chain for the pixels of a list.  One lane per (slot j, channel): the radiance of frame f of
+// the launch is rad[f][j], its number z = (the slot's frame + frame_off + f) & 0x7fffffff -- the number the list kernels seeded it
+// with.  A slot that starts at frame 0 starts afresh, every other one resumes the pixel's mean.  The slots' frames differ, so 1/z is
+// tabulated for all of [1, PT_FOLD_RCP_N).  Listed pixels are distinct (the caller's contract), so no two lanes share a word.
+__global__ __launch_bounds__(256) void pt_fold_list_kernel(const PtFoldListParams P)
+{
+    __shared__ double tab[3][128];
+    __shared__ float rcp_z[PT_FOLD_RCP_N];
+    for (int k = (int)threadIdx.x; k < 384; k += 256) {
+        int w = k >> 7, i = k & 127;
+        tab[w][i] = w == 0 ? pt_pow_logc_tab[i] : w == 1 ? pt_pow_logl_tab[i] : pt_pow_exp2_tab[i];
+    }
+    for (int k = 1 + (int)threadIdx.x; k < PT_FOLD_RCP_N; k += 256) rcp_z[k] = 1.0f / (float)k;
+    __syncthreads();
+    const double* LC = tab[0];
+    const double* LL = tab[1];
+    const double* ET = tab[2];
+    const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned j = tid / 3u, ch = tid - 3u * j;
+    if (j >= P.num_listed) return;
+    const uint2 slot = P.slots[j];
+    float* px = reinterpret_cast<float*>(P.fb + pt_slot_pixel(slot, P.npix_local));
+    const uint32_t z0 = slot.y + P.frame_off;
+    PtFoldChain s;
+    s.m = 0.0f;
+    s.v = 0.0f;
+    s.E = 0.0;
+    s.l = 0.0;
+    s.reg = false;
+    if ((z0 & 0x7fffffffu) != 0u) s.m = px[ch];   // a resumed pixel: its first decode is the literal pow
+    const float* radp = P.rad + (size_t)tid;      // (== rad + j * 3 + ch: consecutive lanes read consecutive floats)
+    const size_t stride = (size_t)P.num_listed * 3u;
+    for (int f = 0; f < P.frame_count; ++f) {
+        const float c = radp[(size_t)f * stride];
+        pt_fold_frame(s, (int)((z0 + (uint32_t)f) & 0x7fffffffu), c, rcp_z, LC, LL, ET, nullptr);
+    }
+    if (P.frame_count > 0) {
+        px[ch] = s.m;
+        if (ch == 0u) px[3] = 1.0f;
+    }
+}
+
+// pt_sample_moments_list_kernel: pt_sample_moments_kernel's rule (pt_moments_add, frames ascending, one lane per pixel) for the
+// pixels of a list: slot j's samples are samples[f][j].  The record is read, never reset
+__global__ __launch_bounds__(256) void pt_sample_moments_list_kernel(const float* __restrict__ samples, PtPixelMoments* __restrict__ moments,
+                                                                     const uint2* __restrict__ slots, uint32_t num_listed, uint32_t npix,
+                                                                     int32_t frames)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= num_listed) return;
+    PtPixelMoments& m = moments[pt_slot_pixel(slots[j], npix)];
+    PtMomentsAcc a = { m.sum[0], m.sum[1], m.sum[2], m.sum2[0], m.sum2[1], m.sum2[2], m.n, m.rejected };
+    const size_t stride = (size_t)num_listed * 3u;
+    const float* src = samples + (size_t)j * 3u;
+    for (int32_t f = 0; f < frames; ++f) {
+        pt_moments_add(a, src[0], src[1], src[2]);
+        src += stride;
+    }
+    m.sum[0] = a.s0, m.sum[1] = a.s1, m.sum[2] = a.s2;
+    m.sum2[0] = a.q0, m.sum2[1] = a.q1, m.sum2[2] = a.q2;
+    m.n = a.n, m.rejected = a.rejected;
+}
+
+// The rule of pt_adaptive_select for one record: *taken = n + rejected (64 bits).  mean, var, b and c restate the expressions of
+// pt_moments_resolve_kernel (which stays as it is): binary64, every operation rounded on its own.  The comparison is false for a NaN.
+PTK_DEV bool pt_adaptive_active(const PtPixelMoments& m, const PtAdaptiveRule& R, uint64_t* taken)
+{
+    const uint32_t n = m.n;
+    *taken = (uint64_t)n + (uint64_t)m.rejected;
+    if (*taken >= (uint64_t)R.max_samples) return false;
+    if (n < R.min_samples) return true;
+    if (n < 2u) return false;
+    const double nd = (double)n;
+    double mean[3], var[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        mean[ch] = m.sum[ch] / nd;
+        const double t = m.sum[ch] * mean[ch];
+        const double d = m.sum2[ch] - t;
+        const double v = d / (double)(n - 1u);
+        var[ch] = v > 0.0 ? v : 0.0;
+    }
+    const double b = ((var[0] / nd) + (var[1] / nd)) + (var[2] / nd);
+    const double c = ((mean[0] * mean[0]) + (mean[1] * mean[1])) + (mean[2] * mean[2]);
+    return b > R.tol2 * (c + R.floor2);
+}
+
+// An ordered compaction on the light table's tiling (a thread owns PT_LIGHT_SCAN_ITEMS consecutive pixels, a workgroup one tile of
+// PT_LIGHT_SCAN_TILE): pt_adaptive_count_kernel counts each tile's active pixels, pt_adaptive_tiles_kernel turns the counts into the
+// tiles' offsets and writes the header, pt_adaptive_scatter_kernel evaluates the rule again (the same bits) and stores the slots at
+// offset + the prefix within the tile.  Integer throughout: the list does not depend on the order of the scan.
+__global__ __launch_bounds__(PT_LIGHT_SCAN_BLOCK) void pt_adaptive_count_kernel(const PtPixelMoments* __restrict__ moments, uint32_t npix,
+                                                                                const PtAdaptiveRule R, uint64_t* __restrict__ tile_sums)
+{
+    __shared__ uint64_t lds[PT_LIGHT_SCAN_BLOCK];
+    const uint64_t first = (uint64_t)blockIdx.x * PT_LIGHT_SCAN_TILE + threadIdx.x * PT_LIGHT_SCAN_ITEMS;
+    uint64_t sum = 0ull;
+    for (unsigned k = 0; k < PT_LIGHT_SCAN_ITEMS; ++k) {
+        uint64_t taken;
+        if (first + k < (uint64_t)npix && pt_adaptive_active(moments[first + k], R, &taken)) ++sum;
+    }
+    uint64_t total;
+    pt_light_block_scan(sum, lds, &total);
+    if (threadIdx.x == 0u) tile_sums[blockIdx.x] = total;
+}
+
+// one workgroup: tile_sums[0 .. ntiles) become exclusive prefix sums; the header takes the count
+__global__ __launch_bounds__(PT_LIGHT_SCAN_BLOCK) void pt_adaptive_tiles_kernel(uint64_t* __restrict__ tile_sums, unsigned ntiles, uint32_t* __restrict__ header)
+{
+    __shared__ uint64_t lds[PT_LIGHT_SCAN_BLOCK];
+    const unsigned per = (ntiles + PT_LIGHT_SCAN_BLOCK - 1u) / PT_LIGHT_SCAN_BLOCK;
+    const unsigned first = threadIdx.x * per < ntiles ? threadIdx.x * per : ntiles, end = ntiles - first < per ? ntiles : first + per;
+    uint64_t sum = 0ull;
+    for (unsigned i = first; i < end; ++i) sum += tile_sums[i];
+    uint64_t total;
+    uint64_t run = pt_light_block_scan(sum, lds, &total);
+    for (unsigned i = first; i < end; ++i) {
+        const uint64_t v = tile_sums[i];
+        tile_sums[i] = run;
+        run += v;
+    }
+    if (threadIdx.x < 4u) header[threadIdx.x] = threadIdx.x == 0u ? (uint32_t)total : 0u;   // (total <= npix < 2^32)
+}
+
+__global__ __launch_bounds__(PT_LIGHT_SCAN_BLOCK) void pt_adaptive_scatter_kernel(const PtPixelMoments* __restrict__ moments, uint32_t npix,
+                                                                                  const PtAdaptiveRule R, const uint64_t* __restrict__ tile_sums,
+                                                                                  uint2* __restrict__ slots)
+{
+    __shared__ uint64_t lds[PT_LIGHT_SCAN_BLOCK];
+    const uint64_t first = (uint64_t)blockIdx.x * PT_LIGHT_SCAN_TILE + threadIdx.x * PT_LIGHT_SCAN_ITEMS;
+    uint32_t frame[PT_LIGHT_SCAN_ITEMS];
+    unsigned active = 0u;   // bit k: pixel first + k is listed
+    for (unsigned k = 0; k < PT_LIGHT_SCAN_ITEMS; ++k) {
+        uint64_t taken = 0ull;
+        if (first + k < (uint64_t)npix && pt_adaptive_active(moments[first + k], R, &taken)) active |= 1u << k;
+        frame[k] = (uint32_t)taken;
+    }
+    uint64_t total;
+    uint64_t at = tile_sums[blockIdx.x] + pt_light_block_scan((uint64_t)__popc(active), lds, &total);   // (at most the pixel's own index)
+    for (unsigned k = 0; k < PT_LIGHT_SCAN_ITEMS; ++k)
+        if (active & (1u << k)) slots[at++] = make_uint2((uint32_t)(first + k), frame[k]);
+}
+
 // ------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------
+hipError_t ptk_fold_list(const PtFoldListParams& p, hipStream_t s)
+{
+    if (p.num_listed == 0 || p.frame_count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pt_fold_list_kernel, dim3((unsigned)(((size_t)p.num_listed * 3 + 255) / 256)), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t ptk_sample_moments_list(const float* samples, PtPixelMoments* moments, const uint2* slots, uint32_t num_listed, uint32_t npix,
+                                   int32_t frames, hipStream_t s)
+{
+    if (num_listed == 0 || npix == 0 || frames <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pt_sample_moments_list_kernel, dim3((unsigned)(((uint64_t)num_listed + 255u) / 256u)), dim3(256), 0, s, samples, moments, slots,
+                       num_listed, npix, frames);
+    return hipGetLastError();
+}
+
+hipError_t ptk_adaptive_select(const PtPixelMoments* moments, uint32_t npix, const PtAdaptiveRule& rule, void* list, hipStream_t s)
+{
+    if (npix == 0) return hipMemsetAsync(list, 0, 16, s);
+    const unsigned ntiles = (unsigned)PT_LIGHT_TABLE_TILES(npix);
+    uint2* slots = reinterpret_cast<uint2*>(static_cast<char*>(list) + 16);
+    uint64_t* tile_sums = reinterpret_cast<uint64_t*>(slots + npix);   // the build's scratch, behind the specified part
+    hipLaunchKernelGGL(pt_adaptive_count_kernel, dim3(ntiles), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, moments, npix, rule, tile_sums);
+    hipLaunchKernelGGL(pt_adaptive_tiles_kernel, dim3(1), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, tile_sums, ntiles, static_cast<uint32_t*>(list));
+    hipLaunchKernelGGL(pt_adaptive_scatter_kernel, dim3(ntiles), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, moments, npix, rule, tile_sums, slots);
+    return hipGetLastError();
+}
+
 hipError_t ptk_prep_triangles(const PtRawTriangle* raw, PtPrepTriangle* out, int ntri, unsigned int* det_bound_bits,
                               hipStream_t s)
 {
@@ -4252,21 +4450,21 @@ hipError_t ptk_indirect_power(const PtIndirectPowerParams& a, int bvh_blocks, Pt
     return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, m.bvh, bvh_blocks, s);
 }
 
-// the roulette kernels of one (MIS, POWER) estimator: pt_pick's shape, as ptk_indirect_power has it
-template <bool MIS, bool POWER>
-static hipError_t pt_launch_indirect_rr(const PtIndirectRrParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
+// the roulette kernels of one (MIS, POWER) estimator: pt_pick's shape, as ptk_indirect_power has it.  LIST: their list forms
+template <bool MIS, bool POWER, bool LIST = false>
+static hipError_t pt_launch_indirect_rr(const PtIndirectArgs<MIS, POWER, true, LIST>& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
 {
     const bool q3 = m.quads == 3;
-    void (*kernel)(const PtIndirectRrParams);
+    void (*kernel)(const PtIndirectArgs<MIS, POWER, true, LIST>);
     if (m.bvh) {
-        kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3, MIS, POWER, true>, pt_indirect_bvh_kernel<true, 0, MIS, POWER, true>,
-                         pt_indirect_bvh_kernel<false, 0, MIS, POWER, true>);
+        kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3, MIS, POWER, true, LIST>, pt_indirect_bvh_kernel<true, 0, MIS, POWER, true, LIST>,
+                         pt_indirect_bvh_kernel<false, 0, MIS, POWER, true, LIST>);
         return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, true, bvh_blocks, s);
     }
     const int ntri = a.d.t.ntri;
-    if (ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_rr_kernel<true, 1, 3, MIS, POWER>, pt_indirect_rr_kernel<true, 1, 0, MIS, POWER>,
-                                                 pt_indirect_rr_kernel<false, 1, 0, MIS, POWER>);
-    else kernel = m.det_bounded ? pt_indirect_rr_kernel<true, 2, 0, MIS, POWER> : pt_indirect_rr_kernel<false, 2, 0, MIS, POWER>;
+    if (ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_rr_kernel<true, 1, 3, MIS, POWER, LIST>, pt_indirect_rr_kernel<true, 1, 0, MIS, POWER, LIST>,
+                                                 pt_indirect_rr_kernel<false, 1, 0, MIS, POWER, LIST>);
+    else kernel = m.det_bounded ? pt_indirect_rr_kernel<true, 2, 0, MIS, POWER, LIST> : pt_indirect_rr_kernel<false, 2, 0, MIS, POWER, LIST>;
     // one wave per run of PT_RR_RUN items, the table kernels' LDS without the pools (pt_launch_search's brute-force form)
     const unsigned wg_waves = PT_TRACE_THREADS / 64;
     const unsigned waves = (a.d.nitems + (unsigned)PT_RR_RUN - 1u) / (unsigned)PT_RR_RUN;
@@ -4287,6 +4485,20 @@ int ptk_indirect_rr_bvh_blocks_per_cu(bool mis, bool power)
     const size_t lds = ptk_trace_bvh_lds_bytes();
     if (power) return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, true, true>, lds) : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, true, true>, lds);
     return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, false, true>, lds) : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, false, true>, lds);
+}
+
+hipError_t ptk_indirect_list(const PtIndirectListParams& a, int bvh_blocks, PtSearchMode m, bool mis, bool power, hipStream_t s)
+{
+    if (a.d.nitems == 0) return hipSuccess;
+    if (power) return mis ? pt_launch_indirect_rr<true, true, true>(a, bvh_blocks, m, s) : pt_launch_indirect_rr<false, true, true>(a, bvh_blocks, m, s);
+    return mis ? pt_launch_indirect_rr<true, false, true>(a, bvh_blocks, m, s) : pt_launch_indirect_rr<false, false, true>(a, bvh_blocks, m, s);
+}
+
+int ptk_indirect_list_bvh_blocks_per_cu(bool mis, bool power)
+{
+    const size_t lds = ptk_trace_bvh_lds_bytes();
+    if (power) return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, true, true, true>, lds) : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, true, true, true>, lds);
+    return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, false, true, true>, lds) : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, false, true, true>, lds);
 }
 
 int ptk_indirect_power_bvh_blocks_per_cu(bool mis)

@@ -141,6 +141,7 @@ struct pt_device_s {
     int indirect_mis_bvh_blocks_per_cu;   // ... and of its MIS instantiation
     int direct_power_bvh_blocks_per_cu, indirect_power_bvh_blocks_per_cu, indirect_power_mis_bvh_blocks_per_cu;   // ... and of the POWER ones
     int indirect_rr_bvh_blocks_per_cu[2][2];   // ... and of the roulette ones, [mis][power]
+    int indirect_list_bvh_blocks_per_cu[2][2]; // ... and of their list forms (pt_render_indirect_pixels)
     unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
     unsigned int* trav_dev;  // ... as the device addresses it
     // ---- fused-render workspace: the STREAMING renderer (render_part, plan_chunks, the ring).  A render walks its frames in chunks of
@@ -368,7 +369,10 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->indirect_power_bvh_blocks_per_cu = ptk_indirect_power_bvh_blocks_per_cu(false);
     d->indirect_power_mis_bvh_blocks_per_cu = ptk_indirect_power_bvh_blocks_per_cu(true);
     for (int mis = 0; mis < 2; ++mis)
-        for (int power = 0; power < 2; ++power) d->indirect_rr_bvh_blocks_per_cu[mis][power] = ptk_indirect_rr_bvh_blocks_per_cu(mis != 0, power != 0);
+        for (int power = 0; power < 2; ++power) {
+            d->indirect_rr_bvh_blocks_per_cu[mis][power] = ptk_indirect_rr_bvh_blocks_per_cu(mis != 0, power != 0);
+            d->indirect_list_bvh_blocks_per_cu[mis][power] = ptk_indirect_list_bvh_blocks_per_cu(mis != 0, power != 0);
+        }
     *out = d;
     return PT_OK;
 }
@@ -1803,17 +1807,22 @@ static_assert(sizeof(pt_indirect_params) == 64, "pt_indirect_params layout");
 // illumination (its own kernels), otherwise the depth of an indirect render.  mis: the MIS estimator, which reads light_counts (NULL
 // otherwise).  table: NULL = the uniform choice, otherwise {cdf, tri_q} of pt_light_table, the choice by power.  what: the message
 // for a field out of range.  rr: NULL, or the roulette of pt_render_indirect_rr (checked by it; max_bounces > 0): the launch is ptk_indirect_rr
+// pixels: NULL, or the list of pt_render_indirect_pixels (rr given): frame_count frames of each listed pixel, the launch is
+// ptk_indirect_list and the fold ptk_fold_list; the workspace is laid out for num_listed pixels
+struct PtPixelList { pt_buffer_t list; uint32_t num_listed; };
 static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts, bool mis,
                       pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params& a, int max_bounces, const char* what,
-                      const pt_camera* cam, pt_event_t ev, const pt_buffer_t* table = nullptr, const pt_roulette* rr = nullptr)
+                      const pt_camera* cam, pt_event_t ev, const pt_buffer_t* table = nullptr, const pt_roulette* rr = nullptr,
+                      const PtPixelList* pixels = nullptr)
 {
+    pt_buffer_t list = pixels ? pixels->list : nullptr;
     const bool power = table != nullptr;
     pt_buffer_t cdf = power ? table[0] : nullptr, tri_q = power ? table[1] : nullptr;
     int rc;
     PtCamera c = reference_camera();
     if (cam && (rc = camera_derive(cam, &c))) return rc;
-    if (!triangles || !materials || !samples || !framebuffer) return fail(PT_ERR_INVALID, "null buffer handle");
-    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer, cdf, tri_q })) || (rc = check_event(d, ev))) return rc;
+    if (!triangles || !materials || !samples || !framebuffer || (pixels && !list)) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer, cdf, tri_q, list })) || (rc = check_event(d, ev))) return rc;
     if (a.num_triangles < 0 || a.num_materials < 1 || a.num_lights < 0 || a.light_samples < 1 || a.light_samples > 256)
         return fail(PT_ERR_INVALID, "%s", what);
     if (a.num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
@@ -1827,13 +1836,15 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     if ((rc = check_image(what, a.width, a.height, a.frame_begin, a.frame_count, a.stripe_rows, a.n_ranks, a.rank, npix64)))
         return rc;
     const uint32_t npix = (uint32_t)npix64;
-    const size_t frame_bytes = (size_t)npix * 12, fb_bytes = (size_t)npix * sizeof(float4), light_bytes = (size_t)a.num_lights * sizeof(int32_t);
+    if (pixels && pixels->num_listed > npix) return fail(PT_ERR_INVALID, "%u pixels listed, the local image has %u", pixels->num_listed, npix);
+    const uint32_t wpix = pixels ? pixels->num_listed : npix;   // the pixels of one frame of the workspace
+    const size_t frame_bytes = (size_t)wpix * 12, fb_bytes = (size_t)npix * sizeof(float4), light_bytes = (size_t)a.num_lights * sizeof(int32_t);
     if ((rc = check_triangles(triangles, a.num_triangles))) return rc;
     if ((size_t)a.num_materials * sizeof(PtRawMaterial) > materials->bytes)
         return fail(PT_ERR_RANGE, "material buffer holds %zu bytes, %d materials need %zu", materials->bytes, a.num_materials,
                     (size_t)a.num_materials * sizeof(PtRawMaterial));
     if (lights && light_bytes > lights->bytes) return fail(PT_ERR_RANGE, "light list holds %zu bytes, %d lights need %zu", lights->bytes, a.num_lights, light_bytes);
-    if (frame_bytes > samples->bytes) return fail(PT_ERR_RANGE, "sample workspace holds %zu bytes, one frame of %u pixels needs %zu", samples->bytes, npix, frame_bytes);
+    if (frame_bytes > samples->bytes) return fail(PT_ERR_RANGE, "sample workspace holds %zu bytes, one frame of %u pixels needs %zu", samples->bytes, wpix, frame_bytes);
     if (fb_bytes > framebuffer->bytes) return fail(PT_ERR_RANGE, "framebuffer holds %zu bytes, %u pixels need %zu", framebuffer->bytes, npix, fb_bytes);
     if ((uintptr_t)samples->dptr & 3u) return fail(PT_ERR_INVALID, "the sample workspace must be 4-byte aligned");
     if ((uintptr_t)framebuffer->dptr & 15u) return fail(PT_ERR_INVALID, "the framebuffer must be 16-byte aligned");
@@ -1863,17 +1874,24 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
                 return fail(PT_ERR_INVALID, "the light table overlaps the sample workspace, the framebuffer, the light list or the light counts");
         if (ranges_overlap(cdf, cdf_bytes, tri_q, q_bytes)) return fail(PT_ERR_INVALID, "the light table's cdf and tri_q overlap");
     }
+    if (pixels) {
+        const size_t list_bytes = 16 + (size_t)pixels->num_listed * sizeof(pt_pixel_slot);
+        if (list_bytes > list->bytes) return fail(PT_ERR_RANGE, "the pixel list holds %zu bytes, %u slots need %zu", list->bytes, pixels->num_listed, list_bytes);
+        if ((uintptr_t)list->dptr & 7u) return fail(PT_ERR_INVALID, "the pixel list must be 8-byte aligned");
+        if (ranges_overlap(list, list_bytes, samples, samples->bytes) || ranges_overlap(list, list_bytes, framebuffer, fb_bytes))
+            return fail(PT_ERR_INVALID, "the pixel list overlaps the sample workspace or the framebuffer");
+    }
     // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
     if ((rc = check_traversal(d))) return rc;
     if ((rc = enter_stream(d))) return rc;
-    if (a.frame_count == 0 || npix == 0) {
+    if (a.frame_count == 0 || wpix == 0) {   // (no local pixel: none listed)
         if ((rc = event_begin(d, ev))) return rc;
         return event_end(d, ev);
     }
     PtSearch search;
     if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
     if ((rc = event_begin(d, ev))) return rc;
-    PtIndirectRrParams ip;   // (every indirect block is a base of it)
+    PtIndirectListParams ip;   // (every indirect block is a base of it)
     memset(&ip, 0, sizeof ip);
     ip.B = max_bounces;
     if (rr) {
@@ -1888,7 +1906,7 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     p.cam = c;
     p.lights = a.num_lights > 0 ? (const int32_t*)lights->dptr : nullptr;
     p.samples = (float*)samples->dptr;
-    p.npix = npix;
+    p.npix = wpix;
     p.K = a.light_samples;
     p.nl = a.num_lights;
     ip.counts = mis && a.num_lights > 0 ? (const int32_t*)light_counts->dptr : nullptr;
@@ -1901,17 +1919,34 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     fp.rad = p.samples;
     fp.fb = (float4*)framebuffer->dptr;
     fp.npix_local = npix;
-    const int per_cu = rr ? d->indirect_rr_bvh_blocks_per_cu[mis][power] :
+    PtFoldListParams lp;
+    memset(&lp, 0, sizeof lp);
+    if (pixels) {
+        ip.slots = reinterpret_cast<const uint2*>(static_cast<const char*>(list->dptr) + 16);
+        lp.rad = p.samples;
+        lp.fb = fp.fb;
+        lp.slots = ip.slots;
+        lp.num_listed = wpix;
+        lp.npix_local = npix;
+    }
+    const int per_cu = pixels ? d->indirect_list_bvh_blocks_per_cu[mis][power] : rr ? d->indirect_rr_bvh_blocks_per_cu[mis][power] :
                        power ? (mis ? d->indirect_power_mis_bvh_blocks_per_cu
                                     : max_bounces > 0 ? d->indirect_power_bvh_blocks_per_cu : d->direct_power_bvh_blocks_per_cu)
                              : (mis ? d->indirect_mis_bvh_blocks_per_cu : max_bounces > 0 ? d->indirect_bvh_blocks_per_cu : d->direct_bvh_blocks_per_cu);
     const int bvh_blocks = !search.mode.bvh ? 0 : d->prop.multiProcessorCount * per_cu;   // (each kernel its own grid: pt_kernels.h)
     // whole frames per chunk: what the workspace holds, fewer than 2^31 samples per launch; a launch, then its fold
-    const int64_t per_chunk = (int64_t)std::min<uint64_t>(samples->bytes / frame_bytes, 0x7fffffffu / npix);
+    const int64_t per_chunk = (int64_t)std::min<uint64_t>(samples->bytes / frame_bytes, 0x7fffffffu / wpix);
     for (int64_t done = 0; done < a.frame_count; done += per_chunk) {
         const int nf = (int)std::min<int64_t>(per_chunk, a.frame_count - done);
         p.frame0 = a.frame_begin + (int)done;
-        p.nitems = (uint32_t)nf * npix;
+        p.nitems = (uint32_t)nf * wpix;
+        if (pixels) {   // every slot continues from its own frame: the call's offset, then the frames of the chunks before
+            ip.frame_off = lp.frame_off = (uint32_t)p.frame0;
+            lp.frame_count = nf;
+            HIP_TRY(ptk_indirect_list(ip, bvh_blocks, search.mode, mis, power, d->stream));
+            HIP_TRY(ptk_fold_list(lp, d->stream));
+            continue;
+        }
         if (power && max_bounces == 0) {
             static_cast<PtDirectParams&>(dp) = p;
             dp.cdf = ip.cdf;
@@ -1945,7 +1980,7 @@ extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_
 // pt_render_indirect and pt_render_indirect_mis: the same parameter block, the same checks of it
 static int render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts, bool mis,
                            pt_buffer_t samples, pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev,
-                           const pt_buffer_t* table = nullptr, const pt_roulette* rr = nullptr)
+                           const pt_buffer_t* table = nullptr, const pt_roulette* rr = nullptr, const PtPixelList* pixels = nullptr)
 {
     int rc = use_device(d);
     if (rc) return rc;
@@ -1961,7 +1996,7 @@ static int render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t mat
     a.light_samples = b.light_samples;
     a.stripe_rows = b.stripe_rows; a.n_ranks = b.n_ranks; a.rank = b.rank;
     return render_lit(d, triangles, materials, lights, light_counts, mis, samples, framebuffer, a, b.max_bounces,
-                      "invalid indirect-illumination parameters", cam, ev, table, rr);
+                      "invalid indirect-illumination parameters", cam, ev, table, rr, pixels);
 }
 
 extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
@@ -2004,9 +2039,11 @@ extern "C" int pt_render_indirect_power(pt_device_t d, pt_buffer_t triangles, pt
 // ---- Russian roulette (include/pt_shim.h) ------------------------------------------------------------------------------------------
 static_assert(sizeof(pt_roulette) == 16, "pt_roulette layout");
 
-extern "C" int pt_render_indirect_rr(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
-                                     pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
-                                     const pt_indirect_params* params, const pt_roulette* roulette, const pt_camera* cam, pt_event_t ev)
+// pt_render_indirect_rr, and with `pixels` pt_render_indirect_pixels: the same checks of the roulette and the table
+static int render_indirect_rr(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
+                              pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
+                              const pt_indirect_params* params, const pt_roulette* roulette, const pt_camera* cam, pt_event_t ev,
+                              const PtPixelList* pixels)
 {
     if (mis != 0 && mis != 1) return fail(PT_ERR_INVALID, "mis must be 0 or 1");
     if (!roulette) return fail(PT_ERR_INVALID, "roulette == NULL");
@@ -2019,7 +2056,85 @@ extern "C" int pt_render_indirect_rr(pt_device_t d, pt_buffer_t triangles, pt_bu
         return fail(PT_ERR_INVALID, "the light table is cdf AND tri_q (pt_light_table), or neither for the uniform choice");
     const pt_buffer_t table[2] = { cdf, tri_q };
     return render_indirect(d, triangles, materials, lights, mis ? light_counts : nullptr, mis != 0, samples, framebuffer, params, cam, ev,
-                           power ? table : nullptr, &r);
+                           power ? table : nullptr, &r, pixels);
+}
+
+extern "C" int pt_render_indirect_rr(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
+                                     pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
+                                     const pt_indirect_params* params, const pt_roulette* roulette, const pt_camera* cam, pt_event_t ev)
+{
+    return render_indirect_rr(d, triangles, materials, lights, mis, light_counts, cdf, tri_q, samples, framebuffer, params, roulette, cam, ev, nullptr);
+}
+
+// ---- adaptive sampling (include/pt_shim.h) -------------------------------------------------------------------------------------
+static_assert(sizeof(pt_adaptive_rule) == 32 && sizeof(pt_pixel_slot) == 8 && sizeof(pt_pixel_slot) == sizeof(uint2), "adaptive record layout");
+
+extern "C" int pt_render_indirect_pixels(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
+                                         pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
+                                         pt_buffer_t list, uint32_t num_listed, const pt_indirect_params* params, const pt_roulette* roulette,
+                                         const pt_camera* cam, pt_event_t ev)
+{
+    const PtPixelList pixels = { list, num_listed };
+    return render_indirect_rr(d, triangles, materials, lights, mis, light_counts, cdf, tri_q, samples, framebuffer, params, roulette, cam, ev, &pixels);
+}
+
+extern "C" size_t pt_adaptive_list_bytes(uint32_t num_pixels) { return PT_ADAPTIVE_LIST_BYTES(num_pixels); }
+
+extern "C" int pt_adaptive_select(pt_device_t d, pt_buffer_t moments, uint32_t num_pixels, const pt_adaptive_rule* rule, pt_buffer_t list, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!moments || !list) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { moments, list })) || (rc = check_event(d, ev))) return rc;
+    if (!rule) return fail(PT_ERR_INVALID, "rule == NULL");
+    const pt_adaptive_rule r = *rule;
+    if (!(r.tol2 >= 0.0) || !(r.floor2 >= 0.0)) return fail(PT_ERR_INVALID, "tol2 and floor2 must not be negative or NaN");
+    if (r.reserved[0] != 0 || r.reserved[1] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    const size_t moment_bytes = (size_t)num_pixels * sizeof(pt_pixel_moments), list_bytes = pt_adaptive_list_bytes(num_pixels);
+    if (moment_bytes > moments->bytes) return fail(PT_ERR_RANGE, "moments hold %zu bytes, %u pixels need %zu", moments->bytes, num_pixels, moment_bytes);
+    if (list_bytes > list->bytes)
+        return fail(PT_ERR_RANGE, "the pixel list holds %zu bytes, %u pixels need %zu (pt_adaptive_list_bytes)", list->bytes, num_pixels, list_bytes);
+    if ((uintptr_t)moments->dptr & 7u) return fail(PT_ERR_INVALID, "the moments must be 8-byte aligned");
+    if ((uintptr_t)list->dptr & 7u) return fail(PT_ERR_INVALID, "the pixel list must be 8-byte aligned");
+    if (ranges_overlap(moments, moment_bytes, list, list_bytes)) return fail(PT_ERR_INVALID, "the moments and the pixel list overlap");
+    if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
+    const PtAdaptiveRule k = { r.tol2, r.floor2, r.min_samples, r.max_samples };
+    HIP_TRY(ptk_adaptive_select((const PtPixelMoments*)moments->dptr, num_pixels, k, list->dptr, d->stream));
+    list->version++;
+    return event_end(d, ev);
+}
+
+extern "C" int pt_sample_moments_pixels(pt_device_t d, pt_buffer_t samples, pt_buffer_t moments, pt_buffer_t list, uint32_t num_listed,
+                                        int32_t frame_count, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!samples || !moments || !list) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { samples, moments, list })) || (rc = check_event(d, ev))) return rc;
+    if (frame_count < 0) return fail(PT_ERR_INVALID, "frame_count < 0");
+    // the local pixels: the whole records the moments buffer holds
+    const size_t records = std::min<size_t>(moments->bytes / sizeof(pt_pixel_moments), 0xffffffffu);
+    if ((size_t)num_listed > records) return fail(PT_ERR_INVALID, "%u pixels listed, the moments hold %zu records", num_listed, records);
+    const size_t moment_bytes = records * sizeof(pt_pixel_moments), list_bytes = 16 + (size_t)num_listed * sizeof(pt_pixel_slot);
+    const size_t frame_bytes = (size_t)num_listed * 3u * sizeof(float);
+    if (frame_bytes && (size_t)frame_count > samples->bytes / frame_bytes)
+        return fail(PT_ERR_RANGE, "sample buffer holds %zu bytes, %d frames of %u pixels need more", samples->bytes, frame_count, num_listed);
+    const size_t sample_bytes = frame_bytes * (size_t)frame_count;
+    if (list_bytes > list->bytes) return fail(PT_ERR_RANGE, "the pixel list holds %zu bytes, %u slots need %zu", list->bytes, num_listed, list_bytes);
+    if ((uintptr_t)moments->dptr & 7u) return fail(PT_ERR_INVALID, "the moments must be 8-byte aligned");
+    if ((uintptr_t)samples->dptr & 3u) return fail(PT_ERR_INVALID, "the samples must be 4-byte aligned");
+    if ((uintptr_t)list->dptr & 7u) return fail(PT_ERR_INVALID, "the pixel list must be 8-byte aligned");
+    if (ranges_overlap(samples, sample_bytes, moments, moment_bytes) || ranges_overlap(list, list_bytes, moments, moment_bytes) ||
+        ranges_overlap(list, list_bytes, samples, sample_bytes))
+        return fail(PT_ERR_INVALID, "the samples, the moments and the pixel list overlap");
+    if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
+    if (num_listed && frame_count) {
+        HIP_TRY(ptk_sample_moments_list((const float*)samples->dptr, (PtPixelMoments*)moments->dptr,
+                                        reinterpret_cast<const uint2*>(static_cast<const char*>(list->dptr) + 16), num_listed, (uint32_t)records,
+                                        frame_count, d->stream));
+        moments->version++;
+    }
+    return event_end(d, ev);
 }
 
 extern "C" size_t pt_light_table_bytes(int num_lights)

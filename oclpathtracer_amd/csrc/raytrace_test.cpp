@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power] | --only IndirectIllumination [--mis] [--lights power] [--roulette R[,cap]]] [--noise]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power] | --only IndirectIllumination [--mis] [--lights power] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]]] [--noise]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <chrono>
 #include <cmath>
@@ -121,6 +121,8 @@ struct Options {
     bool power = false;               // --lights power: DirectIllumination / IndirectIllumination choose their lights by power
     int rrFirst = 0;                  // --roulette R[,cap]: IndirectIllumination through pt_render_indirect_rr (0 = no roulette)
     float rrCap = 0.95f;
+    double adaptTol = -1.0;           // --adaptive TOL[,MIN[,MAX]]: IndirectIllumination renders MIN frames, then only the pixels still noisy (< 0 = off)
+    int adaptMin = 16, adaptMax = 0;  // MAX 0 = --frames
     bool noise = false;               // --noise: DirectIllumination / IndirectIllumination print the image's noise summary
     std::string scene = "cornellbox.bin", outDir = ".", dump, only;
 };
@@ -376,6 +378,11 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
 // most cap (0.95 unless given), under --mis and --lights power as they are set -- and the file's name gains _rr before .ppm.
 // With --noise either case renders in calls of at most as many frames as the workspace holds, takes the samples' moments after each
 // (pt_sample_moments) and prints one more line, after the case's own: the summary of pt_moments_resolve.  The image is the same.
+// With --adaptive TOL[,MIN[,MAX]] IndirectIllumination renders MIN frames (16 unless given) as above, then pass by pass lists the pixels
+// whose own relative standard error lies above TOL and that have fewer than MAX samples (--frames unless given) with
+// pt_adaptive_select, renders one workspace of further frames of the listed pixels with pt_render_indirect_pixels and counts them with
+// pt_sample_moments_pixels, until the list is empty; it prints the list's length per pass and the sample total, and the file's name
+// gains _adaptive before .ppm.
 // bounces: 0 = DirectIllumination, otherwise IndirectIllumination at that depth.
 static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
 {
@@ -456,16 +463,52 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
         if (bounces) return pt_render_indirect(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, samples.m_handle, image.m_handle, &q, 0, 0);
         return pt_render_direct(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, samples.m_handle, image.m_handle, &p, 0, 0);
     };
-    Buffer<pt_pixel_moments> moments(m_d, o.noise ? npix : 0);
+    const bool adaptive = bounces && o.adaptTol >= 0.0;
+    Buffer<pt_pixel_moments> moments(m_d, o.noise || adaptive ? npix : 0);
+    Buffer<unsigned char> pixelList(m_d, adaptive ? pt_adaptive_list_bytes((uint32_t)npix) : 0);
+    unsigned long long adaptiveSamples = 0;
+    std::string adaptivePasses;
     Buffer<unsigned char> summary(m_d, o.noise ? pt_moments_summary_bytes((uint32_t)npix) : 0);
-    if (o.noise && o.frames > 0) {
-        for (int first = 0; first < o.frames; first += chunk) {
-            const int count = o.frames - first < chunk ? o.frames - first : chunk;
+    const int uniformFrames = adaptive ? (o.adaptMin < 1 ? 1 : o.adaptMin) : o.frames;
+    if ((o.noise || adaptive) && uniformFrames > 0) {
+        for (int first = 0; first < uniformFrames; first += chunk) {
+            const int count = uniformFrames - first < chunk ? uniformFrames - first : chunk;
             IASSERT(render(first, count) == PT_OK);
             IASSERT(pt_sample_moments(m_d->m_handle, samples.m_handle, moments.m_handle, (uint32_t)npix, count, first == 0, 0) == PT_OK);
         }
     } else
         IASSERT(render(0, o.frames) == PT_OK);
+    if (adaptive) {
+        pt_adaptive_rule rule;
+        std::memset(&rule, 0, sizeof rule);
+        rule.tol2 = o.adaptTol * o.adaptTol;
+        rule.floor2 = 1e-2 * 1e-2;
+        rule.min_samples = (uint32_t)uniformFrames;
+        rule.max_samples = (uint32_t)(o.adaptMax > 0 ? o.adaptMax : o.frames);
+        pt_roulette play = roulette;
+        if (!rr) { play.first_bounce = 65535; play.max_survival = 1.0f; }   // no roulette: a first bounce no path reaches
+        adaptiveSamples = (unsigned long long)npix * (unsigned long long)uniformFrames;
+        for (;;) {
+            uint32_t header[4] = { 0, 0, 0, 0 };
+            IASSERT(pt_adaptive_select(m_d->m_handle, moments.m_handle, (uint32_t)npix, &rule, pixelList.m_handle, 0) == PT_OK);
+            pixelList.read((unsigned char*)header, sizeof header);
+            DeviceUtils::waitForCompletion(m_d);
+            const uint32_t listed = header[0];
+            if (listed == 0 || g_failures) break;
+            adaptivePasses += (adaptivePasses.empty() ? "" : " ") + std::to_string(listed);
+            const size_t fit = npix * (size_t)chunk / listed;   // frames of this list the workspace holds
+            const int hold = (int)(fit < 0x7fffffffu / listed ? fit : 0x7fffffffu / listed);
+            for (int done = 0; done < chunk; done += hold) {
+                q.frame_begin = done;
+                q.frame_count = chunk - done < hold ? chunk - done : hold;
+                IASSERT(pt_render_indirect_pixels(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0,
+                                                  o.power ? cdf.m_handle : 0, o.power ? triq.m_handle : 0, samples.m_handle, image.m_handle,
+                                                  pixelList.m_handle, listed, &q, &play, 0, 0) == PT_OK);
+                IASSERT(pt_sample_moments_pixels(m_d->m_handle, samples.m_handle, moments.m_handle, pixelList.m_handle, listed, q.frame_count, 0) == PT_OK);
+            }
+            adaptiveSamples += (unsigned long long)listed * (unsigned long long)chunk;
+        }
+    }
     IASSERT(pt_tonemap_ppm(m_d->m_handle, image.m_handle, rgb.m_handle, npix, 0) == PT_OK);
     std::vector<int> h(3 * npix, 0);
     rgb.read(h.data(), 3 * npix);
@@ -480,10 +523,13 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     else
         std::printf("DirectIllumination%s: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", o.power ? " (lights by power)" : "", dimension, dimension,
                     o.frames, (int)lights.size(), secs);
+    if (adaptive)
+        std::printf("adaptive: tolerance %g min %d max %d passes [%s] samples %llu\n", o.adaptTol, uniformFrames, o.adaptMax > 0 ? o.adaptMax : o.frames,
+                    adaptivePasses.c_str(), adaptiveSamples);
     if (o.noise) {
         pt_noise_summary ns;
         std::memset(&ns, 0, sizeof ns);
-        if (o.frames > 0) {
+        if (o.frames > 0 || adaptive) {
             IASSERT(pt_moments_resolve(m_d->m_handle, moments.m_handle, (uint32_t)npix, 0, summary.m_handle, 0) == PT_OK);
             summary.read((unsigned char*)&ns, sizeof ns);
             DeviceUtils::waitForCompletion(m_d);
@@ -497,6 +543,7 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     if (mis && std::strlen(path) + 5 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_mis.ppm");
     if (o.power && std::strlen(path) + 7 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_power.ppm");
     if (rr && std::strlen(path) + 4 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_rr.ppm");
+    if (adaptive && std::strlen(path) + 10 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_adaptive.ppm");
     FILE* fp = std::fopen(path, "w");
     IASSERT(fp != 0);
     if (fp) {
@@ -530,6 +577,17 @@ int main(int argc, char** argv)
             if (end && *end == ',') o.rrCap = std::strtof(end + 1, &end);
             if (o.rrFirst < 1 || !end || *end != 0 || !(o.rrCap > 0.0f && o.rrCap <= 1.0f)) {
                 std::fprintf(stderr, "--roulette takes R[,cap] with R >= 1 and cap in (0, 1]\n");
+                return 2;
+            }
+        }
+        else if (a == "--adaptive") {
+            const std::string v = next();
+            char* end = 0;
+            o.adaptTol = std::strtod(v.c_str(), &end);
+            if (end && *end == ',') o.adaptMin = (int)std::strtol(end + 1, &end, 10);
+            if (end && *end == ',') o.adaptMax = (int)std::strtol(end + 1, &end, 10);
+            if (end == v.c_str() || !end || *end != 0 || !(o.adaptTol >= 0.0) || o.adaptMin < 1 || o.adaptMax < 0) {
+                std::fprintf(stderr, "--adaptive takes TOL[,MIN[,MAX]] with TOL >= 0, MIN >= 1 and MAX >= 1\n");
                 return 2;
             }
         }

@@ -57,7 +57,9 @@ class DirectRenderer:
     frames are traced by one launch and folded by the next.  ``stripe_rows`` / ``n_ranks`` / ``rank`` select the rows this device
     owns, as for ``Renderer``.  The search follows the device's options exactly as renders do.  ``moments``: keep per-pixel moments
     of the samples (``variance``, ``noise``, ``render_until``); the image is the same bit for bit, ``render`` issues its frames as calls
-    of at most ``chunk_frames`` frames, each followed by ``pt_sample_moments``, and accepts ``frame_begin`` 0 or ``frames_done`` only."""
+    of at most ``chunk_frames`` frames, each followed by ``pt_sample_moments``, and accepts ``frame_begin`` 0 or ``frames_done`` only.
+    Adaptive sampling (``render_adaptive``) is ``IndirectRenderer``'s alone: for direct illumination use ``IndirectRenderer(max_bounces=1)``,
+    whose image is this renderer's bit for bit."""
 
     def __init__(self, dev: adl.Device, triangles, materials, width: int, height: int, *, light_samples: int = 1, lights=None,
                  camera: Optional[Camera] = None, num_triangles: Optional[int] = None, num_materials: Optional[int] = None,

@@ -25,6 +25,11 @@ is unchanged while most of the searches a deep path spends on a throughput of a 
 ``light_choice`` and ``moments``; ``None`` makes exactly the calls of a renderer without it.  A ``first_bounce`` of ``max_bounces`` or more
 plays no roulette and gives the parent's image bit for bit.
 
+``render_adaptive`` (with ``moments=True``) spends later frames only on the pixels that are still noisy: after a uniform start the
+device lists the pixels whose own relative standard error lies above a tolerance (``pt_adaptive_select``), renders further frames of
+the listed pixels only (``pt_render_indirect_pixels``), each from its own frame number, and counts them (``pt_sample_moments_pixels``)
+until the list is empty.  Every pixel still holds exactly what a uniform render holds for it after as many frames as it has received.
+
 ``include/pt_shim.h`` states every step.  All compute is HIP in libptshim.so.
 """
 from __future__ import annotations
@@ -64,6 +69,11 @@ class Roulette(collections.namedtuple("Roulette", "first_bounce max_survival")):
         raise TypeError("roulette must be None, a Roulette or an int (the first bounce)")
 
 
+# what render_adaptive returns: the list length of every pass, the samples the call has rendered (the uniform start included), and
+# sample_counts() after it
+AdaptiveResult = collections.namedtuple("AdaptiveResult", "passes samples counts")
+
+
 class IndirectRenderer(DirectRenderer):
     """``DirectRenderer`` (its arguments, buffers, ``render`` / ``read`` / ``release``) with paths of up to ``max_bounces``
     vertices and ``light_samples`` light samples at each of them; ``mis``: with multiple importance sampling; ``roulette``: a
@@ -80,6 +90,8 @@ class IndirectRenderer(DirectRenderer):
         self.roulette = Roulette.of(roulette)
         self._rr = None if self.roulette is None else shim.Roulette(self.roulette.first_bounce, self.roulette.max_survival)
         self.counts = None
+        self.pixel_list = None      # the list of render_adaptive, allocated by its first call
+        self._adaptive = False      # an adaptive pass has run since the last start at frame 0: the pixels share no frame number
         if not 1 <= self.max_bounces <= 65535:
             raise ValueError("max_bounces must lie in 1..65535")
         super().__init__(dev, triangles, materials, width, height, **kw)
@@ -119,8 +131,92 @@ class IndirectRenderer(DirectRenderer):
                                                 ctypes.byref(self._cam) if self._cam is not None else None,
                                                 sync._h if sync is not None else None)
 
+    def render(self, frames: int, frame_begin=None, sync=None) -> None:
+        """``DirectRenderer.render``; after an adaptive pass only a start at frame 0 is accepted: the pixels no longer share a frame
+        number that a uniform render could continue from."""
+        if self._adaptive:
+            if frame_begin is None or int(frame_begin) != 0:
+                raise ValueError("after render_adaptive the pixels share no frame number: render from frame_begin=0")
+            self._adaptive = False
+        super().render(frames, frame_begin, sync)
+
+    def set_camera(self, camera) -> None:
+        super().set_camera(camera)
+        self._adaptive = False
+
+    def sample_counts(self) -> np.ndarray:
+        """uint32 per local pixel: the samples the pixel has received since the last start at frame 0, finite or rejected (n +
+        rejected of its moments); synchronises."""
+        self._need_moments()
+        rec = np.zeros(self.local_pixels * ctypes.sizeof(shim.PixelMoments) // 4, np.uint32)
+        if self.local_pixels and self._moments_valid:
+            self.mom.read(rec, rec.nbytes)
+            self.dev.waitForCompletion()
+        rec = rec.reshape(self.local_pixels, -1)
+        return rec[:, 12] + rec[:, 13]   # (uint32: wraps as the record's fields do)
+
+    def render_adaptive(self, tolerance: float, *, max_samples: int, min_samples: int = 16, frames_per_pass=None,
+                        floor: float = 1e-2) -> AdaptiveResult:
+        """Render until every local pixel's own relative standard error lies at or below ``tolerance`` or the pixel has ``max_samples``
+        samples.  If fewer than ``min_samples`` frames are done, they are rendered uniformly first (``render``).  Then, pass by pass:
+        the device lists the pixels that have received fewer than ``max_samples`` samples and have fewer than ``min_samples`` finite
+        ones or b > tolerance^2 * (c + floor^2) -- b the squared standard error of the pixel's mean, c its squared mean, summed over the
+        channels as ``noise()`` sums them --, the host reads the list's length (ONE HOST WAIT PER PASS, as ``render_until`` has), and
+        ``frames_per_pass`` (default ``chunk_frames``) further frames of the listed pixels are rendered and counted.  It ends with an
+        empty list.  ``max_samples`` is tested on entry to a pass, so a pixel may end with up to ``max_samples + frames_per_pass - 1``
+        samples.  ``floor`` keeps a black pixel from never stopping.
+
+        Stopping on a variance estimated from the very samples that are averaged biases the image; the bias enters
+        only through the number of samples a pixel stops at: the pixel's value is the uniform render's after that many frames, bit
+        for bit.  Returns ``AdaptiveResult``.  Afterwards ``render`` accepts frame_begin 0 only; ``variance``, ``noise`` and
+        ``sample_counts`` work as they are, and a further ``render_adaptive`` goes on from the pixels' own counts."""
+        self._need_moments()
+        tolerance, floor = float(tolerance), float(floor)
+        min_samples, max_samples = int(min_samples), int(max_samples)
+        fpp = self.chunk_frames if frames_per_pass is None else int(frames_per_pass)
+        if not tolerance >= 0.0 or not floor >= 0.0:
+            raise ValueError("tolerance and floor must not be negative or NaN")
+        if min_samples < 0 or max_samples < 1 or fpp < 1 or max_samples + fpp > 0x7fffffff or min_samples > 0x7fffffff:
+            raise ValueError("min_samples >= 0, max_samples >= 1, frames_per_pass >= 1, and frame numbers must stay below 2^31")
+        rendered = 0
+        if not self._adaptive and self.frames_done < min_samples:
+            rendered = (min_samples - self.frames_done) * self.local_pixels
+            self.render(min_samples - self.frames_done)
+        passes = []
+        if not (self.local_pixels and self._moments_valid):
+            return AdaptiveResult((), rendered, self.sample_counts())
+        if self.pixel_list is None:
+            self.pixel_list = adl.Buffer(self.dev, self._lib.pt_adaptive_list_bytes(self.local_pixels), np.uint8)
+        rule = shim.AdaptiveRule(tolerance * tolerance, floor * floor, min_samples, max_samples)
+        rr = self._rr if self._rr is not None else shim.Roulette(65535, 1.0)   # (no roulette: a first bounce no path reaches)
+        power = self.light_choice == "power"
+        nl = len(self.lights)
+        header = np.zeros(1, np.uint32)
+        while True:
+            shim.check(self._lib.pt_adaptive_select(self.dev._h, self.mom._h, self.local_pixels, ctypes.byref(rule), self.pixel_list._h, None))
+            self.pixel_list.read(header, header.nbytes)
+            self.dev.waitForCompletion()
+            listed = int(header[0])
+            if listed == 0:
+                break
+            passes.append(listed)
+            self._adaptive = True
+            hold = min(self.samples.getSize() // (3 * listed), 0x7fffffff // listed)   # frames of this list a call may render: all of them are counted
+            done = 0
+            while done < fpp:
+                k = min(hold, fpp - done)
+                shim.check(self._lib.pt_render_indirect_pixels(
+                    self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if nl else None, int(self.mis), self.counts._h if self.mis else None,
+                    self.cdf._h if power else None, self.tri_q._h if power else None, self.samples._h, self.fb._h, self.pixel_list._h,
+                    listed, ctypes.byref(self.params(k, done)), ctypes.byref(rr), ctypes.byref(self._cam) if self._cam is not None else None, None))
+                shim.check(self._lib.pt_sample_moments_pixels(self.dev._h, self.samples._h, self.mom._h, self.pixel_list._h, listed, k, None))
+                done += k
+            rendered += listed * fpp
+        return AdaptiveResult(tuple(passes), rendered, self.sample_counts())
+
     def release(self) -> None:
-        if self.counts is not None:
-            self.counts.release()
-            self.counts = None
+        for name in ("counts", "pixel_list"):
+            if getattr(self, name) is not None:
+                getattr(self, name).release()
+                setattr(self, name, None)
         super().release()

@@ -158,6 +158,22 @@ class NoiseSummary(_c.Structure):
     _fields_ = [("var_sum", _c.c_double), ("se2_sum", _c.c_double), ("mean2_sum", _c.c_double),
                 ("pixels", _c.c_uint64), ("samples", _c.c_uint64), ("rejected", _c.c_uint64)]
 
+class AdaptiveRule(_c.Structure):
+    """pt_adaptive_rule (32 bytes): a pixel is listed while it has received fewer than max_samples samples and has fewer than
+    min_samples finite ones or a squared standard error of its mean above tol2 * (its squared mean + floor2); reserved must be 0."""
+
+    _fields_ = [("tol2", _c.c_double), ("floor2", _c.c_double), ("min_samples", _c.c_uint32), ("max_samples", _c.c_uint32),
+                ("reserved", _c.c_uint32 * 2)]
+
+
+class PixelSlot(_c.Structure):
+    """pt_pixel_slot (8 bytes): a local pixel and the number of its next frame.  A list is 16 bytes {count, reserved[3]}, then slots."""
+
+    _fields_ = [("pixel", _c.c_uint32), ("frame", _c.c_uint32)]
+
+
+PT_PIXEL_LIST_HEADER = 16
+
 # every symbol include/pt_shim.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "pt_last_error": (_c.c_char_p, []),
@@ -227,6 +243,11 @@ SIGNATURES = {
     "pt_sample_moments": (_c.c_int, [_H, _H, _H, _c.c_uint32, _c.c_int32, _c.c_int, _H]),
     "pt_moments_summary_bytes": (_c.c_size_t, [_c.c_uint32]),
     "pt_moments_resolve": (_c.c_int, [_H, _H, _c.c_uint32, _H, _H, _H]),
+    "pt_adaptive_list_bytes": (_c.c_size_t, [_c.c_uint32]),
+    "pt_adaptive_select": (_c.c_int, [_H, _H, _c.c_uint32, _c.POINTER(AdaptiveRule), _H, _H]),
+    "pt_render_indirect_pixels": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _H, _c.c_uint32, _c.POINTER(IndirectParams),
+                                             _c.POINTER(Roulette), _c.POINTER(Camera), _H]),
+    "pt_sample_moments_pixels": (_c.c_int, [_H, _H, _H, _H, _c.c_uint32, _c.c_int32, _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_bvh_snapshot": (_c.c_int, [_H, _c.POINTER(BvhInfo), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
