@@ -290,10 +290,6 @@ struct PtDirectParams {
     int32_t K;                    // light samples per hit
     int32_t nl;                   // lights in the list, 0 .. 2^24 - 1 ((float)nl is exact)
 };
-// bvh_blocks: the persistent grid of the LBVH kernel, CUs x ptk_direct_bvh_blocks_per_cu -- the kernel runs on the driver but at four waves
-// per SIMD, so ptk_query_bvh_blocks_per_cu's premise (five waves) does not hold for it
-hipError_t ptk_direct(const PtDirectParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s);
-int ptk_direct_bvh_blocks_per_cu(void);
 // indirect illumination (pt_render_indirect): direct illumination's launch with the path's depth.  samples[item] = max(L, 0) of the
 // whole path; everything else is as PtDirectParams says (the helpers of both take its PtDirectParams)
 struct PtIndirectParams {
@@ -304,12 +300,6 @@ struct PtIndirectParams {
 struct PtIndirectMisParams : PtIndirectParams {
     const int32_t* counts;        // [ntri] list entries per triangle (ptk_light_counts); not read when nl = 0
 };
-// bvh_blocks: CUs x ptk_indirect_bvh_blocks_per_cu -- the LBVH kernel's own occupancy (a path's state is larger than a direct sample's).
-// mis: pt_render_indirect_mis's estimator (the MIS = true instantiations of the same kernels); bvh_blocks is then CUs x
-// ptk_indirect_mis_bvh_blocks_per_cu
-hipError_t ptk_indirect(const PtIndirectMisParams& a, int bvh_blocks, PtSearchMode m, bool mis, hipStream_t s);
-int ptk_indirect_bvh_blocks_per_cu(void);
-int ptk_indirect_mis_bvh_blocks_per_cu(void);
 // counts[t] = the entries of lights[0 .. nl) whose index, clamped into [0, ntri), is t: one clear, one kernel of vector atomics
 hipError_t ptk_light_counts(const int32_t* lights, int nl, int ntri, int32_t* counts, hipStream_t s);
 // light choice by power (pt_render_direct_power, pt_render_indirect_power): the POWER = true instantiations take these blocks, every
@@ -323,11 +313,6 @@ struct PtIndirectPowerParams : PtIndirectMisParams {
     const uint64_t* cdf;
     const uint32_t* tri_q;
 };
-// bvh_blocks: CUs x ptk_direct_power_bvh_blocks_per_cu / ptk_indirect_power_bvh_blocks_per_cu(mis): each LBVH kernel's own figure
-hipError_t ptk_direct_power(const PtDirectPowerParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s);
-hipError_t ptk_indirect_power(const PtIndirectPowerParams& a, int bvh_blocks, PtSearchMode m, bool mis, hipStream_t s);
-int ptk_direct_power_bvh_blocks_per_cu(void);
-int ptk_indirect_power_bvh_blocks_per_cu(bool mis);
 // Russian roulette (pt_render_indirect_rr): the RR = true instantiations take this block, whichever of the four estimators they are
 // (counts, cdf and tri_q are null where the estimator does not read them); every other instantiation its block as before.  R and cap
 // are wave-uniform: they add no per-lane state
@@ -335,11 +320,6 @@ struct PtIndirectRrParams : PtIndirectPowerParams {
     int32_t R;                    // first_bounce >= 1: the roulette is played at vertex i when i + 1 >= R and i < B - 1
     float cap;                    // max_survival in (0, 1]
 };
-// One launch of the roulette kernels.  LBVH (m.bvh): pt_indirect_bvh_kernel's RR = true instantiations on the persistent grid of
-// bvh_blocks = CUs x ptk_indirect_rr_bvh_blocks_per_cu(mis, power) workgroups.  Brute force: pt_indirect_rr_kernel, one wave per
-// PT_RR_RUN (pt_constants.h) consecutive items, which refills its dead lanes from its run
-hipError_t ptk_indirect_rr(const PtIndirectRrParams& a, int bvh_blocks, PtSearchMode m, bool mis, bool power, hipStream_t s);
-int ptk_indirect_rr_bvh_blocks_per_cu(bool mis, bool power);
 // adaptive sampling (pt_render_indirect_pixels): the LIST = true instantiations of the roulette kernels take this block, every other
 // instantiation its block as before.  A launch runs over a LIST of pixels: d.npix is the number of listed pixels, item = f * d.npix + j
 // is frame f of slot j, whose local pixel is min(slots[j].x, d.t.npix_local - 1) and whose frame number is (slots[j].y + frame_off + f)
@@ -348,8 +328,24 @@ struct PtIndirectListParams : PtIndirectRrParams {
     const uint2* slots;           // [d.npix] pt_pixel_slot {pixel, frame}
     uint32_t frame_off;           // the frames every listed pixel has received from this call already
 };
-hipError_t ptk_indirect_list(const PtIndirectListParams& a, int bvh_blocks, PtSearchMode m, bool mis, bool power, hipStream_t s);
-int ptk_indirect_list_bvh_blocks_per_cu(bool mis, bool power);
+// A kind of lit render names its kernels.  The 14 valid values:
+//   direct illumination (pt_direct_kernel, pt_direct_bvh_kernel):          indirect = mis = rr = list = 0;  power 0 / 1
+//   indirect illumination (pt_indirect_kernel, pt_indirect_bvh_kernel):    indirect = 1, rr = list = 0;     mis 0 / 1 x power 0 / 1
+//   ... with Russian roulette (pt_indirect_rr_kernel, ..._bvh_kernel RR):  indirect = rr = 1, list = 0;     mis x power
+//   ... over a list of pixels (their LIST forms):                          indirect = rr = list = 1;        mis x power
+// list implies rr, rr implies indirect, mis comes only with indirect
+struct PtLitKind { bool indirect, mis, power, rr, list; };
+static inline bool ptk_lit_kind_valid(PtLitKind k) { return (!k.list || k.rr) && (!k.rr || k.indirect) && (!k.mis || k.indirect); }
+static inline int ptk_lit_kind_index(PtLitKind k) { return k.indirect | k.mis << 1 | k.power << 2 | k.rr << 3 | k.list << 4; }   // a table's index
+#define PT_LIT_KIND_INDICES 32
+// THE launch of a lit render, whatever its kind: `a` is the largest block, and each instantiation is passed its own, sliced from it
+// (PtDirectPowerParams is made of a.d, a.cdf and a.tri_q).  LBVH (m.bvh): the kind's kernel on a persistent grid of at most bvh_blocks
+// = CUs x ptk_lit_bvh_blocks_per_cu(k) workgroups -- the occupancy of the kind's OWN <true, 3> instantiation with the trace kernel's
+// LDS: the direct kernels run at four waves per SIMD, the indirect ones at three, so ptk_query_bvh_blocks_per_cu's premise (five) holds
+// for none.  Brute force: one wave per 64 items; the roulette and list kinds one wave per PT_RR_RUN (pt_constants.h) consecutive
+// items, which refills its dead lanes from its run
+hipError_t ptk_lit(const PtIndirectListParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s);
+int ptk_lit_bvh_blocks_per_cu(PtLitKind k);
 // the fold of a list launch: one lane per (slot j, channel) folds rad[f][j], f = 0 .. frame_count - 1 ascending, into fb[the slot's
 // pixel] with the slot's own frame numbers (pt_fold_frame); pixels that are not listed are neither read nor written
 struct PtFoldListParams {

@@ -3315,7 +3315,7 @@ struct PtDirectWork {
 
 // Four waves per SIMD (128 VGPRs), not the five of the driver's other kernels: a sample's state between its rays is 25 registers
 // against ambient occlusion's 16, and at five waves (96 VGPRs) the kernel spills 19 of them (profiles/direct/kernel_resources.txt).
-// Its persistent grid is therefore its own figure, ptk_direct_bvh_blocks_per_cu, not ptk_query_bvh_blocks_per_cu
+// Its persistent grid is therefore its own figure, ptk_lit_bvh_blocks_per_cu of its kind, not ptk_query_bvh_blocks_per_cu
 #define PT_DIRECT_BVH_WAVES 4
 template <bool DET_BOUNDED, int BIGQ, bool POWER = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_DIRECT_BVH_WAVES, PT_DIRECT_BVH_WAVES)))
@@ -3879,9 +3879,9 @@ struct PtIndirectWork {
 
 // Three waves per SIMD (168 VGPRs), chosen from the compiler's resource report (profiles/indirect/kernel_resources.txt): a path's
 // state between its searches is 33 registers against direct's 25, and at direct's four waves (128 VGPRs) the kernel spills 25 of
-// them to scratch; at three it uses 158-159 and spills none.  Its persistent grid is its own figure, ptk_indirect_bvh_blocks_per_cu.
+// them to scratch; at three it uses 158-159 and spills none.  Its persistent grid is its own figure, ptk_lit_bvh_blocks_per_cu of its kind.
 // The MIS instantiations use 163-164 of the 168 at the same three waves and spill none either (profiles/mis/kernel_resources.txt);
-// their grid figure is ptk_indirect_mis_bvh_blocks_per_cu (the same occupancy, asked of their own code objects)
+// their grid figure is their own kind's (the same occupancy, asked of their own code objects)
 #ifndef PT_INDIRECT_BVH_WAVES   // (tools/kernel_resources.sh -DPT_INDIRECT_BVH_WAVES=4 reads the other choice)
 #define PT_INDIRECT_BVH_WAVES 3
 #endif
@@ -4362,21 +4362,80 @@ int ptk_trace_blocks_per_cu(int ntri)
                                   : pt_blocks_per_cu(pt_trace_tiled_kernel<true>, ptk_trace_lds_bytes(ntri));
 }
 
-// ---- batched ray queries and ambient occlusion ------------------------------------------------------------------------------
+// ---- searches that take items: ray queries, ambient occlusion, the lit renders ------------------------------------------------
 // (instantiated here, after every trace kernel)
-// the instantiation of a kernel family for the scene: the packed filter (k3) needs the bounded reciprocal
-template <class Kernel> static Kernel pt_pick(bool det_bounded, bool q3, Kernel k3, Kernel k0, Kernel unbounded)
+// A kernel FAMILY names a parameter block and its two templates: bvh<DET_BOUNDED, BIGQ>() on the LBVH driver and
+// table<DET_BOUNDED, LDS_TABLE, QUADS>() over the brute-force table.  THE choice of a family's instantiation for a scene, written
+// once: the LBVH, the table in LDS or the tiled table; the packed filter (3) needs the bounded reciprocal, and the tiled table has
+// no packed form.  Eight instantiations per family, no other
+template <class F> static auto pt_choose(PtSearchMode m, int ntri) -> void (*)(const typename F::Params)
 {
-    return det_bounded ? (q3 ? k3 : k0) : unbounded;
+    const bool q3 = m.quads == 3;
+    if (m.bvh) return m.det_bounded ? (q3 ? F::template bvh<true, 3>() : F::template bvh<true, 0>()) : F::template bvh<false, 0>();
+    if (ntri <= PT_LDS_TRI_MAX) return m.det_bounded ? (q3 ? F::template table<true, 1, 3>() : F::template table<true, 1, 0>()) : F::template table<false, 1, 0>();
+    return m.det_bounded ? F::template table<true, 2, 0>() : F::template table<false, 2, 0>();
 }
 
-// One launch of a kernel whose waves take 64 items each over a scene of ntri triangles -- LBVH: a persistent grid of at most bvh_blocks workgroups (what the chip
-// holds) with the trace kernel's LDS; brute force: one wave per 64 items, the table kernels' LDS without the pools
-template <class Params>
-static hipError_t pt_launch_search(void (*kernel)(const Params), const Params& p, int ntri, unsigned nitems, bool bvh, int bvh_blocks, hipStream_t s)
+template <bool ANY> struct PtQueryFamily {   // ANY: the any-hit search through the LBVH; the table search is the closest one
+    using Params = PtQueryParams;
+    template <bool DB, int BIGQ> static constexpr auto bvh() { return pt_query_bvh_kernel<DB, BIGQ, ANY>; }
+    template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table() { return pt_query_kernel<DB, LDS_TABLE, QUADS>; }
+};
+struct PtAoFamily {
+    using Params = PtAoParams;
+    template <bool DB, int BIGQ> static constexpr auto bvh() { return pt_ao_bvh_kernel<DB, BIGQ>; }
+    template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table() { return pt_ao_kernel<DB, LDS_TABLE, QUADS>; }
+};
+// a kind of lit render (PtLitKind); RR: the table kernels are the refilling ones, a wave of which owns PT_RR_RUN items
+template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST> struct PtLitFamily {
+    using Params = std::conditional_t<INDIRECT, PtIndirectArgs<MIS, POWER, RR, LIST>, PtDirectArgs<POWER>>;
+    static constexpr unsigned run = RR ? PT_RR_RUN : 64;
+    template <bool DB, int BIGQ> static constexpr auto bvh()
+    {
+        if constexpr (INDIRECT) return pt_indirect_bvh_kernel<DB, BIGQ, MIS, POWER, RR, LIST>;
+        else return pt_direct_bvh_kernel<DB, BIGQ, POWER>;
+    }
+    template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table()
+    {
+        if constexpr (RR) return pt_indirect_rr_kernel<DB, LDS_TABLE, QUADS, MIS, POWER, LIST>;
+        else if constexpr (INDIRECT) return pt_indirect_kernel<DB, LDS_TABLE, QUADS, MIS, POWER>;
+        else return pt_direct_kernel<DB, LDS_TABLE, QUADS, POWER>;
+    }
+    // the instantiations' own block, sliced from the largest (every indirect block is a base of it; direct by power: direct's and the table)
+    static Params params(const PtIndirectListParams& a)
+    {
+        if constexpr (INDIRECT) return a;
+        else if constexpr (!POWER) return a.d;
+        else {
+            PtDirectPowerParams p;
+            __builtin_memset(&p, 0, sizeof p);
+            static_cast<PtDirectParams&>(p) = a.d;
+            p.cdf = a.cdf;
+            p.tri_q = a.tri_q;
+            return p;
+        }
+    }
+};
+// fn(the family of kind k): the 14 valid kinds and no other -- direct illumination has neither MIS nor roulette, a list is played with roulette
+template <class Fn> static auto pt_lit_family(PtLitKind k, Fn fn)
 {
-    const unsigned wg_waves = PT_TRACE_THREADS / 64;
-    unsigned blocks = ((nitems + 63u) / 64u + wg_waves - 1u) / wg_waves;
+    auto estimator = [&](auto mis, auto power) {
+        constexpr bool M = decltype(mis)::value, P = decltype(power)::value;
+        if constexpr (!M) if (!k.indirect) return fn(PtLitFamily<false, false, P, false, false>());
+        return k.list ? fn(PtLitFamily<true, M, P, true, true>()) : k.rr ? fn(PtLitFamily<true, M, P, true, false>()) : fn(PtLitFamily<true, M, P, false, false>());
+    };
+    const std::true_type yes;
+    const std::false_type no;
+    return k.mis ? (k.power ? estimator(yes, yes) : estimator(yes, no)) : (k.power ? estimator(no, yes) : estimator(no, no));
+}
+
+// One launch of a kernel over nitems items of a scene of ntri triangles -- LBVH: a persistent grid of at most bvh_blocks workgroups (what the chip
+// holds), its waves take 64 items at a time, with the trace kernel's LDS; brute force: one wave per `run` items, the table kernels' LDS without the pools
+template <class Params>
+static hipError_t pt_launch_search(void (*kernel)(const Params), const Params& p, int ntri, unsigned nitems, unsigned run, bool bvh, int bvh_blocks, hipStream_t s)
+{
+    const unsigned wg_waves = PT_TRACE_THREADS / 64, per_wave = bvh ? 64u : run;
+    unsigned blocks = ((nitems + per_wave - 1u) / per_wave + wg_waves - 1u) / wg_waves;
     if (bvh && bvh_blocks > 0 && blocks > (unsigned)bvh_blocks) blocks = (unsigned)bvh_blocks;
     const size_t lds = bvh ? ptk_trace_bvh_lds_bytes()
                            : (size_t)(ntri <= PT_LDS_TRI_MAX ? pt_lds_total<1, false>(ntri) : pt_lds_total<2, false>(ntri)) * sizeof(float);
@@ -4387,124 +4446,29 @@ static hipError_t pt_launch_search(void (*kernel)(const Params), const Params& p
 hipError_t ptk_query(const PtQueryParams& q, int bvh_blocks, PtSearchMode m, bool any, hipStream_t s)
 {
     if (q.nrays == 0) return hipSuccess;
-    const bool q3 = m.quads == 3;
-    void (*kernel)(const PtQueryParams);
-    if (m.bvh && any) kernel = pt_pick(m.det_bounded, q3, pt_query_bvh_kernel<true, 3, true>, pt_query_bvh_kernel<true, 0, true>, pt_query_bvh_kernel<false, 0, true>);
-    else if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_query_bvh_kernel<true, 3, false>, pt_query_bvh_kernel<true, 0, false>, pt_query_bvh_kernel<false, 0, false>);
-    else if (q.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_query_kernel<true, 1, 3>, pt_query_kernel<true, 1, 0>, pt_query_kernel<false, 1, 0>);
-    else kernel = m.det_bounded ? pt_query_kernel<true, 2, 0> : pt_query_kernel<false, 2, 0>;
-    return pt_launch_search(kernel, q, q.t.ntri, q.nrays, m.bvh, bvh_blocks, s);
+    const auto kernel = any ? pt_choose<PtQueryFamily<true>>(m, q.t.ntri) : pt_choose<PtQueryFamily<false>>(m, q.t.ntri);
+    return pt_launch_search(kernel, q, q.t.ntri, q.nrays, 64u, m.bvh, bvh_blocks, s);
 }
 
 hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
 {
     if (a.nitems == 0) return hipSuccess;
-    const bool q3 = m.quads == 3;
-    void (*kernel)(const PtAoParams);
-    if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_ao_bvh_kernel<true, 3>, pt_ao_bvh_kernel<true, 0>, pt_ao_bvh_kernel<false, 0>);
-    else if (a.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_ao_kernel<true, 1, 3>, pt_ao_kernel<true, 1, 0>, pt_ao_kernel<false, 1, 0>);
-    else kernel = m.det_bounded ? pt_ao_kernel<true, 2, 0> : pt_ao_kernel<false, 2, 0>;
-    return pt_launch_search(kernel, a, a.t.ntri, a.nitems, m.bvh, bvh_blocks, s);
+    return pt_launch_search(pt_choose<PtAoFamily>(m, a.t.ntri), a, a.t.ntri, a.nitems, 64u, m.bvh, bvh_blocks, s);
 }
 
-hipError_t ptk_direct(const PtDirectParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
-{
-    if (a.nitems == 0) return hipSuccess;
-    const bool q3 = m.quads == 3;
-    void (*kernel)(const PtDirectParams);
-    if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_direct_bvh_kernel<true, 3>, pt_direct_bvh_kernel<true, 0>, pt_direct_bvh_kernel<false, 0>);
-    else if (a.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_direct_kernel<true, 1, 3>, pt_direct_kernel<true, 1, 0>, pt_direct_kernel<false, 1, 0>);
-    else kernel = m.det_bounded ? pt_direct_kernel<true, 2, 0> : pt_direct_kernel<false, 2, 0>;
-    return pt_launch_search(kernel, a, a.t.ntri, a.nitems, m.bvh, bvh_blocks, s);
-}
-
-int ptk_direct_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_direct_bvh_kernel<true, 3>, ptk_trace_bvh_lds_bytes()); }
-
-hipError_t ptk_direct_power(const PtDirectPowerParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
-{
-    if (a.nitems == 0) return hipSuccess;
-    const bool q3 = m.quads == 3;
-    void (*kernel)(const PtDirectPowerParams);
-    if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_direct_bvh_kernel<true, 3, true>, pt_direct_bvh_kernel<true, 0, true>, pt_direct_bvh_kernel<false, 0, true>);
-    else if (a.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_direct_kernel<true, 1, 3, true>, pt_direct_kernel<true, 1, 0, true>, pt_direct_kernel<false, 1, 0, true>);
-    else kernel = m.det_bounded ? pt_direct_kernel<true, 2, 0, true> : pt_direct_kernel<false, 2, 0, true>;
-    return pt_launch_search(kernel, a, a.t.ntri, a.nitems, m.bvh, bvh_blocks, s);
-}
-
-int ptk_direct_power_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_direct_bvh_kernel<true, 3, true>, ptk_trace_bvh_lds_bytes()); }
-
-hipError_t ptk_indirect_power(const PtIndirectPowerParams& a, int bvh_blocks, PtSearchMode m, bool mis, hipStream_t s)
+hipError_t ptk_lit(const PtIndirectListParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s)
 {
     if (a.d.nitems == 0) return hipSuccess;
-    const bool q3 = m.quads == 3;
-    void (*kernel)(const PtIndirectPowerParams);
-    if (mis) {
-        if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3, true, true>, pt_indirect_bvh_kernel<true, 0, true, true>, pt_indirect_bvh_kernel<false, 0, true, true>);
-        else if (a.d.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_kernel<true, 1, 3, true, true>, pt_indirect_kernel<true, 1, 0, true, true>, pt_indirect_kernel<false, 1, 0, true, true>);
-        else kernel = m.det_bounded ? pt_indirect_kernel<true, 2, 0, true, true> : pt_indirect_kernel<false, 2, 0, true, true>;
-    } else {
-        if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3, false, true>, pt_indirect_bvh_kernel<true, 0, false, true>, pt_indirect_bvh_kernel<false, 0, false, true>);
-        else if (a.d.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_kernel<true, 1, 3, false, true>, pt_indirect_kernel<true, 1, 0, false, true>, pt_indirect_kernel<false, 1, 0, false, true>);
-        else kernel = m.det_bounded ? pt_indirect_kernel<true, 2, 0, false, true> : pt_indirect_kernel<false, 2, 0, false, true>;
-    }
-    return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, m.bvh, bvh_blocks, s);
+    return pt_lit_family(k, [&](auto f) {
+        using F = decltype(f);
+        const typename F::Params p = F::params(a);
+        return pt_launch_search(pt_choose<F>(m, a.d.t.ntri), p, a.d.t.ntri, a.d.nitems, F::run, m.bvh, bvh_blocks, s);
+    });
 }
 
-// the roulette kernels of one (MIS, POWER) estimator: pt_pick's shape, as ptk_indirect_power has it.  LIST: their list forms
-template <bool MIS, bool POWER, bool LIST = false>
-static hipError_t pt_launch_indirect_rr(const PtIndirectArgs<MIS, POWER, true, LIST>& a, int bvh_blocks, PtSearchMode m, hipStream_t s)
+int ptk_lit_bvh_blocks_per_cu(PtLitKind k)
 {
-    const bool q3 = m.quads == 3;
-    void (*kernel)(const PtIndirectArgs<MIS, POWER, true, LIST>);
-    if (m.bvh) {
-        kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3, MIS, POWER, true, LIST>, pt_indirect_bvh_kernel<true, 0, MIS, POWER, true, LIST>,
-                         pt_indirect_bvh_kernel<false, 0, MIS, POWER, true, LIST>);
-        return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, true, bvh_blocks, s);
-    }
-    const int ntri = a.d.t.ntri;
-    if (ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_rr_kernel<true, 1, 3, MIS, POWER, LIST>, pt_indirect_rr_kernel<true, 1, 0, MIS, POWER, LIST>,
-                                                 pt_indirect_rr_kernel<false, 1, 0, MIS, POWER, LIST>);
-    else kernel = m.det_bounded ? pt_indirect_rr_kernel<true, 2, 0, MIS, POWER, LIST> : pt_indirect_rr_kernel<false, 2, 0, MIS, POWER, LIST>;
-    // one wave per run of PT_RR_RUN items, the table kernels' LDS without the pools (pt_launch_search's brute-force form)
-    const unsigned wg_waves = PT_TRACE_THREADS / 64;
-    const unsigned waves = (a.d.nitems + (unsigned)PT_RR_RUN - 1u) / (unsigned)PT_RR_RUN;
-    const size_t lds = (size_t)(ntri <= PT_LDS_TRI_MAX ? pt_lds_total<1, false>(ntri) : pt_lds_total<2, false>(ntri)) * sizeof(float);
-    hipLaunchKernelGGL(kernel, dim3((waves + wg_waves - 1u) / wg_waves), dim3(PT_TRACE_THREADS), lds, s, a);
-    return hipGetLastError();
-}
-
-hipError_t ptk_indirect_rr(const PtIndirectRrParams& a, int bvh_blocks, PtSearchMode m, bool mis, bool power, hipStream_t s)
-{
-    if (a.d.nitems == 0) return hipSuccess;
-    if (power) return mis ? pt_launch_indirect_rr<true, true>(a, bvh_blocks, m, s) : pt_launch_indirect_rr<false, true>(a, bvh_blocks, m, s);
-    return mis ? pt_launch_indirect_rr<true, false>(a, bvh_blocks, m, s) : pt_launch_indirect_rr<false, false>(a, bvh_blocks, m, s);
-}
-
-int ptk_indirect_rr_bvh_blocks_per_cu(bool mis, bool power)
-{
-    const size_t lds = ptk_trace_bvh_lds_bytes();
-    if (power) return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, true, true>, lds) : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, true, true>, lds);
-    return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, false, true>, lds) : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, false, true>, lds);
-}
-
-hipError_t ptk_indirect_list(const PtIndirectListParams& a, int bvh_blocks, PtSearchMode m, bool mis, bool power, hipStream_t s)
-{
-    if (a.d.nitems == 0) return hipSuccess;
-    if (power) return mis ? pt_launch_indirect_rr<true, true, true>(a, bvh_blocks, m, s) : pt_launch_indirect_rr<false, true, true>(a, bvh_blocks, m, s);
-    return mis ? pt_launch_indirect_rr<true, false, true>(a, bvh_blocks, m, s) : pt_launch_indirect_rr<false, false, true>(a, bvh_blocks, m, s);
-}
-
-int ptk_indirect_list_bvh_blocks_per_cu(bool mis, bool power)
-{
-    const size_t lds = ptk_trace_bvh_lds_bytes();
-    if (power) return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, true, true, true>, lds) : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, true, true, true>, lds);
-    return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, false, true, true>, lds) : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, false, true, true>, lds);
-}
-
-int ptk_indirect_power_bvh_blocks_per_cu(bool mis)
-{
-    return mis ? pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true, true>, ptk_trace_bvh_lds_bytes())
-               : pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, false, true>, ptk_trace_bvh_lds_bytes());
+    return pt_lit_family(k, [](auto f) { return pt_blocks_per_cu(decltype(f)::template bvh<true, 3>(), ptk_trace_bvh_lds_bytes()); });
 }
 
 hipError_t ptk_light_table(const PtRawTriangle* tris, int ntri, const PtRawMaterial* mats, int nmat, const int32_t* lights, int nl,
@@ -4524,24 +4488,6 @@ hipError_t ptk_light_table(const PtRawTriangle* tris, int ntri, const PtRawMater
     hipLaunchKernelGGL(pt_light_tiles_kernel, dim3(1), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, tile_sums, ntiles, cdf);
     hipLaunchKernelGGL(pt_light_scan_kernel, dim3(ntiles), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, cdf, nl, tile_sums);
     return hipGetLastError();
-}
-
-hipError_t ptk_indirect(const PtIndirectMisParams& a, int bvh_blocks, PtSearchMode m, bool mis, hipStream_t s)
-{
-    if (a.d.nitems == 0) return hipSuccess;
-    const bool q3 = m.quads == 3;
-    if (mis) {
-        void (*kernel)(const PtIndirectMisParams);
-        if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3, true>, pt_indirect_bvh_kernel<true, 0, true>, pt_indirect_bvh_kernel<false, 0, true>);
-        else if (a.d.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_kernel<true, 1, 3, true>, pt_indirect_kernel<true, 1, 0, true>, pt_indirect_kernel<false, 1, 0, true>);
-        else kernel = m.det_bounded ? pt_indirect_kernel<true, 2, 0, true> : pt_indirect_kernel<false, 2, 0, true>;
-        return pt_launch_search(kernel, a, a.d.t.ntri, a.d.nitems, m.bvh, bvh_blocks, s);
-    }
-    void (*kernel)(const PtIndirectParams);
-    if (m.bvh) kernel = pt_pick(m.det_bounded, q3, pt_indirect_bvh_kernel<true, 3>, pt_indirect_bvh_kernel<true, 0>, pt_indirect_bvh_kernel<false, 0>);
-    else if (a.d.t.ntri <= PT_LDS_TRI_MAX) kernel = pt_pick(m.det_bounded, q3, pt_indirect_kernel<true, 1, 3>, pt_indirect_kernel<true, 1, 0>, pt_indirect_kernel<false, 1, 0>);
-    else kernel = m.det_bounded ? pt_indirect_kernel<true, 2, 0> : pt_indirect_kernel<false, 2, 0>;
-    return pt_launch_search(kernel, static_cast<const PtIndirectParams&>(a), a.d.t.ntri, a.d.nitems, m.bvh, bvh_blocks, s);
 }
 
 hipError_t ptk_light_counts(const int32_t* lights, int nl, int ntri, int32_t* counts, hipStream_t s)
@@ -4580,9 +4526,6 @@ hipError_t ptk_moments_resolve(const PtPixelMoments* moments, uint32_t npix, voi
     }
     return e;
 }
-
-int ptk_indirect_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3>, ptk_trace_bvh_lds_bytes()); }
-int ptk_indirect_mis_bvh_blocks_per_cu(void) { return pt_blocks_per_cu(pt_indirect_bvh_kernel<true, 3, true>, ptk_trace_bvh_lds_bytes()); }
 
 hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s)
 {

@@ -136,12 +136,7 @@ struct pt_device_s {
     uint64_t bvh_builds;        // LBVH builds so far (PT_OPT_BVH_BUILD_COUNT)
     int bvh_blocks_per_cu;
     int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query and ambient-occlusion kernels (pt_bvh_drive)
-    int direct_bvh_blocks_per_cu;  // ... and of the direct-illumination kernel, which runs at four waves per SIMD
-    int indirect_bvh_blocks_per_cu;   // ... and of the indirect-illumination kernel, at its own occupancy
-    int indirect_mis_bvh_blocks_per_cu;   // ... and of its MIS instantiation
-    int direct_power_bvh_blocks_per_cu, indirect_power_bvh_blocks_per_cu, indirect_power_mis_bvh_blocks_per_cu;   // ... and of the POWER ones
-    int indirect_rr_bvh_blocks_per_cu[2][2];   // ... and of the roulette ones, [mis][power]
-    int indirect_list_bvh_blocks_per_cu[2][2]; // ... and of their list forms (pt_render_indirect_pixels)
+    int lit_bvh_blocks_per_cu[PT_LIT_KIND_INDICES];   // ... and of the lit renders' LBVH kernels, each kind its own (ptk_lit_kind_index)
     unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
     unsigned int* trav_dev;  // ... as the device addresses it
     // ---- fused-render workspace: the STREAMING renderer (render_part, plan_chunks, the ring).  A render walks its frames in chunks of
@@ -362,17 +357,10 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->blocks_per_cu = ptk_trace_blocks_per_cu(36);
     d->bvh_blocks_per_cu = ptk_trace_bvh_blocks_per_cu();
     d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
-    d->direct_bvh_blocks_per_cu = ptk_direct_bvh_blocks_per_cu();
-    d->indirect_bvh_blocks_per_cu = ptk_indirect_bvh_blocks_per_cu();
-    d->indirect_mis_bvh_blocks_per_cu = ptk_indirect_mis_bvh_blocks_per_cu();
-    d->direct_power_bvh_blocks_per_cu = ptk_direct_power_bvh_blocks_per_cu();
-    d->indirect_power_bvh_blocks_per_cu = ptk_indirect_power_bvh_blocks_per_cu(false);
-    d->indirect_power_mis_bvh_blocks_per_cu = ptk_indirect_power_bvh_blocks_per_cu(true);
-    for (int mis = 0; mis < 2; ++mis)
-        for (int power = 0; power < 2; ++power) {
-            d->indirect_rr_bvh_blocks_per_cu[mis][power] = ptk_indirect_rr_bvh_blocks_per_cu(mis != 0, power != 0);
-            d->indirect_list_bvh_blocks_per_cu[mis][power] = ptk_indirect_list_bvh_blocks_per_cu(mis != 0, power != 0);
-        }
+    for (int i = 0; i < PT_LIT_KIND_INDICES; ++i) {
+        const PtLitKind k = { (i & 1) != 0, (i & 2) != 0, (i & 4) != 0, (i & 8) != 0, (i & 16) != 0 };
+        if (ptk_lit_kind_valid(k)) d->lit_bvh_blocks_per_cu[ptk_lit_kind_index(k)] = ptk_lit_bvh_blocks_per_cu(k);
+    }
     *out = d;
     return PT_OK;
 }
@@ -753,6 +741,8 @@ static int check_triangles(const pt_buffer_s* tris, int n)
         return fail(PT_ERR_RANGE, "triangle buffer holds %zu bytes, %d triangles need %zu", tris->bytes, n, (size_t)n * sizeof(PtRawTriangle));
     return PT_OK;
 }
+
+#include "pt_span.h"   // PtSpan and ranges_overlap, span_fits, span_aligned, spans_apart: the buffer checks of the entry points
 
 static int event_begin(pt_device_s* d, pt_event_s* ev)
 {
@@ -1670,12 +1660,6 @@ extern "C" int pt_render_frames(pt_device_t d, pt_buffer_t triangles, pt_buffer_
 // LBVH and filter tables (prepare_search): a triangle buffer the renders use is neither prepared again nor rebuilt.
 static_assert(sizeof(pt_ray) == 32 && sizeof(pt_hit) == 48, "query record layout");
 
-static bool ranges_overlap(const pt_buffer_s* a, size_t abytes, const pt_buffer_s* b, size_t bbytes)
-{
-    const uintptr_t a0 = (uintptr_t)a->dptr, b0 = (uintptr_t)b->dptr;
-    return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 // pt_intersect_rays and pt_occluded_rays: the argument checks, the deferred error, the stream, the scene, the launch.
 // occluded: 1 / 0 results (int32) instead of pt_hit records; early_exit: (occluded only) through the LBVH the search is the any-hit
 // one, which stops at the first accepted triangle -- brute force keeps the two-pass closest search (a few dozen triangles leave
@@ -1755,13 +1739,10 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
     if (((long long)a.frame_begin + a.frame_count) * a.rays_per_sample > 0xffffffffLL)
         return fail(PT_ERR_RANGE, "(frame_begin + frame_count) x rays_per_sample exceeds 2^32 - 1: the counts could wrap");
     const uint32_t npix = (uint32_t)npix64;
-    const size_t count_bytes = (size_t)npix * 8, image_bytes = (size_t)npix * sizeof(float4);
-    if ((rc = check_triangles(triangles, a.num_triangles))) return rc;
-    if (count_bytes > counts->bytes) return fail(PT_ERR_RANGE, "count buffer holds %zu bytes, %u pixels need %zu", counts->bytes, npix, count_bytes);
-    if (image && image_bytes > image->bytes) return fail(PT_ERR_RANGE, "image buffer holds %zu bytes, %u pixels need %zu", image->bytes, npix, image_bytes);
-    if ((uintptr_t)counts->dptr & 7u) return fail(PT_ERR_INVALID, "the count buffer must be 8-byte aligned");
-    if (image && ((uintptr_t)image->dptr & 15u)) return fail(PT_ERR_INVALID, "the image buffer must be 16-byte aligned");
-    if (image && ranges_overlap(counts, count_bytes, image, image_bytes)) return fail(PT_ERR_INVALID, "the counts and the image overlap");
+    const size_t count_bytes = (size_t)npix * 8;
+    const PtSpan C = { counts, count_bytes, 8, "the count buffer" }, G = { image, (size_t)npix * sizeof(float4), 16, "the image buffer" };
+    if ((rc = check_triangles(triangles, a.num_triangles)) || (rc = span_fits(C)) || (rc = span_fits(G))) return rc;
+    if ((rc = span_aligned(C)) || (rc = span_aligned(G)) || (rc = spans_apart({ C, G }))) return rc;
     // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
     if ((rc = check_traversal(d))) return rc;
     if ((rc = enter_stream(d))) return rc;
@@ -1802,29 +1783,50 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
 static_assert(sizeof(pt_direct_params) == 64, "pt_direct_params layout");
 static_assert(sizeof(pt_indirect_params) == 64, "pt_indirect_params layout");
 
-// pt_render_direct, pt_render_indirect, pt_render_indirect_mis and the two _power entry points: one validation, one chunk loop.
-// `a`: the fields the parameter blocks share (each entry point has looked at its own reserved ones).  max_bounces: 0 = direct
-// illumination (its own kernels), otherwise the depth of an indirect render.  mis: the MIS estimator, which reads light_counts (NULL
-// otherwise).  table: NULL = the uniform choice, otherwise {cdf, tri_q} of pt_light_table, the choice by power.  what: the message
-// for a field out of range.  rr: NULL, or the roulette of pt_render_indirect_rr (checked by it; max_bounces > 0): the launch is ptk_indirect_rr
-// pixels: NULL, or the list of pt_render_indirect_pixels (rr given): frame_count frames of each listed pixel, the launch is
-// ptk_indirect_list and the fold ptk_fold_list; the workspace is laid out for num_listed pixels
-struct PtPixelList { pt_buffer_t list; uint32_t num_listed; };
-static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts, bool mis,
-                      pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params& a, int max_bounces, const char* what,
-                      const pt_camera* cam, pt_event_t ev, const pt_buffer_t* table = nullptr, const pt_roulette* rr = nullptr,
-                      const PtPixelList* pixels = nullptr)
+static_assert(sizeof(pt_roulette) == 16, "pt_roulette layout");
+static_assert(sizeof(pt_adaptive_rule) == 32 && sizeof(pt_pixel_slot) == 8 && sizeof(pt_pixel_slot) == sizeof(uint2), "adaptive record layout");
+
+// ONE lit call, as its entry point describes it: pt_render_direct, pt_render_indirect, pt_render_indirect_mis, the two _power entry
+// points, pt_render_indirect_rr and pt_render_indirect_pixels each fill one and hand it to render_lit -- one validation, one chunk loop
+struct PtLitCall {
+    PtLitKind kind;             // which kernels (pt_kernels.h); what follows is read as far as the kind says
+    pt_buffer_t triangles, materials, lights, samples, framebuffer;
+    pt_buffer_t light_counts;   // kind.mis: the list entries per triangle (pt_light_counts)
+    pt_buffer_t cdf, tri_q;     // kind.power: the selection table (pt_light_table)
+    pt_buffer_t list;           // kind.list: the pixel list; frame_count frames of each of its num_listed slots are rendered, the
+    uint32_t num_listed;        //   workspace is laid out for num_listed pixels and the fold is ptk_fold_list
+    pt_direct_params a;         // the fields the parameter blocks share (each entry point has looked at its own reserved ones)
+    int max_bounces;            // kind.indirect: the depth of the paths
+    pt_roulette rr;             // kind.rr: the roulette (roulette_args has checked it)
+    const pt_camera* cam;
+    pt_event_t ev;
+    const char* what;           // the message for a field out of range
+};
+
+static PtLitCall lit_call(PtLitKind kind, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
+                          pt_buffer_t framebuffer, const pt_camera* cam, pt_event_t ev)
 {
-    pt_buffer_t list = pixels ? pixels->list : nullptr;
-    const bool power = table != nullptr;
-    pt_buffer_t cdf = power ? table[0] : nullptr, tri_q = power ? table[1] : nullptr;
+    PtLitCall c = {};
+    c.kind = kind;
+    c.triangles = triangles; c.materials = materials; c.lights = lights; c.samples = samples; c.framebuffer = framebuffer;
+    c.cam = cam; c.ev = ev;
+    c.what = kind.indirect ? "invalid indirect-illumination parameters" : "invalid direct-illumination parameters";
+    return c;
+}
+
+static int render_lit(pt_device_t d, const PtLitCall& c)
+{
+    const pt_direct_params& a = c.a;
+    const bool mis = c.kind.mis, power = c.kind.power;
+    const pt_buffer_t triangles = c.triangles, materials = c.materials, lights = c.lights, light_counts = c.light_counts, cdf = c.cdf,
+                      tri_q = c.tri_q, samples = c.samples, framebuffer = c.framebuffer, list = c.list;
     int rc;
-    PtCamera c = reference_camera();
-    if (cam && (rc = camera_derive(cam, &c))) return rc;
-    if (!triangles || !materials || !samples || !framebuffer || (pixels && !list)) return fail(PT_ERR_INVALID, "null buffer handle");
-    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer, cdf, tri_q, list })) || (rc = check_event(d, ev))) return rc;
+    PtCamera cam = reference_camera();
+    if (c.cam && (rc = camera_derive(c.cam, &cam))) return rc;
+    if (!triangles || !materials || !samples || !framebuffer || (c.kind.list && !list)) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer, cdf, tri_q, list })) || (rc = check_event(d, c.ev))) return rc;
     if (a.num_triangles < 0 || a.num_materials < 1 || a.num_lights < 0 || a.light_samples < 1 || a.light_samples > 256)
-        return fail(PT_ERR_INVALID, "%s", what);
+        return fail(PT_ERR_INVALID, "%s", c.what);
     if (a.num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
     if (a.num_lights > 0 && !lights) return fail(PT_ERR_INVALID, "num_lights > 0 needs a light list");
     if (mis && a.num_lights > 0 && !light_counts) return fail(PT_ERR_INVALID, "num_lights > 0 needs the light counts (pt_light_counts)");
@@ -1833,87 +1835,58 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     if ((uint64_t)a.num_triangles * 64u > 0xffffffffull || (uint64_t)a.num_materials * 64u > 0xffffffffull)
         return fail(PT_ERR_INVALID, "a scene has fewer than 2^26 triangles and 2^26 materials");
     uint64_t npix64;
-    if ((rc = check_image(what, a.width, a.height, a.frame_begin, a.frame_count, a.stripe_rows, a.n_ranks, a.rank, npix64)))
+    if ((rc = check_image(c.what, a.width, a.height, a.frame_begin, a.frame_count, a.stripe_rows, a.n_ranks, a.rank, npix64)))
         return rc;
     const uint32_t npix = (uint32_t)npix64;
-    if (pixels && pixels->num_listed > npix) return fail(PT_ERR_INVALID, "%u pixels listed, the local image has %u", pixels->num_listed, npix);
-    const uint32_t wpix = pixels ? pixels->num_listed : npix;   // the pixels of one frame of the workspace
-    const size_t frame_bytes = (size_t)wpix * 12, fb_bytes = (size_t)npix * sizeof(float4), light_bytes = (size_t)a.num_lights * sizeof(int32_t);
-    if ((rc = check_triangles(triangles, a.num_triangles))) return rc;
-    if ((size_t)a.num_materials * sizeof(PtRawMaterial) > materials->bytes)
-        return fail(PT_ERR_RANGE, "material buffer holds %zu bytes, %d materials need %zu", materials->bytes, a.num_materials,
-                    (size_t)a.num_materials * sizeof(PtRawMaterial));
-    if (lights && light_bytes > lights->bytes) return fail(PT_ERR_RANGE, "light list holds %zu bytes, %d lights need %zu", lights->bytes, a.num_lights, light_bytes);
-    if (frame_bytes > samples->bytes) return fail(PT_ERR_RANGE, "sample workspace holds %zu bytes, one frame of %u pixels needs %zu", samples->bytes, wpix, frame_bytes);
-    if (fb_bytes > framebuffer->bytes) return fail(PT_ERR_RANGE, "framebuffer holds %zu bytes, %u pixels need %zu", framebuffer->bytes, npix, fb_bytes);
-    if ((uintptr_t)samples->dptr & 3u) return fail(PT_ERR_INVALID, "the sample workspace must be 4-byte aligned");
-    if ((uintptr_t)framebuffer->dptr & 15u) return fail(PT_ERR_INVALID, "the framebuffer must be 16-byte aligned");
-    if (lights && a.num_lights > 0 && ((uintptr_t)lights->dptr & 3u)) return fail(PT_ERR_INVALID, "the light list must be 4-byte aligned");
-    if (ranges_overlap(samples, samples->bytes, framebuffer, fb_bytes)) return fail(PT_ERR_INVALID, "the sample workspace and the framebuffer overlap");
-    if (lights && (ranges_overlap(lights, light_bytes, samples, samples->bytes) || ranges_overlap(lights, light_bytes, framebuffer, fb_bytes)))
-        return fail(PT_ERR_INVALID, "the light list overlaps the sample workspace or the framebuffer");
-    if (mis && a.num_lights > 0) {   // (with no lights the counts are not read)
-        const size_t count_bytes = (size_t)a.num_triangles * sizeof(int32_t);
-        if (count_bytes > light_counts->bytes)
-            return fail(PT_ERR_RANGE, "light counts hold %zu bytes, %d triangles need %zu", light_counts->bytes, a.num_triangles, count_bytes);
-        if ((uintptr_t)light_counts->dptr & 3u) return fail(PT_ERR_INVALID, "the light counts must be 4-byte aligned");
-        if (ranges_overlap(light_counts, count_bytes, samples, samples->bytes) || ranges_overlap(light_counts, count_bytes, framebuffer, fb_bytes) ||
-            ranges_overlap(light_counts, count_bytes, lights, light_bytes))
-            return fail(PT_ERR_INVALID, "the light counts overlap the sample workspace, the framebuffer or the light list");
-    }
-    if (power && a.num_lights > 0) {   // (with no lights the table is not read)
-        const size_t cdf_bytes = ((size_t)a.num_lights + 1) * sizeof(uint64_t), q_bytes = (size_t)a.num_triangles * sizeof(uint32_t);
-        if (cdf_bytes > cdf->bytes) return fail(PT_ERR_RANGE, "the light table's cdf holds %zu bytes, %d lights need %zu", cdf->bytes, a.num_lights, cdf_bytes);
-        if (q_bytes > tri_q->bytes) return fail(PT_ERR_RANGE, "the light table's tri_q holds %zu bytes, %d triangles need %zu", tri_q->bytes, a.num_triangles, q_bytes);
-        if ((uintptr_t)cdf->dptr & 7u) return fail(PT_ERR_INVALID, "the light table's cdf must be 8-byte aligned");
-        if (q_bytes && ((uintptr_t)tri_q->dptr & 3u)) return fail(PT_ERR_INVALID, "the light table's tri_q must be 4-byte aligned");
-        const pt_buffer_s* others[] = { samples, framebuffer, lights, mis ? light_counts : nullptr };
-        const size_t other_bytes[] = { samples->bytes, fb_bytes, light_bytes, (size_t)a.num_triangles * sizeof(int32_t) };
-        for (int i = 0; i < 4; ++i)
-            if (others[i] && (ranges_overlap(cdf, cdf_bytes, others[i], other_bytes[i]) || ranges_overlap(tri_q, q_bytes, others[i], other_bytes[i])))
-                return fail(PT_ERR_INVALID, "the light table overlaps the sample workspace, the framebuffer, the light list or the light counts");
-        if (ranges_overlap(cdf, cdf_bytes, tri_q, q_bytes)) return fail(PT_ERR_INVALID, "the light table's cdf and tri_q overlap");
-    }
-    if (pixels) {
-        const size_t list_bytes = 16 + (size_t)pixels->num_listed * sizeof(pt_pixel_slot);
-        if (list_bytes > list->bytes) return fail(PT_ERR_RANGE, "the pixel list holds %zu bytes, %u slots need %zu", list->bytes, pixels->num_listed, list_bytes);
-        if ((uintptr_t)list->dptr & 7u) return fail(PT_ERR_INVALID, "the pixel list must be 8-byte aligned");
-        if (ranges_overlap(list, list_bytes, samples, samples->bytes) || ranges_overlap(list, list_bytes, framebuffer, fb_bytes))
-            return fail(PT_ERR_INVALID, "the pixel list overlaps the sample workspace or the framebuffer");
-    }
+    if (c.kind.list && c.num_listed > npix) return fail(PT_ERR_INVALID, "%u pixels listed, the local image has %u", c.num_listed, npix);
+    const uint32_t wpix = c.kind.list ? c.num_listed : npix;   // the pixels of one frame of the workspace
+    const size_t frame_bytes = (size_t)wpix * 12;
+    // the spans, group by group: what every kind uses; the counts; the table; the list.  With no lights none of the light buffers is
+    // read.  The workspace must hold one frame, and ALL of it must lie apart from the rest: a chunk may fill it
+    const bool lit = a.num_lights > 0;
+    const PtSpan M = { materials, (size_t)a.num_materials * sizeof(PtRawMaterial), 1, "the material buffer" },
+                 L = { lights, (size_t)a.num_lights * sizeof(int32_t), 4, "the light list" },
+                 S = { samples, frame_bytes, 4, "the sample workspace" }, W = { samples, samples->bytes, 4, "the sample workspace" },
+                 F = { framebuffer, (size_t)npix * sizeof(float4), 16, "the framebuffer" },
+                 N = { mis && lit ? light_counts : nullptr, (size_t)a.num_triangles * sizeof(int32_t), 4, "the light-count buffer" },
+                 Q = { power && lit ? cdf : nullptr, ((size_t)a.num_lights + 1) * sizeof(uint64_t), 8, "the light table's cdf" },
+                 T = { power && lit ? tri_q : nullptr, (size_t)a.num_triangles * sizeof(uint32_t), 4, "the light table's tri_q" },
+                 P = { c.kind.list ? list : nullptr, 16 + (size_t)c.num_listed * sizeof(pt_pixel_slot), 8, "the pixel list" };
+    if ((rc = check_triangles(triangles, a.num_triangles)) || (rc = span_fits(M)) || (rc = span_fits(L)) || (rc = span_fits(S)) || (rc = span_fits(F))) return rc;
+    if ((rc = span_aligned(S)) || (rc = span_aligned(F)) || (lit && (rc = span_aligned(L))) || (rc = spans_apart({ W, F, L }))) return rc;
+    if ((rc = span_fits(N)) || (rc = span_aligned(N)) || (rc = spans_apart({ N, W, F, L }))) return rc;
+    if ((rc = span_fits(Q)) || (rc = span_fits(T)) || (rc = span_aligned(Q)) || (T.bytes && (rc = span_aligned(T))) || (rc = spans_apart({ Q, T, W, F, L, N }))) return rc;
+    if ((rc = span_fits(P)) || (rc = span_aligned(P)) || (rc = spans_apart({ P, W, F }))) return rc;
     // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
     if ((rc = check_traversal(d))) return rc;
     if ((rc = enter_stream(d))) return rc;
     if (a.frame_count == 0 || wpix == 0) {   // (no local pixel: none listed)
-        if ((rc = event_begin(d, ev))) return rc;
-        return event_end(d, ev);
+        if ((rc = event_begin(d, c.ev))) return rc;
+        return event_end(d, c.ev);
     }
     PtSearch search;
     if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
-    if ((rc = event_begin(d, ev))) return rc;
-    PtIndirectListParams ip;   // (every indirect block is a base of it)
+    if ((rc = event_begin(d, c.ev))) return rc;
+    PtIndirectListParams ip;   // (every kind's block is a base of it, or made of it: ptk_lit)
     memset(&ip, 0, sizeof ip);
-    ip.B = max_bounces;
-    if (rr) {
-        ip.R = rr->first_bounce;
-        ip.cap = rr->max_survival;
-    }
+    ip.B = c.max_bounces;
+    ip.R = c.rr.first_bounce;   // (zeros without roulette)
+    ip.cap = c.rr.max_survival;
     PtDirectParams& p = ip.d;
     search_fields(d, search, p.t);   // (an empty scene: the brute-force form over zero triangles, every sample the background)
     image_geometry(p.t, a.width, a.height, a.stripe_rows, a.n_ranks, a.rank, npix);
     p.t.mats = (const PtRawMaterial*)materials->dptr;
     p.t.nmat = a.num_materials;
-    p.cam = c;
-    p.lights = a.num_lights > 0 ? (const int32_t*)lights->dptr : nullptr;
+    p.cam = cam;
+    p.lights = lit ? (const int32_t*)lights->dptr : nullptr;
     p.samples = (float*)samples->dptr;
     p.npix = wpix;
     p.K = a.light_samples;
     p.nl = a.num_lights;
-    ip.counts = mis && a.num_lights > 0 ? (const int32_t*)light_counts->dptr : nullptr;
-    ip.cdf = power && a.num_lights > 0 ? (const uint64_t*)cdf->dptr : nullptr;
-    ip.tri_q = power && a.num_lights > 0 ? (const uint32_t*)tri_q->dptr : nullptr;
-    PtDirectPowerParams dp;   // (direct by power: direct's block and the table)
-    memset(&dp, 0, sizeof dp);
+    ip.counts = N.buf ? (const int32_t*)light_counts->dptr : nullptr;
+    ip.cdf = Q.buf ? (const uint64_t*)cdf->dptr : nullptr;
+    ip.tri_q = T.buf ? (const uint32_t*)tri_q->dptr : nullptr;
+    ip.slots = P.buf ? reinterpret_cast<const uint2*>(static_cast<const char*>(list->dptr) + 16) : nullptr;
     PtFoldParams fp;
     memset(&fp, 0, sizeof fp);
     fp.rad = p.samples;
@@ -1921,95 +1894,97 @@ static int render_lit(pt_device_t d, pt_buffer_t triangles, pt_buffer_t material
     fp.npix_local = npix;
     PtFoldListParams lp;
     memset(&lp, 0, sizeof lp);
-    if (pixels) {
-        ip.slots = reinterpret_cast<const uint2*>(static_cast<const char*>(list->dptr) + 16);
-        lp.rad = p.samples;
-        lp.fb = fp.fb;
-        lp.slots = ip.slots;
-        lp.num_listed = wpix;
-        lp.npix_local = npix;
-    }
-    const int per_cu = pixels ? d->indirect_list_bvh_blocks_per_cu[mis][power] : rr ? d->indirect_rr_bvh_blocks_per_cu[mis][power] :
-                       power ? (mis ? d->indirect_power_mis_bvh_blocks_per_cu
-                                    : max_bounces > 0 ? d->indirect_power_bvh_blocks_per_cu : d->direct_power_bvh_blocks_per_cu)
-                             : (mis ? d->indirect_mis_bvh_blocks_per_cu : max_bounces > 0 ? d->indirect_bvh_blocks_per_cu : d->direct_bvh_blocks_per_cu);
-    const int bvh_blocks = !search.mode.bvh ? 0 : d->prop.multiProcessorCount * per_cu;   // (each kernel its own grid: pt_kernels.h)
+    lp.rad = p.samples;
+    lp.fb = fp.fb;
+    lp.slots = ip.slots;
+    lp.num_listed = wpix;
+    lp.npix_local = npix;
+    // each kind's LBVH kernel on its own grid (pt_kernels.h)
+    const int bvh_blocks = !search.mode.bvh ? 0 : d->prop.multiProcessorCount * d->lit_bvh_blocks_per_cu[ptk_lit_kind_index(c.kind)];
     // whole frames per chunk: what the workspace holds, fewer than 2^31 samples per launch; a launch, then its fold
     const int64_t per_chunk = (int64_t)std::min<uint64_t>(samples->bytes / frame_bytes, 0x7fffffffu / wpix);
     for (int64_t done = 0; done < a.frame_count; done += per_chunk) {
         const int nf = (int)std::min<int64_t>(per_chunk, a.frame_count - done);
-        p.frame0 = a.frame_begin + (int)done;
+        p.frame0 = fp.frame_begin = a.frame_begin + (int)done;
         p.nitems = (uint32_t)nf * wpix;
-        if (pixels) {   // every slot continues from its own frame: the call's offset, then the frames of the chunks before
-            ip.frame_off = lp.frame_off = (uint32_t)p.frame0;
-            lp.frame_count = nf;
-            HIP_TRY(ptk_indirect_list(ip, bvh_blocks, search.mode, mis, power, d->stream));
-            HIP_TRY(ptk_fold_list(lp, d->stream));
-            continue;
-        }
-        if (power && max_bounces == 0) {
-            static_cast<PtDirectParams&>(dp) = p;
-            dp.cdf = ip.cdf;
-            dp.tri_q = ip.tri_q;
-        }
-        HIP_TRY(rr ? ptk_indirect_rr(ip, bvh_blocks, search.mode, mis, power, d->stream) :
-                power ? (max_bounces > 0 ? ptk_indirect_power(ip, bvh_blocks, search.mode, mis, d->stream) : ptk_direct_power(dp, bvh_blocks, search.mode, d->stream))
-                      : (max_bounces > 0 ? ptk_indirect(ip, bvh_blocks, search.mode, mis, d->stream) : ptk_direct(p, bvh_blocks, search.mode, d->stream)));
-        fp.frame_begin = p.frame0;
-        fp.frame_count = nf;
-        HIP_TRY(ptk_fold(fp, d->stream));
+        fp.frame_count = lp.frame_count = nf;
+        // a list: every slot continues from its own frame -- the call's offset, then the frames of the chunks before (no other kind's block holds it)
+        ip.frame_off = lp.frame_off = (uint32_t)p.frame0;
+        HIP_TRY(ptk_lit(ip, c.kind, bvh_blocks, search.mode, d->stream));
+        HIP_TRY(c.kind.list ? ptk_fold_list(lp, d->stream) : ptk_fold(fp, d->stream));
     }
     samples->version++;
     framebuffer->version++;
-    return event_end(d, ev);
+    return event_end(d, c.ev);
 }
 
-extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
-                                pt_buffer_t framebuffer, const pt_direct_params* params, const pt_camera* cam, pt_event_t ev)
+// what the direct entry points check of their block, and what the indirect ones do -- both after use_device --: the block pointer,
+// max_bounces, the reserved fields; the shared fields go to c.a
+static int direct_block(const pt_direct_params* params, PtLitCall& c)
 {
-    int rc = use_device(d);
-    if (rc) return rc;
     if (!params) return fail(PT_ERR_INVALID, "params == NULL");
-    const pt_direct_params a = *params;
+    c.a = *params;
     for (int i = 0; i < 5; ++i)
-        if (a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
-    return render_lit(d, triangles, materials, lights, nullptr, false, samples, framebuffer, a, 0, "invalid direct-illumination parameters", cam, ev);
+        if (c.a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    return PT_OK;
 }
-
-// ---- indirect illumination (include/pt_shim.h) ---------------------------------------------------------------------------------
-// pt_render_indirect and pt_render_indirect_mis: the same parameter block, the same checks of it
-static int render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts, bool mis,
-                           pt_buffer_t samples, pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev,
-                           const pt_buffer_t* table = nullptr, const pt_roulette* rr = nullptr, const PtPixelList* pixels = nullptr)
+static int indirect_block(const pt_indirect_params* params, PtLitCall& c)
 {
-    int rc = use_device(d);
-    if (rc) return rc;
     if (!params) return fail(PT_ERR_INVALID, "params == NULL");
     const pt_indirect_params b = *params;
     if (b.max_bounces < 1 || b.max_bounces > 65535) return fail(PT_ERR_INVALID, "max_bounces must lie in 1..65535");
     for (int i = 0; i < 4; ++i)
         if (b.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
-    pt_direct_params a;   // the shared fields, in direct's block
-    memset(&a, 0, sizeof a);
+    pt_direct_params& a = c.a;   // (zeros: lit_call)
     a.width = b.width; a.height = b.height; a.frame_begin = b.frame_begin; a.frame_count = b.frame_count;
     a.num_triangles = b.num_triangles; a.num_materials = b.num_materials; a.num_lights = b.num_lights;
     a.light_samples = b.light_samples;
     a.stripe_rows = b.stripe_rows; a.n_ranks = b.n_ranks; a.rank = b.rank;
-    return render_lit(d, triangles, materials, lights, light_counts, mis, samples, framebuffer, a, b.max_bounces,
-                      "invalid indirect-illumination parameters", cam, ev, table, rr, pixels);
+    c.max_bounces = b.max_bounces;
+    return PT_OK;
+}
+// what pt_render_indirect_rr and pt_render_indirect_pixels check before anything else: mis, the roulette, the table's two halves
+static int roulette_args(int mis, const pt_roulette* roulette, pt_buffer_t cdf, pt_buffer_t tri_q, const pt_indirect_params* params, PtLitCall& c)
+{
+    if (mis != 0 && mis != 1) return fail(PT_ERR_INVALID, "mis must be 0 or 1");
+    if (!roulette) return fail(PT_ERR_INVALID, "roulette == NULL");
+    c.rr = *roulette;
+    if (c.rr.first_bounce < 1) return fail(PT_ERR_INVALID, "first_bounce must be at least 1");
+    if (!(c.rr.max_survival > 0.0f && c.rr.max_survival <= 1.0f)) return fail(PT_ERR_INVALID, "max_survival must lie in (0, 1]");   // (false for NaN)
+    if (c.rr.reserved[0] != 0 || c.rr.reserved[1] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    if (params && params->num_lights > 0 && (cdf || tri_q) && !(cdf && tri_q))
+        return fail(PT_ERR_INVALID, "the light table is cdf AND tri_q (pt_light_table), or neither for the uniform choice");
+    return PT_OK;
 }
 
+extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
+                                pt_buffer_t framebuffer, const pt_direct_params* params, const pt_camera* cam, pt_event_t ev)
+{
+    PtLitCall c = lit_call({ false, false, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    int rc = use_device(d);
+    if (rc || (rc = direct_block(params, c))) return rc;
+    return render_lit(d, c);
+}
+
+// ---- indirect illumination (include/pt_shim.h) ---------------------------------------------------------------------------------
 extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
                                   pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
 {
-    return render_indirect(d, triangles, materials, lights, nullptr, false, samples, framebuffer, params, cam, ev);
+    PtLitCall c = lit_call({ true, false, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    int rc = use_device(d);
+    if (rc || (rc = indirect_block(params, c))) return rc;
+    return render_lit(d, c);
 }
 
 extern "C" int pt_render_indirect_mis(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts,
                                       pt_buffer_t samples, pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam,
                                       pt_event_t ev)
 {
-    return render_indirect(d, triangles, materials, lights, light_counts, true, samples, framebuffer, params, cam, ev);
+    PtLitCall c = lit_call({ true, true, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    c.light_counts = light_counts;
+    int rc = use_device(d);
+    if (rc || (rc = indirect_block(params, c))) return rc;
+    return render_lit(d, c);
 }
 
 // ---- light choice by power (include/pt_shim.h) -----------------------------------------------------------------------------------
@@ -2017,14 +1992,11 @@ extern "C" int pt_render_direct_power(pt_device_t d, pt_buffer_t triangles, pt_b
                                       pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params* params,
                                       const pt_camera* cam, pt_event_t ev)
 {
+    PtLitCall c = lit_call({ false, false, true, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    c.cdf = cdf; c.tri_q = tri_q;
     int rc = use_device(d);
-    if (rc) return rc;
-    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
-    const pt_direct_params a = *params;
-    for (int i = 0; i < 5; ++i)
-        if (a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
-    const pt_buffer_t table[2] = { cdf, tri_q };
-    return render_lit(d, triangles, materials, lights, nullptr, false, samples, framebuffer, a, 0, "invalid direct-illumination parameters", cam, ev, table);
+    if (rc || (rc = direct_block(params, c))) return rc;
+    return render_lit(d, c);
 }
 
 extern "C" int pt_render_indirect_power(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
@@ -2032,50 +2004,40 @@ extern "C" int pt_render_indirect_power(pt_device_t d, pt_buffer_t triangles, pt
                                         pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
 {
     if (mis != 0 && mis != 1) return fail(PT_ERR_INVALID, "mis must be 0 or 1");
-    const pt_buffer_t table[2] = { cdf, tri_q };
-    return render_indirect(d, triangles, materials, lights, mis ? light_counts : nullptr, mis != 0, samples, framebuffer, params, cam, ev, table);
+    PtLitCall c = lit_call({ true, mis != 0, true, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    c.light_counts = mis ? light_counts : nullptr;
+    c.cdf = cdf; c.tri_q = tri_q;
+    int rc = use_device(d);
+    if (rc || (rc = indirect_block(params, c))) return rc;
+    return render_lit(d, c);
 }
 
-// ---- Russian roulette (include/pt_shim.h) ------------------------------------------------------------------------------------------
-static_assert(sizeof(pt_roulette) == 16, "pt_roulette layout");
-
-// pt_render_indirect_rr, and with `pixels` pt_render_indirect_pixels: the same checks of the roulette and the table
-static int render_indirect_rr(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
-                              pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
-                              const pt_indirect_params* params, const pt_roulette* roulette, const pt_camera* cam, pt_event_t ev,
-                              const PtPixelList* pixels)
-{
-    if (mis != 0 && mis != 1) return fail(PT_ERR_INVALID, "mis must be 0 or 1");
-    if (!roulette) return fail(PT_ERR_INVALID, "roulette == NULL");
-    const pt_roulette r = *roulette;
-    if (r.first_bounce < 1) return fail(PT_ERR_INVALID, "first_bounce must be at least 1");
-    if (!(r.max_survival > 0.0f && r.max_survival <= 1.0f)) return fail(PT_ERR_INVALID, "max_survival must lie in (0, 1]");   // (false for NaN)
-    if (r.reserved[0] != 0 || r.reserved[1] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
-    const bool power = cdf || tri_q;   // both NULL: the uniform choice
-    if (params && params->num_lights > 0 && power && !(cdf && tri_q))
-        return fail(PT_ERR_INVALID, "the light table is cdf AND tri_q (pt_light_table), or neither for the uniform choice");
-    const pt_buffer_t table[2] = { cdf, tri_q };
-    return render_indirect(d, triangles, materials, lights, mis ? light_counts : nullptr, mis != 0, samples, framebuffer, params, cam, ev,
-                           power ? table : nullptr, &r, pixels);
-}
-
+// ---- Russian roulette and adaptive sampling (include/pt_shim.h) --------------------------------------------------------------------
+// (cdf and tri_q both NULL: the uniform choice)
 extern "C" int pt_render_indirect_rr(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
                                      pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
                                      const pt_indirect_params* params, const pt_roulette* roulette, const pt_camera* cam, pt_event_t ev)
 {
-    return render_indirect_rr(d, triangles, materials, lights, mis, light_counts, cdf, tri_q, samples, framebuffer, params, roulette, cam, ev, nullptr);
+    PtLitCall c = lit_call({ true, mis != 0, cdf || tri_q, true, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    c.light_counts = mis ? light_counts : nullptr;
+    c.cdf = cdf; c.tri_q = tri_q;
+    int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
+    if (rc || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
+    return render_lit(d, c);
 }
-
-// ---- adaptive sampling (include/pt_shim.h) -------------------------------------------------------------------------------------
-static_assert(sizeof(pt_adaptive_rule) == 32 && sizeof(pt_pixel_slot) == 8 && sizeof(pt_pixel_slot) == sizeof(uint2), "adaptive record layout");
 
 extern "C" int pt_render_indirect_pixels(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
                                          pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
                                          pt_buffer_t list, uint32_t num_listed, const pt_indirect_params* params, const pt_roulette* roulette,
                                          const pt_camera* cam, pt_event_t ev)
 {
-    const PtPixelList pixels = { list, num_listed };
-    return render_indirect_rr(d, triangles, materials, lights, mis, light_counts, cdf, tri_q, samples, framebuffer, params, roulette, cam, ev, &pixels);
+    PtLitCall c = lit_call({ true, mis != 0, cdf || tri_q, true, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    c.light_counts = mis ? light_counts : nullptr;
+    c.cdf = cdf; c.tri_q = tri_q;
+    c.list = list; c.num_listed = num_listed;
+    int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
+    if (rc || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
+    return render_lit(d, c);
 }
 
 extern "C" size_t pt_adaptive_list_bytes(uint32_t num_pixels) { return PT_ADAPTIVE_LIST_BYTES(num_pixels); }
@@ -2090,13 +2052,9 @@ extern "C" int pt_adaptive_select(pt_device_t d, pt_buffer_t moments, uint32_t n
     const pt_adaptive_rule r = *rule;
     if (!(r.tol2 >= 0.0) || !(r.floor2 >= 0.0)) return fail(PT_ERR_INVALID, "tol2 and floor2 must not be negative or NaN");
     if (r.reserved[0] != 0 || r.reserved[1] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
-    const size_t moment_bytes = (size_t)num_pixels * sizeof(pt_pixel_moments), list_bytes = pt_adaptive_list_bytes(num_pixels);
-    if (moment_bytes > moments->bytes) return fail(PT_ERR_RANGE, "moments hold %zu bytes, %u pixels need %zu", moments->bytes, num_pixels, moment_bytes);
-    if (list_bytes > list->bytes)
-        return fail(PT_ERR_RANGE, "the pixel list holds %zu bytes, %u pixels need %zu (pt_adaptive_list_bytes)", list->bytes, num_pixels, list_bytes);
-    if ((uintptr_t)moments->dptr & 7u) return fail(PT_ERR_INVALID, "the moments must be 8-byte aligned");
-    if ((uintptr_t)list->dptr & 7u) return fail(PT_ERR_INVALID, "the pixel list must be 8-byte aligned");
-    if (ranges_overlap(moments, moment_bytes, list, list_bytes)) return fail(PT_ERR_INVALID, "the moments and the pixel list overlap");
+    const PtSpan M = { moments, (size_t)num_pixels * sizeof(pt_pixel_moments), 8, "the moment buffer" },
+                 P = { list, pt_adaptive_list_bytes(num_pixels), 8, "the pixel list (pt_adaptive_list_bytes)" };
+    if ((rc = span_fits(M)) || (rc = span_fits(P)) || (rc = span_aligned(M)) || (rc = span_aligned(P)) || (rc = spans_apart({ M, P }))) return rc;
     if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
     const PtAdaptiveRule k = { r.tol2, r.floor2, r.min_samples, r.max_samples };
     HIP_TRY(ptk_adaptive_select((const PtPixelMoments*)moments->dptr, num_pixels, k, list->dptr, d->stream));
@@ -2115,18 +2073,12 @@ extern "C" int pt_sample_moments_pixels(pt_device_t d, pt_buffer_t samples, pt_b
     // the local pixels: the whole records the moments buffer holds
     const size_t records = std::min<size_t>(moments->bytes / sizeof(pt_pixel_moments), 0xffffffffu);
     if ((size_t)num_listed > records) return fail(PT_ERR_INVALID, "%u pixels listed, the moments hold %zu records", num_listed, records);
-    const size_t moment_bytes = records * sizeof(pt_pixel_moments), list_bytes = 16 + (size_t)num_listed * sizeof(pt_pixel_slot);
     const size_t frame_bytes = (size_t)num_listed * 3u * sizeof(float);
-    if (frame_bytes && (size_t)frame_count > samples->bytes / frame_bytes)
+    if (frame_bytes && (size_t)frame_count > samples->bytes / frame_bytes)   // (a quotient: the product may not fit a size_t)
         return fail(PT_ERR_RANGE, "sample buffer holds %zu bytes, %d frames of %u pixels need more", samples->bytes, frame_count, num_listed);
-    const size_t sample_bytes = frame_bytes * (size_t)frame_count;
-    if (list_bytes > list->bytes) return fail(PT_ERR_RANGE, "the pixel list holds %zu bytes, %u slots need %zu", list->bytes, num_listed, list_bytes);
-    if ((uintptr_t)moments->dptr & 7u) return fail(PT_ERR_INVALID, "the moments must be 8-byte aligned");
-    if ((uintptr_t)samples->dptr & 3u) return fail(PT_ERR_INVALID, "the samples must be 4-byte aligned");
-    if ((uintptr_t)list->dptr & 7u) return fail(PT_ERR_INVALID, "the pixel list must be 8-byte aligned");
-    if (ranges_overlap(samples, sample_bytes, moments, moment_bytes) || ranges_overlap(list, list_bytes, moments, moment_bytes) ||
-        ranges_overlap(list, list_bytes, samples, sample_bytes))
-        return fail(PT_ERR_INVALID, "the samples, the moments and the pixel list overlap");
+    const PtSpan S = { samples, frame_bytes * (size_t)frame_count, 4, "the sample buffer" }, M = { moments, records * sizeof(pt_pixel_moments), 8, "the moment buffer" },
+                 P = { list, 16 + (size_t)num_listed * sizeof(pt_pixel_slot), 8, "the pixel list" };
+    if ((rc = span_fits(P)) || (rc = span_aligned(M)) || (rc = span_aligned(S)) || (rc = span_aligned(P)) || (rc = spans_apart({ S, M, P }))) return rc;
     if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
     if (num_listed && frame_count) {
         HIP_TRY(ptk_sample_moments_list((const float*)samples->dptr, (PtPixelMoments*)moments->dptr,
@@ -2152,24 +2104,14 @@ extern "C" int pt_light_table(pt_device_t d, pt_buffer_t triangles, int num_tria
     if (num_lights < 0 || num_triangles < 0 || num_materials < 1) return fail(PT_ERR_INVALID, "invalid light-table parameters");
     if (num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
     if (num_lights > 0 && !lights) return fail(PT_ERR_INVALID, "num_lights > 0 needs a light list");
-    const size_t light_bytes = (size_t)num_lights * sizeof(int32_t), cdf_bytes = pt_light_table_bytes(num_lights),
-                 q_bytes = (size_t)num_triangles * sizeof(uint32_t);
-    if ((rc = check_triangles(triangles, num_triangles))) return rc;
-    if ((size_t)num_materials * sizeof(PtRawMaterial) > materials->bytes)
-        return fail(PT_ERR_RANGE, "material buffer holds %zu bytes, %d materials need %zu", materials->bytes, num_materials,
-                    (size_t)num_materials * sizeof(PtRawMaterial));
-    if (lights && light_bytes > lights->bytes) return fail(PT_ERR_RANGE, "light list holds %zu bytes, %d lights need %zu", lights->bytes, num_lights, light_bytes);
-    if (cdf_bytes > cdf->bytes) return fail(PT_ERR_RANGE, "the light table's cdf holds %zu bytes, %d lights need %zu (pt_light_table_bytes)", cdf->bytes, num_lights, cdf_bytes);
-    if (q_bytes > tri_q->bytes) return fail(PT_ERR_RANGE, "the light table's tri_q holds %zu bytes, %d triangles need %zu", tri_q->bytes, num_triangles, q_bytes);
-    if ((uintptr_t)cdf->dptr & 7u) return fail(PT_ERR_INVALID, "the light table's cdf must be 8-byte aligned");
-    if (q_bytes && ((uintptr_t)tri_q->dptr & 3u)) return fail(PT_ERR_INVALID, "the light table's tri_q must be 4-byte aligned");
-    if (lights && num_lights > 0 && ((uintptr_t)lights->dptr & 3u)) return fail(PT_ERR_INVALID, "the light list must be 4-byte aligned");
-    const pt_buffer_s* in[] = { triangles, materials, lights };
-    const size_t in_bytes[] = { (size_t)num_triangles * sizeof(PtRawTriangle), (size_t)num_materials * sizeof(PtRawMaterial), light_bytes };
-    for (int i = 0; i < 3; ++i)
-        if (in[i] && (ranges_overlap(cdf, cdf_bytes, in[i], in_bytes[i]) || ranges_overlap(tri_q, q_bytes, in[i], in_bytes[i])))
-            return fail(PT_ERR_INVALID, "the light table overlaps the triangles, the materials or the light list");
-    if (ranges_overlap(cdf, cdf_bytes, tri_q, q_bytes)) return fail(PT_ERR_INVALID, "the light table's cdf and tri_q overlap");
+    const PtSpan R = { triangles, (size_t)num_triangles * sizeof(PtRawTriangle), 1, "the triangle buffer" },
+                 M = { materials, (size_t)num_materials * sizeof(PtRawMaterial), 1, "the material buffer" },
+                 L = { lights, (size_t)num_lights * sizeof(int32_t), 4, "the light list" },
+                 Q = { cdf, pt_light_table_bytes(num_lights), 8, "the light table's cdf (pt_light_table_bytes)" },
+                 T = { tri_q, (size_t)num_triangles * sizeof(uint32_t), 4, "the light table's tri_q" };
+    if ((rc = span_fits(R)) || (rc = span_fits(M)) || (rc = span_fits(L)) || (rc = span_fits(Q)) || (rc = span_fits(T))) return rc;
+    if ((rc = span_aligned(Q)) || (T.bytes && (rc = span_aligned(T))) || (num_lights > 0 && (rc = span_aligned(L)))) return rc;
+    if ((rc = spans_apart({ Q, T }, { R, M, L }))) return rc;   // (the inputs are only read)
     if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
     HIP_TRY(ptk_light_table((const PtRawTriangle*)triangles->dptr, num_triangles, (const PtRawMaterial*)materials->dptr, num_materials,
                             num_lights > 0 ? (const int32_t*)lights->dptr : nullptr, num_lights, (uint64_t*)cdf->dptr, (uint32_t*)tri_q->dptr, d->stream));
@@ -2187,12 +2129,11 @@ extern "C" int pt_light_counts(pt_device_t d, pt_buffer_t lights, int num_lights
     if (num_lights < 0 || num_triangles < 0) return fail(PT_ERR_INVALID, "invalid light-count parameters");
     if (num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
     if (num_lights > 0 && !lights) return fail(PT_ERR_INVALID, "num_lights > 0 needs a light list");
-    const size_t light_bytes = (size_t)num_lights * sizeof(int32_t), count_bytes = (size_t)num_triangles * sizeof(int32_t);
-    if (lights && light_bytes > lights->bytes) return fail(PT_ERR_RANGE, "light list holds %zu bytes, %d lights need %zu", lights->bytes, num_lights, light_bytes);
-    if (count_bytes > counts->bytes) return fail(PT_ERR_RANGE, "light counts hold %zu bytes, %d triangles need %zu", counts->bytes, num_triangles, count_bytes);
-    if (count_bytes && ((uintptr_t)counts->dptr & 3u)) return fail(PT_ERR_INVALID, "the light counts must be 4-byte aligned");
-    if (lights && num_lights > 0 && ((uintptr_t)lights->dptr & 3u)) return fail(PT_ERR_INVALID, "the light list must be 4-byte aligned");
-    if (lights && ranges_overlap(lights, light_bytes, counts, count_bytes)) return fail(PT_ERR_INVALID, "the light list and the light counts overlap");
+    const PtSpan L = { lights, (size_t)num_lights * sizeof(int32_t), 4, "the light list" },
+                 N = { counts, (size_t)num_triangles * sizeof(int32_t), 4, "the light-count buffer" };
+    if ((rc = span_fits(L)) || (rc = span_fits(N)) || (N.bytes && (rc = span_aligned(N))) || (num_lights > 0 && (rc = span_aligned(L))) ||
+        (rc = spans_apart({ L, N })))
+        return rc;
     if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
     HIP_TRY(ptk_light_counts(num_lights > 0 ? (const int32_t*)lights->dptr : nullptr, num_lights, num_triangles, (int32_t*)counts->dptr, d->stream));
     counts->version++;
@@ -2211,15 +2152,12 @@ extern "C" int pt_sample_moments(pt_device_t d, pt_buffer_t samples, pt_buffer_t
     if (!samples || !moments) return fail(PT_ERR_INVALID, "null buffer handle");
     if ((rc = check_same_device(d, { samples, moments })) || (rc = check_event(d, ev))) return rc;
     if (frame_count < 0) return fail(PT_ERR_INVALID, "frame_count < 0");
-    const size_t moment_bytes = (size_t)num_pixels * sizeof(pt_pixel_moments);
     const size_t frame_bytes = (size_t)num_pixels * 3u * sizeof(float);
-    if (frame_bytes && (size_t)frame_count > samples->bytes / frame_bytes)
+    if (frame_bytes && (size_t)frame_count > samples->bytes / frame_bytes)   // (a quotient: the product may not fit a size_t)
         return fail(PT_ERR_RANGE, "sample buffer holds %zu bytes, %d frames of %u pixels need more", samples->bytes, frame_count, num_pixels);
-    const size_t sample_bytes = frame_bytes * (size_t)frame_count;
-    if (moment_bytes > moments->bytes) return fail(PT_ERR_RANGE, "moments hold %zu bytes, %u pixels need %zu", moments->bytes, num_pixels, moment_bytes);
-    if ((uintptr_t)moments->dptr & 7u) return fail(PT_ERR_INVALID, "the moments must be 8-byte aligned");
-    if ((uintptr_t)samples->dptr & 3u) return fail(PT_ERR_INVALID, "the samples must be 4-byte aligned");
-    if (ranges_overlap(samples, sample_bytes, moments, moment_bytes)) return fail(PT_ERR_INVALID, "the samples and the moments overlap");
+    const PtSpan S = { samples, frame_bytes * (size_t)frame_count, 4, "the sample buffer" },
+                 M = { moments, (size_t)num_pixels * sizeof(pt_pixel_moments), 8, "the moment buffer" };
+    if ((rc = span_fits(M)) || (rc = span_aligned(M)) || (rc = span_aligned(S)) || (rc = spans_apart({ S, M }))) return rc;
     if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
     if (num_pixels && frame_count) {
         HIP_TRY(ptk_sample_moments((const float*)samples->dptr, (PtPixelMoments*)moments->dptr, num_pixels, frame_count, reset != 0, d->stream));
@@ -2236,18 +2174,11 @@ extern "C" int pt_moments_resolve(pt_device_t d, pt_buffer_t moments, uint32_t n
     if (rc) return rc;
     if (!moments) return fail(PT_ERR_INVALID, "null buffer handle");
     if ((rc = check_same_device(d, { moments, noise, summary })) || (rc = check_event(d, ev))) return rc;
-    const size_t moment_bytes = (size_t)num_pixels * sizeof(pt_pixel_moments), noise_bytes = (size_t)num_pixels * 16u,
-                 summary_bytes = pt_moments_summary_bytes(num_pixels);
-    if (moment_bytes > moments->bytes) return fail(PT_ERR_RANGE, "moments hold %zu bytes, %u pixels need %zu", moments->bytes, num_pixels, moment_bytes);
-    if (noise && noise_bytes > noise->bytes) return fail(PT_ERR_RANGE, "the noise map holds %zu bytes, %u pixels need %zu", noise->bytes, num_pixels, noise_bytes);
-    if (summary && summary_bytes > summary->bytes)
-        return fail(PT_ERR_RANGE, "the summary holds %zu bytes, %u pixels need %zu (pt_moments_summary_bytes)", summary->bytes, num_pixels, summary_bytes);
-    if ((uintptr_t)moments->dptr & 7u) return fail(PT_ERR_INVALID, "the moments must be 8-byte aligned");
-    if (noise && ((uintptr_t)noise->dptr & 15u)) return fail(PT_ERR_INVALID, "the noise map must be 16-byte aligned");
-    if (summary && ((uintptr_t)summary->dptr & 7u)) return fail(PT_ERR_INVALID, "the summary must be 8-byte aligned");
-    if ((noise && ranges_overlap(moments, moment_bytes, noise, noise_bytes)) || (summary && ranges_overlap(moments, moment_bytes, summary, summary_bytes)) ||
-        (noise && summary && ranges_overlap(noise, noise_bytes, summary, summary_bytes)))
-        return fail(PT_ERR_INVALID, "the moments, the noise map and the summary overlap");
+    const PtSpan M = { moments, (size_t)num_pixels * sizeof(pt_pixel_moments), 8, "the moment buffer" },
+                 V = { noise, (size_t)num_pixels * 16u, 16, "the noise map" },
+                 U = { summary, pt_moments_summary_bytes(num_pixels), 8, "the summary (pt_moments_summary_bytes)" };
+    if ((rc = span_fits(M)) || (rc = span_fits(V)) || (rc = span_fits(U))) return rc;
+    if ((rc = span_aligned(M)) || (rc = span_aligned(V)) || (rc = span_aligned(U)) || (rc = spans_apart({ M, V, U }))) return rc;
     if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
     if (num_pixels && (noise || summary)) {
         HIP_TRY(ptk_moments_resolve((const PtPixelMoments*)moments->dptr, num_pixels, noise ? noise->dptr : nullptr,

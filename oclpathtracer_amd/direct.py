@@ -32,6 +32,11 @@ _WORKSPACE_BYTES = 64 << 20   # the default workspace holds as many whole frames
 Noise = collections.namedtuple("Noise", "variance_per_sample relative_error pixels samples rejected")
 
 
+def _handle(obj):
+    """the library's handle of an optional object (a SyncObject, a Buffer); None stays None"""
+    return obj._h if obj is not None else None
+
+
 def _check_lights(lights, num_triangles: int) -> np.ndarray:
     a = np.asarray(lights)
     if a.dtype.kind not in "iu":
@@ -144,11 +149,20 @@ class DirectRenderer:
         self.cdf = adl.Buffer(self.dev, self._lib.pt_light_table_bytes(nl) // 8, np.uint64)
         self.tri_q = adl.Buffer(self.dev, max(self.num_triangles, 1), np.uint32)
         shim.check(self._lib.pt_light_table(self.dev._h, self.tbuf._h, self.num_triangles, self.mbuf._h, self.num_materials,
-                                            self.lbuf._h if nl else None, nl, self.cdf._h, self.tri_q._h, None))
+                                            self._lights_h(), nl, self.cdf._h, self.tri_q._h, None))
 
     def _set_camera(self, camera: Optional[Camera]) -> None:
         self._cam = Camera.struct_of(camera)   # rejected here, before anything is enqueued
         self.camera = camera
+
+    # the handles every entry point takes the same way
+    def _lights_h(self):
+        """the light list's handle; None for an empty list (the buffer then holds one unused entry)"""
+        return self.lbuf._h if len(self.lights) else None
+
+    def _cam_ref(self):
+        """the camera's struct by reference; None for the reference's camera"""
+        return ctypes.byref(self._cam) if self._cam is not None else None
 
     def set_camera(self, camera: Optional[Camera]) -> None:
         """Render from ``camera`` from now on (None: the reference's); the next render starts again at frame 0."""
@@ -198,14 +212,10 @@ class DirectRenderer:
     def _call(self, p, sync) -> int:
         """the entry point's return code (a renderer with another argument list overrides this)"""
         if self.light_choice == "power":
-            return self._lib.pt_render_direct_power(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
-                                                    self.cdf._h, self.tri_q._h, self.samples._h, self.fb._h, ctypes.byref(p),
-                                                    ctypes.byref(self._cam) if self._cam is not None else None,
-                                                    sync._h if sync is not None else None)
-        return getattr(self._lib, self._ENTRY)(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
-                                               self.samples._h, self.fb._h, ctypes.byref(p),
-                                               ctypes.byref(self._cam) if self._cam is not None else None,
-                                               sync._h if sync is not None else None)
+            return self._lib.pt_render_direct_power(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), self.cdf._h, self.tri_q._h,
+                                                    self.samples._h, self.fb._h, ctypes.byref(p), self._cam_ref(), _handle(sync))
+        return getattr(self._lib, self._ENTRY)(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), self.samples._h, self.fb._h,
+                                               ctypes.byref(p), self._cam_ref(), _handle(sync))
 
     def read(self) -> np.ndarray:
         """Local framebuffer as (local_rows * width, 4) float32, the renderer's layout (synchronises)."""

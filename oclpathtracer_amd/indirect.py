@@ -41,7 +41,7 @@ import math
 import numpy as np
 
 from . import adl, shim
-from .direct import DirectRenderer
+from .direct import DirectRenderer, _handle
 from .render import BOUNCES
 
 
@@ -98,8 +98,7 @@ class IndirectRenderer(DirectRenderer):
         if self.mis:
             try:
                 self.counts = adl.Buffer(dev, max(self.num_triangles, 1), np.int32)
-                shim.check(self._lib.pt_light_counts(dev._h, self.lbuf._h if len(self.lights) else None, len(self.lights),
-                                                     self.num_triangles, self.counts._h, None))
+                shim.check(self._lib.pt_light_counts(dev._h, self._lights_h(), len(self.lights), self.num_triangles, self.counts._h, None))
             except Exception:
                 self.release()
                 raise
@@ -110,26 +109,21 @@ class IndirectRenderer(DirectRenderer):
         return p
 
     def _call(self, p, sync) -> int:
+        scene3 = (self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h())
         if self._rr is not None:
-            power = self.light_choice == "power"
-            return self._lib.pt_render_indirect_rr(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
-                                                   int(self.mis), self.counts._h if self.mis else None,
-                                                   self.cdf._h if power else None, self.tri_q._h if power else None,
-                                                   self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(self._rr),
-                                                   ctypes.byref(self._cam) if self._cam is not None else None,
-                                                   sync._h if sync is not None else None)
+            return self._lib.pt_render_indirect_rr(*scene3, *self._estimator(), self.samples._h, self.fb._h, ctypes.byref(p),
+                                                   ctypes.byref(self._rr), self._cam_ref(), _handle(sync))
         if self.light_choice == "power":
-            return self._lib.pt_render_indirect_power(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
-                                                      int(self.mis), self.counts._h if self.mis else None, self.cdf._h, self.tri_q._h,
-                                                      self.samples._h, self.fb._h, ctypes.byref(p),
-                                                      ctypes.byref(self._cam) if self._cam is not None else None,
-                                                      sync._h if sync is not None else None)
+            return self._lib.pt_render_indirect_power(*scene3, *self._estimator(), self.samples._h, self.fb._h, ctypes.byref(p),
+                                                      self._cam_ref(), _handle(sync))
         if not self.mis:
             return super()._call(p, sync)
-        return self._lib.pt_render_indirect_mis(self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if len(self.lights) else None,
-                                                self.counts._h, self.samples._h, self.fb._h, ctypes.byref(p),
-                                                ctypes.byref(self._cam) if self._cam is not None else None,
-                                                sync._h if sync is not None else None)
+        return self._lib.pt_render_indirect_mis(*scene3, self.counts._h, self.samples._h, self.fb._h, ctypes.byref(p), self._cam_ref(),
+                                                _handle(sync))
+
+    def _estimator(self):
+        """(mis, counts, cdf, tri_q) as the entry points with an estimator argument take them: a handle the estimator does not read is None"""
+        return int(self.mis), _handle(self.counts), _handle(self.cdf), _handle(self.tri_q)
 
     def render(self, frames: int, frame_begin=None, sync=None) -> None:
         """``DirectRenderer.render``; after an adaptive pass only a start at frame 0 is accepted: the pixels no longer share a frame
@@ -189,8 +183,6 @@ class IndirectRenderer(DirectRenderer):
             self.pixel_list = adl.Buffer(self.dev, self._lib.pt_adaptive_list_bytes(self.local_pixels), np.uint8)
         rule = shim.AdaptiveRule(tolerance * tolerance, floor * floor, min_samples, max_samples)
         rr = self._rr if self._rr is not None else shim.Roulette(65535, 1.0)   # (no roulette: a first bounce no path reaches)
-        power = self.light_choice == "power"
-        nl = len(self.lights)
         header = np.zeros(1, np.uint32)
         while True:
             shim.check(self._lib.pt_adaptive_select(self.dev._h, self.mom._h, self.local_pixels, ctypes.byref(rule), self.pixel_list._h, None))
@@ -206,9 +198,8 @@ class IndirectRenderer(DirectRenderer):
             while done < fpp:
                 k = min(hold, fpp - done)
                 shim.check(self._lib.pt_render_indirect_pixels(
-                    self.dev._h, self.tbuf._h, self.mbuf._h, self.lbuf._h if nl else None, int(self.mis), self.counts._h if self.mis else None,
-                    self.cdf._h if power else None, self.tri_q._h if power else None, self.samples._h, self.fb._h, self.pixel_list._h,
-                    listed, ctypes.byref(self.params(k, done)), ctypes.byref(rr), ctypes.byref(self._cam) if self._cam is not None else None, None))
+                    self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), *self._estimator(), self.samples._h, self.fb._h,
+                    self.pixel_list._h, listed, ctypes.byref(self.params(k, done)), ctypes.byref(rr), self._cam_ref(), None))
                 shim.check(self._lib.pt_sample_moments_pixels(self.dev._h, self.samples._h, self.mom._h, self.pixel_list._h, listed, k, None))
                 done += k
             rendered += listed * fpp
