@@ -815,6 +815,72 @@ int pt_sample_moments_pixels(pt_device_t dev, pt_buffer_t samples /* float[frame
                              pt_buffer_t moments /* pt_pixel_moments[] */, pt_buffer_t list, uint32_t num_listed, int32_t frame_count,
                              pt_event_t ev);
 
+/* ---- resampled light sampling (RIS) ---------------------------------------------------------------------------------------
+ * Every estimator above chooses the light of a light sample without looking at the shading point: in a room of many emitters of
+ * similar power the choice by power is the uniform choice, and almost every shadow ray goes to a light that is far away, faces
+ * away or contributes little.  A shadow ray is the expensive part of a light sample -- on the LBVH a whole any-hit search --, a
+ * candidate (three uniforms, one table lookup, a BRDF value, a geometry term) needs no search.  Resampled importance sampling draws
+ * M = candidates of them from the table, keeps one in proportion to its unshadowed contribution at this vertex and casts the one ray.
+ * New estimators beside the old ones, which are unchanged.
+ *
+ * RIS replaces a light sample: steps 3a-3g of pt_render_direct in the table form of "light choice by power", with the MIS weighting
+ * of pt_render_indirect_mis where MIS is on.  1 <= M <= 32, a run-time value.  RIS requires the table: cdf and tri_q are needed
+ * whenever num_lights > 0; there is no uniform-choice form.
+ * For light sample k of a vertex: wsum = 0, have = false; for m = 0 .. M - 1, in this order:
+ *  1. r0, r1, r2 are drawn and candidate m is evaluated exactly as the light sample by power is (3a-3g with 3b and 3f of the table):
+ *     it contributes or not, and if it does it has c_m, the shadow ray (o_m, d_m) and its limit tl_m = min(dist - 0.02f, 1e20f).  With
+ *     MIS c_m carries the balance factor kp / (kp * counts[j] + pbl) when the vertex is not the last and sl > 0, with the same kp = K
+ *     * pe formed from the table's inv.  A table of total 0 draws the three uniforms and does not contribute.
+ *  2. if m >= 1: r = getRandomFloat(&seed), drawn whether or not the candidate contributes.  A light sample therefore always consumes
+ *     4M - 1 uniforms, and M = 1 the parent's three.
+ *  3. if the candidate contributes: s_m = max(c.x, max(c.y, c.z)) with the reference's max ((a < b) ? b : a).  If s_m > 0 (false for
+ *     NaN): wsum = wsum + s_m; then candidate m is kept (its c, o, d, tl, s) and have = true if and only if !have or r * wsum < s_m
+ *     -- the product is one binary32 multiplication.  (A reservoir of one: candidate m replaces the kept one with probability s_m / wsum.)
+ * After the loop: !have: no ray is cast and nothing is added.  Otherwise g = (wsum / (float)M) / s_sel, two generic IEEE divisions
+ * (the operands have no proven window for a short form), and c = c_sel * g per channel.  The shadow ray is the parent's in every
+ * respect: tl <= 0 is open and unsearched, otherwise the any-hit search up to tl, and S += c when open.  An infinite s gives a NaN
+ * sample (inf / inf); that is defined behaviour, and pt_sample_moments rejects it.
+ * Why it is unbiased: c_m is (the integrand without visibility) / (the source density q_i / total x 1 / area, in solid angle).  The
+ * target s_m is its largest channel, positive wherever any channel of the integrand is, for materials that are not negative.  The
+ * kept candidate's c_sel x V x (mean of the M weights s_m) / s_sel is the RIS estimator of the integral of integrand x visibility:
+ * its expectation over the kept index and then over the candidates is that of one candidate's c_m x V, which is the parent's.
+ * Why the MIS weights still partition: the light-side factor kp * counts / (kp * counts + pbl) is part of the candidate's integrand;
+ * the BRDF ray's wb is untouched; both are formed from the same source densities as without RIS and sum to 1 for every direction,
+ * and any partition of unity is unbiased.  This is NO LONGER the balance heuristic with respect to the resampled density, which is
+ * intractable: it is the parent's weights applied to a better light technique.  The two MIS rules are unchanged: the last vertex
+ * is not weighted, sl <= 0 is not weighted.
+ * Identities: M = 1 draws nothing extra and has g = 1.0f exactly (wsum = s, s / 1 = s, s / s = 1 for a finite s > 0), so framebuffer
+ * and workspace are the parent's bit for bit -- pt_render_direct_power for pt_render_direct_ris, pt_render_indirect_rr with the table
+ * for pt_render_indirect_ris, pt_render_indirect_pixels for pt_render_indirect_pixels_ris -- on every input where each contributing
+ * light sample has a finite c with s > 0, or c = 0 in all channels (the parent casts a ray for a zero c and adds zero; RIS casts
+ * none).  num_lights == 0 is the parent's image for every M.  B == 1: the indirect image is pt_render_direct_ris' at the same M.
+ *
+ * The three entry points take their parents' arguments -- pt_render_direct_power's, pt_render_indirect_rr's (R >= B plays no
+ * roulette, as there), pt_render_indirect_pixels' -- plus the pt_ris block.  Behaviour and errors: the parents', word for word -- one
+ * validation, one chunk loop, one fold, the handle's stream, the deferred PT_ERR_TRAVERSAL --, plus, before anything is enqueued,
+ * PT_ERR_INVALID for ris NULL, candidates outside 1 .. 32, a reserved word of pt_ris not 0, and cdf or tri_q NULL while num_lights > 0. */
+typedef struct pt_ris {
+    int32_t candidates;     /* M, 1 .. 32 */
+    int32_t reserved[3];    /* must be 0 */
+} pt_ris;                   /* 16 bytes */
+int pt_render_direct_ris(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                         pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, pt_buffer_t cdf, pt_buffer_t tri_q /* may be NULL when 0 */,
+                         pt_buffer_t samples /* workspace */, pt_buffer_t framebuffer, const pt_direct_params* params, const pt_ris* ris,
+                         const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
+int pt_render_indirect_ris(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                           pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, int mis,
+                           pt_buffer_t light_counts /* int32[num_triangles]; may be NULL when mis or num_lights is 0 */,
+                           pt_buffer_t cdf, pt_buffer_t tri_q /* may be NULL when num_lights is 0 */, pt_buffer_t samples /* workspace */,
+                           pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_roulette* roulette, const pt_ris* ris,
+                           const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
+int pt_render_indirect_pixels_ris(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                                  pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, int mis,
+                                  pt_buffer_t light_counts /* int32[num_triangles]; may be NULL when mis or num_lights is 0 */,
+                                  pt_buffer_t cdf, pt_buffer_t tri_q /* may be NULL when num_lights is 0 */, pt_buffer_t samples /* workspace */,
+                                  pt_buffer_t framebuffer, pt_buffer_t list, uint32_t num_listed, const pt_indirect_params* params,
+                                  const pt_roulette* roulette, const pt_ris* ris, const pt_camera* cam /* NULL = the reference's */,
+                                  pt_event_t ev);
+
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.
  * pt_profile_query synchronises the stream and returns the summed duration and launch count

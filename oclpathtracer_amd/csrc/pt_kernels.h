@@ -328,23 +328,37 @@ struct PtIndirectListParams : PtIndirectRrParams {
     const uint2* slots;           // [d.npix] pt_pixel_slot {pixel, frame}
     uint32_t frame_off;           // the frames every listed pixel has received from this call already
 };
-// A kind of lit render names its kernels.  The 14 valid values:
+// resampled light sampling (pt_render_direct_ris, pt_render_indirect_ris, pt_render_indirect_pixels_ris): the RIS = true instantiations
+// take these blocks, every other instantiation its block as before (their code does not move).  M is wave-uniform: it adds no per-lane
+// state; the roulette form does not read slots and frame_off
+struct PtDirectRisParams : PtDirectPowerParams {
+    int32_t M;                    // candidates per light sample, 1 .. 32
+};
+struct PtIndirectRisParams : PtIndirectListParams {
+    int32_t M;
+};
+// A kind of lit render names its kernels.  The 14 valid values without ris:
 //   direct illumination (pt_direct_kernel, pt_direct_bvh_kernel):          indirect = mis = rr = list = 0;  power 0 / 1
 //   indirect illumination (pt_indirect_kernel, pt_indirect_bvh_kernel):    indirect = 1, rr = list = 0;     mis 0 / 1 x power 0 / 1
 //   ... with Russian roulette (pt_indirect_rr_kernel, ..._bvh_kernel RR):  indirect = rr = 1, list = 0;     mis x power
 //   ... over a list of pixels (their LIST forms):                          indirect = rr = list = 1;        mis x power
 // list implies rr, rr implies indirect, mis comes only with indirect
-struct PtLitKind { bool indirect, mis, power, rr, list; };
-static inline bool ptk_lit_kind_valid(PtLitKind k) { return (!k.list || k.rr) && (!k.rr || k.indirect) && (!k.mis || k.indirect); }
-static inline int ptk_lit_kind_index(PtLitKind k) { return k.indirect | k.mis << 1 | k.power << 2 | k.rr << 3 | k.list << 4; }   // a table's index
-#define PT_LIT_KIND_INDICES 32
+// and the 5 with ris (the RIS = true instantiations of the same templates): direct by power; the roulette and the list kinds by power,
+// mis 0 / 1.  ris implies power, and an indirect ris kind has rr (R >= B plays no roulette)
+struct PtLitKind { bool indirect, mis, power, rr, list, ris; };
+static inline bool ptk_lit_kind_valid(PtLitKind k)
+{
+    return (!k.list || k.rr) && (!k.rr || k.indirect) && (!k.mis || k.indirect) && (!k.ris || (k.power && k.rr == k.indirect));
+}
+static inline int ptk_lit_kind_index(PtLitKind k) { return k.indirect | k.mis << 1 | k.power << 2 | k.rr << 3 | k.list << 4 | k.ris << 5; }   // a table's index
+#define PT_LIT_KIND_INDICES 64
 // THE launch of a lit render, whatever its kind: `a` is the largest block, and each instantiation is passed its own, sliced from it
 // (PtDirectPowerParams is made of a.d, a.cdf and a.tri_q).  LBVH (m.bvh): the kind's kernel on a persistent grid of at most bvh_blocks
 // = CUs x ptk_lit_bvh_blocks_per_cu(k) workgroups -- the occupancy of the kind's OWN <true, 3> instantiation with the trace kernel's
 // LDS: the direct kernels run at four waves per SIMD, the indirect ones at three, so ptk_query_bvh_blocks_per_cu's premise (five) holds
 // for none.  Brute force: one wave per 64 items; the roulette and list kinds one wave per PT_RR_RUN (pt_constants.h) consecutive
 // items, which refills its dead lanes from its run
-hipError_t ptk_lit(const PtIndirectListParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s);
+hipError_t ptk_lit(const PtIndirectRisParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s);
 int ptk_lit_bvh_blocks_per_cu(PtLitKind k);
 // the fold of a list launch: one lane per (slot j, channel) folds rad[f][j], f = 0 .. frame_count - 1 ascending, into fb[the slot's
 // pixel] with the slot's own frame numbers (pt_fold_frame); pixels that are not listed are neither read nor written

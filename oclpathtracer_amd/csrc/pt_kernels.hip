@@ -3113,6 +3113,8 @@ PTK_DEV void pt_direct_surface(const PtDirectParams& D, const f3& o, const f3& d
 // the 24-bit uniform u, the entry with cdf[i] <= x < cdf[i + 1] by binary search -- and total / q_i stands where (float)nl stands in the
 // weight; an empty table (total = 0) contributes nothing.  The search's temporaries die before the light's record is gathered.
 // POWER = false is the uniform choice, the parent's code.
+// WI_ONLY (pt_ris_light's candidates): o returns wi and d is not written -- the ray (o, d) is formed from wi by the caller, for the kept
+// candidate alone, with the two statements below.
 PTK_DEV float pt_light_table_inv(const uint64_t* cdf, int nl, float r0, unsigned& li)
 {
     const uint64_t total = cdf[nl];
@@ -3130,7 +3132,7 @@ PTK_DEV float pt_light_table_inv(const uint64_t* cdf, int nl, float r0, unsigned
     return (float)total / (float)(cdf[lo + 1u] - cdf[lo]);   // >= 1
 }
 
-template <bool MIS = false, bool POWER = false>
+template <bool MIS = false, bool POWER = false, bool WI_ONLY = false>
 PTK_DEV bool pt_direct_light(const PtDirectParams& D, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed, f3& c, f3& o, f3& d,
                              float& tl, const int32_t* counts = nullptr, bool weigh = false, const uint64_t* cdf = nullptr)
 {
@@ -3195,10 +3197,56 @@ PTK_DEV bool pt_direct_light(const PtDirectParams& D, const f3& p, const f3& n, 
         }
     }
     c = mk3((f.x * (emj.x * 3.0f)) * w, (f.y * (emj.y * 3.0f)) * w, (f.z * (emj.z * 3.0f)) * w);
-    o = add3(p, scale3(wi, 0.01f));   // :257
-    d = normalize3(wi);
+    if constexpr (WI_ONLY) {
+        o = wi;
+    } else {
+        o = add3(p, scale3(wi, 0.01f));   // :257
+        d = normalize3(wi);
+    }
     tl = dist - 0.02f;
     tl = tl < 1e20f ? tl : 1e20f;
+    return true;
+}
+
+// Resampled light sample (RIS; include/pt_shim.h states every step): M candidates, each pt_direct_light<MIS, true>'s -- its three
+// uniforms, its table lookup, its c with the balance factor where the parent has it -- and from the second on one uniform r more, drawn
+// whether or not the candidate contributes: 4M - 1 uniforms.  A candidate that contributes with s = max channel of c > 0 (false for
+// NaN) adds s to wsum and is kept iff none is held or r * wsum < s, a reservoir of one.  True when one is held: c = c_sel * ((wsum / M)
+// / s_sel), two generic IEEE divisions, and (o, d, tl) are its ray -- the caller casts it as the parent casts its own.  False: nothing
+// is written.  M is wave-uniform, so the lanes of a wave evaluate their candidates in step; the reservoir -- the kept c, wi (the ray is
+// formed from it after the loop: nine registers, not twelve), tl and s, and wsum -- dies here: what a lane holds across the search is
+// the parent's c, o, d, tl.  M = 1: no r, wsum = s, g = 1.0f.
+template <bool MIS>
+PTK_DEV bool pt_ris_light(const PtDirectParams& D, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed, f3& c, f3& o, f3& d,
+                          float& tl, const int32_t* counts, bool weigh, const uint64_t* cdf, int M)
+{
+    float wsum = 0.0f, ssel = 0.0f;
+    bool have = false;
+    f3 cs = mk3(0.0f, 0.0f, 0.0f), ws = cs;
+    float ts = 0.0f;
+    for (int m = 0; m < M; ++m) {
+        f3 cm = mk3(0.0f, 0.0f, 0.0f), wm = cm, unused = cm;
+        float tm = 0.0f;
+        const bool ok = pt_direct_light<MIS, true, true>(D, p, n, wo, mid, seed, cm, wm, unused, tm, counts, weigh, cdf);
+        float r = 0.0f;
+        if (m >= 1) r = pt_random_float(seed);
+        if (ok) {
+            const float s = pt_max(cm.x, pt_max(cm.y, cm.z));
+            if (s > 0.0f) {
+                wsum = wsum + s;
+                if (!have || r * wsum < s) {
+                    cs = cm; ws = wm; ts = tm; ssel = s;
+                    have = true;
+                }
+            }
+        }
+    }
+    if (!have) return false;
+    const float g = (wsum / (float)M) / ssel;
+    c = mk3(cs.x * g, cs.y * g, cs.z * g);
+    o = add3(p, scale3(ws, 0.01f));   // :257
+    d = normalize3(ws);
+    tl = ts;
     return true;
 }
 
@@ -3214,13 +3262,15 @@ PTK_DEV f3 pt_direct_radiance(const PtDirectParams& D, unsigned mid, const f3& S
 // contributes, all in step (pt_ao_kernel's shape); a light sample no lane of the wave casts a ray for costs no search.
 // POWER: the light is chosen through pt_light_table's cdf (pt_direct_light<false, true>); such an instantiation takes
 // PtDirectPowerParams, the others PtDirectParams as before
-template <bool POWER> using PtDirectArgs = std::conditional_t<POWER, PtDirectPowerParams, PtDirectParams>;
+// RIS (pt_render_direct_ris; POWER only): the light sample is pt_ris_light's; such an instantiation takes PtDirectRisParams
+template <bool POWER, bool RIS = false> using PtDirectArgs = std::conditional_t<RIS, PtDirectRisParams, std::conditional_t<POWER, PtDirectPowerParams, PtDirectParams>>;
 PTK_DEV const uint64_t* pt_light_cdf(const PtDirectParams&) { return nullptr; }
 PTK_DEV const uint64_t* pt_light_cdf(const PtDirectPowerParams& D) { return D.cdf; }
 
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool POWER = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDirectArgs<POWER> D)
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool POWER = false, bool RIS = false>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDirectArgs<POWER, RIS> D)
 {
+    static_assert(POWER || !RIS, "resampling draws its candidates from the light table");
     const PtTraceParams& P = D.t;
     const unsigned lane = pt_lane_id();
     const int ntri = P.ntri;
@@ -3247,7 +3297,8 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDir
             f3 c = mk3(0.0f, 0.0f, 0.0f);
             float tlim = 0.0f;
             bool cast = false;
-            if constexpr (POWER) { if (hit) cast = pt_direct_light<false, true>(D, p, n, wo, mid, seed, c, o, d, tlim, nullptr, false, pt_light_cdf(D)); }
+            if constexpr (RIS) { if (hit) cast = pt_ris_light<false>(D, p, n, wo, mid, seed, c, o, d, tlim, nullptr, false, D.cdf, D.M); }
+            else if constexpr (POWER) { if (hit) cast = pt_direct_light<false, true>(D, p, n, wo, mid, seed, c, o, d, tlim, nullptr, false, pt_light_cdf(D)); }
             else if (hit) cast = pt_direct_light(D, p, n, wo, mid, seed, c, o, d, tlim);
             const bool live = cast & (tlim > 0.0f);
             bool occluded = false;
@@ -3268,10 +3319,10 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDir
 // LBVH (pt_bvh_drive): one item = one sample; the lane runs its searches one after the other -- the primary ray's closest search,
 // then the any-hit searches of the light samples that contribute -- and is free when the sample is stored.  A light sample that
 // does not contribute is passed over inside next_ray: it costs the lane no refill
-template <bool POWER = false>
+template <bool POWER = false, bool RIS = false>
 struct PtDirectWork {
     static constexpr bool ANY = true;
-    const PtDirectArgs<POWER>& D;
+    const PtDirectArgs<POWER, RIS>& D;
     unsigned n;
     int k;           // the current ray: -1 = the primary, 0 .. K-1 = the shadow ray of light sample k
     unsigned item, mid;
@@ -3300,7 +3351,8 @@ struct PtDirectWork {
         }
         if (D.nl > 0)
             while (++k < D.K) {
-                if constexpr (POWER) { if (pt_direct_light<false, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, nullptr, false, pt_light_cdf(D))) return true; }
+                if constexpr (RIS) { if (pt_ris_light<false>(D, p, nrm, wo, mid, seed, c, o, d, tl, nullptr, false, D.cdf, D.M)) return true; }
+                else if constexpr (POWER) { if (pt_direct_light<false, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, nullptr, false, pt_light_cdf(D))) return true; }
                 else if (pt_direct_light(D, p, nrm, wo, mid, seed, c, o, d, tl)) return true;
             }
         pt_direct_store(D, item, pt_direct_radiance(D, mid, S));
@@ -3317,12 +3369,12 @@ struct PtDirectWork {
 // against ambient occlusion's 16, and at five waves (96 VGPRs) the kernel spills 19 of them (profiles/direct/kernel_resources.txt).
 // Its persistent grid is therefore its own figure, ptk_lit_bvh_blocks_per_cu of its kind, not ptk_query_bvh_blocks_per_cu
 #define PT_DIRECT_BVH_WAVES 4
-template <bool DET_BOUNDED, int BIGQ, bool POWER = false>
+template <bool DET_BOUNDED, int BIGQ, bool POWER = false, bool RIS = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_DIRECT_BVH_WAVES, PT_DIRECT_BVH_WAVES)))
-void pt_direct_bvh_kernel(const PtDirectArgs<POWER> D)
+void pt_direct_bvh_kernel(const PtDirectArgs<POWER, RIS> D)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtDirectWork<POWER> W = { D, D.nitems, -1, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0 };
+    PtDirectWork<POWER, RIS> W = { D, D.nitems, -1, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0 };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(D.t, W);
 }
 
@@ -3543,8 +3595,8 @@ PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f
 }
 
 // the parameter block of an instantiation, and its counts (none without MIS)
-template <bool MIS, bool POWER = false, bool RR = false, bool LIST = false>
-using PtIndirectArgs = std::conditional_t<LIST, PtIndirectListParams, std::conditional_t<RR, PtIndirectRrParams, std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>>>;
+template <bool MIS, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false>
+using PtIndirectArgs = std::conditional_t<RIS, PtIndirectRisParams, std::conditional_t<LIST, PtIndirectListParams, std::conditional_t<RR, PtIndirectRrParams, std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>>>>;
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectParams&) { return nullptr; }
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectMisParams& I) { return I.counts; }
 PTK_DEV const uint64_t* pt_light_cdf(const PtIndirectParams&) { return nullptr; }
@@ -3713,9 +3765,21 @@ PTK_DEV void pt_list_item_begin(const PtIndirectListParams& I, unsigned item, un
 // exhausted), and every live lane either ends its path in it or raises its bounce, which is below B; every refill raises `next`,
 // which is at most `end`.  So a wave runs at most PT_RR_RUN * B iterations.  No spin, no persistent grid.
 // LIST (pt_render_indirect_pixels): the items are frames of a list of pixels; only the sample's start differs (pt_list_item_begin)
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS, bool POWER, bool LIST = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST> I)
+// RIS (pt_render_indirect_ris, pt_render_indirect_pixels_ris; POWER only): the light sample is pt_ris_light's -- the candidates of the
+// wave's lanes in step, then the one shadow search, none when no lane holds a candidate; the block is PtIndirectRisParams
+// The RIS forms carry an occupancy pin, the parents' six waves per SIMD (80 VGPRs): unpinned the compiler takes 81-82 registers for a
+// loop it holds in 80 without a spill.  The tiled MIS forms are the exception: at six waves they spill 3 VGPRs (16 bytes of scratch),
+// so they are pinned to the five they need (85 VGPRs, no scratch); profiles/ris/kernel_resources.txt has both figures.  A pin of 0 is
+// no pin: the attribute is not emitted, and the RIS = false instantiations are the parent's code
+#ifndef PT_RR_RIS_TILED_MIS_WAVES   // (tools/kernel_resources.sh -DPT_RR_RIS_TILED_MIS_WAVES=6 reads the other choice)
+#define PT_RR_RIS_TILED_MIS_WAVES 5
+#endif
+template <bool RIS, int LDS_TABLE, bool MIS> inline constexpr int PT_RR_WAVES_PIN = !RIS ? 0 : (LDS_TABLE == 2 && MIS) ? PT_RR_RIS_TILED_MIS_WAVES : 6;
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS, bool POWER, bool LIST = false, bool RIS = false>
+__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_RR_WAVES_PIN<RIS, LDS_TABLE, MIS>)))
+void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS> I)
 {
+    static_assert(POWER || !RIS, "resampling draws its candidates from the light table");
     static_assert(PT_RR_RUN % 64 == 0 && PT_RR_RUN >= 64, "a run is whole waves of items");
     const PtDirectParams& D = I.d;
     const PtTraceParams& P = D.t;
@@ -3774,7 +3838,8 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_rr_kernel(const 
                 f3 c = mk3(0.0f, 0.0f, 0.0f);
                 float tlim = 0.0f;
                 bool cast = false;
-                if constexpr (POWER) { if (hit) cast = pt_direct_light<MIS, true>(D, p, n, wo, mid, seed, c, o, d, tlim, I.counts, i < I.B - 1, I.cdf); }
+                if constexpr (RIS) { if (hit) cast = pt_ris_light<MIS>(D, p, n, wo, mid, seed, c, o, d, tlim, I.counts, i < I.B - 1, I.cdf, I.M); }
+                else if constexpr (POWER) { if (hit) cast = pt_direct_light<MIS, true>(D, p, n, wo, mid, seed, c, o, d, tlim, I.counts, i < I.B - 1, I.cdf); }
                 else if (hit) cast = pt_direct_light<MIS>(D, p, n, wo, mid, seed, c, o, d, tlim, I.counts, i < I.B - 1);
                 const bool live = cast & (tlim > 0.0f);
                 bool occluded = false;
@@ -3809,11 +3874,12 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_rr_kernel(const 
 // wo is the negated incoming direction, which the shadow rays overwrite in d, so it is kept; o is dead while p is live.
 // With MIS a lane also holds pb from the BRDF sample to the next closest hit, across that search: 34 registers.  The counts and the
 // emitter's record are gathered where they are used, as the materials are.
-template <bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false>
+template <bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false>
 struct PtIndirectWork {
     static_assert(RR || !LIST, "a list launch is a roulette launch");
+    static_assert(!RIS || (POWER && RR), "resampling comes with the light table, in the roulette family");
     static constexpr bool ANY = true;
-    const PtIndirectArgs<MIS, POWER, RR, LIST>& I;
+    const PtIndirectArgs<MIS, POWER, RR, LIST, RIS>& I;
     unsigned n;
     int k;           // the current ray: -1 = the vertex's closest search, 0 .. K-1 = the shadow ray of light sample k
     int bounce;      // loop index i of traceRays (:229)
@@ -3852,7 +3918,8 @@ struct PtIndirectWork {
         }
         if (D.nl > 0) {
             while (++k < D.K) {
-                if constexpr (POWER) { if (pt_direct_light<MIS, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, pt_indirect_counts(I), bounce < I.B - 1, pt_light_cdf(I))) return true; }
+                if constexpr (RIS) { if (pt_ris_light<MIS>(D, p, nrm, wo, mid, seed, c, o, d, tl, I.counts, bounce < I.B - 1, I.cdf, I.M)) return true; }
+                else if constexpr (POWER) { if (pt_direct_light<MIS, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, pt_indirect_counts(I), bounce < I.B - 1, pt_light_cdf(I))) return true; }
                 else if (pt_direct_light<MIS>(D, p, nrm, wo, mid, seed, c, o, d, tl, pt_indirect_counts(I), bounce < I.B - 1)) return true;
             }
             pt_indirect_lit(D, mask, S, L);
@@ -3889,12 +3956,13 @@ struct PtIndirectWork {
 // scalar, the roulette's r, s and q die where they are used (profiles/roulette/kernel_resources.txt has the compiler's figures)
 // The LIST = true instantiations (pt_render_indirect_pixels) take PtIndirectListParams: the slot is loaded and dies in begin(), the
 // pointer and the offset are scalar (profiles/adaptive/kernel_resources.txt)
-template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false>
+// The RIS = true instantiations take PtIndirectRisParams: M is scalar, the reservoir lives inside pt_ris_light (profiles/ris/kernel_resources.txt)
+template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_INDIRECT_BVH_WAVES, PT_INDIRECT_BVH_WAVES)))
-void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER, RR, LIST> I)
+void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER, RR, LIST, RIS> I)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtIndirectWork<MIS, POWER, RR, LIST> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
+    PtIndirectWork<MIS, POWER, RR, LIST, RIS> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(I.d.t, W);
 }
 
@@ -4387,40 +4455,46 @@ struct PtAoFamily {
     template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table() { return pt_ao_kernel<DB, LDS_TABLE, QUADS>; }
 };
 // a kind of lit render (PtLitKind); RR: the table kernels are the refilling ones, a wave of which owns PT_RR_RUN items
-template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST> struct PtLitFamily {
-    using Params = std::conditional_t<INDIRECT, PtIndirectArgs<MIS, POWER, RR, LIST>, PtDirectArgs<POWER>>;
+template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST, bool RIS = false> struct PtLitFamily {
+    using Params = std::conditional_t<INDIRECT, PtIndirectArgs<MIS, POWER, RR, LIST, RIS>, PtDirectArgs<POWER, RIS>>;
     static constexpr unsigned run = RR ? PT_RR_RUN : 64;
     template <bool DB, int BIGQ> static constexpr auto bvh()
     {
-        if constexpr (INDIRECT) return pt_indirect_bvh_kernel<DB, BIGQ, MIS, POWER, RR, LIST>;
-        else return pt_direct_bvh_kernel<DB, BIGQ, POWER>;
+        if constexpr (INDIRECT) return pt_indirect_bvh_kernel<DB, BIGQ, MIS, POWER, RR, LIST, RIS>;
+        else return pt_direct_bvh_kernel<DB, BIGQ, POWER, RIS>;
     }
     template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table()
     {
-        if constexpr (RR) return pt_indirect_rr_kernel<DB, LDS_TABLE, QUADS, MIS, POWER, LIST>;
+        if constexpr (RR) return pt_indirect_rr_kernel<DB, LDS_TABLE, QUADS, MIS, POWER, LIST, RIS>;
         else if constexpr (INDIRECT) return pt_indirect_kernel<DB, LDS_TABLE, QUADS, MIS, POWER>;
-        else return pt_direct_kernel<DB, LDS_TABLE, QUADS, POWER>;
+        else return pt_direct_kernel<DB, LDS_TABLE, QUADS, POWER, RIS>;
     }
     // the instantiations' own block, sliced from the largest (every indirect block is a base of it; direct by power: direct's and the table)
-    static Params params(const PtIndirectListParams& a)
+    static Params params(const PtIndirectRisParams& a)
     {
         if constexpr (INDIRECT) return a;
         else if constexpr (!POWER) return a.d;
         else {
-            PtDirectPowerParams p;
+            Params p;
             __builtin_memset(&p, 0, sizeof p);
             static_cast<PtDirectParams&>(p) = a.d;
             p.cdf = a.cdf;
             p.tri_q = a.tri_q;
+            if constexpr (RIS) p.M = a.M;
             return p;
         }
     }
 };
-// fn(the family of kind k): the 14 valid kinds and no other -- direct illumination has neither MIS nor roulette, a list is played with roulette
+// fn(the family of kind k): the 14 valid kinds without ris, the 5 with it and no other -- direct illumination has neither MIS nor roulette, a
+// list is played with roulette, resampling comes by power and, indirect, in the roulette family
 template <class Fn> static auto pt_lit_family(PtLitKind k, Fn fn)
 {
     auto estimator = [&](auto mis, auto power) {
         constexpr bool M = decltype(mis)::value, P = decltype(power)::value;
+        if constexpr (P) if (k.ris) {
+            if constexpr (!M) if (!k.indirect) return fn(PtLitFamily<false, false, true, false, false, true>());
+            return k.list ? fn(PtLitFamily<true, M, true, true, true, true>()) : fn(PtLitFamily<true, M, true, true, false, true>());
+        }
         if constexpr (!M) if (!k.indirect) return fn(PtLitFamily<false, false, P, false, false>());
         return k.list ? fn(PtLitFamily<true, M, P, true, true>()) : k.rr ? fn(PtLitFamily<true, M, P, true, false>()) : fn(PtLitFamily<true, M, P, false, false>());
     };
@@ -4456,7 +4530,7 @@ hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream
     return pt_launch_search(pt_choose<PtAoFamily>(m, a.t.ntri), a, a.t.ntri, a.nitems, 64u, m.bvh, bvh_blocks, s);
 }
 
-hipError_t ptk_lit(const PtIndirectListParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s)
+hipError_t ptk_lit(const PtIndirectRisParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s)
 {
     if (a.d.nitems == 0) return hipSuccess;
     return pt_lit_family(k, [&](auto f) {

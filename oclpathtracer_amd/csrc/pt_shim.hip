@@ -358,7 +358,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->bvh_blocks_per_cu = ptk_trace_bvh_blocks_per_cu();
     d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
     for (int i = 0; i < PT_LIT_KIND_INDICES; ++i) {
-        const PtLitKind k = { (i & 1) != 0, (i & 2) != 0, (i & 4) != 0, (i & 8) != 0, (i & 16) != 0 };
+        const PtLitKind k = { (i & 1) != 0, (i & 2) != 0, (i & 4) != 0, (i & 8) != 0, (i & 16) != 0, (i & 32) != 0 };
         if (ptk_lit_kind_valid(k)) d->lit_bvh_blocks_per_cu[ptk_lit_kind_index(k)] = ptk_lit_bvh_blocks_per_cu(k);
     }
     *out = d;
@@ -1784,10 +1784,12 @@ static_assert(sizeof(pt_direct_params) == 64, "pt_direct_params layout");
 static_assert(sizeof(pt_indirect_params) == 64, "pt_indirect_params layout");
 
 static_assert(sizeof(pt_roulette) == 16, "pt_roulette layout");
+static_assert(sizeof(pt_ris) == 16, "pt_ris layout");
 static_assert(sizeof(pt_adaptive_rule) == 32 && sizeof(pt_pixel_slot) == 8 && sizeof(pt_pixel_slot) == sizeof(uint2), "adaptive record layout");
 
 // ONE lit call, as its entry point describes it: pt_render_direct, pt_render_indirect, pt_render_indirect_mis, the two _power entry
-// points, pt_render_indirect_rr and pt_render_indirect_pixels each fill one and hand it to render_lit -- one validation, one chunk loop
+// points, pt_render_indirect_rr, pt_render_indirect_pixels and the three _ris entry points each fill one and hand it to render_lit -- one
+// validation, one chunk loop
 struct PtLitCall {
     PtLitKind kind;             // which kernels (pt_kernels.h); what follows is read as far as the kind says
     pt_buffer_t triangles, materials, lights, samples, framebuffer;
@@ -1798,6 +1800,7 @@ struct PtLitCall {
     pt_direct_params a;         // the fields the parameter blocks share (each entry point has looked at its own reserved ones)
     int max_bounces;            // kind.indirect: the depth of the paths
     pt_roulette rr;             // kind.rr: the roulette (roulette_args has checked it)
+    int candidates;             // kind.ris: M (ris_args has checked it)
     const pt_camera* cam;
     pt_event_t ev;
     const char* what;           // the message for a field out of range
@@ -1867,8 +1870,9 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     PtSearch search;
     if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
     if ((rc = event_begin(d, c.ev))) return rc;
-    PtIndirectListParams ip;   // (every kind's block is a base of it, or made of it: ptk_lit)
+    PtIndirectRisParams ip;   // (every kind's block is a base of it, or made of it: ptk_lit)
     memset(&ip, 0, sizeof ip);
+    ip.M = c.candidates;       // (zero without resampling)
     ip.B = c.max_bounces;
     ip.R = c.rr.first_bounce;   // (zeros without roulette)
     ip.cap = c.rr.max_survival;
@@ -1960,7 +1964,7 @@ static int roulette_args(int mis, const pt_roulette* roulette, pt_buffer_t cdf, 
 extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
                                 pt_buffer_t framebuffer, const pt_direct_params* params, const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ false, false, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    PtLitCall c = lit_call({ false, false, false, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
     int rc = use_device(d);
     if (rc || (rc = direct_block(params, c))) return rc;
     return render_lit(d, c);
@@ -1970,7 +1974,7 @@ extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_
 extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
                                   pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, false, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    PtLitCall c = lit_call({ true, false, false, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
     int rc = use_device(d);
     if (rc || (rc = indirect_block(params, c))) return rc;
     return render_lit(d, c);
@@ -1980,7 +1984,7 @@ extern "C" int pt_render_indirect_mis(pt_device_t d, pt_buffer_t triangles, pt_b
                                       pt_buffer_t samples, pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam,
                                       pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, true, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    PtLitCall c = lit_call({ true, true, false, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
     c.light_counts = light_counts;
     int rc = use_device(d);
     if (rc || (rc = indirect_block(params, c))) return rc;
@@ -1992,7 +1996,7 @@ extern "C" int pt_render_direct_power(pt_device_t d, pt_buffer_t triangles, pt_b
                                       pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params* params,
                                       const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ false, false, true, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    PtLitCall c = lit_call({ false, false, true, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
     c.cdf = cdf; c.tri_q = tri_q;
     int rc = use_device(d);
     if (rc || (rc = direct_block(params, c))) return rc;
@@ -2004,7 +2008,7 @@ extern "C" int pt_render_indirect_power(pt_device_t d, pt_buffer_t triangles, pt
                                         pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
 {
     if (mis != 0 && mis != 1) return fail(PT_ERR_INVALID, "mis must be 0 or 1");
-    PtLitCall c = lit_call({ true, mis != 0, true, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    PtLitCall c = lit_call({ true, mis != 0, true, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
     c.light_counts = mis ? light_counts : nullptr;
     c.cdf = cdf; c.tri_q = tri_q;
     int rc = use_device(d);
@@ -2018,7 +2022,7 @@ extern "C" int pt_render_indirect_rr(pt_device_t d, pt_buffer_t triangles, pt_bu
                                      pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
                                      const pt_indirect_params* params, const pt_roulette* roulette, const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, mis != 0, cdf || tri_q, true, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    PtLitCall c = lit_call({ true, mis != 0, cdf || tri_q, true, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
     c.light_counts = mis ? light_counts : nullptr;
     c.cdf = cdf; c.tri_q = tri_q;
     int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
@@ -2031,12 +2035,63 @@ extern "C" int pt_render_indirect_pixels(pt_device_t d, pt_buffer_t triangles, p
                                          pt_buffer_t list, uint32_t num_listed, const pt_indirect_params* params, const pt_roulette* roulette,
                                          const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, mis != 0, cdf || tri_q, true, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    PtLitCall c = lit_call({ true, mis != 0, cdf || tri_q, true, true, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
     c.light_counts = mis ? light_counts : nullptr;
     c.cdf = cdf; c.tri_q = tri_q;
     c.list = list; c.num_listed = num_listed;
     int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
     if (rc || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
+    return render_lit(d, c);
+}
+
+// ---- resampled light sampling (include/pt_shim.h) ----------------------------------------------------------------------------------
+// what the three _ris entry points check before anything else: the block, M, the reserved words, the table (there is no uniform form)
+static int ris_args(const pt_ris* ris, pt_buffer_t cdf, pt_buffer_t tri_q, int num_lights, PtLitCall& c)
+{
+    if (!ris) return fail(PT_ERR_INVALID, "ris == NULL");
+    const pt_ris r = *ris;
+    if (r.candidates < 1 || r.candidates > 32) return fail(PT_ERR_INVALID, "candidates must lie in 1..32");
+    if (r.reserved[0] != 0 || r.reserved[1] != 0 || r.reserved[2] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    if (num_lights > 0 && !(cdf && tri_q)) return fail(PT_ERR_INVALID, "resampling needs the light table: cdf AND tri_q (pt_light_table)");
+    c.candidates = r.candidates;
+    return PT_OK;
+}
+
+extern "C" int pt_render_direct_ris(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t cdf,
+                                    pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params* params,
+                                    const pt_ris* ris, const pt_camera* cam, pt_event_t ev)
+{
+    PtLitCall c = lit_call({ false, false, true, false, false, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    c.cdf = cdf; c.tri_q = tri_q;
+    int rc = ris_args(ris, cdf, tri_q, params ? params->num_lights : 0, c);
+    if (rc || (rc = use_device(d)) || (rc = direct_block(params, c))) return rc;
+    return render_lit(d, c);
+}
+
+extern "C" int pt_render_indirect_ris(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
+                                      pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
+                                      const pt_indirect_params* params, const pt_roulette* roulette, const pt_ris* ris, const pt_camera* cam,
+                                      pt_event_t ev)
+{
+    PtLitCall c = lit_call({ true, mis != 0, true, true, false, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    c.light_counts = mis ? light_counts : nullptr;
+    c.cdf = cdf; c.tri_q = tri_q;
+    int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
+    if (rc || (rc = ris_args(ris, cdf, tri_q, params ? params->num_lights : 0, c)) || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
+    return render_lit(d, c);
+}
+
+extern "C" int pt_render_indirect_pixels_ris(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
+                                             pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples,
+                                             pt_buffer_t framebuffer, pt_buffer_t list, uint32_t num_listed, const pt_indirect_params* params,
+                                             const pt_roulette* roulette, const pt_ris* ris, const pt_camera* cam, pt_event_t ev)
+{
+    PtLitCall c = lit_call({ true, mis != 0, true, true, true, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    c.light_counts = mis ? light_counts : nullptr;
+    c.cdf = cdf; c.tri_q = tri_q;
+    c.list = list; c.num_listed = num_listed;
+    int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
+    if (rc || (rc = ris_args(ris, cdf, tri_q, params ? params->num_lights : 0, c)) || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
     return render_lit(d, c);
 }
 

@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power] | --only IndirectIllumination [--mis] [--lights power] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]]] [--noise]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power [--candidates M]] | --only IndirectIllumination [--mis] [--lights power [--candidates M]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]]] [--noise]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <chrono>
 #include <cmath>
@@ -119,6 +119,7 @@ struct Options {
     int deviceIdx = 0, dim = 512, frames = 10000;
     bool batch = true, mis = false;   // mis: IndirectIllumination through pt_render_indirect_mis
     bool power = false;               // --lights power: DirectIllumination / IndirectIllumination choose their lights by power
+    int candidates = 0;               // --candidates M (with --lights power): resampled light samples through the _ris entry points (0 = none)
     int rrFirst = 0;                  // --roulette R[,cap]: IndirectIllumination through pt_render_indirect_rr (0 = no roulette)
     float rrCap = 0.95f;
     double adaptTol = -1.0;           // --adaptive TOL[,MIN[,MAX]]: IndirectIllumination renders MIN frames, then only the pixels still noisy (< 0 = off)
@@ -376,6 +377,8 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
 // pt_render_indirect_power, the table made by pt_light_table) and the file's name ends in _power.ppm (_mis_power.ppm with --mis).
 // With --roulette R[,cap] IndirectIllumination goes through pt_render_indirect_rr -- Russian roulette from vertex R on with survival at
 // most cap (0.95 unless given), under --mis and --lights power as they are set -- and the file's name gains _rr before .ppm.
+// With --lights power --candidates M every light sample is resampled from M candidates (pt_render_direct_ris, pt_render_indirect_ris,
+// which plays the roulette of --roulette or none, and pt_render_indirect_pixels_ris under --adaptive) and the file's name gains _risM.
 // With --noise either case renders in calls of at most as many frames as the workspace holds, takes the samples' moments after each
 // (pt_sample_moments) and prints one more line, after the case's own: the summary of pt_moments_resolve.  The image is the same.
 // With --adaptive TOL[,MIN[,MAX]] IndirectIllumination renders MIN frames (16 unless given) as above, then pass by pass lists the pixels
@@ -440,6 +443,14 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     std::memset(&roulette, 0, sizeof roulette);
     roulette.first_bounce = o.rrFirst;
     roulette.max_survival = o.rrCap;
+    const bool resample = o.power && o.candidates > 0;
+    pt_ris ris;
+    std::memset(&ris, 0, sizeof ris);
+    ris.candidates = o.candidates;
+    pt_roulette none;   // no roulette: a first bounce no path reaches
+    std::memset(&none, 0, sizeof none);
+    none.first_bounce = 65535;
+    none.max_survival = 1.0f;
     pt_buffer_t lh = lights.empty() ? 0 : lBuffer.m_handle;
     if (o.power)
         IASSERT(pt_light_table(m_d->m_handle, tBuffer.m_handle, p.num_triangles, mBuffer.m_handle, p.num_materials, lh, p.num_lights, cdf.m_handle,
@@ -449,6 +460,12 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     auto render = [&](int first, int count) {
         p.frame_begin = q.frame_begin = first;
         p.frame_count = q.frame_count = count;
+        if (resample && bounces)
+            return pt_render_indirect_ris(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0, cdf.m_handle,
+                                          triq.m_handle, samples.m_handle, image.m_handle, &q, rr ? &roulette : &none, &ris, 0, 0);
+        if (resample)
+            return pt_render_direct_ris(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cdf.m_handle, triq.m_handle, samples.m_handle,
+                                        image.m_handle, &p, &ris, 0, 0);
         if (rr)
             return pt_render_indirect_rr(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0,
                                          o.power ? cdf.m_handle : 0, o.power ? triq.m_handle : 0, samples.m_handle, image.m_handle, &q, &roulette, 0, 0);
@@ -485,8 +502,7 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
         rule.floor2 = 1e-2 * 1e-2;
         rule.min_samples = (uint32_t)uniformFrames;
         rule.max_samples = (uint32_t)(o.adaptMax > 0 ? o.adaptMax : o.frames);
-        pt_roulette play = roulette;
-        if (!rr) { play.first_bounce = 65535; play.max_survival = 1.0f; }   // no roulette: a first bounce no path reaches
+        const pt_roulette play = rr ? roulette : none;
         adaptiveSamples = (unsigned long long)npix * (unsigned long long)uniformFrames;
         for (;;) {
             uint32_t header[4] = { 0, 0, 0, 0 };
@@ -501,9 +517,14 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
             for (int done = 0; done < chunk; done += hold) {
                 q.frame_begin = done;
                 q.frame_count = chunk - done < hold ? chunk - done : hold;
-                IASSERT(pt_render_indirect_pixels(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0,
-                                                  o.power ? cdf.m_handle : 0, o.power ? triq.m_handle : 0, samples.m_handle, image.m_handle,
-                                                  pixelList.m_handle, listed, &q, &play, 0, 0) == PT_OK);
+                if (resample)
+                    IASSERT(pt_render_indirect_pixels_ris(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0,
+                                                          cdf.m_handle, triq.m_handle, samples.m_handle, image.m_handle, pixelList.m_handle, listed,
+                                                          &q, &play, &ris, 0, 0) == PT_OK);
+                else
+                    IASSERT(pt_render_indirect_pixels(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0,
+                                                      o.power ? cdf.m_handle : 0, o.power ? triq.m_handle : 0, samples.m_handle, image.m_handle,
+                                                      pixelList.m_handle, listed, &q, &play, 0, 0) == PT_OK);
                 IASSERT(pt_sample_moments_pixels(m_d->m_handle, samples.m_handle, moments.m_handle, pixelList.m_handle, listed, q.frame_count, 0) == PT_OK);
             }
             adaptiveSamples += (unsigned long long)listed * (unsigned long long)chunk;
@@ -514,14 +535,16 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     rgb.read(h.data(), 3 * npix);
     DeviceUtils::waitForCompletion(m_d);
     double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    char risText[48] = "";
+    if (resample) std::snprintf(risText, sizeof risText, " (%d candidates per light sample)", o.candidates);
     if (bounces) {
         char rrText[64] = "";
         if (rr) std::snprintf(rrText, sizeof rrText, " (roulette from %d, at most %g)", o.rrFirst, (double)o.rrCap);
-        std::printf("IndirectIllumination%s%s%s: %d x %d x %d frames, %d bounces, K = 1, %d lights in %.3f s\n", mis ? " (MIS)" : "",
-                    o.power ? " (lights by power)" : "", rrText, dimension, dimension, o.frames, bounces, (int)lights.size(), secs);
+        std::printf("IndirectIllumination%s%s%s%s: %d x %d x %d frames, %d bounces, K = 1, %d lights in %.3f s\n", mis ? " (MIS)" : "",
+                    o.power ? " (lights by power)" : "", risText, rrText, dimension, dimension, o.frames, bounces, (int)lights.size(), secs);
     }
     else
-        std::printf("DirectIllumination%s: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", o.power ? " (lights by power)" : "", dimension, dimension,
+        std::printf("DirectIllumination%s%s: %d x %d x %d frames, K = 4, %d lights in %.3f s\n", o.power ? " (lights by power)" : "", risText, dimension, dimension,
                     o.frames, (int)lights.size(), secs);
     if (adaptive)
         std::printf("adaptive: tolerance %g min %d max %d passes [%s] samples %llu\n", o.adaptTol, uniformFrames, o.adaptMax > 0 ? o.adaptMax : o.frames,
@@ -543,6 +566,7 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     if (mis && std::strlen(path) + 5 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_mis.ppm");
     if (o.power && std::strlen(path) + 7 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_power.ppm");
     if (rr && std::strlen(path) + 4 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_rr.ppm");
+    if (resample && std::strlen(path) + 8 < sizeof path) std::snprintf(path + std::strlen(path) - 4, 12, "_ris%d.ppm", o.candidates);
     if (adaptive && std::strlen(path) + 10 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_adaptive.ppm");
     FILE* fp = std::fopen(path, "w");
     IASSERT(fp != 0);
@@ -591,6 +615,10 @@ int main(int argc, char** argv)
                 return 2;
             }
         }
+        else if (a == "--candidates") {
+            o.candidates = std::atoi(next());
+            if (o.candidates < 1 || o.candidates > 32) { std::fprintf(stderr, "--candidates takes M in 1..32\n"); return 2; }
+        }
         else if (a == "--lights") {
             const std::string v = next();
             if (v != "uniform" && v != "power") { std::fprintf(stderr, "--lights takes uniform or power\n"); return 2; }
@@ -599,6 +627,7 @@ int main(int argc, char** argv)
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (o.dim < 1 || o.frames < 0) { std::fprintf(stderr, "bad --dim/--frames\n"); return 2; }
+    if (o.candidates > 0 && !o.power) { std::fprintf(stderr, "--candidates needs --lights power (the candidates are drawn from the light table)\n"); return 2; }
     struct { const char* name; int kind; } tests[] = { { "initialize", 0 }, { "deviceInfo", 1 }, { "MemoryAllocation", 2 }, { "writeRead", 3 },
                                                        { "getHostPtr", 4 }, { "kernelExecution", 5 }, { "RayCast", 6 },
                                                        { "AmbientOcclusion", 7 }, { "DirectIllumination", 8 }, { "IndirectIllumination", 9 } };

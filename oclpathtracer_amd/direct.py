@@ -8,6 +8,9 @@ or open.  The result is the renderer's framebuffer -- with no lights it is the r
 ``light_choice="power"`` chooses the light triangle in proportion to the power it emits instead (``pt_render_direct_power``, through a
 table built once on the device by ``pt_light_table``): the same expectation, and far less noise where the emitters differ in size
 or brightness.
+``candidates=M`` (with ``light_choice="power"``) resamples every light sample (``pt_render_direct_ris``): M candidates are drawn from the
+table, one is kept in proportion to its unshadowed contribution at the shading point, and the one shadow ray goes to it -- the same
+expectation, and far less noise where many emitters have similar power and most of them are far from, or face away from, the point.
 ``moments=True`` keeps per-pixel noise estimates beside the image: after every call the first and second moments of the samples'
 linear radiance are taken from the workspace on the device (``pt_sample_moments``), and ``variance()``, ``noise()`` and
 ``render_until()`` read them -- a variance map, an image-wide figure of 48 bytes, and a render that stops at a noise level.
@@ -58,7 +61,8 @@ class DirectRenderer:
     one prepared scene and one LBVH (``num_triangles`` / ``num_materials`` then say how many records count, and ``lights`` must
     be given).  ``lights``: the triangle indices light samples are drawn from (None: ``scene.emitters``); an empty list leaves the
     emitted light alone.  ``light_choice``: ``"uniform"`` -- every entry of the list with the same probability -- or ``"power"`` --
-    in proportion to area x emission; the renderer then owns the selection table.  ``chunk_frames`` sizes the sample workspace: that many
+    in proportion to area x emission; the renderer then owns the selection table.  ``candidates``: 1 .. 32 candidates per light sample
+    (resampled importance sampling; more than 1 needs ``light_choice="power"``; 1 makes exactly the calls of a renderer without it).  ``chunk_frames`` sizes the sample workspace: that many
     frames are traced by one launch and folded by the next.  ``stripe_rows`` / ``n_ranks`` / ``rank`` select the rows this device
     owns, as for ``Renderer``.  The search follows the device's options exactly as renders do.  ``moments``: keep per-pixel moments
     of the samples (``variance``, ``noise``, ``render_until``); the image is the same bit for bit, ``render`` issues its frames as calls
@@ -69,10 +73,11 @@ class DirectRenderer:
     def __init__(self, dev: adl.Device, triangles, materials, width: int, height: int, *, light_samples: int = 1, lights=None,
                  camera: Optional[Camera] = None, num_triangles: Optional[int] = None, num_materials: Optional[int] = None,
                  stripe_rows: int = 16, n_ranks: int = 1, rank: int = 0, chunk_frames: Optional[int] = None,
-                 light_choice: str = "uniform", moments: bool = False):
+                 light_choice: str = "uniform", moments: bool = False, candidates: int = 1):
         if light_choice not in ("uniform", "power"):
             raise ValueError('light_choice must be "uniform" or "power"')
         self.light_choice = light_choice
+        self.set_candidates(candidates)
         self.cdf = self.tri_q = None
         self.moments = bool(moments)
         self.mom = self.summary = self.noise_map = None
@@ -151,6 +156,18 @@ class DirectRenderer:
         shim.check(self._lib.pt_light_table(self.dev._h, self.tbuf._h, self.num_triangles, self.mbuf._h, self.num_materials,
                                             self._lights_h(), nl, self.cdf._h, self.tri_q._h, None))
 
+    def set_candidates(self, candidates: int, through_ris: bool = False) -> None:
+        """``candidates`` (1 .. 32) per light sample from the next render on; more than 1 needs ``light_choice="power"``.  The image of
+        another M is another image: start again at frame 0.  ``through_ris``: with ``light_choice="power"``, render through the RIS
+        entry points even with 1 candidate -- the parent's image bit for bit by the RIS kernels, which is what a measurement of their
+        cost compares (``tools/ris_rates.py``); otherwise 1 candidate makes exactly the calls of a renderer without resampling."""
+        if isinstance(candidates, bool) or int(candidates) != candidates or not 1 <= int(candidates) <= 32:
+            raise ValueError("candidates must be an integer in 1..32")
+        if (int(candidates) > 1 or through_ris) and self.light_choice != "power":
+            raise ValueError('candidates > 1 needs light_choice="power": the candidates are drawn from the light table')
+        self.candidates = int(candidates)
+        self._ris = shim.Ris(self.candidates) if self.candidates > 1 or through_ris else None
+
     def _set_camera(self, camera: Optional[Camera]) -> None:
         self._cam = Camera.struct_of(camera)   # rejected here, before anything is enqueued
         self.camera = camera
@@ -211,6 +228,10 @@ class DirectRenderer:
 
     def _call(self, p, sync) -> int:
         """the entry point's return code (a renderer with another argument list overrides this)"""
+        if self._ris is not None:
+            return self._lib.pt_render_direct_ris(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), self.cdf._h, self.tri_q._h,
+                                                  self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(self._ris), self._cam_ref(),
+                                                  _handle(sync))
         if self.light_choice == "power":
             return self._lib.pt_render_direct_power(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), self.cdf._h, self.tri_q._h,
                                                     self.samples._h, self.fb._h, ctypes.byref(p), self._cam_ref(), _handle(sync))

@@ -25,6 +25,10 @@ is unchanged while most of the searches a deep path spends on a throughput of a 
 ``light_choice`` and ``moments``; ``None`` makes exactly the calls of a renderer without it.  A ``first_bounce`` of ``max_bounces`` or more
 plays no roulette and gives the parent's image bit for bit.
 
+``candidates=M`` (with ``light_choice="power"``) resamples every light sample of every vertex as ``DirectRenderer`` does
+(``pt_render_indirect_ris``; without ``roulette`` none is played).  It composes with ``mis``, ``roulette``, ``moments`` and
+``render_adaptive``, which then renders its lists through ``pt_render_indirect_pixels_ris``.
+
 ``render_adaptive`` (with ``moments=True``) spends later frames only on the pixels that are still noisy: after a uniform start the
 device lists the pixels whose own relative standard error lies above a tolerance (``pt_adaptive_select``), renders further frames of
 the listed pixels only (``pt_render_indirect_pixels``), each from its own frame number, and counts them (``pt_sample_moments_pixels``)
@@ -110,6 +114,10 @@ class IndirectRenderer(DirectRenderer):
 
     def _call(self, p, sync) -> int:
         scene3 = (self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h())
+        if self._ris is not None:
+            rr = self._rr if self._rr is not None else shim.Roulette(65535, 1.0)   # (no roulette: a first bounce no path reaches)
+            return self._lib.pt_render_indirect_ris(*scene3, *self._estimator(), self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(rr),
+                                                    ctypes.byref(self._ris), self._cam_ref(), _handle(sync))
         if self._rr is not None:
             return self._lib.pt_render_indirect_rr(*scene3, *self._estimator(), self.samples._h, self.fb._h, ctypes.byref(p),
                                                    ctypes.byref(self._rr), self._cam_ref(), _handle(sync))
@@ -197,9 +205,12 @@ class IndirectRenderer(DirectRenderer):
             done = 0
             while done < fpp:
                 k = min(hold, fpp - done)
-                shim.check(self._lib.pt_render_indirect_pixels(
-                    self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), *self._estimator(), self.samples._h, self.fb._h,
-                    self.pixel_list._h, listed, ctypes.byref(self.params(k, done)), ctypes.byref(rr), self._cam_ref(), None))
+                head = (self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), *self._estimator(), self.samples._h, self.fb._h,
+                        self.pixel_list._h, listed, ctypes.byref(self.params(k, done)), ctypes.byref(rr))
+                if self._ris is not None:
+                    shim.check(self._lib.pt_render_indirect_pixels_ris(*head, ctypes.byref(self._ris), self._cam_ref(), None))
+                else:
+                    shim.check(self._lib.pt_render_indirect_pixels(*head, self._cam_ref(), None))
                 shim.check(self._lib.pt_sample_moments_pixels(self.dev._h, self.samples._h, self.mom._h, self.pixel_list._h, listed, k, None))
                 done += k
             rendered += listed * fpp

@@ -145,6 +145,13 @@ class Roulette(_c.Structure):
     _fields_ = [("first_bounce", _c.c_int32), ("max_survival", _c.c_float), ("reserved", _c.c_int32 * 2)]
 
 
+class Ris(_c.Structure):
+    """pt_ris (16 bytes): resampled light sampling -- candidates (M, 1 .. 32) drawn from the light table per light sample, one of which
+    is kept in proportion to its unshadowed contribution; reserved must be 0."""
+
+    _fields_ = [("candidates", _c.c_int32), ("reserved", _c.c_int32 * 3)]
+
+
 class PixelMoments(_c.Structure):
     """pt_pixel_moments (56 bytes): per channel the sum and the sum of squares of a pixel's finite samples, their number, and the
     number of samples rejected for a NaN or an infinity."""
@@ -247,6 +254,11 @@ SIGNATURES = {
     "pt_adaptive_select": (_c.c_int, [_H, _H, _c.c_uint32, _c.POINTER(AdaptiveRule), _H, _H]),
     "pt_render_indirect_pixels": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _H, _c.c_uint32, _c.POINTER(IndirectParams),
                                              _c.POINTER(Roulette), _c.POINTER(Camera), _H]),
+    "pt_render_direct_ris": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(DirectParams), _c.POINTER(Ris), _c.POINTER(Camera), _H]),
+    "pt_render_indirect_ris": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Roulette),
+                                          _c.POINTER(Ris), _c.POINTER(Camera), _H]),
+    "pt_render_indirect_pixels_ris": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _H, _c.c_uint32, _c.POINTER(IndirectParams),
+                                                 _c.POINTER(Roulette), _c.POINTER(Ris), _c.POINTER(Camera), _H]),
     "pt_sample_moments_pixels": (_c.c_int, [_H, _H, _H, _H, _c.c_uint32, _c.c_int32, _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),

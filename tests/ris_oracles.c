@@ -1,0 +1,12 @@
+/*
+ * ris_oracles.c -- the one translation unit of tests/libtest_ris_oracle.so (tests/ris_oracle.py builds it).  TEST INFRASTRUCTURE.
+ * The restatements ris_oracle.c builds on, in tests/roulette_oracles.c's order (camera_oracle.c includes oracle/pt_oracle.c whole),
+ * then ris_oracle.c itself.
+ */
+#include "camera_oracle.c"
+#include "direct_oracle.c"
+#include "indirect_oracle.c"
+#include "mis_oracle.c"
+#include "power_oracle.c"
+#include "roulette_oracle.c"
+#include "ris_oracle.c"
