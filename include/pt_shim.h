@@ -881,6 +881,94 @@ int pt_render_indirect_pixels_ris(pt_device_t dev, pt_buffer_t triangles, pt_buf
                                   const pt_roulette* roulette, const pt_ris* ris, const pt_camera* cam /* NULL = the reference's */,
                                   pt_event_t ev);
 
+/* ---- environment lighting: an octahedral sky map ------------------------------------------------------------------------------
+ * Every estimator above gives a ray that leaves the scene the constant max(0.45, 0) (:235).  These two take the sky from a map of
+ * the caller's, look it up where a ray misses, and SAMPLE it: Ke environment samples per vertex, chosen through an integer table
+ * in proportion to what a texel emits into its solid angle, balanced against the BRDF ray as the emitter samples are.  New
+ * estimators beside the old ones, which are unchanged.  Every operation is binary32 under the renderer's arithmetic contract (dot,
+ * normalize, sqrt and the IEEE "/" as there); sgn(v) = (v < 0.0f) ? -1.0f : 1.0f (-0 and NaN give +1).
+ *
+ * THE MAP: env = float4[N * N], row-major, w ignored; N a power of two, 1 <= N <= 2048; y is up.  Texels are used as they are: a
+ * negative or NaN texel is the caller's business.  An octahedral map, because it needs no atan2 or acos: only fabs, +, *, "/", sqrt.
+ *  - The index of a coordinate c: v = ((c + 1.0f) * 0.5f) * (float)N; !(v >= 0.0f) gives 0 (a NaN, a negative); v >= (float)(N - 1)
+ *    gives N - 1 (an infinity too); otherwise (uint32)v, which the conversion defines because 0 <= v < N - 1.  Never out of range.
+ *  - Direction to texel, for ANY d: s = (fabs(d.x) + fabs(d.y)) + fabs(d.z); x = d.x / s; z = d.z / s; with d.y >= 0.0f (true for -0)
+ *    (a, b) = (x, z), otherwise -- a NaN d.y too -- (a, b) = ((1.0f - fabs(z)) * sgn(x), (1.0f - fabs(x)) * sgn(z)); texel = index(b) * N +
+ *    index(a); Le(d) is its value.  A NaN direction has v = NaN in both coordinates: texel 0.
+ *  - (a, b) to the octahedron's point: h = (1.0f - fabs(a)) - fabs(b); h >= 0.0f: P = (a, h, b), otherwise P = ((1.0f - fabs(b)) *
+ *    sgn(a), h, (1.0f - fabs(a)) * sgn(b)); P2 = dot(P, P); r = sqrt(P2); the direction is normalize(P).
+ *  - The solid angle of da db at P is da db / r^3 (the plane |x| + |y| + |z| = 1 lies at distance 1 / sqrt(3) and its area element is
+ *    sqrt(3) da db); for a direction d, r = sqrt(dot(d, d)) / s.  A direction of a texel of table weight q therefore has the density
+ *    pdf = (((float)q / (float)total) * (((float)N * (float)N) * 0.25f)) * ((r * r) * r) per solid angle.
+ *
+ * pt_env_table builds the table as pt_light_table builds its own, on its layout, tiling and scans, for the N * N texels in row-major
+ * order: texel i = row * N + col has the centre (a, b) = (((float)col + 0.5f) * (2.0f / (float)N) - 1.0f, likewise of row), P and rc =
+ * sqrt(dot(P, P)) as above, and the weight p_i = ((Le.x + Le.y) + Le.z) * (1.0f / ((rc * rc) * rc)), counted as 0 unless p_i > 0.0f &&
+ * p_i < INFINITY; pmax, q_i = max(1, (uint32)((p_i / pmax) * 65536.0f)) (0 where p_i is 0) and the uint64 prefix sum cdf[0 .. N * N]
+ * are pt_light_table's steps 3-5.  There is no second table: q_i = cdf[i + 1] - cdf[i].  cdf: pt_env_table_bytes(N) bytes (0 for an N
+ * out of range); words 0 .. N * N are the table, what lies behind is the build's scratch.  Integer, so equal to a sequential
+ * restatement bit for bit.  Behaviour is pt_light_table's; errors, before anything is enqueued: PT_ERR_INVALID for a NULL handle, N
+ * not a power of two in 1..2048, env not 16-byte or cdf not 8-byte aligned, the two overlapping, a buffer of another device;
+ * PT_ERR_RANGE for a buffer too small.
+ *
+ * pt_render_direct_env is pt_render_direct_power's estimator, pt_render_indirect_env is pt_render_indirect_rr's with mis = 1 and the
+ * choice by power (cdf and tri_q; with num_lights == 0 lights, light_counts, cdf and tri_q may all be NULL), with these changes,
+ * Ke = env_samples:
+ *  - A MISS of a ray of direction d adds Le(d) where max(0.45, 0) stood.  Direct: L = max(Le(d).c, 0).  Indirect: L.c = L.c + mask.c *
+ *    Le(d).c; at a vertex i >= 1 with Ke > 0 it is weighted, L.c = L.c + mask.c * (Le(d).c * wb), wb = pb / ((float)Ke * pdf(d) + pb) with
+ *    pdf(d) formed from the texel's q and r = sqrt(dot(d, d)) / s; q == 0 or total == 0 gives wb = 1.0f.
+ *  - AFTER THE K LIGHT SAMPLES of a vertex, Ke environment samples on the same seed, Se starting at 0.  For each:
+ *     a. r0, r1, r2 = getRandomFloat(&seed), always drawn;
+ *     b. total = cdf[N * N]; total == 0: the sample does not contribute.  Otherwise texel i by the table exactly as step 3b of the
+ *        choice by power: u = min((uint32)(r0 * 16777216.0f), 16777215u), x = (u * total) >> 24, cdf[i] <= x < cdf[i + 1]; q = cdf[i + 1]
+ *        - cdf[i]; col = i % N, row = i / N;
+ *     c. (a, b) = (((float)col + r1) * (2.0f / (float)N) - 1.0f, ((float)row + r2) * (2.0f / (float)N) - 1.0f);
+ *     d. P, P2, r as above; wi = normalize(P); cs = dot(wi, n);
+ *     e. it contributes only when cs > 0.0f (false for NaN) and m.type is 1 or 2;
+ *     f. f and, with MIS, pbl from pt_render_direct step 3e and pt_render_indirect_mis, unchanged;
+ *     g. pdf as above from q, total and r; w = cs / pdf; c = (f * Le_i) * w per channel, Le_i the chosen texel's value -- the direction
+ *        is not looked up a second time;
+ *     h. indirect, when i < B - 1: kp = (float)Ke * pdf; w = w * (kp / (kp + pbl)) before c is formed;
+ *     i. the shadow ray getRay(p + wi * 0.01f, wi) with limit 1e20f through the any-hit search; an open ray adds c to Se.
+ *    Then indirect: L.c = L.c + mask.c * (Se.c / (float)Ke); direct: L = max((E + S / (float)K) + Se / (float)Ke, 0).  With Ke == 0
+ *    nothing is drawn and nothing is added (no 0 / 0).
+ *  - The order at a vertex: surface, emission, light samples, environment samples, BRDF sample, roulette.  The last vertex's
+ *    environment samples are unweighted, for the reason its light samples are: no BRDF ray follows.
+ * Why the weights partition: emitters and sky are disjoint sources -- a direction either finds a triangle or leaves the scene --, so
+ * each is balanced against the BRDF ray alone.  For a direction that leaves the scene the Ke environment samples have the density kp
+ * = Ke pdf against the BRDF's pb, and kp / (kp + pb) + pb / (kp + pb) = 1; the emitter samples never produce such a direction with an
+ * open ray, and the environment samples never find an emitter (their ray is occluded by it).  The roulette leaves pb as it is.
+ * Identities, bit for bit in workspace and framebuffer:
+ *  - every texel (0.45, 0.45, 0.45) and Ke == 0: the parent's, pt_render_direct_power / pt_render_indirect_rr with mis = 1 and the table,
+ *    for every N, every search and with or without roulette;
+ *  - B == 1: the indirect form is the direct form (under pt_render_indirect's exclusion of an emissive component of -0, and for
+ *    texels without a component of -0: direct keeps max(-0, 0) = -0 where indirect forms 0 + -0 = +0);
+ *  - num_triangles == 0: every sample is max(Le(d), 0) of its primary ray, the map seen through the camera.
+ * Behaviour and errors: the parents', word for word -- one validation, one chunk loop, one fold, the handle's stream, the deferred
+ * PT_ERR_TRAVERSAL --, plus, before anything is enqueued: PT_ERR_INVALID for environment NULL, size not a power of two in 1..2048,
+ * env_samples outside 0..256, a reserved word not 0, env NULL, env_cdf NULL while env_samples > 0, env not 16-byte or env_cdf not 8-byte
+ * aligned, either overlapping any other buffer of the call, a buffer of another device; PT_ERR_RANGE for env smaller than N * N * 16
+ * bytes or env_cdf smaller than 8 * (N * N + 1) bytes.  env_cdf is not read when env_samples == 0. */
+typedef struct pt_environment {
+    int32_t size;           /* N: a power of two, 1 .. 2048 */
+    int32_t env_samples;    /* Ke, 0 .. 256, per vertex */
+    int32_t reserved[2];    /* must be 0 */
+} pt_environment;           /* 16 bytes */
+size_t pt_env_table_bytes(int size);
+int pt_env_table(pt_device_t dev, pt_buffer_t env /* float4[size * size] */, int size, pt_buffer_t cdf /* pt_env_table_bytes(size) bytes */,
+                 pt_event_t ev);
+int pt_render_direct_env(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                         pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, pt_buffer_t cdf, pt_buffer_t tri_q /* may be NULL when 0 */,
+                         pt_buffer_t env, pt_buffer_t env_cdf /* may be NULL when env_samples is 0 */, pt_buffer_t samples /* workspace */,
+                         pt_buffer_t framebuffer, const pt_direct_params* params, const pt_environment* environment,
+                         const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
+int pt_render_indirect_env(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                           pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */,
+                           pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q /* may be NULL when num_lights is 0 */,
+                           pt_buffer_t env, pt_buffer_t env_cdf /* may be NULL when env_samples is 0 */, pt_buffer_t samples /* workspace */,
+                           pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_roulette* roulette,
+                           const pt_environment* environment, const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
+
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.
  * pt_profile_query synchronises the stream and returns the summed duration and launch count

@@ -337,6 +337,24 @@ struct PtDirectRisParams : PtDirectPowerParams {
 struct PtIndirectRisParams : PtIndirectListParams {
     int32_t M;
 };
+// environment lighting (pt_render_direct_env, pt_render_indirect_env): the ENV = true instantiations take these blocks, every other
+// instantiation its block as before (their code does not move).  The four fields are wave-uniform: they add no per-lane state
+struct PtEnvMap {
+    const float4* texels;         // [N * N] row-major, w ignored
+    const uint64_t* cdf;          // [N * N + 1] as ptk_env_table writes it; not read when Ke = 0
+    int32_t N;                    // a power of two, 1 .. 2048
+    int32_t Ke;                   // environment samples per vertex, 0 .. 256
+};
+struct PtDirectEnvParams : PtDirectPowerParams {
+    PtEnvMap env;
+};
+struct PtIndirectEnvParams : PtIndirectRrParams {
+    PtEnvMap env;
+};
+// what ptk_lit is handed: the largest block of the kinds without env, and the map
+struct PtLitParams : PtIndirectRisParams {
+    PtEnvMap env;
+};
 // A kind of lit render names its kernels.  The 14 valid values without ris:
 //   direct illumination (pt_direct_kernel, pt_direct_bvh_kernel):          indirect = mis = rr = list = 0;  power 0 / 1
 //   indirect illumination (pt_indirect_kernel, pt_indirect_bvh_kernel):    indirect = 1, rr = list = 0;     mis 0 / 1 x power 0 / 1
@@ -345,20 +363,26 @@ struct PtIndirectRisParams : PtIndirectListParams {
 // list implies rr, rr implies indirect, mis comes only with indirect
 // and the 5 with ris (the RIS = true instantiations of the same templates): direct by power; the roulette and the list kinds by power,
 // mis 0 / 1.  ris implies power, and an indirect ris kind has rr (R >= B plays no roulette)
-struct PtLitKind { bool indirect, mis, power, rr, list, ris; };
+// and the 2 with env (the ENV = true instantiations): direct by power; the roulette kind by power with mis.  env implies power, excludes
+// ris and list, and an indirect env kind has mis and rr
+struct PtLitKind { bool indirect, mis, power, rr, list, ris, env; };
 static inline bool ptk_lit_kind_valid(PtLitKind k)
 {
-    return (!k.list || k.rr) && (!k.rr || k.indirect) && (!k.mis || k.indirect) && (!k.ris || (k.power && k.rr == k.indirect));
+    return (!k.list || k.rr) && (!k.rr || k.indirect) && (!k.mis || k.indirect) && (!k.ris || (k.power && k.rr == k.indirect)) &&
+           (!k.env || (k.power && !k.ris && !k.list && k.rr == k.indirect && k.mis == k.indirect));
 }
-static inline int ptk_lit_kind_index(PtLitKind k) { return k.indirect | k.mis << 1 | k.power << 2 | k.rr << 3 | k.list << 4 | k.ris << 5; }   // a table's index
-#define PT_LIT_KIND_INDICES 64
+static inline int ptk_lit_kind_index(PtLitKind k)   // a table's index
+{
+    return k.indirect | k.mis << 1 | k.power << 2 | k.rr << 3 | k.list << 4 | k.ris << 5 | k.env << 6;
+}
+#define PT_LIT_KIND_INDICES 128
 // THE launch of a lit render, whatever its kind: `a` is the largest block, and each instantiation is passed its own, sliced from it
 // (PtDirectPowerParams is made of a.d, a.cdf and a.tri_q).  LBVH (m.bvh): the kind's kernel on a persistent grid of at most bvh_blocks
 // = CUs x ptk_lit_bvh_blocks_per_cu(k) workgroups -- the occupancy of the kind's OWN <true, 3> instantiation with the trace kernel's
 // LDS: the direct kernels run at four waves per SIMD, the indirect ones at three, so ptk_query_bvh_blocks_per_cu's premise (five) holds
 // for none.  Brute force: one wave per 64 items; the roulette and list kinds one wave per PT_RR_RUN (pt_constants.h) consecutive
 // items, which refills its dead lanes from its run
-hipError_t ptk_lit(const PtIndirectRisParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s);
+hipError_t ptk_lit(const PtLitParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s);
 int ptk_lit_bvh_blocks_per_cu(PtLitKind k);
 // the fold of a list launch: one lane per (slot j, channel) folds rad[f][j], f = 0 .. frame_count - 1 ascending, into fb[the slot's
 // pixel] with the slot's own frame numbers (pt_fold_frame); pixels that are not listed are neither read nor written
@@ -394,6 +418,11 @@ hipError_t ptk_adaptive_select(const PtPixelMoments* moments, uint32_t npix, con
 #define PT_LIGHT_TABLE_WORDS(nl) ((size_t)(nl) + 2 + PT_LIGHT_TABLE_TILES(nl))
 hipError_t ptk_light_table(const PtRawTriangle* tris, int ntri, const PtRawMaterial* mats, int nmat, const int32_t* lights, int nl,
                            uint64_t* cdf, uint32_t* tri_q, hipStream_t s);
+// pt_env_table: the selection table of the N * N texels of an octahedral map, on the light table's layout, tiling and scan -- cdf:
+// PT_LIGHT_TABLE_WORDS(N * N) uint64, cdf[0 .. N * N], then the same scratch.  Two kernels of its own (the texels' weights and their
+// maximum; quantise and tile sums), then pt_light_table's two scans, unchanged.  There is no second table: q_i = cdf[i + 1] - cdf[i]
+#define PT_ENV_SIZE_MAX 2048
+hipError_t ptk_env_table(const float4* texels, int N, uint64_t* cdf, hipStream_t s);
 // sample moments (pt_sample_moments, pt_moments_resolve): the records of include/pt_shim.h
 struct PtPixelMoments {           // pt_pixel_moments, 56 bytes
     double sum[3], sum2[3];

@@ -3250,6 +3250,173 @@ PTK_DEV bool pt_ris_light(const PtDirectParams& D, const f3& p, const f3& n, con
     return true;
 }
 
+// ---- environment lighting: an octahedral sky map (include/pt_shim.h, "environment lighting", states every expression) ----
+// The map is N x N texels, N a power of two, y up; a direction d maps to the unit square through its L1 normalisation, the lower
+// hemisphere folded outward over the diagonals.  Only fabs, +, *, the IEEE "/" and sqrt: a CPU restatement agrees bit for bit.
+
+PTK_DEV float pt_env_sgn(float v) { return v < 0.0f ? -1.0f : 1.0f; }   // (-0 and NaN give +1)
+
+// the index of coordinate c in [-1, 1]: floor(((c + 1) * 0.5) * N) clamped into [0, N - 1], comparison first, so that it is defined for
+// every float -- a NaN or a negative v gives 0, anything from N - 1 up (infinity too) gives N - 1 -- and the conversion only ever sees a
+// value in [0, N - 1)
+PTK_DEV unsigned pt_env_index(float c, int N)
+{
+    const float v = ((c + 1.0f) * 0.5f) * (float)N;
+    if (!(v >= 0.0f)) return 0u;
+    return v >= (float)(N - 1) ? (unsigned)(N - 1) : (unsigned)v;
+}
+
+// the texel of direction d (any length, any float): row * N + col < N * N; s = (|d.x| + |d.y|) + |d.z| is returned for the density
+PTK_DEV unsigned pt_env_texel(const f3& d, int N, float& s)
+{
+    s = (__builtin_fabsf(d.x) + __builtin_fabsf(d.y)) + __builtin_fabsf(d.z);
+    const float x = d.x / s, z = d.z / s;
+    float a = x, b = z;
+    if (!(d.y >= 0.0f)) {   // the lower hemisphere (and a NaN d.y)
+        a = (1.0f - __builtin_fabsf(z)) * pt_env_sgn(x);
+        b = (1.0f - __builtin_fabsf(x)) * pt_env_sgn(z);
+    }
+    return pt_env_index(b, N) * (unsigned)N + pt_env_index(a, N);
+}
+
+// the point P of the octahedron |x| + |y| + |z| = 1 over (a, b) in [-1, 1]^2; its direction is normalize(P), r = |P|
+PTK_DEV f3 pt_env_point(float a, float b)
+{
+    const float fa = __builtin_fabsf(a), fb = __builtin_fabsf(b);
+    const float h = (1.0f - fa) - fb;
+    if (h >= 0.0f) return mk3(a, h, b);
+    return mk3((1.0f - fb) * pt_env_sgn(a), h, (1.0f - fa) * pt_env_sgn(b));
+}
+
+// the density, per solid angle, of a direction of texel weight q whose octahedron point lies at distance r: (q / total) (N^2 / 4) r^3
+PTK_DEV float pt_env_pdf(uint64_t q, uint64_t total, int N, float r)
+{
+    const float nn4 = ((float)N * (float)N) * 0.25f;   // exact: N is a power of two
+    return (((float)q / (float)total) * nn4) * ((r * r) * r);
+}
+
+// a 16-byte texel / an 8-byte table word at a 32-bit byte offset from the wave-uniform base (N * N <= 2^22 texels)
+PTK_DEV float4 pt_env_load(const float4* texels, unsigned i)
+{
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(texels) + (size_t)(i * 16u));
+}
+PTK_DEV uint64_t pt_env_word(const uint64_t* cdf, unsigned i)
+{
+    return *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(cdf) + (size_t)(i * 8u));
+}
+
+// What a ray (direction d) that leaves the scene adds per unit of mask: the texel of d.  `weigh` (MIS, a vertex i >= 1, Ke > 0): times
+// wb = pb / (Ke pdf(d) + pb), the balance against the environment samples of the vertex before; q = 0 or total = 0 gives wb = 1
+PTK_DEV f3 pt_env_miss(const PtEnvMap& E, const f3& d, bool weigh, float pb)
+{
+    float s;
+    const unsigned i = pt_env_texel(d, E.N, s);
+    const float4 le = pt_env_load(E.texels, i);
+    f3 Le = mk3(le.x, le.y, le.z);
+    if (weigh) {
+        const uint64_t total = pt_env_word(E.cdf, (unsigned)(E.N * E.N));
+        const uint64_t q = pt_env_word(E.cdf, i + 1u) - pt_env_word(E.cdf, i);
+        float wb = 1.0f;
+        if (q != 0ull && total != 0ull) {
+            const float r = pt_sqrt(dot3(d, d)) / s;
+            wb = pb / ((float)E.Ke * pt_env_pdf(q, total, E.N, r) + pb);
+        }
+        Le = scale3(Le, wb);
+    }
+    return Le;
+}
+
+// Environment sample of the vertex (p, n, wo) on material mid (steps a-i of the contract): pt_direct_light's shape -- true when it
+// contributes, then c is its contribution if the shadow ray (o, d) is open; the ray's limit is 1e20, always searched.  The three
+// uniforms are drawn whatever follows.  The texel is chosen through the table as the choice by power chooses its entry; the BRDF value
+// f and the density pbl are pt_direct_light's statements.  MIS with `weigh` (the vertex is not the path's last): c carries kp / (kp +
+// pbl), kp = Ke pdf -- the sky has no back side and no count
+template <bool MIS>
+PTK_DEV bool pt_env_light(const PtDirectParams& D, const PtEnvMap& E, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed, f3& c,
+                          f3& o, f3& d, bool weigh)
+{
+    const float r0 = pt_random_float(seed), r1 = pt_random_float(seed), r2 = pt_random_float(seed);
+    const unsigned nn = (unsigned)(E.N * E.N);
+    const uint64_t total = pt_env_word(E.cdf, nn);
+    if (total == 0ull) return false;   // (an empty table: the three uniforms are drawn, no ray is cast)
+    unsigned u = (unsigned)(r0 * 16777216.0f);   // (getRandomFloat can return 1.0)
+    u = u > 16777215u ? 16777215u : u;
+    const uint64_t x = ((uint64_t)u * total) >> 24;
+    unsigned lo = 0u, hi = nn;   // cdf[lo] <= x < cdf[hi]
+    while (hi - lo > 1u) {
+        const unsigned m = (lo + hi) >> 1;
+        if (pt_env_word(E.cdf, m) <= x) lo = m; else hi = m;
+    }
+    const uint64_t q = pt_env_word(E.cdf, lo + 1u) - pt_env_word(E.cdf, lo);
+    const unsigned col = lo & (unsigned)(E.N - 1), row = lo >> (31 - __builtin_clz((unsigned)E.N));
+    const float step = 2.0f / (float)E.N;   // exact
+    const f3 P = pt_env_point(((float)col + r1) * step - 1.0f, ((float)row + r2) * step - 1.0f);
+    const float P2 = dot3(P, P);
+    const float r = pt_sqrt(P2);
+    const f3 wi = scale3(P, pt_normalize_factor(P2));
+    const float cs = dot3(wi, n);
+    if (!(cs > 0.0f)) return false;   // (false for NaN)
+    const float4 alb = pt_rec16(D.t.mats, mid, 0u), rt = pt_rec16(D.t.mats, mid, 32u);   // albedo | roughness, type
+    const int type = __float_as_int(rt.y);
+    f3 f;
+    float pbl = 0.0f;   // (MIS) the BRDF sample's density towards wi
+    if (type == 1) {   // :203
+        f = mk3(alb.x * PTK_INV_PI, alb.y * PTK_INV_PI, alb.z * PTK_INV_PI);
+        if constexpr (MIS) pbl = cs * PTK_INV_PI;   // :201
+    } else if (type == 2) {   // :205-217 at the half vector of wo and wi
+        const f3 wh = normalize3(add3(wo, wi));
+        const float ct = dot3(wh, n);
+        const float r2g = rt.x * rt.x;
+        const float gd = ct * ct * (r2g - 1.0f) + 1.0f;
+        const float Dg = pt_div(r2g * PTK_INV_PI, gd * gd);   // pow(x, 2.0f) is x*x in PTSPEC (:177)
+        if constexpr (MIS) pbl = Dg * ct / (4.0f * dot3(wo, wh));   // :215
+        const float dwon = dot3(wo, n);
+        if (cs * dwon < 0.0f) {   // :211
+            f = mk3(0.0f, 0.0f, 0.0f);
+        } else {
+            const float g = pt_div(Dg, 4.0f * cs * dwon);
+            f = mk3(alb.x * g * 2.0f, alb.y * g * 2.0f, alb.z * g * 2.0f);
+        }
+    } else {
+        return false;   // :220
+    }
+    const float4 le = pt_env_load(E.texels, lo);
+    const float pdf = pt_env_pdf(q, total, E.N, r);
+    float w = cs / pdf;
+    if constexpr (MIS) {
+        if (weigh) {
+            const float kp = (float)E.Ke * pdf;
+            w = w * (kp / (kp + pbl));
+        }
+    }
+    c = mk3((f.x * le.x) * w, (f.y * le.y) * w, (f.z * le.z) * w);
+    o = add3(p, scale3(wi, 0.01f));   // :257
+    d = normalize3(wi);
+    return true;
+}
+
+// L += mask * (Se / Ke) of a vertex's environment samples
+PTK_DEV void pt_env_lit(int Ke, const f3& mask, const f3& S, f3& L)
+{
+    const float Kf = (float)Ke;
+    L.x = L.x + mask.x * (S.x / Kf);
+    L.y = L.y + mask.y * (S.y / Kf);
+    L.z = L.z + mask.z * (S.z / Kf);
+}
+
+// direct illumination under the map: max((E + S / K) + Se / Ke, 0); Ke = 0 adds nothing (pt_direct_radiance's value, bit for bit)
+PTK_DEV f3 pt_direct_env_radiance(const PtDirectParams& D, int Ke, unsigned mid, const f3& S, const f3& Se)
+{
+    const float4 emi = pt_rec16(D.t.mats, mid, 16u);
+    const float Kf = (float)D.K;
+    f3 v = mk3(emi.x * 3.0f + S.x / Kf, emi.y * 3.0f + S.y / Kf, emi.z * 3.0f + S.z / Kf);
+    if (Ke > 0) {
+        const float Kef = (float)Ke;
+        v = mk3(v.x + Se.x / Kef, v.y + Se.y / Kef, v.z + Se.z / Kef);
+    }
+    return mk3(pt_max(v.x, 0.0f), pt_max(v.y, 0.0f), pt_max(v.z, 0.0f));
+}
+
 // the sample's radiance max(E + S / K, 0), E = 1.0f * emissive * 3.0f of the hit's material (:241)
 PTK_DEV f3 pt_direct_radiance(const PtDirectParams& D, unsigned mid, const f3& S)
 {
@@ -3263,14 +3430,18 @@ PTK_DEV f3 pt_direct_radiance(const PtDirectParams& D, unsigned mid, const f3& S
 // POWER: the light is chosen through pt_light_table's cdf (pt_direct_light<false, true>); such an instantiation takes
 // PtDirectPowerParams, the others PtDirectParams as before
 // RIS (pt_render_direct_ris; POWER only): the light sample is pt_ris_light's; such an instantiation takes PtDirectRisParams
-template <bool POWER, bool RIS = false> using PtDirectArgs = std::conditional_t<RIS, PtDirectRisParams, std::conditional_t<POWER, PtDirectPowerParams, PtDirectParams>>;
+// ENV (pt_render_direct_env; POWER only, never with RIS): a miss stores the map's texel, and the Ke environment samples follow the K
+// light samples in the same shape -- a search only when some lane casts --, summed apart in Se; the block is PtDirectEnvParams
+template <bool POWER, bool RIS = false, bool ENV = false>
+using PtDirectArgs = std::conditional_t<ENV, PtDirectEnvParams, std::conditional_t<RIS, PtDirectRisParams, std::conditional_t<POWER, PtDirectPowerParams, PtDirectParams>>>;
 PTK_DEV const uint64_t* pt_light_cdf(const PtDirectParams&) { return nullptr; }
 PTK_DEV const uint64_t* pt_light_cdf(const PtDirectPowerParams& D) { return D.cdf; }
 
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool POWER = false, bool RIS = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDirectArgs<POWER, RIS> D)
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool POWER = false, bool RIS = false, bool ENV = false>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDirectArgs<POWER, RIS, ENV> D)
 {
     static_assert(POWER || !RIS, "resampling draws its candidates from the light table");
+    static_assert(!ENV || (POWER && !RIS), "the environment comes with the choice by power, without resampling");
     const PtTraceParams& P = D.t;
     const unsigned lane = pt_lane_id();
     const int ntri = P.ntri;
@@ -3289,6 +3460,12 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDir
     const bool hit = act & (hidx >= 0);
     const float bg = pt_max(0.45f, 0.0f);   // :235
     f3 L = mk3(bg, bg, bg);
+    if constexpr (ENV) {
+        if (act & !hit) {
+            const f3 le = pt_env_miss(D.env, d, false, 0.0f);
+            L = mk3(pt_max(le.x, 0.0f), pt_max(le.y, 0.0f), pt_max(le.z, 0.0f));
+        }
+    }
     if (__ballot(hit) != 0ull) {
         f3 p = o, n = d, wo = d, S = mk3(0.0f, 0.0f, 0.0f);
         unsigned mid = 0u;
@@ -3311,7 +3488,26 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDir
             }
             if (cast & !occluded) S = add3(S, c);
         }
-        if (hit) L = pt_direct_radiance(D, mid, S);
+        if constexpr (ENV) {
+            f3 Se = mk3(0.0f, 0.0f, 0.0f);
+            for (int k = 0; k < D.env.Ke; ++k) {
+                f3 c = mk3(0.0f, 0.0f, 0.0f);
+                bool cast = false;
+                if (hit) cast = pt_env_light<false>(D, D.env, p, n, wo, mid, seed, c, o, d, false);
+                bool occluded = false;
+                if (__ballot(cast) != 0ull) {
+                    float t = cast ? 1e20f : 0.0f, su = 0.0f, sv = 0.0f;
+                    int sidx = -1;
+                    pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, cast, t, su, sv, sidx,
+                                                                         P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+                    occluded = cast & (sidx >= 0) & (t < 1e20f);
+                }
+                if (cast & !occluded) Se = add3(Se, c);
+            }
+            if (hit) L = pt_direct_env_radiance(D, D.env.Ke, mid, S, Se);
+        } else {
+            if (hit) L = pt_direct_radiance(D, mid, S);
+        }
     }
     if (act) pt_direct_store(D, item, L);
 }
@@ -3319,16 +3515,20 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDir
 // LBVH (pt_bvh_drive): one item = one sample; the lane runs its searches one after the other -- the primary ray's closest search,
 // then the any-hit searches of the light samples that contribute -- and is free when the sample is stored.  A light sample that
 // does not contribute is passed over inside next_ray: it costs the lane no refill
-template <bool POWER = false, bool RIS = false>
+// ENV: k goes on over K .. K + Ke - 1, the environment samples.  Before the first of them E + S / K is folded into `base` and S starts
+// again as Se: a lane's state grows by these three registers (PtNoEnv is empty in every other instantiation)
+struct PtNoEnv {};
+template <bool POWER = false, bool RIS = false, bool ENV = false>
 struct PtDirectWork {
     static constexpr bool ANY = true;
-    const PtDirectArgs<POWER, RIS>& D;
+    const PtDirectArgs<POWER, RIS, ENV>& D;
     unsigned n;
     int k;           // the current ray: -1 = the primary, 0 .. K-1 = the shadow ray of light sample k
     unsigned item, mid;
     uint32_t seed;
     float tl;        // the shadow ray's limit
     f3 o, d, p, nrm, wo, S, c;
+    [[no_unique_address]] std::conditional_t<ENV, f3, PtNoEnv> base;
     PTK_DEV void begin(unsigned item_)
     {
         unsigned lp;
@@ -3340,6 +3540,11 @@ struct PtDirectWork {
     {
         if (k < 0) {
             if (L.hidx < 0) {
+                if constexpr (ENV) {
+                    const f3 le = pt_env_miss(D.env, d, false, 0.0f);
+                    pt_direct_store(D, item, mk3(pt_max(le.x, 0.0f), pt_max(le.y, 0.0f), pt_max(le.z, 0.0f)));
+                    return false;
+                }
                 const float bg = pt_max(0.45f, 0.0f);   // :235
                 pt_direct_store(D, item, mk3(bg, bg, bg));
                 return false;
@@ -3348,6 +3553,28 @@ struct PtDirectWork {
             S = mk3(0.0f, 0.0f, 0.0f);
         } else if (L.hidx < 0) {   // (an any-hit search: L.hidx >= 0 alone says occluded; a ray that searched nothing is open)
             S = add3(S, c);
+        }
+        if constexpr (ENV) {
+            if (k < D.K) {   // the light samples are not over (k = -1 among them)
+                if (D.nl > 0)
+                    while (++k < D.K)
+                        if (pt_direct_light<false, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, nullptr, false, D.cdf)) return true;
+                const float4 emi = pt_rec16(D.t.mats, mid, 16u);
+                const float Kf = (float)D.K;
+                base = mk3(emi.x * 3.0f + S.x / Kf, emi.y * 3.0f + S.y / Kf, emi.z * 3.0f + S.z / Kf);   // pt_direct_env_radiance's first line
+                S = mk3(0.0f, 0.0f, 0.0f);
+                k = D.K - 1;
+            }
+            tl = 1e20f;
+            while (++k < D.K + D.env.Ke)
+                if (pt_env_light<false>(D, D.env, p, nrm, wo, mid, seed, c, o, d, false)) return true;
+            f3 v = base;
+            if (D.env.Ke > 0) {
+                const float Kef = (float)D.env.Ke;
+                v = mk3(v.x + S.x / Kef, v.y + S.y / Kef, v.z + S.z / Kef);
+            }
+            pt_direct_store(D, item, mk3(pt_max(v.x, 0.0f), pt_max(v.y, 0.0f), pt_max(v.z, 0.0f)));
+            return false;
         }
         if (D.nl > 0)
             while (++k < D.K) {
@@ -3369,12 +3596,18 @@ struct PtDirectWork {
 // against ambient occlusion's 16, and at five waves (96 VGPRs) the kernel spills 19 of them (profiles/direct/kernel_resources.txt).
 // Its persistent grid is therefore its own figure, ptk_lit_bvh_blocks_per_cu of its kind, not ptk_query_bvh_blocks_per_cu
 #define PT_DIRECT_BVH_WAVES 4
-template <bool DET_BOUNDED, int BIGQ, bool POWER = false, bool RIS = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_DIRECT_BVH_WAVES, PT_DIRECT_BVH_WAVES)))
-void pt_direct_bvh_kernel(const PtDirectArgs<POWER, RIS> D)
+// The ENV = true instantiations run at three: next_ray holds the light sample and the environment sample -- its table search in 64-bit
+// words among them -- and at four waves would spill 33 VGPRs (profiles/env/kernel_resources.txt has both figures)
+#ifndef PT_DIRECT_ENV_BVH_WAVES   // (tools/kernel_resources.sh -DPT_DIRECT_ENV_BVH_WAVES=4 reads the other choice)
+#define PT_DIRECT_ENV_BVH_WAVES 3
+#endif
+template <bool DET_BOUNDED, int BIGQ, bool POWER = false, bool RIS = false, bool ENV = false>
+__global__ __launch_bounds__(PT_TRACE_THREADS)
+__attribute__((amdgpu_waves_per_eu(ENV ? PT_DIRECT_ENV_BVH_WAVES : PT_DIRECT_BVH_WAVES, ENV ? PT_DIRECT_ENV_BVH_WAVES : PT_DIRECT_BVH_WAVES)))
+void pt_direct_bvh_kernel(const PtDirectArgs<POWER, RIS, ENV> D)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtDirectWork<POWER, RIS> W = { D, D.nitems, -1, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0 };
+    PtDirectWork<POWER, RIS, ENV> W = { D, D.nitems, -1, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, {} };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(D.t, W);
 }
 
@@ -3585,6 +3818,49 @@ __global__ __launch_bounds__(PT_LIGHT_SCAN_BLOCK) void pt_light_scan_kernel(uint
     }
 }
 
+// ---- pt_env_table: the selection table of an octahedral map's texels (include/pt_shim.h) ----
+// pt_light_table's construction with another weight: p_i = ((Le.x + Le.y) + Le.z) * (1 / rc^3), rc the distance of the octahedron's
+// point over the texel's centre -- the texel's solid angle up to the constant 4 / N^2 --, 0 unless positive and finite.  The two
+// kernels below stand where pt_light_weight_kernel and pt_light_quantise_kernel stand; the two scans are pt_light_table's own
+PTK_DEV float pt_env_weight(const float4* __restrict__ texels, int N, unsigned i)
+{
+    const unsigned col = i & (unsigned)(N - 1), row = i >> (31 - __builtin_clz((unsigned)N));
+    const float step = 2.0f / (float)N;
+    const f3 P = pt_env_point(((float)col + 0.5f) * step - 1.0f, ((float)row + 0.5f) * step - 1.0f);
+    const float rc = pt_sqrt(dot3(P, P));
+    const float4 le = texels[i];
+    const float pw = ((le.x + le.y) + le.z) * (1.0f / ((rc * rc) * rc));
+    return pw > 0.0f && pw < __builtin_inff() ? pw : 0.0f;
+}
+
+__global__ __launch_bounds__(PT_LIGHT_SCAN_BLOCK) void pt_env_weight_kernel(const float4* __restrict__ texels, int N, uint32_t* __restrict__ pmax_bits)
+{
+    const unsigned i = blockIdx.x * PT_LIGHT_SCAN_BLOCK + threadIdx.x;
+    if (i >= (unsigned)(N * N)) return;
+    const float pw = pt_env_weight(texels, N, i);
+    if (pw > 0.0f) atomicMax(pmax_bits, __float_as_uint(pw));
+}
+
+__global__ __launch_bounds__(PT_LIGHT_SCAN_BLOCK) void pt_env_quantise_kernel(const float4* __restrict__ texels, int N, const uint32_t* __restrict__ pmax_bits,
+                                                                              uint64_t* __restrict__ cdf, uint64_t* __restrict__ tile_sums)
+{
+    __shared__ uint64_t lds[PT_LIGHT_SCAN_BLOCK];
+    const float pmax = __uint_as_float(*pmax_bits);
+    const unsigned nl = (unsigned)(N * N);
+    const unsigned first = blockIdx.x * PT_LIGHT_SCAN_TILE + threadIdx.x * PT_LIGHT_SCAN_ITEMS;
+    uint64_t sum = 0ull;
+    for (unsigned k = 0; k < PT_LIGHT_SCAN_ITEMS; ++k) {
+        const unsigned i = first + k;
+        if (i >= nl) break;
+        const uint32_t q = pt_light_quantum(pt_env_weight(texels, N, i), pmax);
+        cdf[i + 1u] = q;
+        sum += q;
+    }
+    uint64_t total;
+    pt_light_block_scan(sum, lds, &total);
+    if (threadIdx.x == 0u) tile_sums[blockIdx.x] = total;
+}
+
 // :241, in that order
 PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f3& mask, f3& L)
 {
@@ -3595,8 +3871,8 @@ PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f
 }
 
 // the parameter block of an instantiation, and its counts (none without MIS)
-template <bool MIS, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false>
-using PtIndirectArgs = std::conditional_t<RIS, PtIndirectRisParams, std::conditional_t<LIST, PtIndirectListParams, std::conditional_t<RR, PtIndirectRrParams, std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>>>>;
+template <bool MIS, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false>
+using PtIndirectArgs = std::conditional_t<ENV, PtIndirectEnvParams, std::conditional_t<RIS, PtIndirectRisParams, std::conditional_t<LIST, PtIndirectListParams, std::conditional_t<RR, PtIndirectRrParams, std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>>>>>;
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectParams&) { return nullptr; }
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectMisParams& I) { return I.counts; }
 PTK_DEV const uint64_t* pt_light_cdf(const PtIndirectParams&) { return nullptr; }
@@ -3774,12 +4050,22 @@ PTK_DEV void pt_list_item_begin(const PtIndirectListParams& I, unsigned item, un
 #ifndef PT_RR_RIS_TILED_MIS_WAVES   // (tools/kernel_resources.sh -DPT_RR_RIS_TILED_MIS_WAVES=6 reads the other choice)
 #define PT_RR_RIS_TILED_MIS_WAVES 5
 #endif
-template <bool RIS, int LDS_TABLE, bool MIS> inline constexpr int PT_RR_WAVES_PIN = !RIS ? 0 : (LDS_TABLE == 2 && MIS) ? PT_RR_RIS_TILED_MIS_WAVES : 6;
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS, bool POWER, bool LIST = false, bool RIS = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_RR_WAVES_PIN<RIS, LDS_TABLE, MIS>)))
-void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS> I)
+// ENV (pt_render_indirect_env; MIS and POWER, neither LIST nor RIS): a miss adds mask times the map's texel -- weighted against the
+// environment samples of the vertex before when i >= 1 and Ke > 0 --, and the Ke environment samples of a vertex follow its K light
+// samples in the same shape, a search only when some lane casts; the block is PtIndirectEnvParams.  PT_RR_ENV_WAVES is their pin
+// -- the parents' six waves per SIMD for the tiled forms; the forms with the table in LDS would spill a VGPR at six (8 bytes of scratch)
+// and are pinned to five (profiles/env/kernel_resources.txt has both figures)
+#ifndef PT_RR_ENV_LDS_WAVES   // (tools/kernel_resources.sh -DPT_RR_ENV_LDS_WAVES=6 reads the other choice)
+#define PT_RR_ENV_LDS_WAVES 5
+#endif
+template <bool RIS, int LDS_TABLE, bool MIS, bool ENV = false>
+inline constexpr int PT_RR_WAVES_PIN = ENV ? (LDS_TABLE == 1 ? PT_RR_ENV_LDS_WAVES : 6) : !RIS ? 0 : (LDS_TABLE == 2 && MIS) ? PT_RR_RIS_TILED_MIS_WAVES : 6;
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS, bool POWER, bool LIST = false, bool RIS = false, bool ENV = false>
+__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_RR_WAVES_PIN<RIS, LDS_TABLE, MIS, ENV>)))
+void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS, ENV> I)
 {
     static_assert(POWER || !RIS, "resampling draws its candidates from the light table");
+    static_assert(!ENV || (MIS && POWER && !LIST && !RIS), "the environment comes with MIS and the choice by power, without a list or resampling");
     static_assert(PT_RR_RUN % 64 == 0 && PT_RR_RUN >= 64, "a run is whole waves of items");
     const PtDirectParams& D = I.d;
     const PtTraceParams& P = D.t;
@@ -3823,7 +4109,14 @@ void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS> I)
         pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, alive, tmax, hu, hv, hidx,
                                                              P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
         const bool hit = alive & (hidx >= 0);
-        if (alive & !hit) L = add3(L, scale3(mask, pt_max(0.45f, 0.0f)));   // :235
+        if constexpr (ENV) {
+            if (alive & !hit) {
+                const f3 le = pt_env_miss(I.env, d, i >= 1 && I.env.Ke > 0, pb);
+                L = mk3(L.x + mask.x * le.x, L.y + mask.y * le.y, L.z + mask.z * le.z);
+            }
+        } else {
+            if (alive & !hit) L = add3(L, scale3(mask, pt_max(0.45f, 0.0f)));   // :235
+        }
         f3 p = o, n = d, wo = d;
         unsigned mid = 0u;
         if (hit) {
@@ -3854,6 +4147,26 @@ void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS> I)
             }
             if (hit) pt_indirect_lit(D, mask, S, L);
         }
+        if constexpr (ENV) {
+            if (I.env.Ke > 0 && __ballot(hit) != 0ull) {
+                f3 S = mk3(0.0f, 0.0f, 0.0f);
+                for (int k = 0; k < I.env.Ke; ++k) {
+                    f3 c = mk3(0.0f, 0.0f, 0.0f);
+                    bool cast = false;
+                    if (hit) cast = pt_env_light<true>(D, I.env, p, n, wo, mid, seed, c, o, d, i < I.B - 1);
+                    bool occluded = false;
+                    if (__ballot(cast) != 0ull) {
+                        float t = cast ? 1e20f : 0.0f, su = 0.0f, sv = 0.0f;
+                        int sidx = -1;
+                        pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, cast, t, su, sv, sidx,
+                                                                             P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+                        occluded = cast & (sidx >= 0) & (t < 1e20f);
+                    }
+                    if (cast & !occluded) S = add3(S, c);
+                }
+                if (hit) pt_env_lit(I.env.Ke, mask, S, L);
+            }
+        }
         // the BRDF sample and the roulette of vertex i; at the last vertex nothing is drawn
         bool on = false;
         if (hit && i < I.B - 1) {
@@ -3874,12 +4187,15 @@ void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS> I)
 // wo is the negated incoming direction, which the shadow rays overwrite in d, so it is kept; o is dead while p is live.
 // With MIS a lane also holds pb from the BRDF sample to the next closest hit, across that search: 34 registers.  The counts and the
 // emitter's record are gathered where they are used, as the materials are.
-template <bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false>
+// ENV: k goes on over K .. K + Ke - 1, the environment samples of the vertex.  S / K is folded into L before the first of them and S
+// starts again as Se: a lane's state does not grow
+template <bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false>
 struct PtIndirectWork {
     static_assert(RR || !LIST, "a list launch is a roulette launch");
     static_assert(!RIS || (POWER && RR), "resampling comes with the light table, in the roulette family");
+    static_assert(!ENV || (MIS && POWER && RR && !LIST && !RIS), "the environment comes with MIS and the light table, in the roulette family");
     static constexpr bool ANY = true;
-    const PtIndirectArgs<MIS, POWER, RR, LIST, RIS>& I;
+    const PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV>& I;
     unsigned n;
     int k;           // the current ray: -1 = the vertex's closest search, 0 .. K-1 = the shadow ray of light sample k
     int bounce;      // loop index i of traceRays (:229)
@@ -3904,7 +4220,12 @@ struct PtIndirectWork {
         const PtDirectParams& D = I.d;
         if (k < 0) {
             if (R.hidx < 0) {
-                L = add3(L, scale3(mask, pt_max(0.45f, 0.0f)));   // :235
+                if constexpr (ENV) {
+                    const f3 le = pt_env_miss(I.env, d, bounce >= 1 && I.env.Ke > 0, pb);
+                    L = mk3(L.x + mask.x * le.x, L.y + mask.y * le.y, L.z + mask.z * le.z);
+                } else {
+                    L = add3(L, scale3(mask, pt_max(0.45f, 0.0f)));   // :235
+                }
                 pt_indirect_store(D, item, L);
                 return false;
             }
@@ -3916,7 +4237,21 @@ struct PtIndirectWork {
         } else if (R.hidx < 0) {   // (an any-hit search: R.hidx >= 0 alone says occluded; a ray that searched nothing is open)
             S = add3(S, c);
         }
-        if (D.nl > 0) {
+        if constexpr (ENV) {
+            if (k < D.K) {   // the light samples are not over (k = -1 among them)
+                if (D.nl > 0) {
+                    while (++k < D.K)
+                        if (pt_direct_light<true, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, I.counts, bounce < I.B - 1, I.cdf)) return true;
+                    pt_indirect_lit(D, mask, S, L);
+                    S = mk3(0.0f, 0.0f, 0.0f);
+                }
+                k = D.K - 1;
+            }
+            tl = 1e20f;
+            while (++k < D.K + I.env.Ke)
+                if (pt_env_light<true>(D, I.env, p, nrm, wo, mid, seed, c, o, d, bounce < I.B - 1)) return true;
+            if (I.env.Ke > 0) pt_env_lit(I.env.Ke, mask, S, L);
+        } else if (D.nl > 0) {
             while (++k < D.K) {
                 if constexpr (RIS) { if (pt_ris_light<MIS>(D, p, nrm, wo, mid, seed, c, o, d, tl, I.counts, bounce < I.B - 1, I.cdf, I.M)) return true; }
                 else if constexpr (POWER) { if (pt_direct_light<MIS, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, pt_indirect_counts(I), bounce < I.B - 1, pt_light_cdf(I))) return true; }
@@ -3957,12 +4292,18 @@ struct PtIndirectWork {
 // The LIST = true instantiations (pt_render_indirect_pixels) take PtIndirectListParams: the slot is loaded and dies in begin(), the
 // pointer and the offset are scalar (profiles/adaptive/kernel_resources.txt)
 // The RIS = true instantiations take PtIndirectRisParams: M is scalar, the reservoir lives inside pt_ris_light (profiles/ris/kernel_resources.txt)
-template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_INDIRECT_BVH_WAVES, PT_INDIRECT_BVH_WAVES)))
-void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER, RR, LIST, RIS> I)
+// The ENV = true instantiations take PtIndirectEnvParams: the map's fields are scalar, Se shares S's registers.  They run at TWO waves:
+// at three they would spill 37 VGPRs inside next_ray (profiles/env/kernel_resources.txt has both figures)
+#ifndef PT_INDIRECT_ENV_BVH_WAVES   // (tools/kernel_resources.sh -DPT_INDIRECT_ENV_BVH_WAVES=3 reads the other choice)
+#define PT_INDIRECT_ENV_BVH_WAVES 2
+#endif
+template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false>
+__global__ __launch_bounds__(PT_TRACE_THREADS)
+__attribute__((amdgpu_waves_per_eu(ENV ? PT_INDIRECT_ENV_BVH_WAVES : PT_INDIRECT_BVH_WAVES, ENV ? PT_INDIRECT_ENV_BVH_WAVES : PT_INDIRECT_BVH_WAVES)))
+void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV> I)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtIndirectWork<MIS, POWER, RR, LIST, RIS> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
+    PtIndirectWork<MIS, POWER, RR, LIST, RIS, ENV> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(I.d.t, W);
 }
 
@@ -4455,24 +4796,30 @@ struct PtAoFamily {
     template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table() { return pt_ao_kernel<DB, LDS_TABLE, QUADS>; }
 };
 // a kind of lit render (PtLitKind); RR: the table kernels are the refilling ones, a wave of which owns PT_RR_RUN items
-template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST, bool RIS = false> struct PtLitFamily {
-    using Params = std::conditional_t<INDIRECT, PtIndirectArgs<MIS, POWER, RR, LIST, RIS>, PtDirectArgs<POWER, RIS>>;
+template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST, bool RIS = false, bool ENV = false> struct PtLitFamily {
+    using Params = std::conditional_t<INDIRECT, PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV>, PtDirectArgs<POWER, RIS, ENV>>;
     static constexpr unsigned run = RR ? PT_RR_RUN : 64;
     template <bool DB, int BIGQ> static constexpr auto bvh()
     {
-        if constexpr (INDIRECT) return pt_indirect_bvh_kernel<DB, BIGQ, MIS, POWER, RR, LIST, RIS>;
-        else return pt_direct_bvh_kernel<DB, BIGQ, POWER, RIS>;
+        if constexpr (INDIRECT) return pt_indirect_bvh_kernel<DB, BIGQ, MIS, POWER, RR, LIST, RIS, ENV>;
+        else return pt_direct_bvh_kernel<DB, BIGQ, POWER, RIS, ENV>;
     }
     template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table()
     {
-        if constexpr (RR) return pt_indirect_rr_kernel<DB, LDS_TABLE, QUADS, MIS, POWER, LIST, RIS>;
+        if constexpr (RR) return pt_indirect_rr_kernel<DB, LDS_TABLE, QUADS, MIS, POWER, LIST, RIS, ENV>;
         else if constexpr (INDIRECT) return pt_indirect_kernel<DB, LDS_TABLE, QUADS, MIS, POWER>;
-        else return pt_direct_kernel<DB, LDS_TABLE, QUADS, POWER, RIS>;
+        else return pt_direct_kernel<DB, LDS_TABLE, QUADS, POWER, RIS, ENV>;
     }
     // the instantiations' own block, sliced from the largest (every indirect block is a base of it; direct by power: direct's and the table)
-    static Params params(const PtIndirectRisParams& a)
+    static Params params(const PtLitParams& a)
     {
-        if constexpr (INDIRECT) return a;
+        if constexpr (INDIRECT && ENV) {
+            Params p;
+            __builtin_memset(&p, 0, sizeof p);
+            static_cast<PtIndirectRrParams&>(p) = a;
+            p.env = a.env;
+            return p;
+        } else if constexpr (INDIRECT) return a;
         else if constexpr (!POWER) return a.d;
         else {
             Params p;
@@ -4481,6 +4828,7 @@ template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST, bool RIS = fa
             p.cdf = a.cdf;
             p.tri_q = a.tri_q;
             if constexpr (RIS) p.M = a.M;
+            if constexpr (ENV) p.env = a.env;
             return p;
         }
     }
@@ -4491,6 +4839,10 @@ template <class Fn> static auto pt_lit_family(PtLitKind k, Fn fn)
 {
     auto estimator = [&](auto mis, auto power) {
         constexpr bool M = decltype(mis)::value, P = decltype(power)::value;
+        if constexpr (P) if (k.env) {
+            if constexpr (!M) return fn(PtLitFamily<false, false, true, false, false, false, true>());
+            else return fn(PtLitFamily<true, true, true, true, false, false, true>());
+        }
         if constexpr (P) if (k.ris) {
             if constexpr (!M) if (!k.indirect) return fn(PtLitFamily<false, false, true, false, false, true>());
             return k.list ? fn(PtLitFamily<true, M, true, true, true, true>()) : fn(PtLitFamily<true, M, true, true, false, true>());
@@ -4530,7 +4882,7 @@ hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream
     return pt_launch_search(pt_choose<PtAoFamily>(m, a.t.ntri), a, a.t.ntri, a.nitems, 64u, m.bvh, bvh_blocks, s);
 }
 
-hipError_t ptk_lit(const PtIndirectRisParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s)
+hipError_t ptk_lit(const PtLitParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s)
 {
     if (a.d.nitems == 0) return hipSuccess;
     return pt_lit_family(k, [&](auto f) {
@@ -4559,6 +4911,23 @@ hipError_t ptk_light_table(const PtRawTriangle* tris, int ntri, const PtRawMater
                        tris, ntri, mats, nmat, lights, nl, reinterpret_cast<uint32_t*>(pmax));
     hipLaunchKernelGGL(pt_light_quantise_kernel, dim3(ntiles), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, tris, ntri, mats, nmat, lights, nl,
                        reinterpret_cast<const uint32_t*>(pmax), cdf, tri_q, tile_sums);
+    hipLaunchKernelGGL(pt_light_tiles_kernel, dim3(1), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, tile_sums, ntiles, cdf);
+    hipLaunchKernelGGL(pt_light_scan_kernel, dim3(ntiles), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, cdf, nl, tile_sums);
+    return hipGetLastError();
+}
+
+hipError_t ptk_env_table(const float4* texels, int N, uint64_t* cdf, hipStream_t s)
+{
+    const int nl = N * N;   // 1 .. 2^22
+    const unsigned ntiles = (unsigned)PT_LIGHT_TABLE_TILES(nl);
+    uint64_t* pmax = cdf + (size_t)nl + 1;   // pt_light_table's scratch: the maximum's bits, then the tile sums
+    uint64_t* tile_sums = pmax + 1;
+    hipError_t e = hipMemsetAsync(pmax, 0, sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pt_env_weight_kernel, dim3(((unsigned)nl + PT_LIGHT_SCAN_BLOCK - 1u) / PT_LIGHT_SCAN_BLOCK), dim3(PT_LIGHT_SCAN_BLOCK), 0, s,
+                       texels, N, reinterpret_cast<uint32_t*>(pmax));
+    hipLaunchKernelGGL(pt_env_quantise_kernel, dim3(ntiles), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, texels, N, reinterpret_cast<const uint32_t*>(pmax), cdf,
+                       tile_sums);
     hipLaunchKernelGGL(pt_light_tiles_kernel, dim3(1), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, tile_sums, ntiles, cdf);
     hipLaunchKernelGGL(pt_light_scan_kernel, dim3(ntiles), dim3(PT_LIGHT_SCAN_BLOCK), 0, s, cdf, nl, tile_sums);
     return hipGetLastError();

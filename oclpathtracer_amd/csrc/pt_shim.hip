@@ -358,7 +358,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->bvh_blocks_per_cu = ptk_trace_bvh_blocks_per_cu();
     d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
     for (int i = 0; i < PT_LIT_KIND_INDICES; ++i) {
-        const PtLitKind k = { (i & 1) != 0, (i & 2) != 0, (i & 4) != 0, (i & 8) != 0, (i & 16) != 0, (i & 32) != 0 };
+        const PtLitKind k = { (i & 1) != 0, (i & 2) != 0, (i & 4) != 0, (i & 8) != 0, (i & 16) != 0, (i & 32) != 0, (i & 64) != 0 };
         if (ptk_lit_kind_valid(k)) d->lit_bvh_blocks_per_cu[ptk_lit_kind_index(k)] = ptk_lit_bvh_blocks_per_cu(k);
     }
     *out = d;
@@ -1785,11 +1785,12 @@ static_assert(sizeof(pt_indirect_params) == 64, "pt_indirect_params layout");
 
 static_assert(sizeof(pt_roulette) == 16, "pt_roulette layout");
 static_assert(sizeof(pt_ris) == 16, "pt_ris layout");
+static_assert(sizeof(pt_environment) == 16, "pt_environment layout");
 static_assert(sizeof(pt_adaptive_rule) == 32 && sizeof(pt_pixel_slot) == 8 && sizeof(pt_pixel_slot) == sizeof(uint2), "adaptive record layout");
 
 // ONE lit call, as its entry point describes it: pt_render_direct, pt_render_indirect, pt_render_indirect_mis, the two _power entry
-// points, pt_render_indirect_rr, pt_render_indirect_pixels and the three _ris entry points each fill one and hand it to render_lit -- one
-// validation, one chunk loop
+// points, pt_render_indirect_rr, pt_render_indirect_pixels, the three _ris and the two _env entry points each fill one and hand it to
+// render_lit -- one validation, one chunk loop
 struct PtLitCall {
     PtLitKind kind;             // which kernels (pt_kernels.h); what follows is read as far as the kind says
     pt_buffer_t triangles, materials, lights, samples, framebuffer;
@@ -1801,6 +1802,8 @@ struct PtLitCall {
     int max_bounces;            // kind.indirect: the depth of the paths
     pt_roulette rr;             // kind.rr: the roulette (roulette_args has checked it)
     int candidates;             // kind.ris: M (ris_args has checked it)
+    pt_buffer_t env, env_cdf;   // kind.env: the map and its selection table (pt_env_table)
+    pt_environment e;           //   and its block (env_args has checked it)
     const pt_camera* cam;
     pt_event_t ev;
     const char* what;           // the message for a field out of range
@@ -1827,7 +1830,7 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     PtCamera cam = reference_camera();
     if (c.cam && (rc = camera_derive(c.cam, &cam))) return rc;
     if (!triangles || !materials || !samples || !framebuffer || (c.kind.list && !list)) return fail(PT_ERR_INVALID, "null buffer handle");
-    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer, cdf, tri_q, list })) || (rc = check_event(d, c.ev))) return rc;
+    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer, cdf, tri_q, list, c.env, c.env_cdf })) || (rc = check_event(d, c.ev))) return rc;
     if (a.num_triangles < 0 || a.num_materials < 1 || a.num_lights < 0 || a.light_samples < 1 || a.light_samples > 256)
         return fail(PT_ERR_INVALID, "%s", c.what);
     if (a.num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
@@ -1860,6 +1863,11 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     if ((rc = span_fits(N)) || (rc = span_aligned(N)) || (rc = spans_apart({ N, W, F, L }))) return rc;
     if ((rc = span_fits(Q)) || (rc = span_fits(T)) || (rc = span_aligned(Q)) || (T.bytes && (rc = span_aligned(T))) || (rc = spans_apart({ Q, T, W, F, L, N }))) return rc;
     if ((rc = span_fits(P)) || (rc = span_aligned(P)) || (rc = spans_apart({ P, W, F }))) return rc;
+    // the map and its table (kind.env): read only, so they must lie apart from what is written; the table is not read when Ke = 0
+    const size_t texels = c.kind.env ? (size_t)c.e.size * (size_t)c.e.size : 0;
+    const PtSpan E = { c.kind.env ? c.env : nullptr, texels * sizeof(float4), 16, "the environment map" },
+                 C = { c.kind.env && c.e.env_samples > 0 ? c.env_cdf : nullptr, (texels + 1) * sizeof(uint64_t), 8, "the environment table's cdf" };
+    if ((rc = span_fits(E)) || (rc = span_fits(C)) || (rc = span_aligned(E)) || (rc = span_aligned(C)) || (rc = spans_apart({ E, C, W, F, L, N, Q, T }))) return rc;
     // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
     if ((rc = check_traversal(d))) return rc;
     if ((rc = enter_stream(d))) return rc;
@@ -1870,8 +1878,14 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     PtSearch search;
     if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
     if ((rc = event_begin(d, c.ev))) return rc;
-    PtIndirectRisParams ip;   // (every kind's block is a base of it, or made of it: ptk_lit)
+    PtLitParams ip;   // (every kind's block is a base of it, or made of it: ptk_lit)
     memset(&ip, 0, sizeof ip);
+    if (c.kind.env) {
+        ip.env.texels = (const float4*)c.env->dptr;
+        ip.env.cdf = C.buf ? (const uint64_t*)c.env_cdf->dptr : nullptr;
+        ip.env.N = c.e.size;
+        ip.env.Ke = c.e.env_samples;
+    }
     ip.M = c.candidates;       // (zero without resampling)
     ip.B = c.max_bounces;
     ip.R = c.rr.first_bounce;   // (zeros without roulette)
@@ -2093,6 +2107,65 @@ extern "C" int pt_render_indirect_pixels_ris(pt_device_t d, pt_buffer_t triangle
     int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
     if (rc || (rc = ris_args(ris, cdf, tri_q, params ? params->num_lights : 0, c)) || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
     return render_lit(d, c);
+}
+
+// ---- environment lighting (include/pt_shim.h) ----------------------------------------------------------------------------------------
+static bool env_size_valid(int N) { return N >= 1 && N <= PT_ENV_SIZE_MAX && (N & (N - 1)) == 0; }
+
+// what the two _env entry points check before anything else: the block, N, Ke, the reserved words, the map, the table when it is read
+static int env_args(const pt_environment* environment, pt_buffer_t env, pt_buffer_t env_cdf, PtLitCall& c)
+{
+    if (!environment) return fail(PT_ERR_INVALID, "environment == NULL");
+    c.e = *environment;
+    if (!env_size_valid(c.e.size)) return fail(PT_ERR_INVALID, "the map's size must be a power of two in 1..%d", PT_ENV_SIZE_MAX);
+    if (c.e.env_samples < 0 || c.e.env_samples > 256) return fail(PT_ERR_INVALID, "env_samples must lie in 0..256");
+    if (c.e.reserved[0] != 0 || c.e.reserved[1] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    if (!env) return fail(PT_ERR_INVALID, "the environment map is NULL");
+    if (c.e.env_samples > 0 && !env_cdf) return fail(PT_ERR_INVALID, "env_samples > 0 needs the environment table (pt_env_table)");
+    c.env = env; c.env_cdf = env_cdf;
+    return PT_OK;
+}
+
+extern "C" int pt_render_direct_env(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t cdf,
+                                    pt_buffer_t tri_q, pt_buffer_t env, pt_buffer_t env_cdf, pt_buffer_t samples, pt_buffer_t framebuffer,
+                                    const pt_direct_params* params, const pt_environment* environment, const pt_camera* cam, pt_event_t ev)
+{
+    PtLitCall c = lit_call({ false, false, true, false, false, false, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    c.cdf = cdf; c.tri_q = tri_q;
+    int rc = env_args(environment, env, env_cdf, c);
+    if (rc || (rc = use_device(d)) || (rc = direct_block(params, c))) return rc;
+    return render_lit(d, c);
+}
+
+extern "C" int pt_render_indirect_env(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts,
+                                      pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t env, pt_buffer_t env_cdf, pt_buffer_t samples,
+                                      pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_roulette* roulette,
+                                      const pt_environment* environment, const pt_camera* cam, pt_event_t ev)
+{
+    PtLitCall c = lit_call({ true, true, true, true, false, false, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    c.light_counts = light_counts;
+    c.cdf = cdf; c.tri_q = tri_q;
+    int rc = roulette_args(1, roulette, cdf, tri_q, params, c);
+    if (rc || (rc = env_args(environment, env, env_cdf, c)) || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
+    return render_lit(d, c);
+}
+
+extern "C" size_t pt_env_table_bytes(int N) { return env_size_valid(N) ? PT_LIGHT_TABLE_WORDS((size_t)N * (size_t)N) * sizeof(uint64_t) : 0; }
+
+extern "C" int pt_env_table(pt_device_t d, pt_buffer_t env, int N, pt_buffer_t cdf, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!env || !cdf) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { env, cdf })) || (rc = check_event(d, ev))) return rc;
+    if (!env_size_valid(N)) return fail(PT_ERR_INVALID, "the map's size must be a power of two in 1..%d", PT_ENV_SIZE_MAX);
+    const PtSpan E = { env, (size_t)N * (size_t)N * sizeof(float4), 16, "the environment map" },
+                 Q = { cdf, pt_env_table_bytes(N), 8, "the environment table's cdf (pt_env_table_bytes)" };
+    if ((rc = span_fits(E)) || (rc = span_fits(Q)) || (rc = span_aligned(E)) || (rc = span_aligned(Q)) || (rc = spans_apart({ Q }, { E }))) return rc;
+    if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
+    HIP_TRY(ptk_env_table((const float4*)env->dptr, N, (uint64_t*)cdf->dptr, d->stream));
+    cdf->version++;
+    return event_end(d, ev);
 }
 
 extern "C" size_t pt_adaptive_list_bytes(uint32_t num_pixels) { return PT_ADAPTIVE_LIST_BYTES(num_pixels); }

@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power [--candidates M]] | --only IndirectIllumination [--mis] [--lights power [--candidates M]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]]] [--noise]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]]] [--noise]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <chrono>
 #include <cmath>
@@ -120,6 +120,7 @@ struct Options {
     bool batch = true, mis = false;   // mis: IndirectIllumination through pt_render_indirect_mis
     bool power = false;               // --lights power: DirectIllumination / IndirectIllumination choose their lights by power
     int candidates = 0;               // --candidates M (with --lights power): resampled light samples through the _ris entry points (0 = none)
+    int env = 0, envSamples = 1;      // --env sun|grey[,Ke] (with --lights power; IndirectIllumination: with --mis): 1 = sun, 2 = grey; Ke environment samples per vertex
     int rrFirst = 0;                  // --roulette R[,cap]: IndirectIllumination through pt_render_indirect_rr (0 = no roulette)
     float rrCap = 0.95f;
     double adaptTol = -1.0;           // --adaptive TOL[,MIN[,MAX]]: IndirectIllumination renders MIN frames, then only the pixels still noisy (< 0 = off)
@@ -379,6 +380,10 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
 // most cap (0.95 unless given), under --mis and --lights power as they are set -- and the file's name gains _rr before .ppm.
 // With --lights power --candidates M every light sample is resampled from M candidates (pt_render_direct_ris, pt_render_indirect_ris,
 // which plays the roulette of --roulette or none, and pt_render_indirect_pixels_ris under --adaptive) and the file's name gains _risM.
+// With --lights power --env sun|grey[,Ke] the sky is an octahedral map of 64 x 64 texels (pt_render_direct_env, pt_render_indirect_env, which
+// needs --mis and plays the roulette of --roulette or none) -- grey: every texel 0.45, the constant sky; sun: four adjacent texels of 5 000 a
+// little off the zenith on that sky -- sampled Ke times per vertex (1 unless given; 0 looks the map up only), and the file's name gains
+// _envsun or _envgrey.
 // With --noise either case renders in calls of at most as many frames as the workspace holds, takes the samples' moments after each
 // (pt_sample_moments) and prints one more line, after the case's own: the summary of pt_moments_resolve.  The image is the same.
 // With --adaptive TOL[,MIN[,MAX]] IndirectIllumination renders MIN frames (16 unless given) as above, then pass by pass lists the pixels
@@ -451,6 +456,23 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     std::memset(&none, 0, sizeof none);
     none.first_bounce = 65535;
     none.max_survival = 1.0f;
+    // --env: the map, its table and its block
+    const int envSize = 64;
+    Buffer<float4_t> envMap(m_d, o.env ? (size_t)envSize * envSize : 0);
+    Buffer<unsigned long long> envCdf(m_d, o.env ? pt_env_table_bytes(envSize) / 8 : 0);
+    pt_environment environment;
+    std::memset(&environment, 0, sizeof environment);
+    environment.size = envSize;
+    environment.env_samples = o.envSamples;
+    if (o.env) {
+        std::vector<float4_t> texels((size_t)envSize * envSize);
+        for (size_t i = 0; i < texels.size(); i++) { texels[i].x = texels[i].y = texels[i].z = 0.45f; texels[i].w = 1.0f; }
+        if (o.env == 1)
+            for (int r = 35; r <= 36; r++)
+                for (int c = 38; c <= 39; c++) texels[(size_t)r * envSize + c].x = texels[(size_t)r * envSize + c].y = texels[(size_t)r * envSize + c].z = 5000.0f;
+        envMap.write(texels.data(), texels.size());
+        IASSERT(pt_env_table(m_d->m_handle, envMap.m_handle, envSize, envCdf.m_handle, 0) == PT_OK);
+    }
     pt_buffer_t lh = lights.empty() ? 0 : lBuffer.m_handle;
     if (o.power)
         IASSERT(pt_light_table(m_d->m_handle, tBuffer.m_handle, p.num_triangles, mBuffer.m_handle, p.num_materials, lh, p.num_lights, cdf.m_handle,
@@ -460,6 +482,12 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     auto render = [&](int first, int count) {
         p.frame_begin = q.frame_begin = first;
         p.frame_count = q.frame_count = count;
+        if (o.env && bounces)
+            return pt_render_indirect_env(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cBuffer.m_handle, cdf.m_handle, triq.m_handle,
+                                          envMap.m_handle, envCdf.m_handle, samples.m_handle, image.m_handle, &q, rr ? &roulette : &none, &environment, 0, 0);
+        if (o.env)
+            return pt_render_direct_env(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cdf.m_handle, triq.m_handle, envMap.m_handle,
+                                        envCdf.m_handle, samples.m_handle, image.m_handle, &p, &environment, 0, 0);
         if (resample && bounces)
             return pt_render_indirect_ris(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0, cdf.m_handle,
                                           triq.m_handle, samples.m_handle, image.m_handle, &q, rr ? &roulette : &none, &ris, 0, 0);
@@ -535,8 +563,9 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     rgb.read(h.data(), 3 * npix);
     DeviceUtils::waitForCompletion(m_d);
     double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    char risText[48] = "";
+    char risText[64] = "";
     if (resample) std::snprintf(risText, sizeof risText, " (%d candidates per light sample)", o.candidates);
+    if (o.env) std::snprintf(risText, sizeof risText, " (%s sky, %d environment samples)", o.env == 1 ? "sun" : "grey", o.envSamples);
     if (bounces) {
         char rrText[64] = "";
         if (rr) std::snprintf(rrText, sizeof rrText, " (roulette from %d, at most %g)", o.rrFirst, (double)o.rrCap);
@@ -567,6 +596,7 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     if (o.power && std::strlen(path) + 7 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_power.ppm");
     if (rr && std::strlen(path) + 4 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_rr.ppm");
     if (resample && std::strlen(path) + 8 < sizeof path) std::snprintf(path + std::strlen(path) - 4, 12, "_ris%d.ppm", o.candidates);
+    if (o.env && std::strlen(path) + 9 < sizeof path) std::strcpy(path + std::strlen(path) - 4, o.env == 1 ? "_envsun.ppm" : "_envgrey.ppm");
     if (adaptive && std::strlen(path) + 10 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_adaptive.ppm");
     FILE* fp = std::fopen(path, "w");
     IASSERT(fp != 0);
@@ -619,6 +649,15 @@ int main(int argc, char** argv)
             o.candidates = std::atoi(next());
             if (o.candidates < 1 || o.candidates > 32) { std::fprintf(stderr, "--candidates takes M in 1..32\n"); return 2; }
         }
+        else if (a == "--env") {
+            const std::string v = next();
+            const size_t comma = v.find(',');
+            const std::string kind = v.substr(0, comma);
+            if (kind != "sun" && kind != "grey") { std::fprintf(stderr, "--env takes sun or grey, then [,Ke]\n"); return 2; }
+            o.env = kind == "sun" ? 1 : 2;
+            if (comma != std::string::npos) o.envSamples = std::atoi(v.c_str() + comma + 1);
+            if (o.envSamples < 0 || o.envSamples > 256) { std::fprintf(stderr, "--env: Ke lies in 0..256\n"); return 2; }
+        }
         else if (a == "--lights") {
             const std::string v = next();
             if (v != "uniform" && v != "power") { std::fprintf(stderr, "--lights takes uniform or power\n"); return 2; }
@@ -628,6 +667,8 @@ int main(int argc, char** argv)
     }
     if (o.dim < 1 || o.frames < 0) { std::fprintf(stderr, "bad --dim/--frames\n"); return 2; }
     if (o.candidates > 0 && !o.power) { std::fprintf(stderr, "--candidates needs --lights power (the candidates are drawn from the light table)\n"); return 2; }
+    if (o.env && (!o.power || o.candidates > 0 || o.adaptTol >= 0.0)) { std::fprintf(stderr, "--env needs --lights power and goes with neither --candidates nor --adaptive\n"); return 2; }
+    if (o.env && o.only == "IndirectIllumination" && !o.mis) { std::fprintf(stderr, "--env with IndirectIllumination needs --mis\n"); return 2; }
     struct { const char* name; int kind; } tests[] = { { "initialize", 0 }, { "deviceInfo", 1 }, { "MemoryAllocation", 2 }, { "writeRead", 3 },
                                                        { "getHostPtr", 4 }, { "kernelExecution", 5 }, { "RayCast", 6 },
                                                        { "AmbientOcclusion", 7 }, { "DirectIllumination", 8 }, { "IndirectIllumination", 9 } };

@@ -11,6 +11,9 @@ or brightness.
 ``candidates=M`` (with ``light_choice="power"``) resamples every light sample (``pt_render_direct_ris``): M candidates are drawn from the
 table, one is kept in proportion to its unshadowed contribution at the shading point, and the one shadow ray goes to it -- the same
 expectation, and far less noise where many emitters have similar power and most of them are far from, or face away from, the point.
+``environment=env`` (an ``environment.Environment``, with ``light_choice="power"``) takes the light of a ray that leaves the scene from
+an octahedral sky map instead of the constant 0.45, and ``env_samples=Ke`` samples that map Ke times per hit in proportion to what its
+texels emit (``pt_render_direct_env``): a small bright source in the sky -- a sun -- is found by sampling, not by chance.
 ``moments=True`` keeps per-pixel noise estimates beside the image: after every call the first and second moments of the samples'
 linear radiance are taken from the workspace on the device (``pt_sample_moments``), and ``variance()``, ``noise()`` and
 ``render_until()`` read them -- a variance map, an image-wide figure of 48 bytes, and a render that stops at a noise level.
@@ -26,6 +29,7 @@ import numpy as np
 
 from . import adl, scene, shim
 from .camera import Camera
+from .environment import Environment, check_env_samples
 
 _WORKSPACE_BYTES = 64 << 20   # the default workspace holds as many whole frames as fit in this, at most 64
 
@@ -73,11 +77,14 @@ class DirectRenderer:
     def __init__(self, dev: adl.Device, triangles, materials, width: int, height: int, *, light_samples: int = 1, lights=None,
                  camera: Optional[Camera] = None, num_triangles: Optional[int] = None, num_materials: Optional[int] = None,
                  stripe_rows: int = 16, n_ranks: int = 1, rank: int = 0, chunk_frames: Optional[int] = None,
-                 light_choice: str = "uniform", moments: bool = False, candidates: int = 1):
+                 light_choice: str = "uniform", moments: bool = False, candidates: int = 1, environment: Optional[Environment] = None,
+                 env_samples: int = 0):
         if light_choice not in ("uniform", "power"):
             raise ValueError('light_choice must be "uniform" or "power"')
         self.light_choice = light_choice
+        self.environment, self.env_samples, self._env = None, 0, None
         self.set_candidates(candidates)
+        self._check_environment(environment, env_samples)
         self.cdf = self.tri_q = None
         self.moments = bool(moments)
         self.mom = self.summary = self.noise_map = None
@@ -144,6 +151,7 @@ class DirectRenderer:
                 self.summary = adl.Buffer(dev, self._lib.pt_moments_summary_bytes(n), np.uint8)
             if self.light_choice == "power":
                 self._build_table()
+            self.set_environment(environment, env_samples)
         except Exception:
             self.release()
             raise
@@ -165,8 +173,37 @@ class DirectRenderer:
             raise ValueError("candidates must be an integer in 1..32")
         if (int(candidates) > 1 or through_ris) and self.light_choice != "power":
             raise ValueError('candidates > 1 needs light_choice="power": the candidates are drawn from the light table')
+        if (int(candidates) > 1 or through_ris) and self.environment is not None:
+            raise ValueError("an environment renders without resampling: candidates must be 1")
         self.candidates = int(candidates)
         self._ris = shim.Ris(self.candidates) if self.candidates > 1 or through_ris else None
+
+    def _check_environment(self, environment, env_samples) -> int:
+        """what an environment asks of the renderer, refused before any device call; returns Ke"""
+        ke = check_env_samples(env_samples)
+        if environment is None:
+            if ke:
+                raise ValueError("env_samples needs an environment")
+            return 0
+        if not isinstance(environment, Environment):
+            raise TypeError("environment must be an environment.Environment")
+        if self.light_choice != "power":
+            raise ValueError('an environment needs light_choice="power"')
+        if self._ris is not None:
+            raise ValueError("an environment renders without resampling: candidates must be 1")
+        return ke
+
+    def set_environment(self, environment: Optional[Environment], env_samples: int = 0) -> None:
+        """Render under ``environment`` with ``env_samples`` environment samples per vertex from now on (None: the constant sky); the
+        map and its table are made on this device on first use and stay the environment's own.  The image of another sky is another
+        image: the next render starts again at frame 0."""
+        ke = self._check_environment(environment, env_samples)
+        self.environment, self.env_samples = environment, ke
+        self._env = None
+        if environment is not None:
+            self._env = environment.buffers(self.dev) + (environment.block(ke),)
+        self.frames_done = 0
+        self._moments_valid = False
 
     def _set_camera(self, camera: Optional[Camera]) -> None:
         self._cam = Camera.struct_of(camera)   # rejected here, before anything is enqueued
@@ -228,6 +265,11 @@ class DirectRenderer:
 
     def _call(self, p, sync) -> int:
         """the entry point's return code (a renderer with another argument list overrides this)"""
+        if self._env is not None:
+            env, env_cdf, block = self._env
+            return self._lib.pt_render_direct_env(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), self.cdf._h, self.tri_q._h, env._h,
+                                                  env_cdf._h, self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(block),
+                                                  self._cam_ref(), _handle(sync))
         if self._ris is not None:
             return self._lib.pt_render_direct_ris(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), self.cdf._h, self.tri_q._h,
                                                   self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(self._ris), self._cam_ref(),

@@ -29,6 +29,11 @@ plays no roulette and gives the parent's image bit for bit.
 (``pt_render_indirect_ris``; without ``roulette`` none is played).  It composes with ``mis``, ``roulette``, ``moments`` and
 ``render_adaptive``, which then renders its lists through ``pt_render_indirect_pixels_ris``.
 
+``environment=env, env_samples=Ke`` (with ``mis=True`` and ``light_choice="power"``) lights the scene by an octahedral sky map as
+``DirectRenderer`` does, at every vertex (``pt_render_indirect_env``): a ray that leaves the scene adds the map's texel, Ke environment
+samples per vertex find what is small and bright in the sky, and the two are balanced as the emitter samples and the BRDF ray are.
+It composes with ``roulette`` and ``moments``; not with ``candidates`` or ``render_adaptive``.
+
 ``render_adaptive`` (with ``moments=True``) spends later frames only on the pixels that are still noisy: after a uniform start the
 device lists the pixels whose own relative standard error lies above a tolerance (``pt_adaptive_select``), renders further frames of
 the listed pixels only (``pt_render_indirect_pixels``), each from its own frame number, and counts them (``pt_sample_moments_pixels``)
@@ -92,6 +97,8 @@ class IndirectRenderer(DirectRenderer):
         self.max_bounces = int(max_bounces)
         self.mis = bool(mis)
         self.roulette = Roulette.of(roulette)
+        if kw.get("environment") is not None and not self.mis:
+            raise ValueError("an environment needs mis=True: the sky is balanced against the BRDF ray")
         self._rr = None if self.roulette is None else shim.Roulette(self.roulette.first_bounce, self.roulette.max_survival)
         self.counts = None
         self.pixel_list = None      # the list of render_adaptive, allocated by its first call
@@ -114,6 +121,12 @@ class IndirectRenderer(DirectRenderer):
 
     def _call(self, p, sync) -> int:
         scene3 = (self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h())
+        if self._env is not None:
+            env, env_cdf, block = self._env
+            rr = self._rr if self._rr is not None else shim.Roulette(65535, 1.0)   # (no roulette: a first bounce no path reaches)
+            return self._lib.pt_render_indirect_env(*scene3, _handle(self.counts), _handle(self.cdf), _handle(self.tri_q), env._h, env_cdf._h,
+                                                    self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(rr), ctypes.byref(block),
+                                                    self._cam_ref(), _handle(sync))
         if self._ris is not None:
             rr = self._rr if self._rr is not None else shim.Roulette(65535, 1.0)   # (no roulette: a first bounce no path reaches)
             return self._lib.pt_render_indirect_ris(*scene3, *self._estimator(), self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(rr),
@@ -146,6 +159,12 @@ class IndirectRenderer(DirectRenderer):
         super().set_camera(camera)
         self._adaptive = False
 
+    def set_environment(self, environment, env_samples: int = 0) -> None:
+        if environment is not None and not self.mis:
+            raise ValueError("an environment needs mis=True: the sky is balanced against the BRDF ray")
+        super().set_environment(environment, env_samples)
+        self._adaptive = False
+
     def sample_counts(self) -> np.ndarray:
         """uint32 per local pixel: the samples the pixel has received since the last start at frame 0, finite or rejected (n +
         rejected of its moments); synchronises."""
@@ -173,6 +192,8 @@ class IndirectRenderer(DirectRenderer):
         for bit.  Returns ``AdaptiveResult``.  Afterwards ``render`` accepts frame_begin 0 only; ``variance``, ``noise`` and
         ``sample_counts`` work as they are, and a further ``render_adaptive`` goes on from the pixels' own counts."""
         self._need_moments()
+        if self._env is not None:
+            raise ValueError("render_adaptive does not render under an environment")
         tolerance, floor = float(tolerance), float(floor)
         min_samples, max_samples = int(min_samples), int(max_samples)
         fpp = self.chunk_frames if frames_per_pass is None else int(frames_per_pass)

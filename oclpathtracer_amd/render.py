@@ -175,7 +175,7 @@ class Renderer:
 
     def direct_renderer(self, **kw):
         """A :class:`direct.DirectRenderer` of this renderer's image over its triangle and material buffers (keyword arguments:
-        DirectRenderer's, ``light_choice``, ``candidates`` and ``moments`` among them; the image size, camera and sharding default to this renderer's): direct-illumination renders and renders
+        DirectRenderer's, ``light_choice``, ``candidates``, ``environment`` / ``env_samples`` and ``moments`` among them; the image size, camera and sharding default to this renderer's): direct-illumination renders and renders
         share the device's prepared scene and LBVH.  Without ``lights`` the list is ``scene.emitters`` of the scene read back from
         the buffers (which waits for the device, once).  Release it before the renderer."""
         from .direct import DirectRenderer
@@ -184,7 +184,7 @@ class Renderer:
 
     def indirect_renderer(self, **kw):
         """An :class:`indirect.IndirectRenderer` over this renderer's buffers, as :meth:`direct_renderer` gives a DirectRenderer
-        (keyword arguments: IndirectRenderer's, ``max_bounces``, ``mis``, ``light_choice``, ``candidates``, ``roulette`` and ``moments`` among them)."""
+        (keyword arguments: IndirectRenderer's, ``max_bounces``, ``mis``, ``light_choice``, ``candidates``, ``roulette``, ``environment`` / ``env_samples`` and ``moments`` among them)."""
         from .indirect import IndirectRenderer
 
         return self._lit_renderer(IndirectRenderer, kw)

@@ -152,6 +152,13 @@ class Ris(_c.Structure):
     _fields_ = [("candidates", _c.c_int32), ("reserved", _c.c_int32 * 3)]
 
 
+class Environment(_c.Structure):
+    """pt_environment (16 bytes): the octahedral sky map of pt_render_direct_env / pt_render_indirect_env -- size (N, a power of two in
+    1 .. 2048) and env_samples (Ke, 0 .. 256, per vertex); reserved must be 0."""
+
+    _fields_ = [("size", _c.c_int32), ("env_samples", _c.c_int32), ("reserved", _c.c_int32 * 2)]
+
+
 class PixelMoments(_c.Structure):
     """pt_pixel_moments (56 bytes): per channel the sum and the sum of squares of a pixel's finite samples, their number, and the
     number of samples rejected for a NaN or an infinity."""
@@ -260,6 +267,12 @@ SIGNATURES = {
     "pt_render_indirect_pixels_ris": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _H, _c.c_uint32, _c.POINTER(IndirectParams),
                                                  _c.POINTER(Roulette), _c.POINTER(Ris), _c.POINTER(Camera), _H]),
     "pt_sample_moments_pixels": (_c.c_int, [_H, _H, _H, _H, _c.c_uint32, _c.c_int32, _H]),
+    "pt_env_table_bytes": (_c.c_size_t, [_c.c_int]),
+    "pt_env_table": (_c.c_int, [_H, _H, _c.c_int, _H, _H]),
+    "pt_render_direct_env": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(DirectParams), _c.POINTER(Environment),
+                                        _c.POINTER(Camera), _H]),
+    "pt_render_indirect_env": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Roulette),
+                                          _c.POINTER(Environment), _c.POINTER(Camera), _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_bvh_snapshot": (_c.c_int, [_H, _c.POINTER(BvhInfo), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
