@@ -291,7 +291,9 @@ typedef struct pt_render_params {
     int32_t width, height;   /* cRes.x, cRes.y */
     int32_t frame_begin;     /* first cRes.z */
     int32_t frame_count;
-    int32_t max_bounces;     /* BOUNCES (16, GenerateColors.cl:5); 2 = build-defined "direct" mode */
+    int32_t max_bounces;     /* BOUNCES (16, GenerateColors.cl:5); 2 = build-defined "direct" mode.  1..65535; at most 256 on a scene of
+                              * at most 256 triangles rendered without the LBVH (PT_ERR_INVALID above that: a parked path of that
+                              * kernel keeps its bounce count in 8 bits; PT_OPT_ACCEL 2 renders such a scene at any depth) */
     int32_t num_triangles;   /* NUM_TRIANGLES (36, :6) */
     int32_t num_materials;   /* bound for the material fetch at :239 */
     int32_t stripe_rows;     /* >= 1 */

@@ -141,7 +141,7 @@ struct PtTraceParams {
     // the unstarted rest of its batch) to its region of `carry` and exits -- and the next launch of the render (carry_in_waves = the grid of this one, in
     // waves) resumes them beside its own work: no launch but a render's last (carry_out = 0: total_batches may be 0) has a tail
     // of waves running out of paths.  Which launch finishes a path never affects its result.
-    uint32_t* carry;              // PT_CARRY_STRIDE_DW dwords per wave of the grid
+    uint32_t* carry;              // per wave of the grid PT_CARRY_HIT_STRIDE_DW dwords (table kernels) or PT_CARRY_STRIDE_DW (LBVH kernel)
     uint32_t carry_in_waves;
     uint32_t carry_out;
     PtCamera cam;                 // read from the kernarg segment where rays are generated and where pass 1 checks a ray (every kernel)
@@ -153,7 +153,12 @@ struct PtTraceParams {
 #define PT_QUEUE_STOP_WORD (PT_QUEUE_SHARDS * PT_QUEUE_SHARD_WORDS)
 #define PT_QUEUE_WORDS ((PT_QUEUE_SHARDS + 1) * PT_QUEUE_SHARD_WORDS)
 #define PT_CARRY_RECORDS 64       // a wave stops with an empty pool and parks its (at most 64) live paths
-#define PT_CARRY_STRIDE_DW (16 + PT_CARRY_RECORDS * 15)   // header (paths, pix, end, ring frame, absolute frame) + the parked-path record as arrays
+#define PT_CARRY_STRIDE_DW (16 + PT_CARRY_RECORDS * 15)   // header (paths, pix, end, ring frame, absolute frame) + the parked-path record as arrays (the LBVH kernel's)
+// the table kernels park SEARCHED paths (pt_trace_body): 18 dwords a record -- hit point, direction, mask, L, seed, ro, hu, hv, fl | bounce, triangle
+#define PT_CARRY_HIT_STRIDE_DW (16 + PT_CARRY_RECORDS * 18)
+// The kernel with the table in LDS packs fl | bounce << 16 | triangle << 24 into one dword (17 a record: what lets its pools fit 8 workgroups
+// a CU): a parked path's bounce count, below max_bounces, must fit 8 bits, and so must its triangle (PT_LDS_TRI_MAX).  The host refuses a deeper render on that kernel (pt_shim.hip: render_part).
+#define PT_PACKED_BOUNCE_MAX 256
 
 struct PtFoldParams {
     const float* rad;   // [frame_count][npix_local][3]

@@ -1000,18 +1000,24 @@ PTK_DEV unsigned pt_ring_offset(unsigned lp, unsigned frame)
 
 
 // ---- shade one bounce of a live path (:229-258); on path end store its radiance --------------------
-// Returns true when the path has finished (its radiance is stored, what is left in `s` is dead).  The caller decides how it keeps
-// "alive": the table kernels as a wave-uniform lane mask (pt_trace_body), the LBVH kernel as a per-lane flag (pt_shade below).
+// Three parts, which the LBVH kernel runs as one (pt_shade_path below) and the table kernels where their loop has them (pt_trace_body):
+// the miss, the hit, and the store of a finished path's radiance.
+
+// the ray hit nothing: the background, and the path is over (:235)
+PTK_DEV void pt_shade_miss(PtPath& s)
+{
+    const float bg = pt_max(0.45f, 0.0f);
+    s.L = add3(s.L, scale3(s.mask, bg));  // :235
+}
+
+// The ray (origin no longer needed, s.d) hit triangle hidx at p = o + d t, barycentrics (hu, hv).  Returns true when the path has
+// finished (pdf <= 0, depth); otherwise s.o / s.d are its next ray.  s.o is read only through p.
 template <bool DET_BOUNDED, bool LATE>
-PTK_DEV bool pt_shade_path(const PtTraceParams& P, PtPath& s, float tmax, float hu, float hv, int hidx)
+PTK_DEV bool pt_shade_hit(const PtTraceParams& P, PtPath& s, const f3 p, float hu, float hv, int hidx)
 {
     const pt_kargs_p K = pt_kargs();  // tris, mats, nmat, max_bounces: read here, not kept in SGPRs
     bool finished = false;
-    if (hidx < 0) {
-        const float bg = pt_max(0.45f, 0.0f);
-        s.L = add3(s.L, scale3(s.mask, bg));  // :235
-        finished = true;
-    } else {
+    {
         // The direction sample's angle first: here only the path state is live.  (pt_sincos takes its binary32 branch on every
         // angle this path forms, phi in [0, 2 pi]; its binary64 branch is dead at run time.)  Both BRDFs draw phi first, then the
         // second uniform (:163-164, :182-183).
@@ -1033,7 +1039,6 @@ PTK_DEV bool pt_shade_path(const PtTraceParams& P, PtPath& s, float tmax, float 
         int mid = __float_as_int(nid.w);
         mid = mid < 0 ? 0 : mid;
         mid = mid > nm1 ? nm1 : mid;
-        f3 p = add3(s.o, scale3(s.d, tmax));
         float w = 1.0f - hu - hv;
         f3 n = normalize3(add3(add3(scale3(N, hu), scale3(N, hv)), scale3(N, w)));
 
@@ -1122,7 +1127,13 @@ PTK_DEV bool pt_shade_path(const PtTraceParams& P, PtPath& s, float tmax, float 
             }
         }
     }
-    if (finished) {
+    return finished;
+}
+
+// the finished path's radiance goes to its record of the staging ring
+PTK_DEV void pt_path_finish(const PtPath& s)
+{
+    {
         // :260; the w lane of the reference's float4 is overwritten with 1.0 by gammaCorrect (:293) and never read
         // before: three floats per sample are staged, not four (measured at the full 256 spp, profiles/r02/
         // pmc_r02_summary.txt: 35.2 bytes of HBM traffic per sample against 41.0 with aligned 16-byte records --
@@ -1153,6 +1164,21 @@ PTK_DEV bool pt_shade_path(const PtTraceParams& P, PtPath& s, float tmax, float 
             *reinterpret_cast<pt_f3v*>(out) = v;
         }
     }
+}
+
+// One bounce of a live path whose search returned (tmax, hu, hv, hidx).  Returns true when the path has finished (its radiance is
+// stored, what is left in `s` is dead).
+template <bool DET_BOUNDED, bool LATE>
+PTK_DEV bool pt_shade_path(const PtTraceParams& P, PtPath& s, float tmax, float hu, float hv, int hidx)
+{
+    bool finished = false;
+    if (hidx < 0) {
+        pt_shade_miss(s);
+        finished = true;
+    } else {
+        finished = pt_shade_hit<DET_BOUNDED, LATE>(P, s, add3(s.o, scale3(s.d, tmax)), hu, hv, hidx);
+    }
+    if (finished) pt_path_finish(s);
     return finished;
 }
 
@@ -1189,7 +1215,16 @@ PTK_DEV void pt_flush_counters(const PtTraceParams& P, unsigned lane, unsigned n
 //     one material, so the untaken BRDF branch is skipped wave-wide).  The following bounces refill the
 //     ~10 lanes that end per bounce from the pool, which lasts ~5 bounces -- until the next fresh phase.
 // Which lane runs which sample, and in which order, never affects a sample's result.
-#define PT_POOL 64  // parked-path slots per wave (a fresh phase parks at most 64 live paths)
+//
+// The pool holds SEARCHED paths.  Lanes die at the search far more often than in shading (an open scene: 9 of 10 samples end at a
+// miss), so a pool of paths waiting for their search -- parked and resumed before it -- left every lane whose ray missed idle through
+// the shading phase that followed.  With hit records in the pool such a lane finishes the moment the search returns, takes a parked
+// path on the spot and shades it in the same iteration: shading runs with every lane the pool can fill (pt_trace_body).
+//
+// 68-byte records (pt_hit_store) and the 20 480 B a workgroup may have for 8 of them to fit a CU leave room for 56 per wave, not 64:
+// a fresh phase parks every live path, so it starts only when at most PT_POOL lanes are alive, i.e. at least 8 are dead.  Until then
+// the iteration goes on with its fewer than 8 idle lanes and asks again after the next search.
+#define PT_POOL 56  // parked-path slots per wave (a fresh phase parks at most PT_POOL live paths: pt_trace_body)
 
 struct PtWaveQueue {  // wave-uniform (SGPRs): the wave's current range [pix, end) of local pixels of `frame`
     unsigned pix, end, frame;   // frame: counted from the render's first frame (what a path keeps as `fl`)
@@ -1252,12 +1287,11 @@ PTK_DEV bool pt_queue_refill(const PtTraceParams& P, unsigned lane, PtWaveQueue&
     return true;
 }
 
-// The parked-path record: 60 bytes, three float4 and three dwords, wherever a path waits --
+// PtPathSlots says where a waiting path's record lives: float4 word j of record k at A[j fs + k], dword j at W[j ws + k wk] (float4
+// arrays: conflict-free b128 accesses in LDS, lane k moving entry k coalesced in a carry region).
+// The record of a path BEFORE its search (the LBVH kernel's checkpoint): 60 bytes, three float4 and three dwords --
 //   [0] o.xyz d.x   [1] d.yz mask.xy   [2] mask.z L.xyz   [3] seed, ro, fl | bounce << 16     (ro: PtPath::ro, where its radiance goes)
-// PtPathSlots says where: float4 word j of record k at A[j fs + k], dword j at W[j ws + k wk].  The pool of a wave (LDS) keeps three
-// float4 arrays of PT_POOL entries (conflict-free b128 accesses) and one array of dword triples.  (64-byte slots would put the
-// workgroup over 160 KB / 8: the LDS is what decides whether 8 workgroups -- 8 waves per SIMD -- fit a CU.)  A carry region keeps
-// three float4 arrays and three dword arrays of PT_CARRY_RECORDS entries (lane k moves entry k, coalesced).
+// in three float4 arrays and three dword arrays of PT_CARRY_RECORDS entries.
 struct PtPathSlots {
     float4* A;
     unsigned* W;
@@ -1266,9 +1300,68 @@ struct PtPathSlots {
     PTK_DEV unsigned& word(unsigned j, unsigned k) const { return W[j * ws + wk * k]; }
 };
 
-#define PT_POOL_DWORDS (PT_POOL * 15)
-PTK_DEV PtPathSlots pt_pool_slots(float4* pool) { return { pool, reinterpret_cast<unsigned*>(pool + 3 * PT_POOL), PT_POOL, 1u, 3u }; }
 PTK_DEV PtPathSlots pt_carry_slots(uint32_t* region) { return { (float4*)(region + 16), region + 16 + PT_CARRY_RECORDS * 12, PT_CARRY_RECORDS, PT_CARRY_RECORDS, 1u }; }
+
+// The table kernels park SEARCHED paths (pt_trace_body): the record keeps the hit, not the ray's origin and t --
+//   [0] p.xyz d.x   [1] d.yz mask.xy   [2] mask.z L.xyz   [3] seed, ro, hu, hv     (p = o + d t: all that shading reads of o)
+// and NW dwords: fl | bounce << 16 | triangle << 24 beside the LDS table (NW 1: a triangle below PT_LDS_TRI_MAX and a bounce count below
+// PT_PACKED_BOUNCE_MAX fit 8 bits each, 68 bytes a record), fl | bounce << 16 and the triangle otherwise (NW 2).  The pool keeps four
+// float4 arrays of PT_POOL entries and one array of NW dwords per record, a carry region four float4 arrays and two dword arrays of
+// PT_CARRY_RECORDS entries (PT_CARRY_HIT_STRIDE_DW: one stride for both forms).
+static_assert(PT_LDS_TRI_MAX <= 256 && PT_PACKED_BOUNCE_MAX <= 256, "triangle and bounce count of a parked path: 8 bits each of the packed word");
+template <int LDS_TABLE> __host__ __device__ constexpr unsigned pt_hit_words() { return LDS_TABLE == 1 ? 1u : 2u; }
+template <int LDS_TABLE> __host__ __device__ constexpr unsigned pt_pool_dwords() { return PT_POOL * (16u + pt_hit_words<LDS_TABLE>()); }
+// the waves' pools follow one another, and each begins with its float4 arrays: a pool is whole float4s (56 records are, 57 of 17 dwords
+// are not), or the next wave's b128 accesses are misaligned; and a stopping wave's pool goes to its region record by record
+static_assert(pt_pool_dwords<1>() % 4u == 0u && pt_pool_dwords<2>() % 4u == 0u, "a wave's pool must be a whole number of float4: the next pool's 16-byte alignment");
+static_assert(PT_POOL <= PT_CARRY_RECORDS, "a checkpoint region holds a whole pool");
+template <unsigned NW> PTK_DEV PtPathSlots pt_pool_slots(float4* pool) { return { pool, reinterpret_cast<unsigned*>(pool + 4 * PT_POOL), PT_POOL, 1u, NW }; }
+PTK_DEV PtPathSlots pt_carry_hit_slots(uint32_t* region) { return { (float4*)(region + 16), region + 16 + PT_CARRY_RECORDS * 16, PT_CARRY_RECORDS, PT_CARRY_RECORDS, 1u }; }
+
+// what a lane of a table kernel holds between the search and shading: the path (s.o is the hit point) and the hit
+struct PtHit {
+    float hu, hv;
+    int hidx;
+};
+
+template <unsigned NW>
+PTK_DEV void pt_hit_store(const PtPathSlots& S, unsigned k, const PtPath& s, const PtHit& h)
+{
+    S.vec(0, k) = make_float4(s.o.x, s.o.y, s.o.z, s.d.x);
+    S.vec(1, k) = make_float4(s.d.y, s.d.z, s.mask.x, s.mask.y);
+    S.vec(2, k) = make_float4(s.mask.z, s.L.x, s.L.y, s.L.z);
+    S.vec(3, k) = make_float4(__uint_as_float(s.seed), __uint_as_float(s.ro), h.hu, h.hv);
+    const unsigned w = s.fl | ((unsigned)s.bounce << 16);  // fl below 65 536 (pt_render_frames checks: the ring has fewer frames); a parked path hit: hidx >= 0
+    if (NW == 1u) {
+        S.word(0, k) = w | ((unsigned)h.hidx << 24);       // bounce < max_bounces <= PT_PACKED_BOUNCE_MAX (render_part checks), hidx < PT_LDS_TRI_MAX
+    } else {
+        S.word(0, k) = w;                                  // bounce < max_bounces <= 65 535 (pt_render_frames checks)
+        S.word(1, k) = (unsigned)h.hidx;
+    }
+}
+
+template <unsigned NW>
+PTK_DEV void pt_hit_load(const PtPathSlots& S, unsigned k, PtPath& s, PtHit& h)
+{
+    const float4 a0 = S.vec(0, k), a1 = S.vec(1, k), a2 = S.vec(2, k), a3 = S.vec(3, k);
+    const unsigned w = S.word(0, k);
+    s.o = mk3(a0.x, a0.y, a0.z);
+    s.d = mk3(a0.w, a1.x, a1.y);
+    s.mask = mk3(a1.z, a1.w, a2.x);
+    s.L = mk3(a2.y, a2.z, a2.w);
+    s.seed = __float_as_uint(a3.x);
+    s.ro = __float_as_uint(a3.y);
+    h.hu = a3.z;
+    h.hv = a3.w;
+    s.fl = w & 0xffffu;
+    if (NW == 1u) {
+        s.bounce = (int)((w >> 16) & 0xffu);
+        h.hidx = (int)(w >> 24);
+    } else {
+        s.bounce = (int)(w >> 16);
+        h.hidx = (int)S.word(1, k);
+    }
+}
 
 PTK_DEV void pt_path_store(const PtPathSlots& S, unsigned k, const PtPath& s)
 {
@@ -1295,18 +1388,20 @@ PTK_DEV void pt_path_load(const PtPathSlots& S, unsigned k, PtPath& s)
 }
 
 // (alive: the wave's live lanes as a lane mask, here and in pt_pool_pop / pt_start_fresh -- see pt_trace_body)
-PTK_DEV void pt_pool_push(float4* pool, unsigned& pool_n, const PtPath& s, pt_lanes& alive)
+template <unsigned NW>
+PTK_DEV void pt_pool_push(float4* pool, unsigned& pool_n, const PtPath& s, const PtHit& h, pt_lanes& alive)
 {
     const pt_lanes live = alive;
     if (PT_ON(live)) {
-        const unsigned k = pool_n + pt_mbcnt(live);
-        pt_path_store(pt_pool_slots(pool), k, s);
+        const unsigned k = pool_n + pt_mbcnt(live);   // (below PT_POOL: the caller parks into an empty pool at most PT_POOL live paths)
+        pt_hit_store<NW>(pt_pool_slots<NW>(pool), k, s, h);
     }
     pool_n += (unsigned)__popcll(live);
     alive = 0ull;
 }
 
-PTK_DEV void pt_pool_pop(float4* pool, unsigned& pool_n, PtPath& s, pt_lanes& alive)
+template <unsigned NW>
+PTK_DEV void pt_pool_pop(float4* pool, unsigned& pool_n, PtPath& s, PtHit& h, pt_lanes& alive)
 {
     const pt_lanes need = ~alive;
     const unsigned n_need = (unsigned)__popcll(need);
@@ -1321,7 +1416,7 @@ PTK_DEV void pt_pool_pop(float4* pool, unsigned& pool_n, PtPath& s, pt_lanes& al
     const pt_lanes taking = need & PT_LANES(rank < take);   // the first `take` dead lanes
     if (PT_ON(taking)) {
         const unsigned k = pool_n - 1u - rank;
-        pt_path_load(pt_pool_slots(pool), k, s);
+        pt_hit_load<NW>(pt_pool_slots<NW>(pool), k, s, h);
     }
     alive |= taking;
     pool_n -= take;
@@ -1334,7 +1429,8 @@ PTK_DEV void pt_pool_pop(float4* pool, unsigned& pool_n, PtPath& s, pt_lanes& al
 // ---- checkpointed launches (PtTraceParams::carry) ---------------------------------------------------------------------
 // A wave stops only where its pool is empty and a fresh phase would begin: it parks its live paths exactly as a fresh phase does
 // (the bounce loop's own pt_pool_push site -- a second copy of that code after the loop cost fourteen spilled registers INSIDE
-// the loop) and leaves; the pool then goes to the wave's region: 16 header dwords and n parked-path records (pt_path_store).
+// the loop) and leaves; the pool then goes to the wave's region: 16 header dwords and n records of searched paths (pt_hit_store), the
+// regions PT_CARRY_HIT_STRIDE_DW apart.  (The LBVH kernel's regions: n records of pt_path_store, PT_CARRY_STRIDE_DW apart.)
 
 // the header: n paths, the rest of the batch, the wave's tallies.  The tallies travel with the checkpoint and reach the stats buffer
 // at the end of the render's last launch, where the waves leave one by one: 8 192 waves leaving TOGETHER, two or three atomics each
@@ -1350,16 +1446,17 @@ PTK_DEV void pt_carry_header(uint32_t* region, unsigned n, const PtWaveQueue& q,
     region[6] = n_carried + n + (q.end - q.pix);
 }
 
+template <unsigned NW>
 PTK_DEV void pt_carry_store(uint32_t* region, unsigned lane, float4* pool, unsigned pool_n, const PtWaveQueue& q, unsigned n_rays, unsigned n_samples,
                             unsigned n_carried)
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the wave's own pool writes, read by other lanes: as in pt_pool_pop
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < pool_n) {
-        const PtPathSlots from = pt_pool_slots(pool), to = pt_carry_slots(region);
-        for (unsigned j = 0; j < 3u; ++j) to.vec(j, lane) = from.vec(j, lane);
-        for (unsigned j = 0; j < 3u; ++j) to.word(j, lane) = from.word(j, lane);
+    if (lane < pool_n) {   // (pool_n <= PT_POOL <= PT_CARRY_RECORDS)
+        const PtPathSlots from = pt_pool_slots<NW>(pool), to = pt_carry_hit_slots(region);
+        for (unsigned j = 0; j < 4u; ++j) to.vec(j, lane) = from.vec(j, lane);
+        for (unsigned j = 0; j < NW; ++j) to.word(j, lane) = from.word(j, lane);
     }
     if (lane == 0u) pt_carry_header(region, pool_n, q, n_rays, n_samples, n_carried);
 }
@@ -1377,11 +1474,11 @@ PTK_DEV void pt_carry_store_lanes(uint32_t* region, unsigned lane, const PtPath&
     if (lane == 0u) pt_carry_header(region, n_live, q, n_rays, n_samples, n_carried);
 }
 
-// resumes a checkpoint: the parked paths go straight into lanes (at most 64: the pool was empty when they were parked), the rest
-// of the batch becomes the wave's current range
+// Resuming a checkpoint.  The header first, for either kernel: the tallies, and the rest of the batch becomes the wave's current
+// range; returns the number of records.  Then the records go straight into lanes (at most 64: the pool was empty when they were
+// parked) -- pt_carry_load for the LBVH kernel's paths, pt_carry_hit_load for the table kernels' searched ones.
 template <bool LATE>
-PTK_DEV void pt_carry_load(const PtTraceParams& P, uint32_t* region, unsigned lane, PtPath& s, bool& alive, PtWaveQueue& q, unsigned& n_rays,
-                           unsigned& n_samples, unsigned& n_carried)
+PTK_DEV unsigned pt_carry_header_load(const PtTraceParams& P, const uint32_t* region, PtWaveQueue& q, unsigned& n_rays, unsigned& n_samples, unsigned& n_carried)
 {
     const pt_kargs_p K = pt_kargs();
     const unsigned n = __builtin_amdgcn_readfirstlane(region[0]);
@@ -1392,8 +1489,28 @@ PTK_DEV void pt_carry_load(const PtTraceParams& P, uint32_t* region, unsigned la
     q.end = __builtin_amdgcn_readfirstlane(region[2]);
     q.frame = __builtin_amdgcn_readfirstlane(region[3]);
     pt_queue_locate<LATE>(P, K, q);
+    return n;
+}
+
+template <bool LATE>
+PTK_DEV void pt_carry_load(const PtTraceParams& P, uint32_t* region, unsigned lane, PtPath& s, bool& alive, PtWaveQueue& q, unsigned& n_rays,
+                           unsigned& n_samples, unsigned& n_carried)
+{
+    const unsigned n = pt_carry_header_load<LATE>(P, region, q, n_rays, n_samples, n_carried);
     if (lane < n) {
         pt_path_load(pt_carry_slots(region), lane, s);
+        alive = true;
+    }
+}
+
+// the table kernels': the records are searched paths (pt_hit_store; NW as the kernel that stored them, the same kernel of the same render)
+template <bool LATE, unsigned NW>
+PTK_DEV void pt_carry_hit_load(const PtTraceParams& P, uint32_t* region, unsigned lane, PtPath& s, PtHit& h, bool& alive, PtWaveQueue& q, unsigned& n_rays,
+                               unsigned& n_samples, unsigned& n_carried)
+{
+    const unsigned n = pt_carry_header_load<LATE>(P, region, q, n_rays, n_samples, n_carried);
+    if (lane < n) {
+        pt_hit_load<NW>(pt_carry_hit_slots(region), lane, s, h);
         alive = true;
     }
 }
@@ -1503,7 +1620,8 @@ PTK_DEV PtPath pt_path_idle()  // what a lane without a path holds
 // and so would everything computed from it (the addresses that use it live in SGPRs)
 PTK_DEV unsigned pt_wave_in_wg() { return (unsigned)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
 PTK_DEV unsigned pt_wave() { return blockIdx.x * (PT_TRACE_THREADS / 64) + pt_wave_in_wg(); }
-PTK_DEV uint32_t* pt_carry_region(uint32_t* carry, unsigned wave) { return carry + (size_t)wave * PT_CARRY_STRIDE_DW; }
+// (stride: PT_CARRY_STRIDE_DW for the LBVH kernel, PT_CARRY_HIT_STRIDE_DW for the table kernels)
+PTK_DEV uint32_t* pt_carry_region(uint32_t* carry, unsigned wave, unsigned stride = PT_CARRY_STRIDE_DW) { return carry + (size_t)wave * stride; }
 
 // this wave's pass-2 tail: 64 key slots at w, then the pending-pair ring; tile: its record tile (TILED mode only)
 PTK_DEV PtTail pt_tail_init(pt_lds_u32* w, unsigned tile, unsigned lane)
@@ -1529,13 +1647,13 @@ PTK_DEV void pt_lds_table_load(const PtPrepTriangle* tris, int n)
 }
 
 // ---- the LDS of a table-kernel workgroup, in dwords (the bodies, ptk_trace_lds_bytes): the triangle table (LDS_TABLE 1,
-// ntri <= PT_LDS_TRI_MAX), then the waves' pools of parked paths (PT_POOL_DWORDS each), then their pass-2 tails (64 x 8 B keys + PT_TAIL_LIST
+// ntri <= PT_LDS_TRI_MAX), then the waves' pools of parked paths (pt_pool_dwords each), then their pass-2 tails (64 x 8 B keys + PT_TAIL_LIST
 // pairs of 2 B beside the table, of 4 B without), then their record tiles of the current 32-triangle chunk (LDS_TABLE 2: TILED)
 #define PT_LDS_TILE_DW (32u * PT_LDS_TRI_STRIDE)
 template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_tail_dw() { return 128u + (LDS_TABLE == 1 ? PT_TAIL_LIST / 2u : PT_TAIL_LIST); }
 template <int LDS_TABLE> __host__ __device__ __forceinline__ unsigned pt_lds_pools(int ntri) { return LDS_TABLE == 1 ? ntri * PT_LDS_TRI_STRIDE : 0; }
 // (POOLS = false: the brute-force query and AO kernels, which park nothing)
-template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ unsigned pt_lds_tails(int ntri) { return pt_lds_pools<LDS_TABLE>(ntri) + (POOLS ? (PT_TRACE_THREADS / 64) * PT_POOL_DWORDS : 0u); }
+template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ unsigned pt_lds_tails(int ntri) { return pt_lds_pools<LDS_TABLE>(ntri) + (POOLS ? (PT_TRACE_THREADS / 64) * pt_pool_dwords<LDS_TABLE>() : 0u); }
 template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ unsigned pt_lds_tiles(int ntri) { return pt_lds_tails<LDS_TABLE, POOLS>(ntri) + (PT_TRACE_THREADS / 64) * pt_lds_tail_dw<LDS_TABLE>(); }
 template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ unsigned pt_lds_total(int ntri) { return pt_lds_tiles<LDS_TABLE, POOLS>(ntri) + (LDS_TABLE == 2 ? (PT_TRACE_THREADS / 64) * PT_LDS_TILE_DW : 0u); }
 
@@ -1554,7 +1672,8 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
     }
     // this wave's pool of parked paths, pass-2 tail and record tile
     const unsigned wave_in_wg = pt_wave_in_wg();
-    float4* pool = reinterpret_cast<float4*>(pt_lds_tab + pt_lds_pools<LDS_TABLE>(ntri) + wave_in_wg * PT_POOL_DWORDS);
+    constexpr unsigned NW = pt_hit_words<LDS_TABLE>();   // the parked record's dwords beside its four float4 (pt_hit_store)
+    float4* pool = reinterpret_cast<float4*>(pt_lds_tab + pt_lds_pools<LDS_TABLE>(ntri) + wave_in_wg * pt_pool_dwords<LDS_TABLE>());
     unsigned pool_n = 0u;                    // parked paths (wave-uniform)
     PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_lds_tails<LDS_TABLE>(ntri) + (threadIdx.x >> 6) * pt_lds_tail_dw<LDS_TABLE>(),
                              pt_lds_tiles<LDS_TABLE>(ntri) + (threadIdx.x >> 6) * PT_LDS_TILE_DW, lane);
@@ -1564,13 +1683,17 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
     // start and finish, and used as it is where lanes are selected by it (PT_ON) -- not a per-lane 0/1 in a VGPR that every such
     // place first compares into a mask and selects back out of one.
     pt_lanes alive = 0ull;
+    // A live lane holds a SEARCHED path at the top of the loop: s with the hit point in s.o (all that shading reads of the origin) and
+    // the hit h -- or a miss (h.hidx < 0), which ends there.
     PtPath s = pt_path_idle();
+    PtHit h = { 0.0f, 0.0f, -1 };
+    pt_lanes ended = 0ull;   // lanes whose path the last shading phase ended: their radiance goes out with the misses', at the loop's one store
     unsigned n_rays = 0, n_samples = 0, n_carried = 0;   // (n_carried: samples this wave's checkpoints have handed on, PT_STAT_CARRIED)
-    // checkpointed launches: resume what the previous launch of the render left in this wave's region
+    // checkpointed launches: resume what the previous launch of the render left in this wave's region (searched paths, all of them hits)
     const unsigned wave = pt_wave();
     if (wave < P.carry_in_waves) {
         bool resumed = false;
-        pt_carry_load<true>(P, pt_carry_region(P.carry, wave), lane, s, resumed, q, n_rays, n_samples, n_carried);
+        pt_carry_hit_load<true, NW>(P, pt_carry_region(P.carry, wave, PT_CARRY_HIT_STRIDE_DW), lane, s, h, resumed, q, n_rays, n_samples, n_carried);
         alive = PT_LANES(resumed);
     }
     q.g = wave & (PT_QUEUE_SHARDS - 1u);   // the wave's first shard of this launch's queue
@@ -1578,29 +1701,58 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, c_regen = 0, c_loop = 0, c_shade = 0, c_iters = 0, c_steps = 0, c_p1 = 0;
 #endif
 
+    // One iteration: the paths the search ended (misses) and the ones shading ended store their radiance; dead lanes take parked
+    // paths -- or, when the pool is empty, the live ones are parked and 64 fresh samples start (no shading then: straight to their
+    // search, and round again); the live lanes, every one with a hit, shade; the lanes that shading left with a new ray search.
+    // Each of these -- the store, the park, the pop, shading, the search -- has ONE site in the loop (a second copy of the park code once
+    // cost fourteen spilled registers inside it).
     for (;;) {
         PT_STAMP(t0);
-        bool primary = false;   // (wave-uniform) this bounce is a fresh wave of 64 primary rays ...
+        {
+            const pt_lanes missed = alive & PT_LANES(h.hidx < 0);
+            if (PT_ON(missed)) pt_shade_miss(s);
+            const pt_lanes over = missed | ended;   // (ended lanes left `alive` where they shaded; their L has waited in their registers)
+            if (PT_ON(over)) pt_path_finish(s);
+            n_samples += (unsigned)__popcll(over);
+            alive &= ~missed;
+            ended = 0ull;
+        }
+        bool fresh = false;     // (wave-uniform) this iteration starts samples: no shading, their primary rays are searched next ...
+        bool primary = false;   // ... as a full wave of 64 primary rays ...
         unsigned pix0 = 0u;     // ... of the local pixels pix0 + lane
         if (~alive != 0ull) {
-            if (pool_n == 0u) {
+            // (a fresh phase parks every live path: it needs room for them -- PT_POOL)
+            if (pool_n == 0u && (unsigned)__popcll(alive) <= (unsigned)PT_POOL) {
                 const int next = pt_queue_next<true>(P, lane, q, s, alive);
                 if (next != 0) {
-                    pt_pool_push(pool, pool_n, s, alive);                // park every live path ...
+                    pt_pool_push<NW>(pool, pool_n, s, h, alive);         // park every live path ...
                     if (next == 2) break;                                // ... for the next launch (a checkpoint) ...
                     primary = pt_start_fresh<true>(P, lane, q, s, alive, pix0);   // ... or start 64 coherent primary rays
+                    fresh = true;
                 }
             }
-            pt_pool_pop(pool, pool_n, s, alive);           // dead lanes resume parked paths
+            if (!fresh) pt_pool_pop<NW>(pool, pool_n, s, h, alive);   // dead lanes resume parked paths
         }
-        if (alive == 0ull) break;
+        if (!fresh && alive == 0ull) break;
         PT_STAMP(t1);
 
-        // ---- intersectWorld (:137-154) ------------------------------------------------------
+        // ---- shading: every live lane has a hit ------------------------------------------------
+        if (!fresh) {
+            bool finished = false;
+            if (PT_ON(alive)) finished = pt_shade_hit<DET_BOUNDED, true>(P, s, s.o, h.hu, h.hv, h.hidx);
+            ended = PT_LANES(finished);   // (a dead lane did not shade: its bit is 0)
+            alive &= ~ended;
+        }
+        PT_STAMP(t2);
+
+        // ---- intersectWorld (:137-154): the new rays -- of the lanes that shading left alive, or of the fresh samples --------------
         float tmax = 1e20f, hu = 0.0f, hv = 0.0f;
         int hidx = -1;
         unsigned p2steps = 0;
-        if (QUADS == 3 && DET_BOUNDED && primary && P.pmask != nullptr)
+        n_rays += (unsigned)__popcll(alive);
+        if (alive == 0ull) {
+            // (shading ended every path: nothing to search)
+        } else if (QUADS == 3 && DET_BOUNDED && primary && P.pmask != nullptr)
             p2steps = pt_intersect_primary<DET_BOUNDED, LDS_TABLE>(T, P.tris, ntri, s.o, s.d, PT_ON(alive), tmax, hu, hv, hidx, P.pmask[pix0 + lane], tl, lane,
                                                                    PT_VALIDATE_FILTER && P.stats ? P.stats + 2 : nullptr);
         else
@@ -1620,16 +1772,12 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         (void)p2steps;
 #endif
 
-        PT_STAMP(t2);
-        n_rays += (unsigned)__popcll(alive);
-        bool finished = false;
-        if (PT_ON(alive)) finished = pt_shade_path<DET_BOUNDED, true>(P, s, tmax, hu, hv, hidx);
-        const pt_lanes done = PT_LANES(finished);   // (a dead lane did not shade: its bit is 0)
-        n_samples += (unsigned)__popcll(done);
-        alive &= ~done;
+        // the searched path: its hit point by the very operations shading formed it with (:257 reads the origin only through it)
+        s.o = add3(s.o, scale3(s.d, tmax));
+        h.hu = hu; h.hv = hv; h.hidx = hidx;
 #if PT_STAMPS
         PT_STAMP(t3);
-        c_regen += t1 - t0; c_loop += t2 - t1; c_shade += t3 - t2; c_iters++;
+        c_regen += t1 - t0; c_shade += t2 - t1; c_loop += t3 - t2; c_iters++;
 #endif
     }
 
@@ -1647,7 +1795,7 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         // (a wave that left the loop because nothing was alive holds nothing: no parked path, no rest of a batch -- an empty checkpoint)
         const pt_kargs_p K = pt_kargs();
         if (K->carry_out != 0u) {
-            pt_carry_store(pt_carry_region(K->carry, wave), lane, pool, pool_n, q, n_rays, n_samples, n_carried);
+            pt_carry_store<NW>(pt_carry_region(K->carry, wave, PT_CARRY_HIT_STRIDE_DW), lane, pool, pool_n, q, n_rays, n_samples, n_carried);
             return;   // (the tallies went with it)
         }
     }
@@ -1661,7 +1809,7 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
 // 6 -> 34.1, 7 -> 32.0); three things had to give for 8: the arguments only regeneration and shading need are re-read
 // from the kernarg segment instead of living in SGPRs (pt_kargs: no v_readlane spills, 78 SGPRs), the fresh phase lost
 // its per-lane divisions and the camera basis its registers (64 VGPRs without scratch), and the LDS of a workgroup
-// shrank to 20 160 B (60-byte pool slots, 2-byte tail pairs) so that 8 workgroups fit the CU's 160 KB.
+// stays within 20 480 B (20 032: 56 pool slots of 68 bytes per wave, 2-byte tail pairs) so that 8 workgroups fit the CU's 160 KB.
 #ifndef PT_TRACE_WAVES
 #define PT_TRACE_WAVES 8
 #endif

@@ -165,7 +165,7 @@ struct pt_device_s {
     bool lanes_busy;         // lane work is enqueued that `stream` has not been ordered behind
     bool main_dirty;         // work has been enqueued on `stream` that the lanes have not been ordered behind
     uint64_t chunk_seq, render_seq;
-    PtWs<uint32_t> carry[2]; // per lane: the checkpoint regions of its renders' trace launches (PT_CARRY_STRIDE_DW dwords per wave)
+    PtWs<uint32_t> carry[2]; // per lane: the checkpoint regions of its renders' trace launches (PT_CARRY_HIT_STRIDE_DW dwords per wave)
     PtWs<uint2> pmask;       // primary-ray candidate masks of the local pixels (pt_primary_mask_kernel), for as many pixels as it holds
     struct { uint64_t scene_gen; int32_t g[7]; PtCamera cam; bool valid; } pmask_key;  // what the masks in hand were made for
     PtWs<unsigned int> counters;  // PT_QUEUE_COUNTERS work-queue counters, PT_QUEUE_STRIDE words apart: zero between launches
@@ -1409,7 +1409,9 @@ static int ensure_carry(pt_device_s* d, int blocks)
     if ((size_t)blocks * wg_waves > waves) return fail(PT_ERR_INVALID, "grid larger than the checkpoint regions");
     for (int k = 0; k < 2; ++k)
         if (!d->carry[k]) {   // once per device handle, at its first such render
-            hipError_t e = ws_malloc(d, d->carry[k], waves * PT_CARRY_STRIDE_DW * sizeof(uint32_t));
+            // (a region serves whichever kernel the render runs: the table kernels' searched-path records are the larger)
+            static_assert(PT_CARRY_HIT_STRIDE_DW >= PT_CARRY_STRIDE_DW, "a checkpoint region holds either kernel's records");
+            hipError_t e = ws_malloc(d, d->carry[k], waves * PT_CARRY_HIT_STRIDE_DW * sizeof(uint32_t));
             if (e != hipSuccess) return fail(PT_ERR_OOM, "checkpoint buffer allocation failed: %s", hipGetErrorString(e));
         }
     return PT_OK;
@@ -1424,6 +1426,10 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
     PtSearch search;
     if ((rc = prepare_search(d, tris, rp.num_triangles, cam.eye, search))) return rc;
     const bool use_bvh = search.mode.bvh;
+    // the kernel with the table in LDS parks a path's bounce count in 8 bits (PT_PACKED_BOUNCE_MAX)
+    if (!use_bvh && rp.num_triangles <= PT_LDS_TRI_MAX && rp.max_bounces > PT_PACKED_BOUNCE_MAX)
+        return fail(PT_ERR_INVALID, "max_bounces above %d on a scene of at most %d triangles without the LBVH (a parked path packs its bounce count in 8 bits)",
+                    PT_PACKED_BOUNCE_MAX, PT_LDS_TRI_MAX);
     int nchunks, chunk;
     if ((rc = plan_chunks(d, rp.frame_count, npix, nchunks, chunk))) return rc;
     const bool want_pmask = d->opt_pmask && search.mode.quads == 3 && !use_bvh && rp.num_triangles <= 64 && search.mode.det_bounded;

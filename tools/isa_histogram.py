@@ -2,7 +2,7 @@
 """Instruction classes of the trace kernel's bounce loop, by phase, weighted by the phases' measured time shares.
 
 The PT_STAMPS=1 diagnostic build brackets the loop's phases with s_memtime (csrc/pt_kernels.hip: t0 loop top, t1 after regeneration,
-ta / tb around pass 1 of the closest-hit search, t2 after pass 2, t3 after shading); tools/stamps.py measures the phases' shares of a
+t2 after shading, ta / tb around pass 1 of the closest-hit search that follows it, t3 after pass 2); tools/stamps.py measures the phases' shares of a
 wave-bounce on the GPU.  This script compiles that build to assembly (no GPU needed), cuts the loop of pt_trace_kernel<true,1,3>
 at the stamps, classifies every instruction between two stamps, and prints per class
     sum over phases of  (time share of the phase) x (class's share of the phase's VALU instructions)
@@ -50,8 +50,8 @@ def main():
     t = open(ASM).read()
     a = t.index(KERNEL + ":"); b = t.index(".Lfunc_end", a)
     lines = t[a:b].split("\n")
-    stamps = [i for i in range(len(lines)) if "s_memtime" in lines[i]]   # t0 t1 ta tb t2 t3, in program order (the kernel has no others)
-    names = ["regeneration (t0-t1)", "search set-up (t1-ta)", "pass 1 (ta-tb)", "pass 2 (tb-t2)", "shading (t2-t3)"]
+    stamps = [i for i in range(len(lines)) if "s_memtime" in lines[i]]   # t0 t1 t2 ta tb t3, in program order (the kernel has no others)
+    names = ["regeneration (t0-t1)", "shading (t1-t2)", "search set-up (t2-ta)", "pass 1 (ta-tb)", "pass 2 (tb-t3)"]
     if len(stamps) != 6:
         print("expected 6 stamps in the kernel, found %d at %r" % (len(stamps), stamps)); sys.exit(1)
     args = [float(x) for x in sys.argv[1:5]]
@@ -60,7 +60,7 @@ def main():
         m = re.search(r"shares: regen ([\d.]+) pass1 ([\d.]+) pass2 ([\d.]+) shade ([\d.]+)", open(f).read()) if os.path.exists(f) else None
         args = [float(x) for x in m.groups()] if m else [6.5, 29.5, 30.7, 33.3]
     regen, p1, p2, shade = args
-    share = {names[0]: regen, names[1]: 0.0, names[2]: p1, names[3]: p2, names[4]: shade}   # (the set-up is inside the "loop" figure of stamps.py: counted with pass 2)
+    share = {names[0]: regen, names[1]: shade, names[2]: 0.0, names[3]: p1, names[4]: p2}   # (the set-up is inside the "loop" figure of stamps.py: counted with pass 2)
     hist, per_phase = {}, {}
     for k, name in enumerate(names):
         counts = {}
@@ -71,11 +71,11 @@ def main():
             counts[c] = counts.get(c, 0) + 1
         per_phase[name] = counts
     # the set-up's instructions run once per bounce like pass 2's head: fold them into pass 2
-    for c, n in per_phase[names[1]].items(): per_phase[names[3]][c] = per_phase[names[3]].get(c, 0) + n
+    for c, n in per_phase[names[2]].items(): per_phase[names[4]][c] = per_phase[names[4]].get(c, 0) + n
     valu = lambda c: not c in ("LDS", "vector memory", "scalar memory", "SALU / branch / wait", "other")
     print("static instructions of the bounce loop of %s (PT_STAMPS=1 build), by phase; shares of a wave-bounce: regeneration %.1f %%, pass 1 %.1f %%, pass 2 %.1f %%, shading %.1f %%"
           % ("pt_trace_kernel<true,1,3>", regen, p1, p2, shade))
-    for name in (names[0], names[2], names[3], names[4]):
+    for name in (names[0], names[3], names[4], names[1]):
         counts = per_phase[name]
         nv = sum(n for c, n in counts.items() if valu(c))
         print("\n%s: %d instructions, %d of them VALU" % (name, sum(counts.values()), nv))
@@ -92,10 +92,10 @@ def main():
 # same; a 64-bit move as two), v_mov_b32 v,s 4.38, a lane access 4.39
 PRICE = {"constant": 2.38, "vgpr": 2.38, "sgpr": 4.38, "lane": 4.39}
 PHASES = ("regeneration", "pass 1", "pass 2", "shading")
-REGEN_FN = re.compile(r"pt_(queue_|pool_|path_|start_fresh|sample_begin|generate_ray|camera_|pixel_|stripe_row|ring_offset|carry_|mbcnt|hash)")
+REGEN_FN = re.compile(r"pt_(queue_|pool_|path_|hit_|shade_miss|start_fresh|sample_begin|generate_ray|camera_|pixel_|stripe_row|ring_offset|carry_|mbcnt|hash)")
 PASS1_FN = re.compile(r"pt_(quad3_pass1|pk_|push_flag|tri_pass1|load_tri)")
 PASS2_FN = re.compile(r"pt_(pass2_|tri_pass2|tail_|tri_candidate|fetch_rec|from_lane|stage_tile|intersect_primary)")
-SHADE_FN = re.compile(r"pt_shade")
+SHADE_FN = re.compile(r"pt_shade(?!_miss)")   # (the miss part runs with the store, at the top of the iteration)
 
 def source_phases(src):
     """line of pt_kernels.hip -> phase, from the function the line is in (and, inside the loop's own functions, from where in them)"""
@@ -109,8 +109,8 @@ def source_phases(src):
             if "if (!alive) m = 0u" in l: mark = "pass 2"
             phase[i] = mark or "pass 1"
         elif fn == "pt_trace_body":
-            if "PT_STAMP(t1)" in l: mark = "pass 2"       # (the search's call: its set-up and whatever is left of it there)
-            if "PT_STAMP(t2)" in l: mark = "shading"
+            if "PT_STAMP(t1)" in l: mark = "shading"
+            if "PT_STAMP(t2)" in l: mark = "pass 2"       # (the search's call: its set-up and whatever is left of it there)
             phase[i] = mark or "regeneration"
         elif SHADE_FN.match(fn): phase[i] = "shading"
         elif PASS1_FN.match(fn): phase[i] = "pass 1"

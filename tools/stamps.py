@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: per-phase s_memtime shares of the trace kernel (needs the PT_STAMPS=1 build).
+A wave-iteration is one round of the bounce loop.  One that starts fresh samples has no shading phase (the primary rays go straight to the
+search), so shading phases = wave-iterations - fresh phases; on an image of whole waves and batches a fresh phase starts 64 samples.
 usage: PT_SHIM_LIB=.../libptshim_stamps.so python tools/stamps.py [W H spp depth]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,6 +27,10 @@ if variant == 1:  # stats[6] = pass-1 ticks, a part of c_loop
 tot = c_regen + c_loop + c_shade + c_sort
 print("variant", variant, " stats[7] per wave-iteration (v1: pass-2 steps, v2: triangles fully tested): %.1f" % (c_full / max(iters, 1)))
 print("samples %d rays %d wave-iterations %d  lanes busy per iteration %.1f/64" % (samples, rays, iters, rays / max(iters, 1)))
+if (W * H) % 128 == 0:  # whole waves and whole batches: every fresh phase starts 64 samples, and its iteration has a search but no shading
+    fresh = samples // 64
+    print("fresh phases %d  search phases %d (%.4f per sample)  shading phases %d (%.4f per sample)  lanes per secondary search %.1f/64"
+          % (fresh, iters, iters / max(samples, 1), iters - fresh, (iters - fresh) / max(samples, 1), (rays - samples) / max(iters - fresh, 1)))
 for n, c in (("regen", c_regen), ("sort", c_sort), ("loop", c_loop), ("shade", c_shade)):
     print("%-6s %5.1f%%   %.0f ticks per wave-iteration" % (n, 100.0 * c / max(tot, 1), c / max(iters, 1)))
 if variant == 1:
