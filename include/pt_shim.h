@@ -188,7 +188,18 @@ enum pt_option {
     /* read-only (pt_device_get_option): LBVH builds this handle has made.  A scene is built once; a triangle buffer the caller can
      * write behind the ABI (pt_buffer_wrap, pt_buffer_device_ptr) is prepared again for every render, and built again only when the
      * checksum of its records has changed. */
-    PT_OPT_BVH_BUILD_COUNT = 11
+    PT_OPT_BVH_BUILD_COUNT = 11,
+    /* 1 (default): for quad scenes of up to 64 triangles on the brute-force path, the scene upload also tabulates, per cell of
+     * (triangle a ray leaves, tile of that triangle's plane, cell of a cube map of directions), a conservative candidate set of
+     * the triangles such a ray can meet; a path's secondary rays then look their candidates up instead of running the pass-1
+     * filter.  The table depends on the scene alone -- a camera change or another image size does no table work -- and is part of
+     * the handle's workspace (pt_device_workspace_memory; 442 368 bytes per triangle: 15.9 MB for the Cornell box's 36).  A ray the table does not cover (an origin
+     * further than about 0.01 from the triangle it left, a direction that is not of unit length) keeps every triangle; a scene with a triangle for which no table is made (degenerate; a height of less than about 0.65, against
+     * which the rays' 0.01 offset is not small; too far from the origin of coordinates for the classification's rounding) declines the
+     * table and renders through pass 1, as the parent of this option did.  The scene's first render builds the table (about 23 ms for
+     * the Cornell box) and, once per scene, waits for the device to read the prepared records back.  0 = off:
+     * secondary rays run pass 1 (A/B timing, parity tests).  Identical pixels either way. */
+    PT_OPT_SECONDARY_MASKS = 12
 };
 int pt_device_set_option(pt_device_t dev, int option, int64_t value);
 int64_t pt_device_get_option(pt_device_t dev, int option);
@@ -1014,6 +1025,15 @@ int pt_bvh_snapshot(pt_device_t dev, pt_bvh_info* info, void* records, size_t re
  * PT_ERR_INVALID when no table stands (no render has used masks yet, or its scene has been replaced), PT_ERR_RANGE when
  * capacity is too small (num_pixels is still filled). */
 int pt_primary_mask_snapshot(pt_device_t dev, uint32_t* num_pixels, void* masks, size_t capacity);
+
+/* Test hook: a read-only copy of the secondary-ray candidate masks of the scene in hand (PT_OPT_SECONDARY_MASKS).  `info` receives
+ * {entries, triangles, T, C}: entries = triangles * T * T * 6 * C * C; entry ((k T + iu) T + iv) 6 C C + (face C + ia) C + ib is the
+ * cell of origin triangle k, tile (iu, iv) of its plane and direction cell (face, ia, ib) -- csrc/pt_secmask.h says which rays map
+ * to it -- in the word format of pt_primary_mask_snapshot.  `masks` (may be NULL) receives 8 bytes per entry; `capacity` entries
+ * must fit.  It changes nothing: no table is made, no scene is prepared.  PT_ERR_INVALID when no table stands for the prepared
+ * scene (none rendered yet, or the scene declined it: more than 64 triangles, not made of quads, through the LBVH, the option 0 at
+ * every render so far), PT_ERR_RANGE when capacity is too small (info is still filled). */
+int pt_secondary_mask_snapshot(pt_device_t dev, uint32_t info[4], void* masks, size_t capacity);
 
 /* Scatter the gathered per-rank local framebuffers (n_ranks slabs of slab_rows x width
  * float4 each, slab k = rank k) into the full image (height x width float4). */

@@ -145,6 +145,9 @@ struct PtTraceParams {
     uint32_t carry_in_waves;
     uint32_t carry_out;
     PtCamera cam;                 // read from the kernarg segment where rays are generated and where pass 1 checks a ray (every kernel)
+    const uint2* smask;           // quad mode 3, <= 64 triangles: the scene's table of secondary-ray candidate masks (pt_secmask.h: the
+                                  // classification records, then one uint2 per cell); null = pass 1 for secondary rays.  Read from the
+                                  // kernarg segment by the table trace kernels only
 };
 // a work queue: PT_QUEUE_SHARDS counters and, behind them, the stop word of checkpointed launches (one bit per shard found empty), each on
 // a line of its own, PT_QUEUE_SHARD_WORDS apart (4 KiB + 128 B: whatever the address-to-channel map is, neighbours differ in both fields)
@@ -204,6 +207,9 @@ static inline size_t ptk_p1tab_floats(int ntri) { return (size_t)((ntri / 2 + 1)
 // fills p.pmask (when not null) for the image geometry and the camera of p from the prepared records p.tris: per pixel the triangles
 // whose whole exact test (:96-125) some primary ray of the pixel can pass
 hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s);
+// fills table (PT_SM_TABLE_BYTES(ntri) bytes, pt_secmask.h) from the prepared records: per cell of (origin triangle, tile of its plane,
+// direction cell) the triangles whose whole exact test some ray of the cell can pass.  ntri <= PT_SM_TRI_MAX
+hipError_t ptk_secondary_masks(const PtPrepTriangle* tris, int ntri, uint2* table, hipStream_t s);
 // which search a launch runs (pt_shim.hip: prepare_search decides it, once, for renders, queries and ambient occlusion alike)
 struct PtSearchMode {
     // traverse p.bvh instead of the brute-force two-pass search; then `quads` is about the table of the big triangles kept out

@@ -28,6 +28,7 @@
 #include "pt_kernels.h"
 
 #include "pt_device_math.h"
+#include "pt_secmask.h"
 
 #include <type_traits>
 
@@ -350,6 +351,20 @@ __global__ void pt_primary_mask_kernel(const PtMaskParams P)
         m[c] |= (keep ? 1u : 0u) << (nc - 1 - (j & 31));
     }
     P.out[lp] = make_uint2(m[0], m[1]);
+}
+
+// ------------------------------------------------------------------------------------------
+// secondary-ray candidate masks (quad scenes of up to 64 triangles): the table of pt_secmask.h, where the derivation stands
+// ------------------------------------------------------------------------------------------
+// Once per scene: the first ntri threads write the classification records of the table's head, then one thread per cell writes its
+// mask (pt_sm_entry, binary64: the very function the host test compiles).  Nothing of it depends on a camera or an image.
+__global__ void pt_secondary_mask_kernel(const PtPrepTriangle* tris, int ntri, uint2* table)
+{
+    const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < (unsigned)ntri) reinterpret_cast<PtSmTri*>(table)[e] = pt_sm_tri_record(tris[e].p1, tris[e].e1, tris[e].e2);
+    if (e >= (unsigned)ntri * PT_SM_TRI_ENTRIES) return;
+    const PtSmMask m = pt_sm_entry(reinterpret_cast<const float*>(tris), ntri, e);
+    table[PT_SM_HEAD_ENTRIES + e] = make_uint2(m.x, m.y);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -918,10 +933,11 @@ PTK_DEV unsigned pt_intersect_two_pass(pt_const_f32p T, const PtPrepTriangle* tr
     return steps;
 }
 
-// closest hit of a FRESH wave of primary rays whose pixels have candidate masks (pt_primary_mask_kernel):
+// closest hit of rays that bring their candidate masks along -- a FRESH wave of primary rays whose pixels have them
+// (pt_primary_mask_kernel), or secondary rays whose cells have them (pt_secondary_mask_kernel; an uncovered ray brings all ones):
 // pass 1 is skipped, pass 2 is the one of pt_intersect_two_pass.  ntri <= 64 (two chunks).
 template <bool DET_BOUNDED, int LDS_TABLE>
-PTK_DEV unsigned pt_intersect_primary(pt_const_f32p T, const PtPrepTriangle* tris, int ntri, const f3& o, const f3& d, bool alive,
+PTK_DEV unsigned pt_intersect_masked(pt_const_f32p T, const PtPrepTriangle* tris, int ntri, const f3& o, const f3& d, bool alive,
                                       float& tmax, float& hu, float& hv, int& hidx, uint2 pm, PtTail tl, unsigned lane,
                                       unsigned long long* vstat = nullptr)
 {
@@ -1660,6 +1676,9 @@ template <int LDS_TABLE, bool POOLS = true> __host__ __device__ __forceinline__ 
 #ifndef PT_TRACE_UNIT_DIR
 #define PT_TRACE_UNIT_DIR 1  // 0: the trace kernels' filter tests |d|^2 as every other kernel's does (A/B builds, tools/build_variant.sh)
 #endif
+#ifndef PT_TRACE_SECONDARY_MASKS
+#define PT_TRACE_SECONDARY_MASKS 1  // 0: the lookup of secondary rays' candidate masks is compiled out (A/B builds, tools/build_variant.sh)
+#endif
 template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
 PTK_DEV void pt_trace_body(const PtTraceParams& P)
 {
@@ -1750,11 +1769,66 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         int hidx = -1;
         unsigned p2steps = 0;
         n_rays += (unsigned)__popcll(alive);
+        // the rays' candidate masks, where a table has them (ONE site for the masked search: the primary rays' masks by pixel, a
+        // secondary ray's by the cell of (the triangle it leaves, its origin's tile, its direction): pt_secmask.h)
+        bool masked = false;
+        uint2 pm = make_uint2(0u, 0u);
+        if (QUADS == 3 && DET_BOUNDED && alive != 0ull) {
+            if (primary && P.pmask != nullptr) {
+                pm = P.pmask[pix0 + lane];
+                masked = true;
+            } else if (LDS_TABLE == 1 && PT_TRACE_SECONDARY_MASKS && !fresh) {
+                // (the table and the triangle count from the kernarg segment -- the compiler loads the count behind the null test, a second scalar
+                // load with its own wait: no SGPR is held for either through the loop, and the loop's own copy of ntri, which the register
+                // allocator keeps in a spill lane, is not touched)
+                const pt_kargs_p KS = pt_kargs();
+                const uint2* const sm = KS->smask;
+                const int nt = KS->ntri;
+                if (sm != nullptr) {
+#if PT_STAMPS
+                    unsigned long long ta = 0, tb = 0;
+                    PT_STAMP(ta);
+#endif
+                    const PtSmMask ones = pt_sm_all_ones(nt);   // (scalar)
+                    pm = make_uint2(ones.x, ones.y);
+                    if (PT_ON(alive)) {
+                        // the record of the triangle just shaded and the cell's mask: 32-bit offsets against the scalar base, as the
+                        // {n, id} gather; every alive lane shaded a hit, and the index is clamped into the table whatever it is
+                        const char* const base = reinterpret_cast<const char*>(sm);
+                        // (the table holds the cells of ntri triangles, 1 <= ntri <= PT_SM_TRI_MAX: pt_shim.hip, refresh_smask)
+                        const unsigned k = (unsigned)h.hidx < (unsigned)(nt - 1) ? (unsigned)h.hidx : (unsigned)(nt - 1);
+                        const float4 ra = *reinterpret_cast<const float4*>(base + (size_t)(k * 48u));
+                        const float4 rb = *reinterpret_cast<const float4*>(base + (size_t)(k * 48u + 16u));
+                        const float4 rn = *reinterpret_cast<const float4*>(base + (size_t)(k * 48u + 32u));
+                        const float A[4] = { ra.x, ra.y, ra.z, ra.w }, B[4] = { rb.x, rb.y, rb.z, rb.w }, N[4] = { rn.x, rn.y, rn.z, rn.w };
+                        unsigned entry;
+                        const bool covered = pt_sm_classify(A, B, N, s.o.x, s.o.y, s.o.z, s.d.x, s.d.y, s.d.z, k, &entry);
+                        const uint2 v = *reinterpret_cast<const uint2*>(base + (size_t)(entry * 8u + (unsigned)(PT_SM_HEAD_ENTRIES * 8)));
+                        if (covered) pm = v;
+#if PT_VALIDATE_FILTER
+                        // DIAGNOSTIC build: secondary rays that looked their mask up, and those of them the table does not cover (stats[10], [11])
+                        if (P.stats) {
+                            const pt_lanes unc = PT_LANES(!covered);
+                            if (lane == (unsigned)__builtin_ctzll(alive)) {
+                                atomicAdd(&P.stats[10], (unsigned long long)__popcll(alive));
+                                atomicAdd(&P.stats[11], (unsigned long long)__popcll(unc & alive));
+                            }
+                        }
+#endif
+                    }
+                    masked = true;
+#if PT_STAMPS
+                    PT_STAMP(tb);
+                    c_p1 += tb - ta;
+#endif
+                }
+            }
+        }
         if (alive == 0ull) {
             // (shading ended every path: nothing to search)
-        } else if (QUADS == 3 && DET_BOUNDED && primary && P.pmask != nullptr)
-            p2steps = pt_intersect_primary<DET_BOUNDED, LDS_TABLE>(T, P.tris, ntri, s.o, s.d, PT_ON(alive), tmax, hu, hv, hidx, P.pmask[pix0 + lane], tl, lane,
-                                                                   PT_VALIDATE_FILTER && P.stats ? P.stats + 2 : nullptr);
+        } else if (masked)
+            p2steps = pt_intersect_masked<DET_BOUNDED, LDS_TABLE>(T, P.tris, ntri, s.o, s.d, PT_ON(alive), tmax, hu, hv, hidx, pm, tl, lane,
+                                                                  PT_VALIDATE_FILTER && P.stats ? P.stats + 2 : nullptr);
         else
             p2steps = pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS, PT_TRACE_UNIT_DIR != 0>(T, P.tris, ntri, s.o, s.d, PT_ON(alive), tmax, hu, hv, hidx,
                                                                                           P.quad_delta1, P.ray_radius,
@@ -4815,6 +4889,14 @@ hipError_t ptk_primary_masks(const PtTraceParams& p, hipStream_t s)
     m.npix_local = p.npix_local;
     m.cam = p.cam;
     hipLaunchKernelGGL(pt_primary_mask_kernel, dim3((p.npix_local + 255u) / 256u), dim3(256), 0, s, m);
+    return hipGetLastError();
+}
+
+hipError_t ptk_secondary_masks(const PtPrepTriangle* tris, int ntri, uint2* table, hipStream_t s)
+{
+    if (!table || ntri <= 0 || ntri > PT_SM_TRI_MAX) return hipErrorInvalidValue;
+    const unsigned n = (unsigned)ntri * PT_SM_TRI_ENTRIES;
+    hipLaunchKernelGGL(pt_secondary_mask_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, tris, ntri, table);
     return hipGetLastError();
 }
 

@@ -1,0 +1,322 @@
+// pt_secmask.h -- candidate masks of SECONDARY rays: which triangles a ray that leaves triangle k can hit.
+// One implementation for the device (pt_secondary_mask_kernel, pt_trace_body: pt_kernels.hip) and for the host (g++ compiles this
+// header into the stand-alone program of tests/test_secondary_masks_cpu.py).  No contraction on either side (-ffp-contract=off).
+//
+// A path that continues after shading starts its next ray at o = p + 0.01 wi (:257), p the hit point on triangle k: the origin
+// lies within about 0.01 of k's plane, over k or just beside it.  What such a ray can hit depends on the scene alone -- not on the
+// camera, the image or the frame -- so the answer is tabulated once per scene: one uint2 (pass 1's bit order, the format of
+// pt_primary_mask_kernel) per CELL = (origin triangle k, tile (iu, iv) of k's plane, direction cell (face, ia, ib) of a cube map).
+// The trace kernel classifies a ray from its own floats o, d and k (pt_sm_classify), loads the cell's mask and runs pass 2 on it;
+// pass 1 is not run.  Pass 2 applies the reference's whole test exactly, so the masks only have to be SUPERSETS:
+//
+//   CONTRACT.  Bit j of a cell is cleared only if the reference's test (GenerateColors.cl:96-125, against the initial tmax)
+//   accepts triangle j for NO ray that pt_sm_classify can map to the cell.
+//
+// ---- the classification (binary32, pt_sm_classify) and its real-number preimage ------------------------------------------------
+// Triangle k = {p1, e1, e2} (the floats of the prepared record, exact numbers here), n = e1 x e2, nh = n / |n|.  Every point is
+// o = p1 + uu e1 + vv e2 + hh nh for unique reals (uu, vv, hh).  With the dual vectors a* = (e2 x n) / |n|^2, b* = (n x e1) / |n|^2
+// (a* . e1 = 1, a* . e2 = 0, a* . nh = 0, likewise b*):  uu = a* . (o - p1), vv = b* . (o - p1), hh = nh . (o - p1).
+// The record PtSmTri holds three affine forms, made in binary64 and rounded to binary32:
+//     tu = A . o + A3 ~ (uu + G) / (1 + 2 G) * T       tv likewise       th = N . o + N3 ~ hh / H
+// G = PT_SM_GUARD is a guard band: the tiles cover uu, vv in [-G, 1 + G], so an origin pushed 0.01 past an edge of k still has a
+// tile.  A triangle gets a table only if the band holds that push whatever its direction: 0.0101 |a*| <= G and 0.0101 |b*| <= G (edges
+// and heights of about 0.65 and more).  A ray from a hit inside such a triangle is then covered but for rounding; a smaller triangle has
+// no table (pt_sm_geom: invalid), and the host declines the whole table for a scene that holds one (pt_shim.hip: refresh_smask), because a
+// lane with the all-ones mask makes its whole wave's pass 2 long: 20 % of the rays of a scene of such triangles were uncovered.  (They cover the whole parallelogram, not only the triangle: the origin over the other half of a quad is as common.)
+// H = 0.0101 + 32 u max_i(|p1_i| + |e1_i| + |e2_i|) is the plane distance the table is proved for: 0.01 |wi| of :257 (wi is unit to
+// rounding) and the rounding of the hit point.  Nothing is assumed about it: the device tests |th| <= 1 with its own floats.
+// A ray is COVERED when  0 <= tu < T,  0 <= tv < T,  |th| <= 1  and  0.999 <= fl(d . d) <= 1.001; its tile is (trunc tu, trunc tv).
+// Any NaN fails a comparison: uncovered.  An uncovered ray keeps every triangle (the caller gives it the all-ones mask).
+//   Rounding of a form.  The device evaluates fma(A2, oz, fma(A1, oy, fma(A0, ox, A3))): three roundings, each relative 2^-24 =: u
+//   of a partial sum bounded by Q = sum_i |A_i o_i| + |A3|, and the four constants are within u relative of their real values
+//   (binary64 work is 2^-29 times finer).  So |tu - tu_real| <= 4.02 u Q.  Q needs a bound on o.  Let m >= 1 be the least number with
+//   |uu|, |vv| <= m (1 + G) and |hh| <= m H; then |o_i - p1_i| <= m ((1 + G)(|e1_i| + |e2_i|) + H) and Q <= m E with
+//   E = sum_i |A_i| (|p1_i| + (1 + G)(|e1_i| + |e2_i|) + H) + |A3|.  A covered ray has its three floats in range, so each real
+//   form is in range up to its rounding: m <= 1 + 4.02 u m Emax, Emax the largest of E_u / T, E_v / T, E_h.  The builder REQUIRES
+//   8 u E_u <= 0.25, 8 u E_v <= 0.25 (a quarter of a tile) and 8 u E_h <= 0.25 (else triangle k has no table: its record is NaN,
+//   every ray from it is uncovered, its cells are all-ones); then 4.02 u Emax <= 0.126, m <= 1.15 and |tu - tu_real| <= 4.02 * 1.15
+//   u E < 8 u E =: du (tile units), dv likewise, |th - th_real| <= 8 u E_h =: dh.  (A triangle far from the origin of coordinates
+//   meets the limit through E_h: |p1| / H roundings of 2^-24.)
+//   Preimage of tile (iu, iv):  tu_real in [iu - du, iu + 1 + du], so uu = tu_real (1 + 2G) / T - G within ru = (0.5 + du)(1 + 2G) / T
+//   of its centre uc; vv likewise; |hh| <= Hr = H (1 + dh).  The origins of a cell are oc + Du e1 + Dv e2 + Dh nh with
+//   oc = p1 + uc e1 + vc e2, |Du| <= ru, |Dv| <= rv, |Dh| <= Hr: a boundary origin belongs to both neighbours' sets.
+// The direction.  m = the axis of the largest |d_i| (ties: the lower axis), a = (m + 1) % 3, b = (m + 2) % 3, face = 2 m + (d_m < 0),
+//     ca = fma(d_a * r, C / 2, C / 2), r ~ 1 / |d_m|,  ia = clamp(trunc ca, 0, C - 1),  ib likewise.
+// r is the quotient rounded (host) or v_rcp_f32 (device, 1 ulp): relative 2^-23 at the most; the product and the fma add 2^-24 each of
+// values below 1 and C: |ca - ca_real| <= (2.5 * 2^-23) C / 2 + 2^-24 C < 3.4e-6 for C <= 16.  The builder takes dc = 1e-4 cell units.
+// |d_a| <= |d_m| holds for the floats, so the real ratio qa = d_a / |d_m| is in [-1, 1] and in [(ia - dc) 2 / C - 1, (ia + 1 + dc) 2 / C - 1].
+// With L = |d|_2: fl(d . d) in [0.999, 1.001] gives L in [0.9994, 1.0006] (three roundings of u).  d = L g (s, qa, qb) in the axes
+// (m, a, b), g = (1 + qa^2 + qb^2)^(-1/2), which is largest where |qa|, |qb| are smallest in the cell and smallest where they are
+// largest.  So |d_m| in [0.9994 gmin, 1.0006 gmax] =: [l0, l1] and d_a in the interval product of [qa0, qa1] and [l0, l1]; d_b
+// likewise: a BOX dc +- rd for the direction.  (The trace kernels' directions are unit to 1 +- 4e-7, the UNIT_DIR comment of
+// pt_kernels.hip; nothing here relies on it -- the classification tests the length itself.)
+//
+// ---- the bounds (binary64, pt_sm_entry) -------------------------------------------------------------------------------------------
+// Target triangle j = {q1, f1, f2}, tvec = o - q1 = tc + D, tc = oc - q1, D = Du e1 + Dv e2 + Dh nh, d = dc + e, |e_i| <= rd_i.  The
+// reference's four numerators, as real forms:
+//     det = d . (f2 x f1)                   linear in d
+//     un  = d . (f2 x tvec)                 bilinear
+//     vn  = d . (tvec x f1)                 bilinear
+//     tn  = tvec . (f1 x f2)                linear in o
+// For a vector X:  radd(X) = sum_i rd_i |X_i|  bounds |e . X|;  rado(X) = ru |e1 . X| + rv |e2 . X| + Hr |nh . X|  bounds |D . X|.
+//     det: centre dc . Kd, Kd = f2 x f1;              radius radd(Kd)
+//     un:  centre dc . (f2 x tc);                     radius radd(f2 x tc) + rado(dc x f2) + X(f2)       [dc . (f2 x D) = D . (dc x f2)]
+//     vn:  centre dc . (tc x f1);                     radius radd(tc x f1) + rado(f1 x dc) + X(f1)       [dc . (D x f1) = D . (f1 x dc)]
+//     tn:  centre tc . G, G = f1 x f2;                radius rado(G)
+// X(f) = sum_i rd_i (ru |(f x e1)_i| + rv |(f x e2)_i| + Hr |(f x nh)_i|) bounds the second-order term |e . (f x D)|.
+// The reference's own rounding: its floats un_ref .. differ from these real forms by at most (the accounting of the comment above
+// pt_primary_mask_kernel, 7 u S per form with S = |a|_1 |b|_1 for a . (d x b); here tvec = fl(o - q1) is not a constant but one more
+// rounding of u per component, and tn_ref = fl_dot(f2, fl_cross(tvec, f1)) errs by less than 6.3 u |tvec|_1 |f1|_1 |f2|_1)
+//     rho = 32 u S,   S_det = |f1|_1 |f2|_1,  S_u = tv1 |f2|_1,  S_v = tv1 |f1|_1,  S_t = tv1 |f1|_1 |f2|_1,
+//     tv1 = |tc|_1 + ru |e1|_1 + rv |e2|_1 + 3 Hr >= |tvec|_1 over the cell
+// (32 against the 9 needed).  Radius and rho are inflated by 0.1 % against the builder's own (binary64) rounding, plus an absolute
+// 2e-24 that covers the -1e-24 threshold of pt_tri_pass1 and every underflow.  With lo / hi = centre -+ that:
+//     the reference accepts only if  det_ref >= 1e-8,  un_ref >= -1e-24,  vn_ref >= -1e-24,  un_ref + vn_ref <= det_ref * 1.000001,  tn_ref > 0
+// (the thresholds derived above pt_primary_mask_kernel), so bit j is CLEARED only when, for the whole cell,
+//     det_hi < 0.999e-8   or   un_hi < 0   or   vn_hi < 0   or   un_lo + vn_lo > det_hi * 1.000002   or   tn_hi <= 0.
+// SUB-CELLS.  First-order bounds over a whole cell are loose (the Cornell box: 6.9 candidates per ray at T = C = 8 where pass 1 keeps
+// 3.3), so pt_sm_entry cuts the cell's ranges -- [iu - du, iu + 1 + du], the same for v, and the two ratio ranges -- into PT_SM_SO^2 x
+// PT_SM_SD^2 sub-cells, bounds each as above and keeps a triangle that ANY sub-cell keeps: the sub-cells' preimages cover the cell's.
+// Every comparison is written so that a NaN keeps the bit.  A degenerate origin triangle (n = 0, a non-finite or oversized
+// constant: pt_sm_geom) has all-ones cells.  Directions below the surface are bounded like any other.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define PT_SM_HD __host__ __device__ static inline
+#else
+#define PT_SM_HD static inline
+#endif
+
+// tiles per edge of a triangle's plane, direction cells per edge of a cube face (profiles/secondary_masks/steps.txt)
+#ifndef PT_SM_T
+#define PT_SM_T 12
+#endif
+#ifndef PT_SM_C
+#define PT_SM_C 8
+#endif
+// the builder cuts a cell into SO x SO origin sub-tiles and SD x SD direction sub-cells and bounds each (pt_sm_entry)
+#ifndef PT_SM_SO
+#define PT_SM_SO 2
+#endif
+#ifndef PT_SM_SD
+#define PT_SM_SD 4
+#endif
+#define PT_SM_GUARD (1.0 / 64.0)
+#define PT_SM_DIRS (6 * PT_SM_C * PT_SM_C)
+#define PT_SM_TRI_ENTRIES (PT_SM_T * PT_SM_T * PT_SM_DIRS)
+#define PT_SM_TRI_MAX 64
+// the table: PT_SM_TRI_MAX classification records, padded to PT_SM_HEAD_ENTRIES uint2, then ntri * PT_SM_TRI_ENTRIES masks
+struct PtSmTri { float A[4], B[4], N[4]; };   // tu = A . o + A[3], tv = B . o + B[3], th = N . o + N[3]
+#define PT_SM_HEAD_ENTRIES (PT_SM_TRI_MAX * sizeof(PtSmTri) / 8)
+#define PT_SM_TABLE_BYTES(ntri) ((PT_SM_HEAD_ENTRIES + (size_t)(ntri) * PT_SM_TRI_ENTRIES) * 8)
+
+struct PtSmMask { unsigned x, y; };   // uint2
+
+// ---- the classification ---------------------------------------------------------------------------------------------------------
+PT_SM_HD float pt_sm_form(const float* F, float ox, float oy, float oz)
+{
+    return __builtin_fmaf(F[2], oz, __builtin_fmaf(F[1], oy, __builtin_fmaf(F[0], ox, F[3])));
+}
+
+// the cell of the ray (o, d) leaving triangle k, as an index into the masks behind the table's head; false: uncovered
+PT_SM_HD bool pt_sm_classify(const float* A, const float* B, const float* N, float ox, float oy, float oz, float dx, float dy, float dz,
+                             unsigned k, unsigned* entry)
+{
+    const float tu = pt_sm_form(A, ox, oy, oz), tv = pt_sm_form(B, ox, oy, oz), th = pt_sm_form(N, ox, oy, oz);
+    const float dd = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+    const bool covered = (tu >= 0.0f) & (tu < (float)PT_SM_T) & (tv >= 0.0f) & (tv < (float)PT_SM_T) & (__builtin_fabsf(th) <= 1.0f) &
+                         (dd >= 0.999f) & (dd <= 1.001f);
+    const float ax = __builtin_fabsf(dx), ay = __builtin_fabsf(dy), az = __builtin_fabsf(dz);
+    const bool mx = (ax >= ay) & (ax >= az), my = ay >= az;
+    const unsigned m = mx ? 0u : my ? 1u : 2u;
+    const float dm = mx ? dx : my ? dy : dz;
+    const float da = mx ? dy : my ? dz : dx;
+    const float db = mx ? dz : my ? dx : dy;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float r = __builtin_amdgcn_rcpf(__builtin_fabsf(dm));
+#else
+    const float r = 1.0f / __builtin_fabsf(dm);
+#endif
+    // (an uncovered ray's numbers may be anything: they are replaced before the conversions, whose result is never used then)
+    const float ca = covered ? __builtin_fmaf(da * r, 0.5f * PT_SM_C, 0.5f * PT_SM_C) : 0.0f;
+    const float cb = covered ? __builtin_fmaf(db * r, 0.5f * PT_SM_C, 0.5f * PT_SM_C) : 0.0f;
+    const float ca_c = __builtin_fminf(__builtin_fmaxf(ca, 0.0f), (float)(PT_SM_C - 1));
+    const float cb_c = __builtin_fminf(__builtin_fmaxf(cb, 0.0f), (float)(PT_SM_C - 1));
+    const unsigned ia = (unsigned)(int)ca_c, ib = (unsigned)(int)cb_c;
+    const unsigned iu = (unsigned)(int)(covered ? tu : 0.0f), iv = (unsigned)(int)(covered ? tv : 0.0f);
+    const unsigned face = 2u * m + (dm < 0.0f ? 1u : 0u);
+    *entry = ((k * PT_SM_T + iu) * PT_SM_T + iv) * PT_SM_DIRS + (face * PT_SM_C + ia) * PT_SM_C + ib;
+    return covered;
+}
+
+// ---- the builder ------------------------------------------------------------------------------------------------------------------
+struct PtSmV3 { double x, y, z; };
+PT_SM_HD PtSmV3 pt_sm_v(double x, double y, double z) { PtSmV3 r = { x, y, z }; return r; }
+PT_SM_HD PtSmV3 pt_sm_vf(const float* p) { return pt_sm_v((double)p[0], (double)p[1], (double)p[2]); }
+PT_SM_HD PtSmV3 pt_sm_cross(PtSmV3 a, PtSmV3 b) { return pt_sm_v(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+PT_SM_HD double pt_sm_dot(PtSmV3 a, PtSmV3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+PT_SM_HD PtSmV3 pt_sm_sub(PtSmV3 a, PtSmV3 b) { return pt_sm_v(a.x - b.x, a.y - b.y, a.z - b.z); }
+PT_SM_HD PtSmV3 pt_sm_axpy(double s, PtSmV3 a, PtSmV3 b) { return pt_sm_v(s * a.x + b.x, s * a.y + b.y, s * a.z + b.z); }
+PT_SM_HD double pt_sm_n1(PtSmV3 a) { return fabs(a.x) + fabs(a.y) + fabs(a.z); }
+PT_SM_HD double pt_sm_absdot(PtSmV3 r, PtSmV3 a) { return r.x * fabs(a.x) + r.y * fabs(a.y) + r.z * fabs(a.z); }
+
+#define PT_SM_U 5.9604644775390625e-8   // 2^-24
+
+// an origin triangle's frame: what the classification record is made from and what the bounds need of it
+struct PtSmGeom {
+    PtSmV3 p1, e1, e2, nh;
+    double H, du, dv, dh;   // the plane distance; the forms' rounding in tile units (du, dv) and in units of H (dh)
+    PtSmTri rec;            // NaN when !valid
+    bool valid;
+};
+
+PT_SM_HD void pt_sm_form_make(PtSmV3 w, double c, double scale, PtSmV3 reach, PtSmV3 p1, float* F, double* E)
+{
+    // F . o + F[3] ~ (w . (o - p1) + c) * scale; E: the bound of sum |F_i o_i| + |F[3]| over the origins within `reach` of p1
+    F[0] = (float)(w.x * scale); F[1] = (float)(w.y * scale); F[2] = (float)(w.z * scale);
+    F[3] = (float)((c - pt_sm_dot(w, p1)) * scale);
+    *E = fabs((double)F[0]) * (fabs(p1.x) + reach.x) + fabs((double)F[1]) * (fabs(p1.y) + reach.y) + fabs((double)F[2]) * (fabs(p1.z) + reach.z) +
+         fabs((double)F[3]);
+}
+
+PT_SM_HD PtSmGeom pt_sm_geom(const float* p1, const float* e1, const float* e2)
+{
+    PtSmGeom g;
+    g.p1 = pt_sm_vf(p1); g.e1 = pt_sm_vf(e1); g.e2 = pt_sm_vf(e2);
+    const PtSmV3 n = pt_sm_cross(g.e1, g.e2);
+    const double nn = pt_sm_dot(n, n), ln = sqrt(nn);
+    g.nh = pt_sm_v(n.x / ln, n.y / ln, n.z / ln);
+    const PtSmV3 as = pt_sm_cross(g.e2, n), bs = pt_sm_cross(n, g.e1);   // a* |n|^2, b* |n|^2
+    const double ext = fmax(fabs(g.p1.x) + fabs(g.e1.x) + fabs(g.e2.x), fmax(fabs(g.p1.y) + fabs(g.e1.y) + fabs(g.e2.y), fabs(g.p1.z) + fabs(g.e1.z) + fabs(g.e2.z)));
+    g.H = 0.0101 + 32.0 * PT_SM_U * ext;
+    const double G = PT_SM_GUARD, st = (double)PT_SM_T / (1.0 + 2.0 * G);
+    const PtSmV3 reach = pt_sm_v((1.0 + G) * (fabs(g.e1.x) + fabs(g.e2.x)) + g.H, (1.0 + G) * (fabs(g.e1.y) + fabs(g.e2.y)) + g.H,
+                                 (1.0 + G) * (fabs(g.e1.z) + fabs(g.e2.z)) + g.H);
+    double Eu, Ev, Eh;
+    pt_sm_form_make(pt_sm_v(as.x / nn, as.y / nn, as.z / nn), G, st, reach, g.p1, g.rec.A, &Eu);
+    pt_sm_form_make(pt_sm_v(bs.x / nn, bs.y / nn, bs.z / nn), G, st, reach, g.p1, g.rec.B, &Ev);
+    pt_sm_form_make(g.nh, 0.0, 1.0 / g.H, reach, g.p1, g.rec.N, &Eh);
+    g.du = 8.0 * PT_SM_U * Eu; g.dv = 8.0 * PT_SM_U * Ev; g.dh = 8.0 * PT_SM_U * Eh;
+    bool ok = nn > 0.0 && g.du <= 0.25 && g.dv <= 0.25 && g.dh <= 0.25;   // (a NaN fails)
+    // the guard band must hold the ray's offset: 0.0101 along any direction of the plane moves uu by at most 0.0101 |a*|, vv by 0.0101 |b*|
+    ok = ok && 0.0101 * sqrt(pt_sm_dot(as, as)) / nn <= G && 0.0101 * sqrt(pt_sm_dot(bs, bs)) / nn <= G;
+    for (int i = 0; i < 4; ++i)
+        ok = ok && fabs((double)g.rec.A[i]) < 1e30 && fabs((double)g.rec.B[i]) < 1e30 && fabs((double)g.rec.N[i]) < 1e30;
+    g.valid = ok;
+    if (!ok)
+        for (int i = 0; i < 4; ++i) g.rec.A[i] = g.rec.B[i] = g.rec.N[i] = __builtin_nanf("");
+    return g;
+}
+
+// the record alone (the trace kernel's gather)
+PT_SM_HD PtSmTri pt_sm_tri_record(const float* p1, const float* e1, const float* e2) { return pt_sm_geom(p1, e1, e2).rec; }
+
+PT_SM_HD PtSmMask pt_sm_all_ones(int ntri)
+{
+    PtSmMask m;
+    const int n0 = ntri < 32 ? ntri : 32, n1 = ntri - 32 < 0 ? 0 : ntri - 32 > 32 ? 32 : ntri - 32;
+    m.x = n0 == 32 ? ~0u : (1u << n0) - 1u;
+    m.y = n1 == 32 ? ~0u : (1u << n1) - 1u;
+    return m;
+}
+
+// [lo, hi] of q / |d_m| for direction cell index i, clipped to [-1, 1]
+PT_SM_HD void pt_sm_ratio_range(int i, double* lo, double* hi)
+{
+    const double dc = 1e-4;
+    *lo = fmax(-1.0, ((double)i - dc) * (2.0 / PT_SM_C) - 1.0);
+    *hi = fmin(1.0, ((double)i + 1.0 + dc) * (2.0 / PT_SM_C) - 1.0);
+}
+PT_SM_HD double pt_sm_absmin(double lo, double hi) { return lo > 0.0 ? lo : hi < 0.0 ? -hi : 0.0; }
+PT_SM_HD double pt_sm_absmax(double lo, double hi) { return fmax(fabs(lo), fabs(hi)); }
+PT_SM_HD void pt_sm_set(PtSmV3* v, unsigned axis, double x) { if (axis == 0u) v->x = x; else if (axis == 1u) v->y = x; else v->z = x; }
+
+// bit j of the cell's mask over ONE sub-cell: origins oc + Du e1 + Dv e2 + Dh nh (|Du| <= ru, |Dv| <= rv, |Dh| <= Hr), directions dc +- rd
+PT_SM_HD bool pt_sm_keep(const PtSmGeom& g, PtSmV3 oc, double ru, double rv, double Hr, PtSmV3 dc, PtSmV3 rd, const float* tj)
+{
+    const double INF = 1.001, ABS = 2e-24, RHO = 32.0 * PT_SM_U;
+    const PtSmV3 q1 = pt_sm_vf(tj), f1 = pt_sm_vf(tj + 3), f2 = pt_sm_vf(tj + 6);
+    const PtSmV3 tc = pt_sm_sub(oc, q1);
+    const double f1n = pt_sm_n1(f1), f2n = pt_sm_n1(f2);
+    const double tv1 = pt_sm_n1(tc) + ru * pt_sm_n1(g.e1) + rv * pt_sm_n1(g.e2) + 3.0 * Hr;
+    // det
+    const PtSmV3 Kd = pt_sm_cross(f2, f1);
+    const double det_hi = pt_sm_dot(dc, Kd) + ((pt_sm_absdot(rd, Kd) + RHO * f1n * f2n) * INF + ABS);
+    if (det_hi < 0.999e-8) return false;                                                // :100 (a NaN fails the comparison and goes on)
+    // tn = tvec . (f1 x f2)
+    const PtSmV3 Gt = pt_sm_cross(f1, f2);
+    const double tn_c = pt_sm_dot(tc, Gt);
+    const double tn_r = (ru * fabs(pt_sm_dot(g.e1, Gt)) + rv * fabs(pt_sm_dot(g.e2, Gt)) + Hr * fabs(pt_sm_dot(g.nh, Gt)) + RHO * tv1 * f1n * f2n) * INF + ABS;
+    if (tn_c + tn_r <= 0.0) return false;                                               // :125, t > 0
+    // un = d . (f2 x tvec)
+    const PtSmV3 Ku = pt_sm_cross(f2, tc), Du = pt_sm_cross(dc, f2);
+    const PtSmV3 x1 = pt_sm_cross(f2, g.e1), x2 = pt_sm_cross(f2, g.e2), x3 = pt_sm_cross(f2, g.nh);
+    const double un_c = pt_sm_dot(dc, Ku);
+    const double un_r = (pt_sm_absdot(rd, Ku) + ru * fabs(pt_sm_dot(g.e1, Du)) + rv * fabs(pt_sm_dot(g.e2, Du)) + Hr * fabs(pt_sm_dot(g.nh, Du)) +
+                         ru * pt_sm_absdot(rd, x1) + rv * pt_sm_absdot(rd, x2) + Hr * pt_sm_absdot(rd, x3) + RHO * tv1 * f2n) * INF + ABS;
+    if (un_c + un_r < 0.0) return false;                                                // :109, u >= 0
+    // vn = d . (tvec x f1)
+    const PtSmV3 Kv = pt_sm_cross(tc, f1), Dv = pt_sm_cross(f1, dc);
+    const PtSmV3 y1 = pt_sm_cross(f1, g.e1), y2 = pt_sm_cross(f1, g.e2), y3 = pt_sm_cross(f1, g.nh);
+    const double vn_c = pt_sm_dot(dc, Kv);
+    const double vn_r = (pt_sm_absdot(rd, Kv) + ru * fabs(pt_sm_dot(g.e1, Dv)) + rv * fabs(pt_sm_dot(g.e2, Dv)) + Hr * fabs(pt_sm_dot(g.nh, Dv)) +
+                         ru * pt_sm_absdot(rd, y1) + rv * pt_sm_absdot(rd, y2) + Hr * pt_sm_absdot(rd, y3) + RHO * tv1 * f1n) * INF + ABS;
+    if (vn_c + vn_r < 0.0) return false;                                                // :117, v >= 0
+    if ((un_c - un_r) + (vn_c - vn_r) > det_hi * 1.000002) return false;                // :117, u + v <= 1
+    return true;
+}
+
+// the mask of one cell.  tris: ntri records of 16 floats {p1, e1, e2, ...} (PtPrepTriangle); entry: the cell's index as
+// pt_sm_classify forms it (k = entry / PT_SM_TRI_ENTRIES < ntri).  The cell is cut into PT_SM_SO x PT_SM_SO origin sub-tiles and
+// PT_SM_SD x PT_SM_SD direction sub-cells, whose preimages cover the cell's; a triangle is kept when ANY sub-cell keeps it.
+PT_SM_HD PtSmMask pt_sm_entry(const float* tris, int ntri, unsigned entry)
+{
+    const unsigned k = entry / PT_SM_TRI_ENTRIES, within = entry - k * PT_SM_TRI_ENTRIES;
+    const unsigned tile = within / PT_SM_DIRS, cell = within - tile * PT_SM_DIRS;
+    const unsigned iu = tile / PT_SM_T, iv = tile - iu * PT_SM_T;
+    const unsigned face = cell / (PT_SM_C * PT_SM_C), ia = (cell / PT_SM_C) % PT_SM_C, ib = cell % PT_SM_C;
+    const float* tk = tris + 16 * k;
+    const PtSmGeom g = pt_sm_geom(tk, tk + 3, tk + 6);
+    const PtSmMask ones = pt_sm_all_ones(ntri);
+    if (!g.valid) return ones;
+    const double G = PT_SM_GUARD, su = (1.0 + 2.0 * G) / PT_SM_T, Hr = g.H * (1.0 + g.dh);
+    const unsigned m = face >> 1, a = (m + 1u) % 3u, b = (m + 2u) % 3u;
+    const double s = (face & 1u) ? -1.0 : 1.0;
+    double qa0, qa1, qb0, qb1;
+    pt_sm_ratio_range((int)ia, &qa0, &qa1);
+    pt_sm_ratio_range((int)ib, &qb0, &qb1);
+    // tu_real in [iu - du, iu + 1 + du], tv_real likewise
+    const double tu0 = (double)iu - g.du, tuw = (1.0 + 2.0 * g.du) / PT_SM_SO, tv0 = (double)iv - g.dv, tvw = (1.0 + 2.0 * g.dv) / PT_SM_SO;
+    const double qaw = (qa1 - qa0) / PT_SM_SD, qbw = (qb1 - qb0) / PT_SM_SD;
+    PtSmMask out = { 0u, 0u };
+    for (int sd = 0; sd < PT_SM_SD * PT_SM_SD; ++sd) {
+        // ---- the directions of the sub-cell: a box
+        const double a0 = qa0 + qaw * (sd / PT_SM_SD), a1 = a0 + qaw, b0 = qb0 + qbw * (sd % PT_SM_SD), b1 = b0 + qbw;
+        const double amin = pt_sm_absmin(a0, a1), amax = pt_sm_absmax(a0, a1), bmin = pt_sm_absmin(b0, b1), bmax = pt_sm_absmax(b0, b1);
+        const double l0 = 0.9994 / sqrt(1.0 + amax * amax + bmax * bmax), l1 = 1.0006 / sqrt(1.0 + amin * amin + bmin * bmin);
+        const double a_lo = fmin(a0 * l0, a0 * l1), a_hi = fmax(a1 * l0, a1 * l1);
+        const double b_lo = fmin(b0 * l0, b0 * l1), b_hi = fmax(b1 * l0, b1 * l1);
+        PtSmV3 dc = pt_sm_v(0, 0, 0), rd = pt_sm_v(0, 0, 0);
+        pt_sm_set(&dc, m, s * 0.5 * (l0 + l1)); pt_sm_set(&rd, m, 0.5 * (l1 - l0));
+        pt_sm_set(&dc, a, 0.5 * (a_lo + a_hi)); pt_sm_set(&rd, a, 0.5 * (a_hi - a_lo));
+        pt_sm_set(&dc, b, 0.5 * (b_lo + b_hi)); pt_sm_set(&rd, b, 0.5 * (b_hi - b_lo));
+        for (int so = 0; so < PT_SM_SO * PT_SM_SO; ++so) {
+            // ---- the origins of the sub-tile (the halves of a width are inflated by 1e-9 of it: the cuts are formed in binary64)
+            const double uc = (tu0 + tuw * ((so / PT_SM_SO) + 0.5)) * su - G, vc = (tv0 + tvw * ((so % PT_SM_SO) + 0.5)) * su - G;
+            const double ru = 0.5 * tuw * su * (1.0 + 1e-9), rv = 0.5 * tvw * su * (1.0 + 1e-9);
+            const PtSmV3 oc = pt_sm_axpy(uc, g.e1, pt_sm_axpy(vc, g.e2, g.p1));
+            for (int j = 0; j < ntri; ++j) {
+                const int c = j >> 5;
+                const int nc = ntri - 32 * c < 32 ? ntri - 32 * c : 32;
+                const unsigned bit = 1u << (nc - 1 - (j & 31));
+                if ((c == 0 ? out.x : out.y) & bit) continue;   // kept already
+                if (pt_sm_keep(g, oc, ru, rv, Hr, dc, rd, tris + 16 * j)) { if (c == 0) out.x |= bit; else out.y |= bit; }
+            }
+        }
+        if (out.x == ones.x && out.y == ones.y) break;
+    }
+    return out;
+}

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "pt_kernels.h"
+#include "pt_secmask.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -107,7 +108,7 @@ struct pt_device_s {
     uint64_t used, peak;
     int live_buffers;
     uint64_t workspace;      // device bytes held by this handle for itself (every PtWs below)
-    int64_t opt_batch, opt_chunk, opt_profile, opt_quads, opt_accel, opt_tally, opt_pmask, opt_bvh_stack, opt_lanes, opt_carry;
+    int64_t opt_batch, opt_chunk, opt_profile, opt_quads, opt_accel, opt_tally, opt_pmask, opt_bvh_stack, opt_lanes, opt_carry, opt_smask;
     pt_kernel_s kernels[KERNEL_COUNT];
     PendingFrames pending;
     // ---- the prepared scene, its filter tables and its LBVH (ensure_prep, ensure_bvh, ensure_anchor, prepare_search)
@@ -168,6 +169,8 @@ struct pt_device_s {
     PtWs<uint32_t> carry[2]; // per lane: the checkpoint regions of its renders' trace launches (PT_CARRY_HIT_STRIDE_DW dwords per wave)
     PtWs<uint2> pmask;       // primary-ray candidate masks of the local pixels (pt_primary_mask_kernel), for as many pixels as it holds
     struct { uint64_t scene_gen; int32_t g[7]; PtCamera cam; bool valid; } pmask_key;  // what the masks in hand were made for
+    PtWs<uint2> smask;       // secondary-ray candidate masks of the prepared scene (pt_secmask.h: PT_SM_TABLE_BYTES of the largest scene so far)
+    struct { uint64_t scene_gen; int32_t ntri; bool valid, declined; } smask_key;  // the scene the table in hand was made for, as pmask_key; declined: that scene has a triangle without a table
     PtWs<unsigned int> counters;  // PT_QUEUE_COUNTERS work-queue counters, PT_QUEUE_STRIDE words apart: zero between launches
     bool counters_dirty;     // a failed call may have left one non-zero
     // ---- per-kernel timing (pt_profile_*)
@@ -206,6 +209,10 @@ static int prof_end(hipStream_t st, hipEvent_t stop)
 
 #ifndef PT_DEFAULT_PRIMARY_MASKS
 #define PT_DEFAULT_PRIMARY_MASKS 1  // PT_OPT_PRIMARY_MASKS of a new device handle (A/B builds set 0)
+#endif
+
+#ifndef PT_DEFAULT_SECONDARY_MASKS
+#define PT_DEFAULT_SECONDARY_MASKS 1  // PT_OPT_SECONDARY_MASKS of a new device handle (A/B builds set 0)
 #endif
 
 static int g_init_count = 0;
@@ -273,6 +280,7 @@ static void destroy_device_objects(pt_device_s* d)
     ws_free(d, d->bvh);
     ws_free(d, d->ring);
     ws_free(d, d->pmask);
+    ws_free(d, d->smask);
     ws_free(d, d->counters);
     ws_free(d, d->bigtab);
     ws_free(d, d->bigidx);
@@ -324,6 +332,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->stream = d->own_stream;
     d->opt_batch = 1;
     d->opt_pmask = PT_DEFAULT_PRIMARY_MASKS;
+    d->opt_smask = PT_DEFAULT_SECONDARY_MASKS;
     d->opt_bvh_stack = 64;
     d->opt_lanes = 2;
     d->opt_carry = 1;
@@ -590,6 +599,9 @@ extern "C" int pt_device_set_option(pt_device_t d, int option, int64_t value)
     case PT_OPT_PRIMARY_MASKS:
         d->opt_pmask = value ? 1 : 0;
         return PT_OK;
+    case PT_OPT_SECONDARY_MASKS:
+        d->opt_smask = value ? 1 : 0;
+        return PT_OK;
     case PT_OPT_BVH_STACK_LIMIT:
         if (value < 1 || value > 64) return fail(PT_ERR_INVALID, "the LBVH stack limit must be 1..64");
         d->opt_bvh_stack = value;
@@ -620,6 +632,7 @@ extern "C" int64_t pt_device_get_option(pt_device_t d, int option)
     case PT_OPT_ACCEL: return d->opt_accel;
     case PT_OPT_BVH_TALLY: return d->opt_tally;
     case PT_OPT_PRIMARY_MASKS: return d->opt_pmask;
+    case PT_OPT_SECONDARY_MASKS: return d->opt_smask;
     case PT_OPT_BVH_STACK_LIMIT: return d->opt_bvh_stack;
     case PT_OPT_RENDER_LANES: return d->opt_lanes;
     case PT_OPT_CHECKPOINT: return d->opt_carry;
@@ -1322,6 +1335,43 @@ static int refresh_pmask(pt_device_s* d, const pt_render_params& rp, const PtCam
     return PT_OK;
 }
 
+// secondary-ray candidate masks (PT_OPT_SECONDARY_MASKS, pt_secmask.h): a function of the prepared scene ALONE -- no camera, no image
+// geometry -- made once per scene, on the handle's stream, behind the lanes.  The table is sized by the scene (the Cornell box: 15.9 MB;
+// 64 triangles: 28.3 MB) and allocated where the scene's table is made; it grows for a scene of more triangles and is kept otherwise,
+// so a render of a scene whose table stands neither allocates nor builds.
+static int refresh_smask(pt_device_s* d, int ntri)
+{
+    int rc;
+    if ((d->smask_key.valid || d->smask_key.declined) && d->smask_key.scene_gen == d->scene_gen && d->smask_key.ntri == ntri) return PT_OK;
+    if ((rc = stream_enqueue(d))) return rc;   // (a render with the old table may still be running)
+    d->smask_key.valid = d->smask_key.declined = false;
+    // A triangle without a table (degenerate, too small or too far from the origin of coordinates for the classification's rounding:
+    // pt_sm_geom) sends all its rays to pass 2 with every triangle, which costs far more than pass 1 saves: such a scene declines the
+    // table.  The records are read back once per scene (4 KiB at the most; the upload has just waited for the device anyway).
+    {
+        PtPrepTriangle host[PT_SM_TRI_MAX];
+        HIP_TRY(hipMemcpyAsync(host, d->prep.p, (size_t)ntri * sizeof(PtPrepTriangle), hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        bool all = true;
+        for (int k = 0; k < ntri && all; ++k) all = pt_sm_geom(host[k].p1, host[k].e1, host[k].e2).valid;
+        d->smask_key.scene_gen = d->scene_gen;
+        d->smask_key.ntri = ntri;
+        d->smask_key.declined = !all;
+        if (!all) return PT_OK;
+    }
+    if (d->smask.bytes < PT_SM_TABLE_BYTES(ntri)) {
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        ws_free(d, d->smask);
+        hipError_t e = ws_malloc(d, d->smask, PT_SM_TABLE_BYTES(ntri));
+        if (e != hipSuccess) return fail(PT_ERR_OOM, "secondary-mask allocation (%zu bytes) failed: %s", (size_t)PT_SM_TABLE_BYTES(ntri), hipGetErrorString(e));
+    }
+    HIP_TRY(ptk_secondary_masks(d->prep, ntri, d->smask, d->stream));
+    d->smask_key.scene_gen = d->scene_gen;
+    d->smask_key.ntri = ntri;
+    d->smask_key.valid = true;
+    return PT_OK;
+}
+
 // The masks' footprint bound (the comment above pt_primary_mask_kernel) takes every ray of a pixel to lie within
 // eps = 1.01 h + 4e-6 of the centre ray, h = half a pixel's diagonal on the image plane: that needs the image-plane point the
 // kernels compute to be the real one to a small part of a pixel.  It is not on a very large image.  With u = 2^-24 and a pixel
@@ -1437,6 +1487,12 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
     if (want_pmask && !use_pmask) d->pmask_key.valid = false;   // declined: no table stands for this render (pt_primary_mask_snapshot)
     bool make_pmask = false;
     if (use_pmask && (rc = refresh_pmask(d, rp, cam, npix, make_pmask))) return rc;
+    // the secondary rays' table: the same scenes, whatever the camera and the image; a scene that does not qualify declines it and
+    // no table stands for it (pt_secondary_mask_snapshot) -- the allocation stays for the next one that does
+    const bool can_smask = search.mode.quads == 3 && !use_bvh && rp.num_triangles <= PT_SM_TRI_MAX && search.mode.det_bounded;
+    const bool use_smask = can_smask && d->opt_smask;
+    if (!can_smask) d->smask_key.valid = d->smask_key.declined = false;
+    if (use_smask && (rc = refresh_smask(d, rp.num_triangles))) return rc;
     if (d->counters_dirty) {   // an earlier call failed between a trace launch and the fold that resets its counter
         if ((rc = stream_enqueue(d))) return rc;
         HIP_TRY(hipMemsetAsync(d->counters, 0, WS_COUNTERS, d->stream));
@@ -1446,6 +1502,7 @@ static int render_part(pt_device_s* d, pt_buffer_s* tris, pt_buffer_s* mats, pt_
     int blocks;
     if ((rc = choose_batch(d, use_bvh, npix, chunk, batch, bpf, blocks))) return rc;
     PtTraceParams tp = trace_params(d, mats, stats, rp, cam, npix, search, use_pmask, chunk, batch, bpf);
+    tp.smask = use_smask && d->smask_key.valid ? d->smask.p : nullptr;
     if (make_pmask) {
         HIP_TRY(ptk_primary_masks(tp, d->stream));  // (once per scene, camera and image geometry: one thread per pixel)
         d->pmask_key.valid = true;
@@ -2470,6 +2527,24 @@ extern "C" int pt_primary_mask_snapshot(pt_device_t d, uint32_t* num_pixels, voi
     if (masks) {
         if (capacity < npix) return fail(PT_ERR_RANGE, "pt_primary_mask_snapshot: %zu pixels do not fit %zu", npix, capacity);
         if (npix) HIP_TRY(hipMemcpy(masks, d->pmask.p, npix * sizeof(uint2), hipMemcpyDeviceToHost));
+    }
+    return PT_OK;
+}
+
+// test hook (include/pt_shim.h): the secondary-ray candidate masks of the scene in hand, copied out
+extern "C" int pt_secondary_mask_snapshot(pt_device_t d, uint32_t info[4], void* masks, size_t capacity)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!info) return fail(PT_ERR_INVALID, "pt_secondary_mask_snapshot: info is null");
+    if ((rc = flush_pending(d)) || (rc = stream_wait(d))) return rc;   // (the table is made on the handle's stream, read by the lanes)
+    if (!d->smask_key.valid || d->smask_key.scene_gen != d->scene_gen || d->smask_key.ntri != d->prep_ntri || !d->smask.p)
+        return fail(PT_ERR_INVALID, "no secondary-ray masks stand for the prepared scene");
+    const size_t n = (size_t)d->smask_key.ntri * PT_SM_TRI_ENTRIES;
+    info[0] = (uint32_t)n; info[1] = (uint32_t)d->smask_key.ntri; info[2] = PT_SM_T; info[3] = PT_SM_C;
+    if (masks) {
+        if (capacity < n) return fail(PT_ERR_RANGE, "pt_secondary_mask_snapshot: %zu entries do not fit %zu", n, capacity);
+        HIP_TRY(hipMemcpy(masks, d->smask.p + PT_SM_HEAD_ENTRIES, n * sizeof(uint2), hipMemcpyDeviceToHost));
     }
     return PT_OK;
 }

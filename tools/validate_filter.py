@@ -58,6 +58,8 @@ samples, rays, pairs, ref_keep, flt_keep, viol = (int(x) for x in out[:6])
 print("%-8s qf=%d %dx%d x %d%s: %d rays, %.4g pairs examined; reference keeps %.3f%%, filter keeps %.3f%%; VIOLATIONS: %d"
       % (kind, quad_filter, W, H, spp, " camera=%s" % sys.argv[6] if camera else "", rays, pairs, 100.0 * ref_keep / max(pairs, 1),
          100.0 * flt_keep / max(pairs, 1), viol))
+if out[10]:  # secondary rays searched with a looked-up mask (PT_OPT_SECONDARY_MASKS), and those the table did not cover (all-ones mask)
+    print("         secondary masks: %d rays looked up, %d of them uncovered (%.5f%%)" % (int(out[10]), int(out[11]), 100.0 * int(out[11]) / int(out[10])))
 r.release(); adl.DeviceUtils.deallocate(dev)
 if out[6] or out[7]:  # shared-u filter active: headroom of its error bounds (must be <= 1)
     r1, r3 = (float(np.array([x], np.uint64).astype(np.uint32).view(np.float32)[0]) for x in out[6:8])
