@@ -358,11 +358,18 @@ __global__ void pt_primary_mask_kernel(const PtMaskParams P)
 // ------------------------------------------------------------------------------------------
 // Once per scene: the first ntri threads write the classification records of the table's head, then one thread per cell writes its
 // mask (pt_sm_entry, binary64: the very function the host test compiles).  Nothing of it depends on a camera or an image.
-__global__ void pt_secondary_mask_kernel(const PtPrepTriangle* tris, int ntri, uint2* table)
+// A cell's work is a walk through boxes whose length differs a hundredfold between cells, and a wave takes as long as its longest lane.
+// How long a cell takes follows its direction more than its tile (a direction below the surface is done after one box per triangle),
+// so the lanes of a wave take the SAME direction cell over consecutive tiles -- thread i of a triangle has the cell (tile i % T^2,
+// direction i / T^2) -- and no register may spill: 256 threads per block leave the walk its 188 VGPRs (profiles/tight_masks/pmc_summary.txt).
+__global__ __launch_bounds__(256) void pt_secondary_mask_kernel(const PtPrepTriangle* tris, int ntri, uint2* table)
 {
-    const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < (unsigned)ntri) reinterpret_cast<PtSmTri*>(table)[e] = pt_sm_tri_record(tris[e].p1, tris[e].e1, tris[e].e2);
-    if (e >= (unsigned)ntri * PT_SM_TRI_ENTRIES) return;
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (unsigned)ntri) reinterpret_cast<PtSmTri*>(table)[i] = pt_sm_tri_record(tris[i].p1, tris[i].e1, tris[i].e2);
+    if (i >= (unsigned)ntri * PT_SM_TRI_ENTRIES) return;
+    const unsigned k = i / PT_SM_TRI_ENTRIES, within = i - k * PT_SM_TRI_ENTRIES;
+    const unsigned dir = within / (PT_SM_T * PT_SM_T), tile = within - dir * (PT_SM_T * PT_SM_T);
+    const unsigned e = k * PT_SM_TRI_ENTRIES + tile * PT_SM_DIRS + dir;   // (a permutation of the triangle's cells: e < ntri * PT_SM_TRI_ENTRIES)
     const PtSmMask m = pt_sm_entry(reinterpret_cast<const float*>(tris), ntri, e);
     table[PT_SM_HEAD_ENTRIES + e] = make_uint2(m.x, m.y);
 }

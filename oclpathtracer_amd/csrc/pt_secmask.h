@@ -74,11 +74,39 @@
 //     the reference accepts only if  det_ref >= 1e-8,  un_ref >= -1e-24,  vn_ref >= -1e-24,  un_ref + vn_ref <= det_ref * 1.000001,  tn_ref > 0
 // (the thresholds derived above pt_primary_mask_kernel), so bit j is CLEARED only when, for the whole cell,
 //     det_hi < 0.999e-8   or   un_hi < 0   or   vn_hi < 0   or   un_lo + vn_lo > det_hi * 1.000002   or   tn_hi <= 0.
-// SUB-CELLS.  First-order bounds over a whole cell are loose (the Cornell box: 6.9 candidates per ray at T = C = 8 where pass 1 keeps
-// 3.3), so pt_sm_entry cuts the cell's ranges -- [iu - du, iu + 1 + du], the same for v, and the two ratio ranges -- into PT_SM_SO^2 x
-// PT_SM_SD^2 sub-cells, bounds each as above and keeps a triangle that ANY sub-cell keeps: the sub-cells' preimages cover the cell's.
+// REFINEMENT.  First-order bounds over a whole cell are loose (the Cornell box: 6.9 candidates per ray at T = C = 8 where pass 1 keeps
+// 3.3), so pt_sm_entry refines, per target triangle j: a BOX is a product of sub-ranges of the cell's four ranges -- [iu - du, iu + 1 + du],
+// the same for v, and the two ratio ranges -- and is bounded exactly as a cell above.  Starting at the whole cell a box is, in this order,
+//     CLEARED  when one of the five bounds above (pt_sm_keep) or the separating plane below (pt_sm_sep) shows that no ray of it is accepted;
+//     KEPT     when a witness ray of it is accepted: the box's centre origin at plane distance 0, +Hr or -Hr and its centre direction pass
+//              the real forms strictly (pt_sm_witness, binary64).  A witness only spares work: keeping a bit is always within the CONTRACT;
+//     KEPT     when it stands at depth PT_SM_DEPTH, or when PT_SM_BUDGET boxes of the pair (cell, j) have been bounded;
+//     otherwise all four ranges are halved, and j is kept when any of the 16 children keeps it.
+// The children's preimages cover the parent's (the halves of a width are inflated by 1e-9 of it: the cuts are formed in binary64), so a
+// bit is cleared only when boxes that cover the whole cell were each cleared.  The walk is depth first in a fixed order without recursion:
+// the box at depth L is named by L bits in each of four index words, whose lowest bits are the child counter of that depth (the stack).
 // Every comparison is written so that a NaN keeps the bit.  A degenerate origin triangle (n = 0, a non-finite or oversized
 // constant: pt_sm_geom) has all-ones cells.  Directions below the surface are bounded like any other.
+//
+// ---- the separating plane (binary64, pt_sm_sep) ---------------------------------------------------------------------------------
+// Each of the five bounds asks whether some ray of the box passes ONE condition; none asks whether one ray passes all of them.  The
+// plane does.  For a real ray with det != 0 Cramer's rule gives, exactly,  o + (tn / det) d = q1 + (un / det) f1 + (vn / det) f2.  Let
+// det_lo = centre - radius - rho_det > 0 bound det from below over the box (the quantities of pt_sm_keep).  By the acceptance
+// conditions above and |x_ref - x| <= rho_x, a ray the reference accepts has, with u = un / det, v = vn / det, t = tn / det,
+//     u >= -eu,  eu = (rho_u + 1e-24) / det_lo;      v >= -ev likewise;      t >= -et,  et = rho_t / det_lo;
+//     u + v <= 1 + es,  es = 2e-6 + (1.000001 rho_det + rho_u + rho_v) / det_lo        [un + vn <= 1.000001 (det + rho_det) + rho_u + rho_v]
+// so its point P = o + t d lies in the INFLATED triangle with the corners (u, v) = (-eu, -ev), (1 + es + ev, -ev), (-eu, 1 + es + eu).
+// Also t |d|_2 = |P - o|_2 <= |tvec|_1 + (|u| + |v|)-weighted edges <= tv1 + (1 + eu + ev + es)(|f1|_1 + |f2|_1), and |d|_2 >= 0.9994:
+// t <= R = 1.001 (tv1 + (1 + eu + ev + es)(|f1|_1 + |f2|_1)).  Now take ANY vector w.  Over the box  w . d <= mw = w . dc + radd(w)  and
+// |w . d| <= aw = |w . dc| + radd(w);  w . o <= w . oc + rado(w).  Hence for every accepted ray of the box, relative to q1,
+//     w . (P - q1)  <=  w . tc + rado(w) + et aw + R max(mw, 0)            [t w . d <= R mw for t >= 0, <= et aw for -et <= t < 0]
+// while w . (P - q1) >= the least of u (w . f1) + v (w . f2) over the three corners.  If the first is LESS than the second no ray of
+// the box is accepted: the bit is cleared.  The choice of w needs no proof, only the inequality does.  pt_sm_sep tries, for each
+// a of {e1, e2, nh, f1, f2, f2 - f1}, the plane through a and an extreme direction dk of the box: w = +-(a x dk), the sign towards
+// the triangle's centroid, dk the corner of the direction box that maximises w . d (found from w = +-(a x dc) in two rounds; then
+// mw is a rounding of 0).  The radii and the rho are inflated by 0.1 % and the absolute 2e-24 as above, and 1e-13 |w|_1 R is added
+// against the builder's own rounding of the two sides (a few 1e-16 of |w|_1 times lengths below R).  The test is used only where
+// det_lo > PT_SM_SEP_DET |f1|_1 |f2|_1 (the e are then at most 0.02 tv1 / |f|_1); elsewhere the box has the five bounds alone.
 #pragma once
 
 #include <math.h>
@@ -97,12 +125,16 @@
 #ifndef PT_SM_C
 #define PT_SM_C 8
 #endif
-// the builder cuts a cell into SO x SO origin sub-tiles and SD x SD direction sub-cells and bounds each (pt_sm_entry)
-#ifndef PT_SM_SO
-#define PT_SM_SO 2
+// the builder's refinement (pt_sm_entry): the depth at which a box is kept, the boxes bounded per pair (cell, target triangle) before
+// it is kept, and the least det_lo / (|f1|_1 |f2|_1) at which the separating plane is tried (profiles/tight_masks/steps.txt)
+#ifndef PT_SM_DEPTH
+#define PT_SM_DEPTH 3
 #endif
-#ifndef PT_SM_SD
-#define PT_SM_SD 4
+#ifndef PT_SM_BUDGET
+#define PT_SM_BUDGET 96
+#endif
+#ifndef PT_SM_SEP_DET
+#define PT_SM_SEP_DET 1e-4
 #endif
 #define PT_SM_GUARD (1.0 / 64.0)
 #define PT_SM_DIRS (6 * PT_SM_C * PT_SM_C)
@@ -234,7 +266,7 @@ PT_SM_HD double pt_sm_absmin(double lo, double hi) { return lo > 0.0 ? lo : hi <
 PT_SM_HD double pt_sm_absmax(double lo, double hi) { return fmax(fabs(lo), fabs(hi)); }
 PT_SM_HD void pt_sm_set(PtSmV3* v, unsigned axis, double x) { if (axis == 0u) v->x = x; else if (axis == 1u) v->y = x; else v->z = x; }
 
-// bit j of the cell's mask over ONE sub-cell: origins oc + Du e1 + Dv e2 + Dh nh (|Du| <= ru, |Dv| <= rv, |Dh| <= Hr), directions dc +- rd
+// bit j of the cell's mask over ONE box, by the five bounds: origins oc + Du e1 + Dv e2 + Dh nh (|Du| <= ru, |Dv| <= rv, |Dh| <= Hr), directions dc +- rd
 PT_SM_HD bool pt_sm_keep(const PtSmGeom& g, PtSmV3 oc, double ru, double rv, double Hr, PtSmV3 dc, PtSmV3 rd, const float* tj)
 {
     const double INF = 1.001, ABS = 2e-24, RHO = 32.0 * PT_SM_U;
@@ -269,9 +301,101 @@ PT_SM_HD bool pt_sm_keep(const PtSmGeom& g, PtSmV3 oc, double ru, double rv, dou
     return true;
 }
 
+// a host program may count the builder's work: PT_SM_TALLY(0) per box bounded, PT_SM_TALLY(1 + i) when the plane of the i-th a separates
+#ifndef PT_SM_TALLY
+#define PT_SM_TALLY(i)
+#endif
+
+// the corner of the direction box dc +- rd at which w . d is largest
+PT_SM_HD PtSmV3 pt_sm_corner(PtSmV3 dc, PtSmV3 rd, PtSmV3 w)
+{
+    return pt_sm_v(w.x < 0.0 ? dc.x - rd.x : dc.x + rd.x, w.y < 0.0 ? dc.y - rd.y : dc.y + rd.y, w.z < 0.0 ? dc.z - rd.z : dc.z + rd.z);
+}
+
+// true: a plane separates the rays of the box from the inflated triangle j (the derivation: "the separating plane" above)
+PT_SM_HD bool pt_sm_sep(const PtSmGeom& g, PtSmV3 oc, double ru, double rv, double Hr, PtSmV3 dc, PtSmV3 rd, const float* tj)
+{
+    const double INF = 1.001, ABS = 2e-24, RHO = 32.0 * PT_SM_U;
+    const PtSmV3 q1 = pt_sm_vf(tj), f1 = pt_sm_vf(tj + 3), f2 = pt_sm_vf(tj + 6);
+    const PtSmV3 tc = pt_sm_sub(oc, q1);
+    const double f1n = pt_sm_n1(f1), f2n = pt_sm_n1(f2);
+    const double tv1 = pt_sm_n1(tc) + ru * pt_sm_n1(g.e1) + rv * pt_sm_n1(g.e2) + 3.0 * Hr;
+    const PtSmV3 Kd = pt_sm_cross(f2, f1);
+    const double rho_d = RHO * f1n * f2n * INF + ABS, rho_u = RHO * tv1 * f2n * INF + ABS, rho_v = RHO * tv1 * f1n * INF + ABS;
+    const double det_lo = pt_sm_dot(dc, Kd) - (pt_sm_absdot(rd, Kd) * INF + rho_d);
+    if (!(det_lo > PT_SM_SEP_DET * f1n * f2n)) return false;   // (a NaN: no plane)
+    const double eu = rho_u / det_lo, ev = rho_v / det_lo, et = (RHO * tv1 * f1n * f2n * INF + ABS) / det_lo;
+    const double es = 2e-6 + (1.000001 * rho_d + rho_u + rho_v) / det_lo;
+    const double R = 1.001 * (tv1 + (1.0 + eu + ev + es) * (f1n + f2n));
+    // towards the triangle: its centroid from the box's centre, (f1 + f2) / 3 - tc
+    const PtSmV3 to = pt_sm_v((f1.x + f2.x) / 3.0 - tc.x, (f1.y + f2.y) / 3.0 - tc.y, (f1.z + f2.z) / 3.0 - tc.z);
+    for (int i = 0; i < 6; ++i) {
+        const PtSmV3 a = i == 0 ? g.e1 : i == 1 ? g.e2 : i == 2 ? g.nh : i == 3 ? f1 : i == 4 ? f2 : pt_sm_sub(f2, f1);
+        PtSmV3 w = pt_sm_cross(a, dc);
+        const double sg = pt_sm_dot(w, to) < 0.0 ? -1.0 : 1.0;
+        for (int round = 0; round < 3; ++round) {
+            w = pt_sm_v(sg * w.x, sg * w.y, sg * w.z);
+            if (round < 2) w = pt_sm_cross(a, pt_sm_corner(dc, rd, w));
+        }
+        const double wdc = pt_sm_dot(w, dc), rdw = pt_sm_absdot(rd, w), mw = wdc + rdw;
+        const double mpos = mw <= 0.0 ? 0.0 : mw;   // (a NaN stays one)
+        const double lhs = pt_sm_dot(w, tc) + ((ru * fabs(pt_sm_dot(g.e1, w)) + rv * fabs(pt_sm_dot(g.e2, w)) + Hr * fabs(pt_sm_dot(g.nh, w)) +
+                                                et * (fabs(wdc) + rdw) + R * mpos) * INF + 1e-13 * pt_sm_n1(w) * R);
+        const double w1 = pt_sm_dot(w, f1), w2 = pt_sm_dot(w, f2);
+        const double c0 = -eu * w1 - ev * w2, c1 = (1.0 + es + ev) * w1 - ev * w2, c2 = -eu * w1 + (1.0 + es + eu) * w2;
+        if (lhs < c0 && lhs < c1 && lhs < c2) { PT_SM_TALLY(1 + i); return true; }
+    }
+    return false;
+}
+
+// true: the ray (o, d) passes triangle j's real forms strictly (binary64; the test is invariant under the length of d)
+PT_SM_HD bool pt_sm_witness(PtSmV3 o, PtSmV3 d, const float* tj)
+{
+    const PtSmV3 q1 = pt_sm_vf(tj), f1 = pt_sm_vf(tj + 3), f2 = pt_sm_vf(tj + 6);
+    const PtSmV3 tv = pt_sm_sub(o, q1);
+    const double det = pt_sm_dot(d, pt_sm_cross(f2, f1)), un = pt_sm_dot(d, pt_sm_cross(f2, tv)), vn = pt_sm_dot(d, pt_sm_cross(tv, f1));
+    const double tn = pt_sm_dot(tv, pt_sm_cross(f1, f2));
+    const double m = 1e-6 * det;
+    return det > 1e-6 * pt_sm_n1(f1) * pt_sm_n1(f2) && un > m && vn > m && un + vn < det - m && tn > 0.0;
+}
+
+// the ranges of a cell in the builder's terms, and one box of them
+struct PtSmCell {
+    double tu0, tuw, tv0, tvw, qa0, qaw, qb0, qbw;   // the low end and the width of [iu - du, iu + 1 + du], of v's, of the two ratio ranges
+    double su, Hr, s;                                // tile units to uu; the plane distance; the sign of d_m
+    unsigned m, a, b;                                // the axes of the face
+};
+
+// the box at depth `lvl` with the indices (xu, xv, xa, xb), each below 2^lvl, against triangle j: 0 cleared, 1 kept, 2 undecided
+PT_SM_HD int pt_sm_box(const PtSmGeom& g, const PtSmCell& c, int lvl, unsigned xu, unsigned xv, unsigned xa, unsigned xb, const float* tj)
+{
+    const double G = PT_SM_GUARD, sc = 1.0 / (double)(1u << lvl);
+    PT_SM_TALLY(0);
+    // ---- the directions of the box (each end moved out by 1e-9 of the width: the cuts are formed in binary64)
+    const double qaw = c.qaw * sc, qbw = c.qbw * sc;
+    const double a0 = c.qa0 + qaw * ((double)xa - 1e-9), a1 = c.qa0 + qaw * ((double)xa + (1.0 + 1e-9));
+    const double b0 = c.qb0 + qbw * ((double)xb - 1e-9), b1 = c.qb0 + qbw * ((double)xb + (1.0 + 1e-9));
+    const double amin = pt_sm_absmin(a0, a1), amax = pt_sm_absmax(a0, a1), bmin = pt_sm_absmin(b0, b1), bmax = pt_sm_absmax(b0, b1);
+    const double l0 = 0.9994 / sqrt(1.0 + amax * amax + bmax * bmax), l1 = 1.0006 / sqrt(1.0 + amin * amin + bmin * bmin);
+    const double a_lo = fmin(a0 * l0, a0 * l1), a_hi = fmax(a1 * l0, a1 * l1);
+    const double b_lo = fmin(b0 * l0, b0 * l1), b_hi = fmax(b1 * l0, b1 * l1);
+    PtSmV3 dc = pt_sm_v(0, 0, 0), rd = pt_sm_v(0, 0, 0);
+    pt_sm_set(&dc, c.m, c.s * 0.5 * (l0 + l1)); pt_sm_set(&rd, c.m, 0.5 * (l1 - l0));
+    pt_sm_set(&dc, c.a, 0.5 * (a_lo + a_hi)); pt_sm_set(&rd, c.a, 0.5 * (a_hi - a_lo));
+    pt_sm_set(&dc, c.b, 0.5 * (b_lo + b_hi)); pt_sm_set(&rd, c.b, 0.5 * (b_hi - b_lo));
+    // ---- its origins (the halves of a width are inflated by 1e-9 of it: the cuts are formed in binary64)
+    const double tuw = c.tuw * sc, tvw = c.tvw * sc;
+    const double uc = (c.tu0 + tuw * ((double)xu + 0.5)) * c.su - G, vc = (c.tv0 + tvw * ((double)xv + 0.5)) * c.su - G;
+    const double ru = 0.5 * tuw * c.su * (1.0 + 1e-9), rv = 0.5 * tvw * c.su * (1.0 + 1e-9);
+    const PtSmV3 oc = pt_sm_axpy(uc, g.e1, pt_sm_axpy(vc, g.e2, g.p1));
+    if (!pt_sm_keep(g, oc, ru, rv, c.Hr, dc, rd, tj)) return 0;
+    if (pt_sm_sep(g, oc, ru, rv, c.Hr, dc, rd, tj)) return 0;
+    if (pt_sm_witness(oc, dc, tj) || pt_sm_witness(pt_sm_axpy(c.Hr, g.nh, oc), dc, tj) || pt_sm_witness(pt_sm_axpy(-c.Hr, g.nh, oc), dc, tj)) return 1;
+    return 2;
+}
+
 // the mask of one cell.  tris: ntri records of 16 floats {p1, e1, e2, ...} (PtPrepTriangle); entry: the cell's index as
-// pt_sm_classify forms it (k = entry / PT_SM_TRI_ENTRIES < ntri).  The cell is cut into PT_SM_SO x PT_SM_SO origin sub-tiles and
-// PT_SM_SD x PT_SM_SD direction sub-cells, whose preimages cover the cell's; a triangle is kept when ANY sub-cell keeps it.
+// pt_sm_classify forms it (k = entry / PT_SM_TRI_ENTRIES < ntri)
 PT_SM_HD PtSmMask pt_sm_entry(const float* tris, int ntri, unsigned entry)
 {
     const unsigned k = entry / PT_SM_TRI_ENTRIES, within = entry - k * PT_SM_TRI_ENTRIES;
@@ -280,43 +404,51 @@ PT_SM_HD PtSmMask pt_sm_entry(const float* tris, int ntri, unsigned entry)
     const unsigned face = cell / (PT_SM_C * PT_SM_C), ia = (cell / PT_SM_C) % PT_SM_C, ib = cell % PT_SM_C;
     const float* tk = tris + 16 * k;
     const PtSmGeom g = pt_sm_geom(tk, tk + 3, tk + 6);
-    const PtSmMask ones = pt_sm_all_ones(ntri);
-    if (!g.valid) return ones;
-    const double G = PT_SM_GUARD, su = (1.0 + 2.0 * G) / PT_SM_T, Hr = g.H * (1.0 + g.dh);
-    const unsigned m = face >> 1, a = (m + 1u) % 3u, b = (m + 2u) % 3u;
-    const double s = (face & 1u) ? -1.0 : 1.0;
-    double qa0, qa1, qb0, qb1;
-    pt_sm_ratio_range((int)ia, &qa0, &qa1);
-    pt_sm_ratio_range((int)ib, &qb0, &qb1);
+    if (!g.valid) return pt_sm_all_ones(ntri);
+    PtSmCell c;
+    c.su = (1.0 + 2.0 * PT_SM_GUARD) / PT_SM_T; c.Hr = g.H * (1.0 + g.dh);
+    c.m = face >> 1; c.a = (c.m + 1u) % 3u; c.b = (c.m + 2u) % 3u;
+    c.s = (face & 1u) ? -1.0 : 1.0;
+    double qa1, qb1;
+    pt_sm_ratio_range((int)ia, &c.qa0, &qa1);
+    pt_sm_ratio_range((int)ib, &c.qb0, &qb1);
+    c.qaw = qa1 - c.qa0; c.qbw = qb1 - c.qb0;
     // tu_real in [iu - du, iu + 1 + du], tv_real likewise
-    const double tu0 = (double)iu - g.du, tuw = (1.0 + 2.0 * g.du) / PT_SM_SO, tv0 = (double)iv - g.dv, tvw = (1.0 + 2.0 * g.dv) / PT_SM_SO;
-    const double qaw = (qa1 - qa0) / PT_SM_SD, qbw = (qb1 - qb0) / PT_SM_SD;
+    c.tu0 = (double)iu - g.du; c.tuw = 1.0 + 2.0 * g.du; c.tv0 = (double)iv - g.dv; c.tvw = 1.0 + 2.0 * g.dv;
+    // ONE loop over the boxes of all pairs (cell, j), a box per round: on the device a lane that is done with an easy triangle goes on to
+    // its next one while its neighbours still refine theirs.  Per j the walk is depth first ("REFINEMENT" above); the lowest bits of
+    // xu, xv, xa, xb are the child counter of the depth
     PtSmMask out = { 0u, 0u };
-    for (int sd = 0; sd < PT_SM_SD * PT_SM_SD; ++sd) {
-        // ---- the directions of the sub-cell: a box
-        const double a0 = qa0 + qaw * (sd / PT_SM_SD), a1 = a0 + qaw, b0 = qb0 + qbw * (sd % PT_SM_SD), b1 = b0 + qbw;
-        const double amin = pt_sm_absmin(a0, a1), amax = pt_sm_absmax(a0, a1), bmin = pt_sm_absmin(b0, b1), bmax = pt_sm_absmax(b0, b1);
-        const double l0 = 0.9994 / sqrt(1.0 + amax * amax + bmax * bmax), l1 = 1.0006 / sqrt(1.0 + amin * amin + bmin * bmin);
-        const double a_lo = fmin(a0 * l0, a0 * l1), a_hi = fmax(a1 * l0, a1 * l1);
-        const double b_lo = fmin(b0 * l0, b0 * l1), b_hi = fmax(b1 * l0, b1 * l1);
-        PtSmV3 dc = pt_sm_v(0, 0, 0), rd = pt_sm_v(0, 0, 0);
-        pt_sm_set(&dc, m, s * 0.5 * (l0 + l1)); pt_sm_set(&rd, m, 0.5 * (l1 - l0));
-        pt_sm_set(&dc, a, 0.5 * (a_lo + a_hi)); pt_sm_set(&rd, a, 0.5 * (a_hi - a_lo));
-        pt_sm_set(&dc, b, 0.5 * (b_lo + b_hi)); pt_sm_set(&rd, b, 0.5 * (b_hi - b_lo));
-        for (int so = 0; so < PT_SM_SO * PT_SM_SO; ++so) {
-            // ---- the origins of the sub-tile (the halves of a width are inflated by 1e-9 of it: the cuts are formed in binary64)
-            const double uc = (tu0 + tuw * ((so / PT_SM_SO) + 0.5)) * su - G, vc = (tv0 + tvw * ((so % PT_SM_SO) + 0.5)) * su - G;
-            const double ru = 0.5 * tuw * su * (1.0 + 1e-9), rv = 0.5 * tvw * su * (1.0 + 1e-9);
-            const PtSmV3 oc = pt_sm_axpy(uc, g.e1, pt_sm_axpy(vc, g.e2, g.p1));
-            for (int j = 0; j < ntri; ++j) {
-                const int c = j >> 5;
-                const int nc = ntri - 32 * c < 32 ? ntri - 32 * c : 32;
-                const unsigned bit = 1u << (nc - 1 - (j & 31));
-                if ((c == 0 ? out.x : out.y) & bit) continue;   // kept already
-                if (pt_sm_keep(g, oc, ru, rv, Hr, dc, rd, tris + 16 * j)) { if (c == 0) out.x |= bit; else out.y |= bit; }
+    unsigned xu = 0u, xv = 0u, xa = 0u, xb = 0u;
+    int j = 0, lvl = 0, boxes = 0;
+    while (j < ntri) {
+        const int r = pt_sm_box(g, c, lvl, xu, xv, xa, xb, tris + 16 * j);
+        ++boxes;
+        const bool keep = r == 1 || (r == 2 && (lvl >= PT_SM_DEPTH || boxes >= PT_SM_BUDGET));
+        bool done = keep;
+        if (!keep && r == 2) { ++lvl; xu <<= 1; xv <<= 1; xa <<= 1; xb <<= 1; }   // the first child
+        if (r == 0) {
+            // cleared: the next sibling, or the parent's when this was the last; the pair is done when the whole cell is cleared
+            for (;;) {
+                if (lvl == 0) { done = true; break; }
+                const unsigned child = (xu & 1u) | ((xv & 1u) << 1) | ((xa & 1u) << 2) | ((xb & 1u) << 3);
+                if (child < 15u) {
+                    const unsigned n = child + 1u;
+                    xu = (xu & ~1u) | (n & 1u); xv = (xv & ~1u) | ((n >> 1) & 1u); xa = (xa & ~1u) | ((n >> 2) & 1u); xb = (xb & ~1u) | ((n >> 3) & 1u);
+                    break;
+                }
+                --lvl; xu >>= 1; xv >>= 1; xa >>= 1; xb >>= 1;
             }
         }
-        if (out.x == ones.x && out.y == ones.y) break;
+        if (done) {
+            if (keep) {
+                const int ch = j >> 5;
+                const int nc = ntri - 32 * ch < 32 ? ntri - 32 * ch : 32;
+                const unsigned bit = 1u << (nc - 1 - (j & 31));
+                if (ch == 0) out.x |= bit; else out.y |= bit;
+            }
+            ++j; lvl = 0; boxes = 0; xu = xv = xa = xb = 0u;
+        }
     }
     return out;
 }
