@@ -348,17 +348,42 @@ typedef struct pt_camera {
     float center[3];     /* :266, the point looked at (eye + (0, 0, -1)) */
     float up[3];         /* :267 (0, 1, 0) */
     float fov_y_deg;     /* vertical field of view in degrees, (0, 180) (:263: 60) */
-    int32_t reserved[6]; /* must be 0 */
-} pt_camera;             /* 64 bytes */
+    float lens_radius;   /* R, world units: finite and >= 0; 0 (or -0) is the pinhole */
+    float focus_distance;/* F: 0 or finite and > 0; must be > 0 when lens_radius > 0 */
+    int32_t reserved[4]; /* must be 0 */
+} pt_camera;             /* 64 bytes; all six trailing words 0 is the camera without a lens (ABI version 2 as before) */
+/* THE THIN LENS.  The reference has half of one: generateRay forms pointAimed = eye + 4.0f * dir (:285) and shoots from the eye through
+ * it -- a focus distance of 4 and an aperture of zero.  With lens_radius == 0 a sample is exactly that: the literal 4.0f, no extra draw,
+ * the same bits, whatever focus_distance holds.  With R = lens_radius > 0 and F = focus_distance: the two jitter draws come first
+ * (:278-279), dir is formed as at :278-284, then two more uniforms are drawn, u1 then u2, before anything else touches the seed, and in
+ * binary32 under PTSPEC (no contraction, scale3 then add3, the contract's sqrt, its sin / cos on [0, 2 pi]: getRandomFloat may
+ * return 1.0, which stays inside that range)
+ *     r   = R * sqrt(u1)            phi = TWO_PI * u2
+ *     lx  = r * cos(phi)            ly  = r * sin(phi)
+ *     org = (eye + holDir * lx) + upDir * ly
+ *     pointAimed = eye + F * dir                       (:285 with its literal made a parameter)
+ *     ray = getRay(org, normalize(pointAimed - org))   (:287; getRay normalises once more)
+ * The focus surface is the SPHERE of radius F about the eye (the reference's own expression, not a plane); the lens is the disc of
+ * radius R in the plane of holDir and upDir, sampled uniformly in area.  No relation between R and F is required; a degenerate
+ * pointAimed == org makes a NaN ray, defined behaviour as every NaN path here is.  Everything after the primary ray -- the seed going
+ * on, the walk, the light samples, the store, the fold -- is untouched.
+ * WHO TAKES A LENS: every entry point that takes a pt_camera and starts its samples one by one -- pt_render_ao; pt_render_direct and
+ * its _power, _ris, _env forms; pt_render_indirect and its _mis, _power, _rr, _ris, _env, _pixels, _pixels_ris forms; pt_camera_rays,
+ * whose origins are then the lens points, so a query of those rays traces a lens render's first bounce bit for bit.
+ * WHO REFUSES: pt_render_frames_camera returns PT_ERR_INVALID for lens_radius > 0, before anything is enqueued -- its kernels' primary-ray
+ * masks and pass-1 tables are built on org == eye bit for bit.  pt_render_indirect with no lights renders that image bit for bit and
+ * takes the lens.  pt_render_frames and the Adl-shaped launches have no camera at all. */
 
 /* the reference's camera (:263-267) */
 void pt_camera_reference(pt_camera* out);
-/* Host only, no device: validate cam and return its derived values {eye xyz, viewDir xyz, holDir xyz, upDir xyz, angle, 0, 0, 0}.
- * PT_ERR_INVALID when an input is not finite, fov_y_deg is outside (0, 180), a reserved field is not 0, or a derived value is
- * not finite (center == eye, up parallel to the view direction) -- cases in which the reference makes NaN rays. */
+/* Host only, no device: validate cam and return its derived values {eye xyz, viewDir xyz, holDir xyz, upDir xyz, angle, lens_radius,
+ * focus_distance, 0}.  PT_ERR_INVALID when an input is not finite, fov_y_deg is outside (0, 180), a reserved field is not 0, lens_radius
+ * is negative or not finite, focus_distance is negative or not finite, lens_radius > 0 with focus_distance == 0, or a derived value is
+ * not finite (center == eye, up parallel to the view direction) -- cases in which the reference makes NaN rays.  Every entry point that
+ * takes a camera validates it so, before anything is enqueued. */
 int pt_camera_derive(const pt_camera* cam, float out[16]);
-/* pt_render_frames seen from cam (validated as pt_camera_derive does; an invalid camera renders nothing and returns
- * PT_ERR_INVALID).  cam == NULL is exactly pt_render_frames.  Rendering with another camera than the previous call rewrites
+/* pt_render_frames seen from cam (validated as pt_camera_derive does; an invalid camera, or one with lens_radius > 0, renders nothing
+ * and returns PT_ERR_INVALID).  cam == NULL is exactly pt_render_frames.  Rendering with another camera than the previous call rewrites
  * the pass-1 filter's tables on the device, behind the renders in flight; it neither waits for the device nor allocates.
  * (The Adl-shaped GenerateColors launches -- pt_launch_2d -- keep the reference's camera: its kernel signature has none.) */
 int pt_render_frames_camera(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t framebuffer,
@@ -392,7 +417,7 @@ int pt_intersect_rays(pt_device_t dev, pt_buffer_t triangles, int num_triangles,
                       pt_buffer_t out, size_t num_rays, int mode, pt_event_t ev);
 /* width x height rays into `rays`: ray gid = y * width + x is the primary ray the renderer traces for pixel gid in frame
  * `frame` (seed gid + hash(frame), :305-308; the camera's jitter and expression, :278-287) seen from cam (NULL = the
- * reference's; validated as by pt_render_frames_camera).  origin = the eye, tmax = 1e20, dir = the vector the reference passes
+ * reference's; validated as by pt_camera_derive).  origin = the eye -- with lens_radius > 0 the sample's lens point --, tmax = 1e20, dir = the vector the reference passes
  * to getRay at :287, normalised once: pt_intersect_rays normalises it again as getRay does, so a query of these rays traces the
  * renderer's primary rays bit for bit. */
 int pt_camera_rays(pt_device_t dev, const pt_camera* cam /* NULL = reference */, int width, int height,

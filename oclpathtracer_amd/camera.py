@@ -29,19 +29,27 @@ def _vec3(v, what: str) -> Vec3:
 @dataclass(frozen=True)
 class Camera:
     """``eye`` looks at ``center``; ``up`` fixes the roll; ``fov_y_deg`` is the vertical field of view in degrees, in (0, 180).
-    Invalid cameras (non-finite values, ``center == eye``, ``up`` parallel to the view direction) raise ``ValueError`` here,
-    before anything is enqueued."""
+    ``lens_radius`` > 0 (world units) makes it a thin lens focused on the sphere of radius ``focus_distance`` about the eye
+    (include/pt_shim.h: pt_camera); 0 is the pinhole.  The sample-by-sample renderers (``AORenderer``, ``DirectRenderer``,
+    ``IndirectRenderer``) and ``RayCaster.camera_rays`` take a lens; the fused ones (``Renderer``, ``ProgressiveRenderer``,
+    ``StripeImage``) refuse it.
+    Invalid cameras (non-finite values, ``center == eye``, ``up`` parallel to the view direction, a negative lens radius or focus
+    distance, a lens without a focus distance) raise ``ValueError`` here, before anything is enqueued."""
 
     eye: Vec3
     center: Vec3
     up: Vec3 = (0.0, 1.0, 0.0)
     fov_y_deg: float = 60.0
+    lens_radius: float = 0.0
+    focus_distance: float = 0.0
 
     def __post_init__(self):
         object.__setattr__(self, "eye", _vec3(self.eye, "eye"))
         object.__setattr__(self, "center", _vec3(self.center, "center"))
         object.__setattr__(self, "up", _vec3(self.up, "up"))
         object.__setattr__(self, "fov_y_deg", float(np.float32(self.fov_y_deg)))
+        object.__setattr__(self, "lens_radius", float(np.float32(self.lens_radius)))
+        object.__setattr__(self, "focus_distance", float(np.float32(self.focus_distance)))
         self.derive()   # validates
 
     @classmethod
@@ -73,6 +81,36 @@ class Camera:
         dist = margin * radius / math.sin(half)
         return cls(tuple(c - dist * v), tuple(c), tuple(up), fov_y_deg)
 
+    def with_lens(self, lens_radius: float, focus_distance: Optional[float] = None, focus_on: Optional[Sequence[float]] = None) -> "Camera":
+        """This camera with a thin lens of ``lens_radius``, focused at ``focus_distance`` or on the point ``focus_on`` (the distance is
+        |point - eye|): exactly one of the two, unless ``lens_radius`` is 0 (the pinhole, which needs neither)."""
+        if (focus_distance is None) == (focus_on is None) and not (focus_on is None and float(lens_radius) == 0.0):
+            raise ValueError("camera: give exactly one of focus_distance and focus_on")
+        if focus_on is not None:
+            p = np.asarray(_vec3(focus_on, "focus_on"), np.float64)
+            focus_distance = float(np.sqrt(((p - np.asarray(self.eye, np.float64)) ** 2).sum()))
+        return Camera(self.eye, self.center, self.up, self.fov_y_deg, lens_radius, 0.0 if focus_distance is None else focus_distance)
+
+    def pinhole_ray(self, u: float = 0.5, v: float = 0.5, aspect: float = 1.0) -> Tuple[np.ndarray, np.ndarray]:
+        """(origin, unit direction), float64, of the ray through image position (``u``, ``v``) in [0, 1]^2 -- (0, 0) the top left corner --
+        of an image of width / height ``aspect``, without jitter and without a lens."""
+        d = self.derive().astype(np.float64)
+        eye, view, hol, up, angle = d[0:3], d[3:6], d[6:9], d[9:12], d[12]
+        w = hol * ((2.0 * u - 1.0) * angle * aspect) + up * ((1.0 - 2.0 * v) * angle) + view
+        return eye, w / np.sqrt((w * w).sum())
+
+    def autofocus(self, caster, lens_radius: float, u: float = 0.5, v: float = 0.5, aspect: float = 1.0) -> "Camera":
+        """This camera with a thin lens of ``lens_radius`` focused on what the pinhole ray of image position (``u``, ``v``) hits: one
+        closest-hit query through ``caster`` (a ``RayCaster`` of the scene), the focus distance is the hit's ``t``.  Raises
+        ``ValueError`` when the ray leaves the scene."""
+        from .query import make_rays
+
+        o, w = self.pinhole_ray(u, v, aspect)
+        hit = caster.closest(make_rays(o[None, :], w[None, :]))[0]
+        if int(hit["tri"]) < 0 or not np.isfinite(hit["t"]):
+            raise ValueError("camera: nothing to focus on at image position (%g, %g)" % (u, v))
+        return self.with_lens(lens_radius, focus_distance=float(hit["t"]))
+
     @classmethod
     def struct_of(cls, camera: Optional["Camera"]) -> Optional[shim.Camera]:
         """What every entry point that takes a camera hands to the library: None (the reference's camera) for None, else the
@@ -91,11 +129,13 @@ class Camera:
         s.center[:] = self.center
         s.up[:] = self.up
         s.fov_y_deg = self.fov_y_deg
+        s.lens_radius = self.lens_radius
+        s.focus_distance = self.focus_distance
         return s
 
     def derive(self) -> np.ndarray:
         """The renderer's derived values (pt_camera_derive): float32[16] = eye xyz, viewDir xyz, holDir xyz, upDir xyz,
-        angle = tan(fov / 2), 0, 0, 0."""
+        angle = tan(fov / 2), lens_radius, focus_distance, 0."""
         out = np.zeros(16, np.float32)
         s = self.to_struct()
         rc = shim.load().pt_camera_derive(ctypes.byref(s), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))

@@ -246,6 +246,42 @@ PTK_DEV double pt_k64(double c)
 }
 
 // ---- sin/cos of phi >= 0: Cody-Waite by pi/2 in binary64, Taylor to r^15 / r^16, one rounding ----
+// A binary32 literal made in a VGPR at its point of use (pt_k64's counterpart).  A Horner chain's first fma takes two literals, one of
+// which has to sit in a VGPR; left alone, hipcc hoists that v_mov out of every enclosing loop, where it stays live for the kernel's lifetime
+PTK_DEV float pt_k32v(float c)
+{
+    asm volatile("" : "+v"(c));
+    return c;
+}
+
+// the binary32 form, for a phi KNOWN to lie in [0, PTK_F32_SINCOS_MAX] (pt_sincos's first branch, alone: a caller that forms
+// phi = 2 pi xi from a draw it has just made needs no binary64 branch -- and none of its register pairs).
+// PIN: the chains' leading coefficients are made where they are used (pt_k32v) -- for a caller inside a loop of a kernel that sits
+// exactly on a register step (the lens, pt_kernels.hip: pt_lens_aim); the value is the same
+template <bool PIN = false>
+PTK_DEV void pt_sincos_f32(float phi, float& s_out, float& c_out)
+{
+    const float kf = __builtin_rintf(phi * PTK_F32_TWO_OVER_PI);
+    float r = pt_fma(-kf, PTK_F32_PIO2_A, phi);
+    r = pt_fma(-kf, PTK_F32_PIO2_B, r);
+    r = pt_fma(-kf, PTK_F32_PIO2_C, r);
+    r = pt_fma(-kf, PTK_F32_PIO2_D, r);
+    const float r2 = r * r;
+    float ps = PIN ? pt_k32v(PTK_F32_SIN_S4) : PTK_F32_SIN_S4;
+    ps = pt_fma(ps, r2, PTK_F32_SIN_S3);
+    ps = pt_fma(ps, r2, PTK_F32_SIN_S2);
+    ps = pt_fma(ps, r2, PTK_F32_SIN_S1);
+    const float sn = pt_fma(r * r2, ps, r);
+    float pc = PIN ? pt_k32v(PTK_F32_COS_C4) : PTK_F32_COS_C4;
+    pc = pt_fma(pc, r2, PTK_F32_COS_C3);
+    pc = pt_fma(pc, r2, PTK_F32_COS_C2);
+    pc = pt_fma(pc, r2, PTK_F32_COS_C1);
+    const float cs = pt_fma(r2, pt_fma(r2, pc, -0.5f), 1.0f);
+    const int q = (int)kf & 3;
+    s_out = (q == 0) ? sn : (q == 1) ? cs : (q == 2) ? -sn : -cs;
+    c_out = (q == 0) ? cs : (q == 1) ? -sn : (q == 2) ? -cs : sn;
+}
+
 PTK_DEV void pt_sincos(float phi, float& s_out, float& c_out)
 {
     // PTSPEC: on [0, PTK_F32_SINCOS_MAX] -- every angle the path forms (phi = 2 pi xi) -- binary32
@@ -254,25 +290,7 @@ PTK_DEV void pt_sincos(float phi, float& s_out, float& c_out)
     // The binary64 evaluation below (the only one until this was measured at 5.6 % of the trace
     // kernel) remains for any other argument.
     if (__builtin_expect(phi >= 0.0f && phi <= PTK_F32_SINCOS_MAX, 1)) {
-        const float kf = __builtin_rintf(phi * PTK_F32_TWO_OVER_PI);
-        float r = pt_fma(-kf, PTK_F32_PIO2_A, phi);
-        r = pt_fma(-kf, PTK_F32_PIO2_B, r);
-        r = pt_fma(-kf, PTK_F32_PIO2_C, r);
-        r = pt_fma(-kf, PTK_F32_PIO2_D, r);
-        const float r2 = r * r;
-        float ps = PTK_F32_SIN_S4;
-        ps = pt_fma(ps, r2, PTK_F32_SIN_S3);
-        ps = pt_fma(ps, r2, PTK_F32_SIN_S2);
-        ps = pt_fma(ps, r2, PTK_F32_SIN_S1);
-        const float sn = pt_fma(r * r2, ps, r);
-        float pc = PTK_F32_COS_C4;
-        pc = pt_fma(pc, r2, PTK_F32_COS_C3);
-        pc = pt_fma(pc, r2, PTK_F32_COS_C2);
-        pc = pt_fma(pc, r2, PTK_F32_COS_C1);
-        const float cs = pt_fma(r2, pt_fma(r2, pc, -0.5f), 1.0f);
-        const int q = (int)kf & 3;
-        s_out = (q == 0) ? sn : (q == 1) ? cs : (q == 2) ? -sn : -cs;
-        c_out = (q == 0) ? cs : (q == 1) ? -sn : (q == 2) ? -cs : sn;
+        pt_sincos_f32(phi, s_out, c_out);
         return;
     }
     double x = (double)phi;

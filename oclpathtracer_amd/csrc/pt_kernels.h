@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 // The reference's packed 64-byte device records (GenerateColors.cl:12-28).
@@ -91,6 +92,13 @@ static_assert(sizeof(PtLeafTri) == 64, "leaf record layout");
 struct PtCamera {
     float eye[3], view[3], hol[3], up[3];
     float angle;
+};
+// ... and its thin lens (include/pt_shim.h: pt_camera), carried by the launches that start their samples through pt_item_begin,
+// pt_list_item_begin or pt_camera_rays_kernel -- ambient occlusion, the lit renders, the camera-ray query.  lens_radius = 0 is the
+// pinhole: the code of before, no extra draw.  The fused trace kernels have no lens: PtTraceParams keeps the plain PtCamera, so
+// their kernel arguments do not move (their masks and pass-1 tables are built on org == eye bit for bit)
+struct PtLensCamera : PtCamera {
+    float lens_radius, focus_distance;
 };
 
 struct PtTraceParams {
@@ -276,7 +284,7 @@ int ptk_query_bvh_blocks_per_cu(void);
 // geometry (width, inv_width, inv_height, aspect, stripe_rows, n_ranks, rank); cam is the camera
 struct PtAoParams {
     PtTraceParams t;
-    PtCamera cam;
+    PtLensCamera cam;
     unsigned long long* counts;   // [npix] open | hits << 32 (the {open, hits} uint32 pair), added to
     uint32_t npix;                // local pixels
     uint32_t nitems;              // samples of this launch, frame-major: item = f * npix + local pixel (< 2^31)
@@ -284,6 +292,11 @@ struct PtAoParams {
     int32_t K;                    // occlusion rays per hit
     float tlim;                   // min(radius, 1e20)
 };
+// (pt_kernels.hip reads the lens from the kernarg segment at this one place, whichever block the kernel takes: pt_lens_kargs)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"   // (PtLensCamera has a base: offsetof is conditionally supported, and clang supports it)
+static_assert(offsetof(PtAoParams, cam) == sizeof(PtTraceParams), "PtAoParams begins { t, cam }");
+#pragma clang diagnostic pop
 hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream_t s);
 // image[i] = float4(a, a, a, 1) of counts[i] = {open, hits}: a = open / (K hits), miss_value when hits = 0
 hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uint32_t K, float miss_value, hipStream_t s);
@@ -292,7 +305,7 @@ hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uin
 // which ptk_fold folds into the framebuffer (PtFoldParams::rad = samples, frame_begin = frame0)
 struct PtDirectParams {
     PtTraceParams t;
-    PtCamera cam;
+    PtLensCamera cam;
     const int32_t* lights;        // [nl] triangle indices, clamped into [0, ntri) where they are used; not read when nl = 0
     float* samples;               // [nitems][3] max(E + S / K, 0)
     uint32_t npix;                // local pixels
@@ -301,6 +314,10 @@ struct PtDirectParams {
     int32_t K;                    // light samples per hit
     int32_t nl;                   // lights in the list, 0 .. 2^24 - 1 ((float)nl is exact)
 };
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(offsetof(PtDirectParams, cam) == sizeof(PtTraceParams), "PtDirectParams begins { t, cam }");
+#pragma clang diagnostic pop
 // indirect illumination (pt_render_indirect): direct illumination's launch with the path's depth.  samples[item] = max(L, 0) of the
 // whole path; everything else is as PtDirectParams says (the helpers of both take its PtDirectParams)
 struct PtIndirectParams {
@@ -454,7 +471,7 @@ hipError_t ptk_sample_moments(const float* samples, PtPixelMoments* moments, uin
 // record 0.  One launch per level of 2048-element tiles
 hipError_t ptk_moments_resolve(const PtPixelMoments* moments, uint32_t npix, void* noise, PtNoiseSummary* summary, hipStream_t s);
 // rays[2 gid], rays[2 gid + 1] = the pt_ray of pixel gid, frame `frame` (the renderer's sample start) for the camera cam
-hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s);
+hipError_t ptk_camera_rays(const PtLensCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s);
 // dynamic LDS of a trace workgroup (pt_kernels.hip: pt_lds_total, pt_bvh_lds_total)
 size_t ptk_trace_lds_bytes(int ntri);
 int ptk_trace_blocks_per_cu(int ntri);

@@ -244,6 +244,66 @@ PTK_DEV void pt_generate_ray(int xc, int yc, float inv_w, float inv_h, float asp
     pt_camera_ray(x, y, inv_w, inv_h, aspect, c, org, dir_out);
 }
 
+// The thin lens (include/pt_shim.h: pt_camera), for lens_radius R > 0: after the jitter draws and `dir` of :278-284, two more draws,
+// u1 then u2; the origin is the point (r cos(phi), r sin(phi)), r = R sqrt(u1), phi = TWO_PI u2, of the disc in the plane of holDir and
+// upDir about the eye (uniform in area), and the ray goes from it through pointAimed = eye + F dir -- :285 with its literal 4.0f made
+// the focus distance F.  `aim` is what getRay receives at :287, normalised once, as pt_camera_aim's.  Its temporaries die here: what
+// leaves is an origin and a direction, as from the pinhole.
+PTK_DEV void pt_lens_aim(float x, float y, float inv_w, float inv_h, float aspect, const PtCam& c, float R, float F, uint32_t& seed, f3& org,
+                         f3& aim)
+{
+    // The two draws follow the jitter's in the seed's sequence; what is COMPUTED first is the lens point, while only x and y wait: at most
+    // five values of this function are live at a time (its callers sit inside refill loops with every register spoken for).
+    // phi = TWO_PI u2 <= RN(2 pi) < PTK_F32_SINCOS_MAX for u2 in [0, 1] (getRandomFloat may return 1.0): the binary32 form, no guard
+    const float u1 = pt_random_float(seed);
+    const float u2 = pt_random_float(seed);
+    const float r = R * pt_sqrt(u1);
+    const float phi = PTK_TWO_PI * u2;
+    float sp, cp;
+    pt_sincos_f32<true>(phi, sp, cp);
+    const float lx = r * cp, ly = r * sp;
+    org = add3(add3(c.eye, scale3(c.hol, lx)), scale3(c.up, ly));
+    x = (2.0f * ((x + 0.5f) * inv_w) - 1.0f) * c.angle * aspect;
+    y = -(1.0f - 2.0f * ((y + 0.5f) * inv_h)) * c.angle;
+    const float my = -1.0f * y;
+    const f3 dir = normalize3(add3(add3(scale3(c.hol, x), scale3(c.up, my)), c.view));
+    const f3 pointAimed = add3(c.eye, scale3(dir, F));
+    aim = normalize3(sub3(pointAimed, org));  // :287
+}
+
+// The lens of a launch that starts its samples through pt_item_begin / pt_list_item_begin, RE-READ from the kernarg segment where a sample
+// starts, as the trace kernels re-read their block (pt_kargs): every such kernel's first argument begins { PtTraceParams t; PtLensCamera
+// cam; ... } (PtAoParams, PtDirectParams and what is built on it).  The roulette, list and LBVH kernels start samples inside their refill
+// loop and several sit exactly on a register step: taken from the by-value copy, the two values and the test on them were hoisted out of
+// that loop and stayed live through the searches -- ten more SGPR spills and, in 24 instantiations, a vector spill.  Read here, nothing of
+// the lens is live once the sample has its ray.
+struct PtLensArgs { PtTraceParams t; PtLensCamera cam; };
+PTK_DEV const __attribute__((address_space(4))) PtLensCamera* pt_lens_kargs()
+{
+    typedef const __attribute__((address_space(4))) PtLensArgs* args_p;
+    args_p k = (args_p)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return &k->cam;
+}
+
+// the sample start's ray, with or without a lens: the branch is uniform for a launch, and lens_radius = 0 (-0, too) takes pt_generate_ray
+// as it stands, whatever focus_distance holds.  `cam` is the launch's camera, the by-value copy of what pt_lens_kargs reads
+PTK_DEV void pt_generate_lens_ray(int xc, int yc, float inv_w, float inv_h, float aspect, const PtLensCamera& cam, uint32_t& seed, f3& org,
+                                  f3& dir_out)
+{
+    const auto* lens = pt_lens_kargs();
+    const float R = lens->lens_radius;
+    if (R > 0.0f) {
+        float x, y;
+        pt_pixel_jitter(xc, yc, seed, x, y);
+        f3 aim;
+        pt_lens_aim(x, y, inv_w, inv_h, aspect, PT_CAM_K(cam), R, lens->focus_distance, seed, org, aim);
+        dir_out = normalize3(aim);  // getRay's own normalize (:75)
+    } else {
+        pt_generate_ray(xc, yc, inv_w, inv_h, aspect, PT_CAM_K(cam), seed, org, dir_out);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // primary-ray candidate masks (quad scenes of up to 64 triangles)
 // ------------------------------------------------------------------------------------------
@@ -3116,7 +3176,7 @@ void pt_query_bvh_kernel(const PtQueryParams Q)
 
 // ray gid of frame `frame` as the renderer traces it (seed :305-308, pixel jitter, the camera's expression), with the direction
 // getRay receives at :287 -- a query normalises it once more, as getRay does, and traces the renderer's primary ray bit for bit
-__global__ __launch_bounds__(256) void pt_camera_rays_kernel(const PtCamera cam, int width, unsigned npix, float inv_w, float inv_h, float aspect,
+__global__ __launch_bounds__(256) void pt_camera_rays_kernel(const PtLensCamera cam, int width, unsigned npix, float inv_w, float inv_h, float aspect,
                                                              int frame, float4* __restrict__ rays)
 {
     const unsigned gid = blockIdx.x * 256u + threadIdx.x;
@@ -3126,7 +3186,8 @@ __global__ __launch_bounds__(256) void pt_camera_rays_kernel(const PtCamera cam,
     float fx, fy;
     pt_pixel_jitter((int)x, (int)y, seed, fx, fy);
     f3 org, aim;
-    pt_camera_aim(fx, fy, inv_w, inv_h, aspect, PT_CAM_K(cam), org, aim);
+    if (cam.lens_radius > 0.0f) pt_lens_aim(fx, fy, inv_w, inv_h, aspect, PT_CAM_K(cam), cam.lens_radius, cam.focus_distance, seed, org, aim);
+    else pt_camera_aim(fx, fy, inv_w, inv_h, aspect, PT_CAM_K(cam), org, aim);
     rays[2 * (size_t)gid] = make_float4(org.x, org.y, org.z, 1e20f);
     rays[2 * (size_t)gid + 1] = make_float4(aim.x, aim.y, aim.z, 0.0f);
 }
@@ -3141,7 +3202,7 @@ __global__ __launch_bounds__(256) void pt_camera_rays_kernel(const PtCamera cam,
 
 // the start of sample `item` of a frame-major launch over npix local pixels from frame frame0 on (item = f * npix + local pixel): its
 // local pixel and its primary ray (pt_sample_begin's seed and camera ray) -- ambient occlusion and direct illumination alike
-PTK_DEV void pt_item_begin(const PtTraceParams& P, const PtCamera& cam, unsigned npix, int frame0, unsigned item, unsigned& lp, uint32_t& seed,
+PTK_DEV void pt_item_begin(const PtTraceParams& P, const PtLensCamera& cam, unsigned npix, int frame0, unsigned item, unsigned& lp, uint32_t& seed,
                            f3& o, f3& d)
 {
     const unsigned f = item / npix;
@@ -3150,7 +3211,7 @@ PTK_DEV void pt_item_begin(const PtTraceParams& P, const PtCamera& cam, unsigned
     pt_pixel_xy<false>(P, nullptr, lp, x, grow);
     const unsigned gid = grow * (unsigned)P.width + x;
     seed = gid + pt_hash_u32((uint32_t)(frame0 + (int)f));
-    pt_generate_ray((int)x, (int)grow, P.inv_width, P.inv_height, P.aspect, PT_CAM_K(cam), seed, o, d);
+    pt_generate_lens_ray((int)x, (int)grow, P.inv_width, P.inv_height, P.aspect, cam, seed, o, d);
 }
 
 PTK_DEV void pt_ao_begin(const PtAoParams& A, unsigned item, unsigned& lp, uint32_t& seed, f3& o, f3& d)
@@ -4256,7 +4317,7 @@ PTK_DEV void pt_list_item_begin(const PtIndirectListParams& I, unsigned item, un
     pt_pixel_xy<false>(P, nullptr, lp, x, grow);
     const unsigned gid = grow * (unsigned)P.width + x;
     seed = gid + pt_hash_u32(frame);
-    pt_generate_ray((int)x, (int)grow, P.inv_width, P.inv_height, P.aspect, PT_CAM_K(I.d.cam), seed, o, d);
+    pt_generate_lens_ray((int)x, (int)grow, P.inv_width, P.inv_height, P.aspect, I.d.cam, seed, o, d);
 }
 
 // Brute force with Russian roulette (pt_render_indirect_rr): a NEW kernel beside pt_indirect_kernel, which stays as it is.  Roulette
@@ -5214,7 +5275,7 @@ hipError_t ptk_ao_resolve(const uint2* counts, float4* image, uint32_t npix, uin
     return hipGetLastError();
 }
 
-hipError_t ptk_camera_rays(const PtCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s)
+hipError_t ptk_camera_rays(const PtLensCamera& cam, int width, int height, int frame, float4* rays, hipStream_t s)
 {
     const unsigned npix = (unsigned)width * (unsigned)height;
     if (npix == 0) return hipSuccess;

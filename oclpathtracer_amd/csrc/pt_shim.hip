@@ -991,6 +991,8 @@ static HostV3 hv_normalize(HostV3 a)
     return { a.x * inv, a.y * inv, a.z * inv };
 }
 
+static_assert(sizeof(pt_camera) == 64 && offsetof(pt_camera, lens_radius) == 40 && offsetof(pt_camera, focus_distance) == 44 &&
+              offsetof(pt_camera, reserved) == 48, "pt_camera layout");
 static void camera_reference(pt_camera* c)
 {
     memset(c, 0, sizeof *c);
@@ -1000,10 +1002,15 @@ static void camera_reference(pt_camera* c)
     c->fov_y_deg = 60.0f;                                               // :263
 }
 
-static int camera_derive(const pt_camera* c, PtCamera* out)
+// THE camera derivation, shared by every entry point: the pinhole's thirteen values and the thin lens (include/pt_shim.h: pt_camera).
+// The lens is validated here and nowhere else; an entry point that takes none (pt_render_frames_camera) refuses lens_radius > 0 itself
+static int camera_derive(const pt_camera* c, PtLensCamera* out)
 {
-    for (int i = 0; i < 6; ++i)
+    for (int i = 0; i < 4; ++i)
         if (c->reserved[i] != 0) return fail(PT_ERR_INVALID, "camera: reserved fields must be zero");
+    if (!(std::isfinite(c->lens_radius) && c->lens_radius >= 0.0f)) return fail(PT_ERR_INVALID, "camera: lens_radius must be finite and >= 0");
+    if (!(std::isfinite(c->focus_distance) && c->focus_distance >= 0.0f)) return fail(PT_ERR_INVALID, "camera: focus_distance must be 0 or finite and > 0");
+    if (c->lens_radius > 0.0f && !(c->focus_distance > 0.0f)) return fail(PT_ERR_INVALID, "camera: lens_radius > 0 needs focus_distance > 0");
     for (int i = 0; i < 3; ++i)
         if (!std::isfinite(c->eye[i]) || !std::isfinite(c->center[i]) || !std::isfinite(c->up[i]))
             return fail(PT_ERR_INVALID, "camera: eye, center and up must be finite");
@@ -1024,15 +1031,17 @@ static int camera_derive(const pt_camera* c, PtCamera* out)
     memcpy(out->hol, v + 6, sizeof out->hol);
     memcpy(out->up, v + 9, sizeof out->up);
     out->angle = angle;
+    out->lens_radius = c->lens_radius;
+    out->focus_distance = c->focus_distance;
     return PT_OK;
 }
 
-static PtCamera reference_camera()
+static PtLensCamera reference_camera()
 {
-    static const PtCamera c = [] {
+    static const PtLensCamera c = [] {
         pt_camera rc;
         camera_reference(&rc);
-        PtCamera r;
+        PtLensCamera r;
         camera_derive(&rc, &r);
         return r;
     }();
@@ -1047,11 +1056,11 @@ extern "C" void pt_camera_reference(pt_camera* out)
 extern "C" int pt_camera_derive(const pt_camera* cam, float out[16])
 {
     if (!cam || !out) return fail(PT_ERR_INVALID, "null argument");
-    PtCamera c;
+    PtLensCamera c;
     int rc = camera_derive(cam, &c);
     if (rc) return rc;
     const float v[16] = { c.eye[0], c.eye[1], c.eye[2], c.view[0], c.view[1], c.view[2], c.hol[0], c.hol[1], c.hol[2],
-                          c.up[0], c.up[1], c.up[2], c.angle, 0.0f, 0.0f, 0.0f };
+                          c.up[0], c.up[1], c.up[2], c.angle, c.lens_radius, c.focus_distance, 0.0f };
     memcpy(out, v, sizeof v);
     return PT_OK;
 }
@@ -1267,7 +1276,7 @@ static int prepare_search(pt_device_s* d, const pt_buffer_s* tris, int ntri, con
     if ((rc = ensure_prep(d, tris, ntri))) return rc;
     if (use_bvh && (rc = ensure_bvh(d, tris, ntri))) return rc;
     PtFilterTable& ft = use_bvh ? d->big_filter : d->scene_filter;
-    const PtCamera ref = reference_camera();
+    const PtLensCamera ref = reference_camera();
     const float* anchor = eye ? eye : ft.anchor_valid ? ft.anchor : ref.eye;
     if ((rc = use_bvh ? ensure_anchor(d, ft, d->bigtab, d->nbig, anchor) : ensure_anchor(d, ft, d->prep, d->prep_ntri, anchor))) return rc;
     s.mode = { use_bvh, d->prep_det_bounded, (d->opt_quads == 0 || d->opt_quads == 4) ? ft.quads : 0 };
@@ -1706,8 +1715,12 @@ extern "C" int pt_render_frames_camera(pt_device_t d, pt_buffer_t triangles, pt_
     int rc = use_device(d);
     if (rc) return rc;
     if (!params) return fail(PT_ERR_INVALID, "params == NULL");
-    PtCamera c = reference_camera();
+    PtLensCamera c = reference_camera();
     if (cam && (rc = camera_derive(cam, &c))) return rc;   // (nothing enqueued, nothing submitted)
+    // the fused kernels' primary-ray masks and pass-1 tables are built on org == eye bit for bit: no lens here
+    if (c.lens_radius > 0.0f)
+        return fail(PT_ERR_INVALID, "pt_render_frames_camera takes no thin lens (lens_radius > 0): render it with pt_render_indirect and no lights "
+                                    "(IndirectRenderer), which computes the same image and takes the lens");
     if ((rc = flush_pending(d))) return rc;
     return render_internal(d, triangles, materials, framebuffer, *params, c, 0, stats, ev);
 }
@@ -1788,7 +1801,7 @@ extern "C" int pt_render_ao(pt_device_t d, pt_buffer_t triangles, pt_buffer_t co
     if (rc) return rc;
     if (!params) return fail(PT_ERR_INVALID, "params == NULL");
     const pt_ao_params a = *params;
-    PtCamera c = reference_camera();
+    PtLensCamera c = reference_camera();
     if (cam && (rc = camera_derive(cam, &c))) return rc;
     if (!triangles || !counts) return fail(PT_ERR_INVALID, "null buffer handle");
     if ((rc = check_same_device(d, { triangles, counts, image })) || (rc = check_event(d, ev))) return rc;
@@ -1890,7 +1903,7 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     const pt_buffer_t triangles = c.triangles, materials = c.materials, lights = c.lights, light_counts = c.light_counts, cdf = c.cdf,
                       tri_q = c.tri_q, samples = c.samples, framebuffer = c.framebuffer, list = c.list;
     int rc;
-    PtCamera cam = reference_camera();
+    PtLensCamera cam = reference_camera();
     if (c.cam && (rc = camera_derive(c.cam, &cam))) return rc;
     if (!triangles || !materials || !samples || !framebuffer || (c.kind.list && !list)) return fail(PT_ERR_INVALID, "null buffer handle");
     if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer, cdf, tri_q, list, c.env, c.env_cdf })) || (rc = check_event(d, c.ev))) return rc;
@@ -2384,7 +2397,7 @@ extern "C" int pt_camera_rays(pt_device_t d, const pt_camera* cam, int width, in
 {
     int rc = use_device(d);
     if (rc) return rc;
-    PtCamera c = reference_camera();
+    PtLensCamera c = reference_camera();
     if (cam && (rc = camera_derive(cam, &c))) return rc;
     if (!rays) return fail(PT_ERR_INVALID, "null buffer handle");
     if ((rc = check_same_device(d, { rays })) || (rc = check_event(d, ev))) return rc;

@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]]] [--noise]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]]] [--noise] [--lens R[,F]]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <chrono>
 #include <cmath>
@@ -126,6 +126,7 @@ struct Options {
     double adaptTol = -1.0;           // --adaptive TOL[,MIN[,MAX]]: IndirectIllumination renders MIN frames, then only the pixels still noisy (< 0 = off)
     int adaptMin = 16, adaptMax = 0;  // MAX 0 = --frames
     bool noise = false;               // --noise: DirectIllumination / IndirectIllumination print the image's noise summary
+    float lensR = 0.0f, lensF = 0.0f; // --lens R[,F]: AmbientOcclusion / DirectIllumination / IndirectIllumination through a thin lens of radius R focused at F (0 = where the image's centre ray hits)
     std::string scene = "cornellbox.bin", outDir = ".", dump, only;
 };
 
@@ -316,6 +317,35 @@ static void test_RayCast(DeviceTest& f, const Options& o)
     delete materialBuffer;
 }
 
+// --lens R[,F]: the reference's camera with a thin lens (pt_camera: lens_radius, focus_distance).  Without F the lens is focused where
+// the pinhole ray of the image's centre -- from the eye along the view direction -- hits the scene, found with pt_intersect_rays; a
+// centre ray that leaves the scene fails the case.  Returns `cam`, or 0 without --lens (the entry points then take the reference's camera).
+static const pt_camera* lens_camera(Device* m_d, const Options& o, pt_buffer_t triangles, int numTriangles, pt_camera* cam)
+{
+    if (!(o.lensR > 0.0f)) return 0;
+    pt_camera_reference(cam);
+    cam->lens_radius = o.lensR;
+    cam->focus_distance = o.lensF;
+    if (!(o.lensF > 0.0f)) {
+        Buffer<pt_ray> ray(m_d, 1);
+        Buffer<pt_hit> hit(m_d, 1);
+        pt_ray r;
+        std::memset(&r, 0, sizeof r);
+        for (int k = 0; k < 3; k++) { r.origin[k] = cam->eye[k]; r.dir[k] = cam->center[k] - cam->eye[k]; }
+        r.tmax = 1e20f;
+        ray.write(&r, 1);
+        pt_hit h;
+        std::memset(&h, 0, sizeof h);
+        IASSERT(pt_intersect_rays(m_d->m_handle, triangles, numTriangles, ray.m_handle, hit.m_handle, 1, PT_QUERY_CLOSEST, 0) == PT_OK);
+        hit.read(&h, 1);
+        DeviceUtils::waitForCompletion(m_d);
+        IASSERT(h.tri >= 0);
+        cam->focus_distance = h.tri >= 0 ? h.t : 1.0f;
+    }
+    std::printf("lens: radius %g, focused at %g\n", cam->lens_radius, cam->focus_distance);
+    return cam;
+}
+
 // TEST_F(DeviceTest, AmbientOcclusion): the reference declares the case with an empty body (RaytraceTest.cpp:293-295).  Here it
 // renders the scene's ambient occlusion through pt_render_ao -- dim x dim, --frames frames, K = 16, radius 1.0 -- and writes
 // ambientOcclusion_<version>.ppm through pt_tonemap_ppm, as RayCast writes its image.  Run only when asked for (--only).
@@ -345,8 +375,10 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
     p.radius = 1.0f;
     p.miss_value = 1.0f;
     p.stripe_rows = 1; p.n_ranks = 1; p.rank = 0;
+    pt_camera lens;
+    const pt_camera* cam = lens_camera(m_d, o, tBuffer.m_handle, p.num_triangles, &lens);
     auto t0 = std::chrono::steady_clock::now();
-    IASSERT(pt_render_ao(m_d->m_handle, tBuffer.m_handle, counts.m_handle, image.m_handle, &p, 0, 0) == PT_OK);
+    IASSERT(pt_render_ao(m_d->m_handle, tBuffer.m_handle, counts.m_handle, image.m_handle, &p, cam, 0) == PT_OK);
     IASSERT(pt_tonemap_ppm(m_d->m_handle, image.m_handle, rgb.m_handle, npix, 0) == PT_OK);
     std::vector<int> h(3 * npix, 0);
     rgb.read(h.data(), 3 * npix);
@@ -355,6 +387,7 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
     std::printf("AmbientOcclusion: %d x %d x %d frames, K = 16, radius 1.0 in %.3f s\n", dimension, dimension, o.frames, secs);
     char path[512];
     f.getFilePath(o.outDir.c_str(), "ambientOcclusion", "ppm", path, sizeof path);
+    if (cam && std::strlen(path) + 6 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_lens.ppm");
     FILE* fp = std::fopen(path, "w");
     IASSERT(fp != 0);
     if (fp) {
@@ -479,34 +512,36 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
                                triq.m_handle, 0) == PT_OK);
     if (mis) IASSERT(pt_light_counts(m_d->m_handle, lh, p.num_lights, p.num_triangles, cBuffer.m_handle, 0) == PT_OK);
     // frames [first, first + count) through the case's entry point
+    pt_camera lens;
+    const pt_camera* cam = lens_camera(m_d, o, tBuffer.m_handle, p.num_triangles, &lens);
     auto render = [&](int first, int count) {
         p.frame_begin = q.frame_begin = first;
         p.frame_count = q.frame_count = count;
         if (o.env && bounces)
             return pt_render_indirect_env(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cBuffer.m_handle, cdf.m_handle, triq.m_handle,
-                                          envMap.m_handle, envCdf.m_handle, samples.m_handle, image.m_handle, &q, rr ? &roulette : &none, &environment, 0, 0);
+                                          envMap.m_handle, envCdf.m_handle, samples.m_handle, image.m_handle, &q, rr ? &roulette : &none, &environment, cam, 0);
         if (o.env)
             return pt_render_direct_env(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cdf.m_handle, triq.m_handle, envMap.m_handle,
-                                        envCdf.m_handle, samples.m_handle, image.m_handle, &p, &environment, 0, 0);
+                                        envCdf.m_handle, samples.m_handle, image.m_handle, &p, &environment, cam, 0);
         if (resample && bounces)
             return pt_render_indirect_ris(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0, cdf.m_handle,
-                                          triq.m_handle, samples.m_handle, image.m_handle, &q, rr ? &roulette : &none, &ris, 0, 0);
+                                          triq.m_handle, samples.m_handle, image.m_handle, &q, rr ? &roulette : &none, &ris, cam, 0);
         if (resample)
             return pt_render_direct_ris(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cdf.m_handle, triq.m_handle, samples.m_handle,
-                                        image.m_handle, &p, &ris, 0, 0);
+                                        image.m_handle, &p, &ris, cam, 0);
         if (rr)
             return pt_render_indirect_rr(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0,
-                                         o.power ? cdf.m_handle : 0, o.power ? triq.m_handle : 0, samples.m_handle, image.m_handle, &q, &roulette, 0, 0);
+                                         o.power ? cdf.m_handle : 0, o.power ? triq.m_handle : 0, samples.m_handle, image.m_handle, &q, &roulette, cam, 0);
         if (o.power && bounces)
             return pt_render_indirect_power(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0, cdf.m_handle,
-                                            triq.m_handle, samples.m_handle, image.m_handle, &q, 0, 0);
+                                            triq.m_handle, samples.m_handle, image.m_handle, &q, cam, 0);
         if (o.power)
             return pt_render_direct_power(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cdf.m_handle, triq.m_handle, samples.m_handle,
-                                          image.m_handle, &p, 0, 0);
+                                          image.m_handle, &p, cam, 0);
         if (mis)
-            return pt_render_indirect_mis(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cBuffer.m_handle, samples.m_handle, image.m_handle, &q, 0, 0);
-        if (bounces) return pt_render_indirect(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, samples.m_handle, image.m_handle, &q, 0, 0);
-        return pt_render_direct(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, samples.m_handle, image.m_handle, &p, 0, 0);
+            return pt_render_indirect_mis(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, cBuffer.m_handle, samples.m_handle, image.m_handle, &q, cam, 0);
+        if (bounces) return pt_render_indirect(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, samples.m_handle, image.m_handle, &q, cam, 0);
+        return pt_render_direct(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, samples.m_handle, image.m_handle, &p, cam, 0);
     };
     const bool adaptive = bounces && o.adaptTol >= 0.0;
     Buffer<pt_pixel_moments> moments(m_d, o.noise || adaptive ? npix : 0);
@@ -548,11 +583,11 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
                 if (resample)
                     IASSERT(pt_render_indirect_pixels_ris(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0,
                                                           cdf.m_handle, triq.m_handle, samples.m_handle, image.m_handle, pixelList.m_handle, listed,
-                                                          &q, &play, &ris, 0, 0) == PT_OK);
+                                                          &q, &play, &ris, cam, 0) == PT_OK);
                 else
                     IASSERT(pt_render_indirect_pixels(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, mis ? 1 : 0, mis ? cBuffer.m_handle : 0,
                                                       o.power ? cdf.m_handle : 0, o.power ? triq.m_handle : 0, samples.m_handle, image.m_handle,
-                                                      pixelList.m_handle, listed, &q, &play, 0, 0) == PT_OK);
+                                                      pixelList.m_handle, listed, &q, &play, cam, 0) == PT_OK);
                 IASSERT(pt_sample_moments_pixels(m_d->m_handle, samples.m_handle, moments.m_handle, pixelList.m_handle, listed, q.frame_count, 0) == PT_OK);
             }
             adaptiveSamples += (unsigned long long)listed * (unsigned long long)chunk;
@@ -598,6 +633,7 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     if (resample && std::strlen(path) + 8 < sizeof path) std::snprintf(path + std::strlen(path) - 4, 12, "_ris%d.ppm", o.candidates);
     if (o.env && std::strlen(path) + 9 < sizeof path) std::strcpy(path + std::strlen(path) - 4, o.env == 1 ? "_envsun.ppm" : "_envgrey.ppm");
     if (adaptive && std::strlen(path) + 10 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_adaptive.ppm");
+    if (cam && std::strlen(path) + 6 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_lens.ppm");
     FILE* fp = std::fopen(path, "w");
     IASSERT(fp != 0);
     if (fp) {
@@ -645,6 +681,16 @@ int main(int argc, char** argv)
                 return 2;
             }
         }
+        else if (a == "--lens") {
+            const std::string v = next();
+            char* end = 0;
+            o.lensR = std::strtof(v.c_str(), &end);
+            if (end && *end == ',') o.lensF = std::strtof(end + 1, &end);
+            if (end == v.c_str() || !end || *end != 0 || !(o.lensR > 0.0f) || !std::isfinite(o.lensR) || !(o.lensF >= 0.0f) || !std::isfinite(o.lensF)) {
+                std::fprintf(stderr, "--lens takes R[,F] with R > 0 and F > 0 (without F: the distance the image's centre ray travels)\n");
+                return 2;
+            }
+        }
         else if (a == "--candidates") {
             o.candidates = std::atoi(next());
             if (o.candidates < 1 || o.candidates > 32) { std::fprintf(stderr, "--candidates takes M in 1..32\n"); return 2; }
@@ -668,6 +714,10 @@ int main(int argc, char** argv)
     if (o.dim < 1 || o.frames < 0) { std::fprintf(stderr, "bad --dim/--frames\n"); return 2; }
     if (o.candidates > 0 && !o.power) { std::fprintf(stderr, "--candidates needs --lights power (the candidates are drawn from the light table)\n"); return 2; }
     if (o.env && (!o.power || o.candidates > 0 || o.adaptTol >= 0.0)) { std::fprintf(stderr, "--env needs --lights power and goes with neither --candidates nor --adaptive\n"); return 2; }
+    if (o.lensR > 0.0f && o.only != "AmbientOcclusion" && o.only != "DirectIllumination" && o.only != "IndirectIllumination") {
+        std::fprintf(stderr, "--lens goes with --only AmbientOcclusion, DirectIllumination or IndirectIllumination (RayCast's kernels take no lens)\n");
+        return 2;
+    }
     if (o.env && o.only == "IndirectIllumination" && !o.mis) { std::fprintf(stderr, "--env with IndirectIllumination needs --mis\n"); return 2; }
     struct { const char* name; int kind; } tests[] = { { "initialize", 0 }, { "deviceInfo", 1 }, { "MemoryAllocation", 2 }, { "writeRead", 3 },
                                                        { "getHostPtr", 4 }, { "kernelExecution", 5 }, { "RayCast", 6 },

@@ -22,7 +22,7 @@ import torch
 import torch.distributed as dist
 
 from . import adl, shim
-from .render import Renderer
+from .render import Renderer, refuse_lens
 
 
 class StripePlan:
@@ -89,6 +89,7 @@ class StripeImage:
         takes it; see ``bench.py``).  Every render must then start at frame 0 or continue its own slot's frames.
         ``camera``: the viewpoint (a :class:`~oclpathtracer_amd.camera.Camera`, None = the reference's); seeds and camera rays use
         global pixel ids, so the assembled image equals the one-device image for any camera."""
+        refuse_lens(camera)   # (before a tensor is allocated or a wait enqueued)
         self.dev, self.world, self.rank = dev, int(world), int(rank)
         self.width, self.height = int(width), int(height)
         self.plan = StripePlan(height, stripe_rows, world)

@@ -64,6 +64,14 @@ def raycast_reference_loop(dev: adl.Device, triangles: np.ndarray, materials: np
     return out
 
 
+def refuse_lens(camera: Optional[Camera]) -> None:
+    """The fused renderer (``Renderer`` and what is built on it: ``ProgressiveRenderer``, ``StripeImage``) takes no thin lens, as
+    pt_render_frames_camera takes none: its kernels' primary-ray masks are built on origin == eye.  Raised before anything is enqueued."""
+    if isinstance(camera, Camera) and camera.lens_radius > 0.0:
+        raise ValueError("the fused renderer takes no thin lens (lens_radius > 0): use IndirectRenderer with no lights, which "
+                         "renders the same image and takes the lens, or Camera.with_lens(0.0) for the pinhole")
+
+
 class Renderer:
     """One device's share of an image, rendered with the fused multi-frame entry point.
 
@@ -122,6 +130,7 @@ class Renderer:
         self.frames_done = frame_begin + frames
 
     def _set_camera(self, camera: Optional[Camera]) -> None:
+        refuse_lens(camera)
         self._cam = Camera.struct_of(camera)
         self.camera = camera
 

@@ -56,13 +56,27 @@ class RenderParams(_c.Structure):
     ]
 
 
-class Camera(_c.Structure):
-    """pt_camera (64 bytes): eye, center, up, vertical field of view in degrees; reserved must be 0."""
+class _CameraLens(_c.Structure):
+    _fields_ = [("lens_radius", _c.c_float), ("focus_distance", _c.c_float)]
 
+
+class _CameraTail(_c.Union):
+    """the six trailing words of pt_camera: the thin lens' two floats laid over the first two of ``reserved``"""
+
+    _anonymous_ = ("lens",)
+    _fields_ = [("lens", _CameraLens), ("reserved", _c.c_int32 * 6)]
+
+
+class Camera(_c.Structure):
+    """pt_camera (64 bytes): eye, center, up, vertical field of view in degrees; the thin lens (``lens_radius``, ``focus_distance``:
+    offsets 40 and 44, both 0 = the pinhole) and four reserved words, which must be 0.  ``reserved`` is the view of all six trailing
+    words, as before the lens: ``reserved[0]`` and ``reserved[1]`` are the bits of the two floats."""
+
+    _anonymous_ = ("tail",)
     _fields_ = [
         ("eye", _c.c_float * 3), ("center", _c.c_float * 3), ("up", _c.c_float * 3),
         ("fov_y_deg", _c.c_float),
-        ("reserved", _c.c_int32 * 6),
+        ("tail", _CameraTail),
     ]
 
 
