@@ -163,10 +163,16 @@ struct PtTraceParams {
 #define PT_QUEUE_SHARD_WORDS 1056
 #define PT_QUEUE_STOP_WORD (PT_QUEUE_SHARDS * PT_QUEUE_SHARD_WORDS)
 #define PT_QUEUE_WORDS ((PT_QUEUE_SHARDS + 1) * PT_QUEUE_SHARD_WORDS)
-#define PT_CARRY_RECORDS 64       // a wave stops with an empty pool and parks its (at most 64) live paths
+#define PT_POOL 56                // parked-path slots per wave of a table kernel (why 56: above PtWaveQueue, pt_kernels.hip)
+#define PT_CARRY_RECORDS 64       // the LBVH kernel has no pool: a wave stops with its (at most 64) live lanes
 #define PT_CARRY_STRIDE_DW (16 + PT_CARRY_RECORDS * 15)   // header (paths, pix, end, ring frame, absolute frame) + the parked-path record as arrays (the LBVH kernel's)
-// the table kernels park SEARCHED paths (pt_trace_body): 18 dwords a record -- hit point, direction, mask, L, seed, ro, hu, hv, fl | bounce, triangle
-#define PT_CARRY_HIT_STRIDE_DW (16 + PT_CARRY_RECORDS * 18)
+// the table kernels park SEARCHED paths (pt_trace_body): 18 dwords a record -- hit point, direction, mask, L, seed, ro, hu, hv, fl | bounce, triangle.
+// A wave of theirs stops by parking its live paths into its EMPTY pool, as a fresh phase does, and stores the pool: at most PT_POOL records, never 64
+#define PT_CARRY_HIT_RECORDS PT_POOL
+#define PT_CARRY_HIT_STRIDE_DW (16 + PT_CARRY_HIT_RECORDS * 18)
+// one allocation serves a render whichever kernel it runs (pt_shim.hip: PT_CARRY_HIT_STRIDE_DW dwords per wave); 1 024 dwords, 4 KiB, a region
+static_assert(PT_CARRY_HIT_STRIDE_DW >= PT_CARRY_STRIDE_DW, "a checkpoint region holds either kernel's records");
+static_assert(PT_CARRY_HIT_STRIDE_DW % 4 == 0 && PT_CARRY_STRIDE_DW % 4 == 0, "a region's float4 arrays begin 16 dwords in: every region 16-byte aligned");
 // The kernel with the table in LDS packs fl | bounce << 16 | triangle << 24 into one dword (17 a record: what lets its pools fit 8 workgroups
 // a CU): a parked path's bounce count, below max_bounces, must fit 8 bits, and so must its triangle (PT_LDS_TRI_MAX).  The host refuses a deeper render on that kernel (pt_shim.hip: render_part).
 #define PT_PACKED_BOUNCE_MAX 256

@@ -1307,7 +1307,7 @@ PTK_DEV void pt_flush_counters(const PtTraceParams& P, unsigned lane, unsigned n
 // 68-byte records (pt_hit_store) and the 20 480 B a workgroup may have for 8 of them to fit a CU leave room for 56 per wave, not 64:
 // a fresh phase parks every live path, so it starts only when at most PT_POOL lanes are alive, i.e. at least 8 are dead.  Until then
 // the iteration goes on with its fewer than 8 idle lanes and asks again after the next search.
-#define PT_POOL 56  // parked-path slots per wave (a fresh phase parks at most PT_POOL live paths: pt_trace_body)
+// PT_POOL, the parked-path slots per wave, is defined in pt_kernels.h: the checkpoint regions are sized by it (PT_CARRY_HIT_RECORDS).
 
 struct PtWaveQueue {  // wave-uniform (SGPRs): the wave's current range [pix, end) of local pixels of `frame`
     unsigned pix, end, frame;   // frame: counted from the render's first frame (what a path keeps as `fl`)
@@ -1390,16 +1390,16 @@ PTK_DEV PtPathSlots pt_carry_slots(uint32_t* region) { return { (float4*)(region
 // and NW dwords: fl | bounce << 16 | triangle << 24 beside the LDS table (NW 1: a triangle below PT_LDS_TRI_MAX and a bounce count below
 // PT_PACKED_BOUNCE_MAX fit 8 bits each, 68 bytes a record), fl | bounce << 16 and the triangle otherwise (NW 2).  The pool keeps four
 // float4 arrays of PT_POOL entries and one array of NW dwords per record, a carry region four float4 arrays and two dword arrays of
-// PT_CARRY_RECORDS entries (PT_CARRY_HIT_STRIDE_DW: one stride for both forms).
+// PT_CARRY_HIT_RECORDS = PT_POOL entries (PT_CARRY_HIT_STRIDE_DW: one stride for both forms).
 static_assert(PT_LDS_TRI_MAX <= 256 && PT_PACKED_BOUNCE_MAX <= 256, "triangle and bounce count of a parked path: 8 bits each of the packed word");
 template <int LDS_TABLE> __host__ __device__ constexpr unsigned pt_hit_words() { return LDS_TABLE == 1 ? 1u : 2u; }
 template <int LDS_TABLE> __host__ __device__ constexpr unsigned pt_pool_dwords() { return PT_POOL * (16u + pt_hit_words<LDS_TABLE>()); }
 // the waves' pools follow one another, and each begins with its float4 arrays: a pool is whole float4s (56 records are, 57 of 17 dwords
 // are not), or the next wave's b128 accesses are misaligned; and a stopping wave's pool goes to its region record by record
 static_assert(pt_pool_dwords<1>() % 4u == 0u && pt_pool_dwords<2>() % 4u == 0u, "a wave's pool must be a whole number of float4: the next pool's 16-byte alignment");
-static_assert(PT_POOL <= PT_CARRY_RECORDS, "a checkpoint region holds a whole pool");
+static_assert(PT_POOL <= PT_CARRY_HIT_RECORDS, "a checkpoint region holds a whole pool");
 template <unsigned NW> PTK_DEV PtPathSlots pt_pool_slots(float4* pool) { return { pool, reinterpret_cast<unsigned*>(pool + 4 * PT_POOL), PT_POOL, 1u, NW }; }
-PTK_DEV PtPathSlots pt_carry_hit_slots(uint32_t* region) { return { (float4*)(region + 16), region + 16 + PT_CARRY_RECORDS * 16, PT_CARRY_RECORDS, PT_CARRY_RECORDS, 1u }; }
+PTK_DEV PtPathSlots pt_carry_hit_slots(uint32_t* region) { return { (float4*)(region + 16), region + 16 + PT_CARRY_HIT_RECORDS * 16, PT_CARRY_HIT_RECORDS, PT_CARRY_HIT_RECORDS, 1u }; }
 
 // what a lane of a table kernel holds between the search and shading: the path (s.o is the hit point) and the hit
 struct PtHit {
@@ -1536,7 +1536,7 @@ PTK_DEV void pt_carry_store(uint32_t* region, unsigned lane, float4* pool, unsig
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the wave's own pool writes, read by other lanes: as in pt_pool_pop
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < pool_n) {   // (pool_n <= PT_POOL <= PT_CARRY_RECORDS)
+    if (lane < pool_n) {   // (pool_n <= PT_POOL = PT_CARRY_HIT_RECORDS)
         const PtPathSlots from = pt_pool_slots<NW>(pool), to = pt_carry_hit_slots(region);
         for (unsigned j = 0; j < 4u; ++j) to.vec(j, lane) = from.vec(j, lane);
         for (unsigned j = 0; j < NW; ++j) to.word(j, lane) = from.word(j, lane);
@@ -1558,7 +1558,7 @@ PTK_DEV void pt_carry_store_lanes(uint32_t* region, unsigned lane, const PtPath&
 }
 
 // Resuming a checkpoint.  The header first, for either kernel: the tallies, and the rest of the batch becomes the wave's current
-// range; returns the number of records.  Then the records go straight into lanes (at most 64: the pool was empty when they were
+// range; returns the number of records.  Then the records go straight into lanes (at most 64, of a table kernel at most PT_POOL: the pool was empty when they were
 // parked) -- pt_carry_load for the LBVH kernel's paths, pt_carry_hit_load for the table kernels' searched ones.
 template <bool LATE>
 PTK_DEV unsigned pt_carry_header_load(const PtTraceParams& P, const uint32_t* region, PtWaveQueue& q, unsigned& n_rays, unsigned& n_samples, unsigned& n_carried)

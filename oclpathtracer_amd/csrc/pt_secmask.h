@@ -118,12 +118,13 @@
 #define PT_SM_HD static inline
 #endif
 
-// tiles per edge of a triangle's plane, direction cells per edge of a cube face (profiles/secondary_masks/steps.txt)
+// tiles per edge of a triangle's plane, direction cells per edge of a cube face (profiles/secondary_masks/steps.txt; the split between
+// the two, and the odd C: profiles/table_shape/steps.txt)
 #ifndef PT_SM_T
 #define PT_SM_T 12
 #endif
 #ifndef PT_SM_C
-#define PT_SM_C 8
+#define PT_SM_C 11
 #endif
 // the builder's refinement (pt_sm_entry): the depth at which a box is kept, the boxes bounded per pair (cell, target triangle) before
 // it is kept, and the least det_lo / (|f1|_1 |f2|_1) at which the separating plane is tried (profiles/tight_masks/steps.txt)
@@ -144,6 +145,10 @@
 struct PtSmTri { float A[4], B[4], N[4]; };   // tu = A . o + A[3], tv = B . o + B[3], th = N . o + N[3]
 #define PT_SM_HEAD_ENTRIES (PT_SM_TRI_MAX * sizeof(PtSmTri) / 8)
 #define PT_SM_TABLE_BYTES(ntri) ((PT_SM_HEAD_ENTRIES + (size_t)(ntri) * PT_SM_TRI_ENTRIES) * 8)
+// the classification's rounding bound (|ca - ca_real| < 3.4e-6 against the builder's dc = 1e-4, above) is worked out for C <= 16; C / 2 and
+// C - 1 are exact floats for any such C, odd or even.  The trace kernel and the builder address an entry by a 32-bit byte offset
+static_assert(PT_SM_T >= 1 && PT_SM_C >= 1 && PT_SM_C <= 16, "pt_sm_classify's rounding bound is derived for C <= 16");
+static_assert(PT_SM_TABLE_BYTES(PT_SM_TRI_MAX) < 0x100000000ull, "an entry's byte offset in the largest table must fit 32 bits");
 
 struct PtSmMask { unsigned x, y; };   // uint2
 

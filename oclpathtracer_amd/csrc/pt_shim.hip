@@ -1468,8 +1468,8 @@ static int ensure_carry(pt_device_s* d, int blocks)
     if ((size_t)blocks * wg_waves > waves) return fail(PT_ERR_INVALID, "grid larger than the checkpoint regions");
     for (int k = 0; k < 2; ++k)
         if (!d->carry[k]) {   // once per device handle, at its first such render
-            // (a region serves whichever kernel the render runs: the table kernels' searched-path records are the larger)
-            static_assert(PT_CARRY_HIT_STRIDE_DW >= PT_CARRY_STRIDE_DW, "a checkpoint region holds either kernel's records");
+            // (a region serves whichever kernel the render runs: PT_POOL searched-path records of a table kernel are more than the LBVH
+            // kernel's 64 paths -- pt_kernels.h asserts it)
             hipError_t e = ws_malloc(d, d->carry[k], waves * PT_CARRY_HIT_STRIDE_DW * sizeof(uint32_t));
             if (e != hipSuccess) return fail(PT_ERR_OOM, "checkpoint buffer allocation failed: %s", hipGetErrorString(e));
         }
