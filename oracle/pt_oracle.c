@@ -16,18 +16,20 @@
  *                                              all W*H work-items
  *
  * PARITY PINNING.  The reference holds no golden vectors, known-answer tests or pixel
- * assertions for this path, its kernel cannot execute in the build
- * container (no OpenCL device) and the OpenCL built-ins it calls (normalize, dot, cross,
- * sin, cos, tan, pow, sqrt, "/") have implementation-defined rounding.  Against the real
- * OpenCL output this oracle is therefore "parity unpinned".  It is pinned instead by the
- * hand-derivable known answers of SURVEY.md S8c (tests/test_oracle_kat.py): the integer
- * RNG/hash values, the camera constants, the decoded scene table and the behavioural
- * invariants of intersectWorld / accumulate -- and, statistically, by the one output of the
- * real OpenCL path tracer that the reference holds, its rendered image
- * FinalRendered_Specular.jpg: block means committed as tests/golden/reference_jpg_blocks_*.npy;
- * this oracle at 128x128 x 800 frames through the reference's output stage matches them to a
- * mean |difference| of 1.9 of 255 (Monte-Carlo + JPEG noise).  Bit-level parity with OpenCL
- * remains unpinned.
+ * assertions for this path and its kernel cannot execute as OpenCL in the build
+ * container (no OpenCL device).  Its program text can: oracle/Makefile's target `ref` compiles
+ * the reference's kernel file itself for the host over PTSPEC stand-ins for the OpenCL built-ins
+ * it calls (ref_glue.cl, ref_builtins.cpp), and tests/test_reference_program_cpu.py compares this
+ * file with it bit for bit -- whole renders, the fold, every function at its edges -- so every
+ * expression, conversion, draw order and branch below is pinned to the reference's text.
+ * What stays unpinned is what OpenCL leaves implementation-defined: the rounding of the built-ins
+ * (normalize, dot, cross, sin, cos, tan, pow, sqrt, "/") and whether the compiler contracts.
+ * Against those stand the hand-derivable known answers of SURVEY.md S8c (tests/test_oracle_kat.py)
+ * and, statistically, the one output of the real OpenCL path tracer that the reference holds, its
+ * rendered image FinalRendered_Specular.jpg: block means committed as
+ * tests/golden/reference_jpg_blocks_*.npy; this oracle at 128x128 x 800 frames through the
+ * reference's output stage matches them to a mean |difference| of 1.9 of 255 (Monte-Carlo + JPEG
+ * noise).
  *
  * ARITHMETIC SPEC (PTSPEC) -- the choices OpenCL leaves open, fixed here and
  * mirrored bit-for-bit by the HIP kernels:
@@ -667,6 +669,140 @@ void ptor_kat_paths(const void* tris, int ntri, const void* mats, const int32_t*
         ptor_ray r = ptor_generate_ray(gid[k] % W, gid[k] / W, W, H, &seed);
         v3 c = ptor_trace_rays(&r, (const ptor_triangle*)tris, ntri, (const ptor_material*)mats, &seed, max_bounces, &st, log);
         out3[3 * k] = c.x; out3[3 * k + 1] = c.y; out3[3 * k + 2] = c.z;
+    }
+}
+
+/* ---- the functions that had no entry point of their own, for the comparison with the reference's compiled program text
+ * (tests/test_reference_program_cpu.py); each works on n records */
+PTOR_CLONES
+void ptor_kat_hash_array(const uint32_t* x, uint32_t* out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = ptor_hash_u32(x[i]);
+}
+
+PTOR_CLONES
+void ptor_kat_random_array(const uint32_t* seed, uint32_t* seed_after, float* value, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t s = seed[i];
+        value[i] = ptor_random_float(&s);
+        seed_after[i] = s;
+    }
+}
+
+/* getRay (:73-87): out6 = origin, dir */
+PTOR_CLONES
+void ptor_kat_get_ray(const float* origin3, const float* dir3, float* out6, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        const float *o = origin3 + 3 * i, *d = dir3 + 3 * i;
+        ptor_ray r = ptor_get_ray(v3_make(o[0], o[1], o[2]), v3_make(d[0], d[1], d[2]));
+        float* q = out6 + 6 * i;
+        q[0] = r.origin.x; q[1] = r.origin.y; q[2] = r.origin.z; q[3] = r.dir.x; q[4] = r.dir.y; q[5] = r.dir.z;
+    }
+}
+
+/* intersectTriangle (:89-135): ray i, its direction as given, against triangle tri[i] with tmax[i]; out7 = t, p, n (zeros when
+ * not accepted) */
+PTOR_CLONES
+void ptor_kat_intersect_triangle(const void* tris, const int32_t* tri, const float* origin3, const float* dir3, const float* tmax,
+                                 float* out7, int32_t* hit, int64_t n)
+{
+    ptor_stats st;
+    memset(&st, 0, sizeof st);
+    for (int64_t i = 0; i < n; ++i) {
+        const float *o = origin3 + 3 * i, *d = dir3 + 3 * i;
+        ptor_ray r;
+        r.origin = v3_make(o[0], o[1], o[2]);
+        r.dir = v3_make(d[0], d[1], d[2]);
+        ptor_hit rec;
+        memset(&rec, 0, sizeof rec);
+        hit[i] = ptor_intersect_triangle(&r, (const ptor_triangle*)tris + tri[i], tri[i], &rec, tmax[i], &st);
+        float* q = out7 + 7 * i;
+        q[0] = rec.t; q[1] = rec.p.x; q[2] = rec.p.y; q[3] = rec.p.z; q[4] = rec.n.x; q[5] = rec.n.y; q[6] = rec.n.z;
+    }
+}
+
+PTOR_CLONES
+void ptor_kat_reflect(const float* v3_, const float* n3, float* out3, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        const float *v = v3_ + 3 * i, *m = n3 + 3 * i;
+        v3 r = ptor_reflect(v3_make(v[0], v[1], v[2]), v3_make(m[0], m[1], m[2]));
+        out3[3 * i] = r.x; out3[3 * i + 1] = r.y; out3[3 * i + 2] = r.z;
+    }
+}
+
+PTOR_CLONES
+void ptor_kat_sample_hemisphere_cosine(const float* n3, const uint32_t* seed, float* out3, uint32_t* seed_after, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        const float* m = n3 + 3 * i;
+        uint32_t s = seed[i];
+        v3 r = ptor_sample_hemisphere_cosine(v3_make(m[0], m[1], m[2]), &s);
+        out3[3 * i] = r.x; out3[3 * i + 1] = r.y; out3[3 * i + 2] = r.z;
+        seed_after[i] = s;
+    }
+}
+
+PTOR_CLONES
+void ptor_kat_sample_ggx(const float* n3, const float* roughness, const uint32_t* seed, float* out3, float* cos_theta,
+                         uint32_t* seed_after, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        const float* m = n3 + 3 * i;
+        uint32_t s = seed[i];
+        float ct = 0.0f;
+        v3 r = ptor_sample_ggx(v3_make(m[0], m[1], m[2]), roughness[i], &ct, &s);
+        out3[3 * i] = r.x; out3[3 * i + 1] = r.y; out3[3 * i + 2] = r.z;
+        cos_theta[i] = ct;
+        seed_after[i] = s;
+    }
+}
+
+PTOR_CLONES
+void ptor_kat_distribution_ggx(const float* cos_theta, const float* roughness, float* out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = ptor_distribution_ggx(cos_theta[i], roughness[i]);
+}
+
+/* Brdf (:195-221): colour3 is the value's x, y, z; wi3 and pdf are in-out (a branch that leaves one untouched leaves what the
+ * caller put there) */
+PTOR_CLONES
+void ptor_kat_brdf(const float* wo3, const float* normal3, const void* mats, const int32_t* mat_index, const uint32_t* seed,
+                   float* colour3, float* wi3, float* pdf, uint32_t* seed_after, int64_t n)
+{
+    ptor_stats st;
+    memset(&st, 0, sizeof st);
+    for (int64_t i = 0; i < n; ++i) {
+        const float *w = wo3 + 3 * i, *m = normal3 + 3 * i;
+        uint32_t s = seed[i];
+        v3 wi = v3_make(wi3[3 * i], wi3[3 * i + 1], wi3[3 * i + 2]);
+        float p = pdf[i];
+        v3 c = ptor_brdf(v3_make(w[0], w[1], w[2]), &wi, &p, v3_make(m[0], m[1], m[2]), (const ptor_material*)mats + mat_index[i], &s, &st);
+        colour3[3 * i] = c.x; colour3[3 * i + 1] = c.y; colour3[3 * i + 2] = c.z;
+        wi3[3 * i] = wi.x; wi3[3 * i + 1] = wi.y; wi3[3 * i + 2] = wi.z;
+        pdf[i] = p;
+        seed_after[i] = s;
+    }
+}
+
+/* traceRays (:223-261) from a given ray (its direction as given) and seed: out3 = radiance */
+PTOR_CLONES
+void ptor_kat_trace_rays(const void* tris, int ntri, const void* mats, const float* origin3, const float* dir3, const uint32_t* seed,
+                         int max_bounces, float* out3, uint32_t* seed_after, int64_t n)
+{
+    ptor_stats st;
+    memset(&st, 0, sizeof st);
+    for (int64_t i = 0; i < n; ++i) {
+        const float *o = origin3 + 3 * i, *d = dir3 + 3 * i;
+        uint32_t s = seed[i];
+        ptor_ray r;
+        r.origin = v3_make(o[0], o[1], o[2]);
+        r.dir = v3_make(d[0], d[1], d[2]);
+        v3 c = ptor_trace_rays(&r, (const ptor_triangle*)tris, ntri, (const ptor_material*)mats, &s, max_bounces, &st, 0);
+        out3[3 * i] = c.x; out3[3 * i + 1] = c.y; out3[3 * i + 2] = c.z;
+        seed_after[i] = s;
     }
 }
 
