@@ -515,6 +515,46 @@ int pt_render_direct(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materia
                      pt_buffer_t framebuffer, const pt_direct_params* params, const pt_camera* cam /* NULL = the reference's */,
                      pt_event_t ev);
 
+/* ---- first-hit feature buffers -------------------------------------------------------------------------------------
+ * What a denoiser, a compositor or a model takes beside the noisy image: albedo, shading normal, depth / coverage and emission at
+ * the first hit, per SAMPLE, over the same jittered (and, with a lens, defocused) samples the lit renders take.  The library
+ * neither filters nor denoises; pt_sample_moments turns each output into ordered binary64 sums, pt_moments_resolve into means and
+ * variances.  A sample of pixel gid = y * width + x in frame z is steps 1 and 2 of pt_render_direct, expression for expression:
+ *  1. seed = gid + hash(z) (GenerateColors.cl:308), the renderer's primary ray (o, d) (:263-288; with the camera's lens when it has
+ *     one) and its closest hit from 1e20 (:137-154).
+ *  2. On a hit: p = o + d t (:127); n = the HitRecord normal (:128-130) turned to face the ray (:243: n when dot(n, d) < 0,
+ *     otherwise n * -1.0f); m = materials[the triangle's id, clamped into [0, num_materials) as shading clamps it].
+ * Item i = f * npix + lp -- frame frame_begin + f, local pixel lp of the stripe layout of pt_render_params, npix local pixels --
+ * writes three floats to X[i] of every output X that is not NULL:
+ *     albedo     m.albedo[0..2] as stored, whatever m.type          a miss: (0, 0, 0)
+ *     normal     n                                                  a miss: (0, 0, 0)
+ *     depth      (t, 1.0f, -dot(n, d)), the contract's dot          a miss: (0, 0, 0)
+ *     emission   1.0f * m.emissive[0..2] * 3.0f (:241)              a miss: (0, 0, 0)
+ * depth's second channel is the coverage weight: a pixel's mean depth over its hits is sum[0] / sum[1], its coverage sum[1] / n.
+ * Nothing is clamped or filtered: the NaN normal of a degenerate triangle is stored as it is (pt_sample_moments counts the sample
+ * as rejected).  The layout [frame][local pixel][3] is the sample workspace's: each output goes to pt_sample_moments as it is.
+ * One launch per call, no chunking: every output given must hold frame_count x npix x 12 bytes, and frame_count x npix must stay
+ * below 2^31.  frame_begin only numbers the frames: there is no framebuffer and nothing is accumulated here.
+ * Feature renders behave like AO and direct renders: the handle's stream, behind renders in flight, asynchronous (ev); the scene,
+ * LBVH and filter tables as a query uses them (no anchor move, no rebuild); once the scene is prepared no allocation and no wait;
+ * PT_OPT_ACCEL and PT_OPT_QUAD_FILTER choose the search; a cut-short LBVH search raises PT_ERR_TRAVERSAL (deferred).
+ * num_triangles = 0 writes misses.  The version of every buffer written is bumped.
+ * Errors come before anything is enqueued and leave the outputs untouched: PT_ERR_INVALID for a field out of range (num_triangles
+ * < 0, num_materials < 1), a reserved field not 0, a camera pt_camera_derive rejects, triangles or materials NULL, all four outputs
+ * NULL, an output not 4-byte aligned, outputs overlapping each other or the triangle or material buffer, a buffer of another device,
+ * frame_begin + frame_count or width x height above 2^31 - 1; PT_ERR_RANGE for a buffer too small or frame_count x npix above
+ * 2^31 - 1. */
+enum { PT_FEATURE_ALBEDO = 1, PT_FEATURE_NORMAL = 2, PT_FEATURE_DEPTH = 4, PT_FEATURE_EMISSION = 8 };   /* names for a caller's masks */
+typedef struct pt_feature_params {
+    int32_t width, height, frame_begin, frame_count;   /* the image; frame_begin numbers the frames; frame_count 0 enqueues nothing */
+    int32_t num_triangles, num_materials;              /* num_triangles >= 0 (0 = every sample a miss), num_materials >= 1 */
+    int32_t stripe_rows, n_ranks, rank;                /* image sharding exactly as pt_render_params */
+    int32_t reserved[7];                               /* must be 0 */
+} pt_feature_params;                                   /* 64 bytes */
+int pt_render_features(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                       pt_buffer_t albedo, pt_buffer_t normal, pt_buffer_t depth, pt_buffer_t emission /* float[frame_count][npix][3]; each may be NULL */,
+                       const pt_feature_params* params, const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
+
 /* ---- indirect illumination -----------------------------------------------------------------------------------------
  * The IndirectIllumination case the reference's harness declares (test/RaytraceTest.cpp:301-303) with an empty body: the
  * renderer's multi-bounce walk (traceRays, GenerateColors.cl:223-261) with direct illumination's light sample taken at every

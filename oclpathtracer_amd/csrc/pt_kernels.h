@@ -324,6 +324,19 @@ struct PtDirectParams {
 #pragma clang diagnostic ignored "-Winvalid-offsetof"
 static_assert(offsetof(PtDirectParams, cam) == sizeof(PtTraceParams), "PtDirectParams begins { t, cam }");
 #pragma clang diagnostic pop
+// first-hit feature buffers (pt_render_features): direct illumination's sample up to its surface.  Of d the launch reads t (the search,
+// the image geometry, mats and nmat >= 1), cam, npix, nitems and frame0; lights, samples, K and nl are not read.  Item i = f * npix +
+// local pixel writes 12 bytes to X[i] of every output X that is not null: the first hit's albedo, facing normal, (t, 1, -dot(n, d)) and
+// emission; a miss writes zeros
+struct PtFeatureParams {
+    PtDirectParams d;
+    float* albedo;                // [nitems][3] each; null = the launch does not write it
+    float* normal;
+    float* depth;
+    float* emission;
+};
+// bvh_blocks: ptk_query's (the LBVH form is a kernel of the driver at five waves per SIMD, as the closest query and ambient occlusion)
+hipError_t ptk_render_features(const PtFeatureParams& f, int bvh_blocks, PtSearchMode m, hipStream_t s);
 // indirect illumination (pt_render_indirect): direct illumination's launch with the path's depth.  samples[item] = max(L, 0) of the
 // whole path; everything else is as PtDirectParams says (the helpers of both take its PtDirectParams)
 struct PtIndirectParams {

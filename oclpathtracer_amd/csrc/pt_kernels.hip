@@ -3902,6 +3902,109 @@ void pt_direct_bvh_kernel(const PtDirectArgs<POWER, RIS, ENV> D)
 }
 
 // ------------------------------------------------------------------------------------------
+// first-hit feature buffers (pt_render_features)
+// ------------------------------------------------------------------------------------------
+// One work item is one sample, as for direct illumination (pt_item_begin): the renderer's primary ray and its closest hit from tmax
+// 1e20, the surface and the clamped material index (pt_direct_surface) -- direct illumination's steps 1 and 2, and nothing after them.
+// Item i writes 12 bytes to X[i] of every output X the launch has: the material's albedo as stored, the facing normal, (t, 1, -dot(n, d))
+// and the emission emissive * 3 (:241); a miss writes zeros.  Nothing is clamped: a NaN goes out as it is.  Which outputs exist is
+// uniform for the launch: the four pointers are tested on the by-value block, once per record.
+PTK_DEV void pt_feature_put(float* out, unsigned item, const f3& v)
+{
+    pt_f3v w;
+    w.x = v.x; w.y = v.y; w.z = v.z;
+    *reinterpret_cast<pt_f3v*>(out + (size_t)item * 3u) = w;
+}
+
+// the records of sample `item`: hit = its primary ray (direction d) hit at t, n the facing normal, mid the clamped material index --
+// one gather of the material's first 32 bytes, then up to four stores
+PTK_DEV void pt_feature_store(const PtFeatureParams& F, unsigned item, bool hit, const f3& d, float t, const f3& n, unsigned mid)
+{
+    f3 alb = mk3(0.0f, 0.0f, 0.0f), emi = alb, nrm = alb, dep = alb;
+    if (hit) {
+        const float4 a = pt_rec16(F.d.t.mats, mid, 0u), e = pt_rec16(F.d.t.mats, mid, 16u);
+        alb = mk3(a.x, a.y, a.z);
+        emi = mk3(e.x * 3.0f, e.y * 3.0f, e.z * 3.0f);   // 1.0f * emissive * 3.0f (:241)
+        nrm = n;
+        dep = mk3(t, 1.0f, -dot3(n, d));
+    }
+    if (F.albedo) pt_feature_put(F.albedo, item, alb);
+    if (F.normal) pt_feature_put(F.normal, item, nrm);
+    if (F.depth) pt_feature_put(F.depth, item, dep);
+    if (F.emission) pt_feature_put(F.emission, item, emi);
+}
+
+// brute force: one wave = 64 consecutive samples and one search -- pt_direct_kernel up to its surface.  A wave none of whose lanes
+// hit stores its miss records and is done
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_feature_kernel(const PtFeatureParams F)
+{
+    const PtTraceParams& P = F.d.t;
+    const unsigned lane = pt_lane_id();
+    const int ntri = P.ntri;
+    PtTail tl = pt_table_wg_setup<LDS_TABLE>(P, lane);
+    const f3 anchor = mk3(P.cam.eye[0], P.cam.eye[1], P.cam.eye[2]);
+    const unsigned item = pt_wave() * 64u + lane;
+    const bool act = item < F.d.nitems;
+    unsigned lp = 0u;
+    uint32_t seed = 0u;
+    f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f);
+    if (act) pt_item_begin(P, F.d.cam, F.d.npix, F.d.frame0, item, lp, seed, o, d);
+    float tmax = 1e20f, hu = 0.0f, hv = 0.0f;
+    int hidx = -1;
+    pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS>((pt_const_f32p)(const float*)P.tris, P.tris, ntri, o, d, act, tmax, hu, hv, hidx,
+                                                         P.quad_delta1, P.ray_radius, (pt_const_f32p)P.p1tab, P.p1_lo, P.p1_hi, anchor, tl, lane);
+    const bool hit = act & (hidx >= 0);
+    f3 p = o, n = d, wo = d;
+    unsigned mid = 0u;
+    if (__ballot(hit) == 0ull) {
+        if (act) pt_feature_store(F, item, false, d, tmax, n, mid);
+        return;
+    }
+    if (hit) pt_direct_surface(F.d, o, d, tmax, hu, hv, hidx, p, n, wo, mid);
+    if (act) pt_feature_store(F, item, hit, d, tmax, n, mid);
+}
+
+// LBVH (pt_bvh_drive): one item = one sample = one closest search; the lane is free when its records are stored.  A ray starts
+// at the lens, which may lie anywhere: the slabs carry the ray term of the margin, as for queries and ambient occlusion
+struct PtFeatureWork {
+    static constexpr bool ANY = false;
+    const PtFeatureParams& F;
+    unsigned n, item;
+    f3 o, d;
+    PTK_DEV void begin(unsigned item_)
+    {
+        unsigned lp;
+        uint32_t seed;
+        item = item_;
+        pt_item_begin(F.d.t, F.d.cam, F.d.npix, F.d.frame0, item, lp, seed, o, d);
+    }
+    PTK_DEV bool next_ray(const PtBvhLane& L)
+    {
+        f3 p = o, nrm = d, wo = d;
+        unsigned mid = 0u;
+        const bool hit = L.hidx >= 0;
+        if (hit) pt_direct_surface(F.d, o, d, L.tmax, L.hu, L.hv, L.hidx, p, nrm, wo, mid);
+        pt_feature_store(F, item, hit, d, L.tmax, nrm, mid);
+        return false;
+    }
+    PTK_DEV const f3& org() const { return o; }
+    PTK_DEV const f3& dir() const { return d; }
+    PTK_DEV float limit() const { return 1e20f; }
+    PTK_DEV bool live() const { return true; }
+    PTK_DEV bool any() const { return false; }
+};
+
+template <bool DET_BOUNDED, int BIGQ>
+__global__ __launch_bounds__(PT_TRACE_THREADS) PT_BVH_WAVES_ATTR
+void pt_feature_bvh_kernel(const PtFeatureParams F)
+{
+    const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
+    PtFeatureWork W = { F, F.d.nitems, 0u, o0, d0 };
+    pt_bvh_drive<DET_BOUNDED, BIGQ>(F.d.t, W);
+}
+
+// ------------------------------------------------------------------------------------------
 // indirect illumination (pt_render_indirect)
 // ------------------------------------------------------------------------------------------
 // The renderer's multi-bounce walk (traceRays, :223-261) with direct illumination's light sample taken at every vertex
@@ -5093,6 +5196,11 @@ struct PtAoFamily {
     template <bool DB, int BIGQ> static constexpr auto bvh() { return pt_ao_bvh_kernel<DB, BIGQ>; }
     template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table() { return pt_ao_kernel<DB, LDS_TABLE, QUADS>; }
 };
+struct PtFeatureFamily {
+    using Params = PtFeatureParams;
+    template <bool DB, int BIGQ> static constexpr auto bvh() { return pt_feature_bvh_kernel<DB, BIGQ>; }
+    template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table() { return pt_feature_kernel<DB, LDS_TABLE, QUADS>; }
+};
 // a kind of lit render (PtLitKind); RR: the table kernels are the refilling ones, a wave of which owns PT_RR_RUN items
 template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST, bool RIS = false, bool ENV = false> struct PtLitFamily {
     using Params = std::conditional_t<INDIRECT, PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV>, PtDirectArgs<POWER, RIS, ENV>>;
@@ -5178,6 +5286,12 @@ hipError_t ptk_ao(const PtAoParams& a, int bvh_blocks, PtSearchMode m, hipStream
 {
     if (a.nitems == 0) return hipSuccess;
     return pt_launch_search(pt_choose<PtAoFamily>(m, a.t.ntri), a, a.t.ntri, a.nitems, 64u, m.bvh, bvh_blocks, s);
+}
+
+hipError_t ptk_render_features(const PtFeatureParams& f, int bvh_blocks, PtSearchMode m, hipStream_t s)
+{
+    if (f.d.nitems == 0) return hipSuccess;
+    return pt_launch_search(pt_choose<PtFeatureFamily>(m, f.d.t.ntri), f, f.d.t.ntri, f.d.nitems, 64u, m.bvh, bvh_blocks, s);
 }
 
 hipError_t ptk_lit(const PtLitParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s)

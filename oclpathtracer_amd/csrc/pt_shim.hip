@@ -2060,6 +2060,73 @@ extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_
     return render_lit(d, c);
 }
 
+// ---- first-hit feature buffers (include/pt_shim.h) -----------------------------------------------------------------------------
+static_assert(sizeof(pt_feature_params) == 64, "pt_feature_params layout");
+
+extern "C" int pt_render_features(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t albedo, pt_buffer_t normal,
+                                  pt_buffer_t depth, pt_buffer_t emission, const pt_feature_params* params, const pt_camera* cam, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
+    const pt_feature_params a = *params;
+    PtLensCamera c = reference_camera();
+    if (cam && (rc = camera_derive(cam, &c))) return rc;
+    if (!triangles || !materials) return fail(PT_ERR_INVALID, "null buffer handle");
+    if (!albedo && !normal && !depth && !emission) return fail(PT_ERR_INVALID, "at least one of the four outputs must be given");
+    if ((rc = check_same_device(d, { triangles, materials, albedo, normal, depth, emission })) || (rc = check_event(d, ev))) return rc;
+    if (a.num_triangles < 0 || a.num_materials < 1) return fail(PT_ERR_INVALID, "invalid feature parameters");
+    for (int i = 0; i < 7; ++i)
+        if (a.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    // the hit's {n, id} and its material are gathered by 32-bit byte offsets into the 64-byte records, as shading gathers them
+    if ((uint64_t)a.num_triangles * 64u > 0xffffffffull || (uint64_t)a.num_materials * 64u > 0xffffffffull)
+        return fail(PT_ERR_INVALID, "a scene has fewer than 2^26 triangles and 2^26 materials");
+    uint64_t npix64;
+    if ((rc = check_image("invalid feature parameters", a.width, a.height, a.frame_begin, a.frame_count, a.stripe_rows, a.n_ranks, a.rank, npix64)))
+        return rc;
+    const uint32_t npix = (uint32_t)npix64;
+    // one launch, frame-major samples: fewer than 2^31 of them
+    const uint64_t items = (uint64_t)a.frame_count * npix;
+    if (items > 0x7fffffffull) return fail(PT_ERR_RANGE, "frame_count x local pixels = %llu samples: at most 2^31 - 1 per call", (unsigned long long)items);
+    const size_t out_bytes = (size_t)items * 12;
+    const PtSpan R = { triangles, (size_t)a.num_triangles * sizeof(PtRawTriangle), 1, "the triangle buffer" },
+                 M = { materials, (size_t)a.num_materials * sizeof(PtRawMaterial), 1, "the material buffer" },
+                 A = { albedo, out_bytes, 4, "the albedo buffer" }, N = { normal, out_bytes, 4, "the normal buffer" },
+                 D = { depth, out_bytes, 4, "the depth buffer" }, E = { emission, out_bytes, 4, "the emission buffer" };
+    if ((rc = check_triangles(triangles, a.num_triangles)) || (rc = span_fits(M))) return rc;
+    if ((rc = span_fits(A)) || (rc = span_fits(N)) || (rc = span_fits(D)) || (rc = span_fits(E))) return rc;
+    if ((rc = span_aligned(A)) || (rc = span_aligned(N)) || (rc = span_aligned(D)) || (rc = span_aligned(E))) return rc;
+    if ((rc = spans_apart({ A, N, D, E }, { R, M }))) return rc;   // (the scene is only read)
+    // a search that was cut short earlier is reported before anything new is enqueued (PT_ERR_TRAVERSAL is deferred)
+    if ((rc = check_traversal(d))) return rc;
+    if ((rc = enter_stream(d))) return rc;
+    if (items == 0) {
+        if ((rc = event_begin(d, ev))) return rc;
+        return event_end(d, ev);
+    }
+    PtSearch search;
+    if ((rc = prepare_search(d, triangles, a.num_triangles, nullptr, search))) return rc;
+    if ((rc = event_begin(d, ev))) return rc;
+    PtFeatureParams p;
+    memset(&p, 0, sizeof p);
+    search_fields(d, search, p.d.t);   // (an empty scene: the brute-force form over zero triangles, every sample a miss)
+    image_geometry(p.d.t, a.width, a.height, a.stripe_rows, a.n_ranks, a.rank, npix);
+    p.d.t.mats = (const PtRawMaterial*)materials->dptr;
+    p.d.t.nmat = a.num_materials;
+    p.d.cam = c;
+    p.d.npix = npix;
+    p.d.nitems = (uint32_t)items;
+    p.d.frame0 = a.frame_begin;
+    p.albedo = albedo ? (float*)albedo->dptr : nullptr;
+    p.normal = normal ? (float*)normal->dptr : nullptr;
+    p.depth = depth ? (float*)depth->dptr : nullptr;
+    p.emission = emission ? (float*)emission->dptr : nullptr;
+    HIP_TRY(ptk_render_features(p, search.driver_blocks, search.mode, d->stream));
+    for (pt_buffer_t b : { albedo, normal, depth, emission })
+        if (b) b->version++;
+    return event_end(d, ev);
+}
+
 // ---- indirect illumination (include/pt_shim.h) ---------------------------------------------------------------------------------
 extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
                                   pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)

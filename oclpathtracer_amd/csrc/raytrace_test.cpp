@@ -10,8 +10,9 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]]] [--noise] [--lens R[,F]]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only Features | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]]] [--noise] [--lens R[,F]]
 // Exit code 0 = every check passed.  Own code; no gtest.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -398,6 +399,97 @@ static void test_AmbientOcclusion(DeviceTest& f, const Options& o)
     }
 }
 
+// Features (not a case of the reference's): the first-hit feature buffers of the scene through pt_render_features -- dim x dim, --frames
+// frames, all four outputs, in calls of as many frames as a 64 MiB workspace per output holds, the depth samples' moments taken after
+// each call (pt_sample_moments) -- prints the image's coverage and mean depth, and cross-checks frame 0 on the device against the
+// library's other route to the same data, pt_camera_rays + pt_intersect_rays: t, |normal|, and the hit material's albedo and emission
+// bit for bit, a miss all zeros.  A mismatch fails the case.  Run only when asked for (--only).
+static uint32_t bits_of(float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; }
+
+static void test_Features(DeviceTest& f, const Options& o)
+{
+    Device* m_d = f.m_d;
+    std::vector<Triangle> triangles;
+    std::vector<Material> materials;
+    if (!loadModel(o.scene.c_str(), triangles, materials)) {
+        std::printf("Error loading model !!\n");
+        ++g_failures;
+        return;
+    }
+    const int dimension = o.dim;
+    const size_t npix = (size_t)dimension * dimension;
+    const int perCall = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(o.frames, 1), ((size_t)64 << 20) / (npix * 12)));
+    Buffer<Triangle> tBuffer(m_d, triangles.size());
+    Buffer<Material> mBuffer(m_d, materials.size());
+    Buffer<float> albedo(m_d, 3 * npix * perCall), normal(m_d, 3 * npix * perCall), depth(m_d, 3 * npix * perCall), emission(m_d, 3 * npix * perCall);
+    Buffer<pt_pixel_moments> moments(m_d, npix);
+    tBuffer.write(triangles.data(), triangles.size());
+    mBuffer.write(materials.data(), materials.size());
+    pt_feature_params p;
+    std::memset(&p, 0, sizeof p);
+    p.width = dimension; p.height = dimension;
+    p.num_triangles = (int)triangles.size();
+    p.num_materials = (int)materials.size();
+    p.stripe_rows = 1; p.n_ranks = 1; p.rank = 0;
+    pt_camera lens;
+    const pt_camera* cam = lens_camera(m_d, o, tBuffer.m_handle, p.num_triangles, &lens);
+
+    // frame 0 by both routes, before the render overwrites the workspaces
+    Buffer<pt_ray> rays(m_d, npix);
+    Buffer<pt_hit> hits(m_d, npix);
+    p.frame_begin = 0; p.frame_count = 1;
+    IASSERT(pt_render_features(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, albedo.m_handle, normal.m_handle, depth.m_handle,
+                               emission.m_handle, &p, cam, 0) == PT_OK);
+    IASSERT(pt_camera_rays(m_d->m_handle, cam, dimension, dimension, 0, rays.m_handle, 0) == PT_OK);
+    IASSERT(pt_intersect_rays(m_d->m_handle, tBuffer.m_handle, p.num_triangles, rays.m_handle, hits.m_handle, npix, PT_QUERY_CLOSEST, 0) == PT_OK);
+    std::vector<float> ha(3 * npix), hn(3 * npix), hd(3 * npix), he(3 * npix);
+    std::vector<pt_hit> hh(npix);
+    albedo.read(ha.data(), 3 * npix); normal.read(hn.data(), 3 * npix); depth.read(hd.data(), 3 * npix); emission.read(he.data(), 3 * npix);
+    hits.read(hh.data(), npix);
+    DeviceUtils::waitForCompletion(m_d);
+    size_t mismatches = 0, hitCount = 0;
+    const int nmat = (int)materials.size();
+    for (size_t i = 0; i < npix; i++) {
+        const pt_hit& h = hh[i];
+        bool same = true;
+        if (h.tri < 0) {
+            for (int k = 0; k < 3; k++) same = same && !bits_of(ha[3 * i + k]) && !bits_of(hn[3 * i + k]) && !bits_of(hd[3 * i + k]) && !bits_of(he[3 * i + k]);
+        } else {
+            ++hitCount;
+            const Material& m = materials[(size_t)std::min(std::max(h.material, 0), nmat - 1)];
+            const float alb[3] = { m.albedo.x, m.albedo.y, m.albedo.z }, emi[3] = { m.emissive.x * 3.0f, m.emissive.y * 3.0f, m.emissive.z * 3.0f };
+            same = bits_of(hd[3 * i]) == bits_of(h.t) && hd[3 * i + 1] == 1.0f;
+            for (int k = 0; k < 3; k++)
+                same = same && ((bits_of(hn[3 * i + k]) ^ bits_of(h.n[k])) & 0x7fffffffu) == 0 && bits_of(ha[3 * i + k]) == bits_of(alb[k]) &&
+                       bits_of(he[3 * i + k]) == bits_of(emi[k]);
+        }
+        if (!same && mismatches++ < 4) std::fprintf(stderr, "Features: pixel %zu of frame 0 differs from pt_camera_rays + pt_intersect_rays\n", i);
+    }
+    IASSERT(mismatches == 0);
+    std::printf("Features: frame 0 equals pt_camera_rays + pt_intersect_rays on %zu pixels (%zu hits)\n", npix, hitCount);
+
+    auto t0 = std::chrono::steady_clock::now();
+    for (int first = 0; first < o.frames; first += perCall) {
+        p.frame_begin = first;
+        p.frame_count = std::min(perCall, o.frames - first);
+        IASSERT(pt_render_features(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, albedo.m_handle, normal.m_handle, depth.m_handle,
+                                   emission.m_handle, &p, cam, 0) == PT_OK);
+        IASSERT(pt_sample_moments(m_d->m_handle, depth.m_handle, moments.m_handle, (uint32_t)npix, p.frame_count, first == 0, 0) == PT_OK);
+    }
+    std::vector<pt_pixel_moments> hm(npix);
+    std::memset(hm.data(), 0, npix * sizeof(pt_pixel_moments));
+    if (o.frames > 0) moments.read(hm.data(), npix);
+    DeviceUtils::waitForCompletion(m_d);
+    double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    double tsum = 0.0, hsum = 0.0, nsum = 0.0, rejected = 0.0;
+    for (size_t i = 0; i < npix; i++) { tsum += hm[i].sum[0]; hsum += hm[i].sum[1]; nsum += hm[i].n; rejected += hm[i].rejected; }
+    std::printf("Features: %d x %d x %d frames, four outputs, in %.3f s = %.1f Msamples/s (calls + moments + readback)\n", dimension, dimension,
+                o.frames, secs, (double)npix * o.frames / secs / 1e6);
+    std::printf("Features: coverage %.6f, mean depth %.6f over %.0f hits of %.0f samples, %.0f rejected\n", nsum > 0 ? hsum / nsum : 0.0,
+                hsum > 0 ? tsum / hsum : 0.0, hsum, nsum, rejected);
+    IASSERT(nsum + rejected == (double)npix * o.frames);
+}
+
 // TEST_F(DeviceTest, DirectIllumination): the reference declares the case with an empty body (RaytraceTest.cpp:297-299).  Here it
 // renders the scene lit directly by its emitters through pt_render_direct -- dim x dim, --frames frames, K = 4 light samples; the
 // light list is built here: the triangles whose material has an emissive component above 0, ascending -- and writes
@@ -714,17 +806,17 @@ int main(int argc, char** argv)
     if (o.dim < 1 || o.frames < 0) { std::fprintf(stderr, "bad --dim/--frames\n"); return 2; }
     if (o.candidates > 0 && !o.power) { std::fprintf(stderr, "--candidates needs --lights power (the candidates are drawn from the light table)\n"); return 2; }
     if (o.env && (!o.power || o.candidates > 0 || o.adaptTol >= 0.0)) { std::fprintf(stderr, "--env needs --lights power and goes with neither --candidates nor --adaptive\n"); return 2; }
-    if (o.lensR > 0.0f && o.only != "AmbientOcclusion" && o.only != "DirectIllumination" && o.only != "IndirectIllumination") {
-        std::fprintf(stderr, "--lens goes with --only AmbientOcclusion, DirectIllumination or IndirectIllumination (RayCast's kernels take no lens)\n");
+    if (o.lensR > 0.0f && o.only != "AmbientOcclusion" && o.only != "DirectIllumination" && o.only != "IndirectIllumination" && o.only != "Features") {
+        std::fprintf(stderr, "--lens goes with --only AmbientOcclusion, Features, DirectIllumination or IndirectIllumination (RayCast's kernels take no lens)\n");
         return 2;
     }
     if (o.env && o.only == "IndirectIllumination" && !o.mis) { std::fprintf(stderr, "--env with IndirectIllumination needs --mis\n"); return 2; }
     struct { const char* name; int kind; } tests[] = { { "initialize", 0 }, { "deviceInfo", 1 }, { "MemoryAllocation", 2 }, { "writeRead", 3 },
                                                        { "getHostPtr", 4 }, { "kernelExecution", 5 }, { "RayCast", 6 },
-                                                       { "AmbientOcclusion", 7 }, { "DirectIllumination", 8 }, { "IndirectIllumination", 9 } };
+                                                       { "AmbientOcclusion", 7 }, { "DirectIllumination", 8 }, { "IndirectIllumination", 9 }, { "Features", 10 } };
     for (auto& t : tests) {
         if (!o.only.empty() && o.only != t.name) continue;
-        if (o.only.empty() && t.kind >= 7) continue;   // AmbientOcclusion, DirectIllumination and IndirectIllumination run only when asked for: the default run is RaytraceTest's seven cases
+        if (o.only.empty() && t.kind >= 7) continue;   // AmbientOcclusion, DirectIllumination, IndirectIllumination and Features run only when asked for: the default run is RaytraceTest's seven cases
         std::printf("[ RUN      ] DeviceTest.%s\n", t.name);
         int before = g_failures;
         DeviceTest f;
@@ -739,6 +831,7 @@ int main(int argc, char** argv)
         case 7: test_AmbientOcclusion(f, o); break;
         case 8: test_Illumination(f, o, 0); break;
         case 9: test_Illumination(f, o, 16); break;
+        case 10: test_Features(f, o); break;
         default: break;
         }
         f.TearDown();

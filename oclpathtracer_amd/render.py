@@ -198,6 +198,20 @@ class Renderer:
 
         return self._lit_renderer(IndirectRenderer, kw)
 
+    def feature_renderer(self, **kw):
+        """A :class:`features.FeatureRenderer` of this renderer's image over its triangle and material buffers (keyword arguments:
+        FeatureRenderer's, ``features`` and ``workspace_frames`` among them; the image size, camera and sharding default to this
+        renderer's): first-hit albedo, normal, depth and emission with their variances, over the samples the lit renders take, through
+        the device's prepared scene and LBVH.  Release it before the renderer."""
+        from .features import FeatureRenderer
+
+        kw.setdefault("camera", self.camera)
+        kw.setdefault("stripe_rows", self.stripe_rows)
+        kw.setdefault("n_ranks", self.n_ranks)
+        kw.setdefault("rank", self.rank)
+        return FeatureRenderer(self.dev, self.tbuf, self.mbuf, kw.pop("width", self.width), kw.pop("height", self.height),
+                               num_triangles=self.num_triangles, num_materials=self.num_materials, **kw)
+
     def _lit_renderer(self, cls, kw):
         kw.setdefault("camera", self.camera)
         kw.setdefault("stripe_rows", self.stripe_rows)

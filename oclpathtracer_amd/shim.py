@@ -125,6 +125,22 @@ class DirectParams(_c.Structure):
     ]
 
 
+PT_FEATURE_ALBEDO, PT_FEATURE_NORMAL, PT_FEATURE_DEPTH, PT_FEATURE_EMISSION = 1, 2, 4, 8
+
+
+class FeatureParams(_c.Structure):
+    """pt_feature_params (64 bytes): image, frames (frame_begin only numbers them), triangles, materials, image sharding as
+    RenderParams; reserved must be 0."""
+
+    _fields_ = [
+        ("width", _c.c_int32), ("height", _c.c_int32),
+        ("frame_begin", _c.c_int32), ("frame_count", _c.c_int32),
+        ("num_triangles", _c.c_int32), ("num_materials", _c.c_int32),
+        ("stripe_rows", _c.c_int32), ("n_ranks", _c.c_int32), ("rank", _c.c_int32),
+        ("reserved", _c.c_int32 * 7),
+    ]
+
+
 class IndirectParams(_c.Structure):
     """pt_indirect_params (64 bytes): DirectParams' fields (K light samples per vertex) and the path's depth max_bounces; reserved
     must be 0."""
@@ -260,6 +276,7 @@ SIGNATURES = {
     "pt_occluded_rays": (_c.c_int, [_H, _H, _c.c_int, _H, _H, _c.c_size_t, _H]),
     "pt_render_ao": (_c.c_int, [_H, _H, _H, _H, _c.POINTER(AoParams), _c.POINTER(Camera), _H]),
     "pt_render_direct": (_c.c_int, [_H, _H, _H, _H, _H, _H, _c.POINTER(DirectParams), _c.POINTER(Camera), _H]),
+    "pt_render_features": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _c.POINTER(FeatureParams), _c.POINTER(Camera), _H]),
     "pt_render_indirect": (_c.c_int, [_H, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Camera), _H]),
     "pt_light_counts": (_c.c_int, [_H, _H, _c.c_int, _c.c_int, _H, _H]),
     "pt_render_indirect_mis": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Camera), _H]),
