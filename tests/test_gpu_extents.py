@@ -2,6 +2,8 @@
 frame numbers up to 2^31 - 2 -- against the CPU oracle, bit for bit (assert_fb_equal: equal bits, equal NaN positions; no tolerance
 anywhere).  The inputs and what the oracle says of them are tests/extent_cases.py's; tests/test_extents_cpu.py proves that each reaches
 its corner.  A rank of a striped render owns a few rows however large the image, so every case but WIDE has a few hundred pixels.
+The lit estimators include the RIS, environment and thin-lens forms; the pixel lists, the features, the lens AO render and the lens
+rays are in tests/test_gpu_extents_lists.py.
 
 WIDE, (2^24 + 256) x 127, is one row of 16 777 472 pixels, 134 M samples all but a few thousand of which miss the scene; its renders
 go through a device handle of their own, so that the 0.5 GB staging ring it needs does not change the chunking of the tests after it.
@@ -21,10 +23,13 @@ import extent_cases as xc
 import extent_oracle as eo
 import primary_accept
 from conftest import assert_fb_equal
+from env_scenes import env_map
 from gpu_support import lit_with_samples, options, render
 from oclpathtracer_amd import adl, shim
 from oclpathtracer_amd.ao import AORenderer
 from oclpathtracer_amd.direct import DirectRenderer
+from oclpathtracer_amd.environment import Environment
+from oclpathtracer_amd.features import FeatureRenderer
 from oclpathtracer_amd.indirect import IndirectRenderer, Roulette
 from oclpathtracer_amd.render import Renderer
 from roulette_support import roulette_with_samples
@@ -195,21 +200,38 @@ def test_masks_are_declined_only_beyond_the_footprint_bound(device, W, H, stripe
 
 
 # ---- the lit renderers -------------------------------------------------------------------------------------------------------------
-def _lit(device, est, W, H, frames, **kw):
-    B, mis, power, rr = xc.LIT[est]
-    sc = xc.cornell()
-    if rr is not None:
-        return roulette_with_samples(device, sc, W, H, frames, xc.LIT_K, B, rr[0], rr[1], mis=mis, power=power, **kw)
-    return lit_with_samples(device, sc, W, H, frames, xc.LIT_K, max_bounces=B, mis=mis, **kw)
+def _lit(device, est, tall, W, H, frames, **kw):
+    """one render of an estimator of xc.LIT on its scene (xc.scene_of) through the entry point the Python renderers choose for it --
+    pt_render_direct_ris / pt_render_indirect_ris with candidates, pt_render_direct_env / pt_render_indirect_env with the map, the camera
+    with its lens: (framebuffer, the sample workspace)"""
+    e = xc.LIT[est]
+    sc = xc.scene_of(est, tall)
+    if not (e.M or e.Ke or e.lens):   # what existed before, as before
+        if e.rr is not None:
+            return roulette_with_samples(device, sc, W, H, frames, xc.LIT_K, e.B, e.rr[0], e.rr[1], mis=e.mis, power=e.power, **kw)
+        return lit_with_samples(device, sc, W, H, frames, xc.LIT_K, max_bounces=e.B, mis=e.mis, **kw)
+    if e.M:
+        kw["candidates"] = e.M
+    if e.Ke:
+        kw.update(environment=Environment(env_map(xc.ENV_MAP)), env_samples=e.Ke)
+    if e.rr is not None:
+        kw["roulette"] = Roulette(*e.rr)
+    try:
+        return lit_with_samples(device, sc, W, H, frames, xc.LIT_K, max_bounces=e.B, mis=e.mis, light_choice="power" if e.power else "uniform", **kw)
+    finally:
+        if e.Ke:
+            kw["environment"].release()
 
 
 @pytest.mark.parametrize("name", list(xc.TALL))
 @pytest.mark.parametrize("est", list(xc.LIT))
 def test_lit_tall(device, est, name):
+    """TALL: gids up to W * H - 1 under every estimator -- RIS (4M - 1 uniforms per light sample), the environment, the lens (two more
+    draws, a shifted origin)"""
     want_fb, want_ws = xc.lit_tall(est, name)
     for accel in (1, 2):
         with options(device, ACCEL=accel):
-            fb, ws = _lit(device, est, xc.TALL_W, xc.TALL_H, xc.LIT_FRAMES, **xc.TALL[name])
+            fb, ws = _lit(device, est, True, xc.TALL_W, xc.TALL_H, xc.LIT_FRAMES, **xc.TALL[name])
         assert_fb_equal(ws, want_ws, "%s %s accel %d: radiance before the fold" % (est, name, accel))
         assert_fb_equal(fb, want_fb, "%s %s accel %d" % (est, name, accel))
 
@@ -217,9 +239,10 @@ def test_lit_tall(device, est, name):
 @pytest.mark.parametrize("name", list(xc.LATE))
 @pytest.mark.parametrize("est", list(xc.LIT))
 def test_lit_late(device, est, name):
+    """LATE: frame numbers about 2048, 2^24 and up to 2^31 - 2 under every estimator"""
     frame_begin, frames = xc.LATE[name]
     want_fb, want_ws = xc.lit_late(est, name)
-    fb, ws = _lit(device, est, xc.LATE_W, xc.LATE_H, frames, frame_begin=frame_begin, fb_init=xc.late_start())
+    fb, ws = _lit(device, est, False, xc.LATE_W, xc.LATE_H, frames, frame_begin=frame_begin, fb_init=xc.late_start())
     assert_fb_equal(ws, want_ws, "%s %s: radiance before the fold" % (est, name))
     assert_fb_equal(fb, want_fb, "%s %s" % (est, name))
 
@@ -298,11 +321,15 @@ def _raw(device, buf, elements, dtype):
 
 
 def test_a_rank_without_rows_renders_nothing(device):
-    """H = 5 in stripes of 4 over 3 ranks: rank 2 owns no row.  Every entry point returns PT_OK (the wrappers raise otherwise) and leaves
-    its one-element buffers as they were"""
+    """EMPTY: H = 5 in stripes of 4 over 3 ranks: rank 2 owns no row.  Every entry point returns PT_OK (the wrappers raise otherwise),
+    leaves its one-element buffers as they were and enqueues nothing that the following wait reports: the fused and the lit renderers,
+    their RIS and environment forms, the features, ambient occlusion, the list renders of no slot, the moments of no pixel;
+    pt_adaptive_select of no pixel writes a header of zeros"""
     tris, mats, lights, cam = xc.cornell()
     W, H, st = xc.EMPTY_W, xc.EMPTY_H, xc.EMPTY_STRIPES
     four = np.full((1, 4), SENTINEL, np.float32)
+    lib = shim.load()
+    sky = Environment(env_map(xc.ENV_MAP))
     r = Renderer(device, tris, mats, W, H, want_stats=True, **st)
     try:
         assert r.local_pixels == 0
@@ -317,19 +344,77 @@ def test_a_rank_without_rows_renders_nothing(device):
     lit = [DirectRenderer(device, tris, mats, W, H, light_samples=1, chunk_frames=2, **st),
            IndirectRenderer(device, tris, mats, W, H, light_samples=1, max_bounces=4, chunk_frames=2, **st),
            IndirectRenderer(device, tris, mats, W, H, light_samples=1, max_bounces=4, mis=True, light_choice="power", roulette=Roulette(1, 0.5),
-                            chunk_frames=2, **st)]
+                            chunk_frames=2, **st),
+           DirectRenderer(device, tris, mats, W, H, light_samples=1, chunk_frames=2, light_choice="power", candidates=xc.LIT_M, **st),
+           IndirectRenderer(device, tris, mats, W, H, light_samples=1, max_bounces=4, mis=True, light_choice="power", roulette=Roulette(1, 0.5),
+                            candidates=xc.LIT_M, chunk_frames=2, **st),
+           DirectRenderer(device, tris, mats, W, H, light_samples=1, chunk_frames=2, light_choice="power", environment=sky,
+                          env_samples=xc.LIT_KE, **st),
+           IndirectRenderer(device, tris, mats, W, H, light_samples=1, max_bounces=4, mis=True, light_choice="power", roulette=Roulette(1, 0.5),
+                            environment=sky, env_samples=xc.LIT_KE, chunk_frames=2, **st)]
+    record = np.full(56, 0xA5, np.uint8)
+    mb, pl = adl.Buffer(device, 56, np.uint8), adl.Buffer(device, lib.pt_adaptive_list_bytes(0), np.uint8)
+    header = np.full(pl.getSize(), 0xA5, np.uint8)
+    mb.write(record, 56)
+    pl.write(header, len(header))
     for d in lit:
         try:
+            what = "%s, %d candidates, %d environment samples" % (type(d).__name__, d.candidates, d.env_samples)
             assert d.local_pixels == 0
             d.fb.write(four, 1)
             ws = np.full(d.samples.getSize(), SENTINEL, np.float32)
             d.samples.write(ws, len(ws))
             d.render(3)
-            assert np.array_equal(_raw(device, d.fb, 1, np.float32), four.reshape(-1)), type(d).__name__
-            assert np.array_equal(_raw(device, d.samples, len(ws), np.float32), ws), type(d).__name__
+            d.render(2, 2 ** 31 - 3)
+            if isinstance(d, IndirectRenderer) and d.roulette is not None and d.environment is None:
+                # the list renders of no slot, through the plain and the RIS form, and the moments of no listed pixel
+                head = (device._h, d.tbuf._h, d.mbuf._h, d._lights_h(), *d._estimator(), d.samples._h, d.fb._h, pl._h, 0,
+                        ctypes.byref(d.params(3, 0)), ctypes.byref(d._rr))
+                assert lib.pt_render_indirect_pixels(*head, None, None) == shim.PT_OK, what
+                assert lib.pt_render_indirect_pixels_ris(*head, ctypes.byref(shim.Ris(xc.LIT_M)), None, None) == shim.PT_OK, what
+                assert lib.pt_sample_moments_pixels(device._h, d.samples._h, mb._h, pl._h, 0, 3, None) == shim.PT_OK, what
+                assert lib.pt_sample_moments(device._h, d.samples._h, mb._h, 0, 3, 1, None) == shim.PT_OK, what
+            assert np.array_equal(_raw(device, d.fb, 1, np.float32), four.reshape(-1)), what
+            assert np.array_equal(_raw(device, d.samples, len(ws), np.float32), ws), what
+            assert np.array_equal(_raw(device, mb, 56, np.uint8), record) and np.array_equal(_raw(device, pl, len(header), np.uint8), header), what
             device.waitForCompletion()
         finally:
             d.release()
+    sky.release()
+    # selection and resolve of no pixel
+    nb, sb = adl.Buffer(device, 16, np.uint8), adl.Buffer(device, max(48, lib.pt_moments_summary_bytes(0)), np.uint8)
+    try:
+        noise = np.full(16, 0xA5, np.uint8)
+        summary = np.full(sb.getSize(), 0xA5, np.uint8)
+        nb.write(noise, 16)
+        sb.write(summary, len(summary))
+        assert lib.pt_moments_resolve(device._h, mb._h, 0, nb._h, sb._h, None) == shim.PT_OK
+        assert np.array_equal(_raw(device, nb, 16, np.uint8), noise) and np.array_equal(_raw(device, sb, len(summary), np.uint8), summary)
+        rule = shim.AdaptiveRule(0.0, 0.0, 1, 1)
+        assert lib.pt_adaptive_select(device._h, mb._h, 0, ctypes.byref(rule), pl._h, None) == shim.PT_OK
+        assert not _raw(device, pl, 16, np.uint8).any(), "the header of an empty selection is not zeros"
+        assert np.array_equal(_raw(device, mb, 56, np.uint8), record)
+        device.waitForCompletion()
+    finally:
+        for b in (mb, pl, nb, sb):
+            b.release()
+    # the features
+    f = FeatureRenderer(device, tris, mats, W, H, features=("albedo", "normal", "depth", "emission"), workspace_frames=3, **st)
+    try:
+        assert f.local_pixels == 0
+        ws = np.full(9, SENTINEL, np.float32)
+        for name in f.features:
+            f.samples[name].write(ws, 9)
+            f.mom[name].write(record, 56)
+        f.render(3)
+        p = f.params(2, 2 ** 31 - 3)
+        assert lib.pt_render_features(device._h, f.tbuf._h, f.mbuf._h, *[f.samples[n]._h for n in f.features], ctypes.byref(p), None, None) == shim.PT_OK
+        for name in f.features:
+            assert np.array_equal(_raw(device, f.samples[name], 9, np.float32), ws), name
+            assert np.array_equal(_raw(device, f.mom[name], 56, np.uint8), record), name
+        device.waitForCompletion()
+    finally:
+        f.release()
     a = AORenderer(device, tris, W, H, rays_per_sample=2, radius=AO_RADIUS, **st)
     try:
         assert a.local_pixels == 0
