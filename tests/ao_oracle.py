@@ -35,3 +35,21 @@ def decisions(tris, W, H, gid, frame, K, radius):
     open_k = np.zeros((len(gid), K), np.uint8)
     lib().oao_decisions(ptr(tris), len(tris), W, H, ptr(gid), ptr(frame), len(gid), K, float(radius), ptr(hit), ptr(open_k))
     return hit, open_k
+
+
+# the unbounded scenes that shade (scenes.slab; tests/lit_cells.py has their forms): (search, scene, PT_OPT_ACCEL), and the render of
+# tests/test_gpu_ao.py on them -- a radius no hit lies beyond, so that rays from the boxes reach the slab far out
+SLAB_FORMS = (("lds", "slab:1", 1), ("tiled", "slab:10", 1), ("lbvh", "slab:15", 0))
+SLAB_W, SLAB_H, SLAB_FRAMES, SLAB_K, SLAB_RADIUS = 24, 16, 2, 4, 1e20
+
+
+def _slab_counts(scene):
+    from scenes import edge_scene
+
+    tris, _, _, cam = edge_scene(scene)[1]
+    return (counts(tris, SLAB_W, SLAB_H, 0, SLAB_FRAMES, SLAB_K, SLAB_RADIUS, cam=cam),)
+
+
+def slab_counts(scene):
+    """the counts of the slab render of ``scene``: computed once, shared, read-only"""
+    return direct_oracle.once(_slab_counts, scene)[0]

@@ -13,6 +13,8 @@ from oclpathtracer_amd import scene as _scene
 from oclpathtracer_amd.camera import Camera
 
 W, H = 40, 24   # 960 pixels: 15 full waves
+SLAB_W, SLAB_H = 24, 16
+SLAB_FORMS = (("lds", "slab:1", 1), ("tiled", "slab:10", 1), ("lbvh", "slab:15", 0))   # (search, case, PT_OPT_ACCEL): lit_cells' slab forms
 
 
 
@@ -69,7 +71,8 @@ _CASES = {}
 
 
 def case(name):
-    """(tris, mats, camera) of cornell, odd_materials, other_type, from_behind, non_finite, soup, with_big, lens, empty"""
+    """(tris, mats, camera) of cornell, odd_materials, other_type, from_behind, non_finite, soup, with_big, lens, empty, slab:COPIES (an
+    unbounded scene that shades: scenes.slab)"""
     if name not in _CASES:
         box, mats = _scene.load_model()
         if name == "cornell":
@@ -92,6 +95,9 @@ def case(name):
             c = (box, mats, Camera(eye=ref.eye, center=ref.center, up=ref.up, fov_y_deg=ref.fov_y_deg, lens_radius=LENS_R, focus_distance=LENS_F))
         elif name == "empty":
             c = (box[:0].copy(), mats, None)
+        elif name.startswith("slab:"):
+            t, m, _, cam = scenes.edge_scene(name)[1]
+            c = (t, m, cam)
         else:
             raise ValueError(name)
         _CASES[name] = c

@@ -1,16 +1,21 @@
-"""Every lit kernel once: the table of tests/test_gpu_lit_cells.py -- the 14 kinds of lit render under the 8 forms of the search, 112
+"""Every lit kernel once: the table of tests/test_gpu_lit_cells.py -- the 21 kinds of lit render under the 11 forms of the search, 231
 cells, one kernel instantiation each -- and what the restatements say of every cell.  tests/test_lit_cells_cpu.py proves from this
 table alone that each form's scene reaches its form.  TEST INFRASTRUCTURE.
 
 A kind is what an entry point renders: direct illumination with the uniform or the power choice; indirect illumination, the roulette
-(pt_render_indirect_rr) and the pixel list (pt_render_indirect_pixels), each for the four estimators (mis, power).  A form is what the
-search of a scene is: the LBVH, the table in LDS (at most 256 triangles) or the tiled table; over packed quads, independent triangles
-with the short reciprocal (every |e1|_1 |e2|_1 <= PT_DET_BOUND_MAX = 2e19), or unbounded ones.  The scenes are scenes.direct_scaled's:
-1, 10 and 15 nested Cornell boxes (36, 360 and 540 triangles) times 2^0, and times 2^30 for the unbounded forms: the largest
-|e1|_1 |e2|_1 of the box is 62.58, times 2^60 it is 7.2e19 (2^58 leaves 1.8e19, still bounded).  At that scale the reference's ray
-generator (eye + 4 dir, then - eye) rounds every primary direction away: every sample of the unbounded cells is the background, in the
-restatements and on the device alike.  Those cells show that the unbounded kernels are launched, run and write the right records, not
-what they compute.
+(pt_render_indirect_rr) and the pixel list (pt_render_indirect_pixels), each for the four estimators (mis, power); resampled light
+sampling with M = 8 candidates (direct, the roulette and the list kind by power, plain and MIS); environment lighting under a 16 x 16
+map of distinct texels with one environment sample (direct, and the roulette kind by power with MIS) -- the 21 values that
+ptk_lit_kind_valid accepts.  A form is what the search of a scene is: the LBVH, the table in LDS (at most 256 triangles) or the tiled
+table; over packed quads, independent triangles with the short reciprocal (every |e1|_1 |e2|_1 <= PT_DET_BOUND_MAX = 2e19), or
+unbounded ones.  Eight forms' scenes are scenes.direct_scaled's: 1, 10 and 15 nested Cornell boxes (36, 360 and 540 triangles) times
+2^0, and times 2^30 for three unbounded forms: the largest |e1|_1 |e2|_1 of the box is 62.58, times 2^60 it is 7.2e19 (2^58 leaves
+1.8e19, still bounded).  At that scale the reference's ray generator (eye + 4 dir, then - eye) rounds every primary direction away:
+every sample of those cells is the background, in the restatements and on the device alike.  The cells of those three forms --
+lbvh_unbounded, lds_unbounded, tiled_unbounded -- show that the unbounded kernels are launched, run and write the right records, not
+what they compute.  The cells of lds_slab, tiled_slab and lbvh_slab (SHADING_UNBOUNDED) show what they compute: scenes.slab's 1, 10 and
+15 boxes at unit scale beside one huge triangle under them, which alone lifts the scene over the bound; half of the first hits are on
+that triangle, a quarter on the boxes, light samples at its vertices are open and occluded, and no sample is non-finite.
 
 Every cell renders 24 x 16 pixels x 2 frames, K = 2, B = 6 -- 768 items: 12 waves, 3 workgroups -- the roulette kinds with R = 1 and a
 cap of 0.25, so that roulette is played at every vertex, the list kinds a scattered list of 101 pixels at mixed frames."""
@@ -21,21 +26,42 @@ import collections
 import numpy as np
 
 import direct_oracle as do
+import env_oracle as eo
 import indirect_oracle as io
 import mis_oracle as mo
 import power_oracle as po
+import ris_oracle as rs
 import roulette_oracle as ro
+from env_scenes import env_map
 from scenes import edge_scene
 
 W, H, FRAMES, K, B, R, CAP, LISTED = 24, 16, 2, 2, 6, 1, 0.25, 101
+M, KE, ENV_MAP = 8, 1, "gradient:16"   # the RIS kinds' candidates; the env kinds' samples and map: a distinct value per texel, none of them 0.45
 LDS_TRI_MAX, BVH_AUTO_MIN, DET_BOUND_MAX = 256, 512, np.float32(2.0e19)   # csrc/pt_kernels.h: PT_LDS_TRI_MAX, PT_BVH_AUTO_MIN, PT_DET_BOUND_MAX
 BVH_BIG_DIV, BVH_BIG_MAX = np.float32(16.0), 64                          # csrc/pt_bvh.hip, csrc/pt_kernels.h
 
-Kind = collections.namedtuple("Kind", "name indirect mis power rr list")
+Kind = collections.namedtuple("Kind", "name indirect mis power rr list ris env", defaults=(False, False))
 _ESTIMATORS = (("", False, False), ("_mis", True, False), ("_power", False, True), ("_mis_power", True, True))
 KINDS = (Kind("direct", False, False, False, False, False), Kind("direct_power", False, False, True, False, False)) + \
     tuple(Kind(base + est, True, mis, power, rr, lst) for base, rr, lst in (("indirect", False, False), ("rr", True, False), ("list", True, True))
-          for est, mis, power in _ESTIMATORS)
+          for est, mis, power in _ESTIMATORS) + \
+    (Kind("ris_direct", False, False, True, False, False, ris=True),) + \
+    tuple(Kind("ris_" + base + est, True, mis, True, True, lst, ris=True) for base, lst in (("rr", False), ("list", True))
+          for est, mis in (("", False), ("_mis", True))) + \
+    (Kind("env_direct", False, False, True, False, False, env=True), Kind("env_rr_mis", True, True, True, True, False, env=True))
+LIT_KIND_INDICES = 128   # csrc/pt_kernels.h: PT_LIT_KIND_INDICES
+
+
+def kind_valid(k) -> bool:
+    """ptk_lit_kind_valid (csrc/pt_kernels.h), restated"""
+    return (not k.list or k.rr) and (not k.rr or k.indirect) and (not k.mis or k.indirect) and \
+        (not k.ris or (k.power and k.rr == k.indirect)) and \
+        (not k.env or (k.power and not k.ris and not k.list and k.rr == k.indirect and k.mis == k.indirect))
+
+
+def kind_index(k) -> int:
+    """ptk_lit_kind_index, restated"""
+    return k.indirect | k.mis << 1 | k.power << 2 | k.rr << 3 | k.list << 4 | k.ris << 5 | k.env << 6
 
 # search: "lbvh", "lds" or "tiled"; quads: 3 = the packed shared-u filter over the searched table, 0 = independent triangles;
 # bounded: the short exact reciprocal.  quad / accel: PT_OPT_QUAD_FILTER / PT_OPT_ACCEL of the cell's renders
@@ -51,8 +77,14 @@ FORMS = (
     Form("lds_unbounded", "scaled:1,30", 0, 1, "lds", False, 0),
     Form("tiled", "scaled:10,0", 0, 1, "tiled", True, 0),
     Form("tiled_unbounded", "scaled:10,30", 0, 1, "tiled", False, 0),
+    # scenes.slab: the boxes at unit scale and one huge triangle that alone lifts the scene over the bound -- unbounded forms that shade.
+    # At 15 copies the slab is the one triangle longer than 1/16 of the scene: a big table of one
+    Form("lds_slab", "slab:1", 0, 1, "lds", False, 0),
+    Form("tiled_slab", "slab:10", 0, 1, "tiled", False, 0),
+    Form("lbvh_slab", "slab:15", 0, 0, "lbvh", False, 0),
 )
-# cells left out by name, with the reason: (form name, kind name).  None: all 112 are in the table
+SHADING_UNBOUNDED = ("lds_slab", "tiled_slab", "lbvh_slab")
+# cells left out by name, with the reason: (form name, kind name).  None: all 231 are in the table
 LEFT_OUT = ()
 CELLS = tuple((f, k) for f in FORMS for k in KINDS if (f.name, k.name) not in LEFT_OUT)
 
@@ -107,7 +139,14 @@ def _want(kind_name, scene):
     tris, mats, lights, cam = edge_scene(scene)[1]
     gid, frame = do.sample_ids(W, H, FRAMES)
     kw = dict(lights=lights, cam=cam)
-    if k.rr:
+    if k.ris:
+        rkw = dict(B=B, R=R, cap=CAP, mis=k.mis, **kw) if k.indirect else kw
+        fb, rad = rs.render(tris, mats, W, H, 0, FRAMES, K, M, **rkw), rs.samples(tris, mats, W, H, gid, frame, K, M, **rkw)
+    elif k.env:
+        ekw = dict(B=B, R=R, cap=CAP, **kw) if k.indirect else kw
+        t = env_map(ENV_MAP)
+        fb, rad = eo.render(tris, mats, t, W, H, 0, FRAMES, K, KE, **ekw), eo.samples(tris, mats, t, W, H, gid, frame, K, KE, **ekw)
+    elif k.rr:
         fb = ro.render(tris, mats, W, H, 0, FRAMES, K, B, R, CAP, mis=k.mis, power=k.power, **kw)
         rad = ro.samples(tris, mats, W, H, gid, frame, K, B, R, CAP, mis=k.mis, power=k.power, **kw)[0]
     elif k.power:

@@ -6,6 +6,8 @@ generated from fixed seeds, and the order of the draws from a generator is part 
   * the far-origin scenes (tests/lbvh_far.py has their ray families): tile_scene, soup(2000, 5);
   * scenes at the edges of what the LBVH takes -- scale, offset, shape, the builder's boundaries -- with rays to query them:
     scene(name) for name in NAMES (tests/test_lbvh_scale_cpu.py: the oracle's scale identities; tests/test_gpu_lbvh_scenes.py);
+  * slab: the boxes at unit scale beside ONE huge triangle that lifts the scene over PT_DET_BOUND_MAX -- the scene on which the
+    unbounded kernels shade (tests/lit_cells.py), and as slab541 a cluster beside an outlier for the LBVH's builder;
   * scenes at the edges of direct illumination's light sample, each (tris, mats, lights, camera or None): direct_scaled,
     direct_light_list, direct_other_type, direct_from_behind (tests/test_direct_cpu.py proves that each reaches its edge,
     tests/test_gpu_direct_edges.py renders them); glossy_room, the GGX branch at every roughness a guard can meet (and, with
@@ -331,11 +333,13 @@ def scene(name):
     if name in ("n511", "n512"):
         t = soup(int(name[1:]), 51, 0.3)
         return t, soup_rays(t)
+    if name == "slab541":
+        return edge_scene("slab:15")[1][0], slab_rays()
     raise ValueError(name)
 
 
 NAMES = ["scale%d" % k for k in SCALES] + ["offset%d" % j for j in OFFSETS] + \
-        ["squeezed", "stretched", "shared_point", "big64", "big65", "none_finite", "one_finite", "n511", "n512"]
+        ["squeezed", "stretched", "shared_point", "big64", "big65", "none_finite", "one_finite", "n511", "n512", "slab541"]
 
 
 # ---- direct illumination: the light sample's edges ------------------------------------------------------------------------------
@@ -352,6 +356,63 @@ def direct_scaled(copies, k):
     cam = Camera(eye=tuple(np.float32(v) * s for v in ref.eye), center=tuple(np.float32(v) * s for v in ref.center), up=ref.up,
                  fov_y_deg=ref.fov_y_deg)
     return tris, mats, _scene.emitters(tris, mats), cam
+
+
+SLAB_L, SLAB_L_BOUNDED = 2.5e9, 2.2e9
+SLAB_P1 = (-60.0, -0.25, -2.5)
+SLAB_EYE, SLAB_CENTER = (7.0, 4.5, 5.0), (0.0, 1.5, -2.5)
+
+
+def slab_edges(L=SLAB_L):
+    """(e1, e2) of the slab: diagonal in the plane y = const, so that |e1|_1 |e2|_1 = 4 L^2 while |e1 x e2| = 2 L^2"""
+    return np.array([L, 0.0, L], np.float32), np.array([L, 0.0, -L], np.float32)
+
+
+def slab(copies, L=SLAB_L, p1=SLAB_P1):
+    """nested_boxes(copies) at unit scale plus ONE huge triangle, the last, 0.25 below the boxes' floor, with a material of its own (the
+    last: a copy of material 0, diffuse, albedo 0.7), seen by an oblique camera.  The slab alone puts the scene above PT_DET_BOUND_MAX
+    (4 L^2 = 2.5e19 > 2e19: L > 2.24e9), so every search of the scene is the unbounded one, while the camera, the boxes, the lights and
+    the shadow rays are an ordinary scene's.  Its layout keeps the reference's triangle test precise: p1 lies near the scene (origin -
+    p1 keeps the origin), the winding gives det > 0 for rays from above (one side is culled), and the normal's square 4 L^4 stays below
+    FLT_MAX (L < 3.03e9), which axis-parallel edges of that L1 product cannot.  It covers the wedge x > -60, |z + 2.5| < x + 60.
+    L = SLAB_L_BOUNDED is the bounded twin."""
+    from oclpathtracer_amd.camera import Camera
+
+    tris, mats = nested_boxes(copies)
+    mats = np.concatenate([mats, mats[:1]])
+    assert mats[-1]["type"] == _scene.DIFFUSE and abs(float(mats[-1]["albedo"][0]) - 0.7) < 1e-6 and not mats[-1]["emissive"][:3].any()
+    one = np.zeros(1, _scene.TRIANGLE_DTYPE)
+    e1, e2 = slab_edges(L)
+    a = np.asarray(p1, np.float32)
+    one["p1"][0, :3], one["p2"][0, :3], one["p3"][0, :3] = a, a + e1, a + e2
+    one["id"] = len(mats) - 1
+    tris = np.concatenate([tris, one])
+    return tris, mats, _scene.emitters(tris, mats), Camera(eye=SLAB_EYE, center=SLAB_CENTER, up=(0.0, 1.0, 0.0), fov_y_deg=60.0)
+
+
+SLAB_RAYS_W, SLAB_RAYS_H = 64, 32
+
+
+def slab_rays(seed=541):
+    """4 096 rays for slab(15), a cluster beside an outlier (the scene's extent is 5e9, the 540 small triangles share one cell of the
+    LBVH's 16-bit grid, and the box margin PT_BVH_EPS x extent is wider than the cluster): the 64 x 32 primary rays of the scene's camera
+    at frame 0 (the restatement of pt_camera_rays: they see the slab around the boxes), then 2 048 rays that start ON the slab, under
+    the boxes and up to 2 beside them, and go upwards -- the slab culls them (they leave its back), the boxes' floor too, and what they
+    hit is the inside of the boxes"""
+    import query_oracle
+
+    tris, _, _, cam = edge_scene("slab:15")[1]
+    first = query_oracle.camera_rays(SLAB_RAYS_W, SLAB_RAYS_H, 0, cam)
+    n = len(first)
+    pts = np.concatenate([tris[f][:-1, :3] for f in ("p1", "p2", "p3")])
+    lo, hi = pts.min(0) - np.float32(2.0), pts.max(0) + np.float32(2.0)
+    rng = np.random.default_rng(seed)
+    r = np.zeros((n, 8), np.float32)
+    r[:, 0], r[:, 1], r[:, 2] = rng.uniform(lo[0], hi[0], n), SLAB_P1[1], rng.uniform(lo[2], hi[2], n)
+    d = rng.normal(size=(n, 3))
+    d[:, 1] = np.abs(d[:, 1])
+    r[:, 3], r[:, 4:7] = 1e20, d
+    return np.concatenate([first, r])
 
 
 MIXED_SCALE = -7   # the k at which direct_scaled(10 or 15, k) has occluded, searched-open and unsearched shadow rays side by side
@@ -444,7 +505,7 @@ _EDGE_SCENES = {}
 
 def edge_scene(name):
     """(name, (tris, mats, lights or None, camera or None)) of a named input of the illumination edge tests, each built once:
-    cornell, nested:COPIES, scaled:COPIES,K, lights:list|36|10|all, glossy:SHIFT, finite:SHIFT, other_type, from_behind"""
+    cornell, nested:COPIES, scaled:COPIES,K, slab:COPIES[,bounded], lights:list|36|10|all, glossy:SHIFT, finite:SHIFT, other_type, from_behind"""
     if name not in _EDGE_SCENES:
         kind, _, arg = name.partition(":")
         if kind == "cornell":
@@ -454,6 +515,9 @@ def edge_scene(name):
         elif kind == "scaled":
             copies, k = arg.split(",")
             sc = direct_scaled(int(copies), int(k))
+        elif kind == "slab":   # slab:COPIES, or slab:COPIES,bounded for the twin below the bound
+            copies, _, twin = arg.partition(",")
+            sc = slab(int(copies), {"": SLAB_L, "bounded": SLAB_L_BOUNDED}[twin])
         elif kind == "lights":
             sc = direct_light_list(*{"list": (), "36": ([36],), "10": ([10],), "all": (np.arange(37),)}[arg])
         elif kind == "glossy":

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import ao_oracle
 from conftest import ROOT
 
 
@@ -114,6 +115,23 @@ def test_closed_box_is_always_occluded():
     cam = Camera(eye=(0.1, -0.2, 0.3), center=(0.15, -0.15, -1.0), up=(0.0, 1.0, 0.0), fov_y_deg=40.0)
     c = ao_oracle.counts(box, 16, 12, 0, 2, 6, 1e20, cam=cam)
     assert np.all(c[..., 1] == 2) and np.all(c[..., 0] == 0)
+
+
+@pytest.mark.parametrize("search,scene,accel", ao_oracle.SLAB_FORMS)
+def test_the_slab_scenes_are_open_and_occluded(search, scene, accel):
+    """the unbounded scenes of tests/test_gpu_ao.py take their search unbounded, and on at least 0.3 of the pixels a sample hits and
+    one of its rays is open (measured: 0.64 - 0.66; on 0.39 - 0.41 of them a ray is occluded as well)"""
+    import lit_cells as lc
+    from scenes import edge_scene
+
+    tris = edge_scene(scene)[1][0]
+    assert lc.form_of(tris, 0, accel)[:2] == (search, False)
+    c = ao_oracle.slab_counts(scene)
+    opened, hits = c[..., 0], c[..., 1]
+    both = ((opened > 0) & (hits > 0)).mean()
+    partly = ((opened > 0) & (opened < ao_oracle.SLAB_K * hits)).mean()
+    print("%s: open and hits non-zero on %.2f of the pixels, partly occluded on %.2f" % (scene, both, partly))
+    assert both >= 0.3 and partly > 0
 
 
 def test_restatement_agrees_with_a_float64_model(cornell):

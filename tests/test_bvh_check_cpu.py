@@ -111,3 +111,29 @@ def test_every_single_mutation_is_rejected(snap):
         print("%-48s -> %s" % (name, e.value))
         seen += 1
     assert seen == 12
+
+
+def test_a_cluster_beside_an_outlier():
+    """slab541 (scenes.slab(15) and scenes.slab_rays) without a device: the oracle hits with at least 0.5 of the 4 096 rays, at least
+    0.1 of the hits on the slab and 0.3 on the boxes; the 540 small triangles are smaller than ONE cell of the 16-bit grid on every axis
+    and the margin PT_BVH_EPS x extent is wider than the cluster; and the checker's rules -- tightness included -- can hold on such a
+    grid: the reference builder's hierarchy passes them, so a device hierarchy that fails them is the builder's fault, not the rule's"""
+    import query_oracle as qo
+    import scenes
+
+    tris, rays = scenes.scene("slab541")
+    assert len(tris) == 541 and len(rays) == 4096 and "slab541" in scenes.NAMES
+    wt = qo.closest_threads(tris, rays)[:, 1].view(np.int32)
+    hit = wt >= 0
+    slab, boxes = (wt[hit] == 540).mean(), (wt[hit] < 540).mean()
+    print("slab541: the oracle hits with %.2f of the rays (camera %.2f, upward %.2f), %.2f of the hits on the slab, %.2f on the boxes"
+          % (hit.mean(), hit[:2048].mean(), hit[2048:].mean(), slab, boxes))
+    assert hit.mean() >= 0.5 and slab >= 0.1 and boxes >= 0.3
+    assert hit[2048:].mean() >= 0.2 and not (wt[2048:] == 540).any(), "the upward rays leave the slab's back and meet the boxes"
+    v, finite, lo, hi = B.tri_boxes(tris)
+    gmin, gstep = B.reference_grid(v, finite, lo, hi)
+    eps = B.scene_eps(v, finite)
+    cluster = hi[:540].max(0) - lo[:540].min(0)
+    assert np.all(cluster < gstep) and eps > cluster.max() and eps > 2 * gstep.max()
+    out = B.check(tris, *B.reference_build(tris))
+    assert out["leaves"] == 540 and list(B.big_set(finite, lo, hi)) == [540]

@@ -145,6 +145,25 @@ def test_the_soups_and_the_lens_are_seen():
     assert np.array_equal(lens.tri >= 0, lens.depth[..., 1] == 1.0)
 
 
+def test_the_slab_scenes_show_the_slab():
+    """the unbounded scenes of tests/test_gpu_features.py take their search unbounded; the slab's own material (the table's last, met on
+    no box) shows in at least 0.4 of the samples -- its id and albedo stored, its depth a hit's -- the boxes in 0.2, and no normal is NaN"""
+    import lit_cells as lc
+
+    for search, name, accel in fc.SLAB_FORMS:
+        tris, mats, cam = fc.case(name)
+        assert lc.form_of(tris, 0, accel)[:2] == (search, False)
+        s = fc.oracle(name, fc.SLAB_W, fc.SLAB_H)
+        slab = s.tri == len(tris) - 1
+        boxes = (s.tri >= 0) & ~slab
+        print("%s: slab %.2f, boxes %.2f, misses %.2f of the samples" % (name, slab.mean(), boxes.mean(), (s.tri < 0).mean()))
+        assert slab.mean() >= 0.4 and boxes.mean() >= 0.2 and (s.tri < 0).any()
+        assert np.all(s.id[slab] == len(mats) - 1) and not np.any(s.id[boxes] == len(mats) - 1)
+        assert np.array_equal(_bits(s.albedo[slab]), np.broadcast_to(_bits(mats["albedo"][-1, :3]), s.albedo[slab].shape))
+        assert np.all(s.depth[slab][:, 1] == 1.0) and np.all(s.depth[slab][:, 0] > 0.0) and np.isfinite(s.depth).all()
+        assert not np.isnan(s.normal).any() and np.all(s.normal[slab] == np.float32([0.0, 1.0, 0.0]))
+
+
 def test_stripes_are_the_whole_image_rows():
     """stripe_rows = 5, n_ranks = 3, rank = 1 of 24 rows: rows 5-9 and 20-23, nine rows, with the whole image's samples"""
     part = fc.oracle("cornell", stripe_rows=5, n_ranks=3, rank=1)

@@ -11,7 +11,7 @@ import ao_oracle as ao
 from conftest import assert_fb_equal
 from gpu_support import SEARCHES, cornell_rays, harness_ppm, options, refill_rays
 from oclpathtracer_amd import shim
-from scenes import soup_with_duplicates
+from scenes import edge_scene, soup_with_duplicates
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +47,18 @@ def test_counts_bit_exact(device, cornell, quad, accel):
             what = "%dx%d r%g q%d a%d" % (W, H, radius, quad, accel)
             assert np.array_equal(got, want), what + ": counts differ at %d pixels" % int((got != want).any(-1).sum())
             _check_image(img, got, 8, 1.0, what)
+
+
+@pytest.mark.parametrize("search,scene,accel", ao.SLAB_FORMS, ids=[f[0] for f in ao.SLAB_FORMS])
+def test_unbounded_scene_that_shades(device, search, scene, accel):
+    """pt_ao_kernel<false, ..> over the table in LDS and the tiled one, pt_ao_bvh_kernel<false, ..>: the boxes beside one triangle that
+    lifts the scene over PT_DET_BOUND_MAX (scenes.slab), where samples hit, and rays are open and occluded (tests/test_ao_cpu.py)"""
+    tris, _, _, cam = edge_scene(scene)[1]
+    want = ao.slab_counts(scene)
+    with options(device, QUAD_FILTER=0, ACCEL=accel):
+        got, img = _render(device, tris, ao.SLAB_W, ao.SLAB_H, ao.SLAB_FRAMES, ao.SLAB_K, ao.SLAB_RADIUS, camera=cam, stripe_rows=1)
+    assert np.array_equal(got, want), "%s: counts differ at %d pixels" % (scene, int((got != want).any(-1).sum()))
+    _check_image(img, got, ao.SLAB_K, 1.0, scene)
 
 
 def test_progressive_equals_one_call_and_frame_zero_overwrites(device, cornell):

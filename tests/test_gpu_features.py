@@ -144,6 +144,15 @@ def test_lbvh(device, name):
     _assert_case(device, name)
 
 
+@pytest.mark.parametrize("search,name,accel", fc.SLAB_FORMS, ids=[f[0] for f in fc.SLAB_FORMS])
+def test_unbounded_scene_that_shades(device, search, name, accel):
+    """pt_feature_kernel<false, ..> over the table in LDS and the tiled one, pt_feature_bvh_kernel<false, ..>: the boxes beside one
+    triangle that lifts the scene over PT_DET_BOUND_MAX (scenes.slab), all four outputs; the slab's material shows in half the samples
+    (tests/test_features_cpu.py)"""
+    with options(device, QUAD_FILTER=0, ACCEL=accel):
+        _assert_case(device, name, fc.SLAB_W, fc.SLAB_H)
+
+
 def test_brute_force_equals_the_lbvh(device):
     """PT_OPT_ACCEL = 1 on the soup: the tiled brute-force kernel, the LBVH's samples and the oracle's"""
     want = _render(device, "soup")

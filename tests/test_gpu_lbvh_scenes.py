@@ -63,14 +63,21 @@ def test_scene_through_the_lbvh(device, name):
         assert (wt >= 0).mean() >= 0.2, name + ": a case that hardly hits tests nothing"
     # |e1| |e2| above PT_DET_BOUND_MAX: the shim then takes the exact-division (DET_BOUNDED = false) kernels.  The test can show the
     # precondition (here, with the L1 norms the shim's own bound uses) and the results, not which instantiation ran.
-    if name.startswith("scale") and int(name[5:]) >= 34:
+    if name == "slab541" or name.startswith("scale") and int(name[5:]) >= 34:
         e1 = np.abs(tris["p2"][:, :3].astype(np.float64) - tris["p1"][:, :3]).sum(1)
         e2 = np.abs(tris["p3"][:, :3].astype(np.float64) - tris["p1"][:, :3]).sum(1)
         assert (e1 * e2).max() > 2.0e19
+    if name == "slab541":                                       # (tests/test_bvh_check_cpu.py has the same conditions without a device)
+        hit = wt >= 0
+        assert hit.mean() >= 0.5 and (wt[hit] == len(tris) - 1).mean() >= 0.1 and (wt[hit] < len(tris) - 1).mean() >= 0.3
     lib = shim.load()
     count = lambda: lib.pt_device_get_option(device._h, shim.PT_OPT_BVH_BUILD_COUNT)
     rc = RayCaster(device, tris)
     try:
+        if name == "slab541":                                   # its first half is what pt_camera_rays makes of the scene's camera
+            cam = S.edge_scene("slab:15")[1][3]
+            first = rc.camera_rays(S.SLAB_RAYS_W, S.SLAB_RAYS_H, 0, cam)
+            assert np.array_equal(words8(first).view(np.uint32), rays[: len(first)].view(np.uint32)), "pt_camera_rays differs from its restatement"
         if name in ("n511", "n512"):                            # PT_OPT_ACCEL = 0: the hierarchy from 512 triangles on
             with options(device, ACCEL=0):
                 b = count()
@@ -84,6 +91,9 @@ def test_scene_through_the_lbvh(device, name):
             early = rc.occluded(rays, early_exit=True)
             assert count() - b == (0 if name == "n512" else 1), name + ": the shim did not take the LBVH"
             check_hierarchy(device, tris, name)
+            if name == "slab541":                               # no search was cut short: nothing is deferred to the next observing call
+                assert lib.pt_sync(device._h) == shim.PT_OK, lib.pt_last_error()
+                assert snapshot(device)[3].tolist() == [len(tris) - 1], "the slab alone is kept out of the hierarchy"
             if name in ("big64", "big65"):                      # the builder's n > PT_BVH_BIG_MAX and k < PT_BVH_BIG_MAX comparisons sit here
                 assert len(snapshot(device)[3]) == (64 if name == "big64" else 0), name + ": the scene no longer sits on the boundary"
         with options(device, ACCEL=1):
@@ -98,6 +108,34 @@ def test_scene_through_the_lbvh(device, name):
     assert_hits_equal(got1, want, name + " brute force against the oracle")
     assert_hits_equal(got2, got1, name + " LBVH against brute force")
     assert np.array_equal(occ, (wt >= 0).astype(np.int32)) and np.array_equal(early, occ)
+
+
+def words8(rays) -> np.ndarray:
+    """pt_ray records (RAY_DTYPE or [N, 8] float32) as float32 [N, 8]"""
+    return np.ascontiguousarray(np.asarray(rays)).view(np.float32).reshape(-1, 8)
+
+
+def test_cluster_beside_an_outlier_needs_no_deep_stack(device):
+    """slab541: 540 triangles in one cell of the 16-bit grid beside a triangle of 5e9, a box margin (PT_BVH_EPS x extent = 3e5) wider
+    than the cluster, so that every ray that comes near enters every node.  A tallying render from the scene's camera reports the
+    deepest traversal stack any ray needed: within the capacity of 64, and the render equals the oracle's -- no subtree was lost, no
+    PT_ERR_TRAVERSAL was raised (the read and pt_sync would report it)."""
+    import camera_oracle
+    from conftest import assert_fb_equal
+    from gpu_support import render
+
+    tris, mats, _, cam = S.edge_scene("slab:15")[1]
+    W, H, frames, depth = 24, 16, 2, 6
+    want, st = camera_oracle.render(tris, mats, W, H, frames, cam, max_bounces=depth, want_stats=True)
+    with options(device, ACCEL=2, BVH_TALLY=1):
+        got, gst = render(device, tris, mats, W, H, frames, depth=depth, camera=cam, want_stats=True)
+        assert shim.load().pt_sync(device._h) == shim.PT_OK
+    stack = int(gst[shim.PT_STAT_BVH_MAX_STACK])
+    print("slab541: deepest traversal stack %d of 64, %d nodes entered and %d triangles tested by %d rays"
+          % (stack, int(gst[shim.PT_STAT_BVH_NODES]), int(gst[shim.PT_STAT_BVH_TRIS]), int(gst[shim.PT_STAT_RAYS])))
+    assert 1 <= stack <= 64
+    assert_fb_equal(got, want, "slab541, tallying render")
+    assert int(gst[shim.PT_STAT_RAYS]) == st["rays"]
 
 
 def test_snapshot_refuses_when_no_lbvh_stands(device):

@@ -1,7 +1,8 @@
-"""Every lit kernel once on the MI355X, bit for bit: the 14 kinds of lit render under the 8 forms of the search (tests/lit_cells.py),
+"""Every lit kernel once on the MI355X, bit for bit: the 21 kinds of lit render under the 11 forms of the search (tests/lit_cells.py),
 one kernel instantiation per cell.  Each cell's framebuffer and sample workspace (the radiance before the fold) are compared with the
-restatements the lit tests use (direct_oracle, indirect_oracle, mis_oracle, power_oracle, roulette_oracle), NaN positions equal.  A
-launcher that picked another cell's kernel -- the plain estimator for MIS with the power choice on a tiled table, say -- shows here.
+restatements the lit tests use (direct_oracle, indirect_oracle, mis_oracle, power_oracle, roulette_oracle, ris_oracle, env_oracle), NaN
+positions equal.  A launcher that picked another cell's kernel -- the plain estimator for MIS with the power choice on a tiled table,
+say -- shows here; on the three slab forms an unbounded kernel that shades, samples a light or folds wrongly shows as well.
 
 tests/test_lit_cells_cpu.py proves that each scene takes its form.  On the device the LBVH forms are asserted through
 pt_bvh_snapshot: a hierarchy stands for the scene, and the triangles kept out of it -- the table the two-pass search runs over -- are
@@ -16,16 +17,22 @@ import pytest
 import lit_cells as lc
 from adaptive_support import PixelBuffers, _run_list
 from conftest import assert_fb_equal
+from env_scenes import env_map
 from gpu_support import lit_with_samples, options
 from oclpathtracer_amd import shim
+from oclpathtracer_amd.environment import Environment
 from oclpathtracer_amd.indirect import Roulette
 from scenes import edge_scene
 
 pytestmark = pytest.mark.gpu
 
 
-def _render(device, kind, scene4):
+def _render(device, kind, scene4, sky):
     kw = dict(light_choice="power" if kind.power else "uniform")
+    if kind.ris:
+        kw.update(candidates=lc.M)
+    if kind.env:
+        kw.update(environment=sky, env_samples=lc.KE)
     if kind.indirect:
         kw.update(max_bounces=lc.B, mis=kind.mis)
     if kind.rr:
@@ -47,21 +54,25 @@ def _assert_lbvh(device, form, tris):
 def test_every_kind_under_the_form(device, form):
     scene4 = edge_scene(form.scene)[1]
     kinds = [k for f, k in lc.CELLS if f is form]
-    assert len(kinds) >= 13
+    assert len(kinds) >= 20
     slots = lc.slots()
-    with options(device, QUAD_FILTER=form.quad, ACCEL=form.accel):
-        for kind in (k for k in kinds if not k.list):
-            what = "%s %s" % (form.name, kind.name)
-            want_fb, want_rad = lc.wanted(kind, form.scene)
-            fb, ws = _render(device, kind, scene4)
-            assert_fb_equal(ws, want_rad, what + ": radiance before the fold")
-            assert_fb_equal(fb, want_fb, what)
-        b = PixelBuffers(device, scene4, lc.W, lc.H, frames=lc.FRAMES)
-        try:
+    sky = Environment(env_map(lc.ENV_MAP))
+    b = None
+    try:
+        with options(device, QUAD_FILTER=form.quad, ACCEL=form.accel):
+            for kind in (k for k in kinds if not k.list):
+                what = "%s %s" % (form.name, kind.name)
+                want_fb, want_rad = lc.wanted(kind, form.scene)
+                fb, ws = _render(device, kind, scene4, sky)
+                assert_fb_equal(ws, want_rad, what + ": radiance before the fold")
+                assert_fb_equal(fb, want_fb, what)
+            b = PixelBuffers(device, scene4, lc.W, lc.H, frames=lc.FRAMES)
             for kind in (k for k in kinds if k.list):
                 _run_list(device, b, form.scene, lc.W, lc.H, slots, lc.FRAMES, lc.K, lc.B, lc.R, lc.CAP, kind.mis, kind.power,
-                          "%s %s" % (form.name, kind.name))
+                          "%s %s" % (form.name, kind.name), candidates=lc.M if kind.ris else 0)
             if form.search == "lbvh":
                 _assert_lbvh(device, form, scene4[0])
-        finally:
+    finally:
+        if b is not None:
             b.release()
+        sky.release()

@@ -260,6 +260,26 @@ def test_tiled_brute_force_between_the_lds_table_and_the_lbvh(device, oracle, co
     assert gst[shim.PT_STAT_RAYS] == st["rays"]
 
 
+@pytest.mark.parametrize("search,copies,accel", [("tiled", 10, 1), ("lbvh", 15, 0)])
+def test_unbounded_trace_kernels_on_a_scene_they_shade(device, search, copies, accel):
+    """The tiled and the LBVH trace kernel with DET_BOUNDED = false: the boxes at unit scale beside one triangle that alone lifts the
+    scene over PT_DET_BOUND_MAX (scenes.slab; tests/test_lit_cells_cpu.py proves that half of the first hits are on it, a quarter on
+    the boxes, and that paths return to it), from the scene's camera, one frame per launch so that the checkpointed launches take part"""
+    import camera_oracle
+    import lit_cells as lc
+
+    tris, mats, _, cam = scenes.edge_scene("slab:%d" % copies)[1]
+    assert lc.form_of(tris, 0, accel)[:2] == (search, False)
+    W, H, frames, depth = 24, 16, 4, 6
+    want, st = camera_oracle.render(tris, mats, W, H, frames, cam, max_bounces=depth, want_stats=True)
+    # (three quarters of the primary rays hit, and a hit that is no emitter sends a ray on: at least 1.5 rays per sample)
+    assert np.isfinite(want).all() and st["rays"] >= 1.5 * W * H * frames
+    with options(device, QUAD_FILTER=0, ACCEL=accel, CHUNK_FRAMES=1):
+        got, gst = render(device, tris, mats, W, H, frames, depth=depth, camera=cam, want_stats=True)
+    assert_fb_equal(got, want, "slab:%d through the %s trace kernel" % (copies, search))
+    assert gst[shim.PT_STAT_RAYS] == st["rays"] and int(gst[shim.PT_STAT_CARRIED]) > 0
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,ntri", [("cornell", 36), ("soup", 300), ("soup", 2000), ("soup", 20000), ("degenerate", 36),
                                         ("pairs_broken", 36), ("quads_far", 36)])
