@@ -1047,6 +1047,62 @@ int pt_render_indirect_env(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t m
                            pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_roulette* roulette,
                            const pt_environment* environment, const pt_camera* cam /* NULL = the reference's */, pt_event_t ev);
 
+/* ---- radiance queries: path-traced radiance along the caller's rays ---------------------------------------------------------------
+ * pt_radiance_rays is pt_render_indirect_rr with the third sample start: the item's primary ray is read from a buffer of pt_ray, not
+ * made by a camera for a pixel.  Light probes, lightmap and vertex baking, irradiance sensors, panoramic, orthographic or fisheye
+ * cameras and per-ray radiance for a model trained elsewhere are all this call over rays the caller makes.
+ *
+ * THE ITEM.  With n = num_rays, item i = s * n + r is sample sample_begin + s of ray r:
+ *   - its seed is (first_ray + r) + hash(sample_begin + s) in uint32 -- the renderers' gid + hash(frame), :308, with the ray's id
+ *     first_ray + r standing for the pixel and the sample's number for the frame;
+ *   - its primary ray is getRay(origin, dir) of rays[r] (:73-77): loaded and normalised exactly as pt_intersect_rays does it (a
+ *     zero-length or non-finite direction is defined behaviour there and here: the search finds nothing or what IEEE makes of it);
+ *   - NO uniform is drawn before the walk (the renderers draw the two jitter uniforms, and the lens two more);
+ *   - tmax and reserved of the record are NOT read: a radiance ray is unbounded, as every path segment is;
+ *   - from there on it is pt_render_indirect_rr's sample from its closest search from 1e20 on, word for word: the estimator chosen by
+ *     mis and cdf / tri_q (both NULL = the uniform choice), K = light_samples per vertex, B = max_bounces vertices, the roulette
+ *     (first_bounce >= B plays none);
+ *   - samples[i] receives max(L, 0), 12 bytes: the layout [sample][ray][3] is the sample workspace's.
+ * Put differently: a call computes pt_render_indirect_rr's workspace for an image of first_ray + num_rays x 1 pixels whose pixel id
+ * starts at rays[id - first_ray] with no jitter draw.  Two calls over rays [0, a) and [a, n) with first_ray 0 and a equal one call.
+ *
+ * CHUNKS.  The samples are walked in chunks of min(samples left, floor(bytes of `samples` / (n x 12)), floor((2^31 - 1) / n)); there
+ * is no framebuffer and no fold.  With `moments` given, each chunk is followed by pt_sample_moments' accumulation over it, in ascending
+ * sample order, and `reset` applies to the first chunk only: one call of a + b samples equals two calls of a and b (reset, then not)
+ * bit for bit, and the workspace may hold as little as one sample of every ray.  With moments == NULL the workspace must hold all
+ * sample_count x n x 12 bytes (PT_ERR_RANGE otherwise: earlier chunks would be overwritten unseen).
+ *
+ * BEHAVIOUR is pt_render_indirect_rr's: the handle's stream, behind the work in flight, asynchronous (ev); the prepared scene, LBVH and
+ * filter tables as a query uses them -- no anchor move, no rebuild; no allocation and no host wait once the scene is prepared;
+ * PT_OPT_ACCEL and PT_OPT_QUAD_FILTER choose the search; PT_ERR_TRAVERSAL is deferred; num_triangles = 0 gives the background
+ * (0.45 per channel); the versions of `samples` and `moments` are bumped.  num_rays = 0 or sample_count = 0 enqueues nothing and
+ * touches no buffer, the moments with `reset` set included.
+ *
+ * ERRORS come before anything is enqueued and leave the buffers untouched: the parents' checks on scene, lights, counts, table,
+ * roulette, K, B and reserved words; PT_ERR_INVALID for rays == NULL, rays or moments of another device, rays not 16-byte aligned,
+ * moments not 8-byte aligned, samples not 4-byte aligned, any two of rays, samples, moments overlapping each other or the light
+ * buffers, a negative sample_begin or sample_count, first_ray + num_rays or sample_begin + sample_count above 2^31 - 1; PT_ERR_RANGE
+ * for rays smaller than n x 32 bytes, moments smaller than n x 56 bytes, a workspace that does not hold one sample of every ray, or
+ * all of them when moments is NULL.
+ * Not here: a ray set per sample, tmax on the first segment, resampling, the environment and pixel lists for rays. */
+typedef struct pt_radiance_params {
+    uint32_t num_rays;       /* n; 0 enqueues nothing */
+    uint32_t first_ray;      /* the id of rays[0]: ray r has id first_ray + r; first_ray + num_rays <= 2^31 - 1 */
+    int32_t  sample_begin;   /* >= 0: samples [sample_begin, sample_begin + sample_count) of every ray; the sum <= 2^31 - 1 */
+    int32_t  sample_count;   /* >= 0; 0 enqueues nothing */
+    int32_t  num_triangles, num_materials, num_lights, light_samples;   /* as pt_indirect_params */
+    int32_t  max_bounces;    /* B, 1..65535 */
+    int32_t  reset;          /* != 0: the moments start from zeros at this call's first chunk (pt_sample_moments' reset) */
+    int32_t  reserved[6];    /* must be 0 */
+} pt_radiance_params;        /* 64 bytes */
+int pt_radiance_rays(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materials,
+                     pt_buffer_t lights /* int32[num_lights]; may be NULL when 0 */, int mis,
+                     pt_buffer_t light_counts /* mis only */, pt_buffer_t cdf, pt_buffer_t tri_q /* both NULL = uniform choice */,
+                     pt_buffer_t rays /* pt_ray[num_rays] */, pt_buffer_t samples /* workspace */,
+                     pt_buffer_t moments /* pt_pixel_moments[num_rays]; may be NULL */,
+                     const pt_radiance_params* params, const pt_roulette* roulette /* not NULL; first_bounce >= B plays none */,
+                     pt_event_t ev);
+
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.
  * pt_profile_query synchronises the stream and returns the summed duration and launch count

@@ -398,9 +398,20 @@ struct PtDirectEnvParams : PtDirectPowerParams {
 struct PtIndirectEnvParams : PtIndirectRrParams {
     PtEnvMap env;
 };
-// what ptk_lit is handed: the largest block of the kinds without env, and the map
+// radiance queries (pt_radiance_rays): the RAYS = true instantiations of the roulette kernels take this block, every other
+// instantiation its block as before (their code does not move).  A launch runs over the caller's RAYS: d.npix is the number of rays n,
+// item = s * n + r is sample d.frame0 + s of ray r, whose seed is (first_ray + r) + pt_hash_u32(d.frame0 + s) and whose primary ray is
+// getRay of rays[2 r], rays[2 r + 1] (pt_query_load: tmax and reserved are not read); d.cam and the image geometry of d.t are not
+// read.  The sample is stored at samples[item] as before
+struct PtIndirectRaysParams : PtIndirectRrParams {
+    const float4* rays;           // [d.npix] pt_ray: origin xyz tmax | dir xyz reserved (two float4)
+    uint32_t first_ray;           // the id of rays[0]
+};
+// what ptk_lit is handed: the largest block of the kinds without env, the map, and the rays
 struct PtLitParams : PtIndirectRisParams {
     PtEnvMap env;
+    const float4* rays;
+    uint32_t first_ray;
 };
 // A kind of lit render names its kernels.  The 14 valid values without ris:
 //   direct illumination (pt_direct_kernel, pt_direct_bvh_kernel):          indirect = mis = rr = list = 0;  power 0 / 1
@@ -423,14 +434,20 @@ static inline int ptk_lit_kind_index(PtLitKind k)   // a table's index
     return k.indirect | k.mis << 1 | k.power << 2 | k.rr << 3 | k.list << 4 | k.ris << 5 | k.env << 6;
 }
 #define PT_LIT_KIND_INDICES 128
+// Radiance queries (pt_radiance_rays) are a second START of a kind's items, beside the kind: a kind names the estimator and the item map
+// of an image render and stays as it stands above; with `rays` its items are samples of the caller's rays (the RAYS = true
+// instantiations, PtIndirectRaysParams).  The 4 kinds that take rays are the roulette kinds, mis 0 / 1 x power 0 / 1 -- the shape of the
+// list kinds: rays need rr and exclude list, ris and env.  Tables over kinds gain a second row for them
+static inline bool ptk_lit_rays_valid(PtLitKind k) { return ptk_lit_kind_valid(k) && k.rr && !k.list && !k.ris && !k.env; }
 // THE launch of a lit render, whatever its kind: `a` is the largest block, and each instantiation is passed its own, sliced from it
 // (PtDirectPowerParams is made of a.d, a.cdf and a.tri_q).  LBVH (m.bvh): the kind's kernel on a persistent grid of at most bvh_blocks
 // = CUs x ptk_lit_bvh_blocks_per_cu(k) workgroups -- the occupancy of the kind's OWN <true, 3> instantiation with the trace kernel's
 // LDS: the direct kernels run at four waves per SIMD, the indirect ones at three, so ptk_query_bvh_blocks_per_cu's premise (five) holds
 // for none.  Brute force: one wave per 64 items; the roulette and list kinds one wave per PT_RR_RUN (pt_constants.h) consecutive
 // items, which refills its dead lanes from its run
-hipError_t ptk_lit(const PtLitParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s);
-int ptk_lit_bvh_blocks_per_cu(PtLitKind k);
+// rays: (ptk_lit_rays_valid(k)) the kind's RAYS instantiations: a.rays and a.first_ray are read, a.d.cam and the image geometry are not
+hipError_t ptk_lit(const PtLitParams& a, PtLitKind k, bool rays, int bvh_blocks, PtSearchMode m, hipStream_t s);
+int ptk_lit_bvh_blocks_per_cu(PtLitKind k, bool rays);
 // the fold of a list launch: one lane per (slot j, channel) folds rad[f][j], f = 0 .. frame_count - 1 ascending, into fb[the slot's
 // pixel] with the slot's own frame numbers (pt_fold_frame); pixels that are not listed are neither read nor written
 struct PtFoldListParams {

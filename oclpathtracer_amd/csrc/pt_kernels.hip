@@ -4264,8 +4264,8 @@ PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f
 }
 
 // the parameter block of an instantiation, and its counts (none without MIS)
-template <bool MIS, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false>
-using PtIndirectArgs = std::conditional_t<ENV, PtIndirectEnvParams, std::conditional_t<RIS, PtIndirectRisParams, std::conditional_t<LIST, PtIndirectListParams, std::conditional_t<RR, PtIndirectRrParams, std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>>>>>;
+template <bool MIS, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false, bool RAYS = false>
+using PtIndirectArgs = std::conditional_t<RAYS, PtIndirectRaysParams, std::conditional_t<ENV, PtIndirectEnvParams, std::conditional_t<RIS, PtIndirectRisParams, std::conditional_t<LIST, PtIndirectListParams, std::conditional_t<RR, PtIndirectRrParams, std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>>>>>>;
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectParams&) { return nullptr; }
 PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectMisParams& I) { return I.counts; }
 PTK_DEV const uint64_t* pt_light_cdf(const PtIndirectParams&) { return nullptr; }
@@ -4423,6 +4423,20 @@ PTK_DEV void pt_list_item_begin(const PtIndirectListParams& I, unsigned item, un
     pt_generate_lens_ray((int)x, (int)grow, P.inv_width, P.inv_height, P.aspect, I.d.cam, seed, o, d);
 }
 
+// the start of item `item` of a RAYS launch (PtIndirectRaysParams; pt_radiance_rays): sample s = item / rays of ray r = item % rays.  Its
+// seed is the renderers' gid + pt_hash_u32(frame) with gid = first_ray + r and frame = frame0 + s, in uint32; its primary ray is the
+// record's, loaded and normalised as a query's (pt_query_load: two 16-byte vector loads per lane, consecutive lanes consecutive 32-byte
+// records -- 2 KiB contiguous per wave).  No uniform is drawn, and tmax and reserved are loaded with their float4 but not read
+PTK_DEV void pt_ray_item_begin(const PtIndirectRaysParams& I, unsigned item, uint32_t& seed, f3& o, f3& d)
+{
+    const unsigned s = item / I.d.npix;
+    const unsigned r = item - s * I.d.npix;
+    seed = (I.first_ray + r) + pt_hash_u32((uint32_t)I.d.frame0 + s);
+    const PtQueryRay q = pt_query_load(I.rays, r);
+    o = q.o;
+    d = q.d;
+}
+
 // Brute force with Russian roulette (pt_render_indirect_rr): a NEW kernel beside pt_indirect_kernel, which stays as it is.  Roulette
 // shortens the average path, hardly the longest of 64, so in a kernel that walks 64 samples in lock step it would only empty the exec
 // mask.  Here a wave owns a contiguous RUN of PT_RR_RUN items, [run0, end), and REFILLS: at the top of every iteration the lanes whose
@@ -4434,6 +4448,9 @@ PTK_DEV void pt_list_item_begin(const PtIndirectListParams& I, unsigned item, un
 // exhausted), and every live lane either ends its path in it or raises its bounce, which is below B; every refill raises `next`,
 // which is at most `end`.  So a wave runs at most PT_RR_RUN * B iterations.  No spin, no persistent grid.
 // LIST (pt_render_indirect_pixels): the items are frames of a list of pixels; only the sample's start differs (pt_list_item_begin)
+// RAYS (pt_radiance_rays; neither LIST, RIS nor ENV): the items are samples of the caller's rays; only the sample's start differs
+// (pt_ray_item_begin), the block is PtIndirectRaysParams.  No pin: the compiler holds every form at its parent's waves per SIMD
+// (profiles/radiance/kernel_resources.txt)
 // RIS (pt_render_indirect_ris, pt_render_indirect_pixels_ris; POWER only): the light sample is pt_ris_light's -- the candidates of the
 // wave's lanes in step, then the one shadow search, none when no lane holds a candidate; the block is PtIndirectRisParams
 // The RIS forms carry an occupancy pin, the parents' six waves per SIMD (80 VGPRs): unpinned the compiler takes 81-82 registers for a
@@ -4453,11 +4470,12 @@ PTK_DEV void pt_list_item_begin(const PtIndirectListParams& I, unsigned item, un
 #endif
 template <bool RIS, int LDS_TABLE, bool MIS, bool ENV = false>
 inline constexpr int PT_RR_WAVES_PIN = ENV ? (LDS_TABLE == 1 ? PT_RR_ENV_LDS_WAVES : 6) : !RIS ? 0 : (LDS_TABLE == 2 && MIS) ? PT_RR_RIS_TILED_MIS_WAVES : 6;
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS, bool POWER, bool LIST = false, bool RIS = false, bool ENV = false>
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS, bool POWER, bool LIST = false, bool RIS = false, bool ENV = false, bool RAYS = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_RR_WAVES_PIN<RIS, LDS_TABLE, MIS, ENV>)))
-void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS, ENV> I)
+void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS, ENV, RAYS> I)
 {
     static_assert(POWER || !RIS, "resampling draws its candidates from the light table");
+    static_assert(!RAYS || (!LIST && !RIS && !ENV), "the caller's rays come without a list, resampling or the environment");
     static_assert(!ENV || (MIS && POWER && !LIST && !RIS), "the environment comes with MIS and the choice by power, without a list or resampling");
     static_assert(PT_RR_RUN % 64 == 0 && PT_RR_RUN >= 64, "a run is whole waves of items");
     const PtDirectParams& D = I.d;
@@ -4483,9 +4501,10 @@ void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS, ENV
         if (!alive) {
             const unsigned it = next + pt_mbcnt(dead);
             if (it < end) {
-                unsigned lp;
+                [[maybe_unused]] unsigned lp;
                 item = it;
-                if constexpr (LIST) pt_list_item_begin(I, item, lp, seed, o, d);
+                if constexpr (RAYS) pt_ray_item_begin(I, item, seed, o, d);
+                else if constexpr (LIST) pt_list_item_begin(I, item, lp, seed, o, d);
                 else pt_item_begin(P, D.cam, D.npix, D.frame0, item, lp, seed, o, d);
                 L = mk3(0.0f, 0.0f, 0.0f);
                 mask = mk3(1.0f, 1.0f, 1.0f);
@@ -4582,13 +4601,14 @@ void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS, ENV
 // emitter's record are gathered where they are used, as the materials are.
 // ENV: k goes on over K .. K + Ke - 1, the environment samples of the vertex.  S / K is folded into L before the first of them and S
 // starts again as Se: a lane's state does not grow
-template <bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false>
+template <bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false, bool RAYS = false>
 struct PtIndirectWork {
     static_assert(RR || !LIST, "a list launch is a roulette launch");
+    static_assert(!RAYS || (RR && !LIST && !RIS && !ENV), "the caller's rays come in the roulette family, without a list, resampling or the environment");
     static_assert(!RIS || (POWER && RR), "resampling comes with the light table, in the roulette family");
     static_assert(!ENV || (MIS && POWER && RR && !LIST && !RIS), "the environment comes with MIS and the light table, in the roulette family");
     static constexpr bool ANY = true;
-    const PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV>& I;
+    const PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV, RAYS>& I;
     unsigned n;
     int k;           // the current ray: -1 = the vertex's closest search, 0 .. K-1 = the shadow ray of light sample k
     int bounce;      // loop index i of traceRays (:229)
@@ -4599,9 +4619,10 @@ struct PtIndirectWork {
     float pb;        // (MIS; otherwise never touched) the pdf of the BRDF sample that made the current ray
     PTK_DEV void begin(unsigned item_)
     {
-        unsigned lp;
+        [[maybe_unused]] unsigned lp;
         item = item_;
-        if constexpr (LIST) pt_list_item_begin(I, item, lp, seed, o, d);
+        if constexpr (RAYS) pt_ray_item_begin(I, item, seed, o, d);
+        else if constexpr (LIST) pt_list_item_begin(I, item, lp, seed, o, d);
         else pt_item_begin(I.d.t, I.d.cam, I.d.npix, I.d.frame0, item, lp, seed, o, d);
         k = -1;
         bounce = 0;
@@ -4684,19 +4705,21 @@ struct PtIndirectWork {
 // scalar, the roulette's r, s and q die where they are used (profiles/roulette/kernel_resources.txt has the compiler's figures)
 // The LIST = true instantiations (pt_render_indirect_pixels) take PtIndirectListParams: the slot is loaded and dies in begin(), the
 // pointer and the offset are scalar (profiles/adaptive/kernel_resources.txt)
+// The RAYS = true instantiations (pt_radiance_rays) take PtIndirectRaysParams: the record is loaded and dies in begin(), the pointer and
+// first_ray are scalar (profiles/radiance/kernel_resources.txt)
 // The RIS = true instantiations take PtIndirectRisParams: M is scalar, the reservoir lives inside pt_ris_light (profiles/ris/kernel_resources.txt)
 // The ENV = true instantiations take PtIndirectEnvParams: the map's fields are scalar, Se shares S's registers.  They run at TWO waves:
 // at three they would spill 37 VGPRs inside next_ray (profiles/env/kernel_resources.txt has both figures)
 #ifndef PT_INDIRECT_ENV_BVH_WAVES   // (tools/kernel_resources.sh -DPT_INDIRECT_ENV_BVH_WAVES=3 reads the other choice)
 #define PT_INDIRECT_ENV_BVH_WAVES 2
 #endif
-template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false>
+template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false, bool RAYS = false>
 __global__ __launch_bounds__(PT_TRACE_THREADS)
 __attribute__((amdgpu_waves_per_eu(ENV ? PT_INDIRECT_ENV_BVH_WAVES : PT_INDIRECT_BVH_WAVES, ENV ? PT_INDIRECT_ENV_BVH_WAVES : PT_INDIRECT_BVH_WAVES)))
-void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV> I)
+void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV, RAYS> I)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtIndirectWork<MIS, POWER, RR, LIST, RIS, ENV> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
+    PtIndirectWork<MIS, POWER, RR, LIST, RIS, ENV, RAYS> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(I.d.t, W);
 }
 
@@ -5202,28 +5225,29 @@ struct PtFeatureFamily {
     template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table() { return pt_feature_kernel<DB, LDS_TABLE, QUADS>; }
 };
 // a kind of lit render (PtLitKind); RR: the table kernels are the refilling ones, a wave of which owns PT_RR_RUN items
-template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST, bool RIS = false, bool ENV = false> struct PtLitFamily {
-    using Params = std::conditional_t<INDIRECT, PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV>, PtDirectArgs<POWER, RIS, ENV>>;
+template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST, bool RIS = false, bool ENV = false, bool RAYS = false> struct PtLitFamily {
+    using Params = std::conditional_t<INDIRECT, PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV, RAYS>, PtDirectArgs<POWER, RIS, ENV>>;
     static constexpr unsigned run = RR ? PT_RR_RUN : 64;
     template <bool DB, int BIGQ> static constexpr auto bvh()
     {
-        if constexpr (INDIRECT) return pt_indirect_bvh_kernel<DB, BIGQ, MIS, POWER, RR, LIST, RIS, ENV>;
+        if constexpr (INDIRECT) return pt_indirect_bvh_kernel<DB, BIGQ, MIS, POWER, RR, LIST, RIS, ENV, RAYS>;
         else return pt_direct_bvh_kernel<DB, BIGQ, POWER, RIS, ENV>;
     }
     template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table()
     {
-        if constexpr (RR) return pt_indirect_rr_kernel<DB, LDS_TABLE, QUADS, MIS, POWER, LIST, RIS, ENV>;
+        if constexpr (RR) return pt_indirect_rr_kernel<DB, LDS_TABLE, QUADS, MIS, POWER, LIST, RIS, ENV, RAYS>;
         else if constexpr (INDIRECT) return pt_indirect_kernel<DB, LDS_TABLE, QUADS, MIS, POWER>;
         else return pt_direct_kernel<DB, LDS_TABLE, QUADS, POWER, RIS, ENV>;
     }
     // the instantiations' own block, sliced from the largest (every indirect block is a base of it; direct by power: direct's and the table)
     static Params params(const PtLitParams& a)
     {
-        if constexpr (INDIRECT && ENV) {
+        if constexpr (INDIRECT && (ENV || RAYS)) {
             Params p;
             __builtin_memset(&p, 0, sizeof p);
             static_cast<PtIndirectRrParams&>(p) = a;
-            p.env = a.env;
+            if constexpr (ENV) p.env = a.env;
+            if constexpr (RAYS) { p.rays = a.rays; p.first_ray = a.first_ray; }
             return p;
         } else if constexpr (INDIRECT) return a;
         else if constexpr (!POWER) return a.d;
@@ -5241,10 +5265,11 @@ template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST, bool RIS = fa
 };
 // fn(the family of kind k): the 14 valid kinds without ris, the 5 with it and no other -- direct illumination has neither MIS nor roulette, a
 // list is played with roulette, resampling comes by power and, indirect, in the roulette family
-template <class Fn> static auto pt_lit_family(PtLitKind k, Fn fn)
+template <class Fn> static auto pt_lit_family(PtLitKind k, bool rays, Fn fn)
 {
     auto estimator = [&](auto mis, auto power) {
         constexpr bool M = decltype(mis)::value, P = decltype(power)::value;
+        if (rays) return fn(PtLitFamily<true, M, P, true, false, false, false, true>());   // (ptk_lit_rays_valid: a roulette kind, nothing else)
         if constexpr (P) if (k.env) {
             if constexpr (!M) return fn(PtLitFamily<false, false, true, false, false, false, true>());
             else return fn(PtLitFamily<true, true, true, true, false, false, true>());
@@ -5294,19 +5319,19 @@ hipError_t ptk_render_features(const PtFeatureParams& f, int bvh_blocks, PtSearc
     return pt_launch_search(pt_choose<PtFeatureFamily>(m, f.d.t.ntri), f, f.d.t.ntri, f.d.nitems, 64u, m.bvh, bvh_blocks, s);
 }
 
-hipError_t ptk_lit(const PtLitParams& a, PtLitKind k, int bvh_blocks, PtSearchMode m, hipStream_t s)
+hipError_t ptk_lit(const PtLitParams& a, PtLitKind k, bool rays, int bvh_blocks, PtSearchMode m, hipStream_t s)
 {
     if (a.d.nitems == 0) return hipSuccess;
-    return pt_lit_family(k, [&](auto f) {
+    return pt_lit_family(k, rays, [&](auto f) {
         using F = decltype(f);
         const typename F::Params p = F::params(a);
         return pt_launch_search(pt_choose<F>(m, a.d.t.ntri), p, a.d.t.ntri, a.d.nitems, F::run, m.bvh, bvh_blocks, s);
     });
 }
 
-int ptk_lit_bvh_blocks_per_cu(PtLitKind k)
+int ptk_lit_bvh_blocks_per_cu(PtLitKind k, bool rays)
 {
-    return pt_lit_family(k, [](auto f) { return pt_blocks_per_cu(decltype(f)::template bvh<true, 3>(), ptk_trace_bvh_lds_bytes()); });
+    return pt_lit_family(k, rays, [](auto f) { return pt_blocks_per_cu(decltype(f)::template bvh<true, 3>(), ptk_trace_bvh_lds_bytes()); });
 }
 
 hipError_t ptk_light_table(const PtRawTriangle* tris, int ntri, const PtRawMaterial* mats, int nmat, const int32_t* lights, int nl,

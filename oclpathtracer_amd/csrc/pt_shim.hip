@@ -137,7 +137,7 @@ struct pt_device_s {
     uint64_t bvh_builds;        // LBVH builds so far (PT_OPT_BVH_BUILD_COUNT)
     int bvh_blocks_per_cu;
     int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query and ambient-occlusion kernels (pt_bvh_drive)
-    int lit_bvh_blocks_per_cu[PT_LIT_KIND_INDICES];   // ... and of the lit renders' LBVH kernels, each kind its own (ptk_lit_kind_index)
+    int lit_bvh_blocks_per_cu[2][PT_LIT_KIND_INDICES];   // ... and of the lit renders' LBVH kernels, each kind its own (ptk_lit_kind_index)
     unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
     unsigned int* trav_dev;  // ... as the device addresses it
     // ---- fused-render workspace: the STREAMING renderer (render_part, plan_chunks, the ring).  A render walks its frames in chunks of
@@ -368,7 +368,8 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
     for (int i = 0; i < PT_LIT_KIND_INDICES; ++i) {
         const PtLitKind k = { (i & 1) != 0, (i & 2) != 0, (i & 4) != 0, (i & 8) != 0, (i & 16) != 0, (i & 32) != 0, (i & 64) != 0 };
-        if (ptk_lit_kind_valid(k)) d->lit_bvh_blocks_per_cu[ptk_lit_kind_index(k)] = ptk_lit_bvh_blocks_per_cu(k);
+        if (ptk_lit_kind_valid(k)) d->lit_bvh_blocks_per_cu[0][ptk_lit_kind_index(k)] = ptk_lit_bvh_blocks_per_cu(k, false);
+        if (ptk_lit_rays_valid(k)) d->lit_bvh_blocks_per_cu[1][ptk_lit_kind_index(k)] = ptk_lit_bvh_blocks_per_cu(k, true);   // (row 1: the RAYS forms)
     }
     *out = d;
     return PT_OK;
@@ -1865,8 +1866,8 @@ static_assert(sizeof(pt_environment) == 16, "pt_environment layout");
 static_assert(sizeof(pt_adaptive_rule) == 32 && sizeof(pt_pixel_slot) == 8 && sizeof(pt_pixel_slot) == sizeof(uint2), "adaptive record layout");
 
 // ONE lit call, as its entry point describes it: pt_render_direct, pt_render_indirect, pt_render_indirect_mis, the two _power entry
-// points, pt_render_indirect_rr, pt_render_indirect_pixels, the three _ris and the two _env entry points each fill one and hand it to
-// render_lit -- one validation, one chunk loop
+// points, pt_render_indirect_rr, pt_render_indirect_pixels, the three _ris and the two _env entry points and pt_radiance_rays each fill
+// one and hand it to render_lit -- one validation, one chunk loop
 struct PtLitCall {
     PtLitKind kind;             // which kernels (pt_kernels.h); what follows is read as far as the kind says
     pt_buffer_t triangles, materials, lights, samples, framebuffer;
@@ -1880,6 +1881,11 @@ struct PtLitCall {
     int candidates;             // kind.ris: M (ris_args has checked it)
     pt_buffer_t env, env_cdf;   // kind.env: the map and its selection table (pt_env_table)
     pt_environment e;           //   and its block (env_args has checked it)
+    bool from_rays;             // pt_radiance_rays (ptk_lit_rays_valid(kind)): the caller's rays stand where the local pixels stand --
+    pt_buffer_t rays, moments;  //   a.frame_begin / a.frame_count are the sample range, the image fields of `a` and the camera are not
+    uint32_t num_rays;          //   read, there is no framebuffer and no fold; each chunk is followed by ptk_sample_moments into
+    uint32_t first_ray;         //   `moments` (may be NULL), `reset` at the first
+    int reset;
     const pt_camera* cam;
     pt_event_t ev;
     const char* what;           // the message for a field out of range
@@ -1905,8 +1911,9 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     int rc;
     PtLensCamera cam = reference_camera();
     if (c.cam && (rc = camera_derive(c.cam, &cam))) return rc;
-    if (!triangles || !materials || !samples || !framebuffer || (c.kind.list && !list)) return fail(PT_ERR_INVALID, "null buffer handle");
-    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer, cdf, tri_q, list, c.env, c.env_cdf })) || (rc = check_event(d, c.ev))) return rc;
+    const bool rays = c.from_rays;   // (no framebuffer: the rays stand in its place)
+    if (!triangles || !materials || !samples || (!rays && !framebuffer) || (c.kind.list && !list) || (rays && !c.rays)) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { triangles, materials, lights, light_counts, samples, framebuffer, cdf, tri_q, list, c.env, c.env_cdf, c.rays, c.moments })) || (rc = check_event(d, c.ev))) return rc;
     if (a.num_triangles < 0 || a.num_materials < 1 || a.num_lights < 0 || a.light_samples < 1 || a.light_samples > 256)
         return fail(PT_ERR_INVALID, "%s", c.what);
     if (a.num_lights >= (1 << 24)) return fail(PT_ERR_INVALID, "num_lights must stay below 2^24 (its float32 value must be exact)");
@@ -1917,11 +1924,16 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     if ((uint64_t)a.num_triangles * 64u > 0xffffffffull || (uint64_t)a.num_materials * 64u > 0xffffffffull)
         return fail(PT_ERR_INVALID, "a scene has fewer than 2^26 triangles and 2^26 materials");
     uint64_t npix64;
-    if ((rc = check_image(c.what, a.width, a.height, a.frame_begin, a.frame_count, a.stripe_rows, a.n_ranks, a.rank, npix64)))
+    if (rays) {   // the ids first_ray .. first_ray + n - 1 and the samples' numbers are the renderers' gid and frame: below 2^31
+        if (a.frame_begin < 0 || a.frame_count < 0) return fail(PT_ERR_INVALID, "%s", c.what);
+        if ((uint64_t)c.first_ray + c.num_rays > 0x7fffffffull) return fail(PT_ERR_INVALID, "first_ray + num_rays exceeds 2^31 - 1");
+        if ((long long)a.frame_begin + a.frame_count > 0x7fffffffLL) return fail(PT_ERR_INVALID, "sample_begin + sample_count exceeds 2^31 - 1");
+        npix64 = c.num_rays;
+    } else if ((rc = check_image(c.what, a.width, a.height, a.frame_begin, a.frame_count, a.stripe_rows, a.n_ranks, a.rank, npix64)))
         return rc;
     const uint32_t npix = (uint32_t)npix64;
     if (c.kind.list && c.num_listed > npix) return fail(PT_ERR_INVALID, "%u pixels listed, the local image has %u", c.num_listed, npix);
-    const uint32_t wpix = c.kind.list ? c.num_listed : npix;   // the pixels of one frame of the workspace
+    const uint32_t wpix = c.kind.list ? c.num_listed : npix;   // the pixels (the rays) of one frame of the workspace
     const size_t frame_bytes = (size_t)wpix * 12;
     // the spans, group by group: what every kind uses; the counts; the table; the list.  With no lights none of the light buffers is
     // read.  The workspace must hold one frame, and ALL of it must lie apart from the rest: a chunk may fill it
@@ -1939,6 +1951,14 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     if ((rc = span_fits(N)) || (rc = span_aligned(N)) || (rc = spans_apart({ N, W, F, L }))) return rc;
     if ((rc = span_fits(Q)) || (rc = span_fits(T)) || (rc = span_aligned(Q)) || (T.bytes && (rc = span_aligned(T))) || (rc = spans_apart({ Q, T, W, F, L, N }))) return rc;
     if ((rc = span_fits(P)) || (rc = span_aligned(P)) || (rc = spans_apart({ P, W, F }))) return rc;
+    // the rays and the moments (from_rays).  Without moments nothing consumes a chunk before the next overwrites it: the workspace
+    // must then hold every sample of the call
+    const PtSpan Y = { rays ? c.rays : nullptr, (size_t)wpix * sizeof(pt_ray), 16, "the ray buffer" },
+                 Z = { rays ? c.moments : nullptr, (size_t)wpix * sizeof(pt_pixel_moments), 8, "the moment buffer" };
+    if ((rc = span_fits(Y)) || (rc = span_fits(Z))) return rc;
+    if (rays && !c.moments && frame_bytes && (size_t)a.frame_count > samples->bytes / frame_bytes)   // (a quotient: the product may not fit a size_t)
+        return fail(PT_ERR_RANGE, "the sample workspace holds %zu bytes, %d samples of %u rays without moments need more", samples->bytes, a.frame_count, wpix);
+    if ((rc = span_aligned(Y)) || (rc = span_aligned(Z)) || (rc = spans_apart({ Y, Z, W }, { L, N, Q, T }))) return rc;
     // the map and its table (kind.env): read only, so they must lie apart from what is written; the table is not read when Ke = 0
     const size_t texels = c.kind.env ? (size_t)c.e.size * (size_t)c.e.size : 0;
     const PtSpan E = { c.kind.env ? c.env : nullptr, texels * sizeof(float4), 16, "the environment map" },
@@ -1968,7 +1988,7 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     ip.cap = c.rr.max_survival;
     PtDirectParams& p = ip.d;
     search_fields(d, search, p.t);   // (an empty scene: the brute-force form over zero triangles, every sample the background)
-    image_geometry(p.t, a.width, a.height, a.stripe_rows, a.n_ranks, a.rank, npix);
+    if (!rays) image_geometry(p.t, a.width, a.height, a.stripe_rows, a.n_ranks, a.rank, npix);   // (a ray launch reads no image field)
     p.t.mats = (const PtRawMaterial*)materials->dptr;
     p.t.nmat = a.num_materials;
     p.cam = cam;
@@ -1981,10 +2001,12 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     ip.cdf = Q.buf ? (const uint64_t*)cdf->dptr : nullptr;
     ip.tri_q = T.buf ? (const uint32_t*)tri_q->dptr : nullptr;
     ip.slots = P.buf ? reinterpret_cast<const uint2*>(static_cast<const char*>(list->dptr) + 16) : nullptr;
+    ip.rays = Y.buf ? (const float4*)c.rays->dptr : nullptr;
+    ip.first_ray = c.first_ray;
     PtFoldParams fp;
     memset(&fp, 0, sizeof fp);
     fp.rad = p.samples;
-    fp.fb = (float4*)framebuffer->dptr;
+    fp.fb = framebuffer ? (float4*)framebuffer->dptr : nullptr;
     fp.npix_local = npix;
     PtFoldListParams lp;
     memset(&lp, 0, sizeof lp);
@@ -1994,7 +2016,7 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     lp.num_listed = wpix;
     lp.npix_local = npix;
     // each kind's LBVH kernel on its own grid (pt_kernels.h)
-    const int bvh_blocks = !search.mode.bvh ? 0 : d->prop.multiProcessorCount * d->lit_bvh_blocks_per_cu[ptk_lit_kind_index(c.kind)];
+    const int bvh_blocks = !search.mode.bvh ? 0 : d->prop.multiProcessorCount * d->lit_bvh_blocks_per_cu[rays ? 1 : 0][ptk_lit_kind_index(c.kind)];
     // whole frames per chunk: what the workspace holds, fewer than 2^31 samples per launch; a launch, then its fold
     const int64_t per_chunk = (int64_t)std::min<uint64_t>(samples->bytes / frame_bytes, 0x7fffffffu / wpix);
     for (int64_t done = 0; done < a.frame_count; done += per_chunk) {
@@ -2004,11 +2026,16 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
         fp.frame_count = lp.frame_count = nf;
         // a list: every slot continues from its own frame -- the call's offset, then the frames of the chunks before (no other kind's block holds it)
         ip.frame_off = lp.frame_off = (uint32_t)p.frame0;
-        HIP_TRY(ptk_lit(ip, c.kind, bvh_blocks, search.mode, d->stream));
-        HIP_TRY(c.kind.list ? ptk_fold_list(lp, d->stream) : ptk_fold(fp, d->stream));
+        HIP_TRY(ptk_lit(ip, c.kind, rays, bvh_blocks, search.mode, d->stream));
+        // the rays: no fold -- the chunk's moments, in ascending sample order, from zeros at the call's first chunk when it says so
+        if (rays) {
+            if (c.moments) HIP_TRY(ptk_sample_moments(p.samples, (PtPixelMoments*)c.moments->dptr, wpix, nf, c.reset != 0 && done == 0, d->stream));
+        } else
+            HIP_TRY(c.kind.list ? ptk_fold_list(lp, d->stream) : ptk_fold(fp, d->stream));
     }
     samples->version++;
-    framebuffer->version++;
+    if (framebuffer) framebuffer->version++;
+    if (rays && c.moments) c.moments->version++;
     return event_end(d, c.ev);
 }
 
@@ -2198,6 +2225,41 @@ extern "C" int pt_render_indirect_pixels(pt_device_t d, pt_buffer_t triangles, p
     c.list = list; c.num_listed = num_listed;
     int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
     if (rc || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
+    return render_lit(d, c);
+}
+
+// ---- radiance queries (include/pt_shim.h) ------------------------------------------------------------------------------------------
+static_assert(sizeof(pt_radiance_params) == 64, "pt_radiance_params layout");
+
+// pt_render_indirect_rr's call with the caller's rays in place of the image: the ray count stands where the local pixels stand and
+// the sample range where the frames stand (render_lit, from_rays)
+extern "C" int pt_radiance_rays(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, int mis,
+                                pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t rays, pt_buffer_t samples,
+                                pt_buffer_t moments, const pt_radiance_params* params, const pt_roulette* roulette, pt_event_t ev)
+{
+    PtLitCall c = lit_call({ true, mis != 0, cdf || tri_q, true, false, false }, triangles, materials, lights, samples, nullptr, nullptr, ev);
+    c.from_rays = true;
+    c.what = "invalid radiance-query parameters";
+    c.light_counts = mis ? light_counts : nullptr;
+    c.cdf = cdf; c.tri_q = tri_q;
+    c.rays = rays; c.moments = moments;
+    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
+    const pt_radiance_params b = *params;
+    pt_indirect_params ib;   // the fields roulette_args and the parents' checks read
+    memset(&ib, 0, sizeof ib);
+    ib.num_lights = b.num_lights;
+    int rc = roulette_args(mis, roulette, cdf, tri_q, &ib, c);
+    if (rc || (rc = use_device(d))) return rc;
+    if (b.max_bounces < 1 || b.max_bounces > 65535) return fail(PT_ERR_INVALID, "max_bounces must lie in 1..65535");
+    for (int i = 0; i < 6; ++i)
+        if (b.reserved[i] != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    pt_direct_params& a = c.a;   // (zeros: lit_call; the image fields stay zero and are not read)
+    a.frame_begin = b.sample_begin; a.frame_count = b.sample_count;
+    a.num_triangles = b.num_triangles; a.num_materials = b.num_materials; a.num_lights = b.num_lights;
+    a.light_samples = b.light_samples;
+    c.max_bounces = b.max_bounces;
+    c.num_rays = b.num_rays; c.first_ray = b.first_ray;
+    c.reset = b.reset;
     return render_lit(d, c);
 }
 

@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only Features | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]]] [--noise] [--lens R[,F]]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only Features | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]] | --only RadianceRays [--mis] [--lights power] [--roulette R[,cap]]] [--noise] [--lens R[,F]]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <algorithm>
 #include <chrono>
@@ -736,6 +736,92 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
     }
 }
 
+// RadianceRays (not a case of the reference's): path-traced radiance along rays of the caller's through pt_radiance_rays.  The rays are
+// pt_camera_rays' of frame 0 at dim x dim; every ray takes --frames samples at 16 bounces and K = 1, under --mis, --lights power and
+// --roulette R[,cap] as IndirectIllumination takes them, in chunks of what a 64 MiB workspace holds, with moments.  Prints the mean
+// radiance over all rays and the summary of pt_moments_resolve.  Run only when asked for (--only).
+static void test_RadianceRays(DeviceTest& f, const Options& o)
+{
+    Device* m_d = f.m_d;
+    std::vector<Triangle> triangles;
+    std::vector<Material> materials;
+    if (!loadModel(o.scene.c_str(), triangles, materials)) {
+        std::printf("Error loading model !!\n");
+        ++g_failures;
+        return;
+    }
+    std::vector<int> lights;
+    for (size_t i = 0; i < triangles.size(); i++) {
+        const int id = triangles[i].id;
+        if (id < 0 || (size_t)id >= materials.size()) continue;
+        const Material& m = materials[(size_t)id];
+        if (m.emissive.x > 0.0f || m.emissive.y > 0.0f || m.emissive.z > 0.0f) lights.push_back((int)i);
+    }
+    const int dimension = o.dim;
+    const size_t n = (size_t)dimension * dimension;
+    const size_t hold = std::max<size_t>(1, std::min<size_t>((size_t)std::max(o.frames, 1), ((size_t)64 << 20) / (n * 12)));
+    Buffer<Triangle> tBuffer(m_d, triangles.size());
+    Buffer<Material> mBuffer(m_d, materials.size());
+    Buffer<int> lBuffer(m_d, lights.size() ? lights.size() : 1);
+    Buffer<int> cBuffer(m_d, triangles.size() ? triangles.size() : 1);
+    Buffer<unsigned long long> cdf(m_d, pt_light_table_bytes((int)lights.size()) / 8);
+    Buffer<unsigned int> triq(m_d, triangles.size() ? triangles.size() : 1);
+    Buffer<pt_ray> rays(m_d, n);
+    Buffer<float> samples(m_d, 3 * n * hold);
+    Buffer<pt_pixel_moments> moments(m_d, n);
+    Buffer<unsigned char> summary(m_d, pt_moments_summary_bytes((uint32_t)n));
+    tBuffer.write(triangles.data(), triangles.size());
+    mBuffer.write(materials.data(), materials.size());
+    if (!lights.empty()) lBuffer.write(lights.data(), lights.size());
+    const int ntri = (int)triangles.size(), nl = (int)lights.size();
+    pt_buffer_t lh = nl ? lBuffer.m_handle : 0;
+    if (o.mis) IASSERT(pt_light_counts(m_d->m_handle, lh, nl, ntri, cBuffer.m_handle, 0) == PT_OK);
+    if (o.power) IASSERT(pt_light_table(m_d->m_handle, tBuffer.m_handle, ntri, mBuffer.m_handle, (int)materials.size(), lh, nl, cdf.m_handle, triq.m_handle, 0) == PT_OK);
+    IASSERT(pt_camera_rays(m_d->m_handle, 0, dimension, dimension, 0, rays.m_handle, 0) == PT_OK);
+    pt_radiance_params p;
+    std::memset(&p, 0, sizeof p);
+    p.num_rays = (uint32_t)n;
+    p.sample_count = o.frames;
+    p.num_triangles = ntri; p.num_materials = (int)materials.size(); p.num_lights = nl;
+    p.light_samples = 1;
+    p.max_bounces = 16;
+    p.reset = 1;
+    pt_roulette roulette;
+    std::memset(&roulette, 0, sizeof roulette);
+    roulette.first_bounce = o.rrFirst > 0 ? o.rrFirst : 65535;   // (no roulette: a first bounce no path reaches)
+    roulette.max_survival = o.rrFirst > 0 ? o.rrCap : 1.0f;
+    auto t0 = std::chrono::steady_clock::now();
+    IASSERT(pt_radiance_rays(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, lh, o.mis ? 1 : 0, o.mis ? cBuffer.m_handle : 0,
+                             o.power ? cdf.m_handle : 0, o.power ? triq.m_handle : 0, rays.m_handle, samples.m_handle, moments.m_handle, &p,
+                             &roulette, 0) == PT_OK);
+    std::vector<pt_pixel_moments> hm(n);
+    std::memset(hm.data(), 0, n * sizeof(pt_pixel_moments));
+    pt_noise_summary ns;
+    std::memset(&ns, 0, sizeof ns);
+    if (o.frames > 0) {
+        IASSERT(pt_moments_resolve(m_d->m_handle, moments.m_handle, (uint32_t)n, 0, summary.m_handle, 0) == PT_OK);
+        moments.read(hm.data(), n);
+        summary.read((unsigned char*)&ns, sizeof ns);
+    }
+    DeviceUtils::waitForCompletion(m_d);
+    double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    double sum[3] = { 0.0, 0.0, 0.0 }, count = 0.0;
+    for (size_t i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++) sum[k] += hm[i].sum[k];
+        count += hm[i].n;
+    }
+    char rrText[64] = "";
+    if (o.rrFirst > 0) std::snprintf(rrText, sizeof rrText, " (roulette from %d, at most %g)", o.rrFirst, (double)o.rrCap);
+    std::printf("RadianceRays%s%s%s: %zu rays x %d samples, 16 bounces, K = 1, %d lights in %.3f s\n", o.mis ? " (MIS)" : "",
+                o.power ? " (lights by power)" : "", rrText, n, o.frames, nl, secs);
+    std::printf("mean radiance %.9g %.9g %.9g over %.0f finite samples\n", count > 0 ? sum[0] / count : 0.0, count > 0 ? sum[1] / count : 0.0,
+                count > 0 ? sum[2] / count : 0.0, count);
+    std::printf("noise: variance_per_sample %.17g relative_error %.17g pixels %llu samples %llu rejected %llu\n",
+                ns.var_sum / (3.0 * (double)ns.pixels), std::sqrt(ns.se2_sum / ns.mean2_sum), (unsigned long long)ns.pixels,
+                (unsigned long long)ns.samples, (unsigned long long)ns.rejected);
+    IASSERT((double)ns.samples + (double)ns.rejected == (double)n * o.frames);
+}
+
 int main(int argc, char** argv)
 {
     Options o;
@@ -813,10 +899,11 @@ int main(int argc, char** argv)
     if (o.env && o.only == "IndirectIllumination" && !o.mis) { std::fprintf(stderr, "--env with IndirectIllumination needs --mis\n"); return 2; }
     struct { const char* name; int kind; } tests[] = { { "initialize", 0 }, { "deviceInfo", 1 }, { "MemoryAllocation", 2 }, { "writeRead", 3 },
                                                        { "getHostPtr", 4 }, { "kernelExecution", 5 }, { "RayCast", 6 },
-                                                       { "AmbientOcclusion", 7 }, { "DirectIllumination", 8 }, { "IndirectIllumination", 9 }, { "Features", 10 } };
+                                                       { "AmbientOcclusion", 7 }, { "DirectIllumination", 8 }, { "IndirectIllumination", 9 }, { "Features", 10 },
+                                                       { "RadianceRays", 11 } };
     for (auto& t : tests) {
         if (!o.only.empty() && o.only != t.name) continue;
-        if (o.only.empty() && t.kind >= 7) continue;   // AmbientOcclusion, DirectIllumination, IndirectIllumination and Features run only when asked for: the default run is RaytraceTest's seven cases
+        if (o.only.empty() && t.kind >= 7) continue;   // AmbientOcclusion, DirectIllumination, IndirectIllumination, Features and RadianceRays run only when asked for: the default run is RaytraceTest's seven cases
         std::printf("[ RUN      ] DeviceTest.%s\n", t.name);
         int before = g_failures;
         DeviceTest f;
@@ -832,6 +919,7 @@ int main(int argc, char** argv)
         case 8: test_Illumination(f, o, 0); break;
         case 9: test_Illumination(f, o, 16); break;
         case 10: test_Features(f, o); break;
+        case 11: test_RadianceRays(f, o); break;
         default: break;
         }
         f.TearDown();

@@ -57,6 +57,69 @@ def _check_lights(lights, num_triangles: int) -> np.ndarray:
     return np.ascontiguousarray(a, np.int32)
 
 
+class SceneBuffers:
+    """The scene of a lit call on ``dev``: the triangle and material buffers, the light list and its buffer -- what ``DirectRenderer``,
+    ``IndirectRenderer`` and ``radiance.RadianceCaster`` are built on.  Everything about the scene that can be refused is refused
+    before the first device call.  ``own_tbuf`` / ``own_mbuf`` say which of the two buffers were made here; the light buffer always is."""
+
+    def __init__(self, dev: adl.Device, triangles, materials, lights, num_triangles: Optional[int], num_materials: Optional[int]):
+        t_host = isinstance(triangles, np.ndarray)
+        m_host = isinstance(materials, np.ndarray)
+        if not (t_host or isinstance(triangles, adl.Buffer)) or (t_host and triangles.dtype != scene.TRIANGLE_DTYPE):
+            raise TypeError("triangles must be a scene.TRIANGLE_DTYPE array or an adl.Buffer")
+        if not (m_host or isinstance(materials, adl.Buffer)) or (m_host and materials.dtype != scene.MATERIAL_DTYPE):
+            raise TypeError("materials must be a scene.MATERIAL_DTYPE array or an adl.Buffer")
+        if not t_host and num_triangles is None:
+            raise ValueError("num_triangles is required with an adl.Buffer of triangles")
+        if not m_host and num_materials is None:
+            raise ValueError("num_materials is required with an adl.Buffer of materials")
+        ntri = len(triangles) if t_host else int(num_triangles)
+        nmat = len(materials) if m_host else int(num_materials)
+        if ntri < 0 or nmat < 1:
+            raise ValueError("a scene needs num_triangles >= 0 and at least one material")
+        if lights is None:
+            if not (t_host and m_host):
+                raise ValueError("lights must be given with adl.Buffers of triangles or materials (scene.emitters derives them)")
+            lights = scene.emitters(triangles, materials)
+        self.lights = _check_lights(lights, ntri)
+        self.num_materials = nmat
+
+        self.tbuf, self.num_triangles, self.own_tbuf = scene.triangle_buffer(dev, triangles, num_triangles)
+        self.own_mbuf = False
+        if m_host:
+            self.mbuf, self.own_mbuf = adl.Buffer(dev, nmat, scene.MATERIAL_DTYPE), True
+            self.mbuf.write(np.ascontiguousarray(materials), nmat)
+        else:
+            self.mbuf = materials
+        self.lbuf = adl.Buffer(dev, max(len(self.lights), 1), np.int32)
+        if len(self.lights):
+            self.lbuf.write(self.lights, len(self.lights))
+
+
+def light_table(lib, dev: adl.Device, tbuf, num_triangles: int, mbuf, num_materials: int, lights_h, num_lights: int):
+    """(cdf, tri_q): the selection table of a light list, built once on the device (pt_light_table) into two new buffers"""
+    cdf = adl.Buffer(dev, lib.pt_light_table_bytes(num_lights) // 8, np.uint64)
+    tri_q = adl.Buffer(dev, max(num_triangles, 1), np.uint32)
+    try:
+        shim.check(lib.pt_light_table(dev._h, tbuf._h, num_triangles, mbuf._h, num_materials, lights_h, num_lights, cdf._h, tri_q._h, None))
+    except Exception:
+        cdf.release()
+        tri_q.release()
+        raise
+    return cdf, tri_q
+
+
+def light_counts(lib, dev: adl.Device, lights_h, num_lights: int, num_triangles: int):
+    """the list entries per triangle, counted once on the device (pt_light_counts) into a new buffer"""
+    counts = adl.Buffer(dev, max(num_triangles, 1), np.int32)
+    try:
+        shim.check(lib.pt_light_counts(dev._h, lights_h, num_lights, num_triangles, counts._h, None))
+    except Exception:
+        counts.release()
+        raise
+    return counts
+
+
 class DirectRenderer:
     """Direct illumination of a ``width`` x ``height`` image of ``triangles`` with ``materials`` on ``dev``.
 
@@ -107,37 +170,11 @@ class DirectRenderer:
         self._set_camera(camera)
         self.tbuf = self.mbuf = self.lbuf = self.samples = self.fb = None
         self._own_tbuf = self._own_mbuf = False
-        # everything about the scene that can be refused is refused before the first device call
-        t_host = isinstance(triangles, np.ndarray)
-        m_host = isinstance(materials, np.ndarray)
-        if not (t_host or isinstance(triangles, adl.Buffer)) or (t_host and triangles.dtype != scene.TRIANGLE_DTYPE):
-            raise TypeError("triangles must be a scene.TRIANGLE_DTYPE array or an adl.Buffer")
-        if not (m_host or isinstance(materials, adl.Buffer)) or (m_host and materials.dtype != scene.MATERIAL_DTYPE):
-            raise TypeError("materials must be a scene.MATERIAL_DTYPE array or an adl.Buffer")
-        if not t_host and num_triangles is None:
-            raise ValueError("num_triangles is required with an adl.Buffer of triangles")
-        if not m_host and num_materials is None:
-            raise ValueError("num_materials is required with an adl.Buffer of materials")
-        ntri = len(triangles) if t_host else int(num_triangles)
-        nmat = len(materials) if m_host else int(num_materials)
-        if ntri < 0 or nmat < 1:
-            raise ValueError("a scene needs num_triangles >= 0 and at least one material")
-        if lights is None:
-            if not (t_host and m_host):
-                raise ValueError("lights must be given with adl.Buffers of triangles or materials (scene.emitters derives them)")
-            lights = scene.emitters(triangles, materials)
-        self.lights = _check_lights(lights, ntri)
-        self.num_materials = nmat
-
-        self.tbuf, self.num_triangles, self._own_tbuf = scene.triangle_buffer(dev, triangles, num_triangles)
-        if m_host:
-            self.mbuf, self._own_mbuf = adl.Buffer(dev, nmat, scene.MATERIAL_DTYPE), True
-            self.mbuf.write(np.ascontiguousarray(materials), nmat)
-        else:
-            self.mbuf = materials
-        self.lbuf = adl.Buffer(dev, max(len(self.lights), 1), np.int32)
-        if len(self.lights):
-            self.lbuf.write(self.lights, len(self.lights))
+        # everything about the scene that can be refused is refused before the first device call (SceneBuffers)
+        s = SceneBuffers(dev, triangles, materials, lights, num_triangles, num_materials)
+        self.lights, self.num_triangles, self.num_materials = s.lights, s.num_triangles, s.num_materials
+        self.tbuf, self.mbuf, self.lbuf = s.tbuf, s.mbuf, s.lbuf
+        self._own_tbuf, self._own_mbuf = s.own_tbuf, s.own_mbuf
         n = max(self.local_pixels, 1)
         if chunk_frames is None:
             chunk_frames = max(1, min(64, _WORKSPACE_BYTES // (12 * n)))
@@ -158,11 +195,8 @@ class DirectRenderer:
 
     def _build_table(self) -> None:
         """the selection table of the list, built once on the device (pt_light_table) into buffers of this renderer's"""
-        nl = len(self.lights)
-        self.cdf = adl.Buffer(self.dev, self._lib.pt_light_table_bytes(nl) // 8, np.uint64)
-        self.tri_q = adl.Buffer(self.dev, max(self.num_triangles, 1), np.uint32)
-        shim.check(self._lib.pt_light_table(self.dev._h, self.tbuf._h, self.num_triangles, self.mbuf._h, self.num_materials,
-                                            self._lights_h(), nl, self.cdf._h, self.tri_q._h, None))
+        self.cdf, self.tri_q = light_table(self._lib, self.dev, self.tbuf, self.num_triangles, self.mbuf, self.num_materials,
+                                           self._lights_h(), len(self.lights))
 
     def set_candidates(self, candidates: int, through_ris: bool = False) -> None:
         """``candidates`` (1 .. 32) per light sample from the next render on; more than 1 needs ``light_choice="power"``.  The image of

@@ -50,7 +50,7 @@ import math
 import numpy as np
 
 from . import adl, shim
-from .direct import DirectRenderer, _handle
+from .direct import DirectRenderer, _handle, light_counts
 from .render import BOUNCES
 
 
@@ -108,8 +108,7 @@ class IndirectRenderer(DirectRenderer):
         super().__init__(dev, triangles, materials, width, height, **kw)
         if self.mis:
             try:
-                self.counts = adl.Buffer(dev, max(self.num_triangles, 1), np.int32)
-                shim.check(self._lib.pt_light_counts(dev._h, self._lights_h(), len(self.lights), self.num_triangles, self.counts._h, None))
+                self.counts = light_counts(self._lib, dev, self._lights_h(), len(self.lights), self.num_triangles)
             except Exception:
                 self.release()
                 raise
@@ -236,6 +235,18 @@ class IndirectRenderer(DirectRenderer):
                 done += k
             rendered += listed * fpp
         return AdaptiveResult(tuple(passes), rendered, self.sample_counts())
+
+    def radiance_caster(self, *, workspace_bytes=None):
+        """A ``radiance.RadianceCaster`` on this renderer's own scene, light list, counts and table -- one prepared scene, one LBVH --
+        with its ``light_samples``, ``max_bounces``, ``mis``, ``light_choice`` and ``roulette``.  Radiance queries take neither
+        resampling nor an environment.  Release the caster before the renderer."""
+        from .radiance import RadianceCaster, _WORKSPACE_BYTES
+
+        if self._ris is not None or self._env is not None:
+            raise ValueError("radiance queries take neither resampling (candidates) nor an environment")
+        return RadianceCaster(self.dev, self.tbuf, self.mbuf, light_samples=self.light_samples, max_bounces=self.max_bounces, mis=self.mis,
+                              light_choice=self.light_choice, roulette=self.roulette,
+                              workspace_bytes=_WORKSPACE_BYTES if workspace_bytes is None else workspace_bytes, _share=self)
 
     def release(self) -> None:
         for name in ("counts", "pixel_list"):

@@ -190,6 +190,23 @@ class Environment(_c.Structure):
     _fields_ = [("size", _c.c_int32), ("env_samples", _c.c_int32), ("reserved", _c.c_int32 * 2)]
 
 
+class RadianceParams(_c.Structure):
+    """pt_radiance_params (64 bytes): the rays (their number, the id of the first), the sample range of every ray, the scene's counts
+    and K as IndirectParams, the path's depth, reset != 0 = the moments start from zeros; reserved must be 0."""
+
+    _fields_ = [
+        ("num_rays", _c.c_uint32), ("first_ray", _c.c_uint32),
+        ("sample_begin", _c.c_int32), ("sample_count", _c.c_int32),
+        ("num_triangles", _c.c_int32), ("num_materials", _c.c_int32), ("num_lights", _c.c_int32),
+        ("light_samples", _c.c_int32),
+        ("max_bounces", _c.c_int32), ("reset", _c.c_int32),
+        ("reserved", _c.c_int32 * 6),
+    ]
+
+
+assert _c.sizeof(RadianceParams) == 64
+
+
 class PixelMoments(_c.Structure):
     """pt_pixel_moments (56 bytes): per channel the sum and the sum of squares of a pixel's finite samples, their number, and the
     number of samples rejected for a NaN or an infinity."""
@@ -305,6 +322,7 @@ SIGNATURES = {
                                         _c.POINTER(Camera), _H]),
     "pt_render_indirect_env": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Roulette),
                                           _c.POINTER(Environment), _c.POINTER(Camera), _H]),
+    "pt_radiance_rays": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _H, _c.POINTER(RadianceParams), _c.POINTER(Roulette), _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_bvh_snapshot": (_c.c_int, [_H, _c.POINTER(BvhInfo), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
