@@ -199,7 +199,12 @@ enum pt_option {
      * table and renders through pass 1, as the parent of this option did.  The scene's first render builds the table (about 23 ms for
      * the Cornell box) and, once per scene, waits for the device to read the prepared records back.  0 = off:
      * secondary rays run pass 1 (A/B timing, parity tests).  Identical pixels either way. */
-    PT_OPT_SECONDARY_MASKS = 12
+    PT_OPT_SECONDARY_MASKS = 12,
+    /* how a level of pt_denoise gathers its 5 x 5 taps, for A/B timing and parity tests: 1 = every lane loads its taps from global
+     * memory (coalesced across the lanes of a row at every step); 2 = at steps 1 and 2 a workgroup first stages its 32 x 8 pixels
+     * and their halo in LDS (larger steps gather as under 1: their halo dwarfs the tile); 0 (default) = the faster of the two per
+     * step as measured (profiles/denoise/rates.txt).  Identical bits under every setting. */
+    PT_OPT_DENOISE_TILE = 13
 };
 int pt_device_set_option(pt_device_t dev, int option, int64_t value);
 int64_t pt_device_get_option(pt_device_t dev, int option);
@@ -517,9 +522,9 @@ int pt_render_direct(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materia
 
 /* ---- first-hit feature buffers -------------------------------------------------------------------------------------
  * What a denoiser, a compositor or a model takes beside the noisy image: albedo, shading normal, depth / coverage and emission at
- * the first hit, per SAMPLE, over the same jittered (and, with a lens, defocused) samples the lit renders take.  The library
+ * the first hit, per SAMPLE, over the same jittered (and, with a lens, defocused) samples the lit renders take.  This call
  * neither filters nor denoises; pt_sample_moments turns each output into ordered binary64 sums, pt_moments_resolve into means and
- * variances.  A sample of pixel gid = y * width + x in frame z is steps 1 and 2 of pt_render_direct, expression for expression:
+ * variances, and pt_denoise takes the sums as the guides of its filter.  A sample of pixel gid = y * width + x in frame z is steps 1 and 2 of pt_render_direct, expression for expression:
  *  1. seed = gid + hash(z) (GenerateColors.cl:308), the renderer's primary ray (o, d) (:263-288; with the camera's lens when it has
  *     one) and its closest hit from 1e20 (:137-154).
  *  2. On a hit: p = o + d t (:127); n = the HitRecord normal (:128-130) turned to face the ray (:243: n when dot(n, d) < 0,
@@ -1102,6 +1107,71 @@ int pt_radiance_rays(pt_device_t dev, pt_buffer_t triangles, pt_buffer_t materia
                      pt_buffer_t moments /* pt_pixel_moments[num_rays]; may be NULL */,
                      const pt_radiance_params* params, const pt_roulette* roulette /* not NULL; first_bounce >= B plays none */,
                      pt_event_t ev);
+
+/* ---- the denoiser: a feature-guided a-trous filter over the moments ------------------------------------------------------
+ * An image-space filter over records the library already writes: the lit renderers' per-pixel moments of the radiance
+ * (pt_sample_moments) and the moments of pt_render_features' albedo, normal, depth and emission samples over the same frames.  No
+ * reference counterpart; no existing kernel, entry point or image changes.  The filter is the edge-avoiding a-trous wavelet with a
+ * variance-driven luminance term: `levels` passes of one 5 x 5 kernel whose taps lie 1 << i pixels apart in pass i, each tap
+ * weighted down by how far its depth, albedo, emission, normal and -- measured against the pixel's own noise -- luminance lie from
+ * the centre's.  The arithmetic below IS the contract: binary32 unless said otherwise, every operation rounded on its own (no
+ * contraction), the IEEE "/" and sqrt, sums in the stated order.  A restatement that follows it equals `out` bit for bit.
+ *
+ * PREPARE, per pixel p = y * width + x (every quotient a binary64 division, rounded once to binary32):
+ *  - colour: c[k] = (float)(n > 0 ? sum[k] / (double)n : 0) from colour[p];
+ *  - with v[k] of pt_moments_resolve's step 1 and n >= 2: var = (float)(((v[0] / n) + (v[1] / n)) + (v[2] / n)), binary64 (that
+ *    call's b: the squared standard error of the pixel's mean, summed over the channels); with n < 2: var = 0;
+ *  - a, nrm, e: the means of albedo[p], normal[p], emission[p] by the colour's rule (nrm is not renormalised);
+ *  - z = sum[1] > 0 ? (float)(sum[0] / sum[1]) : 0 from depth[p] (the mean t over the pixel's hits);
+ *  - gx = 0.5f * (z(x + 1, y) - z(x - 1, y)), gy = 0.5f * (z(x, y + 1) - z(x, y - 1)), neighbour coordinates clamped into the image.
+ * LEVEL i = 0 .. levels - 1, s = 1 << i, per pixel p = (x, y) from the level's input (c, var) -- prepare's for i = 0, the output of
+ * level i - 1 otherwise; a, nrm, e, z, gx, gy stay prepare's:
+ *  - l = (c[0] + c[1]) + c[2] (of p and of every tap);
+ *  - the variance prefilter gv = (sum of k * var_q) / (sum of k), both sums from +0 over the taps dy = -1 .. 1 (outer), dx = -1 .. 1
+ *    (inner), q = (x + dx, y + dy) (NOT scaled by s), taps outside the image skipped, k = kk[|dx|] * kk[|dy|], kk = (0.5f, 0.25f);
+ *  - den_l = sigma_l * sqrt(gv) + eps_l;
+ *  - sw, sc[0..2], sv start at +0; taps dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = (x + dx s, y + dy s) (exact integers), taps
+ *    outside the image skipped, h = kw[|dx|] * kw[|dy|], kw = (0.375f, 0.25f, 0.0625f):
+ *      the centre tap: w = h, whatever the pixel holds (so sw >= 9/64 for finite inputs);
+ *      every other tap: X = 0, then in this order
+ *        depth:    t = (gx_p * (float)(dx s)) + (gy_p * (float)(dy s));  X = X + fabs(z_p - z_q) / (sigma_z * fabs(t) + eps_z)
+ *        albedo:   d = a_p - a_q;  X = X + (((d[0] * d[0]) + (d[1] * d[1])) + (d[2] * d[2])) / sigma_a
+ *        emission: d = e_p - e_q;  X = X + (((d[0] * d[0]) + (d[1] * d[1])) + (d[2] * d[2])) / sigma_e
+ *        always:   X = X + fabs(l_p - l_q) / den_l
+ *      Y = 1.0f + X * 0.0625f;  Y = Y * Y, four times;  w = h / Y   (h / (1 + X / 16)^16 stands in for h exp(-X): no exp here)
+ *        normal:   D = ((nrm_p[0] * nrm_q[0]) + (nrm_p[1] * nrm_q[1])) + (nrm_p[2] * nrm_q[2]);  D = D > 0 ? D : 0;  D = D * D,
+ *                  normal_squarings times;  w = w * D
+ *      sw = sw + w;  sc[k] = sc[k] + w * c_q[k];  sv = sv + (w * w) * var_q;
+ *  - the level's output: c[k] = sc[k] / sw, var = sv / (sw * sw).
+ * out[p] = (c[0], c[1], c[2], var) after the last level; levels = 0 writes prepare's.  A guide that is NULL drops its term: no depth
+ * = no depth term, no albedo / emission = that term left out of X, no normal = w is not multiplied by D.  Non-finite sums give what
+ * IEEE makes of these expressions.
+ *
+ * scratch: the caller's buffer of pt_denoise_scratch_bytes(width, height) bytes (a function of width x height alone; 0 for an
+ * invalid size); its contents are the build's and unspecified -- here six binary32 float4 planes: (c, var), (nrm, z), (a, gx),
+ * (e, gy) and two for the levels to alternate between.  No guide is stored narrower than binary32.
+ * PT_OPT_DENOISE_TILE chooses how a level gathers its taps; every setting gives the same bits (the tap order is per pixel).
+ * Behaviour is pt_moments_resolve's: the handle's stream, behind work in flight, asynchronous (ev); nothing is allocated and the
+ * host waits for nothing; the versions of out and scratch are bumped.  The image is the WHOLE image: the records of a striped or
+ * multi-rank render are not one.
+ * Errors come before anything is enqueued and leave the buffers untouched: PT_ERR_INVALID for dev, colour, scratch, out or params
+ * NULL, a buffer of another device, width or height < 1, width x height > 2^31 - 1, levels or normal_squarings outside 0 .. 8, a
+ * sigma or an eps that is not finite and > 0, a reserved word not 0, a moments buffer not 8-byte aligned, out or scratch not 16-byte
+ * aligned, any two of the buffers overlapping; PT_ERR_RANGE for a buffer too small (a moments buffer: width x height x 56 bytes;
+ * out: width x height x 16; scratch: pt_denoise_scratch_bytes). */
+typedef struct pt_denoise_params {
+    int32_t width, height;        /* the WHOLE image; width x height <= 2^31 - 1, both >= 1 */
+    int32_t levels;               /* 0 .. 8 a-trous levels; level i has step 1 << i; 0 = prepare only */
+    int32_t normal_squarings;     /* 0 .. 8: the normal weight is max(dot, 0)^(2^k) by k squarings */
+    float   sigma_l, sigma_z, sigma_a, sigma_e;   /* finite, > 0 */
+    float   eps_l, eps_z;                         /* finite, > 0 */
+    int32_t reserved[6];          /* must be 0 */
+} pt_denoise_params;              /* 64 bytes */
+size_t pt_denoise_scratch_bytes(int32_t width, int32_t height);
+int pt_denoise(pt_device_t dev, pt_buffer_t colour /* pt_pixel_moments[width x height] */,
+               pt_buffer_t albedo, pt_buffer_t normal, pt_buffer_t depth, pt_buffer_t emission /* the same records; each may be NULL */,
+               pt_buffer_t scratch, pt_buffer_t out /* float4[width x height]: r, g, b, variance */,
+               const pt_denoise_params* params, pt_event_t ev);
 
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.

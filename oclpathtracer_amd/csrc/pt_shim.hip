@@ -20,6 +20,7 @@
 #include <utility>
 #include <vector>
 
+#include "pt_denoise.h"
 #include "pt_kernels.h"
 #include "pt_secmask.h"
 
@@ -108,7 +109,7 @@ struct pt_device_s {
     uint64_t used, peak;
     int live_buffers;
     uint64_t workspace;      // device bytes held by this handle for itself (every PtWs below)
-    int64_t opt_batch, opt_chunk, opt_profile, opt_quads, opt_accel, opt_tally, opt_pmask, opt_bvh_stack, opt_lanes, opt_carry, opt_smask;
+    int64_t opt_batch, opt_chunk, opt_profile, opt_quads, opt_accel, opt_tally, opt_pmask, opt_bvh_stack, opt_lanes, opt_carry, opt_smask, opt_denoise;
     pt_kernel_s kernels[KERNEL_COUNT];
     PendingFrames pending;
     // ---- the prepared scene, its filter tables and its LBVH (ensure_prep, ensure_bvh, ensure_anchor, prepare_search)
@@ -333,6 +334,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->opt_batch = 1;
     d->opt_pmask = PT_DEFAULT_PRIMARY_MASKS;
     d->opt_smask = PT_DEFAULT_SECONDARY_MASKS;
+    d->opt_denoise = PT_DENOISE_GATHER_AUTO;
     d->opt_bvh_stack = 64;
     d->opt_lanes = 2;
     d->opt_carry = 1;
@@ -603,6 +605,10 @@ extern "C" int pt_device_set_option(pt_device_t d, int option, int64_t value)
     case PT_OPT_SECONDARY_MASKS:
         d->opt_smask = value ? 1 : 0;
         return PT_OK;
+    case PT_OPT_DENOISE_TILE:
+        if (value < 0 || value > 2) return fail(PT_ERR_INVALID, "the denoiser's gather must be 0 (auto), 1 (global loads) or 2 (LDS tile at steps 1 and 2)");
+        d->opt_denoise = value;
+        return PT_OK;
     case PT_OPT_BVH_STACK_LIMIT:
         if (value < 1 || value > 64) return fail(PT_ERR_INVALID, "the LBVH stack limit must be 1..64");
         d->opt_bvh_stack = value;
@@ -634,6 +640,7 @@ extern "C" int64_t pt_device_get_option(pt_device_t d, int option)
     case PT_OPT_BVH_TALLY: return d->opt_tally;
     case PT_OPT_PRIMARY_MASKS: return d->opt_pmask;
     case PT_OPT_SECONDARY_MASKS: return d->opt_smask;
+    case PT_OPT_DENOISE_TILE: return d->opt_denoise;
     case PT_OPT_BVH_STACK_LIMIT: return d->opt_bvh_stack;
     case PT_OPT_RENDER_LANES: return d->opt_lanes;
     case PT_OPT_CHECKPOINT: return d->opt_carry;
@@ -2519,6 +2526,54 @@ extern "C" int pt_moments_resolve(pt_device_t d, pt_buffer_t moments, uint32_t n
         if (noise) noise->version++;
         if (summary) summary->version++;
     }
+    return event_end(d, ev);
+}
+
+// ---- the denoiser (include/pt_shim.h; kernels: pt_denoise.hip) -------------------------------------------------------------
+static_assert(sizeof(pt_denoise_params) == 64, "pt_denoise_params layout");
+
+extern "C" size_t pt_denoise_scratch_bytes(int32_t width, int32_t height)
+{
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height > 0x7fffffffull) return 0;
+    return (size_t)width * (size_t)height * PT_DENOISE_PLANES * sizeof(float4);
+}
+
+extern "C" int pt_denoise(pt_device_t d, pt_buffer_t colour, pt_buffer_t albedo, pt_buffer_t normal, pt_buffer_t depth, pt_buffer_t emission,
+                          pt_buffer_t scratch, pt_buffer_t out, const pt_denoise_params* params, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!colour || !scratch || !out) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { colour, albedo, normal, depth, emission, scratch, out })) || (rc = check_event(d, ev))) return rc;
+    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
+    const pt_denoise_params q = *params;
+    const size_t scratch_bytes = pt_denoise_scratch_bytes(q.width, q.height);
+    if (!scratch_bytes) return fail(PT_ERR_INVALID, "invalid image size %d x %d", q.width, q.height);
+    if (q.levels < 0 || q.levels > PT_DENOISE_MAX_LEVELS) return fail(PT_ERR_INVALID, "levels must be 0..%d", PT_DENOISE_MAX_LEVELS);
+    if (q.normal_squarings < 0 || q.normal_squarings > 8) return fail(PT_ERR_INVALID, "normal_squarings must be 0..8");
+    for (float v : { q.sigma_l, q.sigma_z, q.sigma_a, q.sigma_e, q.eps_l, q.eps_z })
+        if (!(v > 0.0f) || !std::isfinite(v)) return fail(PT_ERR_INVALID, "every sigma and eps must be finite and > 0");
+    for (int32_t r : q.reserved)
+        if (r != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    const size_t npix = (size_t)q.width * (size_t)q.height, rec = npix * sizeof(pt_pixel_moments);
+    const PtSpan C = { colour, rec, 8, "the colour moments" }, A = { albedo, rec, 8, "the albedo moments" }, N = { normal, rec, 8, "the normal moments" },
+                 Z = { depth, rec, 8, "the depth moments" }, E = { emission, rec, 8, "the emission moments" },
+                 S = { scratch, scratch_bytes, 16, "the scratch (pt_denoise_scratch_bytes)" }, O = { out, npix * 16u, 16, "the output" };
+    for (const PtSpan& s : { C, A, N, Z, E, S, O })
+        if ((rc = span_fits(s))) return rc;
+    for (const PtSpan& s : { C, A, N, Z, E, S, O })
+        if ((rc = span_aligned(s))) return rc;
+    if ((rc = spans_apart({ C, A, N, Z, E, S, O }))) return rc;
+    if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
+    PtDenoiseArgs a;
+    a.width = q.width, a.height = q.height, a.levels = q.levels, a.squarings = q.normal_squarings;
+    a.guides = (albedo ? PT_DENOISE_GUIDE_ALBEDO : 0u) | (normal ? PT_DENOISE_GUIDE_NORMAL : 0u) | (depth ? PT_DENOISE_GUIDE_DEPTH : 0u) |
+               (emission ? PT_DENOISE_GUIDE_EMISSION : 0u);
+    a.sigma_l = q.sigma_l, a.sigma_z = q.sigma_z, a.sigma_a = q.sigma_a, a.sigma_e = q.sigma_e, a.eps_l = q.eps_l, a.eps_z = q.eps_z;
+    HIP_TRY(ptk_denoise(colour->dptr, albedo ? albedo->dptr : nullptr, normal ? normal->dptr : nullptr, depth ? depth->dptr : nullptr,
+                        emission ? emission->dptr : nullptr, (float4*)scratch->dptr, (float4*)out->dptr, a, (int)d->opt_denoise, d->stream));
+    scratch->version++;
+    out->version++;
     return event_end(d, ev);
 }
 

@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only Features | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]] | --only RadianceRays [--mis] [--lights power] [--roulette R[,cap]]] [--noise] [--lens R[,F]]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only Features | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]] | --only RadianceRays [--mis] [--lights power] [--roulette R[,cap]]] [--noise [--denoise [levels]]] [--lens R[,F]]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <algorithm>
 #include <chrono>
@@ -126,6 +126,7 @@ struct Options {
     float rrCap = 0.95f;
     double adaptTol = -1.0;           // --adaptive TOL[,MIN[,MAX]]: IndirectIllumination renders MIN frames, then only the pixels still noisy (< 0 = off)
     int adaptMin = 16, adaptMax = 0;  // MAX 0 = --frames
+    int denoise = -1;                 // --denoise [levels]: with --noise, the mean variance before and after pt_denoise (< 0 = off)
     bool noise = false;               // --noise: DirectIllumination / IndirectIllumination print the image's noise summary
     float lensR = 0.0f, lensF = 0.0f; // --lens R[,F]: AmbientOcclusion / DirectIllumination / IndirectIllumination through a thin lens of radius R focused at F (0 = where the image's centre ray hits)
     std::string scene = "cornellbox.bin", outDir = ".", dump, only;
@@ -511,6 +512,9 @@ static void test_Features(DeviceTest& f, const Options& o)
 // _envsun or _envgrey.
 // With --noise either case renders in calls of at most as many frames as the workspace holds, takes the samples' moments after each
 // (pt_sample_moments) and prints one more line, after the case's own: the summary of pt_moments_resolve.  The image is the same.
+// With --noise --denoise [levels] (5 unless given) the case also renders the first-hit features of the same frames (pt_render_features,
+// their moments by pt_sample_moments), filters the radiance moments with pt_denoise under the library's default parameters and prints
+// one more line: the mean over the pixels of the variance of the pixel's value before (levels = 0) and after the filter.
 // With --adaptive TOL[,MIN[,MAX]] IndirectIllumination renders MIN frames (16 unless given) as above, then pass by pass lists the pixels
 // whose own relative standard error lies above TOL and that have fewer than MAX samples (--frames unless given) with
 // pt_adaptive_select, renders one workspace of further frames of the listed pixels with pt_render_indirect_pixels and counts them with
@@ -717,6 +721,45 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
                     ns.var_sum / (3.0 * (double)ns.pixels), std::sqrt(ns.se2_sum / ns.mean2_sum), (unsigned long long)ns.pixels,
                     (unsigned long long)ns.samples, (unsigned long long)ns.rejected);
     }
+    if (o.noise && o.denoise >= 0 && o.frames > 0) {
+        Buffer<float> fs[4] = { Buffer<float>(m_d, 3 * npix * (size_t)chunk), Buffer<float>(m_d, 3 * npix * (size_t)chunk),
+                                Buffer<float>(m_d, 3 * npix * (size_t)chunk), Buffer<float>(m_d, 3 * npix * (size_t)chunk) };
+        Buffer<pt_pixel_moments> fm[4] = { Buffer<pt_pixel_moments>(m_d, npix), Buffer<pt_pixel_moments>(m_d, npix),
+                                           Buffer<pt_pixel_moments>(m_d, npix), Buffer<pt_pixel_moments>(m_d, npix) };
+        pt_feature_params fp;
+        std::memset(&fp, 0, sizeof fp);
+        fp.width = dimension; fp.height = dimension;
+        fp.num_triangles = p.num_triangles; fp.num_materials = p.num_materials;
+        fp.stripe_rows = 1; fp.n_ranks = 1; fp.rank = 0;
+        for (int first = 0; first < o.frames; first += chunk) {
+            fp.frame_begin = first;
+            fp.frame_count = o.frames - first < chunk ? o.frames - first : chunk;
+            IASSERT(pt_render_features(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, fs[0].m_handle, fs[1].m_handle, fs[2].m_handle,
+                                       fs[3].m_handle, &fp, cam, 0) == PT_OK);
+            for (int k = 0; k < 4; k++)
+                IASSERT(pt_sample_moments(m_d->m_handle, fs[k].m_handle, fm[k].m_handle, (uint32_t)npix, fp.frame_count, first == 0, 0) == PT_OK);
+        }
+        pt_denoise_params dp;
+        std::memset(&dp, 0, sizeof dp);
+        dp.width = dimension; dp.height = dimension;
+        dp.normal_squarings = 7;
+        dp.sigma_l = 4.0f; dp.sigma_z = 1.0f; dp.sigma_a = 0.01f; dp.sigma_e = 0.01f;
+        dp.eps_l = 1e-6f; dp.eps_z = 1e-4f;
+        Buffer<unsigned char> scratch(m_d, pt_denoise_scratch_bytes(dimension, dimension));
+        Buffer<float4_t> filtered(m_d, npix);
+        std::vector<float4_t> hf(npix);
+        double meanVar[2] = { 0.0, 0.0 };
+        for (int pass = 0; pass < 2; pass++) {
+            dp.levels = pass ? o.denoise : 0;
+            IASSERT(pt_denoise(m_d->m_handle, moments.m_handle, fm[0].m_handle, fm[1].m_handle, fm[2].m_handle, fm[3].m_handle, scratch.m_handle,
+                               filtered.m_handle, &dp, 0) == PT_OK);
+            filtered.read(hf.data(), npix);
+            DeviceUtils::waitForCompletion(m_d);
+            for (size_t i = 0; i < npix; i++) meanVar[pass] += hf[i].w;
+            meanVar[pass] /= (double)npix;
+        }
+        std::printf("denoise: levels %d mean_variance unfiltered %.9g filtered %.9g\n", o.denoise, meanVar[0], meanVar[1]);
+    }
     char path[512];
     f.getFilePath(o.outDir.c_str(), bounces ? "indirectIllumination" : "directIllumination", "ppm", path, sizeof path);
     if (mis && std::strlen(path) + 5 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_mis.ppm");
@@ -838,6 +881,11 @@ int main(int argc, char** argv)
         else if (a == "--no-batch") o.batch = false;
         else if (a == "--mis") o.mis = true;
         else if (a == "--noise") o.noise = true;
+        else if (a == "--denoise") {
+            o.denoise = 5;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') o.denoise = std::atoi(argv[++i]);
+            if (o.denoise > 8) { std::fprintf(stderr, "--denoise takes 0..8 levels\n"); return 2; }
+        }
         else if (a == "--roulette") {
             const std::string v = next();
             char* end = 0;
@@ -894,6 +942,10 @@ int main(int argc, char** argv)
     if (o.env && (!o.power || o.candidates > 0 || o.adaptTol >= 0.0)) { std::fprintf(stderr, "--env needs --lights power and goes with neither --candidates nor --adaptive\n"); return 2; }
     if (o.lensR > 0.0f && o.only != "AmbientOcclusion" && o.only != "DirectIllumination" && o.only != "IndirectIllumination" && o.only != "Features") {
         std::fprintf(stderr, "--lens goes with --only AmbientOcclusion, Features, DirectIllumination or IndirectIllumination (RayCast's kernels take no lens)\n");
+        return 2;
+    }
+    if (o.denoise >= 0 && (!o.noise || o.adaptTol >= 0.0 || (o.only != "DirectIllumination" && o.only != "IndirectIllumination"))) {
+        std::fprintf(stderr, "--denoise goes with --only DirectIllumination or IndirectIllumination and --noise, not with --adaptive\n");
         return 2;
     }
     if (o.env && o.only == "IndirectIllumination" && !o.mis) { std::fprintf(stderr, "--env with IndirectIllumination needs --mis\n"); return 2; }

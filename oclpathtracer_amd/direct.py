@@ -370,6 +370,16 @@ class DirectRenderer:
                 break
         return self.frames_done
 
+    def denoiser(self, **kw):
+        """``(Denoiser, FeatureRenderer)`` for this renderer's image (``denoise.for_renderer``): the feature renderer keeps albedo,
+        normal, depth and emission, shares this renderer's scene buffers and camera and has rendered ``frames_done`` frames;
+        ``d.denoise(self.mom, f)`` filters the image (render both on by the same number of frames before the next call).  ``kw`` are
+        ``Denoiser``'s parameters.  ValueError for ``n_ranks != 1`` -- a rank's stripes are not a whole image -- and without
+        ``moments=True``.  Both objects are the caller's to release, before this renderer."""
+        from .denoise import for_renderer
+
+        return for_renderer(self, **kw)
+
     def release(self) -> None:
         for b in (self.lbuf, self.samples, self.fb, self.cdf, self.tri_q, self.mom, self.summary, self.noise_map):
             if b is not None:

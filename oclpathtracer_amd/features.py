@@ -6,7 +6,7 @@ A sample of a pixel traces the renderer's primary ray -- direct illumination's s
 records the material's albedo as stored, the normal turned to face the ray, ``(t, 1, -dot(n, d))`` and the emission; a miss records
 zeros.  The second channel of ``depth`` is the coverage weight: the mean depth over a pixel's hits is sum[0] / sum[1].  Every feature's
 samples go through ``pt_sample_moments`` on the device, frames ascending, so a pixel's sums, mean and variance are those of all its
-frames.  The library filters nothing and denoises nothing: these buffers are what an external denoiser takes.
+frames.  Nothing is filtered here: the moments are what ``denoise.Denoiser`` (``pt_denoise``) takes as the guides of its filter.
 ``include/pt_shim.h`` states every expression.  All compute is HIP in libptshim.so; nothing here has a CPU fallback.
 """
 from __future__ import annotations

@@ -19,6 +19,7 @@ PT_INFO_NAME, PT_INFO_BOARD, PT_INFO_VENDOR, PT_INFO_VERSION = range(4)
 PT_OPT_BATCH_FRAMES, PT_OPT_CHUNK_FRAMES, PT_OPT_PROFILE_RETURN_TIME = 0, 1, 2   # (3 is not assigned)
 PT_OPT_QUAD_FILTER, PT_OPT_ACCEL, PT_OPT_BVH_TALLY, PT_OPT_PRIMARY_MASKS, PT_OPT_BVH_STACK_LIMIT, PT_OPT_RENDER_LANES, PT_OPT_CHECKPOINT, PT_OPT_BVH_BUILD_COUNT = 4, 5, 6, 7, 8, 9, 10, 11
 PT_OPT_SECONDARY_MASKS = 12
+PT_OPT_DENOISE_TILE = 13   # pt_denoise: 0 = auto, 1 = global gathers, 2 = an LDS halo tile at steps 1 and 2 (identical bits)
 PT_SHIM_ABI_VERSION = 2  # include/pt_shim.h; load() refuses a library of another version
 PT_MAX_ARG_SIZE = 64
 PT_MAX_ARG_COUNT = 64
@@ -236,6 +237,21 @@ class PixelSlot(_c.Structure):
 
 PT_PIXEL_LIST_HEADER = 16
 
+
+class DenoiseParams(_c.Structure):
+    """pt_denoise_params (64 bytes): the whole image, the a-trous levels (0 .. 8; level i has step 1 << i), the squarings of the normal
+    weight (0 .. 8), the four sigmas and the two eps (finite, > 0); reserved must be 0."""
+
+    _fields_ = [
+        ("width", _c.c_int32), ("height", _c.c_int32), ("levels", _c.c_int32), ("normal_squarings", _c.c_int32),
+        ("sigma_l", _c.c_float), ("sigma_z", _c.c_float), ("sigma_a", _c.c_float), ("sigma_e", _c.c_float),
+        ("eps_l", _c.c_float), ("eps_z", _c.c_float),
+        ("reserved", _c.c_int32 * 6),
+    ]
+
+
+assert _c.sizeof(DenoiseParams) == 64
+
 # every symbol include/pt_shim.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "pt_last_error": (_c.c_char_p, []),
@@ -323,6 +339,8 @@ SIGNATURES = {
     "pt_render_indirect_env": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(IndirectParams), _c.POINTER(Roulette),
                                           _c.POINTER(Environment), _c.POINTER(Camera), _H]),
     "pt_radiance_rays": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _H, _c.POINTER(RadianceParams), _c.POINTER(Roulette), _H]),
+    "pt_denoise_scratch_bytes": (_c.c_size_t, [_c.c_int32, _c.c_int32]),
+    "pt_denoise": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(DenoiseParams), _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_bvh_snapshot": (_c.c_int, [_H, _c.POINTER(BvhInfo), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
