@@ -343,15 +343,24 @@ struct PtIndirectParams {
     PtDirectParams d;
     int32_t B;                    // max_bounces, 1 .. 65535
 };
-// pt_render_indirect_mis: the MIS = true instantiations take this block, the others PtIndirectParams as before (their code does not move)
+// THE PARAMETER BLOCKS OF THE LIT KERNELS.  A kind's bits (PtLitKind, below) select the block its instantiations take; a kernel whose
+// kind lacks a bit takes the block it took before that bit existed, at the same kernarg offsets.  The last row that applies wins:
+//   kind bit            direct block          indirect block          what the block adds
+//   (none)              PtDirectParams        PtIndirectParams        B
+//   mis                 --                    PtIndirectMisParams     counts: the list entries per triangle (pt_render_indirect_mis)
+//   power               PtDirectPowerParams   PtIndirectPowerParams   cdf, tri_q: pt_light_table's selection table (the _power entry points)
+//   rr                  --                    PtIndirectRrParams      R, cap: the roulette, whichever estimator (counts, cdf, tri_q null where not read)
+//   list                --                    PtIndirectListParams    slots, frame_off: a LIST of pixels (pt_render_indirect_pixels)
+//   ris                 PtDirectRisParams     PtIndirectRisParams     M: the candidates of a resampled light sample (the _ris entry points)
+//   env                 PtDirectEnvParams     PtIndirectEnvParams     env: the octahedral map and its table (the _env entry points)
+//   rays (bit 7)        --                    PtIndirectRaysParams    rays, first_ray: the caller's rays (pt_radiance_rays)
+// Every added field is wave-uniform: none adds per-lane state
 struct PtIndirectMisParams : PtIndirectParams {
     const int32_t* counts;        // [ntri] list entries per triangle (ptk_light_counts); not read when nl = 0
 };
 // counts[t] = the entries of lights[0 .. nl) whose index, clamped into [0, ntri), is t: one clear, one kernel of vector atomics
 hipError_t ptk_light_counts(const int32_t* lights, int nl, int ntri, int32_t* counts, hipStream_t s);
-// light choice by power (pt_render_direct_power, pt_render_indirect_power): the POWER = true instantiations take these blocks, every
-// other instantiation its block as before (their code does not move).  cdf: uint64[nl + 1], tri_q: uint32[ntri], as pt_light_table
-// writes them; neither is read when nl = 0
+// cdf: uint64[nl + 1], tri_q: uint32[ntri], as pt_light_table writes them; neither is read when nl = 0
 struct PtDirectPowerParams : PtDirectParams {
     const uint64_t* cdf;
     const uint32_t* tri_q;
@@ -360,32 +369,23 @@ struct PtIndirectPowerParams : PtIndirectMisParams {
     const uint64_t* cdf;
     const uint32_t* tri_q;
 };
-// Russian roulette (pt_render_indirect_rr): the RR = true instantiations take this block, whichever of the four estimators they are
-// (counts, cdf and tri_q are null where the estimator does not read them); every other instantiation its block as before.  R and cap
-// are wave-uniform: they add no per-lane state
 struct PtIndirectRrParams : PtIndirectPowerParams {
     int32_t R;                    // first_bounce >= 1: the roulette is played at vertex i when i + 1 >= R and i < B - 1
     float cap;                    // max_survival in (0, 1]
 };
-// adaptive sampling (pt_render_indirect_pixels): the LIST = true instantiations of the roulette kernels take this block, every other
-// instantiation its block as before.  A launch runs over a LIST of pixels: d.npix is the number of listed pixels, item = f * d.npix + j
-// is frame f of slot j, whose local pixel is min(slots[j].x, d.t.npix_local - 1) and whose frame number is (slots[j].y + frame_off + f)
-// & 0x7fffffff; d.frame0 is not read.  The sample is stored at samples[item] as before
+// A list launch: d.npix is the number of listed pixels, item = f * d.npix + j is frame f of slot j, whose local pixel is
+// min(slots[j].x, d.t.npix_local - 1) and whose frame number is (slots[j].y + frame_off + f) & 0x7fffffff; d.frame0 is not read.  The
+// sample is stored at samples[item] as before
 struct PtIndirectListParams : PtIndirectRrParams {
     const uint2* slots;           // [d.npix] pt_pixel_slot {pixel, frame}
     uint32_t frame_off;           // the frames every listed pixel has received from this call already
 };
-// resampled light sampling (pt_render_direct_ris, pt_render_indirect_ris, pt_render_indirect_pixels_ris): the RIS = true instantiations
-// take these blocks, every other instantiation its block as before (their code does not move).  M is wave-uniform: it adds no per-lane
-// state; the roulette form does not read slots and frame_off
 struct PtDirectRisParams : PtDirectPowerParams {
     int32_t M;                    // candidates per light sample, 1 .. 32
 };
-struct PtIndirectRisParams : PtIndirectListParams {
+struct PtIndirectRisParams : PtIndirectListParams {   // (the roulette form does not read slots and frame_off)
     int32_t M;
 };
-// environment lighting (pt_render_direct_env, pt_render_indirect_env): the ENV = true instantiations take these blocks, every other
-// instantiation its block as before (their code does not move).  The four fields are wave-uniform: they add no per-lane state
 struct PtEnvMap {
     const float4* texels;         // [N * N] row-major, w ignored
     const uint64_t* cdf;          // [N * N + 1] as ptk_env_table writes it; not read when Ke = 0
@@ -398,11 +398,9 @@ struct PtDirectEnvParams : PtDirectPowerParams {
 struct PtIndirectEnvParams : PtIndirectRrParams {
     PtEnvMap env;
 };
-// radiance queries (pt_radiance_rays): the RAYS = true instantiations of the roulette kernels take this block, every other
-// instantiation its block as before (their code does not move).  A launch runs over the caller's RAYS: d.npix is the number of rays n,
-// item = s * n + r is sample d.frame0 + s of ray r, whose seed is (first_ray + r) + pt_hash_u32(d.frame0 + s) and whose primary ray is
-// getRay of rays[2 r], rays[2 r + 1] (pt_query_load: tmax and reserved are not read); d.cam and the image geometry of d.t are not
-// read.  The sample is stored at samples[item] as before
+// A rays launch: d.npix is the number of rays n, item = s * n + r is sample d.frame0 + s of ray r, whose seed is (first_ray + r) +
+// pt_hash_u32(d.frame0 + s) and whose primary ray is getRay of rays[2 r], rays[2 r + 1] (pt_query_load: tmax and reserved are not
+// read); d.cam and the image geometry of d.t are not read.  The sample is stored at samples[item] as before
 struct PtIndirectRaysParams : PtIndirectRrParams {
     const float4* rays;           // [d.npix] pt_ray: origin xyz tmax | dir xyz reserved (two float4)
     uint32_t first_ray;           // the id of rays[0]
@@ -416,38 +414,44 @@ struct PtLitParams : PtIndirectRisParams {
 // A kind of lit render names its kernels.  The 14 valid values without ris:
 //   direct illumination (pt_direct_kernel, pt_direct_bvh_kernel):          indirect = mis = rr = list = 0;  power 0 / 1
 //   indirect illumination (pt_indirect_kernel, pt_indirect_bvh_kernel):    indirect = 1, rr = list = 0;     mis 0 / 1 x power 0 / 1
-//   ... with Russian roulette (pt_indirect_rr_kernel, ..._bvh_kernel RR):  indirect = rr = 1, list = 0;     mis x power
-//   ... over a list of pixels (their LIST forms):                          indirect = rr = list = 1;        mis x power
+//   ... with Russian roulette (pt_indirect_rr_kernel, ..._bvh_kernel):     indirect = rr = 1, list = 0;     mis x power
+//   ... over a list of pixels (their list forms):                          indirect = rr = list = 1;        mis x power
 // list implies rr, rr implies indirect, mis comes only with indirect
-// and the 5 with ris (the RIS = true instantiations of the same templates): direct by power; the roulette and the list kinds by power,
-// mis 0 / 1.  ris implies power, and an indirect ris kind has rr (R >= B plays no roulette)
-// and the 2 with env (the ENV = true instantiations): direct by power; the roulette kind by power with mis.  env implies power, excludes
-// ris and list, and an indirect env kind has mis and rr
+// and the 5 with ris: direct by power; the roulette and the list kinds by power, mis 0 / 1.  ris implies power, and an indirect ris kind
+// has rr (R >= B plays no roulette); and the 2 with env: direct by power; the roulette kind by power with mis.  env implies power,
+// excludes ris and list, and an indirect env kind has mis and rr
 struct PtLitKind { bool indirect, mis, power, rr, list, ris, env; };
-static inline bool ptk_lit_kind_valid(PtLitKind k)
+constexpr bool ptk_lit_kind_valid(PtLitKind k)
 {
     return (!k.list || k.rr) && (!k.rr || k.indirect) && (!k.mis || k.indirect) && (!k.ris || (k.power && k.rr == k.indirect)) &&
            (!k.env || (k.power && !k.ris && !k.list && k.rr == k.indirect && k.mis == k.indirect));
 }
-static inline int ptk_lit_kind_index(PtLitKind k)   // a table's index
-{
-    return k.indirect | k.mis << 1 | k.power << 2 | k.rr << 3 | k.list << 4 | k.ris << 5 | k.env << 6;
-}
+// a table's index, and back (the bits above PT_LIT_KIND_INDICES are not read)
+constexpr int ptk_lit_kind_index(PtLitKind k) { return k.indirect | k.mis << 1 | k.power << 2 | k.rr << 3 | k.list << 4 | k.ris << 5 | k.env << 6; }
 #define PT_LIT_KIND_INDICES 128
+constexpr PtLitKind ptk_lit_kind_of(unsigned i) { return { (i & 1) != 0, (i & 2) != 0, (i & 4) != 0, (i & 8) != 0, (i & 16) != 0, (i & 32) != 0, (i & 64) != 0 }; }
 // Radiance queries (pt_radiance_rays) are a second START of a kind's items, beside the kind: a kind names the estimator and the item map
-// of an image render and stays as it stands above; with `rays` its items are samples of the caller's rays (the RAYS = true
-// instantiations, PtIndirectRaysParams).  The 4 kinds that take rays are the roulette kinds, mis 0 / 1 x power 0 / 1 -- the shape of the
-// list kinds: rays need rr and exclude list, ris and env.  Tables over kinds gain a second row for them
-static inline bool ptk_lit_rays_valid(PtLitKind k) { return ptk_lit_kind_valid(k) && k.rr && !k.list && !k.ris && !k.env; }
-// THE launch of a lit render, whatever its kind: `a` is the largest block, and each instantiation is passed its own, sliced from it
-// (PtDirectPowerParams is made of a.d, a.cdf and a.tri_q).  LBVH (m.bvh): the kind's kernel on a persistent grid of at most bvh_blocks
-// = CUs x ptk_lit_bvh_blocks_per_cu(k) workgroups -- the occupancy of the kind's OWN <true, 3> instantiation with the trace kernel's
-// LDS: the direct kernels run at four waves per SIMD, the indirect ones at three, so ptk_query_bvh_blocks_per_cu's premise (five) holds
-// for none.  Brute force: one wave per 64 items; the roulette and list kinds one wave per PT_RR_RUN (pt_constants.h) consecutive
-// items, which refills its dead lanes from its run
-// rays: (ptk_lit_rays_valid(k)) the kind's RAYS instantiations: a.rays and a.first_ray are read, a.d.cam and the image geometry are not
-hipError_t ptk_lit(const PtLitParams& a, PtLitKind k, bool rays, int bvh_blocks, PtSearchMode m, hipStream_t s);
-int ptk_lit_bvh_blocks_per_cu(PtLitKind k, bool rays);
+// of an image render and stays as it stands above; with `rays` its items are samples of the caller's rays.  The 4 kinds that take rays
+// are the roulette kinds, mis 0 / 1 x power 0 / 1 -- the shape of the list kinds: rays need rr and exclude list, ris and env
+constexpr bool ptk_lit_rays_valid(PtLitKind k) { return ptk_lit_kind_valid(k) && k.rr && !k.list && !k.ris && !k.env; }
+// THE kind below the C ABI, one number: the kind's index, and bit 7 (PT_LIT_KIND_INDICES) for the forms that render the caller's rays --
+// the kernels' one kind parameter (pt_kernels.hip: PtKindOf) and the index of a table over kinds, whose second half is the rays forms'.
+// The two predicates above say which of the PT_LIT_KINDS values exist; nothing else lists them
+#define PT_LIT_KINDS (2 * PT_LIT_KIND_INDICES)
+constexpr unsigned ptk_lit_kind(PtLitKind k, bool rays) { return (unsigned)ptk_lit_kind_index(k) | (rays ? PT_LIT_KIND_INDICES : 0); }
+constexpr bool ptk_lit_valid(unsigned kind)
+{
+    const PtLitKind k = ptk_lit_kind_of(kind);
+    return kind < PT_LIT_KINDS && (kind & PT_LIT_KIND_INDICES ? ptk_lit_rays_valid(k) : ptk_lit_kind_valid(k));
+}
+// THE launch of a lit render, whatever its kind (ptk_lit_valid): `a` is the largest block, and each instantiation is passed its own,
+// sliced from it (PtDirectPowerParams is made of a.d, a.cdf and a.tri_q).  LBVH (m.bvh): the kind's kernel on a persistent grid of at
+// most bvh_blocks = CUs x ptk_lit_bvh_blocks_per_cu(kind) workgroups -- the occupancy of the kind's OWN <true, 3> instantiation with the
+// trace kernel's LDS: the direct kernels run at four waves per SIMD, the indirect ones at three, so ptk_query_bvh_blocks_per_cu's
+// premise (five) holds for none.  Brute force: one wave per 64 items; the roulette and list kinds one wave per PT_RR_RUN
+// (pt_constants.h) consecutive items, which refills its dead lanes from its run.  A rays kind reads neither a.d.cam nor the image geometry
+hipError_t ptk_lit(const PtLitParams& a, unsigned kind, int bvh_blocks, PtSearchMode m, hipStream_t s);
+int ptk_lit_bvh_blocks_per_cu(unsigned kind);
 // the fold of a list launch: one lane per (slot j, channel) folds rad[f][j], f = 0 .. frame_count - 1 ascending, into fb[the slot's
 // pixel] with the slot's own frame numbers (pt_fold_frame); pixels that are not listed are neither read nor written
 struct PtFoldListParams {

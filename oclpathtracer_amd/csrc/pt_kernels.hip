@@ -31,6 +31,7 @@
 #include "pt_secmask.h"
 
 #include <type_traits>
+#include <utility>
 
 typedef const __attribute__((address_space(4))) float* pt_const_f32p;  // scalar (SMEM) loads
 
@@ -3392,10 +3393,33 @@ PTK_DEV void pt_direct_surface(const PtDirectParams& D, const f3& o, const f3& d
     mid = pt_clamp_index(__float_as_int(id), D.t.nmat);
 }
 
+// THE kind of a lit kernel (pt_kernels.h: ptk_lit_kind): the one kind parameter of every lit template, its bits by name, and which of
+// them go together -- the two predicates of pt_kernels.h, so that no template can be instantiated for a kind that does not exist
+template <unsigned KIND> struct PtKindOf {
+    static constexpr PtLitKind k = ptk_lit_kind_of(KIND);
+    static constexpr bool indirect = k.indirect, mis = k.mis, power = k.power, rr = k.rr, list = k.list, ris = k.ris, env = k.env;
+    static constexpr bool rays = (KIND & PT_LIT_KIND_INDICES) != 0;
+    static_assert(ptk_lit_valid(KIND), "not a kind of lit render (ptk_lit_kind_valid, ptk_lit_rays_valid)");
+    // (never called) its return type is the kind's parameter block: the table of pt_kernels.h from its last row up
+    static auto block()
+    {
+        if constexpr (rays) return PtIndirectRaysParams();
+        else if constexpr (env) return std::conditional_t<indirect, PtIndirectEnvParams, PtDirectEnvParams>();
+        else if constexpr (ris) return std::conditional_t<indirect, PtIndirectRisParams, PtDirectRisParams>();
+        else if constexpr (list) return PtIndirectListParams();
+        else if constexpr (rr) return PtIndirectRrParams();
+        else if constexpr (power) return std::conditional_t<indirect, PtIndirectPowerParams, PtDirectPowerParams>();
+        else if constexpr (mis) return PtIndirectMisParams();
+        else return std::conditional_t<indirect, PtIndirectParams, PtDirectParams>();
+    }
+};
+template <unsigned KIND> using PtKindArgs = decltype(PtKindOf<KIND>::block());
+
 // Light sample k of the sample at (p, n, wo) on material mid (steps a-g of the contract).  True when it contributes: then c is its
 // contribution if the shadow ray (o, d) is open, and tl the ray's limit (not above 0: nothing is searched, the ray is open).  The
 // three uniforms are drawn whatever follows.  The quotients are pt_div's: the short form inside its guarded window, the generic
 // division outside it -- the IEEE quotient either way.
+// MIS, POWER: the kind's bits.
 // MIS (pt_render_indirect_mis): with `weigh` (the vertex is not the path's last) and the light's front towards the vertex (sl > 0) the
 // weight takes the balance factor kp / (kp counts[j] + pbl) against the BRDF's density pbl towards wi; these quotients are the
 // generic IEEE division (their operands have no proven window).  MIS = false is the code of pt_render_direct and pt_render_indirect.
@@ -3422,10 +3446,11 @@ PTK_DEV float pt_light_table_inv(const uint64_t* cdf, int nl, float r0, unsigned
     return (float)total / (float)(cdf[lo + 1u] - cdf[lo]);   // >= 1
 }
 
-template <bool MIS = false, bool POWER = false, bool WI_ONLY = false>
+template <unsigned KIND, bool WI_ONLY = false>
 PTK_DEV bool pt_direct_light(const PtDirectParams& D, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed, f3& c, f3& o, f3& d,
-                             float& tl, const int32_t* counts = nullptr, bool weigh = false, const uint64_t* cdf = nullptr)
+                             float& tl, const int32_t* counts, bool weigh, const uint64_t* cdf)
 {
+    constexpr bool MIS = PtKindOf<KIND>::mis, POWER = PtKindOf<KIND>::power;
     const float r0 = pt_random_float(seed), r1 = pt_random_float(seed), r2 = pt_random_float(seed);
     float nlf;       // the reciprocal of the probability of the entry chosen: nl, or total / q_i
     unsigned li;
@@ -3498,7 +3523,7 @@ PTK_DEV bool pt_direct_light(const PtDirectParams& D, const f3& p, const f3& n, 
     return true;
 }
 
-// Resampled light sample (RIS; include/pt_shim.h states every step): M candidates, each pt_direct_light<MIS, true>'s -- its three
+// Resampled light sample (RIS; include/pt_shim.h states every step): M candidates, each pt_direct_light's -- its three
 // uniforms, its table lookup, its c with the balance factor where the parent has it -- and from the second on one uniform r more, drawn
 // whether or not the candidate contributes: 4M - 1 uniforms.  A candidate that contributes with s = max channel of c > 0 (false for
 // NaN) adds s to wsum and is kept iff none is held or r * wsum < s, a reservoir of one.  True when one is held: c = c_sel * ((wsum / M)
@@ -3506,7 +3531,7 @@ PTK_DEV bool pt_direct_light(const PtDirectParams& D, const f3& p, const f3& n, 
 // is written.  M is wave-uniform, so the lanes of a wave evaluate their candidates in step; the reservoir -- the kept c, wi (the ray is
 // formed from it after the loop: nine registers, not twelve), tl and s, and wsum -- dies here: what a lane holds across the search is
 // the parent's c, o, d, tl.  M = 1: no r, wsum = s, g = 1.0f.
-template <bool MIS>
+template <unsigned KIND>
 PTK_DEV bool pt_ris_light(const PtDirectParams& D, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed, f3& c, f3& o, f3& d,
                           float& tl, const int32_t* counts, bool weigh, const uint64_t* cdf, int M)
 {
@@ -3517,7 +3542,7 @@ PTK_DEV bool pt_ris_light(const PtDirectParams& D, const f3& p, const f3& n, con
     for (int m = 0; m < M; ++m) {
         f3 cm = mk3(0.0f, 0.0f, 0.0f), wm = cm, unused = cm;
         float tm = 0.0f;
-        const bool ok = pt_direct_light<MIS, true, true>(D, p, n, wo, mid, seed, cm, wm, unused, tm, counts, weigh, cdf);
+        const bool ok = pt_direct_light<KIND, true>(D, p, n, wo, mid, seed, cm, wm, unused, tm, counts, weigh, cdf);
         float r = 0.0f;
         if (m >= 1) r = pt_random_float(seed);
         if (ok) {
@@ -3715,23 +3740,29 @@ PTK_DEV f3 pt_direct_radiance(const PtDirectParams& D, unsigned mid, const f3& S
     return mk3(pt_max(emi.x * 3.0f + S.x / Kf, 0.0f), pt_max(emi.y * 3.0f + S.y / Kf, 0.0f), pt_max(emi.z * 3.0f + S.z / Kf, 0.0f));
 }
 
+// the light sample of a vertex as the kind draws it: resampled (pt_ris_light), chosen by power, or uniform; A is the kind's block, D its
+// PtDirectParams.  weigh: (MIS) the vertex is not the path's last
+template <unsigned KIND>
+PTK_DEV bool pt_kind_light(const PtKindArgs<KIND>& A, const PtDirectParams& D, const f3& p, const f3& n, const f3& wo, unsigned mid, uint32_t& seed,
+                           f3& c, f3& o, f3& d, float& tl, bool weigh)
+{
+    using K = PtKindOf<KIND>;
+    const int32_t* counts = nullptr;   // (no kind without MIS reads the counts, none without POWER the table)
+    const uint64_t* cdf = nullptr;
+    if constexpr (K::mis) counts = A.counts;
+    if constexpr (K::power) cdf = A.cdf;
+    if constexpr (K::ris) return pt_ris_light<KIND>(D, p, n, wo, mid, seed, c, o, d, tl, counts, weigh, cdf, A.M);
+    else return pt_direct_light<KIND>(D, p, n, wo, mid, seed, c, o, d, tl, counts, weigh, cdf);
+}
+
 // brute force: one wave = 64 consecutive samples; the primary search, then the K shadow rays of the lanes whose light sample
 // contributes, all in step (pt_ao_kernel's shape); a light sample no lane of the wave casts a ray for costs no search.
-// POWER: the light is chosen through pt_light_table's cdf (pt_direct_light<false, true>); such an instantiation takes
-// PtDirectPowerParams, the others PtDirectParams as before
-// RIS (pt_render_direct_ris; POWER only): the light sample is pt_ris_light's; such an instantiation takes PtDirectRisParams
-// ENV (pt_render_direct_env; POWER only, never with RIS): a miss stores the map's texel, and the Ke environment samples follow the K
-// light samples in the same shape -- a search only when some lane casts --, summed apart in Se; the block is PtDirectEnvParams
-template <bool POWER, bool RIS = false, bool ENV = false>
-using PtDirectArgs = std::conditional_t<ENV, PtDirectEnvParams, std::conditional_t<RIS, PtDirectRisParams, std::conditional_t<POWER, PtDirectPowerParams, PtDirectParams>>>;
-PTK_DEV const uint64_t* pt_light_cdf(const PtDirectParams&) { return nullptr; }
-PTK_DEV const uint64_t* pt_light_cdf(const PtDirectPowerParams& D) { return D.cdf; }
-
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool POWER = false, bool RIS = false, bool ENV = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDirectArgs<POWER, RIS, ENV> D)
+// env (pt_render_direct_env): a miss stores the map's texel, and the Ke environment samples follow the K light samples in the same
+// shape -- a search only when some lane casts --, summed apart in Se
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, unsigned KIND>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtKindArgs<KIND> D)
 {
-    static_assert(POWER || !RIS, "resampling draws its candidates from the light table");
-    static_assert(!ENV || (POWER && !RIS), "the environment comes with the choice by power, without resampling");
+    constexpr bool ENV = PtKindOf<KIND>::env;
     const PtTraceParams& P = D.t;
     const unsigned lane = pt_lane_id();
     const int ntri = P.ntri;
@@ -3764,9 +3795,7 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDir
             f3 c = mk3(0.0f, 0.0f, 0.0f);
             float tlim = 0.0f;
             bool cast = false;
-            if constexpr (RIS) { if (hit) cast = pt_ris_light<false>(D, p, n, wo, mid, seed, c, o, d, tlim, nullptr, false, D.cdf, D.M); }
-            else if constexpr (POWER) { if (hit) cast = pt_direct_light<false, true>(D, p, n, wo, mid, seed, c, o, d, tlim, nullptr, false, pt_light_cdf(D)); }
-            else if (hit) cast = pt_direct_light(D, p, n, wo, mid, seed, c, o, d, tlim);
+            if (hit) cast = pt_kind_light<KIND>(D, D, p, n, wo, mid, seed, c, o, d, tlim, false);
             const bool live = cast & (tlim > 0.0f);
             bool occluded = false;
             if (__ballot(live) != 0ull) {
@@ -3808,10 +3837,10 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_direct_kernel(const PtDir
 // ENV: k goes on over K .. K + Ke - 1, the environment samples.  Before the first of them E + S / K is folded into `base` and S starts
 // again as Se: a lane's state grows by these three registers (PtNoEnv is empty in every other instantiation)
 struct PtNoEnv {};
-template <bool POWER = false, bool RIS = false, bool ENV = false>
+template <unsigned KIND>
 struct PtDirectWork {
-    static constexpr bool ANY = true;
-    const PtDirectArgs<POWER, RIS, ENV>& D;
+    static constexpr bool ANY = true, ENV = PtKindOf<KIND>::env;
+    const PtKindArgs<KIND>& D;
     unsigned n;
     int k;           // the current ray: -1 = the primary, 0 .. K-1 = the shadow ray of light sample k
     unsigned item, mid;
@@ -3848,7 +3877,7 @@ struct PtDirectWork {
             if (k < D.K) {   // the light samples are not over (k = -1 among them)
                 if (D.nl > 0)
                     while (++k < D.K)
-                        if (pt_direct_light<false, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, nullptr, false, D.cdf)) return true;
+                        if (pt_kind_light<KIND>(D, D, p, nrm, wo, mid, seed, c, o, d, tl, false)) return true;
                 const float4 emi = pt_rec16(D.t.mats, mid, 16u);
                 const float Kf = (float)D.K;
                 base = mk3(emi.x * 3.0f + S.x / Kf, emi.y * 3.0f + S.y / Kf, emi.z * 3.0f + S.z / Kf);   // pt_direct_env_radiance's first line
@@ -3868,9 +3897,7 @@ struct PtDirectWork {
         }
         if (D.nl > 0)
             while (++k < D.K) {
-                if constexpr (RIS) { if (pt_ris_light<false>(D, p, nrm, wo, mid, seed, c, o, d, tl, nullptr, false, D.cdf, D.M)) return true; }
-                else if constexpr (POWER) { if (pt_direct_light<false, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, nullptr, false, pt_light_cdf(D))) return true; }
-                else if (pt_direct_light(D, p, nrm, wo, mid, seed, c, o, d, tl)) return true;
+                if (pt_kind_light<KIND>(D, D, p, nrm, wo, mid, seed, c, o, d, tl, false)) return true;
             }
         pt_direct_store(D, item, pt_direct_radiance(D, mid, S));
         return false;
@@ -3886,18 +3913,18 @@ struct PtDirectWork {
 // against ambient occlusion's 16, and at five waves (96 VGPRs) the kernel spills 19 of them (profiles/direct/kernel_resources.txt).
 // Its persistent grid is therefore its own figure, ptk_lit_bvh_blocks_per_cu of its kind, not ptk_query_bvh_blocks_per_cu
 #define PT_DIRECT_BVH_WAVES 4
-// The ENV = true instantiations run at three: next_ray holds the light sample and the environment sample -- its table search in 64-bit
+// The env kinds run at three: next_ray holds the light sample and the environment sample -- its table search in 64-bit
 // words among them -- and at four waves would spill 33 VGPRs (profiles/env/kernel_resources.txt has both figures)
 #ifndef PT_DIRECT_ENV_BVH_WAVES   // (tools/kernel_resources.sh -DPT_DIRECT_ENV_BVH_WAVES=4 reads the other choice)
 #define PT_DIRECT_ENV_BVH_WAVES 3
 #endif
-template <bool DET_BOUNDED, int BIGQ, bool POWER = false, bool RIS = false, bool ENV = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS)
-__attribute__((amdgpu_waves_per_eu(ENV ? PT_DIRECT_ENV_BVH_WAVES : PT_DIRECT_BVH_WAVES, ENV ? PT_DIRECT_ENV_BVH_WAVES : PT_DIRECT_BVH_WAVES)))
-void pt_direct_bvh_kernel(const PtDirectArgs<POWER, RIS, ENV> D)
+constexpr int pt_direct_bvh_waves(unsigned kind) { return ptk_lit_kind_of(kind).env ? PT_DIRECT_ENV_BVH_WAVES : PT_DIRECT_BVH_WAVES; }
+template <bool DET_BOUNDED, int BIGQ, unsigned KIND>
+__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(pt_direct_bvh_waves(KIND), pt_direct_bvh_waves(KIND))))
+void pt_direct_bvh_kernel(const PtKindArgs<KIND> D)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtDirectWork<POWER, RIS, ENV> W = { D, D.nitems, -1, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, {} };
+    PtDirectWork<KIND> W = { D, D.nitems, -1, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, {} };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(D.t, W);
 }
 
@@ -4014,9 +4041,9 @@ void pt_feature_bvh_kernel(const PtFeatureParams F)
 // BRDF sample (pt_indirect_bounce), which ends the path at pdf <= 0 and otherwise scales mask and gives the next ray.
 // samples[item] = max(L, 0); pt_fold_kernel folds them.
 // MIS (pt_render_indirect_mis) is a compile-time flag of the same kernels: the light samples of every vertex but the last are
-// weighted against the BRDF sample (pt_direct_light<true>), the path carries that sample's pdf (pb), and a later vertex on an emitter
+// weighted against the BRDF sample (pt_direct_light), the path carries that sample's pdf (pb), and a later vertex on an emitter
 // adds its emission weighted the other way (pt_indirect_emission_mis).  The MIS = false instantiations are pt_render_indirect's code,
-// instruction for instruction (profiles/mis/disasm_comparison.txt); they take PtIndirectParams, the others PtIndirectMisParams.
+// instruction for instruction (profiles/mis/disasm_comparison.txt).
 
 // The BRDF sample at the vertex (p, n, wo) on material mid: Brdf (:195-221) and :251-257 as pt_shade states them -- the same draws
 // (phi, then the second uniform), the same shared sqrt pair, the same guarded short quotients (pt_div_by, pt_div, pt_div_pair,
@@ -4263,16 +4290,6 @@ PTK_DEV void pt_indirect_emission(const PtDirectParams& D, unsigned mid, const f
     L.z = L.z + mask.z * emi.z * 3.0f;
 }
 
-// the parameter block of an instantiation, and its counts (none without MIS)
-template <bool MIS, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false, bool RAYS = false>
-using PtIndirectArgs = std::conditional_t<RAYS, PtIndirectRaysParams, std::conditional_t<ENV, PtIndirectEnvParams, std::conditional_t<RIS, PtIndirectRisParams, std::conditional_t<LIST, PtIndirectListParams, std::conditional_t<RR, PtIndirectRrParams, std::conditional_t<POWER, PtIndirectPowerParams, std::conditional_t<MIS, PtIndirectMisParams, PtIndirectParams>>>>>>>;
-PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectParams&) { return nullptr; }
-PTK_DEV const int32_t* pt_indirect_counts(const PtIndirectMisParams& I) { return I.counts; }
-PTK_DEV const uint64_t* pt_light_cdf(const PtIndirectParams&) { return nullptr; }
-PTK_DEV const uint64_t* pt_light_cdf(const PtIndirectPowerParams& I) { return I.cdf; }
-PTK_DEV const uint32_t* pt_light_tri_q(const PtIndirectParams&) { return nullptr; }
-PTK_DEV const uint32_t* pt_light_tri_q(const PtIndirectPowerParams& I) { return I.tri_q; }
-
 // (MIS) the emission of a vertex i >= 1, found by the BRDF ray (o, d) at distance t, weighted against the light samples of the vertex
 // before: pe is the density those give the same point -- from the hit triangle's record N = cross(e2, e1), its own distance
 // tt = t + 0.01f (the ray began 0.01 off that vertex, :257) and its count --, pb the density of the BRDF sample that made the ray.
@@ -4306,6 +4323,17 @@ PTK_DEV void pt_indirect_emission_mis(const PtDirectParams& D, const int32_t* co
     L.x = L.x + ((mask.x * emi.x) * 3.0f) * wb;
     L.y = L.y + ((mask.y * emi.y) * 3.0f) * wb;
     L.z = L.z + ((mask.z * emi.z) * 3.0f) * wb;
+}
+
+// the emission of vertex i as the kind adds it: whole at the first vertex and without lights; at a later vertex weighted (MIS), or not at
+// all -- there the light samples of the vertex before have counted it
+template <unsigned KIND>
+PTK_DEV void pt_kind_emission(const PtKindArgs<KIND>& I, int i, unsigned mid, int hidx, const f3& d, float t, float pb, const f3& mask, f3& L)
+{
+    using K = PtKindOf<KIND>;
+    if (i == 0 || I.d.nl == 0) pt_indirect_emission(I.d, mid, mask, L);
+    else if constexpr (K::mis && K::power) pt_indirect_emission_mis<true>(I.d, I.counts, mid, hidx, d, t, pb, mask, L, I.cdf, I.tri_q);
+    else if constexpr (K::mis) pt_indirect_emission_mis(I.d, I.counts, mid, hidx, d, t, pb, mask, L);
 }
 
 // L += mask * (S / K) of a vertex's light samples
@@ -4343,9 +4371,11 @@ PTK_DEV bool pt_roulette(float cap, uint32_t& seed, f3& mask)
 // brute force: one wave = 64 consecutive samples, pt_direct_kernel's shape inside a loop over the bounces.  The wave searches in step
 // with the lanes still alive and leaves the loop when none is; a light sample no lane casts a ray for costs no search.  Lanes whose
 // path has ended are NOT given new samples: the wave runs as long as its longest path (DESIGN.md S4 states the cost).
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS = false, bool POWER = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtIndirectArgs<MIS, POWER> I)
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, unsigned KIND>
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtKindArgs<KIND> I)
 {
+    constexpr bool MIS = PtKindOf<KIND>::mis;
+    static_assert(PtKindOf<KIND>::indirect && !PtKindOf<KIND>::rr, "the roulette kinds' table kernel is pt_indirect_rr_kernel");
     const PtDirectParams& D = I.d;
     const PtTraceParams& P = D.t;
     const unsigned lane = pt_lane_id();
@@ -4374,9 +4404,7 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
         unsigned mid = 0u;
         if (hit) {
             pt_direct_surface(D, o, d, tmax, hu, hv, hidx, p, n, wo, mid);
-            if (i == 0 || D.nl == 0) pt_indirect_emission(D, mid, mask, L);
-            else if constexpr (MIS && POWER) pt_indirect_emission_mis<true>(D, pt_indirect_counts(I), mid, hidx, d, tmax, pb, mask, L, pt_light_cdf(I), pt_light_tri_q(I));
-            else if constexpr (MIS) pt_indirect_emission_mis(D, pt_indirect_counts(I), mid, hidx, d, tmax, pb, mask, L);
+            pt_kind_emission<KIND>(I, i, mid, hidx, d, tmax, pb, mask, L);
         }
         if (D.nl > 0) {
             f3 S = mk3(0.0f, 0.0f, 0.0f);
@@ -4384,8 +4412,7 @@ __global__ __launch_bounds__(PT_TRACE_THREADS) void pt_indirect_kernel(const PtI
                 f3 c = mk3(0.0f, 0.0f, 0.0f);
                 float tlim = 0.0f;
                 bool cast = false;
-                if constexpr (POWER) { if (hit) cast = pt_direct_light<MIS, true>(D, p, n, wo, mid, seed, c, o, d, tlim, pt_indirect_counts(I), i < I.B - 1, pt_light_cdf(I)); }
-                else if (hit) cast = pt_direct_light<MIS>(D, p, n, wo, mid, seed, c, o, d, tlim, pt_indirect_counts(I), i < I.B - 1);
+                if (hit) cast = pt_kind_light<KIND>(I, D, p, n, wo, mid, seed, c, o, d, tlim, i < I.B - 1);
                 const bool live = cast & (tlim > 0.0f);
                 bool occluded = false;
                 if (__ballot(live) != 0ull) {
@@ -4447,36 +4474,37 @@ PTK_DEV void pt_ray_item_begin(const PtIndirectRaysParams& I, unsigned item, uin
 // Termination: an iteration starts with at least one live lane (else the wave leaves: no lane alive means the refill found the run
 // exhausted), and every live lane either ends its path in it or raises its bounce, which is below B; every refill raises `next`,
 // which is at most `end`.  So a wave runs at most PT_RR_RUN * B iterations.  No spin, no persistent grid.
-// LIST (pt_render_indirect_pixels): the items are frames of a list of pixels; only the sample's start differs (pt_list_item_begin)
-// RAYS (pt_radiance_rays; neither LIST, RIS nor ENV): the items are samples of the caller's rays; only the sample's start differs
-// (pt_ray_item_begin), the block is PtIndirectRaysParams.  No pin: the compiler holds every form at its parent's waves per SIMD
-// (profiles/radiance/kernel_resources.txt)
-// RIS (pt_render_indirect_ris, pt_render_indirect_pixels_ris; POWER only): the light sample is pt_ris_light's -- the candidates of the
-// wave's lanes in step, then the one shadow search, none when no lane holds a candidate; the block is PtIndirectRisParams
-// The RIS forms carry an occupancy pin, the parents' six waves per SIMD (80 VGPRs): unpinned the compiler takes 81-82 registers for a
-// loop it holds in 80 without a spill.  The tiled MIS forms are the exception: at six waves they spill 3 VGPRs (16 bytes of scratch),
-// so they are pinned to the five they need (85 VGPRs, no scratch); profiles/ris/kernel_resources.txt has both figures.  A pin of 0 is
-// no pin: the attribute is not emitted, and the RIS = false instantiations are the parent's code
+// The kind's bits (PtKindOf):
+// list (pt_render_indirect_pixels): the items are frames of a list of pixels; only the sample's start differs (pt_list_item_begin)
+// rays (pt_radiance_rays): the items are samples of the caller's rays; only the sample's start differs (pt_ray_item_begin).  No pin:
+// the compiler holds every form at its parent's waves per SIMD (profiles/radiance/kernel_resources.txt)
+// ris (pt_render_indirect_ris, pt_render_indirect_pixels_ris): the light sample is pt_ris_light's -- the candidates of the wave's
+// lanes in step, then the one shadow search, none when no lane holds a candidate.  These forms carry an occupancy pin, the parents'
+// six waves per SIMD (80 VGPRs): unpinned the compiler takes 81-82 registers for a loop it holds in 80 without a spill.  The tiled MIS
+// forms are the exception: at six waves they spill 3 VGPRs (16 bytes of scratch), so they are pinned to the five they need (85 VGPRs,
+// no scratch); profiles/ris/kernel_resources.txt has both figures.  A pin of 0 is no pin: the attribute is not emitted
 #ifndef PT_RR_RIS_TILED_MIS_WAVES   // (tools/kernel_resources.sh -DPT_RR_RIS_TILED_MIS_WAVES=6 reads the other choice)
 #define PT_RR_RIS_TILED_MIS_WAVES 5
 #endif
-// ENV (pt_render_indirect_env; MIS and POWER, neither LIST nor RIS): a miss adds mask times the map's texel -- weighted against the
-// environment samples of the vertex before when i >= 1 and Ke > 0 --, and the Ke environment samples of a vertex follow its K light
-// samples in the same shape, a search only when some lane casts; the block is PtIndirectEnvParams.  PT_RR_ENV_WAVES is their pin
-// -- the parents' six waves per SIMD for the tiled forms; the forms with the table in LDS would spill a VGPR at six (8 bytes of scratch)
-// and are pinned to five (profiles/env/kernel_resources.txt has both figures)
+// env (pt_render_indirect_env): a miss adds mask times the map's texel -- weighted against the environment samples of the vertex
+// before when i >= 1 and Ke > 0 --, and the Ke environment samples of a vertex follow its K light samples in the same shape, a search
+// only when some lane casts.  Their pin is the parents' six waves per SIMD for the tiled forms; the forms with the table in LDS would
+// spill a VGPR at six (8 bytes of scratch) and are pinned to five (profiles/env/kernel_resources.txt has both figures)
 #ifndef PT_RR_ENV_LDS_WAVES   // (tools/kernel_resources.sh -DPT_RR_ENV_LDS_WAVES=6 reads the other choice)
 #define PT_RR_ENV_LDS_WAVES 5
 #endif
-template <bool RIS, int LDS_TABLE, bool MIS, bool ENV = false>
-inline constexpr int PT_RR_WAVES_PIN = ENV ? (LDS_TABLE == 1 ? PT_RR_ENV_LDS_WAVES : 6) : !RIS ? 0 : (LDS_TABLE == 2 && MIS) ? PT_RR_RIS_TILED_MIS_WAVES : 6;
-template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, bool MIS, bool POWER, bool LIST = false, bool RIS = false, bool ENV = false, bool RAYS = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(PT_RR_WAVES_PIN<RIS, LDS_TABLE, MIS, ENV>)))
-void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS, ENV, RAYS> I)
+constexpr int pt_rr_waves_pin(unsigned kind, int lds_table)
 {
-    static_assert(POWER || !RIS, "resampling draws its candidates from the light table");
-    static_assert(!RAYS || (!LIST && !RIS && !ENV), "the caller's rays come without a list, resampling or the environment");
-    static_assert(!ENV || (MIS && POWER && !LIST && !RIS), "the environment comes with MIS and the choice by power, without a list or resampling");
+    const PtLitKind k = ptk_lit_kind_of(kind);
+    return k.env ? (lds_table == 1 ? PT_RR_ENV_LDS_WAVES : 6) : !k.ris ? 0 : (lds_table == 2 && k.mis) ? PT_RR_RIS_TILED_MIS_WAVES : 6;
+}
+template <bool DET_BOUNDED, int LDS_TABLE, int QUADS, unsigned KIND>
+__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(pt_rr_waves_pin(KIND, LDS_TABLE))))
+void pt_indirect_rr_kernel(const PtKindArgs<KIND> I)
+{
+    using K = PtKindOf<KIND>;
+    constexpr bool MIS = K::mis, LIST = K::list, ENV = K::env, RAYS = K::rays;
+    static_assert(K::rr, "the refilling kernel is the roulette kinds'");
     static_assert(PT_RR_RUN % 64 == 0 && PT_RR_RUN >= 64, "a run is whole waves of items");
     const PtDirectParams& D = I.d;
     const PtTraceParams& P = D.t;
@@ -4533,9 +4561,7 @@ void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS, ENV
         unsigned mid = 0u;
         if (hit) {
             pt_direct_surface(D, o, d, tmax, hu, hv, hidx, p, n, wo, mid);
-            if (i == 0 || D.nl == 0) pt_indirect_emission(D, mid, mask, L);
-            else if constexpr (MIS && POWER) pt_indirect_emission_mis<true>(D, I.counts, mid, hidx, d, tmax, pb, mask, L, I.cdf, I.tri_q);
-            else if constexpr (MIS) pt_indirect_emission_mis(D, I.counts, mid, hidx, d, tmax, pb, mask, L);
+            pt_kind_emission<KIND>(I, i, mid, hidx, d, tmax, pb, mask, L);
         }
         if (D.nl > 0 && __ballot(hit) != 0ull) {
             f3 S = mk3(0.0f, 0.0f, 0.0f);
@@ -4543,9 +4569,7 @@ void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS, ENV
                 f3 c = mk3(0.0f, 0.0f, 0.0f);
                 float tlim = 0.0f;
                 bool cast = false;
-                if constexpr (RIS) { if (hit) cast = pt_ris_light<MIS>(D, p, n, wo, mid, seed, c, o, d, tlim, I.counts, i < I.B - 1, I.cdf, I.M); }
-                else if constexpr (POWER) { if (hit) cast = pt_direct_light<MIS, true>(D, p, n, wo, mid, seed, c, o, d, tlim, I.counts, i < I.B - 1, I.cdf); }
-                else if (hit) cast = pt_direct_light<MIS>(D, p, n, wo, mid, seed, c, o, d, tlim, I.counts, i < I.B - 1);
+                if (hit) cast = pt_kind_light<KIND>(I, D, p, n, wo, mid, seed, c, o, d, tlim, i < I.B - 1);
                 const bool live = cast & (tlim > 0.0f);
                 bool occluded = false;
                 if (__ballot(live) != 0ull) {
@@ -4601,14 +4625,11 @@ void pt_indirect_rr_kernel(const PtIndirectArgs<MIS, POWER, true, LIST, RIS, ENV
 // emitter's record are gathered where they are used, as the materials are.
 // ENV: k goes on over K .. K + Ke - 1, the environment samples of the vertex.  S / K is folded into L before the first of them and S
 // starts again as Se: a lane's state does not grow
-template <bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false, bool RAYS = false>
+template <unsigned KIND>
 struct PtIndirectWork {
-    static_assert(RR || !LIST, "a list launch is a roulette launch");
-    static_assert(!RAYS || (RR && !LIST && !RIS && !ENV), "the caller's rays come in the roulette family, without a list, resampling or the environment");
-    static_assert(!RIS || (POWER && RR), "resampling comes with the light table, in the roulette family");
-    static_assert(!ENV || (MIS && POWER && RR && !LIST && !RIS), "the environment comes with MIS and the light table, in the roulette family");
-    static constexpr bool ANY = true;
-    const PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV, RAYS>& I;
+    using K = PtKindOf<KIND>;
+    static constexpr bool ANY = true, MIS = K::mis, RR = K::rr, LIST = K::list, ENV = K::env, RAYS = K::rays;
+    const PtKindArgs<KIND>& I;
     unsigned n;
     int k;           // the current ray: -1 = the vertex's closest search, 0 .. K-1 = the shadow ray of light sample k
     int bounce;      // loop index i of traceRays (:229)
@@ -4644,9 +4665,7 @@ struct PtIndirectWork {
                 return false;
             }
             pt_direct_surface(D, o, d, R.tmax, R.hu, R.hv, R.hidx, p, nrm, wo, mid);
-            if (bounce == 0 || D.nl == 0) pt_indirect_emission(D, mid, mask, L);
-            else if constexpr (MIS && POWER) pt_indirect_emission_mis<true>(D, pt_indirect_counts(I), mid, R.hidx, d, R.tmax, pb, mask, L, pt_light_cdf(I), pt_light_tri_q(I));
-            else if constexpr (MIS) pt_indirect_emission_mis(D, pt_indirect_counts(I), mid, R.hidx, d, R.tmax, pb, mask, L);
+            pt_kind_emission<KIND>(I, bounce, mid, R.hidx, d, R.tmax, pb, mask, L);
             S = mk3(0.0f, 0.0f, 0.0f);
         } else if (R.hidx < 0) {   // (an any-hit search: R.hidx >= 0 alone says occluded; a ray that searched nothing is open)
             S = add3(S, c);
@@ -4655,7 +4674,7 @@ struct PtIndirectWork {
             if (k < D.K) {   // the light samples are not over (k = -1 among them)
                 if (D.nl > 0) {
                     while (++k < D.K)
-                        if (pt_direct_light<true, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, I.counts, bounce < I.B - 1, I.cdf)) return true;
+                        if (pt_kind_light<KIND>(I, D, p, nrm, wo, mid, seed, c, o, d, tl, bounce < I.B - 1)) return true;
                     pt_indirect_lit(D, mask, S, L);
                     S = mk3(0.0f, 0.0f, 0.0f);
                 }
@@ -4667,9 +4686,7 @@ struct PtIndirectWork {
             if (I.env.Ke > 0) pt_env_lit(I.env.Ke, mask, S, L);
         } else if (D.nl > 0) {
             while (++k < D.K) {
-                if constexpr (RIS) { if (pt_ris_light<MIS>(D, p, nrm, wo, mid, seed, c, o, d, tl, I.counts, bounce < I.B - 1, I.cdf, I.M)) return true; }
-                else if constexpr (POWER) { if (pt_direct_light<MIS, true>(D, p, nrm, wo, mid, seed, c, o, d, tl, pt_indirect_counts(I), bounce < I.B - 1, pt_light_cdf(I))) return true; }
-                else if (pt_direct_light<MIS>(D, p, nrm, wo, mid, seed, c, o, d, tl, pt_indirect_counts(I), bounce < I.B - 1)) return true;
+                if (pt_kind_light<KIND>(I, D, p, nrm, wo, mid, seed, c, o, d, tl, bounce < I.B - 1)) return true;
             }
             pt_indirect_lit(D, mask, S, L);
         }
@@ -4701,25 +4718,21 @@ struct PtIndirectWork {
 #ifndef PT_INDIRECT_BVH_WAVES   // (tools/kernel_resources.sh -DPT_INDIRECT_BVH_WAVES=4 reads the other choice)
 #define PT_INDIRECT_BVH_WAVES 3
 #endif
-// The RR = true instantiations (Russian roulette, pt_roulette in next_ray) take PtIndirectRrParams and keep the three waves: R and cap are
-// scalar, the roulette's r, s and q die where they are used (profiles/roulette/kernel_resources.txt has the compiler's figures)
-// The LIST = true instantiations (pt_render_indirect_pixels) take PtIndirectListParams: the slot is loaded and dies in begin(), the
-// pointer and the offset are scalar (profiles/adaptive/kernel_resources.txt)
-// The RAYS = true instantiations (pt_radiance_rays) take PtIndirectRaysParams: the record is loaded and dies in begin(), the pointer and
-// first_ray are scalar (profiles/radiance/kernel_resources.txt)
-// The RIS = true instantiations take PtIndirectRisParams: M is scalar, the reservoir lives inside pt_ris_light (profiles/ris/kernel_resources.txt)
-// The ENV = true instantiations take PtIndirectEnvParams: the map's fields are scalar, Se shares S's registers.  They run at TWO waves:
-// at three they would spill 37 VGPRs inside next_ray (profiles/env/kernel_resources.txt has both figures)
+// The other kinds keep the three waves: what their blocks add is scalar (R and cap, the slot pointer and the frame offset, the ray
+// pointer and first_ray, M), and what they load dies where it is used -- the roulette's r, s and q, the slot and the ray record in
+// begin(), the reservoir inside pt_ris_light (profiles/roulette, adaptive, radiance, ris: kernel_resources.txt)
+// The env kinds: the map's fields are scalar, Se shares S's registers.  They run at TWO waves: at three they would spill 37 VGPRs
+// inside next_ray (profiles/env/kernel_resources.txt has both figures)
 #ifndef PT_INDIRECT_ENV_BVH_WAVES   // (tools/kernel_resources.sh -DPT_INDIRECT_ENV_BVH_WAVES=3 reads the other choice)
 #define PT_INDIRECT_ENV_BVH_WAVES 2
 #endif
-template <bool DET_BOUNDED, int BIGQ, bool MIS = false, bool POWER = false, bool RR = false, bool LIST = false, bool RIS = false, bool ENV = false, bool RAYS = false>
-__global__ __launch_bounds__(PT_TRACE_THREADS)
-__attribute__((amdgpu_waves_per_eu(ENV ? PT_INDIRECT_ENV_BVH_WAVES : PT_INDIRECT_BVH_WAVES, ENV ? PT_INDIRECT_ENV_BVH_WAVES : PT_INDIRECT_BVH_WAVES)))
-void pt_indirect_bvh_kernel(const PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV, RAYS> I)
+constexpr int pt_indirect_bvh_waves(unsigned kind) { return ptk_lit_kind_of(kind).env ? PT_INDIRECT_ENV_BVH_WAVES : PT_INDIRECT_BVH_WAVES; }
+template <bool DET_BOUNDED, int BIGQ, unsigned KIND>
+__global__ __launch_bounds__(PT_TRACE_THREADS) __attribute__((amdgpu_waves_per_eu(pt_indirect_bvh_waves(KIND), pt_indirect_bvh_waves(KIND))))
+void pt_indirect_bvh_kernel(const PtKindArgs<KIND> I)
 {
     const f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
-    PtIndirectWork<MIS, POWER, RR, LIST, RIS, ENV, RAYS> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
+    PtIndirectWork<KIND> W = { I, I.d.nitems, -1, 0, 0u, 0u, 0u, 0.0f, o0, d0, o0, d0, d0, o0, o0, o0, o0, 0.0f };
     pt_bvh_drive<DET_BOUNDED, BIGQ>(I.d.t, W);
 }
 
@@ -5224,67 +5237,51 @@ struct PtFeatureFamily {
     template <bool DB, int BIGQ> static constexpr auto bvh() { return pt_feature_bvh_kernel<DB, BIGQ>; }
     template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table() { return pt_feature_kernel<DB, LDS_TABLE, QUADS>; }
 };
-// a kind of lit render (PtLitKind); RR: the table kernels are the refilling ones, a wave of which owns PT_RR_RUN items
-template <bool INDIRECT, bool MIS, bool POWER, bool RR, bool LIST, bool RIS = false, bool ENV = false, bool RAYS = false> struct PtLitFamily {
-    using Params = std::conditional_t<INDIRECT, PtIndirectArgs<MIS, POWER, RR, LIST, RIS, ENV, RAYS>, PtDirectArgs<POWER, RIS, ENV>>;
-    static constexpr unsigned run = RR ? PT_RR_RUN : 64;
+// a kind of lit render (ptk_lit_kind); rr: the table kernels are the refilling ones, a wave of which owns PT_RR_RUN items
+template <unsigned KIND> struct PtLitFamily {
+    using K = PtKindOf<KIND>;
+    using Params = PtKindArgs<KIND>;
+    static constexpr unsigned run = K::rr ? PT_RR_RUN : 64;
     template <bool DB, int BIGQ> static constexpr auto bvh()
     {
-        if constexpr (INDIRECT) return pt_indirect_bvh_kernel<DB, BIGQ, MIS, POWER, RR, LIST, RIS, ENV, RAYS>;
-        else return pt_direct_bvh_kernel<DB, BIGQ, POWER, RIS, ENV>;
+        if constexpr (K::indirect) return pt_indirect_bvh_kernel<DB, BIGQ, KIND>;
+        else return pt_direct_bvh_kernel<DB, BIGQ, KIND>;
     }
     template <bool DB, int LDS_TABLE, int QUADS> static constexpr auto table()
     {
-        if constexpr (RR) return pt_indirect_rr_kernel<DB, LDS_TABLE, QUADS, MIS, POWER, LIST, RIS, ENV, RAYS>;
-        else if constexpr (INDIRECT) return pt_indirect_kernel<DB, LDS_TABLE, QUADS, MIS, POWER>;
-        else return pt_direct_kernel<DB, LDS_TABLE, QUADS, POWER, RIS, ENV>;
+        if constexpr (K::rr) return pt_indirect_rr_kernel<DB, LDS_TABLE, QUADS, KIND>;
+        else if constexpr (K::indirect) return pt_indirect_kernel<DB, LDS_TABLE, QUADS, KIND>;
+        else return pt_direct_kernel<DB, LDS_TABLE, QUADS, KIND>;
     }
     // the instantiations' own block, sliced from the largest (every indirect block is a base of it; direct by power: direct's and the table)
     static Params params(const PtLitParams& a)
     {
-        if constexpr (INDIRECT && (ENV || RAYS)) {
-            Params p;
-            __builtin_memset(&p, 0, sizeof p);
-            static_cast<PtIndirectRrParams&>(p) = a;
-            if constexpr (ENV) p.env = a.env;
-            if constexpr (RAYS) { p.rays = a.rays; p.first_ray = a.first_ray; }
-            return p;
-        } else if constexpr (INDIRECT) return a;
-        else if constexpr (!POWER) return a.d;
+        if constexpr (K::indirect && !K::env && !K::rays) return a;
+        else if constexpr (!K::indirect && !K::power) return a.d;
         else {
             Params p;
             __builtin_memset(&p, 0, sizeof p);
-            static_cast<PtDirectParams&>(p) = a.d;
-            p.cdf = a.cdf;
-            p.tri_q = a.tri_q;
-            if constexpr (RIS) p.M = a.M;
-            if constexpr (ENV) p.env = a.env;
+            if constexpr (K::indirect) static_cast<PtIndirectRrParams&>(p) = a;
+            else { static_cast<PtDirectParams&>(p) = a.d; p.cdf = a.cdf; p.tri_q = a.tri_q; }
+            if constexpr (K::ris) p.M = a.M;
+            if constexpr (K::env) p.env = a.env;
+            if constexpr (K::rays) { p.rays = a.rays; p.first_ray = a.first_ray; }
             return p;
         }
     }
 };
-// fn(the family of kind k): the 14 valid kinds without ris, the 5 with it and no other -- direct illumination has neither MIS nor roulette, a
-// list is played with roulette, resampling comes by power and, indirect, in the roulette family
-template <class Fn> static auto pt_lit_family(PtLitKind k, bool rays, Fn fn)
+// fn(the family of `kind`), instantiated for every value ptk_lit_valid accepts and for no other: the predicates of pt_kernels.h ARE
+// the list of kinds.  `none` is the answer for a value they refuse
+template <class R, class Fn, unsigned... I> static R pt_lit_family(unsigned kind, R none, Fn fn, std::integer_sequence<unsigned, I...>)
 {
-    auto estimator = [&](auto mis, auto power) {
-        constexpr bool M = decltype(mis)::value, P = decltype(power)::value;
-        if (rays) return fn(PtLitFamily<true, M, P, true, false, false, false, true>());   // (ptk_lit_rays_valid: a roulette kind, nothing else)
-        if constexpr (P) if (k.env) {
-            if constexpr (!M) return fn(PtLitFamily<false, false, true, false, false, false, true>());
-            else return fn(PtLitFamily<true, true, true, true, false, false, true>());
-        }
-        if constexpr (P) if (k.ris) {
-            if constexpr (!M) if (!k.indirect) return fn(PtLitFamily<false, false, true, false, false, true>());
-            return k.list ? fn(PtLitFamily<true, M, true, true, true, true>()) : fn(PtLitFamily<true, M, true, true, false, true>());
-        }
-        if constexpr (!M) if (!k.indirect) return fn(PtLitFamily<false, false, P, false, false>());
-        return k.list ? fn(PtLitFamily<true, M, P, true, true>()) : k.rr ? fn(PtLitFamily<true, M, P, true, false>()) : fn(PtLitFamily<true, M, P, false, false>());
+    auto one = [&](auto i) {
+        if constexpr (ptk_lit_valid(decltype(i)::value))
+            if (kind == decltype(i)::value) none = fn(PtLitFamily<decltype(i)::value>());
     };
-    const std::true_type yes;
-    const std::false_type no;
-    return k.mis ? (k.power ? estimator(yes, yes) : estimator(yes, no)) : (k.power ? estimator(no, yes) : estimator(no, no));
+    (one(std::integral_constant<unsigned, I>()), ...);
+    return none;
 }
+template <class R, class Fn> static R pt_lit_family(unsigned kind, R none, Fn fn) { return pt_lit_family(kind, none, fn, std::make_integer_sequence<unsigned, PT_LIT_KINDS>()); }
 
 // One launch of a kernel over nitems items of a scene of ntri triangles -- LBVH: a persistent grid of at most bvh_blocks workgroups (what the chip
 // holds), its waves take 64 items at a time, with the trace kernel's LDS; brute force: one wave per `run` items, the table kernels' LDS without the pools
@@ -5319,19 +5316,19 @@ hipError_t ptk_render_features(const PtFeatureParams& f, int bvh_blocks, PtSearc
     return pt_launch_search(pt_choose<PtFeatureFamily>(m, f.d.t.ntri), f, f.d.t.ntri, f.d.nitems, 64u, m.bvh, bvh_blocks, s);
 }
 
-hipError_t ptk_lit(const PtLitParams& a, PtLitKind k, bool rays, int bvh_blocks, PtSearchMode m, hipStream_t s)
+hipError_t ptk_lit(const PtLitParams& a, unsigned kind, int bvh_blocks, PtSearchMode m, hipStream_t s)
 {
     if (a.d.nitems == 0) return hipSuccess;
-    return pt_lit_family(k, rays, [&](auto f) {
+    return pt_lit_family(kind, hipErrorInvalidValue, [&](auto f) {
         using F = decltype(f);
         const typename F::Params p = F::params(a);
         return pt_launch_search(pt_choose<F>(m, a.d.t.ntri), p, a.d.t.ntri, a.d.nitems, F::run, m.bvh, bvh_blocks, s);
     });
 }
 
-int ptk_lit_bvh_blocks_per_cu(PtLitKind k, bool rays)
+int ptk_lit_bvh_blocks_per_cu(unsigned kind)
 {
-    return pt_lit_family(k, rays, [](auto f) { return pt_blocks_per_cu(decltype(f)::template bvh<true, 3>(), ptk_trace_bvh_lds_bytes()); });
+    return pt_lit_family(kind, 0, [](auto f) { return pt_blocks_per_cu(decltype(f)::template bvh<true, 3>(), ptk_trace_bvh_lds_bytes()); });
 }
 
 hipError_t ptk_light_table(const PtRawTriangle* tris, int ntri, const PtRawMaterial* mats, int nmat, const int32_t* lights, int nl,

@@ -138,7 +138,7 @@ struct pt_device_s {
     uint64_t bvh_builds;        // LBVH builds so far (PT_OPT_BVH_BUILD_COUNT)
     int bvh_blocks_per_cu;
     int query_bvh_blocks_per_cu;   // the persistent grid of the LBVH query and ambient-occlusion kernels (pt_bvh_drive)
-    int lit_bvh_blocks_per_cu[2][PT_LIT_KIND_INDICES];   // ... and of the lit renders' LBVH kernels, each kind its own (ptk_lit_kind_index)
+    int lit_bvh_blocks_per_cu[PT_LIT_KINDS];   // ... and of the lit renders' LBVH kernels, each kind its own (ptk_lit_kind: the second half the rays forms')
     unsigned int* trav_host; // the LBVH's sticky "search cut short" words: host memory the kernels store to (PT_ERR_TRAVERSAL)
     unsigned int* trav_dev;  // ... as the device addresses it
     // ---- fused-render workspace: the STREAMING renderer (render_part, plan_chunks, the ring).  A render walks its frames in chunks of
@@ -368,11 +368,8 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->blocks_per_cu = ptk_trace_blocks_per_cu(36);
     d->bvh_blocks_per_cu = ptk_trace_bvh_blocks_per_cu();
     d->query_bvh_blocks_per_cu = ptk_query_bvh_blocks_per_cu();
-    for (int i = 0; i < PT_LIT_KIND_INDICES; ++i) {
-        const PtLitKind k = { (i & 1) != 0, (i & 2) != 0, (i & 4) != 0, (i & 8) != 0, (i & 16) != 0, (i & 32) != 0, (i & 64) != 0 };
-        if (ptk_lit_kind_valid(k)) d->lit_bvh_blocks_per_cu[0][ptk_lit_kind_index(k)] = ptk_lit_bvh_blocks_per_cu(k, false);
-        if (ptk_lit_rays_valid(k)) d->lit_bvh_blocks_per_cu[1][ptk_lit_kind_index(k)] = ptk_lit_bvh_blocks_per_cu(k, true);   // (row 1: the RAYS forms)
-    }
+    for (unsigned kind = 0; kind < PT_LIT_KINDS; ++kind)
+        if (ptk_lit_valid(kind)) d->lit_bvh_blocks_per_cu[kind] = ptk_lit_bvh_blocks_per_cu(kind);
     *out = d;
     return PT_OK;
 }
@@ -1898,12 +1895,15 @@ struct PtLitCall {
     const char* what;           // the message for a field out of range
 };
 
-static PtLitCall lit_call(PtLitKind kind, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
-                          pt_buffer_t framebuffer, const pt_camera* cam, pt_event_t ev)
+// (light_counts, cdf, tri_q: NULL from an entry point that has none; the counts are kept only for a kind that reads them)
+static PtLitCall lit_call(PtLitKind kind, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t light_counts,
+                          pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer, const pt_camera* cam, pt_event_t ev)
 {
     PtLitCall c = {};
     c.kind = kind;
     c.triangles = triangles; c.materials = materials; c.lights = lights; c.samples = samples; c.framebuffer = framebuffer;
+    c.light_counts = kind.mis ? light_counts : nullptr;
+    c.cdf = cdf; c.tri_q = tri_q;
     c.cam = cam; c.ev = ev;
     c.what = kind.indirect ? "invalid indirect-illumination parameters" : "invalid direct-illumination parameters";
     return c;
@@ -2023,7 +2023,8 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
     lp.num_listed = wpix;
     lp.npix_local = npix;
     // each kind's LBVH kernel on its own grid (pt_kernels.h)
-    const int bvh_blocks = !search.mode.bvh ? 0 : d->prop.multiProcessorCount * d->lit_bvh_blocks_per_cu[rays ? 1 : 0][ptk_lit_kind_index(c.kind)];
+    const unsigned kind = ptk_lit_kind(c.kind, rays);
+    const int bvh_blocks = !search.mode.bvh ? 0 : d->prop.multiProcessorCount * d->lit_bvh_blocks_per_cu[kind];
     // whole frames per chunk: what the workspace holds, fewer than 2^31 samples per launch; a launch, then its fold
     const int64_t per_chunk = (int64_t)std::min<uint64_t>(samples->bytes / frame_bytes, 0x7fffffffu / wpix);
     for (int64_t done = 0; done < a.frame_count; done += per_chunk) {
@@ -2033,7 +2034,7 @@ static int render_lit(pt_device_t d, const PtLitCall& c)
         fp.frame_count = lp.frame_count = nf;
         // a list: every slot continues from its own frame -- the call's offset, then the frames of the chunks before (no other kind's block holds it)
         ip.frame_off = lp.frame_off = (uint32_t)p.frame0;
-        HIP_TRY(ptk_lit(ip, c.kind, rays, bvh_blocks, search.mode, d->stream));
+        HIP_TRY(ptk_lit(ip, kind, bvh_blocks, search.mode, d->stream));
         // the rays: no fold -- the chunk's moments, in ascending sample order, from zeros at the call's first chunk when it says so
         if (rays) {
             if (c.moments) HIP_TRY(ptk_sample_moments(p.samples, (PtPixelMoments*)c.moments->dptr, wpix, nf, c.reset != 0 && done == 0, d->stream));
@@ -2088,7 +2089,8 @@ static int roulette_args(int mis, const pt_roulette* roulette, pt_buffer_t cdf, 
 extern "C" int pt_render_direct(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
                                 pt_buffer_t framebuffer, const pt_direct_params* params, const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ false, false, false, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    PtLitKind k = {};
+    PtLitCall c = lit_call(k, triangles, materials, lights, nullptr, nullptr, nullptr, samples, framebuffer, cam, ev);
     int rc = use_device(d);
     if (rc || (rc = direct_block(params, c))) return rc;
     return render_lit(d, c);
@@ -2165,7 +2167,8 @@ extern "C" int pt_render_features(pt_device_t d, pt_buffer_t triangles, pt_buffe
 extern "C" int pt_render_indirect(pt_device_t d, pt_buffer_t triangles, pt_buffer_t materials, pt_buffer_t lights, pt_buffer_t samples,
                                   pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, false, false, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
+    PtLitKind k = {}; k.indirect = true;
+    PtLitCall c = lit_call(k, triangles, materials, lights, nullptr, nullptr, nullptr, samples, framebuffer, cam, ev);
     int rc = use_device(d);
     if (rc || (rc = indirect_block(params, c))) return rc;
     return render_lit(d, c);
@@ -2175,8 +2178,8 @@ extern "C" int pt_render_indirect_mis(pt_device_t d, pt_buffer_t triangles, pt_b
                                       pt_buffer_t samples, pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam,
                                       pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, true, false, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
-    c.light_counts = light_counts;
+    PtLitKind k = {}; k.indirect = k.mis = true;
+    PtLitCall c = lit_call(k, triangles, materials, lights, light_counts, nullptr, nullptr, samples, framebuffer, cam, ev);
     int rc = use_device(d);
     if (rc || (rc = indirect_block(params, c))) return rc;
     return render_lit(d, c);
@@ -2187,8 +2190,8 @@ extern "C" int pt_render_direct_power(pt_device_t d, pt_buffer_t triangles, pt_b
                                       pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params* params,
                                       const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ false, false, true, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
-    c.cdf = cdf; c.tri_q = tri_q;
+    PtLitKind k = {}; k.power = true;
+    PtLitCall c = lit_call(k, triangles, materials, lights, nullptr, cdf, tri_q, samples, framebuffer, cam, ev);
     int rc = use_device(d);
     if (rc || (rc = direct_block(params, c))) return rc;
     return render_lit(d, c);
@@ -2199,9 +2202,8 @@ extern "C" int pt_render_indirect_power(pt_device_t d, pt_buffer_t triangles, pt
                                         pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_camera* cam, pt_event_t ev)
 {
     if (mis != 0 && mis != 1) return fail(PT_ERR_INVALID, "mis must be 0 or 1");
-    PtLitCall c = lit_call({ true, mis != 0, true, false, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
-    c.light_counts = mis ? light_counts : nullptr;
-    c.cdf = cdf; c.tri_q = tri_q;
+    PtLitKind k = {}; k.indirect = k.power = true; k.mis = mis != 0;
+    PtLitCall c = lit_call(k, triangles, materials, lights, light_counts, cdf, tri_q, samples, framebuffer, cam, ev);
     int rc = use_device(d);
     if (rc || (rc = indirect_block(params, c))) return rc;
     return render_lit(d, c);
@@ -2213,9 +2215,8 @@ extern "C" int pt_render_indirect_rr(pt_device_t d, pt_buffer_t triangles, pt_bu
                                      pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer,
                                      const pt_indirect_params* params, const pt_roulette* roulette, const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, mis != 0, cdf || tri_q, true, false, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
-    c.light_counts = mis ? light_counts : nullptr;
-    c.cdf = cdf; c.tri_q = tri_q;
+    PtLitKind k = {}; k.indirect = k.rr = true; k.mis = mis != 0; k.power = cdf || tri_q;
+    PtLitCall c = lit_call(k, triangles, materials, lights, light_counts, cdf, tri_q, samples, framebuffer, cam, ev);
     int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
     if (rc || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
     return render_lit(d, c);
@@ -2226,9 +2227,8 @@ extern "C" int pt_render_indirect_pixels(pt_device_t d, pt_buffer_t triangles, p
                                          pt_buffer_t list, uint32_t num_listed, const pt_indirect_params* params, const pt_roulette* roulette,
                                          const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, mis != 0, cdf || tri_q, true, true, false }, triangles, materials, lights, samples, framebuffer, cam, ev);
-    c.light_counts = mis ? light_counts : nullptr;
-    c.cdf = cdf; c.tri_q = tri_q;
+    PtLitKind k = {}; k.indirect = k.rr = k.list = true; k.mis = mis != 0; k.power = cdf || tri_q;
+    PtLitCall c = lit_call(k, triangles, materials, lights, light_counts, cdf, tri_q, samples, framebuffer, cam, ev);
     c.list = list; c.num_listed = num_listed;
     int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
     if (rc || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
@@ -2244,11 +2244,10 @@ extern "C" int pt_radiance_rays(pt_device_t d, pt_buffer_t triangles, pt_buffer_
                                 pt_buffer_t light_counts, pt_buffer_t cdf, pt_buffer_t tri_q, pt_buffer_t rays, pt_buffer_t samples,
                                 pt_buffer_t moments, const pt_radiance_params* params, const pt_roulette* roulette, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, mis != 0, cdf || tri_q, true, false, false }, triangles, materials, lights, samples, nullptr, nullptr, ev);
+    PtLitKind k = {}; k.indirect = k.rr = true; k.mis = mis != 0; k.power = cdf || tri_q;
+    PtLitCall c = lit_call(k, triangles, materials, lights, light_counts, cdf, tri_q, samples, nullptr, nullptr, ev);
     c.from_rays = true;
     c.what = "invalid radiance-query parameters";
-    c.light_counts = mis ? light_counts : nullptr;
-    c.cdf = cdf; c.tri_q = tri_q;
     c.rays = rays; c.moments = moments;
     if (!params) return fail(PT_ERR_INVALID, "params == NULL");
     const pt_radiance_params b = *params;
@@ -2287,8 +2286,8 @@ extern "C" int pt_render_direct_ris(pt_device_t d, pt_buffer_t triangles, pt_buf
                                     pt_buffer_t tri_q, pt_buffer_t samples, pt_buffer_t framebuffer, const pt_direct_params* params,
                                     const pt_ris* ris, const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ false, false, true, false, false, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
-    c.cdf = cdf; c.tri_q = tri_q;
+    PtLitKind k = {}; k.power = k.ris = true;
+    PtLitCall c = lit_call(k, triangles, materials, lights, nullptr, cdf, tri_q, samples, framebuffer, cam, ev);
     int rc = ris_args(ris, cdf, tri_q, params ? params->num_lights : 0, c);
     if (rc || (rc = use_device(d)) || (rc = direct_block(params, c))) return rc;
     return render_lit(d, c);
@@ -2299,9 +2298,8 @@ extern "C" int pt_render_indirect_ris(pt_device_t d, pt_buffer_t triangles, pt_b
                                       const pt_indirect_params* params, const pt_roulette* roulette, const pt_ris* ris, const pt_camera* cam,
                                       pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, mis != 0, true, true, false, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
-    c.light_counts = mis ? light_counts : nullptr;
-    c.cdf = cdf; c.tri_q = tri_q;
+    PtLitKind k = {}; k.indirect = k.rr = k.power = k.ris = true; k.mis = mis != 0;
+    PtLitCall c = lit_call(k, triangles, materials, lights, light_counts, cdf, tri_q, samples, framebuffer, cam, ev);
     int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
     if (rc || (rc = ris_args(ris, cdf, tri_q, params ? params->num_lights : 0, c)) || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
     return render_lit(d, c);
@@ -2312,9 +2310,8 @@ extern "C" int pt_render_indirect_pixels_ris(pt_device_t d, pt_buffer_t triangle
                                              pt_buffer_t framebuffer, pt_buffer_t list, uint32_t num_listed, const pt_indirect_params* params,
                                              const pt_roulette* roulette, const pt_ris* ris, const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, mis != 0, true, true, true, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
-    c.light_counts = mis ? light_counts : nullptr;
-    c.cdf = cdf; c.tri_q = tri_q;
+    PtLitKind k = {}; k.indirect = k.rr = k.list = k.power = k.ris = true; k.mis = mis != 0;
+    PtLitCall c = lit_call(k, triangles, materials, lights, light_counts, cdf, tri_q, samples, framebuffer, cam, ev);
     c.list = list; c.num_listed = num_listed;
     int rc = roulette_args(mis, roulette, cdf, tri_q, params, c);
     if (rc || (rc = ris_args(ris, cdf, tri_q, params ? params->num_lights : 0, c)) || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
@@ -2342,8 +2339,8 @@ extern "C" int pt_render_direct_env(pt_device_t d, pt_buffer_t triangles, pt_buf
                                     pt_buffer_t tri_q, pt_buffer_t env, pt_buffer_t env_cdf, pt_buffer_t samples, pt_buffer_t framebuffer,
                                     const pt_direct_params* params, const pt_environment* environment, const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ false, false, true, false, false, false, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
-    c.cdf = cdf; c.tri_q = tri_q;
+    PtLitKind k = {}; k.power = k.env = true;
+    PtLitCall c = lit_call(k, triangles, materials, lights, nullptr, cdf, tri_q, samples, framebuffer, cam, ev);
     int rc = env_args(environment, env, env_cdf, c);
     if (rc || (rc = use_device(d)) || (rc = direct_block(params, c))) return rc;
     return render_lit(d, c);
@@ -2354,9 +2351,8 @@ extern "C" int pt_render_indirect_env(pt_device_t d, pt_buffer_t triangles, pt_b
                                       pt_buffer_t framebuffer, const pt_indirect_params* params, const pt_roulette* roulette,
                                       const pt_environment* environment, const pt_camera* cam, pt_event_t ev)
 {
-    PtLitCall c = lit_call({ true, true, true, true, false, false, true }, triangles, materials, lights, samples, framebuffer, cam, ev);
-    c.light_counts = light_counts;
-    c.cdf = cdf; c.tri_q = tri_q;
+    PtLitKind k = {}; k.indirect = k.mis = k.rr = k.power = k.env = true;
+    PtLitCall c = lit_call(k, triangles, materials, lights, light_counts, cdf, tri_q, samples, framebuffer, cam, ev);
     int rc = roulette_args(1, roulette, cdf, tri_q, params, c);
     if (rc || (rc = env_args(environment, env, env_cdf, c)) || (rc = use_device(d)) || (rc = indirect_block(params, c))) return rc;
     return render_lit(d, c);
