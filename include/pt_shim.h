@@ -204,7 +204,12 @@ enum pt_option {
      * memory (coalesced across the lanes of a row at every step); 2 = at steps 1 and 2 a workgroup first stages its 32 x 8 pixels
      * and their halo in LDS (larger steps gather as under 1: their halo dwarfs the tile); 0 (default) = the faster of the two per
      * step as measured (profiles/denoise/rates.txt).  Identical bits under every setting. */
-    PT_OPT_DENOISE_TILE = 13
+    PT_OPT_DENOISE_TILE = 13,
+    /* how pt_reproject reaches the previous view's records, for A/B timing and parity tests: 1 = one kernel, every lane reads its
+     * four taps' 56-byte records directly; 2 = a prepare pass first turns the previous view's normal and depth records into one
+     * float4 per pixel in the scratch, the taps read 16 bytes each and the colour record only where a tap survives; 0 (default) =
+     * the faster of the two as measured (profiles/reproject/rates.txt).  Identical bits under every setting. */
+    PT_OPT_REPROJECT_FORM = 14
 };
 int pt_device_set_option(pt_device_t dev, int option, int64_t value);
 int64_t pt_device_get_option(pt_device_t dev, int option);
@@ -1172,6 +1177,94 @@ int pt_denoise(pt_device_t dev, pt_buffer_t colour /* pt_pixel_moments[width x h
                pt_buffer_t albedo, pt_buffer_t normal, pt_buffer_t depth, pt_buffer_t emission /* the same records; each may be NULL */,
                pt_buffer_t scratch, pt_buffer_t out /* float4[width x height]: r, g, b, variance */,
                const pt_denoise_params* params, pt_event_t ev);
+
+/* ---- temporal reprojection: carry the moments across a camera move --------------------------------------------------------
+ * The other half of a preview that survives a camera move: each pixel of the NEW view re-projects its first hit into the PREVIOUS
+ * view and, where the same surface was seen there, takes that view's history -- its radiance moments -- over.  The inputs are records
+ * the library already writes: the lit renderers' moments (pt_sample_moments) as the previous camera saw them, and the normal and depth
+ * moments of pt_render_features under both cameras (depth samples are (t, 1, -dot(n, d)): sum[0] / sum[1] is the mean t over a pixel's
+ * hits, sum[2] / sum[1] the mean incidence cosine).  The scene is static: a pixel's motion comes from the two cameras and its own
+ * depth alone.  out_colour is the history ALONE, as cur_cam sees it; the moments are sums, so the caller accumulates the new camera's
+ * samples on top of it with pt_sample_moments(..., reset = 0).  No reference counterpart; no existing kernel, entry point or image
+ * changes.  The arithmetic below IS the contract: binary32 unless it says binary64, every operation rounded on its own (no
+ * contraction), the IEEE "/" and sqrt, sums in the stated order, every comparison written so that a NaN makes it false.  A
+ * restatement that follows it equals out_colour and out_info bit for bit.
+ *
+ * Here dot(a, b) = ((a[0] * b[0]) + (a[1] * b[1])) + (a[2] * b[2]), and vector operations act component by component.  Both cameras
+ * are derived on the host exactly as pt_camera_derive derives them -- eye, viewDir, holDir, upDir, angle; primed names are prev_cam's
+ * --, and the host forms, once, invWidth = 1.0f / (float)width, invHeight = 1.0f / (float)height, aspect = (float)width /
+ * (float)height and cos_min2 = cos_min * cos_min.  mean(R) of a moment record R is (float)(R.sum[k] / (double)R.n), k = 0 .. 2, or 0
+ * for R.n = 0; depth(R) is (float)(R.sum[0] / R.sum[1]).
+ * Per pixel p = (x, y), index y * width + x.  Every pixel starts as a zero record in out_colour and (0, 0, 0, 0) in out_info; a step
+ * that says "stop" leaves what has been written so far.
+ *  1. D = cur_depth[p].  Unless D.sum[1] > 0, stop (no coverage, no history).  z = depth(D), cz = (float)(D.sum[2] / D.sum[1]).
+ *  2. The pixel-centre ray of cur_cam (GenerateColors.cl:281-284 with the jitter at its centre):
+ *       xs = (2.0f * (((float)x + 0.5f) * invWidth) - 1.0f) * angle * aspect;   ys = -(1.0f - 2.0f * (((float)y + 0.5f) * invHeight)) * angle;
+ *       w = (holDir * xs + upDir * (-1.0f * ys)) + viewDir;   dir = w * (1.0f / sqrt(dot(w, w)));   P = eye + dir * z.
+ *  3. P seen from prev_cam: v = P - eye';  dz = dot(v, viewDir').  Unless dz > 0, stop.
+ *       a = dot(v, holDir') / dz;   b = dot(v, upDir') / dz;
+ *       fx = ((a / (angle' * aspect) + 1.0f) * 0.5f) * (float)width - 0.5f;   fy = ((1.0f - b / angle') * 0.5f) * (float)height - 0.5f;
+ *       r = sqrt(dot(v, v)).
+ *  4. Unless fx > -1 && fx < (float)width && fy > -1 && fy < (float)height, stop.  x0 = (int)floor(fx), tx = fx - (float)x0; y0 and
+ *     ty likewise from fy.  c = cz > 0.125f ? cz : 0.125f.  With both normal buffers given, nc = mean(cur_normal[p]).
+ *  5. Four taps, dy = 0, 1 (outer), dx = 0, 1 (inner), q = (x0 + dx, y0 + dy); Wd, Nn, M[0..2], S[0..2] are binary64 and start at +0:
+ *       - a tap outside the image is skipped;
+ *       - bw = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
+ *       - skipped when prev_colour[q].n == 0, or unless prev_depth[q].sum[1] > 0;
+ *       - the depth test: z_q = depth(prev_depth[q]); skipped unless fabs(z_q - r) * c <= tol_z * r  (the surface the tap saw lies
+ *         at the distance P has from the old eye; the cosine loosens the tolerance on a surface seen at a slant);
+ *       - the normal test, only with both normal buffers given: nq = mean(prev_normal[q]) (neither mean is renormalised);
+ *         Dn = dot(nc, nq); skipped unless Dn > 0 && Dn * Dn >= cos_min2 * (dot(nc, nc) * dot(nq, nq));
+ *       - the noise test, only with max_noise > 0, in binary64 with C = prev_colour[q] and n_q = (double)C.n: m[k] = C.sum[k] / n_q;
+ *         B = 0 for C.n < 2, otherwise with v[k] = (C.sum2[k] - C.sum[k] * m[k]) / (double)(C.n - 1), v[k] = v[k] > 0 ? v[k] : 0
+ *         (pt_moments_resolve's step 1): B = ((v[0] / n_q) + (v[1] / n_q)) + (v[2] / n_q), the squared standard error of the tap's
+ *         mean; skipped unless B <= (double)max_noise * (((m[0] * m[0]) + (m[1] * m[1])) + (m[2] * m[2])).  A record whose mean is
+ *         one rare bright sample among dark ones has B equal to its squared mean, whatever its n: it knows no more than that one
+ *         sample, and a history is not taken from it (the new view's own samples start the pixel afresh);
+ *       - with C = prev_colour[q] and n_q = (double)C.n:  Wd = Wd + (double)bw;  Nn = Nn + (double)bw * n_q;
+ *         M[k] = M[k] + (double)bw * (C.sum[k] / n_q);  S[k] = S[k] + (double)bw * (C.sum2[k] / n_q).
+ *  6. out_info[p] = (fx, fy, (float)Wd, 0).  Unless Wd >= (double)min_weight && Wd > 0, stop.  N = Nn / Wd;
+ *     N = N < (double)max_history ? N : (double)max_history;  n_h = (uint32)floor(N).  When n_h == 0, stop.
+ *  7. out_colour[p]: sum[k] = (M[k] / Wd) * (double)n_h, sum2[k] = (S[k] / Wd) * (double)n_h, n = n_h, rejected = 0;
+ *     out_info[p].w = (float)n_h.
+ * So max_history = 0, and a prev_colour of zero records, write zero records.  With both cameras equal the result is close to, not
+ * equal to, the history capped at max_history: the round trip of steps 2 and 3 is exact to about 1e-4 pixel, not exactly.
+ * Non-finite inputs give what IEEE makes of these expressions.
+ *
+ * scratch: the caller's buffer of pt_reproject_scratch_bytes(width, height) bytes (a function of width x height alone; 0 for an
+ * invalid size); its contents are the build's and unspecified -- here one float4 per pixel of the previous view, (nq, z_q), with a
+ * NaN z_q standing for a tap step 5 skips for what the tap itself holds (no samples, no coverage, the noise test).  PT_OPT_REPROJECT_FORM chooses between that form and one kernel
+ * that reads the records directly; both give the same bits.
+ * Behaviour is pt_denoise's: the handle's stream, behind work in flight, asynchronous (ev); nothing is allocated and the host waits
+ * for nothing; the versions of out_colour, out_info and scratch are bumped.  The image is the WHOLE image.
+ * Errors come before anything is enqueued and leave the buffers untouched: PT_ERR_INVALID for dev, prev_colour, prev_depth,
+ * cur_depth, scratch, out_colour or params NULL, a buffer of another device, width or height < 1, width x height > 2^31 - 1,
+ * max_history < 0, tol_z not finite and > 0, cos_min not finite in [0, 1], min_weight not finite in [0, 1), max_noise not finite
+ * and >= 0, a reserved word not 0,
+ * exactly one of the two normal buffers given, a camera pt_camera_derive rejects, a camera with lens_radius > 0 (the geometry above
+ * is the pinhole's), a moments buffer not 8-byte aligned, out_info or scratch not 16-byte aligned, any two of the buffers
+ * overlapping; PT_ERR_RANGE for a buffer too small (moments: width x height x 56 bytes; out_info: width x height x 16). */
+typedef struct pt_reproject_params {
+    int32_t width, height;        /* the WHOLE image; width x height <= 2^31 - 1, both >= 1 */
+    int32_t max_history;          /* >= 0: the cap on the history length a pixel takes over */
+    float   tol_z;                /* finite, > 0: the relative depth tolerance of a tap */
+    float   cos_min;              /* finite, in [0, 1]: the least cosine between the two mean normals */
+    float   min_weight;           /* finite, in [0, 1): the least sum of the surviving taps' bilinear weights */
+    float   max_noise;            /* finite, >= 0: the largest squared standard error of a tap's mean, relative to its squared mean; 0 = no noise test */
+    int32_t reserved[9];          /* must be 0 */
+} pt_reproject_params;            /* 64 bytes */
+size_t pt_reproject_scratch_bytes(int32_t width, int32_t height);
+int pt_reproject(pt_device_t dev,
+                 pt_buffer_t prev_colour /* pt_pixel_moments[width x height], the history, seen from prev_cam */,
+                 pt_buffer_t prev_normal /* feature moments under prev_cam; may be NULL */,
+                 pt_buffer_t prev_depth /* feature moments under prev_cam; required */,
+                 pt_buffer_t cur_normal /* feature moments under cur_cam; may be NULL */,
+                 pt_buffer_t cur_depth /* feature moments under cur_cam; required */,
+                 pt_buffer_t scratch,
+                 pt_buffer_t out_colour /* pt_pixel_moments[width x height]: the history as cur_cam sees it */,
+                 pt_buffer_t out_info /* float4[width x height], may be NULL: (fx, fy, weight, history length) */,
+                 const pt_reproject_params* params, const pt_camera* prev_cam, const pt_camera* cur_cam /* NULL = the reference's */,
+                 pt_event_t ev);
 
 /* Per-kernel device timing for measurement (bench.py "roofline"): when enabled, every launch of
  * the trace / fold kernels is bracketed by a HIP event pair on the device's stream.

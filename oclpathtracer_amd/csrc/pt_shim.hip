@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "pt_denoise.h"
+#include "pt_reproject.h"
 #include "pt_kernels.h"
 #include "pt_secmask.h"
 
@@ -109,7 +110,7 @@ struct pt_device_s {
     uint64_t used, peak;
     int live_buffers;
     uint64_t workspace;      // device bytes held by this handle for itself (every PtWs below)
-    int64_t opt_batch, opt_chunk, opt_profile, opt_quads, opt_accel, opt_tally, opt_pmask, opt_bvh_stack, opt_lanes, opt_carry, opt_smask, opt_denoise;
+    int64_t opt_batch, opt_chunk, opt_profile, opt_quads, opt_accel, opt_tally, opt_pmask, opt_bvh_stack, opt_lanes, opt_carry, opt_smask, opt_denoise, opt_reproject;
     pt_kernel_s kernels[KERNEL_COUNT];
     PendingFrames pending;
     // ---- the prepared scene, its filter tables and its LBVH (ensure_prep, ensure_bvh, ensure_anchor, prepare_search)
@@ -335,6 +336,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->opt_pmask = PT_DEFAULT_PRIMARY_MASKS;
     d->opt_smask = PT_DEFAULT_SECONDARY_MASKS;
     d->opt_denoise = PT_DENOISE_GATHER_AUTO;
+    d->opt_reproject = PT_REPROJECT_FORM_AUTO;
     d->opt_bvh_stack = 64;
     d->opt_lanes = 2;
     d->opt_carry = 1;
@@ -606,6 +608,10 @@ extern "C" int pt_device_set_option(pt_device_t d, int option, int64_t value)
         if (value < 0 || value > 2) return fail(PT_ERR_INVALID, "the denoiser's gather must be 0 (auto), 1 (global loads) or 2 (LDS tile at steps 1 and 2)");
         d->opt_denoise = value;
         return PT_OK;
+    case PT_OPT_REPROJECT_FORM:
+        if (value < 0 || value > 2) return fail(PT_ERR_INVALID, "the reprojection's form must be 0 (auto), 1 (one kernel over the records) or 2 (a prepare pass first)");
+        d->opt_reproject = value;
+        return PT_OK;
     case PT_OPT_BVH_STACK_LIMIT:
         if (value < 1 || value > 64) return fail(PT_ERR_INVALID, "the LBVH stack limit must be 1..64");
         d->opt_bvh_stack = value;
@@ -638,6 +644,7 @@ extern "C" int64_t pt_device_get_option(pt_device_t d, int option)
     case PT_OPT_PRIMARY_MASKS: return d->opt_pmask;
     case PT_OPT_SECONDARY_MASKS: return d->opt_smask;
     case PT_OPT_DENOISE_TILE: return d->opt_denoise;
+    case PT_OPT_REPROJECT_FORM: return d->opt_reproject;
     case PT_OPT_BVH_STACK_LIMIT: return d->opt_bvh_stack;
     case PT_OPT_RENDER_LANES: return d->opt_lanes;
     case PT_OPT_CHECKPOINT: return d->opt_carry;
@@ -2570,6 +2577,79 @@ extern "C" int pt_denoise(pt_device_t d, pt_buffer_t colour, pt_buffer_t albedo,
                         emission ? emission->dptr : nullptr, (float4*)scratch->dptr, (float4*)out->dptr, a, (int)d->opt_denoise, d->stream));
     scratch->version++;
     out->version++;
+    return event_end(d, ev);
+}
+
+// ---- temporal reprojection (include/pt_shim.h; kernels: pt_reproject.hip) ----------------------------------------------------
+static_assert(sizeof(pt_reproject_params) == 64, "pt_reproject_params layout");
+
+extern "C" size_t pt_reproject_scratch_bytes(int32_t width, int32_t height)
+{
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height > 0x7fffffffull) return 0;
+    return (size_t)width * (size_t)height * sizeof(float4);
+}
+
+static PtReprojectCam reproject_camera(const PtLensCamera& c)
+{
+    PtReprojectCam r;
+    memcpy(r.eye, c.eye, sizeof r.eye);
+    memcpy(r.view, c.view, sizeof r.view);
+    memcpy(r.hol, c.hol, sizeof r.hol);
+    memcpy(r.up, c.up, sizeof r.up);
+    r.angle = c.angle;
+    return r;
+}
+
+extern "C" int pt_reproject(pt_device_t d, pt_buffer_t prev_colour, pt_buffer_t prev_normal, pt_buffer_t prev_depth, pt_buffer_t cur_normal,
+                            pt_buffer_t cur_depth, pt_buffer_t scratch, pt_buffer_t out_colour, pt_buffer_t out_info,
+                            const pt_reproject_params* params, const pt_camera* prev_cam, const pt_camera* cur_cam, pt_event_t ev)
+{
+    int rc = use_device(d);
+    if (rc) return rc;
+    if (!prev_colour || !prev_depth || !cur_depth || !scratch || !out_colour) return fail(PT_ERR_INVALID, "null buffer handle");
+    if ((rc = check_same_device(d, { prev_colour, prev_normal, prev_depth, cur_normal, cur_depth, scratch, out_colour, out_info })) ||
+        (rc = check_event(d, ev)))
+        return rc;
+    if (!params) return fail(PT_ERR_INVALID, "params == NULL");
+    const pt_reproject_params q = *params;
+    const size_t scratch_bytes = pt_reproject_scratch_bytes(q.width, q.height);
+    if (!scratch_bytes) return fail(PT_ERR_INVALID, "invalid image size %d x %d", q.width, q.height);
+    if (q.max_history < 0) return fail(PT_ERR_INVALID, "max_history must be >= 0");
+    if (!(q.tol_z > 0.0f) || !std::isfinite(q.tol_z)) return fail(PT_ERR_INVALID, "tol_z must be finite and > 0");
+    if (!(q.cos_min >= 0.0f && q.cos_min <= 1.0f)) return fail(PT_ERR_INVALID, "cos_min must lie in [0, 1]");
+    if (!(q.min_weight >= 0.0f && q.min_weight < 1.0f)) return fail(PT_ERR_INVALID, "min_weight must lie in [0, 1)");
+    if (!(q.max_noise >= 0.0f) || !std::isfinite(q.max_noise)) return fail(PT_ERR_INVALID, "max_noise must be finite and >= 0");
+    for (int32_t r : q.reserved)
+        if (r != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    if ((prev_normal == nullptr) != (cur_normal == nullptr)) return fail(PT_ERR_INVALID, "the normal test takes both normal buffers or neither");
+    PtLensCamera pc = reference_camera(), cc = reference_camera();
+    if (prev_cam && (rc = camera_derive(prev_cam, &pc))) return rc;
+    if (cur_cam && (rc = camera_derive(cur_cam, &cc))) return rc;
+    if (pc.lens_radius > 0.0f || cc.lens_radius > 0.0f) return fail(PT_ERR_INVALID, "pt_reproject takes pinhole cameras: lens_radius must be 0");
+    const size_t npix = (size_t)q.width * (size_t)q.height, rec = npix * sizeof(pt_pixel_moments);
+    const PtSpan C = { prev_colour, rec, 8, "the previous colour moments" }, PN = { prev_normal, rec, 8, "the previous normal moments" },
+                 PD = { prev_depth, rec, 8, "the previous depth moments" }, CN = { cur_normal, rec, 8, "the current normal moments" },
+                 CD = { cur_depth, rec, 8, "the current depth moments" },
+                 S = { scratch, scratch_bytes, 16, "the scratch (pt_reproject_scratch_bytes)" },
+                 O = { out_colour, rec, 8, "the output moments" }, I = { out_info, npix * 16u, 16, "the output info" };
+    for (const PtSpan& s : { C, PN, PD, CN, CD, S, O, I })
+        if ((rc = span_fits(s))) return rc;
+    for (const PtSpan& s : { C, PN, PD, CN, CD, S, O, I })
+        if ((rc = span_aligned(s))) return rc;
+    if ((rc = spans_apart({ C, PN, PD, CN, CD, S, O, I }))) return rc;
+    if ((rc = enter_stream(d)) || (rc = event_begin(d, ev))) return rc;
+    PtReprojectArgs a;
+    a.width = q.width, a.height = q.height, a.max_history = q.max_history;
+    a.tol_z = q.tol_z, a.cos_min2 = q.cos_min * q.cos_min, a.min_weight = q.min_weight;
+    a.max_noise = q.max_noise;
+    a.inv_width = 1.0f / (float)q.width, a.inv_height = 1.0f / (float)q.height, a.aspect = (float)q.width / (float)q.height;
+    a.prev = reproject_camera(pc), a.cur = reproject_camera(cc);
+    HIP_TRY(ptk_reproject(prev_colour->dptr, prev_normal ? prev_normal->dptr : nullptr, prev_depth->dptr, cur_normal ? cur_normal->dptr : nullptr,
+                          cur_depth->dptr, (float4*)scratch->dptr, out_colour->dptr, out_info ? (float4*)out_info->dptr : nullptr, a,
+                          (int)d->opt_reproject, d->stream));
+    scratch->version++;
+    out_colour->version++;
+    if (out_info) out_info->version++;
     return event_end(d, ev);
 }
 

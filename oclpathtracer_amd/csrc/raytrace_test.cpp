@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only Features | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]] | --only RadianceRays [--mis] [--lights power] [--roulette R[,cap]]] [--noise [--denoise [levels]]] [--lens R[,F]]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only Features | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]] | --only RadianceRays [--mis] [--lights power] [--roulette R[,cap]]] [--noise [--denoise [levels]] [--reproject DX,DY,DZ[,N]]] [--lens R[,F]]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <algorithm>
 #include <chrono>
@@ -127,6 +127,9 @@ struct Options {
     double adaptTol = -1.0;           // --adaptive TOL[,MIN[,MAX]]: IndirectIllumination renders MIN frames, then only the pixels still noisy (< 0 = off)
     int adaptMin = 16, adaptMax = 0;  // MAX 0 = --frames
     int denoise = -1;                 // --denoise [levels]: with --noise, the mean variance before and after pt_denoise (< 0 = off)
+    bool reproject = false;           // --reproject DX,DY,DZ[,N]: with --noise, move eye and centre by the offset and re-project the moments (pt_reproject)
+    float moveBy[3] = { 0.0f, 0.0f, 0.0f };
+    int maxHistory = 32;              // N: pt_reproject_params.max_history
     bool noise = false;               // --noise: DirectIllumination / IndirectIllumination print the image's noise summary
     float lensR = 0.0f, lensF = 0.0f; // --lens R[,F]: AmbientOcclusion / DirectIllumination / IndirectIllumination through a thin lens of radius R focused at F (0 = where the image's centre ray hits)
     std::string scene = "cornellbox.bin", outDir = ".", dump, only;
@@ -512,6 +515,9 @@ static void test_Features(DeviceTest& f, const Options& o)
 // _envsun or _envgrey.
 // With --noise either case renders in calls of at most as many frames as the workspace holds, takes the samples' moments after each
 // (pt_sample_moments) and prints one more line, after the case's own: the summary of pt_moments_resolve.  The image is the same.
+// With --noise --reproject DX,DY,DZ[,N] the case also renders the normal and depth features of the same frames, moves eye and centre by
+// the offset, renders one feature frame from there and re-projects the radiance moments (pt_reproject, the library's default
+// parameters, max_history = N, 32 unless given); it prints one line more: how many pixels took history and its mean length.
 // With --noise --denoise [levels] (5 unless given) the case also renders the first-hit features of the same frames (pt_render_features,
 // their moments by pt_sample_moments), filters the radiance moments with pt_denoise under the library's default parameters and prints
 // one more line: the mean over the pixels of the variance of the pixel's value before (levels = 0) and after the filter.
@@ -760,6 +766,48 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
         }
         std::printf("denoise: levels %d mean_variance unfiltered %.9g filtered %.9g\n", o.denoise, meanVar[0], meanVar[1]);
     }
+    if (o.noise && o.reproject && o.frames > 0) {
+        // the features of the case's frames under its camera, one feature frame numbered on under the moved camera, then the moments
+        // re-projected under the library's default parameters: how many pixels took history, and how much of it
+        pt_camera moved;
+        pt_camera_reference(&moved);
+        for (int k = 0; k < 3; k++) { moved.eye[k] += o.moveBy[k]; moved.center[k] += o.moveBy[k]; }
+        Buffer<float> fs[2] = { Buffer<float>(m_d, 3 * npix * (size_t)chunk), Buffer<float>(m_d, 3 * npix * (size_t)chunk) };
+        Buffer<pt_pixel_moments> fm[4] = { Buffer<pt_pixel_moments>(m_d, npix), Buffer<pt_pixel_moments>(m_d, npix),
+                                           Buffer<pt_pixel_moments>(m_d, npix), Buffer<pt_pixel_moments>(m_d, npix) };   // normal, depth: old, new
+        pt_feature_params fp;
+        std::memset(&fp, 0, sizeof fp);
+        fp.width = dimension; fp.height = dimension;
+        fp.num_triangles = p.num_triangles; fp.num_materials = p.num_materials;
+        fp.stripe_rows = 1; fp.n_ranks = 1; fp.rank = 0;
+        auto features = [&](int first, int count, const pt_camera* c, int set) {
+            fp.frame_begin = first;
+            fp.frame_count = count;
+            IASSERT(pt_render_features(m_d->m_handle, tBuffer.m_handle, mBuffer.m_handle, 0, fs[0].m_handle, fs[1].m_handle, 0, &fp, c, 0) == PT_OK);
+            for (int k = 0; k < 2; k++)
+                IASSERT(pt_sample_moments(m_d->m_handle, fs[k].m_handle, fm[set + k].m_handle, (uint32_t)npix, count, set == 2 || first == 0, 0) == PT_OK);
+        };
+        for (int first = 0; first < o.frames; first += chunk) features(first, o.frames - first < chunk ? o.frames - first : chunk, cam, 0);
+        features(o.frames, 1, &moved, 2);
+        pt_reproject_params rp;
+        std::memset(&rp, 0, sizeof rp);
+        rp.width = dimension; rp.height = dimension;
+        rp.max_history = o.maxHistory;
+        rp.tol_z = 0.05f; rp.cos_min = 0.9f; rp.min_weight = 0.6f; rp.max_noise = 0.5f;
+        Buffer<unsigned char> scratch(m_d, pt_reproject_scratch_bytes(dimension, dimension));
+        Buffer<pt_pixel_moments> carried(m_d, npix);
+        Buffer<float4_t> info(m_d, npix);
+        IASSERT(pt_reproject(m_d->m_handle, moments.m_handle, fm[0].m_handle, fm[1].m_handle, fm[2].m_handle, fm[3].m_handle, scratch.m_handle,
+                             carried.m_handle, info.m_handle, &rp, cam, &moved, 0) == PT_OK);
+        std::vector<float4_t> hi(npix);
+        info.read(hi.data(), npix);
+        DeviceUtils::waitForCompletion(m_d);
+        unsigned long long took = 0;
+        double length = 0.0;
+        for (size_t i = 0; i < npix; i++)
+            if (hi[i].w > 0.0f) { took++; length += hi[i].w; }
+        std::printf("reproject: history pixels %llu of %llu mean_length %.9g\n", took, (unsigned long long)npix, took ? length / (double)took : 0.0);
+    }
     char path[512];
     f.getFilePath(o.outDir.c_str(), bounces ? "indirectIllumination" : "directIllumination", "ppm", path, sizeof path);
     if (mis && std::strlen(path) + 5 < sizeof path) std::strcpy(path + std::strlen(path) - 4, "_mis.ppm");
@@ -886,6 +934,24 @@ int main(int argc, char** argv)
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') o.denoise = std::atoi(argv[++i]);
             if (o.denoise > 8) { std::fprintf(stderr, "--denoise takes 0..8 levels\n"); return 2; }
         }
+        else if (a == "--reproject") {
+            const std::string v = next();
+            char* end = 0;
+            const char* c = v.c_str();
+            bool ok = true;
+            for (int k = 0; k < 3 && ok; k++) {
+                o.moveBy[k] = std::strtof(c, &end);
+                ok = end != c && std::isfinite(o.moveBy[k]) && (k == 2 || *end == ',');
+                c = end + 1;
+            }
+            if (ok && *end == ',') {
+                c = end + 1;
+                o.maxHistory = (int)std::strtol(c, &end, 10);
+                ok = end != c && o.maxHistory >= 0;
+            }
+            if (!ok || *end != 0) { std::fprintf(stderr, "--reproject takes DX,DY,DZ[,N] with finite offsets and N >= 0\n"); return 2; }
+            o.reproject = true;
+        }
         else if (a == "--roulette") {
             const std::string v = next();
             char* end = 0;
@@ -946,6 +1012,10 @@ int main(int argc, char** argv)
     }
     if (o.denoise >= 0 && (!o.noise || o.adaptTol >= 0.0 || (o.only != "DirectIllumination" && o.only != "IndirectIllumination"))) {
         std::fprintf(stderr, "--denoise goes with --only DirectIllumination or IndirectIllumination and --noise, not with --adaptive\n");
+        return 2;
+    }
+    if (o.reproject && (!o.noise || o.adaptTol >= 0.0 || o.lensR > 0.0f || (o.only != "DirectIllumination" && o.only != "IndirectIllumination"))) {
+        std::fprintf(stderr, "--reproject goes with --only DirectIllumination or IndirectIllumination and --noise, with neither --adaptive nor --lens\n");
         return 2;
     }
     if (o.env && o.only == "IndirectIllumination" && !o.mis) { std::fprintf(stderr, "--env with IndirectIllumination needs --mis\n"); return 2; }

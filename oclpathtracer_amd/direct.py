@@ -380,6 +380,15 @@ class DirectRenderer:
 
         return for_renderer(self, **kw)
 
+    def temporal(self, **kw):
+        """A ``temporal.TemporalAccumulator`` on this renderer: ``render(frames)`` as before, and ``move(camera)`` carries the moments
+        across a camera move (``pt_reproject``) instead of starting again.  ``kw`` are ``Reprojector``'s parameters.  ValueError
+        without ``moments=True``, for ``n_ranks != 1`` and with a lens.  The accumulator is the caller's to release, before this
+        renderer."""
+        from .temporal import TemporalAccumulator
+
+        return TemporalAccumulator(self, **kw)
+
     def release(self) -> None:
         for b in (self.lbuf, self.samples, self.fb, self.cdf, self.tri_q, self.mom, self.summary, self.noise_map):
             if b is not None:

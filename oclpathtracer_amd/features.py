@@ -107,16 +107,18 @@ class FeatureRenderer:
         if name not in self.samples:
             raise KeyError("this renderer keeps no %r: its features are %s" % (name, self.features))
 
-    def render(self, frames: int, frame_begin: Optional[int] = None, sync: Optional[adl.SyncObject] = None) -> None:
+    def render(self, frames: int, frame_begin: Optional[int] = None, sync: Optional[adl.SyncObject] = None, *, restart: bool = False) -> None:
         """Enqueue frames [frame_begin, frame_begin + frames) (default: continue after the last call) in calls of at most
         ``workspace_frames`` frames, each followed by the moments of every feature's samples; frame_begin 0 starts the moments afresh.
-        frame_begin must be 0 or ``frames_done``: a frame rendered twice would be counted twice."""
+        frame_begin must be 0 or ``frames_done``: a frame rendered twice would be counted twice.  ``restart``: the moments start
+        afresh at ANY frame_begin -- the image of a new camera whose frames go on where a lit renderer's stand
+        (``temporal.TemporalAccumulator``)."""
         if frame_begin is None:
             frame_begin = self.frames_done
         frames, frame_begin = int(frames), int(frame_begin)
         if frames < 0 or frame_begin < 0 or frame_begin + frames > 0x7fffffff:
             raise ValueError("invalid frame range [%d, %d)" % (frame_begin, frame_begin + frames))
-        if frames > 0 and frame_begin not in (0, self.frames_done):
+        if frames > 0 and not restart and frame_begin not in (0, self.frames_done):
             raise ValueError("a render starts at frame 0 or at frames_done (%d), not at %d" % (self.frames_done, frame_begin))
         cam = ctypes.byref(self._cam) if self._cam is not None else None
         outs = [self.samples[f]._h if f in self.samples else None for f in FEATURES]
@@ -130,7 +132,7 @@ class FeatureRenderer:
                 ev = sync._h if sync is not None and last and i == len(self.features) - 1 else None
                 if self.local_pixels:
                     shim.check(self._lib.pt_sample_moments(self.dev._h, self.samples[f]._h, self.mom[f]._h, self.local_pixels, k,
-                                                           int(first == 0), ev))
+                                                           int(first == 0 or (restart and first == frame_begin)), ev))
             first += k
         if frames > 0:
             self._valid = True

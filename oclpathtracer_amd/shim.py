@@ -20,6 +20,7 @@ PT_OPT_BATCH_FRAMES, PT_OPT_CHUNK_FRAMES, PT_OPT_PROFILE_RETURN_TIME = 0, 1, 2  
 PT_OPT_QUAD_FILTER, PT_OPT_ACCEL, PT_OPT_BVH_TALLY, PT_OPT_PRIMARY_MASKS, PT_OPT_BVH_STACK_LIMIT, PT_OPT_RENDER_LANES, PT_OPT_CHECKPOINT, PT_OPT_BVH_BUILD_COUNT = 4, 5, 6, 7, 8, 9, 10, 11
 PT_OPT_SECONDARY_MASKS = 12
 PT_OPT_DENOISE_TILE = 13   # pt_denoise: 0 = auto, 1 = global gathers, 2 = an LDS halo tile at steps 1 and 2 (identical bits)
+PT_OPT_REPROJECT_FORM = 14   # pt_reproject: 0 = auto, 1 = one kernel over the records, 2 = a prepare pass first (identical bits)
 PT_SHIM_ABI_VERSION = 2  # include/pt_shim.h; load() refuses a library of another version
 PT_MAX_ARG_SIZE = 64
 PT_MAX_ARG_COUNT = 64
@@ -252,6 +253,21 @@ class DenoiseParams(_c.Structure):
 
 assert _c.sizeof(DenoiseParams) == 64
 
+
+class ReprojectParams(_c.Structure):
+    """pt_reproject_params (64 bytes): the whole image, the cap on the history length taken over (>= 0), the relative depth tolerance
+    (finite, > 0), the least cosine between the mean normals (in [0, 1]), the least sum of surviving bilinear weights (in [0, 1)) and
+    the largest squared relative standard error of a tap's mean (finite, >= 0; 0 = no noise test); reserved must be 0."""
+
+    _fields_ = [
+        ("width", _c.c_int32), ("height", _c.c_int32), ("max_history", _c.c_int32),
+        ("tol_z", _c.c_float), ("cos_min", _c.c_float), ("min_weight", _c.c_float), ("max_noise", _c.c_float),
+        ("reserved", _c.c_int32 * 9),
+    ]
+
+
+assert _c.sizeof(ReprojectParams) == 64
+
 # every symbol include/pt_shim.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "pt_last_error": (_c.c_char_p, []),
@@ -341,6 +357,8 @@ SIGNATURES = {
     "pt_radiance_rays": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _H, _c.POINTER(RadianceParams), _c.POINTER(Roulette), _H]),
     "pt_denoise_scratch_bytes": (_c.c_size_t, [_c.c_int32, _c.c_int32]),
     "pt_denoise": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(DenoiseParams), _H]),
+    "pt_reproject_scratch_bytes": (_c.c_size_t, [_c.c_int32, _c.c_int32]),
+    "pt_reproject": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(ReprojectParams), _c.POINTER(Camera), _c.POINTER(Camera), _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
     "pt_profile_query": (_c.c_int, [_H, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)]),
     "pt_bvh_snapshot": (_c.c_int, [_H, _c.POINTER(BvhInfo), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
