@@ -209,7 +209,11 @@ enum pt_option {
      * four taps' 56-byte records directly; 2 = a prepare pass first turns the previous view's normal and depth records into one
      * float4 per pixel in the scratch, the taps read 16 bytes each and the colour record only where a tap survives; 0 (default) =
      * the faster of the two as measured (profiles/reproject/rates.txt).  Identical bits under every setting. */
-    PT_OPT_REPROJECT_FORM = 14
+    PT_OPT_REPROJECT_FORM = 14,
+    /* how the pool pass of pt_denoise_spatial reaches its 7 x 7 taps, for A/B timing and parity tests: 1 = every lane loads its taps'
+     * records and guides from global memory; 2 = a workgroup first stages its 32 x 8 pixels and their halo of 3 in LDS; 0 (default)
+     * = the faster of the two as measured (profiles/denoise_spatial/rates.txt).  Identical bits under every setting. */
+    PT_OPT_DENOISE_SPATIAL_FORM = 15
 };
 int pt_device_set_option(pt_device_t dev, int option, int64_t value);
 int64_t pt_device_get_option(pt_device_t dev, int option);
@@ -1177,6 +1181,49 @@ int pt_denoise(pt_device_t dev, pt_buffer_t colour /* pt_pixel_moments[width x h
                pt_buffer_t albedo, pt_buffer_t normal, pt_buffer_t depth, pt_buffer_t emission /* the same records; each may be NULL */,
                pt_buffer_t scratch, pt_buffer_t out /* float4[width x height]: r, g, b, variance */,
                const pt_denoise_params* params, pt_event_t ev);
+
+/* ---- the denoiser for pixels that hold a single sample: a pooled variance before the levels --------------------------------
+ * pt_denoise's prepare gives a pixel with n < 2 the variance 0: one sample carries none.  A level then forms den_l = eps_l, the
+ * luminance term sends every tap but the centre to weight 0, and the pixel passes through unfiltered -- a one-frame render
+ * whole, and after a camera move (pt_reproject) the pixels that took no history.  pt_denoise_spatial is pt_denoise with one pass
+ * between PREPARE and the levels: a pixel whose own variance is unknown takes the pooled per-sample variance of its guide-similar
+ * 7 x 7 neighbourhood, as the squared standard error of its own mean.  pt_denoise itself, its parameter block, its scratch size
+ * and its bits do not change.  The arithmetic below IS the contract: binary32 unless it says binary64, every operation rounded on
+ * its own (no contraction), the IEEE "/", sums in the stated order.  A restatement that follows it equals `out` bit for bit.
+ *
+ * PREPARE is pt_denoise's, for every pixel.
+ * POOL, per pixel p = (x, y) with 1 <= n_p < below, n_p = colour[p].n:
+ *  - Wn, A[0..2], B[0..2] are binary64 and start at +0; taps dy = -3 .. 3 (outer), dx = -3 .. 3 (inner), q = (x + dx, y + dy), taps
+ *    outside the image skipped:
+ *      the centre tap: w = 1.0f;
+ *      every other tap: X = 0, then in this order
+ *        depth:    t = (gx_p * (float)dx) + (gy_p * (float)dy);  X = X + fabs(z_p - z_q) / (sigma_z * fabs(t) + eps_z)
+ *        albedo, emission: exactly the level's two terms
+ *        (there is NO luminance term: the pixel's noise, which would scale it, is what is being estimated)
+ *      Y = 1.0f + X * 0.0625f;  Y = Y * Y, four times;  w = 1.0f / Y
+ *        normal:   the level's D (clamped at 0, squared normal_squarings times);  w = w * D
+ *      with C = colour[q] and wd = (double)w:  Wn = Wn + wd * (double)C.n;  A[k] = A[k] + wd * C.sum[k];
+ *      B[k] = B[k] + wd * C.sum2[k]   (each product and each sum rounded on its own);
+ *  - per channel: M = A[k] / Wn;  T = M * M;  V = B[k] / Wn - T;  V = V > 0 ? V : +0;  Q[k] = V / (double)n_p;
+ *  - var_p = (float)((Q[0] + Q[1]) + Q[2]).  The centre tap gives Wn >= n_p >= 1 for finite inputs.
+ * A pixel with n_p = 0 or n_p >= below keeps PREPARE's var; c never changes.  A guide that is NULL drops its term as in the levels;
+ * with no guide at all the pool is a 7 x 7 box.
+ * LEVELS are pt_denoise's, run from (c, var); levels = 0 writes (c, var) with the pooled values in channel 3.
+ * Identity: with below <= 1 no pixel is named and the bits of out equal pt_denoise's.  below = 2 names exactly the pixels whose
+ * variance is unknown and is the recommended value: replacing the own two- or three-sample variance of a pixel by the pooled one
+ * measured worse (a firefly's own variance is what lets the levels blur it away; profiles/denoise_spatial/quality.txt).
+ *
+ * Everything pt_denoise documents holds word for word: the buffers, the validation, errors before anything is enqueued, the
+ * behaviour, and the scratch -- still pt_denoise_scratch_bytes (the pass writes one channel of the (c, var) plane).
+ * PT_OPT_DENOISE_SPATIAL_FORM chooses how the pass gathers its taps; every setting gives the same bits.
+ * Errors, added to pt_denoise's: PT_ERR_INVALID for spatial NULL, below < 0, a reserved word of spatial not 0. */
+typedef struct pt_denoise_spatial_params {
+    int32_t below;                /* >= 0: a pixel with 1 <= n < below takes the pooled variance; 0 and 1 name no pixel */
+    int32_t reserved[7];          /* must be 0 */
+} pt_denoise_spatial_params;      /* 32 bytes */
+int pt_denoise_spatial(pt_device_t dev, pt_buffer_t colour, pt_buffer_t albedo, pt_buffer_t normal, pt_buffer_t depth,
+                       pt_buffer_t emission, pt_buffer_t scratch, pt_buffer_t out,
+                       const pt_denoise_params* params, const pt_denoise_spatial_params* spatial, pt_event_t ev);
 
 /* ---- temporal reprojection: carry the moments across a camera move --------------------------------------------------------
  * The other half of a preview that survives a camera move: each pixel of the NEW view re-projects its first hit into the PREVIOUS

@@ -10,6 +10,8 @@
 #define PT_DENOISE_MAX_LEVELS 8
 enum { PT_DENOISE_GUIDE_ALBEDO = 1, PT_DENOISE_GUIDE_NORMAL = 2, PT_DENOISE_GUIDE_DEPTH = 4, PT_DENOISE_GUIDE_EMISSION = 8 };
 enum { PT_DENOISE_GATHER_AUTO = 0, PT_DENOISE_GATHER_GLOBAL = 1, PT_DENOISE_GATHER_LDS = 2 };   // PT_OPT_DENOISE_TILE
+enum { PT_DENOISE_POOL_AUTO = 0, PT_DENOISE_POOL_GLOBAL = 1, PT_DENOISE_POOL_LDS = 2 };         // PT_OPT_DENOISE_SPATIAL_FORM
+#define PT_DENOISE_POOL_RADIUS 3   // pt_denoise_spatial pools over 7 x 7
 
 struct PtDenoiseArgs {
     int32_t width, height, levels, squarings;
@@ -20,3 +22,6 @@ struct PtDenoiseArgs {
 // 56-byte moment records (PtPixelMoments of pt_kernels.h), passed untyped: this header includes none of the renderers'
 hipError_t ptk_denoise(const void* colour, const void* albedo, const void* normal, const void* depth, const void* emission,
                        float4* scratch, float4* out, const PtDenoiseArgs& args, int gather, hipStream_t s);
+// pt_denoise_spatial: the same launches with the pool pass between prepare and level 0; `below` <= 1 names no pixel and skips it
+hipError_t ptk_denoise_spatial(const void* colour, const void* albedo, const void* normal, const void* depth, const void* emission,
+                               float4* scratch, float4* out, const PtDenoiseArgs& args, int32_t below, int gather, int pool_form, hipStream_t s);

@@ -9,6 +9,7 @@
 //   TILE_S = 0     every lane loads its taps from global memory;
 //   TILE_S = 1, 2  the workgroup first stages its pixels and their halo of 2 s, (32 + 4 s) x (8 + 4 s) float4 per plane, in LDS
 //                  (27 648 and 40 960 bytes) and the taps read that.  At s >= 4 the halo dwarfs the tile: those steps gather globally.
+// pt_denoise_spatial runs a third kernel between the two, pt_denoise_pool_kernel (below, with its own comment).
 // No atomics, no flags, nothing the host waits for.
 #include "pt_denoise.h"
 
@@ -235,22 +236,175 @@ __global__ __launch_bounds__(PTD_THREADS) void pt_denoise_level_kernel(const Ptd
     L.cv_out[p] = make_float4(sc0 / sw, sc1 / sw, sc2 / sw, sv / (sw * sw));
 }
 
+// ---- pt_denoise_spatial's POOL (include/pt_shim.h): a pixel with 1 <= n < below takes the pooled per-sample variance of its
+// guide-similar 7 x 7 neighbourhood, over its own n.  One lane per pixel; a lane reads the colour RECORDS of its neighbours and the
+// prepared guide planes, and writes channel .w of its own pixel of (c, var) alone: nothing in the launch reads what it writes.
+// Two forms with the same per-pixel tap order, hence the same bits:
+//   TILE = false  every lane loads its 49 taps from global memory: 52 bytes of a record and up to three float4 a tap;
+//   TILE = true   the workgroup first stages its pixels and their halo of 3, 38 x 14 entries, in LDS -- one array per field, so that
+//                 a row of lanes reads consecutive 4-, 8- and 16-byte words: n 2 128, sum and sum2 12 768 each, three guide planes
+//                 8 512 each, 53 200 bytes.
+// A workgroup none of whose pixels is listed leaves before it stages or gathers anything: one vote, after each lane has read its own
+// n, through a barrier every lane reaches.
+#define PTD_PR PT_DENOISE_POOL_RADIUS
+#define PTD_PW (PTD_TW + 2 * PTD_PR)
+#define PTD_PH (PTD_TH + 2 * PTD_PR)
+#define PTD_PN (PTD_PW * PTD_PH)
+
+struct PtdPool {
+    const PtdRecord* colour;
+    const float4* nz;   // (nrm, z)
+    const float4* ag;   // (a, gx)
+    const float4* eg;   // (e, gy)
+    float4* cv;         // (c, var): .w of a listed pixel is written
+    int32_t width, height, squarings;
+    uint32_t below, guides;
+    float sigma_z, sigma_a, sigma_e, eps_z;
+};
+
+template <bool TILE>
+__global__ __launch_bounds__(PTD_THREADS) void pt_denoise_pool_kernel(const PtdPool P)
+{
+    __shared__ uint32_t vote[PTD_THREADS / 64];
+    __shared__ uint32_t l_n[TILE ? PTD_PN : 1];
+    __shared__ double l_sum[3][TILE ? PTD_PN : 1], l_sum2[3][TILE ? PTD_PN : 1];
+    __shared__ float4 l_g[3][TILE ? PTD_PN : 1];
+    const int width = P.width, height = P.height;
+    const bool g_a = P.guides & PT_DENOISE_GUIDE_ALBEDO, g_n = P.guides & PT_DENOISE_GUIDE_NORMAL, g_z = P.guides & PT_DENOISE_GUIDE_DEPTH,
+               g_e = P.guides & PT_DENOISE_GUIDE_EMISSION;
+    int x0, y0;
+    ptd_tile_origin(width, x0, y0);
+    const int x = x0 + (int)(threadIdx.x % PTD_TW), y = y0 + (int)(threadIdx.x / PTD_TW);
+    const bool inside = x < width && y < height;
+    const size_t p = (size_t)y * (size_t)width + (size_t)x;
+    const uint32_t n_p = inside ? P.colour[p].n : 0u;
+    const bool listed = n_p >= 1u && n_p < P.below;
+
+    // the vote: a wave's ballot, then one word per wave across the barrier (the four words are uniform, so is the exit)
+    const bool wave_any = __ballot(listed) != 0ull;
+    if (threadIdx.x % 64u == 0u) vote[threadIdx.x / 64u] = wave_any;
+    __syncthreads();
+    if (!(vote[0] | vote[1] | vote[2] | vote[3])) return;
+
+    if (TILE) {   // stage the tile and its halo; an entry outside the image is never read (its tap is skipped)
+        for (int i = (int)threadIdx.x; i < PTD_PN; i += PTD_THREADS) {
+            const int hx = x0 - PTD_PR + i % PTD_PW, hy = y0 - PTD_PR + i / PTD_PW;
+            if (hx < 0 || hy < 0 || hx >= width || hy >= height) continue;
+            const size_t q = (size_t)hy * (size_t)width + (size_t)hx;
+            const PtdRecord& m = P.colour[q];
+            l_n[i] = m.n;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) l_sum[k][i] = m.sum[k], l_sum2[k][i] = m.sum2[k];
+            if (g_n || g_z) l_g[0][i] = P.nz[q];
+            if (g_a) l_g[1][i] = P.ag[q];
+            if (g_e) l_g[2][i] = P.eg[q];
+        }
+        __syncthreads();
+    }
+    if (!listed) return;   // (after the last barrier)
+
+    // the centre's guides: gx and gy are needed here alone, so the tile's taps never read (e, gy) without the emission guide
+    const float4 np = g_n || g_z ? P.nz[p] : ptd_zero4();
+    const float4 ap = g_a || g_z ? P.ag[p] : ptd_zero4();
+    const float4 ep = g_e || g_z ? P.eg[p] : ptd_zero4();
+
+    double Wn = 0.0, A[3] = { 0.0, 0.0, 0.0 }, B[3] = { 0.0, 0.0, 0.0 };
+#pragma unroll 1
+    for (int dy = -PTD_PR; dy <= PTD_PR; ++dy) {
+        const int qy = y + dy;
+        if (qy < 0 || qy >= height) continue;
+#pragma unroll
+        for (int dx = -PTD_PR; dx <= PTD_PR; ++dx) {
+            const int qx = x + dx;
+            if (qx < 0 || qx >= width) continue;
+            const size_t q = (size_t)qy * (size_t)width + (size_t)qx;
+            const int li = (qy - y0 + PTD_PR) * PTD_PW + (qx - x0 + PTD_PR);
+            float w;
+            if (dx == 0 && dy == 0) {
+                w = 1.0f;
+            } else {
+                float X = 0.0f;
+                float4 nq = ptd_zero4();
+                if (g_n || g_z) nq = TILE ? l_g[0][TILE ? li : 0] : P.nz[q];
+                if (g_z) {
+                    const float t = (ap.w * (float)dx) + (ep.w * (float)dy);
+                    X = X + __builtin_fabsf(np.w - nq.w) / (P.sigma_z * __builtin_fabsf(t) + P.eps_z);
+                }
+                if (g_a) {
+                    const float4 aq = TILE ? l_g[1][TILE ? li : 0] : P.ag[q];
+                    const float d0 = ap.x - aq.x, d1 = ap.y - aq.y, d2 = ap.z - aq.z;
+                    X = X + (((d0 * d0) + (d1 * d1)) + (d2 * d2)) / P.sigma_a;
+                }
+                if (g_e) {
+                    const float4 eq = TILE ? l_g[2][TILE ? li : 0] : P.eg[q];
+                    const float d0 = ep.x - eq.x, d1 = ep.y - eq.y, d2 = ep.z - eq.z;
+                    X = X + (((d0 * d0) + (d1 * d1)) + (d2 * d2)) / P.sigma_e;
+                }
+                float Y = 1.0f + X * 0.0625f;
+                Y = Y * Y;
+                Y = Y * Y;
+                Y = Y * Y;
+                Y = Y * Y;
+                w = 1.0f / Y;
+                if (g_n) {
+                    float D = ((np.x * nq.x) + (np.y * nq.y)) + (np.z * nq.z);
+                    D = D > 0.0f ? D : 0.0f;
+                    for (int k = 0; k < P.squarings; ++k) D = D * D;
+                    w = w * D;
+                }
+            }
+            const double wd = (double)w;
+            const PtdRecord& m = P.colour[q];
+            Wn = Wn + wd * (double)(TILE ? l_n[TILE ? li : 0] : m.n);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                A[k] = A[k] + wd * (TILE ? l_sum[k][TILE ? li : 0] : m.sum[k]);
+                B[k] = B[k] + wd * (TILE ? l_sum2[k][TILE ? li : 0] : m.sum2[k]);
+            }
+        }
+    }
+    double Q[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double M = A[k] / Wn;
+        const double T = M * M;
+        double V = B[k] / Wn - T;
+        V = V > 0.0 ? V : 0.0;
+        Q[k] = V / (double)n_p;
+    }
+    P.cv[p].w = (float)((Q[0] + Q[1]) + Q[2]);
+}
+
 }   // namespace
 
-hipError_t ptk_denoise(const void* colour, const void* albedo, const void* normal, const void* depth, const void* emission,
-                       float4* scratch, float4* out, const PtDenoiseArgs& a, int gather, hipStream_t s)
+static void ptd_planes(float4* scratch, const PtDenoiseArgs& a, float4*& cv, float4*& nz, float4*& ag, float4*& eg, float4* pong[2],
+                       uint32_t& tiles)
 {
     const size_t npix = (size_t)a.width * (size_t)a.height;
-    const uint32_t tiles = (((uint32_t)a.width + PTD_TW - 1u) / PTD_TW) * (((uint32_t)a.height + PTD_TH - 1u) / PTD_TH);
-    float4* const cv = scratch;
-    float4* const nz = scratch + npix;
-    float4* const ag = scratch + 2 * npix;
-    float4* const eg = scratch + 3 * npix;
-    float4* const pong[2] = { scratch + 4 * npix, scratch + 5 * npix };
+    tiles = (((uint32_t)a.width + PTD_TW - 1u) / PTD_TW) * (((uint32_t)a.height + PTD_TH - 1u) / PTD_TH);
+    cv = scratch, nz = scratch + npix, ag = scratch + 2 * npix, eg = scratch + 3 * npix;
+    pong[0] = scratch + 4 * npix, pong[1] = scratch + 5 * npix;
+}
+
+// prepare: (c, var) into the scratch, or into `out` when no level follows
+static hipError_t ptd_prepare(const void* colour, const void* albedo, const void* normal, const void* depth, const void* emission,
+                              float4* scratch, float4* out, const PtDenoiseArgs& a, hipStream_t s)
+{
+    float4 *cv, *nz, *ag, *eg, *pong[2];
+    uint32_t tiles;
+    ptd_planes(scratch, a, cv, nz, ag, eg, pong, tiles);
     hipLaunchKernelGGL(pt_denoise_prepare_kernel, dim3(tiles), dim3(PTD_THREADS), 0, s, (const PtdRecord*)colour, (const PtdRecord*)albedo,
                        (const PtdRecord*)normal, (const PtdRecord*)depth, (const PtdRecord*)emission, a.levels ? cv : out, nz, ag, eg, a.width,
                        a.height);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+static hipError_t ptd_levels(float4* scratch, float4* out, const PtDenoiseArgs& a, int gather, hipStream_t s)
+{
+    float4 *cv, *nz, *ag, *eg, *pong[2];
+    uint32_t tiles;
+    ptd_planes(scratch, a, cv, nz, ag, eg, pong, tiles);
+    hipError_t e = hipSuccess;
     for (int i = 0; i < a.levels && e == hipSuccess; ++i) {
         PtdLevel L;
         L.cv_in = i == 0 ? cv : pong[(i - 1) & 1];
@@ -268,4 +422,35 @@ hipError_t ptk_denoise(const void* colour, const void* albedo, const void* norma
         e = hipGetLastError();
     }
     return e;
+}
+
+hipError_t ptk_denoise(const void* colour, const void* albedo, const void* normal, const void* depth, const void* emission,
+                       float4* scratch, float4* out, const PtDenoiseArgs& a, int gather, hipStream_t s)
+{
+    const hipError_t e = ptd_prepare(colour, albedo, normal, depth, emission, scratch, out, a, s);
+    return e == hipSuccess ? ptd_levels(scratch, out, a, gather, s) : e;
+}
+
+hipError_t ptk_denoise_spatial(const void* colour, const void* albedo, const void* normal, const void* depth, const void* emission,
+                               float4* scratch, float4* out, const PtDenoiseArgs& a, int32_t below, int gather, int pool_form, hipStream_t s)
+{
+    hipError_t e = ptd_prepare(colour, albedo, normal, depth, emission, scratch, out, a, s);
+    if (e == hipSuccess && below > 1) {   // (0 and 1 name no pixel)
+        float4 *cv, *nz, *ag, *eg, *pong[2];
+        uint32_t tiles;
+        ptd_planes(scratch, a, cv, nz, ag, eg, pong, tiles);
+        PtdPool P;
+        P.colour = (const PtdRecord*)colour;
+        P.nz = nz, P.ag = ag, P.eg = eg;
+        P.cv = a.levels ? cv : out;
+        P.width = a.width, P.height = a.height, P.squarings = a.squarings;
+        P.below = (uint32_t)below, P.guides = a.guides;
+        P.sigma_z = a.sigma_z, P.sigma_a = a.sigma_a, P.sigma_e = a.sigma_e, P.eps_z = a.eps_z;
+        // PT_DENOISE_POOL_AUTO is the faster form as measured on the MI355X (profiles/denoise_spatial/rates.txt): at 1024^2 with every
+        // pixel listed the tile takes 0.19 ms, the global gathers 0.75 ms; with 3 % listed after a camera move both take 0.18 ms
+        if (pool_form == PT_DENOISE_POOL_GLOBAL) hipLaunchKernelGGL(pt_denoise_pool_kernel<false>, dim3(tiles), dim3(PTD_THREADS), 0, s, P);
+        else hipLaunchKernelGGL(pt_denoise_pool_kernel<true>, dim3(tiles), dim3(PTD_THREADS), 0, s, P);
+        e = hipGetLastError();
+    }
+    return e == hipSuccess ? ptd_levels(scratch, out, a, gather, s) : e;
 }

@@ -110,7 +110,7 @@ struct pt_device_s {
     uint64_t used, peak;
     int live_buffers;
     uint64_t workspace;      // device bytes held by this handle for itself (every PtWs below)
-    int64_t opt_batch, opt_chunk, opt_profile, opt_quads, opt_accel, opt_tally, opt_pmask, opt_bvh_stack, opt_lanes, opt_carry, opt_smask, opt_denoise, opt_reproject;
+    int64_t opt_batch, opt_chunk, opt_profile, opt_quads, opt_accel, opt_tally, opt_pmask, opt_bvh_stack, opt_lanes, opt_carry, opt_smask, opt_denoise, opt_reproject, opt_denoise_spatial;
     pt_kernel_s kernels[KERNEL_COUNT];
     PendingFrames pending;
     // ---- the prepared scene, its filter tables and its LBVH (ensure_prep, ensure_bvh, ensure_anchor, prepare_search)
@@ -336,6 +336,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->opt_pmask = PT_DEFAULT_PRIMARY_MASKS;
     d->opt_smask = PT_DEFAULT_SECONDARY_MASKS;
     d->opt_denoise = PT_DENOISE_GATHER_AUTO;
+    d->opt_denoise_spatial = PT_DENOISE_POOL_AUTO;
     d->opt_reproject = PT_REPROJECT_FORM_AUTO;
     d->opt_bvh_stack = 64;
     d->opt_lanes = 2;
@@ -612,6 +613,10 @@ extern "C" int pt_device_set_option(pt_device_t d, int option, int64_t value)
         if (value < 0 || value > 2) return fail(PT_ERR_INVALID, "the reprojection's form must be 0 (auto), 1 (one kernel over the records) or 2 (a prepare pass first)");
         d->opt_reproject = value;
         return PT_OK;
+    case PT_OPT_DENOISE_SPATIAL_FORM:
+        if (value < 0 || value > 2) return fail(PT_ERR_INVALID, "the pool pass's form must be 0 (auto), 1 (global loads) or 2 (LDS tile)");
+        d->opt_denoise_spatial = value;
+        return PT_OK;
     case PT_OPT_BVH_STACK_LIMIT:
         if (value < 1 || value > 64) return fail(PT_ERR_INVALID, "the LBVH stack limit must be 1..64");
         d->opt_bvh_stack = value;
@@ -645,6 +650,7 @@ extern "C" int64_t pt_device_get_option(pt_device_t d, int option)
     case PT_OPT_SECONDARY_MASKS: return d->opt_smask;
     case PT_OPT_DENOISE_TILE: return d->opt_denoise;
     case PT_OPT_REPROJECT_FORM: return d->opt_reproject;
+    case PT_OPT_DENOISE_SPATIAL_FORM: return d->opt_denoise_spatial;
     case PT_OPT_BVH_STACK_LIMIT: return d->opt_bvh_stack;
     case PT_OPT_RENDER_LANES: return d->opt_lanes;
     case PT_OPT_CHECKPOINT: return d->opt_carry;
@@ -2541,8 +2547,10 @@ extern "C" size_t pt_denoise_scratch_bytes(int32_t width, int32_t height)
     return (size_t)width * (size_t)height * PT_DENOISE_PLANES * sizeof(float4);
 }
 
-extern "C" int pt_denoise(pt_device_t d, pt_buffer_t colour, pt_buffer_t albedo, pt_buffer_t normal, pt_buffer_t depth, pt_buffer_t emission,
-                          pt_buffer_t scratch, pt_buffer_t out, const pt_denoise_params* params, pt_event_t ev)
+// pt_denoise (spatial_call false: `spatial` is not looked at) and pt_denoise_spatial: one validation, one enqueue
+static int denoise_call(pt_device_t d, pt_buffer_t colour, pt_buffer_t albedo, pt_buffer_t normal, pt_buffer_t depth, pt_buffer_t emission,
+                        pt_buffer_t scratch, pt_buffer_t out, const pt_denoise_params* params, bool spatial_call,
+                        const pt_denoise_spatial_params* spatial, pt_event_t ev)
 {
     int rc = use_device(d);
     if (rc) return rc;
@@ -2558,6 +2566,14 @@ extern "C" int pt_denoise(pt_device_t d, pt_buffer_t colour, pt_buffer_t albedo,
         if (!(v > 0.0f) || !std::isfinite(v)) return fail(PT_ERR_INVALID, "every sigma and eps must be finite and > 0");
     for (int32_t r : q.reserved)
         if (r != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+    int32_t below = 0;
+    if (spatial_call) {
+        if (!spatial) return fail(PT_ERR_INVALID, "spatial == NULL");
+        if (spatial->below < 0) return fail(PT_ERR_INVALID, "below must be >= 0");
+        for (int32_t r : spatial->reserved)
+            if (r != 0) return fail(PT_ERR_INVALID, "reserved fields must be zero");
+        below = spatial->below;
+    }
     const size_t npix = (size_t)q.width * (size_t)q.height, rec = npix * sizeof(pt_pixel_moments);
     const PtSpan C = { colour, rec, 8, "the colour moments" }, A = { albedo, rec, 8, "the albedo moments" }, N = { normal, rec, 8, "the normal moments" },
                  Z = { depth, rec, 8, "the depth moments" }, E = { emission, rec, 8, "the emission moments" },
@@ -2573,11 +2589,31 @@ extern "C" int pt_denoise(pt_device_t d, pt_buffer_t colour, pt_buffer_t albedo,
     a.guides = (albedo ? PT_DENOISE_GUIDE_ALBEDO : 0u) | (normal ? PT_DENOISE_GUIDE_NORMAL : 0u) | (depth ? PT_DENOISE_GUIDE_DEPTH : 0u) |
                (emission ? PT_DENOISE_GUIDE_EMISSION : 0u);
     a.sigma_l = q.sigma_l, a.sigma_z = q.sigma_z, a.sigma_a = q.sigma_a, a.sigma_e = q.sigma_e, a.eps_l = q.eps_l, a.eps_z = q.eps_z;
-    HIP_TRY(ptk_denoise(colour->dptr, albedo ? albedo->dptr : nullptr, normal ? normal->dptr : nullptr, depth ? depth->dptr : nullptr,
-                        emission ? emission->dptr : nullptr, (float4*)scratch->dptr, (float4*)out->dptr, a, (int)d->opt_denoise, d->stream));
+    const void *ca = albedo ? albedo->dptr : nullptr, *cn = normal ? normal->dptr : nullptr, *cz = depth ? depth->dptr : nullptr,
+               *ce = emission ? emission->dptr : nullptr;
+    if (spatial_call)
+        HIP_TRY(ptk_denoise_spatial(colour->dptr, ca, cn, cz, ce, (float4*)scratch->dptr, (float4*)out->dptr, a, below, (int)d->opt_denoise,
+                                    (int)d->opt_denoise_spatial, d->stream));
+    else
+        HIP_TRY(ptk_denoise(colour->dptr, ca, cn, cz, ce, (float4*)scratch->dptr, (float4*)out->dptr, a, (int)d->opt_denoise, d->stream));
     scratch->version++;
     out->version++;
     return event_end(d, ev);
+}
+
+extern "C" int pt_denoise(pt_device_t d, pt_buffer_t colour, pt_buffer_t albedo, pt_buffer_t normal, pt_buffer_t depth, pt_buffer_t emission,
+                          pt_buffer_t scratch, pt_buffer_t out, const pt_denoise_params* params, pt_event_t ev)
+{
+    return denoise_call(d, colour, albedo, normal, depth, emission, scratch, out, params, false, nullptr, ev);
+}
+
+static_assert(sizeof(pt_denoise_spatial_params) == 32, "pt_denoise_spatial_params layout");
+
+extern "C" int pt_denoise_spatial(pt_device_t d, pt_buffer_t colour, pt_buffer_t albedo, pt_buffer_t normal, pt_buffer_t depth,
+                                  pt_buffer_t emission, pt_buffer_t scratch, pt_buffer_t out, const pt_denoise_params* params,
+                                  const pt_denoise_spatial_params* spatial, pt_event_t ev)
+{
+    return denoise_call(d, colour, albedo, normal, depth, emission, scratch, out, params, true, spatial, ev);
 }
 
 // ---- temporal reprojection (include/pt_shim.h; kernels: pt_reproject.hip) ----------------------------------------------------

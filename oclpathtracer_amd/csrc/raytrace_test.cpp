@@ -10,7 +10,7 @@
 // the reference hard-codes (512 x 512, 10 000 frames, ../test/cornellbox.bin) are options here.
 //
 //   raytrace_test [--device N] [--dim 512] [--frames 10000] [--scene cornellbox.bin]
-//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only Features | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]] | --only RadianceRays [--mis] [--lights power] [--roulette R[,cap]]] [--noise [--denoise [levels]] [--reproject DX,DY,DZ[,N]]] [--lens R[,F]]
+//                 [--out-dir .] [--dump fb.raw] [--no-batch] [--only RayCast | --only AmbientOcclusion | --only Features | --only DirectIllumination [--lights power [--candidates M | --env sun|grey[,Ke]]] | --only IndirectIllumination [--mis] [--lights power [--candidates M | --env sun|grey[,Ke]]] [--roulette R[,cap]] [--adaptive TOL[,MIN[,MAX]]] | --only RadianceRays [--mis] [--lights power] [--roulette R[,cap]]] [--noise [--denoise [levels] [--spatial [N]]] [--reproject DX,DY,DZ[,N]]] [--lens R[,F]]
 // Exit code 0 = every check passed.  Own code; no gtest.
 #include <algorithm>
 #include <chrono>
@@ -127,6 +127,7 @@ struct Options {
     double adaptTol = -1.0;           // --adaptive TOL[,MIN[,MAX]]: IndirectIllumination renders MIN frames, then only the pixels still noisy (< 0 = off)
     int adaptMin = 16, adaptMax = 0;  // MAX 0 = --frames
     int denoise = -1;                 // --denoise [levels]: with --noise, the mean variance before and after pt_denoise (< 0 = off)
+    int spatial = -1;                 // --spatial [N]: with --denoise, pt_denoise_spatial with below = N (2 unless given; < 0 = pt_denoise)
     bool reproject = false;           // --reproject DX,DY,DZ[,N]: with --noise, move eye and centre by the offset and re-project the moments (pt_reproject)
     float moveBy[3] = { 0.0f, 0.0f, 0.0f };
     int maxHistory = 32;              // N: pt_reproject_params.max_history
@@ -521,6 +522,8 @@ static void test_Features(DeviceTest& f, const Options& o)
 // With --noise --denoise [levels] (5 unless given) the case also renders the first-hit features of the same frames (pt_render_features,
 // their moments by pt_sample_moments), filters the radiance moments with pt_denoise under the library's default parameters and prints
 // one more line: the mean over the pixels of the variance of the pixel's value before (levels = 0) and after the filter.
+// With --spatial [N] (2 unless given) on top both calls are pt_denoise_spatial with below = N, and the line gains N and the count of
+// pixels that took the pooled variance (1 <= n < N).
 // With --adaptive TOL[,MIN[,MAX]] IndirectIllumination renders MIN frames (16 unless given) as above, then pass by pass lists the pixels
 // whose own relative standard error lies above TOL and that have fewer than MAX samples (--frames unless given) with
 // pt_adaptive_select, renders one workspace of further frames of the listed pixels with pt_render_indirect_pixels and counts them with
@@ -751,20 +754,37 @@ static void test_Illumination(DeviceTest& f, const Options& o, int bounces)
         dp.normal_squarings = 7;
         dp.sigma_l = 4.0f; dp.sigma_z = 1.0f; dp.sigma_a = 0.01f; dp.sigma_e = 0.01f;
         dp.eps_l = 1e-6f; dp.eps_z = 1e-4f;
+        pt_denoise_spatial_params sp;
+        std::memset(&sp, 0, sizeof sp);
+        sp.below = o.spatial >= 0 ? o.spatial : 0;
         Buffer<unsigned char> scratch(m_d, pt_denoise_scratch_bytes(dimension, dimension));
         Buffer<float4_t> filtered(m_d, npix);
         std::vector<float4_t> hf(npix);
         double meanVar[2] = { 0.0, 0.0 };
         for (int pass = 0; pass < 2; pass++) {
             dp.levels = pass ? o.denoise : 0;
-            IASSERT(pt_denoise(m_d->m_handle, moments.m_handle, fm[0].m_handle, fm[1].m_handle, fm[2].m_handle, fm[3].m_handle, scratch.m_handle,
-                               filtered.m_handle, &dp, 0) == PT_OK);
+            if (o.spatial >= 0)
+                IASSERT(pt_denoise_spatial(m_d->m_handle, moments.m_handle, fm[0].m_handle, fm[1].m_handle, fm[2].m_handle, fm[3].m_handle,
+                                           scratch.m_handle, filtered.m_handle, &dp, &sp, 0) == PT_OK);
+            else
+                IASSERT(pt_denoise(m_d->m_handle, moments.m_handle, fm[0].m_handle, fm[1].m_handle, fm[2].m_handle, fm[3].m_handle, scratch.m_handle,
+                                   filtered.m_handle, &dp, 0) == PT_OK);
             filtered.read(hf.data(), npix);
             DeviceUtils::waitForCompletion(m_d);
             for (size_t i = 0; i < npix; i++) meanVar[pass] += hf[i].w;
             meanVar[pass] /= (double)npix;
         }
-        std::printf("denoise: levels %d mean_variance unfiltered %.9g filtered %.9g\n", o.denoise, meanVar[0], meanVar[1]);
+        if (o.spatial >= 0) {
+            std::vector<pt_pixel_moments> hm(npix);
+            moments.read(hm.data(), npix);
+            DeviceUtils::waitForCompletion(m_d);
+            unsigned long long pooled = 0;
+            for (size_t i = 0; i < npix; i++) pooled += hm[i].n >= 1u && hm[i].n < (uint32_t)o.spatial;
+            std::printf("denoise: levels %d mean_variance unfiltered %.9g filtered %.9g spatial below %d pooled_pixels %llu\n", o.denoise, meanVar[0],
+                        meanVar[1], o.spatial, pooled);
+        }
+        else
+            std::printf("denoise: levels %d mean_variance unfiltered %.9g filtered %.9g\n", o.denoise, meanVar[0], meanVar[1]);
     }
     if (o.noise && o.reproject && o.frames > 0) {
         // the features of the case's frames under its camera, one feature frame numbered on under the moved camera, then the moments
@@ -934,6 +954,10 @@ int main(int argc, char** argv)
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') o.denoise = std::atoi(argv[++i]);
             if (o.denoise > 8) { std::fprintf(stderr, "--denoise takes 0..8 levels\n"); return 2; }
         }
+        else if (a == "--spatial") {
+            o.spatial = 2;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') o.spatial = std::atoi(argv[++i]);
+        }
         else if (a == "--reproject") {
             const std::string v = next();
             char* end = 0;
@@ -1014,6 +1038,7 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--denoise goes with --only DirectIllumination or IndirectIllumination and --noise, not with --adaptive\n");
         return 2;
     }
+    if (o.spatial >= 0 && o.denoise < 0) { std::fprintf(stderr, "--spatial goes with --denoise\n"); return 2; }
     if (o.reproject && (!o.noise || o.adaptTol >= 0.0 || o.lensR > 0.0f || (o.only != "DirectIllumination" && o.only != "IndirectIllumination"))) {
         std::fprintf(stderr, "--reproject goes with --only DirectIllumination or IndirectIllumination and --noise, with neither --adaptive nor --lens\n");
         return 2;

@@ -5,6 +5,9 @@ normal, depth and emission over the same jittered samples.
 ``levels`` passes of one 5 x 5 kernel whose taps lie ``1 << i`` pixels apart in pass i; a tap counts for less the further its depth,
 albedo, emission, normal and -- measured against the pixel's own noise -- luminance lie from the centre's.  The result is the filtered
 mean radiance (linear, not the gamma framebuffer) and, in the fourth channel, the variance the filter leaves in it.
+A pixel that holds ONE sample has no variance of its own: the filter leaves it as it is -- a one-frame render whole, and after a camera
+move the pixels that took no history.  ``spatial_below=SPATIAL_BELOW`` (``pt_denoise_spatial``) gives such pixels the pooled variance of
+their guide-similar 7 x 7 neighbourhood before the levels run, so that they are filtered like their neighbours.
 ``include/pt_shim.h`` states every expression.  All compute is HIP in libptshim.so; nothing here has a CPU fallback.
 """
 from __future__ import annotations
@@ -20,14 +23,22 @@ from .features import FEATURES, FeatureRenderer
 # the starting values of the numpy prototype the filter was designed on (Cornell box, 48 x 48, 8 frames: the relative MSE falls to
 # 0.025 of the unfiltered mean's; profiles/denoise/quality.txt)
 DEFAULTS = dict(levels=5, sigma_l=4.0, sigma_z=1.0, sigma_a=0.01, sigma_e=0.01, eps_l=1e-6, eps_z=1e-4, normal_squarings=7)
+# the recommended ``spatial_below``: exactly the pixels whose variance is unknown (n = 1).  On the same Cornell data one frame's median
+# relative MSE after the filter falls from 0.128 to 0.023; values above 2 measured WORSE (two frames: mean 0.21 -> 0.73 at 4, because a
+# firefly's own two-sample variance is what lets the levels blur it away; profiles/denoise_spatial/quality.txt)
+SPATIAL_BELOW = 2
 
 
 class Denoiser:
     """The filter for ``width`` x ``height`` images on ``dev``: owns the scratch and the output, sized once.  The parameters are
-    ``pt_denoise_params``' and are refused here as the library refuses them."""
+    ``pt_denoise_params``' and are refused here as the library refuses them.  ``spatial_below``: 0 (the default) calls ``pt_denoise``,
+    which leaves one-sample pixels unfiltered; anything else calls ``pt_denoise_spatial`` with that ``below`` -- a pixel with
+    ``1 <= n < spatial_below`` takes the pooled variance of its neighbourhood.  ``SPATIAL_BELOW`` (2) is the recommended value; values
+    above 2 measured worse here."""
 
     def __init__(self, dev: adl.Device, width: int, height: int, *, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 1.0,
-                 sigma_a: float = 0.01, sigma_e: float = 0.01, eps_l: float = 1e-6, eps_z: float = 1e-4, normal_squarings: int = 7):
+                 sigma_a: float = 0.01, sigma_e: float = 0.01, eps_l: float = 1e-6, eps_z: float = 1e-4, normal_squarings: int = 7,
+                 spatial_below: int = 0):
         self.dev = dev
         self._lib = shim.load()
         self.width, self.height = int(width), int(height)
@@ -42,7 +53,13 @@ class Denoiser:
             v = float(getattr(p, name))   # (as binary32 holds it)
             if not (v > 0.0 and math.isfinite(v)):
                 raise ValueError("%s must be finite and > 0 in binary32" % name)
+        if isinstance(spatial_below, bool) or int(spatial_below) != spatial_below or not 0 <= int(spatial_below) <= 0x7fffffff:
+            raise ValueError("spatial_below must be an integer in 0 .. 2^31 - 1")
         self.params = p
+        self.spatial = None
+        if int(spatial_below):
+            self.spatial = shim.DenoiseSpatialParams()
+            self.spatial.below = int(spatial_below)
         self.pixels = self.width * self.height
         self.scratch = self.out = self._sync = None
         self.scratch = adl.Buffer(dev, self._lib.pt_denoise_scratch_bytes(self.width, self.height), np.uint8)
@@ -65,7 +82,11 @@ class Denoiser:
         return [features.mom[f]._h if f in features.mom else None for f in FEATURES]
 
     def _enqueue(self, colour: adl.Buffer, features, out_h, ev) -> None:
-        shim.check(self._lib.pt_denoise(self.dev._h, colour._h, *self._guides(features), self.scratch._h, out_h, ctypes.byref(self.params), ev))
+        if self.spatial is None:
+            shim.check(self._lib.pt_denoise(self.dev._h, colour._h, *self._guides(features), self.scratch._h, out_h, ctypes.byref(self.params), ev))
+        else:
+            shim.check(self._lib.pt_denoise_spatial(self.dev._h, colour._h, *self._guides(features), self.scratch._h, out_h,
+                                                    ctypes.byref(self.params), ctypes.byref(self.spatial), ev))
 
     def denoise(self, colour: adl.Buffer, features=None, *, as_tensor: bool = False):
         """Filter the image whose moments ``colour`` holds (``pt_pixel_moments[width * height]``: a lit renderer's ``mom``), guided by
@@ -103,7 +124,8 @@ class Denoiser:
 
 def for_renderer(renderer, **kw):
     """``(Denoiser, FeatureRenderer)`` for a lit renderer that keeps moments (``DirectRenderer.denoiser``): the feature renderer
-    keeps all four features, shares the renderer's scene buffers and camera and is brought to the renderer's frame count."""
+    keeps all four features, shares the renderer's scene buffers and camera and is brought to the renderer's frame count.  ``kw`` are
+    ``Denoiser``'s, ``spatial_below`` among them."""
     if renderer.n_ranks != 1:
         raise ValueError("the denoiser filters whole images: n_ranks must be 1 (a rank's stripes are not an image)")
     if not renderer.moments:

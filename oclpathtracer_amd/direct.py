@@ -374,7 +374,8 @@ class DirectRenderer:
         """``(Denoiser, FeatureRenderer)`` for this renderer's image (``denoise.for_renderer``): the feature renderer keeps albedo,
         normal, depth and emission, shares this renderer's scene buffers and camera and has rendered ``frames_done`` frames;
         ``d.denoise(self.mom, f)`` filters the image (render both on by the same number of frames before the next call).  ``kw`` are
-        ``Denoiser``'s parameters.  ValueError for ``n_ranks != 1`` -- a rank's stripes are not a whole image -- and without
+        ``Denoiser``'s parameters, among them ``spatial_below`` (``denoise.SPATIAL_BELOW`` filters one-sample pixels too; at the default
+        0 they pass through unfiltered).  ValueError for ``n_ranks != 1`` -- a rank's stripes are not a whole image -- and without
         ``moments=True``.  Both objects are the caller's to release, before this renderer."""
         from .denoise import for_renderer
 

@@ -21,6 +21,7 @@ PT_OPT_QUAD_FILTER, PT_OPT_ACCEL, PT_OPT_BVH_TALLY, PT_OPT_PRIMARY_MASKS, PT_OPT
 PT_OPT_SECONDARY_MASKS = 12
 PT_OPT_DENOISE_TILE = 13   # pt_denoise: 0 = auto, 1 = global gathers, 2 = an LDS halo tile at steps 1 and 2 (identical bits)
 PT_OPT_REPROJECT_FORM = 14   # pt_reproject: 0 = auto, 1 = one kernel over the records, 2 = a prepare pass first (identical bits)
+PT_OPT_DENOISE_SPATIAL_FORM = 15   # pt_denoise_spatial's pool pass: 0 = auto, 1 = global gathers, 2 = an LDS tile with halo 3 (identical bits)
 PT_SHIM_ABI_VERSION = 2  # include/pt_shim.h; load() refuses a library of another version
 PT_MAX_ARG_SIZE = 64
 PT_MAX_ARG_COUNT = 64
@@ -254,6 +255,16 @@ class DenoiseParams(_c.Structure):
 assert _c.sizeof(DenoiseParams) == 64
 
 
+class DenoiseSpatialParams(_c.Structure):
+    """pt_denoise_spatial_params (32 bytes): a pixel with 1 <= n < below takes the pooled variance of its 7 x 7 neighbourhood (>= 0;
+    0 and 1 name no pixel); reserved must be 0."""
+
+    _fields_ = [("below", _c.c_int32), ("reserved", _c.c_int32 * 7)]
+
+
+assert _c.sizeof(DenoiseSpatialParams) == 32
+
+
 class ReprojectParams(_c.Structure):
     """pt_reproject_params (64 bytes): the whole image, the cap on the history length taken over (>= 0), the relative depth tolerance
     (finite, > 0), the least cosine between the mean normals (in [0, 1]), the least sum of surviving bilinear weights (in [0, 1)) and
@@ -357,6 +368,7 @@ SIGNATURES = {
     "pt_radiance_rays": (_c.c_int, [_H, _H, _H, _H, _c.c_int, _H, _H, _H, _H, _H, _H, _c.POINTER(RadianceParams), _c.POINTER(Roulette), _H]),
     "pt_denoise_scratch_bytes": (_c.c_size_t, [_c.c_int32, _c.c_int32]),
     "pt_denoise": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(DenoiseParams), _H]),
+    "pt_denoise_spatial": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(DenoiseParams), _c.POINTER(DenoiseSpatialParams), _H]),
     "pt_reproject_scratch_bytes": (_c.c_size_t, [_c.c_int32, _c.c_int32]),
     "pt_reproject": (_c.c_int, [_H, _H, _H, _H, _H, _H, _H, _H, _H, _c.POINTER(ReprojectParams), _c.POINTER(Camera), _c.POINTER(Camera), _H]),
     "pt_profile_enable": (_c.c_int, [_H, _c.c_int]),
