@@ -271,6 +271,9 @@ hipError_t ptk_math(const float* in, float* out, int n, hipStream_t s);
 hipError_t ptk_fold_check(unsigned long long* out, int mode, unsigned first, unsigned long long count, hipStream_t s);
 // pt_shade's short forms -- the guarded quotients, 1 / sqrt -- against the literal operations (pt_shade_check_kernel); out: 8 counters
 hipError_t ptk_shade_check(unsigned long long* out, int mode, unsigned first, unsigned long long count, hipStream_t s);
+// the masked search's pending-pair list on given masks (pt_pair_check_kernel): masks: cases x 64 lanes x {low, high word};
+// out: cases x (2 + cap) words -- pairs, rounds, then the pairs (triangle << 6 | ray lane) in the order the rounds test them
+hipError_t ptk_pair_check(const uint2* masks, unsigned* out, int ntri, unsigned cases, unsigned cap, hipStream_t s);
 // batched ray queries (pt_intersect_rays): t carries the search -- the prepared scene (tris, ntri), the filter of the table the
 // two-pass search runs over (quad_delta1 .. p1_hi, its anchor in cam.eye), the LBVH (bvh .. nbig, bvh_flags, bvh_stack_limit);
 // the other fields of t are not read

@@ -595,6 +595,20 @@ PTK_DEV void pt_tri_pass2(const PtTriRec& r, int i, bool valid, const f3& o, con
     hidx = ok ? i : hidx;
 }
 
+// PT_STAMPS=1 is a DIAGNOSTIC build (tools/stamps.py): per-phase s_memtime shares of a
+// wave-bounce go to stats[2..5], the split of pass 2 to stats[8..13]; never shipped, never timed for the bench.
+#ifndef PT_STAMPS
+#define PT_STAMPS 0
+#endif
+#if PT_STAMPS
+#define PT_STAMP(var) do { __builtin_amdgcn_sched_barrier(0); var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define PT_STAMP(var) do { } while (0)
+#endif
+// pass 2 of the PT_STAMPS build, split (ticks of a wave): its own steps, building the pending-pair list, the tail's rounds, the merge at
+// the end; and two tallies: iterations of the list-building loops, searches.  Other builds pass no such record and compile none of it.
+struct PtStampSplit { unsigned long long own, append, rounds, finish, iters, searches; };
+
 // ---- pass 2, balanced across lanes: the TAIL ---------------------------------------------------------
 // Survivors per ray: 3.3 on average, 8.3 at the wave's slowest lane -- walking every lane's own survivors
 // to the end ran the exact test at 39 % lane efficiency.  The closest hit is order-free: the winner of the
@@ -607,6 +621,9 @@ PTK_DEV void pt_tri_pass2(const PtTriRec& r, int i, bool valid, const f3& o, con
 // own walk found re-runs the exact test on that one triangle (same operations on the same operands: the
 // same t, u, v bit for bit).  The list outlives the 32-triangle chunks of a large scene, so a brute-force
 // search over thousands of triangles runs its rare survivors at full lane width too.
+// The append loop below moves one pair per lane and iteration: it runs as long as the slowest lane has survivors, 7.4 iterations per
+// masked search of the Cornell box and a seventh of a wave-iteration's ticks (profiles/pair_list/stamps.txt).  The masked search of the
+// trace kernels builds its list otherwise (pt_pair_list_build, further down); the two-pass, tiled and LBVH searches keep this loop.
 #ifndef PT_TAIL_LANES
 #define PT_TAIL_LANES 32  // own steps continue while more lanes than this still hold a survivor; 0 = never use the tail
 #endif
@@ -707,8 +724,13 @@ PTK_DEV void pt_tail_round(PtTail& tl, unsigned cnt, unsigned lane, const PtPrep
 // pass 2 of one 32-triangle chunk whose survivor mask is m (bit n-1-j <-> triangle base + j)
 template <bool DET_BOUNDED, int LDS_TABLE>
 PTK_DEV void pt_pass2_chunk(unsigned m, int base, int n, const PtPrepTriangle* tris, const f3& o, const f3& d, float& tmax, float& hu,
-                            float& hv, int& hidx, PtTail& tl, unsigned lane, unsigned& steps)
+                            float& hv, int& hidx, PtTail& tl, unsigned lane, unsigned& steps, PtStampSplit* sp = nullptr)
 {
+    (void)sp;
+#if PT_STAMPS
+    unsigned long long s0 = 0, s1 = 0, s2 = 0, ra = 0, rb = 0, rsum = 0;
+    PT_STAMP(s0);
+#endif
     // own steps: every lane tests its next survivor (index 0 and ok = false once it has none left),
     // while more than PT_TAIL_LANES lanes still hold one
     if (LDS_TABLE == 2 && (unsigned)__popcll(PT_LANES(m != 0u)) > (unsigned)PT_TAIL_LANES) pt_stage_tile(tris, base, n, tl.tile, lane);
@@ -724,9 +746,13 @@ PTK_DEV void pt_pass2_chunk(unsigned m, int base, int n, const PtPrepTriangle* t
         const PtTriRec r = LDS_TABLE == 2 ? pt_fetch_rec<2>(tris, n - 32 + (int)lz, tl.tile) : pt_fetch_rec<LDS_TABLE>(tris, i);
         pt_tri_pass2<DET_BOUNDED>(r, i, valid, o, d, tmax, hu, hv, hidx);
     }
+    PT_STAMP(s1);
     // the rest of this chunk's survivors join the wave's pending pairs
     if (PT_TAIL_LANES > 0) {
         for (pt_lanes has = PT_LANES(m != 0u); has != 0ull; has = PT_LANES(m != 0u)) {
+#if PT_STAMPS
+            if (sp) sp->iters++;
+#endif
             if (m != 0u) {
                 unsigned lz;
                 asm("v_ffbh_u32_e32 %0, %1" : "=v"(lz) : "v"(m));
@@ -737,22 +763,37 @@ PTK_DEV void pt_pass2_chunk(unsigned m, int base, int n, const PtPrepTriangle* t
             tl.wr += (unsigned)__popcll(has);
             if (tl.wr - tl.rd >= 64u) {
                 ++steps;
+                PT_STAMP(ra);
                 pt_tail_round<DET_BOUNDED, LDS_TABLE>(tl, 64u, lane, tris, o, d);
+#if PT_STAMPS
+                PT_STAMP(rb);
+                rsum += rb - ra;
+#endif
             }
         }
     }
+#if PT_STAMPS
+    PT_STAMP(s2);
+    if (sp) { sp->own += s1 - s0; sp->append += (s2 - s1) - rsum; sp->rounds += rsum; }
+#endif
 }
 
 // end of a search: the pending pairs, then the merge of what the tail found
 template <bool DET_BOUNDED, int LDS_TABLE>
 PTK_DEV void pt_pass2_finish(const PtPrepTriangle* tris, const f3& o, const f3& d, float& tmax, float& hu, float& hv, int& hidx,
-                             PtTail& tl, unsigned lane, unsigned& steps)
+                             PtTail& tl, unsigned lane, unsigned& steps, PtStampSplit* sp = nullptr)
 {
+    (void)sp;
+#if PT_STAMPS
+    unsigned long long s0 = 0, s1 = 0, s2 = 0;
+    PT_STAMP(s0);
+#endif
     if (PT_TAIL_LANES > 0) {
         if (tl.wr != tl.rd) {
             ++steps;
             pt_tail_round<DET_BOUNDED, LDS_TABLE>(tl, tl.wr - tl.rd, lane, tris, o, d);
         }
+        PT_STAMP(s1);
         if (tl.wr != 0u) {  // (wave-uniform) this search used the tail: merge what it found
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -773,6 +814,10 @@ PTK_DEV void pt_pass2_finish(const PtPrepTriangle* tris, const f3& o, const f3& 
             hidx = better ? ki : hidx;
         }
     }
+#if PT_STAMPS
+    PT_STAMP(s2);
+    if (sp) { sp->rounds += s1 - s0; sp->finish += s2 - s1; }
+#endif
 }
 
 // closest hit over triangles [0, ntri): chunks of 32 triangles, pass 1 then pass 2 per chunk.
@@ -854,17 +899,6 @@ PTK_DEV void pt_quad3_pass1(pt_const_f32p t, const PtRay3& r, pt_f2& un, pt_f2& 
     un = pt_pk_fnma_hi(r.dxy, s[7], un);
     un = pt_pk_fnma_lo(r.dzMx, s[8], un);
 }
-
-// PT_STAMPS=1 is a DIAGNOSTIC build (tools/stamps.py): per-phase s_memtime shares of a
-// wave-bounce go to stats[2..5]; never shipped, never timed for the bench.
-#ifndef PT_STAMPS
-#define PT_STAMPS 0
-#endif
-#if PT_STAMPS
-#define PT_STAMP(var) do { __builtin_amdgcn_sched_barrier(0); var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define PT_STAMP(var) do { } while (0)
-#endif
 
 // QUADS: 0 = independent triangles (pt_tri_pass1), 3 = packed shared-u filter (pt_quad3_pass1)
 // UNIT_DIR: the caller vouches for |d|^2 <= 1.001, the shared-u bound's assumption about the direction, and the filter does not test
@@ -1001,54 +1035,197 @@ PTK_DEV unsigned pt_intersect_two_pass(pt_const_f32p T, const PtPrepTriangle* tr
     return steps;
 }
 
+// ---- the masked search's pending pairs: ONE survivor set per search, its list built with HELPER LANES ------------------------------
+// A masked search of 33 .. 64 triangles used to run pt_pass2_chunk per mask word: two headers, two own walks, two append loops.  And an
+// append loop moves one pair per lane and iteration, so it runs as long as the wave's slowest lane has survivors (8.3 of them, above) --
+// its last iterations under an exec mask of a lane or two -- while the lanes whose own walk is over, more than half of the wave by
+// then (PT_TAIL_LANES), idle.  Here the own steps walk the low word alone, as before, and what is left of it and the whole high word
+// are appended ONCE, by twice the lanes:
+//   * the k-th lane that still holds survivors (its rank: mbcnt of the ballot) sends its number to lane k, and the lanes that hold
+//     none send theirs behind those -- a whole permutation, one ds_permute, every lane receives once, no LDS memory and no barrier;
+//   * lanes 2k and 2k+1 fetch that owner's number and its two words (three ds_bpermute) and adopt one half of its survivors each:
+//     the bits at odd positions of the low word with those at even positions of the high word, or the other way round.  The two
+//     triangles of a quad are neighbours, so are their bits, and the halves come out even; both words fold into ONE 32-bit set whose bit
+//     position still tells the word -- the loop's body is the 32-bit one plus the word's offset;
+//   * more than 32 owners (PT_TAIL_LANES above 32 only) take a second turn of the same code.
+// A pair is still (triangle << 6 | the RAY's lane), whoever appended it: pt_tail_round and pt_pass2_finish are the two-pass search's own.
+// Every pair is listed exactly once (pt_pair_check_kernel, tests/test_gpu_pair_list.py); the search's winner is argmin (t, index)
+// whatever the order the pairs are tested in -- the own walk keeps ascending order and its strict t < tmax, the merge compares (t, index).
+// lo: bit nlo-1-j <-> triangle j (nlo = min(ntri, 32)); hi: bit ntri-33-j <-> triangle 32+j; both 0 in a lane without a ray.
+// round(cnt): test the first cnt pending pairs (every lane calls it).  Returns the iterations of the loop (diagnostics).
+#ifndef PT_PAIR_LIST
+#define PT_PAIR_LIST 2  // the masked search's list: 0 = a chunk per word (the two-pass search's code), 1 = one survivor set, 2 = and helper lanes
+#endif
+#ifndef PT_PAIR_TAIL_LANES
+// the masked search's own steps continue while more lanes than this hold a survivor of the low word.  Fewer than the two-pass search's 32:
+// a pair listed by helper lanes costs less than it did, so more of them go to the rounds, which run full, and fewer own steps run half
+// empty.  24.42 ms per step at 24 against 24.60 at 32, 24.50 at 28, 24.44 at 20 and 25.22 at 40 (profiles/pair_list/bench_ab.txt).
+#define PT_PAIR_TAIL_LANES (PT_TAIL_LANES < 24 ? PT_TAIL_LANES : 24)
+#endif
+template <int LDS_TABLE, class ROUND>
+PTK_DEV unsigned pt_pair_list_build(unsigned lo, unsigned hi, int ntri, PtTail& tl, unsigned lane, ROUND&& round)
+{
+    const bool mine = (lo | hi) != 0u;
+    const pt_lanes owners = PT_LANES(mine);
+    if (owners == 0ull) return 0u;
+    const int off_lo = (ntri < 32 ? ntri : 32) - 32, off_hi = ntri - 32;   // triangle = leading zeros + the word's offset
+    unsigned iters = 0u;
+    if (PT_PAIR_LIST < 2) {
+        // every lane appends its own survivors in ONE loop: the low word's while it has any, then the high word's
+        for (pt_lanes has = owners; has != 0ull; has = PT_LANES((lo | hi) != 0u)) {
+            ++iters;
+            if ((lo | hi) != 0u) {
+                const bool low = lo != 0u;
+                unsigned m = low ? lo : hi, lz;
+                asm("v_ffbh_u32_e32 %0, %1" : "=v"(lz) : "v"(m));
+                m &= ~(0x80000000u >> (lz & 31u));
+                lo = low ? m : lo;
+                hi = low ? hi : m;
+                pt_tail_put<LDS_TABLE>(tl, (tl.wr + pt_mbcnt(has)) & (PT_TAIL_LIST - 1u), ((unsigned)((low ? off_lo : off_hi) + (int)lz) << 6) | lane);
+            }
+            tl.wr += (unsigned)__popcll(has);
+            if (tl.wr - tl.rd >= 64u) round(64u);
+        }
+        return iters;
+    }
+    const unsigned n_owners = (unsigned)__popcll(owners);
+    const unsigned rank = pt_mbcnt(owners);
+    const unsigned dest = mine ? rank : n_owners + lane - rank;   // (lane - rank: the lanes below this one that hold nothing)
+    const unsigned owner_at = (unsigned)__builtin_amdgcn_ds_permute((int)(dest << 2), (int)lane);   // lane k: the k-th owner's number
+    const unsigned own_bits = (lane & 1u) ? 0x55555555u : 0xAAAAAAAAu;   // this lane's half of a low word; of a high word the other bits
+    const unsigned pair_lo = (unsigned)off_lo << 6, pair_hi = (unsigned)(off_hi - off_lo) << 6;   // (off_lo <= 0 wraps; lz + off_lo >= 0 for every set bit)
+    for (unsigned first = 0u; first < n_owners; first += 32u) {
+        const unsigned k = first + (lane >> 1);
+        const unsigned ray = (unsigned)__builtin_amdgcn_ds_bpermute((int)(k << 2), (int)owner_at);
+        const unsigned wlo = (unsigned)__builtin_amdgcn_ds_bpermute((int)(ray << 2), (int)lo);
+        const unsigned whi = (unsigned)__builtin_amdgcn_ds_bpermute((int)(ray << 2), (int)hi);
+        unsigned m = k < n_owners ? (wlo & own_bits) | (whi & ~own_bits) : 0u;
+        for (pt_lanes has = PT_LANES(m != 0u); has != 0ull; has = PT_LANES(m != 0u)) {
+            ++iters;
+            if (m != 0u) {
+                unsigned lz;
+                asm("v_ffbh_u32_e32 %0, %1" : "=v"(lz) : "v"(m));
+                m &= ~(0x80000000u >> (lz & 31u));
+                // bit 31 - lz is of the low word where own_bits has it: lanes 2k at odd positions (lz even), lanes 2k+1 at even ones
+                // (the word's offset, times 64, as ONE multiply-add on a wave-uniform operand: left to the compiler it is a select between two
+                // copies of scalars, five instructions more)
+                const unsigned high = (lz ^ lane) & 1u;
+                unsigned pair;
+                asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(pair) : "v"(high), "s"(pair_hi), "v"((lz << 6) | ray));
+                pair += pair_lo;
+                pt_tail_put<LDS_TABLE>(tl, (tl.wr + pt_mbcnt(has)) & (PT_TAIL_LIST - 1u), pair);
+            }
+            tl.wr += (unsigned)__popcll(has);
+            if (tl.wr - tl.rd >= 64u) round(64u);
+        }
+    }
+    return iters;
+}
+
 // closest hit of rays that bring their candidate masks along -- a FRESH wave of primary rays whose pixels have them
 // (pt_primary_mask_kernel), or secondary rays whose cells have them (pt_secondary_mask_kernel; an uncovered ray brings all ones):
-// pass 1 is skipped, pass 2 is the one of pt_intersect_two_pass.  ntri <= 64 (two chunks).
+// pass 1 is skipped.  ntri <= 64 (two mask words).  Beside the LDS table (LDS_TABLE 1) the two words are ONE survivor set
+// (pt_pair_list_build, above); elsewhere pass 2 is the one of pt_intersect_two_pass, chunk by chunk.
+#if PT_VALIDATE_FILTER
+// DIAGNOSTIC build (tools/validate_filter.py): one mask word m of the n triangles from base against the reference's test
+PTK_DEV void pt_validate_mask_word(pt_const_f32p T, int base, int n, unsigned m, const f3& o, const f3& d, bool alive, unsigned long long* vstat)
+{
+    if (alive && vstat) {  // the reference's whole test (:96-125, against the initial tmax of :141) must never accept a pair the mask dropped
+        unsigned mx = 0u;
+        for (int jj = 0; jj < n; ++jj) {
+            const PtTriRec r = pt_load_tri(T, base + jj);
+            float pvx = pt_fma(d.y, r.e2z, -(d.z * r.e2y));
+            float pvy = pt_fma(d.z, r.e2x, -(d.x * r.e2z));
+            float pvz = pt_fma(d.x, r.e2y, -(d.y * r.e2x));
+            float det = pt_fma(r.e1z, pvz, pt_fma(r.e1y, pvy, r.e1x * pvx));
+            bool keep = !(det < 1e-8f || -det > 1e-8f);
+            float inv_det = 1.0f / det;
+            float tvx = o.x - r.p1x, tvy = o.y - r.p1y, tvz = o.z - r.p1z;
+            float u = pt_fma(tvz, pvz, pt_fma(tvy, pvy, tvx * pvx)) * inv_det;
+            keep = keep && !(u < 0.0f || u > 1.0f);
+            float qvx = pt_fma(tvy, r.e1z, -(tvz * r.e1y));
+            float qvy = pt_fma(tvz, r.e1x, -(tvx * r.e1z));
+            float qvz = pt_fma(tvx, r.e1y, -(tvy * r.e1x));
+            float v = pt_fma(d.z, qvz, pt_fma(d.y, qvy, d.x * qvx)) * inv_det;
+            keep = keep && !(v < 0.0f || u + v > 1.0f);
+            float tt = pt_fma(r.e2z, qvz, pt_fma(r.e2y, qvy, r.e2x * qvx)) * inv_det;
+            keep = keep && (tt > 0.0f && tt < 1e20f);
+            mx |= (keep ? 1u : 0u) << (n - 1 - jj);
+        }
+        atomicAdd(&vstat[0], (unsigned long long)n);
+        atomicAdd(&vstat[1], (unsigned long long)__popc(mx));
+        atomicAdd(&vstat[2], (unsigned long long)__popc(m));
+        atomicAdd(&vstat[3], (unsigned long long)__popc(mx & ~m));   // VIOLATIONS: must stay 0
+    }
+}
+#endif
+
 template <bool DET_BOUNDED, int LDS_TABLE>
 PTK_DEV unsigned pt_intersect_masked(pt_const_f32p T, const PtPrepTriangle* tris, int ntri, const f3& o, const f3& d, bool alive,
                                       float& tmax, float& hu, float& hv, int& hidx, uint2 pm, PtTail tl, unsigned lane,
-                                      unsigned long long* vstat = nullptr)
+                                      unsigned long long* vstat = nullptr, PtStampSplit* sp = nullptr)
 {
-    (void)T; (void)vstat;
+    (void)T; (void)vstat; (void)sp;
     tl.wr = tl.rd = 0u;
     tl.kbest = ~0ull;
     unsigned steps = 0;
-    for (int base = 0; base < ntri; base += 32) {
-        const int n = ntri - base < 32 ? ntri - base : 32;
-        unsigned m = base == 0 ? pm.x : pm.y;
-#if PT_VALIDATE_FILTER
-        if (alive && vstat) {  // the reference's whole test (:96-125, against the initial tmax of :141) must never accept a pair the mask dropped
-            unsigned mx = 0u;
-            for (int jj = 0; jj < n; ++jj) {
-                const PtTriRec r = pt_load_tri(T, base + jj);
-                float pvx = pt_fma(d.y, r.e2z, -(d.z * r.e2y));
-                float pvy = pt_fma(d.z, r.e2x, -(d.x * r.e2z));
-                float pvz = pt_fma(d.x, r.e2y, -(d.y * r.e2x));
-                float det = pt_fma(r.e1z, pvz, pt_fma(r.e1y, pvy, r.e1x * pvx));
-                bool keep = !(det < 1e-8f || -det > 1e-8f);
-                float inv_det = 1.0f / det;
-                float tvx = o.x - r.p1x, tvy = o.y - r.p1y, tvz = o.z - r.p1z;
-                float u = pt_fma(tvz, pvz, pt_fma(tvy, pvy, tvx * pvx)) * inv_det;
-                keep = keep && !(u < 0.0f || u > 1.0f);
-                float qvx = pt_fma(tvy, r.e1z, -(tvz * r.e1y));
-                float qvy = pt_fma(tvz, r.e1x, -(tvx * r.e1z));
-                float qvz = pt_fma(tvx, r.e1y, -(tvy * r.e1x));
-                float v = pt_fma(d.z, qvz, pt_fma(d.y, qvy, d.x * qvx)) * inv_det;
-                keep = keep && !(v < 0.0f || u + v > 1.0f);
-                float tt = pt_fma(r.e2z, qvz, pt_fma(r.e2y, qvy, r.e2x * qvx)) * inv_det;
-                keep = keep && (tt > 0.0f && tt < 1e20f);
-                mx |= (keep ? 1u : 0u) << (n - 1 - jj);
-            }
-            atomicAdd(&vstat[0], (unsigned long long)n);
-            atomicAdd(&vstat[1], (unsigned long long)__popc(mx));
-            atomicAdd(&vstat[2], (unsigned long long)__popc(m));
-            atomicAdd(&vstat[3], (unsigned long long)__popc(mx & ~m));   // VIOLATIONS: must stay 0
-        }
+#if PT_STAMPS
+    if (sp) sp->searches++;
 #endif
-        if (!alive) m = 0u;
-        pt_pass2_chunk<DET_BOUNDED, LDS_TABLE>(m, base, n, tris, o, d, tmax, hu, hv, hidx, tl, lane, steps);
+    if (LDS_TABLE == 1 && PT_PAIR_LIST > 0 && PT_PAIR_TAIL_LANES > 0) {
+        // one survivor set (pt_pair_list_build): own steps over the low word while more than PT_PAIR_TAIL_LANES lanes hold a survivor of
+        // it -- the loop of pt_pass2_chunk -- then ONE list of what is left of it and of the high word
+        const int n = ntri < 32 ? ntri : 32;
+        unsigned m = pm.x, mh = ntri > 32 ? pm.y : 0u;
+#if PT_VALIDATE_FILTER
+        pt_validate_mask_word(T, 0, n, m, o, d, alive, vstat);
+        if (ntri > 32) pt_validate_mask_word(T, 32, ntri - 32, mh, o, d, alive, vstat);
+#endif
+        if (!alive) m = mh = 0u;
+#if PT_STAMPS
+        unsigned long long s0 = 0, s1 = 0, s2 = 0, rsum = 0;
+        PT_STAMP(s0);
+#endif
+        for (pt_lanes more = PT_LANES(m != 0u); (unsigned)__popcll(more) > (unsigned)PT_PAIR_TAIL_LANES; more = PT_LANES(m != 0u)) {
+            ++steps;
+            const bool valid = m != 0u;
+            unsigned lz;  // (-1 for m = 0: a wild index into the LDS table, whose out-of-range reads return 0; the result is discarded)
+            asm("v_ffbh_u32_e32 %0, %1" : "=v"(lz) : "v"(m));
+            const int i = n - 32 + (int)lz;
+            m &= ~(0x80000000u >> (lz & 31u));
+            const PtTriRec r = pt_fetch_rec<1>(tris, i);
+            pt_tri_pass2<DET_BOUNDED>(r, i, valid, o, d, tmax, hu, hv, hidx);
+        }
+        PT_STAMP(s1);
+        const unsigned iters = pt_pair_list_build<LDS_TABLE>(m, mh, ntri, tl, lane, [&](unsigned cnt) {
+#if PT_STAMPS
+            unsigned long long ra = 0, rb = 0;
+            PT_STAMP(ra);
+#endif
+            ++steps;
+            pt_tail_round<DET_BOUNDED, LDS_TABLE>(tl, cnt, lane, tris, o, d);
+#if PT_STAMPS
+            PT_STAMP(rb);
+            rsum += rb - ra;
+#endif
+        });
+        (void)iters;
+#if PT_STAMPS
+        PT_STAMP(s2);
+        if (sp) { sp->own += s1 - s0; sp->append += (s2 - s1) - rsum; sp->rounds += rsum; sp->iters += iters; }
+#endif
+    } else {
+        for (int base = 0; base < ntri; base += 32) {
+            const int n = ntri - base < 32 ? ntri - base : 32;
+            unsigned m = base == 0 ? pm.x : pm.y;
+#if PT_VALIDATE_FILTER
+            pt_validate_mask_word(T, base, n, m, o, d, alive, vstat);
+#endif
+            if (!alive) m = 0u;
+            pt_pass2_chunk<DET_BOUNDED, LDS_TABLE>(m, base, n, tris, o, d, tmax, hu, hv, hidx, tl, lane, steps, sp);
+        }
     }
-    pt_pass2_finish<DET_BOUNDED, LDS_TABLE>(tris, o, d, tmax, hu, hv, hidx, tl, lane, steps);
+    pt_pass2_finish<DET_BOUNDED, LDS_TABLE>(tris, o, d, tmax, hu, hv, hidx, tl, lane, steps, sp);
     return steps;
 }
 
@@ -1786,6 +1963,7 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
     q.g = wave & (PT_QUEUE_SHARDS - 1u);   // the wave's first shard of this launch's queue
 #if PT_STAMPS
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, c_regen = 0, c_loop = 0, c_shade = 0, c_iters = 0, c_steps = 0, c_p1 = 0;
+    PtStampSplit c_split = { 0, 0, 0, 0, 0, 0 };   // (the masked searches' pass 2 alone)
 #endif
 
     // One iteration: the paths the search ended (misses) and the ones shading ended store their radiance; dead lanes take parked
@@ -1896,7 +2074,13 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
             // (shading ended every path: nothing to search)
         } else if (masked)
             p2steps = pt_intersect_masked<DET_BOUNDED, LDS_TABLE>(T, P.tris, ntri, s.o, s.d, PT_ON(alive), tmax, hu, hv, hidx, pm, tl, lane,
-                                                                  PT_VALIDATE_FILTER && P.stats ? P.stats + 2 : nullptr);
+                                                                  PT_VALIDATE_FILTER && P.stats ? P.stats + 2 : nullptr,
+#if PT_STAMPS
+                                                                  &c_split
+#else
+                                                                  nullptr
+#endif
+                                                                  );
         else
             p2steps = pt_intersect_two_pass<DET_BOUNDED, LDS_TABLE, QUADS, PT_TRACE_UNIT_DIR != 0>(T, P.tris, ntri, s.o, s.d, PT_ON(alive), tmax, hu, hv, hidx,
                                                                                           P.quad_delta1, P.ray_radius,
@@ -1931,6 +2115,12 @@ PTK_DEV void pt_trace_body(const PtTraceParams& P)
         atomicAdd(&P.stats[5], c_iters);
         atomicAdd(&P.stats[7], c_steps);
         atomicAdd(&P.stats[6], c_p1);
+        atomicAdd(&P.stats[8], c_split.own);
+        atomicAdd(&P.stats[9], c_split.append);
+        atomicAdd(&P.stats[10], c_split.rounds);
+        atomicAdd(&P.stats[11], c_split.finish);
+        atomicAdd(&P.stats[12], c_split.iters);
+        atomicAdd(&P.stats[13], c_split.searches);
     }
 #endif
     {
@@ -2890,6 +3080,37 @@ __global__ __launch_bounds__(256) void pt_shade_check_kernel(unsigned long long*
     }
     if (seen) atomicAdd(out + 4, (unsigned long long)seen);
     if (inside) atomicAdd(out + 5, (unsigned long long)inside);
+}
+
+// the masked search's list builder (pt_pair_list_build) and the rounds' lane mapping (pt_tail_get, as pt_tail_round reads the ring) on
+// masks the caller gives: one wave of 64 lanes per case, masks[case * 64 + lane] = that lane's two words (the high one counts where
+// ntri > 32, as in pt_intersect_masked).  out[case * (2 + cap)]: the pairs the rounds would test, then the rounds, then the pairs
+// themselves (triangle << 6 | ray lane) in the order tested, the first `cap` of them.  The ring is the search's: PT_TAIL_LIST pairs of 2 bytes.
+__global__ __launch_bounds__(64) void pt_pair_check_kernel(const uint2* __restrict__ masks, unsigned* __restrict__ out, int ntri, unsigned cap)
+{
+    __shared__ __attribute__((aligned(4))) unsigned short ring[PT_TAIL_LIST];
+    const unsigned lane = pt_lane_id();
+    PtTail tl;
+    tl.keys = nullptr;
+    tl.list = (pt_lds_u32*)ring;
+    tl.wr = tl.rd = 0u;
+    tl.kbest = ~0ull; tl.ku = tl.kv = 0.0f;
+    tl.tile = 0u;
+    const uint2 pm = masks[(size_t)blockIdx.x * 64u + lane];
+    unsigned* const o = out + (size_t)blockIdx.x * (2u + cap);
+    unsigned n_out = 0u, rounds = 0u;
+    auto round = [&](unsigned cnt) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (lane < cnt && n_out + lane < cap) o[2u + n_out + lane] = pt_tail_get<1>(tl, (tl.rd + lane) & (PT_TAIL_LIST - 1u));
+        n_out += cnt;
+        tl.rd += cnt;
+        ++rounds;
+    };
+    pt_pair_list_build<1>(pm.x, ntri > 32 ? pm.y : 0u, ntri, tl, lane, round);
+    if (tl.wr != tl.rd) round(tl.wr - tl.rd);   // (pt_pass2_finish)
+    if (lane == 0u) { o[0] = n_out; o[1] = rounds; }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -5164,6 +5385,13 @@ hipError_t ptk_shade_check(unsigned long long* out, int mode, unsigned first, un
     if (count == 0) return hipSuccess;
     const unsigned long long want = (count + 255) / 256;
     hipLaunchKernelGGL(pt_shade_check_kernel, dim3((unsigned)(want < 65536ull ? want : 65536ull)), dim3(256), 0, s, out, mode, first, count);
+    return hipGetLastError();
+}
+
+hipError_t ptk_pair_check(const uint2* masks, unsigned* out, int ntri, unsigned cases, unsigned cap, hipStream_t s)
+{
+    if (cases == 0) return hipSuccess;
+    hipLaunchKernelGGL(pt_pair_check_kernel, dim3(cases), dim3(64), 0, s, masks, out, ntri, cap);
     return hipGetLastError();
 }
 

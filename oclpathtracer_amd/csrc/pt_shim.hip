@@ -51,7 +51,7 @@ extern "C" int pt_abi_version(void) { return PT_SHIM_ABI_VERSION; }
 // ------------------------------------------------------------------------------------------
 // objects
 // ------------------------------------------------------------------------------------------
-enum { KERNEL_GENERATE_COLORS = 0, KERNEL_FILL = 1, KERNEL_MATH = 2, KERNEL_FOLD_CHECK = 3, KERNEL_SHADE_CHECK = 4, KERNEL_COUNT = 5 };
+enum { KERNEL_GENERATE_COLORS = 0, KERNEL_FILL = 1, KERNEL_MATH = 2, KERNEL_FOLD_CHECK = 3, KERNEL_SHADE_CHECK = 4, KERNEL_PAIR_CHECK = 5, KERNEL_COUNT = 6 };
 
 struct pt_kernel_s {
     int id;
@@ -346,6 +346,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->kernels[KERNEL_MATH] = { KERNEL_MATH, "PtShimTest", "MathKernel" };
     d->kernels[KERNEL_FOLD_CHECK] = { KERNEL_FOLD_CHECK, "PtShimTest", "FoldCheckKernel" };
     d->kernels[KERNEL_SHADE_CHECK] = { KERNEL_SHADE_CHECK, "PtShimTest", "ShadeCheckKernel" };
+    d->kernels[KERNEL_PAIR_CHECK] = { KERNEL_PAIR_CHECK, "PtShimTest", "PairCheckKernel" };
     bool ok = ws_malloc(d, d->bigtab, WS_BIGTAB) == hipSuccess && ws_malloc(d, d->bigidx, WS_BIGIDX) == hipSuccess &&
               ws_malloc(d, d->counters, WS_COUNTERS) == hipSuccess && ws_malloc(d, d->big_filter.p1tab, ws_big_p1tab()) == hipSuccess &&
               ws_malloc(d, d->det_bound_dev, WS_DETBOUND) == hipSuccess;
@@ -3062,6 +3063,32 @@ static int launch_shade_check(pt_device_s* d, const pt_launch_arg* a, int nargs,
     return event_end(d, ev);
 }
 
+static int launch_pair_check(pt_device_s* d, const pt_launch_arg* a, int nargs, pt_event_s* ev)
+{
+    // PairCheckKernel(const uint2* masks, uint* out, int ntri, uint cases, uint cap): the masked search's pending-pair list on the
+    // caller's masks, one wave of 64 lanes per case (csrc/pt_kernels.hip, pt_pair_check_kernel); the work-item count of the launch is
+    // ignored.  masks: cases x 64 x 2 words; out: cases x (2 + cap) words
+    if (nargs != 5 || !a[0].is_buffer || !a[1].is_buffer || a[2].is_buffer || a[2].size != 4 || a[3].is_buffer || a[3].size != 4 ||
+        a[4].is_buffer || a[4].size != 4)
+        return fail(PT_ERR_ARGS, "PairCheckKernel expects (buffer, buffer, int, uint, uint)");
+    pt_buffer_s *masks = a[0].buffer, *out = a[1].buffer;
+    if (!masks || !out || masks->dev != d || out->dev != d) return fail(PT_ERR_ARGS, "PairCheckKernel: bad buffer");
+    int32_t ntri;
+    uint32_t cases, cap;
+    memcpy(&ntri, a[2].data, 4);
+    memcpy(&cases, a[3].data, 4);
+    memcpy(&cap, a[4].data, 4);
+    if (ntri < 1 || ntri > 64) return fail(PT_ERR_ARGS, "PairCheckKernel: %d triangles", ntri);
+    if (cases > 65536u || cap > 4096u) return fail(PT_ERR_ARGS, "PairCheckKernel: %u cases of %u pairs", cases, cap);
+    if (masks->bytes < (size_t)cases * 64u * 8u || out->bytes < (size_t)cases * (2u + cap) * 4u)
+        return fail(PT_ERR_ARGS, "PairCheckKernel: buffer too small");
+    int rc = enter_stream(d);
+    if (rc || (rc = event_begin(d, ev))) return rc;
+    HIP_TRY(ptk_pair_check((const uint2*)masks->dptr, (unsigned*)out->dptr, ntri, cases, cap, d->stream));
+    out->version++;
+    return event_end(d, ev);
+}
+
 extern "C" int pt_launch_2d(pt_device_t d, pt_kernel_t k, const pt_launch_arg* args, int nargs, int ntx, int nty, int lx,
                             int ly, pt_event_t ev, float* ms_out)
 {
@@ -3082,6 +3109,7 @@ extern "C" int pt_launch_2d(pt_device_t d, pt_kernel_t k, const pt_launch_arg* a
     case KERNEL_MATH: return launch_math(d, args, nargs, n, ev);
     case KERNEL_FOLD_CHECK: return launch_fold_check(d, args, nargs, ev);
     case KERNEL_SHADE_CHECK: return launch_shade_check(d, args, nargs, ev);
+    case KERNEL_PAIR_CHECK: return launch_pair_check(d, args, nargs, ev);
     default: return fail(PT_ERR_NOT_FOUND, "unknown kernel id");
     }
 }

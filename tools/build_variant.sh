@@ -6,5 +6,5 @@ name=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 SRC=${SRC_DIR:-$ROOT/oclpathtracer_amd/csrc}
 cd "$SRC"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wno-unused-function -Wno-unused-value -Wno-unused-result "$@" -shared -o "$ROOT/oclpathtracer_amd/libptshim_$name.so" pt_kernels.hip pt_shim.hip pt_bvh.hip $([ -f pt_denoise.hip ] && echo pt_denoise.hip)
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wno-unused-function -Wno-unused-value -Wno-unused-result "$@" -shared -o "$ROOT/oclpathtracer_amd/libptshim_$name.so" pt_kernels.hip pt_shim.hip pt_bvh.hip $([ -f pt_denoise.hip ] && echo pt_denoise.hip) $([ -f pt_reproject.hip ] && echo pt_reproject.hip)
 echo "built libptshim_$name.so ($*)"

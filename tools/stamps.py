@@ -35,4 +35,10 @@ for n, c in (("regen", c_regen), ("sort", c_sort), ("loop", c_loop), ("shade", c
     print("%-6s %5.1f%%   %.0f ticks per wave-iteration" % (n, 100.0 * c / max(tot, 1), c / max(iters, 1)))
 if variant == 1:
     print("       of loop: pass 1 %.1f%% of the total (%.0f ticks per wave-iteration), pass 2 the rest" % (100.0 * c_p1 / max(tot, 1), c_p1 / max(iters, 1)))
+# the masked searches' pass 2, split (stats[8..13]: csrc/pt_kernels.hip, PtStampSplit)
+own, append, rounds, finish, list_iters, searches = (int(x) for x in out[8:14])
+if searches:
+    print("masked searches %d (%.3f per wave-iteration)  list-building iterations per search %.2f" % (searches, searches / max(iters, 1), list_iters / searches))
+    for n, c in (("own steps", own), ("list building", append), ("tail rounds", rounds), ("merge", finish)):
+        print("  %-13s %5.1f%% of the total   %.0f ticks per wave-iteration   %.0f per masked search" % (n, 100.0 * c / max(tot, 1), c / max(iters, 1), c / searches))
 r.release(); adl.DeviceUtils.deallocate(dev)
