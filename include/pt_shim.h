@@ -274,7 +274,7 @@ int pt_event_elapsed_ns(pt_event_t ev, uint64_t* ns_out);
  * resolves.  Unknown kernels -> PT_ERR_NOT_FOUND and *out = NULL (Adl returns 0).
  * Registered: ("GenerateColors","GenerateColors"), ("PtShimTest","FillKernel"),
  * ("PtShimTest","MathKernel"), ("PtShimTest","FoldCheckKernel"), ("PtShimTest","ShadeCheckKernel"),
- * ("PtShimTest","PairCheckKernel") -- the last five are smoke/parity-test kernels. */
+ * ("PtShimTest","PairCheckKernel"), ("PtShimTest","SearchCheckKernel") -- the last six are smoke/parity-test kernels. */
 int pt_kernel_get(pt_device_t dev, const char* file_name, const char* func_name, pt_kernel_t* out);
 
 #define PT_MAX_ARG_SIZE 64  /* Launcher::MAX_ARG_SIZE  Adl/AdlKernel.h:129 */

@@ -274,6 +274,10 @@ hipError_t ptk_shade_check(unsigned long long* out, int mode, unsigned first, un
 // the masked search's pending-pair list on given masks (pt_pair_check_kernel): masks: cases x 64 lanes x {low, high word};
 // out: cases x (2 + cap) words -- pairs, rounds, then the pairs (triangle << 6 | ray lane) in the order the rounds test them
 hipError_t ptk_pair_check(const uint2* masks, unsigned* out, int ntri, unsigned cases, unsigned cap, hipStream_t s);
+// the masked search itself on given rays and masks (pt_search_check_kernel): tris: the prepared scene, 1 <= ntri <= 64, det-bounded;
+// rays: cases x 64 lanes x {origin xyz, alive word | direction xyz, unused}; masks: cases x 64 x {low, high word};
+// out: cases x 64 x {hidx, t, hu, hv (bits) | steps, 0, 0, 0}
+hipError_t ptk_search_check(const PtPrepTriangle* tris, int ntri, const float4* rays, const uint2* masks, uint4* out, unsigned cases, hipStream_t s);
 // batched ray queries (pt_intersect_rays): t carries the search -- the prepared scene (tris, ntri), the filter of the table the
 // two-pass search runs over (quad_delta1 .. p1_hi, its anchor in cam.eye), the LBVH (bvh .. nbig, bvh_flags, bvh_stack_limit);
 // the other fields of t are not read

@@ -3113,6 +3113,37 @@ __global__ __launch_bounds__(64) void pt_pair_check_kernel(const uint2* __restri
     if (lane == 0u) { o[0] = n_out; o[1] = rounds; }
 }
 
+// the masked search ITSELF -- pt_intersect_masked<true, 1>, the trace kernel's call: own steps, list, rounds, merge -- on rays and masks
+// the caller gives: one wave of 64 lanes per case, workgroups of the trace kernel's size whose waves share ONE LDS triangle table and
+// hold a tail each, as there (the layout of the brute-force query kernel: pt_lds_*, POOLS = false).  rays[2 (case * 64 + lane)] =
+// origin xyz and an alive word (bits, 0 = a lane without a ray), then direction xyz -- handed to the search as it is -- and a word not
+// read; masks[case * 64 + lane] = the lane's two words (lo: bit nlo-1-j <-> triangle j, hi: bit ntri-33-j <-> triangle 32+j).  Bits of
+// triangles the scene does not have are dropped here: no table holds one, and they would index past the records; a high word at 32
+// triangles or fewer goes in as it is -- the search must not read it.  out[2 (case * 64 + lane)] = {hidx, t, hu, hv} (bits), then the
+// search's step count and three zeros.
+__global__ __launch_bounds__(PT_TRACE_THREADS) void pt_search_check_kernel(const PtPrepTriangle* __restrict__ tris, int ntri, const float4* __restrict__ rays,
+                                                                          const uint2* __restrict__ masks, uint4* __restrict__ out, unsigned cases)
+{
+    const unsigned lane = pt_lane_id();
+    pt_lds_table_load(tris, ntri);
+    __syncthreads();
+    PtTail tl = pt_tail_init((pt_lds_u32*)pt_lds_tab + pt_lds_tails<1, false>(ntri) + pt_wave_in_wg() * pt_lds_tail_dw<1>(), 0u, lane);
+    const unsigned c = pt_wave();
+    if (c >= cases) return;   // (wave-uniform, behind the workgroup's only barrier)
+    const size_t i = (size_t)c * 64u + lane;
+    const float4 ro = rays[2 * i], rd = rays[2 * i + 1];
+    uint2 pm = masks[i];
+    const int nlo = ntri < 32 ? ntri : 32, nhi = ntri - 32;
+    pm.x &= 0xFFFFFFFFu >> (32 - nlo);
+    if (nhi > 0) pm.y &= 0xFFFFFFFFu >> (32 - nhi);
+    float tmax = 1e20f, hu = 0.0f, hv = 0.0f;
+    int hidx = -1;
+    const unsigned steps = pt_intersect_masked<true, 1>((pt_const_f32p)(const float*)tris, tris, ntri, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z),
+                                                        __float_as_uint(ro.w) != 0u, tmax, hu, hv, hidx, pm, tl, lane);
+    out[2 * i] = make_uint4((unsigned)hidx, __float_as_uint(tmax), __float_as_uint(hu), __float_as_uint(hv));
+    out[2 * i + 1] = make_uint4(steps, 0u, 0u, 0u);
+}
+
 // ------------------------------------------------------------------------------------------
 // multi-GPU assembly, output stage, shim smoke-test kernel
 // ------------------------------------------------------------------------------------------
@@ -5392,6 +5423,15 @@ hipError_t ptk_pair_check(const uint2* masks, unsigned* out, int ntri, unsigned 
 {
     if (cases == 0) return hipSuccess;
     hipLaunchKernelGGL(pt_pair_check_kernel, dim3(cases), dim3(64), 0, s, masks, out, ntri, cap);
+    return hipGetLastError();
+}
+
+hipError_t ptk_search_check(const PtPrepTriangle* tris, int ntri, const float4* rays, const uint2* masks, uint4* out, unsigned cases, hipStream_t s)
+{
+    if (cases == 0) return hipSuccess;
+    const unsigned wg_waves = PT_TRACE_THREADS / 64;
+    const size_t lds = (size_t)pt_lds_total<1, false>(ntri) * sizeof(float);
+    hipLaunchKernelGGL(pt_search_check_kernel, dim3((cases + wg_waves - 1) / wg_waves), dim3(PT_TRACE_THREADS), lds, s, tris, ntri, rays, masks, out, cases);
     return hipGetLastError();
 }
 

@@ -51,7 +51,7 @@ extern "C" int pt_abi_version(void) { return PT_SHIM_ABI_VERSION; }
 // ------------------------------------------------------------------------------------------
 // objects
 // ------------------------------------------------------------------------------------------
-enum { KERNEL_GENERATE_COLORS = 0, KERNEL_FILL = 1, KERNEL_MATH = 2, KERNEL_FOLD_CHECK = 3, KERNEL_SHADE_CHECK = 4, KERNEL_PAIR_CHECK = 5, KERNEL_COUNT = 6 };
+enum { KERNEL_GENERATE_COLORS = 0, KERNEL_FILL = 1, KERNEL_MATH = 2, KERNEL_FOLD_CHECK = 3, KERNEL_SHADE_CHECK = 4, KERNEL_PAIR_CHECK = 5, KERNEL_SEARCH_CHECK = 6, KERNEL_COUNT = 7 };
 
 struct pt_kernel_s {
     int id;
@@ -347,6 +347,7 @@ extern "C" int pt_device_create(int device_idx, pt_device_t* out)
     d->kernels[KERNEL_FOLD_CHECK] = { KERNEL_FOLD_CHECK, "PtShimTest", "FoldCheckKernel" };
     d->kernels[KERNEL_SHADE_CHECK] = { KERNEL_SHADE_CHECK, "PtShimTest", "ShadeCheckKernel" };
     d->kernels[KERNEL_PAIR_CHECK] = { KERNEL_PAIR_CHECK, "PtShimTest", "PairCheckKernel" };
+    d->kernels[KERNEL_SEARCH_CHECK] = { KERNEL_SEARCH_CHECK, "PtShimTest", "SearchCheckKernel" };
     bool ok = ws_malloc(d, d->bigtab, WS_BIGTAB) == hipSuccess && ws_malloc(d, d->bigidx, WS_BIGIDX) == hipSuccess &&
               ws_malloc(d, d->counters, WS_COUNTERS) == hipSuccess && ws_malloc(d, d->big_filter.p1tab, ws_big_p1tab()) == hipSuccess &&
               ws_malloc(d, d->det_bound_dev, WS_DETBOUND) == hipSuccess;
@@ -3089,6 +3090,39 @@ static int launch_pair_check(pt_device_s* d, const pt_launch_arg* a, int nargs, 
     return event_end(d, ev);
 }
 
+static int launch_search_check(pt_device_s* d, const pt_launch_arg* a, int nargs, pt_event_s* ev)
+{
+    // SearchCheckKernel(const pt_triangle* tris, const float4* rays, const uint2* masks, uint4* out, int ntri, uint cases): the masked
+    // search itself on the caller's rays and masks, one wave of 64 lanes per case (csrc/pt_kernels.hip, pt_search_check_kernel); the
+    // work-item count of the launch is ignored.  tris: the raw scene, prepared here as a render prepares it (ensure_prep; the search
+    // reads records only, so neither the quad pairing nor an anchor is asked for) -- finite and det-bounded, as every scene that
+    // carries masks is; rays: cases x 64 x 8 words; masks: cases x 64 x 2 words; out: cases x 64 x 8 words
+    if (nargs != 6 || !a[0].is_buffer || !a[1].is_buffer || !a[2].is_buffer || !a[3].is_buffer || a[4].is_buffer || a[4].size != 4 ||
+        a[5].is_buffer || a[5].size != 4)
+        return fail(PT_ERR_ARGS, "SearchCheckKernel expects (buffer, buffer, buffer, buffer, int, uint)");
+    pt_buffer_s *tris = a[0].buffer, *rays = a[1].buffer, *masks = a[2].buffer, *out = a[3].buffer;
+    if (!tris || !rays || !masks || !out || tris->dev != d || rays->dev != d || masks->dev != d || out->dev != d)
+        return fail(PT_ERR_ARGS, "SearchCheckKernel: bad buffer");
+    int32_t ntri;
+    uint32_t cases;
+    memcpy(&ntri, a[4].data, 4);
+    memcpy(&cases, a[5].data, 4);
+    if (ntri < 1 || ntri > 64) return fail(PT_ERR_ARGS, "SearchCheckKernel: %d triangles", ntri);
+    if (cases > 65536u) return fail(PT_ERR_ARGS, "SearchCheckKernel: %u cases", cases);
+    if (tris->bytes < (size_t)ntri * sizeof(PtRawTriangle) || rays->bytes < (size_t)cases * 64u * 32u || masks->bytes < (size_t)cases * 64u * 8u ||
+        out->bytes < (size_t)cases * 64u * 32u)
+        return fail(PT_ERR_ARGS, "SearchCheckKernel: buffer too small");
+    if (out == tris || out == rays || out == masks) return fail(PT_ERR_ARGS, "SearchCheckKernel: the results overlap an input");
+    int rc = enter_stream(d);
+    if (rc || (rc = ensure_prep(d, tris, ntri))) return rc;
+    if (!d->prep_finite || !d->prep_det_bounded)
+        return fail(PT_ERR_ARGS, "SearchCheckKernel: the scene is not finite and det-bounded (no such scene carries masks)");
+    if ((rc = event_begin(d, ev))) return rc;
+    HIP_TRY(ptk_search_check(d->prep, ntri, (const float4*)rays->dptr, (const uint2*)masks->dptr, (uint4*)out->dptr, cases, d->stream));
+    out->version++;
+    return event_end(d, ev);
+}
+
 extern "C" int pt_launch_2d(pt_device_t d, pt_kernel_t k, const pt_launch_arg* args, int nargs, int ntx, int nty, int lx,
                             int ly, pt_event_t ev, float* ms_out)
 {
@@ -3110,6 +3144,7 @@ extern "C" int pt_launch_2d(pt_device_t d, pt_kernel_t k, const pt_launch_arg* a
     case KERNEL_FOLD_CHECK: return launch_fold_check(d, args, nargs, ev);
     case KERNEL_SHADE_CHECK: return launch_shade_check(d, args, nargs, ev);
     case KERNEL_PAIR_CHECK: return launch_pair_check(d, args, nargs, ev);
+    case KERNEL_SEARCH_CHECK: return launch_search_check(d, args, nargs, ev);
     default: return fail(PT_ERR_NOT_FOUND, "unknown kernel id");
     }
 }

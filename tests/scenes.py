@@ -3,6 +3,8 @@ generated from fixed seeds, and the order of the draws from a generator is part 
 
   * building blocks: small, soup, soup_with_duplicates, nested_boxes;
   * scenes that steer the trace kernels and the LBVH builder: variant, bvh_edge, deep, horizon_tiles, random_quads;
+  * scenes of up to 64 triangles, whose rays bring candidate masks: joined, box_prefix, sixty_four; sheets with sheet_rays, on which
+    a ray's test accepts many triangles and the nearest is rarely the first (tests/masked_search_cases.py);
   * the far-origin scenes (tests/lbvh_far.py has their ray families): tile_scene, soup(2000, 5);
   * scenes at the edges of what the LBVH takes -- scale, offset, shape, the builder's boundaries -- with rays to query them:
     scene(name) for name in NAMES (tests/test_lbvh_scale_cpu.py: the oracle's scale identities; tests/test_gpu_lbvh_scenes.py);
@@ -226,6 +228,86 @@ def random_quads(seed: int):
         m["type"] = _scene.SPECULAR if rng.random() < 0.3 else _scene.DIFFUSE
         m["roughness"] = np.float32(10.0 ** rng.uniform(-2.5, -0.3)) if m["type"] == _scene.SPECULAR else 0.0
     return tris, mats
+
+
+def joined(*parts):
+    """scenes one after the other, the material indices of each moved behind the ones before"""
+    tris, mats, base = [], [], 0
+    for t, m in parts:
+        t = t.copy()
+        t["id"] += base
+        base += len(m)
+        tris.append(t)
+        mats.append(m)
+    return np.concatenate(tris), np.concatenate(mats)
+
+
+def box_prefix(n):
+    """the first n triangles of the Cornell box, with all its materials"""
+    tris, mats = _scene.load_model()
+    return tris[:n].copy(), mats
+
+
+def sixty_four():
+    """the box and two random quad scenes behind it: 64 triangles, both mask words full"""
+    return joined(_scene.load_model(), random_quads(105), random_quads(1007))
+
+
+SHEET_SPACING = 0.09375
+SHEET_COPIES = ((5, 6), (1, 20), (25, 30))   # (quad, its copy): coincident triangles low/low, low/high and high/high in the mask words
+
+
+def sheets(alternate=False, seed=20261021):
+    """32 quads (a,b,c),(c,d,a) = 64 triangles parallel to z = const before the reference camera: half-sizes 1 .. 2.5, centres near
+    (0, 2.75), stacked SHEET_SPACING apart from z = 1 downwards in an order that is a fixed shuffle of the quad index, all facing +z --
+    a ray along -z passes the whole test of many triangles, and the nearest is rarely the lowest index.  Three whole quads are copies
+    of others (SHEET_COPIES): their triangles tie in t, u and v bit for bit, and the lower index has to win.  alternate: the odd quads
+    are mirrored to face -z, so that a bounced ray meets the sheets between."""
+    rng = np.random.default_rng(seed)
+    nq = 32
+    level = rng.permutation(nq)
+    tris = np.zeros(2 * nq, _scene.TRIANGLE_DTYPE)
+    mats = np.zeros(nq, _scene.MATERIAL_DTYPE)
+    for q in range(nq):
+        hx, hy = (np.float32(h) for h in 1.0 + 1.5 * np.sqrt(rng.uniform(0.0, 1.0, 2)))   # (more large sheets than small ones)
+        cx, cy = (np.float32(c) for c in np.array([0.0, 2.75]) + rng.uniform(-0.25, 0.25, 2))
+        z = np.float32(1.0 - SHEET_SPACING * level[q])
+        a, b, c, d = (cx - hx, cy - hy, z), (cx + hx, cy - hy, z), (cx + hx, cy + hy, z), (cx - hx, cy + hy, z)
+        if alternate and q & 1:
+            b, d = d, b
+        for k, (p1, p2, p3) in enumerate(((a, b, c), (c, d, a))):
+            t = tris[2 * q + k]
+            t["p1"][:3], t["p2"][:3], t["p3"][:3] = p1, p2, p3
+            t["id"] = q
+        m = mats[q]
+        m["albedo"] = tuple(rng.uniform(0.2, 0.95, 3)) + (1.0,)
+        m["emissive"] = (12.0, 12.0, 12.0, 1.0) if q % 5 == 2 else (0.0, 0.0, 0.0, 1.0)
+        m["type"] = _scene.SPECULAR if q % 7 == 3 else _scene.DIFFUSE
+        m["roughness"] = np.float32(0.2) if m["type"] == _scene.SPECULAR else 0.0
+    for src, dst in SHEET_COPIES:
+        for f in ("p1", "p2", "p3"):
+            tris[f][2 * dst: 2 * dst + 2] = tris[f][2 * src: 2 * src + 2]
+    return tris, mats
+
+
+def sheet_rays(n, seed=20261022):
+    """pt_ray words for sheets(): 80 % of the origins before the stack and the rest inside it, directions about -z with a spread of
+    0.35 and lengths 0.1 .. 10, a tenth of them turned the other way (everything is culled); the last eight rays hold a NaN or an
+    infinity in the origin or the direction"""
+    rng = np.random.default_rng(seed)
+    r = np.zeros((n, 8), np.float32)
+    front = rng.uniform(size=n) < 0.8
+    r[:, 0] = rng.uniform(-1.6, 1.6, n)
+    r[:, 1] = 2.75 + rng.uniform(-1.6, 1.6, n)
+    r[:, 2] = np.where(front, rng.uniform(1.05, 4.0, n), rng.uniform(1.0 - 31 * SHEET_SPACING, 1.0, n))
+    r[:, 3] = 1e20
+    d = np.concatenate([rng.normal(0.0, 0.35, (n, 2)), -np.ones((n, 1))], axis=1)
+    d[rng.uniform(size=n) < 0.1] *= -1.0
+    r[:, 4:7] = d * 10.0 ** rng.uniform(-1, 1, (n, 1))
+    bad = np.array([np.nan, np.inf, -np.inf, np.nan, np.inf, -np.inf, np.nan, np.inf], np.float32)
+    for k in range(8):
+        r[n - 8 + k, (0, 1, 2, 4, 5, 6, 4, 2)[k]] = bad[k]
+    return r
 
 
 def tile_scene() -> np.ndarray:

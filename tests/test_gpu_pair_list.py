@@ -17,34 +17,19 @@ import scenes
 from conftest import assert_fb_equal
 from gpu_support import options, render
 from oclpathtracer_amd import scene as _scene, shim
+from scenes import box_prefix, joined
 
 pytestmark = pytest.mark.gpu
 
 FRAMES = 4
 
 
-def _joined(*parts):
-    tris, mats, base = [], [], 0
-    for t, m in parts:
-        t = t.copy()
-        t["id"] += base
-        base += len(m)
-        tris.append(t)
-        mats.append(m)
-    return np.concatenate(tris), np.concatenate(mats)
-
-
-def _box_prefix(n):
-    tris, mats = _scene.load_model()
-    return tris[:n].copy(), mats
-
-
 SCENES = {
-    32: lambda: _box_prefix(32),
-    33: lambda: _box_prefix(33),
-    34: lambda: _box_prefix(34),
+    32: lambda: box_prefix(32),
+    33: lambda: box_prefix(33),
+    34: lambda: box_prefix(34),
     36: _scene.load_model,
-    64: lambda: _joined(_scene.load_model(), scenes.random_quads(105), scenes.random_quads(1007)),
+    64: lambda: joined(_scene.load_model(), scenes.random_quads(105), scenes.random_quads(1007)),
 }
 SIZES = [(64, 64), (33, 97)]
 

@@ -18,29 +18,13 @@ from gpu_support import options, render
 from oclpathtracer_amd import scene as _scene, shim
 from oclpathtracer_amd.camera import Camera
 from oclpathtracer_amd.render import Renderer
+from scenes import box_prefix, joined
 from test_gpu_secondary_masks import no_table, oracle_rows, snapshot
 from test_secondary_masks_cpu import records
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 STRIDE = 1009   # (a prime, and not the 211 of tests/test_gpu_secondary_masks.py)
-
-
-def joined(*parts):
-    """scenes one after the other, the material indices of each moved behind the ones before"""
-    tris, mats, base = [], [], 0
-    for t, m in parts:
-        t = t.copy()
-        t["id"] += base
-        base += len(m)
-        tris.append(t)
-        mats.append(m)
-    return np.concatenate(tris), np.concatenate(mats)
-
-
-def box_prefix(n):
-    tris, mats = _scene.load_model()
-    return tris[:n].copy(), mats
 
 
 def far_cornell():
