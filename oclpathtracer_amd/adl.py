@@ -234,8 +234,9 @@ class SyncObject:
             pass
 
 
-def _ev(sync: Optional[SyncObject]):
-    return sync._h if sync is not None else None
+def _handle(obj):
+    """the library's handle of an optional object (a SyncObject, a Buffer); None stays None"""
+    return obj._h if obj is not None else None
 
 
 class Buffer:
@@ -296,27 +297,27 @@ class Buffer:
         """Buffer<T>::write(host ptr | Buffer)  (Adl.h:218,222)."""
         lib = self.m_device._lib
         if isinstance(src, Buffer):
-            shim.check(lib.pt_buffer_copy(self._h, src._h, self._bytes(nElems), self._bytes(dstOffsetNElems), 0, _ev(syncObj)))
+            shim.check(lib.pt_buffer_copy(self._h, src._h, self._bytes(nElems), self._bytes(dstOffsetNElems), 0, _handle(syncObj)))
             return
         a = np.ascontiguousarray(src)
         if a.nbytes < self._bytes(nElems):
             raise ValueError("host source smaller than nElems")
         self._keep = a  # asynchronous copy: keep the source alive until the next sync
         shim.check(lib.pt_buffer_write(self._h, a.ctypes.data_as(ctypes.c_void_p), self._bytes(nElems),
-                                       self._bytes(dstOffsetNElems), _ev(syncObj)))
+                                       self._bytes(dstOffsetNElems), _handle(syncObj)))
 
     def read(self, dst, nElems: int, srcOffsetNElems: int = 0, syncObj: Optional[SyncObject] = None) -> None:
         """Buffer<T>::read(host ptr | Buffer)  (Adl.h:220,224)."""
         lib = self.m_device._lib
         if isinstance(dst, Buffer):
-            shim.check(lib.pt_buffer_copy(dst._h, self._h, self._bytes(nElems), 0, self._bytes(srcOffsetNElems), _ev(syncObj)))
+            shim.check(lib.pt_buffer_copy(dst._h, self._h, self._bytes(nElems), 0, self._bytes(srcOffsetNElems), _handle(syncObj)))
             return
         if not (isinstance(dst, np.ndarray) and dst.flags.c_contiguous and dst.flags.writeable):
             raise ValueError("read() needs a writable C-contiguous numpy array")
         if dst.nbytes < self._bytes(nElems):
             raise ValueError("host destination smaller than nElems")
         shim.check(lib.pt_buffer_read(self._h, dst.ctypes.data_as(ctypes.c_void_p), self._bytes(nElems),
-                                      self._bytes(srcOffsetNElems), _ev(syncObj)))
+                                      self._bytes(srcOffsetNElems), _handle(syncObj)))
 
     def getHostPtr(self, size: int = -1, blocking: bool = False) -> np.ndarray:
         """Buffer<T>::getHostPtr (Adl/Adl.inl:247-252): non-blocking by default -- call
@@ -413,6 +414,6 @@ class Launcher:
         ms = ctypes.c_float(0.0)
         kh = self.m_kernel.m_kernel if self.m_kernel is not None else None
         shim.check(self.m_deviceData._lib.pt_launch_2d(self.m_deviceData._h, kh, self._args, self.m_idx, numThreadsX,
-                                                       numThreadsY, localSizeX, localSizeY, _ev(syncObj),
+                                                       numThreadsY, localSizeX, localSizeY, _handle(syncObj),
                                                        ctypes.byref(ms)))
         return ms.value

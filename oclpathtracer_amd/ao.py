@@ -17,9 +17,10 @@ import numpy as np
 
 from . import adl, scene, shim
 from .camera import Camera
+from .image import ImageRenderer, ImageShare, frame_range
 
 
-class AORenderer:
+class AORenderer(ImageRenderer, scene.SceneHolder):
     """Ambient occlusion of a ``width`` x ``height`` image of ``triangles`` on ``dev``.
 
     ``triangles``: a ``scene.TRIANGLE_DTYPE`` array (uploaded to a buffer of this renderer's), or an ``adl.Buffer`` that already
@@ -32,61 +33,41 @@ class AORenderer:
                  stripe_rows: int = 16, n_ranks: int = 1, rank: int = 0):
         self.dev = dev
         self._lib = shim.load()
-        self.width, self.height = int(width), int(height)
         self.rays_per_sample, self.radius, self.miss_value = int(rays_per_sample), float(radius), float(miss_value)
-        self.stripe_rows, self.n_ranks, self.rank = int(stripe_rows), int(n_ranks), int(rank)
-        if self.width < 1 or self.height < 1 or self.width * self.height > 0x7fffffff:
-            raise ValueError("invalid image size %dx%d" % (self.width, self.height))
+        ImageShare.__init__(self, width, height, stripe_rows, n_ranks, rank)
         if not 1 <= self.rays_per_sample <= 256:
             raise ValueError("rays_per_sample must lie in 1..256")
         if not (math.isfinite(self.radius) and self.radius > 0.0):
             raise ValueError("radius must be finite and > 0")
         if not math.isfinite(self.miss_value):
             raise ValueError("miss_value must be finite")
-        self.local_rows = self._lib.pt_local_rows(self.height, self.stripe_rows, self.n_ranks, self.rank)
-        if self.local_rows < 0:
-            raise ValueError("invalid stripe geometry")
-        self.local_pixels = self.local_rows * self.width
         self._set_camera(camera)
-        self.tbuf = self.counts = self.image = None
-        self.tbuf, self.num_triangles, self._own_tbuf = scene.triangle_buffer(dev, triangles, num_triangles)
+        self.counts = self.image = None
+        self.scene = scene.SceneBuffers(dev, triangles, num_triangles, shape="triangles")
         n = max(self.local_pixels, 1)
-        self.counts = adl.Buffer(dev, 2 * n, np.uint32)
-        self.image = adl.Buffer(dev, n, adl.float4)
-        self.frames_done = 0
-
-    def _set_camera(self, camera: Optional[Camera]) -> None:
-        self._cam = Camera.struct_of(camera)   # rejected here, before anything is enqueued
-        self.camera = camera
-
-    def set_camera(self, camera: Optional[Camera]) -> None:
-        """AO from ``camera`` from now on (None: the reference's); the next render starts again at frame 0."""
-        self._set_camera(camera)
+        try:
+            self.counts = adl.Buffer(dev, 2 * n, np.uint32)
+            self.image = adl.Buffer(dev, n, adl.float4)
+        except Exception:
+            self.release()
+            raise
         self.frames_done = 0
 
     def params(self, frames: int, frame_begin: int) -> shim.AoParams:
-        p = shim.AoParams()
-        p.width, p.height = self.width, self.height
-        p.frame_begin, p.frame_count = frame_begin, frames
+        p = self.fill(shim.AoParams(), frames, frame_begin)
         p.num_triangles, p.rays_per_sample = self.num_triangles, self.rays_per_sample
         p.radius, p.miss_value = self.radius, self.miss_value
-        p.stripe_rows, p.n_ranks, p.rank = self.stripe_rows, self.n_ranks, self.rank
         return p
 
     def render(self, frames: int, frame_begin: Optional[int] = None, *, sync: Optional[adl.SyncObject] = None) -> None:
         """Enqueue frames [frame_begin, frame_begin + frames) (default: continue after the last call); frame_begin 0 starts the
         counts afresh.  The image is resolved from the counts afterwards."""
-        if frame_begin is None:
-            frame_begin = self.frames_done
-        frames, frame_begin = int(frames), int(frame_begin)
-        if frames < 0 or frame_begin < 0 or frame_begin + frames > 0x7fffffff:
-            raise ValueError("invalid frame range [%d, %d)" % (frame_begin, frame_begin + frames))
+        frames, frame_begin = frame_range(frames, frame_begin, self.frames_done)
         if (frame_begin + frames) * self.rays_per_sample > 0xffffffff:
             raise ValueError("(frame_begin + frames) x rays_per_sample exceeds 2^32 - 1: the counts could wrap")
         p = self.params(frames, frame_begin)
-        shim.check(self._lib.pt_render_ao(self.dev._h, self.tbuf._h, self.counts._h, self.image._h, ctypes.byref(p),
-                                          ctypes.byref(self._cam) if self._cam is not None else None,
-                                          sync._h if sync is not None else None))
+        shim.check(self._lib.pt_render_ao(self.dev._h, self.tbuf._h, self.counts._h, self.image._h, ctypes.byref(p), self._cam_ref(),
+                                          adl._handle(sync)))
         self.frames_done = frame_begin + frames
 
     def read_counts(self) -> np.ndarray:
@@ -113,9 +94,8 @@ class AORenderer:
         for b in (self.counts, self.image):
             if b is not None:
                 b.release()
-        if self._own_tbuf and self.tbuf is not None:
-            self.tbuf.release()
-        self.tbuf = self.counts = self.image = None
+        self.counts = self.image = None
+        self.scene.release()
 
 
 def resolve(counts: np.ndarray, rays_per_sample: int, miss_value: float = 1.0) -> np.ndarray:

@@ -19,6 +19,8 @@ import numpy as np
 
 from . import adl, shim
 from .features import FEATURES, FeatureRenderer
+from .image import check_size
+from .query import into_tensor
 
 # the starting values of the numpy prototype the filter was designed on (Cornell box, 48 x 48, 8 frames: the relative MSE falls to
 # 0.025 of the unfiltered mean's; profiles/denoise/quality.txt)
@@ -41,9 +43,7 @@ class Denoiser:
                  spatial_below: int = 0):
         self.dev = dev
         self._lib = shim.load()
-        self.width, self.height = int(width), int(height)
-        if self.width < 1 or self.height < 1 or self.width * self.height > 0x7fffffff:
-            raise ValueError("invalid image size %dx%d" % (self.width, self.height))
+        self.width, self.height = check_size(width, height)
         if not 0 <= int(levels) <= 8 or not 0 <= int(normal_squarings) <= 8:
             raise ValueError("levels and normal_squarings must lie in 0..8")
         p = shim.DenoiseParams()
@@ -79,7 +79,7 @@ class Denoiser:
             raise ValueError("the features must be those of the whole %dx%d image" % (self.width, self.height))
         if not features._valid:
             raise ValueError("the feature renderer has rendered nothing yet")
-        return [features.mom[f]._h if f in features.mom else None for f in FEATURES]
+        return [adl._handle(features.mom.get(f)) for f in FEATURES]
 
     def _enqueue(self, colour: adl.Buffer, features, out_h, ev) -> None:
         if self.spatial is None:
@@ -97,17 +97,7 @@ class Denoiser:
             import torch
 
             out = torch.zeros((self.height, self.width, 4), dtype=torch.float32, device="cuda:%d" % self.dev.m_deviceIdx)
-            stream = torch.cuda.current_stream(out.device)
-            wrap = adl.Buffer()
-            wrap.setRawPtr(self.dev, int(out.data_ptr()), int(out.numel() * out.element_size()))
-            if self._sync is None:
-                self._sync = adl.SyncObject(self.dev)
-            try:
-                self.dev.waitStream(stream.cuda_stream)
-                self._enqueue(colour, features, wrap._h, self._sync._h)
-                self._sync.waitOnStream(stream.cuda_stream)
-            finally:
-                wrap.release()   # (waits for the device: the tensor is complete when this returns)
+            self._sync = into_tensor(self.dev, out, self._sync, lambda out_h, ev: self._enqueue(colour, features, out_h, ev))
             return out
         self._enqueue(colour, features, self.out._h, None)
         res = np.zeros((self.height, self.width, 4), np.float32)
@@ -133,9 +123,7 @@ def for_renderer(renderer, **kw):
     d = Denoiser(renderer.dev, renderer.width, renderer.height, **kw)
     f = None
     try:
-        f = FeatureRenderer(renderer.dev, renderer.tbuf, renderer.mbuf, renderer.width, renderer.height, features=FEATURES,
-                            camera=renderer.camera, num_triangles=renderer.num_triangles, num_materials=renderer.num_materials,
-                            stripe_rows=renderer.stripe_rows)
+        f = FeatureRenderer.on(renderer, features=FEATURES)
         if renderer.frames_done:
             f.render(renderer.frames_done, 0)
     except Exception:

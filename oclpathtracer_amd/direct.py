@@ -30,6 +30,8 @@ import numpy as np
 from . import adl, scene, shim
 from .camera import Camera
 from .environment import Environment, check_env_samples
+from .features import variance_map
+from .image import ImageRenderer, ImageShare, frame_range
 
 _WORKSPACE_BYTES = 64 << 20   # the default workspace holds as many whole frames as fit in this, at most 64
 
@@ -37,63 +39,6 @@ _WORKSPACE_BYTES = 64 << 20   # the default workspace holds as many whole frames
 # relative standard error sqrt(sum of the pixels' squared standard errors / sum of their squared means); the pixels with at least two
 # finite samples (the only ones both figures count); the finite samples and the samples rejected for a NaN or an infinity, all pixels
 Noise = collections.namedtuple("Noise", "variance_per_sample relative_error pixels samples rejected")
-
-
-def _handle(obj):
-    """the library's handle of an optional object (a SyncObject, a Buffer); None stays None"""
-    return obj._h if obj is not None else None
-
-
-def _check_lights(lights, num_triangles: int) -> np.ndarray:
-    a = np.asarray(lights)
-    if a.dtype.kind not in "iu":
-        raise TypeError("lights must be an array of integers (triangle indices)")
-    if a.ndim != 1:
-        raise ValueError("lights must be one-dimensional")
-    if len(a) >= 1 << 24:
-        raise ValueError("at most 2^24 - 1 lights")
-    if len(a) and (int(a.min()) < 0 or int(a.max()) >= num_triangles):
-        raise ValueError("a light index lies outside [0, %d)" % num_triangles)
-    return np.ascontiguousarray(a, np.int32)
-
-
-class SceneBuffers:
-    """The scene of a lit call on ``dev``: the triangle and material buffers, the light list and its buffer -- what ``DirectRenderer``,
-    ``IndirectRenderer`` and ``radiance.RadianceCaster`` are built on.  Everything about the scene that can be refused is refused
-    before the first device call.  ``own_tbuf`` / ``own_mbuf`` say which of the two buffers were made here; the light buffer always is."""
-
-    def __init__(self, dev: adl.Device, triangles, materials, lights, num_triangles: Optional[int], num_materials: Optional[int]):
-        t_host = isinstance(triangles, np.ndarray)
-        m_host = isinstance(materials, np.ndarray)
-        if not (t_host or isinstance(triangles, adl.Buffer)) or (t_host and triangles.dtype != scene.TRIANGLE_DTYPE):
-            raise TypeError("triangles must be a scene.TRIANGLE_DTYPE array or an adl.Buffer")
-        if not (m_host or isinstance(materials, adl.Buffer)) or (m_host and materials.dtype != scene.MATERIAL_DTYPE):
-            raise TypeError("materials must be a scene.MATERIAL_DTYPE array or an adl.Buffer")
-        if not t_host and num_triangles is None:
-            raise ValueError("num_triangles is required with an adl.Buffer of triangles")
-        if not m_host and num_materials is None:
-            raise ValueError("num_materials is required with an adl.Buffer of materials")
-        ntri = len(triangles) if t_host else int(num_triangles)
-        nmat = len(materials) if m_host else int(num_materials)
-        if ntri < 0 or nmat < 1:
-            raise ValueError("a scene needs num_triangles >= 0 and at least one material")
-        if lights is None:
-            if not (t_host and m_host):
-                raise ValueError("lights must be given with adl.Buffers of triangles or materials (scene.emitters derives them)")
-            lights = scene.emitters(triangles, materials)
-        self.lights = _check_lights(lights, ntri)
-        self.num_materials = nmat
-
-        self.tbuf, self.num_triangles, self.own_tbuf = scene.triangle_buffer(dev, triangles, num_triangles)
-        self.own_mbuf = False
-        if m_host:
-            self.mbuf, self.own_mbuf = adl.Buffer(dev, nmat, scene.MATERIAL_DTYPE), True
-            self.mbuf.write(np.ascontiguousarray(materials), nmat)
-        else:
-            self.mbuf = materials
-        self.lbuf = adl.Buffer(dev, max(len(self.lights), 1), np.int32)
-        if len(self.lights):
-            self.lbuf.write(self.lights, len(self.lights))
 
 
 def light_table(lib, dev: adl.Device, tbuf, num_triangles: int, mbuf, num_materials: int, lights_h, num_lights: int):
@@ -120,7 +65,7 @@ def light_counts(lib, dev: adl.Device, lights_h, num_lights: int, num_triangles:
     return counts
 
 
-class DirectRenderer:
+class DirectRenderer(ImageRenderer, scene.SceneHolder):
     """Direct illumination of a ``width`` x ``height`` image of ``triangles`` with ``materials`` on ``dev``.
 
     ``triangles`` / ``materials``: ``scene.TRIANGLE_DTYPE`` / ``scene.MATERIAL_DTYPE`` arrays (uploaded to buffers of this
@@ -154,27 +99,15 @@ class DirectRenderer:
         self._moments_valid = False   # the moments buffer holds this image's sums (a call from frame 0 has reset it)
         self.dev = dev
         self._lib = shim.load()
-        self.width, self.height = int(width), int(height)
         self.light_samples = int(light_samples)
-        self.stripe_rows, self.n_ranks, self.rank = int(stripe_rows), int(n_ranks), int(rank)
-        if self.width < 1 or self.height < 1 or self.width * self.height > 0x7fffffff:
-            raise ValueError("invalid image size %dx%d" % (self.width, self.height))
+        ImageShare.__init__(self, width, height, stripe_rows, n_ranks, rank)
         if not 1 <= self.light_samples <= 256:
             raise ValueError("light_samples must lie in 1..256")
         if chunk_frames is not None and int(chunk_frames) < 1:
             raise ValueError("chunk_frames must be at least 1")
-        self.local_rows = self._lib.pt_local_rows(self.height, self.stripe_rows, self.n_ranks, self.rank)
-        if self.local_rows < 0:
-            raise ValueError("invalid stripe geometry")
-        self.local_pixels = self.local_rows * self.width
         self._set_camera(camera)
-        self.tbuf = self.mbuf = self.lbuf = self.samples = self.fb = None
-        self._own_tbuf = self._own_mbuf = False
-        # everything about the scene that can be refused is refused before the first device call (SceneBuffers)
-        s = SceneBuffers(dev, triangles, materials, lights, num_triangles, num_materials)
-        self.lights, self.num_triangles, self.num_materials = s.lights, s.num_triangles, s.num_materials
-        self.tbuf, self.mbuf, self.lbuf = s.tbuf, s.mbuf, s.lbuf
-        self._own_tbuf, self._own_mbuf = s.own_tbuf, s.own_mbuf
+        self.samples = self.fb = None
+        self.scene = scene.SceneBuffers(dev, triangles, num_triangles, materials, num_materials, lights)
         n = max(self.local_pixels, 1)
         if chunk_frames is None:
             chunk_frames = max(1, min(64, _WORKSPACE_BYTES // (12 * n)))
@@ -236,25 +169,10 @@ class DirectRenderer:
         self._env = None
         if environment is not None:
             self._env = environment.buffers(self.dev) + (environment.block(ke),)
-        self.frames_done = 0
-        self._moments_valid = False
+        self._restart()
 
-    def _set_camera(self, camera: Optional[Camera]) -> None:
-        self._cam = Camera.struct_of(camera)   # rejected here, before anything is enqueued
-        self.camera = camera
-
-    # the handles every entry point takes the same way
-    def _lights_h(self):
-        """the light list's handle; None for an empty list (the buffer then holds one unused entry)"""
-        return self.lbuf._h if len(self.lights) else None
-
-    def _cam_ref(self):
-        """the camera's struct by reference; None for the reference's camera"""
-        return ctypes.byref(self._cam) if self._cam is not None else None
-
-    def set_camera(self, camera: Optional[Camera]) -> None:
-        """Render from ``camera`` from now on (None: the reference's); the next render starts again at frame 0."""
-        self._set_camera(camera)
+    def _restart(self) -> None:
+        """another camera or another sky is another image: the next render starts at frame 0, and so do the figures"""
         self.frames_done = 0
         self._moments_valid = False
 
@@ -263,26 +181,17 @@ class DirectRenderer:
     _ENTRY = "pt_render_direct"
 
     def params(self, frames: int, frame_begin: int):
-        p = self._PARAMS()
-        p.width, p.height = self.width, self.height
-        p.frame_begin, p.frame_count = frame_begin, frames
+        p = self.fill(self._PARAMS(), frames, frame_begin)
         p.num_triangles, p.num_materials, p.num_lights = self.num_triangles, self.num_materials, len(self.lights)
         p.light_samples = self.light_samples
-        p.stripe_rows, p.n_ranks, p.rank = self.stripe_rows, self.n_ranks, self.rank
         return p
 
     def render(self, frames: int, frame_begin: Optional[int] = None, sync: Optional[adl.SyncObject] = None) -> None:
         """Enqueue frames [frame_begin, frame_begin + frames) (default: continue after the last call); frame_begin 0 starts the
         running mean afresh.  With ``moments`` the frames go out as calls of at most ``chunk_frames`` frames, each followed by the
         moments of its samples, and frame_begin must be 0 or ``frames_done``: a frame rendered twice would be counted twice."""
-        if frame_begin is None:
-            frame_begin = self.frames_done
-        frames, frame_begin = int(frames), int(frame_begin)
-        if frames < 0 or frame_begin < 0 or frame_begin + frames > 0x7fffffff:
-            raise ValueError("invalid frame range [%d, %d)" % (frame_begin, frame_begin + frames))
+        frames, frame_begin = frame_range(frames, frame_begin, self.frames_done, resumes=self.moments, who="with moments a render")
         if self.moments and frames > 0:
-            if frame_begin not in (0, self.frames_done):
-                raise ValueError("with moments a render starts at frame 0 or at frames_done (%d), not at %d" % (self.frames_done, frame_begin))
             first, end = frame_begin, frame_begin + frames
             while first < end:
                 k = min(self.chunk_frames, end - first)
@@ -303,16 +212,16 @@ class DirectRenderer:
             env, env_cdf, block = self._env
             return self._lib.pt_render_direct_env(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), self.cdf._h, self.tri_q._h, env._h,
                                                   env_cdf._h, self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(block),
-                                                  self._cam_ref(), _handle(sync))
+                                                  self._cam_ref(), adl._handle(sync))
         if self._ris is not None:
             return self._lib.pt_render_direct_ris(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), self.cdf._h, self.tri_q._h,
                                                   self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(self._ris), self._cam_ref(),
-                                                  _handle(sync))
+                                                  adl._handle(sync))
         if self.light_choice == "power":
             return self._lib.pt_render_direct_power(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), self.cdf._h, self.tri_q._h,
-                                                    self.samples._h, self.fb._h, ctypes.byref(p), self._cam_ref(), _handle(sync))
+                                                    self.samples._h, self.fb._h, ctypes.byref(p), self._cam_ref(), adl._handle(sync))
         return getattr(self._lib, self._ENTRY)(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), self.samples._h, self.fb._h,
-                                               ctypes.byref(p), self._cam_ref(), _handle(sync))
+                                               ctypes.byref(p), self._cam_ref(), adl._handle(sync))
 
     def read(self) -> np.ndarray:
         """Local framebuffer as (local_rows * width, 4) float32, the renderer's layout (synchronises)."""
@@ -331,30 +240,23 @@ class DirectRenderer:
         last start at frame 0: ``(var float32 [local_pixels, 3], n uint32 [local_pixels])``, n the pixel's finite samples (a pixel
         with n < 2 has variance 0).  Resolved on the device (``pt_moments_resolve``); synchronises."""
         self._need_moments()
-        rec = np.zeros((self.local_pixels, 4), np.float32)
-        if self.local_pixels and self._moments_valid:
-            if self.noise_map is None:
-                self.noise_map = adl.Buffer(self.dev, self.local_pixels, adl.float4)
-            shim.check(self._lib.pt_moments_resolve(self.dev._h, self.mom._h, self.local_pixels, self.noise_map._h, None, None))
-            self.noise_map.read(rec, self.local_pixels)
-            self.dev.waitForCompletion()
-        return np.ascontiguousarray(rec[:, :3]), np.ascontiguousarray(rec[:, 3]).view(np.uint32)
+        var, n, self.noise_map = variance_map(self, self.mom, self._moments_valid, self.noise_map)
+        return var, n
 
     def noise(self) -> Noise:
         """The image-wide noise figures (``Noise``) of the frames rendered since the last start at frame 0, reduced on the device and
         read back in 48 bytes; synchronises.  Without a pixel of two finite samples both figures are NaN."""
         self._need_moments()
-        words = np.zeros(6, np.uint64)
+        raw = np.zeros(ctypes.sizeof(shim.NoiseSummary), np.uint8)
         if self.local_pixels and self._moments_valid:
             shim.check(self._lib.pt_moments_resolve(self.dev._h, self.mom._h, self.local_pixels, None, self.summary._h, None))
-            self.summary.read(words, words.nbytes)
+            self.summary.read(raw, raw.nbytes)
             self.dev.waitForCompletion()
-        var_sum, se2_sum, mean2_sum = words[:3].view(np.float64)
-        pixels, samples, rejected = (int(w) for w in words[3:])
+        s = shim.NoiseSummary.from_buffer(raw)
         with np.errstate(divide="ignore", invalid="ignore"):
-            per_sample = float(var_sum / np.float64(3 * pixels))
-            relative = float(np.sqrt(se2_sum / mean2_sum))
-        return Noise(per_sample, relative, pixels, samples, rejected)
+            per_sample = float(np.float64(s.var_sum) / np.float64(3 * s.pixels))
+            relative = float(np.sqrt(np.float64(s.se2_sum) / np.float64(s.mean2_sum)))
+        return Noise(per_sample, relative, s.pixels, s.samples, s.rejected)
 
     def render_until(self, relative_error: float, max_frames: int, check_every: Optional[int] = None) -> int:
         """Render on from ``frames_done``, ``check_every`` frames at a time (default ``chunk_frames``), until ``noise().relative_error``
@@ -391,12 +293,9 @@ class DirectRenderer:
         return TemporalAccumulator(self, **kw)
 
     def release(self) -> None:
-        for b in (self.lbuf, self.samples, self.fb, self.cdf, self.tri_q, self.mom, self.summary, self.noise_map):
+        for b in (self.samples, self.fb, self.cdf, self.tri_q, self.mom, self.summary, self.noise_map):
             if b is not None:
                 b.release()
         self.cdf = self.tri_q = self.mom = self.summary = self.noise_map = None
-        if self._own_tbuf and self.tbuf is not None:
-            self.tbuf.release()
-        if self._own_mbuf and self.mbuf is not None:
-            self.mbuf.release()
-        self.tbuf = self.mbuf = self.lbuf = self.samples = self.fb = None
+        self.samples = self.fb = None
+        self.scene.release()

@@ -16,16 +16,33 @@ from typing import Optional
 
 import numpy as np
 
-from . import adl, scene, shim
+from . import adl, image, scene, shim
 from .camera import Camera
+from .image import LIMIT, ImageRenderer, ImageShare, frame_range
+from .query import into_tensor
+from .shim import MOMENTS_DTYPE
 
 FEATURES = ("albedo", "normal", "depth", "emission")   # the order of pt_render_features' outputs
-MOMENTS_DTYPE = np.dtype([("sum", np.float64, 3), ("sum2", np.float64, 3), ("n", np.uint32), ("rejected", np.uint32)])   # pt_pixel_moments
-assert MOMENTS_DTYPE.itemsize == ctypes.sizeof(shim.PixelMoments) == 56
 _WORKSPACE_BYTES = 64 << 20   # the default workspaces hold, all together, as many whole frames as fit in this, at most 64
 
 
-class FeatureRenderer:
+def variance_map(r, mom: adl.Buffer, valid: bool, noise_map: Optional[adl.Buffer], idle_wait: bool = False):
+    """``(var float32 [local_pixels, 3], n uint32 [local_pixels], the noise map)`` of renderer ``r``'s moments ``mom``: resolved on the
+    device (``pt_moments_resolve``) into ``noise_map`` (made here on first use), read back and split; synchronises.  Zeros while the
+    moments are not ``valid``, without a device call -- but for a wait where the caller has always waited (``idle_wait``)."""
+    rec = np.zeros((r.local_pixels, 4), np.float32)
+    if r.local_pixels and valid:
+        if noise_map is None:
+            noise_map = adl.Buffer(r.dev, r.local_pixels, adl.float4)
+        shim.check(r._lib.pt_moments_resolve(r.dev._h, mom._h, r.local_pixels, noise_map._h, None, None))
+        noise_map.read(rec, r.local_pixels)
+        r.dev.waitForCompletion()
+    elif idle_wait:
+        r.dev.waitForCompletion()
+    return np.ascontiguousarray(rec[:, :3]), np.ascontiguousarray(rec[:, 3]).view(np.uint32), noise_map
+
+
+class FeatureRenderer(ImageRenderer, scene.SceneHolder):
     """First-hit features of a ``width`` x ``height`` image of ``triangles`` with ``materials`` on ``dev``.
 
     ``triangles`` / ``materials``: ``scene.TRIANGLE_DTYPE`` / ``scene.MATERIAL_DTYPE`` arrays (uploaded to buffers of this renderer's),
@@ -43,41 +60,20 @@ class FeatureRenderer:
         self.features = tuple(features)
         if not self.features or len(set(self.features)) != len(self.features) or any(f not in FEATURES for f in self.features):
             raise ValueError("features must be a non-empty selection of %s without repeats" % (FEATURES,))
-        self.width, self.height = int(width), int(height)
-        self.stripe_rows, self.n_ranks, self.rank = int(stripe_rows), int(n_ranks), int(rank)
-        if self.width < 1 or self.height < 1 or self.width * self.height > 0x7fffffff:
-            raise ValueError("invalid image size %dx%d" % (self.width, self.height))
+        ImageShare.__init__(self, width, height, stripe_rows, n_ranks, rank)
         if workspace_frames is not None and int(workspace_frames) < 1:
             raise ValueError("workspace_frames must be at least 1")
-        self.local_rows = self._lib.pt_local_rows(self.height, self.stripe_rows, self.n_ranks, self.rank)
-        if self.local_rows < 0:
-            raise ValueError("invalid stripe geometry")
-        self.local_pixels = self.local_rows * self.width
         self._set_camera(camera)
-        self.tbuf = self.mbuf = self._noise = self._sync = None
-        self._own_tbuf = self._own_mbuf = False
+        self._noise = self._sync = None
         self.samples, self.mom = {}, {}
-        m_host = isinstance(materials, np.ndarray)
-        if not (m_host or isinstance(materials, adl.Buffer)) or (m_host and materials.dtype != scene.MATERIAL_DTYPE):
-            raise TypeError("materials must be a scene.MATERIAL_DTYPE array or an adl.Buffer")
-        if not m_host and num_materials is None:
-            raise ValueError("num_materials is required with an adl.Buffer of materials")
-        self.num_materials = len(materials) if m_host else int(num_materials)
-        if self.num_materials < 1:
-            raise ValueError("a scene needs at least one material")
+        self.scene = scene.SceneBuffers(dev, triangles, num_triangles, materials, num_materials, shape="materials")
         n = max(self.local_pixels, 1)
         if workspace_frames is None:
             workspace_frames = max(1, min(64, _WORKSPACE_BYTES // (12 * n * len(self.features))))
-        self.workspace_frames = min(int(workspace_frames), max(1, 0x7fffffff // n))   # (a call is one launch: fewer than 2^31 samples)
+        self.workspace_frames = min(int(workspace_frames), max(1, LIMIT // n))   # (a call is one launch: fewer than 2^31 samples)
         self.frames_done = 0
         self._valid = False   # the moments hold this image's sums (a call from frame 0 has reset them)
         try:
-            self.tbuf, self.num_triangles, self._own_tbuf = scene.triangle_buffer(dev, triangles, num_triangles)
-            if m_host:
-                self.mbuf, self._own_mbuf = adl.Buffer(dev, self.num_materials, scene.MATERIAL_DTYPE), True
-                self.mbuf.write(np.ascontiguousarray(materials), self.num_materials)
-            else:
-                self.mbuf = materials
             for f in self.features:
                 self.samples[f] = adl.Buffer(dev, 3 * n * self.workspace_frames, np.float32)
                 self.mom[f] = adl.Buffer(dev, n * MOMENTS_DTYPE.itemsize, np.uint8)
@@ -85,22 +81,22 @@ class FeatureRenderer:
             self.release()
             raise
 
-    def _set_camera(self, camera: Optional[Camera]) -> None:
-        self._cam = Camera.struct_of(camera)   # rejected here, before anything is enqueued
-        self.camera = camera
+    @classmethod
+    def on(cls, renderer, **kw) -> "FeatureRenderer":
+        """A feature renderer on ``renderer``'s scene buffers (``Renderer.feature_renderer``, ``DirectRenderer.denoiser`` and
+        ``.temporal``): one prepared scene, one LBVH.  ``kw`` are this class's; the image size, camera and sharding default to
+        ``renderer``'s.  Release it before the renderer."""
+        width, height = image.like(renderer, kw)
+        return cls(renderer.dev, renderer.tbuf, renderer.mbuf, width, height, num_triangles=renderer.num_triangles,
+                   num_materials=renderer.num_materials, **kw)
 
-    def set_camera(self, camera: Optional[Camera]) -> None:
-        """Features from ``camera``, its lens included, from now on (None: the reference's); the next render starts again at frame 0."""
-        self._set_camera(camera)
+    def _restart(self) -> None:
         self.frames_done = 0
         self._valid = False
 
     def params(self, frames: int, frame_begin: int) -> shim.FeatureParams:
-        p = shim.FeatureParams()
-        p.width, p.height = self.width, self.height
-        p.frame_begin, p.frame_count = frame_begin, frames
+        p = self.fill(shim.FeatureParams(), frames, frame_begin)
         p.num_triangles, p.num_materials = self.num_triangles, self.num_materials
-        p.stripe_rows, p.n_ranks, p.rank = self.stripe_rows, self.n_ranks, self.rank
         return p
 
     def _need(self, name: str) -> None:
@@ -113,23 +109,16 @@ class FeatureRenderer:
         frame_begin must be 0 or ``frames_done``: a frame rendered twice would be counted twice.  ``restart``: the moments start
         afresh at ANY frame_begin -- the image of a new camera whose frames go on where a lit renderer's stand
         (``temporal.TemporalAccumulator``)."""
-        if frame_begin is None:
-            frame_begin = self.frames_done
-        frames, frame_begin = int(frames), int(frame_begin)
-        if frames < 0 or frame_begin < 0 or frame_begin + frames > 0x7fffffff:
-            raise ValueError("invalid frame range [%d, %d)" % (frame_begin, frame_begin + frames))
-        if frames > 0 and not restart and frame_begin not in (0, self.frames_done):
-            raise ValueError("a render starts at frame 0 or at frames_done (%d), not at %d" % (self.frames_done, frame_begin))
-        cam = ctypes.byref(self._cam) if self._cam is not None else None
-        outs = [self.samples[f]._h if f in self.samples else None for f in FEATURES]
+        frames, frame_begin = frame_range(frames, frame_begin, self.frames_done, resumes=not restart)
+        outs = [adl._handle(self.samples.get(f)) for f in FEATURES]
         first, end = frame_begin, frame_begin + frames
         while first < end:
             k = min(self.workspace_frames, end - first)
             p = self.params(k, first)
-            shim.check(self._lib.pt_render_features(self.dev._h, self.tbuf._h, self.mbuf._h, *outs, ctypes.byref(p), cam, None))
+            shim.check(self._lib.pt_render_features(self.dev._h, self.tbuf._h, self.mbuf._h, *outs, ctypes.byref(p), self._cam_ref(), None))
             last = first + k == end
             for i, f in enumerate(self.features):
-                ev = sync._h if sync is not None and last and i == len(self.features) - 1 else None
+                ev = adl._handle(sync) if last and i == len(self.features) - 1 else None
                 if self.local_pixels:
                     shim.check(self._lib.pt_sample_moments(self.dev._h, self.samples[f]._h, self.mom[f]._h, self.local_pixels, k,
                                                            int(first == 0 or (restart and first == frame_begin)), ev))
@@ -167,33 +156,11 @@ class FeatureRenderer:
 
             out = torch.zeros((self.local_pixels, 4), dtype=torch.float32, device="cuda:%d" % self.dev.m_deviceIdx)
             if self.local_pixels and self._valid:
-                self._resolve_into(name, out)
+                self._sync = into_tensor(self.dev, out, self._sync, lambda out_h, ev: shim.check(
+                    self._lib.pt_moments_resolve(self.dev._h, self.mom[name]._h, self.local_pixels, out_h, None, ev)))
             return out
-        rec = np.zeros((self.local_pixels, 4), np.float32)
-        if self.local_pixels and self._valid:
-            if self._noise is None:
-                self._noise = adl.Buffer(self.dev, self.local_pixels, adl.float4)
-            shim.check(self._lib.pt_moments_resolve(self.dev._h, self.mom[name]._h, self.local_pixels, self._noise._h, None, None))
-            self._noise.read(rec, self.local_pixels)
-        self.dev.waitForCompletion()
-        return np.ascontiguousarray(rec[:, :3]), np.ascontiguousarray(rec[:, 3]).view(np.uint32)
-
-    def _resolve_into(self, name: str, out) -> None:
-        """pt_moments_resolve into a tensor of the caller's, as RayCaster writes into one: behind torch's stream, and torch's later
-        work behind the result"""
-        import torch
-
-        stream = torch.cuda.current_stream(out.device)
-        wrap = adl.Buffer()
-        wrap.setRawPtr(self.dev, int(out.data_ptr()), int(out.numel() * out.element_size()))
-        if self._sync is None:
-            self._sync = adl.SyncObject(self.dev)
-        try:
-            self.dev.waitStream(stream.cuda_stream)
-            shim.check(self._lib.pt_moments_resolve(self.dev._h, self.mom[name]._h, self.local_pixels, wrap._h, None, self._sync._h))
-            self._sync.waitOnStream(stream.cuda_stream)
-        finally:
-            wrap.release()   # (waits for the device: the tensor is complete when this returns)
+        var, n, self._noise = variance_map(self, self.mom[name], self._valid, self._noise, idle_wait=True)
+        return var, n
 
     def depth(self):
         """``(mean t over the pixel's hits float64 [local_pixels], coverage float64 [local_pixels])`` from the depth feature's sums:
@@ -223,8 +190,4 @@ class FeatureRenderer:
                 b.release()
         self.samples, self.mom = {}, {}
         self._noise = self._sync = None
-        if self._own_tbuf and self.tbuf is not None:
-            self.tbuf.release()
-        if self._own_mbuf and self.mbuf is not None:
-            self.mbuf.release()
-        self.tbuf = self.mbuf = None
+        self.scene.release()

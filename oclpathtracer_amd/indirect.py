@@ -50,7 +50,7 @@ import math
 import numpy as np
 
 from . import adl, shim
-from .direct import DirectRenderer, _handle, light_counts
+from .direct import DirectRenderer, light_counts
 from .render import BOUNCES
 
 
@@ -99,7 +99,7 @@ class IndirectRenderer(DirectRenderer):
         self.roulette = Roulette.of(roulette)
         if kw.get("environment") is not None and not self.mis:
             raise ValueError("an environment needs mis=True: the sky is balanced against the BRDF ray")
-        self._rr = None if self.roulette is None else shim.Roulette(self.roulette.first_bounce, self.roulette.max_survival)
+        self._rr = None if self.roulette is None else shim.Roulette(*self.roulette)
         self.counts = None
         self.pixel_list = None      # the list of render_adaptive, allocated by its first call
         self._adaptive = False      # an adaptive pass has run since the last start at frame 0: the pixels share no frame number
@@ -122,28 +122,27 @@ class IndirectRenderer(DirectRenderer):
         scene3 = (self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h())
         if self._env is not None:
             env, env_cdf, block = self._env
-            rr = self._rr if self._rr is not None else shim.Roulette(65535, 1.0)   # (no roulette: a first bounce no path reaches)
-            return self._lib.pt_render_indirect_env(*scene3, _handle(self.counts), _handle(self.cdf), _handle(self.tri_q), env._h, env_cdf._h,
-                                                    self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(rr), ctypes.byref(block),
-                                                    self._cam_ref(), _handle(sync))
+            return self._lib.pt_render_indirect_env(*scene3, adl._handle(self.counts), adl._handle(self.cdf), adl._handle(self.tri_q), env._h, env_cdf._h,
+                                                    self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(self._rr or shim.NO_ROULETTE), ctypes.byref(block),
+                                                    self._cam_ref(), adl._handle(sync))
         if self._ris is not None:
-            rr = self._rr if self._rr is not None else shim.Roulette(65535, 1.0)   # (no roulette: a first bounce no path reaches)
-            return self._lib.pt_render_indirect_ris(*scene3, *self._estimator(), self.samples._h, self.fb._h, ctypes.byref(p), ctypes.byref(rr),
-                                                    ctypes.byref(self._ris), self._cam_ref(), _handle(sync))
+            return self._lib.pt_render_indirect_ris(*scene3, *self._estimator(), self.samples._h, self.fb._h, ctypes.byref(p),
+                                                    ctypes.byref(self._rr or shim.NO_ROULETTE),
+                                                    ctypes.byref(self._ris), self._cam_ref(), adl._handle(sync))
         if self._rr is not None:
             return self._lib.pt_render_indirect_rr(*scene3, *self._estimator(), self.samples._h, self.fb._h, ctypes.byref(p),
-                                                   ctypes.byref(self._rr), self._cam_ref(), _handle(sync))
+                                                   ctypes.byref(self._rr), self._cam_ref(), adl._handle(sync))
         if self.light_choice == "power":
             return self._lib.pt_render_indirect_power(*scene3, *self._estimator(), self.samples._h, self.fb._h, ctypes.byref(p),
-                                                      self._cam_ref(), _handle(sync))
+                                                      self._cam_ref(), adl._handle(sync))
         if not self.mis:
             return super()._call(p, sync)
         return self._lib.pt_render_indirect_mis(*scene3, self.counts._h, self.samples._h, self.fb._h, ctypes.byref(p), self._cam_ref(),
-                                                _handle(sync))
+                                                adl._handle(sync))
 
     def _estimator(self):
         """(mis, counts, cdf, tri_q) as the entry points with an estimator argument take them: a handle the estimator does not read is None"""
-        return int(self.mis), _handle(self.counts), _handle(self.cdf), _handle(self.tri_q)
+        return int(self.mis), adl._handle(self.counts), adl._handle(self.cdf), adl._handle(self.tri_q)
 
     def render(self, frames: int, frame_begin=None, sync=None) -> None:
         """``DirectRenderer.render``; after an adaptive pass only a start at frame 0 is accepted: the pixels no longer share a frame
@@ -154,26 +153,24 @@ class IndirectRenderer(DirectRenderer):
             self._adaptive = False
         super().render(frames, frame_begin, sync)
 
-    def set_camera(self, camera) -> None:
-        super().set_camera(camera)
+    def _restart(self) -> None:
+        super()._restart()
         self._adaptive = False
 
     def set_environment(self, environment, env_samples: int = 0) -> None:
         if environment is not None and not self.mis:
             raise ValueError("an environment needs mis=True: the sky is balanced against the BRDF ray")
         super().set_environment(environment, env_samples)
-        self._adaptive = False
 
     def sample_counts(self) -> np.ndarray:
         """uint32 per local pixel: the samples the pixel has received since the last start at frame 0, finite or rejected (n +
         rejected of its moments); synchronises."""
         self._need_moments()
-        rec = np.zeros(self.local_pixels * ctypes.sizeof(shim.PixelMoments) // 4, np.uint32)
+        rec = np.zeros(self.local_pixels, shim.MOMENTS_DTYPE)
         if self.local_pixels and self._moments_valid:
-            self.mom.read(rec, rec.nbytes)
+            self.mom.read(rec.view(np.uint8), rec.nbytes)
             self.dev.waitForCompletion()
-        rec = rec.reshape(self.local_pixels, -1)
-        return rec[:, 12] + rec[:, 13]   # (uint32: wraps as the record's fields do)
+        return rec["n"] + rec["rejected"]   # (uint32: wraps as the record's fields do)
 
     def render_adaptive(self, tolerance: float, *, max_samples: int, min_samples: int = 16, frames_per_pass=None,
                         floor: float = 1e-2) -> AdaptiveResult:
@@ -210,7 +207,7 @@ class IndirectRenderer(DirectRenderer):
         if self.pixel_list is None:
             self.pixel_list = adl.Buffer(self.dev, self._lib.pt_adaptive_list_bytes(self.local_pixels), np.uint8)
         rule = shim.AdaptiveRule(tolerance * tolerance, floor * floor, min_samples, max_samples)
-        rr = self._rr if self._rr is not None else shim.Roulette(65535, 1.0)   # (no roulette: a first bounce no path reaches)
+        rr = self._rr or shim.NO_ROULETTE
         header = np.zeros(1, np.uint32)
         while True:
             shim.check(self._lib.pt_adaptive_select(self.dev._h, self.mom._h, self.local_pixels, ctypes.byref(rule), self.pixel_list._h, None))

@@ -51,23 +51,42 @@ def _is_tensor(x) -> bool:
     return type(x).__module__.startswith("torch")
 
 
-class RayCaster:
-    """Closest-hit and occlusion queries against ``triangles`` on ``dev``.
+# ---- argument checks (before anything is enqueued) --------------------------------------------------------------------
+def check_numpy_rays(rays) -> np.ndarray:
+    a = np.asarray(rays)
+    if a.dtype == RAY_DTYPE and a.ndim == 1:
+        return np.ascontiguousarray(a)
+    if a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == RAY_WORDS:
+        return np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
+    raise TypeError("rays must be a RAY_DTYPE array or float32 [N, 8]; got %s %s" % (a.dtype, a.shape))
 
-    ``triangles``: a ``scene.TRIANGLE_DTYPE`` array (uploaded to a buffer of this caster's), or an ``adl.Buffer`` that already
-    holds them -- the renderer's own (``Renderer.ray_caster``), so that queries and renders share one prepared scene and one LBVH
-    (``num_triangles`` then says how many records count).  The search follows the device's options exactly as renders do."""
 
-    def __init__(self, dev: adl.Device, triangles, *, num_triangles: Optional[int] = None):
+def check_tensor_rays(t, dev: adl.Device) -> None:
+    import torch
+
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != RAY_WORDS:
+        raise TypeError("ray tensors must be float32 [N, 8]; got %s %s" % (t.dtype, tuple(t.shape)))
+    if not t.is_cuda:
+        raise ValueError("ray tensors must live on the device")
+    if t.device.index != dev.m_deviceIdx:
+        raise ValueError("ray tensor on %s, the caster's device is cuda:%d" % (t.device, dev.m_deviceIdx))
+    if not t.is_contiguous():
+        raise ValueError("ray tensors must be contiguous")
+    if t.data_ptr() % 16:
+        raise ValueError("ray tensors must be 16-byte aligned")
+
+
+class DeviceIO:
+    """How a caster's arguments and results reach the device: staging buffers for numpy arrays, grown on demand, and for torch
+    tensors wraps of their address ranges, kept (see ``_WRAP_KEEP``), with the one event that orders a call against torch's stream."""
+
+    def __init__(self, dev: adl.Device):
         self.dev = dev
-        self._lib = shim.load()
-        self.tbuf, self.num_triangles, self._own_tbuf = scene.triangle_buffer(dev, triangles, num_triangles)
         self._host = {}    # role -> (adl.Buffer, capacity in bytes): device staging of the numpy path, grown on demand
         self._wrapped = {}  # (address, bytes) -> adl.Buffer: address ranges of caller tensors, wrapped with pt_buffer_wrap (oldest first)
         self._sync = None
 
-    # ---- buffers ------------------------------------------------------------------------------------------------------
-    def _staging(self, role: str, nbytes: int) -> adl.Buffer:
+    def staging(self, role: str, nbytes: int) -> adl.Buffer:
         buf, cap = self._host.get(role, (None, 0))
         if buf is None or cap < nbytes:
             if buf is not None:
@@ -77,7 +96,7 @@ class RayCaster:
             self._host[role] = (buf, cap)
         return buf
 
-    def _wrap(self, t) -> adl.Buffer:
+    def wrap(self, t) -> adl.Buffer:
         """The wrap of t's address range (made once per range; never freed here: see _WRAP_KEEP)."""
         key = (int(t.data_ptr()), int(t.numel() * t.element_size()))
         b = self._wrapped.pop(key, None)
@@ -87,39 +106,67 @@ class RayCaster:
         self._wrapped[key] = b   # (most recently used last)
         return b
 
-    def _trim_wraps(self) -> None:
+    def trim_wraps(self) -> None:
         """Free the least recently used wraps beyond _WRAP_KEEP -- called only right after a wait for the device."""
         while len(self._wrapped) > _WRAP_KEEP:
             self._wrapped.pop(next(iter(self._wrapped))).release()
 
-    def _event(self) -> adl.SyncObject:
-        if self._sync is None:
-            self._sync = adl.SyncObject(self.dev)
-        return self._sync
-
-    # ---- argument checks (before anything is enqueued) ----------------------------------------------------------------
-    @staticmethod
-    def _check_numpy_rays(rays) -> np.ndarray:
-        a = np.asarray(rays)
-        if a.dtype == RAY_DTYPE and a.ndim == 1:
-            return np.ascontiguousarray(a)
-        if a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == RAY_WORDS:
-            return np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
-        raise TypeError("rays must be a RAY_DTYPE array or float32 [N, 8]; got %s %s" % (a.dtype, a.shape))
-
-    def _check_tensor_rays(self, t):
+    def on_tensors(self, enqueue, *tensors) -> None:
+        """``enqueue(*wraps, event handle)`` on the tensors' memory, behind what torch's current stream holds -- the arguments are
+        written and the results' memory is free there -- and torch's later work behind the event: device-side waits only.  The wraps
+        do not hold the tensors: their memory follows torch's stream rules."""
         import torch
 
-        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != RAY_WORDS:
-            raise TypeError("ray tensors must be float32 [N, 8]; got %s %s" % (t.dtype, tuple(t.shape)))
-        if not t.is_cuda:
-            raise ValueError("ray tensors must live on the device")
-        if t.device.index != self.dev.m_deviceIdx:
-            raise ValueError("ray tensor on %s, the caster's device is cuda:%d" % (t.device, self.dev.m_deviceIdx))
-        if not t.is_contiguous():
-            raise ValueError("ray tensors must be contiguous")
-        if t.data_ptr() % 16:
-            raise ValueError("ray tensors must be 16-byte aligned")
+        stream = torch.cuda.current_stream(tensors[0].device)
+        wraps = [self.wrap(t) for t in tensors]
+        if self._sync is None:
+            self._sync = adl.SyncObject(self.dev)
+        self.dev.waitStream(stream.cuda_stream)
+        enqueue(*wraps, self._sync._h)
+        self._sync.waitOnStream(stream.cuda_stream)
+
+    def release(self) -> None:
+        for b in [b for b, _ in self._host.values()] + list(self._wrapped.values()):
+            b.release()
+        self._host.clear()
+        self._wrapped.clear()
+        if self._sync is not None:
+            self._sync.release()
+            self._sync = None
+
+
+def into_tensor(dev: adl.Device, out, sync: Optional[adl.SyncObject], enqueue) -> adl.SyncObject:
+    """One result into a tensor of the caller's: ``enqueue(handle of out's memory, event handle)`` behind torch's current stream,
+    and torch's later work behind the event (``sync``, made here when None, and returned).  Unlike a caster's, the wrap is not
+    kept: it is released here, which waits for the device -- the tensor is complete when this returns."""
+    import torch
+
+    stream = torch.cuda.current_stream(out.device)
+    wrap = adl.Buffer()
+    wrap.setRawPtr(dev, int(out.data_ptr()), int(out.numel() * out.element_size()))
+    if sync is None:
+        sync = adl.SyncObject(dev)
+    try:
+        dev.waitStream(stream.cuda_stream)
+        enqueue(wrap._h, sync._h)
+        sync.waitOnStream(stream.cuda_stream)
+    finally:
+        wrap.release()
+    return sync
+
+
+class RayCaster(scene.SceneHolder):
+    """Closest-hit and occlusion queries against ``triangles`` on ``dev``.
+
+    ``triangles``: a ``scene.TRIANGLE_DTYPE`` array (uploaded to a buffer of this caster's), or an ``adl.Buffer`` that already
+    holds them -- the renderer's own (``Renderer.ray_caster``), so that queries and renders share one prepared scene and one LBVH
+    (``num_triangles`` then says how many records count).  The search follows the device's options exactly as renders do."""
+
+    def __init__(self, dev: adl.Device, triangles, *, num_triangles: Optional[int] = None):
+        self.dev = dev
+        self._lib = shim.load()
+        self.scene = scene.SceneBuffers(dev, triangles, num_triangles, shape="triangles")
+        self._io = DeviceIO(dev)
 
     # ---- queries ------------------------------------------------------------------------------------------------------
     def closest(self, rays):
@@ -144,36 +191,31 @@ class RayCaster:
     def _query(self, rays, mode: int):
         if _is_tensor(rays):
             return self._query_tensor(rays, mode)
-        r = self._check_numpy_rays(rays)
+        r = check_numpy_rays(rays)
         n = len(r)
         out = np.zeros(n, HIT_DTYPE) if mode == shim.PT_QUERY_CLOSEST else np.zeros(n, np.int32)
-        rb = self._staging("rays", r.nbytes)
-        ob = self._staging("out", out.nbytes)
+        rb = self._io.staging("rays", r.nbytes)
+        ob = self._io.staging("out", out.nbytes)
         if n:
             rb.write(r.view(np.uint8), r.nbytes)
         self._launch(rb, ob, n, mode, None)
         if n:
             ob.read(out.view(np.uint8), out.nbytes)
         self.dev.waitForCompletion()
-        self._trim_wraps()
+        self._io.trim_wraps()
         return out
 
     def _query_tensor(self, rays, mode: int):
         import torch
 
-        self._check_tensor_rays(rays)
+        check_tensor_rays(rays, self.dev)
         n = rays.shape[0]
         shape = (n, HIT_WORDS) if mode == shim.PT_QUERY_CLOSEST else (n,)
         out = torch.empty(shape, dtype=torch.float32 if mode == shim.PT_QUERY_CLOSEST else torch.int32, device=rays.device)
         if n == 0:
             return out
-        stream = torch.cuda.current_stream(rays.device)
-        rays.record_stream(stream)                # (the wraps do not hold the tensors: their memory follows torch's stream rules)
-        rb, ob = self._wrap(rays), self._wrap(out)
-        ev = self._event()
-        self.dev.waitStream(stream.cuda_stream)   # the rays are written and the results' memory is free on torch's stream
-        self._launch(rb, ob, n, mode, ev._h)
-        ev.waitOnStream(stream.cuda_stream)       # torch's later work sees the results
+        rays.record_stream(torch.cuda.current_stream(rays.device))
+        self._io.on_tensors(lambda rb, ob, ev: self._launch(rb, ob, n, mode, ev), rays, out)
         return out
 
     def camera_rays(self, width: int, height: int, frame: int, camera: Optional[Camera] = None, *, as_tensor: bool = False):
@@ -190,29 +232,16 @@ class RayCaster:
             import torch
 
             out = torch.empty((n, RAY_WORDS), dtype=torch.float32, device="cuda:%d" % self.dev.m_deviceIdx)
-            stream = torch.cuda.current_stream(out.device)
-            ob = self._wrap(out)
-            ev = self._event()
-            self.dev.waitStream(stream.cuda_stream)
-            shim.check(self._lib.pt_camera_rays(self.dev._h, cam, width, height, frame, ob._h, ev._h))
-            ev.waitOnStream(stream.cuda_stream)
+            self._io.on_tensors(lambda ob, ev: shim.check(self._lib.pt_camera_rays(self.dev._h, cam, width, height, frame, ob._h, ev)), out)
             return out
         out = np.zeros(n, RAY_DTYPE)
-        ob = self._staging("camera", out.nbytes)
+        ob = self._io.staging("camera", out.nbytes)
         shim.check(self._lib.pt_camera_rays(self.dev._h, cam, width, height, frame, ob._h, None))
         ob.read(out.view(np.uint8), out.nbytes)
         self.dev.waitForCompletion()
-        self._trim_wraps()
+        self._io.trim_wraps()
         return out
 
     def release(self) -> None:
-        for b in [b for b, _ in self._host.values()] + list(self._wrapped.values()):
-            b.release()
-        self._host.clear()
-        self._wrapped.clear()
-        if self._sync is not None:
-            self._sync.release()
-            self._sync = None
-        if self._own_tbuf and self.tbuf is not None:
-            self.tbuf.release()
-        self.tbuf = None
+        self._io.release()
+        self.scene.release()

@@ -26,14 +26,14 @@ from typing import Optional
 
 import numpy as np
 
-from . import adl, shim
-from .direct import SceneBuffers, _handle, light_counts, light_table
+from . import adl, scene, shim
+from .direct import light_counts, light_table
+from .image import check_size
 from .indirect import Roulette
-from .query import RAY_DTYPE, RayCaster, _is_tensor, make_rays  # noqa: F401  (RAY_DTYPE: the record of the rays, for callers)
+from .query import RAY_DTYPE, DeviceIO, _is_tensor, check_numpy_rays, check_tensor_rays, make_rays  # noqa: F401  (RAY_DTYPE: the record of the rays, for callers)
 from .render import BOUNCES
 
 _WORKSPACE_BYTES = 64 << 20   # the default sample workspace: the samples of every ray that fit are walked by one launch
-_MOMENT_BYTES = ctypes.sizeof(shim.PixelMoments)
 _ID_MAX = 0x7fffffff
 
 RadianceResult = collections.namedtuple("RadianceResult", "mean variance n rejected")
@@ -54,10 +54,8 @@ def panorama_rays(eye, width: int, height: int) -> np.ndarray:
     """The rays of a latitude-longitude panorama seen from ``eye``: a ``RAY_DTYPE`` array of ``width * height`` rays, ray
     ``y * width + x`` through the centre of pixel (x, y).  Longitude runs over the columns from -pi to pi about the y axis (the
     image's centre column looks along -z, as the reference's camera does), latitude over the rows from straight up to straight down."""
-    width, height = int(width), int(height)
     e = np.asarray(eye, np.float64).reshape(-1)
-    if width < 1 or height < 1 or width * height > _ID_MAX:
-        raise ValueError("invalid panorama size %dx%d" % (width, height))
+    width, height = check_size(width, height, "panorama")
     if e.shape != (3,) or not np.all(np.isfinite(e)):
         raise ValueError("eye must be three finite numbers")
     phi = (np.arange(width, dtype=np.float64) + 0.5) / width * (2.0 * np.pi) - np.pi
@@ -67,7 +65,7 @@ def panorama_rays(eye, width: int, height: int) -> np.ndarray:
     return make_rays(np.broadcast_to(e, (width * height, 3)), d.reshape(-1, 3))
 
 
-class RadianceCaster:
+class RadianceCaster(scene.SceneHolder):
     """Radiance along rays through ``triangles`` with ``materials`` on ``dev``.
 
     ``triangles`` / ``materials`` / ``lights`` / ``num_triangles`` / ``num_materials``: as for ``DirectRenderer`` (arrays, or ``adl.Buffer``s
@@ -90,46 +88,34 @@ class RadianceCaster:
             raise ValueError("max_bounces must lie in 1..65535")
         if isinstance(workspace_bytes, bool) or int(workspace_bytes) < 12:
             raise ValueError("workspace_bytes must hold at least one sample (12 bytes)")
-        rr = self.roulette if self.roulette is not None else Roulette(65535, 1.0)   # (no roulette: a first bounce no path reaches)
-        self._rr = shim.Roulette(rr.first_bounce, rr.max_survival)
+        self._rr = shim.NO_ROULETTE if self.roulette is None else shim.Roulette(*self.roulette)
         self.dev = dev
         self._lib = shim.load()
         self.counts = self.cdf = self.tri_q = self.samples = None
-        self._own = []          # the buffers release() frees
         self._acc = None        # ("numpy" | "torch", N, the moments tensor or None): what accumulate=True continues
-        if _share is not None:  # a renderer's scene, list, counts and table: none of them is this caster's to free
-            s = _share
-            self.counts, self.cdf, self.tri_q = s.counts, s.cdf, s.tri_q
+        self._shared = _share is not None   # a renderer's scene, list, counts and table: none of them is this caster's to free
+        if self._shared:
+            self.scene = _share.scene.borrowed()
+            self.counts, self.cdf, self.tri_q = _share.counts, _share.cdf, _share.tri_q
         else:
-            s = SceneBuffers(dev, triangles, materials, lights, num_triangles, num_materials)
-            self._own += [s.lbuf] + ([s.tbuf] if s.own_tbuf else []) + ([s.mbuf] if s.own_mbuf else [])
-        self.lights, self.num_triangles, self.num_materials = s.lights, s.num_triangles, s.num_materials
-        self.tbuf, self.mbuf, self.lbuf = s.tbuf, s.mbuf, s.lbuf
-        self._io = RayCaster(dev, self.tbuf, num_triangles=self.num_triangles)   # the staging and wrap helpers of the ray queries
+            self.scene = scene.SceneBuffers(dev, triangles, num_triangles, materials, num_materials, lights)
+        self._io = DeviceIO(dev)
         try:
-            if _share is None and self.mis:
+            if not self._shared and self.mis:
                 self.counts = light_counts(self._lib, dev, self._lights_h(), len(self.lights), self.num_triangles)
-                self._own.append(self.counts)
-            if _share is None and light_choice == "power":
+            if not self._shared and light_choice == "power":
                 self.cdf, self.tri_q = light_table(self._lib, dev, self.tbuf, self.num_triangles, self.mbuf, self.num_materials,
                                                    self._lights_h(), len(self.lights))
-                self._own += [self.cdf, self.tri_q]
             self.samples = adl.Buffer(dev, int(workspace_bytes), np.uint8)
-            self._own.append(self.samples)
         except Exception:
             self.release()
             raise
 
-    def _lights_h(self):
-        return self.lbuf._h if len(self.lights) else None
-
     def _workspace(self, n: int) -> adl.Buffer:
         """the sample workspace, grown to hold one sample of n rays"""
         if self.samples.getSize() < 12 * n:
-            self._own.remove(self.samples)
             self.samples.release()
             self.samples = adl.Buffer(self.dev, 12 * n, np.uint8)
-            self._own.append(self.samples)
         return self.samples
 
     def _enqueue(self, rb, mb, nb, n: int, samples: int, sample_begin: int, first_ray: int, reset: bool, ev) -> None:
@@ -140,7 +126,7 @@ class RadianceCaster:
         p.num_triangles, p.num_materials, p.num_lights = self.num_triangles, self.num_materials, len(self.lights)
         p.light_samples, p.max_bounces, p.reset = self.light_samples, self.max_bounces, int(reset)
         shim.check(self._lib.pt_radiance_rays(self.dev._h, self.tbuf._h, self.mbuf._h, self._lights_h(), int(self.mis),
-                                              _handle(self.counts) if self.mis else None, _handle(self.cdf), _handle(self.tri_q), rb._h,
+                                              adl._handle(self.counts) if self.mis else None, adl._handle(self.cdf), adl._handle(self.tri_q), rb._h,
                                               self._workspace(n)._h, mb._h, ctypes.byref(p), ctypes.byref(self._rr), None))
         shim.check(self._lib.pt_moments_resolve(self.dev._h, mb._h, n, nb._h, None, ev))
 
@@ -154,10 +140,10 @@ class RadianceCaster:
             raise TypeError("accumulate must be a bool")
         tensor = _is_tensor(rays)
         if tensor:
-            self._io._check_tensor_rays(rays)
+            check_tensor_rays(rays, self.dev)
             n = int(rays.shape[0])
         else:
-            r = self._io._check_numpy_rays(rays)
+            r = check_numpy_rays(rays)
             n = len(r)
         check_range(n, samples, sample_begin, first_ray)
         samples, sample_begin, first_ray = int(samples), int(sample_begin), int(first_ray)
@@ -167,56 +153,50 @@ class RadianceCaster:
             raise ValueError("accumulate=True continues the last call: %d %s rays, not %d %s rays" % (self._acc[1], self._acc[0], n, form))
         if tensor:
             return self._radiance_tensor(rays, n, samples, sample_begin, first_ray, go_on)
-        mom = np.zeros((n, _MOMENT_BYTES // 4), np.uint32)
+        mom = np.zeros(n, shim.MOMENTS_DTYPE)
         noise = np.zeros((n, 4), np.float32)
         if n:
-            rb = self._io._staging("rays", r.nbytes)
-            mb = self._io._staging("moments", mom.nbytes)
-            nb = self._io._staging("noise", noise.nbytes)
+            rb = self._io.staging("rays", r.nbytes)
+            mb = self._io.staging("moments", mom.nbytes)
+            nb = self._io.staging("noise", noise.nbytes)
             rb.write(r.view(np.uint8), r.nbytes)
             if not go_on:   # (a call of no samples enqueues nothing: the record starts from zeros here)
                 mb.write(mom.view(np.uint8), mom.nbytes)
             self._enqueue(rb, mb, nb, n, samples, sample_begin, first_ray, not go_on, None)
-            mb.read(mom.view(np.uint8).reshape(-1), mom.nbytes)
+            mb.read(mom.view(np.uint8), mom.nbytes)
             nb.read(noise.view(np.uint8).reshape(-1), noise.nbytes)
         self.dev.waitForCompletion()
-        self._io._trim_wraps()
+        self._io.trim_wraps()
         self._acc = (form, n, None)
-        sums = np.ascontiguousarray(mom[:, :6]).view(np.float64)   # sum[3]; sum2 is not needed here
-        cnt = mom[:, 12].copy()
+        cnt = mom["n"].copy()
         with np.errstate(divide="ignore", invalid="ignore"):
-            mean = np.where(cnt[:, None] > 0, sums / cnt[:, None].astype(np.float64), 0.0).astype(np.float32)
-        return RadianceResult(mean, np.ascontiguousarray(noise[:, :3]), cnt, mom[:, 13].copy())
+            mean = np.where(cnt[:, None] > 0, mom["sum"] / cnt[:, None].astype(np.float64), 0.0).astype(np.float32)
+        return RadianceResult(mean, np.ascontiguousarray(noise[:, :3]), cnt, mom["rejected"].copy())
 
     def _radiance_tensor(self, rays, n: int, samples: int, sample_begin: int, first_ray: int, go_on: bool) -> RadianceResult:
         import torch
 
         dev = rays.device
-        mom = self._acc[2] if go_on else torch.zeros((n, _MOMENT_BYTES // 8), dtype=torch.float64, device=dev)
+        mom = self._acc[2] if go_on else torch.zeros((n, shim.MOMENTS_DTYPE.itemsize // 8), dtype=torch.float64, device=dev)
         noise = torch.zeros((n, 4), dtype=torch.float32, device=dev)
         if n:
-            stream = torch.cuda.current_stream(dev)
-            rays.record_stream(stream)   # (the wraps do not hold the tensors: their memory follows torch's stream rules)
-            rb, mb, nb = self._io._wrap(rays), self._io._wrap(mom), self._io._wrap(noise)
-            ev = self._io._event()
-            self.dev.waitStream(stream.cuda_stream)   # the rays are written and the results' memory is zeroed on torch's stream
-            self._enqueue(rb, mb, nb, n, samples, sample_begin, first_ray, not go_on, ev._h)
-            ev.waitOnStream(stream.cuda_stream)       # torch's later work sees the results
+            rays.record_stream(torch.cuda.current_stream(dev))
+            self._io.on_tensors(lambda rb, mb, nb, ev: self._enqueue(rb, mb, nb, n, samples, sample_begin, first_ray, not go_on, ev),
+                                rays, mom, noise)
         self._acc = ("torch", n, mom)
-        words = mom.view(torch.int32).view(n, _MOMENT_BYTES // 4)
-        cnt, rej = words[:, 12].contiguous(), words[:, 13].contiguous()
+        # the record's fields as columns of its 32-bit words (torch has no structured dtype): n and rejected by their offsets
+        words = mom.view(torch.int32).view(n, shim.MOMENTS_DTYPE.itemsize // 4)
+        cnt, rej = (words[:, shim.MOMENTS_DTYPE.fields[f][1] // 4].contiguous() for f in ("n", "rejected"))
         cntd = (cnt.to(torch.int64) & 0xffffffff).to(torch.float64)[:, None]
-        mean = torch.where(cntd > 0, mom[:, :3] / cntd, torch.zeros_like(mom[:, :3])).to(torch.float32)
+        sums = mom[:, shim.MOMENTS_DTYPE.fields["sum"][1] // 8:][:, :3]
+        mean = torch.where(cntd > 0, sums / cntd, torch.zeros_like(sums)).to(torch.float32)
         return RadianceResult(mean, noise[:, :3].contiguous(), cnt.view(torch.uint32), rej.view(torch.uint32))
 
     def release(self) -> None:
-        for b in self._own:
+        self.scene.release()
+        for b in (self.samples,) if self._shared else (self.counts, self.cdf, self.tri_q, self.samples):
             if b is not None:
                 b.release()
-        self._own = []
         self._acc = None
-        if getattr(self, "_io", None) is not None:
-            self._io.tbuf = None   # (not the helper's to free)
-            self._io.release()
-            self._io = None
-        self.tbuf = self.mbuf = self.lbuf = self.counts = self.cdf = self.tri_q = self.samples = None
+        self._io.release()
+        self.counts = self.cdf = self.tri_q = self.samples = None

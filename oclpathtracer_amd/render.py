@@ -14,7 +14,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import adl, scene, shim
+from . import adl, image, scene, shim
 from .camera import Camera
 
 BOUNCES = 16        # GenerateColors.cl:5
@@ -72,7 +72,7 @@ def refuse_lens(camera: Optional[Camera]) -> None:
                          "renders the same image and takes the lens, or Camera.with_lens(0.0) for the pinhole")
 
 
-class Renderer:
+class Renderer(image.ImageRenderer):
     """One device's share of an image, rendered with the fused multi-frame entry point.
 
     ``n_ranks``/``rank``/``stripe_rows`` select the rows this device owns (rows are
@@ -87,14 +87,8 @@ class Renderer:
                  want_stats: bool = False, camera: Optional[Camera] = None):
         self.dev = dev
         self._set_camera(camera)
-        self.width, self.height = int(width), int(height)
-        self.n_ranks, self.rank, self.stripe_rows = int(n_ranks), int(rank), int(stripe_rows)
+        image.ImageShare.__init__(self, width, height, stripe_rows, n_ranks, rank, sized=False)   # (pt_render_frames refuses a bad size)
         self.num_triangles, self.num_materials = len(triangles), len(materials)
-        lib = shim.load()
-        self.local_rows = lib.pt_local_rows(self.height, self.stripe_rows, self.n_ranks, self.rank)
-        if self.local_rows < 0:
-            raise ValueError("invalid stripe geometry")
-        self.local_pixels = self.local_rows * self.width
         self.tbuf, self.mbuf = upload_scene(dev, triangles, materials)
         self.fb = adl.Buffer(dtype=adl.float4)
         if fb_device_ptr is None:
@@ -113,33 +107,21 @@ class Renderer:
         ``fb``: another framebuffer of the same size to render into (a pipeline's second buffer)."""
         if frame_begin is None:
             frame_begin = self.frames_done
-        p = shim.RenderParams()
-        p.width, p.height = self.width, self.height
-        p.frame_begin, p.frame_count = int(frame_begin), int(frames)
+        p = self.fill(shim.RenderParams(), int(frames), int(frame_begin))
         p.max_bounces = int(max_bounces)
         p.num_triangles, p.num_materials = self.num_triangles, self.num_materials
-        p.stripe_rows, p.n_ranks, p.rank = self.stripe_rows, self.n_ranks, self.rank
         if self._cam is None:
             shim.check(shim.load().pt_render_frames(self.dev._h, self.tbuf._h, self.mbuf._h, (fb or self.fb)._h, ctypes.byref(p),
-                                                    self.stats._h if self.stats else None,
-                                                    sync._h if sync is not None else None))
+                                                    adl._handle(self.stats), adl._handle(sync)))
         else:
             shim.check(shim.load().pt_render_frames_camera(self.dev._h, self.tbuf._h, self.mbuf._h, (fb or self.fb)._h, ctypes.byref(p),
-                                                           ctypes.byref(self._cam), self.stats._h if self.stats else None,
-                                                           sync._h if sync is not None else None))
+                                                           self._cam_ref(), adl._handle(self.stats), adl._handle(sync)))
         self.frames_done = frame_begin + frames
 
     def _set_camera(self, camera: Optional[Camera]) -> None:
+        """(a moved camera invalidates the running mean, GenerateColors.cl:314-321: ``set_camera`` restarts the accumulation)"""
         refuse_lens(camera)
-        self._cam = Camera.struct_of(camera)
-        self.camera = camera
-
-    def set_camera(self, camera: Optional[Camera]) -> None:
-        """Render from ``camera`` from now on (None: the reference's).  A moved camera invalidates the running mean
-        (GenerateColors.cl:314-321): accumulation restarts, the next render is frame 0.  Renders already enqueued keep the
-        camera they were enqueued with."""
-        self._set_camera(camera)
-        self.frames_done = 0
+        super()._set_camera(camera)
 
     def read(self) -> np.ndarray:
         """Local framebuffer as (local_rows*W, 4) float32 (synchronises)."""
@@ -175,12 +157,8 @@ class Renderer:
         LBVH.  Release it before the renderer."""
         from .ao import AORenderer
 
-        kw.setdefault("camera", self.camera)
-        kw.setdefault("stripe_rows", self.stripe_rows)
-        kw.setdefault("n_ranks", self.n_ranks)
-        kw.setdefault("rank", self.rank)
-        return AORenderer(self.dev, self.tbuf, kw.pop("width", self.width), kw.pop("height", self.height),
-                          num_triangles=kw.pop("num_triangles", self.num_triangles), **kw)
+        width, height = image.like(self, kw)
+        return AORenderer(self.dev, self.tbuf, width, height, num_triangles=kw.pop("num_triangles", self.num_triangles), **kw)
 
     def direct_renderer(self, **kw):
         """A :class:`direct.DirectRenderer` of this renderer's image over its triangle and material buffers (keyword arguments:
@@ -205,18 +183,10 @@ class Renderer:
         the device's prepared scene and LBVH.  Release it before the renderer."""
         from .features import FeatureRenderer
 
-        kw.setdefault("camera", self.camera)
-        kw.setdefault("stripe_rows", self.stripe_rows)
-        kw.setdefault("n_ranks", self.n_ranks)
-        kw.setdefault("rank", self.rank)
-        return FeatureRenderer(self.dev, self.tbuf, self.mbuf, kw.pop("width", self.width), kw.pop("height", self.height),
-                               num_triangles=self.num_triangles, num_materials=self.num_materials, **kw)
+        return FeatureRenderer.on(self, **kw)
 
     def _lit_renderer(self, cls, kw):
-        kw.setdefault("camera", self.camera)
-        kw.setdefault("stripe_rows", self.stripe_rows)
-        kw.setdefault("n_ranks", self.n_ranks)
-        kw.setdefault("rank", self.rank)
+        width, height = image.like(self, kw)
         if kw.get("lights") is None:
             tris = np.zeros(self.num_triangles, scene.TRIANGLE_DTYPE)
             mats = np.zeros(self.num_materials, scene.MATERIAL_DTYPE)
@@ -226,13 +196,7 @@ class Renderer:
                 self.mbuf.read(mats, self.num_materials)
             self.dev.waitForCompletion()
             kw["lights"] = scene.emitters(tris, mats)
-        return cls(self.dev, self.tbuf, self.mbuf, kw.pop("width", self.width), kw.pop("height", self.height),
-                   num_triangles=self.num_triangles, num_materials=self.num_materials, **kw)
-
-    def global_rows(self) -> np.ndarray:
-        """Global row index of every local row (ascending)."""
-        rows = np.arange(self.height)
-        return rows[(rows // self.stripe_rows) % self.n_ranks == self.rank]
+        return cls(self.dev, self.tbuf, self.mbuf, width, height, num_triangles=self.num_triangles, num_materials=self.num_materials, **kw)
 
     def release(self) -> None:
         for b in (self.tbuf, self.mbuf, self.fb, self.stats):

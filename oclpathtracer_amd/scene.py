@@ -8,6 +8,7 @@ Mirrors the host half of the reference harness:
                          ``test/RaytraceTest.cpp:50-76`` / ``test/ClKernels/GenerateColors.cl:12-28``.
 * ``make_soup``       -- the synthetic 1M-triangle scene of BASELINE.json configs[4]
                          (definition: SURVEY.md S8d, "C5").
+* ``SceneBuffers``    -- the scene on a device: who made which buffer, and so who frees it.
 
 Fields the reference leaves uninitialised (``Material.roughness`` of diffuse surfaces, all
 padding) are zero here.
@@ -18,6 +19,8 @@ import os
 import struct
 
 import numpy as np
+
+from . import adl
 
 DIFFUSE = 1
 SPECULAR = 2
@@ -177,8 +180,6 @@ def load_model(path: str | None = None, materials=None):
 def triangle_buffer(dev, triangles, num_triangles=None):
     """``(buffer, count, owned)`` of what a caster or renderer was given as its triangles: a ``TRIANGLE_DTYPE`` array, uploaded to
     a buffer of the caller's own, or an ``adl.Buffer`` that already holds them (``num_triangles`` then says how many count)."""
-    from . import adl
-
     if isinstance(triangles, adl.Buffer):
         if num_triangles is None:
             raise ValueError("num_triangles is required with an adl.Buffer of triangles")
@@ -192,6 +193,102 @@ def triangle_buffer(dev, triangles, num_triangles=None):
     if len(tris):
         buf.write(tris, len(tris))
     return buf, len(tris), True
+
+
+def check_lights(lights, num_triangles: int) -> np.ndarray:
+    a = np.asarray(lights)
+    if a.dtype.kind not in "iu":
+        raise TypeError("lights must be an array of integers (triangle indices)")
+    if a.ndim != 1:
+        raise ValueError("lights must be one-dimensional")
+    if len(a) >= 1 << 24:
+        raise ValueError("at most 2^24 - 1 lights")
+    if len(a) and (int(a.min()) < 0 or int(a.max()) >= num_triangles):
+        raise ValueError("a light index lies outside [0, %d)" % num_triangles)
+    return np.ascontiguousarray(a, np.int32)
+
+
+class SceneBuffers:
+    """The scene of a caster or renderer on ``dev``, in one of three shapes: ``"triangles"`` (the ray queries, ambient occlusion),
+    ``"materials"`` (the feature buffers) and ``"lit"`` (both, the light list and its buffer: the lit renderers, the radiance queries).
+    ``triangles`` / ``materials``: ``TRIANGLE_DTYPE`` / ``MATERIAL_DTYPE`` arrays, uploaded to buffers made here, or ``adl.Buffer``s
+    that already hold them (``num_triangles`` / ``num_materials`` then say how many records count).  ``lights``: triangle indices
+    (None: ``emitters``, which needs both arrays).  Everything about the scene that can be refused is refused before the first device
+    call, each shape's refusals in the order they have always come.  ``release()`` frees the buffers made here and no others."""
+
+    def __init__(self, dev, triangles, num_triangles=None, materials=None, num_materials=None, lights=None, *, shape: str = "lit"):
+        lit, with_materials = shape == "lit", shape != "triangles"
+        self.tbuf = self.mbuf = self.lbuf = self.lights = None
+        self.num_triangles = self.num_materials = 0
+        self._made = []
+        t_host = isinstance(triangles, np.ndarray)
+        m_host = isinstance(materials, np.ndarray)
+        if lit and (not (t_host or isinstance(triangles, adl.Buffer)) or (t_host and triangles.dtype != TRIANGLE_DTYPE)):
+            raise TypeError("triangles must be a scene.TRIANGLE_DTYPE array or an adl.Buffer")
+        if with_materials and (not (m_host or isinstance(materials, adl.Buffer)) or (m_host and materials.dtype != MATERIAL_DTYPE)):
+            raise TypeError("materials must be a scene.MATERIAL_DTYPE array or an adl.Buffer")
+        if lit and not t_host and num_triangles is None:
+            raise ValueError("num_triangles is required with an adl.Buffer of triangles")
+        if with_materials:
+            if not m_host and num_materials is None:
+                raise ValueError("num_materials is required with an adl.Buffer of materials")
+            self.num_materials = len(materials) if m_host else int(num_materials)
+        if lit:
+            ntri = len(triangles) if t_host else int(num_triangles)
+            if ntri < 0 or self.num_materials < 1:
+                raise ValueError("a scene needs num_triangles >= 0 and at least one material")
+            if lights is None:
+                if not (t_host and m_host):
+                    raise ValueError("lights must be given with adl.Buffers of triangles or materials (scene.emitters derives them)")
+                lights = emitters(triangles, materials)
+            self.lights = check_lights(lights, ntri)
+        elif with_materials and self.num_materials < 1:
+            raise ValueError("a scene needs at least one material")
+        try:
+            self.tbuf, self.num_triangles, made = triangle_buffer(dev, triangles, num_triangles)   # (the other shapes' triangles are refused here)
+            if made:
+                self._made.append(self.tbuf)
+            if with_materials:
+                self.mbuf = materials
+                if m_host:
+                    self.mbuf = adl.Buffer(dev, self.num_materials, MATERIAL_DTYPE)
+                    self._made.append(self.mbuf)
+                    self.mbuf.write(np.ascontiguousarray(materials), self.num_materials)
+            if lit:
+                self.lbuf = adl.Buffer(dev, max(len(self.lights), 1), np.int32)
+                self._made.insert(0, self.lbuf)   # (the list goes first, the scene it indexes after it)
+                if len(self.lights):
+                    self.lbuf.write(self.lights, len(self.lights))
+        except Exception:
+            self.release()
+            raise
+
+    def borrowed(self) -> "SceneBuffers":
+        """this scene for a second holder (a caster on a renderer's scene), whose ``release()`` frees none of it"""
+        s = SceneBuffers.__new__(SceneBuffers)
+        s.__dict__.update(self.__dict__, _made=[])
+        return s
+
+    def release(self) -> None:
+        for b in self._made:
+            b.release()
+        self._made = []
+        self.tbuf = self.mbuf = self.lbuf = None
+
+
+class SceneHolder:
+    """What a caster or renderer that holds a ``SceneBuffers`` as ``self.scene`` shows of it as its own."""
+
+    _SHOWN = ("tbuf", "mbuf", "lbuf", "lights", "num_triangles", "num_materials")
+
+    def __getattr__(self, name):   # (reached only for what the holder has not set itself)
+        if name in SceneHolder._SHOWN:
+            return getattr(self.scene, name)
+        raise AttributeError("%s has no attribute %r" % (type(self).__name__, name))
+
+    def _lights_h(self):
+        """the light list's handle; None for an empty list (the buffer then holds one unused entry)"""
+        return self.scene.lbuf._h if len(self.scene.lights) else None
 
 
 def emitters(triangles: np.ndarray, materials: np.ndarray) -> np.ndarray:

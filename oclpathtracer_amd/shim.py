@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PT_SHIM_LIB lets an experiment point at an alternative build of the same ABI (A/B kernel variants)
 LIB_PATH = os.environ.get("PT_SHIM_LIB") or os.path.join(_HERE, "libptshim.so")
@@ -179,6 +181,9 @@ class Roulette(_c.Structure):
     _fields_ = [("first_bounce", _c.c_int32), ("max_survival", _c.c_float), ("reserved", _c.c_int32 * 2)]
 
 
+NO_ROULETTE = Roulette(65535, 1.0)   # what an entry point that takes a pt_roulette gets for none: a first bounce no path reaches
+
+
 class Ris(_c.Structure):
     """pt_ris (16 bytes): resampled light sampling -- candidates (M, 1 .. 32) drawn from the light table per light sample, one of which
     is kept in proportion to its unshadowed contribution; reserved must be 0."""
@@ -215,6 +220,11 @@ class PixelMoments(_c.Structure):
     number of samples rejected for a NaN or an infinity."""
 
     _fields_ = [("sum", _c.c_double * 3), ("sum2", _c.c_double * 3), ("n", _c.c_uint32), ("rejected", _c.c_uint32)]
+
+
+# the same record for numpy: what every reader of a moments buffer decodes it through
+MOMENTS_DTYPE = np.dtype([("sum", np.float64, 3), ("sum2", np.float64, 3), ("n", np.uint32), ("rejected", np.uint32)])
+assert MOMENTS_DTYPE.itemsize == _c.sizeof(PixelMoments) == 56
 
 
 class NoiseSummary(_c.Structure):

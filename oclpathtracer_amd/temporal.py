@@ -18,7 +18,8 @@ import numpy as np
 
 from . import adl, shim
 from .camera import Camera
-from .features import FEATURES, MOMENTS_DTYPE, FeatureRenderer
+from .features import FEATURES, FeatureRenderer
+from .image import check_size
 
 # the values the numpy prototype settled on (Cornell box, an 8-frame history under a shifted and a panned camera: at 48 x 48 the median
 # relative MSE of history plus two new frames is 0.015 against 0.065 for the two frames alone; at 96 x 96 one of 67 pixels hidden from
@@ -42,9 +43,7 @@ class Reprojector:
                  min_weight: float = 0.6, max_noise: float = 0.5):
         self.dev = dev
         self._lib = shim.load()
-        self.width, self.height = int(width), int(height)
-        if self.width < 1 or self.height < 1 or self.width * self.height > 0x7fffffff:
-            raise ValueError("invalid image size %dx%d" % (self.width, self.height))
+        self.width, self.height = check_size(width, height)
         if isinstance(max_history, bool) or int(max_history) != max_history or not 0 <= int(max_history) <= 0x7fffffff:
             raise ValueError("max_history must be an integer in 0 .. 2^31 - 1")
         p = shim.ReprojectParams()
@@ -72,7 +71,7 @@ class Reprojector:
             raise ValueError("reprojection needs the depth feature")
         if not features._valid:
             raise ValueError("a feature renderer has rendered nothing yet")
-        return (features.mom["normal"]._h if "normal" in features.mom else None), features.mom["depth"]._h
+        return adl._handle(features.mom.get("normal")), features.mom["depth"]._h
 
     def reproject(self, prev_colour: adl.Buffer, prev_features: FeatureRenderer, cur_features: FeatureRenderer,
                   prev_camera: Optional[Camera], cur_camera: Optional[Camera], out: adl.Buffer, info: Optional[adl.Buffer] = None,
@@ -89,9 +88,8 @@ class Reprojector:
             pn = cn = None
         pc, cc = _pinhole(prev_camera), _pinhole(cur_camera)
         ref = lambda s: ctypes.byref(s) if s is not None else None
-        shim.check(self._lib.pt_reproject(self.dev._h, prev_colour._h, pn, pd, cn, cd, self.scratch._h, out._h,
-                                          info._h if info is not None else None, ctypes.byref(self.params), ref(pc), ref(cc),
-                                          sync._h if sync is not None else None))
+        shim.check(self._lib.pt_reproject(self.dev._h, prev_colour._h, pn, pd, cn, cd, self.scratch._h, out._h, adl._handle(info),
+                                          ctypes.byref(self.params), ref(pc), ref(cc), adl._handle(sync)))
 
     def release(self) -> None:
         if self.scratch is not None:
@@ -126,11 +124,9 @@ class TemporalAccumulator:
         self._moved = False
         try:
             self.reprojector = Reprojector(r.dev, r.width, r.height, **kw)
-            make = lambda: FeatureRenderer(r.dev, r.tbuf, r.mbuf, r.width, r.height, features=FEATURES, camera=r.camera,
-                                           num_triangles=r.num_triangles, num_materials=r.num_materials, stripe_rows=r.stripe_rows)
-            self.features = make()
-            self._previous = make()
-            self.history_buf = adl.Buffer(r.dev, self.pixels * MOMENTS_DTYPE.itemsize, np.uint8)
+            self.features = FeatureRenderer.on(r, features=FEATURES)
+            self._previous = FeatureRenderer.on(r, features=FEATURES)
+            self.history_buf = adl.Buffer(r.dev, self.pixels * shim.MOMENTS_DTYPE.itemsize, np.uint8)
             self.info_buf = adl.Buffer(r.dev, self.pixels, adl.float4)
             if r.frames_done:
                 self.features.render(r.frames_done, 0)
@@ -154,7 +150,7 @@ class TemporalAccumulator:
             r.set_camera(camera)
             self.features.set_camera(camera)
             return
-        self.history_buf.write(r.mom, self.pixels * MOMENTS_DTYPE.itemsize)                      # 1: the history
+        self.history_buf.write(r.mom, self.pixels * shim.MOMENTS_DTYPE.itemsize)                      # 1: the history
         self.features, self._previous = self._previous, self.features                            # 2: the new view's features
         self.features._set_camera(camera)
         self.features.render(self.feature_frames, r.frames_done, restart=True)
@@ -163,7 +159,7 @@ class TemporalAccumulator:
         self._moved = True
 
     def _records(self) -> np.ndarray:
-        rec = np.zeros(self.pixels, MOMENTS_DTYPE)
+        rec = np.zeros(self.pixels, shim.MOMENTS_DTYPE)
         r = self.renderer
         if r._moments_valid:
             r.mom.read(rec.view(np.uint8), rec.nbytes)

@@ -107,7 +107,7 @@ def query(rc, rays, early_exit):
     for _ in range(reps):
         rc.occluded(rays, early_exit=early_exit)
         torch.cuda.synchronize()
-        ts.append(rc._sync.getExecutionTimeNanoseconds() * 1e-9)   # the call's own event pair
+        ts.append(rc._io._sync.getExecutionTimeNanoseconds() * 1e-9)   # the call's own event pair
     return median(ts)
 
 

@@ -54,7 +54,7 @@ def time_query(rc, rays, mode):
     ts = []
     for _ in range(reps):
         fn(rays)
-        ts.append(rc._sync.getExecutionTimeNanoseconds() * 1e-9)   # the query's own event pair
+        ts.append(rc._io._sync.getExecutionTimeNanoseconds() * 1e-9)   # the query's own event pair
     ts.sort()
     return ts[len(ts) // 2], ts[0]
 
